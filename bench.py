@@ -19,10 +19,16 @@ buffers whose slots the decoder's last kernel writes directly (zero copy: one HI
 Given explicitly at N = 1 the collective runs on a one-rank group and `collective.overhead_pct` reports its own per-step cost.
 Rank 0 writes ONE JSON line to stdout (everything else that writes to fd 1 -- RCCL's banner -- is sent to stderr).
 
-W warm-up steps, then `--repeats` (default 5) timed regions of EXACTLY K steps each, every region bracketed by a barrier
-+ torch.cuda.synchronize() on both sides, MAX over ranks per region; `value` uses the MEDIAN region (all are listed).
+W warm-up steps, then `--repeats` timed regions of EXACTLY K steps each (default: one region, so K is the number of timed steps;
+5 under --full), every region bracketed by a barrier + torch.cuda.synchronize() on both sides, MAX over ranks per region;
+`value` uses the MEDIAN region (all are listed), `ms_per_step` = its wall time / K.
 
-Extra objects on the line:
+A plain run does only what the headline needs: set-up, warm-up, the timed steps, `--dump-outputs DIR` if given, the line.
+`--dump-outputs DIR` writes what the timed path computed in its last step as DIR/<name>.npy (float32): `logits` (or `masks`
+under --output masks), or `<name>_sample` -- a fixed, seeded sample of at most 8 M elements -- when the whole output would pass
+64 MB; the input and the weights are seeded, so two builds can be compared output for output.
+
+--full adds everything else the benchmark measures or checks (rank 0), as extra objects on the line:
   roofline      the dominant decoder kernel against the roof that binds it (the f16-split level 4: HBM; `f32_mfma_frac` beside it for
                 comparison with rounds 1-2): algorithmic FLOPs or bytes per launch / its average duration measured with
                 HIP events on the launch stream over instrumented eager passes right after the timed regions (a graph
@@ -113,12 +119,36 @@ def cpu_baseline(model_cpu, size, budget_s=12.0):
             'decoder_ms': round(1e3 * dec / n, 2), 'encoder_ms': round(1e3 * enc / n, 2)}
 
 
+DUMP_MAX_BYTES = 64 << 20          # --dump-outputs: the whole output up to this size, else a seeded sample
+DUMP_SAMPLE = 8 << 20              # elements in that sample
+
+
+def dump_outputs(directory, y, name):
+    """DIR/<name>.npy: the output of the timed path's last step as float32, or DIR/<name>_sample.npy, the same fixed, seeded
+    sample of its flattened elements (distinct indices, ascending) when the whole would pass DUMP_MAX_BYTES."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    y = y.detach()
+    if 4 * y.numel() > DUMP_MAX_BYTES:
+        idx = torch.randint(0, y.numel(), (DUMP_SAMPLE,), generator=torch.Generator().manual_seed(0)).unique()
+        y, name = y.reshape(-1)[idx.to(y.device)], name + '_sample'
+    np.save(os.path.join(directory, name + '.npy'), y.float().cpu().numpy())
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=200)
     ap.add_argument('--warmup', type=int, default=20)
-    ap.add_argument('--repeats', type=int, default=5, help='timed regions of --steps steps each; value = their median')
+    ap.add_argument('--repeats', type=int, default=None,
+                    help='timed regions of --steps steps each; value = their median (default 1; 5 under --full)')
+    ap.add_argument('--full', action='store_true',
+                    help='besides the headline: PMC traffic passes, roofline, parity vs the stock model, the other arithmetic, two frames '
+                         'in flight, the reference protocol, the CPU baseline and the other BASELINE configurations (a plain run: '
+                         'set-up, warm-up, the timed steps, --dump-outputs, the line)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help="write the timed path's output of its last step as DIR/<name>.npy (float32; a fixed, seeded sample of an "
+                         'output over 64 MB)')
     ap.add_argument('--model', default='m', choices=sorted(MODELS),
                     help='m: HyperSeg-M 1024x512 bs1/GPU (default, the headline metric); s: HyperSeg-S 1536x768 bs1/GPU; '
                          'sc: CamVid-S 768x576; l: HyperSeg-L 512x512, global batch 32 sharded over the GPUs; lc: CamVid HyperSeg-L 1024x768 '
@@ -172,6 +202,10 @@ def main(argv=None):
     ap.add_argument('--traffic-dir', default=None,
                     help='directory with rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this command (same session)')
     args = ap.parse_args(argv)
+    if args.repeats is None:
+        args.repeats = 5 if args.full else 1
+    if not args.full:
+        args.no_extras = True                               # a plain run: no traffic passes, no side legs, no stock-model copies
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         # plain `python bench.py --gpus N` (the shape of the driver's N = 1 command; the reference's counterpart is one command for N
         # GPUs too: nn.DataParallel, test_fps.py:155-156): launch the N ranks ourselves, one process per GPU, under torch.distributed.run;
@@ -399,6 +433,8 @@ def main(argv=None):
     else:
         loop, comm, zero_copy = make_loop(policy, gather)
     times = run_timed(loop, args.steps, args.warmup, max(1, args.repeats))
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, loop.last_y, 'masks' if args.output == 'masks' else 'logits')
     med = statistics.median(times)
     fps = args.steps * global_batch / med
     rank_fps = torch.tensor([args.steps * batch / med], dtype=torch.float64, device=None if stub else dev)

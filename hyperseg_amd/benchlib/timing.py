@@ -19,11 +19,12 @@ class StepLoop:
         self.to_payload = to_payload or (lambda y: y)
         self.device = device
         self.last = None              # the most recent collected (step, tensor) pair, for checks outside the timing
+        self.last_y = None            # what forward() returned for the most recent step (bench.py --dump-outputs)
         self.cuda = device is not None and device.type == 'cuda'
 
     def step(self, i):
         y = self.forward(i) if self.forward_takes_step else self.forward()
-        self.last_step = i
+        self.last_step, self.last_y = i, y
         if self.comm is not None:
             done = self.comm.submit(i, self.to_payload(y))
             if done is not None:

@@ -107,7 +107,8 @@ def test_loads_a_checkpoint_the_reference_wrote(golden, tmp_path):
     assert all(k.startswith('module.') for k in state['state_dict'])
     save_checkpoint(str(tmp_path), 'model', state, is_best=True)
     assert sorted(os.listdir(tmp_path)) == [str(f) for f in g['ckpt.files']]
-    mine = torch.load(tmp_path / 'model_latest.pth', weights_only=True)
+    # with a GPU present DataParallel moves the module to cuda:0 and the file holds device tensors: compare values on the CPU
+    mine = torch.load(tmp_path / 'model_latest.pth', weights_only=True, map_location='cpu')
     assert list(mine.keys()) == list(ck.keys()) and mine['arch'] == ck['arch']
     assert list(mine['state_dict'].keys()) == list(ck['state_dict'].keys())
     assert all(torch.equal(mine['state_dict'][k], v) for k, v in ck['state_dict'].items())

@@ -264,6 +264,34 @@ def test_bench_plain_command_launches_its_own_ranks():
     assert bad.returncode != 0
 
 
+def test_bench_plain_run_times_the_steps_and_dumps_the_last_output(tmp_path):
+    """A plain `bench.py --gpus 1 --steps K --warmup W` times ONE region of exactly K steps (`ms_per_step` is its wall time / K);
+    --dump-outputs DIR writes the output of the last timed step as float32 .npy; --full times its 5 regions as before.
+    Stubbed model (CPU): the stub's output names its call count, so the file shows WHICH step it holds."""
+    import json
+    import subprocess
+    import numpy as np
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ, HS_BENCH_STUB='1')
+    for k in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE', 'MASTER_ADDR', 'MASTER_PORT'):
+        env.pop(k, None)
+    cmd = [sys.executable, os.path.join(root, 'bench.py'), '--gpus', '1', '--steps', '5', '--warmup', '2']
+    r = subprocess.run(cmd + ['--dump-outputs', str(tmp_path / 'out')], env=env, cwd=root, capture_output=True, timeout=240)
+    assert r.returncode == 0, r.stderr.decode()[-2000:]
+    lines = [l for l in r.stdout.decode().splitlines() if l.strip()]
+    assert len(lines) == 1, lines
+    d = json.loads(lines[0])
+    assert d['steps'] == 5 and d['warmup'] == 2 and d['repeats']['n'] == 1 and d['repeats']['ms_per_step'] == [d['ms_per_step']]
+    assert abs(d['value'] - 1 / (d['ms_per_step'] * 1e-3)) < 0.01 * d['value']
+    assert sorted(os.listdir(tmp_path / 'out')) == ['logits.npy']
+    y = np.load(tmp_path / 'out' / 'logits.npy')
+    assert y.dtype == np.float32 and y.shape == (1, 19, 512 // 16, 1024 // 16)
+    assert (y == float((1 + 2 + 5) % 7)).all()                 # call 1: the set-up forward, then 2 warm-up and 5 timed steps
+    r = subprocess.run(cmd + ['--full'], env=env, cwd=root, capture_output=True, timeout=240)
+    assert r.returncode == 0, r.stderr.decode()[-2000:]
+    assert json.loads(r.stdout.decode().strip().splitlines()[-1])['repeats']['n'] == 5
+
+
 def test_link_schedule_and_fitting_policy():
     """The per-link arithmetic behind bench.py's N > 1 default: at 8 x HyperSeg-M the RCCL ring all-gather of fp32 logits
     asks ~360 GB/s of one xGMI link and direction (76.5 available), the all-pairs schedule 51 -- the default must be the latter -- while

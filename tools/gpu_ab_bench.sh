@@ -9,7 +9,7 @@ for round in 1 2; do
   for v in product "$@"; do
     lib=$R/hyperseg_amd/lib/libhyperseg_hip_$v.so; [ $v = product ] && lib=$R/hyperseg_amd/lib/libhyperseg_hip.so
     [ -f $lib ] || { echo "missing $lib" | tee -a $out; continue; }
-    HS_HIP_LIB=$lib timeout 120 python bench.py $BENCH_ARGS --steps ${BENCH_STEPS:-300} --warmup 30 --no-cpu-baseline --no-extras 2>/dev/null | \
+    HS_HIP_LIB=$lib timeout 120 python bench.py $BENCH_ARGS --steps ${BENCH_STEPS:-300} --warmup 30 --repeats 5 --no-cpu-baseline --no-extras 2>/dev/null | \
       python -c "import sys,json; d=json.loads(sys.stdin.readline()); print('$round $v', d['value'], d['ms_per_step'])" | tee -a $out
   done
 done

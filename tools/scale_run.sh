@@ -17,10 +17,10 @@ base=""
 for n in 1 2 4 8; do
   out=gpurun_out/scale_${model}_${coll}_${gather}_N$n.json
   if [ "$n" = 1 ]; then
-    timeout 900 python bench.py --gpus 1 --steps "$steps" --warmup "$warmup" --model "$model" --no-cpu-baseline --traffic off > "$out" 2> "${out%.json}.err"
+    timeout 900 python bench.py --gpus 1 --steps "$steps" --warmup "$warmup" --repeats 5 --model "$model" --no-cpu-baseline --traffic off > "$out" 2> "${out%.json}.err"
   else
     timeout 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node "$n" --master-addr 127.0.0.1 --master-port $((29500 + n)) \
-      bench.py --gpus "$n" --steps "$steps" --warmup "$warmup" --model "$model" --collective "$coll" --gather "$gather" > "$out" 2> "${out%.json}.err"
+      bench.py --gpus "$n" --steps "$steps" --warmup "$warmup" --repeats 5 --model "$model" --collective "$coll" --gather "$gather" > "$out" 2> "${out%.json}.err"
   fi
   rc=$?
   python - "$out" "$n" "$rc" "$base" <<'PY'
