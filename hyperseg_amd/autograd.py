@@ -20,7 +20,33 @@ def needs_grad(*tensors):
     return torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in tensors)
 
 
-DTYPE_CODES = {torch.float32: 0, torch.bfloat16: 1}       # hs_dtype of include/hyperseg_hip.h
+DTYPE_CODES = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}       # hs_dtype of include/hyperseg_hip.h
+HALF_DTYPES = (torch.bfloat16, torch.float16)
+
+
+def storage_dtype(*tensors):
+    """Storage type of the training route's activations: the autocast dtype while ``torch.autocast('cuda')`` is on (bf16 or fp16), else
+    the half type of the tensors passed in, else fp32.  Two half types in one step (e.g. bf16 tensors under fp16 autocast) raise
+    NotImplementedError: nothing converts between them silently."""
+    halves = {t.dtype for t in tensors if isinstance(t, torch.Tensor) and t.dtype in HALF_DTYPES}
+    if torch.is_autocast_enabled('cuda'):
+        ad = torch.get_autocast_dtype('cuda')
+        if ad not in HALF_DTYPES:
+            raise NotImplementedError(f"training route under torch.autocast('cuda', dtype={ad}): only torch.bfloat16 and torch.float16 "
+                                      'autocast are supported (fp32 without autocast)')
+        halves.add(ad)
+    if len(halves) > 1:
+        a, b = sorted(str(d) for d in halves)
+        raise NotImplementedError(f'training route: {a} and {b} in one step (one half storage type per step; convert the tensors '
+                                  'or match the autocast dtype)')
+    return halves.pop() if halves else torch.float32
+
+
+def refuse_mixed_halves(*tensors):
+    """storage_dtype's check alone, for Functions that keep the type they are given (BatchNorm, the tile re-layouts, the losses): a half
+    tensor whose type differs from the autocast dtype raises."""
+    if any(isinstance(t, torch.Tensor) and t.dtype in HALF_DTYPES for t in tensors):
+        storage_dtype(*tensors)
 
 
 def _plain_conv(kind, dtype, a, b, ld, shape, meta, out):
@@ -91,16 +117,16 @@ def _dbank_for(slot, bank, written_cols, device):
 class PatchConv(torch.autograd.Function):
     """y = patch_conv(x, bank): Op A / Op B with plain tensors.  Saves x and the bank; backward launches the input- and
     the per-patch weight-gradient kernels.  fp32 tensors take the fp32 kernels; under ``torch.autocast('cuda',
-    dtype=torch.bfloat16)`` (or with a bf16 ``x``) the ACTIVATIONS and their gradients are stored as bf16 and every sum is
-    accumulated in fp32 (hs_patch_conv_plain_*: BASELINE config 5).  The bank and its gradient stay fp32 in both cases: they
+    dtype=torch.bfloat16)`` or ``torch.float16`` (or with a bf16 / fp16 ``x``) the ACTIVATIONS and their gradients are stored in that
+    half type and every sum is accumulated in fp32 (hs_patch_conv_plain_*: BASELINE config 5).  The bank and its gradient stay fp32 in both cases: they
     sit between this layer and signal2weights, which is fp32, so a bf16 bank meant one cast launch per layer and direction
     (30 of the 147 launches of the config-5 step under autocast, visit r4m) for a few per cent of a launch's bytes."""
 
     @staticmethod
     def forward(ctx, x, bank, grid, c_out, k, padding, padding_mode, groups):
         # (no custom_fwd(cast_inputs=...): it would narrow the bank too, and widen its gradient again in backward)
-        if torch.is_autocast_enabled('cuda') and x.is_cuda and x.is_floating_point():
-            x = x.to(torch.bfloat16)
+        if x.is_cuda and x.is_floating_point():
+            x = x.to(storage_dtype(x))
         if x.dtype not in DTYPE_CODES:
             raise NotImplementedError(f'PatchConv: dtype {x.dtype} is not supported (supported: '
                                       f'{", ".join(str(d) for d in DTYPE_CODES)})')
@@ -170,6 +196,7 @@ class HaloTiles(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, grid, patch_major=False):
+        refuse_mixed_halves(x)
         x = x.contiguous()
         b, c, h, w = x.shape
         fh, fw = grid
@@ -227,6 +254,7 @@ class DwTilesValid(torch.autograd.Function):
     @staticmethod
     def forward(ctx, t, bank, size, grid, patch_major=False):
         ctx.grad_slot = _grad_slot(bank)
+        refuse_mixed_halves(t)
         t = t.contiguous()
         h, w = size
         c = t.shape[1]
@@ -274,10 +302,11 @@ def tiles_supported(x):
 
 class BNActTrain(torch.autograd.Function):
     """BatchNorm2d (training mode, batch statistics, running estimates updated in place) + none / ReLU / ReLU6 in two launches per
-    direction (hs_bn_act_train_fwd / _bwd).  fp32 parameters; x in fp32 or bf16 storage."""
+    direction (hs_bn_act_train_fwd / _bwd).  fp32 parameters; x in fp32, bf16 or fp16 storage."""
 
     @staticmethod
     def forward(ctx, x, weight, bias, running_mean, running_var, momentum, eps, act, counter=None):
+        refuse_mixed_halves(x)
         x = x.contiguous()
         b, c = x.shape[:2]
         px = x.numel() // (b * c)
@@ -461,8 +490,8 @@ class PatchConvBN(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, running_mean, running_var, momentum, eps, act, counter, bank, grid, c_out):
         ctx.grad_slot = _grad_slot(bank)
-        if torch.is_autocast_enabled('cuda') and x.is_floating_point():
-            x = x.to(torch.bfloat16)
+        if x.is_floating_point():
+            x = x.to(storage_dtype(x))
         x = x.contiguous()
         b, c, h, w = x.shape
         fh, fw = grid
@@ -525,7 +554,7 @@ def patch_conv_bn(bn, act_layer, x, bank, grid, c_out):
     b, c, h, w = x.shape
     fh, fw = grid
     covered = act >= 0 and c_out <= 32 and c <= 64 and h % fh == 0 and w % fw == 0 and (h // fh) * (w // fw) >= 64 \
-        and (not torch.is_autocast_enabled('cuda') or torch.get_autocast_dtype('cuda') == torch.bfloat16)
+        and (not torch.is_autocast_enabled('cuda') or torch.get_autocast_dtype('cuda') in HALF_DTYPES)
     if not covered:
         return patch_conv_apply(bn_act(bn, act_layer, x), bank, grid, c_out, 1, 0, 'zeros', 1)
     nbt = bn.num_batches_tracked
@@ -632,6 +661,7 @@ class PixelCrossEntropy(torch.autograd.Function):
             raise ValueError(f'PixelCrossEntropy: expected int64 class indices, got {target.dtype}')
         if target.device != logits.device:
             raise ValueError(f'PixelCrossEntropy: target on {target.device}, logits on {logits.device}')
+        refuse_mixed_halves(logits)
         logits, target = logits.contiguous(), target.contiguous()
         n, c = logits.shape[:2]
         px = logits.numel() // (n * c)
@@ -704,6 +734,7 @@ class BootstrappedCrossEntropy(torch.autograd.Function):
                              f'{tuple(logits.shape)}, got {tuple(target.shape)}')
         if target.dtype != torch.int64 or target.device != logits.device:
             raise ValueError(f'BootstrappedCrossEntropy: expected int64 class indices on {logits.device}, got {target.dtype} on {target.device}')
+        refuse_mixed_halves(logits)
         logits, target = logits.contiguous(), target.contiguous()
         n, c = logits.shape[:2]
         px = logits.numel() // (n * c)
@@ -863,17 +894,16 @@ class BootstrapMeanOfBatch(torch.autograd.Function):
 
 def patch_conv_apply(*args):
     """``PatchConv.apply`` behind the autocast-dtype check."""
-    if torch.is_autocast_enabled('cuda') and torch.get_autocast_dtype('cuda') != torch.bfloat16:
-        # there is no fp16 storage type
+    if torch.is_autocast_enabled('cuda') and torch.get_autocast_dtype('cuda') not in HALF_DTYPES:
         raise NotImplementedError(f"patch conv under torch.autocast('cuda', dtype={torch.get_autocast_dtype('cuda')}): only "
-                                  'torch.bfloat16 autocast is supported (fp32 without autocast)')
+                                  'torch.bfloat16 and torch.float16 autocast are supported (fp32 without autocast)')
     return PatchConv.apply(*args)
 
 
 class UpsampleBilinear(torch.autograd.Function):
-    """F.interpolate(x, size, mode='bilinear', align_corners=False) for fp32 / bf16 CUDA tensors, forward and adjoint on the HIP
-    kernels (hs_upsample_bilinear_fwd / _bf16_fwd / _typed_bwd): the decoder's final logits in training.  bf16 storage in, bf16
-    storage out (f32 arithmetic, one rounding), as the stock op under autocast -- without its widen / narrow cast launches."""
+    """F.interpolate(x, size, mode='bilinear', align_corners=False) for fp32 / bf16 / fp16 CUDA tensors, forward and adjoint on the HIP
+    kernels (hs_upsample_bilinear_fwd / _bf16_fwd / _f16_fwd / _typed_bwd): the decoder's final logits in training.  Half storage in,
+    the same half storage out (f32 arithmetic, one rounding), as the stock op under autocast -- without its widen / narrow cast launches."""
 
     @staticmethod
     def forward(ctx, x, size):
@@ -882,11 +912,11 @@ class UpsampleBilinear(torch.autograd.Function):
         if x.dtype == torch.float32:
             return HF.upsample_bilinear(x, size)
         b, c, hi, wi = x.shape
+        name = 'hs_upsample_bilinear_bf16_fwd' if x.dtype == torch.bfloat16 else 'hs_upsample_bilinear_f16_fwd'
         with _hip.device_scope(x.device):
-            y = torch.empty(b, c, size[0], size[1], device=x.device, dtype=torch.bfloat16)
-            st = _hip.lib.hs_upsample_bilinear_bf16_fwd(_hip.dev_ptr(x, 'x', torch.bfloat16), b, c, hi, wi, size[0], size[1], y.data_ptr(),
-                                                        _hip.stream_ptr())
-            _hip.check(st, 'hs_upsample_bilinear_bf16_fwd')
+            y = torch.empty(b, c, size[0], size[1], device=x.device, dtype=x.dtype)
+            st = getattr(_hip.lib, name)(_hip.dev_ptr(x, 'x', x.dtype), b, c, hi, wi, size[0], size[1], y.data_ptr(), _hip.stream_ptr())
+            _hip.check(st, name)
         return y
 
     @staticmethod
@@ -902,9 +932,11 @@ class UpsampleBilinear(torch.autograd.Function):
 
 def upsample_bilinear(x, size):
     """F.interpolate(x, size, mode='bilinear', align_corners=False), differentiable: own kernels for up-sampling CUDA tensors in
-    fp32 / bf16 storage (the decoder's final logits upsample in training), the stock op otherwise."""
+    fp32 / bf16 / fp16 storage (the decoder's final logits upsample in training), the stock op otherwise."""
     import torch.nn.functional as F
-    if (x.is_cuda and x.dtype in (torch.float32, torch.bfloat16) and size[0] >= x.shape[2] and size[1] >= x.shape[3]
+    if x.is_cuda and x.dtype in HALF_DTYPES:
+        storage_dtype(x)                                       # (a half type other than autocast's: refused, not converted)
+    if (x.is_cuda and x.dtype in DTYPE_CODES and size[0] >= x.shape[2] and size[1] >= x.shape[3]
             and x.shape[0] * x.shape[1] <= 65535):
         return UpsampleBilinear.apply(x, tuple(size))
     return F.interpolate(x, size, mode='bilinear', align_corners=False)
@@ -979,18 +1011,17 @@ class StageMaterialize(torch.autograd.Function):
     """cat(coords, skip, bilinear(prev)) as ONE launch under autograd (hs_stage_input_typed_fwd, the materialising twin of the
     kernels' prologue): the stock formulation is two linspaces, a stack, the interpolation and a concatenation per level and
     step -- five to six launches.  Backward: the skip's gradient is a channel range of dy (a view), the previous level's is the
-    bilinear adjoint (hs_upsample_bilinear_typed_bwd) of its range; coordinates are constants.  Under bf16 autocast (or with a
-    bf16 previous level) the previous level is read as stored and the result is written as bf16 -- what the first convolution
-    reads -- and the adjoint runs bf16 -> bf16: no cast launch on either side (18 of them per config-5 step before)."""
+    bilinear adjoint (hs_upsample_bilinear_typed_bwd) of its range; coordinates are constants.  Under bf16 / fp16 autocast (or with a
+    half previous level) the previous level is read as stored and the result is written in that half type -- what the first
+    convolution reads -- and the adjoint runs half -> half: no cast launch on either side (18 of them per config-5 step before)."""
 
     @staticmethod
     def forward(ctx, skip, prev, coords):
-        low = (torch.is_autocast_enabled('cuda') and torch.get_autocast_dtype('cuda') == torch.bfloat16) or \
-            (prev is not None and prev.dtype == torch.bfloat16) or skip.dtype == torch.bfloat16
+        out = storage_dtype(skip, prev)
         stage = HF.StageInput(skip.contiguous().float(), prev.contiguous() if prev is not None else None, coords=coords)
         ctx.meta = (tuple(skip.shape), tuple(prev.shape) if prev is not None else None, bool(coords), skip.dtype,
                     prev.dtype if prev is not None else None)
-        return stage.materialize(torch.bfloat16 if low else torch.float32)
+        return stage.materialize(out)
 
     @staticmethod
     def backward(ctx, dy):
@@ -1022,9 +1053,9 @@ def materialize_stage(stage):
     import torch.nn.functional as F
     skip, prev = stage.skip, stage.prev
     b, _, h, w = skip.shape
-    ok = skip.is_cuda and skip.dtype in (torch.float32, torch.bfloat16) and b * max(skip.shape[1], 1) <= 65535
+    ok = skip.is_cuda and skip.dtype in DTYPE_CODES and b * max(skip.shape[1], 1) <= 65535
     if ok and prev is not None:
-        ok = prev.dtype in (torch.float32, torch.bfloat16) and h >= prev.shape[2] and w >= prev.shape[3] and \
+        ok = prev.dtype in DTYPE_CODES and h >= prev.shape[2] and w >= prev.shape[3] and \
             prev.shape[0] * prev.shape[1] <= 65535
     if ok and USE_HIP_STAGE:
         return StageMaterialize.apply(skip, prev, stage.coords)

@@ -59,7 +59,7 @@ __device__ __forceinline__ Tap bilinear_tap(int dst, float scale, int in_size) {
 // instructions; the compiler's 32-bit division by a run-time value is ~25 (the image-level training kernels did up to 18 per thread).
 __device__ __forceinline__ int div_by_inv(int n, float inv_d) { return (int)(((float)n + 0.5f) * inv_d); }
 
-// Storage types of the training-path kernels: fp32, or bf16 storage with fp32 arithmetic (rounded to nearest-even once on store).
+// Storage types of the training-path kernels: fp32, or bf16 / fp16 storage with fp32 arithmetic (rounded to nearest-even once on store).
 struct bf16_t { uint16_t v; };
 
 template <typename T> struct Store;
@@ -87,6 +87,21 @@ template <> struct Store<bf16_t> {
     }
 };
 
+// IEEE binary16 storage (fp16 autocast): widened exactly on load (v_cvt_f32_f16), rounded to nearest-even once on store by the hardware
+// conversion (v_cvt_f16_f32: overflow gives +-inf as torch's .half() does, NaN stays NaN); arithmetic in fp32 as for bf16_t.
+struct f16_t { uint16_t v; };
+typedef _Float16 hs_h16x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ float f16_widen(uint32_t r) { return (float)__builtin_bit_cast(_Float16, (uint16_t)r); }
+__device__ __forceinline__ uint16_t f16_round(float x) { return __builtin_bit_cast(uint16_t, (_Float16)x); }
+template <> struct Store<f16_t> {
+    static __device__ __forceinline__ float ld(const f16_t* p, size_t i) { return f16_widen(p[i].v); }
+    typedef uint32_t raw_t;
+    static __device__ __forceinline__ raw_t raw(const f16_t* p, size_t i) { return p[i].v; }
+    static __device__ __forceinline__ float cvt(raw_t r) { return f16_widen(r); }
+    static __device__ __forceinline__ void pin(raw_t& r) { asm volatile("" : "+v"(r)); }
+    static __device__ __forceinline__ void st(f16_t* p, size_t i, float x) { p[i].v = f16_round(x); }
+};
+
 // two adjacent elements as one aligned load / store (the address must be a multiple of two elements)
 using bw_f32x2 = __attribute__((ext_vector_type(2))) float;
 template <typename T> struct Pair;
@@ -108,6 +123,15 @@ template <> struct Pair<bf16_t> {
         return u >> 16;
     }
     static __device__ __forceinline__ void st(bf16_t* p, size_t i, float a, float b) { *reinterpret_cast<uint32_t*>(p + i) = bits(a) | (bits(b) << 16); }
+};
+template <> struct Pair<f16_t> {
+    static __device__ __forceinline__ void unpack(uint32_t v, float& a, float& b) {
+        const hs_h16x2 h = __builtin_bit_cast(hs_h16x2, v); a = (float)h[0]; b = (float)h[1];
+    }
+    static __device__ __forceinline__ void ld(const f16_t* p, size_t i, float& a, float& b) { unpack(*reinterpret_cast<const uint32_t*>(p + i), a, b); }
+    // the two values rounded by the hardware conversion and stored as ONE 4-byte word (as Pair<bf16_t>::st)
+    static __device__ __forceinline__ uint32_t pack(float a, float b) { return __builtin_bit_cast(uint32_t, hs_h16x2{(_Float16)a, (_Float16)b}); }
+    static __device__ __forceinline__ void st(f16_t* p, size_t i, float a, float b) { *reinterpret_cast<uint32_t*>(p + i) = pack(a, b); }
 };
 
 // Slices a training-mode BatchNorm channel is cut into: partial[(c * BN_CHUNKS + chunk) * 2 + {0, 1}] = {sum, sum of squares} of
@@ -131,7 +155,7 @@ __device__ __forceinline__ StagePos stage_pos(const StageIn& s, int y, int x) {
 }
 
 // Value of stage-input channel c of batch b at a sampled position.  TP: storage type of the previous level (fp32 everywhere but the
-// training path under bf16 autocast, hs_stage_input_typed_fwd).
+// training path under bf16 / fp16 autocast, hs_stage_input_typed_fwd).
 template <typename TP = float>
 __device__ __forceinline__ float stage_value(const StageIn& s, int b, int c, const StagePos& p) {
     if (p.y < 0 || p.x < 0) return 0.0f;

@@ -117,7 +117,7 @@ struct Conv1Args {
 // instead of run-time integer divisions, which were a third of this kernel's ~970 vector instructions per wave
 // (profiles/round3_pmc_k1_and_s2w.txt).  PWL = -1: any patch size.
 // TS (round 6): storage type of the input (given as the stage's `skip`) and of the output: float everywhere but the bf16 training step's k = 1
-// levels (launch_conv1x1_bf16: no coordinates, no previous level, no epilogue), whose generic kernel was 6 us per launch slower than this one.
+// levels (launch_conv1x1_h16: bf16 or fp16, no coordinates, no previous level, no epilogue), whose generic kernel was 6 us per launch slower than this one.
 template <int PWL, typename TS = float>
 __device__ __forceinline__ void conv1x1_body(const Conv1Args& a, const int patch, float* __restrict__ lds) {
     const int ph_ = PWL >= 0 ? (1 << PWL) : a.ph, pw_ = PWL >= 0 ? (1 << PWL) : a.pw;
@@ -502,7 +502,8 @@ void upsample_bilinear_kernel(const float* __restrict__ x, int planes, int Hi, i
 // The exact-2x case in bf16 storage (round 6: the training step's last launch under autocast -- the general kernel below, four 2-byte loads and a
 // 2-byte store per output, took 21.9 us where the fp32 step's upsample2x_kernel takes 9.9): upsample2x_kernel's block of 2 x 4 outputs per
 // thread from a 3 x 4 input neighbourhood, f32 arithmetic in the same operation order, each output row leaving as ONE 8-byte store.
-__device__ __forceinline__ void up2x_block_bf16(const bf16_t* __restrict__ base, int Hi, int Wi, int yi, int q, float (&o0)[4], float (&o1)[4]) {
+template <typename T>
+__device__ __forceinline__ void up2x_block_h16(const T* __restrict__ base, int Hi, int Wi, int yi, int q, float (&o0)[4], float (&o1)[4]) {
     const int xi = 2 * q;
     const int xm = xi > 0 ? xi - 1 : 0, xp = xi + 2 < Wi ? xi + 2 : Wi - 1;
     const int ym = yi > 0 ? yi - 1 : 0, yp = yi + 1 < Hi ? yi + 1 : Hi - 1;
@@ -510,9 +511,9 @@ __device__ __forceinline__ void up2x_block_bf16(const bf16_t* __restrict__ base,
     const int ys[3] = {ym, yi, yp};
 #pragma unroll
     for (int rr = 0; rr < 3; ++rr) {
-        const bf16_t* row = base + (size_t)ys[rr] * Wi;
-        in[rr][0] = Store<bf16_t>::ld(row, xm); in[rr][1] = Store<bf16_t>::ld(row, xi);
-        in[rr][2] = Store<bf16_t>::ld(row, xi + 1); in[rr][3] = Store<bf16_t>::ld(row, xp);
+        const T* row = base + (size_t)ys[rr] * Wi;
+        in[rr][0] = Store<T>::ld(row, xm); in[rr][1] = Store<T>::ld(row, xi);
+        in[rr][2] = Store<T>::ld(row, xi + 1); in[rr][3] = Store<T>::ld(row, xp);
     }
     float hz[3][4];
 #pragma unroll
@@ -532,15 +533,21 @@ __device__ __forceinline__ void up2x_block_bf16(const bf16_t* __restrict__ base,
         o1[c] = 0.75f * hz[1][c] + 0.25f * hz[2][c];
     }
 }
-__device__ __forceinline__ void store4_bf16(bf16_t* __restrict__ dst, const float (&o)[4]) {      // dst 8-byte aligned
+__device__ __forceinline__ void store4_h16(bf16_t* __restrict__ dst, const float (&o)[4]) {      // dst 8-byte aligned
     bf16_t t[4];
 #pragma unroll
     for (int i = 0; i < 4; ++i) Store<bf16_t>::st(t, i, o[i]);
     typedef unsigned v2u __attribute__((ext_vector_type(2)));
     *reinterpret_cast<v2u*>(dst) = v2u{(unsigned)t[0].v | ((unsigned)t[1].v << 16), (unsigned)t[2].v | ((unsigned)t[3].v << 16)};
 }
+__device__ __forceinline__ void store4_h16(f16_t* __restrict__ dst, const float (&o)[4]) {
+    typedef unsigned v2u __attribute__((ext_vector_type(2)));
+    *reinterpret_cast<v2u*>(dst) = v2u{Pair<f16_t>::pack(o[0], o[1]), Pair<f16_t>::pack(o[2], o[3])};
+}
+// T: bf16_t or f16_t
+template <typename T>
 __global__ __launch_bounds__(256)
-void upsample2x_bf16_kernel(const bf16_t* __restrict__ x, int planes, int Hi, int Wi, bf16_t* __restrict__ y) {
+void upsample2x_h16_kernel(const T* __restrict__ x, int planes, int Hi, int Wi, T* __restrict__ y) {
     const int wq = Wi >> 1;                 // pairs of input columns
     const size_t n = (size_t)planes * Hi * wq;
     const int Wo = 2 * Wi;
@@ -548,30 +555,31 @@ void upsample2x_bf16_kernel(const bf16_t* __restrict__ x, int planes, int Hi, in
         const int q = e % wq; size_t r = e / wq;
         const int yi = r % Hi; const size_t pl = r / Hi;
         float o0[4], o1[4];
-        up2x_block_bf16(x + pl * Hi * Wi, Hi, Wi, yi, q, o0, o1);
-        bf16_t* dst = y + (pl * 2 * Hi + 2 * yi) * Wo + 4 * q;
-        store4_bf16(dst, o0);
-        store4_bf16(dst + Wo, o1);
+        up2x_block_h16(x + pl * Hi * Wi, Hi, Wi, yi, q, o0, o1);
+        T* dst = y + (pl * 2 * Hi + 2 * yi) * Wo + 4 * q;
+        store4_h16(dst, o0);
+        store4_h16(dst + Wo, o1);
     }
 }
 
+template <typename T>
 __global__ __launch_bounds__(256)
-void upsample_bilinear_bf16_kernel(const bf16_t* __restrict__ x, int planes, int Hi, int Wi, int Ho, int Wo,
-                                   float scale_y, float scale_x, bf16_t* __restrict__ y) {
+void upsample_bilinear_h16_kernel(const T* __restrict__ x, int planes, int Hi, int Wi, int Ho, int Wo,
+                                  float scale_y, float scale_x, T* __restrict__ y) {
     const int wq = (Wo + 3) / 4;
     const size_t n = (size_t)planes * Ho * wq;
     for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (size_t)gridDim.x * blockDim.x) {
         const int q = e % wq; size_t r = e / wq;
         const int yo = r % Ho; const size_t pl = r / Ho;
         const Row4 t = row4_taps(yo, q, Hi, Wi, Wo, scale_y, scale_x);
-        const bf16_t* r0 = x + pl * Hi * Wi + (size_t)t.ty.i0 * Wi;
-        const bf16_t* r1 = x + pl * Hi * Wi + (size_t)t.ty.i1 * Wi;
-        bf16_t* dst = y + (pl * Ho + yo) * Wo + 4 * q;
+        const T* r0 = x + pl * Hi * Wi + (size_t)t.ty.i0 * Wi;
+        const T* r1 = x + pl * Hi * Wi + (size_t)t.ty.i1 * Wi;
+        T* dst = y + (pl * Ho + yo) * Wo + 4 * q;
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-            const float top = t.tx[i].l0 * Store<bf16_t>::ld(r0, t.tx[i].i0) + t.tx[i].l1 * Store<bf16_t>::ld(r0, t.tx[i].i1);
-            const float bot = t.tx[i].l0 * Store<bf16_t>::ld(r1, t.tx[i].i0) + t.tx[i].l1 * Store<bf16_t>::ld(r1, t.tx[i].i1);
-            if (4 * q + i < Wo) Store<bf16_t>::st(dst, i, t.ty.l0 * top + t.ty.l1 * bot);
+            const float top = t.tx[i].l0 * Store<T>::ld(r0, t.tx[i].i0) + t.tx[i].l1 * Store<T>::ld(r0, t.tx[i].i1);
+            const float bot = t.tx[i].l0 * Store<T>::ld(r1, t.tx[i].i0) + t.tx[i].l1 * Store<T>::ld(r1, t.tx[i].i1);
+            if (4 * q + i < Wo) Store<T>::st(dst, i, t.ty.l0 * top + t.ty.l1 * bot);
         }
     }
 }
@@ -659,11 +667,11 @@ static int launch_conv1x1(const StageIn& si, int batch, int fh, int fw, int ph, 
 #undef HS_K1_LAUNCH
 }
 
-// The same form for the bf16 training step's k = 1 levels (hs_patch_conv_plain_fwd, hs_patch_conv_train.hip): x (B, cin, H, W) and y (B, c_out, H, W)
-// in bf16, fp32 bank, groups = 1, no epilogue.  1 = the form does not apply (the caller keeps its generic kernel).
+// The same form for the bf16 / fp16 training step's k = 1 levels (hs_patch_conv_plain_fwd, hs_patch_conv_train.hip): x (B, cin, H, W) and y (B, c_out, H, W)
+// in the half type `dtype`, fp32 bank, groups = 1, no epilogue.  1 = the form does not apply (the caller keeps its generic kernel).
 namespace hs {
-int launch_conv1x1_bf16(const void* x, int batch, int cin, int H, int W, int fh, int fw, const float* bank, long ld, int c_out, void* y,
-                        hipStream_t stream) {
+int launch_conv1x1_h16(int dtype, const void* x, int batch, int cin, int H, int W, int fh, int fw, const float* bank, long ld, int c_out, void* y,
+                       hipStream_t stream) {
     const int ph = H / fh, pw = W / fw;
     const size_t hp4 = ((size_t)c_out * cin + 3) & ~(size_t)3;
     const size_t lds1 = (hp4 + (size_t)cin * ph * pw) * sizeof(float);
@@ -680,11 +688,17 @@ int launch_conv1x1_bf16(const void* x, int batch, int cin, int H, int W, int fh,
     while (split < 64 && outs * split * 2 <= CONV_THREADS && split * 2 <= cin) split *= 2;
     f.split = split;
     const dim3 grid((unsigned)((long)batch * fh * fw));
-    if (ph == pw && ph == 1) hipLaunchKernelGGL((patch_conv1x1_kernel<0, bf16_t>), grid, dim3(CONV_THREADS), lds1, stream, f);
-    else if (ph == pw && ph == 2) hipLaunchKernelGGL((patch_conv1x1_kernel<1, bf16_t>), grid, dim3(CONV_THREADS), lds1, stream, f);
-    else if (ph == pw && ph == 4) hipLaunchKernelGGL((patch_conv1x1_kernel<2, bf16_t>), grid, dim3(CONV_THREADS), lds1, stream, f);
-    else if (ph == pw && ph == 8) hipLaunchKernelGGL((patch_conv1x1_kernel<3, bf16_t>), grid, dim3(CONV_THREADS), lds1, stream, f);
-    else hipLaunchKernelGGL((patch_conv1x1_kernel<-1, bf16_t>), grid, dim3(CONV_THREADS), lds1, stream, f);
+    auto go = [&](auto h) {
+        using T = decltype(h);
+        if (ph == pw && ph == 1) hipLaunchKernelGGL((patch_conv1x1_kernel<0, T>), grid, dim3(CONV_THREADS), lds1, stream, f);
+        else if (ph == pw && ph == 2) hipLaunchKernelGGL((patch_conv1x1_kernel<1, T>), grid, dim3(CONV_THREADS), lds1, stream, f);
+        else if (ph == pw && ph == 4) hipLaunchKernelGGL((patch_conv1x1_kernel<2, T>), grid, dim3(CONV_THREADS), lds1, stream, f);
+        else if (ph == pw && ph == 8) hipLaunchKernelGGL((patch_conv1x1_kernel<3, T>), grid, dim3(CONV_THREADS), lds1, stream, f);
+        else hipLaunchKernelGGL((patch_conv1x1_kernel<-1, T>), grid, dim3(CONV_THREADS), lds1, stream, f);
+    };
+    if (dtype == HS_DTYPE_BF16) go(bf16_t{});
+    else if (dtype == HS_DTYPE_F16) go(f16_t{});
+    else return 1;
     return launch_status();
 }
 }  // namespace hs
@@ -790,22 +804,28 @@ extern "C" int hs_stage_input_typed_fwd(const hs_stage_input* in, int32_t prev_d
     int st = make_stage(in, &s);
     if (st != HS_OK) return st;
     if (!y) return HS_ERR_BAD_ARG;
-    if ((prev_dtype != HS_DTYPE_F32 && prev_dtype != HS_DTYPE_BF16) || (out_dtype != HS_DTYPE_F32 && out_dtype != HS_DTYPE_BF16)) return HS_ERR_BAD_ARG;
+    auto known = [](int d) { return d == HS_DTYPE_F32 || d == HS_DTYPE_BF16 || d == HS_DTYPE_F16; };
+    if (!known(prev_dtype) || !known(out_dtype)) return HS_ERR_BAD_ARG;
+    if (prev_dtype != HS_DTYPE_F32 && out_dtype != HS_DTYPE_F32 && prev_dtype != out_dtype) return HS_ERR_BAD_ARG;     // one half type per step
     const size_t n = (size_t)s.B * s.cin() * s.H * s.W;
     const dim3 blocks((unsigned)((n + 255) / 256 > 8192 ? 8192 : (n + 255) / 256));
     hipStream_t q = (hipStream_t)stream;
-    if ((long)s.B * s.cin() <= 65535) {
-        const dim3 g2((s.W + 63) / 64, (s.H + 15) / 16, s.B * s.cin());            // four rows per thread
-        if (prev_dtype == HS_DTYPE_F32 && out_dtype == HS_DTYPE_F32) hipLaunchKernelGGL((stage_input_plane_kernel<float, float>), g2, dim3(256), 0, q, s, (float*)y);
-        else if (prev_dtype == HS_DTYPE_F32) hipLaunchKernelGGL((stage_input_plane_kernel<float, bf16_t>), g2, dim3(256), 0, q, s, (bf16_t*)y);
-        else if (out_dtype == HS_DTYPE_F32) hipLaunchKernelGGL((stage_input_plane_kernel<bf16_t, float>), g2, dim3(256), 0, q, s, (float*)y);
-        else hipLaunchKernelGGL((stage_input_plane_kernel<bf16_t, bf16_t>), g2, dim3(256), 0, q, s, (bf16_t*)y);
-        return launch_status();
-    }
-    if (prev_dtype == HS_DTYPE_F32 && out_dtype == HS_DTYPE_F32) hipLaunchKernelGGL((stage_input_kernel<float, float>), blocks, dim3(256), 0, q, s, (float*)y);
-    else if (prev_dtype == HS_DTYPE_F32) hipLaunchKernelGGL((stage_input_kernel<float, bf16_t>), blocks, dim3(256), 0, q, s, (bf16_t*)y);
-    else if (out_dtype == HS_DTYPE_F32) hipLaunchKernelGGL((stage_input_kernel<bf16_t, float>), blocks, dim3(256), 0, q, s, (float*)y);
-    else hipLaunchKernelGGL((stage_input_kernel<bf16_t, bf16_t>), blocks, dim3(256), 0, q, s, (bf16_t*)y);
+    const bool planes = (long)s.B * s.cin() <= 65535;
+    const dim3 g2((s.W + 63) / 64, (s.H + 15) / 16, s.B * s.cin());                  // four rows per thread
+    auto go = [&](auto tp, auto to) {
+        using TP = decltype(tp); using TO = decltype(to);
+        if (planes) hipLaunchKernelGGL((stage_input_plane_kernel<TP, TO>), g2, dim3(256), 0, q, s, (TO*)y);
+        else hipLaunchKernelGGL((stage_input_kernel<TP, TO>), blocks, dim3(256), 0, q, s, (TO*)y);
+    };
+    const int half = prev_dtype != HS_DTYPE_F32 ? prev_dtype : out_dtype;           // the step's half type (or F32: none)
+    auto with_half = [&](auto h) {
+        if (prev_dtype == HS_DTYPE_F32 && out_dtype == HS_DTYPE_F32) go(float{}, float{});
+        else if (prev_dtype == HS_DTYPE_F32) go(float{}, h);
+        else if (out_dtype == HS_DTYPE_F32) go(h, float{});
+        else go(h, h);
+    };
+    if (half == HS_DTYPE_F16) with_half(f16_t{});
+    else with_half(bf16_t{});
     return launch_status();
 }
 
@@ -829,20 +849,36 @@ extern "C" int hs_upsample_argmax_fwd(const float* x, int32_t batch, int32_t cha
     return launch_status();
 }
 
+// bf16 / fp16 storage in and out (dtype: HS_DTYPE_BF16 | HS_DTYPE_F16); the exact-2x shapes with an even width take the 2 x 4 block kernel
+static int upsample_bilinear_h16(int dtype, const void* x, int batch, int channels, int Hi, int Wi, int Ho, int Wo, void* y, hipStream_t stream) {
+    if (!x || !y || batch <= 0 || channels <= 0 || Hi <= 0 || Wi <= 0 || Ho <= 0 || Wo <= 0) return HS_ERR_BAD_ARG;
+    auto go = [&](auto h) {
+        using T = decltype(h);
+        if (Ho == 2 * Hi && Wo == 2 * Wi && (Wi & 1) == 0 && (((size_t)y) & 7) == 0) {          // rows of 4 k outputs: 8-byte stores
+            const size_t n2 = (size_t)batch * channels * Hi * (Wi / 2);
+            const unsigned blocks2 = (unsigned)((n2 + 255) / 256 > 8192 ? 8192 : (n2 + 255) / 256);
+            hipLaunchKernelGGL(upsample2x_h16_kernel<T>, dim3(blocks2), dim3(256), 0, stream, (const T*)x, batch * channels, Hi, Wi, (T*)y);
+            return;
+        }
+        const size_t n = (size_t)batch * channels * Ho * ((Wo + 3) / 4);
+        const unsigned blocks = (unsigned)((n + 255) / 256 > 16384 ? 16384 : (n + 255) / 256);
+        hipLaunchKernelGGL(upsample_bilinear_h16_kernel<T>, dim3(blocks), dim3(256), 0, stream,
+                           (const T*)x, batch * channels, Hi, Wi, Ho, Wo, (float)Hi / (float)Ho, (float)Wi / (float)Wo, (T*)y);
+    };
+    if (dtype == HS_DTYPE_BF16) go(bf16_t{});
+    else if (dtype == HS_DTYPE_F16) go(f16_t{});
+    else return HS_ERR_BAD_ARG;
+    return launch_status();
+}
+
 extern "C" int hs_upsample_bilinear_bf16_fwd(const void* x, int32_t batch, int32_t channels, int32_t Hi, int32_t Wi,
                                              int32_t Ho, int32_t Wo, void* y, void* stream) {
-    if (!x || !y || batch <= 0 || channels <= 0 || Hi <= 0 || Wi <= 0 || Ho <= 0 || Wo <= 0) return HS_ERR_BAD_ARG;
-    if (Ho == 2 * Hi && Wo == 2 * Wi && (Wi & 1) == 0 && (((size_t)y) & 7) == 0) {          // rows of 4 k outputs: 8-byte stores
-        const size_t n2 = (size_t)batch * channels * Hi * (Wi / 2);
-        const unsigned blocks2 = (unsigned)((n2 + 255) / 256 > 8192 ? 8192 : (n2 + 255) / 256);
-        hipLaunchKernelGGL(upsample2x_bf16_kernel, dim3(blocks2), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x, batch * channels, Hi, Wi, (bf16_t*)y);
-        return launch_status();
-    }
-    const size_t n = (size_t)batch * channels * Ho * ((Wo + 3) / 4);
-    const unsigned blocks = (unsigned)((n + 255) / 256 > 16384 ? 16384 : (n + 255) / 256);
-    hipLaunchKernelGGL(upsample_bilinear_bf16_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream,
-                       (const bf16_t*)x, batch * channels, Hi, Wi, Ho, Wo, (float)Hi / (float)Ho, (float)Wi / (float)Wo, (bf16_t*)y);
-    return launch_status();
+    return upsample_bilinear_h16(HS_DTYPE_BF16, x, batch, channels, Hi, Wi, Ho, Wo, y, (hipStream_t)stream);
+}
+
+extern "C" int hs_upsample_bilinear_f16_fwd(const void* x, int32_t batch, int32_t channels, int32_t Hi, int32_t Wi,
+                                            int32_t Ho, int32_t Wo, void* y, void* stream) {
+    return upsample_bilinear_h16(HS_DTYPE_F16, x, batch, channels, Hi, Wi, Ho, Wo, y, (hipStream_t)stream);
 }
 
 extern "C" int hs_upsample_bilinear_fwd(const float* x, int32_t batch, int32_t channels, int32_t Hi, int32_t Wi,

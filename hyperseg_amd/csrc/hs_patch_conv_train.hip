@@ -10,7 +10,7 @@
 // sum is fp32, results are rounded to nearest-even once on store.  The BANK and its gradient are fp32 in either case (round 4):
 // the bank is the output of signal2weights and its gradient the input of that layer's adjoint, both fp32 ("master weights"), it
 // is a few per cent of a launch's bytes, and storing it as bf16 cost a cast launch per layer and direction (30 of the config-5
-// step's 147 launches).
+// step's 147 launches).  fp16 storage (f16_t, torch.autocast's default dtype) is the same contract with IEEE binary16 in memory.
 #include "hs_common.h"
 
 namespace hs {
@@ -194,16 +194,17 @@ static int fill_plain(PlainArgs& a, int64_t ld, int32_t batch, int32_t c_in, int
 }  // namespace hs
 
 namespace hs {
-int launch_conv1x1_bf16(const void* x, int batch, int cin, int H, int W, int fh, int fw, const float* bank, long ld, int c_out, void* y,
-                        hipStream_t stream);                                                         // hs_patch_conv.hip
+int launch_conv1x1_h16(int dtype, const void* x, int batch, int cin, int H, int W, int fh, int fw, const float* bank, long ld, int c_out, void* y,
+                       hipStream_t stream);                                                          // hs_patch_conv.hip
 }
 #ifndef HS_PLAIN_K1_BF16
 #define HS_PLAIN_K1_BF16 1
 #endif
 using namespace hs;
 
-#define HS_BY_DTYPE(dtype, CALL_F32, CALL_BF16) \
-    if ((dtype) == HS_DTYPE_F32) { CALL_F32; } else if ((dtype) == HS_DTYPE_BF16) { CALL_BF16; } else return HS_ERR_BAD_ARG;
+#define HS_BY_DTYPE(dtype, CALL_F32, CALL_BF16, CALL_F16) \
+    if ((dtype) == HS_DTYPE_F32) { CALL_F32; } else if ((dtype) == HS_DTYPE_BF16) { CALL_BF16; } else if ((dtype) == HS_DTYPE_F16) { CALL_F16; } \
+    else return HS_ERR_BAD_ARG;
 
 extern "C" int hs_patch_conv_plain_fwd(int32_t dtype, const void* x, const void* bank, int64_t ld, int32_t batch, int32_t c_in,
                                        int32_t H, int32_t W, int32_t fh, int32_t fw, int32_t c_out, int32_t k, int32_t pad,
@@ -217,8 +218,8 @@ extern "C" int hs_patch_conv_plain_fwd(int32_t dtype, const void* x, const void*
                                    HS_ACT_NONE, y, (hipStream_t)stream);
         if (r != 1) return r;
     }
-    if (dtype == HS_DTYPE_BF16 && k == 1 && pad == 0 && groups == 1 && HS_PLAIN_K1_BF16) {     // tiny patches in bf16: the inference path's k = 1 form, typed (round 6)
-        const int r = launch_conv1x1_bf16(x, batch, c_in, H, W, fh, fw, (const float*)bank, (long)ld, c_out, y, (hipStream_t)stream);
+    if ((dtype == HS_DTYPE_BF16 || dtype == HS_DTYPE_F16) && k == 1 && pad == 0 && groups == 1 && HS_PLAIN_K1_BF16) {     // tiny patches in bf16 / fp16: the inference path's k = 1 form, typed (round 6)
+        const int r = launch_conv1x1_h16(dtype, x, batch, c_in, H, W, fh, fw, (const float*)bank, (long)ld, c_out, y, (hipStream_t)stream);
         if (r != 1) return r;
     }
     a.x = x; a.bank = bank; a.y = y;
@@ -237,15 +238,17 @@ extern "C" int hs_patch_conv_plain_fwd(int32_t dtype, const void* x, const void*
     a.tiles_x = (a.pw + a.TW - 1) / a.TW;
     const size_t lds = tile_bytes(a.TH, a.TW);
     const long blocks = (long)batch * fh * fw * a.tiles_y * a.tiles_x;
-    static std::atomic<unsigned long long> done32{0}, done16{0};
+    static std::atomic<unsigned long long> done32{0}, done16{0}, doneh{0};
     if (lds > 64 * 1024) {
         const int e = dtype == HS_DTYPE_F32 ? allow_full_lds((const void*)plain_fwd_kernel<float>, done32)
+                    : dtype == HS_DTYPE_F16 ? allow_full_lds((const void*)plain_fwd_kernel<f16_t>, doneh)
                                             : allow_full_lds((const void*)plain_fwd_kernel<bf16_t>, done16);
         if (e != HS_OK) return e;
     }
     HS_BY_DTYPE(dtype,
         hipLaunchKernelGGL(plain_fwd_kernel<float>, dim3((unsigned)blocks), dim3(256), lds, (hipStream_t)stream, a),
-        hipLaunchKernelGGL(plain_fwd_kernel<bf16_t>, dim3((unsigned)blocks), dim3(256), lds, (hipStream_t)stream, a))
+        hipLaunchKernelGGL(plain_fwd_kernel<bf16_t>, dim3((unsigned)blocks), dim3(256), lds, (hipStream_t)stream, a),
+        hipLaunchKernelGGL(plain_fwd_kernel<f16_t>, dim3((unsigned)blocks), dim3(256), lds, (hipStream_t)stream, a))
     return launch_status();
 }
 
@@ -266,7 +269,8 @@ extern "C" int hs_patch_conv_plain_bwd_in(int32_t dtype, const void* dy, const v
     const unsigned blocks = (unsigned)((total + 255) / 256 > 32768 ? 32768 : (total + 255) / 256);
     HS_BY_DTYPE(dtype,
         hipLaunchKernelGGL(plain_bwd_in_kernel<float>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, a),
-        hipLaunchKernelGGL(plain_bwd_in_kernel<bf16_t>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, a))
+        hipLaunchKernelGGL(plain_bwd_in_kernel<bf16_t>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, a),
+        hipLaunchKernelGGL(plain_bwd_in_kernel<f16_t>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, a))
     return launch_status();
 }
 
@@ -305,15 +309,17 @@ extern "C" int hs_patch_conv_plain_bwd_w(int32_t dtype, const void* x, const voi
     }
     if (ob <= 0) return HS_ERR_LDS;
     a.ob = ob;
-    static std::atomic<unsigned long long> done32{0}, done16{0};
+    static std::atomic<unsigned long long> done32{0}, done16{0}, doneh{0};
     if (lds > 64 * 1024) {
         const int e = dtype == HS_DTYPE_F32 ? allow_full_lds((const void*)plain_bwd_w_kernel<float>, done32)
+                    : dtype == HS_DTYPE_F16 ? allow_full_lds((const void*)plain_bwd_w_kernel<f16_t>, doneh)
                                             : allow_full_lds((const void*)plain_bwd_w_kernel<bf16_t>, done16);
         if (e != HS_OK) return e;
     }
     dim3 grid((unsigned)(batch * fh * fw), (unsigned)((c_out + ob - 1) / ob));
     HS_BY_DTYPE(dtype,
         hipLaunchKernelGGL(plain_bwd_w_kernel<float>, grid, dim3(256), lds, (hipStream_t)stream, a),
-        hipLaunchKernelGGL(plain_bwd_w_kernel<bf16_t>, grid, dim3(256), lds, (hipStream_t)stream, a))
+        hipLaunchKernelGGL(plain_bwd_w_kernel<bf16_t>, grid, dim3(256), lds, (hipStream_t)stream, a),
+        hipLaunchKernelGGL(plain_bwd_w_kernel<f16_t>, grid, dim3(256), lds, (hipStream_t)stream, a))
     return launch_status();
 }

@@ -1,4 +1,4 @@
-// Training-path helpers around the patch convolutions (BASELINE config 5; round 3).  Plain tensors, storage type T = float | bf16_t.
+// Training-path helpers around the patch convolutions (BASELINE config 5; round 3).  Plain tensors, storage type T = float | bf16_t | f16_t.
 //
 // 1. Halo tiles.  A train-mode v1_0 inverted residual (hyperseg_v1_0.py:328-376) applies each patch's weights to the patch's own
 //    reflect-padded (ph + 2) x (pw + 2) tile; hyperseg_amd lays those tiles side by side as one "tiled image" so that the three layers
@@ -462,10 +462,11 @@ struct BnWalk2 {
         wrap = p >= a.HW; p -= wrap ? a.HW : 0; b += wrap ? 1 : 0;
     }
 };
-__device__ __forceinline__ void bn_unpack2(uint32_t r, float& v0, float& v1) { v0 = __uint_as_float(r << 16); v1 = __uint_as_float(r & 0xffff0000u); }
+__device__ __forceinline__ void bn_unpack2(uint32_t r, float& v0, float& v1, const bf16_t*) { v0 = __uint_as_float(r << 16); v1 = __uint_as_float(r & 0xffff0000u); }
+__device__ __forceinline__ void bn_unpack2(uint32_t r, float& v0, float& v1, const f16_t*) { Pair<f16_t>::unpack(r, v0, v1); }
 // KIND 0: forward statistics (s, q about `k0` = shift); 1: forward apply (y = act(x k0 + ms)); 2: backward statistics; 3: backward apply
-template <int KIND>
-__device__ __forceinline__ void bn_pair_walk(const BnArgs& a, const bf16_t* __restrict__ x, const bf16_t* __restrict__ dy, bf16_t* __restrict__ out, int c,
+template <int KIND, typename T>
+__device__ __forceinline__ void bn_pair_walk(const BnArgs& a, const T* __restrict__ x, const T* __restrict__ dy, T* __restrict__ out, int c,
                                              int chunk, float mean, float invstd, float g, float bb, float k0, float ms, float mq, float& s, float& q) {
     int lo2, hi2;
     bn_slice2(a, chunk, lo2, hi2);
@@ -485,8 +486,8 @@ __device__ __forceinline__ void bn_pair_walk(const BnArgs& a, const bf16_t* __re
         for (int u = 0; u < BN_BATCH; ++u)
             if (e0 + 256 * u < hi2) {
                 float xv[2], dv[2] = {0.f, 0.f}, o[2];
-                bn_unpack2(vx[u], xv[0], xv[1]);
-                if (KIND >= 2) bn_unpack2(vd[u], dv[0], dv[1]);
+                bn_unpack2(vx[u], xv[0], xv[1], x);
+                if (KIND >= 2) bn_unpack2(vd[u], dv[0], dv[1], x);
 #pragma unroll
                 for (int h = 0; h < 2; ++h) {
                     if (KIND == 0) { const float d = xv[h] - k0; s += d; q = fmaf(d, d, q); }
@@ -498,7 +499,7 @@ __device__ __forceinline__ void bn_pair_walk(const BnArgs& a, const bf16_t* __re
                         else { s += d; q = fmaf(d, xh, q); }
                     }
                 }
-                if (KIND == 1 || KIND == 3) Pair<bf16_t>::st(out, at[u], o[0], o[1]);
+                if (KIND == 1 || KIND == 3) Pair<T>::st(out, at[u], o[0], o[1]);
             }
     }
 }
@@ -973,7 +974,7 @@ extern "C" int hs_bank_unpack_fwd(const float* bank, int64_t ld, int32_t batch, 
 extern "C" int hs_upsample_bilinear_typed_bwd(int32_t dtype, const void* dy, int64_t dy_batch_stride, int32_t batch, int32_t channels, int32_t Hi,
                                               int32_t Wi, int32_t Ho, int32_t Wo, void* dx, void* stream) {
     if (!dy || !dx || batch <= 0 || channels <= 0 || Hi <= 0 || Wi <= 0 || Ho <= 0 || Wo <= 0) return HS_ERR_BAD_ARG;
-    if (dtype != HS_DTYPE_F32 && dtype != HS_DTYPE_BF16) return HS_ERR_BAD_ARG;
+    if (dtype != HS_DTYPE_F32 && dtype != HS_DTYPE_BF16 && dtype != HS_DTYPE_F16) return HS_ERR_BAD_ARG;
     if (dy_batch_stride <= 0) dy_batch_stride = (int64_t)channels * Ho * Wo;                         // 0 = packed (B, C, Ho, Wo)
     if (dy_batch_stride < (int64_t)channels * Ho * Wo) return HS_ERR_BAD_ARG;
     if ((long)batch * channels > 65535 || Ho < Hi || Wo < Wi) return HS_ERR_UNSUPPORTED;          // upsampling only (the decoder's use)
@@ -986,11 +987,14 @@ extern "C" int hs_upsample_bilinear_typed_bwd(int32_t dtype, const void* dy, int
     if (Ho == 2 * Hi && Wo == 2 * Wi && (reinterpret_cast<size_t>(dy) % pair_bytes) == 0 && (bs & 1) == 0) {
         const dim3 grid2(((Wi + 1) / 2 + 63) / 64, ((Hi + 1) / 2 + 3) / 4, batch * channels);
         if (dtype == HS_DTYPE_F32) hipLaunchKernelGGL(upsample2x_bwd_kernel<float>, grid2, dim3(256), 0, q, (const float*)dy, channels, bs, Hi, Wi, (float*)dx);
+        else if (dtype == HS_DTYPE_F16) hipLaunchKernelGGL(upsample2x_bwd_kernel<f16_t>, grid2, dim3(256), 0, q, (const f16_t*)dy, channels, bs, Hi, Wi, (f16_t*)dx);
         else hipLaunchKernelGGL(upsample2x_bwd_kernel<bf16_t>, grid2, dim3(256), 0, q, (const bf16_t*)dy, channels, bs, Hi, Wi, (bf16_t*)dx);
         return launch_status();
     }
     if (dtype == HS_DTYPE_F32)
         hipLaunchKernelGGL(upsample_bilinear_bwd_kernel<float>, grid, dim3(256), 0, q, (const float*)dy, channels, bs, Hi, Wi, Ho, Wo, sy, sx, (float*)dx);
+    else if (dtype == HS_DTYPE_F16)
+        hipLaunchKernelGGL(upsample_bilinear_bwd_kernel<f16_t>, grid, dim3(256), 0, q, (const f16_t*)dy, channels, bs, Hi, Wi, Ho, Wo, sy, sx, (f16_t*)dx);
     else
         hipLaunchKernelGGL(upsample_bilinear_bwd_kernel<bf16_t>, grid, dim3(256), 0, q, (const bf16_t*)dy, channels, bs, Hi, Wi, Ho, Wo, sy, sx, (bf16_t*)dx);
     return launch_status();
@@ -1020,10 +1024,13 @@ extern "C" int hs_bn_act_train_fwd(int32_t dtype, const void* x, int32_t batch, 
     if (!x || !y || !save_mean || !save_invstd || !workspace || ((running_mean != nullptr) != (running_var != nullptr))) return HS_ERR_BAD_ARG;
     const dim3 grid(channels, BN_CHUNKS);
     hipStream_t s = (hipStream_t)stream;
-    if ((long)batch * pixels <= BN_SMALL_MAX && (dtype == HS_DTYPE_F32 || dtype == HS_DTYPE_BF16)) {            // one launch: a workgroup per channel
+    if ((long)batch * pixels <= BN_SMALL_MAX && (dtype == HS_DTYPE_F32 || dtype == HS_DTYPE_BF16 || dtype == HS_DTYPE_F16)) {            // one launch: a workgroup per channel
         if (dtype == HS_DTYPE_F32)
             hipLaunchKernelGGL(bn_fwd_small_kernel<float>, dim3(channels), dim3(BN_SMALL_THREADS), 0, s, a, (const float*)x, gamma, beta, running_mean,
                                running_var, save_mean, save_invstd, (float*)y, (long long*)num_batches_tracked);
+        else if (dtype == HS_DTYPE_F16)
+            hipLaunchKernelGGL(bn_fwd_small_kernel<f16_t>, dim3(channels), dim3(BN_SMALL_THREADS), 0, s, a, (const f16_t*)x, gamma, beta, running_mean,
+                               running_var, save_mean, save_invstd, (f16_t*)y, (long long*)num_batches_tracked);
         else
             hipLaunchKernelGGL(bn_fwd_small_kernel<bf16_t>, dim3(channels), dim3(BN_SMALL_THREADS), 0, s, a, (const bf16_t*)x, gamma, beta, running_mean,
                                running_var, save_mean, save_invstd, (bf16_t*)y, (long long*)num_batches_tracked);
@@ -1037,6 +1044,10 @@ extern "C" int hs_bn_act_train_fwd(int32_t dtype, const void* x, int32_t batch, 
         hipLaunchKernelGGL(bn_stats_kernel<bf16_t>, grid, dim3(256), 0, s, a, (const bf16_t*)x, (float*)workspace);
         hipLaunchKernelGGL(bn_apply_kernel<bf16_t>, grid, dim3(256), 0, s, a, (const bf16_t*)x, (const float*)workspace, gamma, beta,
                            running_mean, running_var, save_mean, save_invstd, (bf16_t*)y, (long long*)num_batches_tracked);
+    } else if (dtype == HS_DTYPE_F16) {
+        hipLaunchKernelGGL(bn_stats_kernel<f16_t>, grid, dim3(256), 0, s, a, (const f16_t*)x, (float*)workspace);
+        hipLaunchKernelGGL(bn_apply_kernel<f16_t>, grid, dim3(256), 0, s, a, (const f16_t*)x, (const float*)workspace, gamma, beta,
+                           running_mean, running_var, save_mean, save_invstd, (f16_t*)y, (long long*)num_batches_tracked);
     } else return HS_ERR_BAD_ARG;
     return launch_status();
 }
@@ -1051,6 +1062,7 @@ extern "C" int hs_bn_train_stats_fwd(int32_t dtype, const void* x, int32_t batch
     const dim3 grid(channels, BN_CHUNKS);
     if (dtype == HS_DTYPE_F32) hipLaunchKernelGGL(bn_stats_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, a, (const float*)x, (float*)workspace);
     else if (dtype == HS_DTYPE_BF16) hipLaunchKernelGGL(bn_stats_kernel<bf16_t>, grid, dim3(256), 0, (hipStream_t)stream, a, (const bf16_t*)x, (float*)workspace);
+    else if (dtype == HS_DTYPE_F16) hipLaunchKernelGGL(bn_stats_kernel<f16_t>, grid, dim3(256), 0, (hipStream_t)stream, a, (const f16_t*)x, (float*)workspace);
     else return HS_ERR_BAD_ARG;
     return launch_status();
 }
@@ -1064,10 +1076,13 @@ extern "C" int hs_bn_act_train_bwd(int32_t dtype, const void* x, const void* dy,
     if (!x || !dy || !dx || !save_mean || !save_invstd || !workspace) return HS_ERR_BAD_ARG;
     const dim3 grid(channels, BN_CHUNKS);
     hipStream_t s = (hipStream_t)stream;
-    if ((long)batch * pixels <= BN_SMALL_MAX && (dtype == HS_DTYPE_F32 || dtype == HS_DTYPE_BF16)) {
+    if ((long)batch * pixels <= BN_SMALL_MAX && (dtype == HS_DTYPE_F32 || dtype == HS_DTYPE_BF16 || dtype == HS_DTYPE_F16)) {
         if (dtype == HS_DTYPE_F32)
             hipLaunchKernelGGL(bn_bwd_small_kernel<float>, dim3(channels), dim3(BN_SMALL_THREADS), 0, s, a, (const float*)x, (const float*)dy, gamma, beta,
                                save_mean, save_invstd, (float*)dx, dgamma, dbeta);
+        else if (dtype == HS_DTYPE_F16)
+            hipLaunchKernelGGL(bn_bwd_small_kernel<f16_t>, dim3(channels), dim3(BN_SMALL_THREADS), 0, s, a, (const f16_t*)x, (const f16_t*)dy, gamma, beta,
+                               save_mean, save_invstd, (f16_t*)dx, dgamma, dbeta);
         else
             hipLaunchKernelGGL(bn_bwd_small_kernel<bf16_t>, dim3(channels), dim3(BN_SMALL_THREADS), 0, s, a, (const bf16_t*)x, (const bf16_t*)dy, gamma, beta,
                                save_mean, save_invstd, (bf16_t*)dx, dgamma, dbeta);
@@ -1083,6 +1098,11 @@ extern "C" int hs_bn_act_train_bwd(int32_t dtype, const void* x, const void* dy,
                            save_invstd, (float*)workspace);
         hipLaunchKernelGGL(bn_bwd_apply_kernel<bf16_t>, grid, dim3(256), 0, s, a, (const bf16_t*)x, (const bf16_t*)dy, (const float*)workspace,
                            gamma, beta, save_mean, save_invstd, (bf16_t*)dx, dgamma, dbeta);
+    } else if (dtype == HS_DTYPE_F16) {
+        hipLaunchKernelGGL(bn_bwd_stats_kernel<f16_t>, grid, dim3(256), 0, s, a, (const f16_t*)x, (const f16_t*)dy, gamma, beta, save_mean,
+                           save_invstd, (float*)workspace);
+        hipLaunchKernelGGL(bn_bwd_apply_kernel<f16_t>, grid, dim3(256), 0, s, a, (const f16_t*)x, (const f16_t*)dy, (const float*)workspace,
+                           gamma, beta, save_mean, save_invstd, (f16_t*)dx, dgamma, dbeta);
     } else return HS_ERR_BAD_ARG;
     return launch_status();
 }
@@ -1104,6 +1124,9 @@ extern "C" int hs_bn_act_train_bwd_apply(int32_t dtype, const void* x, const voi
     else if (dtype == HS_DTYPE_BF16)
         hipLaunchKernelGGL(bn_bwd_apply_np_kernel<bf16_t>, grid, dim3(256), 0, s, a, (const bf16_t*)x, (const bf16_t*)dy, partial, (int)n_partials, gamma, beta,
                            save_mean, save_invstd, (bf16_t*)dx, dgamma, dbeta);
+    else if (dtype == HS_DTYPE_F16)
+        hipLaunchKernelGGL(bn_bwd_apply_np_kernel<f16_t>, grid, dim3(256), 0, s, a, (const f16_t*)x, (const f16_t*)dy, partial, (int)n_partials, gamma, beta,
+                           save_mean, save_invstd, (f16_t*)dx, dgamma, dbeta);
     else return HS_ERR_BAD_ARG;
     return launch_status();
 }
@@ -1117,9 +1140,10 @@ static int tile_args(TileArgs& a, int B, int C, int H, int W, int fh, int fw, in
     return HS_OK;
 }
 
-#define HS_TILE_LAUNCH(dtype, KERNEL_F32, KERNEL_BF16, grid, SRC, DST) \
+#define HS_TILE_LAUNCH(dtype, KERNEL_F32, KERNEL_BF16, KERNEL_F16, grid, SRC, DST) \
     if ((dtype) == HS_DTYPE_F32) hipLaunchKernelGGL(KERNEL_F32, grid, dim3(256), 0, (hipStream_t)stream, a, (const float*)(SRC), (float*)(DST)); \
     else if ((dtype) == HS_DTYPE_BF16) hipLaunchKernelGGL(KERNEL_BF16, grid, dim3(256), 0, (hipStream_t)stream, a, (const bf16_t*)(SRC), (bf16_t*)(DST)); \
+    else if ((dtype) == HS_DTYPE_F16) hipLaunchKernelGGL(KERNEL_F16, grid, dim3(256), 0, (hipStream_t)stream, a, (const f16_t*)(SRC), (f16_t*)(DST)); \
     else return HS_ERR_BAD_ARG;
 
 extern "C" int hs_halo_tiles_fwd(int32_t dtype, const void* x, int32_t batch, int32_t channels, int32_t H, int32_t W, int32_t fh,
@@ -1129,7 +1153,7 @@ extern "C" int hs_halo_tiles_fwd(int32_t dtype, const void* x, int32_t batch, in
     if (st != HS_OK) return st;
     if (!x || !tiled) return HS_ERR_BAD_ARG;
     const dim3 grid((fw * (a.pw + 2) + 63) / 64, (fh * (a.ph + 2) + 15) / 16, (batch * channels + 1) / 2);        // four rows of two planes per thread
-    HS_TILE_LAUNCH(dtype, halo_tiles_fwd_kernel<float>, halo_tiles_fwd_kernel<bf16_t>, grid, x, tiled)
+    HS_TILE_LAUNCH(dtype, halo_tiles_fwd_kernel<float>, halo_tiles_fwd_kernel<bf16_t>, halo_tiles_fwd_kernel<f16_t>, grid, x, tiled)
     return launch_status();
 }
 
@@ -1145,16 +1169,17 @@ extern "C" int hs_halo_tiles_bwd(int32_t dtype, const void* dtiled, int32_t batc
         const float inv_npx = 1.0f / (float)npx;
         const int ch = per == 1 ? HS_HALO_BWD_CH_BIG : HS_HALO_BWD_CH_SMALL;      // channels per thread
         const dim3 gridp((unsigned)(fh * fw), (unsigned)((channels + per * ch - 1) / (per * ch)), (unsigned)batch);
-        if (dtype != HS_DTYPE_F32 && dtype != HS_DTYPE_BF16) return HS_ERR_BAD_ARG;
+        if (dtype != HS_DTYPE_F32 && dtype != HS_DTYPE_BF16 && dtype != HS_DTYPE_F16) return HS_ERR_BAD_ARG;
 #define HS_HB_LAUNCH(CH) \
         if (dtype == HS_DTYPE_F32) hipLaunchKernelGGL((halo_tiles_bwd_patch_kernel<float, CH>), gridp, dim3(256), 0, (hipStream_t)stream, a, (const float*)dtiled, (float*)dx, inv_npx); \
+        else if (dtype == HS_DTYPE_F16) hipLaunchKernelGGL((halo_tiles_bwd_patch_kernel<f16_t, CH>), gridp, dim3(256), 0, (hipStream_t)stream, a, (const f16_t*)dtiled, (f16_t*)dx, inv_npx); \
         else hipLaunchKernelGGL((halo_tiles_bwd_patch_kernel<bf16_t, CH>), gridp, dim3(256), 0, (hipStream_t)stream, a, (const bf16_t*)dtiled, (bf16_t*)dx, inv_npx);
         if (ch == 8) { HS_HB_LAUNCH(8) } else if (ch == 4) { HS_HB_LAUNCH(4) } else { HS_HB_LAUNCH(2) }
 #undef HS_HB_LAUNCH
         return launch_status();
     }
     const dim3 grid((W + 63) / 64, (H + 3) / 4, batch * channels);
-    HS_TILE_LAUNCH(dtype, halo_tiles_bwd_kernel<float>, halo_tiles_bwd_kernel<bf16_t>, grid, dtiled, dx)
+    HS_TILE_LAUNCH(dtype, halo_tiles_bwd_kernel<float>, halo_tiles_bwd_kernel<bf16_t>, halo_tiles_bwd_kernel<f16_t>, grid, dtiled, dx)
     return launch_status();
 }
 
@@ -1165,7 +1190,7 @@ extern "C" int hs_tile_interior_fwd(int32_t dtype, const void* tiled, int32_t ba
     if (st != HS_OK) return st;
     if (!tiled || !y) return HS_ERR_BAD_ARG;
     const dim3 grid((W + 63) / 64, (H + 3) / 4, batch * channels);
-    HS_TILE_LAUNCH(dtype, (tile_interior_kernel<float, false>), (tile_interior_kernel<bf16_t, false>), grid, tiled, y)
+    HS_TILE_LAUNCH(dtype, (tile_interior_kernel<float, false>), (tile_interior_kernel<bf16_t, false>), (tile_interior_kernel<f16_t, false>), grid, tiled, y)
     return launch_status();
 }
 
@@ -1176,7 +1201,7 @@ extern "C" int hs_tile_interior_bwd(int32_t dtype, const void* dy, int32_t batch
     if (st != HS_OK) return st;
     if (!dy || !dtiled) return HS_ERR_BAD_ARG;
     const dim3 grid((fw * (a.pw + 2) + 63) / 64, (fh * (a.ph + 2) + 3) / 4, batch * channels);
-    HS_TILE_LAUNCH(dtype, (tile_interior_kernel<float, true>), (tile_interior_kernel<bf16_t, true>), grid, dy, dtiled)
+    HS_TILE_LAUNCH(dtype, (tile_interior_kernel<float, true>), (tile_interior_kernel<bf16_t, true>), (tile_interior_kernel<f16_t, true>), grid, dy, dtiled)
     return launch_status();
 }
 
@@ -1240,12 +1265,15 @@ extern "C" int hs_bootstrap_mean_bwd(const float* values, int32_t n, const float
 extern "C" int hs_cross_entropy_typed_fwd(int32_t dtype, const void* logits, const int64_t* target, int32_t batch, int32_t classes, int64_t pixels,
                                           int64_t ignore_index, float* loss, void* stream) {
     if (!logits || !target || !loss || batch <= 0 || classes <= 0 || pixels <= 0) return HS_ERR_BAD_ARG;
-    if (dtype != HS_DTYPE_F32 && dtype != HS_DTYPE_BF16) return HS_ERR_BAD_ARG;
+    if (dtype != HS_DTYPE_F32 && dtype != HS_DTYPE_BF16 && dtype != HS_DTYPE_F16) return HS_ERR_BAD_ARG;
     const long total = (long)batch * pixels;
     const dim3 blocks((unsigned)((total + 255) / 256 > 65535 * 16 ? 65535 * 16 : (total + 255) / 256));
     if (dtype == HS_DTYPE_F32)
         launch_cross_entropy<false, float>(blocks, (hipStream_t)stream, (const float*)logits, (const long long*)target, classes, (long)pixels, total,
                                            (long long)ignore_index, nullptr, (void*)loss);
+    else if (dtype == HS_DTYPE_F16)
+        launch_cross_entropy<false, f16_t>(blocks, (hipStream_t)stream, (const f16_t*)logits, (const long long*)target, classes, (long)pixels, total,
+                                            (long long)ignore_index, nullptr, (void*)loss);
     else
         launch_cross_entropy<false, bf16_t>(blocks, (hipStream_t)stream, (const bf16_t*)logits, (const long long*)target, classes, (long)pixels, total,
                                             (long long)ignore_index, nullptr, (void*)loss);
@@ -1255,12 +1283,15 @@ extern "C" int hs_cross_entropy_typed_fwd(int32_t dtype, const void* logits, con
 extern "C" int hs_cross_entropy_typed_bwd(int32_t dtype, const void* logits, const int64_t* target, int32_t batch, int32_t classes, int64_t pixels,
                                           int64_t ignore_index, const float* grad_loss, void* grad_logits, void* stream) {
     if (!logits || !target || !grad_loss || !grad_logits || batch <= 0 || classes <= 0 || pixels <= 0) return HS_ERR_BAD_ARG;
-    if (dtype != HS_DTYPE_F32 && dtype != HS_DTYPE_BF16) return HS_ERR_BAD_ARG;
+    if (dtype != HS_DTYPE_F32 && dtype != HS_DTYPE_BF16 && dtype != HS_DTYPE_F16) return HS_ERR_BAD_ARG;
     const long total = (long)batch * pixels;
     const dim3 blocks((unsigned)((total + 255) / 256 > 65535 * 16 ? 65535 * 16 : (total + 255) / 256));
     if (dtype == HS_DTYPE_F32)
         launch_cross_entropy<true, float>(blocks, (hipStream_t)stream, (const float*)logits, (const long long*)target, classes, (long)pixels, total,
                                           (long long)ignore_index, grad_loss, grad_logits);
+    else if (dtype == HS_DTYPE_F16)
+        launch_cross_entropy<true, f16_t>(blocks, (hipStream_t)stream, (const f16_t*)logits, (const long long*)target, classes, (long)pixels, total,
+                                           (long long)ignore_index, grad_loss, grad_logits);
     else
         launch_cross_entropy<true, bf16_t>(blocks, (hipStream_t)stream, (const bf16_t*)logits, (const long long*)target, classes, (long)pixels, total,
                                            (long long)ignore_index, grad_loss, grad_logits);
@@ -1299,12 +1330,15 @@ extern "C" int hs_bootstrapped_ce_bwd(int32_t dtype, const void* logits, const i
                                       int64_t ignore_index, const float* loss, const float* state8, const float* grad_mean, void* grad_logits,
                                       void* stream) {
     if (!logits || !target || !loss || !state8 || !grad_mean || !grad_logits || batch <= 0 || classes <= 0 || pixels <= 0) return HS_ERR_BAD_ARG;
-    if (dtype != HS_DTYPE_F32 && dtype != HS_DTYPE_BF16) return HS_ERR_BAD_ARG;
+    if (dtype != HS_DTYPE_F32 && dtype != HS_DTYPE_BF16 && dtype != HS_DTYPE_F16) return HS_ERR_BAD_ARG;
     const long total = (long)batch * pixels;
     const dim3 blocks((unsigned)((total + 255) / 256 > 65535 * 16 ? 65535 * 16 : (total + 255) / 256));
     if (dtype == HS_DTYPE_F32)
         launch_cross_entropy<true, float>(blocks, (hipStream_t)stream, (const float*)logits, (const long long*)target, classes, (long)pixels, total,
                                           (long long)ignore_index, loss, grad_logits, state8, grad_mean, 1.0f / (float)batch);
+    else if (dtype == HS_DTYPE_F16)
+        launch_cross_entropy<true, f16_t>(blocks, (hipStream_t)stream, (const f16_t*)logits, (const long long*)target, classes, (long)pixels, total,
+                                           (long long)ignore_index, loss, grad_logits, state8, grad_mean, 1.0f / (float)batch);
     else
         launch_cross_entropy<true, bf16_t>(blocks, (hipStream_t)stream, (const bf16_t*)logits, (const long long*)target, classes, (long)pixels, total,
                                            (long long)ignore_index, loss, grad_logits, state8, grad_mean, 1.0f / (float)batch);
@@ -1329,10 +1363,16 @@ struct AdamTable {
     int n;
 };
 
+// AMP (hs_adam_step_amp): torch.optim.Adam(fused=True)'s GradScaler protocol -- a set *found_inf skips the whole step (parameters, moments,
+// step word), otherwise the gradient is divided by *grad_scale (if given) and that unscaled gradient is written back to g, as torch does.
+template <bool AMP = false>
 __global__ __launch_bounds__(256)
 void adam_kernel(AdamTable t, const float* __restrict__ lr_dev, float lr_host, double b1d, double b2d, float eps, float wd, int decoupled,
-                 int maximize, float* __restrict__ steps) {
+                 int maximize, float* __restrict__ steps, const float* __restrict__ grad_scale = nullptr, const float* __restrict__ found_inf = nullptr) {
     const __attribute__((address_space(4))) AdamTable* kt = (const __attribute__((address_space(4))) AdamTable*)__builtin_amdgcn_kernarg_segment_ptr();
+    if constexpr (AMP) {
+        if (*found_inf != 0.0f) return;                        // (uniform across the launch: every workgroup leaves before touching anything)
+    }
     const int blk = (int)blockIdx.x;
     int i = 0;
     for (int q = 1; q < kt->n; ++q)
@@ -1346,6 +1386,7 @@ void adam_kernel(AdamTable t, const float* __restrict__ lr_dev, float lr_host, d
     const long n = kt->numel[i], e0 = (long)(blk - kt->first_block[i]) * ADAM_BLOCK + 4 * (long)threadIdx.x;
     float* __restrict__ p = kt->p[i]; const float* __restrict__ g = kt->g[i];
     float* __restrict__ m = kt->m[i]; float* __restrict__ v = kt->v[i];
+    [[maybe_unused]] const double scale_d = AMP && grad_scale ? (double)*grad_scale : 1.0;
     auto one = [&](float& pv, float gv, float& mv, float& vv) {
         if (maximize) gv = -gv;
         if (wd != 0.0f) { if (decoupled) pv -= lr * wd * pv; else gv += wd * pv; }
@@ -1355,13 +1396,24 @@ void adam_kernel(AdamTable t, const float* __restrict__ lr_dev, float lr_host, d
     };
     if (e0 + 3 < n && ((((size_t)p) | ((size_t)g) | ((size_t)m) | ((size_t)v)) & 15) == 0) {
         float4 pv = *reinterpret_cast<const float4*>(p + e0), mv = *reinterpret_cast<const float4*>(m + e0), vv = *reinterpret_cast<const float4*>(v + e0);
-        const float4 gv = *reinterpret_cast<const float4*>(g + e0);
+        float4 gv = *reinterpret_cast<const float4*>(g + e0);
+        if constexpr (AMP) {
+            if (grad_scale) {                                  // torch: grad /= (double)*grad_scale in opmath float, stored back
+                gv.x = (float)((double)gv.x / scale_d); gv.y = (float)((double)gv.y / scale_d);
+                gv.z = (float)((double)gv.z / scale_d); gv.w = (float)((double)gv.w / scale_d);
+                *reinterpret_cast<float4*>(const_cast<float*>(g) + e0) = gv;
+            }
+        }
         one(pv.x, gv.x, mv.x, vv.x); one(pv.y, gv.y, mv.y, vv.y); one(pv.z, gv.z, mv.z, vv.z); one(pv.w, gv.w, mv.w, vv.w);
         *reinterpret_cast<float4*>(p + e0) = pv; *reinterpret_cast<float4*>(m + e0) = mv; *reinterpret_cast<float4*>(v + e0) = vv;
     } else {
         for (long e = e0; e < n && e < e0 + 4; ++e) {
             float pv = p[e], mv = m[e], vv = v[e];
-            one(pv, g[e], mv, vv);
+            float gv = g[e];
+            if constexpr (AMP) {
+                if (grad_scale) { gv = (float)((double)gv / scale_d); const_cast<float*>(g)[e] = gv; }
+            }
+            one(pv, gv, mv, vv);
             p[e] = pv; m[e] = mv; v[e] = vv;
         }
     }
@@ -1377,13 +1429,11 @@ extern "C" int64_t hs_adam_blocks(const int64_t* numel, int32_t n) {
     return b < 0x7fffffff ? b : 0;
 }
 
-extern "C" int hs_adam_step(float* const* params, const float* const* grads, float* const* exp_avg, float* const* exp_avg_sq, const int64_t* numel,
-                            int32_t n, const float* lr_device, float lr, double beta1, double beta2, float eps, float weight_decay, int32_t decoupled,
-                            int32_t maximize, float* steps, void* stream) {
+static int adam_table(hs::AdamTable& t, int& b, float* const* params, const float* const* grads, float* const* exp_avg, float* const* exp_avg_sq,
+                      const int64_t* numel, int32_t n, float* steps) {
     if (!params || !grads || !exp_avg || !exp_avg_sq || !numel || !steps || n <= 0) return HS_ERR_BAD_ARG;
     if (n > hs::ADAM_MAX_TENSORS) return HS_ERR_UNSUPPORTED;
-    hs::AdamTable t{};
-    int b = 0;
+    b = 0;
     for (int i = 0; i < n; ++i) {
         if (!params[i] || !grads[i] || !exp_avg[i] || !exp_avg_sq[i] || numel[i] <= 0) return HS_ERR_BAD_ARG;
         t.p[i] = params[i]; t.g[i] = grads[i]; t.m[i] = exp_avg[i]; t.v[i] = exp_avg_sq[i]; t.numel[i] = (long)numel[i];
@@ -1393,7 +1443,30 @@ extern "C" int hs_adam_step(float* const* params, const float* const* grads, flo
         b += (int)nb;
     }
     t.first_block[n] = b; t.n = n;
-    hipLaunchKernelGGL(hs::adam_kernel, dim3((unsigned)b), dim3(256), 0, (hipStream_t)stream, t, lr_device, lr, beta1, beta2, eps,
-                       weight_decay, decoupled, maximize, steps);
+    return HS_OK;
+}
+
+extern "C" int hs_adam_step(float* const* params, const float* const* grads, float* const* exp_avg, float* const* exp_avg_sq, const int64_t* numel,
+                            int32_t n, const float* lr_device, float lr, double beta1, double beta2, float eps, float weight_decay, int32_t decoupled,
+                            int32_t maximize, float* steps, void* stream) {
+    hs::AdamTable t{};
+    int b = 0;
+    const int st = adam_table(t, b, params, grads, exp_avg, exp_avg_sq, numel, n, steps);
+    if (st != HS_OK) return st;
+    hipLaunchKernelGGL(hs::adam_kernel<false>, dim3((unsigned)b), dim3(256), 0, (hipStream_t)stream, t, lr_device, lr, beta1, beta2, eps,
+                       weight_decay, decoupled, maximize, steps, nullptr, nullptr);
+    return hs::launch_status();
+}
+
+extern "C" int hs_adam_step_amp(float* const* params, float* const* grads, float* const* exp_avg, float* const* exp_avg_sq, const int64_t* numel,
+                                int32_t n, const float* lr_device, float lr, double beta1, double beta2, float eps, float weight_decay, int32_t decoupled,
+                                int32_t maximize, float* steps, const float* grad_scale, const float* found_inf, void* stream) {
+    if (!found_inf) return HS_ERR_BAD_ARG;
+    hs::AdamTable t{};
+    int b = 0;
+    const int st = adam_table(t, b, params, (const float* const*)grads, exp_avg, exp_avg_sq, numel, n, steps);
+    if (st != HS_OK) return st;
+    hipLaunchKernelGGL(hs::adam_kernel<true>, dim3((unsigned)b), dim3(256), 0, (hipStream_t)stream, t, lr_device, lr, beta1, beta2, eps,
+                       weight_decay, decoupled, maximize, steps, grad_scale, found_inf);
     return hs::launch_status();
 }

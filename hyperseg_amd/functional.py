@@ -98,11 +98,13 @@ class StageInput:
 
     def materialize(self, dtype=torch.float32):
         """The concatenated tensor itself (diagnostics / modules that cannot consume a lazy input; the training path, where
-        ``dtype`` = torch.bfloat16 under autocast and the previous level may be stored as bf16: hs_stage_input_typed_fwd)."""
-        codes = {torch.float32: 0, torch.bfloat16: 1}
+        ``dtype`` = the autocast dtype, bf16 or fp16, and the previous level may be stored in it: hs_stage_input_typed_fwd)."""
+        codes = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}
         pdt = self.prev.dtype if self.prev is not None else torch.float32
         if dtype not in codes or pdt not in codes:
-            raise NotImplementedError(f'stage input: storage types {pdt} -> {dtype} (supported: float32, bfloat16)')
+            raise NotImplementedError(f'stage input: storage types {pdt} -> {dtype} (supported: float32, bfloat16, float16)')
+        if pdt != torch.float32 and dtype != torch.float32 and pdt != dtype:
+            raise NotImplementedError(f'stage input: storage types {pdt} -> {dtype} (one half type per step)')
         st = self.c_struct(pdt)
         y = torch.empty(self.shape, device=self.device, dtype=dtype)
         with _hip.device_scope(self.device):

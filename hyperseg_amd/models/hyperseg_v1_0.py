@@ -607,7 +607,7 @@ class MultiScaleDecoder(EpochOnModeSwitch, nn.Module):
     def _train_banks(self, s):
         """Every level's bank for the training path in ONE launch (autograd.S2WBanksTrain: hs_s2w_train_fwd, three launches back) --
         or None when a level cannot take it (several signal-fed modules in a level, a signal2weights with a bias, K > 80, CPU)."""
-        if not (HA.USE_HIP_S2W_TRAIN and s.is_cuda and s.dtype in (torch.float32, torch.bfloat16)):
+        if not (HA.USE_HIP_S2W_TRAIN and s.is_cuda and s.dtype in (torch.float32, torch.bfloat16, torch.float16)):
             return None
         groups = self._hyper_modules()
         if any(len(g) != 1 for g in groups[:self.levels]) or (self.out_fc is not None and len(groups[-1]) != 1):

@@ -55,7 +55,7 @@ def bootstrapped_cross_entropy(pred, target, k=4096, thresh=0.3, weight=None, ig
     capturing = pred.is_cuda and torch.cuda.is_current_stream_capturing()
     # the per-pixel losses of the WHOLE batch in one pass over (N, C, H, W) (the reference permutes every image to (HW, C) first,
     # bootstrapped_ce_loss.py:20-23: same values, a transposed copy + a softmax + a gather per image and direction)
-    hip_ce = (USE_HIP_BOOTSTRAP and weight is None and pred.is_cuda and pred.dtype in (torch.float32, torch.bfloat16) and pred.dim() == 4
+    hip_ce = (USE_HIP_BOOTSTRAP and weight is None and pred.is_cuda and pred.dtype in (torch.float32, torch.bfloat16, torch.float16) and pred.dim() == 4
               and target.dtype == torch.int64 and target.device == pred.device)
     if hip_ce and USE_FUSED_LOSS and pred.shape[2] * pred.shape[3] > k and pred.shape[0] <= 65535 and pred.shape[2] * pred.shape[3] < 2 ** 31:
         from .autograd import BootstrappedCrossEntropy                     # the whole loss as one Function: its adjoint is one launch (round 6)
@@ -112,7 +112,13 @@ class Adam(torch.optim.Optimizer):
     Capturable by construction: the step count lives on the device (one word per workgroup, incremented by the kernel), ``lr`` may be a
     float or a one-element CUDA tensor (what a scheduler updates in place under a captured step, ``GraphedTrainStep``).  fp32 CUDA
     parameters with dense fp32 gradients only; every parameter of a group that has a gradient takes part, and the SET of those
-    parameters must not change between steps (the per-workgroup step words are laid out for it; a change raises)."""
+    parameters must not change between steps (the per-workgroup step words are laid out for it; a change raises).
+
+    GradScaler protocol (``_step_supports_amp_scaling``): under ``torch.amp.GradScaler.step`` the ``grad_scale`` / ``found_inf`` device
+    tensors the scaler attaches go to ``hs_adam_step_amp`` -- the gradients are unscaled inside the launch (and left unscaled in
+    ``p.grad``, as torch's fused Adam leaves them) and a set ``found_inf`` skips the step on the device: no host read, capturable."""
+
+    _step_supports_amp_scaling = True
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, decoupled_weight_decay=False, maximize=False):
         if not 0.0 <= betas[0] < 1.0 or not 0.0 <= betas[1] < 1.0 or eps < 0.0 or weight_decay < 0.0:
@@ -128,6 +134,8 @@ class Adam(torch.optim.Optimizer):
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
+        # set by torch.amp.GradScaler.step for the duration of this call (grad_scale is None after scaler.unscale_(self))
+        found_inf, grad_scale = getattr(self, 'found_inf', None), getattr(self, 'grad_scale', None)
         for group in self.param_groups:
             ps = [p for p in group['params'] if p.grad is not None]
             if not ps:
@@ -172,13 +180,25 @@ class Adam(torch.optim.Optimizer):
                 lr_dev = lr if isinstance(lr, torch.Tensor) and lr.is_cuda else None
                 if lr_dev is not None and (lr_dev.dtype != torch.float32 or lr_dev.numel() != 1):
                     raise NotImplementedError('hyperseg_amd.training.Adam: a device learning rate must be one fp32 element')
+                args = (arr(chunk), arr(grads), arr([self.state[p]['exp_avg'] for p in chunk]), arr([self.state[p]['exp_avg_sq'] for p in chunk]),
+                        numel, n, lr_dev.data_ptr() if lr_dev is not None else None, 0.0 if lr_dev is not None else float(lr),
+                        float(group['betas'][0]), float(group['betas'][1]), float(group['eps']), float(group['weight_decay']),
+                        int(group['decoupled_weight_decay']), int(group['maximize']), held[1].data_ptr())
+                if found_inf is None:
+                    with _hip.device_scope(dev):
+                        status = _hip.lib.hs_adam_step(*args, _hip.stream_ptr(dev))
+                    _hip.check(status, 'hs_adam_step')
+                    continue
+                inf_dev = _amp_word(found_inf, dev)
+                scale_dev = _amp_word(grad_scale, dev) if grad_scale is not None else None
                 with _hip.device_scope(dev):
-                    status = _hip.lib.hs_adam_step(arr(chunk), arr(grads), arr([self.state[p]['exp_avg'] for p in chunk]),
-                                                   arr([self.state[p]['exp_avg_sq'] for p in chunk]), numel, n,
-                                                   lr_dev.data_ptr() if lr_dev is not None else None, 0.0 if lr_dev is not None else float(lr),
-                                                   float(group['betas'][0]), float(group['betas'][1]), float(group['eps']), float(group['weight_decay']),
-                                                   int(group['decoupled_weight_decay']), int(group['maximize']), held[1].data_ptr(), _hip.stream_ptr(dev))
-                _hip.check(status, 'hs_adam_step')
+                    status = _hip.lib.hs_adam_step_amp(*args, scale_dev.data_ptr() if scale_dev is not None else None, inf_dev.data_ptr(),
+                                                       _hip.stream_ptr(dev))
+                _hip.check(status, 'hs_adam_step_amp')
+                if grad_scale is not None:
+                    for p, g in zip(chunk, grads):
+                        if g is not p.grad:                                        # a non-contiguous gradient: the unscaled copy goes back
+                            p.grad.copy_(g)
         return loss
 
     def _detached_step_words(self):
@@ -227,6 +247,15 @@ class Adam(torch.optim.Optimizer):
         return 0 if held is None else int(held[1][0].item())
 
 
+def _amp_word(t, dev):
+    """A GradScaler's one-element scale / found-inf tensor as an fp32 word on ``dev`` (no host read)."""
+    if t.dtype != torch.float32 or t.device != dev:
+        t = t.to(device=dev, dtype=torch.float32, non_blocking=True)
+    if t.numel() != 1:
+        raise ValueError(f'hyperseg_amd.training.Adam: GradScaler tensors must hold one element, got {tuple(t.shape)}')
+    return t.contiguous()
+
+
 def train_step(model, criterion, optimizer, scheduler, x, target):
     """One optimisation step; returns (loss, prediction).  ``model`` is any callable producing (N, C, h, w) logits."""
     pred = model(x)
@@ -264,10 +293,19 @@ class GraphedTrainStep:
     may still be alive when this object is built -- e.g. a ``loss`` variable that still carries its ``grad_fn``.  Such a graph keeps the
     parameters' gradient accumulators alive, and those stay bound to the stream of the eager steps; the captured backward would then
     hop to that (non-capturing) stream and hipStreamEndCapture dies on ROCm 7.2 (bisected in round 3: ``del loss`` is the whole fix).
-    Keep ``loss.detach()`` / ``float(loss)`` instead."""
+    Keep ``loss.detach()`` / ``float(loss)`` instead.
 
-    def __init__(self, model, criterion, optimizer, inputs, target, warmup=3):
+    ``scaler``: a ``torch.amp.GradScaler`` -- the captured step is then the whole mixed-precision step, ``scaler.scale(loss).backward()``,
+    the inf check, ``scaler.step(optimizer)`` and ``scaler.update()``, with the scale and growth tracker updated on the device by every
+    replay.  It needs an optimizer that takes the scaler's protocol without a host read (``hyperseg_amd.training.Adam``, or torch's
+    ``fused=True`` Adam); the model runs under whatever autocast the caller wraps ``model`` in."""
+
+    def __init__(self, model, criterion, optimizer, inputs, target, warmup=3, scaler=None):
         self.model, self.criterion, self.optimizer = model, criterion, optimizer
+        self.scaler = scaler
+        if scaler is not None and not getattr(optimizer, '_step_supports_amp_scaling', False):
+            raise ValueError('GraphedTrainStep(scaler=...): the optimizer must implement the GradScaler protocol '
+                             '(_step_supports_amp_scaling); a generic optimizer reads found_inf on the host in every step')
         self.inputs, self.target = inputs, target
         self._unit = None
         dev = target.device
@@ -300,10 +338,15 @@ class GraphedTrainStep:
         loss = self.criterion(pred, self.target)
         # the root gradient is a tensor this object owns (made in the warm-up, outside the capture): `loss.backward()` alone makes autograd
         # fill a fresh ones_like(loss) -- one more launch in every replay (round 6: 82 -> 81 per config-5 step)
-        if self._unit is None or self._unit.shape != loss.shape or self._unit.dtype != loss.dtype:
-            self._unit = torch.ones_like(loss)
-        loss.backward(self._unit)
-        self.optimizer.step()
+        root = loss if self.scaler is None else self.scaler.scale(loss)
+        if self._unit is None or self._unit.shape != root.shape or self._unit.dtype != root.dtype:
+            self._unit = torch.ones_like(root)
+        root.backward(self._unit)
+        if self.scaler is None:
+            self.optimizer.step()
+        else:
+            self.scaler.step(self.optimizer)              # the inf check, then the optimizer's own skip / unscale on the device
+            self.scaler.update()
         return loss.detach(), pred.detach()
 
     def step(self, inputs=None, target=None):

@@ -301,6 +301,10 @@ int hs_upsample_bilinear_fwd(const float* x, int32_t batch, int32_t channels, in
  * torch.autocast(bfloat16) (autograd.UpsampleBilinear). */
 int hs_upsample_bilinear_bf16_fwd(const void* x, int32_t batch, int32_t channels, int32_t Hi, int32_t Wi, int32_t Ho, int32_t Wo,
                                   void* y, void* stream);
+/* ... on fp16 storage (IEEE binary16 x and y; the same taps and arithmetic, one round-to-nearest-even on store): the final logits under
+ * torch.autocast(float16). */
+int hs_upsample_bilinear_f16_fwd(const void* x, int32_t batch, int32_t channels, int32_t Hi, int32_t Wi, int32_t Ho, int32_t Wo,
+                                 void* y, void* stream);
 
 /* The same resize with the class argmax taken in registers: mask (B, Ho, Wo) uint8 = argmax_c of the upsampled logits,
  * bit-identical to argmax over hs_upsample_bilinear_fwd's output (shared arithmetic), ties -> lowest class; channels
@@ -327,8 +331,10 @@ int hs_patch_conv_bwd_weight(const float* x, const float* dy, int32_t batch, int
  * reduced-precision path: SURVEY 8d).  `bank` and `dbank` are fp32 (const float* / float*) for either dtype: the bank comes out of
  * signal2weights and its gradient goes into that layer's adjoint, both fp32.  Plain (B, C, H, W) tensors, no fused prologue /
  * epilogue -- the training route composes the stage input, BatchNorm and activations with its own differentiable ops
- * (hyperseg_amd/autograd.py).  Same math as hs_patch_conv_fwd / hs_patch_conv_bwd_input / hs_patch_conv_bwd_weight above. */
-typedef enum { HS_DTYPE_F32 = 0, HS_DTYPE_BF16 = 1 } hs_dtype;
+ * (hyperseg_amd/autograd.py).  Same math as hs_patch_conv_fwd / hs_patch_conv_bwd_input / hs_patch_conv_bwd_weight above.
+ * HS_DTYPE_F16 = IEEE binary16 storage under the same contract (torch.autocast's default dtype; rounding to nearest-even on store,
+ * overflow to +-inf as torch's .half()): every entry point that takes an hs_dtype accepts all three. */
+typedef enum { HS_DTYPE_F32 = 0, HS_DTYPE_BF16 = 1, HS_DTYPE_F16 = 2 } hs_dtype;
 int hs_patch_conv_plain_fwd(int32_t dtype, const void* x, const void* bank, int64_t ld, int32_t batch, int32_t c_in,
                             int32_t H, int32_t W, int32_t fh, int32_t fw, int32_t c_out, int32_t k, int32_t pad,
                             int32_t pad_mode, int32_t groups, void* y, void* stream);
@@ -524,6 +530,12 @@ int64_t hs_adam_blocks(const int64_t* numel, int32_t n);
 int hs_adam_step(float* const* params, const float* const* grads, float* const* exp_avg, float* const* exp_avg_sq, const int64_t* numel,
                  int32_t n, const float* lr_device, float lr, double beta1, double beta2, float eps, float weight_decay, int32_t decoupled,
                  int32_t maximize, float* steps, void* stream);
+/* ... under a GradScaler (torch.optim.Adam(fused=True)'s protocol, no host read): grad_scale (device float, may be null) and found_inf
+ * (device float) are what torch.amp.GradScaler.step hands the optimizer.  *found_inf != 0: nothing is written -- no parameter, no moment,
+ * no step word.  Otherwise every gradient is divided by *grad_scale (if given), written back to `grads` unscaled, and the step is taken. */
+int hs_adam_step_amp(float* const* params, float* const* grads, float* const* exp_avg, float* const* exp_avg_sq, const int64_t* numel,
+                     int32_t n, const float* lr_device, float lr, double beta1, double beta2, float eps, float weight_decay, int32_t decoupled,
+                     int32_t maximize, float* steps, const float* grad_scale, const float* found_inf, void* stream);
 int hs_bootstrap_mean_fwd(const float* values, int32_t n, int32_t k, float thresh, void* workspace, float* out5, void* stream);
 int hs_bootstrap_mean_bwd(const float* values, int32_t n, const float* state5, const float* grad_out, float* grad_values, void* stream);
 /* The same for `images` images at once (one set of launches, grid.y = image): values (images, n), workspace images x
