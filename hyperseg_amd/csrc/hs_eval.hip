@@ -1,0 +1,326 @@
+// On-device evaluation epilogue: the (target, prediction) confusion matrix of the reference's evaluation loop
+// (hyperseg/utils/seg_utils.py:5-36, fed by test.py:166-175 / test_fps.py:184-194) counted on the GPU, either from finished
+// masks (hs_confusion_fwd) or inside the final upsample + arg-max launch, where every output pixel's class index already sits in
+// a register (hs_upsample_confusion_fwd).  Integer counts only: the result does not depend on arrival order.
+//
+// Shape of both kernels ("On-device evaluation"):
+//   * one workgroup of 512 threads per CU (the arg-max bodies hold 136-252 VGPRs: 1024 threads spill), grid-striding over its image's pixels (blockIdx.y = image), counting into a
+//     per-workgroup n x n histogram of 32-bit bins in LDS;
+//   * in the wave, label maps are spatially coherent -- most lanes hold the SAME (t, p) key and a per-lane LDS atomic would
+//     serialise on one bin.  count_key() walks the distinct keys present in the wave (__ballot / __popcll: one LDS add per
+//     distinct key) for a few rounds and only then lets the remaining lanes add for themselves (the uniform-random case);
+//   * across workgroups the whole matrix is a few cache lines, so each workgroup flushes once, at its end: non-zero bins only,
+//     consecutive lanes on consecutive bins, one 64-bit global atomic add each (global_atomic_add_x2, no compare-and-swap).
+// No cross-workgroup waiting of any kind.
+#include <hip/hip_runtime.h>
+#include <cstdint>
+#include "hyperseg_hip.h"
+#include "hs_common.h"
+#include "hs_upsample_taps.h"
+
+namespace hs {
+
+constexpr int EVAL_THREADS = 512;
+constexpr int EVAL_MAX_CLASSES = 128;          // n * n * 4 bytes = 64 KB of LDS at most
+constexpr int EVAL_AGG_ROUNDS = 4;             // distinct keys handled by ballot before lanes add for themselves
+
+// One key per lane (key < 0: nothing to count), all lanes of the wave present.
+__device__ __forceinline__ void count_key(unsigned* __restrict__ hist, int key, int lane) {
+    unsigned long long todo = __ballot(key >= 0);
+#pragma unroll 1
+    for (int it = 0; it < EVAL_AGG_ROUNDS && todo != 0; ++it) {
+        const int leader = __ffsll((long long)todo) - 1;
+        const int k = __builtin_amdgcn_readlane(key, leader);
+        const unsigned long long same = __ballot(key == k);
+        if (lane == leader) atomicAdd(&hist[k], (unsigned)__popcll(same));
+        todo &= ~same;
+    }
+    if ((todo >> lane) & 1ull) atomicAdd(&hist[key], 1u);
+}
+
+// n * t + p, or -1 where the pair is not counted: targets outside [0, n) are ignored (seg_utils.py:15-17).
+template <typename T>
+__device__ __forceinline__ int pair_key(T t, int p, int n) {
+    return (t >= (T)0 && (long long)t < (long long)n) ? n * (int)t + p : -1;
+}
+
+__device__ __forceinline__ void hist_zero(unsigned* hist, int nn) {
+    for (int i = threadIdx.x; i < nn; i += EVAL_THREADS) hist[i] = 0u;
+    __syncthreads();
+}
+__device__ __forceinline__ void hist_flush(const unsigned* hist, int nn, unsigned long long* __restrict__ out) {
+    __syncthreads();
+    for (int i = threadIdx.x; i < nn; i += EVAL_THREADS) {
+        const unsigned v = hist[i];
+        if (v != 0u) atomicAdd(out + i, (unsigned long long)v);
+    }
+}
+
+// 2 consecutive targets / 4 consecutive targets; `vec`: the address is a multiple of the vector's size
+template <typename T> struct Vec2;
+template <> struct Vec2<uint8_t> { typedef uchar2 type; };
+template <> struct Vec2<int64_t> { typedef longlong2 type; };
+template <typename T>
+__device__ __forceinline__ void load2(const T* __restrict__ p, bool vec, T (&t)[2]) {
+    if (vec) {
+        const typename Vec2<T>::type v = *reinterpret_cast<const typename Vec2<T>::type*>(p);
+        t[0] = (T)v.x; t[1] = (T)v.y;
+    } else {
+        t[0] = p[0]; t[1] = p[1];
+    }
+}
+__device__ __forceinline__ void load4(const uint8_t* __restrict__ p, uint8_t (&t)[4]) {
+    const uchar4 v = *reinterpret_cast<const uchar4*>(p);
+    t[0] = v.x; t[1] = v.y; t[2] = v.z; t[3] = v.w;
+}
+__device__ __forceinline__ void load4(const int64_t* __restrict__ p, int64_t (&t)[4]) {
+    const longlong2 a = reinterpret_cast<const longlong2*>(p)[0], b = reinterpret_cast<const longlong2*>(p)[1];
+    t[0] = a.x; t[1] = a.y; t[2] = b.x; t[3] = b.y;
+}
+
+// General resize (any ratio, the identity included): upsample_argmax_kernel's arithmetic -- row4_taps / bilinear_row4, strictly
+// greater wins, first maximum kept -- one thread = 4 consecutive output pixels of a row, then the four pairs are counted.
+template <typename TT>
+__global__ __launch_bounds__(EVAL_THREADS)
+void upsample_confusion_kernel(const float* __restrict__ x, int C, int Hi, int Wi, int Ho, int Wo, float scale_y, float scale_x,
+                               const TT* __restrict__ target, int n, unsigned long long* __restrict__ out, long out_image_stride,
+                               uint8_t* __restrict__ mask, int vec) {
+    extern __shared__ unsigned hist[];
+    const int nn = n * n, lane = threadIdx.x & 63;
+    hist_zero(hist, nn);
+    const size_t b = blockIdx.y;
+    const int wq = (Wo + 3) / 4;
+    const int items = Ho * wq;
+    const float* __restrict__ xb = x + b * C * Hi * Wi;
+    for (int base = blockIdx.x * EVAL_THREADS; base < items; base += gridDim.x * EVAL_THREADS) {      // wave-uniform trip count
+        const int e0 = base + (int)threadIdx.x;
+        const bool live = e0 < items;
+        const int e = live ? e0 : items - 1;
+        const int q = e % wq, yo = e / wq;
+        const Row4 t = row4_taps(yo, q, Hi, Wi, Wo, scale_y, scale_x);
+        float best[4];
+        int idx[4] = {0, 0, 0, 0};
+        bilinear_row4(xb, Wi, t, best);
+#pragma unroll 6
+        for (int c = 1; c < C; ++c) {
+            float o[4];
+            bilinear_row4(xb + (size_t)c * Hi * Wi, Wi, t, o);
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+                if (o[i] > best[i]) { best[i] = o[i]; idx[i] = c; }
+        }
+        const size_t at = (b * Ho + yo) * Wo + 4 * q;
+        TT tv[4];
+        if (vec) {
+            load4(target + at, tv);
+        } else {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) tv[i] = target[at + (4 * q + i < Wo ? i : 0)];
+        }
+        if (mask != nullptr && live) {
+            if (vec) {
+                *reinterpret_cast<uchar4*>(mask + at) = make_uchar4(idx[0], idx[1], idx[2], idx[3]);
+            } else {
+                for (int i = 0; i < 4 && 4 * q + i < Wo; ++i) mask[at + i] = (uint8_t)idx[i];
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+            count_key(hist, (live && 4 * q + i < Wo) ? pair_key<TT>(tv[i], idx[i], n) : -1, lane);
+    }
+    hist_flush(hist, nn, out + b * out_image_stride);
+}
+
+// Exact 2x: upsample2x_argmax_kernel's arithmetic and work split -- up2x_block, four consecutive lanes share one 2 x 4 output block
+// and split the classes among them, two shuffles combine (larger value wins, lower class on ties) -- after which all four lanes
+// hold the block's eight class indices and each counts two of them: lane `sub` takes row sub >> 1, columns 2 (sub & 1) and + 1.
+template <typename TT>
+__global__ __launch_bounds__(EVAL_THREADS)
+void upsample2x_confusion_kernel(const float* __restrict__ x, int C, int Hi, int Wi, const TT* __restrict__ target, int n,
+                                 unsigned long long* __restrict__ out, long out_image_stride, uint8_t* __restrict__ mask, int vec) {
+    extern __shared__ unsigned hist[];
+    const int nn = n * n, lane = threadIdx.x & 63;
+    hist_zero(hist, nn);
+    const size_t b = blockIdx.y;
+    const int wq = Wi >> 1, Wo = 2 * Wi;
+    const int items = Hi * wq;                                  // 2 x 4 output blocks of this image
+    const int sub = (int)(threadIdx.x & 3);
+    const float* __restrict__ xb = x + b * C * Hi * Wi;
+    constexpr float NEG = -3.402823466e38f;
+    for (int base = blockIdx.x * (EVAL_THREADS / 4); base < items; base += gridDim.x * (EVAL_THREADS / 4)) {
+        const int e0 = base + (int)(threadIdx.x >> 2);
+        const bool live = e0 < items;
+        const int e = live ? e0 : items - 1;                    // surplus lanes shadow the last block (shuffles stay convergent)
+        const int q = e % wq, yi = e / wq;
+        float best0[4] = {NEG, NEG, NEG, NEG}, best1[4] = {NEG, NEG, NEG, NEG};
+        int idx0[4] = {sub, sub, sub, sub}, idx1[4] = {sub, sub, sub, sub};
+        for (int c0 = sub; c0 < C; c0 += 20) {
+            float o0[5][4], o1[5][4];
+#pragma unroll
+            for (int u = 0; u < 5; ++u) {
+                const int c = min(c0 + 4 * u, C - 1);
+                up2x_block(xb + (size_t)c * Hi * Wi, Hi, Wi, yi, q, o0[u], o1[u]);
+            }
+#pragma unroll
+            for (int u = 0; u < 5; ++u) {
+                const int c = c0 + 4 * u;
+                if (c < C) {
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) {
+                        if (o0[u][i] > best0[i]) { best0[i] = o0[u][i]; idx0[i] = c; }
+                        if (o1[u][i] > best1[i]) { best1[i] = o1[u][i]; idx1[i] = c; }
+                    }
+                }
+            }
+        }
+#pragma unroll
+        for (int m = 1; m <= 2; m <<= 1) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const float v0 = __shfl_xor(best0[i], m, 64), v1 = __shfl_xor(best1[i], m, 64);
+                const int j0 = __shfl_xor(idx0[i], m, 64), j1 = __shfl_xor(idx1[i], m, 64);
+                if (v0 > best0[i] || (v0 == best0[i] && j0 < idx0[i])) { best0[i] = v0; idx0[i] = j0; }
+                if (v1 > best1[i] || (v1 == best1[i] && j1 < idx1[i])) { best1[i] = v1; idx1[i] = j1; }
+            }
+        }
+        const size_t at = (b * 2 * Hi + 2 * yi) * Wo + 4 * q;
+        if (mask != nullptr && sub == 0 && live) {
+            if (vec) {
+                *reinterpret_cast<uchar4*>(mask + at) = make_uchar4(idx0[0], idx0[1], idx0[2], idx0[3]);
+                *reinterpret_cast<uchar4*>(mask + at + Wo) = make_uchar4(idx1[0], idx1[1], idx1[2], idx1[3]);
+            } else {
+#pragma unroll
+                for (int i = 0; i < 4; ++i) { mask[at + i] = (uint8_t)idx0[i]; mask[at + Wo + i] = (uint8_t)idx1[i]; }
+            }
+        }
+        const bool row1 = (sub & 2) != 0, right = (sub & 1) != 0;
+        const int pa = row1 ? (right ? idx1[2] : idx1[0]) : (right ? idx0[2] : idx0[0]);
+        const int pb = row1 ? (right ? idx1[3] : idx1[1]) : (right ? idx0[3] : idx0[1]);
+        TT tv[2];
+        load2(target + at + (row1 ? Wo : 0) + (right ? 2 : 0), vec != 0, tv);
+        count_key(hist, live ? pair_key<TT>(tv[0], pa, n) : -1, lane);
+        count_key(hist, live ? pair_key<TT>(tv[1], pb, n) : -1, lane);
+    }
+    hist_flush(hist, nn, out + b * out_image_stride);
+}
+
+// Finished predictions: one thread = 4 consecutive elements of its image's row of N.  A prediction outside [0, n) is not
+// counted either (the stock route miscounts or fails there).
+template <typename TP, typename TT>
+__global__ __launch_bounds__(EVAL_THREADS)
+void confusion_kernel(const TP* __restrict__ pred, const TT* __restrict__ target, long N, int n,
+                      unsigned long long* __restrict__ out, long out_image_stride, int vec) {
+    extern __shared__ unsigned hist[];
+    const int nn = n * n, lane = threadIdx.x & 63;
+    hist_zero(hist, nn);
+    const size_t b = blockIdx.y;
+    const TP* __restrict__ pb = pred + b * N;
+    const TT* __restrict__ tb = target + b * N;
+    const long groups = (N + 3) / 4;
+    for (long base = (long)blockIdx.x * EVAL_THREADS; base < groups; base += (long)gridDim.x * EVAL_THREADS) {
+        const long g = base + threadIdx.x;
+        const bool live = g < groups;
+        const long at = 4 * (live ? g : groups - 1);
+        TP pv[4];
+        TT tv[4];
+        if (vec) {
+            load4(pb + at, pv);
+            load4(tb + at, tv);
+        } else {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const long j = at + i < N ? at + i : N - 1;
+                pv[i] = pb[j]; tv[i] = tb[j];
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const bool ok = live && at + i < N && pv[i] >= (TP)0 && (long long)pv[i] < (long long)n;
+            count_key(hist, ok ? pair_key<TT>(tv[i], (int)pv[i], n) : -1, lane);
+        }
+    }
+    hist_flush(hist, nn, out + b * out_image_stride);
+}
+
+static int eval_cus() {
+    static const int cus = [] {                                  // (one process per GPU: every visible device is the same part)
+        int dev = 0, c = 0;
+        return (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&c, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && c > 0) ? c : 256;
+    }();
+    return cus;
+}
+// workgroups per image: about one per CU over the whole batch, never more than there are passes of work
+static unsigned eval_grid_x(long passes, int batch) {
+    long per_image = (eval_cus() + batch - 1) / batch;
+    if (per_image > passes) per_image = passes;
+    return (unsigned)(per_image < 1 ? 1 : per_image);
+}
+static bool eval_storage_ok(int dtype) { return dtype == HS_EVAL_U8 || dtype == HS_EVAL_I64; }
+static bool aligned_to(const void* p, size_t a) { return ((uintptr_t)p % a) == 0; }
+
+}  // namespace hs
+
+using namespace hs;
+
+extern "C" int hs_eval_max_classes(void) { return EVAL_MAX_CLASSES; }
+
+extern "C" int hs_upsample_confusion_fwd(const float* x, int32_t batch, int32_t channels, int32_t Hi, int32_t Wi, int32_t Ho, int32_t Wo,
+                                         const void* target, int32_t target_dtype, int32_t num_classes, int32_t per_image,
+                                         int64_t* confusion, uint8_t* mask, void* stream) {
+    if (!x || !target || !confusion || batch <= 0 || channels <= 0 || Hi <= 0 || Wi <= 0 || Ho <= 0 || Wo <= 0) return HS_ERR_BAD_ARG;
+    if (!eval_storage_ok(target_dtype) || num_classes <= 0 || channels > num_classes) return HS_ERR_BAD_ARG;
+    if (num_classes > 256) return HS_ERR_BAD_ARG;                                            // uint8 class indices
+    if (num_classes > EVAL_MAX_CLASSES || batch > 65535 || (long)Ho * Wo > 0x7fffffffL - 4096) return HS_ERR_UNSUPPORTED;
+    const size_t lds = (size_t)num_classes * num_classes * sizeof(unsigned);
+    const long stride = per_image ? (long)num_classes * num_classes : 0;
+    unsigned long long* out = reinterpret_cast<unsigned long long*>(confusion);
+    const size_t tsz = target_dtype == HS_EVAL_U8 ? 1 : 8;
+    hipStream_t s = (hipStream_t)stream;
+    if (Ho == 2 * Hi && Wo == 2 * Wi && (Wi & 1) == 0) {
+        const int vec = aligned_to(target, 2 * tsz) && (!mask || aligned_to(mask, 4));
+        const long passes = ((long)Hi * (Wi / 2) + EVAL_THREADS / 4 - 1) / (EVAL_THREADS / 4);
+        const dim3 grid(eval_grid_x(passes, batch), (unsigned)batch);
+        if (target_dtype == HS_EVAL_U8)
+            hipLaunchKernelGGL(upsample2x_confusion_kernel<uint8_t>, grid, dim3(EVAL_THREADS), lds, s, x, channels, Hi, Wi,
+                               (const uint8_t*)target, num_classes, out, stride, mask, vec);
+        else
+            hipLaunchKernelGGL(upsample2x_confusion_kernel<int64_t>, grid, dim3(EVAL_THREADS), lds, s, x, channels, Hi, Wi,
+                               (const int64_t*)target, num_classes, out, stride, mask, vec);
+        return launch_status();
+    }
+    const int vec = (Wo & 3) == 0 && aligned_to(target, tsz == 1 ? 4 : 16) && (!mask || aligned_to(mask, 4));
+    const long passes = ((long)Ho * ((Wo + 3) / 4) + EVAL_THREADS - 1) / EVAL_THREADS;
+    const dim3 grid(eval_grid_x(passes, batch), (unsigned)batch);
+    const float sy = (float)Hi / (float)Ho, sx = (float)Wi / (float)Wo;
+    if (target_dtype == HS_EVAL_U8)
+        hipLaunchKernelGGL(upsample_confusion_kernel<uint8_t>, grid, dim3(EVAL_THREADS), lds, s, x, channels, Hi, Wi, Ho, Wo, sy, sx,
+                           (const uint8_t*)target, num_classes, out, stride, mask, vec);
+    else
+        hipLaunchKernelGGL(upsample_confusion_kernel<int64_t>, grid, dim3(EVAL_THREADS), lds, s, x, channels, Hi, Wi, Ho, Wo, sy, sx,
+                           (const int64_t*)target, num_classes, out, stride, mask, vec);
+    return launch_status();
+}
+
+extern "C" int hs_confusion_fwd(const void* pred, int32_t pred_dtype, const void* target, int32_t target_dtype, int32_t batch,
+                                int64_t elements, int32_t num_classes, int32_t per_image, int64_t* confusion, void* stream) {
+    if (!pred || !target || !confusion || batch <= 0 || elements <= 0 || num_classes <= 0) return HS_ERR_BAD_ARG;
+    if (!eval_storage_ok(pred_dtype) || !eval_storage_ok(target_dtype)) return HS_ERR_BAD_ARG;
+    if (num_classes > EVAL_MAX_CLASSES || batch > 65535 || elements > 0x7fffffffL - 4096) return HS_ERR_UNSUPPORTED;
+    const size_t lds = (size_t)num_classes * num_classes * sizeof(unsigned);
+    const long stride = per_image ? (long)num_classes * num_classes : 0;
+    unsigned long long* out = reinterpret_cast<unsigned long long*>(confusion);
+    const size_t psz = pred_dtype == HS_EVAL_U8 ? 1 : 8, tsz = target_dtype == HS_EVAL_U8 ? 1 : 8;
+    const int vec = (elements & 3) == 0 && aligned_to(pred, psz == 1 ? 4 : 16) && aligned_to(target, tsz == 1 ? 4 : 16);
+    const long passes = ((elements + 3) / 4 + EVAL_THREADS - 1) / EVAL_THREADS;
+    const dim3 grid(eval_grid_x(passes, batch), (unsigned)batch), block(EVAL_THREADS);
+    hipStream_t s = (hipStream_t)stream;
+    const long N = (long)elements;
+#define HS_EVAL_LAUNCH(TP, TT) \
+    hipLaunchKernelGGL((confusion_kernel<TP, TT>), grid, block, lds, s, (const TP*)pred, (const TT*)target, N, num_classes, out, stride, vec)
+    if (pred_dtype == HS_EVAL_U8 && target_dtype == HS_EVAL_U8) HS_EVAL_LAUNCH(uint8_t, uint8_t);
+    else if (pred_dtype == HS_EVAL_U8) HS_EVAL_LAUNCH(uint8_t, int64_t);
+    else if (target_dtype == HS_EVAL_U8) HS_EVAL_LAUNCH(int64_t, uint8_t);
+    else HS_EVAL_LAUNCH(int64_t, int64_t);
+#undef HS_EVAL_LAUNCH
+    return launch_status();
+}

@@ -23,15 +23,36 @@ import torch
 import torch.nn as nn
 
 
+def _kernels():
+    """``hyperseg_amd.functional`` when the HIP library is built and loads, else None (a CPU-only use of this module)."""
+    try:
+        from . import functional
+        return functional
+    except Exception:           # the library is missing or does not load: CUDA operands then take the stock route too
+        return None
+
+
 class ConfusionMatrix:
-    """n x n counts of (target, prediction) pairs; targets outside [0, n) are ignored (seg_utils.py:5-36)."""
+    """n x n counts of (target, prediction) pairs; targets outside [0, n) are ignored (seg_utils.py:5-36).  CUDA operands are
+    counted by one launch of the package's kernel (``functional.confusion_update``: no device-to-host synchronisation, no
+    temporaries, capturable in a HIP graph); CPU operands by the reference's stock ops (``update_stock``).  ``per_image``
+    collects the (B, n, n) matrices of ``update_per_image`` / ``HyperGen.evaluate(..., per_image=True)`` calls."""
 
     def __init__(self, num_classes):
         self.num_classes = num_classes
         self.mat = None
+        self.per_image = []
+
+    def matrix(self, device):
+        """``mat``, created on first use (as ``update`` always did)."""
+        if self.mat is None:
+            self.mat = torch.zeros((self.num_classes, self.num_classes), dtype=torch.int64, device=device)
+        return self.mat
 
     @torch.no_grad()
-    def update(self, target, pred):
+    def update_stock(self, target, pred):
+        """The reference's routine on stock torch ops, on whatever device the operands live (``target[valid]`` has a
+        data-dependent shape: a device-to-host synchronisation on CUDA tensors)."""
         n = self.num_classes
         if self.mat is None:
             self.mat = torch.zeros((n, n), dtype=torch.int64, device=target.device)
@@ -39,8 +60,50 @@ class ConfusionMatrix:
         pairs = n * target[valid].to(torch.int64) + pred[valid].to(torch.int64)
         self.mat += torch.bincount(pairs, minlength=n * n).view(n, n)
 
+    def _kernel_route(self, target, pred):
+        if not (target.is_cuda and pred.is_cuda and target.shape == pred.shape and target.numel() > 0
+                and target.dtype in (torch.uint8, torch.int64) and pred.dtype in (torch.uint8, torch.int64)):
+            return None
+        hf = _kernels()
+        return hf if hf is not None and self.num_classes <= hf.eval_max_classes() else None
+
+    @torch.no_grad()
+    def update(self, target, pred):
+        hf = self._kernel_route(target, pred)
+        if hf is None:
+            return self.update_stock(target, pred)
+        hf.confusion_update(pred, target, self.num_classes, out=self.matrix(target.device))
+
+    def add_per_image(self, mats):
+        """Books a batch's (B, n, n) matrices: kept in ``per_image`` and summed into ``mat``."""
+        self.per_image.append(mats)
+        self.matrix(mats.device).add_(mats.sum(0))
+        return mats
+
+    @torch.no_grad()
+    def update_per_image(self, target, pred):
+        """``update`` on operands whose first dimension is the image: returns the batch's (B, n, n) matrices, appends them to
+        ``per_image`` and adds their sum to ``mat`` (test.py:174-175 counts each image on its own for the Jaccard score)."""
+        n, b = self.num_classes, target.shape[0]
+        hf = self._kernel_route(target, pred)
+        if hf is not None:
+            mats = hf.confusion_update(pred, target, n, per_image=True)
+        else:
+            mats = torch.zeros((b, n, n), dtype=torch.int64, device=target.device)
+            for i in range(b):
+                one = ConfusionMatrix(n)
+                one.update_stock(target[i].flatten(), pred[i].flatten())
+                mats[i] = one.mat
+        return self.add_per_image(mats)
+
+    def per_image_matrices(self):
+        """All booked per-image matrices as one (images, n, n) tensor."""
+        n = self.num_classes
+        return torch.cat(self.per_image) if self.per_image else torch.zeros((0, n, n), dtype=torch.int64)
+
     def reset(self):
         self.mat.zero_()
+        self.per_image = []
 
     @torch.no_grad()
     def compute(self):
@@ -49,6 +112,37 @@ class ConfusionMatrix:
         diag = torch.diag(h)
         rows, cols = h.sum(1), h.sum(0)
         return diag.sum() / h.sum(), diag / (rows + 1e-6), diag / (rows + cols - diag + 1e-6)
+
+    def reduce_from_all_processes(self):
+        """Sum ``mat`` over the process group (seg_utils.py:38-44): a no-op when torch.distributed is unavailable or not
+        initialised, else barrier + all_reduce.  An n x n int64 matrix (2.9 KB at 19 classes) is all that multi-GPU evaluation
+        has to move."""
+        if not torch.distributed.is_available():
+            return
+        if not torch.distributed.is_initialized():
+            return
+        torch.distributed.barrier()
+        torch.distributed.all_reduce(self.mat)
+
+
+@torch.no_grad()
+def jaccard_per_image(mats, ignore_index=0, eps=1e-6):
+    """Per-image Jaccard score from per-image confusion matrices ``mats`` (images, n, n): what the reference computes with one
+    ``.item()`` per image (hyperseg/test.py:219-227 on :210-216's matrix) -- rows of ``ignore_index`` dropped from the
+    counts, its union zeroed, intersection / (union + eps) averaged over the classes whose union is positive (NaN for an
+    image with none, as torch.mean of an empty tensor is).  test.py cannot be imported here (torchvision), so the tests pin
+    this function against a restatement of those lines written out in the test itself."""
+    mats = mats.clone()
+    n = mats.shape[-1]
+    if ignore_index is not None and 0 <= ignore_index < n:
+        mats[:, ignore_index, :] = 0                     # calc_conf_mat masks those targets out (test.py:212-213)
+    inter = torch.diagonal(mats, dim1=1, dim2=2)
+    union = mats.sum(2) + mats.sum(1) - inter
+    if ignore_index is not None and ignore_index < n:
+        union[:, ignore_index] = 0
+    score = inter / (union + eps)
+    keep = union > 0
+    return (score * keep).sum(1) / keep.sum(1)
 
 
 def remove_bn(model):
@@ -68,12 +162,18 @@ def _sync(device):
 
 
 @torch.no_grad()
-def measure_fps(model, batches, device, num_classes, passes=2):
+def measure_fps(model, batches, device, num_classes, passes=2, fused_metrics=False):
     """``batches``: list of (input, target) host tensors (inputs pinned when CUDA is used).  Runs ``passes`` passes over
-    them and reports the LAST one (the reference's warm-up + timed pass).  Returns a dict."""
+    them and reports the LAST one (the reference's warm-up + timed pass).  Returns a dict.  ``fused_metrics``: where the
+    model has ``evaluate`` (a HyperGen, a GraphedModel) the frame is scored by the forward's last launch -- INSIDE the timed
+    region, which the reference's protocol keeps outside it; models without it are scored as before."""
     result = {}
+    fused = bool(fused_metrics) and hasattr(model, 'evaluate')
+    owns = fused and getattr(model, 'owns_confusion', False)        # GraphedModel: the matrix lives with the graph
     for p in range(passes):
         conf = ConfusionMatrix(num_classes)
+        if owns:
+            model.reset_confusion()
         total_time, frames = 0.0, 0
         for inp, target in batches:
             target = target.to(device)
@@ -85,11 +185,17 @@ def measure_fps(model, batches, device, num_classes, passes=2):
                 x = inp                          # GraphedModel: the H2D copy lands in the graph's static input buffer
             else:
                 x = inp.to(device, non_blocking=True)
-            pred = model(x)
+            if fused:
+                pred = model.evaluate(x, target) if owns else model.evaluate(x, target, conf)
+            else:
+                pred = model(x)
             _sync(device)
             total_time += time.perf_counter() - t0
             frames += pred.shape[0]
-            conf.update(target.flatten(), pred.argmax(1).flatten() if pred.dim() == 4 else pred.flatten())
+            if not fused:
+                conf.update(target.flatten(), pred.argmax(1).flatten() if pred.dim() == 4 else pred.flatten())
+        if owns:
+            conf.mat = model.confusion.clone()
         acc, _, iou = conf.compute()
         result = {'fps': frames / total_time, 'frames': frames, 'seconds': total_time, 'pass': p,
                   'global_accuracy': float(acc), 'mean_iou': float(iou.mean())}
@@ -117,6 +223,9 @@ def main(argv=None):
     ap.add_argument('--prepare', action='store_true', help='hyperseg_amd.utils.inference.prepare_for_inference (fused encoder)')
     ap.add_argument('--graph', action='store_true', help='replay one HIP graph per frame (utils.inference.GraphedModel) '
                                                          'instead of launching eagerly; same protocol otherwise')
+    ap.add_argument('--fused-metrics', action='store_true',
+                    help="score every frame inside the forward's last launch (model.evaluate): the scoring then falls INSIDE the timed "
+                         "region, which the reference's protocol keeps outside it")
     ap.add_argument('-t', '--trace', action='store_true',
                     help="the reference's torch.jit.trace switch (test_fps.py:49-50, 150-152).  The mirror's modules call the C ABI through "
                          "ctypes, which the tracer cannot see, so a traced module would be wrong; the purpose of tracing there -- no Python / "
@@ -151,14 +260,17 @@ def main(argv=None):
         model = torch.nn.DataParallel(model, args.gpus)
     if args.graph and device.type == 'cuda':
         from .utils.inference import GraphedModel
-        model = GraphedModel(model)
+        model = GraphedModel(model, num_classes=spec['num_classes'] if args.fused_metrics else None)
     bs = args.batch_size or spec['batch']
     uniq = synthetic_batches(min(args.distinct, args.iterations), bs, spec['size'], spec['num_classes'], device)
     batches = [uniq[i % len(uniq)] for i in range(args.iterations)]
-    res = measure_fps(model, batches, device, spec['num_classes'])
+    res = measure_fps(model, batches, device, spec['num_classes'], fused_metrics=args.fused_metrics)
     res.update(config=args.config, batch_size=bs, size=list(spec['size']), device=str(device), remove_bn=args.remove_bn,
                prepared=bool(args.prepare and not args.remove_bn), graph=bool(args.graph and device.type == 'cuda'),
                protocol='test_fps.py: per-iteration sync + H2D + ' + ('HIP-graph replay' if args.graph else 'eager forward'))
+    if args.fused_metrics:
+        res.update(fused_metrics=True, protocol=res['protocol'] + ' + confusion matrix counted inside the timed region by the '
+                   "forward's last launch (the reference scores outside it)")
     print(json.dumps(res))
     return res
 

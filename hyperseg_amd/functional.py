@@ -1263,6 +1263,94 @@ def upsample_argmax(x, size):
     return mask
 
 
+_EVAL_DTYPES = {torch.uint8: 0, torch.int64: 1}          # hs_eval_dtype of include/hyperseg_hip.h
+
+
+def eval_max_classes():
+    """Largest ``num_classes`` the two evaluation kernels take (their per-workgroup LDS histogram); beyond it they raise
+    NotImplementedError and the caller counts with stock ops (``fps.ConfusionMatrix``)."""
+    return int(_hip.lib.hs_eval_max_classes())
+
+
+def _eval_labels(t, name):
+    if not isinstance(t, torch.Tensor) or t.dtype not in _EVAL_DTYPES:
+        raise ValueError(f'{name} must be a uint8 or int64 tensor, got {getattr(t, "dtype", type(t))}')
+    if not t.is_cuda:
+        raise ValueError(f'{name} is on {t.device}: the evaluation kernels run on the GPU (fps.ConfusionMatrix.update counts CPU tensors)')
+    return t if t.is_contiguous() else t.contiguous()
+
+
+def _eval_out(out, shape, device):
+    if out is None:
+        return torch.zeros(shape, dtype=torch.int64, device=device)
+    if not isinstance(out, torch.Tensor) or out.dtype != torch.int64 or tuple(out.shape) != tuple(shape) or out.device != device \
+            or not out.is_contiguous():
+        raise ValueError(f'out must be a contiguous int64 tensor of shape {tuple(shape)} on {device}, got '
+                         f'{getattr(out, "dtype", type(out))} {tuple(getattr(out, "shape", ()))} on {getattr(out, "device", None)}')
+    return out
+
+
+def _eval_classes(num_classes):
+    n = int(num_classes)
+    if n <= 0:
+        raise ValueError(f'num_classes must be positive, got {num_classes}')
+    if n > eval_max_classes():
+        raise NotImplementedError(f'num_classes = {n}: the evaluation kernels cover up to {eval_max_classes()} classes')
+    return n
+
+
+@_on_operand_device
+def upsample_confusion(x, size, target, num_classes, out=None, per_image=False, masks=False):
+    """``upsample_argmax(x, size)`` with every output pixel counted against ``target`` (B, Ho, Wo; uint8 or int64) in the same
+    launch (hs_upsample_confusion_fwd): ``out[t, p] += 1`` for every pixel whose target ``t`` is in [0, num_classes), every
+    other target value ignored (seg_utils.py:15-17).  ``out``: an int64 (n, n) -- ``per_image``: (B, n, n) -- matrix to
+    ACCUMULATE into; None allocates a zeroed one.  Returns ``out``, or ``(out, masks)`` with ``masks=True`` (the uint8 masks,
+    bit-identical to ``upsample_argmax``'s).  Nothing here reads the device: the call is capturable in a HIP graph."""
+    if not isinstance(x, torch.Tensor) or x.dim() != 4:
+        raise ValueError('x must be (B, C, Hi, Wi) logits')
+    b, c, hi, wi = x.shape
+    ho, wo = (int(s) for s in size)
+    target = _eval_labels(target, 'target')
+    if tuple(target.shape) != (b, ho, wo):
+        raise ValueError(f'target has shape {tuple(target.shape)}, expected {(b, ho, wo)}')
+    if target.device != x.device:
+        raise ValueError(f'target is on {target.device}, the logits on {x.device}')
+    if c > int(num_classes):
+        raise ValueError(f'{c} logit channels but num_classes = {num_classes}')
+    if int(num_classes) > 256:
+        raise ValueError('num_classes > 256: the masks are uint8')
+    n = _eval_classes(num_classes)
+    xp = _hip.dev_ptr(x, 'x')
+    out = _eval_out(out, (b, n, n) if per_image else (n, n), x.device)
+    mask = torch.empty(b, ho, wo, device=x.device, dtype=torch.uint8) if masks else None
+    st = _hip.lib.hs_upsample_confusion_fwd(xp, b, c, hi, wi, ho, wo, target.data_ptr(), _EVAL_DTYPES[target.dtype], n,
+                                            1 if per_image else 0, out.data_ptr(), mask.data_ptr() if masks else None,
+                                            _hip.stream_ptr())
+    _hip.check(st, 'hs_upsample_confusion_fwd')
+    return (out, mask) if masks else out
+
+
+@_on_operand_device
+def confusion_update(pred, target, num_classes, out=None, per_image=False):
+    """The same counting from finished predictions (hs_confusion_fwd): ``pred`` and ``target`` uint8 or int64 of one shape;
+    with ``per_image`` their first dimension is the image and ``out`` is (B, n, n).  A prediction outside [0, num_classes) is
+    not counted.  Returns ``out`` (accumulated into when given, else a new zeroed matrix plus this call's counts)."""
+    pred, target = _eval_labels(pred, 'pred'), _eval_labels(target, 'target')
+    if pred.shape != target.shape or pred.numel() == 0:
+        raise ValueError(f'pred {tuple(pred.shape)} and target {tuple(target.shape)} must have one non-empty shape')
+    if pred.device != target.device:
+        raise ValueError(f'pred is on {pred.device}, target on {target.device}')
+    n = _eval_classes(num_classes)
+    b = pred.shape[0] if per_image else 1
+    if per_image and pred.dim() < 2:
+        raise ValueError('per_image needs a leading image dimension')
+    out = _eval_out(out, (b, n, n) if per_image else (n, n), pred.device)
+    st = _hip.lib.hs_confusion_fwd(pred.data_ptr(), _EVAL_DTYPES[pred.dtype], target.data_ptr(), _EVAL_DTYPES[target.dtype], b,
+                                   pred.numel() // b, n, 1 if per_image else 0, out.data_ptr(), _hip.stream_ptr())
+    _hip.check(st, 'hs_confusion_fwd')
+    return out
+
+
 # ------------------------------------------------------------------------------------------
 # small caches keyed on parameter versions (host-side only; used by the fused inference route --
 # tensors that require grad take the hyperseg_amd.autograd route, which folds nothing)

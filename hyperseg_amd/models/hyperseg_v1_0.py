@@ -28,7 +28,7 @@ from torch.nn.modules.utils import _pair
 
 from .. import functional as HF
 from .. import autograd as HA
-from ._common import EpochOnModeSwitch, HyperGenBase, coordinate_grid, per_level, plan_levels, register_coordinate_buffers
+from ._common import EpochOnModeSwitch, HyperGenBase, final_masks_scored, coordinate_grid, per_level, plan_levels, register_coordinate_buffers
 from .layers.meta_conv import MetaConv2d, _apply_epilogue, _require_inference, assemble_block, check_padding_mode
 from .layers.meta_sequential import MetaSequential
 
@@ -646,7 +646,7 @@ class MultiScaleDecoder(EpochOnModeSwitch, nn.Module):
             p = HA.upsample_bilinear(p, x[0].shape[2:])
         return p
 
-    def forward(self, x, s, masks=False):
+    def forward(self, x, s, masks=False, score=None):
         """``masks=True`` (inference only, not in the reference): uint8 argmax masks straight from the final upsample
         kernel instead of logits."""
         if self.training or HA.needs_grad(s, *x, *self.parameters()):
@@ -697,7 +697,7 @@ class MultiScaleDecoder(EpochOnModeSwitch, nn.Module):
             if self.out_fc is not None:
                 p = self.out_fc(p, banks[-1])
             if masks:
-                return HF.upsample_argmax(p, x[0].shape[2:])
+                return HF.upsample_argmax(p, x[0].shape[2:]) if score is None else final_masks_scored(p, x[0].shape[2:], score)
             if p.shape[2:] != x[0].shape[2:]:
                 p = HF.upsample_bilinear(p, x[0].shape[2:], out=getattr(self, 'output_buffer', None))
             return p
@@ -729,7 +729,7 @@ class MultiScaleDecoder(EpochOnModeSwitch, nn.Module):
             if self.out_fc is not None:
                 p = self.out_fc(p, banks[-1])
             if masks:
-                return HF.upsample_argmax(p, x[0].shape[2:])
+                return HF.upsample_argmax(p, x[0].shape[2:]) if score is None else final_masks_scored(p, x[0].shape[2:], score)
             if p.shape[2:] != x[0].shape[2:]:
                 p = HF.upsample_bilinear(p, x[0].shape[2:], out=getattr(self, 'output_buffer', None))
             return p
@@ -795,7 +795,7 @@ class MultiScaleDecoder(EpochOnModeSwitch, nn.Module):
         if self.out_fc is not None:
             p = self.out_fc(p, banks[-1])
         if masks:
-            return HF.upsample_argmax(p, x[0].shape[2:])
+            return HF.upsample_argmax(p, x[0].shape[2:]) if score is None else final_masks_scored(p, x[0].shape[2:], score)
         if p.shape[2:] != x[0].shape[2:]:
             p = HF.upsample_bilinear(p, x[0].shape[2:], out=getattr(self, 'output_buffer', None))
         return p

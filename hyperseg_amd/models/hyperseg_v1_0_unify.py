@@ -17,7 +17,7 @@ from .. import autograd as HA
 from .. import functional as HF
 import numpy as np
 
-from ._common import EpochOnModeSwitch, HyperGenBase, coordinate_grid, per_level, plan_levels, register_coordinate_buffers
+from ._common import EpochOnModeSwitch, HyperGenBase, final_masks_scored, coordinate_grid, per_level, plan_levels, register_coordinate_buffers
 from .hyperseg_v1_0 import (HyperPatch, HyperPatchConv2d, HyperPatchInvertedResidual, HyperPatchNoPadding,  # noqa: F401
                             WeightMapper, _SignalToWeights, divide_feature, make_hyper_patch_conv2d_block,
                             next_multiply)
@@ -139,7 +139,7 @@ class MultiScaleDecoder(EpochOnModeSwitch, nn.Module):
             p = HA.upsample_bilinear(p, x[0].shape[2:])
         return p
 
-    def forward(self, x, s, masks=False):
+    def forward(self, x, s, masks=False, score=None):
         if self.out_fc is not None:
             raise NotImplementedError('with_out_fc=True: the reference itself feeds the raw signal to out_fc here '
                                       '(hyperseg_v1_0_unify.py:252-253); no config uses it')
@@ -188,7 +188,7 @@ class MultiScaleDecoder(EpochOnModeSwitch, nn.Module):
                 w = HF.BankRef(shared.bank[:, r0:r1], shared.shape[0], r1 - r0, shared.grid)
             p = self.level_blocks[level](stage, [w])
         if masks:
-            return HF.upsample_argmax(p, x[0].shape[2:])
+            return HF.upsample_argmax(p, x[0].shape[2:]) if score is None else final_masks_scored(p, x[0].shape[2:], score)
         if p.shape[2:] != x[0].shape[2:]:
             p = HF.upsample_bilinear(p, x[0].shape[2:], out=getattr(self, 'output_buffer', None))
         return p

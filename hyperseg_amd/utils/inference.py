@@ -620,16 +620,24 @@ class GraphedModel(nn.Module):
     gradient, CPU models.  Parameters are read through their storage, so in-place updates are seen; ``load_state_dict``
     on the wrapped model (which rebuilds the fused routes' folded buffers) and ``reset()`` drop the captured graphs."""
 
-    def __init__(self, model, masks=False, warmup=3, clone_output=False, max_graphs=8):
+    def __init__(self, model, masks=False, warmup=3, clone_output=False, max_graphs=8, num_classes=None, per_image=False):
         super().__init__()
         self.model = model
         self.masks, self.warmup, self.clone_output, self.max_graphs = bool(masks), int(warmup), bool(clone_output), int(max_graphs)
-        self._graphs = {}                      # (shape, dtype, device) -> (graph, static_in, static_out, chained-launch owners)
+        self._graphs = {}                      # (shape, dtype, device) -> (graph, static inputs, static_out, chained-launch owners)
         self._replays = 0
         self._hook = model.register_load_state_dict_post_hook(lambda module, incompatible: self.reset())
+        # evaluate(): the classes to count and the graph-owned int64 matrix -- (n, n), or (B, n, n) with per_image (B: the batch
+        # size of the first evaluate call); allocated on the model's device at the first call, never replaced afterwards
+        self.num_classes, self.per_image = (None if num_classes is None else int(num_classes)), bool(per_image)
+        self.confusion = None
 
     def reset(self):
         self._graphs.clear()
+
+    def reset_confusion(self):
+        if self.confusion is not None:
+            self.confusion.zero_()
 
     def _eager(self, x):
         return self.model.segment(x) if self.masks else self.model(x)
@@ -642,33 +650,68 @@ class GraphedModel(nn.Module):
             return False
         return not (torch.is_grad_enabled() and any(q.requires_grad for q in self.model.parameters()))
 
-    def _capture(self, key, x, device):
+    def _capture(self, key, inputs, device, run=None, warm=None):
+        """``inputs``: the tensors to stage (static copies are made); ``run(*static)``: what the graph records (default: the
+        forward); ``warm(*static)``: what the warm-up passes EXECUTE instead (evaluate: the same launches counting into a
+        scratch matrix, so that nothing executed before the first replay reaches the graph's own)."""
+        run = run or self._eager
+        warm = warm or run
         if len(self._graphs) >= self.max_graphs:
             self._graphs.pop(next(iter(self._graphs)))           # oldest shape goes
         with torch.cuda.device(device), torch.no_grad():
-            static_in = torch.empty(x.shape, dtype=x.dtype, device=device)
-            static_in.copy_(x)
+            static = []
+            for x in inputs:
+                static.append(torch.empty(x.shape, dtype=x.dtype, device=device))
+                static[-1].copy_(x)
             main = torch.cuda.current_stream(device)
             side = torch.cuda.Stream(device)
             side.wait_stream(main)
             with torch.cuda.stream(side):
                 for _ in range(max(1, self.warmup)):
-                    self._eager(static_in)
+                    warm(*static)
             main.wait_stream(side)
             torch.cuda.synchronize(device)
             graph = torch.cuda.CUDAGraph()
             from .. import functional as HF
             chained = HF.CHAIN_LAUNCHES_CAPTURED[0]
             with torch.cuda.graph(graph):
-                static_out = self._eager(static_in)
+                static_out = run(*static)
             # a graph that contains the decoder's chained launch (hs_decoder_chain_fwd: its whole grid must be resident at once) is
             # replayed behind functional.ChainGate: never beside another chained launch on this device, whatever stream that one is on
             chains = [m._k1_chain for m in self.model.modules() if getattr(m, '_k1_chain', None) is not None] \
                 if HF.CHAIN_LAUNCHES_CAPTURED[0] != chained else []
-        self._graphs[key] = (graph, static_in, static_out, chains)
+        self._graphs[key] = (graph, static, static_out, chains)
         return self._graphs[key]
 
     accepts_host_input = True                  # hyperseg_amd.fps.measure_fps hands the pinned host batch over as it is
+    owns_confusion = True                      # ... and reads evaluate()'s counts from ``confusion``
+
+    def _replay(self, entry, inputs, device):
+        """Stage ``inputs`` into the entry's static buffers and replay its graph on ``device``'s current stream."""
+        graph, static, static_out, chains = entry
+
+        def go():
+            for dst, src in zip(static, inputs):
+                dst.copy_(src, non_blocking=True)
+            graph.replay()
+
+        with torch.cuda.device(device):        # the replay and the input copy go to the MODEL's device and its current stream
+            if chains:
+                from .. import functional as HF
+                for ch in chains:              # pinned mirrors of the kernel's error word: a frame built on an abandoned wait raises
+                    ch.check_errors()
+                gate = HF.ChainGate.of(device)
+                with gate.lock:
+                    cur = gate.enter(device)
+                    go()
+                    gate.leave(cur)
+                self._replays += 1
+                if self._replays % HF.K1Chain.POLL_EVERY == 0:
+                    for ch in chains:
+                        ch.request_error_copy(device)
+            else:
+                go()
+            return static_out.clone() if self.clone_output else static_out
 
     def forward(self, x):
         p = next(self.model.parameters(), None)
@@ -680,24 +723,59 @@ class GraphedModel(nn.Module):
         key = (tuple(x.shape), x.dtype, device)
         entry = self._graphs.get(key)
         if entry is None:
-            entry = self._capture(key, x, device)
-        graph, static_in, static_out, chains = entry
-        with torch.cuda.device(device):        # the replay and the input copy go to the MODEL's device and its current stream
-            if chains:
-                from .. import functional as HF
-                for ch in chains:              # pinned mirrors of the kernel's error word: a frame built on an abandoned wait raises
-                    ch.check_errors()
-                gate = HF.ChainGate.of(device)
-                with gate.lock:
-                    cur = gate.enter(device)
-                    static_in.copy_(x, non_blocking=True)
-                    graph.replay()
-                    gate.leave(cur)
-                self._replays += 1
-                if self._replays % HF.K1Chain.POLL_EVERY == 0:
-                    for ch in chains:
-                        ch.request_error_copy(device)
+            entry = self._capture(key, [x], device)
+        return self._replay(entry, [x], device)
+
+    def _confusion_on(self, device, batch):
+        n = self.num_classes
+        if n is None:
+            raise ValueError('GraphedModel.evaluate needs num_classes: GraphedModel(model, num_classes=n)')
+        shape = (batch, n, n) if self.per_image else (n, n)
+        if self.confusion is None:
+            self.confusion = torch.zeros(shape, dtype=torch.int64, device=device)
+        elif tuple(self.confusion.shape) != shape or self.confusion.device != device:
+            raise ValueError(f'the graph-owned matrix is {tuple(self.confusion.shape)} on {self.confusion.device}; this call needs '
+                             f'{shape} on {device} (per_image fixes the batch size at the first call)')
+        return self.confusion
+
+    @torch.no_grad()
+    def evaluate(self, x, target):
+        """One replay per frame that also scores it: returns the uint8 masks (the graph's static output, as ``forward``'s) and
+        adds the frame's (target, prediction) counts to ``self.confusion`` -- int64 (n, n), or (B, n, n) with
+        ``per_image=True`` at construction; ``reset_confusion()`` zeroes it.  ``x`` and ``target`` (B, H, W; uint8 or int64) may
+        live on the device or in (pinned) host memory: both are staged into static buffers of the graph.  The graph is the
+        forward's chain of launches with the last one replaced by ``functional.upsample_confusion`` -- a single chain, keyed
+        apart from the ``forward`` graphs.  What the graph cannot serve (``forward``'s list, plus a target of another size or
+        type, or more classes than the kernel covers) is scored eagerly by ``model.evaluate`` into the same matrix."""
+        from .. import functional as HF
+        from ..fps import ConfusionMatrix
+        p = next(self.model.parameters(), None)
+        n = self.num_classes
+        graphable = (self._graphable(x) and isinstance(target, torch.Tensor) and target.dtype in (torch.uint8, torch.int64)
+                     and target.dim() == 3 and x.dim() == 4 and tuple(target.shape) == (x.shape[0],) + tuple(x.shape[2:])
+                     and n is not None and n <= min(256, HF.eval_max_classes()) and hasattr(self.model, 'process_single_tensor'))
+        if not graphable:
+            if p is not None and p.is_cuda:
+                x = [t.to(p.device, non_blocking=True) for t in x] if isinstance(x, (list, tuple)) else x.to(p.device, non_blocking=True)
+                target = target.to(p.device, non_blocking=True)
+            device = target.device
+            cm = ConfusionMatrix(n)
+            if self.per_image:
+                masks = self.model.evaluate(x, target, cm, per_image=True)
+                self._confusion_on(device, target.shape[0]).add_(cm.per_image[-1])
             else:
-                static_in.copy_(x, non_blocking=True)
-                graph.replay()
-            return static_out.clone() if self.clone_output else static_out
+                cm.mat = self._confusion_on(device, target.shape[0])
+                masks = self.model.evaluate(x, target, cm)
+            return masks
+        device = p.device
+        confusion = self._confusion_on(device, x.shape[0])
+        key = ('evaluate', tuple(x.shape), x.dtype, target.dtype, device)
+        entry = self._graphs.get(key)
+        if entry is None:
+            scratch = torch.zeros_like(confusion)                # the warm-up passes execute: their counts go here
+
+            def run(xs, ts, out=confusion):
+                return self.model.process_single_tensor(xs, masks=True, score=(ts, n, out, self.per_image))
+
+            entry = self._capture(key, [x, target], device, run=run, warm=lambda xs, ts: run(xs, ts, scratch))
+        return self._replay(entry, [x, target], device)

@@ -313,6 +313,26 @@ int hs_upsample_bilinear_f16_fwd(const void* x, int32_t batch, int32_t channels,
 int hs_upsample_argmax_fwd(const float* x, int32_t batch, int32_t channels, int32_t Hi, int32_t Wi,
                            int32_t Ho, int32_t Wo, uint8_t* mask, void* stream);
 
+/* On-device evaluation (csrc/hs_eval.hip): the (target, prediction) confusion matrix of the reference's evaluation loop
+ * (hyperseg/utils/seg_utils.py:5-36: mat[t][p] += 1 for every pixel whose target t is in [0, num_classes); every other target
+ * value -- 255, negatives -- is ignored).  Both entries ACCUMULATE into `confusion` (int64, (n, n), or (batch, n, n) with
+ * per_image != 0: image b's counts in slab b -- test.py:174-175 without a host read per image); they never zero it.  Integer
+ * sums: the result does not depend on arrival order.  Label storage: HS_EVAL_U8 or HS_EVAL_I64 (what the reference's loaders
+ * produce).  num_classes <= hs_eval_max_classes() (the per-workgroup LDS histogram; >= 64), else HS_ERR_UNSUPPORTED and the
+ * caller counts some other way.
+ *   hs_upsample_confusion_fwd: hs_upsample_argmax_fwd (same taps, same arg-max rule, the identity resize included) with every
+ *     output pixel counted against target (batch, Ho, Wo) in the same launch.  mask (optional): the uint8 masks, bit-identical
+ *     to hs_upsample_argmax_fwd's.  channels <= num_classes <= 256, else HS_ERR_BAD_ARG.
+ *   hs_confusion_fwd: the same counting from finished predictions, pred and target (batch, elements); a prediction outside
+ *     [0, num_classes) is not counted. */
+typedef enum { HS_EVAL_U8 = 0, HS_EVAL_I64 = 1 } hs_eval_dtype;
+int hs_eval_max_classes(void);
+int hs_upsample_confusion_fwd(const float* x, int32_t batch, int32_t channels, int32_t Hi, int32_t Wi, int32_t Ho, int32_t Wo,
+                              const void* target, int32_t target_dtype, int32_t num_classes, int32_t per_image,
+                              int64_t* confusion, uint8_t* mask, void* stream);
+int hs_confusion_fwd(const void* pred, int32_t pred_dtype, const void* target, int32_t target_dtype, int32_t batch,
+                     int64_t elements, int32_t num_classes, int32_t per_image, int64_t* confusion, void* stream);
+
 /* Backward of hs_patch_conv_fwd (plain input x, no fused prologue / epilogue), fp32 -- SURVEY.md Appendix E.
  * The reference has no backward of its own (autograd over F.pad/unfold/grouped conv2d/fold: meta_patch.py:35-57);
  * these are the adjoints the training path (BASELINE config 5) needs:
