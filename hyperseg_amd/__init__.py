@@ -1,0 +1,9 @@
+"""HyperSeg on the AMD Instinct MI355X: PyTorch-ROCm modules over hand-written HIP kernels."""
+
+
+def __getattr__(name):
+    # exported lazily: importing the package must not import torch-heavy submodules (or the HIP library) as a side effect
+    if name == 'InputNorm':
+        from .utils.inference import InputNorm
+        return InputNorm
+    raise AttributeError(f'module {__name__!r} has no attribute {name!r}')

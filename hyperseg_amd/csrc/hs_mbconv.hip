@@ -255,10 +255,10 @@ int try_launch_mbconv_lean(const float* x, int batch, int c_in, int H, int W, co
                            const float* scale1, const float* shift1, float* y, float* pool, int oth, int tiles_y, int tiles_x,
                            int chunks_per_wg, int ngroups, hipStream_t stream);                 // hs_mbconv_lean.hip
 
-int try_launch_stem_dw_lean(const float* x, int batch, int sH, int sW, const float* w28, int c_mid, const float* scale0, const float* shift0,
-                            int spad_t, int spad_l, int Hs, int Ws, const float* w_dw, int k, int pad_t, int pad_l, const float* scale1,
-                            const float* shift1, float* y, float* pool, int oth, int tiles_y, int tiles_x, int chunks_per_wg, int ngroups,
-                            hipStream_t stream);                                               // hs_mbconv_lean.hip
+int try_launch_stem_dw_lean(const void* x, const float* table, int layout, int batch, int sH, int sW, const float* w28, int c_mid,
+                            const float* scale0, const float* shift0, int spad_t, int spad_l, int Hs, int Ws, const float* w_dw, int k,
+                            int pad_t, int pad_l, const float* scale1, const float* shift1, float* y, float* pool, int oth, int tiles_y,
+                            int tiles_x, int chunks_per_wg, int ngroups, hipStream_t stream);   // hs_mbconv_lean.hip
 
 }  // namespace hs
 
@@ -366,8 +366,26 @@ extern "C" int hs_stem_dw_fwd(const float* x, int32_t batch, int32_t H, int32_t 
     if (batch <= 0 || c_mid <= 0 || H <= 0 || W <= 0 || Hs <= 0 || Ws <= 0 || pad_t < 0 || pad_l < 0) return HS_ERR_BAD_ARG;
     int tiles_y, tiles_x, cpw, ngroups;
     mbx_grid(batch, c_mid, 1, Hs, Ws, tiles_y, tiles_x, cpw, ngroups);
-    const int st = try_launch_stem_dw_lean(x, batch, H, W, w_stem28, c_mid, scale0, shift0, stem_pad_t, stem_pad_l, Hs, Ws, w_dw, k, pad_t,
-                                           pad_l, scale1, shift1, y, pool_partial, mbx_oth(1), tiles_y, tiles_x, cpw, ngroups,
+    const int st = try_launch_stem_dw_lean(x, nullptr, 0, batch, H, W, w_stem28, c_mid, scale0, shift0, stem_pad_t, stem_pad_l, Hs, Ws, w_dw, k,
+                                           pad_t, pad_l, scale1, shift1, y, pool_partial, mbx_oth(1), tiles_y, tiles_x, cpw, ngroups,
+                                           (hipStream_t)stream);
+    return st == 1 ? HS_ERR_UNSUPPORTED : st;
+}
+
+// hs_stem_dw_fwd reading the uint8 frame itself: x (B,H,W,3) for HS_LAYOUT_HWC / (B,3,H,W) for HS_LAYOUT_CHW, table = the (3, 256)
+// dequantisation table (hs_ingest.h).  Same grid, same arithmetic after the lookup: y and pool_partial are bit-identical to hs_stem_dw_fwd on
+// hs_image_ingest_fwd's output; HS_ERR_UNSUPPORTED exactly where hs_stem_dw_fwd returns it.
+extern "C" int hs_stem_dw_u8_fwd(const uint8_t* x, int32_t layout, const float* table, int32_t batch, int32_t H, int32_t W,
+                                 const float* w_stem28, int32_t c_mid, const float* scale0, const float* shift0, int32_t stem_pad_t,
+                                 int32_t stem_pad_l, int32_t Hs, int32_t Ws, const float* w_dw, int32_t k, int32_t pad_t, int32_t pad_l,
+                                 const float* scale1, const float* shift1, float* y, float* pool_partial, void* stream) {
+    if (!x || !table || !w_stem28 || !scale0 || !shift0 || !w_dw || !scale1 || !shift1 || !y) return HS_ERR_BAD_ARG;
+    if (batch <= 0 || c_mid <= 0 || H <= 0 || W <= 0 || Hs <= 0 || Ws <= 0 || pad_t < 0 || pad_l < 0) return HS_ERR_BAD_ARG;
+    if (layout != HS_LAYOUT_HWC && layout != HS_LAYOUT_CHW) return HS_ERR_BAD_ARG;
+    int tiles_y, tiles_x, cpw, ngroups;
+    mbx_grid(batch, c_mid, 1, Hs, Ws, tiles_y, tiles_x, cpw, ngroups);
+    const int st = try_launch_stem_dw_lean(x, table, layout, batch, H, W, w_stem28, c_mid, scale0, shift0, stem_pad_t, stem_pad_l, Hs, Ws, w_dw,
+                                           k, pad_t, pad_l, scale1, shift1, y, pool_partial, mbx_oth(1), tiles_y, tiles_x, cpw, ngroups,
                                            (hipStream_t)stream);
     return st == 1 ? HS_ERR_UNSUPPORTED : st;
 }

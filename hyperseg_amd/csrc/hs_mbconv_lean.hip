@@ -9,7 +9,9 @@
 //   * no channel clamps / masks (the host routes other shapes to the general kernel); positions outside the image still become
 //     exact zeros in h1 (the depthwise conv pads the ACTIVATION);
 //   * the block decode is scalar, with host-made magic numbers for the two divisions.
+#include <type_traits>
 #include "hs_common.h"
+#include "hs_ingest.h"
 
 #ifndef HS_MBL_STAGE
 #define HS_MBL_STAGE 1      // output stores through a per-wave LDS staging area (dev A/B knob: tools/build_variants.py mbl_nostage)
@@ -26,6 +28,12 @@ struct MblArgs {
     int Cmid, H, W, Ho, Wo, pad_t, pad_l, tiles_y, tiles_x, chunks_per_wg, ngroups;
     unsigned m_ngroups, m_tiles_x, m_tiles_y;      // 2^32 / d + 1 (0: d == 1)
     int sH, sW, spad_t, spad_l;                    // STEM form: the raw image x (B, 3, sH, sW) and the stem conv's (top, left) padding
+};
+
+// STEM form reading the uint8 frame itself (hs_stem_dw_u8_fwd): a.x points at bytes, `layout` says where a value sits
+// (0: (B, H, W, 3), 1: (B, 3, H, W)), `table` is the (3, 256) dequantisation table of hs_ingest.h
+struct MblArgsU8 : MblArgs {
+    const float* __restrict__ table; int layout;
 };
 
 template <int K, int S, int OTH, int OTW> struct MblGeom {
@@ -58,6 +66,7 @@ inline unsigned mbl_magic(unsigned d) { return d <= 1 ? 0u : (unsigned)((1ull <<
 __device__ __forceinline__ float mbl_ld(const float* __restrict__ base, unsigned byte_off) {
     return *reinterpret_cast<const float*>(reinterpret_cast<const char*>(base) + (size_t)byte_off);
 }
+__device__ __forceinline__ unsigned mbl_ld8(const unsigned char* __restrict__ base, unsigned byte_off) { return base[(size_t)byte_off]; }
 __device__ __forceinline__ f32x4 mbl_ld4(const float* __restrict__ base, unsigned byte_off) {
     return *reinterpret_cast<const f32x4*>(reinterpret_cast<const char*>(base) + (size_t)byte_off);
 }
@@ -67,12 +76,17 @@ __device__ __forceinline__ f32x4 mbl_ld4(const float* __restrict__ base, unsigne
 // K = 27 (+ 1 zero column: w_e is the stem weight flattened to (Cmid, 27) and padded to 28), its B operand gathered from the image
 // through the 3 x 3 / stride-2 window, k = 9 c + 3 ky + kx.  The stem's output map (16.8 MB at 1024 x 512: written by one launch, read
 // back by the next) never exists; a.H / a.W are ITS size (what the depthwise conv pads and tiles), a.sH / a.sW the image's.
-template <int K, int S, int OTH, int OTW, int KS, bool STEM = false>
+// U8 (STEM only): the image is the uint8 frame as the decoder / camera delivered it; the same 27-tap gather loads one BYTE per tap and lane
+// (offset c plane + y W + x for 'chw', (y W + x) 3 + c for 'hwc') and looks it up in the LDS copy of the dequantisation table -- the float
+// image of ToTensor + Normalize is never written.  The zero-padding mask follows the lookup: padding is zero in the NORMALISED domain, as in
+// the reference (the stem pads what Normalize produced).  Everything after the B fragments is the float form's code.
+template <int K, int S, int OTH, int OTW, int KS, bool STEM = false, bool U8 = false>
 __global__ __launch_bounds__(256, 2)
-void mbconv_lean_kernel(MblArgs a) {
+void mbconv_lean_kernel(std::conditional_t<U8, MblArgsU8, MblArgs> a) {
     using G = MblGeom<K, S, OTH, OTW>;
     constexpr int Cin = 4 * KS;
     static_assert(!STEM || KS == 7, "the stem's K = 27 -> 28");
+    static_assert(!U8 || STEM, "only the stem reads the uint8 frame");
     extern __shared__ __attribute__((aligned(16))) float h1[];                 // [16][H1P]
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -87,7 +101,14 @@ void mbconv_lean_kernel(MblArgs a) {
     const int iy0 = oy0 * S - a.pad_t, ix0 = ox0 * S - a.pad_l;
     const int Cmid = a.Cmid, H = a.H, W = a.W;
     const unsigned plane = STEM ? (unsigned)a.sH * (unsigned)a.sW : (unsigned)H * (unsigned)W;
-    const float* __restrict__ xb = a.x + (size_t)b * (STEM ? 3 : Cin) * plane;
+    const float* __restrict__ xb = a.x + (U8 ? (size_t)0 : (size_t)b * (STEM ? 3 : Cin) * plane);
+    const unsigned char* __restrict__ xb8 = reinterpret_cast<const unsigned char*>(a.x) + (U8 ? (size_t)b * 3 * plane : (size_t)0);
+    float* tab = h1 + G::LDS_FLOATS;                                           // U8: the table, behind the tile and the staging area
+    int pmul = 1;                                                              // U8: bytes from one pixel to the next
+    if constexpr (U8) {
+        ingest_table_to_lds(a.table, tab, tid);
+        pmul = a.layout == 0 ? 3 : 1;
+    }
 
     // dw role of this thread: hidden channel hh of the chunk, output row / row segment
     const int hh = tid >> 4, u = tid & 15;
@@ -134,14 +155,20 @@ void mbconv_lean_kernel(MblArgs a) {
     float bf[G::J][KS];
     int h1off[G::J];                   // LDS offset of this lane's position (-1: none); bit 30: inside the image
     // STEM: this lane's K index of k-step ks is k = 4 ks + lk = 9 c + 3 ky + kx (k = 27: the zero column, any valid tap)
-    int koff[STEM ? KS : 1], kyx[STEM ? KS : 1];
+    int koff[STEM ? KS : 1], kyx[STEM ? KS : 1];      // (U8: the tap's channel in kyx's bits 4-5)
+    unsigned bu[U8 ? G::J : 1][U8 ? KS : 1];          // U8: the gathered bytes, looked up once every load is out
     unsigned smask[STEM ? G::J : 1];
     bool stem_inside = true;
     if constexpr (STEM) {
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) {
             const int k = min(4 * ks + lk, 26), c = k / 9, r = k - 9 * c, ky = r / 3, kx = r - 3 * ky;
-            koff[ks] = c * (int)plane + ky * a.sW + kx; kyx[ks] = 4 * ky + kx;
+            if constexpr (U8) {
+                koff[ks] = a.layout == 0 ? (ky * a.sW + kx) * 3 + c : c * (int)plane + ky * a.sW + kx;
+                kyx[ks] = (4 * ky + kx) | (c << 4);
+            } else {
+                koff[ks] = c * (int)plane + ky * a.sW + kx; kyx[ks] = 4 * ky + kx;
+            }
         }
 #pragma unroll
         for (int jt = 0; jt < G::J; ++jt) smask[jt] = 0u;
@@ -165,21 +192,33 @@ void mbconv_lean_kernel(MblArgs a) {
             // window origin of this stem-output position in the image (positions outside the stem's map: any valid one)
             const int by = 2 * min(max(yy, 0), H - 1) - a.spad_t, bx = 2 * min(max(xx, 0), W - 1) - a.spad_l;
             if (stem_inside) {                                                 // uniform: no tap of this tile leaves the image
-                const int base = by * a.sW + bx;
+                const int base = (by * a.sW + bx) * pmul;
 #pragma unroll
-                for (int ks = 0; ks < KS; ++ks) bf[jt][ks] = mbl_ld(xb, (unsigned)(base + koff[ks]) << 2);
+                for (int ks = 0; ks < KS; ++ks) {
+                    if constexpr (U8) bu[jt][ks] = mbl_ld8(xb8, (unsigned)(base + koff[ks]));
+                    else bf[jt][ks] = mbl_ld(xb, (unsigned)(base + koff[ks]) << 2);
+                }
             } else {
 #pragma unroll
                 for (int ks = 0; ks < KS; ++ks) {
-                    const int iy = by + kyx[ks] / 4, ix = bx + (kyx[ks] & 3);
-                    const int e = koff[ks] - (kyx[ks] / 4) * a.sW - (kyx[ks] & 3)            // c * plane
-                                  + min(max(iy, 0), a.sH - 1) * a.sW + min(max(ix, 0), a.sW - 1);
-                    bf[jt][ks] = mbl_ld(xb, (unsigned)e << 2);
+                    const int t = U8 ? (kyx[ks] & 15) : kyx[ks], ky = t / 4, kx = t & 3;
+                    const int iy = by + ky, ix = bx + kx;
+                    const int e = koff[ks] - (ky * a.sW + kx) * pmul                         // the channel's offset: c * plane, or c ('hwc')
+                                  + (min(max(iy, 0), a.sH - 1) * a.sW + min(max(ix, 0), a.sW - 1)) * pmul;
+                    if constexpr (U8) bu[jt][ks] = mbl_ld8(xb8, (unsigned)e);
+                    else bf[jt][ks] = mbl_ld(xb, (unsigned)e << 2);
                     smask[jt] |= ((unsigned)iy < (unsigned)a.sH && (unsigned)ix < (unsigned)a.sW ? 1u : 0u) << ks;
                 }
             }
         }
         h1off[jt] = ok ? ((pu * G::RS + pv) | (in ? (1 << 30) : 0)) : -1;
+    }
+    if constexpr (U8) {
+        __syncthreads();                                                       // the table is in LDS (and every byte load is out)
+#pragma unroll
+        for (int jt = 0; jt < G::J; ++jt)
+#pragma unroll
+            for (int ks = 0; ks < KS; ++ks) bf[jt][ks] = ingest_dequant(tab, kyx[ks] >> 4, bu[jt][ks]);
     }
     if constexpr (STEM) {
         if (!stem_inside) {                                                    // zero padding of the image: after every load is out
@@ -309,15 +348,15 @@ void mbconv_lean_kernel(MblArgs a) {
 #undef HS_MBL_BARRIER
 }
 
-template <int K, int S, int OTH, int OTW, int KS, bool STEM = false>
-static int launch_mbl(MblArgs& a, int batch, hipStream_t stream) {
+template <int K, int S, int OTH, int OTW, int KS, bool STEM = false, bool U8 = false>
+static int launch_mbl(std::conditional_t<U8, MblArgsU8, MblArgs>& a, int batch, hipStream_t stream) {
     using G = MblGeom<K, S, OTH, OTW>;
     static const int lds_pad = [] { const char* e = getenv("HS_MBX_LDS_PAD"); return e ? atoi(e) : 0; }();      // dev knob: fewer co-resident workgroups (KB)
-    const size_t lds = (size_t)G::LDS_FLOATS * sizeof(float) + (size_t)lds_pad * 1024;
+    const size_t lds = (size_t)(G::LDS_FLOATS + (U8 ? INGEST_TABLE_FLOATS : 0)) * sizeof(float) + (size_t)lds_pad * 1024;
     const size_t blocks = (size_t)batch * a.tiles_y * a.tiles_x * a.ngroups;
     if (blocks > 0x7fffffffu) return 1;
     a.m_ngroups = mbl_magic((unsigned)a.ngroups); a.m_tiles_x = mbl_magic((unsigned)a.tiles_x); a.m_tiles_y = mbl_magic((unsigned)a.tiles_y);
-    hipLaunchKernelGGL((mbconv_lean_kernel<K, S, OTH, OTW, KS, STEM>), dim3((unsigned)blocks), dim3(256), lds, stream, a);
+    hipLaunchKernelGGL((mbconv_lean_kernel<K, S, OTH, OTW, KS, STEM, U8>), dim3((unsigned)blocks), dim3(256), lds, stream, a);
     return launch_status();
 }
 
@@ -357,21 +396,29 @@ int try_launch_mbconv_lean(const float* x, int batch, int c_in, int H, int W, co
 
 // The stem form: x = the image (B, 3, sH, sW), w28 = the stem weight (c_mid, 27) padded to 28 columns, (Hs, Ws) = the stem's output map
 // = the depthwise conv's input and (stride 1, "SAME") output size.  Returns 1 when the shape is not covered.
-int try_launch_stem_dw_lean(const float* x, int batch, int sH, int sW, const float* w28, int c_mid, const float* scale0, const float* shift0,
-                            int spad_t, int spad_l, int Hs, int Ws, const float* w_dw, int k, int pad_t, int pad_l, const float* scale1,
-                            const float* shift1, float* y, float* pool, int oth, int tiles_y, int tiles_x, int chunks_per_wg, int ngroups,
-                            hipStream_t stream) {
+// table != nullptr: x is the uint8 frame in `layout` (MblArgsU8) -- covered exactly where the float form is.
+int try_launch_stem_dw_lean(const void* x, const float* table, int layout, int batch, int sH, int sW, const float* w28, int c_mid,
+                            const float* scale0, const float* shift0, int spad_t, int spad_l, int Hs, int Ws, const float* w_dw, int k,
+                            int pad_t, int pad_l, const float* scale1, const float* shift1, float* y, float* pool, int oth, int tiles_y,
+                            int tiles_x, int chunks_per_wg, int ngroups, hipStream_t stream) {
     if (k != 3 || (c_mid & 15) != 0 || Ws % 16 != 0 || spad_t < 0 || spad_l < 0) return 1;
     if ((size_t)3 * sH * sW >= (1u << 29)) return 1;                          // 32-bit byte offsets, with room for the clamped windows
     if (2 * (Hs - 1) - spad_t >= sH || 2 * (Ws - 1) - spad_l >= sW) return 1;  // every output's window starts inside the image
     if ((((size_t)y | (size_t)scale0 | (size_t)shift0) & 15) != 0) return 1;
-    MblArgs a;
-    a.x = x; a.w_e = w28; a.s0 = scale0; a.b0 = shift0; a.w_dw = w_dw; a.s1 = scale1; a.b1 = shift1; a.y = y; a.pool = pool;
+    MblArgsU8 a;
+    a.x = static_cast<const float*>(x); a.w_e = w28; a.s0 = scale0; a.b0 = shift0; a.w_dw = w_dw; a.s1 = scale1; a.b1 = shift1; a.y = y; a.pool = pool;
     a.Cmid = c_mid; a.H = Hs; a.W = Ws; a.Ho = Hs; a.Wo = Ws; a.pad_t = pad_t; a.pad_l = pad_l;
     a.tiles_y = tiles_y; a.tiles_x = tiles_x; a.chunks_per_wg = chunks_per_wg; a.ngroups = ngroups;
     a.sH = sH; a.sW = sW; a.spad_t = spad_t; a.spad_l = spad_l;
-    if (oth == 16) return launch_mbl<3, 1, 16, 16, 7, true>(a, batch, stream);
-    if (oth == 8) return launch_mbl<3, 1, 8, 16, 7, true>(a, batch, stream);
+    a.table = table; a.layout = layout;
+    if (table != nullptr) {
+        if (oth == 16) return launch_mbl<3, 1, 16, 16, 7, true, true>(a, batch, stream);
+        if (oth == 8) return launch_mbl<3, 1, 8, 16, 7, true, true>(a, batch, stream);
+        return 1;
+    }
+    MblArgs& f = a;
+    if (oth == 16) return launch_mbl<3, 1, 16, 16, 7, true>(f, batch, stream);
+    if (oth == 8) return launch_mbl<3, 1, 8, 16, 7, true>(f, batch, stream);
     return 1;
 }
 

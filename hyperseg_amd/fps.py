@@ -11,6 +11,10 @@ Reproduces the reference's protocol on synthetic frames (no dataset, checkpoint 
 ``torch.cuda.synchronize()`` is guarded so that the plumbing also runs on a CPU-only box (with a CPU-capable model).
 
     python -m hyperseg_amd.fps --config hyperseg-m --iterations 200 [--prepare] [--graph] [--remove-bn] [--batch-size 1]
+                               [--uint8 [--layout hwc|chw]]
+
+``--uint8`` feeds uint8 frames (what a decoder or camera delivers) to a model with the default ``InputNorm`` attached: the
+host-to-device copy moves one byte per value and ToTensor + Normalize run on the device (``utils.inference.InputNorm``).
 
 ``bench.py`` is the judged benchmark (resident input, HIP-graph replay); this harness includes the H2D copy and the
 per-frame synchronisation exactly like the reference's, and by default its eager launches too, so its number is lower.
@@ -202,11 +206,17 @@ def measure_fps(model, batches, device, num_classes, passes=2, fused_metrics=Fal
     return result
 
 
-def synthetic_batches(n, batch_size, size, num_classes, device, seed=0):
+def synthetic_batches(n, batch_size, size, num_classes, device, seed=0, uint8=False, layout='hwc'):
+    """``uint8``: uint8 frames in ``layout`` ('hwc': (B, H, W, 3), 'chw': (B, 3, H, W)) from the same generator seed instead of
+    float32 (B, 3, H, W) images."""
     g = torch.Generator().manual_seed(seed)
     out = []
     for _ in range(n):
-        x = torch.rand(batch_size, 3, *size, generator=g)
+        if uint8:
+            shape = (batch_size,) + tuple(size) + (3,) if layout == 'hwc' else (batch_size, 3) + tuple(size)
+            x = torch.randint(0, 256, shape, generator=g, dtype=torch.uint8)
+        else:
+            x = torch.rand(batch_size, 3, *size, generator=g)
         t = torch.randint(0, num_classes, (batch_size,) + tuple(size), generator=g)
         out.append((x.pin_memory() if device.type == 'cuda' else x, t))
     return out
@@ -226,6 +236,10 @@ def main(argv=None):
     ap.add_argument('--fused-metrics', action='store_true',
                     help="score every frame inside the forward's last launch (model.evaluate): the scoring then falls INSIDE the timed "
                          "region, which the reference's protocol keeps outside it")
+    ap.add_argument('--uint8', action='store_true',
+                    help='uint8 frames with the default InputNorm attached to the model: normalised on the device, a quarter of the '
+                         'bytes over the host link')
+    ap.add_argument('--layout', choices=('hwc', 'chw'), default='hwc', help='layout of the --uint8 frames')
     ap.add_argument('-t', '--trace', action='store_true',
                     help="the reference's torch.jit.trace switch (test_fps.py:49-50, 150-152).  The mirror's modules call the C ABI through "
                          "ctypes, which the tracer cannot see, so a traced module would be wrong; the purpose of tracing there -- no Python / "
@@ -253,6 +267,9 @@ def main(argv=None):
     elif args.prepare:
         from .utils.inference import prepare_for_inference
         prepare_for_inference(model, fold_bn=False, fused_depthwise=True)
+    if args.uint8:
+        from .utils.inference import InputNorm
+        model.input_norm = InputNorm(layout=args.layout)
     model = model.to(device)
     if args.gpus and len(args.gpus) > 1 and device.type == 'cuda':
         if args.graph:
@@ -262,9 +279,12 @@ def main(argv=None):
         from .utils.inference import GraphedModel
         model = GraphedModel(model, num_classes=spec['num_classes'] if args.fused_metrics else None)
     bs = args.batch_size or spec['batch']
-    uniq = synthetic_batches(min(args.distinct, args.iterations), bs, spec['size'], spec['num_classes'], device)
+    uniq = synthetic_batches(min(args.distinct, args.iterations), bs, spec['size'], spec['num_classes'], device,
+                             uint8=args.uint8, layout=args.layout)
     batches = [uniq[i % len(uniq)] for i in range(args.iterations)]
     res = measure_fps(model, batches, device, spec['num_classes'], fused_metrics=args.fused_metrics)
+    frame = uniq[0][0]
+    res.update(input_dtype=str(frame.dtype).replace('torch.', ''), input_bytes_per_frame=frame[0].numel() * frame.element_size())
     res.update(config=args.config, batch_size=bs, size=list(spec['size']), device=str(device), remove_bn=args.remove_bn,
                prepared=bool(args.prepare and not args.remove_bn), graph=bool(args.graph and device.type == 'cuda'),
                protocol='test_fps.py: per-iteration sync + H2D + ' + ('HIP-graph replay' if args.graph else 'eager forward'))

@@ -38,7 +38,7 @@ def _round_up(n, m):
 def _device_of(a):
     if isinstance(a, torch.Tensor):
         return a.device
-    if isinstance(a, (StageInput, BankRef, SignalRef)):
+    if isinstance(a, (StageInput, BankRef, SignalRef, U8Frame)):
         return a.device
     return None
 
@@ -55,6 +55,43 @@ def _on_operand_device(fn):
         with torch.cuda.device(dev):
             return fn(*args, **kwargs)
     return wrapper
+
+
+class U8Frame:
+    """A batch of uint8 frames together with the ``utils.inference.InputNorm`` that describes them, standing where the float image
+    (B, 3, H, W) would: ``shape`` is that image's.  The prepared encoder's stem + depthwise launch reads the bytes themselves
+    (:func:`stem_dw`); ``float_image()`` is the one :func:`image_ingest` launch for whoever needs the float image after all (made at
+    most once, and remembered, so the caller can tell afterwards whether it exists)."""
+
+    requires_grad = False
+    dtype = torch.uint8
+
+    def __init__(self, data, norm):
+        b, h, w = norm.frame_size(data)
+        self.data, self.norm = data.contiguous(), norm
+        self.shape = torch.Size((b, 3, h, w))
+        self.image = None
+
+    @property
+    def device(self):
+        return self.data.device
+
+    @property
+    def is_cuda(self):
+        return self.data.is_cuda
+
+    def contiguous(self):
+        return self
+
+    def float_image(self):
+        if self.image is None:
+            self.image = image_ingest(self.data, self.norm)
+        return self.image
+
+    def size_carrier(self):
+        """The float image if it was made, else a meta tensor of its shape: what the decoder reads the output size from when no
+        level consumes the image."""
+        return self.image if self.image is not None else torch.empty(self.shape, dtype=torch.float32, device='meta')
 
 
 class StageInput:
@@ -990,17 +1027,53 @@ def stem_conv_bn_swish(x, weight, pad_top, pad_left, out_size, scale, shift):
     return y
 
 
+# uint8 frames into the stem + depthwise launch itself wherever the model allows (models/_common.py); 0: always one image_ingest launch
+# in front of the float route (profiles/uint8_ingest_time.txt has both)
+U8_STEM = os.environ.get('HS_U8_STEM', '1') != '0'
+_LAYOUT_CODES = {'hwc': 0, 'chw': 1}                       # HS_LAYOUT_* of include/hyperseg_hip.h
+
+
+@_on_operand_device
+def image_ingest(x_u8, norm, out=None):
+    """uint8 frames -> the float32 image (B, 3, H, W) of the reference's ToTensor + Normalize, one launch (hs_image_ingest_fwd).
+    ``x_u8``: (B, H, W, 3) or (B, 3, H, W) as ``norm.layout`` says (``norm``: a ``utils.inference.InputNorm``); the values are
+    looked up in ``norm``'s table, so the result equals the host transform bit for bit.  ``out``: a contiguous float32
+    (B, 3, H, W) tensor on the same device to write into."""
+    b, h, w = norm.frame_size(x_u8)
+    if out is None:
+        out = torch.empty(b, 3, h, w, device=x_u8.device, dtype=torch.float32)
+    elif not isinstance(out, torch.Tensor) or tuple(out.shape) != (b, 3, h, w) or out.device != x_u8.device:
+        raise ValueError(f'out must be a float32 tensor of shape {(b, 3, h, w)} on {x_u8.device}')
+    st = _hip.lib.hs_image_ingest_fwd(_hip.dev_ptr(x_u8, 'x_u8', torch.uint8), _LAYOUT_CODES[norm.layout], b, 3, h, w,
+                                      _hip.dev_ptr(norm.table(x_u8.device), 'table'), _hip.dev_ptr(out, 'out'), _hip.stream_ptr())
+    _hip.check(st, 'hs_image_ingest_fwd')
+    return out
+
+
 @_on_operand_device
 def stem_dw(x, w_stem28, scale0, shift0, stem_pad_top, stem_pad_left, stem_out_size, w_dw, pad_top, pad_left, scale1, shift1, pool=True):
     """The encoder's stem (3x3 stride-2 conv of the image + BN + swish) and the first block's depthwise 3x3 + BN + swish (+ SE
     pooling partial sums) in ONE launch: the stem's output map never reaches HBM (hs_stem_dw_fwd).  ``w_stem28``: the stem weight
     flattened to (Cmid, 27) plus one zero column.  Returns ``(y, partial)`` / ``y``, or ``None`` when the launch does not cover the
-    shape (the caller then runs the two launches).  Encoder-side helper, opt-in."""
+    shape (the caller then runs the two launches).  ``x`` may be a :class:`U8Frame`: the launch then reads the uint8 frame itself
+    (hs_stem_dw_u8_fwd; same values as on ``image_ingest``'s result), and where it does not cover the shape the frame is ingested
+    and handed to the float form.  Encoder-side helper, opt-in."""
     b, _, h, w = x.shape
     cmid, k = w_dw.shape[0], w_dw.shape[-1]
     hs_, ws_ = stem_out_size
     y = torch.empty(b, cmid, hs_, ws_, device=x.device, dtype=torch.float32)
     partial = torch.empty(b * cmid, _hip.lib.hs_mbconv_tiles(k, 1, hs_, ws_), device=x.device, dtype=torch.float32) if pool else None
+    if isinstance(x, U8Frame):
+        st = _hip.lib.hs_stem_dw_u8_fwd(_hip.dev_ptr(x.data, 'x', torch.uint8), _LAYOUT_CODES[x.norm.layout],
+                                        _hip.dev_ptr(x.norm.table(x.device), 'table'), b, h, w, _hip.dev_ptr(w_stem28, 'w_stem28'), cmid,
+                                        _hip.dev_ptr(scale0, 'scale0'), _hip.dev_ptr(shift0, 'shift0'), stem_pad_top, stem_pad_left, hs_, ws_,
+                                        _hip.dev_ptr(w_dw, 'w_dw'), k, pad_top, pad_left, _hip.dev_ptr(scale1, 'scale1'),
+                                        _hip.dev_ptr(shift1, 'shift1'), y.data_ptr(), partial.data_ptr() if pool else None, _hip.stream_ptr())
+        if st == -3:                   # HS_ERR_UNSUPPORTED: nothing was launched -- the float form on the ingested frame
+            return stem_dw(x.float_image(), w_stem28, scale0, shift0, stem_pad_top, stem_pad_left, stem_out_size, w_dw, pad_top, pad_left,
+                           scale1, shift1, pool=pool)
+        _hip.check(st, 'hs_stem_dw_u8_fwd')
+        return (y, partial) if pool else y
     st = _hip.lib.hs_stem_dw_fwd(_hip.dev_ptr(x, 'x'), b, h, w, _hip.dev_ptr(w_stem28, 'w_stem28'), cmid, _hip.dev_ptr(scale0, 'scale0'),
                                  _hip.dev_ptr(shift0, 'shift0'), stem_pad_top, stem_pad_left, hs_, ws_, _hip.dev_ptr(w_dw, 'w_dw'), k,
                                  pad_top, pad_left, _hip.dev_ptr(scale1, 'scale1'), _hip.dev_ptr(shift1, 'shift1'), y.data_ptr(),

@@ -82,15 +82,51 @@ class HyperGenBase(EpochOnModeSwitch, nn.Module):
 
     inference_hflip = False
     inference_gather = 'mean'
+    # a utils.inference.InputNorm: uint8 frames are then accepted and normalised on the device.  A plain attribute -- no parameter,
+    # no buffer: state_dict() and strict loading of reference checkpoints are as they were
+    input_norm = None
+
+    def frame_size(self, x):
+        """(H, W) of an input tensor: a float image (B, 3, H, W), or uint8 frames in ``input_norm``'s layout."""
+        if x.dtype == torch.uint8:
+            return tuple(self._require_norm().frame_size(x)[1:])
+        return tuple(x.shape[2:])
+
+    def _require_norm(self):
+        if self.input_norm is None:
+            raise TypeError('uint8 input needs the transform that turns it into the image the model was trained on: set '
+                            'model.input_norm = hyperseg_amd.InputNorm(mean, std, layout) (or pass input_norm= to '
+                            'prepare_for_inference); float32 inputs are taken as already normalised')
+        return self.input_norm
+
+    def _takes_u8_stem(self, frame):
+        """The fused uint8 route: the prepared backbone's stem + depthwise launch reads the frame itself and no decoder level reads
+        the image (fewer levels than pyramid entries), so the float image is never written."""
+        bb = self.backbone
+        levels, feats = getattr(self.decoder, 'levels', None), getattr(bb, 'feat_channels', None)
+        if not HF.U8_STEM or levels is None or feats is None or levels >= len(feats) or not hasattr(bb, 'takes_u8_frame'):
+            return False
+        return bb.takes_u8_frame(frame)
 
     @property
     def hyper_params(self):
         return self.decoder.hyper_params
 
     def process_single_tensor(self, x, hflip=False, masks=False, score=None):
+        frame = None
+        if x.dtype == torch.uint8:
+            norm = self._require_norm()
+            if x.is_cuda and not hflip and not self.training:
+                frame = HF.U8Frame(x, norm)
+                if not self._takes_u8_stem(frame):
+                    frame = None
+            if frame is None:
+                x = norm.to_float(x)          # one image_ingest launch, then the float path as it is
         if hflip:
             x = torch.flip(x, [-1])
-        features = self.backbone(x)
+        features = self.backbone(x if frame is None else frame)
+        if frame is not None:
+            x = frame.size_carrier()          # the decoder reads the output size from it, nothing else
         head_out = self.weight_mapper(features[-1])
         if isinstance(head_out, torch.Tensor):
             head_out = head_out.contiguous()
@@ -123,7 +159,7 @@ class HyperGenBase(EpochOnModeSwitch, nn.Module):
         n = confmat.num_classes
         fused = (isinstance(x, torch.Tensor) and x.is_cuda and not self.training and isinstance(target, torch.Tensor)
                  and target.is_cuda and target.dtype in (torch.uint8, torch.int64) and target.dim() == 3
-                 and target.shape[0] == x.shape[0] and target.shape[1:] == x.shape[2:] and n <= min(256, HF.eval_max_classes()))
+                 and target.shape[0] == x.shape[0] and tuple(target.shape[1:]) == self.frame_size(x) and n <= min(256, HF.eval_max_classes()))
         if fused:
             mat = confmat.matrix(x.device)
             if per_image:
@@ -135,8 +171,8 @@ class HyperGenBase(EpochOnModeSwitch, nn.Module):
             if masks.dtype == torch.uint8:
                 return masks
             raise RuntimeError('the decoder returned logits from its masks=True route: nothing was scored')
-        out_res = x.shape[2:] if isinstance(x, torch.Tensor) else x[0].shape[2:]
-        if target.shape[1:] != out_res:
+        out_res = self.frame_size(x if isinstance(x, torch.Tensor) else x[0])
+        if tuple(target.shape[1:]) != out_res:
             pred = self(x)
             pred = HF.upsample_bilinear(pred.contiguous(), tuple(target.shape[1:])) if pred.is_cuda else \
                 torch.nn.functional.interpolate(pred, size=target.shape[1:], mode='bilinear')
@@ -159,13 +195,13 @@ class HyperGenBase(EpochOnModeSwitch, nn.Module):
         if isinstance(x, torch.Tensor):
             return self.process_single_tensor(x)
         assert isinstance(x, (list, tuple)), 'x must be of type list, tuple, or tensor'
-        out_res = x[0].shape[2:]          # the first pyramid level sets the output resolution
+        out_res = self.frame_size(x[0])   # the first pyramid level sets the output resolution
         merged = None
         for level in x:
             y = self.process_single_tensor(level)
             if self.inference_hflip:
                 y = torch.max(y, self.process_single_tensor(level, hflip=True))
-            if y.shape[2:] != out_res:
+            if tuple(y.shape[2:]) != out_res:
                 y = HF.upsample_bilinear(y.contiguous(), out_res)
             merged = self.gather_results(y, merged)
         return merged

@@ -202,6 +202,12 @@ class EfficientNet(nn.Module):
             h, w = (h + st - 1) // st, (w + st - 1) // st
         return (h * w) % 4 == 0
 
+    def takes_u8_frame(self, frame):
+        """Whether this forward would hand ``frame`` (a functional.U8Frame standing for the image) to block 0's stem + depthwise
+        launch, which reads uint8 frames itself: the prepared route is on for this input and that launch is installed."""
+        f0 = self._blocks[0]._fused_dw if len(self._blocks) else None
+        return self._fused_stem is not None and f0 is not None and f0.takes_image() and self._fused_ok(frame)
+
     def extract_features_list(self, inputs):
         use = self._fused_ok(inputs)
         for blk in self._blocks:
@@ -213,6 +219,9 @@ class EfficientNet(nn.Module):
                 blk._fused_active = None
 
     def _extract_features_list(self, inputs, use):
+        # ``inputs`` may be a functional.U8Frame (uint8 frames standing for the image; only when takes_u8_frame() said yes): it offers
+        # shape / is_cuda / requires_grad / contiguous() and nothing else, and is handed to block 0 untouched -- anything added here that
+        # treats ``inputs`` as a tensor must go through ``inputs.float_image()`` first
         f0 = self._blocks[0]._fused_dw if len(self._blocks) else None
         if self._fused_stem is not None and use and f0 is not None and getattr(f0, '_stem', None) is not None:
             x = inputs                          # block 0's fused route runs the stem itself (one launch with its depthwise half)

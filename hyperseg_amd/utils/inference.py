@@ -25,6 +25,69 @@ import torch
 import torch.nn as nn
 
 
+class InputNorm:
+    """The input transform as data: per-channel float32 ``mean`` / ``std`` and the ``layout`` of the uint8 frames they apply to --
+    ``'hwc'``: (B, H, W, 3), what decoders, cameras, PIL and cv2 deliver; ``'chw'``: (B, 3, H, W).  Attached to a model
+    (``model.input_norm = InputNorm(...)`` or ``prepare_for_inference(model, ..., input_norm=...)``) it lets every entry point
+    take uint8 frames and normalise them on the device.  Defaults: the reference's evaluation defaults (test.py:62-63).
+
+    It owns a (3, 256) float32 table, built on the CPU by exactly the arithmetic of the two reference transforms in float32,
+    ``table[c, v] = (float32(v) / 255 - mean[c]) / std[c]`` -- torchvision's ``to_tensor`` (``img.to(float32).div(255)``) and
+    ``normalize`` (``tensor.sub_(mean).div_(std)``), which seg_transforms.ToTensor / Normalize call.  torchvision is not a
+    dependency of this package, so the arithmetic is restated here, not imported.  The kernels look values up in this table
+    (copied once per device), so for uint8 input the lookup IS the transform, bit for bit.  Not a parameter, not a buffer: state
+    dicts are unaffected."""
+
+    LAYOUTS = ('hwc', 'chw')
+
+    def __init__(self, mean=(0.485, 0.456, 0.406), std=(0.229, 0.224, 0.225), layout='hwc'):
+        if layout not in self.LAYOUTS:
+            raise ValueError(f'layout {layout!r}: expected one of {self.LAYOUTS}')
+        self.mean = torch.as_tensor(mean, dtype=torch.float32).flatten().clone()
+        self.std = torch.as_tensor(std, dtype=torch.float32).flatten().clone()
+        if self.mean.numel() != 3 or self.std.numel() != 3:
+            raise ValueError('mean and std must hold one value per channel of a 3-channel frame')
+        if bool((self.std == 0).any()):
+            raise ValueError('std must be non-zero')
+        self.layout = layout
+        values = torch.arange(256, dtype=torch.float32)
+        self._tables = {torch.device('cpu'): ((values.div(255)[None, :] - self.mean[:, None]) / self.std[:, None]).contiguous()}
+
+    def table(self, device='cpu'):
+        """The (3, 256) table on ``device`` (copied there on first use)."""
+        device = torch.device(device)
+        if device.type == 'cuda' and device.index is None:
+            device = torch.device('cuda', torch.cuda.current_device())
+        t = self._tables.get(device)
+        if t is None:
+            t = self._tables[torch.device('cpu')].to(device)
+            if device.type == 'cuda' and not torch.cuda.is_current_stream_capturing():
+                torch.cuda.current_stream(device).synchronize()      # other streams (a capture's side stream, replicas) may read it next
+            self._tables[device] = t
+        return t
+
+    def frame_size(self, x):
+        """(B, H, W) of a batch of uint8 frames in this norm's layout."""
+        if not isinstance(x, torch.Tensor) or x.dtype != torch.uint8 or x.dim() != 4 or x.shape[3 if self.layout == 'hwc' else 1] != 3:
+            want = '(B, H, W, 3)' if self.layout == 'hwc' else '(B, 3, H, W)'
+            raise ValueError(f"InputNorm(layout='{self.layout}') describes uint8 frames of shape {want}, got "
+                             f'{getattr(x, "dtype", type(x))} {tuple(getattr(x, "shape", ()))}')
+        return (x.shape[0], x.shape[1], x.shape[2]) if self.layout == 'hwc' else (x.shape[0], x.shape[2], x.shape[3])
+
+    def to_float(self, x):
+        """The float32 (B, 3, H, W) image of uint8 frames ``x``: one ``functional.image_ingest`` launch on the GPU, the two reference
+        transforms as stock ops on the CPU.  Same values either way."""
+        self.frame_size(x)
+        if x.is_cuda:
+            from .. import functional as HF
+            return HF.image_ingest(x.contiguous(), self)
+        chw = x.permute(0, 3, 1, 2) if self.layout == 'hwc' else x
+        return ((chw.to(torch.float32).div(255) - self.mean[None, :, None, None]) / self.std[None, :, None, None]).contiguous()
+
+    def __repr__(self):
+        return f'InputNorm(mean={self.mean.tolist()}, std={self.std.tolist()}, layout={self.layout!r})'
+
+
 @torch.no_grad()
 def _fold(conv, bn):
     scale = bn.weight / torch.sqrt(bn.running_var + bn.eps)
@@ -270,6 +333,11 @@ class FusedMBConv(nn.Module):
             self.out_offset = carried.clone() if defer_shift else None
             self.project.shift.copy_(torch.zeros_like(carried) if defer_shift else carried)
 
+    def takes_image(self):
+        """Block 0 with the stem attached and the one-launch form switched on: the block is handed the image, and
+        ``functional.stem_dw`` reads it as float32 or as a uint8 frame (functional.U8Frame)."""
+        return self._stem is not None and STEM_DW
+
     def fuses_expand(self, x, ho, wo):
         """[expand + BN + swish + depthwise + BN + swish + pool] as ONE launch (hs_mbconv_expand_dw_fwd): wherever the
         map is large enough to fill the chip with (tile x channel-chunk) workgroups and Cin fits the register-resident
@@ -281,9 +349,11 @@ class FusedMBConv(nn.Module):
         pre = None
         if self._stem is not None and inputs.shape[1] == 3:      # inputs is the image: stem + depthwise half in one launch, or the stem's own launch first
             stem = self._stem[0]
-            img = inputs.contiguous()
+            img = inputs.contiguous()         # (a functional.U8Frame: the launch reads the uint8 frame itself)
             pre = HF.stem_dw(img, stem.w28, stem.scale, stem.shift, stem.pad_t, stem.pad_l, stem.out_size(img),
                              blk._depthwise_conv.weight, self.pad_t, self.pad_l, self.scale, self.shift, pool=True) if STEM_DW else None
+            if pre is None and isinstance(img, HF.U8Frame):
+                img = img.float_image()
             inputs = pre[0] if pre is not None else stem(img)         # (pre: only the shape is read below -- skip is off for this block)
         x = inputs.contiguous()
         b, _, h, w = x.shape
@@ -559,16 +629,21 @@ def set_ir_math(model, mode):
 
 
 def prepare_for_inference(model, fold_bn=True, channels_last=False, fused_depthwise=False, split_gemm=False, ir_math='auto',
-                          chain_k1=True):
+                          chain_k1=True, input_norm=None):
     """In place; returns the number of BatchNorms folded by ``fold_bn``.  ``model``: a HyperGen in eval mode (module
     docstring for what each switch does).  The fused routes are installed first, so ``fold_bn`` only touches the
     Conv -> BatchNorm pairs that no fused route reads.  ``ir_math``: :func:`set_ir_math` for the decoder ('auto' = the
     f16-split inverted residual wherever it exists -- what serving and bench.py run; None leaves the modules' 'f32').
     ``chain_k1``: the decoder's three coarse k = 1 levels as ONE launch with in-launch neighbour hand-offs (hs_k1_chain_fwd;
     v1_0 decoders whose whole grid is resident at once -- the others keep one launch per level).  One frame in flight per model:
-    the launch keeps its generation counter in a per-decoder workspace."""
+    the launch keeps its generation counter in a per-decoder workspace.  ``input_norm``: an :class:`InputNorm` to attach
+    (``model.input_norm``): the model then takes uint8 frames."""
     assert not model.training, 'call model.eval() first'
     folded = 0
+    if input_norm is not None:
+        if not isinstance(input_norm, InputNorm):
+            raise TypeError('input_norm must be a hyperseg_amd.utils.inference.InputNorm')
+        model.input_norm = input_norm
     if ir_math is not None:
         set_ir_math(model, ir_math)
     if hasattr(model, 'decoder'):
@@ -612,7 +687,9 @@ class GraphedModel(nn.Module):
     through this wrapper.
 
     ``forward(x)``: ``x`` a single tensor, on the device or in (pinned) host memory -- it is copied into the graph's
-    static input buffer on the current stream, so the host-to-device copy IS the staging copy.  One graph is captured per
+    static input buffer on the current stream, so the host-to-device copy IS the staging copy.  uint8 frames (a model with an
+    ``input_norm``) are staged as uint8 -- a quarter of the bytes -- and normalised inside the graph; the key holds the uint8 shape,
+    so 'hwc' and 'chw' frames get graphs of their own.  One graph is captured per
     (shape, dtype) on first use (``warmup`` eager forwards on a side stream first: library handles, workspaces and the
     lazily built buffers of the fused routes must exist before capture).  The returned tensor is the graph's static output:
     valid until the next forward of the same shape (``clone_output=True`` hands out copies).  Anything the graph cannot
@@ -624,7 +701,7 @@ class GraphedModel(nn.Module):
         super().__init__()
         self.model = model
         self.masks, self.warmup, self.clone_output, self.max_graphs = bool(masks), int(warmup), bool(clone_output), int(max_graphs)
-        self._graphs = {}                      # (shape, dtype, device) -> (graph, static inputs, static_out, chained-launch owners)
+        self._graphs = {}                      # (shape, dtype, device, input norm of uint8 frames) -> (graph, static inputs, static_out, chained-launch owners)
         self._replays = 0
         self._hook = model.register_load_state_dict_post_hook(lambda module, incompatible: self.reset())
         # evaluate(): the classes to count and the graph-owned int64 matrix -- (n, n), or (B, n, n) with per_image (B: the batch
@@ -683,6 +760,10 @@ class GraphedModel(nn.Module):
         self._graphs[key] = (graph, static, static_out, chains)
         return self._graphs[key]
 
+    def _norm_of(self, x):
+        """Part of a uint8 frame's graph key: the captured launches hold the norm's table and layout."""
+        return getattr(self.model, 'input_norm', None) if x.dtype == torch.uint8 else None
+
     accepts_host_input = True                  # hyperseg_amd.fps.measure_fps hands the pinned host batch over as it is
     owns_confusion = True                      # ... and reads evaluate()'s counts from ``confusion``
 
@@ -720,7 +801,7 @@ class GraphedModel(nn.Module):
                 x = x.to(p.device, non_blocking=True)
             return self._eager(x)
         device = p.device
-        key = (tuple(x.shape), x.dtype, device)
+        key = (tuple(x.shape), x.dtype, device, self._norm_of(x))
         entry = self._graphs.get(key)
         if entry is None:
             entry = self._capture(key, [x], device)
@@ -752,7 +833,8 @@ class GraphedModel(nn.Module):
         p = next(self.model.parameters(), None)
         n = self.num_classes
         graphable = (self._graphable(x) and isinstance(target, torch.Tensor) and target.dtype in (torch.uint8, torch.int64)
-                     and target.dim() == 3 and x.dim() == 4 and tuple(target.shape) == (x.shape[0],) + tuple(x.shape[2:])
+                     and target.dim() == 3 and x.dim() == 4 and hasattr(self.model, 'frame_size')
+                     and tuple(target.shape) == (x.shape[0],) + tuple(self.model.frame_size(x))
                      and n is not None and n <= min(256, HF.eval_max_classes()) and hasattr(self.model, 'process_single_tensor'))
         if not graphable:
             if p is not None and p.is_cuda:
@@ -769,7 +851,7 @@ class GraphedModel(nn.Module):
             return masks
         device = p.device
         confusion = self._confusion_on(device, x.shape[0])
-        key = ('evaluate', tuple(x.shape), x.dtype, target.dtype, device)
+        key = ('evaluate', tuple(x.shape), x.dtype, target.dtype, device, self._norm_of(x))
         entry = self._graphs.get(key)
         if entry is None:
             scratch = torch.zeros_like(confusion)                # the warm-up passes execute: their counts go here

@@ -441,6 +441,23 @@ int hs_stem_dw_fwd(const float* x, int32_t batch, int32_t H, int32_t W, const fl
                    const float* scale0, const float* shift0, int32_t stem_pad_t, int32_t stem_pad_l, int32_t Hs, int32_t Ws,
                    const float* w_dw, int32_t k, int32_t pad_t, int32_t pad_l, const float* scale1, const float* shift1,
                    float* y, float* pool_partial, void* stream);
+/* uint8 frames (what cameras and decoders deliver) normalised on the device.  layout: HS_LAYOUT_HWC = (B, H, W, 3), HS_LAYOUT_CHW =
+ * (B, 3, H, W).  table: (3, 256) floats, table[c][v] = (float(v) / 255 - mean[c]) / std[c] computed on the host in float32 -- the
+ * arithmetic of the reference's ToTensor + Normalize (hyperseg/datasets/seg_transforms.py, defaults test.py:62-63); the kernels look
+ * values up, so their output is bit-identical to the host transform.
+ *   hs_image_ingest_fwd: x -> y (B, 3, H, W) float32 in one launch; any H, W >= 1, any alignment of x (y: a float's 4 bytes), batch <= 65535;
+ *     HS_ERR_UNSUPPORTED for channels != 3.
+ *   hs_stem_dw_u8_fwd: hs_stem_dw_fwd reading x itself (the float image is never written): the other arguments, the outputs (bit for
+ *     bit, against hs_stem_dw_fwd on hs_image_ingest_fwd's result) and the shapes answered with HS_ERR_UNSUPPORTED are hs_stem_dw_fwd's;
+ *     zero padding is applied after the lookup, i.e. in the normalised domain. */
+#define HS_LAYOUT_HWC 0
+#define HS_LAYOUT_CHW 1
+int hs_image_ingest_fwd(const uint8_t* x, int32_t layout, int32_t batch, int32_t channels, int32_t H, int32_t W, const float* table,
+                        float* y, void* stream);
+int hs_stem_dw_u8_fwd(const uint8_t* x, int32_t layout, const float* table, int32_t batch, int32_t H, int32_t W,
+                      const float* w_stem28, int32_t c_mid, const float* scale0, const float* shift0, int32_t stem_pad_t,
+                      int32_t stem_pad_l, int32_t Hs, int32_t Ws, const float* w_dw, int32_t k, int32_t pad_t, int32_t pad_l,
+                      const float* scale1, const float* shift1, float* y, float* pool_partial, void* stream);
 int hs_mbconv_expand_dw_fwd(const float* x, int32_t batch, int32_t c_in, int32_t H, int32_t W,
                             const float* w_expand, int32_t c_mid, const float* scale0, const float* shift0,
                             const float* w_dw, int32_t k, int32_t stride, int32_t pad_t, int32_t pad_l,
