@@ -17,13 +17,6 @@ from ._hip import ACT_NONE, ACT_RELU, ACT_RELU6, PAD_MODES  # noqa: F401  (re-ex
 
 BN_EPS_DEFAULT = 1e-5
 S2W_TRAIN_MAX_LAYERS = 8     # S2W_MAX_LAYERS of csrc/hs_s2w_blocked.h: layers one hs_s2w_train_* / hs_signal2weights_multi_fwd launch takes
-# Late-level banks on a second stream: saves ~14 us of decoder time in isolation, but a forked/joined capture makes
-# the whole-model HIP-graph replay 0.37 ms SLOWER on ROCm 7.2 (measured: 3.62 -> 3.99 ms/frame), so it is off by default.
-USE_SIDE_STREAM = os.environ.get('HS_SIDE_STREAM', '0') == '1'
-# Round 4: the finer fork -- level 0's bank on the current stream, every later level's bank as its own launch on the side stream
-# with one event each, so level l waits for ITS bank only and signal2weights overlaps the latency-bound k = 1 levels
-# (HS_SIDE_STREAM=2; measured by tools/gpu_r4c.sh, decision in DESIGN section 3.1).
-PIPELINE_BANKS = os.environ.get('HS_SIDE_STREAM', '0') == '2'
 # Round 4: the banks of the later levels produced INSIDE the k = 1 levels' launches (CoScheduledBanks / hs_patch_conv_s2w_fwd).
 # MEASURED AND OFF (visit r4e, profiles/round4_coscheduled_banks_ab.txt): the carrying launches grow by what the riders take -- level 2
 # with bank 4 aboard 7.3 -> 15.2 us, kernel sum of (signal2weights + levels 0-2) 37.5 -> 39.4 us, replayed decoder 0.086 -> 0.087 ms.
@@ -353,8 +346,8 @@ S2W_BLOCKED = os.environ.get('HS_S2W_BLOCKED', '1') == '1'     # dev A/B switch:
 @_on_operand_device
 def signal2weights_multi(signal, layers, buf=None):
     """All signal2weights layers of a decoder in ONE launch.  ``layers``: list of dicts with wsw_t, signal_index,
-    signal_channels, groups, rows.  Returns one BankRef per layer (views of one buffer; ``buf``: the caller's, at least
-    ``bank_floats(signal, layers)`` floats -- for callers that issue the launch on another stream than the one that owns the memory)."""
+    signal_channels, groups, rows.  Returns one BankRef per layer (views of one buffer; ``buf``: the caller's own to lay them out
+    in instead of a fresh one, contiguous fp32, at least ``bank_floats(signal, layers)`` elements)."""
     b, _, fh, fw = signal.shape
     signal, sig_ptr, c_signal = _channel_view(signal, 'signal')
     arr, refs = _s2w_layer_table(signal, layers, buf)
@@ -424,24 +417,9 @@ class CoScheduledBanks:
 
 
 def bank_floats(signal, layers):
-    """Floats of the buffer :func:`signal2weights_multi` needs for ``layers``."""
+    """fp32 elements of the buffer :func:`signal2weights_multi` lays the banks of ``layers`` out in (what its ``buf`` must hold)."""
     b, _, fh, fw = signal.shape
     return b * fh * fw * sum(_round_up(l['rows'], 4) for l in layers)
-
-
-class SideStream:
-    """A second HIP stream per device for work that is independent of the decoder's level-to-level chain (the banks
-    of the late levels): forked from / joined to the current stream with events, so it is captured as a parallel
-    branch when the forward runs under HIP-graph capture."""
-    _streams = {}
-
-    @classmethod
-    def get(cls, device):
-        key = (device.type, device.index)
-        with _CACHE_LOCK:
-            if key not in cls._streams:
-                cls._streams[key] = torch.cuda.Stream(device=device)
-            return cls._streams[key]
 
 
 @_on_operand_device

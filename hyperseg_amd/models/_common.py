@@ -66,6 +66,17 @@ def final_masks_scored(p, size, score):
     return HF.upsample_confusion(p, size, target, num_classes, out=out, per_image=per_image, masks=True)[1]
 
 
+def finish_decoder(decoder, p, size, masks, score):
+    """What the v1_0 and unify decoders return for their last level's output ``p``: with ``masks``, the uint8 argmax masks at ``size``
+    straight from the final upsample launch (scored by the same launch when ``score`` is given); otherwise the logits, resized to
+    ``size`` -- into ``decoder.output_buffer`` where a serving wrapper has set one."""
+    if masks:
+        return HF.upsample_argmax(p, size) if score is None else final_masks_scored(p, size, score)
+    if p.shape[2:] != size:
+        p = HF.upsample_bilinear(p, size, out=getattr(decoder, 'output_buffer', None))
+    return p
+
+
 class EpochOnModeSwitch:
     """Mixin (before nn.Module in the bases): every train() / eval() switch invalidates the parameter-derived caches of the
     inference route (functional.bump_weights_epoch) -- training steps change parameters and BatchNorm statistics through

@@ -17,6 +17,7 @@ signal reaches the modules through MetaSequential's clamped slice (D-2), ``weigh
 consumed by ``pop(0)`` (D-3), coordinate buffers exist for checkpoint compatibility but the values
 are generated analytically (D-11).
 """
+from collections import namedtuple
 from functools import partial
 from itertools import groupby
 
@@ -28,7 +29,7 @@ from torch.nn.modules.utils import _pair
 
 from .. import functional as HF
 from .. import autograd as HA
-from ._common import EpochOnModeSwitch, HyperGenBase, final_masks_scored, coordinate_grid, per_level, plan_levels, register_coordinate_buffers
+from ._common import EpochOnModeSwitch, HyperGenBase, finish_decoder, coordinate_grid, per_level, plan_levels, register_coordinate_buffers
 from .layers.meta_conv import MetaConv2d, _apply_epilogue, _require_inference, assemble_block, check_padding_mode
 from .layers.meta_sequential import MetaSequential
 
@@ -53,11 +54,14 @@ class _SignalToWeights:
         self.signal_index = int(signal_index)
         self.signal2weights = nn.Conv2d(int(signal_channels), int(weight_channels), 1, bias=False, groups=int(groups))
 
+    def s2w_shape(self):
+        """The weight-free part of ``s2w_layer``: what planning needs to know of this module's signal2weights (no device work)."""
+        return dict(signal_index=self.signal_index, signal_channels=self.signal_channels, groups=self.signal2weights.groups,
+                    rows=self.hyper_params)
+
     def _s2w_layer(self, rows):
         """Descriptor of this module's signal2weights for the decoder-wide single launch."""
-        conv = self.signal2weights
-        return dict(wsw_t=self._s2w_t.get(conv), signal_index=self.signal_index,
-                    signal_channels=self.signal_channels, groups=conv.groups, rows=rows)
+        return dict(self.s2w_shape(), wsw_t=self._s2w_t.get(self.signal2weights), rows=rows)
 
     def _bank(self, s, rows):
         if isinstance(s, HF.BankRef):
@@ -426,68 +430,112 @@ def divide_feature(in_feature, out_features, min_unit=8):
     return out
 
 
+# where a signal-fed module's filter bank comes from (BankPlan.sources)
+LAUNCH = 'launch'            # the decoder's one hs_signal2weights_multi_fwd launch
+IN_CONSUMER = 'consumer'     # generated inside the consuming launch (hs_patch_conv_gen_fwd): never in HBM
+CARRIED = 'carried'          # rides in the launch of an earlier k = 1 level (hs_patch_conv_s2w_fwd)
+
+# ``sources``: per group (level | out_fc) one of the three above per signal-fed module; ``carry``: _coschedule_plan's map or None;
+# ``chain``: whether the chained launch is to be tried for the coarse levels
+BankPlan = namedtuple('BankPlan', 'sources carry chain')
+
+
+def bank_in_consumer(module, layer, size, grid):
+    """Whether a level generates its bank inside its consumer (no bank in HBM for the coarse k = 1 levels).
+    ``module``: the level's one signal-fed module -- an ungrouped HyperPatchNoPadding; ``layer``: the signal2weights layer that
+    feeds it -- at most 80 signal channels per group; ``size``: the level's feature size -- whole patches of the signal ``grid``, of at
+    most HF.BANK_IN_CONSUMER_MAX_PIXELS pixels (0, the default: never)."""
+    (hl, wl), (fh, fw) = size, grid
+    return isinstance(module, HyperPatchNoPadding) and module.groups == 1 and hl % fh == 0 and wl % fw == 0 and \
+        (hl // fh) * (wl // fw) <= HF.BANK_IN_CONSUMER_MAX_PIXELS and layer['signal_channels'] // layer['groups'] <= 80
+
+
+def _unwrap(seq):
+    """level_<l> = MetaSequential(block), block = MetaSequential(conv, norm, act): the innermost container."""
+    while len(seq) == 1 and isinstance(seq[0], MetaSequential):
+        seq = seq[0]
+    return seq
+
+
+def _frozen_bn(bn):
+    """A BatchNorm2d that folds into a (scale, shift) pair: eval mode and no gradient wanted."""
+    return isinstance(bn, nn.BatchNorm2d) and not bn.training and \
+        not (torch.is_grad_enabled() and bn.weight is not None and bn.weight.requires_grad)
+
+
+def _chain_skip(sk, c_prev, c_in):
+    """The skip feature a chained level reads in place: fp32, contiguous, on the GPU, and [coords | skip | previous level] fills the conv."""
+    return sk.is_cuda and sk.dtype == torch.float32 and sk.is_contiguous() and 2 + sk.shape[1] + c_prev == c_in
+
+
+def _chain_level(seq, ref):
+    """A level the chain takes -- [HyperPatchNoPadding(k = 1, groups = 1), eval BatchNorm?, ReLU | ReLU6?] with a materialised bank --
+    as (conv, affine, act), or None."""
+    from .layers.meta_sequential import _act_code
+    seq = _unwrap(seq)
+    mods = list(seq)
+    if not mods or not isinstance(mods[0], HyperPatchNoPadding) or not isinstance(ref, HF.BankRef):
+        return None
+    conv = mods[0]
+    if conv.kernel_size != (1, 1) or conv.stride != (1, 1) or conv.dilation != (1, 1) or conv.groups != 1 or ref.rows != conv.hyper_params:
+        return None
+    k, aff, act = 1, None, HF.ACT_NONE
+    if k < len(mods) and isinstance(mods[k], nn.BatchNorm2d):
+        if not _frozen_bn(mods[k]):
+            return None
+        aff = seq._fold(k, mods[k])
+        k += 1
+    if k < len(mods) and _act_code(mods[k]) is not None:
+        act = _act_code(mods[k])
+        k += 1
+    return (conv, aff, act) if k == len(mods) else None      # a Dropout or any other tail: the generic route
+
+
+def _chain_ir(seq, ref, sk, c_prev):
+    """The first inverted-residual level as the chain's fourth: the block every reference configuration builds (3 x 3 depthwise,
+    stride 1, reflect halo, BatchNorm2d | identity, ReLU6, no residual) on 8 x 8-pixel patches -- K1Chain.run's ``ir`` dict, or None."""
+    mods = list(_unwrap(seq))
+    blk = mods[0] if len(mods) == 1 else None
+    if not (isinstance(blk, HyperPatchInvertedResidual) and isinstance(ref, HF.BankRef) and ref.rows == blk.hyper_params
+            and not blk.use_res_connect and blk.kernel_size == (3, 3) and blk.stride == 1 and blk.padding_mode == 'reflect'
+            and isinstance(blk.act_layer, nn.ReLU6)
+            and all(_frozen_bn(q) or blk._is_identity(q) for q in (blk.bn1, blk.bn2, blk.bn3))
+            and _chain_skip(sk, c_prev, blk.in_nc)):
+        return None
+    bns = [None if blk._is_identity(q) else blk._affine_of(k, q, sk.device) for k, q in enumerate((blk.bn1, blk.bn2, blk.bn3))]
+    return dict(skip=sk, bank=ref.bank, hidden=blk.hidden_dim, c_out=blk.out_nc, bn=bns)
+
+
+def chain_wanted(owner):
+    """Whether a decoder tries the chained launch on this forward: switched on (``owner.chain_k1`` or HF.K1_CHAIN), and its K1Chain has
+    not refused every shape it was ever shown (that only skips calls that would return None)."""
+    if not (getattr(owner, 'chain_k1', False) or HF.K1_CHAIN):
+        return False
+    kc = getattr(owner, '_k1_chain', None)
+    return not (kc is not None and kc.refuses_everything)
+
+
 def run_decoder_chain(owner, seqs, refs, x):
     """The coarse levels of a v1_0 / unify decoder through functional.K1Chain (hs_k1_chain_fwd / hs_decoder_chain_fwd): levels 0-2 when
-    each is [HyperPatchNoPadding(k = 1, groups = 1), eval BatchNorm?, ReLU | ReLU6?] on patches of 1, 2 and 4 pixels with a materialised
-    bank -- the layout every v1_0 reference configuration builds (hyperseg_v1_0.py:728-760) -- and, when ``owner.chain_ir`` says so, the
-    first inverted-residual level behind them.  ``seqs``: the levels' MetaSequentials; ``refs``: their BankRefs; ``x``: the feature
-    pyramid.  Returns (output, number of levels done) or None (the caller runs the levels one launch each).  The K1Chain object (it
-    owns the launch's workspace) lives on ``owner``."""
-    from .layers.meta_sequential import _act_code
+    each is what _chain_level takes, on patches of 1, 2 and 4 pixels -- the layout every v1_0 reference configuration builds
+    (hyperseg_v1_0.py:728-760) -- and, when ``owner.chain_ir`` says so, the first inverted-residual level behind them (_chain_ir).
+    ``seqs``: the levels' MetaSequentials; ``refs``: their BankRefs; ``x``: the feature pyramid.  Returns (output, number of levels
+    done) or None (the caller runs the levels one launch each).  The K1Chain object (it owns the launch's workspace) lives on
+    ``owner``."""
     if len(seqs) < 3:
         return None
     skips, bnk, couts, affines, acts = [], [], [], [], []
     for l in range(3):
-        seq = seqs[l]
-        mods = list(seq)
-        while len(mods) == 1 and isinstance(mods[0], MetaSequential):      # level_<l> = MetaSequential(block), block = MetaSequential(conv, norm, act)
-            seq = mods[0]
-            mods = list(seq)
-        ref = refs[l]
-        if not mods or not isinstance(mods[0], HyperPatchNoPadding) or not isinstance(ref, HF.BankRef):
+        lvl = _chain_level(seqs[l], refs[l])
+        if lvl is None or not _chain_skip(x[-l - 1], couts[-1] if couts else 0, lvl[0].in_channels):
             return None
-        conv = mods[0]
-        if conv.kernel_size != (1, 1) or conv.stride != (1, 1) or conv.dilation != (1, 1) or conv.groups != 1 or ref.rows != conv.hyper_params:
-            return None
-        k, aff, act = 1, None, HF.ACT_NONE
-        if k < len(mods) and isinstance(mods[k], nn.BatchNorm2d):
-            bn = mods[k]
-            if bn.training or (torch.is_grad_enabled() and bn.weight is not None and bn.weight.requires_grad):
-                return None
-            aff = seq._fold(k, bn)
-            k += 1
-        if k < len(mods) and _act_code(mods[k]) is not None:
-            act = _act_code(mods[k])
-            k += 1
-        if k != len(mods):
-            return None                                  # a Dropout or any other tail: the generic route
-        sk = x[-l - 1]
-        prev_c = couts[-1] if couts else 0
-        if not (sk.is_cuda and sk.dtype == torch.float32 and sk.is_contiguous()) or 2 + sk.shape[1] + prev_c != conv.in_channels:
-            return None
-        skips.append(sk); bnk.append(ref.bank); couts.append(conv.out_channels); affines.append(aff); acts.append(act)
+        conv, aff, act = lvl
+        skips.append(x[-l - 1]); bnk.append(refs[l].bank); couts.append(conv.out_channels); affines.append(aff); acts.append(act)
     if getattr(owner, '_k1_chain', None) is None:
         owner._k1_chain = HF.K1Chain()
-    # the first inverted-residual level rides in the same launch when it is the block every reference configuration builds
-    # (3 x 3 depthwise, stride 1, reflect halo, BatchNorm2d | identity, ReLU6, no residual) on 8 x 8-pixel patches
-    ir = None
     if HF.K1_CHAIN_IR and len(seqs) > 3 and getattr(owner, 'chain_ir', HF.K1_CHAIN_IR_DEFAULT):
-        mods = list(seqs[3])
-        while len(mods) == 1 and isinstance(mods[0], MetaSequential):
-            mods = list(mods[0])
-        ref = refs[3]
-        blk = mods[0] if len(mods) == 1 else None
-        if isinstance(blk, HyperPatchInvertedResidual) and isinstance(ref, HF.BankRef) and ref.rows == blk.hyper_params \
-                and not blk.use_res_connect and blk.kernel_size == (3, 3) and blk.stride == 1 and blk.padding_mode == 'reflect' \
-                and isinstance(blk.act_layer, nn.ReLU6) \
-                and all((isinstance(q, nn.BatchNorm2d) and not q.training and not (torch.is_grad_enabled() and q.weight.requires_grad))
-                        or blk._is_identity(q) for q in (blk.bn1, blk.bn2, blk.bn3)):
-            sk = x[-4]
-            if sk.is_cuda and sk.dtype == torch.float32 and sk.is_contiguous() and 2 + sk.shape[1] + couts[2] == blk.in_nc:
-                bns = [None if blk._is_identity(q) else blk._affine_of(k, q, sk.device) for k, q in enumerate((blk.bn1, blk.bn2, blk.bn3))]
-                ir = dict(skip=sk, bank=ref.bank, hidden=blk.hidden_dim, c_out=blk.out_nc, bn=bns)
-    if ir is not None:
-        y = owner._k1_chain.run(skips, bnk, couts, affines, acts, ir=ir)
+        ir = _chain_ir(seqs[3], refs[3], x[-4], couts[2])
+        y = owner._k1_chain.run(skips, bnk, couts, affines, acts, ir=ir) if ir is not None else None
         if y is not None:
             return y, 4
     y = owner._k1_chain.run(skips, bnk, couts, affines, acts)
@@ -568,7 +616,7 @@ class MultiScaleDecoder(EpochOnModeSwitch, nn.Module):
             self._hyper_cache = found                          # published complete (replica threads may race to build it)
         return self._hyper_cache
 
-    def _coschedule_plan(self, groups, layers):
+    def _coschedule_plan(self, groups):
         """Which k = 1 level's launch carries which later group's signal2weights layers: {level: [group indices]}, or None when the
         decoder does not start with a k = 1 level.  A group must be carried by a level BEFORE the one that consumes it; among the
         allowed carriers the least loaded takes it (cost ~ bank rows x (K + 32) per patch), the latest on a tie -- at HyperSeg-M:
@@ -581,14 +629,10 @@ class MultiScaleDecoder(EpochOnModeSwitch, nn.Module):
                 break
         if n_k1 == 0 or len(groups) < 2 or any(len(g) == 0 for g in groups[:self.levels]):
             return None
-        starts, k0 = [], 0
-        for g in groups:
-            starts.append(k0)
-            k0 += len(g)
         load = [0.0] * n_k1
         carry = {}
         for gi in range(len(groups) - 1, 0, -1):
-            ls = layers[starts[gi]:starts[gi] + len(groups[gi])]
+            ls = [m.s2w_shape() for m in groups[gi]]
             if not ls:
                 continue
             cost = sum(l['rows'] * (l['signal_channels'] / l['groups'] + 32.0) for l in ls)
@@ -646,159 +690,94 @@ class MultiScaleDecoder(EpochOnModeSwitch, nn.Module):
             p = HA.upsample_bilinear(p, x[0].shape[2:])
         return p
 
+    def _bank_plan(self, x, s):
+        """Which filter banks this forward makes, and how: a BankPlan.  Reads shapes and switches only (no device work; CPU and meta
+        tensors do), and the switches on every call.  The routes and their precedence, stated here and nowhere else:
+        1. bank in the consumer: when any level qualifies (bank_in_consumer), those levels generate their banks themselves and one
+           launch makes the rest; no chain, no co-scheduling;
+        2. co-scheduled banks: otherwise, with HF.COSCHEDULE_BANKS on and a carry map from _coschedule_plan, level 0's bank is a
+           launch of its own and every later bank rides in the launch of an earlier k = 1 level; no chain;
+        3. one launch for all banks (the default), and behind it
+        4. the chained launch for the coarse levels, tried when chain_wanted says so.
+        A plan that is not taken when it runs (the chain returns None, the library calls a carrying launch unsupported) falls back
+        to one launch per level / per bank where that is found out."""
+        groups = self._hyper_modules()
+        for g in groups:
+            for m in g:
+                # the reference hands each module s[:, 0:hyper_params] (MetaSequential's clamped slice, Appendix D-2)
+                if m.signal_index + m.signal_channels > min(int(m.hyper_params), s.shape[1]):
+                    raise ValueError('signal slice of a decoder level exceeds what MetaSequential would hand to it')
+        grid = s.shape[-2:]
+        sources = [[LAUNCH] * len(g) for g in groups]
+        for lvl, g in enumerate(groups[:self.levels]):
+            if len(g) == 1 and bank_in_consumer(g[0], g[0].s2w_shape(), x[-lvl - 1].shape[-2:], grid):
+                sources[lvl] = [IN_CONSUMER]
+        if any(IN_CONSUMER in v for v in sources):
+            return BankPlan(sources, None, False)
+        carry = self._coschedule_plan(groups) if HF.COSCHEDULE_BANKS else None
+        if carry is not None:
+            for gi in (gi for riders in carry.values() for gi in riders):
+                sources[gi] = [CARRIED] * len(groups[gi])
+            return BankPlan(sources, carry, False)
+        return BankPlan(sources, None, chain_wanted(self))
+
+    def _make_banks(self, plan, s):
+        """Per group (level | out_fc), what its level is handed: a BankRef out of the ONE launch for every LAUNCH source (the banks
+        only depend on the signal), a SignalRef for a bank generated in its consumer, and for a CARRIED bank its signal2weights layer,
+        which _run_levels replaces by the BankRef once the carrying level has run."""
+        groups = self._hyper_modules()
+        source = [v for g in plan.sources for v in g]
+        layers = [m.s2w_layer(s.device) for g in groups for m in g]
+        keep = [l for l, v in zip(layers, source) if v == LAUNCH]
+        made = iter(HF.signal2weights_multi(s, keep) if keep else [])
+        refs = [next(made) if v == LAUNCH else HF.SignalRef(s, l) if v == IN_CONSUMER else l for l, v in zip(layers, source)]
+        banks, k = [], 0
+        for g in groups:
+            banks.append(refs[k:k + len(g)])
+            k += len(g)
+        return banks
+
+    def _run_levels(self, x, s, banks, plan, first, p):
+        """Levels ``first``.. and the out_fc, one launch each.  A level of ``plan.carry`` runs inside HF.CoScheduledBanks: its launch
+        (hs_patch_conv_s2w_fwd) also produces the banks of its riders, later groups, instead of those standing in front of level 0 as
+        one 15 us launch."""
+        carry = plan.carry or {}
+        for level in range(first, self.levels):
+            # cat(coords, skip, bilinear(p)) is never built: the stage kernel's prologue generates it
+            stage = HF.StageInput(x[-level - 1], p, coords=True)
+            riders = carry.get(level)
+            if riders:
+                with HF.CoScheduledBanks(s, [l for gi in riders for l in banks[gi]]) as co:
+                    p = getattr(self, f'level_{level}')(stage, banks[level])
+                made = iter(co.refs)
+                for gi in riders:
+                    banks[gi] = [next(made) for _ in banks[gi]]
+            else:
+                p = getattr(self, f'level_{level}')(stage, banks[level])
+        if self.out_fc is not None:
+            p = self.out_fc(p, banks[-1])
+        return p
+
     def forward(self, x, s, masks=False, score=None):
         """``masks=True`` (inference only, not in the reference): uint8 argmax masks straight from the final upsample
         kernel instead of logits."""
         if self.training or HA.needs_grad(s, *x, *self.parameters()):
             assert not masks, 'masks=True is an inference-only shortcut'
             return self._forward_autograd(x, s)
-        # every level's filter bank in ONE launch (the banks only depend on the signal)
-        groups = self._hyper_modules()
-        if any(len(g) > 1 for g in groups):
+        if any(len(g) > 1 for g in self._hyper_modules()):
             # several signal-fed modules inside one level (level_layers > 1; no shipped config): the reference hands the
             # k-th of them the signal slice that starts at the hyper-parameter count of its predecessors
             # (meta_sequential.py:35), so their signal_index is relative to that slice -- take the per-module route,
             # which slices exactly like that, instead of the single launch over the whole signal
             assert not masks, 'masks=True needs the single-launch route'
             return self._forward_autograd(x, s)
-        flat = [m for g in groups for m in g]
-        for m in flat:
-            # the reference hands each module s[:, 0:hyper_params] (MetaSequential's clamped slice, Appendix D-2)
-            if m.signal_index + m.signal_channels > min(int(m.hyper_params), s.shape[1]):
-                raise ValueError('signal slice of a decoder level exceeds what MetaSequential would hand to it')
-        # The banks depend on the signal only.  The light k=1 levels' banks are produced on the current stream; the
-        # heavy k=3 levels' banks (80 % of the signal2weights work) on a side stream, overlapping the k=1 levels.
-        n_early = sum(len(g) for l, g in enumerate(groups)
-                      if l < self.levels and all(not isinstance(m, HyperPatchInvertedResidual) for m in g)
-                      and all(all(not isinstance(q, HyperPatchInvertedResidual) for q in groups[e]) for e in range(l)))
-        layers = [m.s2w_layer(s.device) for m in flat]
-        # coarse k = 1 levels generate their bank inside the consumer: no bank in HBM for them (SURVEY 8f rank 1)
-        fh, fw = s.shape[-2:]
-        in_consumer = {}
-        for lvl, g in enumerate(groups[:self.levels]):
-            hl, wl = x[-lvl - 1].shape[-2:]
-            if len(g) == 1 and isinstance(g[0], HyperPatchNoPadding) and g[0].groups == 1 and \
-                    hl % fh == 0 and wl % fw == 0 and (hl // fh) * (wl // fw) <= HF.BANK_IN_CONSUMER_MAX_PIXELS and \
-                    g[0].signal_channels // g[0].signal2weights.groups <= 80:
-                in_consumer[id(g[0])] = HF.SignalRef(s, g[0].s2w_layer(s.device))
-        if in_consumer:
-            keep = [i for i, m in enumerate(flat) if id(m) not in in_consumer]
-            made = HF.signal2weights_multi(s, [layers[i] for i in keep]) if keep else []
-            refs = [in_consumer.get(id(m)) for m in flat]
-            for i, r in zip(keep, made):
-                refs[i] = r
-            banks, k = [], 0
-            for g in groups:
-                banks.append(refs[k:k + len(g)])
-                k += len(g)
-            p = None
-            for level in range(self.levels):
-                p = getattr(self, f'level_{level}')(HF.StageInput(x[-level - 1], p, coords=True), banks[level])
-            if self.out_fc is not None:
-                p = self.out_fc(p, banks[-1])
-            if masks:
-                return HF.upsample_argmax(p, x[0].shape[2:]) if score is None else final_masks_scored(p, x[0].shape[2:], score)
-            if p.shape[2:] != x[0].shape[2:]:
-                p = HF.upsample_bilinear(p, x[0].shape[2:], out=getattr(self, 'output_buffer', None))
-            return p
-        carry = self._coschedule_plan(groups, layers) if HF.COSCHEDULE_BANKS and s.is_cuda and not HF.PIPELINE_BANKS \
-            and not HF.USE_SIDE_STREAM else None
-        if carry is not None:
-            # Level 0's bank as its own launch; every later level's bank rides in the launch of an EARLIER k = 1 level
-            # (HF.CoScheduledBanks -> hs_patch_conv_s2w_fwd): the bank producer's blocks fill the CUs those latency-bound
-            # launches leave idle, instead of standing in front of level 0 as one 15 us launch.
-            per_group, k0 = [], 0
-            for g in groups:
-                per_group.append(layers[k0:k0 + len(g)])
-                k0 += len(g)
-            banks = [None] * len(groups)
-            banks[0] = HF.signal2weights_multi(s, per_group[0])
-            p = None
-            for level in range(self.levels):
-                stage = HF.StageInput(x[-level - 1], p, coords=True)
-                riders = carry.get(level, [])
-                if riders:
-                    with HF.CoScheduledBanks(s, [l for gi in riders for l in per_group[gi]]) as co:
-                        p = getattr(self, f'level_{level}')(stage, banks[level])
-                    k1 = 0
-                    for gi in riders:
-                        banks[gi] = co.refs[k1:k1 + len(per_group[gi])]
-                        k1 += len(per_group[gi])
-                else:
-                    p = getattr(self, f'level_{level}')(stage, banks[level])
-            if self.out_fc is not None:
-                p = self.out_fc(p, banks[-1])
-            if masks:
-                return HF.upsample_argmax(p, x[0].shape[2:]) if score is None else final_masks_scored(p, x[0].shape[2:], score)
-            if p.shape[2:] != x[0].shape[2:]:
-                p = HF.upsample_bilinear(p, x[0].shape[2:], out=getattr(self, 'output_buffer', None))
-            return p
-        side = join_level = None
-        bank_events = {}
-        if HF.PIPELINE_BANKS and s.is_cuda and len(groups) > 1 and len(groups[0]) > 0:
-            # level 0's bank on this stream; each later level's bank = one launch on the side stream + one event: level l waits
-            # for ITS bank only.  Bank memory is allocated here (this stream owns it); under capture the events become graph edges.
-            main = torch.cuda.current_stream(s.device)
-            fork = HF.SideStream.get(s.device)
-            per_level, k = [], 0
-            for g in groups:
-                per_level.append(layers[k:k + len(g)])
-                k += len(g)
-            bufs = [torch.empty(HF.bank_floats(s, ls), device=s.device, dtype=torch.float32) if ls else None for ls in per_level]
-            fork.wait_stream(main)
-            refs = HF.signal2weights_multi(s, per_level[0], buf=bufs[0])
-            with torch.cuda.stream(fork):
-                for l in range(1, len(per_level)):
-                    if per_level[l]:
-                        refs = refs + HF.signal2weights_multi(s, per_level[l], buf=bufs[l])
-                        ev = torch.cuda.Event()
-                        ev.record(fork)
-                        bank_events[l] = ev
-        elif 0 < n_early < len(flat) and s.is_cuda and HF.USE_SIDE_STREAM:
-            main = torch.cuda.current_stream(s.device)      # the MODEL's device, not the caller's current one
-            side = HF.SideStream.get(s.device)
-            side.wait_stream(main)
-            with torch.cuda.stream(side):
-                late = HF.signal2weights_multi(s, layers[n_early:])
-            refs = HF.signal2weights_multi(s, layers[:n_early]) + late
-            cnt = 0
-            for l, g in enumerate(groups):
-                cnt += len(g)
-                if cnt > n_early:
-                    join_level = l
-                    break
-        else:
-            refs = HF.signal2weights_multi(s, layers)
-        banks, k = [], 0
-        for g in groups:
-            banks.append(refs[k:k + len(g)])
-            k += len(g)
-        p, first = None, 0
-        if (getattr(self, 'chain_k1', False) or HF.K1_CHAIN) and side is None and not bank_events and s.is_cuda:
-            # the three coarse k = 1 levels as ONE launch (hs_k1_chain_fwd); None: the shape / residency is not covered
-            done = self._run_k1_chain(x, banks)
-            p, first = done if done is not None else (None, 0)
-        for level in range(first, self.levels):
-            level_layers = getattr(self, f'level_{level}')
-            if side is not None and level == join_level:
-                torch.cuda.current_stream(s.device).wait_stream(side)
-                side = None
-            if level in bank_events:
-                torch.cuda.current_stream(s.device).wait_event(bank_events.pop(level))
-            # cat(coords, skip, bilinear(p)) is never built: the stage kernel's prologue generates it
-            stage = HF.StageInput(x[-level - 1], p, coords=True)
-            p = level_layers(stage, banks[level])
-        if side is not None:
-            torch.cuda.current_stream(s.device).wait_stream(side)
-        for ev in bank_events.values():                     # (the out_fc's bank, or a level without hyper modules: join before leaving)
-            torch.cuda.current_stream(s.device).wait_event(ev)
-        if self.out_fc is not None:
-            p = self.out_fc(p, banks[-1])
-        if masks:
-            return HF.upsample_argmax(p, x[0].shape[2:]) if score is None else final_masks_scored(p, x[0].shape[2:], score)
-        if p.shape[2:] != x[0].shape[2:]:
-            p = HF.upsample_bilinear(p, x[0].shape[2:], out=getattr(self, 'output_buffer', None))
-        return p
+        plan = self._bank_plan(x, s)
+        banks = self._make_banks(plan, s)
+        # the three coarse k = 1 levels as ONE launch (hs_k1_chain_fwd); None: the shape / residency is not covered
+        done = self._run_k1_chain(x, banks) if plan.chain else None
+        p, first = done if done is not None else (None, 0)
+        p = self._run_levels(x, s, banks, plan, first, p)
+        return finish_decoder(self, p, x[0].shape[2:], masks, score)
 
 
 class WeightMapper(nn.Module):

@@ -17,10 +17,10 @@ from .. import autograd as HA
 from .. import functional as HF
 import numpy as np
 
-from ._common import EpochOnModeSwitch, HyperGenBase, final_masks_scored, coordinate_grid, per_level, plan_levels, register_coordinate_buffers
-from .hyperseg_v1_0 import (HyperPatch, HyperPatchConv2d, HyperPatchInvertedResidual, HyperPatchNoPadding,  # noqa: F401
-                            WeightMapper, _SignalToWeights, divide_feature, make_hyper_patch_conv2d_block,
-                            next_multiply)
+from ._common import EpochOnModeSwitch, HyperGenBase, finish_decoder, coordinate_grid, per_level, plan_levels, register_coordinate_buffers
+from .hyperseg_v1_0 import (IN_CONSUMER, LAUNCH, BankPlan, HyperPatch, HyperPatchConv2d, HyperPatchInvertedResidual,  # noqa: F401
+                            HyperPatchNoPadding, WeightMapper, _SignalToWeights, bank_in_consumer, chain_wanted, divide_feature,
+                            make_hyper_patch_conv2d_block, next_multiply, run_decoder_chain)
 from .layers.meta_sequential import MetaSequential
 
 
@@ -139,6 +139,21 @@ class MultiScaleDecoder(EpochOnModeSwitch, nn.Module):
             p = HA.upsample_bilinear(p, x[0].shape[2:])
         return p
 
+    def _bank_plan(self, x, s):
+        """v1_0's BankPlan over the weight layers (``sources``: one entry per weight layer; no co-scheduling here).  The chained
+        launch (levels 0-2, which then need weight layers of their own) reads materialised banks: where it is to be tried, those
+        levels' banks come from the one signal2weights launch; every other coarse k = 1 level with a weight layer of its own
+        generates its bank inside the consumer where bank_in_consumer says so.  No device work."""
+        own = min(self.unify_level - 1, self.levels)
+        chain = self.unify_level - 1 >= 3 and chain_wanted(self)
+        sources = [LAUNCH] * len(self.weight_blocks)
+        for lvl in range(3 if chain else 0, own):
+            block = self.level_blocks[lvl]
+            conv = block[0][0] if len(block) == 1 and isinstance(block[0], MetaSequential) and len(block[0]) else None
+            if bank_in_consumer(conv, self.weight_blocks[lvl].s2w_shape(), x[-lvl - 1].shape[-2:], s.shape[-2:]):
+                sources[lvl] = IN_CONSUMER
+        return BankPlan(sources, None, chain)
+
     def forward(self, x, s, masks=False, score=None):
         if self.out_fc is not None:
             raise NotImplementedError('with_out_fc=True: the reference itself feeds the raw signal to out_fc here '
@@ -146,36 +161,15 @@ class MultiScaleDecoder(EpochOnModeSwitch, nn.Module):
         if self.training or HA.needs_grad(s, *x, *self.parameters()):
             assert not masks, 'masks=True is an inference-only shortcut'
             return self._forward_autograd(x, s)
-        wl = list(self.weight_blocks)
+        plan = self._bank_plan(x, s)
         ul = self.unify_level
-        layers = [m.s2w_layer(s.device) for m in wl]
-        # coarse k = 1 levels with a weight layer of their own generate their bank inside the consumer; every other
-        # weight layer is produced by one launch
-        fh, fw = s.shape[-2:]
-        refs = [None] * len(wl)
-        # the chained launch (levels 0-2) reads materialised banks: with it on, those levels' banks come from the one signal2weights
-        # launch instead of being generated inside their consumers (the SignalRefs made the hook below dead)
-        chain = (getattr(self, 'chain_k1', False) or HF.K1_CHAIN) and s.is_cuda and ul - 1 >= 3 and \
-            not (getattr(self, '_k1_chain', None) is not None and getattr(self._k1_chain, 'refuses_everything', False))
-        for lvl in range(min(ul - 1, self.levels)):
-            if chain and lvl < 3:
-                continue
-            mods = [m for m in self.level_blocks[lvl][0].children()] if len(self.level_blocks[lvl]) == 1 and \
-                isinstance(self.level_blocks[lvl][0], MetaSequential) else []
-            hl, wdt = x[-lvl - 1].shape[-2:]
-            if mods and isinstance(mods[0], HyperPatchNoPadding) and mods[0].groups == 1 and \
-                    hl % fh == 0 and wdt % fw == 0 and (hl // fh) * (wdt // fw) <= HF.BANK_IN_CONSUMER_MAX_PIXELS and \
-                    layers[lvl]['signal_channels'] // layers[lvl]['groups'] <= 80:
-                refs[lvl] = HF.SignalRef(s, layers[lvl])
-        keep = [i for i, r in enumerate(refs) if r is None]
-        for i, r in zip(keep, HF.signal2weights_multi(s, [layers[i] for i in keep])):
-            refs[i] = r
-        p, first = None, 0
-        if chain:
-            # levels 0-2 have weight layers of their own: one launch for the three of them (hs_k1_chain_fwd); None: shape / residency not covered
-            from .hyperseg_v1_0 import run_decoder_chain
-            done = run_decoder_chain(self, [self.level_blocks[l] for l in range(3)], refs[:3], x)
-            p, first = done if done is not None else (None, 0)
+        layers = [m.s2w_layer(s.device) for m in self.weight_blocks]
+        keep = [l for l, v in zip(layers, plan.sources) if v == LAUNCH]
+        made = iter(HF.signal2weights_multi(s, keep))
+        refs = [next(made) if v == LAUNCH else HF.SignalRef(s, l) for l, v in zip(layers, plan.sources)]
+        # levels 0-2 as one launch (hs_k1_chain_fwd); None: shape / residency not covered
+        done = run_decoder_chain(self, [self.level_blocks[l] for l in range(3)], refs[:3], x) if plan.chain else None
+        p, first = done if done is not None else (None, 0)
         for level in range(first, self.levels):
             stage = HF.StageInput(x[-level - 1], p, coords=True)
             if level < ul - 1:
@@ -187,11 +181,7 @@ class MultiScaleDecoder(EpochOnModeSwitch, nn.Module):
                 # rows [r0, r1) of the shared bank, consumed in place (reference: w[:, r0:r1] + .contiguous())
                 w = HF.BankRef(shared.bank[:, r0:r1], shared.shape[0], r1 - r0, shared.grid)
             p = self.level_blocks[level](stage, [w])
-        if masks:
-            return HF.upsample_argmax(p, x[0].shape[2:]) if score is None else final_masks_scored(p, x[0].shape[2:], score)
-        if p.shape[2:] != x[0].shape[2:]:
-            p = HF.upsample_bilinear(p, x[0].shape[2:], out=getattr(self, 'output_buffer', None))
-        return p
+        return finish_decoder(self, p, x[0].shape[2:], masks, score)
 
 
 class HyperGen(HyperGenBase):

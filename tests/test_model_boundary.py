@@ -574,3 +574,71 @@ def test_the_product_never_imports_the_oracle():
     tree, hits = oracle_imports(os.path.join(root, 'bench.py'))
     cb = next(n for n in tree.body if isinstance(n, ast.FunctionDef) and n.name == 'cpu_baseline')
     assert hits and all(cb.lineno <= h <= cb.end_lineno for h in hits), 'bench.py may import oracle/ inside cpu_baseline() only'
+
+
+def _pyramid_shapes(model, size):
+    """Meta tensors shaped like the decoder's inputs at ``size``: the image, the encoder's taps but the last, and the signal."""
+    h, w = size
+    chans = [3] + list(model.backbone.feat_channels)
+    x = [torch.empty(1, c, h >> i, w >> i, device='meta') for i, c in enumerate(chans[:-1])]
+    return x, torch.empty(1, chans[-1], h >> 5, w >> 5, device='meta')
+
+
+def test_decoder_bank_plan_on_the_host(monkeypatch, model_m):
+    """MultiScaleDecoder._bank_plan reads shapes and switches only, so which launches a configuration issues is checked without a device:
+    HyperSeg-M with the default switches (every bank from the one launch, the chain iff ``chain_k1``), with co-scheduling on (the carry
+    map of _coschedule_plan's docstring, no chain) and with banks generated in the consumer at 128 x 256 (levels 0-2, two layers left for
+    the launch, no chain); the unify decoder picks the same levels through the same predicate."""
+    from hyperseg_amd import configs, functional as HF
+    from hyperseg_amd.models.hyperseg_v1_0 import CARRIED, IN_CONSUMER, LAUNCH
+    for name, value in (('COSCHEDULE_BANKS', False), ('BANK_IN_CONSUMER_MAX_PIXELS', 0), ('K1_CHAIN', False)):
+        monkeypatch.setattr(HF, name, value)
+    d = model_m.decoder
+    monkeypatch.setattr(d, 'chain_k1', False, raising=False)
+    x, s = _pyramid_shapes(model_m, (512, 1024))
+    plan = d._bank_plan(x, s)
+    assert plan.sources == [[LAUNCH]] * 5 + [[]] and plan.carry is None and plan.chain is False
+    d.chain_k1 = True
+    plan = d._bank_plan(x, s)
+    assert plan.sources == [[LAUNCH]] * 5 + [[]] and plan.carry is None and plan.chain is True
+    monkeypatch.setattr(HF, 'COSCHEDULE_BANKS', True)
+    plan = d._bank_plan(x, s)
+    assert plan.carry == {0: [1, 2], 1: [3], 2: [4]} and plan.chain is False
+    assert plan.sources == [[LAUNCH]] + [[CARRIED]] * 4 + [[]]
+    monkeypatch.setattr(HF, 'COSCHEDULE_BANKS', False)
+    monkeypatch.setattr(HF, 'BANK_IN_CONSUMER_MAX_PIXELS', 64)
+    x, s = _pyramid_shapes(model_m, (128, 256))
+    plan = d._bank_plan(x, s)
+    assert plan.sources == [[IN_CONSUMER]] * 3 + [[LAUNCH]] * 2 + [[]] and plan.carry is None and plan.chain is False
+    assert sum(v == LAUNCH for g in plan.sources for v in g) == 2
+    # co-scheduling does not come back while a bank is generated in its consumer
+    monkeypatch.setattr(HF, 'COSCHEDULE_BANKS', True)
+    assert d._bank_plan(x, s) == plan
+    monkeypatch.setattr(HF, 'COSCHEDULE_BANKS', False)
+    unify = configs.build('hyperseg-s').eval()
+    u = unify.decoder
+    x, s = _pyramid_shapes(unify, (128, 256))
+    plan = u._bank_plan(x, s)
+    assert plan.sources == [IN_CONSUMER] * 3 + [LAUNCH] and plan.carry is None and plan.chain is False
+    u.chain_k1 = True                       # the chained launch reads materialised banks
+    plan = u._bank_plan(x, s)
+    assert plan.sources == [LAUNCH] * 4 and plan.chain is True
+    monkeypatch.setattr(HF, 'BANK_IN_CONSUMER_MAX_PIXELS', 0)
+    u.chain_k1 = False
+    plan = u._bank_plan(x, s)
+    assert plan.sources == [LAUNCH] * 4 and plan.chain is False
+    with pytest.raises(ValueError, match='signal slice'):
+        d._bank_plan(x, s[:, :8])
+
+
+def test_the_stream_fork_routes_are_gone():
+    """The two HS_SIDE_STREAM bank forks (measured slower on the whole frame, untested, parallel graph branches) left with the decoder's
+    forward refactor: nothing in the package names them any more."""
+    import os
+    root = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'hyperseg_amd')
+    words = ('HS_SIDE_STREAM', 'USE_SIDE_STREAM', 'SideStream', 'PIPELINE_BANKS')
+    for d, _, files in os.walk(root):
+        for f in files:
+            if f.endswith(('.py', '.hip', '.h', '.hpp', '.cpp', '.txt', '.md', '.cmake')):
+                text = open(os.path.join(d, f), errors='replace').read()
+                assert not [w for w in words if w in text], f'{os.path.join(d, f)} names a removed stream-fork route'
