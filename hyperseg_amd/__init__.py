@@ -6,4 +6,7 @@ def __getattr__(name):
     if name == 'InputNorm':
         from .utils.inference import InputNorm
         return InputNorm
+    if name == 'Overlay':
+        from .utils.inference import Overlay
+        return Overlay
     raise AttributeError(f'module {__name__!r} has no attribute {name!r}')

@@ -11,7 +11,7 @@ Reproduces the reference's protocol on synthetic frames (no dataset, checkpoint 
 ``torch.cuda.synchronize()`` is guarded so that the plumbing also runs on a CPU-only box (with a CPU-capable model).
 
     python -m hyperseg_amd.fps --config hyperseg-m --iterations 200 [--prepare] [--graph] [--remove-bn] [--batch-size 1]
-                               [--uint8 [--layout hwc|chw]]
+                               [--uint8 [--layout hwc|chw] [--overlay]]
 
 ``--uint8`` feeds uint8 frames (what a decoder or camera delivers) to a model with the default ``InputNorm`` attached: the
 host-to-device copy moves one byte per value and ToTensor + Normalize run on the device (``utils.inference.InputNorm``).
@@ -166,12 +166,16 @@ def _sync(device):
 
 
 @torch.no_grad()
-def measure_fps(model, batches, device, num_classes, passes=2, fused_metrics=False):
+def measure_fps(model, batches, device, num_classes, passes=2, fused_metrics=False, overlay=False):
     """``batches``: list of (input, target) host tensors (inputs pinned when CUDA is used).  Runs ``passes`` passes over
     them and reports the LAST one (the reference's warm-up + timed pass).  Returns a dict.  ``fused_metrics``: where the
     model has ``evaluate`` (a HyperGen, a GraphedModel) the frame is scored by the forward's last launch -- INSIDE the timed
-    region, which the reference's protocol keeps outside it; models without it are scored as before."""
+    region, which the reference's protocol keeps outside it; models without it are scored as before.  ``overlay``: every frame
+    is served by ``model.overlay`` (masks + the uint8 display blended with ``overlay_style``) instead of the forward, inside the
+    timed region; the masks are scored outside it as the reference's protocol does."""
     result = {}
+    if overlay and fused_metrics:
+        raise ValueError('overlay and fused_metrics both ride on the final upsample launch: one of them per run')
     fused = bool(fused_metrics) and hasattr(model, 'evaluate')
     owns = fused and getattr(model, 'owns_confusion', False)        # GraphedModel: the matrix lives with the graph
     for p in range(passes):
@@ -191,6 +195,8 @@ def measure_fps(model, batches, device, num_classes, passes=2, fused_metrics=Fal
                 x = inp.to(device, non_blocking=True)
             if fused:
                 pred = model.evaluate(x, target) if owns else model.evaluate(x, target, conf)
+            elif overlay:
+                pred = model.overlay(x)[0]
             else:
                 pred = model(x)
             _sync(device)
@@ -240,6 +246,9 @@ def main(argv=None):
                     help='uint8 frames with the default InputNorm attached to the model: normalised on the device, a quarter of the '
                          'bytes over the host link')
     ap.add_argument('--layout', choices=('hwc', 'chw'), default='hwc', help='layout of the --uint8 frames')
+    ap.add_argument('--overlay', action='store_true',
+                    help="serve the display as well (model.overlay): the class map coloured with a seeded synthetic palette and alpha-blended "
+                         "over the uint8 frame by the forward's last launch, inside the timed region; needs --uint8")
     ap.add_argument('-t', '--trace', action='store_true',
                     help="the reference's torch.jit.trace switch (test_fps.py:49-50, 150-152).  The mirror's modules call the C ABI through "
                          "ctypes, which the tracer cannot see, so a traced module would be wrong; the purpose of tracing there -- no Python / "
@@ -251,6 +260,12 @@ def main(argv=None):
     args = ap.parse_args(argv)
     if args.trace:
         args.graph = True
+    if args.overlay and not args.uint8:
+        raise SystemExit('--overlay blends over the uint8 frames: it needs --uint8')
+    if args.overlay and args.fused_metrics:
+        raise SystemExit('--overlay and --fused-metrics both ride on the final upsample launch: one of them per run')
+    if args.overlay and args.gpus and len(args.gpus) > 1:
+        raise SystemExit('--overlay serves one device: with several --gpus run one process per GPU')
 
     from . import configs
     from .utils.synthetic import fill_by_name
@@ -270,6 +285,11 @@ def main(argv=None):
     if args.uint8:
         from .utils.inference import InputNorm
         model.input_norm = InputNorm(layout=args.layout)
+    if args.overlay:
+        from .utils.inference import Overlay
+        palette = torch.randint(0, 256, (spec['num_classes'], 3), generator=torch.Generator().manual_seed(0))
+        model.overlay_style = Overlay(palette, layout=args.layout)
+        model.inference_hflip = False        # inert for tensor inputs, but overlay() takes its segment() + blend route while it is set
     model = model.to(device)
     if args.gpus and len(args.gpus) > 1 and device.type == 'cuda':
         if args.graph:
@@ -282,7 +302,7 @@ def main(argv=None):
     uniq = synthetic_batches(min(args.distinct, args.iterations), bs, spec['size'], spec['num_classes'], device,
                              uint8=args.uint8, layout=args.layout)
     batches = [uniq[i % len(uniq)] for i in range(args.iterations)]
-    res = measure_fps(model, batches, device, spec['num_classes'], fused_metrics=args.fused_metrics)
+    res = measure_fps(model, batches, device, spec['num_classes'], fused_metrics=args.fused_metrics, overlay=args.overlay)
     frame = uniq[0][0]
     res.update(input_dtype=str(frame.dtype).replace('torch.', ''), input_bytes_per_frame=frame[0].numel() * frame.element_size())
     res.update(config=args.config, batch_size=bs, size=list(spec['size']), device=str(device), remove_bn=args.remove_bn,
@@ -291,6 +311,8 @@ def main(argv=None):
     if args.fused_metrics:
         res.update(fused_metrics=True, protocol=res['protocol'] + ' + confusion matrix counted inside the timed region by the '
                    "forward's last launch (the reference scores outside it)")
+    if args.overlay:
+        res.update(overlay=True, protocol=res['protocol'] + " + uint8 overlay blended inside the timed region by the forward's last launch")
     print(json.dumps(res))
     return res
 

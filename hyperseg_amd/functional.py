@@ -1402,6 +1402,66 @@ def confusion_update(pred, target, num_classes, out=None, per_image=False):
     return out
 
 
+def _overlay_out(out, frames):
+    if out is None:
+        return torch.empty_like(frames)
+    if not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or tuple(out.shape) != tuple(frames.shape) or out.device != frames.device \
+            or not out.is_contiguous():
+        raise ValueError(f'out must be a contiguous uint8 tensor of shape {tuple(frames.shape)} on {frames.device}, got '
+                         f'{getattr(out, "dtype", type(out))} {tuple(getattr(out, "shape", ()))} on {getattr(out, "device", None)}')
+    lo, hi = frames.data_ptr(), frames.data_ptr() + frames.numel()
+    if out.data_ptr() < hi and lo < out.data_ptr() + out.numel():
+        raise ValueError('out overlaps the frames: the overlay is written beside its input, never over it')
+    return out
+
+
+def _overlay_frames(frames, style, name='frames'):
+    if not frames.is_cuda:
+        raise ValueError(f'{name} are on {frames.device}: the overlay kernels run on the GPU (Overlay.blend blends CPU tensors)')
+    return frames if frames.is_contiguous() else frames.contiguous()
+
+
+@_on_operand_device
+def overlay(masks, frames, style, out=None):
+    """``style`` (a ``utils.inference.Overlay``) applied to finished uint8 ``masks`` (B, H, W) and the uint8 ``frames`` they belong to
+    ((B, H, W, 3) or (B, 3, H, W) as ``style.layout`` says): the uint8 overlay in the frames' layout, one launch (hs_overlay_fwd), equal
+    to ``style.blend`` on the CPU byte for byte.  ``out``: a contiguous uint8 tensor of the frames' shape to write into (not the frames
+    themselves).  Nothing here reads the device: the call is capturable in a HIP graph."""
+    style.check(frames, masks)
+    frames = _overlay_frames(frames, style)
+    masks = masks if masks.is_contiguous() else masks.contiguous()
+    b, h, w = style.frame_size(frames)
+    out = _overlay_out(out, frames)
+    st = _hip.lib.hs_overlay_fwd(masks.data_ptr(), frames.data_ptr(), _LAYOUT_CODES[style.layout], b, h, w,
+                                 _hip.dev_ptr(style.tables(frames.device), 'tables'), style.num_colors, style.ignore_index,
+                                 out.data_ptr(), _hip.stream_ptr())
+    _hip.check(st, 'hs_overlay_fwd')
+    return out
+
+
+@_on_operand_device
+def upsample_overlay(x, size, frames, style, out=None):
+    """``upsample_argmax(x, size)`` with ``style`` blended over ``frames`` (uint8, at ``size``, in ``style.layout``) as the same launch's
+    epilogue (hs_upsample_overlay_fwd).  Returns ``(masks, overlay)``: the uint8 masks, bit-identical to ``upsample_argmax``'s, and the
+    uint8 overlay, equal to ``overlay(masks, frames, style)``.  ``out``: as :func:`overlay`'s.  Capturable."""
+    if not isinstance(x, torch.Tensor) or x.dim() != 4:
+        raise ValueError('x must be (B, C, Hi, Wi) logits')
+    b, c, hi, wi = x.shape
+    ho, wo = (int(s) for s in size)
+    if tuple(style.frame_size(frames)) != (b, ho, wo):
+        raise ValueError(f'the frames are {tuple(style.frame_size(frames))} (B, H, W), the masks will be {(b, ho, wo)}')
+    frames = _overlay_frames(frames, style)
+    if frames.device != x.device:
+        raise ValueError(f'the frames are on {frames.device}, the logits on {x.device}')
+    out = _overlay_out(out, frames)
+    mask = torch.empty(b, ho, wo, device=x.device, dtype=torch.uint8)
+    st = _hip.lib.hs_upsample_overlay_fwd(_hip.dev_ptr(x, 'x'), b, c, hi, wi, ho, wo, frames.data_ptr(), _LAYOUT_CODES[style.layout],
+                                          _hip.dev_ptr(style.tables(x.device), 'tables'), style.num_colors, style.ignore_index,
+                                          mask.data_ptr(), out.data_ptr(), _hip.stream_ptr())
+    _hip.check(st, 'hs_upsample_overlay_fwd')
+    return mask, out
+
+
 # ------------------------------------------------------------------------------------------
 # small caches keyed on parameter versions (host-side only; used by the fused inference route --
 # tensors that require grad take the hyperseg_amd.autograd route, which folds nothing)

@@ -66,12 +66,33 @@ def final_masks_scored(p, size, score):
     return HF.upsample_confusion(p, size, target, num_classes, out=out, per_image=per_image, masks=True)[1]
 
 
-def finish_decoder(decoder, p, size, masks, score):
+def final_masks_overlaid(p, size, overlay):
+    """The decoders' ``masks=True`` epilogue with the display blended by the same launch: ``overlay`` = (frames, style, out) -- returns
+    ``(masks, overlay)`` of ``HF.upsample_overlay`` (the masks: ``HF.upsample_argmax(p, size)``'s)."""
+    frames, style, out = overlay
+    return HF.upsample_overlay(p, size, frames, style, out=out)
+
+
+def final_masks(p, size, score=None, overlay=None):
+    """What ``masks=True`` returns for the last level's output ``p``: the uint8 argmax masks at ``size`` straight from the final upsample
+    launch -- scored by that launch with ``score``, or blended by it with ``overlay`` (then ``(masks, overlay)``); one or the other."""
+    if score is not None and overlay is not None:
+        raise ValueError('score= and overlay= both ride on the final upsample launch: one of them per forward for now')
+    if overlay is not None:
+        return final_masks_overlaid(p, size, overlay)
+    return HF.upsample_argmax(p, size) if score is None else final_masks_scored(p, size, score)
+
+
+def finish_decoder(decoder, p, size, masks, score, overlay=None):
     """What the v1_0 and unify decoders return for their last level's output ``p``: with ``masks``, the uint8 argmax masks at ``size``
-    straight from the final upsample launch (scored by the same launch when ``score`` is given); otherwise the logits, resized to
-    ``size`` -- into ``decoder.output_buffer`` where a serving wrapper has set one."""
+    straight from the final upsample launch (scored by the same launch when ``score`` is given, blended over the frames by it when
+    ``overlay`` is: :func:`final_masks`); otherwise the logits, resized to ``size`` -- into ``decoder.output_buffer`` where a serving
+    wrapper has set one."""
     if masks:
-        return HF.upsample_argmax(p, size) if score is None else final_masks_scored(p, size, score)
+        return final_masks(p, size, score, overlay)
+    if score is not None and overlay is not None:
+        raise ValueError('score= and overlay= both ride on the final upsample launch: one of them per forward for now')
+    assert overlay is None, 'overlay= rides on the masks=True epilogue'
     if p.shape[2:] != size:
         p = HF.upsample_bilinear(p, size, out=getattr(decoder, 'output_buffer', None))
     return p
@@ -96,6 +117,8 @@ class HyperGenBase(EpochOnModeSwitch, nn.Module):
     # a utils.inference.InputNorm: uint8 frames are then accepted and normalised on the device.  A plain attribute -- no parameter,
     # no buffer: state_dict() and strict loading of reference checkpoints are as they were
     input_norm = None
+    # a utils.inference.Overlay: what ``overlay()`` colours and blends with.  A plain attribute as well
+    overlay_style = None
 
     def frame_size(self, x):
         """(H, W) of an input tensor: a float image (B, 3, H, W), or uint8 frames in ``input_norm``'s layout."""
@@ -123,7 +146,7 @@ class HyperGenBase(EpochOnModeSwitch, nn.Module):
     def hyper_params(self):
         return self.decoder.hyper_params
 
-    def process_single_tensor(self, x, hflip=False, masks=False, score=None):
+    def process_single_tensor(self, x, hflip=False, masks=False, score=None, overlay=None):
         frame = None
         if x.dtype == torch.uint8:
             norm = self._require_norm()
@@ -142,9 +165,14 @@ class HyperGenBase(EpochOnModeSwitch, nn.Module):
         if isinstance(head_out, torch.Tensor):
             head_out = head_out.contiguous()
         pyramid = [t.contiguous() for t in [x] + features[:-1]]
+        if score is not None and overlay is not None:
+            raise ValueError('score= and overlay= both ride on the final upsample launch: one of them per forward for now')
         if score is not None:
             assert masks and not hflip, 'scoring rides on the masks=True epilogue of an unflipped frame'
             y = self.decoder(pyramid, head_out, masks=True, score=score)
+        elif overlay is not None:
+            assert masks and not hflip, 'the overlay rides on the masks=True epilogue of an unflipped frame'
+            return self.decoder(pyramid, head_out, masks=True, overlay=overlay)
         else:
             y = self.decoder(pyramid, head_out, masks=True) if masks else self.decoder(pyramid, head_out)
         return torch.flip(y, [-1]) if hflip else y
@@ -195,6 +223,45 @@ class HyperGenBase(EpochOnModeSwitch, nn.Module):
         else:
             confmat.update(target.flatten(), masks.flatten())
         return masks
+
+    @torch.no_grad()
+    def overlay(self, x, frames=None, style=None, out=None):
+        """``segment(x)`` plus the display: returns ``(masks, overlay)`` -- the uint8 masks and the class map coloured and alpha-blended
+        over the uint8 frames, as uint8 in the frames' layout (``style``: a ``utils.inference.Overlay``, default
+        ``self.overlay_style``).  A uint8 ``x`` is its own frame; a float ``x`` needs ``frames=``, the uint8 frames of the same size.
+        A single CUDA tensor in eval mode without h-flip inference is blended by the forward's last launch
+        (``HF.upsample_overlay``) -- no further launch, no read of the device, whether the frame went into the stem launch or through
+        ``image_ingest``.  Everything else -- list inputs, h-flip inference, training mode, CPU -- computes the masks the way
+        ``segment()`` does and calls ``style.blend``.  Same bytes on every route.  ``out``: a uint8 tensor of the frames' shape for
+        the overlay."""
+        style = self.overlay_style if style is None else style
+        if style is None:
+            raise TypeError('overlay() needs a style: set model.overlay_style = hyperseg_amd.Overlay(color_map, alpha, ignore_index, '
+                            'layout) or pass style=')
+        first = x if isinstance(x, torch.Tensor) else x[0]
+        if frames is None:
+            if first.dtype != torch.uint8:
+                raise TypeError('a float input needs frames=: the uint8 frames of the same size that the overlay is blended over '
+                                '(a uint8 input is its own frame)')
+            if style.layout != self._require_norm().layout:
+                raise ValueError(f"the input frames are '{self.input_norm.layout}' (model.input_norm), the style blends over "
+                                 f"'{style.layout}' frames")
+            frames = first
+        size = (first.shape[0],) + self.frame_size(first)
+        if tuple(style.frame_size(frames)) != size:
+            raise ValueError(f'frames are {tuple(style.frame_size(frames))} (B, H, W), the input is {size}')
+        fused = isinstance(x, torch.Tensor) and x.is_cuda and frames.is_cuda and not self.training and not self.inference_hflip
+        if fused:
+            got = self.process_single_tensor(x, masks=True, overlay=(frames, style, out))
+            if isinstance(got, tuple):
+                return got
+            raise RuntimeError('the decoder returned logits from its masks=True route: nothing was blended')
+        masks = self.segment(x)
+        blended = style.blend(frames.to(masks.device), masks)
+        if out is not None:
+            out.copy_(blended)
+            blended = out
+        return masks, blended
 
     def gather_results(self, x, y=None):
         assert x is not None

@@ -17,7 +17,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from .. import functional as HF
-from ._common import EpochOnModeSwitch, HyperGenBase, final_masks_scored, coordinate_grid, per_level
+from ._common import EpochOnModeSwitch, HyperGenBase, final_masks, coordinate_grid, per_level
 from .layers.meta_patch import MetaPatchConv2d, make_meta_patch_conv2d_block
 from .layers.meta_sequential import MetaSequential
 
@@ -146,7 +146,7 @@ class MultiScaleDecoder(EpochOnModeSwitch, nn.Module):
         self.hyper_params = int(self._ranges[-1])
         self._ranges.append(self.hyper_params)
 
-    def forward(self, x, w, masks=False, score=None):
+    def forward(self, x, w, masks=False, score=None, overlay=None):
         assert isinstance(w, (list, tuple))
         assert len(x) <= self.levels
         p = None
@@ -156,9 +156,7 @@ class MultiScaleDecoder(EpochOnModeSwitch, nn.Module):
         if self.out_fc is not None:
             p = self.out_fc(p, w[-1])
         if masks and not (self.training or p.requires_grad):
-            if score is None:
-                return HF.upsample_argmax(p.contiguous(), p.shape[2:])       # identity resize: argmax over classes only
-            return final_masks_scored(p.contiguous(), p.shape[2:], score)
+            return final_masks(p.contiguous(), p.shape[2:], score, overlay)      # identity resize: argmax over classes only
         return p
 
 

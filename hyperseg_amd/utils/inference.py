@@ -88,6 +88,108 @@ class InputNorm:
         return f'InputNorm(mean={self.mean.tolist()}, std={self.std.tolist()}, layout={self.layout!r})'
 
 
+class Overlay:
+    """The display of a prediction as data: the class map coloured with ``color_map`` and alpha-blended over the uint8 frame, returned as
+    uint8 RGB in the frame's ``layout`` -- the reference's ``tensor2rgb(blend_seg(img, pred, color_map, alpha, ignore_index))``
+    (test.py:230-292, utils/seg_utils.py:82-103, utils/img_utils.py:62-75) for ``img = (float32(frame) / 255 - 0.5) / 0.5``, the
+    reference's ``rgb2tensor`` convention.  Defaults: those of test.py's display.  ``color_map``: (n, 3) integers in [0, 255],
+    1 <= n <= 256 (the package ships no dataset palettes).  A pixel whose class is ``ignore_index``, or >= n, keeps the frame's byte;
+    ``ignore_index=-1`` blends every class below n.  Attached to a model (``model.overlay_style = Overlay(...)``) it serves
+    ``model.overlay`` / ``GraphedModel.overlay``.  Not a parameter, not a buffer: state dicts are unaffected.
+
+    It owns three float32 tables, built on the CPU by exactly the reference's float32 operations, so the kernels only look up and add:
+    ``am = 1 - 1 * alpha`` (the blended pixels' ``alpha_mask``), ``A[v] = img[v] * am``, ``A1[v] = img[v]``,
+    ``S[c][ch] = (color_map[c][ch] / 128 - 1) * (1 - am)``; a blended pixel is ``uint8(rint(((A[v] + S[c][ch]) * 0.5 + 0.5) * 255))``, a
+    pixel left alone the same expression on ``A1[v]`` (+ 0), which returns ``v`` for all 256 bytes.  The reference's colour scale is
+    1 / 128, not 1 / 127.5: colour c contributes c * 255 / 256 -- kept, it is what ``blend_seg`` displays."""
+
+    LAYOUTS = InputNorm.LAYOUTS
+
+    def __init__(self, color_map, alpha=0.75, ignore_index=0, layout='hwc'):
+        if layout not in self.LAYOUTS:
+            raise ValueError(f'layout {layout!r}: expected one of {self.LAYOUTS}')
+        cm = torch.as_tensor(color_map)
+        if cm.dim() != 2 or cm.shape[1] != 3 or cm.shape[0] < 1:
+            raise ValueError(f'color_map must be (n, 3) with n >= 1, got shape {tuple(cm.shape)}')
+        if cm.shape[0] > 256:
+            raise ValueError(f'color_map has {cm.shape[0]} rows: class indices are uint8, at most 256 colours')
+        if cm.is_floating_point() or cm.dtype == torch.bool or cm.is_complex():
+            raise ValueError(f'color_map must hold integers in [0, 255], got {cm.dtype}')
+        if int(cm.min()) < 0 or int(cm.max()) > 255:
+            raise ValueError('color_map must hold integers in [0, 255]')
+        alpha = float(alpha)
+        if not 0.0 <= alpha <= 1.0:
+            raise ValueError(f'alpha must lie in [0, 1], got {alpha}')
+        n = cm.shape[0]
+        if int(ignore_index) != ignore_index or not -1 <= int(ignore_index) < n:
+            raise ValueError(f'ignore_index must be a class of the colour map (0..{n - 1}) or -1 (blend every class), got {ignore_index}')
+        self.color_map = cm.to(torch.uint8).cpu().clone()
+        self.alpha, self.ignore_index, self.layout = alpha, int(ignore_index), layout
+        img = (torch.arange(256, dtype=torch.float32).div(255) - 0.5) / 0.5
+        am = 1. - torch.ones((), dtype=torch.float32) * alpha              # blend_seg: 1. - (seg != ignore).float() * alpha
+        self.A1 = img
+        self.A = img * am
+        self.S = (self.color_map.to(torch.float32).div_(128.).sub_(1.) * (1. - am)).contiguous()
+        self._tables = {torch.device('cpu'): torch.cat((self.A, self.A1, self.S.flatten())).contiguous()}
+
+    @property
+    def num_colors(self):
+        return self.color_map.shape[0]
+
+    def tables(self, device='cpu'):
+        """``[A | A1 | S]`` as one flat float32 tensor of 512 + 3 n values on ``device`` (copied there on first use), what the two
+        launches read."""
+        device = torch.device(device)
+        if device.type == 'cuda' and device.index is None:
+            device = torch.device('cuda', torch.cuda.current_device())
+        t = self._tables.get(device)
+        if t is None:
+            t = self._tables[torch.device('cpu')].to(device)
+            if device.type == 'cuda' and not torch.cuda.is_current_stream_capturing():
+                torch.cuda.current_stream(device).synchronize()      # other streams (a capture's side stream, replicas) may read it next
+            self._tables[device] = t
+        return t
+
+    def frame_size(self, frames):
+        """(B, H, W) of a batch of uint8 frames in this style's layout."""
+        if not isinstance(frames, torch.Tensor) or frames.dtype != torch.uint8 or frames.dim() != 4 \
+                or frames.shape[3 if self.layout == 'hwc' else 1] != 3:
+            want = '(B, H, W, 3)' if self.layout == 'hwc' else '(B, 3, H, W)'
+            raise ValueError(f"Overlay(layout='{self.layout}') blends over uint8 frames of shape {want}, got "
+                             f'{getattr(frames, "dtype", type(frames))} {tuple(getattr(frames, "shape", ()))}')
+        return (frames.shape[0], frames.shape[1], frames.shape[2]) if self.layout == 'hwc' else (frames.shape[0], frames.shape[2], frames.shape[3])
+
+    def check(self, frames, masks):
+        """Raises unless ``masks`` are uint8 (B, H, W) class maps of the uint8 ``frames``' size, on the frames' device."""
+        size = self.frame_size(frames)
+        if not isinstance(masks, torch.Tensor) or masks.dtype != torch.uint8:
+            raise ValueError(f'masks must be a uint8 tensor of class indices (segment() returns one; an int64 argmax takes '
+                             f'.to(torch.uint8)), got {getattr(masks, "dtype", type(masks))}')
+        if tuple(masks.shape) != size:
+            raise ValueError(f'masks have shape {tuple(masks.shape)}, the frames are {size} (B, H, W)')
+        if masks.device != frames.device:
+            raise ValueError(f'masks are on {masks.device}, the frames on {frames.device}')
+
+    def blend(self, frames_u8, masks):
+        """The uint8 overlay of ``frames_u8`` (this style's layout) and the uint8 class maps ``masks`` (B, H, W), in the frames' layout:
+        one ``functional.overlay`` launch on the GPU, the same table arithmetic as stock ops on the CPU.  Same bytes either way."""
+        self.check(frames_u8, masks)
+        if frames_u8.is_cuda:
+            from .. import functional as HF
+            return HF.overlay(masks, frames_u8, self)
+        n = self.num_colors
+        cls = masks.long()
+        blended = ((cls < n) & (cls != self.ignore_index)).unsqueeze(-1)                             # (B, H, W, 1)
+        v = (frames_u8 if self.layout == 'hwc' else frames_u8.permute(0, 2, 3, 1)).long()           # (B, H, W, 3)
+        a = torch.where(blended, self.A[v], self.A1[v])
+        s = torch.where(blended, self.S[cls.clamp(max=n - 1)], torch.zeros((), dtype=torch.float32))
+        out = (((a + s) * 0.5 + 0.5) * 255.0).round().to(torch.uint8)
+        return (out if self.layout == 'hwc' else out.permute(0, 3, 1, 2)).contiguous()
+
+    def __repr__(self):
+        return f'Overlay({self.num_colors} colours, alpha={self.alpha}, ignore_index={self.ignore_index}, layout={self.layout!r})'
+
+
 @torch.no_grad()
 def _fold(conv, bn):
     scale = bn.weight / torch.sqrt(bn.running_var + bn.eps)
@@ -792,7 +894,9 @@ class GraphedModel(nn.Module):
                         ch.request_error_copy(device)
             else:
                 go()
-            return static_out.clone() if self.clone_output else static_out
+            if not self.clone_output:
+                return static_out
+            return tuple(t.clone() for t in static_out) if isinstance(static_out, tuple) else static_out.clone()
 
     def forward(self, x):
         p = next(self.model.parameters(), None)
@@ -861,3 +965,38 @@ class GraphedModel(nn.Module):
 
             entry = self._capture(key, [x, target], device, run=run, warm=lambda xs, ts: run(xs, ts, scratch))
         return self._replay(entry, [x, target], device)
+
+    @torch.no_grad()
+    def overlay(self, x, frames=None):
+        """One replay per frame that also draws it: returns ``(masks, overlay)`` as ``model.overlay`` does, blended with
+        ``model.overlay_style``.  A uint8 ``x`` is its own frame; a float ``x`` comes with its uint8 ``frames``.  Both may live on the
+        device or in (pinned) host memory and are staged into static buffers of the graph.  The graph is the forward's chain of launches
+        with the last one replaced by ``functional.upsample_overlay``, keyed like the uint8 ``forward`` graphs plus the style (the
+        captured launch holds its tables, layout and ignore index).  Both returned tensors are graph-owned: valid until the next
+        ``overlay`` of the same shape, which overwrites them (``clone_output=True`` hands out copies).  What the graph cannot serve
+        (``forward``'s list, and h-flip inference) takes ``model.overlay``'s eager routes."""
+        model = self.model
+        style = getattr(model, 'overlay_style', None)
+        p = next(model.parameters(), None)
+        graphable = (style is not None and self._graphable(x) and x.dim() == 4 and not model.inference_hflip
+                     and (frames is not None or x.dtype == torch.uint8) and hasattr(model, 'process_single_tensor'))
+        if not graphable:
+            if p is not None and p.is_cuda:
+                x = [t.to(p.device, non_blocking=True) for t in x] if isinstance(x, (list, tuple)) else x.to(p.device, non_blocking=True)
+                frames = None if frames is None else frames.to(p.device, non_blocking=True)
+            return model.overlay(x, frames=frames)
+        device = p.device
+        if frames is None and style.layout != model._require_norm().layout:
+            raise ValueError(f"the input frames are '{model.input_norm.layout}' (model.input_norm), the style blends over '{style.layout}' frames")
+        size = (x.shape[0],) + tuple(model.frame_size(x))
+        if tuple(style.frame_size(x if frames is None else frames)) != size:
+            raise ValueError(f'frames are {tuple(style.frame_size(x if frames is None else frames))} (B, H, W), the input is {size}')
+        key = ('overlay', tuple(x.shape), x.dtype, None if frames is None else tuple(frames.shape), device, self._norm_of(x), style)
+        entry = self._graphs.get(key)
+        inputs = [x] if frames is None else [x, frames]
+        if entry is None:
+            def run(xs, fs=None):
+                return model.process_single_tensor(xs, masks=True, overlay=(xs if fs is None else fs, style, None))
+
+            entry = self._capture(key, inputs, device, run=run)
+        return self._replay(entry, inputs, device)

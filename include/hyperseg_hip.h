@@ -458,6 +458,22 @@ int hs_stem_dw_u8_fwd(const uint8_t* x, int32_t layout, const float* table, int3
                       const float* w_stem28, int32_t c_mid, const float* scale0, const float* shift0, int32_t stem_pad_t,
                       int32_t stem_pad_l, int32_t Hs, int32_t Ws, const float* w_dw, int32_t k, int32_t pad_t, int32_t pad_l,
                       const float* scale1, const float* shift1, float* y, float* pool_partial, void* stream);
+/* Served overlays (csrc/hs_overlay.hip): the class map coloured and alpha-blended over the uint8 frame, as uint8 RGB in the frame's
+ * layout -- the reference's tensor2rgb(blend_seg(img, pred, color_map, alpha, ignore_index)) (hyperseg/test.py:230-292,
+ * utils/seg_utils.py:82-103, utils/img_utils.py:62-75) for img = (frame / 255 - 0.5) / 0.5.  tables: 512 + 3 * num_colors floats built on
+ * the host in float32 (hyperseg_amd.utils.inference.Overlay): A[256] = img * am, A1[256] = img, S[num_colors][3] =
+ * (color / 128 - 1) * (1 - am) with am = 1 - alpha.  A pixel whose class is ignore_index or >= num_colors keeps the frame's byte; every
+ * other pixel is uint8(rint(((A[v] + S[c][ch]) * 0.5 + 0.5) * 255)).  1 <= num_colors <= 256; overlay must not alias frames.  Any H, W >= 1
+ * and any alignment of frames / overlay.  Neither entry reads anything back: both are capturable.
+ *   hs_overlay_fwd: from finished masks (batch, H, W) uint8; batch <= 65535.
+ *   hs_upsample_overlay_fwd: hs_upsample_argmax_fwd (same taps, same arg-max rule, both of its forms) with the blend as the launch's
+ *     epilogue: writes mask (batch, Ho, Wo), bit-identical to hs_upsample_argmax_fwd's, and overlay; frames are (batch, Ho, Wo) frames.
+ *     mask 4-byte aligned where the exact-2x form applies, else HS_ERR_UNSUPPORTED. */
+int hs_overlay_fwd(const uint8_t* masks, const uint8_t* frames, int32_t layout, int32_t batch, int32_t H, int32_t W,
+                   const float* tables, int32_t num_colors, int32_t ignore_index, uint8_t* overlay, void* stream);
+int hs_upsample_overlay_fwd(const float* x, int32_t batch, int32_t channels, int32_t Hi, int32_t Wi, int32_t Ho, int32_t Wo,
+                            const uint8_t* frames, int32_t layout, const float* tables, int32_t num_colors, int32_t ignore_index,
+                            uint8_t* mask, uint8_t* overlay, void* stream);
 int hs_mbconv_expand_dw_fwd(const float* x, int32_t batch, int32_t c_in, int32_t H, int32_t W,
                             const float* w_expand, int32_t c_mid, const float* scale0, const float* shift0,
                             const float* w_dw, int32_t k, int32_t stride, int32_t pad_t, int32_t pad_l,

@@ -1,0 +1,160 @@
+"""What drawing a frame's overlay costs on top of producing its masks: HyperSeg-M, 1024 x 512, batch 1, after prepare_for_inference.
+
+    timeout -k 10 600 python tools/overlay_time.py [--rounds 7] [--reps 200] [--out profiles/overlay_time.txt]
+
+One process, four variants timed INTERLEAVED (round r times a, b, c, d in turn, ``--rounds`` rounds), each sample a region of ``--reps``
+frames between two device events.  The setup is tools/eval_epilogue_time.py's (float image resident on the device, inference_hflip off), so
+that (a) is the number recorded in profiles/eval_epilogue_time.txt; the uint8 frame the overlay is blended over is resident as well:
+  (a) GraphedModel(masks=True) replay -- masks only;
+  (b) (a) + the reference's display chain as stock torch ops on the device (blend_seg: index into the colour map, permute, mask, repeat,
+      two multiplies, an add; tensor2rgb: un-normalise, permute, round, cast) -- what a user writes without this feature;
+  (c) (a) + one hs_overlay_fwd launch on the masks (functional.overlay);
+  (d) GraphedModel.overlay -- the overlay blended by the forward's last launch (hs_upsample_overlay_fwd).
+Then the served pipeline, uint8 frame in (the fused stem route): (a8) masks only, (d8) GraphedModel.overlay.
+Required (asserted): (c) < (b) and (d) < (b) by more than the spread (max - min over the rounds) of the samples involved; all variants give
+the same bytes.  Reported: (d) - (a), (c) - (a), (d) against (c), and the standalone kernel alone (a graph of 50 launches) with its
+fraction of the HBM roof for 0.5 MB of masks + 1.5 MB of frame read + 1.5 MB of overlay written."""
+import argparse
+import os
+import statistics
+import sys
+
+import torch
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if REPO not in sys.path:
+    sys.path.insert(0, REPO)
+
+HBM_ROOF = 8.0e12        # bytes / s
+
+
+def region_ms(fn, reps):
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    torch.cuda.synchronize()
+    e0.record()
+    for _ in range(reps):
+        fn()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / reps
+
+
+def stock_overlay(img, seg, color_map_tensor, alpha, ignore_index):
+    """blend_seg + tensor2rgb restated with the same stock ops, everything staying on the device.  img: (B, 3, H, W) float32 normalised with
+    mean = std = 0.5; seg: (B, H, W) uint8.  Returns (B, H, W, 3) uint8."""
+    seg_classes = seg.long()
+    seg_classes[seg_classes >= color_map_tensor.shape[0]] = ignore_index
+    seg_rgb = color_map_tensor[seg_classes].permute(0, 3, 1, 2)
+    alpha_mask = (1. - (seg_classes != ignore_index).float() * alpha).unsqueeze(1).repeat(1, 3, 1, 1)
+    blended = img * alpha_mask + seg_rgb * (1. - alpha_mask)
+    out = blended.mul(0.5).add_(0.5).permute(0, 2, 3, 1)
+    return torch.round(out * 255).to(torch.uint8)
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.split('\n')[0])
+    ap.add_argument('--rounds', type=int, default=7)
+    ap.add_argument('--reps', type=int, default=200)
+    ap.add_argument('--out', default=os.path.join(REPO, 'profiles', 'overlay_time.txt'))
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit('overlay_time.py measures on the GPU: no device found')
+    from hyperseg_amd import InputNorm, Overlay, configs, functional as HF
+    from hyperseg_amd.utils.inference import GraphedModel, prepare_for_inference
+    from hyperseg_amd.utils.synthetic import fill_by_name
+    dev = torch.device('cuda:0')
+    n, (h, w) = 19, (512, 1024)
+    model = fill_by_name(configs.build('hyperseg-m').eval(), seed=0)
+    prepare_for_inference(model, fold_bn=False, fused_depthwise=True)
+    model.inference_hflip = False       # inert for tensor inputs, but segment() / overlay() take their logits + argmax routes while it is set
+    model = model.to(dev)
+    g = torch.Generator().manual_seed(1)
+    x = torch.rand(1, 3, h, w, generator=g).to(dev)
+    frames = torch.randint(0, 256, (1, h, w, 3), generator=g, dtype=torch.uint8).to(dev)
+    style = Overlay(torch.randint(0, 256, (n, 3), generator=g))
+    model.overlay_style = style
+    model.input_norm = InputNorm(layout='hwc')
+    img = frames.permute(0, 3, 1, 2).to(torch.float32).div(255).sub_(0.5).div_(0.5).contiguous()      # what the reference's user holds
+    cmt = style.color_map.to(torch.float32).div_(128.).sub_(1.).to(dev)
+    served = GraphedModel(model, masks=True)
+    out_c = torch.empty_like(frames)
+    keep = {}
+
+    def a():
+        return served(x)
+
+    def b():
+        keep['b'] = stock_overlay(img, served(x), cmt, style.alpha, style.ignore_index)
+
+    def c():
+        keep['c'] = HF.overlay(served(x), frames, style, out=out_c)
+
+    def d():
+        keep['d'] = served.overlay(x, frames=frames)[1]
+
+    def a8():
+        return served(frames)
+
+    def d8():
+        keep['d8'] = served.overlay(frames)[1]
+
+    variants = {'a': a, 'b': b, 'c': c, 'd': d, 'a8': a8, 'd8': d8}
+    for fn in variants.values():                    # every shape and graph warmed before anything is timed
+        for _ in range(5):
+            fn()
+    torch.cuda.synchronize()
+    same = torch.equal(keep['b'], keep['c']) and torch.equal(keep['c'], keep['d'])
+    masks8 = served(frames).clone()
+    same8 = torch.equal(keep['d8'], HF.overlay(masks8, frames, style))
+    samples = {k: [] for k in variants}
+    for _ in range(args.rounds):
+        for k, fn in variants.items():
+            samples[k].append(region_ms(fn, args.reps))
+    lines = [f'HyperSeg-M {w}x{h} bs 1, prepared, HIP-graph replay, resident input; {args.rounds} interleaved rounds x {args.reps} frames, ms per frame',
+             f'overlays of (b), (c), (d) equal: {same};  (d8) equals hs_overlay_fwd on its own masks: {same8}']
+    med = {}
+    for k in variants:
+        s = samples[k]
+        med[k] = statistics.median(s)
+        lines.append(f'({k}) median {med[k]:.4f}  min {min(s):.4f}  max {max(s):.4f}  spread {max(s) - min(s):.4f}   samples ' +
+                     ' '.join(f'{v:.4f}' for v in s))
+    spread = {k: max(v) - min(v) for k, v in samples.items()}
+    lines.append(f'(d) - (a) = {med["d"] - med["a"]:+.4f} ms   (c) - (a) = {med["c"] - med["a"]:+.4f} ms   (b) - (a) = {med["b"] - med["a"]:+.4f} ms   '
+                 f'(d8) - (a8) = {med["d8"] - med["a8"]:+.4f} ms')
+    lines.append(f'(b) - (d) = {med["b"] - med["d"]:.4f} ms vs spread {max(spread["b"], spread["d"]):.4f};  '
+                 f'(b) - (c) = {med["b"] - med["c"]:.4f} ms vs spread {max(spread["b"], spread["c"]):.4f};  '
+                 f'(c) - (d) = {med["c"] - med["d"]:+.4f} ms vs spread {max(spread["c"], spread["d"]):.4f}')
+    # the standalone kernel alone: a graph of 50 launches replayed 20 times per sample
+    masks = served(x).clone()
+    for layout in ('hwc', 'chw'):
+        st = Overlay(style.color_map, layout=layout)
+        fr = frames if layout == 'hwc' else frames.permute(0, 3, 1, 2).contiguous()
+        out = torch.empty_like(fr)
+        for _ in range(3):
+            HF.overlay(masks, fr, st, out=out)
+        torch.cuda.synchronize()
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph):
+            for _ in range(50):
+                HF.overlay(masks, fr, st, out=out)
+        graph.replay()
+        s = [1e3 * region_ms(graph.replay, 20) / 50 for _ in range(5)]
+        nbytes = masks.numel() + 2 * fr.numel()
+        us = statistics.median(s)
+        lines.append(f"hs_overlay_fwd alone, {w}x{h} '{layout}': {us:6.2f} us per launch (min {min(s):.2f} max {max(s):.2f})  {nbytes / 1e6:.2f} MB  ->  "
+                     f'{nbytes / us / 1e6:.2f} TB/s = {100 * nbytes / (us * 1e-6) / HBM_ROOF:.0f} % of the 8 TB/s roof')
+    lines.append('note: the launches of that graph rewrite one output from inputs that stay in the 256 MB last-level cache: the figure is the cost of '
+                 'this small launch inside a graph, not HBM streaming')
+    text = '\n'.join(lines)
+    print(text)
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, 'w') as f:
+        f.write(text + '\n')
+    assert same and same8, 'the variants disagree on the overlay'
+    assert med['b'] - med['d'] > max(spread['b'], spread['d']), '(d) is not below (b) by more than the spread'
+    assert med['b'] - med['c'] > max(spread['b'], spread['c']), '(c) is not below (b) by more than the spread'
+
+
+if __name__ == '__main__':
+    with torch.no_grad():               # GraphedModel.forward replays only where nothing can ask for a gradient
+        main()
