@@ -196,7 +196,7 @@ def test_graphed_train_step_with_the_one_launch_adam(dev):
     assert o0.steps_taken() == o1.steps_taken() == 4 and losses_g[-1] < losses_e[0]
 
 
-@pytest.mark.parametrize('autocast', [False, True], ids=['fp32', 'bf16'])
+@pytest.mark.parametrize('autocast', [False, True, torch.float16], ids=['fp32', 'bf16', 'fp16'])
 def test_bank_slices_share_one_gradient_buffer(dev, autocast):
     """autograd.BankSlices (round 5): the three layers of a train-mode inverted residual write their weight gradients into views of ONE
     (patches, ld) buffer, which BankSlices.backward returns as it is -- every gradient of the decoder bit-equal to the route that
@@ -230,7 +230,7 @@ def test_bank_slices_share_one_gradient_buffer(dev, autocast):
             d.load_state_dict(state)
             d.zero_grad()
             s = s0.to(dev).clone().requires_grad_(True)
-            with torch.autocast('cuda', dtype=torch.bfloat16, enabled=autocast):
+            with torch.autocast('cuda', dtype=autocast if autocast is torch.float16 else torch.bfloat16, enabled=bool(autocast)):
                 y = d(x, s)
             (y.float() * r).sum().backward()
             return {**{k: v.grad.clone() for k, v in d.named_parameters() if v.grad is not None}, 'signal': s.grad.clone()}, returned
