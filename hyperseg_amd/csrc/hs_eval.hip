@@ -4,7 +4,7 @@
 // a register (hs_upsample_confusion_fwd).  Integer counts only: the result does not depend on arrival order.
 //
 // Shape of both kernels ("On-device evaluation"):
-//   * one workgroup of 512 threads per CU (the arg-max bodies hold 136-252 VGPRs: 1024 threads spill), grid-striding over its image's pixels (blockIdx.y = image), counting into a
+//   * one workgroup of 512 threads per CU (the arg-max bodies hold 136-256 VGPRs: 1024 threads spill), grid-striding over its image's pixels (blockIdx.y = image), counting into a
 //     per-workgroup n x n histogram of 32-bit bins in LDS;
 //   * in the wave, label maps are spatially coherent -- most lanes hold the SAME (t, p) key and a per-lane LDS atomic would
 //     serialise on one bin.  count_key() walks the distinct keys present in the wave (__ballot / __popcll: one LDS add per
@@ -78,8 +78,8 @@ __device__ __forceinline__ void load4(const int64_t* __restrict__ p, int64_t (&t
     t[0] = a.x; t[1] = a.y; t[2] = b.x; t[3] = b.y;
 }
 
-// General resize (any ratio, the identity included): upsample_argmax_kernel's arithmetic -- row4_taps / bilinear_row4, strictly
-// greater wins, first maximum kept -- one thread = 4 consecutive output pixels of a row, then the four pairs are counted.
+// General resize (any ratio, the identity included): argmax_row4 (hs_upsample_taps.h), one thread = 4 consecutive output pixels of
+// a row, then the four pairs are counted.
 template <typename TT>
 __global__ __launch_bounds__(EVAL_THREADS)
 void upsample_confusion_kernel(const float* __restrict__ x, int C, int Hi, int Wi, int Ho, int Wo, float scale_y, float scale_x,
@@ -98,17 +98,8 @@ void upsample_confusion_kernel(const float* __restrict__ x, int C, int Hi, int W
         const int e = live ? e0 : items - 1;
         const int q = e % wq, yo = e / wq;
         const Row4 t = row4_taps(yo, q, Hi, Wi, Wo, scale_y, scale_x);
-        float best[4];
-        int idx[4] = {0, 0, 0, 0};
-        bilinear_row4(xb, Wi, t, best);
-#pragma unroll 6
-        for (int c = 1; c < C; ++c) {
-            float o[4];
-            bilinear_row4(xb + (size_t)c * Hi * Wi, Wi, t, o);
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-                if (o[i] > best[i]) { best[i] = o[i]; idx[i] = c; }
-        }
+        int idx[4];
+        argmax_row4(xb, C, Hi, Wi, t, idx);
         const size_t at = (b * Ho + yo) * Wo + 4 * q;
         TT tv[4];
         if (vec) {
@@ -131,9 +122,8 @@ void upsample_confusion_kernel(const float* __restrict__ x, int C, int Hi, int W
     hist_flush(hist, nn, out + b * out_image_stride);
 }
 
-// Exact 2x: upsample2x_argmax_kernel's arithmetic and work split -- up2x_block, four consecutive lanes share one 2 x 4 output block
-// and split the classes among them, two shuffles combine (larger value wins, lower class on ties) -- after which all four lanes
-// hold the block's eight class indices and each counts two of them: lane `sub` takes row sub >> 1, columns 2 (sub & 1) and + 1.
+// Exact 2x: argmax2x_block (hs_upsample_taps.h), four consecutive lanes per 2 x 4 output block, after which all four lanes hold the
+// block's eight class indices and each counts two of them: lane `sub` takes row sub >> 1, columns 2 (sub & 1) and + 1.
 template <typename TT>
 __global__ __launch_bounds__(EVAL_THREADS)
 void upsample2x_confusion_kernel(const float* __restrict__ x, int C, int Hi, int Wi, const TT* __restrict__ target, int n,
@@ -146,43 +136,13 @@ void upsample2x_confusion_kernel(const float* __restrict__ x, int C, int Hi, int
     const int items = Hi * wq;                                  // 2 x 4 output blocks of this image
     const int sub = (int)(threadIdx.x & 3);
     const float* __restrict__ xb = x + b * C * Hi * Wi;
-    constexpr float NEG = -3.402823466e38f;
     for (int base = blockIdx.x * (EVAL_THREADS / 4); base < items; base += gridDim.x * (EVAL_THREADS / 4)) {
         const int e0 = base + (int)(threadIdx.x >> 2);
         const bool live = e0 < items;
-        const int e = live ? e0 : items - 1;                    // surplus lanes shadow the last block (shuffles stay convergent)
+        const int e = live ? e0 : items - 1;                    // surplus lanes shadow the last block (argmax2x_block: convergent)
         const int q = e % wq, yi = e / wq;
-        float best0[4] = {NEG, NEG, NEG, NEG}, best1[4] = {NEG, NEG, NEG, NEG};
-        int idx0[4] = {sub, sub, sub, sub}, idx1[4] = {sub, sub, sub, sub};
-        for (int c0 = sub; c0 < C; c0 += 20) {
-            float o0[5][4], o1[5][4];
-#pragma unroll
-            for (int u = 0; u < 5; ++u) {
-                const int c = min(c0 + 4 * u, C - 1);
-                up2x_block(xb + (size_t)c * Hi * Wi, Hi, Wi, yi, q, o0[u], o1[u]);
-            }
-#pragma unroll
-            for (int u = 0; u < 5; ++u) {
-                const int c = c0 + 4 * u;
-                if (c < C) {
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) {
-                        if (o0[u][i] > best0[i]) { best0[i] = o0[u][i]; idx0[i] = c; }
-                        if (o1[u][i] > best1[i]) { best1[i] = o1[u][i]; idx1[i] = c; }
-                    }
-                }
-            }
-        }
-#pragma unroll
-        for (int m = 1; m <= 2; m <<= 1) {
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const float v0 = __shfl_xor(best0[i], m, 64), v1 = __shfl_xor(best1[i], m, 64);
-                const int j0 = __shfl_xor(idx0[i], m, 64), j1 = __shfl_xor(idx1[i], m, 64);
-                if (v0 > best0[i] || (v0 == best0[i] && j0 < idx0[i])) { best0[i] = v0; idx0[i] = j0; }
-                if (v1 > best1[i] || (v1 == best1[i] && j1 < idx1[i])) { best1[i] = v1; idx1[i] = j1; }
-            }
-        }
+        int idx0[4], idx1[4];
+        argmax2x_block(xb, C, Hi, Wi, yi, q, sub, idx0, idx1);
         const size_t at = (b * 2 * Hi + 2 * yi) * Wo + 4 * q;
         if (mask != nullptr && sub == 0 && live) {
             if (vec) {
@@ -276,7 +236,7 @@ extern "C" int hs_upsample_confusion_fwd(const float* x, int32_t batch, int32_t 
     unsigned long long* out = reinterpret_cast<unsigned long long*>(confusion);
     const size_t tsz = target_dtype == HS_EVAL_U8 ? 1 : 8;
     hipStream_t s = (hipStream_t)stream;
-    if (Ho == 2 * Hi && Wo == 2 * Wi && (Wi & 1) == 0) {
+    if (is_exact2x(Hi, Wi, Ho, Wo)) {
         const int vec = aligned_to(target, 2 * tsz) && (!mask || aligned_to(mask, 4));
         const long passes = ((long)Hi * (Wi / 2) + EVAL_THREADS / 4 - 1) / (EVAL_THREADS / 4);
         const dim3 grid(eval_grid_x(passes, batch), (unsigned)batch);

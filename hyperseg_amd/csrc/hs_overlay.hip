@@ -117,9 +117,8 @@ void overlay_kernel(const uint8_t* __restrict__ mask, const uint8_t* __restrict_
     }
 }
 
-// Exact 2x: upsample2x_argmax_kernel's arithmetic and work split (hs_patch_conv.hip) -- up2x_block, four consecutive lanes share one
-// 2 x 4 output block and split the classes among them, two shuffles combine (larger value wins, lower class on ties) -- after which all
-// four lanes hold the block's eight class indices: lane 0 stores the masks, lanes 0 and 1 blend one row of four pixels each.
+// Exact 2x: argmax2x_block (hs_upsample_taps.h), four consecutive lanes per 2 x 4 output block, after which all four lanes hold the
+// block's eight class indices: lane 0 stores the masks, lanes 0 and 1 blend one row of four pixels each.
 template <bool HWC>
 __global__ __launch_bounds__(OVL_THREADS)
 void upsample2x_overlay_kernel(const float* __restrict__ x, int B, int C, int Hi, int Wi, const uint8_t* __restrict__ frames,
@@ -134,42 +133,12 @@ void upsample2x_overlay_kernel(const float* __restrict__ x, int B, int C, int Hi
     const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     const int sub = (int)(t & 3);
     const size_t e0 = t >> 2;
-    const size_t e = e0 < n ? e0 : n - 1;                    // surplus lanes shadow the last block (shuffles stay convergent)
+    const size_t e = e0 < n ? e0 : n - 1;                    // surplus lanes shadow the last block (argmax2x_block: convergent)
     const int q = e % wq; size_t r = e / wq;
     const int yi = r % Hi; const size_t b = r / Hi;
     const float* __restrict__ xb = x + b * C * Hi * Wi;
-    constexpr float NEG = -3.402823466e38f;
-    float best0[4] = {NEG, NEG, NEG, NEG}, best1[4] = {NEG, NEG, NEG, NEG};
-    int idx0[4] = {sub, sub, sub, sub}, idx1[4] = {sub, sub, sub, sub};
-    for (int c0 = sub; c0 < C; c0 += 20) {
-        float o0[5][4], o1[5][4];
-#pragma unroll
-        for (int u = 0; u < 5; ++u) {                        // 5 classes = 60 loads in flight
-            const int c = min(c0 + 4 * u, C - 1);
-            up2x_block(xb + (size_t)c * Hi * Wi, Hi, Wi, yi, q, o0[u], o1[u]);
-        }
-#pragma unroll
-        for (int u = 0; u < 5; ++u) {
-            const int c = c0 + 4 * u;
-            if (c < C) {
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    if (o0[u][i] > best0[i]) { best0[i] = o0[u][i]; idx0[i] = c; }
-                    if (o1[u][i] > best1[i]) { best1[i] = o1[u][i]; idx1[i] = c; }
-                }
-            }
-        }
-    }
-#pragma unroll
-    for (int m = 1; m <= 2; m <<= 1) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const float v0 = __shfl_xor(best0[i], m, 64), v1 = __shfl_xor(best1[i], m, 64);
-            const int j0 = __shfl_xor(idx0[i], m, 64), j1 = __shfl_xor(idx1[i], m, 64);
-            if (v0 > best0[i] || (v0 == best0[i] && j0 < idx0[i])) { best0[i] = v0; idx0[i] = j0; }
-            if (v1 > best1[i] || (v1 == best1[i] && j1 < idx1[i])) { best1[i] = v1; idx1[i] = j1; }
-        }
-    }
+    int idx0[4], idx1[4];
+    argmax2x_block(xb, C, Hi, Wi, yi, q, sub, idx0, idx1);
     if (e0 >= n) return;
     const size_t plane = (size_t)2 * Hi * Wo;
     const size_t pix = (size_t)(2 * yi) * Wo + 4 * q;        // of the block's upper row, inside image b
@@ -186,8 +155,8 @@ void upsample2x_overlay_kernel(const float* __restrict__ x, int B, int C, int Hi
     }
 }
 
-// General resize (any ratio, the identity included): upsample_argmax_kernel's arithmetic -- row4_taps / bilinear_row4, strictly greater
-// wins, first maximum kept -- one thread = 4 consecutive output pixels of a row, which it then blends.
+// General resize (any ratio, the identity included): argmax_row4 (hs_upsample_taps.h), one thread = 4 consecutive output pixels of a
+// row, which it then blends.
 template <bool HWC>
 __global__ __launch_bounds__(OVL_THREADS)
 void upsample_overlay_kernel(const float* __restrict__ x, int B, int C, int Hi, int Wi, int Ho, int Wo, float scale_y, float scale_x,
@@ -204,17 +173,8 @@ void upsample_overlay_kernel(const float* __restrict__ x, int B, int C, int Hi, 
     const int yo = r % Ho; const size_t b = r / Ho;
     const Row4 t = row4_taps(yo, q, Hi, Wi, Wo, scale_y, scale_x);
     const float* __restrict__ xb = x + b * C * Hi * Wi;
-    float best[4];
-    int idx[4] = {0, 0, 0, 0};
-    bilinear_row4(xb, Wi, t, best);
-#pragma unroll 6
-    for (int c = 1; c < C; ++c) {
-        float o[4];
-        bilinear_row4(xb + (size_t)c * Hi * Wi, Wi, t, o);
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-            if (o[i] > best[i]) { best[i] = o[i]; idx[i] = c; }
-    }
+    int idx[4];
+    argmax_row4(xb, C, Hi, Wi, t, idx);
     const size_t plane = (size_t)Ho * Wo, pix = (size_t)yo * Wo + 4 * q;
     const int live = min(4, Wo - 4 * q);
     uint8_t* dst = mask + b * plane + pix;
@@ -258,7 +218,7 @@ extern "C" int hs_upsample_overlay_fwd(const float* x, int32_t batch, int32_t ch
     if (channels > 256) return HS_ERR_UNSUPPORTED;           // uint8 class indices
     hipStream_t s = (hipStream_t)stream;
     const bool hwc = layout == HS_LAYOUT_HWC;
-    if (Ho == 2 * Hi && Wo == 2 * Wi && (Wi & 1) == 0) {            // the form hs_upsample_argmax_fwd takes for this shape: same masks
+    if (is_exact2x(Hi, Wi, Ho, Wo)) {            // the form hs_upsample_argmax_fwd takes for this shape: same masks
         if ((reinterpret_cast<uintptr_t>(mask) & 3) != 0) return HS_ERR_UNSUPPORTED;      // it stores the masks as dwords
         const size_t n2 = (size_t)batch * Hi * (Wi / 2) * 4;         // 4 lanes per 2x4 output block
         const dim3 grid((unsigned)((n2 + OVL_THREADS - 1) / OVL_THREADS)), block(OVL_THREADS);

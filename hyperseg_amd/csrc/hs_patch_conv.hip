@@ -334,9 +334,7 @@ void upsample2x_kernel(const float* __restrict__ x, int planes, int Hi, int Wi, 
 // The same upsample with the class argmax taken in registers: uint8 masks instead of logits (M: 0.5 MB written instead
 // of 39.8 MB, and no separate argmax pass re-reading them).  Ties resolve to the lowest class index.  Replaces
 // F.interpolate + pred.argmax(1) (hyperseg_v1_0.py:250-251 + test.py:171 / test_fps.py:194).
-// Four consecutive lanes share one 2x4 output block and split the classes among them (c = sub, sub + 4, ...): with one
-// thread per block the launch is a single wave per SIMD walking 19 dependent load batches; this way it is four waves per
-// SIMD with <= 5 classes (60 loads, one batch) each, combined with two shuffles (larger value wins, lower class on ties).
+// argmax2x_block (hs_upsample_taps.h): four consecutive lanes per 2 x 4 output block; lane 0 of the quad stores.
 __global__ __launch_bounds__(256)
 void upsample2x_argmax_kernel(const float* __restrict__ x, int B, int C, int Hi, int Wi, uint8_t* __restrict__ mask) {
     const int wq = Wi >> 1;
@@ -349,38 +347,8 @@ void upsample2x_argmax_kernel(const float* __restrict__ x, int B, int C, int Hi,
     const int q = e % wq; size_t r = e / wq;
     const int yi = r % Hi; const size_t b = r / Hi;
     const float* __restrict__ xb = x + b * C * Hi * Wi;
-    constexpr float NEG = -3.402823466e38f;
-    float best0[4] = {NEG, NEG, NEG, NEG}, best1[4] = {NEG, NEG, NEG, NEG};
-    int idx0[4] = {sub, sub, sub, sub}, idx1[4] = {sub, sub, sub, sub};
-    for (int c0 = sub; c0 < C; c0 += 20) {
-        float o0[5][4], o1[5][4];
-#pragma unroll
-        for (int u = 0; u < 5; ++u) {                        // 5 classes = 60 loads in flight
-            const int c = min(c0 + 4 * u, C - 1);
-            up2x_block(xb + (size_t)c * Hi * Wi, Hi, Wi, yi, q, o0[u], o1[u]);
-        }
-#pragma unroll
-        for (int u = 0; u < 5; ++u) {
-            const int c = c0 + 4 * u;
-            if (c < C) {
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    if (o0[u][i] > best0[i]) { best0[i] = o0[u][i]; idx0[i] = c; }
-                    if (o1[u][i] > best1[i]) { best1[i] = o1[u][i]; idx1[i] = c; }
-                }
-            }
-        }
-    }
-#pragma unroll
-    for (int m = 1; m <= 2; m <<= 1) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const float v0 = __shfl_xor(best0[i], m, 64), v1 = __shfl_xor(best1[i], m, 64);
-            const int j0 = __shfl_xor(idx0[i], m, 64), j1 = __shfl_xor(idx1[i], m, 64);
-            if (v0 > best0[i] || (v0 == best0[i] && j0 < idx0[i])) { best0[i] = v0; idx0[i] = j0; }
-            if (v1 > best1[i] || (v1 == best1[i] && j1 < idx1[i])) { best1[i] = v1; idx1[i] = j1; }
-        }
-    }
+    int idx0[4], idx1[4];
+    argmax2x_block(xb, C, Hi, Wi, yi, q, sub, idx0, idx1);
     if (sub == 0 && e0 < n) {
         uint8_t* dst = mask + (b * 2 * Hi + 2 * yi) * Wo + 4 * q;
         *reinterpret_cast<uchar4*>(dst) = make_uchar4(idx0[0], idx0[1], idx0[2], idx0[3]);
@@ -527,6 +495,7 @@ void upsample_bilinear_h16_kernel(const T* __restrict__ x, int planes, int Hi, i
     }
 }
 
+// argmax_row4 (hs_upsample_taps.h): one thread = 4 consecutive output pixels of a row
 __global__ __launch_bounds__(256)
 void upsample_argmax_kernel(const float* __restrict__ x, int B, int C, int Hi, int Wi, int Ho, int Wo, float scale_y,
                             float scale_x, uint8_t* __restrict__ mask) {
@@ -538,17 +507,8 @@ void upsample_argmax_kernel(const float* __restrict__ x, int B, int C, int Hi, i
     const int yo = r % Ho; const size_t b = r / Ho;
     const Row4 t = row4_taps(yo, q, Hi, Wi, Wo, scale_y, scale_x);
     const float* __restrict__ xb = x + b * C * Hi * Wi;
-    float best[4];
-    int idx[4] = {0, 0, 0, 0};
-    bilinear_row4(xb, Wi, t, best);
-#pragma unroll 6
-    for (int c = 1; c < C; ++c) {
-        float o[4];
-        bilinear_row4(xb + (size_t)c * Hi * Wi, Wi, t, o);
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-            if (o[i] > best[i]) { best[i] = o[i]; idx[i] = c; }
-    }
+    int idx[4];
+    argmax_row4(xb, C, Hi, Wi, t, idx);
     uint8_t* dst = mask + (b * Ho + yo) * Wo + 4 * q;
     if ((Wo & 3) == 0) {
         *reinterpret_cast<uchar4*>(dst) = make_uchar4(idx[0], idx[1], idx[2], idx[3]);
@@ -780,7 +740,7 @@ extern "C" int hs_upsample_argmax_fwd(const float* x, int32_t batch, int32_t cha
                                       int32_t Ho, int32_t Wo, uint8_t* mask, void* stream) {
     if (!x || !mask || batch <= 0 || channels <= 0 || Hi <= 0 || Wi <= 0 || Ho <= 0 || Wo <= 0) return HS_ERR_BAD_ARG;
     if (channels > 256) return HS_ERR_UNSUPPORTED;           // uint8 class indices
-    if (Ho == 2 * Hi && Wo == 2 * Wi && (Wi & 1) == 0) {
+    if (is_exact2x(Hi, Wi, Ho, Wo)) {
         const size_t n2 = (size_t)batch * Hi * (Wi / 2) * 4;         // 4 lanes per 2x4 output block
         hipLaunchKernelGGL(upsample2x_argmax_kernel, dim3((unsigned)((n2 + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                            x, batch, channels, Hi, Wi, mask);
@@ -797,7 +757,7 @@ static int upsample_bilinear_h16(int dtype, const void* x, int batch, int channe
     if (!x || !y || batch <= 0 || channels <= 0 || Hi <= 0 || Wi <= 0 || Ho <= 0 || Wo <= 0) return HS_ERR_BAD_ARG;
     auto go = [&](auto h) {
         using T = decltype(h);
-        if (Ho == 2 * Hi && Wo == 2 * Wi && (Wi & 1) == 0 && (((size_t)y) & 7) == 0) {          // rows of 4 k outputs: 8-byte stores
+        if (is_exact2x(Hi, Wi, Ho, Wo) && (((size_t)y) & 7) == 0) {          // rows of 4 k outputs: 8-byte stores
             const size_t n2 = (size_t)batch * channels * Hi * (Wi / 2);
             const unsigned blocks2 = (unsigned)((n2 + 255) / 256 > 8192 ? 8192 : (n2 + 255) / 256);
             hipLaunchKernelGGL(upsample2x_h16_kernel<T>, dim3(blocks2), dim3(256), 0, stream, (const T*)x, batch * channels, Hi, Wi, (T*)y);
@@ -827,7 +787,7 @@ extern "C" int hs_upsample_bilinear_f16_fwd(const void* x, int32_t batch, int32_
 extern "C" int hs_upsample_bilinear_fwd(const float* x, int32_t batch, int32_t channels, int32_t Hi, int32_t Wi,
                                         int32_t Ho, int32_t Wo, float* y, void* stream) {
     if (!x || !y || batch <= 0 || channels <= 0 || Hi <= 0 || Wi <= 0 || Ho <= 0 || Wo <= 0) return HS_ERR_BAD_ARG;
-    if (Ho == 2 * Hi && Wo == 2 * Wi && (Wi & 1) == 0) {
+    if (is_exact2x(Hi, Wi, Ho, Wo)) {
         const size_t n2 = (size_t)batch * channels * Hi * (Wi / 2);
         const unsigned blocks2 = (unsigned)((n2 + 255) / 256 > 8192 ? 8192 : (n2 + 255) / 256);
         hipLaunchKernelGGL(upsample2x_kernel, dim3(blocks2), dim3(256), 0, (hipStream_t)stream,

@@ -1,6 +1,6 @@
-// Tap arithmetic of the final logits resize (F.interpolate(..., 'bilinear', align_corners=False)), shared by every kernel that
-// has to round identically: the logits kernels and the fused arg-max kernel (hs_patch_conv.hip) and the fused arg-max +
-// confusion-matrix kernel (hs_eval.hip).  Moved here unchanged from hs_patch_conv.hip.
+// Tap arithmetic of the final logits resize (F.interpolate(..., 'bilinear', align_corners=False)) and the class arg-max taken over
+// it in registers, shared by every kernel that has to round and break ties identically: the logits kernels and the fused arg-max
+// kernels (hs_patch_conv.hip), the arg-max + confusion-matrix kernels (hs_eval.hip) and the arg-max + overlay kernels (hs_overlay.hip).
 #pragma once
 #include "hs_common.h"
 
@@ -63,6 +63,71 @@ __device__ __forceinline__ void bilinear_row4(const float* __restrict__ plane, i
         const float top = t.tx[i].l0 * r0[t.tx[i].i0] + t.tx[i].l1 * r0[t.tx[i].i1];
         const float bot = t.tx[i].l0 * r1[t.tx[i].i0] + t.tx[i].l1 * r1[t.tx[i].i1];
         out[i] = t.ty.l0 * top + t.ty.l1 * bot;
+    }
+}
+
+// "This shape takes the exact-2x form" (up2x_block: pairs of input columns), for every entry point that chooses between the two forms.
+inline bool is_exact2x(int Hi, int Wi, int Ho, int Wo) { return Ho == 2 * Hi && Wo == 2 * Wi && (Wi & 1) == 0; }
+
+// Class arg-max of the exact-2x form, the one copy behind the masks of hs_upsample_argmax_fwd, hs_upsample_confusion_fwd and
+// hs_upsample_overlay_fwd.  Four consecutive lanes (sub = 0..3) share the 2 x 4 output block (yi, q) of image `xb` and split the
+// classes among them (c = sub, sub + 4, ...): with one thread per block the launch is a single wave per SIMD walking 19 dependent
+// load batches; this way it is four waves per SIMD with <= 5 classes (60 loads, one batch) per trip, combined with two shuffles:
+// the larger value wins, the lower class on ties -- the first maximum, as argmax(1).  On return all four lanes hold the block's
+// eight class indices (idx0: upper row, idx1: lower row).
+// Precondition: the call is wave-convergent (the shuffles read the quad's other lanes) -- a caller with surplus lanes lets them
+// shadow a real block and decides after the call who stores.
+__device__ __forceinline__ void argmax2x_block(const float* __restrict__ xb, int C, int Hi, int Wi, int yi, int q, int sub,
+                                               int (&idx0)[4], int (&idx1)[4]) {
+    constexpr float NEG = -3.402823466e38f;
+    float best0[4] = {NEG, NEG, NEG, NEG}, best1[4] = {NEG, NEG, NEG, NEG};
+#pragma unroll
+    for (int i = 0; i < 4; ++i) idx0[i] = idx1[i] = sub;
+    for (int c0 = sub; c0 < C; c0 += 20) {
+        float o0[5][4], o1[5][4];
+#pragma unroll
+        for (int u = 0; u < 5; ++u) {                        // 5 classes = 60 loads in flight
+            const int c = min(c0 + 4 * u, C - 1);
+            up2x_block(xb + (size_t)c * Hi * Wi, Hi, Wi, yi, q, o0[u], o1[u]);
+        }
+#pragma unroll
+        for (int u = 0; u < 5; ++u) {
+            const int c = c0 + 4 * u;
+            if (c < C) {
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    if (o0[u][i] > best0[i]) { best0[i] = o0[u][i]; idx0[i] = c; }
+                    if (o1[u][i] > best1[i]) { best1[i] = o1[u][i]; idx1[i] = c; }
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int m = 1; m <= 2; m <<= 1) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const float v0 = __shfl_xor(best0[i], m, 64), v1 = __shfl_xor(best1[i], m, 64);
+            const int j0 = __shfl_xor(idx0[i], m, 64), j1 = __shfl_xor(idx1[i], m, 64);
+            if (v0 > best0[i] || (v0 == best0[i] && j0 < idx0[i])) { best0[i] = v0; idx0[i] = j0; }
+            if (v1 > best1[i] || (v1 == best1[i] && j1 < idx1[i])) { best1[i] = v1; idx1[i] = j1; }
+        }
+    }
+}
+
+// Class arg-max of the general form (any ratio, the identity included) over the four output pixels of `t`: strictly greater wins,
+// so the first maximum is kept.  The same one copy behind the three entry points' masks.
+__device__ __forceinline__ void argmax_row4(const float* __restrict__ xb, int C, int Hi, int Wi, const Row4& t, int (&idx)[4]) {
+    float best[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) idx[i] = 0;
+    bilinear_row4(xb, Wi, t, best);
+#pragma unroll 6
+    for (int c = 1; c < C; ++c) {
+        float o[4];
+        bilinear_row4(xb + (size_t)c * Hi * Wi, Wi, t, o);
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+            if (o[i] > best[i]) { best[i] = o[i]; idx[i] = c; }
     }
 }
 

@@ -90,8 +90,6 @@ def finish_decoder(decoder, p, size, masks, score, overlay=None):
     wrapper has set one."""
     if masks:
         return final_masks(p, size, score, overlay)
-    if score is not None and overlay is not None:
-        raise ValueError('score= and overlay= both ride on the final upsample launch: one of them per forward for now')
     assert overlay is None, 'overlay= rides on the masks=True epilogue'
     if p.shape[2:] != size:
         p = HF.upsample_bilinear(p, size, out=getattr(decoder, 'output_buffer', None))
@@ -165,16 +163,10 @@ class HyperGenBase(EpochOnModeSwitch, nn.Module):
         if isinstance(head_out, torch.Tensor):
             head_out = head_out.contiguous()
         pyramid = [t.contiguous() for t in [x] + features[:-1]]
-        if score is not None and overlay is not None:
-            raise ValueError('score= and overlay= both ride on the final upsample launch: one of them per forward for now')
-        if score is not None:
-            assert masks and not hflip, 'scoring rides on the masks=True epilogue of an unflipped frame'
-            y = self.decoder(pyramid, head_out, masks=True, score=score)
-        elif overlay is not None:
-            assert masks and not hflip, 'the overlay rides on the masks=True epilogue of an unflipped frame'
-            return self.decoder(pyramid, head_out, masks=True, overlay=overlay)
-        else:
-            y = self.decoder(pyramid, head_out, masks=True) if masks else self.decoder(pyramid, head_out)
+        assert score is None or (masks and not hflip), 'scoring rides on the masks=True epilogue of an unflipped frame'
+        assert overlay is None or (masks and not hflip), 'the overlay rides on the masks=True epilogue of an unflipped frame'
+        # with overlay=: (masks, overlay), unflipped.  score= and overlay= together: final_masks raises
+        y = self.decoder(pyramid, head_out, masks=True, score=score, overlay=overlay) if masks else self.decoder(pyramid, head_out)
         return torch.flip(y, [-1]) if hflip else y
 
     @torch.no_grad()
