@@ -143,6 +143,7 @@ def _load():
         'hs_eval_max_classes': ([], C.c_int),
         'hs_upsample_confusion_fwd': ([vp, i32, i32, i32, i32, i32, i32, vp, i32, i32, i32, vp, vp, vp], C.c_int),
         'hs_confusion_fwd': ([vp, i32, vp, i32, i32, i64, i32, i32, vp, vp], C.c_int),
+        'hs_upsample2_confusion_fwd': ([vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, i32, i32, i32, vp, vp, vp], C.c_int),
         'hs_stage_input_fwd': ([C.POINTER(StageInputC), vp, vp], C.c_int),
         'hs_stage_input_typed_fwd': ([C.POINTER(StageInputC), i32, i32, vp, vp], C.c_int),
         'hs_patch_conv_bwd_input': ([vp, vp, i64, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp], C.c_int),
@@ -196,7 +197,7 @@ EXPORTS = ['hs_version', 'hs_build_info', 'hs_signal2weights_fwd', 'hs_signal2we
            'hs_patch_conv_bwd_weight', 'hs_halo_tiles_fwd', 'hs_halo_tiles_bwd', 'hs_tile_interior_fwd', 'hs_tile_interior_bwd', 'hs_dw_tiles_fwd', 'hs_dw_tiles_bwd_in', 'hs_dw_tiles_bwd_w',
            'hs_s2w_train_fwd', 'hs_s2w_train_workspace', 'hs_s2w_train_bwd', 'hs_cross_entropy_fwd', 'hs_cross_entropy_bwd', 'hs_cross_entropy_typed_fwd', 'hs_cross_entropy_typed_bwd', 'hs_bootstrapped_ce_fwd', 'hs_bootstrapped_ce_bwd', 'hs_bootstrap_mean_workspace', 'hs_bootstrap_mean_fwd', 'hs_bootstrap_mean_bwd', 'hs_bootstrap_mean_batched_fwd', 'hs_bootstrap_mean_batched_bwd', 'hs_bn_train_workspace', 'hs_bn_train_stats_fwd', 'hs_dw_tiles_bn_fwd', 'hs_dw_tiles_bn_bwd_w', 'hs_patch_conv_bn_fwd', 'hs_patch_conv_bn_bwd_w', 'hs_adam_blocks', 'hs_adam_step', 'hs_bootstrap_mean_of_batch_fwd', 'hs_bootstrap_mean_of_batch_bwd', 'hs_upsample_bilinear_bwd', 'hs_upsample_bilinear_typed_bwd', 'hs_upsample_bilinear_bf16_fwd', 'hs_stage_input_typed_fwd', 'hs_bank_unpack_fwd', 'hs_bn_act_train_fwd',
            'hs_bn_act_train_bwd', 'hs_dw_tiles_bn_bwd_in_partials', 'hs_dw_tiles_bn_bwd_in', 'hs_bn_act_train_bwd_apply', 'hs_patch_conv_plain_fwd', 'hs_patch_conv_plain_bwd_in', 'hs_patch_conv_plain_bwd_w',
-           'hs_upsample_bilinear_f16_fwd', 'hs_adam_step_amp', 'hs_eval_max_classes', 'hs_upsample_confusion_fwd', 'hs_confusion_fwd',
+           'hs_upsample_bilinear_f16_fwd', 'hs_adam_step_amp', 'hs_eval_max_classes', 'hs_upsample_confusion_fwd', 'hs_confusion_fwd', 'hs_upsample2_confusion_fwd',
            'hs_image_ingest_fwd', 'hs_stem_dw_u8_fwd', 'hs_overlay_fwd', 'hs_upsample_overlay_fwd']
 
 

@@ -164,6 +164,106 @@ void upsample2x_confusion_kernel(const float* __restrict__ x, int C, int Hi, int
     hist_flush(hist, nn, out + b * out_image_stride);
 }
 
+// Two resizes composed in registers (x -> mid -> label: the decoder's final resize, then test.py:167-168's to the label's size), the
+// general form: argmax2_row4 (hs_upsample_taps.h), otherwise upsample_confusion_kernel.  target == nullptr: masks only, nothing counted.
+template <typename TT>
+__global__ __launch_bounds__(EVAL_THREADS)
+void upsample2_confusion_kernel(const float* __restrict__ x, int C, Stages2 s, const TT* __restrict__ target, int n,
+                                unsigned long long* __restrict__ out, long out_image_stride, uint8_t* __restrict__ mask, int vec) {
+    extern __shared__ unsigned hist[];
+    const int nn = n * n, lane = threadIdx.x & 63;
+    const bool count = target != nullptr;                        // (uniform)
+    if (count) hist_zero(hist, nn);
+    const size_t b = blockIdx.y;
+    const int Ho = s.Ho, Wo = s.Wo, wq = (Wo + 3) / 4;
+    const int items = Ho * wq;
+    const float* __restrict__ xb = x + b * C * s.Hi * s.Wi;
+    for (int base = blockIdx.x * EVAL_THREADS; base < items; base += gridDim.x * EVAL_THREADS) {      // wave-uniform trip count
+        const int e0 = base + (int)threadIdx.x;
+        const bool live = e0 < items;
+        const int e = live ? e0 : items - 1;
+        const int q = e % wq, yo = e / wq;
+        const Row4x2 t = row4x2_taps(yo, q, s);
+        int idx[4];
+        argmax2_row4(xb, C, s.Hi, s.Wi, t, idx);
+        const size_t at = (b * Ho + yo) * Wo + 4 * q;
+        if (mask != nullptr && live) {
+            if (vec) {
+                *reinterpret_cast<uchar4*>(mask + at) = make_uchar4(idx[0], idx[1], idx[2], idx[3]);
+            } else {
+                for (int i = 0; i < 4 && 4 * q + i < Wo; ++i) mask[at + i] = (uint8_t)idx[i];
+            }
+        }
+        if (count) {
+            TT tv[4];
+            if (vec) {
+                load4(target + at, tv);
+            } else {
+#pragma unroll
+                for (int i = 0; i < 4; ++i) tv[i] = target[at + (4 * q + i < Wo ? i : 0)];
+            }
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+                count_key(hist, (live && 4 * q + i < Wo) ? pair_key<TT>(tv[i], idx[i], n) : -1, lane);
+        }
+    }
+    if (count) hist_flush(hist, nn, out + b * out_image_stride);
+}
+
+// Both stages exact 2x: argmax2x2x_block (hs_upsample_taps.h), four consecutive lanes per x block (yi, q) = 4 x 8 label block, after
+// which all four lanes hold the block's 32 class indices; lane `sub` takes label row 4 yi + sub: its eight indices are stored with
+// two 4-byte stores and counted against eight targets from two vector loads.
+template <typename TT>
+__global__ __launch_bounds__(EVAL_THREADS)
+void upsample2x2x_confusion_kernel(const float* __restrict__ x, int C, int Hi, int Wi, const TT* __restrict__ target, int n,
+                                   unsigned long long* __restrict__ out, long out_image_stride, uint8_t* __restrict__ mask, int vec) {
+    extern __shared__ unsigned hist[];
+    const int nn = n * n, lane = threadIdx.x & 63;
+    const bool count = target != nullptr;                        // (uniform)
+    if (count) hist_zero(hist, nn);
+    const size_t b = blockIdx.y;
+    const int wq = Wi >> 1, Wo = 4 * Wi;
+    const int items = Hi * wq;                                  // 4 x 8 label blocks of this image
+    const int sub = (int)(threadIdx.x & 3);
+    const float* __restrict__ xb = x + b * C * Hi * Wi;
+    for (int base = blockIdx.x * (EVAL_THREADS / 4); base < items; base += gridDim.x * (EVAL_THREADS / 4)) {
+        const int e0 = base + (int)(threadIdx.x >> 2);
+        const bool live = e0 < items;
+        const int e = live ? e0 : items - 1;                    // surplus lanes shadow the last block (argmax2x2x_block: convergent)
+        const int q = e % wq, yi = e / wq;
+        int idx[4][8];
+        argmax2x2x_block(xb, C, Hi, Wi, yi, q, sub, idx);
+        int p[8];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) p[k] = sub == 0 ? idx[0][k] : sub == 1 ? idx[1][k] : sub == 2 ? idx[2][k] : idx[3][k];
+        const size_t at = (b * 4 * Hi + 4 * yi + sub) * Wo + 8 * q;
+        if (mask != nullptr && live) {
+            if (vec) {
+                *reinterpret_cast<uchar4*>(mask + at) = make_uchar4(p[0], p[1], p[2], p[3]);
+                *reinterpret_cast<uchar4*>(mask + at + 4) = make_uchar4(p[4], p[5], p[6], p[7]);
+            } else {
+#pragma unroll
+                for (int k = 0; k < 8; ++k) mask[at + k] = (uint8_t)p[k];
+            }
+        }
+        if (count) {
+            TT ta[4], tb[4];
+            if (vec) {
+                load4(target + at, ta);
+                load4(target + at + 4, tb);
+            } else {
+#pragma unroll
+                for (int k = 0; k < 4; ++k) { ta[k] = target[at + k]; tb[k] = target[at + 4 + k]; }
+            }
+#pragma unroll
+            for (int k = 0; k < 4; ++k) count_key(hist, live ? pair_key<TT>(ta[k], p[k], n) : -1, lane);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) count_key(hist, live ? pair_key<TT>(tb[k], p[4 + k], n) : -1, lane);
+        }
+    }
+    if (count) hist_flush(hist, nn, out + b * out_image_stride);
+}
+
 // Finished predictions: one thread = 4 consecutive elements of its image's row of N.  A prediction outside [0, n) is not
 // counted either (the stock route miscounts or fails there).
 template <typename TP, typename TT>
@@ -258,6 +358,56 @@ extern "C" int hs_upsample_confusion_fwd(const float* x, int32_t batch, int32_t 
     else
         hipLaunchKernelGGL(upsample_confusion_kernel<int64_t>, grid, dim3(EVAL_THREADS), lds, s, x, channels, Hi, Wi, Ho, Wo, sy, sx,
                            (const int64_t*)target, num_classes, out, stride, mask, vec);
+    return launch_status();
+}
+
+extern "C" int hs_upsample2_confusion_fwd(const float* x, int32_t batch, int32_t channels, int32_t Hi, int32_t Wi, int32_t Hm, int32_t Wm,
+                                          int32_t Ho, int32_t Wo, const void* target, int32_t target_dtype, int32_t num_classes,
+                                          int32_t per_image, int64_t* confusion, uint8_t* mask, void* stream) {
+    if (!x || batch <= 0 || channels <= 0 || Hi <= 0 || Wi <= 0 || Hm <= 0 || Wm <= 0 || Ho <= 0 || Wo <= 0) return HS_ERR_BAD_ARG;
+    const bool count = target != nullptr;
+    if (count != (confusion != nullptr) || (!count && !mask)) return HS_ERR_BAD_ARG;          // masks only: neither, and a mask to write
+    if (count) {
+        if (!eval_storage_ok(target_dtype) || num_classes <= 0 || channels > num_classes) return HS_ERR_BAD_ARG;
+        if (num_classes > 256) return HS_ERR_BAD_ARG;                                         // uint8 class indices
+        if (num_classes > EVAL_MAX_CLASSES) return HS_ERR_UNSUPPORTED;
+    } else if (channels > 256) {
+        return HS_ERR_UNSUPPORTED;                                                            // as hs_upsample_argmax_fwd
+    }
+    if (batch > 65535 || (long)Ho * Wo > 0x7fffffffL - 4096 || (long)Hm * Wm > 0x7fffffffL - 4096) return HS_ERR_UNSUPPORTED;
+    const int n = count ? num_classes : 0;
+    const size_t lds = (size_t)n * n * sizeof(unsigned);
+    const long stride = per_image ? (long)n * n : 0;
+    unsigned long long* out = reinterpret_cast<unsigned long long*>(confusion);
+    const bool u8 = !count || target_dtype == HS_EVAL_U8;                                     // masks only: either instantiation serves
+    const bool aligned = (!count || aligned_to(target, u8 ? 4 : 16)) && (!mask || aligned_to(mask, 4));
+    hipStream_t s = (hipStream_t)stream;
+    if (is_exact2x(Hi, Wi, Hm, Wm) && is_exact2x(Hm, Wm, Ho, Wo)) {
+        const int vec = aligned;                                                              // rows of 8 k label pixels
+        const long passes = ((long)Hi * (Wi / 2) + EVAL_THREADS / 4 - 1) / (EVAL_THREADS / 4);
+        const dim3 grid(eval_grid_x(passes, batch), (unsigned)batch);
+        if (u8)
+            hipLaunchKernelGGL(upsample2x2x_confusion_kernel<uint8_t>, grid, dim3(EVAL_THREADS), lds, s, x, channels, Hi, Wi,
+                               (const uint8_t*)target, n, out, stride, mask, vec);
+        else
+            hipLaunchKernelGGL(upsample2x2x_confusion_kernel<int64_t>, grid, dim3(EVAL_THREADS), lds, s, x, channels, Hi, Wi,
+                               (const int64_t*)target, n, out, stride, mask, vec);
+        return launch_status();
+    }
+    Stages2 st;
+    st.Hi = Hi; st.Wi = Wi; st.Hm = Hm; st.Wm = Wm; st.Ho = Ho; st.Wo = Wo;
+    st.exact1 = is_exact2x(Hi, Wi, Hm, Wm); st.exact2 = is_exact2x(Hm, Wm, Ho, Wo);           // the form hs_upsample_bilinear_fwd takes per stage
+    st.sy1 = (float)Hi / (float)Hm; st.sx1 = (float)Wi / (float)Wm;
+    st.sy2 = (float)Hm / (float)Ho; st.sx2 = (float)Wm / (float)Wo;
+    const int vec = (Wo & 3) == 0 && aligned;
+    const long passes = ((long)Ho * ((Wo + 3) / 4) + EVAL_THREADS - 1) / EVAL_THREADS;
+    const dim3 grid(eval_grid_x(passes, batch), (unsigned)batch);
+    if (u8)
+        hipLaunchKernelGGL(upsample2_confusion_kernel<uint8_t>, grid, dim3(EVAL_THREADS), lds, s, x, channels, st,
+                           (const uint8_t*)target, n, out, stride, mask, vec);
+    else
+        hipLaunchKernelGGL(upsample2_confusion_kernel<int64_t>, grid, dim3(EVAL_THREADS), lds, s, x, channels, st,
+                           (const int64_t*)target, n, out, stride, mask, vec);
     return launch_status();
 }
 

@@ -131,4 +131,190 @@ __device__ __forceinline__ void argmax_row4(const float* __restrict__ xb, int C,
     }
 }
 
+// ------------------------------------------------------------------------------------------
+// Two resizes composed in registers (hs_upsample2_confusion_fwd): x (Hi, Wi) -> mid (Hm, Wm) -> label (Ho, Wo), the class score of a
+// label pixel being exactly what hs_upsample_bilinear_fwd(hs_upsample_bilinear_fwd(x -> mid) -> label) stores.  Both forms of that
+// entry are, per axis, l0 * v[i0] + l1 * v[i1] taken horizontally first and vertically second; the second stage's indices are
+// clamped in MID space (ATen's edge rule applied to the mid tensor), never in x's.
+
+// One axis of up2x_block as a Tap over `in_size` samples: odd outputs (0.75, 0.25) on (i, i + 1), even ones (0.25, 0.75) on (i - 1, i),
+// output 0 the edge sample itself (1.0, 0.0), the upper index clamped.
+__device__ __forceinline__ Tap up2x_tap(int dst, int in_size) {
+    const int i = dst >> 1, ip = i + 1 < in_size ? i + 1 : in_size - 1;
+    Tap t;
+    if (dst & 1)    { t.i0 = i;     t.i1 = ip; t.l0 = 0.75f; t.l1 = 0.25f; }
+    else if (i > 0) { t.i0 = i - 1; t.i1 = i;  t.l0 = 0.25f; t.l1 = 0.75f; }
+    else            { t.i0 = 0;     t.i1 = ip; t.l0 = 1.0f;  t.l1 = 0.0f; }
+    return t;
+}
+// The tap of one resize stage: the exact-2x form's where hs_upsample_bilinear_fwd takes that form (is_exact2x), bilinear_row4's otherwise.
+__device__ __forceinline__ Tap stage_tap(int dst, bool exact2x, float scale, int in_size) {
+    return exact2x ? up2x_tap(dst, in_size) : bilinear_tap(dst, scale, in_size);
+}
+// The value either form stores for the output pixel with taps (ty, tx) of `plane`: the operation order of up2x_block and bilinear_row4.
+__device__ __forceinline__ float tap_value(const float* __restrict__ plane, int Wi, const Tap& ty, const Tap& tx) {
+    const float* r0 = plane + (size_t)ty.i0 * Wi;
+    const float* r1 = plane + (size_t)ty.i1 * Wi;
+    const float top = tx.l0 * r0[tx.i0] + tx.l1 * r0[tx.i1];
+    const float bot = tx.l0 * r1[tx.i0] + tx.l1 * r1[tx.i1];
+    return ty.l0 * top + ty.l1 * bot;
+}
+
+// General composition, any first and any second stage.  One thread = 4 consecutive label pixels of a row, as Row4: the label row's
+// two mid rows (ty2) and each pixel's two mid columns (tx2), and for each of those mid rows / columns its taps in x (ty1 / tx1).
+struct Stages2 { int Hi, Wi, Hm, Wm, Ho, Wo; int exact1, exact2; float sy1, sx1, sy2, sx2; };
+struct Row4x2 { Tap ty2; Tap ty1[2]; Tap tx2[4]; Tap tx1[4][2]; };
+__device__ __forceinline__ Row4x2 row4x2_taps(int yo, int q, const Stages2& s) {
+    Row4x2 t;
+    t.ty2 = stage_tap(yo, s.exact2 != 0, s.sy2, s.Hm);
+    t.ty1[0] = stage_tap(t.ty2.i0, s.exact1 != 0, s.sy1, s.Hi);
+    t.ty1[1] = stage_tap(t.ty2.i1, s.exact1 != 0, s.sy1, s.Hi);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int xo = 4 * q + i;
+        t.tx2[i] = stage_tap(xo < s.Wo ? xo : s.Wo - 1, s.exact2 != 0, s.sx2, s.Wm);
+        t.tx1[i][0] = stage_tap(t.tx2[i].i0, s.exact1 != 0, s.sx1, s.Wi);
+        t.tx1[i][1] = stage_tap(t.tx2[i].i1, s.exact1 != 0, s.sx1, s.Wi);
+    }
+    return t;
+}
+__device__ __forceinline__ void bilinear2_row4(const float* __restrict__ plane, int Wi, const Row4x2& t, float (&out)[4]) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const float m00 = tap_value(plane, Wi, t.ty1[0], t.tx1[i][0]), m01 = tap_value(plane, Wi, t.ty1[0], t.tx1[i][1]);
+        const float m10 = tap_value(plane, Wi, t.ty1[1], t.tx1[i][0]), m11 = tap_value(plane, Wi, t.ty1[1], t.tx1[i][1]);
+        const float top = t.tx2[i].l0 * m00 + t.tx2[i].l1 * m01;
+        const float bot = t.tx2[i].l0 * m10 + t.tx2[i].l1 * m11;
+        out[i] = t.ty2.l0 * top + t.ty2.l1 * bot;
+    }
+}
+// argmax_row4 over the composition: strictly greater wins, the first maximum is kept.
+__device__ __forceinline__ void argmax2_row4(const float* __restrict__ xb, int C, int Hi, int Wi, const Row4x2& t, int (&idx)[4]) {
+    float best[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) idx[i] = 0;
+    bilinear2_row4(xb, Wi, t, best);
+#pragma unroll 1
+    for (int c = 1; c < C; ++c) {
+        float o[4];
+        bilinear2_row4(xb + (size_t)c * Hi * Wi, Wi, t, o);
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+            if (o[i] > best[i]) { best[i] = o[i]; idx[i] = c; }
+    }
+}
+
+// Both stages exact 2x: the 3 x 4 neighbourhood of x that up2x_block loads for block (yi, q) determines the 4 x 6 mid values of rows
+// 2 yi - 1 .. 2 yi + 2 and columns 4 q - 1 .. 4 q + 4 (clamped in mid space), and those the 4 x 8 label block at (4 yi, 8 q).
+__device__ __forceinline__ void load2x_block(const float* __restrict__ base, int Hi, int Wi, int yi, int q, float (&in)[3][4]) {
+    const int xi = 2 * q;
+    const int xm = xi > 0 ? xi - 1 : 0, xp = xi + 2 < Wi ? xi + 2 : Wi - 1;
+    const int ym = yi > 0 ? yi - 1 : 0, yp = yi + 1 < Hi ? yi + 1 : Hi - 1;
+    const int ys[3] = {ym, yi, yp};
+#pragma unroll
+    for (int rr = 0; rr < 3; ++rr) {
+        const float* row = base + (size_t)ys[rr] * Wi;
+        in[rr][0] = row[xm]; in[rr][1] = row[xi]; in[rr][2] = row[xi + 1]; in[rr][3] = row[xp];
+    }
+}
+// One axis of the second stage: NOUT consecutive outputs, the first of them even, from the NOUT / 2 + 2 mid samples m[] that start one
+// before the first output's own (m[1]).  `lo`: m[1] is the axis' first sample (output 0 is the edge sample itself, m[0] is not read);
+// `hi`: the last m[] lies past the axis' end (the one before it stands for it: the upper index clamped in mid space).
+// Eight outputs along a row (six mid columns), four along a column (four mid rows).
+template <int NOUT>
+__device__ __forceinline__ void up2x_line(const float (&m)[NOUT / 2 + 2], bool lo, bool hi, float (&o)[NOUT]) {
+    constexpr int L = NOUT / 2 + 2;
+    o[0] = lo ? (1.0f * m[1] + 0.0f * m[2]) : (0.25f * m[0] + 0.75f * m[1]);
+#pragma unroll
+    for (int k = 1; k < NOUT - 1; ++k) {
+        const int i = 1 + (k >> 1);                              // mid sample of output k: odd k -> (i, i + 1), even k -> (i - 1, i)
+        o[k] = (k & 1) ? (0.75f * m[i] + 0.25f * m[i + 1]) : (0.25f * m[i - 1] + 0.75f * m[i]);
+    }
+    o[NOUT - 1] = 0.75f * m[L - 2] + 0.25f * (hi ? m[L - 2] : m[L - 1]);
+}
+__device__ __forceinline__ void up2x2x_block(const float (&in)[3][4], bool top, bool bottom, bool left, bool right, float (&o)[4][8]) {
+    // first stage, horizontal: mid columns 4 q - 1 .. 4 q + 4 of the three x rows (up2x_block's hz, plus one column on either side)
+    float hz[3][6];
+#pragma unroll
+    for (int rr = 0; rr < 3; ++rr) {
+        hz[rr][0] = 0.75f * in[rr][0] + 0.25f * in[rr][1];
+        hz[rr][1] = left ? (1.0f * in[rr][1] + 0.0f * in[rr][2]) : (0.25f * in[rr][0] + 0.75f * in[rr][1]);
+        hz[rr][2] = 0.75f * in[rr][1] + 0.25f * in[rr][2];
+        hz[rr][3] = 0.25f * in[rr][1] + 0.75f * in[rr][2];
+        hz[rr][4] = 0.75f * in[rr][2] + 0.25f * in[rr][3];
+        hz[rr][5] = 0.25f * in[rr][2] + 0.75f * in[rr][3];
+    }
+    // first stage, vertical: mid rows 2 yi - 1 .. 2 yi + 2; second stage, horizontal, on each of them
+    float h2[8][4];                                              // [label column][mid row]
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        float mid[6], line[8];
+#pragma unroll
+        for (int c = 0; c < 6; ++c) {
+            mid[c] = r == 0 ? (0.75f * hz[0][c] + 0.25f * hz[1][c])
+                   : r == 1 ? (top ? (1.0f * hz[1][c] + 0.0f * hz[2][c]) : (0.25f * hz[0][c] + 0.75f * hz[1][c]))
+                   : r == 2 ? (0.75f * hz[1][c] + 0.25f * hz[2][c])
+                            : (0.25f * hz[1][c] + 0.75f * hz[2][c]);
+        }
+        up2x_line<8>(mid, left, right, line);
+#pragma unroll
+        for (int k = 0; k < 8; ++k) h2[k][r] = line[k];
+    }
+    // second stage, vertical
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        float col[4];
+        up2x_line<4>(h2[k], top, bottom, col);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) o[r][k] = col[r];
+    }
+}
+
+// Class arg-max of the composed exact-2x form: argmax2x_block's split -- four consecutive lanes share x block (yi, q), classes
+// c = sub, sub + 4, ..., five of them (60 loads) in flight per trip -- over the 4 x 8 label block, combined with the same two shuffles
+// (the larger value wins, the lower class on ties).  On return all four lanes hold the block's 32 class indices, idx[label row][column].
+// Precondition: wave-convergent, as argmax2x_block.
+__device__ __forceinline__ void argmax2x2x_block(const float* __restrict__ xb, int C, int Hi, int Wi, int yi, int q, int sub,
+                                                 int (&idx)[4][8]) {
+    constexpr float NEG = -3.402823466e38f;
+    const bool top = yi == 0, bottom = yi == Hi - 1, left = q == 0, right = 2 * q + 2 >= Wi;
+    float best[4][8];
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+#pragma unroll
+        for (int k = 0; k < 8; ++k) { best[r][k] = NEG; idx[r][k] = sub; }
+    for (int c0 = sub; c0 < C; c0 += 20) {
+        float in[5][3][4];
+#pragma unroll
+        for (int u = 0; u < 5; ++u) {
+            const int c = min(c0 + 4 * u, C - 1);
+            load2x_block(xb + (size_t)c * Hi * Wi, Hi, Wi, yi, q, in[u]);
+        }
+#pragma unroll
+        for (int u = 0; u < 5; ++u) {
+            const int c = c0 + 4 * u;
+            if (c < C) {
+                float o[4][8];
+                up2x2x_block(in[u], top, bottom, left, right, o);
+#pragma unroll
+                for (int r = 0; r < 4; ++r)
+#pragma unroll
+                    for (int k = 0; k < 8; ++k)
+                        if (o[r][k] > best[r][k]) { best[r][k] = o[r][k]; idx[r][k] = c; }
+            }
+        }
+    }
+#pragma unroll
+    for (int m = 1; m <= 2; m <<= 1) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+#pragma unroll
+            for (int k = 0; k < 8; ++k) {
+                const float v = __shfl_xor(best[r][k], m, 64);
+                const int j = __shfl_xor(idx[r][k], m, 64);
+                if (v > best[r][k] || (v == best[r][k] && j < idx[r][k])) { best[r][k] = v; idx[r][k] = j; }
+            }
+    }
+}
+
 }  // namespace hs

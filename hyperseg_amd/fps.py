@@ -11,7 +11,11 @@ Reproduces the reference's protocol on synthetic frames (no dataset, checkpoint 
 ``torch.cuda.synchronize()`` is guarded so that the plumbing also runs on a CPU-only box (with a CPU-capable model).
 
     python -m hyperseg_amd.fps --config hyperseg-m --iterations 200 [--prepare] [--graph] [--remove-bn] [--batch-size 1]
-                               [--uint8 [--layout hwc|chw] [--overlay]]
+                               [--uint8 [--layout hwc|chw] [--overlay]] [--label-size H W] [--fused-metrics]
+
+``--label-size H W`` draws the targets at that size instead of the frame's: the reference's Cityscapes test configs resize the image
+only, so every frame's logits are resized to the label before they are counted (test.py:167-168) -- done here as well, by the
+forward's last launch with ``--fused-metrics``.
 
 ``--uint8`` feeds uint8 frames (what a decoder or camera delivers) to a model with the default ``InputNorm`` attached: the
 host-to-device copy moves one byte per value and ToTensor + Normalize run on the device (``utils.inference.InputNorm``).
@@ -172,7 +176,9 @@ def measure_fps(model, batches, device, num_classes, passes=2, fused_metrics=Fal
     model has ``evaluate`` (a HyperGen, a GraphedModel) the frame is scored by the forward's last launch -- INSIDE the timed
     region, which the reference's protocol keeps outside it; models without it are scored as before.  ``overlay``: every frame
     is served by ``model.overlay`` (masks + the uint8 display blended with ``overlay_style``) instead of the forward, inside the
-    timed region; the masks are scored outside it as the reference's protocol does."""
+    timed region; the masks are scored outside it as the reference's protocol does.  Targets of another size than the frame's are
+    scored at their own resolution: the logits are resized to the label before the arg-max (test.py:167-168), outside the timed region
+    on the unfused route; a model that returns masks hands them out at the label's size where its ``segment`` takes ``size=``."""
     result = {}
     if overlay and fused_metrics:
         raise ValueError('overlay and fused_metrics both ride on the final upsample launch: one of them per run')
@@ -203,18 +209,45 @@ def measure_fps(model, batches, device, num_classes, passes=2, fused_metrics=Fal
             total_time += time.perf_counter() - t0
             frames += pred.shape[0]
             if not fused:
+                if pred.dim() == 4 and pred.shape[2:] != target.shape[1:]:            # test.py:167-168
+                    pred = _resize_logits(pred, tuple(target.shape[1:]))
+                elif pred.dim() == 3 and pred.shape[1:] != target.shape[1:]:
+                    pred = _masks_at(model, x, tuple(target.shape[1:]))
                 conf.update(target.flatten(), pred.argmax(1).flatten() if pred.dim() == 4 else pred.flatten())
         if owns:
             conf.mat = model.confusion.clone()
         acc, _, iou = conf.compute()
         result = {'fps': frames / total_time, 'frames': frames, 'seconds': total_time, 'pass': p,
-                  'global_accuracy': float(acc), 'mean_iou': float(iou.mean())}
+                  'global_accuracy': float(acc), 'mean_iou': float(iou.mean()),
+                  'label_size': list(batches[-1][1].shape[1:]) if batches else None}
     return result
 
 
-def synthetic_batches(n, batch_size, size, num_classes, device, seed=0, uint8=False, layout='hwc'):
+def _resize_logits(pred, size):
+    """``F.interpolate(pred, size, mode='bilinear')`` (test.py:167-168): the package's kernel for CUDA logits, ATen's on the CPU."""
+    hf = _kernels() if pred.is_cuda else None
+    if hf is not None and pred.dtype == torch.float32:
+        return hf.upsample_bilinear(pred.contiguous(), size)
+    return torch.nn.functional.interpolate(pred, size=size, mode='bilinear')
+
+
+def _masks_at(model, x, size):
+    """Masks at the label's size from a model whose forward returns masks at the frame's: its ``segment(x, size=...)`` (a
+    GraphedModel's wrapped model's).  Masks themselves are never resized: the arg-max is taken after the logits' resize."""
+    inner = getattr(model, 'model', model)
+    p = next(inner.parameters(), None) if hasattr(inner, 'parameters') else None
+    if p is not None:
+        x = [t.to(p.device) for t in x] if isinstance(x, (list, tuple)) else x.to(p.device)
+    try:
+        return inner.segment(x, size=size)
+    except (AttributeError, TypeError) as e:
+        raise ValueError(f'the model returns masks at the frame\'s size and has no segment(x, size=...) to produce them at the '
+                         f'label\'s {size}: score it with logits, or with targets of the frame\'s size') from e
+
+
+def synthetic_batches(n, batch_size, size, num_classes, device, seed=0, uint8=False, layout='hwc', label_size=None):
     """``uint8``: uint8 frames in ``layout`` ('hwc': (B, H, W, 3), 'chw': (B, 3, H, W)) from the same generator seed instead of
-    float32 (B, 3, H, W) images."""
+    float32 (B, 3, H, W) images.  ``label_size``: (H, W) of the targets where it is not the frames' (None: the frames')."""
     g = torch.Generator().manual_seed(seed)
     out = []
     for _ in range(n):
@@ -223,7 +256,7 @@ def synthetic_batches(n, batch_size, size, num_classes, device, seed=0, uint8=Fa
             x = torch.randint(0, 256, shape, generator=g, dtype=torch.uint8)
         else:
             x = torch.rand(batch_size, 3, *size, generator=g)
-        t = torch.randint(0, num_classes, (batch_size,) + tuple(size), generator=g)
+        t = torch.randint(0, num_classes, (batch_size,) + tuple(size if label_size is None else label_size), generator=g)
         out.append((x.pin_memory() if device.type == 'cuda' else x, t))
     return out
 
@@ -249,6 +282,9 @@ def main(argv=None):
     ap.add_argument('--overlay', action='store_true',
                     help="serve the display as well (model.overlay): the class map coloured with a seeded synthetic palette and alpha-blended "
                          "over the uint8 frame by the forward's last launch, inside the timed region; needs --uint8")
+    ap.add_argument('--label-size', nargs=2, type=int, metavar=('H', 'W'), default=None,
+                    help="draw the targets at this size instead of the frame's: the logits are resized to it before they are counted "
+                         "(test.py:167-168; the reference's Cityscapes test configs: 1024 2048)")
     ap.add_argument('-t', '--trace', action='store_true',
                     help="the reference's torch.jit.trace switch (test_fps.py:49-50, 150-152).  The mirror's modules call the C ABI through "
                          "ctypes, which the tracer cannot see, so a traced module would be wrong; the purpose of tracing there -- no Python / "
@@ -264,6 +300,8 @@ def main(argv=None):
         raise SystemExit('--overlay blends over the uint8 frames: it needs --uint8')
     if args.overlay and args.fused_metrics:
         raise SystemExit('--overlay and --fused-metrics both ride on the final upsample launch: one of them per run')
+    if args.label_size is not None and min(args.label_size) <= 0:
+        raise SystemExit('--label-size H W: two positive integers')
     if args.overlay and args.gpus and len(args.gpus) > 1:
         raise SystemExit('--overlay serves one device: with several --gpus run one process per GPU')
 
@@ -300,7 +338,7 @@ def main(argv=None):
         model = GraphedModel(model, num_classes=spec['num_classes'] if args.fused_metrics else None)
     bs = args.batch_size or spec['batch']
     uniq = synthetic_batches(min(args.distinct, args.iterations), bs, spec['size'], spec['num_classes'], device,
-                             uint8=args.uint8, layout=args.layout)
+                             uint8=args.uint8, layout=args.layout, label_size=args.label_size)
     batches = [uniq[i % len(uniq)] for i in range(args.iterations)]
     res = measure_fps(model, batches, device, spec['num_classes'], fused_metrics=args.fused_metrics, overlay=args.overlay)
     frame = uniq[0][0]

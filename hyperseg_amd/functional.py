@@ -1381,6 +1381,66 @@ def upsample_confusion(x, size, target, num_classes, out=None, per_image=False, 
     return (out, mask) if masks else out
 
 
+def _size2(size, name):
+    h, w = (int(s) for s in size)
+    if h <= 0 or w <= 0:
+        raise ValueError(f'{name} must be a positive (H, W), got {tuple(size)}')
+    return h, w
+
+
+@_on_operand_device
+def upsample2_confusion(x, mid_size, target, num_classes, out=None, per_image=False, masks=False):
+    """``upsample_confusion`` at the LABEL's resolution: the logits ``x`` (B, C, Hi, Wi) are resized to ``mid_size`` (the frame's size,
+    where the model's logits live) and from there to ``target``'s size (test.py:167-168), arg-maxed and counted against ``target``
+    (B, Ho, Wo; uint8 or int64) in one launch (hs_upsample2_confusion_fwd); neither resized tensor exists in memory.  Masks and
+    counts are bit-identical to ``upsample_bilinear(upsample_bilinear(x, mid_size), target.shape[1:]).argmax(1)`` and its count.
+    ``out``, ``per_image``, ``masks``, the returned value and the errors raised are ``upsample_confusion``'s, which this simply
+    calls when the target is at ``mid_size`` already (or ``x`` is).  Nothing here reads the device: the call is capturable."""
+    if not isinstance(x, torch.Tensor) or x.dim() != 4:
+        raise ValueError('x must be (B, C, Hi, Wi) logits')
+    b, c, hi, wi = x.shape
+    hm, wm = _size2(mid_size, 'mid_size')
+    target = _eval_labels(target, 'target')
+    if target.dim() != 3 or target.shape[0] != b:
+        raise ValueError(f'target has shape {tuple(target.shape)}, expected ({b}, Ho, Wo)')
+    ho, wo = int(target.shape[1]), int(target.shape[2])
+    if (ho, wo) == (hm, wm) or (hi, wi) == (hm, wm):
+        return upsample_confusion(x, (ho, wo), target, num_classes, out=out, per_image=per_image, masks=masks)
+    if target.device != x.device:
+        raise ValueError(f'target is on {target.device}, the logits on {x.device}')
+    if c > int(num_classes):
+        raise ValueError(f'{c} logit channels but num_classes = {num_classes}')
+    if int(num_classes) > 256:
+        raise ValueError('num_classes > 256: the masks are uint8')
+    n = _eval_classes(num_classes)
+    xp = _hip.dev_ptr(x, 'x')
+    out = _eval_out(out, (b, n, n) if per_image else (n, n), x.device)
+    mask = torch.empty(b, ho, wo, device=x.device, dtype=torch.uint8) if masks else None
+    st = _hip.lib.hs_upsample2_confusion_fwd(xp, b, c, hi, wi, hm, wm, ho, wo, target.data_ptr(), _EVAL_DTYPES[target.dtype], n,
+                                             1 if per_image else 0, out.data_ptr(), mask.data_ptr() if masks else None,
+                                             _hip.stream_ptr())
+    _hip.check(st, 'hs_upsample2_confusion_fwd')
+    return (out, mask) if masks else out
+
+
+@_on_operand_device
+def upsample2_argmax(x, mid_size, size):
+    """uint8 masks (B, *size) of the logits ``x`` resized to ``mid_size`` and from there to ``size``, one launch with nothing counted
+    (hs_upsample2_confusion_fwd without a target); neither resized tensor exists in memory.  Bit-identical to
+    ``upsample_bilinear(upsample_bilinear(x, mid_size), size).argmax(1)``; ``upsample_argmax`` where one of the stages is the identity."""
+    if not isinstance(x, torch.Tensor) or x.dim() != 4:
+        raise ValueError('x must be (B, C, Hi, Wi) logits')
+    b, c, hi, wi = x.shape
+    (hm, wm), (ho, wo) = _size2(mid_size, 'mid_size'), _size2(size, 'size')
+    if (ho, wo) == (hm, wm) or (hi, wi) == (hm, wm):
+        return upsample_argmax(x, (ho, wo))
+    mask = torch.empty(b, ho, wo, device=x.device, dtype=torch.uint8)
+    st = _hip.lib.hs_upsample2_confusion_fwd(_hip.dev_ptr(x, 'x'), b, c, hi, wi, hm, wm, ho, wo, None, 0, 0, 0, None, mask.data_ptr(),
+                                             _hip.stream_ptr())
+    _hip.check(st, 'hs_upsample2_confusion_fwd')
+    return mask
+
+
 @_on_operand_device
 def confusion_update(pred, target, num_classes, out=None, per_image=False):
     """The same counting from finished predictions (hs_confusion_fwd): ``pred`` and ``target`` uint8 or int64 of one shape;

@@ -61,9 +61,14 @@ def register_coordinate_buffers(module, coords_res, levels):
 def final_masks_scored(p, size, score):
     """The decoders' ``masks=True`` epilogue with scoring: ``score`` = (target, num_classes, out, per_image) -- the uint8 masks of
     ``HF.upsample_argmax(p, size)`` with every pixel counted against ``target`` into ``out`` by the same launch
-    (``HF.upsample_confusion``)."""
+    (``HF.upsample_confusion``).  A target of another size than ``size`` is scored at ITS resolution, as test.py:167-168 does: the
+    logits at ``size`` are resized once more, to the target's size, before the arg-max -- both resizes composed in the one launch
+    (``HF.upsample2_confusion``), a single one where ``p`` is at ``size`` already; the masks are then at the target's size."""
     target, num_classes, out, per_image = score
-    return HF.upsample_confusion(p, size, target, num_classes, out=out, per_image=per_image, masks=True)[1]
+    label = tuple(target.shape[1:])
+    if label != tuple(size) and tuple(p.shape[2:]) != tuple(size):
+        return HF.upsample2_confusion(p, size, target, num_classes, out=out, per_image=per_image, masks=True)[1]
+    return HF.upsample_confusion(p, label, target, num_classes, out=out, per_image=per_image, masks=True)[1]
 
 
 def final_masks_overlaid(p, size, overlay):
@@ -73,23 +78,31 @@ def final_masks_overlaid(p, size, overlay):
     return HF.upsample_overlay(p, size, frames, style, out=out)
 
 
-def final_masks(p, size, score=None, overlay=None):
+def final_masks(p, size, score=None, overlay=None, out_size=None):
     """What ``masks=True`` returns for the last level's output ``p``: the uint8 argmax masks at ``size`` straight from the final upsample
-    launch -- scored by that launch with ``score``, or blended by it with ``overlay`` (then ``(masks, overlay)``); one or the other."""
+    launch -- scored by that launch with ``score``, or blended by it with ``overlay`` (then ``(masks, overlay)``); one or the other.
+    ``out_size`` (the unscored case): masks of the logits at ``size`` resized once more to ``out_size``, from the same one launch
+    (``HF.upsample2_argmax``); a scored forward takes that size from its target."""
     if score is not None and overlay is not None:
         raise ValueError('score= and overlay= both ride on the final upsample launch: one of them per forward for now')
     if overlay is not None:
+        if out_size is not None and tuple(out_size) != tuple(size):
+            raise ValueError('the overlay is blended over the frames, at their size: out_size= does not go with overlay=')
         return final_masks_overlaid(p, size, overlay)
-    return HF.upsample_argmax(p, size) if score is None else final_masks_scored(p, size, score)
+    if score is not None:
+        return final_masks_scored(p, size, score)
+    if out_size is None or tuple(out_size) == tuple(size):
+        return HF.upsample_argmax(p, size)
+    return HF.upsample2_argmax(p, size, out_size)
 
 
-def finish_decoder(decoder, p, size, masks, score, overlay=None):
+def finish_decoder(decoder, p, size, masks, score, overlay=None, out_size=None):
     """What the v1_0 and unify decoders return for their last level's output ``p``: with ``masks``, the uint8 argmax masks at ``size``
     straight from the final upsample launch (scored by the same launch when ``score`` is given, blended over the frames by it when
     ``overlay`` is: :func:`final_masks`); otherwise the logits, resized to ``size`` -- into ``decoder.output_buffer`` where a serving
     wrapper has set one."""
     if masks:
-        return final_masks(p, size, score, overlay)
+        return final_masks(p, size, score, overlay, out_size)
     assert overlay is None, 'overlay= rides on the masks=True epilogue'
     if p.shape[2:] != size:
         p = HF.upsample_bilinear(p, size, out=getattr(decoder, 'output_buffer', None))
@@ -144,7 +157,7 @@ class HyperGenBase(EpochOnModeSwitch, nn.Module):
     def hyper_params(self):
         return self.decoder.hyper_params
 
-    def process_single_tensor(self, x, hflip=False, masks=False, score=None, overlay=None):
+    def process_single_tensor(self, x, hflip=False, masks=False, score=None, overlay=None, out_size=None):
         frame = None
         if x.dtype == torch.uint8:
             norm = self._require_norm()
@@ -166,31 +179,49 @@ class HyperGenBase(EpochOnModeSwitch, nn.Module):
         assert score is None or (masks and not hflip), 'scoring rides on the masks=True epilogue of an unflipped frame'
         assert overlay is None or (masks and not hflip), 'the overlay rides on the masks=True epilogue of an unflipped frame'
         # with overlay=: (masks, overlay), unflipped.  score= and overlay= together: final_masks raises
-        y = self.decoder(pyramid, head_out, masks=True, score=score, overlay=overlay) if masks else self.decoder(pyramid, head_out)
+        assert out_size is None or (masks and not hflip), 'another output size rides on the masks=True epilogue of an unflipped frame'
+        if out_size is not None:              # masks at another size than the frame's: both resizes in the decoder's last launch
+            y = self.decoder(pyramid, head_out, masks=True, score=score, overlay=overlay, out_size=tuple(out_size))
+        else:
+            y = self.decoder(pyramid, head_out, masks=True, score=score, overlay=overlay) if masks else self.decoder(pyramid, head_out)
         return torch.flip(y, [-1]) if hflip else y
 
     @torch.no_grad()
-    def segment(self, x):
+    def segment(self, x, size=None):
         """uint8 class masks (B, H, W) == ``self(x).argmax(1)`` (the reference's test.py:171 / test_fps.py:194 epilogue).
         For a single tensor in eval mode the argmax is taken inside the final upsample kernel and the full-resolution
-        logits are never written; pyramid / h-flip inference falls back to the logits path."""
-        if isinstance(x, torch.Tensor) and not self.training and not self.inference_hflip:
-            return self.process_single_tensor(x, masks=True)
-        return self(x).argmax(1).to(torch.uint8)
+        logits are never written; pyramid / h-flip inference falls back to the logits path.  ``size``: masks at that (H, W) instead
+        of the frame's -- the logits resized to it before the arg-max, as test.py:167-168 does for a label of another size; from
+        the same one launch (``HF.upsample2_argmax``) where the arg-max is, else the logits route plus that resize."""
+        first = x if isinstance(x, torch.Tensor) else x[0]
+        if size is not None and tuple(size) == self.frame_size(first):
+            size = None
+        fused = isinstance(x, torch.Tensor) and not self.training and not self.inference_hflip
+        if size is None:
+            return self.process_single_tensor(x, masks=True) if fused else self(x).argmax(1).to(torch.uint8)
+        size = tuple(int(s) for s in size)
+        if fused and x.is_cuda:
+            return self.process_single_tensor(x, masks=True, out_size=size)
+        pred = self(x)
+        pred = HF.upsample_bilinear(pred.contiguous(), size) if pred.is_cuda else \
+            torch.nn.functional.interpolate(pred, size=size, mode='bilinear')
+        return pred.argmax(1).to(torch.uint8)
 
     @torch.no_grad()
     def evaluate(self, x, target, confmat, per_image=False):
         """``segment(x)`` plus scoring: returns the uint8 masks and adds this batch's (target, prediction) counts to ``confmat``
         (a ``hyperseg_amd.fps.ConfusionMatrix``; ``per_image=True`` also appends the batch's (B, n, n) matrices to
         ``confmat.per_image`` -- test.py:174-175 without a host read per image).  A single CUDA tensor in eval mode with a
-        target of the output's size is scored by the forward's last launch (``HF.upsample_confusion``): no further launch, no
-        read of the device.  Everything else -- list inputs (pyramid / h-flip inference), a target of another size (the LOGITS
-        are resized to it, test.py:167-168), more classes than the kernel covers, training mode, CPU -- computes the masks the
-        way ``segment()`` / ``forward()`` do and counts them with ``confmat``'s own update.  Same numbers on every route."""
+        target is scored by the forward's last launch: no further launch, no read of the device -- a target of the output's size by
+        ``HF.upsample_confusion``, one of another size at ITS resolution (the LOGITS are resized to it, test.py:167-168 -- the
+        protocol of the reference's Cityscapes test configs) by ``HF.upsample2_confusion``, the returned masks then at the target's
+        size.  Everything else -- list inputs (pyramid / h-flip inference), more classes than the kernel covers, training mode, CPU
+        -- computes the masks the way ``segment()`` / ``forward()`` do (resizing the logits to a target of another size) and
+        counts them with ``confmat``'s own update.  Same numbers on every route."""
         n = confmat.num_classes
         fused = (isinstance(x, torch.Tensor) and x.is_cuda and not self.training and isinstance(target, torch.Tensor)
                  and target.is_cuda and target.dtype in (torch.uint8, torch.int64) and target.dim() == 3
-                 and target.shape[0] == x.shape[0] and tuple(target.shape[1:]) == self.frame_size(x) and n <= min(256, HF.eval_max_classes()))
+                 and target.shape[0] == x.shape[0] and n <= min(256, HF.eval_max_classes()))
         if fused:
             mat = confmat.matrix(x.device)
             if per_image:

@@ -930,15 +930,18 @@ class GraphedModel(nn.Module):
         ``per_image=True`` at construction; ``reset_confusion()`` zeroes it.  ``x`` and ``target`` (B, H, W; uint8 or int64) may
         live on the device or in (pinned) host memory: both are staged into static buffers of the graph.  The graph is the
         forward's chain of launches with the last one replaced by ``functional.upsample_confusion`` -- a single chain, keyed
-        apart from the ``forward`` graphs.  What the graph cannot serve (``forward``'s list, plus a target of another size or
-        type, or more classes than the kernel covers) is scored eagerly by ``model.evaluate`` into the same matrix."""
+        apart from the ``forward`` graphs.  A target of another size than the frame's is scored at its own resolution by the same
+        one launch (``functional.upsample2_confusion``: the logits resized to the label, test.py:167-168), the masks at the
+        target's size; the key holds the target's shape, so each label size gets a graph of its own.  What the graph cannot serve
+        (``forward``'s list, plus a target of another type, or more classes than the kernel covers) is scored eagerly by
+        ``model.evaluate`` into the same matrix."""
         from .. import functional as HF
         from ..fps import ConfusionMatrix
         p = next(self.model.parameters(), None)
         n = self.num_classes
         graphable = (self._graphable(x) and isinstance(target, torch.Tensor) and target.dtype in (torch.uint8, torch.int64)
                      and target.dim() == 3 and x.dim() == 4 and hasattr(self.model, 'frame_size')
-                     and tuple(target.shape) == (x.shape[0],) + tuple(self.model.frame_size(x))
+                     and target.shape[0] == x.shape[0] and target.numel() > 0
                      and n is not None and n <= min(256, HF.eval_max_classes()) and hasattr(self.model, 'process_single_tensor'))
         if not graphable:
             if p is not None and p.is_cuda:
@@ -955,7 +958,7 @@ class GraphedModel(nn.Module):
             return masks
         device = p.device
         confusion = self._confusion_on(device, x.shape[0])
-        key = ('evaluate', tuple(x.shape), x.dtype, target.dtype, device, self._norm_of(x))
+        key = ('evaluate', tuple(x.shape), x.dtype, target.dtype, device, self._norm_of(x), tuple(target.shape))
         entry = self._graphs.get(key)
         if entry is None:
             scratch = torch.zeros_like(confusion)                # the warm-up passes execute: their counts go here

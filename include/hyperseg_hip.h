@@ -332,6 +332,17 @@ int hs_upsample_confusion_fwd(const float* x, int32_t batch, int32_t channels, i
                               int64_t* confusion, uint8_t* mask, void* stream);
 int hs_confusion_fwd(const void* pred, int32_t pred_dtype, const void* target, int32_t target_dtype, int32_t batch,
                      int64_t elements, int32_t num_classes, int32_t per_image, int64_t* confusion, void* stream);
+/* Scoring at the label's resolution (test.py:167-168: the model's logits, at the frame's size, are resized once more to the label's
+ * before the arg-max): hs_upsample_confusion_fwd over TWO resizes composed in registers, x (Hi, Wi) -> mid (Hm, Wm) -> (Ho, Wo).
+ * The class score of a label pixel is exactly what hs_upsample_bilinear_fwd(hs_upsample_bilinear_fwd(x -> Hm, Wm) -> Ho, Wo) stores
+ * (each stage in the form that entry takes for its shape; the second stage clamps in mid index space), so mask and counts are
+ * bit-identical to arg-max + hs_confusion_fwd over those logits -- neither the mid nor the label-size logits are ever in memory.
+ * Two forms: both stages exact 2x (one 3 x 4 neighbourhood of x per 4 x 8 label block), and any other pair of stages (down-sampling
+ * and identity second stages included).  target and confusion may BOTH be NULL: masks only (then mask is required and num_classes,
+ * target_dtype and per_image are not read; channels <= 256).  Otherwise hs_upsample_confusion_fwd's contract. */
+int hs_upsample2_confusion_fwd(const float* x, int32_t batch, int32_t channels, int32_t Hi, int32_t Wi, int32_t Hm, int32_t Wm,
+                               int32_t Ho, int32_t Wo, const void* target, int32_t target_dtype, int32_t num_classes, int32_t per_image,
+                               int64_t* confusion, uint8_t* mask, void* stream);
 
 /* Backward of hs_patch_conv_fwd (plain input x, no fused prologue / epilogue), fp32 -- SURVEY.md Appendix E.
  * The reference has no backward of its own (autograd over F.pad/unfold/grouped conv2d/fold: meta_patch.py:35-57);
