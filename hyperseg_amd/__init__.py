@@ -6,6 +6,9 @@ def __getattr__(name):
     if name == 'InputNorm':
         from .utils.inference import InputNorm
         return InputNorm
+    if name == 'FrameResize':
+        from .utils.inference import FrameResize
+        return FrameResize
     if name == 'Overlay':
         from .utils.inference import Overlay
         return Overlay

@@ -174,6 +174,8 @@ def _load():
         'hs_stem_dw_u8_fwd': ([vp, i32, vp, i32, i32, i32, vp, i32, vp, vp, i32, i32, i32, i32, vp, i32, i32, i32, vp, vp, vp, vp, vp], C.c_int),
         'hs_overlay_fwd': ([vp, vp, i32, i32, i32, i32, vp, i32, i32, vp, vp], C.c_int),
         'hs_upsample_overlay_fwd': ([vp, i32, i32, i32, i32, i32, i32, vp, i32, vp, i32, i32, vp, vp, vp], C.c_int),
+        'hs_frame_resize_fwd': ([vp, i32, i32, i32, i32, vp, vp, i32, i32, vp, vp, i32, i32, i32, i32, i32, i32, i32, C.c_uint32, vp, vp, vp], C.c_int),
+        'hs_label_resize_fwd': ([vp, i32, i32, i32, i32, vp, i32, vp, i32, i32, i32, i32, i32, i32, i32, vp, i32, vp], C.c_int),
         'hs_mbconv_expand_dw_fwd': ([vp, i32, i32, i32, i32, vp, i32, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp], C.c_int),
         'hs_se_gate_fwd': ([vp, i32, i32, i32, C.c_float, vp, vp, i32, vp, vp, vp, vp, vp, i32, vp, vp, vp], C.c_int),
         'hs_gemm_split_kp': ([i32], C.c_int),
@@ -198,7 +200,8 @@ EXPORTS = ['hs_version', 'hs_build_info', 'hs_signal2weights_fwd', 'hs_signal2we
            'hs_s2w_train_fwd', 'hs_s2w_train_workspace', 'hs_s2w_train_bwd', 'hs_cross_entropy_fwd', 'hs_cross_entropy_bwd', 'hs_cross_entropy_typed_fwd', 'hs_cross_entropy_typed_bwd', 'hs_bootstrapped_ce_fwd', 'hs_bootstrapped_ce_bwd', 'hs_bootstrap_mean_workspace', 'hs_bootstrap_mean_fwd', 'hs_bootstrap_mean_bwd', 'hs_bootstrap_mean_batched_fwd', 'hs_bootstrap_mean_batched_bwd', 'hs_bn_train_workspace', 'hs_bn_train_stats_fwd', 'hs_dw_tiles_bn_fwd', 'hs_dw_tiles_bn_bwd_w', 'hs_patch_conv_bn_fwd', 'hs_patch_conv_bn_bwd_w', 'hs_adam_blocks', 'hs_adam_step', 'hs_bootstrap_mean_of_batch_fwd', 'hs_bootstrap_mean_of_batch_bwd', 'hs_upsample_bilinear_bwd', 'hs_upsample_bilinear_typed_bwd', 'hs_upsample_bilinear_bf16_fwd', 'hs_stage_input_typed_fwd', 'hs_bank_unpack_fwd', 'hs_bn_act_train_fwd',
            'hs_bn_act_train_bwd', 'hs_dw_tiles_bn_bwd_in_partials', 'hs_dw_tiles_bn_bwd_in', 'hs_bn_act_train_bwd_apply', 'hs_patch_conv_plain_fwd', 'hs_patch_conv_plain_bwd_in', 'hs_patch_conv_plain_bwd_w',
            'hs_upsample_bilinear_f16_fwd', 'hs_adam_step_amp', 'hs_eval_max_classes', 'hs_upsample_confusion_fwd', 'hs_confusion_fwd', 'hs_upsample2_confusion_fwd',
-           'hs_image_ingest_fwd', 'hs_stem_dw_u8_fwd', 'hs_overlay_fwd', 'hs_upsample_overlay_fwd']
+           'hs_image_ingest_fwd', 'hs_stem_dw_u8_fwd', 'hs_overlay_fwd', 'hs_upsample_overlay_fwd',
+           'hs_frame_resize_fwd', 'hs_label_resize_fwd']
 
 
 def check(status, what):

@@ -1,0 +1,242 @@
+// Camera-size uint8 frames resized on the device with Pillow's 8-bit arithmetic (PIL.Image.resize, BILINEAR / BICUBIC: what the
+// reference's torchvision Resize / RandomResize run on PIL images, hyperseg/datasets/seg_transforms.py:224-246), and labels with its
+// NEAREST index tables.  The device does integer work only: the per-axis tables -- (first source index, taps) and 22-bit fixed-point
+// weights, or nearest indices -- are built on the host in float64 (hyperseg_amd/utils/resample.py), so nothing here has a rounding
+// that would have to be argued about.
+//
+// hs_frame_resize_fwd, ONE launch, the 8-bit intermediate of Pillow's horizontal pass never leaves registers:
+//   * a workgroup is 4 waves; a wave owns 64 consecutive output columns x RS_TY output rows, a thread one column of them (3 channels);
+//   * the thread streams the source rows its RS_TY rows' vertical windows cover (monotone in the row, so one contiguous range): per
+//     source row it makes the horizontal pass of its column -- taps x 3 byte loads against its column's weights, + 2^21, >> 22, clip8:
+//     Pillow's uint8 intermediate -- and adds it, times the vertical weight, into the int32 accumulators of the rows whose window holds
+//     that source row.  Any ksize on either axis: the loops are over the tables' own tap counts;
+//   * up to 8 horizontal taps (every scale down to 1/3 bilinear, bicubic upscaling) the column's weights sit in registers;
+//   * epilogue: + 2^21, >> 22, clip8, then the byte in the input's layout, or -- with InputNorm's table in LDS -- its float32 entry in
+//     planar layout.  A position of the view outside the resized image is the fill byte, through the table as well.
+// Neighbouring threads read overlapping windows of the same source rows: L1 / L2 traffic, HBM sees each source byte about
+// (1 + 2 support / (RS_TY scale)) times.  Bounds read from the tables are clamped to the source, so a wrong table cannot leave the frame.
+#include <hip/hip_runtime.h>
+#include <cstdint>
+#include <climits>
+#include "hyperseg_hip.h"
+#include "hs_common.h"
+#include "hs_ingest.h"
+
+namespace hs {
+
+constexpr int RS_BITS = 22;                    // Pillow's PRECISION_BITS for 8-bit images
+constexpr int RS_HALF = 1 << (RS_BITS - 1);
+constexpr int RS_COLS = 64;                    // output columns per wave
+constexpr int RS_GROUPS = 4;                   // waves per workgroup, each with its own rows
+constexpr int RS_TY = 4;                       // output rows per thread
+constexpr int RS_XREG = 8;                     // horizontal taps kept in registers
+constexpr int RS_MAX_DIM = 1 << 19;            // any frame or view dimension (the grid's y extent stays below 65536)
+
+struct ResizeArgs {
+    const uint8_t* x; void* y; const float* table;
+    const int32_t* yb; const int32_t* ykk; const int32_t* xb; const int32_t* xkk;
+    int Hi, Wi, Hr, Wr, Ho, Wo, oy, ox, yks, xks, hflip;
+    unsigned fill;                             // r | g << 8 | b << 16
+};
+
+__device__ __forceinline__ int clip8(int v) { return min(max(v >> RS_BITS, 0), 255); }
+
+// first index and tap count of table row i, clamped to a source of `size` and a table of `ks` columns
+__device__ __forceinline__ void resize_bounds(const int32_t* __restrict__ bounds, int i, int size, int ks, int& first, int& n) {
+    first = min(max(bounds[2 * i], 0), size - 1);
+    n = max(min(min(bounds[2 * i + 1], ks), size - first), 0);
+}
+
+template <bool HWC, bool NORM, bool XREG>
+__global__ __launch_bounds__(RS_COLS * RS_GROUPS)
+void frame_resize_kernel(const ResizeArgs a) {
+    __shared__ float tab[NORM ? INGEST_TABLE_FLOATS : 1];
+    if constexpr (NORM) {
+        ingest_table_to_lds(a.table, tab, (int)threadIdx.x);
+        __syncthreads();
+    }
+    const int x = blockIdx.x * RS_COLS + (threadIdx.x & (RS_COLS - 1));
+    const int y0 = (blockIdx.y * RS_GROUPS + (threadIdx.x / RS_COLS)) * RS_TY;
+    if (x >= a.Wo || y0 >= a.Ho) return;
+    const size_t b = blockIdx.z;
+    const int rx = a.ox + (a.hflip ? a.Wo - 1 - x : x);
+    const bool col_in = rx >= 0 && rx < a.Wr;
+
+    int ymin[RS_TY], yn[RS_TY], acc[RS_TY][INGEST_CHANNELS];
+    const int32_t* __restrict__ yk[RS_TY];
+    bool row_in[RS_TY];
+    int s0 = INT_MAX, s1 = 0;
+#pragma unroll
+    for (int r = 0; r < RS_TY; ++r) {
+        const int ry = a.oy + y0 + r;
+        row_in[r] = y0 + r < a.Ho && ry >= 0 && ry < a.Hr;
+        ymin[r] = 0; yn[r] = 0; yk[r] = a.ykk;
+        if (row_in[r]) {
+            resize_bounds(a.yb, ry, a.Hi, a.yks, ymin[r], yn[r]);
+            yk[r] = a.ykk + (size_t)ry * a.yks;
+            if (yn[r] > 0) { s0 = min(s0, ymin[r]); s1 = max(s1, ymin[r] + yn[r]); }
+        }
+#pragma unroll
+        for (int c = 0; c < INGEST_CHANNELS; ++c) acc[r][c] = RS_HALF;
+    }
+
+    if (col_in && s0 < s1) {
+        int xmin, xn;
+        resize_bounds(a.xb, rx, a.Wi, a.xks, xmin, xn);
+        const int32_t* __restrict__ xk = a.xkk + (size_t)rx * a.xks;
+        int wx[RS_XREG];
+        if constexpr (XREG) {
+#pragma unroll
+            for (int k = 0; k < RS_XREG; ++k) wx[k] = k < xn ? xk[k] : 0;
+        }
+        const size_t plane = (size_t)a.Hi * a.Wi;
+        for (int sy = s0; sy < s1; ++sy) {
+            int h[INGEST_CHANNELS] = {RS_HALF, RS_HALF, RS_HALF};
+            if constexpr (HWC) {
+                const uint8_t* __restrict__ p = a.x + (b * plane + (size_t)sy * a.Wi + xmin) * 3;
+                if constexpr (XREG) {
+#pragma unroll
+                    for (int k = 0; k < RS_XREG; ++k) {
+                        if (k < xn) {
+#pragma unroll
+                            for (int c = 0; c < INGEST_CHANNELS; ++c) h[c] += (int)p[3 * k + c] * wx[k];
+                        }
+                    }
+                } else {
+                    for (int k = 0; k < xn; ++k) {
+                        const int w = xk[k];
+#pragma unroll
+                        for (int c = 0; c < INGEST_CHANNELS; ++c) h[c] += (int)p[3 * k + c] * w;
+                    }
+                }
+            } else {
+                const uint8_t* __restrict__ p = a.x + b * INGEST_CHANNELS * plane + (size_t)sy * a.Wi + xmin;
+                if constexpr (XREG) {
+#pragma unroll
+                    for (int k = 0; k < RS_XREG; ++k) {
+                        if (k < xn) {
+#pragma unroll
+                            for (int c = 0; c < INGEST_CHANNELS; ++c) h[c] += (int)p[c * plane + k] * wx[k];
+                        }
+                    }
+                } else {
+                    for (int k = 0; k < xn; ++k) {
+                        const int w = xk[k];
+#pragma unroll
+                        for (int c = 0; c < INGEST_CHANNELS; ++c) h[c] += (int)p[c * plane + k] * w;
+                    }
+                }
+            }
+#pragma unroll
+            for (int c = 0; c < INGEST_CHANNELS; ++c) h[c] = clip8(h[c]);          // Pillow's uint8 intermediate
+#pragma unroll
+            for (int r = 0; r < RS_TY; ++r) {
+                const int k = sy - ymin[r];
+                if ((unsigned)k < (unsigned)yn[r]) {
+                    const int w = yk[r][k];
+#pragma unroll
+                    for (int c = 0; c < INGEST_CHANNELS; ++c) acc[r][c] += h[c] * w;
+                }
+            }
+        }
+    }
+
+    const size_t oplane = (size_t)a.Ho * a.Wo;
+#pragma unroll
+    for (int r = 0; r < RS_TY; ++r) {
+        const int y = y0 + r;
+        if (y >= a.Ho) break;
+        const bool inside = col_in && row_in[r];
+        const size_t pix = (size_t)y * a.Wo + x;
+#pragma unroll
+        for (int c = 0; c < INGEST_CHANNELS; ++c) {
+            const unsigned v = inside ? (unsigned)clip8(acc[r][c]) : (a.fill >> (8 * c)) & 255u;
+            if constexpr (NORM) {
+                static_cast<float*>(a.y)[(b * INGEST_CHANNELS + c) * oplane + pix] = ingest_dequant(tab, c, v);
+            } else if constexpr (HWC) {
+                static_cast<uint8_t*>(a.y)[(b * oplane + pix) * 3 + c] = (uint8_t)v;
+            } else {
+                static_cast<uint8_t*>(a.y)[(b * INGEST_CHANNELS + c) * oplane + pix] = (uint8_t)v;
+            }
+        }
+    }
+}
+
+template <bool HWC, bool NORM>
+static void launch_frame_resize(const ResizeArgs& a, dim3 grid, hipStream_t s) {
+    const dim3 block(RS_COLS * RS_GROUPS);
+    if (a.xks <= RS_XREG) hipLaunchKernelGGL((frame_resize_kernel<HWC, NORM, true>), grid, block, 0, s, a);
+    else hipLaunchKernelGGL((frame_resize_kernel<HWC, NORM, false>), grid, block, 0, s, a);
+}
+
+// labels: a gather through the two nearest tables; one thread per output pixel
+template <typename TI, typename TO>
+__global__ __launch_bounds__(256)
+void label_resize_kernel(const TI* __restrict__ x, const int32_t* __restrict__ iy, const int32_t* __restrict__ ix, TO* __restrict__ y,
+                         int Hi, int Wi, int Hr, int Wr, int Ho, int Wo, int oy, int ox, int hflip, int fill) {
+    const long item = (long)blockIdx.x * 256 + threadIdx.x;
+    if (item >= (long)Ho * Wo) return;
+    const int yy = (int)(item / Wo), xx = (int)(item - (long)yy * Wo);
+    const int ry = oy + yy, rx = ox + (hflip ? Wo - 1 - xx : xx);
+    const size_t b = blockIdx.y;
+    TO v = (TO)fill;
+    if (ry >= 0 && ry < Hr && rx >= 0 && rx < Wr) {
+        const int sy = min(max(iy[ry], 0), Hi - 1), sx = min(max(ix[rx], 0), Wi - 1);
+        v = (TO)x[(b * Hi + sy) * (size_t)Wi + sx];
+    }
+    y[b * (size_t)Ho * Wo + (size_t)item] = v;
+}
+
+}  // namespace hs
+
+using namespace hs;
+
+static bool resize_dims_ok(int32_t a, int32_t b, int32_t c, int32_t d, int32_t e, int32_t f) {
+    return a <= RS_MAX_DIM && b <= RS_MAX_DIM && c <= RS_MAX_DIM && d <= RS_MAX_DIM && e <= RS_MAX_DIM && f <= RS_MAX_DIM;
+}
+
+extern "C" int hs_frame_resize_fwd(const uint8_t* x, int32_t layout, int32_t batch, int32_t Hi, int32_t Wi,
+                                   const int32_t* y_bounds, const int32_t* y_kk, int32_t y_ksize, int32_t Hr,
+                                   const int32_t* x_bounds, const int32_t* x_kk, int32_t x_ksize, int32_t Wr,
+                                   int32_t Ho, int32_t Wo, int32_t oy, int32_t ox, int32_t hflip, uint32_t fill_rgb,
+                                   const float* norm_table, void* y, void* stream) {
+    if (!x || !y || !y_bounds || !y_kk || !x_bounds || !x_kk) return HS_ERR_BAD_ARG;
+    if (batch <= 0 || Hi <= 0 || Wi <= 0 || Hr <= 0 || Wr <= 0 || Ho <= 0 || Wo <= 0 || y_ksize <= 0 || x_ksize <= 0) return HS_ERR_BAD_ARG;
+    if (layout != HS_LAYOUT_HWC && layout != HS_LAYOUT_CHW) return HS_ERR_BAD_ARG;
+    if (batch > 65535 || !resize_dims_ok(Hi, Wi, Hr, Wr, Ho, Wo)) return HS_ERR_UNSUPPORTED;
+    if (oy < -RS_MAX_DIM || oy > RS_MAX_DIM || ox < -RS_MAX_DIM || ox > RS_MAX_DIM) return HS_ERR_UNSUPPORTED;
+    ResizeArgs a;
+    a.x = x; a.y = y; a.table = norm_table;
+    a.yb = y_bounds; a.ykk = y_kk; a.xb = x_bounds; a.xkk = x_kk;
+    a.Hi = Hi; a.Wi = Wi; a.Hr = Hr; a.Wr = Wr; a.Ho = Ho; a.Wo = Wo; a.oy = oy; a.ox = ox; a.yks = y_ksize; a.xks = x_ksize;
+    a.hflip = hflip != 0; a.fill = fill_rgb & 0xffffffu;
+    const dim3 grid((unsigned)((Wo + RS_COLS - 1) / RS_COLS), (unsigned)((Ho + RS_GROUPS * RS_TY - 1) / (RS_GROUPS * RS_TY)), (unsigned)batch);
+    hipStream_t s = (hipStream_t)stream;
+    const bool hwc = layout == HS_LAYOUT_HWC;
+    if (norm_table) { if (hwc) launch_frame_resize<true, true>(a, grid, s); else launch_frame_resize<false, true>(a, grid, s); }
+    else { if (hwc) launch_frame_resize<true, false>(a, grid, s); else launch_frame_resize<false, false>(a, grid, s); }
+    return launch_status();
+}
+
+extern "C" int hs_label_resize_fwd(const void* x, int32_t in_dtype, int32_t batch, int32_t Hi, int32_t Wi,
+                                   const int32_t* y_index, int32_t Hr, const int32_t* x_index, int32_t Wr,
+                                   int32_t Ho, int32_t Wo, int32_t oy, int32_t ox, int32_t hflip, int32_t fill,
+                                   void* y, int32_t out_dtype, void* stream) {
+    if (!x || !y || !y_index || !x_index) return HS_ERR_BAD_ARG;
+    if (batch <= 0 || Hi <= 0 || Wi <= 0 || Hr <= 0 || Wr <= 0 || Ho <= 0 || Wo <= 0) return HS_ERR_BAD_ARG;
+    if ((in_dtype != HS_EVAL_U8 && in_dtype != HS_EVAL_I64) || (out_dtype != HS_EVAL_U8 && out_dtype != HS_EVAL_I64)) return HS_ERR_BAD_ARG;
+    if (batch > 65535 || !resize_dims_ok(Hi, Wi, Hr, Wr, Ho, Wo)) return HS_ERR_UNSUPPORTED;
+    if (oy < -RS_MAX_DIM || oy > RS_MAX_DIM || ox < -RS_MAX_DIM || ox > RS_MAX_DIM) return HS_ERR_UNSUPPORTED;
+    const long blocks = ((long)Ho * Wo + 255) / 256;
+    if (blocks > 0x7fffffffL) return HS_ERR_UNSUPPORTED;
+    const dim3 grid((unsigned)blocks, (unsigned)batch), block(256);
+    hipStream_t s = (hipStream_t)stream;
+#define HS_LABEL_LAUNCH(TI, TO) hipLaunchKernelGGL((label_resize_kernel<TI, TO>), grid, block, 0, s, static_cast<const TI*>(x), y_index, \
+                                                   x_index, static_cast<TO*>(y), Hi, Wi, Hr, Wr, Ho, Wo, oy, ox, (int)(hflip != 0), fill)
+    if (in_dtype == HS_EVAL_U8 && out_dtype == HS_EVAL_U8) HS_LABEL_LAUNCH(uint8_t, uint8_t);
+    else if (in_dtype == HS_EVAL_U8) HS_LABEL_LAUNCH(uint8_t, int64_t);
+    else if (out_dtype == HS_EVAL_U8) HS_LABEL_LAUNCH(int64_t, uint8_t);
+    else HS_LABEL_LAUNCH(int64_t, int64_t);
+#undef HS_LABEL_LAUNCH
+    return launch_status();
+}

@@ -11,7 +11,7 @@ Reproduces the reference's protocol on synthetic frames (no dataset, checkpoint 
 ``torch.cuda.synchronize()`` is guarded so that the plumbing also runs on a CPU-only box (with a CPU-capable model).
 
     python -m hyperseg_amd.fps --config hyperseg-m --iterations 200 [--prepare] [--graph] [--remove-bn] [--batch-size 1]
-                               [--uint8 [--layout hwc|chw] [--overlay]] [--label-size H W] [--fused-metrics]
+                               [--uint8 [--layout hwc|chw] [--overlay] [--resize H W [--camera-size H W]]] [--label-size H W] [--fused-metrics]
 
 ``--label-size H W`` draws the targets at that size instead of the frame's: the reference's Cityscapes test configs resize the image
 only, so every frame's logits are resized to the label before they are counted (test.py:167-168) -- done here as well, by the
@@ -19,6 +19,10 @@ forward's last launch with ``--fused-metrics``.
 
 ``--uint8`` feeds uint8 frames (what a decoder or camera delivers) to a model with the default ``InputNorm`` attached: the
 host-to-device copy moves one byte per value and ToTensor + Normalize run on the device (``utils.inference.InputNorm``).
+
+``--resize H W`` (with ``--uint8``) attaches ``FrameResize((H, W))``: the synthetic frames are made at ``--camera-size`` (default twice
+H W) and resized on the device with ``PIL.Image.resize``'s bilinear arithmetic inside the timed region -- the reference's test configs
+do that resize on a host thread before the loop (``utils.inference.FrameResize``).
 
 ``bench.py`` is the judged benchmark (resident input, HIP-graph replay); this harness includes the H2D copy and the
 per-frame synchronisation exactly like the reference's, and by default its eager launches too, so its number is lower.
@@ -285,6 +289,12 @@ def main(argv=None):
     ap.add_argument('--label-size', nargs=2, type=int, metavar=('H', 'W'), default=None,
                     help="draw the targets at this size instead of the frame's: the logits are resized to it before they are counted "
                          "(test.py:167-168; the reference's Cityscapes test configs: 1024 2048)")
+    ap.add_argument('--resize', nargs=2, type=int, metavar=('H', 'W'), default=None,
+                    help="on top of --uint8: attach FrameResize((H, W)) (model.input_resize) -- the synthetic frames are made at "
+                         "--camera-size and resized on the device with PIL.Image.resize's bilinear arithmetic, inside the timed region "
+                         "(the reference's Cityscapes test configs: Resize([512, 1024]) of the 1024 x 2048 frame, on a host thread)")
+    ap.add_argument('--camera-size', nargs=2, type=int, metavar=('H', 'W'), default=None,
+                    help='size of the synthetic camera frames with --resize (default: twice --resize)')
     ap.add_argument('-t', '--trace', action='store_true',
                     help="the reference's torch.jit.trace switch (test_fps.py:49-50, 150-152).  The mirror's modules call the C ABI through "
                          "ctypes, which the tracer cannot see, so a traced module would be wrong; the purpose of tracing there -- no Python / "
@@ -302,6 +312,10 @@ def main(argv=None):
         raise SystemExit('--overlay and --fused-metrics both ride on the final upsample launch: one of them per run')
     if args.label_size is not None and min(args.label_size) <= 0:
         raise SystemExit('--label-size H W: two positive integers')
+    if args.resize is not None and not args.uint8:
+        raise SystemExit('--resize resizes uint8 frames: it needs --uint8')
+    if args.resize is not None and min(args.resize) <= 0 or args.camera_size is not None and (args.resize is None or min(args.camera_size) <= 0):
+        raise SystemExit('--resize H W [--camera-size H W]: positive integers, --camera-size only with --resize')
     if args.overlay and args.gpus and len(args.gpus) > 1:
         raise SystemExit('--overlay serves one device: with several --gpus run one process per GPU')
 
@@ -323,6 +337,12 @@ def main(argv=None):
     if args.uint8:
         from .utils.inference import InputNorm
         model.input_norm = InputNorm(layout=args.layout)
+    frame_size, label_size = tuple(spec['size']), args.label_size
+    if args.resize is not None:
+        from .utils.inference import FrameResize
+        model.input_resize = FrameResize(args.resize, 'bilinear', args.layout)
+        frame_size = tuple(args.camera_size) if args.camera_size is not None else (2 * args.resize[0], 2 * args.resize[1])
+        label_size = tuple(args.resize) if label_size is None else label_size       # the masks come at the resized frame's size
     if args.overlay:
         from .utils.inference import Overlay
         palette = torch.randint(0, 256, (spec['num_classes'], 3), generator=torch.Generator().manual_seed(0))
@@ -337,8 +357,8 @@ def main(argv=None):
         from .utils.inference import GraphedModel
         model = GraphedModel(model, num_classes=spec['num_classes'] if args.fused_metrics else None)
     bs = args.batch_size or spec['batch']
-    uniq = synthetic_batches(min(args.distinct, args.iterations), bs, spec['size'], spec['num_classes'], device,
-                             uint8=args.uint8, layout=args.layout, label_size=args.label_size)
+    uniq = synthetic_batches(min(args.distinct, args.iterations), bs, frame_size, spec['num_classes'], device,
+                             uint8=args.uint8, layout=args.layout, label_size=label_size)
     batches = [uniq[i % len(uniq)] for i in range(args.iterations)]
     res = measure_fps(model, batches, device, spec['num_classes'], fused_metrics=args.fused_metrics, overlay=args.overlay)
     frame = uniq[0][0]
@@ -346,6 +366,9 @@ def main(argv=None):
     res.update(config=args.config, batch_size=bs, size=list(spec['size']), device=str(device), remove_bn=args.remove_bn,
                prepared=bool(args.prepare and not args.remove_bn), graph=bool(args.graph and device.type == 'cuda'),
                protocol='test_fps.py: per-iteration sync + H2D + ' + ('HIP-graph replay' if args.graph else 'eager forward'))
+    if args.resize is not None:
+        res.update(resize=list(args.resize), camera_size=list(frame_size), size=list(args.resize),
+                   protocol=res['protocol'] + ' + camera frame resized on the device inside the timed region')
     if args.fused_metrics:
         res.update(fused_metrics=True, protocol=res['protocol'] + ' + confusion matrix counted inside the timed region by the '
                    "forward's last launch (the reference scores outside it)")

@@ -1522,6 +1522,90 @@ def upsample_overlay(x, size, frames, style, out=None):
     return mask, out
 
 
+def _resize_geometry(in_hw, size, view):
+    from .utils import resample
+    hi, wi = (int(s) for s in in_hw)
+    hr, wr = (int(s) for s in size)
+    if min(hi, wi, hr, wr) < 1:
+        raise ValueError(f'sizes must be >= 1, got {(hi, wi)} -> {(hr, wr)}')
+    return hi, wi, hr, wr, resample.check_view(view, (hr, wr))
+
+
+@_on_operand_device
+def frame_resize(x_u8, size, filter='bilinear', layout='hwc', view=None, norm=None, out=None):
+    """uint8 frames (B, Hi, Wi, 3) / (B, 3, Hi, Wi) (``layout``) resized to ``size`` = (Hr, Wr) with ``PIL.Image.resize``'s 8-bit
+    arithmetic (``filter``: 'bilinear' | 'bicubic'), byte for byte, in one launch (hs_frame_resize_fwd; the tables come from
+    ``utils.resample``).  ``view`` (a ``utils.resample.ResizeView``): the (Ho, Wo) window of the resized image to produce, at a signed
+    offset, optionally flipped, ``fill`` outside -- default the whole image.  Returns uint8 in the input's layout, or with ``norm`` (a
+    ``utils.inference.InputNorm``) the float32 (B, 3, Ho, Wo) image looked up in its table.  ``out``: a contiguous tensor of that
+    shape and dtype to write into.  Equal to ``utils.resample.frame_resize_cpu``.  Nothing here reads the device once the tables are
+    uploaded (first call per geometry): capturable."""
+    from .utils import resample
+    if layout not in _LAYOUT_CODES:
+        raise ValueError(f'layout {layout!r}: expected one of {tuple(_LAYOUT_CODES)}')
+    if filter not in resample.FILTERS:
+        raise ValueError(f'filter {filter!r}: expected one of {resample.FILTERS}')
+    if not isinstance(x_u8, torch.Tensor) or x_u8.dtype != torch.uint8 or x_u8.dim() != 4 or x_u8.shape[3 if layout == 'hwc' else 1] != 3:
+        raise ValueError(f'frames must be uint8 {"(B, H, W, 3)" if layout == "hwc" else "(B, 3, H, W)"}, got '
+                         f'{getattr(x_u8, "dtype", type(x_u8))} {tuple(getattr(x_u8, "shape", ()))}')
+    if norm is not None and norm.layout != layout:
+        raise ValueError(f"norm describes '{norm.layout}' frames, these are '{layout}'")
+    b = x_u8.shape[0]
+    hi, wi, hr, wr, view = _resize_geometry(x_u8.shape[1:3] if layout == 'hwc' else x_u8.shape[2:], size, view)
+    (ho, wo), (oy, ox) = view.size, view.offset
+    if norm is not None:
+        shape, dtype = (b, 3, ho, wo), torch.float32
+    else:
+        shape, dtype = ((b, ho, wo, 3) if layout == 'hwc' else (b, 3, ho, wo)), torch.uint8
+    if out is None:
+        out = torch.empty(shape, device=x_u8.device, dtype=dtype)
+    elif not isinstance(out, torch.Tensor) or tuple(out.shape) != shape or out.dtype != dtype or out.device != x_u8.device:
+        raise ValueError(f'out must be a {dtype} tensor of shape {shape} on {x_u8.device}')
+    if b == 0:
+        raise ValueError('empty batch')
+    yb, ykk = resample.device_coeffs(hi, hr, filter, x_u8.device)
+    xb, xkk = resample.device_coeffs(wi, wr, filter, x_u8.device)
+    fill = view.fill[0] | view.fill[1] << 8 | view.fill[2] << 16
+    st = _hip.lib.hs_frame_resize_fwd(_hip.dev_ptr(x_u8, 'x_u8', torch.uint8), _LAYOUT_CODES[layout], b, hi, wi,
+                                      yb.data_ptr(), ykk.data_ptr(), ykk.shape[1], hr, xb.data_ptr(), xkk.data_ptr(), xkk.shape[1], wr,
+                                      ho, wo, oy, ox, int(view.hflip), fill,
+                                      None if norm is None else _hip.dev_ptr(norm.table(x_u8.device), 'table'),
+                                      _hip.dev_ptr(out, 'out', dtype), _hip.stream_ptr())
+    _hip.check(st, 'hs_frame_resize_fwd')
+    return out
+
+
+_LABEL_DTYPES = {torch.uint8: 0, torch.int64: 1}           # HS_EVAL_U8 / HS_EVAL_I64
+
+
+@_on_operand_device
+def label_resize(t, size, view=None, fill=255, out=None):
+    """Labels (B, Hi, Wi), uint8 or int64, resized to ``size`` with ``PIL.Image.resize(..., NEAREST)``'s index tables (hs_label_resize_fwd,
+    one launch), then ``view`` as :func:`frame_resize`'s with ``fill`` outside (the view's own fill is the frames').  Returns the
+    input's dtype, or ``out``'s (uint8 | int64, contiguous, (B, Ho, Wo)).  Equal to ``utils.resample.label_resize_cpu``."""
+    from .utils import resample
+    if not isinstance(t, torch.Tensor) or t.dtype not in _LABEL_DTYPES or t.dim() != 3:
+        raise ValueError(f'labels must be uint8 or int64 (B, H, W), got {getattr(t, "dtype", type(t))} {tuple(getattr(t, "shape", ()))}')
+    b = t.shape[0]
+    hi, wi, hr, wr, view = _resize_geometry(t.shape[1:], size, view)
+    (ho, wo), (oy, ox) = view.size, view.offset
+    if out is None:
+        out = torch.empty((b, ho, wo), device=t.device, dtype=t.dtype)
+    elif not isinstance(out, torch.Tensor) or tuple(out.shape) != (b, ho, wo) or out.dtype not in _LABEL_DTYPES or out.device != t.device:
+        raise ValueError(f'out must be a uint8 or int64 tensor of shape {(b, ho, wo)} on {t.device}')
+    if b == 0:
+        raise ValueError('empty batch')
+    fill = int(fill)
+    if not (0 <= fill <= 255 or (out.dtype == torch.int64 and -2 ** 31 <= fill < 2 ** 31)):
+        raise ValueError(f'fill {fill} does not fit the output labels')
+    iy, ix = resample.device_nearest(hi, hr, t.device), resample.device_nearest(wi, wr, t.device)
+    st = _hip.lib.hs_label_resize_fwd(_hip.dev_ptr(t, 'labels', t.dtype), _LABEL_DTYPES[t.dtype], b, hi, wi, iy.data_ptr(), hr, ix.data_ptr(), wr,
+                                      ho, wo, oy, ox, int(view.hflip), fill, _hip.dev_ptr(out, 'out', out.dtype), _LABEL_DTYPES[out.dtype],
+                                      _hip.stream_ptr())
+    _hip.check(st, 'hs_label_resize_fwd')
+    return out
+
+
 # ------------------------------------------------------------------------------------------
 # small caches keyed on parameter versions (host-side only; used by the fused inference route --
 # tensors that require grad take the hyperseg_amd.autograd route, which folds nothing)

@@ -130,11 +130,24 @@ class HyperGenBase(EpochOnModeSwitch, nn.Module):
     input_norm = None
     # a utils.inference.Overlay: what ``overlay()`` colours and blends with.  A plain attribute as well
     overlay_style = None
+    # a utils.inference.FrameResize: uint8 frames of another size (camera frames) are resized to it on the device first.  A plain attribute
+    input_resize = None
 
-    def frame_size(self, x):
-        """(H, W) of an input tensor: a float image (B, 3, H, W), or uint8 frames in ``input_norm``'s layout."""
+    def resized(self, x):
+        """``x`` itself, or -- a uint8 frame tensor of another size than ``input_resize``'s -- the resized uint8 frames (one launch)."""
+        resize = self.input_resize
+        if resize is None or not isinstance(x, torch.Tensor) or x.dtype != torch.uint8:
+            return x
+        if resize.layout != self._require_norm().layout:
+            raise ValueError(f"model.input_resize takes '{resize.layout}' frames, model.input_norm describes '{self.input_norm.layout}' frames")
+        return resize(x) if resize.applies_to(x) else x
+
+    def frame_size(self, x, resize=True):
+        """(H, W) of an input tensor as the model sees it: a float image (B, 3, H, W), or uint8 frames in ``input_norm``'s layout -- with
+        ``input_resize`` set, the size they are resized to (``resize=False``: an entry of a list input, which is never resized)."""
         if x.dtype == torch.uint8:
-            return tuple(self._require_norm().frame_size(x)[1:])
+            size = tuple(self._require_norm().frame_size(x)[1:])
+            return tuple(self.input_resize.size) if (resize and self.input_resize is not None) else size
         return tuple(x.shape[2:])
 
     def _require_norm(self):
@@ -193,8 +206,9 @@ class HyperGenBase(EpochOnModeSwitch, nn.Module):
         logits are never written; pyramid / h-flip inference falls back to the logits path.  ``size``: masks at that (H, W) instead
         of the frame's -- the logits resized to it before the arg-max, as test.py:167-168 does for a label of another size; from
         the same one launch (``HF.upsample2_argmax``) where the arg-max is, else the logits route plus that resize."""
+        x = self.resized(x)
         first = x if isinstance(x, torch.Tensor) else x[0]
-        if size is not None and tuple(size) == self.frame_size(first):
+        if size is not None and tuple(size) == self.frame_size(first, isinstance(x, torch.Tensor)):
             size = None
         fused = isinstance(x, torch.Tensor) and not self.training and not self.inference_hflip
         if size is None:
@@ -219,6 +233,7 @@ class HyperGenBase(EpochOnModeSwitch, nn.Module):
         -- computes the masks the way ``segment()`` / ``forward()`` do (resizing the logits to a target of another size) and
         counts them with ``confmat``'s own update.  Same numbers on every route."""
         n = confmat.num_classes
+        x = self.resized(x)
         fused = (isinstance(x, torch.Tensor) and x.is_cuda and not self.training and isinstance(target, torch.Tensor)
                  and target.is_cuda and target.dtype in (torch.uint8, torch.int64) and target.dim() == 3
                  and target.shape[0] == x.shape[0] and n <= min(256, HF.eval_max_classes()))
@@ -233,7 +248,7 @@ class HyperGenBase(EpochOnModeSwitch, nn.Module):
             if masks.dtype == torch.uint8:
                 return masks
             raise RuntimeError('the decoder returned logits from its masks=True route: nothing was scored')
-        out_res = self.frame_size(x if isinstance(x, torch.Tensor) else x[0])
+        out_res = self.frame_size(x, True) if isinstance(x, torch.Tensor) else self.frame_size(x[0], False)
         if tuple(target.shape[1:]) != out_res:
             pred = self(x)
             pred = HF.upsample_bilinear(pred.contiguous(), tuple(target.shape[1:])) if pred.is_cuda else \
@@ -261,6 +276,7 @@ class HyperGenBase(EpochOnModeSwitch, nn.Module):
         if style is None:
             raise TypeError('overlay() needs a style: set model.overlay_style = hyperseg_amd.Overlay(color_map, alpha, ignore_index, '
                             'layout) or pass style=')
+        x = self.resized(x)
         first = x if isinstance(x, torch.Tensor) else x[0]
         if frames is None:
             if first.dtype != torch.uint8:
@@ -270,7 +286,7 @@ class HyperGenBase(EpochOnModeSwitch, nn.Module):
                 raise ValueError(f"the input frames are '{self.input_norm.layout}' (model.input_norm), the style blends over "
                                  f"'{style.layout}' frames")
             frames = first
-        size = (first.shape[0],) + self.frame_size(first)
+        size = (first.shape[0],) + self.frame_size(first, isinstance(x, torch.Tensor))
         if tuple(style.frame_size(frames)) != size:
             raise ValueError(f'frames are {tuple(style.frame_size(frames))} (B, H, W), the input is {size}')
         fused = isinstance(x, torch.Tensor) and x.is_cuda and frames.is_cuda and not self.training and not self.inference_hflip
@@ -294,9 +310,9 @@ class HyperGenBase(EpochOnModeSwitch, nn.Module):
 
     def forward(self, x):
         if isinstance(x, torch.Tensor):
-            return self.process_single_tensor(x)
+            return self.process_single_tensor(self.resized(x))
         assert isinstance(x, (list, tuple)), 'x must be of type list, tuple, or tensor'
-        out_res = self.frame_size(x[0])   # the first pyramid level sets the output resolution
+        out_res = self.frame_size(x[0], resize=False)   # the first pyramid level sets the output resolution
         merged = None
         for level in x:
             y = self.process_single_tensor(level)

@@ -365,3 +365,45 @@ class GraphedTrainStep:
         from .functional import bump_weights_epoch
         bump_weights_epoch()
         return self.loss, self.pred
+
+
+def device_augment(frames_u8, labels, scale, crop, offset, hflip, norm, lbl_fill=255, fill=(0, 0, 0)):
+    """The reference's train-time chain RandomResize -> RandomCrop(pad_if_needed) -> RandomHorizontalFlip -> ToTensor -> Normalize
+    (hyperseg/datasets/seg_transforms.py:224-334) for GIVEN parameters, on the device: per sample one ``functional.frame_resize``
+    launch (bicubic, Pillow's bytes, looked up in ``norm``'s table) and one ``functional.label_resize`` launch (nearest), each
+    producing only the crop.  Drawing the parameters stays with the caller.
+
+    ``frames_u8``: uint8 (B, H, W, 3) / (B, 3, H, W) as ``norm.layout`` says; ``labels``: (B, H, W) uint8 or int64.  ``scale``: the
+    resize factor -- the resized size is ``round((H, W) * scale)``, numpy's rounding as the reference's; ``crop``: (h, w) of the result;
+    ``offset``: (top, left) of the crop IN THE RESIZED IMAGE, signed -- what lies outside is padding: ``fill`` for the frame (before
+    normalisation, as the reference pads the PIL image) and ``lbl_fill`` for the label; ``hflip``: flip the crop.  ``scale``,
+    ``offset`` and ``hflip`` are one value for the batch or a sequence of B.  Returns ``(image float32 (B, 3, h, w), label int64
+    (B, h, w))``.  CPU tensors take ``utils.resample``'s CPU implementation: same values."""
+    import numpy as np
+    from . import functional as HF
+    from .utils import resample
+    b, h, w = norm.frame_size(frames_u8)
+    if not isinstance(labels, torch.Tensor) or tuple(labels.shape) != (b, h, w):
+        raise ValueError(f'labels must be (B, H, W) = {(b, h, w)}, got {tuple(getattr(labels, "shape", ()))}')
+    ch, cw = (int(s) for s in crop)
+
+    def per_sample(v, scalar):
+        return [v] * b if scalar(v) else list(v)
+    scales = per_sample(scale, lambda v: not isinstance(v, (list, tuple)) and getattr(v, 'ndim', 0) == 0)
+    offsets = per_sample(offset, lambda v: len(v) == 2 and not isinstance(v[0], (list, tuple)) and getattr(v[0], 'ndim', 0) == 0)
+    flips = per_sample(hflip, lambda v: not isinstance(v, (list, tuple)) and getattr(v, 'ndim', 0) == 0)
+    if not len(scales) == len(offsets) == len(flips) == b:
+        raise ValueError('scale, offset and hflip take one value, or one per sample')
+    image = torch.empty(b, 3, ch, cw, dtype=torch.float32, device=frames_u8.device)
+    label = torch.empty(b, ch, cw, dtype=torch.int64, device=frames_u8.device)
+    frames_u8, labels = frames_u8.contiguous(), labels.contiguous()
+    for i in range(b):
+        size = tuple(int(s) for s in np.round(np.array((h, w)) * float(scales[i])).astype(int))
+        view = resample.ResizeView((ch, cw), tuple(int(o) for o in offsets[i]), bool(flips[i]), fill)
+        if frames_u8.is_cuda:
+            HF.frame_resize(frames_u8[i:i + 1], size, 'bicubic', norm.layout, view=view, norm=norm, out=image[i:i + 1])
+            HF.label_resize(labels[i:i + 1], size, view=view, fill=lbl_fill, out=label[i:i + 1])
+        else:
+            image[i:i + 1] = resample.frame_resize_cpu(frames_u8[i:i + 1], size, 'bicubic', norm.layout, view=view, norm=norm)
+            label[i:i + 1] = resample.label_resize_cpu(labels[i:i + 1], size, view=view, fill=lbl_fill, out_dtype=torch.int64)
+    return image, label

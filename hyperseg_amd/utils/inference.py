@@ -88,6 +88,52 @@ class InputNorm:
         return f'InputNorm(mean={self.mean.tolist()}, std={self.std.tolist()}, layout={self.layout!r})'
 
 
+class FrameResize:
+    """The resize in front of the model as data: uint8 frames of any size -> ``size`` = (H, W) with ``PIL.Image.resize``'s 8-bit
+    arithmetic (``interpolation``: 'bilinear' | 'bicubic'), byte for byte -- what the reference's test configs run on a host thread as
+    ``torchvision.transforms.Resize`` on the PIL camera frame.  ``layout`` as :class:`InputNorm`'s.  Callable: one
+    ``functional.frame_resize`` launch on CUDA tensors, ``utils.resample.frame_resize_cpu`` on CPU tensors, the same bytes either way.
+    Attached to a model (``model.input_resize = FrameResize(...)`` or ``prepare_for_inference(model, ..., input_resize=...)``), a uint8
+    frame of another size is resized first by ``forward`` / ``segment`` / ``evaluate`` / ``overlay``, and everything after that runs on
+    the resized uint8 frame.  Not a parameter, not a buffer: state dicts are unaffected."""
+
+    LAYOUTS = InputNorm.LAYOUTS
+
+    def __init__(self, size, interpolation='bilinear', layout='hwc'):
+        from . import resample
+        if layout not in self.LAYOUTS:
+            raise ValueError(f'layout {layout!r}: expected one of {self.LAYOUTS}')
+        if interpolation not in resample.FILTERS:
+            raise ValueError(f'interpolation {interpolation!r}: expected one of {resample.FILTERS}')
+        size = tuple(int(s) for s in size)
+        if len(size) != 2 or min(size) < 1:
+            raise ValueError(f'size must be (H, W) with both >= 1, got {size}')
+        self.size, self.interpolation, self.layout = size, interpolation, layout
+
+    def frame_hw(self, x):
+        """(H, W) of uint8 frames in this resize's layout."""
+        return (x.shape[1], x.shape[2]) if self.layout == 'hwc' else (x.shape[2], x.shape[3])
+
+    def applies_to(self, x):
+        """Whether ``x`` is a batch of uint8 frames (this layout) of another size than ``size``."""
+        return (isinstance(x, torch.Tensor) and x.dtype == torch.uint8 and x.dim() == 4 and x.shape[3 if self.layout == 'hwc' else 1] == 3
+                and tuple(self.frame_hw(x)) != self.size)
+
+    def __call__(self, x, view=None, norm=None, out=None):
+        if isinstance(x, torch.Tensor) and x.is_cuda:
+            from .. import functional as HF
+            return HF.frame_resize(x.contiguous(), self.size, self.interpolation, self.layout, view=view, norm=norm, out=out)
+        from . import resample
+        got = resample.frame_resize_cpu(x, self.size, self.interpolation, self.layout, view=view, norm=norm)
+        if out is not None:
+            out.copy_(got)
+            got = out
+        return got
+
+    def __repr__(self):
+        return f'FrameResize(size={self.size}, interpolation={self.interpolation!r}, layout={self.layout!r})'
+
+
 class Overlay:
     """The display of a prediction as data: the class map coloured with ``color_map`` and alpha-blended over the uint8 frame, returned as
     uint8 RGB in the frame's ``layout`` -- the reference's ``tensor2rgb(blend_seg(img, pred, color_map, alpha, ignore_index))``
@@ -731,7 +777,7 @@ def set_ir_math(model, mode):
 
 
 def prepare_for_inference(model, fold_bn=True, channels_last=False, fused_depthwise=False, split_gemm=False, ir_math='auto',
-                          chain_k1=True, input_norm=None):
+                          chain_k1=True, input_norm=None, input_resize=None):
     """In place; returns the number of BatchNorms folded by ``fold_bn``.  ``model``: a HyperGen in eval mode (module
     docstring for what each switch does).  The fused routes are installed first, so ``fold_bn`` only touches the
     Conv -> BatchNorm pairs that no fused route reads.  ``ir_math``: :func:`set_ir_math` for the decoder ('auto' = the
@@ -739,13 +785,18 @@ def prepare_for_inference(model, fold_bn=True, channels_last=False, fused_depthw
     ``chain_k1``: the decoder's three coarse k = 1 levels as ONE launch with in-launch neighbour hand-offs (hs_k1_chain_fwd;
     v1_0 decoders whose whole grid is resident at once -- the others keep one launch per level).  One frame in flight per model:
     the launch keeps its generation counter in a per-decoder workspace.  ``input_norm``: an :class:`InputNorm` to attach
-    (``model.input_norm``): the model then takes uint8 frames."""
+    (``model.input_norm``): the model then takes uint8 frames.  ``input_resize``: a :class:`FrameResize` to attach
+    (``model.input_resize``): uint8 frames of another size are then resized to it on the device first."""
     assert not model.training, 'call model.eval() first'
     folded = 0
     if input_norm is not None:
         if not isinstance(input_norm, InputNorm):
             raise TypeError('input_norm must be a hyperseg_amd.utils.inference.InputNorm')
         model.input_norm = input_norm
+    if input_resize is not None:
+        if not isinstance(input_resize, FrameResize):
+            raise TypeError('input_resize must be a hyperseg_amd.utils.inference.FrameResize')
+        model.input_resize = input_resize
     if ir_math is not None:
         set_ir_math(model, ir_math)
     if hasattr(model, 'decoder'):
@@ -791,7 +842,8 @@ class GraphedModel(nn.Module):
     ``forward(x)``: ``x`` a single tensor, on the device or in (pinned) host memory -- it is copied into the graph's
     static input buffer on the current stream, so the host-to-device copy IS the staging copy.  uint8 frames (a model with an
     ``input_norm``) are staged as uint8 -- a quarter of the bytes -- and normalised inside the graph; the key holds the uint8 shape,
-    so 'hwc' and 'chw' frames get graphs of their own.  One graph is captured per
+    so 'hwc' and 'chw' frames get graphs of their own.  With ``model.input_resize`` set the static buffer holds the camera-size frame
+    and the resize is a node of the graph: one replay per camera frame.  One graph is captured per
     (shape, dtype) on first use (``warmup`` eager forwards on a side stream first: library handles, workspaces and the
     lazily built buffers of the fused routes must exist before capture).  The returned tensor is the graph's static output:
     valid until the next forward of the same shape (``clone_output=True`` hands out copies).  Anything the graph cannot
@@ -863,8 +915,11 @@ class GraphedModel(nn.Module):
         return self._graphs[key]
 
     def _norm_of(self, x):
-        """Part of a uint8 frame's graph key: the captured launches hold the norm's table and layout."""
-        return getattr(self.model, 'input_norm', None) if x.dtype == torch.uint8 else None
+        """Part of a uint8 frame's graph key: the captured launches hold the norm's table and layout, and the resize's geometry."""
+        if x.dtype != torch.uint8:
+            return None
+        norm, resize = getattr(self.model, 'input_norm', None), getattr(self.model, 'input_resize', None)
+        return norm if resize is None else (norm, resize)
 
     accepts_host_input = True                  # hyperseg_amd.fps.measure_fps hands the pinned host batch over as it is
     owns_confusion = True                      # ... and reads evaluate()'s counts from ``confusion``
@@ -964,7 +1019,7 @@ class GraphedModel(nn.Module):
             scratch = torch.zeros_like(confusion)                # the warm-up passes execute: their counts go here
 
             def run(xs, ts, out=confusion):
-                return self.model.process_single_tensor(xs, masks=True, score=(ts, n, out, self.per_image))
+                return self.model.process_single_tensor(self.model.resized(xs), masks=True, score=(ts, n, out, self.per_image))
 
             entry = self._capture(key, [x, target], device, run=run, warm=lambda xs, ts: run(xs, ts, scratch))
         return self._replay(entry, [x, target], device)
@@ -992,13 +1047,14 @@ class GraphedModel(nn.Module):
         if frames is None and style.layout != model._require_norm().layout:
             raise ValueError(f"the input frames are '{model.input_norm.layout}' (model.input_norm), the style blends over '{style.layout}' frames")
         size = (x.shape[0],) + tuple(model.frame_size(x))
-        if tuple(style.frame_size(x if frames is None else frames)) != size:
-            raise ValueError(f'frames are {tuple(style.frame_size(x if frames is None else frames))} (B, H, W), the input is {size}')
+        if frames is not None and tuple(style.frame_size(frames)) != size:
+            raise ValueError(f'frames are {tuple(style.frame_size(frames))} (B, H, W), the input is {size}')
         key = ('overlay', tuple(x.shape), x.dtype, None if frames is None else tuple(frames.shape), device, self._norm_of(x), style)
         entry = self._graphs.get(key)
         inputs = [x] if frames is None else [x, frames]
         if entry is None:
             def run(xs, fs=None):
+                xs = model.resized(xs)               # (a camera-size uint8 frame: the resize is the graph's first node)
                 return model.process_single_tensor(xs, masks=True, overlay=(xs if fs is None else fs, style, None))
 
             entry = self._capture(key, inputs, device, run=run)

@@ -485,6 +485,31 @@ int hs_overlay_fwd(const uint8_t* masks, const uint8_t* frames, int32_t layout, 
 int hs_upsample_overlay_fwd(const float* x, int32_t batch, int32_t channels, int32_t Hi, int32_t Wi, int32_t Ho, int32_t Wo,
                             const uint8_t* frames, int32_t layout, const float* tables, int32_t num_colors, int32_t ignore_index,
                             uint8_t* mask, uint8_t* overlay, void* stream);
+/* Camera-size uint8 frames and their labels resized on the device with Pillow's arithmetic (csrc/hs_resample.hip): what the reference's
+ * torchvision Resize / RandomResize compute on PIL images (hyperseg/datasets/seg_transforms.py:224-246), plus the crop, pad and flip that
+ * follow them (:249-334) as a VIEW, so that only what the crop keeps is resampled.  One geometry per launch, shared by the batch.
+ * Tables (built on the host in float64, hyperseg_amd/utils/resample.py; int32, on the device), per axis, for source size S -> resized R:
+ *   bounds (R, 2) = (first source index, taps) and kk (R, ksize) 22-bit fixed-point weights, zero-padded (frames);  index (R,) (labels).
+ * View: output pixel (y, x) of (Ho, Wo) is resized pixel (oy + y, ox + (hflip ? Wo - 1 - x : x)) of (Hr, Wr), or the fill where that lies
+ * outside; the identity view is Ho = Hr, Wo = Wr, oy = ox = 0, hflip = 0.
+ *   hs_frame_resize_fwd: x uint8 (B, Hi, Wi, 3) | (B, 3, Hi, Wi) by layout.  A pixel is clip8((2^21 + sum px kk) >> 22) along the width
+ *     first, into Pillow's uint8 intermediate (kept in registers, never written), then along the height.  norm_table null: y uint8 in the
+ *     input's layout; else y float32 (B, 3, Ho, Wo), every byte -- the fill included (fill_rgb = r | g << 8 | b << 16) -- looked up in
+ *     the (3, 256) table of hs_image_ingest_fwd.  Any ksize >= 1 on either axis, any sizes >= 1, any alignment of x and y (a float's 4
+ *     bytes for the float form).  Table bounds are clamped to the source.  The caller guarantees 255 * sum |kk| + 2^21 < 2^31 per table row
+ *     (true for both filters at every scale; utils/resample.py asserts it).
+ *   hs_label_resize_fwd: x (B, Hi, Wi) and y (B, Ho, Wo), each HS_EVAL_U8 or HS_EVAL_I64: a gather through the two index tables.
+ * HS_ERR_UNSUPPORTED -- nothing launched -- for batch > 65535, any of Hi, Wi, Hr, Wr, Ho, Wo above 2^19, or |oy|, |ox| above 2^19.
+ * Neither entry reads anything back: both are capturable. */
+int hs_frame_resize_fwd(const uint8_t* x, int32_t layout, int32_t batch, int32_t Hi, int32_t Wi,
+                        const int32_t* y_bounds, const int32_t* y_kk, int32_t y_ksize, int32_t Hr,
+                        const int32_t* x_bounds, const int32_t* x_kk, int32_t x_ksize, int32_t Wr,
+                        int32_t Ho, int32_t Wo, int32_t oy, int32_t ox, int32_t hflip, uint32_t fill_rgb,
+                        const float* norm_table, void* y, void* stream);
+int hs_label_resize_fwd(const void* x, int32_t in_dtype, int32_t batch, int32_t Hi, int32_t Wi,
+                        const int32_t* y_index, int32_t Hr, const int32_t* x_index, int32_t Wr,
+                        int32_t Ho, int32_t Wo, int32_t oy, int32_t ox, int32_t hflip, int32_t fill,
+                        void* y, int32_t out_dtype, void* stream);
 int hs_mbconv_expand_dw_fwd(const float* x, int32_t batch, int32_t c_in, int32_t H, int32_t W,
                             const float* w_expand, int32_t c_mid, const float* scale0, const float* shift0,
                             const float* w_dw, int32_t k, int32_t stride, int32_t pad_t, int32_t pad_l,
