@@ -9,6 +9,9 @@ def __getattr__(name):
     if name == 'FrameResize':
         from .utils.inference import FrameResize
         return FrameResize
+    if name == 'ColorJitterParams':
+        from .utils.jitter import ColorJitterParams
+        return ColorJitterParams
     if name == 'Overlay':
         from .utils.inference import Overlay
         return Overlay

@@ -1606,6 +1606,53 @@ def label_resize(t, size, view=None, fill=255, out=None):
     return out
 
 
+@_on_operand_device
+def color_jitter(x_u8, params, layout='hwc', norm=None, out=None, table=None):
+    """torchvision's ``ColorJitter`` for given parameters on uint8 frames (B, H, W, 3) / (B, 3, H, W) (``layout``), Pillow's bytes
+    (hs_color_jitter_fwd; the arithmetic: ``utils.jitter``).  ``params``: one ``ColorJitterParams`` for the batch or a sequence of B.
+    Returns uint8 in the input's layout, or with ``norm`` (a ``utils.inference.InputNorm``) the float32 (B, 3, H, W) image looked up
+    in its table.  ``out``: a contiguous tensor of that shape and dtype to write into.  Equal to ``utils.jitter.color_jitter_cpu``.
+
+    ``table``: the caller's own parameter records on the device -- int32 (B, ``utils.jitter.TABLE_WORDS``), contiguous, what
+    ``utils.jitter.params_table(params, B).to(device)`` gives; ``params`` is then not read (pass None).  The kernels read the table when
+    they run, so a captured graph replays with what the caller last copied into it.  Launches: a clear of B sums, the mean pass (only
+    samples whose order holds contrast do work) and the apply pass; without ``table``, the apply pass alone when no sample has contrast,
+    and one small host-to-device copy of the records in front.  Nothing is read back: with ``table`` the call is capturable."""
+    from .utils import jitter
+    if layout not in _LAYOUT_CODES:
+        raise ValueError(f'layout {layout!r}: expected one of {tuple(_LAYOUT_CODES)}')
+    if not isinstance(x_u8, torch.Tensor) or x_u8.dtype != torch.uint8 or x_u8.dim() != 4 or x_u8.shape[3 if layout == 'hwc' else 1] != 3:
+        raise ValueError(f'frames must be uint8 {"(B, H, W, 3)" if layout == "hwc" else "(B, 3, H, W)"}, got '
+                         f'{getattr(x_u8, "dtype", type(x_u8))} {tuple(getattr(x_u8, "shape", ()))}')
+    if norm is not None and norm.layout != layout:
+        raise ValueError(f"norm describes '{norm.layout}' frames, these are '{layout}'")
+    b = x_u8.shape[0]
+    h, w = x_u8.shape[1:3] if layout == 'hwc' else x_u8.shape[2:]
+    shape, dtype = ((b, 3, h, w), torch.float32) if norm is not None else (tuple(x_u8.shape), torch.uint8)
+    if b == 0 or h == 0 or w == 0:
+        raise ValueError('empty batch')
+    if table is None:
+        records = jitter.params_table(params, b)
+        need_mean = bool((records[:, 5] >> jitter.OP_CODES['contrast'] & 1).any())
+        table = records.to(x_u8.device)
+    elif (not isinstance(table, torch.Tensor) or table.dtype != torch.int32 or tuple(table.shape) != (b, jitter.TABLE_WORDS)
+          or table.device != x_u8.device or not table.is_contiguous()):
+        raise ValueError(f'table must be a contiguous int32 tensor of shape {(b, jitter.TABLE_WORDS)} on {x_u8.device}')
+    else:
+        need_mean = True                                       # what it will hold when the kernels run is the caller's business
+    if out is None:
+        out = torch.empty(shape, device=x_u8.device, dtype=dtype)
+    elif not isinstance(out, torch.Tensor) or tuple(out.shape) != shape or out.dtype != dtype or out.device != x_u8.device:
+        raise ValueError(f'out must be a {dtype} tensor of shape {shape} on {x_u8.device}')
+    sums = torch.empty(b, device=x_u8.device, dtype=torch.int64) if need_mean else None
+    st = _hip.lib.hs_color_jitter_fwd(_hip.dev_ptr(x_u8, 'x_u8', torch.uint8), _LAYOUT_CODES[layout], b, h, w,
+                                      _hip.dev_ptr(table, 'table', torch.int32), None if sums is None else sums.data_ptr(),
+                                      None if norm is None else _hip.dev_ptr(norm.table(x_u8.device), 'table'),
+                                      _hip.dev_ptr(out, 'out', dtype), _hip.stream_ptr())
+    _hip.check(st, 'hs_color_jitter_fwd')
+    return out
+
+
 # ------------------------------------------------------------------------------------------
 # small caches keyed on parameter versions (host-side only; used by the fused inference route --
 # tensors that require grad take the hyperseg_amd.autograd route, which folds nothing)

@@ -367,7 +367,7 @@ class GraphedTrainStep:
         return self.loss, self.pred
 
 
-def device_augment(frames_u8, labels, scale, crop, offset, hflip, norm, lbl_fill=255, fill=(0, 0, 0)):
+def device_augment(frames_u8, labels, scale, crop, offset, hflip, norm, lbl_fill=255, fill=(0, 0, 0), jitter=None):
     """The reference's train-time chain RandomResize -> RandomCrop(pad_if_needed) -> RandomHorizontalFlip -> ToTensor -> Normalize
     (hyperseg/datasets/seg_transforms.py:224-334) for GIVEN parameters, on the device: per sample one ``functional.frame_resize``
     launch (bicubic, Pillow's bytes, looked up in ``norm``'s table) and one ``functional.label_resize`` launch (nearest), each
@@ -378,7 +378,13 @@ def device_augment(frames_u8, labels, scale, crop, offset, hflip, norm, lbl_fill
     ``offset``: (top, left) of the crop IN THE RESIZED IMAGE, signed -- what lies outside is padding: ``fill`` for the frame (before
     normalisation, as the reference pads the PIL image) and ``lbl_fill`` for the label; ``hflip``: flip the crop.  ``scale``,
     ``offset`` and ``hflip`` are one value for the batch or a sequence of B.  Returns ``(image float32 (B, 3, h, w), label int64
-    (B, h, w))``.  CPU tensors take ``utils.resample``'s CPU implementation: same values."""
+    (B, h, w))``.  CPU tensors take ``utils.resample``'s CPU implementation: same values.
+
+    ``jitter`` (a ``ColorJitterParams``, or a sequence of B; :func:`draw_color_jitter` draws one): torchvision's ``ColorJitter`` at the
+    end of the image chain, as in the reference's Cityscapes HyperSeg-S config -- the resize launch then writes the uint8 crop (padding
+    included: the contrast mean sees it, as it does on the padded PIL image) and ``functional.color_jitter`` produces the normalised
+    image of the whole batch, Pillow's bytes through ``norm``'s table (``utils.jitter.color_jitter_cpu`` for CPU tensors).  ``None``:
+    nothing changes."""
     import numpy as np
     from . import functional as HF
     from .utils import resample
@@ -397,13 +403,45 @@ def device_augment(frames_u8, labels, scale, crop, offset, hflip, norm, lbl_fill
     image = torch.empty(b, 3, ch, cw, dtype=torch.float32, device=frames_u8.device)
     label = torch.empty(b, ch, cw, dtype=torch.int64, device=frames_u8.device)
     frames_u8, labels = frames_u8.contiguous(), labels.contiguous()
+    dst, dst_norm = image, norm
+    if jitter is not None:                                   # the resize writes the uint8 crop, the jitter normalises
+        from .utils import jitter as J
+        jitter = J.per_sample(jitter, b)
+        dst_norm = None
+        dst = torch.empty((b, ch, cw, 3) if norm.layout == 'hwc' else (b, 3, ch, cw), dtype=torch.uint8, device=frames_u8.device)
     for i in range(b):
         size = tuple(int(s) for s in np.round(np.array((h, w)) * float(scales[i])).astype(int))
         view = resample.ResizeView((ch, cw), tuple(int(o) for o in offsets[i]), bool(flips[i]), fill)
         if frames_u8.is_cuda:
-            HF.frame_resize(frames_u8[i:i + 1], size, 'bicubic', norm.layout, view=view, norm=norm, out=image[i:i + 1])
+            HF.frame_resize(frames_u8[i:i + 1], size, 'bicubic', norm.layout, view=view, norm=dst_norm, out=dst[i:i + 1])
             HF.label_resize(labels[i:i + 1], size, view=view, fill=lbl_fill, out=label[i:i + 1])
         else:
-            image[i:i + 1] = resample.frame_resize_cpu(frames_u8[i:i + 1], size, 'bicubic', norm.layout, view=view, norm=norm)
+            dst[i:i + 1] = resample.frame_resize_cpu(frames_u8[i:i + 1], size, 'bicubic', norm.layout, view=view, norm=dst_norm)
             label[i:i + 1] = resample.label_resize_cpu(labels[i:i + 1], size, view=view, fill=lbl_fill, out_dtype=torch.int64)
+    if jitter is not None:
+        if dst.is_cuda:
+            HF.color_jitter(dst, jitter, norm.layout, norm=norm, out=image)
+        else:
+            image = J.color_jitter_cpu(dst, jitter, norm.layout, norm=norm)
     return image, label
+
+
+def draw_color_jitter(brightness=0.0, contrast=0.0, saturation=0.0, hue=0.0, generator=None):
+    """One ``ColorJitterParams`` drawn with the ranges of ``torchvision.transforms.ColorJitter(brightness, contrast, saturation, hue)``:
+    each of the three factors uniform in ``[max(0, 1 - x), 1 + x]``, hue uniform in ``[-x, x]`` (``x <= 0.5``), and a random order of the
+    four operations; an argument of 0 leaves its operation out, as torchvision's ``None`` range does.  ``generator``: a CPU
+    ``torch.Generator``.  A convenience for ``device_augment(jitter=...)``: it does NOT claim to consume random numbers as torchvision
+    does -- torchvision is not a dependency of this package and was not there to compare with, so a seed shared with a torchvision
+    pipeline gives other parameters."""
+    from .utils.jitter import OPS, ColorJitterParams
+    given = dict(zip(OPS, (float(brightness), float(contrast), float(saturation), float(hue))))
+    if any(not 0.0 <= v < float('inf') for v in given.values()) or given['hue'] > 0.5:
+        raise ValueError(f'ranges must be >= 0 and hue <= 0.5, got {given}')
+    order = [OPS[i] for i in torch.randperm(4, generator=generator).tolist()]
+    u = torch.rand(4, generator=generator, dtype=torch.float64).tolist()
+    factors = {}
+    for name, r in zip(OPS, u):
+        x = given[name]
+        lo, hi = (-x, x) if name == 'hue' else (max(0.0, 1.0 - x), 1.0 + x)
+        factors[name] = min(max(lo + (hi - lo) * r, lo), hi) if x > 0 else None
+    return ColorJitterParams(tuple(n for n in order if factors[n] is not None), **factors)

@@ -510,6 +510,22 @@ int hs_label_resize_fwd(const void* x, int32_t in_dtype, int32_t batch, int32_t 
                         const int32_t* y_index, int32_t Hr, const int32_t* x_index, int32_t Wr,
                         int32_t Ho, int32_t Wo, int32_t oy, int32_t ox, int32_t hflip, int32_t fill,
                         void* y, int32_t out_dtype, void* stream);
+/* torchvision's ColorJitter on uint8 RGB frames with Pillow's bytes (csrc/hs_jitter.hip; the arithmetic: hyperseg_amd/utils/jitter.py):
+ * up to four operations per sample, each on the uint8 result of the one before, in the order its record gives.
+ * table: int32 (B, HS_JITTER_TABLE_WORDS), on the device, one record per sample -- word 0 the order, 4 bits per operation from the lowest
+ *   (1 brightness, 2 contrast, 3 saturation, 4 hue; 0 ends it); words 1-3 the float32 bits of the brightness, contrast and saturation
+ *   factors; word 4 the hue shift, a byte added to H mod 256; word 5 the operations present, bit `code` each; words 6-7 unused.  The
+ *   kernels read it when they RUN: a captured graph replays with what the table holds then.  No record can make an access leave the
+ *   frame; an unknown code ends the order.
+ * x uint8 (B, H, W, 3) | (B, 3, H, W) by layout.  norm_table null: y uint8 in the input's layout; else y float32 (B, 3, H, W), every
+ *   byte looked up in the (3, 256) table of hs_image_ingest_fwd.  Any alignment of x and y (a float's 4 bytes for the float form).
+ * sums: B 64-bit words of workspace for the contrast mean (cleared, filled and read by the call: a clear, the mean pass over the
+ *   samples that name contrast, the apply pass).  Null -- the caller's promise that no record names contrast -- launches the apply
+ *   pass alone; a record that names contrast all the same blends against 0.
+ * HS_ERR_UNSUPPORTED -- nothing launched -- for batch > 65535 or H or W above 2^19.  Nothing is read back: capturable. */
+#define HS_JITTER_TABLE_WORDS 8
+int hs_color_jitter_fwd(const uint8_t* x, int32_t layout, int32_t batch, int32_t H, int32_t W, const int32_t* table,
+                        uint64_t* sums, const float* norm_table, void* y, void* stream);
 int hs_mbconv_expand_dw_fwd(const float* x, int32_t batch, int32_t c_in, int32_t H, int32_t W,
                             const float* w_expand, int32_t c_mid, const float* scale0, const float* shift0,
                             const float* w_dw, int32_t k, int32_t stride, int32_t pad_t, int32_t pad_l,
