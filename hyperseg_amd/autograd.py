@@ -20,7 +20,7 @@ def needs_grad(*tensors):
     return torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in tensors)
 
 
-DTYPE_CODES = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}       # hs_dtype of include/hyperseg_hip.h
+DTYPE_CODES = HF.DTYPE_CODES
 HALF_DTYPES = (torch.bfloat16, torch.float16)
 
 
@@ -719,6 +719,47 @@ class BootstrapMean(torch.autograd.Function):
         return gv, None, None
 
 
+def _bootstrapped_ce_forward(ctx, logits, target, ignore_index, k, thresh, confusion=None):
+    """The forward of ``BootstrappedCrossEntropy`` -- and, with ``confusion`` (int64 (n, n), accumulated into), of
+    ``BootstrappedCrossEntropyScored``: the same checks, buffers and saved tensors, the two differ in the launches alone."""
+    if logits.dim() != 4 or tuple(target.shape) != (logits.shape[0],) + tuple(logits.shape[2:]):
+        raise ValueError(f'Expected target of shape {(logits.shape[0],) + tuple(logits.shape[2:])} for logits of shape '
+                         f'{tuple(logits.shape)}, got {tuple(target.shape)}')
+    if target.dtype != torch.int64 or target.device != logits.device:
+        raise ValueError(f'BootstrappedCrossEntropy: expected int64 class indices on {logits.device}, got {target.dtype} on {target.device}')
+    refuse_mixed_halves(logits)
+    logits, target = logits.contiguous(), target.contiguous()
+    n, c = logits.shape[:2]
+    px = logits.numel() // (n * c)
+    if _CHECK_LABELS and target.numel():
+        bad = (target != int(ignore_index)) & ((target < 0) | (target >= c))
+        if bool(bad.any()):
+            raise IndexError(f'Target {int(target[bad][0])} is out of bounds for {c} classes (ignore_index {int(ignore_index)})')
+    with _hip.device_scope(logits.device):
+        ws = torch.empty(n * int(_hip.lib.hs_bootstrap_mean_workspace()), device=logits.device, dtype=torch.uint8)
+        loss = torch.empty(n, px, device=logits.device, dtype=torch.float32)
+        out = torch.empty(n * 8 + 1, device=logits.device, dtype=torch.float32)              # (N, 8) state | the mean
+        if confusion is None:
+            st = _hip.lib.hs_bootstrapped_ce_fwd(DTYPE_CODES[logits.dtype], logits.data_ptr(), target.data_ptr(), n, c, px, int(ignore_index),
+                                                 int(k), float(thresh), ws.data_ptr(), loss.data_ptr(), out.data_ptr(),
+                                                 out.data_ptr() + 4 * n * 8, _hip.stream_ptr())
+            _hip.check(st, 'hs_bootstrapped_ce_fwd')
+        else:                                                    # the same launches, the first one counting as well
+            nc = confusion.shape[-1]
+            if confusion.dtype != torch.int64 or tuple(confusion.shape) != (nc, nc) or confusion.device != logits.device \
+                    or not confusion.is_contiguous():
+                raise ValueError(f'the score matrix must be a contiguous int64 (n, n) tensor on {logits.device}')
+            st = _hip.lib.hs_cross_entropy_score_fwd(DTYPE_CODES[logits.dtype], logits.data_ptr(), target.data_ptr(), n, c, px, int(ignore_index),
+                                                     loss.data_ptr(), nc, 0, confusion.data_ptr(), None, _hip.stream_ptr())
+            _hip.check(st, 'hs_cross_entropy_score_fwd')
+            st = _hip.lib.hs_bootstrap_mean_of_batch_fwd(loss.data_ptr(), n, px, int(k), float(thresh), ws.data_ptr(), out.data_ptr(),
+                                                         out.data_ptr() + 4 * n * 8, _hip.stream_ptr())
+            _hip.check(st, 'hs_bootstrap_mean_of_batch_fwd')
+    ctx.save_for_backward(logits, target, loss, out)
+    ctx.ignore_index = int(ignore_index)
+    return out[n * 8:].view(())
+
+
 class BootstrappedCrossEntropy(torch.autograd.Function):
     """``BootstrappedCrossEntropyLoss.forward`` (hyperseg/losses/bootstrapped_ce_loss.py:15-27) as ONE Function (round 6): logits (N, C, H, W)
     fp32 / bf16, target (N, H, W) int64 -> the batch mean of the per-image bootstrapped losses, a 0-dim fp32 tensor.  The same values as
@@ -729,30 +770,7 @@ class BootstrappedCrossEntropy(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, logits, target, ignore_index, k, thresh):
-        if logits.dim() != 4 or tuple(target.shape) != (logits.shape[0],) + tuple(logits.shape[2:]):
-            raise ValueError(f'Expected target of shape {(logits.shape[0],) + tuple(logits.shape[2:])} for logits of shape '
-                             f'{tuple(logits.shape)}, got {tuple(target.shape)}')
-        if target.dtype != torch.int64 or target.device != logits.device:
-            raise ValueError(f'BootstrappedCrossEntropy: expected int64 class indices on {logits.device}, got {target.dtype} on {target.device}')
-        refuse_mixed_halves(logits)
-        logits, target = logits.contiguous(), target.contiguous()
-        n, c = logits.shape[:2]
-        px = logits.numel() // (n * c)
-        if _CHECK_LABELS and target.numel():
-            bad = (target != int(ignore_index)) & ((target < 0) | (target >= c))
-            if bool(bad.any()):
-                raise IndexError(f'Target {int(target[bad][0])} is out of bounds for {c} classes (ignore_index {int(ignore_index)})')
-        with _hip.device_scope(logits.device):
-            ws = torch.empty(n * int(_hip.lib.hs_bootstrap_mean_workspace()), device=logits.device, dtype=torch.uint8)
-            loss = torch.empty(n, px, device=logits.device, dtype=torch.float32)
-            out = torch.empty(n * 8 + 1, device=logits.device, dtype=torch.float32)              # (N, 8) state | the mean
-            st = _hip.lib.hs_bootstrapped_ce_fwd(DTYPE_CODES[logits.dtype], logits.data_ptr(), target.data_ptr(), n, c, px, int(ignore_index),
-                                                 int(k), float(thresh), ws.data_ptr(), loss.data_ptr(), out.data_ptr(),
-                                                 out.data_ptr() + 4 * n * 8, _hip.stream_ptr())
-            _hip.check(st, 'hs_bootstrapped_ce_fwd')
-        ctx.save_for_backward(logits, target, loss, out)
-        ctx.ignore_index = int(ignore_index)
-        return out[n * 8:].view(())
+        return _bootstrapped_ce_forward(ctx, logits, target, ignore_index, k, thresh)
 
     @staticmethod
     def backward(ctx, g):
@@ -767,6 +785,21 @@ class BootstrappedCrossEntropy(torch.autograd.Function):
                                                  loss.data_ptr(), state.data_ptr(), g.data_ptr(), dl.data_ptr(), _hip.stream_ptr())
             _hip.check(st, 'hs_bootstrapped_ce_bwd')
         return dl, None, None, None, None
+
+
+class BootstrappedCrossEntropyScored(torch.autograd.Function):
+    """``BootstrappedCrossEntropy`` whose loss launch also scores the batch (``BootstrappedCrossEntropyLoss.score``): the per-pixel losses
+    come from hs_cross_entropy_score_fwd, which adds the (target, argmax) counts of the batch to ``confusion`` (int64 (n, n), accumulated)
+    from the logits it already holds in registers; the same batch reduction follows (hs_bootstrap_mean_of_batch_fwd: the launches
+    hs_bootstrapped_ce_fwd makes after its first).  The same loss bits, and the same one-launch adjoint."""
+
+    @staticmethod
+    def forward(ctx, logits, target, ignore_index, k, thresh, confusion):
+        return _bootstrapped_ce_forward(ctx, logits, target, ignore_index, k, thresh, confusion)
+
+    @staticmethod
+    def backward(ctx, g):
+        return BootstrappedCrossEntropy.backward(ctx, g) + (None,)
 
 
 class MetaConvGeneral(torch.autograd.Function):

@@ -75,6 +75,7 @@ inline bool is_exact2x(int Hi, int Wi, int Ho, int Wo) { return Ho == 2 * Hi && 
 // load batches; this way it is four waves per SIMD with <= 5 classes (60 loads, one batch) per trip, combined with two shuffles:
 // the larger value wins, the lower class on ties -- the first maximum, as argmax(1).  On return all four lanes hold the block's
 // eight class indices (idx0: upper row, idx1: lower row).
+// (hs_validate.hip keeps a copy that also hands out the maxima, argmax2x_block_best: an edit here is made there too.)
 // Precondition: the call is wave-convergent (the shuffles read the quad's other lanes) -- a caller with surplus lanes lets them
 // shadow a real block and decides after the call who stores.
 __device__ __forceinline__ void argmax2x_block(const float* __restrict__ xb, int C, int Hi, int Wi, int yi, int q, int sub,
@@ -116,6 +117,7 @@ __device__ __forceinline__ void argmax2x_block(const float* __restrict__ xb, int
 
 // Class arg-max of the general form (any ratio, the identity included) over the four output pixels of `t`: strictly greater wins,
 // so the first maximum is kept.  The same one copy behind the three entry points' masks.
+// (hs_validate.hip keeps a copy that also hands out the maxima, argmax_row4_best: an edit here is made there too.)
 __device__ __forceinline__ void argmax_row4(const float* __restrict__ xb, int C, int Hi, int Wi, const Row4& t, int (&idx)[4]) {
     float best[4];
 #pragma unroll

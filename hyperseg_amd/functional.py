@@ -16,6 +16,7 @@ from . import _hip
 from ._hip import ACT_NONE, ACT_RELU, ACT_RELU6, PAD_MODES  # noqa: F401  (re-exported)
 
 BN_EPS_DEFAULT = 1e-5
+DTYPE_CODES = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}       # hs_dtype of include/hyperseg_hip.h
 S2W_TRAIN_MAX_LAYERS = 8     # S2W_MAX_LAYERS of csrc/hs_s2w_blocked.h: layers one hs_s2w_train_* / hs_signal2weights_multi_fwd launch takes
 # Round 4: the banks of the later levels produced INSIDE the k = 1 levels' launches (CoScheduledBanks / hs_patch_conv_s2w_fwd).
 # MEASURED AND OFF (visit r4e, profiles/round4_coscheduled_banks_ab.txt): the carrying launches grow by what the riders take -- level 2
@@ -1460,6 +1461,77 @@ def confusion_update(pred, target, num_classes, out=None, per_image=False):
                                    pred.numel() // b, n, 1 if per_image else 0, out.data_ptr(), _hip.stream_ptr())
     _hip.check(st, 'hs_confusion_fwd')
     return out
+
+
+def _score_out(num_classes, channels, out, batch, per_image, device):
+    """(n, matrix) of the two loss + score entries: ``num_classes=None`` counts nothing (loss and masks only)."""
+    if num_classes is None:
+        if out is not None:
+            raise ValueError('out= needs num_classes: nothing is counted without it')
+        if channels > 256:
+            raise ValueError('more than 256 logit channels: the masks are uint8')
+        return 0, None
+    n = _eval_classes(num_classes)            # NotImplementedError above eval_max_classes() (<= 256: the masks are uint8)
+    if channels > n:
+        raise ValueError(f'{channels} logit channels but num_classes = {num_classes}')
+    return n, _eval_out(out, (batch, n, n) if per_image else (n, n), device)
+
+
+@_on_operand_device
+def cross_entropy_score(logits, target, ignore_index, num_classes, out=None, per_image=False, masks=False):
+    """The per-pixel cross entropy of (B, C, H, W) logits (f32 / bf16 / f16) against int64 ``target`` (B, H, W) AND the batch's score, one
+    launch (hs_cross_entropy_score_fwd): returns ``(loss, out)`` -- ``(loss, out, masks)`` with ``masks=True``.  ``loss`` (B, H, W) f32 is
+    ``autograd.PixelCrossEntropy``'s bit for bit (0 where the target is ``ignore_index`` or outside [0, C)); the masks are
+    ``logits.argmax(1)`` as uint8; ``out[t, p] += 1`` for every pixel whose target is in [0, num_classes) -- ``confusion_update``'s rule,
+    which does not know ``ignore_index``: an in-range ignored pixel has loss 0 and is still counted, as in the reference's train.py.
+    ``out`` follows ``upsample_confusion``'s convention (accumulated into when given, a new zeroed matrix otherwise; (B, n, n) with
+    ``per_image``); ``num_classes=None`` counts nothing and returns ``out`` None.  Nothing here reads the device: capturable."""
+    if not isinstance(logits, torch.Tensor) or logits.dim() != 4 or logits.dtype not in DTYPE_CODES:
+        raise ValueError('logits must be (B, C, H, W) float32, bfloat16 or float16')
+    b, c, h, w = logits.shape
+    target = _eval_labels(target, 'target')
+    if target.dtype != torch.int64:
+        raise ValueError(f'target must be int64 (what the loss takes), got {target.dtype}')
+    if tuple(target.shape) != (b, h, w):
+        raise ValueError(f'target has shape {tuple(target.shape)}, expected {(b, h, w)}')
+    if target.device != logits.device:
+        raise ValueError(f'target is on {target.device}, the logits on {logits.device}')
+    n, out = _score_out(num_classes, c, out, b, per_image, logits.device)
+    xp = _hip.dev_ptr(logits, 'logits', logits.dtype)
+    loss = torch.empty(b, h, w, device=logits.device, dtype=torch.float32)
+    mask = torch.empty(b, h, w, device=logits.device, dtype=torch.uint8) if masks else None
+    st = _hip.lib.hs_cross_entropy_score_fwd(DTYPE_CODES[logits.dtype], xp, target.data_ptr(), b, c, h * w, int(ignore_index), loss.data_ptr(),
+                                             n, 1 if per_image else 0, None if out is None else out.data_ptr(),
+                                             mask.data_ptr() if masks else None, _hip.stream_ptr())
+    _hip.check(st, 'hs_cross_entropy_score_fwd')
+    return (loss, out, mask) if masks else (loss, out)
+
+
+@_on_operand_device
+def upsample_ce_confusion(x, size, target, ignore_index, num_classes, out=None, per_image=False):
+    """The validation step's last launch (hs_upsample_ce_confusion_fwd): ``x`` (B, C, Hi, Wi) f32 resized to ``size`` in registers, and from
+    each output pixel's scores its cross entropy against ``target`` (B, Ho, Wo; uint8 or int64), its class and its count.  Returns
+    ``(loss, out, masks)``: ``loss`` (B, Ho, Wo) f32 bit-identical to ``PixelCrossEntropy`` on ``upsample_bilinear(x, size)``, the uint8
+    masks to ``upsample_argmax``'s, the counts to ``upsample_confusion``'s (``out``, ``per_image`` and the errors raised: that
+    function's; ``num_classes=None``: nothing counted, ``out`` None).  The resized logits never exist in memory.  Capturable."""
+    if not isinstance(x, torch.Tensor) or x.dim() != 4:
+        raise ValueError('x must be (B, C, Hi, Wi) logits')
+    b, c, hi, wi = x.shape
+    ho, wo = _size2(size, 'size')
+    target = _eval_labels(target, 'target')
+    if tuple(target.shape) != (b, ho, wo):
+        raise ValueError(f'target has shape {tuple(target.shape)}, expected {(b, ho, wo)}')
+    if target.device != x.device:
+        raise ValueError(f'target is on {target.device}, the logits on {x.device}')
+    n, out = _score_out(num_classes, c, out, b, per_image, x.device)
+    xp = _hip.dev_ptr(x, 'x')
+    loss = torch.empty(b, ho, wo, device=x.device, dtype=torch.float32)
+    mask = torch.empty(b, ho, wo, device=x.device, dtype=torch.uint8)
+    st = _hip.lib.hs_upsample_ce_confusion_fwd(xp, b, c, hi, wi, ho, wo, target.data_ptr(), _EVAL_DTYPES[target.dtype], int(ignore_index),
+                                               loss.data_ptr(), n, 1 if per_image else 0, None if out is None else out.data_ptr(),
+                                               mask.data_ptr(), _hip.stream_ptr())
+    _hip.check(st, 'hs_upsample_ce_confusion_fwd')
+    return loss, out, mask
 
 
 def _overlay_out(out, frames):

@@ -78,11 +78,29 @@ def final_masks_overlaid(p, size, overlay):
     return HF.upsample_overlay(p, size, frames, style, out=out)
 
 
-def final_masks(p, size, score=None, overlay=None, out_size=None):
+def final_masks_validated(p, size, score, ignore_index):
+    """The ``masks=True`` epilogue of a validation step: ``score`` = (target, num_classes, out, per_image) as :func:`final_masks_scored`
+    takes it -- ``num_classes`` None: nothing counted -- with the target at ``size``.  Returns ``(masks, per_pixel)``: the launch
+    (``HF.upsample_ce_confusion``) also makes every pixel's cross entropy against the target, f32 (B, H, W), what
+    ``BootstrappedCrossEntropyLoss`` ranks; the logits at ``size`` never exist."""
+    target, num_classes, out, per_image = score
+    if tuple(target.shape[1:]) != tuple(size):
+        raise ValueError(f'loss= needs a target at the output size {tuple(size)}, got {tuple(target.shape[1:])}')
+    per_pixel, _, masks = HF.upsample_ce_confusion(p, size, target, ignore_index, num_classes, out=out, per_image=per_image)
+    return masks, per_pixel
+
+
+def final_masks(p, size, score=None, overlay=None, out_size=None, loss=None):
     """What ``masks=True`` returns for the last level's output ``p``: the uint8 argmax masks at ``size`` straight from the final upsample
     launch -- scored by that launch with ``score``, or blended by it with ``overlay`` (then ``(masks, overlay)``); one or the other.
     ``out_size`` (the unscored case): masks of the logits at ``size`` resized once more to ``out_size``, from the same one launch
-    (``HF.upsample2_argmax``); a scored forward takes that size from its target."""
+    (``HF.upsample2_argmax``); a scored forward takes that size from its target.  ``loss`` (with ``score``): the criterion's
+    ``ignore_index`` -- the launch also makes the per-pixel cross entropy against the score's target, and ``(masks, per_pixel)`` is
+    returned (:func:`final_masks_validated`)."""
+    if loss is not None:
+        if score is None or overlay is not None or (out_size is not None and tuple(out_size) != tuple(size)):
+            raise ValueError('loss= rides on a scored masks=True epilogue at the frame\'s size: score= with it, no overlay=, no out_size=')
+        return final_masks_validated(p, size, score, loss)
     if score is not None and overlay is not None:
         raise ValueError('score= and overlay= both ride on the final upsample launch: one of them per forward for now')
     if overlay is not None:
@@ -96,14 +114,14 @@ def final_masks(p, size, score=None, overlay=None, out_size=None):
     return HF.upsample2_argmax(p, size, out_size)
 
 
-def finish_decoder(decoder, p, size, masks, score, overlay=None, out_size=None):
+def finish_decoder(decoder, p, size, masks, score, overlay=None, out_size=None, loss=None):
     """What the v1_0 and unify decoders return for their last level's output ``p``: with ``masks``, the uint8 argmax masks at ``size``
     straight from the final upsample launch (scored by the same launch when ``score`` is given, blended over the frames by it when
     ``overlay`` is: :func:`final_masks`); otherwise the logits, resized to ``size`` -- into ``decoder.output_buffer`` where a serving
     wrapper has set one."""
     if masks:
-        return final_masks(p, size, score, overlay, out_size)
-    assert overlay is None, 'overlay= rides on the masks=True epilogue'
+        return final_masks(p, size, score, overlay, out_size, loss)
+    assert overlay is None and loss is None, 'overlay= and loss= ride on the masks=True epilogue'
     if p.shape[2:] != size:
         p = HF.upsample_bilinear(p, size, out=getattr(decoder, 'output_buffer', None))
     return p
@@ -170,7 +188,7 @@ class HyperGenBase(EpochOnModeSwitch, nn.Module):
     def hyper_params(self):
         return self.decoder.hyper_params
 
-    def process_single_tensor(self, x, hflip=False, masks=False, score=None, overlay=None, out_size=None):
+    def process_single_tensor(self, x, hflip=False, masks=False, score=None, overlay=None, out_size=None, loss=None):
         frame = None
         if x.dtype == torch.uint8:
             norm = self._require_norm()
@@ -193,6 +211,9 @@ class HyperGenBase(EpochOnModeSwitch, nn.Module):
         assert overlay is None or (masks and not hflip), 'the overlay rides on the masks=True epilogue of an unflipped frame'
         # with overlay=: (masks, overlay), unflipped.  score= and overlay= together: final_masks raises
         assert out_size is None or (masks and not hflip), 'another output size rides on the masks=True epilogue of an unflipped frame'
+        assert loss is None or score is not None, 'the loss rides on a scored masks=True epilogue'
+        if loss is not None:                  # a validation step: (masks, per-pixel losses) from the decoder's last launch
+            return self.decoder(pyramid, head_out, masks=True, score=score, loss=loss)
         if out_size is not None:              # masks at another size than the frame's: both resizes in the decoder's last launch
             y = self.decoder(pyramid, head_out, masks=True, score=score, overlay=overlay, out_size=tuple(out_size))
         else:
@@ -261,6 +282,70 @@ class HyperGenBase(EpochOnModeSwitch, nn.Module):
         else:
             confmat.update(target.flatten(), masks.flatten())
         return masks
+
+    def _validate_fused(self, x, target, criterion, n, staged=False):
+        """validate()'s fused route applies: see there.  ``staged``: a serving wrapper copies ``x`` and ``target`` to the model's device
+        first (``GraphedModel.validate``), so where they live now does not matter."""
+        from ..training import BootstrappedCrossEntropyLoss, USE_HIP_BOOTSTRAP, USE_FUSED_LOSS
+        if not (isinstance(x, torch.Tensor) and x.dim() == 4 and not self.training and isinstance(target, torch.Tensor)
+                and target.dtype in (torch.uint8, torch.int64) and target.dim() == 3 and (staged or (x.is_cuda and target.is_cuda))):
+            return False
+        if not (isinstance(criterion, BootstrappedCrossEntropyLoss) and criterion.weight is None and criterion.score is None
+                and USE_HIP_BOOTSTRAP and USE_FUSED_LOSS):
+            return False
+        if tuple(target.shape) != (x.shape[0],) + self.frame_size(x) or x.shape[0] > 65535:
+            return False
+        pixels = target.shape[1] * target.shape[2]
+        return criterion.k < pixels < 2 ** 31 and (n is None or n <= min(256, HF.eval_max_classes()))
+
+    @torch.no_grad()
+    def validate(self, x, target, criterion, confmat=None, per_image=False):
+        """One validation batch of the reference's epoch loop (train.py:118-126 in ``eval()`` mode under ``no_grad``): returns ``(loss,
+        masks)`` -- ``criterion(self(x), target)`` as a 0-dim f32 tensor (no host read) and the uint8 masks ``self(x).argmax(1)`` -- and
+        adds the batch's (target, prediction) counts to ``confmat`` (a ``hyperseg_amd.fps.ConfusionMatrix``; None: loss and masks only;
+        ``per_image`` as ``evaluate``'s).  ``training.running_scores(confmat.mat)`` gives the numbers train.py picks ``model_best`` by.
+
+        A single CUDA tensor in eval mode, a ``BootstrappedCrossEntropyLoss`` without class weights (and without a ``score`` of its own),
+        a uint8 / int64 target at the frame's size with more than ``criterion.k`` pixels and at most ``HF.eval_max_classes()`` classes:
+        the forward's last launch (``HF.upsample_ce_confusion``) makes the per-pixel losses, the masks and the counts -- the
+        full-resolution logits are never written -- and the criterion's own batch reduction follows (the launches its fused forward
+        makes after its first).  Everything else -- list inputs, training mode, CPU, a target of another size, class weights, another
+        criterion -- computes ``pred = self(x)``, resizes it to the target as ``evaluate`` does, and takes ``criterion(pred,
+        target.long())``, ``argmax`` and ``confmat``'s own update.  On the device every route gives the same loss bits, masks and
+        counts from the same decoder input.  (An unprepared model's stock torch encoder does not repeat its own bits from one call to
+        the next, so two separate passes of it need not agree to the bit, whichever routes they take: DESIGN 3.11.)  The
+        CPU's composed route is stock torch ops: same masks and counts, the loss to rounding."""
+        n = None if confmat is None else confmat.num_classes
+        x = self.resized(x)
+        batch = (x if isinstance(x, torch.Tensor) else x[0]).shape[0]
+        if not isinstance(target, torch.Tensor) or target.is_floating_point() or target.dim() != 3 or target.shape[0] != batch:
+            raise ValueError(f'target must be ({batch}, H, W) class indices (uint8 or int64), got {getattr(target, "dtype", type(target))} '
+                             f'{tuple(getattr(target, "shape", ()))}')
+        if self._validate_fused(x, target, criterion, n):
+            from ..autograd import BootstrapMeanOfBatch
+            out = None
+            if confmat is not None:
+                out = torch.zeros((x.shape[0], n, n), dtype=torch.int64, device=x.device) if per_image else confmat.matrix(x.device)
+            got = self.process_single_tensor(x, masks=True, score=(target, n, out, per_image), loss=criterion.ignore_index)
+            if not isinstance(got, tuple):
+                raise RuntimeError('the decoder returned logits from its masks=True route: nothing was scored')
+            masks, per_pixel = got
+            if confmat is not None and per_image:
+                confmat.add_per_image(out)
+            return BootstrapMeanOfBatch.apply(per_pixel.flatten(1), criterion.k, criterion.thresh), masks
+        pred = self(x)
+        if tuple(pred.shape[2:]) != tuple(target.shape[1:]):
+            pred = HF.upsample_bilinear(pred.contiguous(), tuple(target.shape[1:])) if pred.is_cuda else \
+                torch.nn.functional.interpolate(pred, size=target.shape[1:], mode='bilinear')
+        target = target.to(pred.device)
+        loss = criterion(pred, target.long())
+        masks = pred.argmax(1).to(torch.uint8)
+        if confmat is not None:
+            if per_image:
+                confmat.update_per_image(target, masks)
+            else:
+                confmat.update(target.flatten(), masks.flatten())
+        return loss.detach(), masks
 
     @torch.no_grad()
     def overlay(self, x, frames=None, style=None, out=None):

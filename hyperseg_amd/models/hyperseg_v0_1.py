@@ -146,7 +146,7 @@ class MultiScaleDecoder(EpochOnModeSwitch, nn.Module):
         self.hyper_params = int(self._ranges[-1])
         self._ranges.append(self.hyper_params)
 
-    def forward(self, x, w, masks=False, score=None, overlay=None, out_size=None):
+    def forward(self, x, w, masks=False, score=None, overlay=None, out_size=None, loss=None):
         assert isinstance(w, (list, tuple))
         assert len(x) <= self.levels
         p = None
@@ -157,7 +157,7 @@ class MultiScaleDecoder(EpochOnModeSwitch, nn.Module):
             p = self.out_fc(p, w[-1])
         if masks and not (self.training or p.requires_grad):
             # identity resize: argmax over classes only -- a label / out_size of another size: the one resize to it, then the argmax
-            return final_masks(p.contiguous(), p.shape[2:], score, overlay, out_size)
+            return final_masks(p.contiguous(), p.shape[2:], score, overlay, out_size, loss)
         return p
 
 

@@ -758,7 +758,7 @@ class MultiScaleDecoder(EpochOnModeSwitch, nn.Module):
             p = self.out_fc(p, banks[-1])
         return p
 
-    def forward(self, x, s, masks=False, score=None, overlay=None, out_size=None):
+    def forward(self, x, s, masks=False, score=None, overlay=None, out_size=None, loss=None):
         """``masks=True`` (inference only, not in the reference): uint8 argmax masks straight from the final upsample
         kernel instead of logits."""
         if self.training or HA.needs_grad(s, *x, *self.parameters()):
@@ -777,7 +777,7 @@ class MultiScaleDecoder(EpochOnModeSwitch, nn.Module):
         done = self._run_k1_chain(x, banks) if plan.chain else None
         p, first = done if done is not None else (None, 0)
         p = self._run_levels(x, s, banks, plan, first, p)
-        return finish_decoder(self, p, x[0].shape[2:], masks, score, overlay, out_size)
+        return finish_decoder(self, p, x[0].shape[2:], masks, score, overlay, out_size, loss)
 
 
 class WeightMapper(nn.Module):

@@ -50,14 +50,22 @@ def bootstrap_mean_capturable(per_pixel, k, thresh):
     return torch.where(top[k] > thresh, mean_over, top[:k].mean())
 
 
-def bootstrapped_cross_entropy(pred, target, k=4096, thresh=0.3, weight=None, ignore_index=-100):
-    """pred (N, C, H, W) logits, target (N, H, W) int64 -> scalar."""
+def bootstrapped_cross_entropy(pred, target, k=4096, thresh=0.3, weight=None, ignore_index=-100, score=None):
+    """pred (N, C, H, W) logits, target (N, H, W) int64 -> scalar.  ``score``: ``BootstrappedCrossEntropyLoss.score``."""
     capturing = pred.is_cuda and torch.cuda.is_current_stream_capturing()
     # the per-pixel losses of the WHOLE batch in one pass over (N, C, H, W) (the reference permutes every image to (HW, C) first,
     # bootstrapped_ce_loss.py:20-23: same values, a transposed copy + a softmax + a gather per image and direction)
     hip_ce = (USE_HIP_BOOTSTRAP and weight is None and pred.is_cuda and pred.dtype in (torch.float32, torch.bfloat16, torch.float16) and pred.dim() == 4
               and target.dtype == torch.int64 and target.device == pred.device)
-    if hip_ce and USE_FUSED_LOSS and pred.shape[2] * pred.shape[3] > k and pred.shape[0] <= 65535 and pred.shape[2] * pred.shape[3] < 2 ** 31:
+    fused = hip_ce and USE_FUSED_LOSS and pred.shape[2] * pred.shape[3] > k and pred.shape[0] <= 65535 and pred.shape[2] * pred.shape[3] < 2 ** 31
+    if score is not None:
+        if pred.dim() < 2 or pred.shape[1] > score.num_classes:
+            raise ValueError(f'{pred.shape[1] if pred.dim() > 1 else 0} logit channels but the score counts {score.num_classes} classes')
+        if fused and _score_in_loss_launch(score.num_classes):
+            from .autograd import BootstrappedCrossEntropyScored           # the loss launch counts the batch: no further launch
+            return BootstrappedCrossEntropyScored.apply(pred, target, ignore_index, k, thresh, score.matrix(pred.device))
+        score.update(target.flatten(), pred.detach().argmax(1).flatten())  # every other route: the loss as it was, scored by the matrix itself
+    if fused:
         from .autograd import BootstrappedCrossEntropy                     # the whole loss as one Function: its adjoint is one launch (round 6)
         return BootstrappedCrossEntropy.apply(pred, target, ignore_index, k, thresh)
     if hip_ce:
@@ -81,7 +89,23 @@ def bootstrapped_cross_entropy(pred, target, k=4096, thresh=0.3, weight=None, ig
     return total / float(pred.shape[0])
 
 
+def _score_in_loss_launch(num_classes):
+    from . import functional as HF
+    return num_classes <= min(256, HF.eval_max_classes())
+
+
 class BootstrappedCrossEntropyLoss(nn.Module):
+    """``score``: a plain attribute, default None -- set it to a ``hyperseg_amd.fps.ConfusionMatrix`` and every ``forward`` also adds the
+    batch's (target, ``input.argmax(1)``) counts to it: the running score the reference's epoch loop keeps next to the loss
+    (train.py:124-126, ``running_metrics.update``).  On the fused-loss route (CUDA logits, no class weights, more than ``k`` pixels, at
+    most ``functional.eval_max_classes()`` classes) the loss launch itself counts, from the logits it holds in registers, into
+    ``score.matrix(device)``: the same loss bits, the same gradients, no further launch and nothing read back, so a captured step
+    (``GraphedTrainStep``) counts with every replay.  Every other route computes the loss as without it and calls ``score.update``.
+    Counting follows the reference's ``runningScore``, which does not know ``ignore_index``: every target in [0, n) is counted, also one
+    that equals an in-range ``ignore_index`` (its loss is 0).  :func:`running_scores` turns the matrix into train.py's numbers."""
+
+    score = None
+
     def __init__(self, k=4096, thresh=0.3, weight=None, ignore_index=-100, reduction='mean'):
         super().__init__()
         if reduction != 'mean':
@@ -90,7 +114,31 @@ class BootstrappedCrossEntropyLoss(nn.Module):
         self.register_buffer('weight', weight)
 
     def forward(self, input, target):
-        return bootstrapped_cross_entropy(input, target, self.k, self.thresh, self.weight, self.ignore_index)
+        return bootstrapped_cross_entropy(input, target, self.k, self.thresh, self.weight, self.ignore_index, self.score)
+
+
+@torch.no_grad()
+def running_scores(mat):
+    """``runningScore.get_scores()`` (hyperseg/train.py:310-335) from an (n, n) count matrix of (target, prediction) pairs -- a
+    ``ConfusionMatrix.mat``, a ``GraphedModel.confusion``: ``(scores, class_iou)`` with ``scores`` = {'overall_acc', 'mean_acc',
+    'freqw_acc', 'mean_iou'} as floats and ``class_iou`` a dict class -> IoU.  float64 on the host (one read of the matrix), numpy's
+    semantics: a class without pixels has a nan accuracy / IoU and is left out of the two means (``nanmean``; nan if every class is).
+    Not ``ConfusionMatrix.compute()``, which carries test.py's 1e-6 guards: this is the number train.py picks ``model_best`` by."""
+    hist = torch.as_tensor(mat).detach().to('cpu', torch.float64)
+    if hist.dim() != 2 or hist.shape[0] != hist.shape[1]:
+        raise ValueError(f'expected an (n, n) count matrix, got {tuple(hist.shape)}')
+    diag, rows, cols = torch.diag(hist), hist.sum(1), hist.sum(0)
+    total = hist.sum()
+    acc_cls = diag / rows
+    iu = diag / (rows + cols - diag)
+    freq = rows / total
+
+    def nanmean(v):
+        keep = ~torch.isnan(v)
+        return float(v[keep].mean()) if bool(keep.any()) else float('nan')
+    scores = {'overall_acc': float(diag.sum() / total), 'mean_acc': nanmean(acc_cls),
+              'freqw_acc': float((freq[freq > 0] * iu[freq > 0]).sum()), 'mean_iou': nanmean(iu)}
+    return scores, {c: float(v) for c, v in enumerate(iu)}
 
 
 class PolyLR(LRScheduler):
@@ -298,7 +346,13 @@ class GraphedTrainStep:
     ``scaler``: a ``torch.amp.GradScaler`` -- the captured step is then the whole mixed-precision step, ``scaler.scale(loss).backward()``,
     the inf check, ``scaler.step(optimizer)`` and ``scaler.update()``, with the scale and growth tracker updated on the device by every
     replay.  It needs an optimizer that takes the scaler's protocol without a host read (``hyperseg_amd.training.Adam``, or torch's
-    ``fused=True`` Adam); the model runs under whatever autocast the caller wraps ``model`` in."""
+    ``fused=True`` Adam); the model runs under whatever autocast the caller wraps ``model`` in.
+
+    ``criterion.score`` (``BootstrappedCrossEntropyLoss.score``, a ``ConfusionMatrix``): the loss launch of every replay adds the batch's
+    counts to ``score.mat``.  The matrix exists before the capture (the warm-up creates it) and is never replaced: the graph holds its
+    address.  The warm-up's steps are counted -- they are real optimiser steps on real data -- so after construction the matrix holds
+    ``warmup`` batches (the capture pass records, it does not execute).  ``ConfusionMatrix.reset()`` zeroes the matrix in place, so a
+    reset between epochs is safe; assigning a new tensor to ``score.mat`` is not."""
 
     def __init__(self, model, criterion, optimizer, inputs, target, warmup=3, scaler=None):
         self.model, self.criterion, self.optimizer = model, criterion, optimizer
@@ -316,6 +370,9 @@ class GraphedTrainStep:
             # the optimizer creates its state (moments, step count) on first use: inside a capture those zero fills become graph nodes
             # and EVERY replay would reset the moments
             raise ValueError('GraphedTrainStep: warmup >= 1 is required while the optimizer has no state yet')
+        score = getattr(criterion, 'score', None)
+        if score is not None:
+            score.matrix(dev)                               # created here at the latest: a zero fill inside the capture would be replayed
         side = torch.cuda.Stream(device=dev)
         side.wait_stream(torch.cuda.current_stream(dev))
         with torch.cuda.stream(side):                       # first calls allocate, tune and set kernel attributes: not capturable

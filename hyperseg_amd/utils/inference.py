@@ -851,9 +851,10 @@ class GraphedModel(nn.Module):
     gradient, CPU models.  Parameters are read through their storage, so in-place updates are seen; ``load_state_dict``
     on the wrapped model (which rebuilds the fused routes' folded buffers) and ``reset()`` drop the captured graphs."""
 
-    def __init__(self, model, masks=False, warmup=3, clone_output=False, max_graphs=8, num_classes=None, per_image=False):
+    def __init__(self, model, masks=False, warmup=3, clone_output=False, max_graphs=8, num_classes=None, per_image=False, criterion=None):
         super().__init__()
         self.model = model
+        self.__dict__['criterion'] = criterion  # validate()'s loss; kept out of the module tree: its buffers are not this wrapper's state
         self.masks, self.warmup, self.clone_output, self.max_graphs = bool(masks), int(warmup), bool(clone_output), int(max_graphs)
         self._graphs = {}                      # (shape, dtype, device, input norm of uint8 frames) -> (graph, static inputs, static_out, chained-launch owners)
         self._replays = 0
@@ -1020,6 +1021,58 @@ class GraphedModel(nn.Module):
 
             def run(xs, ts, out=confusion):
                 return self.model.process_single_tensor(self.model.resized(xs), masks=True, score=(ts, n, out, self.per_image))
+
+            entry = self._capture(key, [x, target], device, run=run, warm=lambda xs, ts: run(xs, ts, scratch))
+        return self._replay(entry, [x, target], device)
+
+    @torch.no_grad()
+    def validate(self, x, target):
+        """One replay per validation batch (train.py:118-126 under ``eval()`` / ``no_grad``): returns ``(loss, masks)`` as
+        ``model.validate(x, target, criterion)`` does -- ``criterion``: the ``BootstrappedCrossEntropyLoss`` given at construction -- and,
+        with ``num_classes`` given there, adds the batch's counts to ``self.confusion`` (``reset_confusion()`` zeroes it between
+        epochs; ``training.running_scores(self.confusion)`` gives train.py's numbers).  Built as ``evaluate`` is: ``x`` and ``target`` are
+        staged into static buffers, the graph is the forward's chain with ``functional.upsample_ce_confusion`` as its last launch
+        followed by the criterion's batch reduction, keyed by the shapes and dtypes of both (and apart from the ``forward`` /
+        ``evaluate`` graphs); the warm-up passes count into a scratch matrix.  ``loss`` is the graph's static 0-dim tensor: valid until
+        the next call of the same shape.  The values are ``model.validate``'s (its note on an unprepared model's
+        stock encoder applies).  What the graph cannot serve takes ``model.validate``'s routes, counting into the same
+        matrix."""
+        from ..fps import ConfusionMatrix
+        criterion = self.criterion
+        if criterion is None:
+            raise ValueError('GraphedModel.validate needs the loss: GraphedModel(model, criterion=BootstrappedCrossEntropyLoss(...))')
+        model = self.model
+        p = next(model.parameters(), None)
+        n = self.num_classes
+        graphable = (self._graphable(x) and isinstance(target, torch.Tensor) and target.numel() > 0 and hasattr(model, '_validate_fused')
+                     and model._validate_fused(x, target, criterion, n, staged=True))
+        device = p.device if graphable else None
+        if not graphable:
+            if p is not None and p.is_cuda:
+                x = [t.to(p.device, non_blocking=True) for t in x] if isinstance(x, (list, tuple)) else x.to(p.device, non_blocking=True)
+                target = target.to(p.device, non_blocking=True)
+            if n is None:
+                return model.validate(x, target, criterion)
+            cm = ConfusionMatrix(n)
+            if self.per_image:
+                got = model.validate(x, target, criterion, cm, per_image=True)
+                self._confusion_on(target.device, target.shape[0]).add_(cm.per_image[-1])
+            else:
+                cm.mat = self._confusion_on(target.device, target.shape[0])
+                got = model.validate(x, target, criterion, cm)
+            return got
+        confusion = None if n is None else self._confusion_on(device, x.shape[0])
+        key = ('validate', tuple(x.shape), x.dtype, target.dtype, device, self._norm_of(x), tuple(target.shape), criterion.k, criterion.thresh,
+               criterion.ignore_index)
+        entry = self._graphs.get(key)
+        if entry is None:
+            from ..autograd import BootstrapMeanOfBatch
+            scratch = None if confusion is None else torch.zeros_like(confusion)     # the warm-up passes execute: their counts go here
+
+            def run(xs, ts, out=confusion):
+                masks, per_pixel = model.process_single_tensor(model.resized(xs), masks=True, score=(ts, n, out, self.per_image),
+                                                               loss=criterion.ignore_index)
+                return BootstrapMeanOfBatch.apply(per_pixel.flatten(1), criterion.k, criterion.thresh), masks
 
             entry = self._capture(key, [x, target], device, run=run, warm=lambda xs, ts: run(xs, ts, scratch))
         return self._replay(entry, [x, target], device)

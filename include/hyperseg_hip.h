@@ -344,6 +344,28 @@ int hs_upsample2_confusion_fwd(const float* x, int32_t batch, int32_t channels, 
                                int32_t Ho, int32_t Wo, const void* target, int32_t target_dtype, int32_t num_classes, int32_t per_image,
                                int64_t* confusion, uint8_t* mask, void* stream);
 
+/* The validation step's middle (csrc/hs_validate.hip; hyperseg/train.py:118-126: the loss of a batch and its running score): the
+ * per-pixel cross entropy, the class arg-max and the (target, prediction) count from ONE pass over each pixel's class scores.
+ *   loss (batch, pixels) f32: hs_cross_entropy_typed_fwd's values bit for bit (0 where the target is ignore_index or outside
+ *     [0, channels)) -- what hs_bootstrap_mean_of_batch_fwd reduces to BootstrappedCrossEntropyLoss' value;
+ *   mask (optional) uint8: argmax(1) of the scores widened to f32, the first maximum;
+ *   confusion int64 (n, n) / (batch, n, n) with per_image: ACCUMULATED into, never zeroed, hs_confusion_fwd's rule -- every target in
+ *     [0, num_classes) is counted, an in-range ignore_index included (the reference's runningScore does not know it), everything else
+ *     ignored.  NULL: nothing is counted and num_classes / per_image are not read.
+ * channels <= num_classes <= 256 else HS_ERR_BAD_ARG; num_classes > hs_eval_max_classes(): HS_ERR_UNSUPPORTED, nothing launched.
+ *   hs_cross_entropy_score_fwd: from logits in memory (dtype: f32 / bf16 / f16 storage, (batch, classes, pixels)), int64 targets.
+ *   hs_upsample_ce_confusion_fwd: from x f32 (batch, channels, Hi, Wi) resized to (Ho, Wo) in registers, targets HS_EVAL_U8 or
+ *     HS_EVAL_I64 at (batch, Ho, Wo): loss, mask and counts bit-identical to hs_upsample_bilinear_fwd + hs_cross_entropy_typed_fwd and
+ *     hs_upsample_argmax_fwd + hs_confusion_fwd; the resized logits never exist in memory.  Both forms of the final upsample (exact 2x;
+ *     any other ratio, the identity and down-sampling included).
+ * Nothing is read back: capturable. */
+int hs_cross_entropy_score_fwd(int32_t dtype, const void* logits, const int64_t* target, int32_t batch, int32_t classes, int64_t pixels,
+                               int64_t ignore_index, float* loss, int32_t num_classes, int32_t per_image, int64_t* confusion,
+                               uint8_t* mask, void* stream);
+int hs_upsample_ce_confusion_fwd(const float* x, int32_t batch, int32_t channels, int32_t Hi, int32_t Wi, int32_t Ho, int32_t Wo,
+                                 const void* target, int32_t target_dtype, int64_t ignore_index, float* loss, int32_t num_classes,
+                                 int32_t per_image, int64_t* confusion, uint8_t* mask, void* stream);
+
 /* Backward of hs_patch_conv_fwd (plain input x, no fused prologue / epilogue), fp32 -- SURVEY.md Appendix E.
  * The reference has no backward of its own (autograd over F.pad/unfold/grouped conv2d/fold: meta_patch.py:35-57);
  * these are the adjoints the training path (BASELINE config 5) needs:
