@@ -1351,6 +1351,43 @@ def _eval_classes(num_classes):
     return n
 
 
+def _logits_shape(x):
+    if not isinstance(x, torch.Tensor) or x.dim() != 4:
+        raise ValueError('x must be (B, C, Hi, Wi) logits')
+    return x.shape
+
+
+def _eval_target(target, shape, x):
+    """``target`` as the kernels read it: uint8 or int64, of ``shape`` = (B, Ho, Wo), on the logits' device."""
+    target = _eval_labels(target, 'target')
+    if tuple(target.shape) != shape:
+        raise ValueError(f'target has shape {tuple(target.shape)}, expected {shape}')
+    if target.device != x.device:
+        raise ValueError(f'target is on {target.device}, the logits on {x.device}')
+    return target
+
+
+def _score_out(num_classes, channels, out, batch, per_image, device, counted=False):
+    """(n, matrix) of the scoring entries.  The two loss + score entries: ``num_classes=None`` counts nothing (loss and masks only).
+    ``counted`` (the two upsample + count entries): there is always a count, and what the uint8 masks rule out -- more channels than
+    classes, more than 256 classes -- is a ValueError before the kernels' own limit is a NotImplementedError."""
+    if counted:
+        if channels > int(num_classes):
+            raise ValueError(f'{channels} logit channels but num_classes = {num_classes}')
+        if int(num_classes) > 256:
+            raise ValueError('num_classes > 256: the masks are uint8')
+    elif num_classes is None:
+        if out is not None:
+            raise ValueError('out= needs num_classes: nothing is counted without it')
+        if channels > 256:
+            raise ValueError('more than 256 logit channels: the masks are uint8')
+        return 0, None
+    n = _eval_classes(num_classes)            # NotImplementedError above eval_max_classes() (<= 256: the masks are uint8)
+    if channels > n:
+        raise ValueError(f'{channels} logit channels but num_classes = {num_classes}')
+    return n, _eval_out(out, (batch, n, n) if per_image else (n, n), device)
+
+
 @_on_operand_device
 def upsample_confusion(x, size, target, num_classes, out=None, per_image=False, masks=False):
     """``upsample_argmax(x, size)`` with every output pixel counted against ``target`` (B, Ho, Wo; uint8 or int64) in the same
@@ -1358,24 +1395,12 @@ def upsample_confusion(x, size, target, num_classes, out=None, per_image=False, 
     other target value ignored (seg_utils.py:15-17).  ``out``: an int64 (n, n) -- ``per_image``: (B, n, n) -- matrix to
     ACCUMULATE into; None allocates a zeroed one.  Returns ``out``, or ``(out, masks)`` with ``masks=True`` (the uint8 masks,
     bit-identical to ``upsample_argmax``'s).  Nothing here reads the device: the call is capturable in a HIP graph."""
-    if not isinstance(x, torch.Tensor) or x.dim() != 4:
-        raise ValueError('x must be (B, C, Hi, Wi) logits')
-    b, c, hi, wi = x.shape
+    b, c, hi, wi = _logits_shape(x)
     ho, wo = (int(s) for s in size)
-    target = _eval_labels(target, 'target')
-    if tuple(target.shape) != (b, ho, wo):
-        raise ValueError(f'target has shape {tuple(target.shape)}, expected {(b, ho, wo)}')
-    if target.device != x.device:
-        raise ValueError(f'target is on {target.device}, the logits on {x.device}')
-    if c > int(num_classes):
-        raise ValueError(f'{c} logit channels but num_classes = {num_classes}')
-    if int(num_classes) > 256:
-        raise ValueError('num_classes > 256: the masks are uint8')
-    n = _eval_classes(num_classes)
-    xp = _hip.dev_ptr(x, 'x')
-    out = _eval_out(out, (b, n, n) if per_image else (n, n), x.device)
+    target = _eval_target(target, (b, ho, wo), x)
+    n, out = _score_out(num_classes, c, out, b, per_image, x.device, counted=True)
     mask = torch.empty(b, ho, wo, device=x.device, dtype=torch.uint8) if masks else None
-    st = _hip.lib.hs_upsample_confusion_fwd(xp, b, c, hi, wi, ho, wo, target.data_ptr(), _EVAL_DTYPES[target.dtype], n,
+    st = _hip.lib.hs_upsample_confusion_fwd(_hip.dev_ptr(x, 'x'), b, c, hi, wi, ho, wo, target.data_ptr(), _EVAL_DTYPES[target.dtype], n,
                                             1 if per_image else 0, out.data_ptr(), mask.data_ptr() if masks else None,
                                             _hip.stream_ptr())
     _hip.check(st, 'hs_upsample_confusion_fwd')
@@ -1397,9 +1422,7 @@ def upsample2_confusion(x, mid_size, target, num_classes, out=None, per_image=Fa
     counts are bit-identical to ``upsample_bilinear(upsample_bilinear(x, mid_size), target.shape[1:]).argmax(1)`` and its count.
     ``out``, ``per_image``, ``masks``, the returned value and the errors raised are ``upsample_confusion``'s, which this simply
     calls when the target is at ``mid_size`` already (or ``x`` is).  Nothing here reads the device: the call is capturable."""
-    if not isinstance(x, torch.Tensor) or x.dim() != 4:
-        raise ValueError('x must be (B, C, Hi, Wi) logits')
-    b, c, hi, wi = x.shape
+    b, c, hi, wi = _logits_shape(x)
     hm, wm = _size2(mid_size, 'mid_size')
     target = _eval_labels(target, 'target')
     if target.dim() != 3 or target.shape[0] != b:
@@ -1407,17 +1430,10 @@ def upsample2_confusion(x, mid_size, target, num_classes, out=None, per_image=Fa
     ho, wo = int(target.shape[1]), int(target.shape[2])
     if (ho, wo) == (hm, wm) or (hi, wi) == (hm, wm):
         return upsample_confusion(x, (ho, wo), target, num_classes, out=out, per_image=per_image, masks=masks)
-    if target.device != x.device:
-        raise ValueError(f'target is on {target.device}, the logits on {x.device}')
-    if c > int(num_classes):
-        raise ValueError(f'{c} logit channels but num_classes = {num_classes}')
-    if int(num_classes) > 256:
-        raise ValueError('num_classes > 256: the masks are uint8')
-    n = _eval_classes(num_classes)
-    xp = _hip.dev_ptr(x, 'x')
-    out = _eval_out(out, (b, n, n) if per_image else (n, n), x.device)
+    target = _eval_target(target, (b, ho, wo), x)
+    n, out = _score_out(num_classes, c, out, b, per_image, x.device, counted=True)
     mask = torch.empty(b, ho, wo, device=x.device, dtype=torch.uint8) if masks else None
-    st = _hip.lib.hs_upsample2_confusion_fwd(xp, b, c, hi, wi, hm, wm, ho, wo, target.data_ptr(), _EVAL_DTYPES[target.dtype], n,
+    st = _hip.lib.hs_upsample2_confusion_fwd(_hip.dev_ptr(x, 'x'), b, c, hi, wi, hm, wm, ho, wo, target.data_ptr(), _EVAL_DTYPES[target.dtype], n,
                                              1 if per_image else 0, out.data_ptr(), mask.data_ptr() if masks else None,
                                              _hip.stream_ptr())
     _hip.check(st, 'hs_upsample2_confusion_fwd')
@@ -1429,9 +1445,7 @@ def upsample2_argmax(x, mid_size, size):
     """uint8 masks (B, *size) of the logits ``x`` resized to ``mid_size`` and from there to ``size``, one launch with nothing counted
     (hs_upsample2_confusion_fwd without a target); neither resized tensor exists in memory.  Bit-identical to
     ``upsample_bilinear(upsample_bilinear(x, mid_size), size).argmax(1)``; ``upsample_argmax`` where one of the stages is the identity."""
-    if not isinstance(x, torch.Tensor) or x.dim() != 4:
-        raise ValueError('x must be (B, C, Hi, Wi) logits')
-    b, c, hi, wi = x.shape
+    b, c, hi, wi = _logits_shape(x)
     (hm, wm), (ho, wo) = _size2(mid_size, 'mid_size'), _size2(size, 'size')
     if (ho, wo) == (hm, wm) or (hi, wi) == (hm, wm):
         return upsample_argmax(x, (ho, wo))
@@ -1463,20 +1477,6 @@ def confusion_update(pred, target, num_classes, out=None, per_image=False):
     return out
 
 
-def _score_out(num_classes, channels, out, batch, per_image, device):
-    """(n, matrix) of the two loss + score entries: ``num_classes=None`` counts nothing (loss and masks only)."""
-    if num_classes is None:
-        if out is not None:
-            raise ValueError('out= needs num_classes: nothing is counted without it')
-        if channels > 256:
-            raise ValueError('more than 256 logit channels: the masks are uint8')
-        return 0, None
-    n = _eval_classes(num_classes)            # NotImplementedError above eval_max_classes() (<= 256: the masks are uint8)
-    if channels > n:
-        raise ValueError(f'{channels} logit channels but num_classes = {num_classes}')
-    return n, _eval_out(out, (batch, n, n) if per_image else (n, n), device)
-
-
 @_on_operand_device
 def cross_entropy_score(logits, target, ignore_index, num_classes, out=None, per_image=False, masks=False):
     """The per-pixel cross entropy of (B, C, H, W) logits (f32 / bf16 / f16) against int64 ``target`` (B, H, W) AND the batch's score, one
@@ -1489,13 +1489,9 @@ def cross_entropy_score(logits, target, ignore_index, num_classes, out=None, per
     if not isinstance(logits, torch.Tensor) or logits.dim() != 4 or logits.dtype not in DTYPE_CODES:
         raise ValueError('logits must be (B, C, H, W) float32, bfloat16 or float16')
     b, c, h, w = logits.shape
-    target = _eval_labels(target, 'target')
+    target = _eval_target(target, (b, h, w), logits)
     if target.dtype != torch.int64:
         raise ValueError(f'target must be int64 (what the loss takes), got {target.dtype}')
-    if tuple(target.shape) != (b, h, w):
-        raise ValueError(f'target has shape {tuple(target.shape)}, expected {(b, h, w)}')
-    if target.device != logits.device:
-        raise ValueError(f'target is on {target.device}, the logits on {logits.device}')
     n, out = _score_out(num_classes, c, out, b, per_image, logits.device)
     xp = _hip.dev_ptr(logits, 'logits', logits.dtype)
     loss = torch.empty(b, h, w, device=logits.device, dtype=torch.float32)
@@ -1514,15 +1510,9 @@ def upsample_ce_confusion(x, size, target, ignore_index, num_classes, out=None, 
     ``(loss, out, masks)``: ``loss`` (B, Ho, Wo) f32 bit-identical to ``PixelCrossEntropy`` on ``upsample_bilinear(x, size)``, the uint8
     masks to ``upsample_argmax``'s, the counts to ``upsample_confusion``'s (``out``, ``per_image`` and the errors raised: that
     function's; ``num_classes=None``: nothing counted, ``out`` None).  The resized logits never exist in memory.  Capturable."""
-    if not isinstance(x, torch.Tensor) or x.dim() != 4:
-        raise ValueError('x must be (B, C, Hi, Wi) logits')
-    b, c, hi, wi = x.shape
+    b, c, hi, wi = _logits_shape(x)
     ho, wo = _size2(size, 'size')
-    target = _eval_labels(target, 'target')
-    if tuple(target.shape) != (b, ho, wo):
-        raise ValueError(f'target has shape {tuple(target.shape)}, expected {(b, ho, wo)}')
-    if target.device != x.device:
-        raise ValueError(f'target is on {target.device}, the logits on {x.device}')
+    target = _eval_target(target, (b, ho, wo), x)
     n, out = _score_out(num_classes, c, out, b, per_image, x.device)
     xp = _hip.dev_ptr(x, 'x')
     loss = torch.empty(b, ho, wo, device=x.device, dtype=torch.float32)
@@ -1576,9 +1566,7 @@ def upsample_overlay(x, size, frames, style, out=None):
     """``upsample_argmax(x, size)`` with ``style`` blended over ``frames`` (uint8, at ``size``, in ``style.layout``) as the same launch's
     epilogue (hs_upsample_overlay_fwd).  Returns ``(masks, overlay)``: the uint8 masks, bit-identical to ``upsample_argmax``'s, and the
     uint8 overlay, equal to ``overlay(masks, frames, style)``.  ``out``: as :func:`overlay`'s.  Capturable."""
-    if not isinstance(x, torch.Tensor) or x.dim() != 4:
-        raise ValueError('x must be (B, C, Hi, Wi) logits')
-    b, c, hi, wi = x.shape
+    b, c, hi, wi = _logits_shape(x)
     ho, wo = (int(s) for s in size)
     if tuple(style.frame_size(frames)) != (b, ho, wo):
         raise ValueError(f'the frames are {tuple(style.frame_size(frames))} (B, H, W), the masks will be {(b, ho, wo)}')

@@ -1,6 +1,8 @@
 """Pieces shared by the three HyperSeg model variants of this package (v1_0, v1_0_unify, v0_1): the HyperGen wrapper
 logic (single tensor / pyramid + h-flip inference), per-level argument normalisation, coordinate buffers."""
 import numbers
+from dataclasses import dataclass
+from typing import NamedTuple, Optional
 
 import torch
 import torch.nn as nn
@@ -58,70 +60,78 @@ def register_coordinate_buffers(module, coords_res, levels):
             module.register_buffer(f'coord{h}_{w}', coordinate_grid(h, w))
 
 
-def final_masks_scored(p, size, score):
-    """The decoders' ``masks=True`` epilogue with scoring: ``score`` = (target, num_classes, out, per_image) -- the uint8 masks of
-    ``HF.upsample_argmax(p, size)`` with every pixel counted against ``target`` into ``out`` by the same launch
-    (``HF.upsample_confusion``).  A target of another size than ``size`` is scored at ITS resolution, as test.py:167-168 does: the
-    logits at ``size`` are resized once more, to the target's size, before the arg-max -- both resizes composed in the one launch
-    (``HF.upsample2_confusion``), a single one where ``p`` is at ``size`` already; the masks are then at the target's size."""
-    target, num_classes, out, per_image = score
-    label = tuple(target.shape[1:])
-    if label != tuple(size) and tuple(p.shape[2:]) != tuple(size):
-        return HF.upsample2_confusion(p, size, target, num_classes, out=out, per_image=per_image, masks=True)[1]
-    return HF.upsample_confusion(p, label, target, num_classes, out=out, per_image=per_image, masks=True)[1]
+class Score(NamedTuple):
+    """Count every output pixel against ``target`` (B, H, W; uint8 or int64) into the int64 matrix ``out`` -- (n, n), or (B, n, n) with
+    ``per_image``; ``num_classes`` None: nothing is counted (a validation step that only wants loss and masks)."""
+    target: object
+    num_classes: object
+    out: object
+    per_image: bool
 
 
-def final_masks_overlaid(p, size, overlay):
-    """The decoders' ``masks=True`` epilogue with the display blended by the same launch: ``overlay`` = (frames, style, out) -- returns
-    ``(masks, overlay)`` of ``HF.upsample_overlay`` (the masks: ``HF.upsample_argmax(p, size)``'s)."""
-    frames, style, out = overlay
-    return HF.upsample_overlay(p, size, frames, style, out=out)
+class Blend(NamedTuple):
+    """Colour the class map with ``style`` (a ``utils.inference.Overlay``) and blend it over the uint8 ``frames`` into ``out`` (None: a new
+    tensor)."""
+    frames: object
+    style: object
+    out: object
 
 
-def final_masks_validated(p, size, score, ignore_index):
-    """The ``masks=True`` epilogue of a validation step: ``score`` = (target, num_classes, out, per_image) as :func:`final_masks_scored`
-    takes it -- ``num_classes`` None: nothing counted -- with the target at ``size``.  Returns ``(masks, per_pixel)``: the launch
-    (``HF.upsample_ce_confusion``) also makes every pixel's cross entropy against the target, f32 (B, H, W), what
-    ``BootstrappedCrossEntropyLoss`` ranks; the logits at ``size`` never exist."""
-    target, num_classes, out, per_image = score
-    if tuple(target.shape[1:]) != tuple(size):
-        raise ValueError(f'loss= needs a target at the output size {tuple(size)}, got {tuple(target.shape[1:])}')
-    per_pixel, _, masks = HF.upsample_ce_confusion(p, size, target, ignore_index, num_classes, out=out, per_image=per_image)
-    return masks, per_pixel
+@dataclass
+class Epilogue:
+    """What rides on the decoder's final upsample launch instead of writing the logits: the uint8 arg-max masks, plain -- at the frame's
+    size, or resized once more to ``out_size`` -- or scored by that launch (``score``) or blended over the frames by it (``blend``): one of
+    the two per forward.  ``ignore_index`` (with ``score``): the criterion's -- a validation step, the launch also makes every pixel's
+    cross entropy against the score's target.  A scored forward takes its output size from its target."""
+    score: Optional[Score] = None
+    blend: Optional[Blend] = None
+    out_size: Optional[tuple] = None
+    ignore_index: Optional[int] = None
+
+    def __post_init__(self):
+        if self.ignore_index is not None and (self.score is None or self.blend is not None):
+            raise ValueError('the loss rides on a scored epilogue: a score with it, no blend')
+        if self.score is not None and self.blend is not None:
+            raise ValueError('score and blend both ride on the final upsample launch: one of them per forward for now')
+        if self.out_size is not None:
+            self.out_size = tuple(self.out_size)
+
+    def apply(self, p, size):
+        """The last level's output ``p`` -> the masks at ``size`` (the frame's), straight from the one launch; ``(masks, per_pixel)`` of a
+        validation step (per_pixel: f32 (B, H, W), what ``BootstrappedCrossEntropyLoss`` ranks), ``(masks, overlay)`` of a blend.  A
+        score's target of another size than ``size`` is scored at ITS resolution, as test.py:167-168 does: the logits at ``size`` are
+        resized once more, to the target's size, before the arg-max -- both resizes composed in the one launch, a single one where ``p``
+        is at ``size`` already; the masks are then at the target's size."""
+        size = tuple(size)
+        resized = self.out_size is not None and self.out_size != size
+        if self.score is not None:
+            target, num_classes, out, per_image = self.score
+            label = tuple(target.shape[1:])
+            if self.ignore_index is not None:
+                if resized:
+                    raise ValueError('the loss rides on a scored epilogue at the frame\'s size: no other out_size')
+                if label != size:
+                    raise ValueError(f'the loss needs a target at the output size {size}, got {label}')
+                per_pixel, _, masks = HF.upsample_ce_confusion(p, size, target, self.ignore_index, num_classes, out=out, per_image=per_image)
+                return masks, per_pixel
+            if label != size and tuple(p.shape[2:]) != size:
+                return HF.upsample2_confusion(p, size, target, num_classes, out=out, per_image=per_image, masks=True)[1]
+            return HF.upsample_confusion(p, label, target, num_classes, out=out, per_image=per_image, masks=True)[1]
+        if self.blend is not None:
+            if resized:
+                raise ValueError('the overlay is blended over the frames, at their size: another out_size does not go with a blend')
+            frames, style, out = self.blend
+            return HF.upsample_overlay(p, size, frames, style, out=out)
+        if not resized:
+            return HF.upsample_argmax(p, size)
+        return HF.upsample2_argmax(p, size, self.out_size)
 
 
-def final_masks(p, size, score=None, overlay=None, out_size=None, loss=None):
-    """What ``masks=True`` returns for the last level's output ``p``: the uint8 argmax masks at ``size`` straight from the final upsample
-    launch -- scored by that launch with ``score``, or blended by it with ``overlay`` (then ``(masks, overlay)``); one or the other.
-    ``out_size`` (the unscored case): masks of the logits at ``size`` resized once more to ``out_size``, from the same one launch
-    (``HF.upsample2_argmax``); a scored forward takes that size from its target.  ``loss`` (with ``score``): the criterion's
-    ``ignore_index`` -- the launch also makes the per-pixel cross entropy against the score's target, and ``(masks, per_pixel)`` is
-    returned (:func:`final_masks_validated`)."""
-    if loss is not None:
-        if score is None or overlay is not None or (out_size is not None and tuple(out_size) != tuple(size)):
-            raise ValueError('loss= rides on a scored masks=True epilogue at the frame\'s size: score= with it, no overlay=, no out_size=')
-        return final_masks_validated(p, size, score, loss)
-    if score is not None and overlay is not None:
-        raise ValueError('score= and overlay= both ride on the final upsample launch: one of them per forward for now')
-    if overlay is not None:
-        if out_size is not None and tuple(out_size) != tuple(size):
-            raise ValueError('the overlay is blended over the frames, at their size: out_size= does not go with overlay=')
-        return final_masks_overlaid(p, size, overlay)
-    if score is not None:
-        return final_masks_scored(p, size, score)
-    if out_size is None or tuple(out_size) == tuple(size):
-        return HF.upsample_argmax(p, size)
-    return HF.upsample2_argmax(p, size, out_size)
-
-
-def finish_decoder(decoder, p, size, masks, score, overlay=None, out_size=None, loss=None):
-    """What the v1_0 and unify decoders return for their last level's output ``p``: with ``masks``, the uint8 argmax masks at ``size``
-    straight from the final upsample launch (scored by the same launch when ``score`` is given, blended over the frames by it when
-    ``overlay`` is: :func:`final_masks`); otherwise the logits, resized to ``size`` -- into ``decoder.output_buffer`` where a serving
-    wrapper has set one."""
-    if masks:
-        return final_masks(p, size, score, overlay, out_size, loss)
-    assert overlay is None and loss is None, 'overlay= and loss= ride on the masks=True epilogue'
+def finish_decoder(decoder, p, size, epilogue):
+    """What the v1_0 and unify decoders return for their last level's output ``p``: what ``epilogue`` makes of it (:class:`Epilogue`), or,
+    without one, the logits, resized to ``size`` -- into ``decoder.output_buffer`` where a serving wrapper has set one."""
+    if epilogue is not None:
+        return epilogue.apply(p, size)
     if p.shape[2:] != size:
         p = HF.upsample_bilinear(p, size, out=getattr(decoder, 'output_buffer', None))
     return p
@@ -188,7 +198,9 @@ class HyperGenBase(EpochOnModeSwitch, nn.Module):
     def hyper_params(self):
         return self.decoder.hyper_params
 
-    def process_single_tensor(self, x, hflip=False, masks=False, score=None, overlay=None, out_size=None, loss=None):
+    def process_single_tensor(self, x, hflip=False, epilogue=None):
+        """The logits of one tensor; with ``epilogue`` (an :class:`Epilogue`; inference only, unflipped) what it makes of the decoder's last
+        launch instead: the uint8 masks, or masks and per-pixel losses / overlay."""
         frame = None
         if x.dtype == torch.uint8:
             norm = self._require_norm()
@@ -207,18 +219,34 @@ class HyperGenBase(EpochOnModeSwitch, nn.Module):
         if isinstance(head_out, torch.Tensor):
             head_out = head_out.contiguous()
         pyramid = [t.contiguous() for t in [x] + features[:-1]]
-        assert score is None or (masks and not hflip), 'scoring rides on the masks=True epilogue of an unflipped frame'
-        assert overlay is None or (masks and not hflip), 'the overlay rides on the masks=True epilogue of an unflipped frame'
-        # with overlay=: (masks, overlay), unflipped.  score= and overlay= together: final_masks raises
-        assert out_size is None or (masks and not hflip), 'another output size rides on the masks=True epilogue of an unflipped frame'
-        assert loss is None or score is not None, 'the loss rides on a scored masks=True epilogue'
-        if loss is not None:                  # a validation step: (masks, per-pixel losses) from the decoder's last launch
-            return self.decoder(pyramid, head_out, masks=True, score=score, loss=loss)
-        if out_size is not None:              # masks at another size than the frame's: both resizes in the decoder's last launch
-            y = self.decoder(pyramid, head_out, masks=True, score=score, overlay=overlay, out_size=tuple(out_size))
-        else:
-            y = self.decoder(pyramid, head_out, masks=True, score=score, overlay=overlay) if masks else self.decoder(pyramid, head_out)
+        # (outside training: the decoders assert that themselves)
+        assert epilogue is None or not hflip, 'an epilogue rides on the last launch of an unflipped frame'
+        y = self.decoder(pyramid, head_out, epilogue=epilogue)
         return torch.flip(y, [-1]) if hflip else y
+
+    def _logits_at(self, x, size):
+        """``self(x)``, resized to ``size`` (H, W) where that is another size: the composed routes' logits at a label's resolution
+        (test.py:167-168)."""
+        pred = self(x)
+        if tuple(pred.shape[2:]) == tuple(size):
+            return pred
+        if pred.is_cuda:
+            return HF.upsample_bilinear(pred.contiguous(), tuple(size))
+        return torch.nn.functional.interpolate(pred, size=size, mode='bilinear')
+
+    @staticmethod
+    def _count(confmat, target, masks, per_image):
+        """The composed routes' scoring: ``confmat``'s own update of finished masks."""
+        if per_image:
+            confmat.update_per_image(target, masks)
+        else:
+            confmat.update(target.flatten(), masks.flatten())
+
+    @staticmethod
+    def _scorable(target, batch, n):
+        """What the fused routes of ``evaluate`` and ``validate`` ask of the target and the class count (``n`` None: nothing counted)."""
+        return (isinstance(target, torch.Tensor) and target.dtype in (torch.uint8, torch.int64) and target.dim() == 3
+                and target.shape[0] == batch and (n is None or n <= min(256, HF.eval_max_classes())))
 
     @torch.no_grad()
     def segment(self, x, size=None):
@@ -233,14 +261,11 @@ class HyperGenBase(EpochOnModeSwitch, nn.Module):
             size = None
         fused = isinstance(x, torch.Tensor) and not self.training and not self.inference_hflip
         if size is None:
-            return self.process_single_tensor(x, masks=True) if fused else self(x).argmax(1).to(torch.uint8)
+            return self.process_single_tensor(x, epilogue=Epilogue()) if fused else self(x).argmax(1).to(torch.uint8)
         size = tuple(int(s) for s in size)
         if fused and x.is_cuda:
-            return self.process_single_tensor(x, masks=True, out_size=size)
-        pred = self(x)
-        pred = HF.upsample_bilinear(pred.contiguous(), size) if pred.is_cuda else \
-            torch.nn.functional.interpolate(pred, size=size, mode='bilinear')
-        return pred.argmax(1).to(torch.uint8)
+            return self.process_single_tensor(x, epilogue=Epilogue(out_size=size))
+        return self._logits_at(x, size).argmax(1).to(torch.uint8)
 
     @torch.no_grad()
     def evaluate(self, x, target, confmat, per_image=False):
@@ -256,31 +281,22 @@ class HyperGenBase(EpochOnModeSwitch, nn.Module):
         n = confmat.num_classes
         x = self.resized(x)
         fused = (isinstance(x, torch.Tensor) and x.is_cuda and not self.training and isinstance(target, torch.Tensor)
-                 and target.is_cuda and target.dtype in (torch.uint8, torch.int64) and target.dim() == 3
-                 and target.shape[0] == x.shape[0] and n <= min(256, HF.eval_max_classes()))
+                 and target.is_cuda and self._scorable(target, x.shape[0], n))
         if fused:
             mat = confmat.matrix(x.device)
+            out = torch.zeros((x.shape[0], n, n), dtype=torch.int64, device=x.device) if per_image else mat
+            masks = self.process_single_tensor(x, epilogue=Epilogue(Score(target, n, out, per_image)))
             if per_image:
-                slabs = torch.zeros((x.shape[0], n, n), dtype=torch.int64, device=x.device)
-                masks = self.process_single_tensor(x, masks=True, score=(target, n, slabs, True))
-                confmat.add_per_image(slabs)
-            else:
-                masks = self.process_single_tensor(x, masks=True, score=(target, n, mat, False))
+                confmat.add_per_image(out)
             if masks.dtype == torch.uint8:
                 return masks
-            raise RuntimeError('the decoder returned logits from its masks=True route: nothing was scored')
+            raise RuntimeError('the decoder returned logits where its epilogue was asked for: nothing was scored')
         out_res = self.frame_size(x, True) if isinstance(x, torch.Tensor) else self.frame_size(x[0], False)
         if tuple(target.shape[1:]) != out_res:
-            pred = self(x)
-            pred = HF.upsample_bilinear(pred.contiguous(), tuple(target.shape[1:])) if pred.is_cuda else \
-                torch.nn.functional.interpolate(pred, size=target.shape[1:], mode='bilinear')
-            masks = pred.argmax(1).to(torch.uint8)
+            masks = self._logits_at(x, target.shape[1:]).argmax(1).to(torch.uint8)
         else:
             masks = self.segment(x)
-        if per_image:
-            confmat.update_per_image(target, masks)
-        else:
-            confmat.update(target.flatten(), masks.flatten())
+        self._count(confmat, target, masks, per_image)
         return masks
 
     def _validate_fused(self, x, target, criterion, n, staged=False):
@@ -288,7 +304,7 @@ class HyperGenBase(EpochOnModeSwitch, nn.Module):
         first (``GraphedModel.validate``), so where they live now does not matter."""
         from ..training import BootstrappedCrossEntropyLoss, USE_HIP_BOOTSTRAP, USE_FUSED_LOSS
         if not (isinstance(x, torch.Tensor) and x.dim() == 4 and not self.training and isinstance(target, torch.Tensor)
-                and target.dtype in (torch.uint8, torch.int64) and target.dim() == 3 and (staged or (x.is_cuda and target.is_cuda))):
+                and (staged or (x.is_cuda and target.is_cuda)) and self._scorable(target, x.shape[0], n)):
             return False
         if not (isinstance(criterion, BootstrappedCrossEntropyLoss) and criterion.weight is None and criterion.score is None
                 and USE_HIP_BOOTSTRAP and USE_FUSED_LOSS):
@@ -296,7 +312,7 @@ class HyperGenBase(EpochOnModeSwitch, nn.Module):
         if tuple(target.shape) != (x.shape[0],) + self.frame_size(x) or x.shape[0] > 65535:
             return False
         pixels = target.shape[1] * target.shape[2]
-        return criterion.k < pixels < 2 ** 31 and (n is None or n <= min(256, HF.eval_max_classes()))
+        return criterion.k < pixels < 2 ** 31
 
     @torch.no_grad()
     def validate(self, x, target, criterion, confmat=None, per_image=False):
@@ -326,25 +342,19 @@ class HyperGenBase(EpochOnModeSwitch, nn.Module):
             out = None
             if confmat is not None:
                 out = torch.zeros((x.shape[0], n, n), dtype=torch.int64, device=x.device) if per_image else confmat.matrix(x.device)
-            got = self.process_single_tensor(x, masks=True, score=(target, n, out, per_image), loss=criterion.ignore_index)
+            got = self.process_single_tensor(x, epilogue=Epilogue(Score(target, n, out, per_image), ignore_index=criterion.ignore_index))
             if not isinstance(got, tuple):
-                raise RuntimeError('the decoder returned logits from its masks=True route: nothing was scored')
+                raise RuntimeError('the decoder returned logits where its epilogue was asked for: nothing was scored')
             masks, per_pixel = got
             if confmat is not None and per_image:
                 confmat.add_per_image(out)
             return BootstrapMeanOfBatch.apply(per_pixel.flatten(1), criterion.k, criterion.thresh), masks
-        pred = self(x)
-        if tuple(pred.shape[2:]) != tuple(target.shape[1:]):
-            pred = HF.upsample_bilinear(pred.contiguous(), tuple(target.shape[1:])) if pred.is_cuda else \
-                torch.nn.functional.interpolate(pred, size=target.shape[1:], mode='bilinear')
+        pred = self._logits_at(x, target.shape[1:])
         target = target.to(pred.device)
         loss = criterion(pred, target.long())
         masks = pred.argmax(1).to(torch.uint8)
         if confmat is not None:
-            if per_image:
-                confmat.update_per_image(target, masks)
-            else:
-                confmat.update(target.flatten(), masks.flatten())
+            self._count(confmat, target, masks, per_image)
         return loss.detach(), masks
 
     @torch.no_grad()
@@ -376,10 +386,10 @@ class HyperGenBase(EpochOnModeSwitch, nn.Module):
             raise ValueError(f'frames are {tuple(style.frame_size(frames))} (B, H, W), the input is {size}')
         fused = isinstance(x, torch.Tensor) and x.is_cuda and frames.is_cuda and not self.training and not self.inference_hflip
         if fused:
-            got = self.process_single_tensor(x, masks=True, overlay=(frames, style, out))
+            got = self.process_single_tensor(x, epilogue=Epilogue(blend=Blend(frames, style, out)))
             if isinstance(got, tuple):
                 return got
-            raise RuntimeError('the decoder returned logits from its masks=True route: nothing was blended')
+            raise RuntimeError('the decoder returned logits where its epilogue was asked for: nothing was blended')
         masks = self.segment(x)
         blended = style.blend(frames.to(masks.device), masks)
         if out is not None:

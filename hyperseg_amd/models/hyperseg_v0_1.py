@@ -17,7 +17,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from .. import functional as HF
-from ._common import EpochOnModeSwitch, HyperGenBase, final_masks, coordinate_grid, per_level
+from ._common import EpochOnModeSwitch, HyperGenBase, coordinate_grid, per_level
 from .layers.meta_patch import MetaPatchConv2d, make_meta_patch_conv2d_block
 from .layers.meta_sequential import MetaSequential
 
@@ -146,7 +146,7 @@ class MultiScaleDecoder(EpochOnModeSwitch, nn.Module):
         self.hyper_params = int(self._ranges[-1])
         self._ranges.append(self.hyper_params)
 
-    def forward(self, x, w, masks=False, score=None, overlay=None, out_size=None, loss=None):
+    def forward(self, x, w, epilogue=None):
         assert isinstance(w, (list, tuple))
         assert len(x) <= self.levels
         p = None
@@ -155,9 +155,9 @@ class MultiScaleDecoder(EpochOnModeSwitch, nn.Module):
             p = getattr(self, f'level_{level}')(stage, w[level])
         if self.out_fc is not None:
             p = self.out_fc(p, w[-1])
-        if masks and not (self.training or p.requires_grad):
+        if epilogue is not None and not (self.training or p.requires_grad):
             # identity resize: argmax over classes only -- a label / out_size of another size: the one resize to it, then the argmax
-            return final_masks(p.contiguous(), p.shape[2:], score, overlay, out_size, loss)
+            return epilogue.apply(p.contiguous(), p.shape[2:])
         return p
 
 

@@ -758,18 +758,18 @@ class MultiScaleDecoder(EpochOnModeSwitch, nn.Module):
             p = self.out_fc(p, banks[-1])
         return p
 
-    def forward(self, x, s, masks=False, score=None, overlay=None, out_size=None, loss=None):
-        """``masks=True`` (inference only, not in the reference): uint8 argmax masks straight from the final upsample
-        kernel instead of logits."""
+    def forward(self, x, s, epilogue=None):
+        """``epilogue`` (a ``_common.Epilogue``; inference only, not in the reference): uint8 argmax masks straight from the final
+        upsample kernel instead of logits."""
         if self.training or HA.needs_grad(s, *x, *self.parameters()):
-            assert not masks, 'masks=True is an inference-only shortcut'
+            assert epilogue is None, 'masks=True is an inference-only shortcut'
             return self._forward_autograd(x, s)
         if any(len(g) > 1 for g in self._hyper_modules()):
             # several signal-fed modules inside one level (level_layers > 1; no shipped config): the reference hands the
             # k-th of them the signal slice that starts at the hyper-parameter count of its predecessors
             # (meta_sequential.py:35), so their signal_index is relative to that slice -- take the per-module route,
             # which slices exactly like that, instead of the single launch over the whole signal
-            assert not masks, 'masks=True needs the single-launch route'
+            assert epilogue is None, 'masks=True needs the single-launch route'
             return self._forward_autograd(x, s)
         plan = self._bank_plan(x, s)
         banks = self._make_banks(plan, s)
@@ -777,7 +777,7 @@ class MultiScaleDecoder(EpochOnModeSwitch, nn.Module):
         done = self._run_k1_chain(x, banks) if plan.chain else None
         p, first = done if done is not None else (None, 0)
         p = self._run_levels(x, s, banks, plan, first, p)
-        return finish_decoder(self, p, x[0].shape[2:], masks, score, overlay, out_size, loss)
+        return finish_decoder(self, p, x[0].shape[2:], epilogue)
 
 
 class WeightMapper(nn.Module):

@@ -154,12 +154,12 @@ class MultiScaleDecoder(EpochOnModeSwitch, nn.Module):
                 sources[lvl] = IN_CONSUMER
         return BankPlan(sources, None, chain)
 
-    def forward(self, x, s, masks=False, score=None, overlay=None, out_size=None, loss=None):
+    def forward(self, x, s, epilogue=None):
         if self.out_fc is not None:
             raise NotImplementedError('with_out_fc=True: the reference itself feeds the raw signal to out_fc here '
                                       '(hyperseg_v1_0_unify.py:252-253); no config uses it')
         if self.training or HA.needs_grad(s, *x, *self.parameters()):
-            assert not masks, 'masks=True is an inference-only shortcut'
+            assert epilogue is None, 'masks=True is an inference-only shortcut'
             return self._forward_autograd(x, s)
         plan = self._bank_plan(x, s)
         ul = self.unify_level
@@ -181,7 +181,7 @@ class MultiScaleDecoder(EpochOnModeSwitch, nn.Module):
                 # rows [r0, r1) of the shared bank, consumed in place (reference: w[:, r0:r1] + .contiguous())
                 w = HF.BankRef(shared.bank[:, r0:r1], shared.shape[0], r1 - r0, shared.grid)
             p = self.level_blocks[level](stage, [w])
-        return finish_decoder(self, p, x[0].shape[2:], masks, score, overlay, out_size, loss)
+        return finish_decoder(self, p, x[0].shape[2:], epilogue)
 
 
 class HyperGen(HyperGenBase):

@@ -24,6 +24,8 @@ import os
 import torch
 import torch.nn as nn
 
+from ..models._common import Blend, Epilogue, HyperGenBase, Score
+
 
 class InputNorm:
     """The input transform as data: per-channel float32 ``mean`` / ``std`` and the ``layout`` of the uint8 frames they apply to --
@@ -979,6 +981,34 @@ class GraphedModel(nn.Module):
                              f'{shape} on {device} (per_image fixes the batch size at the first call)')
         return self.confusion
 
+    def _to_model_device(self, x, *more):
+        """``x`` (a tensor or a list of them) and ``more`` (tensors or None) for the wrapped model's eager routes: on its device where
+        that is a GPU, as they are otherwise."""
+        p = next(self.model.parameters(), None)
+        if p is None or not p.is_cuda:
+            return (x, *more)
+
+        def move(t):
+            return None if t is None else t.to(p.device, non_blocking=True)
+        return ([move(t) for t in x] if isinstance(x, (list, tuple)) else move(x), *map(move, more))
+
+    def _score_eagerly(self, scorer, x, target, *args):
+        """``scorer`` (``model.evaluate`` / ``model.validate``) on its eager routes, the counts landing in ``self.confusion``."""
+        from ..fps import ConfusionMatrix
+        cm = ConfusionMatrix(self.num_classes)
+        if self.per_image:
+            got = scorer(x, target, *args, cm, per_image=True)
+            self._confusion_on(target.device, target.shape[0]).add_(cm.per_image[-1])
+        else:
+            cm.mat = self._confusion_on(target.device, target.shape[0])
+            got = scorer(x, target, *args, cm)
+        return got
+
+    def _capture_counting(self, key, inputs, device, run, confusion):
+        """``_capture`` of ``run(*static, out)`` counting into ``confusion``; the warm-up passes execute, so they count into a scratch copy."""
+        scratch = None if confusion is None else torch.zeros_like(confusion)
+        return self._capture(key, inputs, device, run=lambda *static: run(*static, confusion), warm=lambda *static: run(*static, scratch))
+
     @torch.no_grad()
     def evaluate(self, x, target):
         """One replay per frame that also scores it: returns the uint8 masks (the graph's static output, as ``forward``'s) and
@@ -991,38 +1021,20 @@ class GraphedModel(nn.Module):
         target's size; the key holds the target's shape, so each label size gets a graph of its own.  What the graph cannot serve
         (``forward``'s list, plus a target of another type, or more classes than the kernel covers) is scored eagerly by
         ``model.evaluate`` into the same matrix."""
-        from .. import functional as HF
-        from ..fps import ConfusionMatrix
-        p = next(self.model.parameters(), None)
         n = self.num_classes
-        graphable = (self._graphable(x) and isinstance(target, torch.Tensor) and target.dtype in (torch.uint8, torch.int64)
-                     and target.dim() == 3 and x.dim() == 4 and hasattr(self.model, 'frame_size')
-                     and target.shape[0] == x.shape[0] and target.numel() > 0
-                     and n is not None and n <= min(256, HF.eval_max_classes()) and hasattr(self.model, 'process_single_tensor'))
+        graphable = (self._graphable(x) and x.dim() == 4 and hasattr(self.model, 'frame_size') and hasattr(self.model, 'process_single_tensor')
+                     and n is not None and HyperGenBase._scorable(target, x.shape[0], n) and target.numel() > 0)
         if not graphable:
-            if p is not None and p.is_cuda:
-                x = [t.to(p.device, non_blocking=True) for t in x] if isinstance(x, (list, tuple)) else x.to(p.device, non_blocking=True)
-                target = target.to(p.device, non_blocking=True)
-            device = target.device
-            cm = ConfusionMatrix(n)
-            if self.per_image:
-                masks = self.model.evaluate(x, target, cm, per_image=True)
-                self._confusion_on(device, target.shape[0]).add_(cm.per_image[-1])
-            else:
-                cm.mat = self._confusion_on(device, target.shape[0])
-                masks = self.model.evaluate(x, target, cm)
-            return masks
-        device = p.device
+            return self._score_eagerly(self.model.evaluate, *self._to_model_device(x, target))
+        device = next(self.model.parameters()).device
         confusion = self._confusion_on(device, x.shape[0])
         key = ('evaluate', tuple(x.shape), x.dtype, target.dtype, device, self._norm_of(x), tuple(target.shape))
         entry = self._graphs.get(key)
         if entry is None:
-            scratch = torch.zeros_like(confusion)                # the warm-up passes execute: their counts go here
+            def run(xs, ts, out):
+                return self.model.process_single_tensor(self.model.resized(xs), epilogue=Epilogue(Score(ts, n, out, self.per_image)))
 
-            def run(xs, ts, out=confusion):
-                return self.model.process_single_tensor(self.model.resized(xs), masks=True, score=(ts, n, out, self.per_image))
-
-            entry = self._capture(key, [x, target], device, run=run, warm=lambda xs, ts: run(xs, ts, scratch))
+            entry = self._capture_counting(key, [x, target], device, run, confusion)
         return self._replay(entry, [x, target], device)
 
     @torch.no_grad()
@@ -1037,44 +1049,32 @@ class GraphedModel(nn.Module):
         the next call of the same shape.  The values are ``model.validate``'s (its note on an unprepared model's
         stock encoder applies).  What the graph cannot serve takes ``model.validate``'s routes, counting into the same
         matrix."""
-        from ..fps import ConfusionMatrix
         criterion = self.criterion
         if criterion is None:
             raise ValueError('GraphedModel.validate needs the loss: GraphedModel(model, criterion=BootstrappedCrossEntropyLoss(...))')
         model = self.model
-        p = next(model.parameters(), None)
         n = self.num_classes
         graphable = (self._graphable(x) and isinstance(target, torch.Tensor) and target.numel() > 0 and hasattr(model, '_validate_fused')
                      and model._validate_fused(x, target, criterion, n, staged=True))
-        device = p.device if graphable else None
         if not graphable:
-            if p is not None and p.is_cuda:
-                x = [t.to(p.device, non_blocking=True) for t in x] if isinstance(x, (list, tuple)) else x.to(p.device, non_blocking=True)
-                target = target.to(p.device, non_blocking=True)
+            x, target = self._to_model_device(x, target)
             if n is None:
                 return model.validate(x, target, criterion)
-            cm = ConfusionMatrix(n)
-            if self.per_image:
-                got = model.validate(x, target, criterion, cm, per_image=True)
-                self._confusion_on(target.device, target.shape[0]).add_(cm.per_image[-1])
-            else:
-                cm.mat = self._confusion_on(target.device, target.shape[0])
-                got = model.validate(x, target, criterion, cm)
-            return got
+            return self._score_eagerly(model.validate, x, target, criterion)
+        device = next(model.parameters()).device
         confusion = None if n is None else self._confusion_on(device, x.shape[0])
         key = ('validate', tuple(x.shape), x.dtype, target.dtype, device, self._norm_of(x), tuple(target.shape), criterion.k, criterion.thresh,
                criterion.ignore_index)
         entry = self._graphs.get(key)
         if entry is None:
             from ..autograd import BootstrapMeanOfBatch
-            scratch = None if confusion is None else torch.zeros_like(confusion)     # the warm-up passes execute: their counts go here
 
-            def run(xs, ts, out=confusion):
-                masks, per_pixel = model.process_single_tensor(model.resized(xs), masks=True, score=(ts, n, out, self.per_image),
-                                                               loss=criterion.ignore_index)
+            def run(xs, ts, out):
+                masks, per_pixel = model.process_single_tensor(
+                    model.resized(xs), epilogue=Epilogue(Score(ts, n, out, self.per_image), ignore_index=criterion.ignore_index))
                 return BootstrapMeanOfBatch.apply(per_pixel.flatten(1), criterion.k, criterion.thresh), masks
 
-            entry = self._capture(key, [x, target], device, run=run, warm=lambda xs, ts: run(xs, ts, scratch))
+            entry = self._capture_counting(key, [x, target], device, run, confusion)
         return self._replay(entry, [x, target], device)
 
     @torch.no_grad()
@@ -1088,15 +1088,12 @@ class GraphedModel(nn.Module):
         (``forward``'s list, and h-flip inference) takes ``model.overlay``'s eager routes."""
         model = self.model
         style = getattr(model, 'overlay_style', None)
-        p = next(model.parameters(), None)
         graphable = (style is not None and self._graphable(x) and x.dim() == 4 and not model.inference_hflip
                      and (frames is not None or x.dtype == torch.uint8) and hasattr(model, 'process_single_tensor'))
         if not graphable:
-            if p is not None and p.is_cuda:
-                x = [t.to(p.device, non_blocking=True) for t in x] if isinstance(x, (list, tuple)) else x.to(p.device, non_blocking=True)
-                frames = None if frames is None else frames.to(p.device, non_blocking=True)
+            x, frames = self._to_model_device(x, frames)
             return model.overlay(x, frames=frames)
-        device = p.device
+        device = next(model.parameters()).device
         if frames is None and style.layout != model._require_norm().layout:
             raise ValueError(f"the input frames are '{model.input_norm.layout}' (model.input_norm), the style blends over '{style.layout}' frames")
         size = (x.shape[0],) + tuple(model.frame_size(x))
@@ -1108,7 +1105,7 @@ class GraphedModel(nn.Module):
         if entry is None:
             def run(xs, fs=None):
                 xs = model.resized(xs)               # (a camera-size uint8 frame: the resize is the graph's first node)
-                return model.process_single_tensor(xs, masks=True, overlay=(xs if fs is None else fs, style, None))
+                return model.process_single_tensor(xs, epilogue=Epilogue(blend=Blend(xs if fs is None else fs, style, None)))
 
             entry = self._capture(key, inputs, device, run=run)
         return self._replay(entry, inputs, device)

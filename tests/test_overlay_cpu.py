@@ -164,9 +164,11 @@ def test_model_overlay_argument_errors_and_state_dict():
 
 
 def test_score_and_overlay_are_mutually_exclusive():
-    from hyperseg_amd.models._common import final_masks, finish_decoder
-    p = torch.zeros(1, 3, 4, 4)
+    from hyperseg_amd.models._common import Blend, Epilogue, Score
+    score, blend = Score(None, 3, None, False), Blend(None, None, None)
     with pytest.raises(ValueError, match='one of them'):
-        final_masks(p, (8, 8), score=(None, 3, None, False), overlay=(None, None, None))
-    with pytest.raises(ValueError, match='one of them'):
-        finish_decoder(None, p, (8, 8), True, (None, 3, None, False), (None, None, None))
+        Epilogue(score=score, blend=blend)
+    with pytest.raises(ValueError):
+        Epilogue(ignore_index=255)                                 # a loss without a score
+    with pytest.raises(ValueError):
+        Epilogue(blend=blend, ignore_index=255)                    # a loss with a blend

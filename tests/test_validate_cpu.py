@@ -100,17 +100,17 @@ def test_criterion_score_on_cpu(ignore_index):
 def _toy_model():
     """A HyperGenBase whose single-tensor pass is a CPU 1x1 convolution (tests/test_eval_cpu.py's toy net under the models' wrapper):
     every route of the wrapper that does not need the GPU."""
-    from hyperseg_amd.models._common import HyperGenBase
+    from hyperseg_amd.models._common import Epilogue, HyperGenBase
 
     class Toy(HyperGenBase):
         def __init__(self):
             super().__init__()
             self.net = torch.nn.Conv2d(3, 5, 1)
 
-        def process_single_tensor(self, x, hflip=False, masks=False, **kw):
-            assert not hflip and all(v is None for v in kw.values()), 'CPU: nothing rides on the epilogue'
+        def process_single_tensor(self, x, hflip=False, epilogue=None):
+            assert not hflip and epilogue in (None, Epilogue()), 'CPU: nothing rides on the epilogue'
             y = self.net(x)
-            return y.argmax(1).to(torch.uint8) if masks else y
+            return y.argmax(1).to(torch.uint8) if epilogue is not None else y
 
     m = Toy()
     with torch.no_grad():
