@@ -1713,6 +1713,93 @@ def color_jitter(x_u8, params, layout='hwc', norm=None, out=None, table=None):
     return out
 
 
+def _cpu_result(out, res):
+    if not isinstance(out, torch.Tensor) or tuple(out.shape) != tuple(res.shape) or out.dtype != res.dtype or out.device != res.device:
+        raise ValueError(f'out must be a {res.dtype} tensor of shape {tuple(res.shape)} on {res.device}')
+    out.copy_(res)
+    return out
+
+
+@_on_operand_device
+def frame_rotate(x_u8, angle, layout='hwc', size=None, fill=(0, 0, 0), pad_fill=(0, 0, 0), norm=None, out=None, table=None):
+    """uint8 frames (B, H, W, 3) / (B, 3, H, W) (``layout``), all of one size, rotated by ``angle`` degrees counter-clockwise about the
+    centre with ``PIL.Image.rotate(angle, BICUBIC)``'s float64 arithmetic, byte for byte, in one launch (hs_frame_rotate_fwd; the
+    arithmetic: ``utils.rotate``) -- the reference's ``RandomRotation`` and, through ``size``, the ``ConstantPad`` after it.  ``angle``: one
+    value or B values.  ``size``: the padded (Ho, Wo) >= (H, W), the rotated image at its top-left corner -- default the input's own size.
+    ``fill``: 3 bytes where the rotation looks outside the frame; ``pad_fill``: 3 bytes for the padding.  The defaults are the reference's
+    VOC config: ``RandomRotation(30.)`` fills with 0 and ``ConstantPad(512, lbl_fill=255)`` pads the frame with 0.  Returns uint8 in the
+    input's layout, or with ``norm`` (a ``utils.inference.InputNorm``) the float32 (B, 3, Ho, Wo) image looked up in its table, both
+    fills included.  ``out``: a contiguous tensor of that shape and dtype to write into.  Equal to ``utils.rotate.frame_rotate_cpu``.
+
+    ``table``: the caller's own matrices on the device -- float64 (B, 6), contiguous, what ``utils.rotate.matrix_table(H, W, angle,
+    B).to(device)`` gives; ``angle`` is then not read (pass None).  The kernel reads the table when it runs, so a captured graph replays
+    with what the caller last copied into it; without ``table`` there is one small host-to-device copy in front.  Nothing is read back."""
+    from .utils import rotate
+    h, w = rotate._check_frames(x_u8, layout)
+    if not x_u8.is_cuda:                                       # CPU tensors: the same values from the CPU implementation
+        res = rotate.frame_rotate_cpu(x_u8, angle, layout, size, fill, pad_fill, norm, table)
+        return res if out is None else _cpu_result(out, res)
+    if norm is not None and norm.layout != layout:
+        raise ValueError(f"norm describes '{norm.layout}' frames, these are '{layout}'")
+    b = x_u8.shape[0]
+    ho, wo = rotate.check_size(size, h, w)
+    fill, pad_fill = rotate.check_fill(fill), rotate.check_fill(pad_fill, 'pad_fill')
+    if norm is not None:
+        shape, dtype = (b, 3, ho, wo), torch.float32
+    else:
+        shape, dtype = ((b, ho, wo, 3) if layout == 'hwc' else (b, 3, ho, wo)), torch.uint8
+    if table is None:
+        table = rotate.matrix_table(h, w, angle, b).to(x_u8.device)
+    else:
+        rotate.check_table(table, b, torch.float64, x_u8.device)
+    if out is None:
+        out = torch.empty(shape, device=x_u8.device, dtype=dtype)
+    elif not isinstance(out, torch.Tensor) or tuple(out.shape) != shape or out.dtype != dtype or out.device != x_u8.device:
+        raise ValueError(f'out must be a {dtype} tensor of shape {shape} on {x_u8.device}')
+    st = _hip.lib.hs_frame_rotate_fwd(_hip.dev_ptr(x_u8, 'x_u8', torch.uint8), _LAYOUT_CODES[layout], b, h, w,
+                                      _hip.dev_ptr(table, 'table', torch.float64), ho, wo,
+                                      fill[0] | fill[1] << 8 | fill[2] << 16, pad_fill[0] | pad_fill[1] << 8 | pad_fill[2] << 16,
+                                      None if norm is None else _hip.dev_ptr(norm.table(x_u8.device), 'table'),
+                                      _hip.dev_ptr(out, 'out', dtype), _hip.stream_ptr())
+    _hip.check(st, 'hs_frame_rotate_fwd')
+    return out
+
+
+@_on_operand_device
+def label_rotate(t, angle, size=None, fill=0, pad_fill=255, out=None, table=None):
+    """Labels (B, H, W), uint8 or int64, rotated by ``angle`` with ``PIL.Image.rotate(angle, NEAREST)``'s 16.16 fixed-point arithmetic
+    (hs_label_rotate_fwd, one launch; ``utils.rotate``), ``fill`` where the rotation looks outside, padded right and bottom to ``size``
+    with ``pad_fill``.  The defaults are the reference's VOC config: its ``RandomRotation`` rotates the label with ``self.fill`` (0),
+    NOT its ``lbl_fill`` (seg_transforms.py:424), and ``ConstantPad(512, lbl_fill=255)`` pads it with 255.  Returns the input's dtype, or
+    ``out``'s (uint8 | int64, contiguous, (B, Ho, Wo)).  ``table``: the caller's int32 (B, 6) device tensor of
+    ``utils.rotate.fixed_table`` rows, read when the kernel runs (``angle`` is then not read).  Equal to
+    ``utils.rotate.label_rotate_cpu``."""
+    from .utils import rotate
+    h, w = rotate._check_labels(t)
+    if not t.is_cuda:
+        res = rotate.label_rotate_cpu(t, angle, size, fill, pad_fill, None if out is None else getattr(out, 'dtype', None), table)
+        return res if out is None else _cpu_result(out, res)
+    b = t.shape[0]
+    ho, wo = rotate.check_size(size, h, w)
+    if out is None:
+        out = torch.empty((b, ho, wo), device=t.device, dtype=t.dtype)
+    elif not isinstance(out, torch.Tensor) or tuple(out.shape) != (b, ho, wo) or out.dtype not in _LABEL_DTYPES or out.device != t.device:
+        raise ValueError(f'out must be a uint8 or int64 tensor of shape {(b, ho, wo)} on {t.device}')
+    fill, pad_fill = int(fill), int(pad_fill)
+    for name, f in (('fill', fill), ('pad_fill', pad_fill)):
+        if not (0 <= f <= 255 or (out.dtype == torch.int64 and -2 ** 31 <= f < 2 ** 31)):
+            raise ValueError(f'{name} {f} does not fit the output labels')
+    if table is None:
+        table = rotate.fixed_table(h, w, angle, b).to(t.device)
+    else:
+        rotate.check_table(table, b, torch.int32, t.device)
+    st = _hip.lib.hs_label_rotate_fwd(_hip.dev_ptr(t, 'labels', t.dtype), _LABEL_DTYPES[t.dtype], b, h, w,
+                                      _hip.dev_ptr(table, 'table', torch.int32), ho, wo, fill, pad_fill,
+                                      _hip.dev_ptr(out, 'out', out.dtype), _LABEL_DTYPES[out.dtype], _hip.stream_ptr())
+    _hip.check(st, 'hs_label_rotate_fwd')
+    return out
+
+
 # ------------------------------------------------------------------------------------------
 # small caches keyed on parameter versions (host-side only; used by the fused inference route --
 # tensors that require grad take the hyperseg_amd.autograd route, which folds nothing)

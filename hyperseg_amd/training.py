@@ -483,6 +483,104 @@ def device_augment(frames_u8, labels, scale, crop, offset, hflip, norm, lbl_fill
     return image, label
 
 
+def device_augment_voc(frames, labels, hflip, jitter, scale, angle, pad, norm, fill=(0, 0, 0), lbl_fill=255, rotate_fill=(0, 0, 0),
+                       lbl_rotate_fill=0):
+    """The reference's VOC-SBD train chain RandomHorizontalFlip -> ColorJitter -> RandomResize -> RandomRotation -> ConstantPad -> ToTensor
+    -> Normalize (configs/train/vocsbd_efficientnet_b3_hyperseg-l.py:21-24, hyperseg/datasets/seg_transforms.py) for GIVEN parameters, on
+    the device, Pillow's bytes at every stage.  Drawing the parameters stays with the caller, as in :func:`device_augment`.
+
+    ``frames``: a uint8 tensor (B, H, W, 3) / (B, 3, H, W) as ``norm.layout`` says, or a sequence of B such frames without the batch
+    dimension, each of its own size (VOC images differ in size); ``labels``: (B, H, W) uint8 or int64, or a sequence likewise.
+    ``hflip``, ``scale``, ``angle``: one value for the batch or a sequence of B; ``jitter``: a ``ColorJitterParams``, a sequence of B, or
+    None.  Per sample, in the reference's order:
+      * the flip -- an identity-size ``functional.frame_resize`` / ``label_resize`` whose view is flipped.  It is NOT folded into the
+        resize: Pillow's NEAREST index table is not symmetric (a 2:1 reduction reads source 1, 3, ..., the mirror image would read 0, 2,
+        ...), so resizing and then flipping is another label than the reference's;
+      * ``functional.color_jitter``, uint8 out (skipped when ``jitter`` is None; it commutes with the flip exactly -- per-pixel
+        operations and one mean over the whole frame -- and runs first so that it reads the caller's frame);
+      * ``functional.frame_resize`` (bicubic) / ``label_resize`` to ``round((H, W) * scale)``, numpy's rounding as the reference's, uint8
+        out.  ``scale`` None or 1.0: RandomResize did not fire, nothing is resampled;
+      * ``functional.frame_rotate`` with ``size=(pad, pad)`` and ``norm``, writing the sample's slice of the batch; ``label_rotate``
+        likewise, int64 out.
+    Fills, defaults from the reference's config: ``rotate_fill`` (0, 0, 0) and ``lbl_rotate_fill`` 0 -- ``RandomRotation(30.)`` rotates
+    frame AND label with its ``fill`` (seg_transforms.py:424), not with ``lbl_fill``; ``fill`` 0 and ``lbl_fill`` 255 --
+    ``ConstantPad(512, lbl_fill=255)``.  A resized image larger than ``pad`` in either dimension raises ValueError (the reference would
+    return a ragged batch).  Returns ``(image float32 (B, 3, pad, pad), label int64 (B, pad, pad))``.  CPU tensors take the CPU
+    implementations (``utils.jitter`` / ``utils.resample`` / ``utils.rotate``): same values."""
+    import numpy as np
+    from . import functional as HF
+    from .utils import jitter as J
+    from .utils import resample, rotate
+    hwc = norm.layout == 'hwc'
+    if isinstance(frames, torch.Tensor):
+        norm.frame_size(frames)
+        frames = [frames[i] for i in range(frames.shape[0])]
+    if isinstance(labels, torch.Tensor):
+        labels = [labels[i] for i in range(labels.shape[0])]
+    frames, labels = list(frames), list(labels)
+    b = len(frames)
+    if b == 0 or len(labels) != b:
+        raise ValueError(f'frames and labels must hold the same number of samples (>= 1), got {b} and {len(labels)}')
+    pad = int(pad)
+
+    def per_sample(v):
+        seq = list(v) if isinstance(v, (list, tuple)) or getattr(v, 'ndim', 0) > 0 else [v] * b
+        if len(seq) != b:
+            raise ValueError('hflip, scale and angle take one value, or one per sample')
+        return seq
+    flips, scales, angles = per_sample(hflip), per_sample(scale), rotate.per_sample(angle, b)
+    jitters = None if jitter is None else J.per_sample(jitter, b)
+    device = frames[0].device
+    on_gpu = device.type == 'cuda'
+    plan = []
+    for i in range(b):
+        x, t = frames[i], labels[i]
+        if not isinstance(x, torch.Tensor) or x.dtype != torch.uint8 or x.dim() != 3 or x.shape[2 if hwc else 0] != 3:
+            raise ValueError(f'frame {i} must be uint8 {"(H, W, 3)" if hwc else "(3, H, W)"}, got '
+                             f'{getattr(x, "dtype", type(x))} {tuple(getattr(x, "shape", ()))}')
+        h, w = (int(s) for s in (x.shape[:2] if hwc else x.shape[1:]))
+        if not isinstance(t, torch.Tensor) or t.dtype not in (torch.uint8, torch.int64) or tuple(t.shape) != (h, w):
+            raise ValueError(f'label {i} must be uint8 or int64 {(h, w)}, got {getattr(t, "dtype", type(t))} {tuple(getattr(t, "shape", ()))}')
+        if x.device != device or t.device != device:
+            raise ValueError(f'sample {i} is on {x.device} / {t.device}, the first frame on {device}')
+        size = (h, w)
+        if scales[i] is not None and float(scales[i]) != 1.0:
+            size = tuple(int(s) for s in np.round(np.array((h, w)) * float(scales[i])).astype(int))
+        if min(size) < 1:
+            raise ValueError(f'sample {i}: scale {scales[i]} leaves nothing of {(h, w)}')
+        if size[0] > pad or size[1] > pad:
+            raise ValueError(f'sample {i}: the resized image {size} exceeds pad {pad}')
+        rotate._check_hw(h, w)
+        plan.append(((h, w), size))
+    image = torch.empty(b, 3, pad, pad, dtype=torch.float32, device=device)
+    label = torch.empty(b, pad, pad, dtype=torch.int64, device=device)
+    mirror = resample.ResizeView
+    for i, ((h, w), size) in enumerate(plan):
+        x, t = frames[i].contiguous()[None], labels[i].contiguous()[None]
+        if on_gpu:
+            if jitters is not None:
+                x = HF.color_jitter(x, jitters[i], norm.layout)
+            if flips[i]:
+                x = HF.frame_resize(x, (h, w), 'bicubic', norm.layout, view=mirror((h, w), (0, 0), True))
+                t = HF.label_resize(t, (h, w), view=mirror((h, w), (0, 0), True))
+            if size != (h, w):
+                x = HF.frame_resize(x, size, 'bicubic', norm.layout)
+                t = HF.label_resize(t, size)
+            HF.frame_rotate(x, angles[i], norm.layout, (pad, pad), rotate_fill, fill, norm=norm, out=image[i:i + 1])
+            HF.label_rotate(t, angles[i], (pad, pad), lbl_rotate_fill, lbl_fill, out=label[i:i + 1])
+        else:
+            if jitters is not None:
+                x = J.color_jitter_cpu(x, jitters[i], norm.layout)
+            if flips[i]:
+                x, t = x.flip(2 if hwc else 3), t.flip(2)
+            if size != (h, w):
+                x = resample.frame_resize_cpu(x, size, 'bicubic', norm.layout)
+                t = resample.label_resize_cpu(t, size)
+            image[i:i + 1] = rotate.frame_rotate_cpu(x, angles[i], norm.layout, (pad, pad), rotate_fill, fill, norm=norm)
+            label[i:i + 1] = rotate.label_rotate_cpu(t, angles[i], (pad, pad), lbl_rotate_fill, lbl_fill, out_dtype=torch.int64)
+    return image, label
+
+
 def draw_color_jitter(brightness=0.0, contrast=0.0, saturation=0.0, hue=0.0, generator=None):
     """One ``ColorJitterParams`` drawn with the ranges of ``torchvision.transforms.ColorJitter(brightness, contrast, saturation, hue)``:
     each of the three factors uniform in ``[max(0, 1 - x), 1 + x]``, hue uniform in ``[-x, x]`` (``x <= 0.5``), and a random order of the

@@ -548,6 +548,25 @@ int hs_label_resize_fwd(const void* x, int32_t in_dtype, int32_t batch, int32_t 
 #define HS_JITTER_TABLE_WORDS 8
 int hs_color_jitter_fwd(const uint8_t* x, int32_t layout, int32_t batch, int32_t H, int32_t W, const int32_t* table,
                         uint64_t* sums, const float* norm_table, void* y, void* stream);
+/* uint8 frames and labels rotated on the device with Pillow's arithmetic (csrc/hs_rotate.hip; the arithmetic: hyperseg_amd/utils/rotate.py):
+ * PIL.Image.rotate(angle, expand=False) about the centre, what the reference's RandomRotation runs (hyperseg/datasets/seg_transforms.py:
+ * 384-426), and the ConstantPad after it (:181-217) as a VIEW: the output is (Ho, Wo), the rotated (H, W) image at its top-left corner, a
+ * pad fill right of and below it (Ho < H or Wo < W simply shows less of the rotated image).  One size per launch, one transform per sample.
+ *   hs_frame_rotate_fwd: x uint8 (B, H, W, 3) | (B, 3, H, W) by layout; matrices float64 (B, 6), on the device: output pixel (x, y) reads
+ *     the source at ((m0 xi + m1 yi) + m2, (m3 xi + m4 yi) + m5), xi = x + 0.5, yi = y + 0.5 -- BICUBIC, Pillow's float64 4 x 4 filter
+ *     with truncation to the byte; outside the source the rotation fill (fill_rgb = r | g << 8 | b << 16).  norm_table null: y uint8 in
+ *     the input's layout; else y float32 (B, 3, Ho, Wo), every byte -- both fills included -- looked up in the (3, 256) table of
+ *     hs_image_ingest_fwd.  Any alignment of x and y (a float's 4 bytes for the float form).
+ *   hs_label_rotate_fwd: x (B, H, W) and y (B, Ho, Wo), each HS_EVAL_U8 or HS_EVAL_I64; fixed int32 (B, 6), on the device, Pillow's 16.16
+ *     coefficients: NEAREST, source (xs, ys) = ((a2 + y a1 + x a0) >> 16, (a5 + y a4 + x a3) >> 16), the fill outside.
+ * Both read their table when they RUN: a captured graph replays with what the table holds then.  No table can make an access leave the
+ * frame.  HS_ERR_UNSUPPORTED -- nothing launched -- for batch > 65535 or any of H, W, Ho, Wo above 8192 (up to there no intermediate of
+ * Pillow's 32-bit label arithmetic overflows).  Nothing is read back: capturable. */
+int hs_frame_rotate_fwd(const uint8_t* x, int32_t layout, int32_t batch, int32_t H, int32_t W, const double* matrices,
+                        int32_t Ho, int32_t Wo, uint32_t fill_rgb, uint32_t pad_fill_rgb, const float* norm_table,
+                        void* y, void* stream);
+int hs_label_rotate_fwd(const void* x, int32_t in_dtype, int32_t batch, int32_t H, int32_t W, const int32_t* fixed,
+                        int32_t Ho, int32_t Wo, int32_t fill, int32_t pad_fill, void* y, int32_t out_dtype, void* stream);
 int hs_mbconv_expand_dw_fwd(const float* x, int32_t batch, int32_t c_in, int32_t H, int32_t W,
                             const float* w_expand, int32_t c_mid, const float* scale0, const float* shift0,
                             const float* w_dw, int32_t k, int32_t stride, int32_t pad_t, int32_t pad_l,
