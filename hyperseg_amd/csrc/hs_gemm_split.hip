@@ -14,7 +14,13 @@
 //   per wave, K <= 1280).  A wave requests its whole slice of both 16-pixel strips at once (64-byte runs across the pixel
 //   lanes), applies the gate, scales each PIXEL's column by a power of two to < 2^15 (a column scale only scales that column
 //   of D: undone on the lane's own accumulators) and splits it into hi / lo.  Three products per k-step (lo*hi, hi*lo, hi*hi):
-//   error 1.6-2.9e-7 of the f64 product at the encoder's shapes, below the library f32 GEMM's 4.5e-7-1.2e-6.
+//   error 1.6-2.9e-7 of the f64 product at the encoder's shapes, below the library f32 GEMM's 4.5e-7-1.2e-6.  Per element the result
+//   is held to a derived bound relative to sum_k |w||g x| (tests/util_split_ref.py).  The exponent clamp [27, 254] keeps
+//   both scales normal floats: columns (and rows) below 2^-100, f32 subnormals included, are scaled by 2^114 only and keep an
+//   ABSOLUTE error floor of 2^-40 R_m C in place of the relative one (binary16 subnormals are kept by the split and the matrix cores).
+//   RANGE: the partial sums are in row-scaled units (row maximum in [2^14, 2^15)) until w_inv is applied, so 2^15 sum_k |w/R_m||g x|
+//   must stay below 2^127 -- inputs up to about 2^112 / K against a row's largest weights.  Beyond that the result is inf / NaN even
+//   where the exact product would fit an f32; a non-finite x[k][n] makes pixel column n non-finite and leaves every other column alone.
 // * the waves' partial tiles meet in LDS, are summed in wave order (deterministic), scaled by w_inv[row], get the BatchNorm
 //   shift, the activation and the residual, and are stored as 128-byte runs; the tail's operands are requested before the
 //   barrier.  (The probed dev kernel had only the accumulate-onto-Y tail; shift / activation / separate residual are new.)
@@ -86,7 +92,9 @@ void gemm_split_kernel(GemmSplitArgs a) {
     // eight): 50 -> 22 vector-memory instructions per wave at KS = 1 (tools/isa_phases.py) -- these launches are bound by the
     // per-instruction cost of the CU's address path, not by bytes.  N is even and n0 a multiple of 32, so the pair is aligned.
     using gs_f32x2 = __attribute__((ext_vector_type(2))) float;
-    const int ncol0 = min(n0 + NS * lrow, a.N - 1), ncol1 = min(n0 + NS * lrow + 1, a.N - 1);
+    // a ragged block's dead lanes re-read the LAST pair (N - 2, N - 1) in the paired form: clamped to N - 1 their 8-byte load started at
+    // the row's last element and, in the last k-row of the last frame, took its second half from past the end of x
+    const int ncol0 = min(n0 + NS * lrow, a.N - (FAST && !PATCH && NS == 2 ? 2 : 1)), ncol1 = min(n0 + NS * lrow + 1, a.N - 1);
     float xv[NCH][NS][KS][8];
     if constexpr (PATCH) {
         const int oy = ncol0 / a.conv_wo, ox = ncol0 - oy * a.conv_wo;     // NS = 2: Wo even, so ncol1 is the next pixel of the row
@@ -434,7 +442,7 @@ extern "C" int hs_pooled_shift_fwd(const float* partial, int32_t nblk, float inv
 
 // Conv2d(c_in, c_out, kernel 2, stride 2, no padding) on x (B, c_in, 2 Ho, 2 Wo) -> y (B, c_out, Ho, Wo) as the same GEMM with
 // K = 4 c_in read through the window (the context head's down blocks, hyperseg_v1_0.py:396-401): w_frag / w_inv from the conv
-// weight flattened to (c_out, 4 c_in), kp = hs_gemm_split_kp(4 c_in).  64 <= c_in <= 640; Wo even.  pool_partial (optional):
+// weight flattened to (c_out, 4 c_in), kp = hs_gemm_split_kp(4 c_in).  34 <= c_in <= 640 (8 waves); c_in and Wo even.  pool_partial (optional):
 // [B][c_out][ceil(Ho Wo / 16)] sums of y over the 16-pixel blocks, for hs_pooled_shift_fwd (the global average without a launch).
 extern "C" int hs_gemm_split_conv2x2_fwd(const void* w_frag, const float* w_inv, const float* x, const float* shift, int32_t act,
                                          float* y, float* pool_partial, int32_t batch, int32_t c_out, int32_t c_in, int32_t kp,

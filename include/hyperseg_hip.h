@@ -600,7 +600,11 @@ int hs_affine_act_fwd(const float* x, int32_t batch, int32_t channels, int32_t p
  * w_frag / w_inv: the STATIC weight split once on the host into two f16 pieces of every row scaled by a power of two to
  * < 2^15, in MFMA-fragment order [ceil(Cout/16)][kp/32][piece][64 lanes][8] (lane = row % 16 + 16 * kgroup holds
  * w[16 R + row % 16][32 S + 8 kgroup + j]), and the inverse row scales padded to a multiple of 16 rows
- * (hyperseg_amd.functional.gemm_split_weights builds both).  kp = hs_gemm_split_kp(Cin): Cin rounded up to the workgroup's
+ * (hyperseg_amd.functional.gemm_split_weights builds both).  Accuracy: per element within a few 2^-22 of sum_c |w||gate x| plus
+ * the f32 summation (the derived bound: tests/util_split_ref.py).  Range: finite inputs give finite results while
+ * 2^15 * sum_c |w[o,c] / R_o| |gate x| < 2^127, R_o = the power of two above row o's maximum (partial sums are kept in row-scaled
+ * units); beyond that y is inf / NaN although the exact value may fit.  Magnitudes below 2^-100 (f32 subnormals included) are
+ * accepted with an absolute error floor.  A non-finite x[b,c,p] makes y[b,:,p] non-finite and changes no other pixel.  kp = hs_gemm_split_kp(Cin): Cin rounded up to the workgroup's
  * K split (HS_ERR_UNSUPPORTED for Cin > 2560; hs_gemm_split_fwd itself takes Cin <= 1280, the deeper K is the 2x2 form's).  Replaces the library GEMM of an MBConv block's expand / project convolution
  * (efficientnet.py:101, 115) and, through `gate`, the SE multiply (:110-111). */
 int hs_gemm_split_kp(int32_t c_in);
@@ -609,7 +613,7 @@ int hs_gemm_split_fwd(const void* w_frag, const float* w_inv, const float* gate,
                       int32_t pixels, void* stream);
 /* Conv2d(c_in, c_out, kernel 2, stride 2, no padding, no bias) + shift + act with the same arithmetic: x (B,c_in,2Ho,2Wo) ->
  * y (B,c_out,Ho,Wo), the window read on load (K = 4 c_in, k = 4 c + 2 dy + dx: the conv weight's own flatten order; no im2col
- * copy).  w_frag / w_inv from the (c_out, 4 c_in) weight, kp = hs_gemm_split_kp(4 c_in); 64 <= c_in <= 640, c_in and Wo even,
+ * copy).  w_frag / w_inv from the (c_out, 4 c_in) weight, kp = hs_gemm_split_kp(4 c_in); 34 <= c_in <= 640, c_in and Wo even,
  * x 16-byte aligned, else HS_ERR_UNSUPPORTED.  pool_partial (optional): (B, c_out, ceil(Ho Wo / 16)) sums of y over blocks of 16
  * consecutive pixels -- the global average pool that follows, without a launch of its own (hs_pooled_shift_fwd reads it).
  * Replaces F.conv2d + BatchNorm + ReLU of the context head's down blocks (hyperseg_v1_0.py:396-401). */
