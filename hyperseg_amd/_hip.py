@@ -178,6 +178,9 @@ def _load():
         'hs_upsample_overlay_fwd': ([vp, i32, i32, i32, i32, i32, i32, vp, i32, vp, i32, i32, vp, vp, vp], C.c_int),
         'hs_frame_resize_fwd': ([vp, i32, i32, i32, i32, vp, vp, i32, i32, vp, vp, i32, i32, i32, i32, i32, i32, i32, C.c_uint32, vp, vp, vp], C.c_int),
         'hs_label_resize_fwd': ([vp, i32, i32, i32, i32, vp, i32, vp, i32, i32, i32, i32, i32, i32, i32, vp, i32, vp], C.c_int),
+        'hs_resize_tables_fwd': ([vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp], C.c_int),
+        'hs_frame_resize_batch_fwd': ([vp, i32, i32, i32, i32, vp, vp, vp, vp, i32, i32, i32, C.c_uint32, vp, vp, vp], C.c_int),
+        'hs_label_resize_batch_fwd': ([vp, i32, i32, i32, i32, vp, vp, vp, i32, i32, i32, vp, i32, vp], C.c_int),
         'hs_color_jitter_fwd': ([vp, i32, i32, i32, i32, vp, vp, vp, vp, vp], C.c_int),
         'hs_frame_rotate_fwd': ([vp, i32, i32, i32, i32, vp, i32, i32, C.c_uint32, C.c_uint32, vp, vp, vp], C.c_int),
         'hs_label_rotate_fwd': ([vp, i32, i32, i32, i32, vp, i32, i32, i32, i32, vp, i32, vp], C.c_int),
@@ -206,7 +209,7 @@ EXPORTS = ['hs_version', 'hs_build_info', 'hs_signal2weights_fwd', 'hs_signal2we
            'hs_bn_act_train_bwd', 'hs_dw_tiles_bn_bwd_in_partials', 'hs_dw_tiles_bn_bwd_in', 'hs_bn_act_train_bwd_apply', 'hs_patch_conv_plain_fwd', 'hs_patch_conv_plain_bwd_in', 'hs_patch_conv_plain_bwd_w',
            'hs_upsample_bilinear_f16_fwd', 'hs_adam_step_amp', 'hs_eval_max_classes', 'hs_upsample_confusion_fwd', 'hs_confusion_fwd', 'hs_upsample2_confusion_fwd',
            'hs_image_ingest_fwd', 'hs_stem_dw_u8_fwd', 'hs_overlay_fwd', 'hs_upsample_overlay_fwd',
-           'hs_frame_resize_fwd', 'hs_label_resize_fwd', 'hs_color_jitter_fwd', 'hs_frame_rotate_fwd', 'hs_label_rotate_fwd',
+           'hs_frame_resize_fwd', 'hs_label_resize_fwd', 'hs_resize_tables_fwd', 'hs_frame_resize_batch_fwd', 'hs_label_resize_batch_fwd', 'hs_color_jitter_fwd', 'hs_frame_rotate_fwd', 'hs_label_rotate_fwd',
            'hs_cross_entropy_score_fwd', 'hs_upsample_ce_confusion_fwd']
 
 

@@ -15,22 +15,16 @@
 //     planar layout.  A position of the view outside the resized image is the fill byte, through the table as well.
 // Neighbouring threads read overlapping windows of the same source rows: L1 / L2 traffic, HBM sees each source byte about
 // (1 + 2 support / (RS_TY scale)) times.  Bounds read from the tables are clamped to the source, so a wrong table cannot leave the frame.
+// The per-pixel code (the streaming loop, the epilogue) lives in hs_resample_px.h, shared with the batched launch of hs_resample_batch.hip.
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include <climits>
 #include "hyperseg_hip.h"
 #include "hs_common.h"
 #include "hs_ingest.h"
+#include "hs_resample_px.h"
 
 namespace hs {
-
-constexpr int RS_BITS = 22;                    // Pillow's PRECISION_BITS for 8-bit images
-constexpr int RS_HALF = 1 << (RS_BITS - 1);
-constexpr int RS_COLS = 64;                    // output columns per wave
-constexpr int RS_GROUPS = 4;                   // waves per workgroup, each with its own rows
-constexpr int RS_TY = 4;                       // output rows per thread
-constexpr int RS_XREG = 8;                     // horizontal taps kept in registers
-constexpr int RS_MAX_DIM = 1 << 19;            // any frame or view dimension (the grid's y extent stays below 65536)
 
 struct ResizeArgs {
     const uint8_t* x; void* y; const float* table;
@@ -38,14 +32,6 @@ struct ResizeArgs {
     int Hi, Wi, Hr, Wr, Ho, Wo, oy, ox, yks, xks, hflip;
     unsigned fill;                             // r | g << 8 | b << 16
 };
-
-__device__ __forceinline__ int clip8(int v) { return min(max(v >> RS_BITS, 0), 255); }
-
-// first index and tap count of table row i, clamped to a source of `size` and a table of `ks` columns
-__device__ __forceinline__ void resize_bounds(const int32_t* __restrict__ bounds, int i, int size, int ks, int& first, int& n) {
-    first = min(max(bounds[2 * i], 0), size - 1);
-    n = max(min(min(bounds[2 * i + 1], ks), size - first), 0);
-}
 
 template <bool HWC, bool NORM, bool XREG>
 __global__ __launch_bounds__(RS_COLS * RS_GROUPS)
@@ -63,7 +49,7 @@ void frame_resize_kernel(const ResizeArgs a) {
     const bool col_in = rx >= 0 && rx < a.Wr;
 
     int ymin[RS_TY], yn[RS_TY], acc[RS_TY][INGEST_CHANNELS];
-    const int32_t* __restrict__ yk[RS_TY];
+    const int32_t* yk[RS_TY];
     bool row_in[RS_TY];
     int s0 = INT_MAX, s1 = 0;
 #pragma unroll
@@ -84,82 +70,11 @@ void frame_resize_kernel(const ResizeArgs a) {
         int xmin, xn;
         resize_bounds(a.xb, rx, a.Wi, a.xks, xmin, xn);
         const int32_t* __restrict__ xk = a.xkk + (size_t)rx * a.xks;
-        int wx[RS_XREG];
-        if constexpr (XREG) {
-#pragma unroll
-            for (int k = 0; k < RS_XREG; ++k) wx[k] = k < xn ? xk[k] : 0;
-        }
         const size_t plane = (size_t)a.Hi * a.Wi;
-        for (int sy = s0; sy < s1; ++sy) {
-            int h[INGEST_CHANNELS] = {RS_HALF, RS_HALF, RS_HALF};
-            if constexpr (HWC) {
-                const uint8_t* __restrict__ p = a.x + (b * plane + (size_t)sy * a.Wi + xmin) * 3;
-                if constexpr (XREG) {
-#pragma unroll
-                    for (int k = 0; k < RS_XREG; ++k) {
-                        if (k < xn) {
-#pragma unroll
-                            for (int c = 0; c < INGEST_CHANNELS; ++c) h[c] += (int)p[3 * k + c] * wx[k];
-                        }
-                    }
-                } else {
-                    for (int k = 0; k < xn; ++k) {
-                        const int w = xk[k];
-#pragma unroll
-                        for (int c = 0; c < INGEST_CHANNELS; ++c) h[c] += (int)p[3 * k + c] * w;
-                    }
-                }
-            } else {
-                const uint8_t* __restrict__ p = a.x + b * INGEST_CHANNELS * plane + (size_t)sy * a.Wi + xmin;
-                if constexpr (XREG) {
-#pragma unroll
-                    for (int k = 0; k < RS_XREG; ++k) {
-                        if (k < xn) {
-#pragma unroll
-                            for (int c = 0; c < INGEST_CHANNELS; ++c) h[c] += (int)p[c * plane + k] * wx[k];
-                        }
-                    }
-                } else {
-                    for (int k = 0; k < xn; ++k) {
-                        const int w = xk[k];
-#pragma unroll
-                        for (int c = 0; c < INGEST_CHANNELS; ++c) h[c] += (int)p[c * plane + k] * w;
-                    }
-                }
-            }
-#pragma unroll
-            for (int c = 0; c < INGEST_CHANNELS; ++c) h[c] = clip8(h[c]);          // Pillow's uint8 intermediate
-#pragma unroll
-            for (int r = 0; r < RS_TY; ++r) {
-                const int k = sy - ymin[r];
-                if ((unsigned)k < (unsigned)yn[r]) {
-                    const int w = yk[r][k];
-#pragma unroll
-                    for (int c = 0; c < INGEST_CHANNELS; ++c) acc[r][c] += h[c] * w;
-                }
-            }
-        }
+        resize_accumulate<HWC, XREG>(a.x + b * INGEST_CHANNELS * plane, plane, a.Wi, xmin, xn, xk, s0, s1, ymin, yn, yk, acc);
     }
 
-    const size_t oplane = (size_t)a.Ho * a.Wo;
-#pragma unroll
-    for (int r = 0; r < RS_TY; ++r) {
-        const int y = y0 + r;
-        if (y >= a.Ho) break;
-        const bool inside = col_in && row_in[r];
-        const size_t pix = (size_t)y * a.Wo + x;
-#pragma unroll
-        for (int c = 0; c < INGEST_CHANNELS; ++c) {
-            const unsigned v = inside ? (unsigned)clip8(acc[r][c]) : (a.fill >> (8 * c)) & 255u;
-            if constexpr (NORM) {
-                static_cast<float*>(a.y)[(b * INGEST_CHANNELS + c) * oplane + pix] = ingest_dequant(tab, c, v);
-            } else if constexpr (HWC) {
-                static_cast<uint8_t*>(a.y)[(b * oplane + pix) * 3 + c] = (uint8_t)v;
-            } else {
-                static_cast<uint8_t*>(a.y)[(b * INGEST_CHANNELS + c) * oplane + pix] = (uint8_t)v;
-            }
-        }
-    }
+    resize_store<HWC, NORM>(a.y, tab, b, a.Ho, a.Wo, x, y0, col_in, row_in, acc, a.fill);
 }
 
 template <bool HWC, bool NORM>

@@ -5,6 +5,7 @@ Vocabulary: a *bank* is the patch-major per-patch filter b
 [coords | skip | resized previous level] that the reference materialises with torch.cat
 (hyperseg_v1_0.py:231-240) and the kernels generate on the fly.
 """
+import collections
 import ctypes as C
 import functools
 import os
@@ -1663,6 +1664,144 @@ def label_resize(t, size, view=None, fill=255, out=None):
                                       ho, wo, oy, ox, int(view.hflip), fill, _hip.dev_ptr(out, 'out', out.dtype), _LABEL_DTYPES[out.dtype],
                                       _hip.stream_ptr())
     _hip.check(st, 'hs_label_resize_fwd')
+    return out
+
+
+_FILTER_CODES = {'bilinear': 0, 'bicubic': 1}              # HS_RESIZE_* of include/hyperseg_hip.h
+RESIZE_STATUS = {'hr': 1, 'wr': 2, 'y_taps': 4, 'x_taps': 8, 'size': 16}      # HS_RESIZE_STATUS_*: what a sample's status word sums
+RESIZE_PARAM_WORDS = 6                                     # Hr, Wr, oy, ox, hflip, reserved
+
+
+class ResizeTables(collections.namedtuple('ResizeTables', 'bounds kk nearest status workspace in_hw crop ks_max')):
+    """The device-built tables of a batch (:func:`resize_tables`): int32 views of one ``workspace`` -- ``bounds`` (B, 2, M, 2), ``kk``
+    (B, 2, M, ks_max), ``nearest`` (B, 2, M), ``status`` (B,), M = max(crop), axis 0 = y -- and the geometry they were laid out for."""
+    __slots__ = ()
+
+    @staticmethod
+    def words(batch, crop, ks_max):
+        return batch * 2 * max(crop) * (3 + ks_max) + batch
+
+    @classmethod
+    def over(cls, workspace, batch, in_hw, crop, ks_max):
+        m = max(crop)
+        sizes = (batch * 2 * m * 2, batch * 2 * m * ks_max, batch * 2 * m, batch)
+        b, k, n, s = torch.split(workspace[:sum(sizes)], sizes)
+        return cls(b.view(batch, 2, m, 2), k.view(batch, 2, m, ks_max), n.view(batch, 2, m), s, workspace, tuple(in_hw), tuple(crop), ks_max)
+
+
+def _resize_params(params):
+    if (not isinstance(params, torch.Tensor) or params.dtype != torch.int32 or params.dim() != 2 or params.shape[1] != RESIZE_PARAM_WORDS
+            or params.shape[0] == 0 or not params.is_contiguous()):
+        raise ValueError(f'params must be a contiguous int32 tensor of shape (B, {RESIZE_PARAM_WORDS}) = Hr, Wr, oy, ox, hflip, reserved; got '
+                         f'{getattr(params, "dtype", type(params))} {tuple(getattr(params, "shape", ()))}')
+    return params.shape[0]
+
+
+def _batch_tables(tables, params, in_hw, device):
+    b = _resize_params(params)
+    if not isinstance(tables, ResizeTables):
+        raise ValueError('tables must be what resize_tables returned')
+    if params.device != device or tables.workspace.device != device:
+        raise ValueError(f'params and tables must be on {device}')
+    if tables.status.shape[0] != b or tables.in_hw != tuple(in_hw):
+        raise ValueError(f'the tables were built for {tables.status.shape[0]} samples of {tables.in_hw}, these are {b} of {tuple(in_hw)}')
+    return b
+
+
+@_on_operand_device
+def resize_tables(params, in_hw, crop, filter, ks_max, workspace=None):
+    """The resize tables of a whole batch built on the device, one launch (hs_resize_tables_fwd).  ``params``: int32 (B, 6) on the
+    device = ``Hr, Wr, oy, ox, hflip, reserved`` per sample -- the resized size, the signed offset of the ``crop`` = (h, w) window in the
+    resized image, its flip; ``in_hw`` the frames' (H, W); ``filter`` 'bilinear' | 'bicubic'; ``ks_max`` the tables' row width
+    (``utils.resample.ks_for``).  Returns a :class:`ResizeTables` over ``workspace`` (int32, contiguous, at least
+    ``ResizeTables.words(B, crop, ks_max)`` elements; default a new one): the window of ``utils.resample``'s host tables, integer for
+    integer (``utils.resample.window_tables_cpu``).  ``status``: 0 per sample, or a sum of ``RESIZE_STATUS`` codes (a resized size
+    below 1 or above 2^19, more taps than ``ks_max``) -- that sample's tables are empty and the resize launches write fill.  ``params`` is
+    read when the kernel runs and nothing is read back: capturable."""
+    from .utils import resample
+    b = _resize_params(params)
+    if filter not in resample.FILTERS:
+        raise ValueError(f'filter {filter!r}: expected one of {resample.FILTERS}')
+    hi, wi = (int(s) for s in in_hw)
+    ho, wo = (int(s) for s in crop)
+    ks_max = int(ks_max)
+    if min(hi, wi, ho, wo, ks_max) < 1:
+        raise ValueError(f'sizes must be >= 1, got {(hi, wi)} -> {(ho, wo)}, ks_max {ks_max}')
+    words = ResizeTables.words(b, (ho, wo), ks_max)
+    if workspace is None:
+        workspace = torch.empty(words, device=params.device, dtype=torch.int32)
+    elif (not isinstance(workspace, torch.Tensor) or workspace.dtype != torch.int32 or workspace.dim() != 1 or workspace.numel() < words
+          or workspace.device != params.device or not workspace.is_contiguous()):
+        raise ValueError(f'workspace must be a contiguous int32 vector of at least {words} elements on {params.device}')
+    t = ResizeTables.over(workspace, b, (hi, wi), (ho, wo), ks_max)
+    st = _hip.lib.hs_resize_tables_fwd(_hip.dev_ptr(params, 'params', torch.int32), b, hi, wi, ho, wo, _FILTER_CODES[filter], ks_max,
+                                       t.bounds.data_ptr(), t.kk.data_ptr(), t.nearest.data_ptr(), t.status.data_ptr(), _hip.stream_ptr())
+    _hip.check(st, 'hs_resize_tables_fwd')
+    return t
+
+
+@_on_operand_device
+def frame_resize_batch(x_u8, params, tables, layout='hwc', fill=(0, 0, 0), norm=None, out=None):
+    """:func:`frame_resize` for a batch whose samples each have a geometry of their own, one launch (hs_frame_resize_batch_fwd): sample
+    b of the uint8 frames (B, Hi, Wi, 3) / (B, 3, Hi, Wi) is resized to ``params[b]``'s (Hr, Wr) with the filter ``tables`` (a
+    :class:`ResizeTables` built from the same ``params``) were made for, and the ``tables.crop`` window at its offset comes back, flipped
+    where it says, ``fill`` (3 bytes) outside.  Returns uint8 in the input's layout, or with ``norm`` float32 (B, 3, h, w) through its
+    table; ``out`` as :func:`frame_resize`'s.  Per sample the bytes of ``frame_resize(x[b:b+1], (Hr, Wr), view=...)``.  Capturable."""
+    if layout not in _LAYOUT_CODES:
+        raise ValueError(f'layout {layout!r}: expected one of {tuple(_LAYOUT_CODES)}')
+    if not isinstance(x_u8, torch.Tensor) or x_u8.dtype != torch.uint8 or x_u8.dim() != 4 or x_u8.shape[3 if layout == 'hwc' else 1] != 3:
+        raise ValueError(f'frames must be uint8 {"(B, H, W, 3)" if layout == "hwc" else "(B, 3, H, W)"}, got '
+                         f'{getattr(x_u8, "dtype", type(x_u8))} {tuple(getattr(x_u8, "shape", ()))}')
+    if norm is not None and norm.layout != layout:
+        raise ValueError(f"norm describes '{norm.layout}' frames, these are '{layout}'")
+    hi, wi = (int(s) for s in (x_u8.shape[1:3] if layout == 'hwc' else x_u8.shape[2:]))
+    b = _batch_tables(tables, params, (hi, wi), x_u8.device)
+    if x_u8.shape[0] != b:
+        raise ValueError(f'{x_u8.shape[0]} frames, {b} parameter rows')
+    ho, wo = tables.crop
+    fill = tuple(int(f) for f in (fill if isinstance(fill, (tuple, list)) else (fill,) * 3))
+    if len(fill) != 3 or any(not 0 <= f <= 255 for f in fill):
+        raise ValueError(f'fill must be 3 bytes, got {fill!r}')
+    if norm is not None:
+        shape, dtype = (b, 3, ho, wo), torch.float32
+    else:
+        shape, dtype = ((b, ho, wo, 3) if layout == 'hwc' else (b, 3, ho, wo)), torch.uint8
+    if out is None:
+        out = torch.empty(shape, device=x_u8.device, dtype=dtype)
+    elif not isinstance(out, torch.Tensor) or tuple(out.shape) != shape or out.dtype != dtype or out.device != x_u8.device:
+        raise ValueError(f'out must be a {dtype} tensor of shape {shape} on {x_u8.device}')
+    st = _hip.lib.hs_frame_resize_batch_fwd(_hip.dev_ptr(x_u8, 'x_u8', torch.uint8), _LAYOUT_CODES[layout], b, hi, wi,
+                                            _hip.dev_ptr(params, 'params', torch.int32), tables.bounds.data_ptr(), tables.kk.data_ptr(),
+                                            tables.status.data_ptr(), tables.ks_max, ho, wo, fill[0] | fill[1] << 8 | fill[2] << 16,
+                                            None if norm is None else _hip.dev_ptr(norm.table(x_u8.device), 'table'),
+                                            _hip.dev_ptr(out, 'out', dtype), _hip.stream_ptr())
+    _hip.check(st, 'hs_frame_resize_batch_fwd')
+    return out
+
+
+@_on_operand_device
+def label_resize_batch(t, params, tables, fill=255, out=None):
+    """:func:`label_resize` for a batch whose samples each have a geometry of their own, one launch (hs_label_resize_batch_fwd):
+    labels (B, Hi, Wi), uint8 or int64, through ``tables``' nearest indices, the ``tables.crop`` window of each sample with ``fill``
+    outside.  Returns the input's dtype, or ``out``'s (uint8 | int64, contiguous, (B, h, w)).  Capturable."""
+    if not isinstance(t, torch.Tensor) or t.dtype not in _LABEL_DTYPES or t.dim() != 3:
+        raise ValueError(f'labels must be uint8 or int64 (B, H, W), got {getattr(t, "dtype", type(t))} {tuple(getattr(t, "shape", ()))}')
+    hi, wi = (int(s) for s in t.shape[1:])
+    b = _batch_tables(tables, params, (hi, wi), t.device)
+    if t.shape[0] != b:
+        raise ValueError(f'{t.shape[0]} labels, {b} parameter rows')
+    ho, wo = tables.crop
+    if out is None:
+        out = torch.empty((b, ho, wo), device=t.device, dtype=t.dtype)
+    elif not isinstance(out, torch.Tensor) or tuple(out.shape) != (b, ho, wo) or out.dtype not in _LABEL_DTYPES or out.device != t.device:
+        raise ValueError(f'out must be a uint8 or int64 tensor of shape {(b, ho, wo)} on {t.device}')
+    fill = int(fill)
+    if not (0 <= fill <= 255 or (out.dtype == torch.int64 and -2 ** 31 <= fill < 2 ** 31)):
+        raise ValueError(f'fill {fill} does not fit the output labels')
+    st = _hip.lib.hs_label_resize_batch_fwd(_hip.dev_ptr(t, 'labels', t.dtype), _LABEL_DTYPES[t.dtype], b, hi, wi,
+                                            _hip.dev_ptr(params, 'params', torch.int32), tables.nearest.data_ptr(), tables.status.data_ptr(),
+                                            ho, wo, fill, _hip.dev_ptr(out, 'out', out.dtype), _LABEL_DTYPES[out.dtype], _hip.stream_ptr())
+    _hip.check(st, 'hs_label_resize_batch_fwd')
     return out
 
 

@@ -483,6 +483,172 @@ def device_augment(frames_u8, labels, scale, crop, offset, hflip, norm, lbl_fill
     return image, label
 
 
+class BatchAugment:
+    """:func:`device_augment` for training, where RandomResize draws a new scale for every sample: the same chain, the same bytes, in a
+    fixed THREE launches per batch -- ``functional.resize_tables`` builds every sample's resize tables on the device, then
+    ``functional.frame_resize_batch`` and ``functional.label_resize_batch`` resize the whole batch -- where ``device_augment`` builds four
+    tables per new (in, out) pair on the host, uploads and keeps them, and launches twice per sample.  No host table build, no
+    synchronisation, nothing cached; every per-sample parameter sits in one small device tensor that the kernels read when they run, so
+    :meth:`run` can be captured once and replayed with new parameters.
+
+    ``in_hw``: the frames' (H, W); ``crop``: (h, w) of the result; ``norm``: the ``InputNorm`` (its layout is the frames');
+    ``scale_range``: (lo, hi) of the scales that will be asked for -- ``lo`` sizes the tables' rows (``utils.resample.ks_for``);
+    ``filter``: the frames' filter (``device_augment`` is 'bicubic'); ``lbl_fill`` / ``fill``: the padding; ``batch``: the batch size, or
+    None = the first call's.  The object owns the workspace, the ``params`` tensor (int32 (B, 6) = Hr, Wr, oy, ox, hflip, reserved) and a
+    pinned staging buffer, all made at the first GPU call.  One object serves one stream at a time."""
+
+    def __init__(self, in_hw, crop, norm, scale_range, filter='bicubic', lbl_fill=255, fill=(0, 0, 0), batch=None):
+        from .utils import resample
+        self.in_hw = tuple(int(s) for s in in_hw)
+        self.crop = tuple(int(s) for s in crop)
+        if len(self.in_hw) != 2 or len(self.crop) != 2 or min(self.in_hw + self.crop) < 1:
+            raise ValueError(f'in_hw and crop must be two sizes >= 1, got {in_hw} and {crop}')
+        lo, hi = (float(s) for s in scale_range)
+        if not 0.0 < lo <= hi:
+            raise ValueError(f'scale_range must be 0 < lo <= hi, got {scale_range}')
+        if filter not in resample.FILTERS:
+            raise ValueError(f'filter {filter!r}: expected one of {resample.FILTERS}')
+        if batch is not None and int(batch) < 1:
+            raise ValueError(f'batch must be >= 1, got {batch}')
+        self.norm, self.scale_range, self.filter, self.lbl_fill, self.fill = norm, (lo, hi), filter, int(lbl_fill), fill
+        self.batch = None if batch is None else int(batch)
+        smallest = self._resized(lo)
+        if min(smallest) < 1:
+            raise ValueError(f'scale {lo} leaves nothing of {self.in_hw}')
+        # ks_for is the rule; rounding the resized size down can make the true ratio a little larger than 1 / lo
+        self.ks_max = max(resample.ks_for(filter, lo), *(resample.ksize_of(i, o, filter) for i, o in zip(self.in_hw, smallest)))
+        self.params = self.tables = self._staging = self._copied = None
+
+    def _resized(self, scale):
+        import numpy as np
+        return tuple(int(s) for s in np.round(np.array(self.in_hw) * float(scale)).astype(int))
+
+    @property
+    def status(self):
+        """int32 (B,) on the device: 0, or the sum of ``functional.RESIZE_STATUS`` codes of a sample whose parameters the table launch
+        declined (that sample is fill).  Reading it synchronises; the caller chooses when."""
+        return None if self.tables is None else self.tables.status
+
+    @property
+    def workspace(self):
+        return None if self.tables is None else self.tables.workspace
+
+    def _check(self, frames_u8, labels):
+        b, h, w = self.norm.frame_size(frames_u8)
+        if (h, w) != self.in_hw:
+            raise ValueError(f'frames are {(h, w)}, this BatchAugment was made for {self.in_hw}')
+        if not isinstance(labels, torch.Tensor) or tuple(labels.shape) != (b, h, w) or labels.device != frames_u8.device:
+            raise ValueError(f'labels must be (B, H, W) = {(b, h, w)} on {frames_u8.device}, got {tuple(getattr(labels, "shape", ()))}')
+        if self.batch is None:
+            self.batch = b
+        if b != self.batch:
+            raise ValueError(f'{b} frames, this BatchAugment holds batches of {self.batch}')
+        return b
+
+    def _on(self, device):
+        from . import functional as HF
+        if self.tables is None or self.params.device != device:
+            words = HF.ResizeTables.words(self.batch, self.crop, self.ks_max)
+            self.params = torch.zeros(self.batch, HF.RESIZE_PARAM_WORDS, dtype=torch.int32, device=device)
+            self.tables = HF.ResizeTables.over(torch.zeros(words, dtype=torch.int32, device=device), self.batch, self.in_hw, self.crop, self.ks_max)
+            self._staging = torch.zeros(self.batch, HF.RESIZE_PARAM_WORDS, dtype=torch.int32).pin_memory()
+            self._copied = torch.cuda.Event()
+            self.norm.table(device)
+
+    def rows(self, scale, offset, hflip, batch=None):
+        """The ``params`` rows of given augmentation parameters (each one value or a sequence of B, as ``device_augment``'s): a CPU int32
+        (B, 6) tensor.  A scale outside ``scale_range`` raises ValueError."""
+        b = self.batch if batch is None else batch
+
+        def per_sample(v, scalar):
+            return [v] * b if scalar(v) else list(v)
+        scales = per_sample(scale, lambda v: not isinstance(v, (list, tuple)) and getattr(v, 'ndim', 0) == 0)
+        offsets = per_sample(offset, lambda v: len(v) == 2 and not isinstance(v[0], (list, tuple)) and getattr(v[0], 'ndim', 0) == 0)
+        flips = per_sample(hflip, lambda v: not isinstance(v, (list, tuple)) and getattr(v, 'ndim', 0) == 0)
+        if not len(scales) == len(offsets) == len(flips) == b:
+            raise ValueError('scale, offset and hflip take one value, or one per sample')
+        lo, hi = self.scale_range
+        rows = []
+        for s, o, f in zip(scales, offsets, flips):
+            if not lo <= float(s) <= hi:
+                raise ValueError(f'scale {float(s)} is outside scale_range {self.scale_range}')
+            rows.append(self._resized(s) + (int(o[0]), int(o[1]), int(bool(f)), 0))
+        return torch.tensor(rows, dtype=torch.int32)
+
+    def _cpu(self, frames_u8, labels, rows, jitter):
+        from .utils import resample
+        norm, (ch, cw) = self.norm, self.crop
+        b = frames_u8.shape[0]
+        uint8_shape = (b, ch, cw, 3) if norm.layout == 'hwc' else (b, 3, ch, cw)
+        dst = torch.empty(uint8_shape, dtype=torch.uint8) if jitter is not None else torch.empty(b, 3, ch, cw, dtype=torch.float32)
+        label = torch.empty(b, ch, cw, dtype=torch.int64)
+        for i, (hr, wr, oy, ox, flip, _) in enumerate(rows.tolist()):
+            view = resample.ResizeView((ch, cw), (oy, ox), bool(flip), self.fill)
+            dst[i:i + 1] = resample.frame_resize_cpu(frames_u8[i:i + 1], (hr, wr), self.filter, norm.layout, view=view,
+                                                     norm=None if jitter is not None else norm)
+            label[i:i + 1] = resample.label_resize_cpu(labels[i:i + 1], (hr, wr), view=view, fill=self.lbl_fill, out_dtype=torch.int64)
+        if jitter is not None:
+            from .utils import jitter as J
+            dst = J.color_jitter_cpu(dst, J.per_sample(jitter, b), norm.layout, norm=norm)
+        return dst, label
+
+    def _launch(self, frames_u8, labels, params, dst, dst_norm, label):
+        from . import functional as HF
+        tables = HF.resize_tables(params, self.in_hw, self.crop, self.filter, self.ks_max, workspace=self.tables.workspace)
+        HF.frame_resize_batch(frames_u8, params, tables, self.norm.layout, fill=self.fill, norm=dst_norm, out=dst)
+        HF.label_resize_batch(labels, params, tables, fill=self.lbl_fill, out=label)
+
+    def run(self, frames_u8, labels, params=None, out=None):
+        """The three launches over whatever ``self.params`` (or the given device tensor of that shape) holds when they RUN: no host
+        state is read or written, so a captured ``run`` replays with the parameters last copied into the tensor.  ``frames_u8`` and
+        ``labels`` must be contiguous.  ``out``: ``(image, label)`` to write into.  Returns ``(image float32 (B, 3, h, w), label int64
+        (B, h, w))``.  Nothing checks the parameters on the host: a row the table launch declines sets :attr:`status`."""
+        b = self._check(frames_u8, labels)
+        if not frames_u8.is_cuda:
+            rows = self.params if params is None else params
+            if rows is None:
+                raise ValueError('run on CPU tensors needs params')
+            return self._cpu(frames_u8, labels, rows, None)
+        self._on(frames_u8.device)
+        params = self.params if params is None else params
+        ch, cw = self.crop
+        if out is None:
+            image = torch.empty(b, 3, ch, cw, dtype=torch.float32, device=frames_u8.device)
+            label = torch.empty(b, ch, cw, dtype=torch.int64, device=frames_u8.device)
+        else:
+            image, label = out
+        self._launch(frames_u8, labels, params, image, self.norm, label)
+        return image, label
+
+    def __call__(self, frames_u8, labels, scale, offset, hflip, jitter=None):
+        """``device_augment(frames_u8, labels, scale, crop, offset, hflip, norm, lbl_fill, fill, jitter)``: same arguments, same
+        results.  The resized sizes are ``round((H, W) * scale)`` on the host; the parameters go up in one non-blocking copy."""
+        b = self._check(frames_u8, labels)
+        rows = self.rows(scale, offset, hflip, b)                # raises before any launch
+        if not frames_u8.is_cuda:
+            return self._cpu(frames_u8, labels, rows, jitter)
+        from . import functional as HF
+        self._on(frames_u8.device)
+        frames_u8, labels = frames_u8.contiguous(), labels.contiguous()
+        self._copied.synchronize()                               # the previous call's copy has left the staging buffer
+        self._staging.copy_(rows)
+        self.params.copy_(self._staging, non_blocking=True)
+        self._copied.record()
+        ch, cw = self.crop
+        image = torch.empty(b, 3, ch, cw, dtype=torch.float32, device=frames_u8.device)
+        label = torch.empty(b, ch, cw, dtype=torch.int64, device=frames_u8.device)
+        if jitter is None:
+            self._launch(frames_u8, labels, self.params, image, self.norm, label)
+        else:                                                    # the resize writes the uint8 crop, the jitter normalises
+            from .utils import jitter as J
+            jitter = J.per_sample(jitter, b)
+            layout = self.norm.layout
+            crop_u8 = torch.empty((b, ch, cw, 3) if layout == 'hwc' else (b, 3, ch, cw), dtype=torch.uint8, device=frames_u8.device)
+            self._launch(frames_u8, labels, self.params, crop_u8, None, label)
+            HF.color_jitter(crop_u8, jitter, layout, norm=self.norm, out=image)
+        return image, label
+
+
 def device_augment_voc(frames, labels, hflip, jitter, scale, angle, pad, norm, fill=(0, 0, 0), lbl_fill=255, rotate_fill=(0, 0, 0),
                        lbl_rotate_fill=0):
     """The reference's VOC-SBD train chain RandomHorizontalFlip -> ColorJitter -> RandomResize -> RandomRotation -> ConstantPad -> ToTensor

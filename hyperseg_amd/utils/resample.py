@@ -17,7 +17,11 @@ Tables, per axis:
 
 A *view* (:class:`ResizeView`) selects what is produced from the resized image (Hr, Wr): output pixel (y, x) of size (Ho, Wo) is resized
 pixel ``(oy + y, ox + (Wo - 1 - x if hflip else x))``, or ``fill`` where that lies outside -- resize -> pad -> crop -> flip of the train
-chain without resampling what the crop throws away."""
+chain without resampling what the crop throws away.
+
+For a training batch whose samples each draw a scale the device builds the same tables itself, the window of them that the crop reads
+(csrc/hs_resample_batch.hip, ``functional.resize_tables``): :func:`window_tables_cpu` is that layout from the host tables, its oracle,
+and :func:`ks_for` the row width for a range of scales."""
 import collections
 import functools
 import math
@@ -108,6 +112,49 @@ def nearest_index_closed_form(in_size, out_size):
     """``floor((i + 0.5) in / out)``: what Pillow's table is NOT (kept for the test that pins the difference)."""
     a = in_size / out_size
     return torch.from_numpy(np.minimum(np.floor((np.arange(out_size) + 0.5) * a).astype(np.int64), in_size - 1).astype(np.int32))
+
+
+def ks_for(filter, min_scale):
+    """The widest ``kk`` row of ``resample_coeffs(in, out, filter)`` for resize factors ``out / in >= min_scale``:
+    ``2 ceil(support / min(min_scale, 1)) + 1`` -- the ``ks_max`` of the device-built tables (``functional.resize_tables``)."""
+    if filter not in FILTERS:
+        raise ValueError(f'filter {filter!r}: expected one of {FILTERS}')
+    min_scale = float(min_scale)
+    if not min_scale > 0.0:
+        raise ValueError(f'min_scale must be > 0, got {min_scale}')
+    return int(math.ceil(_SUPPORT[filter] / min(min_scale, 1.0))) * 2 + 1
+
+
+def ksize_of(in_size, out_size, filter):
+    """Columns of ``resample_coeffs(in_size, out_size, filter)``'s ``kk`` without building it."""
+    in_size, out_size = _check_sizes(in_size, out_size)
+    return 1 if in_size == out_size else int(math.ceil(_SUPPORT[filter] * max(in_size / out_size, 1.0))) * 2 + 1
+
+
+WindowTables = collections.namedtuple('WindowTables', 'bounds kk nearest')
+
+
+def window_tables_cpu(in_size, out_size, start, extent, filter, ks_max):
+    """Rows ``start .. start + extent - 1`` of the host tables of one axis in the layout the device builds (csrc/hs_resample_batch.hip;
+    its oracle): ``bounds`` int32 (extent, 2), ``kk`` int32 (extent, ks_max) zero-padded, ``nearest`` int32 (extent,).  Row j is
+    resized index ``start + j``; a row outside ``[0, out_size)`` is (0, 0), zeros and 0."""
+    in_size, out_size = _check_sizes(in_size, out_size)
+    start, extent, ks_max = int(start), int(extent), int(ks_max)
+    if extent < 1:
+        raise ValueError(f'extent must be >= 1, got {extent}')
+    b, k = resample_coeffs(in_size, out_size, filter)
+    if k.shape[1] > ks_max:
+        raise ValueError(f'{in_size} -> {out_size} {filter} has {k.shape[1]} taps, ks_max is {ks_max}')
+    near = nearest_index(in_size, out_size)
+    bounds = torch.zeros(extent, 2, dtype=torch.int32)
+    kk = torch.zeros(extent, ks_max, dtype=torch.int32)
+    nearest = torch.zeros(extent, dtype=torch.int32)
+    lo, hi = max(start, 0), min(start + extent, out_size)
+    if lo < hi:
+        bounds[lo - start:hi - start] = b[lo:hi]
+        kk[lo - start:hi - start, :k.shape[1]] = k[lo:hi]
+        nearest[lo - start:hi - start] = near[lo:hi]
+    return WindowTables(bounds, kk, nearest)
 
 
 _DEVICE_TABLES = {}

@@ -532,6 +532,37 @@ int hs_label_resize_fwd(const void* x, int32_t in_dtype, int32_t batch, int32_t 
                         const int32_t* y_index, int32_t Hr, const int32_t* x_index, int32_t Wr,
                         int32_t Ho, int32_t Wo, int32_t oy, int32_t ox, int32_t hflip, int32_t fill,
                         void* y, int32_t out_dtype, void* stream);
+/* The same two resizes for a batch whose samples each have a geometry of their own (RandomResize draws a continuous scale), the
+ * tables built on the device (csrc/hs_resample_batch.hip): three launches per batch, nothing built or cached on the host.
+ * params: int32 (batch, 6) on the device = Hr, Wr, oy, ox, hflip, reserved -- the resized size, the signed offset of the (Ho, Wo)
+ * window in the resized image, the flip of the window; read when the kernels RUN, so a captured graph replays with what it holds then.
+ * Workspace, caller-owned int32, M = max(Ho, Wo), axis 0 = y, row j = window position, resized index r = o + j:
+ *   bounds (batch, 2, M, 2), kk (batch, 2, M, ks_max) zero-padded, nearest (batch, 2, M), status (batch).
+ *   hs_resize_tables_fwd: fills all four.  filter: HS_RESIZE_BILINEAR | HS_RESIZE_BICUBIC.  The integers equal
+ *     utils/resample.py's resample_coeffs / nearest_index rows o .. o + extent - 1 (float64 in the host's operation order; the
+ *     nearest table by Pillow's serial accumulation, one lane per sample and axis).  Rows with r outside [0, size_r), and rows past
+ *     the axis's extent, are (0, 0), zeros and 0.  status[b]: 0, or the sum of the HS_RESIZE_STATUS_* codes that apply -- Hr < 1,
+ *     Wr < 1, a resized size above 2^19, more taps than ks_max on an axis; such a sample's tables are all-empty.
+ *   hs_frame_resize_batch_fwd / hs_label_resize_batch_fwd: hs_frame_resize_fwd / hs_label_resize_fwd per sample, same bytes, one
+ *     launch for the batch; a sample with a non-zero status is fill everywhere, the others are not affected by it.
+ * Tap counts are clamped to ks_max and first indices to the source, table rows are addressed by window position only: no value in
+ * params can make an access leave the workspace or the frames.  HS_ERR_UNSUPPORTED -- nothing launched -- for batch > 65535, any of
+ * Hi, Wi, Ho, Wo above 2^19 or ks_max above 4096.  Nothing is read back: capturable. */
+#define HS_RESIZE_BILINEAR 0
+#define HS_RESIZE_BICUBIC 1
+#define HS_RESIZE_STATUS_HR 1
+#define HS_RESIZE_STATUS_WR 2
+#define HS_RESIZE_STATUS_Y_TAPS 4
+#define HS_RESIZE_STATUS_X_TAPS 8
+#define HS_RESIZE_STATUS_SIZE 16
+int hs_resize_tables_fwd(const int32_t* params, int32_t batch, int32_t Hi, int32_t Wi, int32_t Ho, int32_t Wo, int32_t filter,
+                         int32_t ks_max, int32_t* bounds, int32_t* kk, int32_t* nearest, int32_t* status, void* stream);
+int hs_frame_resize_batch_fwd(const uint8_t* x, int32_t layout, int32_t batch, int32_t Hi, int32_t Wi, const int32_t* params,
+                              const int32_t* bounds, const int32_t* kk, const int32_t* status, int32_t ks_max,
+                              int32_t Ho, int32_t Wo, uint32_t fill_rgb, const float* norm_table, void* y, void* stream);
+int hs_label_resize_batch_fwd(const void* x, int32_t in_dtype, int32_t batch, int32_t Hi, int32_t Wi, const int32_t* params,
+                              const int32_t* nearest, const int32_t* status, int32_t Ho, int32_t Wo, int32_t fill,
+                              void* y, int32_t out_dtype, void* stream);
 /* torchvision's ColorJitter on uint8 RGB frames with Pillow's bytes (csrc/hs_jitter.hip; the arithmetic: hyperseg_amd/utils/jitter.py):
  * up to four operations per sample, each on the uint8 result of the one before, in the order its record gives.
  * table: int32 (B, HS_JITTER_TABLE_WORDS), on the device, one record per sample -- word 0 the order, 4 bits per operation from the lowest
