@@ -184,6 +184,12 @@ def _load():
         'hs_color_jitter_fwd': ([vp, i32, i32, i32, i32, vp, vp, vp, vp, vp], C.c_int),
         'hs_frame_rotate_fwd': ([vp, i32, i32, i32, i32, vp, i32, i32, C.c_uint32, C.c_uint32, vp, vp, vp], C.c_int),
         'hs_label_rotate_fwd': ([vp, i32, i32, i32, i32, vp, i32, i32, i32, i32, vp, i32, vp], C.c_int),
+        'hs_resize_tables_ragged_fwd': ([vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp], C.c_int),
+        'hs_color_jitter_ragged_fwd': ([vp, i32, i32, i32, i32, vp, vp, vp, vp, vp], C.c_int),
+        'hs_frame_resize_ragged_fwd': ([vp, i32, i32, i32, i32, vp, vp, vp, vp, i32, i32, i32, vp, vp], C.c_int),
+        'hs_label_resize_ragged_fwd': ([vp, i32, i32, i32, i32, vp, vp, vp, i32, i32, vp, vp], C.c_int),
+        'hs_frame_rotate_ragged_fwd': ([vp, i32, i32, i32, i32, vp, vp, vp, i32, i32, C.c_uint32, C.c_uint32, vp, vp, vp], C.c_int),
+        'hs_label_rotate_ragged_fwd': ([vp, i32, i32, i32, vp, vp, vp, i32, i32, i32, i32, vp, i32, vp], C.c_int),
         'hs_mbconv_expand_dw_fwd': ([vp, i32, i32, i32, i32, vp, i32, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp], C.c_int),
         'hs_se_gate_fwd': ([vp, i32, i32, i32, C.c_float, vp, vp, i32, vp, vp, vp, vp, vp, i32, vp, vp, vp], C.c_int),
         'hs_gemm_split_kp': ([i32], C.c_int),
@@ -210,6 +216,7 @@ EXPORTS = ['hs_version', 'hs_build_info', 'hs_signal2weights_fwd', 'hs_signal2we
            'hs_upsample_bilinear_f16_fwd', 'hs_adam_step_amp', 'hs_eval_max_classes', 'hs_upsample_confusion_fwd', 'hs_confusion_fwd', 'hs_upsample2_confusion_fwd',
            'hs_image_ingest_fwd', 'hs_stem_dw_u8_fwd', 'hs_overlay_fwd', 'hs_upsample_overlay_fwd',
            'hs_frame_resize_fwd', 'hs_label_resize_fwd', 'hs_resize_tables_fwd', 'hs_frame_resize_batch_fwd', 'hs_label_resize_batch_fwd', 'hs_color_jitter_fwd', 'hs_frame_rotate_fwd', 'hs_label_rotate_fwd',
+           'hs_resize_tables_ragged_fwd', 'hs_color_jitter_ragged_fwd', 'hs_frame_resize_ragged_fwd', 'hs_label_resize_ragged_fwd', 'hs_frame_rotate_ragged_fwd', 'hs_label_rotate_ragged_fwd',
            'hs_cross_entropy_score_fwd', 'hs_upsample_ce_confusion_fwd']
 
 

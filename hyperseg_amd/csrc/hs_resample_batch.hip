@@ -9,8 +9,7 @@
 // hs_resize_tables_fwd, ONE launch, the tables of the WINDOW only (O(crop), not O(resized image)), in a caller-owned workspace,
 // M = max(Ho, Wo) rows per (sample, axis), axis 0 = y:
 //   * bounds (B, 2, M, 2) and kk (B, 2, M, ks_max), one thread per (sample, axis, j): utils/resample.py::resample_coeffs restated in
-//     its operation order, every float64 operation spelt __ddiv_rn / __dmul_rn / __dadd_rn (and the library is built with
-//     -ffp-contract=off), so the integers are the host's.  A tap is evaluated twice, for the sum and for the quotient: same bits;
+//     its operation order (hs_resample_tables.h, shared with the ragged launch of hs_augment_ragged.hip), so the integers are the host's;
 //   * nearest (B, 2, M): Pillow's table is the ACCUMULATION xo = 0.5 a; idx = (int)xo; xo += a, not a closed form, so it is serial
 //     from index 0 to the window's end: one lane per (sample, axis), in a workgroup of its own in the same launch, walks the chain and
 //     stores only the window, clamped to in - 1;
@@ -29,11 +28,9 @@
 #include "hs_common.h"
 #include "hs_ingest.h"
 #include "hs_resample_px.h"
+#include "hs_resample_tables.h"
 
 namespace hs {
-
-constexpr int RT_THREADS = 256;
-constexpr int RT_MAX_KS = 1 << 12;             // ks_max the entry accepts (a table row of 16 KB)
 
 struct AxisGeometry { int in, out, o, extent; };
 
@@ -41,19 +38,6 @@ __device__ __forceinline__ AxisGeometry axis_geometry(const int32_t* __restrict_
     AxisGeometry g;
     g.in = axis ? Wi : Hi; g.out = p[axis]; g.o = p[2 + axis]; g.extent = axis ? Wo : Ho;
     return g;
-}
-
-// resample_coeffs' scalars of one axis
-struct AxisScale { double scale, support, ss; int ksize; };
-
-__device__ __forceinline__ AxisScale axis_scale(int in, int out, double filter_support) {
-    AxisScale s;
-    s.scale = __ddiv_rn((double)in, (double)out);
-    const double filterscale = s.scale > 1.0 ? s.scale : 1.0;
-    s.support = __dmul_rn(filter_support, filterscale);
-    s.ksize = (int)ceil(s.support) * 2 + 1;
-    s.ss = __ddiv_rn(1.0, filterscale);
-    return s;
 }
 
 // HS_RESIZE_STATUS_* of a sample; 0 = its tables are built
@@ -67,23 +51,6 @@ __device__ __forceinline__ int sample_status(const int32_t* __restrict__ p, int 
     if (Hr != Hi && axis_scale(Hi, Hr, filter_support).ksize > ks_max) st |= HS_RESIZE_STATUS_Y_TAPS;
     if (Wr != Wi && axis_scale(Wi, Wr, filter_support).ksize > ks_max) st |= HS_RESIZE_STATUS_X_TAPS;
     return st;
-}
-
-template <bool BICUBIC>
-__device__ __forceinline__ double resize_filter(double x) {
-    x = fabs(x);
-    if constexpr (BICUBIC) {                   // utils/resample.py::_bicubic, a = -0.5, in its parenthesisation
-        if (x < 1.0) return __dadd_rn(__dmul_rn(__dmul_rn(__dadd_rn(__dmul_rn(1.5, x), -2.5), x), x), 1.0);
-        if (x < 2.0) return __dmul_rn(__dadd_rn(__dmul_rn(__dadd_rn(__dmul_rn(__dadd_rn(x, -5.0), x), 8.0), x), -4.0), -0.5);
-        return 0.0;
-    } else {
-        return x < 1.0 ? __dadd_rn(1.0, -x) : 0.0;
-    }
-}
-
-template <bool BICUBIC>
-__device__ __forceinline__ double resize_tap(int k, int xmin, double center, double ss) {
-    return resize_filter<BICUBIC>(__dmul_rn(__dadd_rn(__dadd_rn((double)(k + xmin), -center), 0.5), ss));
 }
 
 template <bool BICUBIC>
@@ -128,24 +95,7 @@ void resize_tables_kernel(const int32_t* __restrict__ params, int Hi, int Wi, in
     const long r = (long)g.o + j;
     int xmin = 0, n = 0;
     if (st == 0 && j < g.extent && r >= 0 && r < g.out) {
-        if (g.in == g.out) {                   // the pass Pillow skips: one tap of 2^22
-            xmin = (int)r; n = 1;
-            k_row[0] = 1 << RS_BITS;
-        } else {
-            const AxisScale s = axis_scale(g.in, g.out, filter_support);
-            const double center = __dmul_rn(__dadd_rn((double)r, 0.5), s.scale);
-            xmin = max((int)__dadd_rn(__dadd_rn(center, -s.support), 0.5), 0);         // C's (int): truncation
-            n = min((int)__dadd_rn(__dadd_rn(center, s.support), 0.5), g.in) - xmin;
-            n = max(min(min(n, s.ksize), ks_max), 0);
-            double ww = 0.0;
-            for (int k = 0; k < n; ++k) ww = __dadd_rn(ww, resize_tap<BICUBIC>(k, xmin, center, s.ss));      // the sequential sum
-            for (int k = 0; k < n; ++k) {
-                double w = resize_tap<BICUBIC>(k, xmin, center, s.ss);
-                if (ww != 0.0) w = __ddiv_rn(w, ww);
-                const double q = __dmul_rn(w, (double)(1 << RS_BITS));
-                k_row[k] = (int)(w < 0.0 ? __dadd_rn(-0.5, q) : __dadd_rn(0.5, q));
-            }
-        }
+        resize_table_row<BICUBIC>(g.in, g.out, (int)r, ks_max, k_row, xmin, n);
     }
     bd[0] = xmin; bd[1] = n;
     for (int k = n; k < ks_max; ++k) k_row[k] = 0;

@@ -27,8 +27,10 @@ __device__ __forceinline__ void resize_bounds(const int32_t* __restrict__ bounds
 }
 
 // Source rows [s0, s1) of one sample through the column's horizontal taps (xmin, xn, xk) into acc: `x` is the sample's first byte,
-// `plane` = Hi Wi.  XREG: xn <= RS_XREG and the column's weights sit in registers.
-template <bool HWC, bool XREG>
+// `plane` = Hi Wi.  XREG: xn <= RS_XREG and the column's weights sit in registers.  STEP = -1: tap k reads source column xmin - k -- a
+// mirrored source, whose first column the caller passes as xmin (hs_augment_ragged.hip flips the SOURCE, as the reference does).  Wi is
+// used as the row pitch only: a frame inside a wider canvas passes the canvas's width and plane.
+template <bool HWC, bool XREG, int STEP = 1>
 __device__ __forceinline__ void resize_accumulate(const uint8_t* __restrict__ x, size_t plane, int Wi, int xmin, int xn,
                                                   const int32_t* __restrict__ xk, int s0, int s1, const int (&ymin)[RS_TY],
                                                   const int (&yn)[RS_TY], const int32_t* const (&yk)[RS_TY],
@@ -47,14 +49,14 @@ __device__ __forceinline__ void resize_accumulate(const uint8_t* __restrict__ x,
                 for (int k = 0; k < RS_XREG; ++k) {
                     if (k < xn) {
 #pragma unroll
-                        for (int c = 0; c < INGEST_CHANNELS; ++c) h[c] += (int)p[3 * k + c] * wx[k];
+                        for (int c = 0; c < INGEST_CHANNELS; ++c) h[c] += (int)p[3 * k * STEP + c] * wx[k];
                     }
                 }
             } else {
                 for (int k = 0; k < xn; ++k) {
                     const int w = xk[k];
 #pragma unroll
-                    for (int c = 0; c < INGEST_CHANNELS; ++c) h[c] += (int)p[3 * k + c] * w;
+                    for (int c = 0; c < INGEST_CHANNELS; ++c) h[c] += (int)p[3 * k * STEP + c] * w;
                 }
             }
         } else {
@@ -64,14 +66,14 @@ __device__ __forceinline__ void resize_accumulate(const uint8_t* __restrict__ x,
                 for (int k = 0; k < RS_XREG; ++k) {
                     if (k < xn) {
 #pragma unroll
-                        for (int c = 0; c < INGEST_CHANNELS; ++c) h[c] += (int)p[c * plane + k] * wx[k];
+                        for (int c = 0; c < INGEST_CHANNELS; ++c) h[c] += (int)p[(long)(c * plane) + k * STEP] * wx[k];
                     }
                 }
             } else {
                 for (int k = 0; k < xn; ++k) {
                     const int w = xk[k];
 #pragma unroll
-                    for (int c = 0; c < INGEST_CHANNELS; ++c) h[c] += (int)p[c * plane + k] * w;
+                    for (int c = 0; c < INGEST_CHANNELS; ++c) h[c] += (int)p[(long)(c * plane) + k * STEP] * w;
                 }
             }
         }

@@ -23,12 +23,9 @@
 #include "hyperseg_hip.h"
 #include "hs_common.h"
 #include "hs_ingest.h"
+#include "hs_rotate_px.h"
 
 namespace hs {
-
-constexpr int RT_COLS = 64;                    // output columns per wave
-constexpr int RT_ROWS = 4;                     // waves per workgroup, one output row each
-constexpr int RT_MAX_DIM = 8192;               // Pillow's 32-bit accumulation of the label path stays inside int32 up to here
 
 struct RotateArgs {
     const uint8_t* x; void* y; const float* table; const double* m;
@@ -36,14 +33,7 @@ struct RotateArgs {
     unsigned fill, pad_fill;                   // r | g << 8 | b << 16
 };
 
-// Pillow's BICUBIC macro: p1 + d (p2 + d (p3 + d p4))
-__device__ __forceinline__ double rotate_cubic(double v1, double v2, double v3, double v4, double d) {
-    const double p2 = __dadd_rn(-v1, v3);
-    const double p3 = __dadd_rn(__dadd_rn(__dmul_rn(2.0, __dadd_rn(v1, -v2)), v3), -v4);
-    const double p4 = __dadd_rn(__dadd_rn(__dadd_rn(-v1, v2), -v3), v4);
-    return __dadd_rn(v2, __dmul_rn(d, __dadd_rn(p2, __dmul_rn(d, __dadd_rn(p3, __dmul_rn(d, p4))))));
-}
-
+// the per-pixel arithmetic is hs_rotate_px.h's, shared with the ragged launch of hs_augment_ragged.hip
 template <bool HWC, bool NORM>
 __global__ __launch_bounds__(RT_COLS * RT_ROWS)
 void frame_rotate_kernel(const RotateArgs a) {
@@ -60,69 +50,14 @@ void frame_rotate_kernel(const RotateArgs a) {
     unsigned out[INGEST_CHANNELS];
 #pragma unroll
     for (int c = 0; c < INGEST_CHANNELS; ++c) out[c] = (a.pad_fill >> (8 * c)) & 255u;
-
     if (x < W && y < H) {
-#pragma unroll
-        for (int c = 0; c < INGEST_CHANNELS; ++c) out[c] = (a.fill >> (8 * c)) & 255u;
-        const double* __restrict__ m = a.m + 6 * b;
-        const double xi = (double)x + 0.5, yi = (double)y + 0.5;
-        double xin = __dadd_rn(__dadd_rn(__dmul_rn(m[0], xi), __dmul_rn(m[1], yi)), m[2]);
-        double yin = __dadd_rn(__dadd_rn(__dmul_rn(m[3], xi), __dmul_rn(m[4], yi)), m[5]);
-        if (xin >= 0.0 && xin < (double)W && yin >= 0.0 && yin < (double)H) {      // false for a NaN
-            xin = __dadd_rn(xin, -0.5);
-            yin = __dadd_rn(yin, -0.5);
-            const double fx = floor(xin), fy = floor(yin);
-            const double dx = __dadd_rn(xin, -fx), dy = __dadd_rn(yin, -fy);
-            const int x0 = (int)fx - 1, y0 = (int)fy - 1;                           // in [-2, W - 2] x [-2, H - 2]
-            int cx[4];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) cx[k] = min(max(x0 + k, 0), W - 1);
-            const size_t plane = (size_t)H * W;
-            const uint8_t* __restrict__ src = a.x + b * INGEST_CHANNELS * plane;
-            double row[4][INGEST_CHANNELS];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const int ry = y0 + k;
-                if (k == 0 || (ry >= 0 && ry < H)) {
-                    const size_t r = (size_t)min(max(ry, 0), H - 1) * W;
-#pragma unroll
-                    for (int c = 0; c < INGEST_CHANNELS; ++c) {
-                        double v[4];
-#pragma unroll
-                        for (int j = 0; j < 4; ++j)
-                            v[j] = (double)(HWC ? src[(r + cx[j]) * INGEST_CHANNELS + c] : src[c * plane + r + cx[j]]);
-                        row[k][c] = rotate_cubic(v[0], v[1], v[2], v[3], dx);
-                    }
-                } else {
-#pragma unroll
-                    for (int c = 0; c < INGEST_CHANNELS; ++c) row[k][c] = row[k > 0 ? k - 1 : 0][c];      // the previous row's result
-                }
-            }
-#pragma unroll
-            for (int c = 0; c < INGEST_CHANNELS; ++c) {
-                const double v = rotate_cubic(row[0][c], row[1][c], row[2][c], row[3][c], dy);
-                out[c] = v <= 0.0 ? 0u : v >= 255.0 ? 255u : (unsigned)(int)v;      // truncation; a NaN gives 0
-                out[c] = min(out[c], 255u);
-            }
-        }
+        const size_t plane = (size_t)H * W;
+        rotate_frame_pixel<HWC>(a.x + b * INGEST_CHANNELS * plane, plane, W, H, W, a.m + 6 * b, x, y, a.fill, out);
     }
-
-    const size_t oplane = (size_t)a.Ho * a.Wo;
-    const size_t pix = (size_t)y * a.Wo + x;
-#pragma unroll
-    for (int c = 0; c < INGEST_CHANNELS; ++c) {
-        if constexpr (NORM) {
-            static_cast<float*>(a.y)[(b * INGEST_CHANNELS + c) * oplane + pix] = ingest_dequant(tab, c, out[c]);
-        } else if constexpr (HWC) {
-            static_cast<uint8_t*>(a.y)[(b * oplane + pix) * 3 + c] = (uint8_t)out[c];
-        } else {
-            static_cast<uint8_t*>(a.y)[(b * INGEST_CHANNELS + c) * oplane + pix] = (uint8_t)out[c];
-        }
-    }
+    rotate_store<HWC, NORM>(a.y, tab, b, a.Ho, a.Wo, x, y, out);
 }
 
-// labels: Pillow's 16.16 fixed-point affine path, integers only; one thread per output pixel.  The sums wrap as 32-bit words (they cannot
-// for a table built from a rotation of a frame up to RT_MAX_DIM), and the source index is used only after the range test.
+// labels: Pillow's 16.16 fixed-point affine path, integers only; one thread per output pixel
 template <typename TI, typename TO>
 __global__ __launch_bounds__(256)
 void label_rotate_kernel(const TI* __restrict__ x, const int32_t* __restrict__ fixed, TO* __restrict__ y,
@@ -133,9 +68,8 @@ void label_rotate_kernel(const TI* __restrict__ x, const int32_t* __restrict__ f
     const size_t b = blockIdx.y;
     TO v = (TO)pad_fill;
     if (yy < H && xx < W) {
-        const int32_t* __restrict__ a = fixed + 6 * b;
-        const int xs = (int)((uint32_t)a[2] + (uint32_t)yy * (uint32_t)a[1] + (uint32_t)xx * (uint32_t)a[0]) >> 16;
-        const int ys = (int)((uint32_t)a[5] + (uint32_t)yy * (uint32_t)a[4] + (uint32_t)xx * (uint32_t)a[3]) >> 16;
+        int xs, ys;
+        rotate_label_source(fixed + 6 * b, xx, yy, xs, ys);
         v = (TO)fill;
         if (xs >= 0 && xs < W && ys >= 0 && ys < H) v = (TO)x[(b * H + ys) * (size_t)W + xs];
     }

@@ -1940,6 +1940,241 @@ def label_rotate(t, angle, size=None, fill=0, pad_fill=255, out=None, table=None
 
 
 # ------------------------------------------------------------------------------------------
+# the VOC train chain for a ragged batch (csrc/hs_augment_ragged.hip): a canvas plus per-sample extents
+# ------------------------------------------------------------------------------------------
+RAGGED_PARAM_WORDS = 8                                     # h, w, Hr, Wr, hflip, 3 reserved: HS_RAGGED_PARAM_WORDS
+RAGGED_STATUS = dict(RESIZE_STATUS, extent=32, canvas=64)  # HS_RESIZE_STATUS_*: what a ragged sample's status word sums
+RAGGED_MAX_DIM = 8192                                      # every canvas and output dimension (the rotation's limit)
+
+
+class RaggedTables(collections.namedtuple('RaggedTables', 'bounds kk nearest status workspace canvas_hw mid_hw ks_max')):
+    """The device-built resize tables of a ragged batch (:func:`resize_tables_ragged`): int32 views of one ``workspace`` -- ``bounds``
+    (B, 2, M, 2), ``kk`` (B, 2, M, ks_max), ``nearest`` (B, 2, M), ``status`` (B,), M = max(mid_hw), axis 0 = y -- and the geometry they
+    were laid out for: ``canvas_hw`` the frames' canvas, ``mid_hw`` the intermediate canvas the resized images go to."""
+    __slots__ = ()
+
+    @staticmethod
+    def words(batch, mid_hw, ks_max):
+        return ResizeTables.words(batch, mid_hw, ks_max)
+
+    @classmethod
+    def over(cls, workspace, batch, canvas_hw, mid_hw, ks_max):
+        t = ResizeTables.over(workspace, batch, canvas_hw, mid_hw, ks_max)
+        return cls(t.bounds, t.kk, t.nearest, t.status, workspace, tuple(canvas_hw), tuple(mid_hw), ks_max)
+
+
+def _ragged_params(params, device=None):
+    if (not isinstance(params, torch.Tensor) or params.dtype != torch.int32 or params.dim() != 2 or params.shape[1] != RAGGED_PARAM_WORDS
+            or params.shape[0] == 0 or not params.is_contiguous() or (device is not None and params.device != device)):
+        raise ValueError(f'params must be a contiguous int32 tensor of shape (B, {RAGGED_PARAM_WORDS}) = h, w, Hr, Wr, hflip, 3 reserved'
+                         f'{"" if device is None else f" on {device}"}; got {getattr(params, "dtype", type(params))} '
+                         f'{tuple(getattr(params, "shape", ()))}')
+    return params.shape[0]
+
+
+def _ragged_hw(hw, name):
+    h, w = (int(s) for s in hw)
+    if not (1 <= h <= RAGGED_MAX_DIM and 1 <= w <= RAGGED_MAX_DIM):
+        raise ValueError(f'{name} must be two sizes in 1..{RAGGED_MAX_DIM}, got {(h, w)}')
+    return h, w
+
+
+def _ragged_frames(x_u8, layout, name='frames'):
+    if layout not in _LAYOUT_CODES:
+        raise ValueError(f'layout {layout!r}: expected one of {tuple(_LAYOUT_CODES)}')
+    if not isinstance(x_u8, torch.Tensor) or x_u8.dtype != torch.uint8 or x_u8.dim() != 4 or x_u8.shape[3 if layout == 'hwc' else 1] != 3:
+        raise ValueError(f'{name} must be uint8 {"(B, H, W, 3)" if layout == "hwc" else "(B, 3, H, W)"}, got '
+                         f'{getattr(x_u8, "dtype", type(x_u8))} {tuple(getattr(x_u8, "shape", ()))}')
+    return _ragged_hw(x_u8.shape[1:3] if layout == 'hwc' else x_u8.shape[2:], name)
+
+
+def _ragged_tables(tables, params, device, canvas_hw=None, mid_hw=None):
+    b = _ragged_params(params, device)
+    if not isinstance(tables, RaggedTables):
+        raise ValueError('tables must be what resize_tables_ragged returned')
+    if tables.workspace.device != device:
+        raise ValueError(f'tables must be on {device}')
+    if tables.status.shape[0] != b or (canvas_hw is not None and tables.canvas_hw != tuple(canvas_hw)) or \
+            (mid_hw is not None and tables.mid_hw != tuple(mid_hw)):
+        raise ValueError(f'the tables were built for {tables.status.shape[0]} samples, canvas {tables.canvas_hw} -> {tables.mid_hw}; these are '
+                         f'{b} samples of {canvas_hw or mid_hw}')
+    return b
+
+
+def _ragged_out(out, shape, dtype, device):
+    if out is None:
+        return torch.empty(shape, device=device, dtype=dtype)
+    if not isinstance(out, torch.Tensor) or tuple(out.shape) != tuple(shape) or out.dtype != dtype or out.device != device:
+        raise ValueError(f'out must be a {dtype} tensor of shape {tuple(shape)} on {device}')
+    return out
+
+
+@_on_operand_device
+def resize_tables_ragged(params, canvas_hw, mid_hw, filter, ks_max, workspace=None):
+    """:func:`resize_tables` for a batch whose samples differ in INPUT size, one launch (hs_resize_tables_ragged_fwd).  ``params``: int32
+    (B, 8) on the device = ``h, w, Hr, Wr, hflip, 3 reserved`` per sample -- the extent of the image in the ``canvas_hw`` = (Hm, Wm)
+    canvas, its resized size, the flip of the source; ``mid_hw`` = (Hc, Wc) the intermediate canvas the resized images go to.  The
+    window is the whole resized image.  Returns a :class:`RaggedTables` over ``workspace`` (int32, contiguous, at least
+    ``RaggedTables.words(B, mid_hw, ks_max)`` elements; default a new one): per sample and axis ``utils.resample.window_tables_cpu(in, out,
+    0, M, filter, ks_max)``, integer for integer.  ``status``: 0 per sample, or a sum of ``RAGGED_STATUS`` codes -- an extent outside
+    the canvas, a resized size below 1 or above ``mid_hw``, more taps than ``ks_max`` (an axis of ``in`` pixels has at most
+    ``min(ksize, in)``); that sample's tables are empty and it comes out as pad fill.  Nothing is read back: capturable."""
+    from .utils import resample
+    b = _ragged_params(params)
+    if filter not in resample.FILTERS:
+        raise ValueError(f'filter {filter!r}: expected one of {resample.FILTERS}')
+    hm, wm = _ragged_hw(canvas_hw, 'canvas_hw')
+    hc, wc = _ragged_hw(mid_hw, 'mid_hw')
+    ks_max = int(ks_max)
+    if ks_max < 1:
+        raise ValueError(f'ks_max must be >= 1, got {ks_max}')
+    words = RaggedTables.words(b, (hc, wc), ks_max)
+    if workspace is None:
+        workspace = torch.empty(words, device=params.device, dtype=torch.int32)
+    elif (not isinstance(workspace, torch.Tensor) or workspace.dtype != torch.int32 or workspace.dim() != 1 or workspace.numel() < words
+          or workspace.device != params.device or not workspace.is_contiguous()):
+        raise ValueError(f'workspace must be a contiguous int32 vector of at least {words} elements on {params.device}')
+    t = RaggedTables.over(workspace, b, (hm, wm), (hc, wc), ks_max)
+    st = _hip.lib.hs_resize_tables_ragged_fwd(_hip.dev_ptr(params, 'params', torch.int32), b, hm, wm, hc, wc, _FILTER_CODES[filter], ks_max,
+                                              t.bounds.data_ptr(), t.kk.data_ptr(), t.nearest.data_ptr(), t.status.data_ptr(),
+                                              _hip.stream_ptr())
+    _hip.check(st, 'hs_resize_tables_ragged_fwd')
+    return t
+
+
+@_on_operand_device
+def color_jitter_ragged(x_u8, params, table, layout='hwc', contrast=True, out=None, sums=None):
+    """:func:`color_jitter` over the top-left ``(h, w)`` region of every sample of a uint8 canvas (B, Hm, Wm, 3) / (B, 3, Hm, Wm)
+    (hs_color_jitter_ragged_fwd): ``params`` the ragged int32 (B, 8) rows, ``table`` the int32 (B, ``utils.jitter.TABLE_WORDS``) records,
+    both on the device and read when the kernels run.  The contrast mean is taken over the region only; nothing outside it is read or
+    written.  Returns a uint8 canvas of the same shape (``out``).  ``contrast=True``: a clear of B sums, the mean pass and the apply pass;
+    ``False`` -- the caller's promise that no record names contrast -- the apply pass alone.  ``sums``: an int64 (B,) device tensor to use
+    as the mean's workspace (default a new one).  Per sample the region holds ``utils.jitter.color_jitter_cpu`` of the cropped frame.
+    Capturable."""
+    from .utils import jitter
+    hm, wm = _ragged_frames(x_u8, layout, 'canvas')
+    b = _ragged_params(params, x_u8.device)
+    if x_u8.shape[0] != b:
+        raise ValueError(f'{x_u8.shape[0]} frames, {b} parameter rows')
+    if (not isinstance(table, torch.Tensor) or table.dtype != torch.int32 or tuple(table.shape) != (b, jitter.TABLE_WORDS)
+            or table.device != x_u8.device or not table.is_contiguous()):
+        raise ValueError(f'table must be a contiguous int32 tensor of shape {(b, jitter.TABLE_WORDS)} on {x_u8.device}')
+    out = _ragged_out(out, x_u8.shape, torch.uint8, x_u8.device)
+    if contrast:
+        sums = _ragged_out(sums, (b,), torch.int64, x_u8.device)
+    st = _hip.lib.hs_color_jitter_ragged_fwd(_hip.dev_ptr(x_u8, 'canvas', torch.uint8), _LAYOUT_CODES[layout], b, hm, wm,
+                                             _hip.dev_ptr(params, 'params', torch.int32), _hip.dev_ptr(table, 'table', torch.int32),
+                                             _hip.dev_ptr(sums, 'sums', torch.int64) if contrast else None,
+                                             _hip.dev_ptr(out, 'out', torch.uint8), _hip.stream_ptr())
+    _hip.check(st, 'hs_color_jitter_ragged_fwd')
+    return out
+
+
+@_on_operand_device
+def frame_resize_ragged(x_u8, params, tables, layout='hwc', out=None):
+    """:func:`frame_resize_batch` for a ragged batch, one launch (hs_frame_resize_ragged_fwd): the ``(h, w)`` region of sample b of the
+    uint8 canvas (B, Hm, Wm, 3) / (B, 3, Hm, Wm), mirrored left-right FIRST where ``params[b]`` says hflip, resized to its (Hr, Wr) with
+    the filter ``tables`` (a :class:`RaggedTables` built from the same ``params``) were made for.  Returns the uint8 intermediate canvas
+    (B, Hc, Wc, 3) / (B, 3, Hc, Wc) (``out``), the resized image at its top left: the bytes of ``frame_resize(region.flip(), (Hr, Wr))``;
+    the pixels outside it are not specified.  Capturable."""
+    hm, wm = _ragged_frames(x_u8, layout, 'canvas')
+    b = _ragged_tables(tables, params, x_u8.device, canvas_hw=(hm, wm))
+    if x_u8.shape[0] != b:
+        raise ValueError(f'{x_u8.shape[0]} frames, {b} parameter rows')
+    hc, wc = tables.mid_hw
+    out = _ragged_out(out, (b, hc, wc, 3) if layout == 'hwc' else (b, 3, hc, wc), torch.uint8, x_u8.device)
+    st = _hip.lib.hs_frame_resize_ragged_fwd(_hip.dev_ptr(x_u8, 'canvas', torch.uint8), _LAYOUT_CODES[layout], b, hm, wm,
+                                             _hip.dev_ptr(params, 'params', torch.int32), tables.bounds.data_ptr(), tables.kk.data_ptr(),
+                                             tables.status.data_ptr(), tables.ks_max, hc, wc, _hip.dev_ptr(out, 'out', torch.uint8),
+                                             _hip.stream_ptr())
+    _hip.check(st, 'hs_frame_resize_ragged_fwd')
+    return out
+
+
+@_on_operand_device
+def label_resize_ragged(t, params, tables, out=None):
+    """:func:`label_resize_batch` for a ragged batch, one launch (hs_label_resize_ragged_fwd): labels (B, Hm, Wm), uint8 or int64 with
+    values in 0..255, the region mirrored first where hflip says, through ``tables``' nearest indices.  Returns the uint8 intermediate
+    canvas (B, Hc, Wc) (``out``), the resized label at its top left.  Capturable."""
+    if not isinstance(t, torch.Tensor) or t.dtype not in _LABEL_DTYPES or t.dim() != 3:
+        raise ValueError(f'labels must be uint8 or int64 (B, H, W), got {getattr(t, "dtype", type(t))} {tuple(getattr(t, "shape", ()))}')
+    hm, wm = _ragged_hw(t.shape[1:], 'labels')
+    b = _ragged_tables(tables, params, t.device, canvas_hw=(hm, wm))
+    if t.shape[0] != b:
+        raise ValueError(f'{t.shape[0]} labels, {b} parameter rows')
+    hc, wc = tables.mid_hw
+    out = _ragged_out(out, (b, hc, wc), torch.uint8, t.device)
+    st = _hip.lib.hs_label_resize_ragged_fwd(_hip.dev_ptr(t, 'labels', t.dtype), _LABEL_DTYPES[t.dtype], b, hm, wm,
+                                             _hip.dev_ptr(params, 'params', torch.int32), tables.nearest.data_ptr(), tables.status.data_ptr(),
+                                             hc, wc, _hip.dev_ptr(out, 'out', torch.uint8), _hip.stream_ptr())
+    _hip.check(st, 'hs_label_resize_ragged_fwd')
+    return out
+
+
+@_on_operand_device
+def frame_rotate_ragged(x_u8, params, tables, matrices, layout='hwc', size=None, fill=(0, 0, 0), pad_fill=(0, 0, 0), norm=None, out=None):
+    """:func:`frame_rotate` for a ragged batch, one launch (hs_frame_rotate_ragged_fwd): sample b's (Hr, Wr) image at the top left of the
+    uint8 intermediate canvas (B, Hc, Wc, 3) / (B, 3, Hc, Wc) rotated by ``matrices[b]`` (float64 (B, 6) on the device, the rows of
+    ``utils.rotate.rotation_matrix(Hr, Wr, angle)``), at the top left of the ``size`` = (Ho, Wo) output (default the canvas's), ``fill``
+    where the rotation looks outside the image, ``pad_fill`` right of and below it -- and everywhere for a sample whose ``tables.status``
+    is not 0.  Returns uint8 in the input's layout, or with ``norm`` float32 (B, 3, Ho, Wo) through its table; ``out`` likewise.
+    Capturable."""
+    from .utils import rotate
+    hc, wc = _ragged_frames(x_u8, layout, 'canvas')
+    b = _ragged_tables(tables, params, x_u8.device, mid_hw=(hc, wc))
+    if x_u8.shape[0] != b:
+        raise ValueError(f'{x_u8.shape[0]} frames, {b} parameter rows')
+    if norm is not None and norm.layout != layout:
+        raise ValueError(f"norm describes '{norm.layout}' frames, these are '{layout}'")
+    ho, wo = (hc, wc) if size is None else _ragged_hw(size, 'size')
+    fill, pad_fill = rotate.check_fill(fill), rotate.check_fill(pad_fill, 'pad_fill')
+    rotate.check_table(matrices, b, torch.float64, x_u8.device)
+    if norm is not None:
+        shape, dtype = (b, 3, ho, wo), torch.float32
+    else:
+        shape, dtype = ((b, ho, wo, 3) if layout == 'hwc' else (b, 3, ho, wo)), torch.uint8
+    out = _ragged_out(out, shape, dtype, x_u8.device)
+    st = _hip.lib.hs_frame_rotate_ragged_fwd(_hip.dev_ptr(x_u8, 'canvas', torch.uint8), _LAYOUT_CODES[layout], b, hc, wc,
+                                             _hip.dev_ptr(params, 'params', torch.int32), tables.status.data_ptr(),
+                                             _hip.dev_ptr(matrices, 'matrices', torch.float64), ho, wo,
+                                             fill[0] | fill[1] << 8 | fill[2] << 16, pad_fill[0] | pad_fill[1] << 8 | pad_fill[2] << 16,
+                                             None if norm is None else _hip.dev_ptr(norm.table(x_u8.device), 'table'),
+                                             _hip.dev_ptr(out, 'out', dtype), _hip.stream_ptr())
+    _hip.check(st, 'hs_frame_rotate_ragged_fwd')
+    return out
+
+
+@_on_operand_device
+def label_rotate_ragged(t, params, tables, fixed, size=None, fill=0, pad_fill=255, out=None):
+    """:func:`label_rotate` for a ragged batch, one launch (hs_label_rotate_ragged_fwd): sample b's (Hr, Wr) label at the top left of the
+    uint8 intermediate canvas (B, Hc, Wc) through ``fixed[b]`` (int32 (B, 6) on the device, ``utils.rotate.nearest_fixed`` rows), padded to
+    ``size`` with ``pad_fill`` (everywhere for a sample whose status is not 0).  Returns int64 (B, Ho, Wo), or ``out``'s dtype (uint8 |
+    int64).  Capturable."""
+    from .utils import rotate
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or t.dim() != 3:
+        raise ValueError(f'the intermediate labels must be uint8 (B, H, W), got {getattr(t, "dtype", type(t))} {tuple(getattr(t, "shape", ()))}')
+    hc, wc = _ragged_hw(t.shape[1:], 'labels')
+    b = _ragged_tables(tables, params, t.device, mid_hw=(hc, wc))
+    if t.shape[0] != b:
+        raise ValueError(f'{t.shape[0]} labels, {b} parameter rows')
+    ho, wo = (hc, wc) if size is None else _ragged_hw(size, 'size')
+    rotate.check_table(fixed, b, torch.int32, t.device)
+    if out is None:
+        out = torch.empty((b, ho, wo), device=t.device, dtype=torch.int64)
+    elif not isinstance(out, torch.Tensor) or tuple(out.shape) != (b, ho, wo) or out.dtype not in _LABEL_DTYPES or out.device != t.device:
+        raise ValueError(f'out must be a uint8 or int64 tensor of shape {(b, ho, wo)} on {t.device}')
+    fill, pad_fill = int(fill), int(pad_fill)
+    for name, f in (('fill', fill), ('pad_fill', pad_fill)):
+        if not (0 <= f <= 255 or (out.dtype == torch.int64 and -2 ** 31 <= f < 2 ** 31)):
+            raise ValueError(f'{name} {f} does not fit the output labels')
+    st = _hip.lib.hs_label_rotate_ragged_fwd(_hip.dev_ptr(t, 'labels', torch.uint8), b, hc, wc, _hip.dev_ptr(params, 'params', torch.int32),
+                                             tables.status.data_ptr(), _hip.dev_ptr(fixed, 'fixed', torch.int32), ho, wo, fill, pad_fill,
+                                             _hip.dev_ptr(out, 'out', out.dtype), _LABEL_DTYPES[out.dtype], _hip.stream_ptr())
+    _hip.check(st, 'hs_label_rotate_ragged_fwd')
+    return out
+
+
+# ------------------------------------------------------------------------------------------
 # small caches keyed on parameter versions (host-side only; used by the fused inference route --
 # tensors that require grad take the hyperseg_amd.autograd route, which folds nothing)
 # ------------------------------------------------------------------------------------------

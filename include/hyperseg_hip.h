@@ -598,6 +598,52 @@ int hs_frame_rotate_fwd(const uint8_t* x, int32_t layout, int32_t batch, int32_t
                         void* y, void* stream);
 int hs_label_rotate_fwd(const void* x, int32_t in_dtype, int32_t batch, int32_t H, int32_t W, const int32_t* fixed,
                         int32_t Ho, int32_t Wo, int32_t fill, int32_t pad_fill, void* y, int32_t out_dtype, void* stream);
+/* The VOC-SBD train chain (flip -> ColorJitter -> RandomResize -> RandomRotation -> ConstantPad -> ToTensor -> Normalize) for a batch
+ * whose samples differ in SIZE, a fixed number of launches per batch (csrc/hs_augment_ragged.hip).  A ragged batch is a canvas plus
+ * extents: frames uint8 (batch, Hm, Wm, 3) | (batch, 3, Hm, Wm) by layout, labels (batch, Hm, Wm), and per sample the (h, w) of the
+ * top-left region that is the image; what lies outside it is never read into a result.
+ * params: int32 (batch, HS_RAGGED_PARAM_WORDS) on the device = h, w, Hr, Wr, hflip, 3 reserved words -- the extent, the resized size, the
+ *   flip of the SOURCE (source column s is column w - 1 - s: flip-then-resize, the reference's order).  Read when the kernels RUN, as are
+ *   the jitter records, the matrices and the 16.16 integers: a captured graph replays with what they hold then.
+ * Workspace, caller-owned int32, M = max(Hc, Wc), axis 0 = y, row j = resized index j:
+ *   bounds (batch, 2, M, 2), kk (batch, 2, M, ks_max) zero-padded, nearest (batch, 2, M), status (batch).
+ *   hs_resize_tables_ragged_fwd: hs_resize_tables_fwd with the input size (h, w) per sample and the window the whole resized image; the
+ *     same integers (utils/resample.py's resample_coeffs / nearest_index of (h -> Hr) and (w -> Wr); in == out is one tap of 2^22 and
+ *     the identity index); rows j >= the resized size are (0, 0), zeros and 0.  status[b]: 0, or the sum of the HS_RESIZE_STATUS_* codes
+ *     that apply -- those of hs_resize_tables_fwd, HS_RESIZE_STATUS_EXTENT for an extent outside [1, Hm] x [1, Wm], HS_RESIZE_STATUS_CANVAS
+ *     for a resized size above (Hc, Wc); an axis has more taps than ks_max when min(ksize, its input size) does.  Such a sample's tables
+ *     are all-empty, every consumer below leaves it alone and its slice of the rotate outputs is the PAD fill; the others are not
+ *     affected.
+ *   hs_color_jitter_ragged_fwd: hs_color_jitter_fwd over each sample's h x w region, the contrast mean that region's; y is a uint8 canvas
+ *     of x's shape whose pixels outside the regions are not written.  sums as there: non-null launches a clear, the mean pass and the
+ *     apply pass (three launches), null the apply pass alone.
+ *   hs_frame_resize_ragged_fwd / hs_label_resize_ragged_fwd: the bytes of hs_frame_resize_fwd / hs_label_resize_fwd of the flipped
+ *     region to (Hr, Wr), written to the top-left of the sample's slice of the uint8 intermediate canvas y (batch, Hc, Wc, 3) |
+ *     (batch, 3, Hc, Wc) | (batch, Hc, Wc); labels (HS_EVAL_U8 or HS_EVAL_I64 in) are stored as bytes.  Pixels outside the resized image
+ *     are not specified.
+ *   hs_frame_rotate_ragged_fwd / hs_label_rotate_ragged_fwd: hs_frame_rotate_fwd / hs_label_rotate_fwd with (H, W) = (Hr, Wr) per sample,
+ *     reading the intermediate canvas, writing (batch, 3 | -, Ho, Wo) as they do (norm_table, fills, out_dtype).
+ * Every consumer clamps the extents to its canvas, table rows to the extents and tap counts to ks_max: no value in params or in a table
+ * can make an access leave a canvas or the workspace.  HS_ERR_UNSUPPORTED -- nothing launched -- for batch > 65535, a canvas or output
+ * dimension above 8192 or ks_max above 4096.  Nothing is read back: capturable. */
+#define HS_RAGGED_PARAM_WORDS 8
+#define HS_RESIZE_STATUS_EXTENT 32
+#define HS_RESIZE_STATUS_CANVAS 64
+int hs_resize_tables_ragged_fwd(const int32_t* params, int32_t batch, int32_t Hm, int32_t Wm, int32_t Hc, int32_t Wc, int32_t filter,
+                                int32_t ks_max, int32_t* bounds, int32_t* kk, int32_t* nearest, int32_t* status, void* stream);
+int hs_color_jitter_ragged_fwd(const uint8_t* x, int32_t layout, int32_t batch, int32_t Hm, int32_t Wm, const int32_t* params,
+                               const int32_t* table, uint64_t* sums, uint8_t* y, void* stream);
+int hs_frame_resize_ragged_fwd(const uint8_t* x, int32_t layout, int32_t batch, int32_t Hm, int32_t Wm, const int32_t* params,
+                               const int32_t* bounds, const int32_t* kk, const int32_t* status, int32_t ks_max,
+                               int32_t Hc, int32_t Wc, uint8_t* y, void* stream);
+int hs_label_resize_ragged_fwd(const void* x, int32_t in_dtype, int32_t batch, int32_t Hm, int32_t Wm, const int32_t* params,
+                               const int32_t* nearest, const int32_t* status, int32_t Hc, int32_t Wc, uint8_t* y, void* stream);
+int hs_frame_rotate_ragged_fwd(const uint8_t* x, int32_t layout, int32_t batch, int32_t Hc, int32_t Wc, const int32_t* params,
+                               const int32_t* status, const double* matrices, int32_t Ho, int32_t Wo, uint32_t fill_rgb,
+                               uint32_t pad_fill_rgb, const float* norm_table, void* y, void* stream);
+int hs_label_rotate_ragged_fwd(const uint8_t* x, int32_t batch, int32_t Hc, int32_t Wc, const int32_t* params, const int32_t* status,
+                               const int32_t* fixed, int32_t Ho, int32_t Wo, int32_t fill, int32_t pad_fill, void* y, int32_t out_dtype,
+                               void* stream);
 int hs_mbconv_expand_dw_fwd(const float* x, int32_t batch, int32_t c_in, int32_t H, int32_t W,
                             const float* w_expand, int32_t c_mid, const float* scale0, const float* shift0,
                             const float* w_dw, int32_t k, int32_t stride, int32_t pad_t, int32_t pad_l,
