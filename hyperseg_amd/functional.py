@@ -1583,6 +1583,113 @@ def upsample_overlay(x, size, frames, style, out=None):
     return mask, out
 
 
+# ------------------------------------------------------------------------------------------
+# uint8 frames and their labels: resize, colour jitter, rotate (csrc/hs_resample.hip, hs_jitter.hip, hs_rotate.hip).  Every wrapper
+# checks its operands with the helpers below -- each raises ValueError, before any launch or host-to-device copy -- allocates, calls
+# its library entry and checks the status.
+# ------------------------------------------------------------------------------------------
+_LABEL_DTYPES = {torch.uint8: 0, torch.int64: 1}           # HS_EVAL_U8 / HS_EVAL_I64
+_FILTER_CODES = {'bilinear': 0, 'bicubic': 1}              # HS_RESIZE_* of include/hyperseg_hip.h
+
+
+def _frames_bhw(x_u8, layout, name='frames'):
+    """(B, H, W) of uint8 frames (B, H, W, 3) / (B, 3, H, W) as ``layout`` says."""
+    if layout not in _LAYOUT_CODES:
+        raise ValueError(f'layout {layout!r}: expected one of {tuple(_LAYOUT_CODES)}')
+    hwc = layout == 'hwc'
+    if not isinstance(x_u8, torch.Tensor) or x_u8.dtype != torch.uint8 or x_u8.dim() != 4 or x_u8.shape[3 if hwc else 1] != 3:
+        raise ValueError(f'{name} must be uint8 {"(B, H, W, 3)" if hwc else "(B, 3, H, W)"}, got '
+                         f'{getattr(x_u8, "dtype", type(x_u8))} {tuple(getattr(x_u8, "shape", ()))}')
+    return (x_u8.shape[0],) + tuple(x_u8.shape[1:3] if hwc else x_u8.shape[2:])
+
+
+def _labels_bhw(t, dtypes=_LABEL_DTYPES, name='labels'):
+    """(B, H, W) of labels (B, H, W), uint8 or int64."""
+    if not isinstance(t, torch.Tensor) or t.dtype not in dtypes or t.dim() != 3:
+        raise ValueError(f'{name} must be {" or ".join(str(d)[6:] for d in dtypes)} (B, H, W), got {getattr(t, "dtype", type(t))} '
+                         f'{tuple(getattr(t, "shape", ()))}')
+    return tuple(t.shape)
+
+
+def _out(out, shape, dtype, device):
+    """``out`` after checking it, or a new tensor."""
+    if out is None:
+        return torch.empty(shape, device=device, dtype=dtype)
+    if not isinstance(out, torch.Tensor) or tuple(out.shape) != tuple(shape) or out.dtype != dtype or out.device != device:
+        raise ValueError(f'out must be a {dtype} tensor of shape {tuple(shape)} on {device}')
+    return out
+
+
+def _frame_out(out, b, h, w, layout, norm, device):
+    """The frame output: float32 (B, 3, H, W) through ``norm``'s table, else uint8 in ``layout``."""
+    if norm is not None:
+        return _out(out, (b, 3, h, w), torch.float32, device)
+    return _out(out, (b, h, w, 3) if layout == 'hwc' else (b, 3, h, w), torch.uint8, device)
+
+
+def _label_out(out, shape, dtype, device):
+    """The label output: ``out``, uint8 or int64, or a new ``dtype`` tensor."""
+    if out is not None and (not isinstance(out, torch.Tensor) or out.dtype not in _LABEL_DTYPES):
+        raise ValueError(f'out must be a uint8 or int64 tensor of shape {tuple(shape)} on {device}')
+    return _out(out, shape, dtype if out is None else out.dtype, device)
+
+
+def _label_fill(fill, out, name='fill'):
+    fill = int(fill)
+    if not (0 <= fill <= 255 or (out.dtype == torch.int64 and -2 ** 31 <= fill < 2 ** 31)):
+        raise ValueError(f'{name} {fill} does not fit the output labels')
+    return fill
+
+
+def _fill_word(fill, name='fill'):
+    """Three fill bytes (or one for all) as the word the kernels take: r | g << 8 | b << 16."""
+    from .utils import rotate
+    r, g, b = rotate.check_fill(fill, name)
+    return r | g << 8 | b << 16
+
+
+def _norm_table(norm, layout, device):
+    """Pointer of ``norm``'s table on ``device`` (None without a norm).  The first use on a device copies the table there: call it after
+    every other check."""
+    if norm is None:
+        return None
+    if norm.layout != layout:
+        raise ValueError(f"norm describes '{norm.layout}' frames, these are '{layout}'")
+    return _hip.dev_ptr(norm.table(device), 'table')
+
+
+def _param_rows(params, words, fields, device=None):
+    """B of the int32 (B, ``words``) parameter tensor the batch kernels read."""
+    if (not isinstance(params, torch.Tensor) or params.dtype != torch.int32 or params.dim() != 2 or params.shape[1] != words
+            or params.shape[0] == 0 or not params.is_contiguous() or (device is not None and params.device != device)):
+        raise ValueError(f'params must be a contiguous int32 tensor of shape (B, {words}) = {fields}{"" if device is None else f" on {device}"}; '
+                         f'got {getattr(params, "dtype", type(params))} {tuple(getattr(params, "shape", ()))}')
+    return params.shape[0]
+
+
+def _workspace(workspace, words, device):
+    if workspace is None:
+        return torch.empty(words, device=device, dtype=torch.int32)
+    if (not isinstance(workspace, torch.Tensor) or workspace.dtype != torch.int32 or workspace.dim() != 1 or workspace.numel() < words
+            or workspace.device != device or not workspace.is_contiguous()):
+        raise ValueError(f'workspace must be a contiguous int32 vector of at least {words} elements on {device}')
+    return workspace
+
+
+def _jitter_table(table, b, device):
+    from .utils import jitter
+    if (not isinstance(table, torch.Tensor) or table.dtype != torch.int32 or tuple(table.shape) != (b, jitter.TABLE_WORDS)
+            or table.device != device or not table.is_contiguous()):
+        raise ValueError(f'table must be a contiguous int32 tensor of shape {(b, jitter.TABLE_WORDS)} on {device}')
+    return table
+
+
+def _filter_code(filter):
+    if filter not in _FILTER_CODES:
+        raise ValueError(f'filter {filter!r}: expected one of {tuple(_FILTER_CODES)}')
+    return _FILTER_CODES[filter]
+
+
 def _resize_geometry(in_hw, size, view):
     from .utils import resample
     hi, wi = (int(s) for s in in_hw)
@@ -1602,41 +1709,22 @@ def frame_resize(x_u8, size, filter='bilinear', layout='hwc', view=None, norm=No
     shape and dtype to write into.  Equal to ``utils.resample.frame_resize_cpu``.  Nothing here reads the device once the tables are
     uploaded (first call per geometry): capturable."""
     from .utils import resample
-    if layout not in _LAYOUT_CODES:
-        raise ValueError(f'layout {layout!r}: expected one of {tuple(_LAYOUT_CODES)}')
-    if filter not in resample.FILTERS:
-        raise ValueError(f'filter {filter!r}: expected one of {resample.FILTERS}')
-    if not isinstance(x_u8, torch.Tensor) or x_u8.dtype != torch.uint8 or x_u8.dim() != 4 or x_u8.shape[3 if layout == 'hwc' else 1] != 3:
-        raise ValueError(f'frames must be uint8 {"(B, H, W, 3)" if layout == "hwc" else "(B, 3, H, W)"}, got '
-                         f'{getattr(x_u8, "dtype", type(x_u8))} {tuple(getattr(x_u8, "shape", ()))}')
-    if norm is not None and norm.layout != layout:
-        raise ValueError(f"norm describes '{norm.layout}' frames, these are '{layout}'")
-    b = x_u8.shape[0]
-    hi, wi, hr, wr, view = _resize_geometry(x_u8.shape[1:3] if layout == 'hwc' else x_u8.shape[2:], size, view)
+    b, hi, wi = _frames_bhw(x_u8, layout)
+    _filter_code(filter)
+    hi, wi, hr, wr, view = _resize_geometry((hi, wi), size, view)
     (ho, wo), (oy, ox) = view.size, view.offset
-    if norm is not None:
-        shape, dtype = (b, 3, ho, wo), torch.float32
-    else:
-        shape, dtype = ((b, ho, wo, 3) if layout == 'hwc' else (b, 3, ho, wo)), torch.uint8
-    if out is None:
-        out = torch.empty(shape, device=x_u8.device, dtype=dtype)
-    elif not isinstance(out, torch.Tensor) or tuple(out.shape) != shape or out.dtype != dtype or out.device != x_u8.device:
-        raise ValueError(f'out must be a {dtype} tensor of shape {shape} on {x_u8.device}')
+    out = _frame_out(out, b, ho, wo, layout, norm, x_u8.device)
     if b == 0:
         raise ValueError('empty batch')
+    table = _norm_table(norm, layout, x_u8.device)
     yb, ykk = resample.device_coeffs(hi, hr, filter, x_u8.device)
     xb, xkk = resample.device_coeffs(wi, wr, filter, x_u8.device)
-    fill = view.fill[0] | view.fill[1] << 8 | view.fill[2] << 16
     st = _hip.lib.hs_frame_resize_fwd(_hip.dev_ptr(x_u8, 'x_u8', torch.uint8), _LAYOUT_CODES[layout], b, hi, wi,
                                       yb.data_ptr(), ykk.data_ptr(), ykk.shape[1], hr, xb.data_ptr(), xkk.data_ptr(), xkk.shape[1], wr,
-                                      ho, wo, oy, ox, int(view.hflip), fill,
-                                      None if norm is None else _hip.dev_ptr(norm.table(x_u8.device), 'table'),
-                                      _hip.dev_ptr(out, 'out', dtype), _hip.stream_ptr())
+                                      ho, wo, oy, ox, int(view.hflip), _fill_word(view.fill), table,
+                                      _hip.dev_ptr(out, 'out', out.dtype), _hip.stream_ptr())
     _hip.check(st, 'hs_frame_resize_fwd')
     return out
-
-
-_LABEL_DTYPES = {torch.uint8: 0, torch.int64: 1}           # HS_EVAL_U8 / HS_EVAL_I64
 
 
 @_on_operand_device
@@ -1645,20 +1733,13 @@ def label_resize(t, size, view=None, fill=255, out=None):
     one launch), then ``view`` as :func:`frame_resize`'s with ``fill`` outside (the view's own fill is the frames').  Returns the
     input's dtype, or ``out``'s (uint8 | int64, contiguous, (B, Ho, Wo)).  Equal to ``utils.resample.label_resize_cpu``."""
     from .utils import resample
-    if not isinstance(t, torch.Tensor) or t.dtype not in _LABEL_DTYPES or t.dim() != 3:
-        raise ValueError(f'labels must be uint8 or int64 (B, H, W), got {getattr(t, "dtype", type(t))} {tuple(getattr(t, "shape", ()))}')
-    b = t.shape[0]
-    hi, wi, hr, wr, view = _resize_geometry(t.shape[1:], size, view)
+    b, hi, wi = _labels_bhw(t)
+    hi, wi, hr, wr, view = _resize_geometry((hi, wi), size, view)
     (ho, wo), (oy, ox) = view.size, view.offset
-    if out is None:
-        out = torch.empty((b, ho, wo), device=t.device, dtype=t.dtype)
-    elif not isinstance(out, torch.Tensor) or tuple(out.shape) != (b, ho, wo) or out.dtype not in _LABEL_DTYPES or out.device != t.device:
-        raise ValueError(f'out must be a uint8 or int64 tensor of shape {(b, ho, wo)} on {t.device}')
+    out = _label_out(out, (b, ho, wo), t.dtype, t.device)
     if b == 0:
         raise ValueError('empty batch')
-    fill = int(fill)
-    if not (0 <= fill <= 255 or (out.dtype == torch.int64 and -2 ** 31 <= fill < 2 ** 31)):
-        raise ValueError(f'fill {fill} does not fit the output labels')
+    fill = _label_fill(fill, out)
     iy, ix = resample.device_nearest(hi, hr, t.device), resample.device_nearest(wi, wr, t.device)
     st = _hip.lib.hs_label_resize_fwd(_hip.dev_ptr(t, 'labels', t.dtype), _LABEL_DTYPES[t.dtype], b, hi, wi, iy.data_ptr(), hr, ix.data_ptr(), wr,
                                       ho, wo, oy, ox, int(view.hflip), fill, _hip.dev_ptr(out, 'out', out.dtype), _LABEL_DTYPES[out.dtype],
@@ -1667,7 +1748,6 @@ def label_resize(t, size, view=None, fill=255, out=None):
     return out
 
 
-_FILTER_CODES = {'bilinear': 0, 'bicubic': 1}              # HS_RESIZE_* of include/hyperseg_hip.h
 RESIZE_STATUS = {'hr': 1, 'wr': 2, 'y_taps': 4, 'x_taps': 8, 'size': 16}      # HS_RESIZE_STATUS_*: what a sample's status word sums
 RESIZE_PARAM_WORDS = 6                                     # Hr, Wr, oy, ox, hflip, reserved
 
@@ -1689,15 +1769,17 @@ class ResizeTables(collections.namedtuple('ResizeTables', 'bounds kk nearest sta
         return cls(b.view(batch, 2, m, 2), k.view(batch, 2, m, ks_max), n.view(batch, 2, m), s, workspace, tuple(in_hw), tuple(crop), ks_max)
 
 
+def _tables_over(cls, workspace, batch, in_hw, out_hw, ks_max, device):
+    """``cls.over`` a workspace that holds the tables (default a new one): ``cls`` is ResizeTables or RaggedTables."""
+    return cls.over(_workspace(workspace, cls.words(batch, out_hw, ks_max), device), batch, in_hw, out_hw, ks_max)
+
+
 def _resize_params(params):
-    if (not isinstance(params, torch.Tensor) or params.dtype != torch.int32 or params.dim() != 2 or params.shape[1] != RESIZE_PARAM_WORDS
-            or params.shape[0] == 0 or not params.is_contiguous()):
-        raise ValueError(f'params must be a contiguous int32 tensor of shape (B, {RESIZE_PARAM_WORDS}) = Hr, Wr, oy, ox, hflip, reserved; got '
-                         f'{getattr(params, "dtype", type(params))} {tuple(getattr(params, "shape", ()))}')
-    return params.shape[0]
+    return _param_rows(params, RESIZE_PARAM_WORDS, 'Hr, Wr, oy, ox, hflip, reserved')
 
 
-def _batch_tables(tables, params, in_hw, device):
+def _batch_tables(tables, params, n, in_hw, device):
+    """B of ``params`` after checking that ``tables`` were built for them and for the ``n`` samples of ``in_hw`` at hand."""
     b = _resize_params(params)
     if not isinstance(tables, ResizeTables):
         raise ValueError('tables must be what resize_tables returned')
@@ -1705,6 +1787,8 @@ def _batch_tables(tables, params, in_hw, device):
         raise ValueError(f'params and tables must be on {device}')
     if tables.status.shape[0] != b or tables.in_hw != tuple(in_hw):
         raise ValueError(f'the tables were built for {tables.status.shape[0]} samples of {tables.in_hw}, these are {b} of {tuple(in_hw)}')
+    if n != b:
+        raise ValueError(f'{n} samples, {b} parameter rows')
     return b
 
 
@@ -1718,23 +1802,15 @@ def resize_tables(params, in_hw, crop, filter, ks_max, workspace=None):
     integer (``utils.resample.window_tables_cpu``).  ``status``: 0 per sample, or a sum of ``RESIZE_STATUS`` codes (a resized size
     below 1 or above 2^19, more taps than ``ks_max``) -- that sample's tables are empty and the resize launches write fill.  ``params`` is
     read when the kernel runs and nothing is read back: capturable."""
-    from .utils import resample
     b = _resize_params(params)
-    if filter not in resample.FILTERS:
-        raise ValueError(f'filter {filter!r}: expected one of {resample.FILTERS}')
+    code = _filter_code(filter)
     hi, wi = (int(s) for s in in_hw)
     ho, wo = (int(s) for s in crop)
     ks_max = int(ks_max)
     if min(hi, wi, ho, wo, ks_max) < 1:
         raise ValueError(f'sizes must be >= 1, got {(hi, wi)} -> {(ho, wo)}, ks_max {ks_max}')
-    words = ResizeTables.words(b, (ho, wo), ks_max)
-    if workspace is None:
-        workspace = torch.empty(words, device=params.device, dtype=torch.int32)
-    elif (not isinstance(workspace, torch.Tensor) or workspace.dtype != torch.int32 or workspace.dim() != 1 or workspace.numel() < words
-          or workspace.device != params.device or not workspace.is_contiguous()):
-        raise ValueError(f'workspace must be a contiguous int32 vector of at least {words} elements on {params.device}')
-    t = ResizeTables.over(workspace, b, (hi, wi), (ho, wo), ks_max)
-    st = _hip.lib.hs_resize_tables_fwd(_hip.dev_ptr(params, 'params', torch.int32), b, hi, wi, ho, wo, _FILTER_CODES[filter], ks_max,
+    t = _tables_over(ResizeTables, workspace, b, (hi, wi), (ho, wo), ks_max, params.device)
+    st = _hip.lib.hs_resize_tables_fwd(_hip.dev_ptr(params, 'params', torch.int32), b, hi, wi, ho, wo, code, ks_max,
                                        t.bounds.data_ptr(), t.kk.data_ptr(), t.nearest.data_ptr(), t.status.data_ptr(), _hip.stream_ptr())
     _hip.check(st, 'hs_resize_tables_fwd')
     return t
@@ -1747,34 +1823,16 @@ def frame_resize_batch(x_u8, params, tables, layout='hwc', fill=(0, 0, 0), norm=
     :class:`ResizeTables` built from the same ``params``) were made for, and the ``tables.crop`` window at its offset comes back, flipped
     where it says, ``fill`` (3 bytes) outside.  Returns uint8 in the input's layout, or with ``norm`` float32 (B, 3, h, w) through its
     table; ``out`` as :func:`frame_resize`'s.  Per sample the bytes of ``frame_resize(x[b:b+1], (Hr, Wr), view=...)``.  Capturable."""
-    if layout not in _LAYOUT_CODES:
-        raise ValueError(f'layout {layout!r}: expected one of {tuple(_LAYOUT_CODES)}')
-    if not isinstance(x_u8, torch.Tensor) or x_u8.dtype != torch.uint8 or x_u8.dim() != 4 or x_u8.shape[3 if layout == 'hwc' else 1] != 3:
-        raise ValueError(f'frames must be uint8 {"(B, H, W, 3)" if layout == "hwc" else "(B, 3, H, W)"}, got '
-                         f'{getattr(x_u8, "dtype", type(x_u8))} {tuple(getattr(x_u8, "shape", ()))}')
-    if norm is not None and norm.layout != layout:
-        raise ValueError(f"norm describes '{norm.layout}' frames, these are '{layout}'")
-    hi, wi = (int(s) for s in (x_u8.shape[1:3] if layout == 'hwc' else x_u8.shape[2:]))
-    b = _batch_tables(tables, params, (hi, wi), x_u8.device)
-    if x_u8.shape[0] != b:
-        raise ValueError(f'{x_u8.shape[0]} frames, {b} parameter rows')
+    n, hi, wi = _frames_bhw(x_u8, layout)
+    b = _batch_tables(tables, params, n, (hi, wi), x_u8.device)
     ho, wo = tables.crop
-    fill = tuple(int(f) for f in (fill if isinstance(fill, (tuple, list)) else (fill,) * 3))
-    if len(fill) != 3 or any(not 0 <= f <= 255 for f in fill):
-        raise ValueError(f'fill must be 3 bytes, got {fill!r}')
-    if norm is not None:
-        shape, dtype = (b, 3, ho, wo), torch.float32
-    else:
-        shape, dtype = ((b, ho, wo, 3) if layout == 'hwc' else (b, 3, ho, wo)), torch.uint8
-    if out is None:
-        out = torch.empty(shape, device=x_u8.device, dtype=dtype)
-    elif not isinstance(out, torch.Tensor) or tuple(out.shape) != shape or out.dtype != dtype or out.device != x_u8.device:
-        raise ValueError(f'out must be a {dtype} tensor of shape {shape} on {x_u8.device}')
+    fill = _fill_word(fill)
+    out = _frame_out(out, b, ho, wo, layout, norm, x_u8.device)
+    table = _norm_table(norm, layout, x_u8.device)
     st = _hip.lib.hs_frame_resize_batch_fwd(_hip.dev_ptr(x_u8, 'x_u8', torch.uint8), _LAYOUT_CODES[layout], b, hi, wi,
                                             _hip.dev_ptr(params, 'params', torch.int32), tables.bounds.data_ptr(), tables.kk.data_ptr(),
-                                            tables.status.data_ptr(), tables.ks_max, ho, wo, fill[0] | fill[1] << 8 | fill[2] << 16,
-                                            None if norm is None else _hip.dev_ptr(norm.table(x_u8.device), 'table'),
-                                            _hip.dev_ptr(out, 'out', dtype), _hip.stream_ptr())
+                                            tables.status.data_ptr(), tables.ks_max, ho, wo, fill, table,
+                                            _hip.dev_ptr(out, 'out', out.dtype), _hip.stream_ptr())
     _hip.check(st, 'hs_frame_resize_batch_fwd')
     return out
 
@@ -1784,20 +1842,11 @@ def label_resize_batch(t, params, tables, fill=255, out=None):
     """:func:`label_resize` for a batch whose samples each have a geometry of their own, one launch (hs_label_resize_batch_fwd):
     labels (B, Hi, Wi), uint8 or int64, through ``tables``' nearest indices, the ``tables.crop`` window of each sample with ``fill``
     outside.  Returns the input's dtype, or ``out``'s (uint8 | int64, contiguous, (B, h, w)).  Capturable."""
-    if not isinstance(t, torch.Tensor) or t.dtype not in _LABEL_DTYPES or t.dim() != 3:
-        raise ValueError(f'labels must be uint8 or int64 (B, H, W), got {getattr(t, "dtype", type(t))} {tuple(getattr(t, "shape", ()))}')
-    hi, wi = (int(s) for s in t.shape[1:])
-    b = _batch_tables(tables, params, (hi, wi), t.device)
-    if t.shape[0] != b:
-        raise ValueError(f'{t.shape[0]} labels, {b} parameter rows')
+    n, hi, wi = _labels_bhw(t)
+    b = _batch_tables(tables, params, n, (hi, wi), t.device)
     ho, wo = tables.crop
-    if out is None:
-        out = torch.empty((b, ho, wo), device=t.device, dtype=t.dtype)
-    elif not isinstance(out, torch.Tensor) or tuple(out.shape) != (b, ho, wo) or out.dtype not in _LABEL_DTYPES or out.device != t.device:
-        raise ValueError(f'out must be a uint8 or int64 tensor of shape {(b, ho, wo)} on {t.device}')
-    fill = int(fill)
-    if not (0 <= fill <= 255 or (out.dtype == torch.int64 and -2 ** 31 <= fill < 2 ** 31)):
-        raise ValueError(f'fill {fill} does not fit the output labels')
+    out = _label_out(out, (b, ho, wo), t.dtype, t.device)
+    fill = _label_fill(fill, out)
     st = _hip.lib.hs_label_resize_batch_fwd(_hip.dev_ptr(t, 'labels', t.dtype), _LABEL_DTYPES[t.dtype], b, hi, wi,
                                             _hip.dev_ptr(params, 'params', torch.int32), tables.nearest.data_ptr(), tables.status.data_ptr(),
                                             ho, wo, fill, _hip.dev_ptr(out, 'out', out.dtype), _LABEL_DTYPES[out.dtype], _hip.stream_ptr())
@@ -1818,44 +1867,24 @@ def color_jitter(x_u8, params, layout='hwc', norm=None, out=None, table=None):
     samples whose order holds contrast do work) and the apply pass; without ``table``, the apply pass alone when no sample has contrast,
     and one small host-to-device copy of the records in front.  Nothing is read back: with ``table`` the call is capturable."""
     from .utils import jitter
-    if layout not in _LAYOUT_CODES:
-        raise ValueError(f'layout {layout!r}: expected one of {tuple(_LAYOUT_CODES)}')
-    if not isinstance(x_u8, torch.Tensor) or x_u8.dtype != torch.uint8 or x_u8.dim() != 4 or x_u8.shape[3 if layout == 'hwc' else 1] != 3:
-        raise ValueError(f'frames must be uint8 {"(B, H, W, 3)" if layout == "hwc" else "(B, 3, H, W)"}, got '
-                         f'{getattr(x_u8, "dtype", type(x_u8))} {tuple(getattr(x_u8, "shape", ()))}')
-    if norm is not None and norm.layout != layout:
-        raise ValueError(f"norm describes '{norm.layout}' frames, these are '{layout}'")
-    b = x_u8.shape[0]
-    h, w = x_u8.shape[1:3] if layout == 'hwc' else x_u8.shape[2:]
-    shape, dtype = ((b, 3, h, w), torch.float32) if norm is not None else (tuple(x_u8.shape), torch.uint8)
+    b, h, w = _frames_bhw(x_u8, layout)
     if b == 0 or h == 0 or w == 0:
         raise ValueError('empty batch')
     if table is None:
         records = jitter.params_table(params, b)
         need_mean = bool((records[:, 5] >> jitter.OP_CODES['contrast'] & 1).any())
-        table = records.to(x_u8.device)
-    elif (not isinstance(table, torch.Tensor) or table.dtype != torch.int32 or tuple(table.shape) != (b, jitter.TABLE_WORDS)
-          or table.device != x_u8.device or not table.is_contiguous()):
-        raise ValueError(f'table must be a contiguous int32 tensor of shape {(b, jitter.TABLE_WORDS)} on {x_u8.device}')
     else:
+        _jitter_table(table, b, x_u8.device)
         need_mean = True                                       # what it will hold when the kernels run is the caller's business
-    if out is None:
-        out = torch.empty(shape, device=x_u8.device, dtype=dtype)
-    elif not isinstance(out, torch.Tensor) or tuple(out.shape) != shape or out.dtype != dtype or out.device != x_u8.device:
-        raise ValueError(f'out must be a {dtype} tensor of shape {shape} on {x_u8.device}')
+    out = _frame_out(out, b, h, w, layout, norm, x_u8.device)
+    norm_table = _norm_table(norm, layout, x_u8.device)
+    if table is None:
+        table = records.to(x_u8.device)
     sums = torch.empty(b, device=x_u8.device, dtype=torch.int64) if need_mean else None
     st = _hip.lib.hs_color_jitter_fwd(_hip.dev_ptr(x_u8, 'x_u8', torch.uint8), _LAYOUT_CODES[layout], b, h, w,
-                                      _hip.dev_ptr(table, 'table', torch.int32), None if sums is None else sums.data_ptr(),
-                                      None if norm is None else _hip.dev_ptr(norm.table(x_u8.device), 'table'),
-                                      _hip.dev_ptr(out, 'out', dtype), _hip.stream_ptr())
+                                      _hip.dev_ptr(table, 'table', torch.int32), None if sums is None else sums.data_ptr(), norm_table,
+                                      _hip.dev_ptr(out, 'out', out.dtype), _hip.stream_ptr())
     _hip.check(st, 'hs_color_jitter_fwd')
-    return out
-
-
-def _cpu_result(out, res):
-    if not isinstance(out, torch.Tensor) or tuple(out.shape) != tuple(res.shape) or out.dtype != res.dtype or out.device != res.device:
-        raise ValueError(f'out must be a {res.dtype} tensor of shape {tuple(res.shape)} on {res.device}')
-    out.copy_(res)
     return out
 
 
@@ -1877,29 +1906,17 @@ def frame_rotate(x_u8, angle, layout='hwc', size=None, fill=(0, 0, 0), pad_fill=
     h, w = rotate._check_frames(x_u8, layout)
     if not x_u8.is_cuda:                                       # CPU tensors: the same values from the CPU implementation
         res = rotate.frame_rotate_cpu(x_u8, angle, layout, size, fill, pad_fill, norm, table)
-        return res if out is None else _cpu_result(out, res)
-    if norm is not None and norm.layout != layout:
-        raise ValueError(f"norm describes '{norm.layout}' frames, these are '{layout}'")
+        return res if out is None else _out(out, res.shape, res.dtype, res.device).copy_(res)
     b = x_u8.shape[0]
     ho, wo = rotate.check_size(size, h, w)
-    fill, pad_fill = rotate.check_fill(fill), rotate.check_fill(pad_fill, 'pad_fill')
-    if norm is not None:
-        shape, dtype = (b, 3, ho, wo), torch.float32
-    else:
-        shape, dtype = ((b, ho, wo, 3) if layout == 'hwc' else (b, 3, ho, wo)), torch.uint8
-    if table is None:
-        table = rotate.matrix_table(h, w, angle, b).to(x_u8.device)
-    else:
-        rotate.check_table(table, b, torch.float64, x_u8.device)
-    if out is None:
-        out = torch.empty(shape, device=x_u8.device, dtype=dtype)
-    elif not isinstance(out, torch.Tensor) or tuple(out.shape) != shape or out.dtype != dtype or out.device != x_u8.device:
-        raise ValueError(f'out must be a {dtype} tensor of shape {shape} on {x_u8.device}')
+    fill, pad_fill = _fill_word(fill), _fill_word(pad_fill, 'pad_fill')
+    table = rotate.matrix_table(h, w, angle, b) if table is None else rotate.check_table(table, b, torch.float64, x_u8.device)
+    out = _frame_out(out, b, ho, wo, layout, norm, x_u8.device)
+    norm_table = _norm_table(norm, layout, x_u8.device)
+    table = table.to(x_u8.device)                              # the host-built one goes up here; the caller's is there already
     st = _hip.lib.hs_frame_rotate_fwd(_hip.dev_ptr(x_u8, 'x_u8', torch.uint8), _LAYOUT_CODES[layout], b, h, w,
-                                      _hip.dev_ptr(table, 'table', torch.float64), ho, wo,
-                                      fill[0] | fill[1] << 8 | fill[2] << 16, pad_fill[0] | pad_fill[1] << 8 | pad_fill[2] << 16,
-                                      None if norm is None else _hip.dev_ptr(norm.table(x_u8.device), 'table'),
-                                      _hip.dev_ptr(out, 'out', dtype), _hip.stream_ptr())
+                                      _hip.dev_ptr(table, 'table', torch.float64), ho, wo, fill, pad_fill, norm_table,
+                                      _hip.dev_ptr(out, 'out', out.dtype), _hip.stream_ptr())
     _hip.check(st, 'hs_frame_rotate_fwd')
     return out
 
@@ -1917,21 +1934,13 @@ def label_rotate(t, angle, size=None, fill=0, pad_fill=255, out=None, table=None
     h, w = rotate._check_labels(t)
     if not t.is_cuda:
         res = rotate.label_rotate_cpu(t, angle, size, fill, pad_fill, None if out is None else getattr(out, 'dtype', None), table)
-        return res if out is None else _cpu_result(out, res)
+        return res if out is None else _out(out, res.shape, res.dtype, res.device).copy_(res)
     b = t.shape[0]
     ho, wo = rotate.check_size(size, h, w)
-    if out is None:
-        out = torch.empty((b, ho, wo), device=t.device, dtype=t.dtype)
-    elif not isinstance(out, torch.Tensor) or tuple(out.shape) != (b, ho, wo) or out.dtype not in _LABEL_DTYPES or out.device != t.device:
-        raise ValueError(f'out must be a uint8 or int64 tensor of shape {(b, ho, wo)} on {t.device}')
-    fill, pad_fill = int(fill), int(pad_fill)
-    for name, f in (('fill', fill), ('pad_fill', pad_fill)):
-        if not (0 <= f <= 255 or (out.dtype == torch.int64 and -2 ** 31 <= f < 2 ** 31)):
-            raise ValueError(f'{name} {f} does not fit the output labels')
-    if table is None:
-        table = rotate.fixed_table(h, w, angle, b).to(t.device)
-    else:
-        rotate.check_table(table, b, torch.int32, t.device)
+    out = _label_out(out, (b, ho, wo), t.dtype, t.device)
+    fill, pad_fill = _label_fill(fill, out), _label_fill(pad_fill, out, 'pad_fill')
+    table = rotate.fixed_table(h, w, angle, b) if table is None else rotate.check_table(table, b, torch.int32, t.device)
+    table = table.to(t.device)                                 # the host-built one goes up here; the caller's is there already
     st = _hip.lib.hs_label_rotate_fwd(_hip.dev_ptr(t, 'labels', t.dtype), _LABEL_DTYPES[t.dtype], b, h, w,
                                       _hip.dev_ptr(table, 'table', torch.int32), ho, wo, fill, pad_fill,
                                       _hip.dev_ptr(out, 'out', out.dtype), _LABEL_DTYPES[out.dtype], _hip.stream_ptr())
@@ -1952,10 +1961,7 @@ class RaggedTables(collections.namedtuple('RaggedTables', 'bounds kk nearest sta
     (B, 2, M, 2), ``kk`` (B, 2, M, ks_max), ``nearest`` (B, 2, M), ``status`` (B,), M = max(mid_hw), axis 0 = y -- and the geometry they
     were laid out for: ``canvas_hw`` the frames' canvas, ``mid_hw`` the intermediate canvas the resized images go to."""
     __slots__ = ()
-
-    @staticmethod
-    def words(batch, mid_hw, ks_max):
-        return ResizeTables.words(batch, mid_hw, ks_max)
+    words = staticmethod(ResizeTables.words)
 
     @classmethod
     def over(cls, workspace, batch, canvas_hw, mid_hw, ks_max):
@@ -1964,12 +1970,7 @@ class RaggedTables(collections.namedtuple('RaggedTables', 'bounds kk nearest sta
 
 
 def _ragged_params(params, device=None):
-    if (not isinstance(params, torch.Tensor) or params.dtype != torch.int32 or params.dim() != 2 or params.shape[1] != RAGGED_PARAM_WORDS
-            or params.shape[0] == 0 or not params.is_contiguous() or (device is not None and params.device != device)):
-        raise ValueError(f'params must be a contiguous int32 tensor of shape (B, {RAGGED_PARAM_WORDS}) = h, w, Hr, Wr, hflip, 3 reserved'
-                         f'{"" if device is None else f" on {device}"}; got {getattr(params, "dtype", type(params))} '
-                         f'{tuple(getattr(params, "shape", ()))}')
-    return params.shape[0]
+    return _param_rows(params, RAGGED_PARAM_WORDS, 'h, w, Hr, Wr, hflip, 3 reserved', device)
 
 
 def _ragged_hw(hw, name):
@@ -1979,16 +1980,9 @@ def _ragged_hw(hw, name):
     return h, w
 
 
-def _ragged_frames(x_u8, layout, name='frames'):
-    if layout not in _LAYOUT_CODES:
-        raise ValueError(f'layout {layout!r}: expected one of {tuple(_LAYOUT_CODES)}')
-    if not isinstance(x_u8, torch.Tensor) or x_u8.dtype != torch.uint8 or x_u8.dim() != 4 or x_u8.shape[3 if layout == 'hwc' else 1] != 3:
-        raise ValueError(f'{name} must be uint8 {"(B, H, W, 3)" if layout == "hwc" else "(B, 3, H, W)"}, got '
-                         f'{getattr(x_u8, "dtype", type(x_u8))} {tuple(getattr(x_u8, "shape", ()))}')
-    return _ragged_hw(x_u8.shape[1:3] if layout == 'hwc' else x_u8.shape[2:], name)
-
-
-def _ragged_tables(tables, params, device, canvas_hw=None, mid_hw=None):
+def _ragged_tables(tables, params, n, device, canvas_hw=None, mid_hw=None):
+    """B of ``params`` after checking that ``tables`` were built for them and for the ``n`` samples of the canvas at hand."""
+    _ragged_hw(canvas_hw or mid_hw, 'canvas')
     b = _ragged_params(params, device)
     if not isinstance(tables, RaggedTables):
         raise ValueError('tables must be what resize_tables_ragged returned')
@@ -1998,15 +1992,9 @@ def _ragged_tables(tables, params, device, canvas_hw=None, mid_hw=None):
             (mid_hw is not None and tables.mid_hw != tuple(mid_hw)):
         raise ValueError(f'the tables were built for {tables.status.shape[0]} samples, canvas {tables.canvas_hw} -> {tables.mid_hw}; these are '
                          f'{b} samples of {canvas_hw or mid_hw}')
+    if n != b:
+        raise ValueError(f'{n} samples, {b} parameter rows')
     return b
-
-
-def _ragged_out(out, shape, dtype, device):
-    if out is None:
-        return torch.empty(shape, device=device, dtype=dtype)
-    if not isinstance(out, torch.Tensor) or tuple(out.shape) != tuple(shape) or out.dtype != dtype or out.device != device:
-        raise ValueError(f'out must be a {dtype} tensor of shape {tuple(shape)} on {device}')
-    return out
 
 
 @_on_operand_device
@@ -2019,23 +2007,15 @@ def resize_tables_ragged(params, canvas_hw, mid_hw, filter, ks_max, workspace=No
     0, M, filter, ks_max)``, integer for integer.  ``status``: 0 per sample, or a sum of ``RAGGED_STATUS`` codes -- an extent outside
     the canvas, a resized size below 1 or above ``mid_hw``, more taps than ``ks_max`` (an axis of ``in`` pixels has at most
     ``min(ksize, in)``); that sample's tables are empty and it comes out as pad fill.  Nothing is read back: capturable."""
-    from .utils import resample
     b = _ragged_params(params)
-    if filter not in resample.FILTERS:
-        raise ValueError(f'filter {filter!r}: expected one of {resample.FILTERS}')
+    code = _filter_code(filter)
     hm, wm = _ragged_hw(canvas_hw, 'canvas_hw')
     hc, wc = _ragged_hw(mid_hw, 'mid_hw')
     ks_max = int(ks_max)
     if ks_max < 1:
         raise ValueError(f'ks_max must be >= 1, got {ks_max}')
-    words = RaggedTables.words(b, (hc, wc), ks_max)
-    if workspace is None:
-        workspace = torch.empty(words, device=params.device, dtype=torch.int32)
-    elif (not isinstance(workspace, torch.Tensor) or workspace.dtype != torch.int32 or workspace.dim() != 1 or workspace.numel() < words
-          or workspace.device != params.device or not workspace.is_contiguous()):
-        raise ValueError(f'workspace must be a contiguous int32 vector of at least {words} elements on {params.device}')
-    t = RaggedTables.over(workspace, b, (hm, wm), (hc, wc), ks_max)
-    st = _hip.lib.hs_resize_tables_ragged_fwd(_hip.dev_ptr(params, 'params', torch.int32), b, hm, wm, hc, wc, _FILTER_CODES[filter], ks_max,
+    t = _tables_over(RaggedTables, workspace, b, (hm, wm), (hc, wc), ks_max, params.device)
+    st = _hip.lib.hs_resize_tables_ragged_fwd(_hip.dev_ptr(params, 'params', torch.int32), b, hm, wm, hc, wc, code, ks_max,
                                               t.bounds.data_ptr(), t.kk.data_ptr(), t.nearest.data_ptr(), t.status.data_ptr(),
                                               _hip.stream_ptr())
     _hip.check(st, 'hs_resize_tables_ragged_fwd')
@@ -2051,17 +2031,15 @@ def color_jitter_ragged(x_u8, params, table, layout='hwc', contrast=True, out=No
     ``False`` -- the caller's promise that no record names contrast -- the apply pass alone.  ``sums``: an int64 (B,) device tensor to use
     as the mean's workspace (default a new one).  Per sample the region holds ``utils.jitter.color_jitter_cpu`` of the cropped frame.
     Capturable."""
-    from .utils import jitter
-    hm, wm = _ragged_frames(x_u8, layout, 'canvas')
+    n, hm, wm = _frames_bhw(x_u8, layout, 'canvas')
+    _ragged_hw((hm, wm), 'canvas')
     b = _ragged_params(params, x_u8.device)
-    if x_u8.shape[0] != b:
-        raise ValueError(f'{x_u8.shape[0]} frames, {b} parameter rows')
-    if (not isinstance(table, torch.Tensor) or table.dtype != torch.int32 or tuple(table.shape) != (b, jitter.TABLE_WORDS)
-            or table.device != x_u8.device or not table.is_contiguous()):
-        raise ValueError(f'table must be a contiguous int32 tensor of shape {(b, jitter.TABLE_WORDS)} on {x_u8.device}')
-    out = _ragged_out(out, x_u8.shape, torch.uint8, x_u8.device)
+    if n != b:
+        raise ValueError(f'{n} frames, {b} parameter rows')
+    _jitter_table(table, b, x_u8.device)
+    out = _out(out, x_u8.shape, torch.uint8, x_u8.device)
     if contrast:
-        sums = _ragged_out(sums, (b,), torch.int64, x_u8.device)
+        sums = _out(sums, (b,), torch.int64, x_u8.device)
     st = _hip.lib.hs_color_jitter_ragged_fwd(_hip.dev_ptr(x_u8, 'canvas', torch.uint8), _LAYOUT_CODES[layout], b, hm, wm,
                                              _hip.dev_ptr(params, 'params', torch.int32), _hip.dev_ptr(table, 'table', torch.int32),
                                              _hip.dev_ptr(sums, 'sums', torch.int64) if contrast else None,
@@ -2077,12 +2055,10 @@ def frame_resize_ragged(x_u8, params, tables, layout='hwc', out=None):
     the filter ``tables`` (a :class:`RaggedTables` built from the same ``params``) were made for.  Returns the uint8 intermediate canvas
     (B, Hc, Wc, 3) / (B, 3, Hc, Wc) (``out``), the resized image at its top left: the bytes of ``frame_resize(region.flip(), (Hr, Wr))``;
     the pixels outside it are not specified.  Capturable."""
-    hm, wm = _ragged_frames(x_u8, layout, 'canvas')
-    b = _ragged_tables(tables, params, x_u8.device, canvas_hw=(hm, wm))
-    if x_u8.shape[0] != b:
-        raise ValueError(f'{x_u8.shape[0]} frames, {b} parameter rows')
+    n, hm, wm = _frames_bhw(x_u8, layout, 'canvas')
+    b = _ragged_tables(tables, params, n, x_u8.device, canvas_hw=(hm, wm))
     hc, wc = tables.mid_hw
-    out = _ragged_out(out, (b, hc, wc, 3) if layout == 'hwc' else (b, 3, hc, wc), torch.uint8, x_u8.device)
+    out = _frame_out(out, b, hc, wc, layout, None, x_u8.device)
     st = _hip.lib.hs_frame_resize_ragged_fwd(_hip.dev_ptr(x_u8, 'canvas', torch.uint8), _LAYOUT_CODES[layout], b, hm, wm,
                                              _hip.dev_ptr(params, 'params', torch.int32), tables.bounds.data_ptr(), tables.kk.data_ptr(),
                                              tables.status.data_ptr(), tables.ks_max, hc, wc, _hip.dev_ptr(out, 'out', torch.uint8),
@@ -2096,14 +2072,10 @@ def label_resize_ragged(t, params, tables, out=None):
     """:func:`label_resize_batch` for a ragged batch, one launch (hs_label_resize_ragged_fwd): labels (B, Hm, Wm), uint8 or int64 with
     values in 0..255, the region mirrored first where hflip says, through ``tables``' nearest indices.  Returns the uint8 intermediate
     canvas (B, Hc, Wc) (``out``), the resized label at its top left.  Capturable."""
-    if not isinstance(t, torch.Tensor) or t.dtype not in _LABEL_DTYPES or t.dim() != 3:
-        raise ValueError(f'labels must be uint8 or int64 (B, H, W), got {getattr(t, "dtype", type(t))} {tuple(getattr(t, "shape", ()))}')
-    hm, wm = _ragged_hw(t.shape[1:], 'labels')
-    b = _ragged_tables(tables, params, t.device, canvas_hw=(hm, wm))
-    if t.shape[0] != b:
-        raise ValueError(f'{t.shape[0]} labels, {b} parameter rows')
+    n, hm, wm = _labels_bhw(t)
+    b = _ragged_tables(tables, params, n, t.device, canvas_hw=(hm, wm))
     hc, wc = tables.mid_hw
-    out = _ragged_out(out, (b, hc, wc), torch.uint8, t.device)
+    out = _out(out, (b, hc, wc), torch.uint8, t.device)
     st = _hip.lib.hs_label_resize_ragged_fwd(_hip.dev_ptr(t, 'labels', t.dtype), _LABEL_DTYPES[t.dtype], b, hm, wm,
                                              _hip.dev_ptr(params, 'params', torch.int32), tables.nearest.data_ptr(), tables.status.data_ptr(),
                                              hc, wc, _hip.dev_ptr(out, 'out', torch.uint8), _hip.stream_ptr())
@@ -2120,26 +2092,17 @@ def frame_rotate_ragged(x_u8, params, tables, matrices, layout='hwc', size=None,
     is not 0.  Returns uint8 in the input's layout, or with ``norm`` float32 (B, 3, Ho, Wo) through its table; ``out`` likewise.
     Capturable."""
     from .utils import rotate
-    hc, wc = _ragged_frames(x_u8, layout, 'canvas')
-    b = _ragged_tables(tables, params, x_u8.device, mid_hw=(hc, wc))
-    if x_u8.shape[0] != b:
-        raise ValueError(f'{x_u8.shape[0]} frames, {b} parameter rows')
-    if norm is not None and norm.layout != layout:
-        raise ValueError(f"norm describes '{norm.layout}' frames, these are '{layout}'")
+    n, hc, wc = _frames_bhw(x_u8, layout, 'canvas')
+    b = _ragged_tables(tables, params, n, x_u8.device, mid_hw=(hc, wc))
     ho, wo = (hc, wc) if size is None else _ragged_hw(size, 'size')
-    fill, pad_fill = rotate.check_fill(fill), rotate.check_fill(pad_fill, 'pad_fill')
+    fill, pad_fill = _fill_word(fill), _fill_word(pad_fill, 'pad_fill')
     rotate.check_table(matrices, b, torch.float64, x_u8.device)
-    if norm is not None:
-        shape, dtype = (b, 3, ho, wo), torch.float32
-    else:
-        shape, dtype = ((b, ho, wo, 3) if layout == 'hwc' else (b, 3, ho, wo)), torch.uint8
-    out = _ragged_out(out, shape, dtype, x_u8.device)
+    out = _frame_out(out, b, ho, wo, layout, norm, x_u8.device)
+    table = _norm_table(norm, layout, x_u8.device)
     st = _hip.lib.hs_frame_rotate_ragged_fwd(_hip.dev_ptr(x_u8, 'canvas', torch.uint8), _LAYOUT_CODES[layout], b, hc, wc,
                                              _hip.dev_ptr(params, 'params', torch.int32), tables.status.data_ptr(),
-                                             _hip.dev_ptr(matrices, 'matrices', torch.float64), ho, wo,
-                                             fill[0] | fill[1] << 8 | fill[2] << 16, pad_fill[0] | pad_fill[1] << 8 | pad_fill[2] << 16,
-                                             None if norm is None else _hip.dev_ptr(norm.table(x_u8.device), 'table'),
-                                             _hip.dev_ptr(out, 'out', dtype), _hip.stream_ptr())
+                                             _hip.dev_ptr(matrices, 'matrices', torch.float64), ho, wo, fill, pad_fill,
+                                             table, _hip.dev_ptr(out, 'out', out.dtype), _hip.stream_ptr())
     _hip.check(st, 'hs_frame_rotate_ragged_fwd')
     return out
 
@@ -2151,22 +2114,12 @@ def label_rotate_ragged(t, params, tables, fixed, size=None, fill=0, pad_fill=25
     ``size`` with ``pad_fill`` (everywhere for a sample whose status is not 0).  Returns int64 (B, Ho, Wo), or ``out``'s dtype (uint8 |
     int64).  Capturable."""
     from .utils import rotate
-    if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or t.dim() != 3:
-        raise ValueError(f'the intermediate labels must be uint8 (B, H, W), got {getattr(t, "dtype", type(t))} {tuple(getattr(t, "shape", ()))}')
-    hc, wc = _ragged_hw(t.shape[1:], 'labels')
-    b = _ragged_tables(tables, params, t.device, mid_hw=(hc, wc))
-    if t.shape[0] != b:
-        raise ValueError(f'{t.shape[0]} labels, {b} parameter rows')
+    n, hc, wc = _labels_bhw(t, (torch.uint8,), 'the intermediate labels')
+    b = _ragged_tables(tables, params, n, t.device, mid_hw=(hc, wc))
     ho, wo = (hc, wc) if size is None else _ragged_hw(size, 'size')
     rotate.check_table(fixed, b, torch.int32, t.device)
-    if out is None:
-        out = torch.empty((b, ho, wo), device=t.device, dtype=torch.int64)
-    elif not isinstance(out, torch.Tensor) or tuple(out.shape) != (b, ho, wo) or out.dtype not in _LABEL_DTYPES or out.device != t.device:
-        raise ValueError(f'out must be a uint8 or int64 tensor of shape {(b, ho, wo)} on {t.device}')
-    fill, pad_fill = int(fill), int(pad_fill)
-    for name, f in (('fill', fill), ('pad_fill', pad_fill)):
-        if not (0 <= f <= 255 or (out.dtype == torch.int64 and -2 ** 31 <= f < 2 ** 31)):
-            raise ValueError(f'{name} {f} does not fit the output labels')
+    out = _label_out(out, (b, ho, wo), torch.int64, t.device)
+    fill, pad_fill = _label_fill(fill, out), _label_fill(pad_fill, out, 'pad_fill')
     st = _hip.lib.hs_label_rotate_ragged_fwd(_hip.dev_ptr(t, 'labels', torch.uint8), b, hc, wc, _hip.dev_ptr(params, 'params', torch.int32),
                                              tables.status.data_ptr(), _hip.dev_ptr(fixed, 'fixed', torch.int32), ho, wo, fill, pad_fill,
                                              _hip.dev_ptr(out, 'out', out.dtype), _LABEL_DTYPES[out.dtype], _hip.stream_ptr())
