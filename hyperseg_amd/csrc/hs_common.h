@@ -134,6 +134,23 @@ template <> struct Pair<f16_t> {
     static __device__ __forceinline__ void st(f16_t* p, size_t i, float a, float b) { *reinterpret_cast<uint32_t*>(p + i) = pack(a, b); }
 };
 
+// Host side: the ONE place an HS_DTYPE_* code picks a kernel instantiation.  with_storage calls f with a value of the code's storage type
+// (the launch is written once: `using T = decltype(tag);` ... kernel<T>, (const T*)x, (T*)y) and returns true; for any other code it calls
+// nothing and returns false -- an extern "C" entry answers that with HS_ERR_BAD_ARG before its first launch or memset, a try_fast_* route
+// with 1 ("not taken").  with_half_storage: the launchers that exist for the two 16-bit types only.  always_inline: the call site compiles to the plain switch
+// (an eager training step is ~150 host-bound launches; the fan-out launchers would otherwise keep one out-of-line copy per arm).
+inline bool storage_known(int dtype) { return dtype == HS_DTYPE_F32 || dtype == HS_DTYPE_BF16 || dtype == HS_DTYPE_F16; }
+inline int storage_bytes(int dtype) { return dtype == HS_DTYPE_F32 ? 4 : 2; }          // of a known code
+template <typename F> __attribute__((always_inline)) inline bool with_half_storage(int dtype, F&& f) {
+    if (dtype == HS_DTYPE_BF16) { f(bf16_t{}); return true; }
+    if (dtype == HS_DTYPE_F16) { f(f16_t{}); return true; }
+    return false;
+}
+template <typename F> __attribute__((always_inline)) inline bool with_storage(int dtype, F&& f) {
+    if (dtype == HS_DTYPE_F32) { f(float{}); return true; }
+    return with_half_storage(dtype, f);
+}
+
 // Slices a training-mode BatchNorm channel is cut into: partial[(c * BN_CHUNKS + chunk) * 2 + {0, 1}] = {sum, sum of squares} of
 // (x - shift) over the slice, shift = the channel's first element (hs_train_aux.hip: bn_stats_kernel; consumers that normalise on load
 // re-derive mean / invstd from the 32 pairs: hs_patch_conv_bwd.hip dw_tiles_*).

@@ -591,18 +591,15 @@ int launch_conv1x1_h16(int dtype, const void* x, int batch, int cin, int H, int 
     while (split < 64 && outs * split * 2 <= CONV_THREADS && split * 2 <= cin) split *= 2;
     f.split = split;
     const dim3 grid((unsigned)((long)batch * fh * fw));
-    auto go = [&](auto h) {
+    const bool half = with_half_storage(dtype, [&](auto h) {
         using T = decltype(h);
         if (ph == pw && ph == 1) hipLaunchKernelGGL((patch_conv1x1_kernel<0, T>), grid, dim3(CONV_THREADS), lds1, stream, f);
         else if (ph == pw && ph == 2) hipLaunchKernelGGL((patch_conv1x1_kernel<1, T>), grid, dim3(CONV_THREADS), lds1, stream, f);
         else if (ph == pw && ph == 4) hipLaunchKernelGGL((patch_conv1x1_kernel<2, T>), grid, dim3(CONV_THREADS), lds1, stream, f);
         else if (ph == pw && ph == 8) hipLaunchKernelGGL((patch_conv1x1_kernel<3, T>), grid, dim3(CONV_THREADS), lds1, stream, f);
         else hipLaunchKernelGGL((patch_conv1x1_kernel<-1, T>), grid, dim3(CONV_THREADS), lds1, stream, f);
-    };
-    if (dtype == HS_DTYPE_BF16) go(bf16_t{});
-    else if (dtype == HS_DTYPE_F16) go(f16_t{});
-    else return 1;
-    return launch_status();
+    });
+    return half ? launch_status() : 1;
 }
 }  // namespace hs
 
@@ -707,28 +704,23 @@ extern "C" int hs_stage_input_typed_fwd(const hs_stage_input* in, int32_t prev_d
     int st = make_stage(in, &s);
     if (st != HS_OK) return st;
     if (!y) return HS_ERR_BAD_ARG;
-    auto known = [](int d) { return d == HS_DTYPE_F32 || d == HS_DTYPE_BF16 || d == HS_DTYPE_F16; };
-    if (!known(prev_dtype) || !known(out_dtype)) return HS_ERR_BAD_ARG;
-    if (prev_dtype != HS_DTYPE_F32 && out_dtype != HS_DTYPE_F32 && prev_dtype != out_dtype) return HS_ERR_BAD_ARG;     // one half type per step
+    if (!storage_known(prev_dtype) || !storage_known(out_dtype)) return HS_ERR_BAD_ARG;
+    if (storage_bytes(prev_dtype) == 2 && storage_bytes(out_dtype) == 2 && prev_dtype != out_dtype) return HS_ERR_BAD_ARG;     // one half type per step
     const size_t n = (size_t)s.B * s.cin() * s.H * s.W;
     const dim3 blocks((unsigned)((n + 255) / 256 > 8192 ? 8192 : (n + 255) / 256));
     hipStream_t q = (hipStream_t)stream;
     const bool planes = (long)s.B * s.cin() <= 65535;
     const dim3 g2((s.W + 63) / 64, (s.H + 15) / 16, s.B * s.cin());                  // four rows per thread
-    auto go = [&](auto tp, auto to) {
-        using TP = decltype(tp); using TO = decltype(to);
-        if (planes) hipLaunchKernelGGL((stage_input_plane_kernel<TP, TO>), g2, dim3(256), 0, q, s, (TO*)y);
-        else hipLaunchKernelGGL((stage_input_kernel<TP, TO>), blocks, dim3(256), 0, q, s, (TO*)y);
-    };
-    const int half = prev_dtype != HS_DTYPE_F32 ? prev_dtype : out_dtype;           // the step's half type (or F32: none)
-    auto with_half = [&](auto h) {
-        if (prev_dtype == HS_DTYPE_F32 && out_dtype == HS_DTYPE_F32) go(float{}, float{});
-        else if (prev_dtype == HS_DTYPE_F32) go(float{}, h);
-        else if (out_dtype == HS_DTYPE_F32) go(h, float{});
-        else go(h, h);
-    };
-    if (half == HS_DTYPE_F16) with_half(f16_t{});
-    else with_half(bf16_t{});
+    with_storage(prev_dtype, [&](auto tp) {
+        with_storage(out_dtype, [&](auto to) {
+            using TP = decltype(tp); using TO = decltype(to);
+            // the mixed pairs (bf16, f16) / (f16, bf16) were rejected above: no kernel is built for them
+            if constexpr (std::is_same<TP, float>::value || std::is_same<TO, float>::value || std::is_same<TP, TO>::value) {
+                if (planes) hipLaunchKernelGGL((stage_input_plane_kernel<TP, TO>), g2, dim3(256), 0, q, s, (TO*)y);
+                else hipLaunchKernelGGL((stage_input_kernel<TP, TO>), blocks, dim3(256), 0, q, s, (TO*)y);
+            }
+        });
+    });
     return launch_status();
 }
 
@@ -755,7 +747,7 @@ extern "C" int hs_upsample_argmax_fwd(const float* x, int32_t batch, int32_t cha
 // bf16 / fp16 storage in and out (dtype: HS_DTYPE_BF16 | HS_DTYPE_F16); the exact-2x shapes with an even width take the 2 x 4 block kernel
 static int upsample_bilinear_h16(int dtype, const void* x, int batch, int channels, int Hi, int Wi, int Ho, int Wo, void* y, hipStream_t stream) {
     if (!x || !y || batch <= 0 || channels <= 0 || Hi <= 0 || Wi <= 0 || Ho <= 0 || Wo <= 0) return HS_ERR_BAD_ARG;
-    auto go = [&](auto h) {
+    const bool half = with_half_storage(dtype, [&](auto h) {
         using T = decltype(h);
         if (is_exact2x(Hi, Wi, Ho, Wo) && (((size_t)y) & 7) == 0) {          // rows of 4 k outputs: 8-byte stores
             const size_t n2 = (size_t)batch * channels * Hi * (Wi / 2);
@@ -767,11 +759,8 @@ static int upsample_bilinear_h16(int dtype, const void* x, int batch, int channe
         const unsigned blocks = (unsigned)((n + 255) / 256 > 16384 ? 16384 : (n + 255) / 256);
         hipLaunchKernelGGL(upsample_bilinear_h16_kernel<T>, dim3(blocks), dim3(256), 0, stream,
                            (const T*)x, batch * channels, Hi, Wi, Ho, Wo, (float)Hi / (float)Ho, (float)Wi / (float)Wo, (T*)y);
-    };
-    if (dtype == HS_DTYPE_BF16) go(bf16_t{});
-    else if (dtype == HS_DTYPE_F16) go(f16_t{});
-    else return HS_ERR_BAD_ARG;
-    return launch_status();
+    });
+    return half ? launch_status() : HS_ERR_BAD_ARG;
 }
 
 extern "C" int hs_upsample_bilinear_bf16_fwd(const void* x, int32_t batch, int32_t channels, int32_t Hi, int32_t Wi,

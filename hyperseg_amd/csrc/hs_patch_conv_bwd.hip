@@ -1111,7 +1111,7 @@ void dw_tiles_bwd_w_kernel(DwtArgs a, DwtBn n, const T* __restrict__ t, const T*
 
 static int dwt_args(DwtArgs& a, int dtype, const void* p, const void* q, long ld, int B, int C, int H, int W, int fh, int fw, int pm) {
     if (!p || !q || B <= 0 || C <= 0 || H <= 0 || W <= 0 || fh <= 0 || fw <= 0 || ld < 9L * C) return HS_ERR_BAD_ARG;
-    if (dtype != HS_DTYPE_F32 && dtype != HS_DTYPE_BF16 && dtype != HS_DTYPE_F16) return HS_ERR_BAD_ARG;
+    if (!storage_known(dtype)) return HS_ERR_BAD_ARG;
     if (H % fh || W % fw) return HS_ERR_NOT_DIVISIBLE;
     const int ph = H / fh, pw = W / fw;
     // pairs: even patch width (then W and the tile image's width are even too); 8-byte aligned tensors; div_by_inv's range
@@ -1137,26 +1137,27 @@ static void fast_args(ConvBwdArgs& a, const void* bank, long ld, int batch, int 
 static bool dw3_pairs(const ConvBwdArgs& a, const void* p, const void* q) {
     return (a.pw & 1) == 0 && (a.W & 1) == 0 && ((((size_t)p) | ((size_t)q)) & 7) == 0 && a.H < (1 << 21) && a.W < (1 << 21) && (long)a.B * a.cin < (1 << 21);
 }
-#define HS_T2(dtype, F32, BF16, F16) do { if ((dtype) == HS_DTYPE_F32) { F32; } else if ((dtype) == HS_DTYPE_F16) { F16; } else { BF16; } } while (0)
 
 int hs::try_fast_fwd(int dtype, const void* x, const void* bank, long ld, int batch, int c_in, int H, int W, int fh, int fw, int c_out,
                      int k, int pad, int pad_mode, int groups, const float* scale, const float* shift, int act, void* y, hipStream_t stream) {
-    if (H % fh || W % fw || (dtype != HS_DTYPE_F32 && dtype != HS_DTYPE_BF16 && dtype != HS_DTYPE_F16)) return 1;
+    if (H % fh || W % fw || !storage_known(dtype)) return 1;
     ConvBwdArgs a;
     fast_args(a, bank, ld, batch, c_in, H, W, fh, fw, c_out);
     if (k == 3 && pad == 1 && pad_mode == HS_PAD_ZEROS && groups == c_in && c_in == c_out && !scale && act == HS_ACT_NONE &&
         (long)batch * c_in <= 65535) {                                  // plain depthwise 3x3 (the autograd path's middle layer)
         if (dw3_pairs(a, x, y)) {
             const dim3 grid2((W / 2 + 63) / 64, (H + 3) / 4, batch * c_in);
-            HS_T2(dtype, hipLaunchKernelGGL((patch_dw3_pair_kernel<0, float>), grid2, dim3(256), 0, stream, a, (const float*)x, (float*)y),
-                         hipLaunchKernelGGL((patch_dw3_pair_kernel<0, bf16_t>), grid2, dim3(256), 0, stream, a, (const bf16_t*)x, (bf16_t*)y),
-                         hipLaunchKernelGGL((patch_dw3_pair_kernel<0, f16_t>), grid2, dim3(256), 0, stream, a, (const f16_t*)x, (f16_t*)y));
+            with_storage(dtype, [&](auto tag) {
+                using T = decltype(tag);
+                hipLaunchKernelGGL((patch_dw3_pair_kernel<0, T>), grid2, dim3(256), 0, stream, a, (const T*)x, (T*)y);
+            });
             return launch_status();
         }
         const dim3 grid((W + 63) / 64, (H + 3) / 4, batch * c_in);
-        HS_T2(dtype, hipLaunchKernelGGL((patch_dw3_kernel<0, float>), grid, dim3(256), 0, stream, a, (const float*)x, (float*)y),
-                     hipLaunchKernelGGL((patch_dw3_kernel<0, bf16_t>), grid, dim3(256), 0, stream, a, (const bf16_t*)x, (bf16_t*)y),
-                     hipLaunchKernelGGL((patch_dw3_kernel<0, f16_t>), grid, dim3(256), 0, stream, a, (const f16_t*)x, (f16_t*)y));
+        with_storage(dtype, [&](auto tag) {
+            using T = decltype(tag);
+            hipLaunchKernelGGL((patch_dw3_kernel<0, T>), grid, dim3(256), 0, stream, a, (const T*)x, (T*)y);
+        });
         return launch_status();
     }
     if (k != 1 || groups != 1 || a.ph * a.pw < 64) return 1;
@@ -1168,9 +1169,8 @@ int hs::try_fast_fwd(int dtype, const void* x, const void* bank, long ld, int ba
     const bool px2 = dw3_pairs(a, x, y) && a.ph * a.pw >= 128;
     const bool affine = scale != nullptr || act != HS_ACT_NONE;
     if (affine && (!scale || !shift)) return 1;                         // an activation without the affine rows: the generic kernel
-#define HS_FW_L(MTV, KQV, PXV, AFV) HS_T2(dtype, hipLaunchKernelGGL((patch_conv_fwd_k1m_kernel<MTV, KQV, PXV, AFV, float>), grid, dim3(256), 0, stream, a, scale, shift, act), \
-                                                 hipLaunchKernelGGL((patch_conv_fwd_k1m_kernel<MTV, KQV, PXV, AFV, bf16_t>), grid, dim3(256), 0, stream, a, scale, shift, act), \
-                                                 hipLaunchKernelGGL((patch_conv_fwd_k1m_kernel<MTV, KQV, PXV, AFV, f16_t>), grid, dim3(256), 0, stream, a, scale, shift, act))
+#define HS_FW_L(MTV, KQV, PXV, AFV) with_storage(dtype, [&](auto tag) { \
+        hipLaunchKernelGGL((patch_conv_fwd_k1m_kernel<MTV, KQV, PXV, AFV, decltype(tag)>), grid, dim3(256), 0, stream, a, scale, shift, act); })
 #define HS_FW(MTV, KQV) if (mt == MTV && kq == KQV) { \
         if (px2 && affine) HS_FW_L(MTV, KQV, 2, true); else if (px2) HS_FW_L(MTV, KQV, 2, false); \
         else if (affine) HS_FW_L(MTV, KQV, 1, true); else HS_FW_L(MTV, KQV, 1, false); \
@@ -1184,29 +1184,31 @@ int hs::try_fast_fwd(int dtype, const void* x, const void* bank, long ld, int ba
 
 int hs::try_fast_bwd_in(int dtype, const void* dy, const void* bank, long ld, int batch, int c_in, int H, int W, int fh, int fw,
                         int c_out, int k, int pad, int pad_mode, int groups, void* dx, hipStream_t stream) {
-    if (H % fh || W % fw || (dtype != HS_DTYPE_F32 && dtype != HS_DTYPE_BF16 && dtype != HS_DTYPE_F16)) return 1;
+    if (H % fh || W % fw || !storage_known(dtype)) return 1;
     ConvBwdArgs a;
     fast_args(a, bank, ld, batch, c_in, H, W, fh, fw, c_out);
     a.dy = (const float*)dy; a.dx = (float*)dx;
     if (k == 3 && pad == 1 && pad_mode == HS_PAD_ZEROS && groups == c_in && c_in == c_out && (long)batch * c_in <= 65535) {
         if (dw3_pairs(a, dy, dx)) {
             const dim3 grid2((W / 2 + 63) / 64, (H + 3) / 4, batch * c_in);
-            HS_T2(dtype, hipLaunchKernelGGL((patch_dw3_pair_kernel<1, float>), grid2, dim3(256), 0, stream, a, (const float*)dy, (float*)dx),
-                         hipLaunchKernelGGL((patch_dw3_pair_kernel<1, bf16_t>), grid2, dim3(256), 0, stream, a, (const bf16_t*)dy, (bf16_t*)dx),
-                         hipLaunchKernelGGL((patch_dw3_pair_kernel<1, f16_t>), grid2, dim3(256), 0, stream, a, (const f16_t*)dy, (f16_t*)dx));
+            with_storage(dtype, [&](auto tag) {
+                using T = decltype(tag);
+                hipLaunchKernelGGL((patch_dw3_pair_kernel<1, T>), grid2, dim3(256), 0, stream, a, (const T*)dy, (T*)dx);
+            });
             return launch_status();
         }
         const dim3 grid((W + 63) / 64, (H + 3) / 4, batch * c_in);
-        HS_T2(dtype, hipLaunchKernelGGL((patch_dw3_kernel<1, float>), grid, dim3(256), 0, stream, a, (const float*)dy, (float*)dx),
-                     hipLaunchKernelGGL((patch_dw3_kernel<1, bf16_t>), grid, dim3(256), 0, stream, a, (const bf16_t*)dy, (bf16_t*)dx),
-                     hipLaunchKernelGGL((patch_dw3_kernel<1, f16_t>), grid, dim3(256), 0, stream, a, (const f16_t*)dy, (f16_t*)dx));
+        with_storage(dtype, [&](auto tag) {
+            using T = decltype(tag);
+            hipLaunchKernelGGL((patch_dw3_kernel<1, T>), grid, dim3(256), 0, stream, a, (const T*)dy, (T*)dx);
+        });
         return launch_status();
     }
     if (k == 1 && groups == 1 && a.ph * a.pw < 16 && c_out <= 1024) {
         const dim3 gridt((unsigned)(batch * fh * fw));
-        HS_T2(dtype, hipLaunchKernelGGL(patch_conv_bwd_input_tiny_kernel<float>, gridt, dim3(128), (size_t)c_out * 64, stream, a),
-                     hipLaunchKernelGGL(patch_conv_bwd_input_tiny_kernel<bf16_t>, gridt, dim3(128), (size_t)c_out * 64, stream, a),
-                     hipLaunchKernelGGL(patch_conv_bwd_input_tiny_kernel<f16_t>, gridt, dim3(128), (size_t)c_out * 64, stream, a));
+        with_storage(dtype, [&](auto tag) {
+            hipLaunchKernelGGL(patch_conv_bwd_input_tiny_kernel<decltype(tag)>, gridt, dim3(128), (size_t)c_out * 64, stream, a);
+        });
         return launch_status();
     }
     if (k != 1 || groups != 1 || a.ph * a.pw < 16) return 1;
@@ -1214,12 +1216,11 @@ int hs::try_fast_bwd_in(int dtype, const void* dy, const void* bank, long ld, in
     const dim3 grid((unsigned)(batch * fh * fw));
     const bool px2 = dw3_pairs(a, dy, dx) && a.ph * a.pw >= 128;
 #define HS_BI(CTV, KQV) if (ct == CTV && kq == KQV) { \
-        if (px2) HS_T2(dtype, hipLaunchKernelGGL((patch_conv_bwd_input_k1m_kernel<CTV, KQV, 2, float>), grid, dim3(256), 0, stream, a), \
-                              hipLaunchKernelGGL((patch_conv_bwd_input_k1m_kernel<CTV, KQV, 2, bf16_t>), grid, dim3(256), 0, stream, a), \
-                              hipLaunchKernelGGL((patch_conv_bwd_input_k1m_kernel<CTV, KQV, 2, f16_t>), grid, dim3(256), 0, stream, a)); \
-        else HS_T2(dtype, hipLaunchKernelGGL((patch_conv_bwd_input_k1m_kernel<CTV, KQV, 1, float>), grid, dim3(256), 0, stream, a), \
-                          hipLaunchKernelGGL((patch_conv_bwd_input_k1m_kernel<CTV, KQV, 1, bf16_t>), grid, dim3(256), 0, stream, a), \
-                          hipLaunchKernelGGL((patch_conv_bwd_input_k1m_kernel<CTV, KQV, 1, f16_t>), grid, dim3(256), 0, stream, a)); \
+        with_storage(dtype, [&](auto tag) { \
+            using T = decltype(tag); \
+            if (px2) hipLaunchKernelGGL((patch_conv_bwd_input_k1m_kernel<CTV, KQV, 2, T>), grid, dim3(256), 0, stream, a); \
+            else hipLaunchKernelGGL((patch_conv_bwd_input_k1m_kernel<CTV, KQV, 1, T>), grid, dim3(256), 0, stream, a); \
+        }); \
         return launch_status(); }
     HS_BI(1, 1) HS_BI(1, 2) HS_BI(1, 3) HS_BI(1, 4) HS_BI(2, 1) HS_BI(2, 2) HS_BI(2, 3) HS_BI(2, 4)
     HS_BI(3, 1) HS_BI(3, 2) HS_BI(3, 3) HS_BI(3, 4) HS_BI(4, 1) HS_BI(4, 2) HS_BI(4, 3) HS_BI(6, 1) HS_BI(6, 2)
@@ -1229,53 +1230,46 @@ int hs::try_fast_bwd_in(int dtype, const void* dy, const void* bank, long ld, in
 
 int hs::try_fast_bwd_w(int dtype, const void* x, const void* dy, int batch, int c_in, int H, int W, int fh, int fw, int c_out, int k,
                        int pad, int pad_mode, int groups, void* dbank, long ld, hipStream_t stream) {
-    if (H % fh || W % fw || (dtype != HS_DTYPE_F32 && dtype != HS_DTYPE_BF16 && dtype != HS_DTYPE_F16)) return 1;
+    if (H % fh || W % fw || !storage_known(dtype)) return 1;
     ConvBwdArgs a;
     fast_args(a, nullptr, ld, batch, c_in, H, W, fh, fw, c_out);
     a.x = (const float*)x; a.dy = (const float*)dy; a.dbank = (float*)dbank;
     if (k == 3 && pad == 1 && pad_mode == HS_PAD_ZEROS && groups == c_in && c_in == c_out && (c_in + 3) / 4 <= 65535) {
         const dim3 grid((unsigned)(batch * fh * fw), (c_in + 3) / 4);
-        if (dw3_pairs(a, x, dy)) {
-            HS_T2(dtype, hipLaunchKernelGGL(patch_dw3_bwd_weight_pair_kernel<float>, grid, dim3(256), 0, stream, a),
-                         hipLaunchKernelGGL(patch_dw3_bwd_weight_pair_kernel<bf16_t>, grid, dim3(256), 0, stream, a),
-                         hipLaunchKernelGGL(patch_dw3_bwd_weight_pair_kernel<f16_t>, grid, dim3(256), 0, stream, a));
-            return launch_status();
-        }
-        HS_T2(dtype, hipLaunchKernelGGL(patch_dw3_bwd_weight_kernel<float>, grid, dim3(256), 0, stream, a),
-                     hipLaunchKernelGGL(patch_dw3_bwd_weight_kernel<bf16_t>, grid, dim3(256), 0, stream, a),
-                     hipLaunchKernelGGL(patch_dw3_bwd_weight_kernel<f16_t>, grid, dim3(256), 0, stream, a));
+        const bool pair = dw3_pairs(a, x, dy);
+        with_storage(dtype, [&](auto tag) {
+            using T = decltype(tag);
+            if (pair) hipLaunchKernelGGL(patch_dw3_bwd_weight_pair_kernel<T>, grid, dim3(256), 0, stream, a);
+            else hipLaunchKernelGGL(patch_dw3_bwd_weight_kernel<T>, grid, dim3(256), 0, stream, a);
+        });
         return launch_status();
     }
     if (k == 1 && groups == 1 && a.ph * a.pw < 16 && (long)c_out * c_in < (1 << 21) && (size_t)(c_out + c_in) * 17 * 4 <= 64 * 1024) {
         const dim3 gridt((unsigned)(batch * fh * fw));
         const size_t lds = (size_t)(c_out + c_in) * 17 * 4;
-        HS_T2(dtype, hipLaunchKernelGGL(patch_conv_bwd_weight_tiny_kernel<float>, gridt, dim3(256), lds, stream, a),
-                     hipLaunchKernelGGL(patch_conv_bwd_weight_tiny_kernel<bf16_t>, gridt, dim3(256), lds, stream, a),
-                     hipLaunchKernelGGL(patch_conv_bwd_weight_tiny_kernel<f16_t>, gridt, dim3(256), lds, stream, a));
+        with_storage(dtype, [&](auto tag) {
+            hipLaunchKernelGGL(patch_conv_bwd_weight_tiny_kernel<decltype(tag)>, gridt, dim3(256), lds, stream, a);
+        });
         return launch_status();
     }
     if (k != 1 || groups != 1 || a.ph * a.pw < 16) return 1;
     const bool vec = (a.pw & 3) == 0 && ((a.ph * a.pw) & 15) == 0 && (W & 3) == 0 &&
-                     ((((size_t)x) | ((size_t)dy)) & (dtype == HS_DTYPE_F32 ? 15 : 7)) == 0;           // four elements per load, either storage type
+                     ((((size_t)x) | ((size_t)dy)) & (4 * storage_bytes(dtype) - 1)) == 0;           // four elements per load, either storage type
     const int mt = (c_out + 15) / 16, nt = (c_in + 15) / 16;
     const dim3 grid((unsigned)(batch * fh * fw));
     const bool pairs = !vec && (a.pw & 1) == 0 && (W & 1) == 0 && ((((size_t)x) | ((size_t)dy)) & 7) == 0;       // either storage type
 #define HS_BW(MTV, NTV) if (mt == MTV && nt == NTV) { \
-        if (vec) HS_T2(dtype, hipLaunchKernelGGL((patch_conv_bwd_weight_k1m_kernel<MTV, NTV, 1, float>), grid, dim3(256), 0, stream, a, ConvBn{}), \
-                              hipLaunchKernelGGL((patch_conv_bwd_weight_k1m_kernel<MTV, NTV, 1, bf16_t>), grid, dim3(256), 0, stream, a, ConvBn{}), \
-                              hipLaunchKernelGGL((patch_conv_bwd_weight_k1m_kernel<MTV, NTV, 1, f16_t>), grid, dim3(256), 0, stream, a, ConvBn{})); \
-        else if (pairs) HS_T2(dtype, hipLaunchKernelGGL((patch_conv_bwd_weight_k1m_kernel<MTV, NTV, 2, float>), grid, dim3(256), 0, stream, a, ConvBn{}), \
-                                     hipLaunchKernelGGL((patch_conv_bwd_weight_k1m_kernel<MTV, NTV, 2, bf16_t>), grid, dim3(256), 0, stream, a, ConvBn{}), \
-                                     hipLaunchKernelGGL((patch_conv_bwd_weight_k1m_kernel<MTV, NTV, 2, f16_t>), grid, dim3(256), 0, stream, a, ConvBn{})); \
-        else HS_T2(dtype, hipLaunchKernelGGL((patch_conv_bwd_weight_k1m_kernel<MTV, NTV, 0, float>), grid, dim3(256), 0, stream, a, ConvBn{}), \
-                          hipLaunchKernelGGL((patch_conv_bwd_weight_k1m_kernel<MTV, NTV, 0, bf16_t>), grid, dim3(256), 0, stream, a, ConvBn{}), \
-                          hipLaunchKernelGGL((patch_conv_bwd_weight_k1m_kernel<MTV, NTV, 0, f16_t>), grid, dim3(256), 0, stream, a, ConvBn{})); \
+        with_storage(dtype, [&](auto tag) { \
+            using T = decltype(tag); \
+            if (vec) hipLaunchKernelGGL((patch_conv_bwd_weight_k1m_kernel<MTV, NTV, 1, T>), grid, dim3(256), 0, stream, a, ConvBn{}); \
+            else if (pairs) hipLaunchKernelGGL((patch_conv_bwd_weight_k1m_kernel<MTV, NTV, 2, T>), grid, dim3(256), 0, stream, a, ConvBn{}); \
+            else hipLaunchKernelGGL((patch_conv_bwd_weight_k1m_kernel<MTV, NTV, 0, T>), grid, dim3(256), 0, stream, a, ConvBn{}); \
+        }); \
         return launch_status(); }
     HS_BW(1, 1) HS_BW(1, 2) HS_BW(1, 3) HS_BW(1, 4) HS_BW(2, 1) HS_BW(2, 2) HS_BW(2, 3) HS_BW(2, 4) HS_BW(3, 1) HS_BW(3, 2) HS_BW(4, 1) HS_BW(4, 2)
 #undef HS_BW
     return 1;
 }
-#undef HS_T2
 
 static int fill_bwd(ConvBwdArgs& a, const float* x, const float* dy, const float* bank, int64_t ld, int32_t batch,
                     int32_t c_in, int32_t H, int32_t W, int32_t fh, int32_t fw, int32_t c_out, int32_t k, int32_t pad,
@@ -1369,9 +1363,10 @@ extern "C" int hs_dw_tiles_fwd(int32_t dtype, const void* tiled, const float* ba
     if (!bank || (((size_t)bank) & 3)) return HS_ERR_BAD_ARG;
     a.bank = bank;
     const dim3 grid((W / 2 + 63) / 64, (H + 3) / 4, batch * channels);
-    if (dtype == HS_DTYPE_F32) hipLaunchKernelGGL((dw_tiles_fwd_kernel<float, false>), grid, dim3(256), 0, (hipStream_t)stream, a, DwtBn{}, (const float*)tiled, (float*)y);
-    else if (dtype == HS_DTYPE_F16) hipLaunchKernelGGL((dw_tiles_fwd_kernel<f16_t, false>), grid, dim3(256), 0, (hipStream_t)stream, a, DwtBn{}, (const f16_t*)tiled, (f16_t*)y);
-    else hipLaunchKernelGGL((dw_tiles_fwd_kernel<bf16_t, false>), grid, dim3(256), 0, (hipStream_t)stream, a, DwtBn{}, (const bf16_t*)tiled, (bf16_t*)y);
+    with_storage(dtype, [&](auto tag) {
+        using T = decltype(tag);
+        hipLaunchKernelGGL((dw_tiles_fwd_kernel<T, false>), grid, dim3(256), 0, (hipStream_t)stream, a, DwtBn{}, (const T*)tiled, (T*)y);
+    });
     return launch_status();
 }
 
@@ -1398,24 +1393,16 @@ extern "C" int hs_dw_tiles_bn_fwd(int32_t dtype, const void* tiled, const float*
     a.bank = bank;
     DwtBn n{bn_partial, gamma, beta, save_mean, save_invstd, running_mean, running_var, (long long*)num_batches_tracked, eps, momentum, 0.f, 0, act};
     dwt_bn_geometry(a, n);
-    if ((a.ph & 3) == 0 && HS_DWT_FWD_RPT4) {       // four output rows per thread (round 6): six tile rows for four outputs rows instead of eight
-        const dim3 grid4((W / 2 + 63) / 64, (H / 4 + 3) / 4, batch * channels);
-        if (dtype == HS_DTYPE_F32) hipLaunchKernelGGL((dw_tiles_fwd_kernel<float, true, 4>), grid4, dim3(256), 0, (hipStream_t)stream, a, n, (const float*)tiled, (float*)y);
-        else if (dtype == HS_DTYPE_F16) hipLaunchKernelGGL((dw_tiles_fwd_kernel<f16_t, true, 4>), grid4, dim3(256), 0, (hipStream_t)stream, a, n, (const f16_t*)tiled, (f16_t*)y);
-        else hipLaunchKernelGGL((dw_tiles_fwd_kernel<bf16_t, true, 4>), grid4, dim3(256), 0, (hipStream_t)stream, a, n, (const bf16_t*)tiled, (bf16_t*)y);
-        return launch_status();
-    }
-    if ((a.ph & 1) == 0) {                 // two output rows per thread: they share a patch
-        const dim3 grid2((W / 2 + 63) / 64, (H / 2 + 3) / 4, batch * channels);
-        if (dtype == HS_DTYPE_F32) hipLaunchKernelGGL((dw_tiles_fwd_kernel<float, true, 2>), grid2, dim3(256), 0, (hipStream_t)stream, a, n, (const float*)tiled, (float*)y);
-        else if (dtype == HS_DTYPE_F16) hipLaunchKernelGGL((dw_tiles_fwd_kernel<f16_t, true, 2>), grid2, dim3(256), 0, (hipStream_t)stream, a, n, (const f16_t*)tiled, (f16_t*)y);
-        else hipLaunchKernelGGL((dw_tiles_fwd_kernel<bf16_t, true, 2>), grid2, dim3(256), 0, (hipStream_t)stream, a, n, (const bf16_t*)tiled, (bf16_t*)y);
-        return launch_status();
-    }
-    const dim3 grid((W / 2 + 63) / 64, (H + 3) / 4, batch * channels);
-    if (dtype == HS_DTYPE_F32) hipLaunchKernelGGL((dw_tiles_fwd_kernel<float, true>), grid, dim3(256), 0, (hipStream_t)stream, a, n, (const float*)tiled, (float*)y);
-    else if (dtype == HS_DTYPE_F16) hipLaunchKernelGGL((dw_tiles_fwd_kernel<f16_t, true>), grid, dim3(256), 0, (hipStream_t)stream, a, n, (const f16_t*)tiled, (f16_t*)y);
-    else hipLaunchKernelGGL((dw_tiles_fwd_kernel<bf16_t, true>), grid, dim3(256), 0, (hipStream_t)stream, a, n, (const bf16_t*)tiled, (bf16_t*)y);
+    // four output rows per thread where the patch height allows (round 6: six tile rows for four output rows instead of eight), else two (they
+    // share a patch), else one
+    const int rows = ((a.ph & 3) == 0 && HS_DWT_FWD_RPT4) ? 4 : ((a.ph & 1) == 0 ? 2 : 1);
+    const dim3 grid((W / 2 + 63) / 64, (H / rows + 3) / 4, batch * channels);
+    with_storage(dtype, [&](auto tag) {
+        using T = decltype(tag);
+        if (rows == 4) hipLaunchKernelGGL((dw_tiles_fwd_kernel<T, true, 4>), grid, dim3(256), 0, (hipStream_t)stream, a, n, (const T*)tiled, (T*)y);
+        else if (rows == 2) hipLaunchKernelGGL((dw_tiles_fwd_kernel<T, true, 2>), grid, dim3(256), 0, (hipStream_t)stream, a, n, (const T*)tiled, (T*)y);
+        else hipLaunchKernelGGL((dw_tiles_fwd_kernel<T, true>), grid, dim3(256), 0, (hipStream_t)stream, a, n, (const T*)tiled, (T*)y);
+    });
     return launch_status();
 }
 
@@ -1428,12 +1415,12 @@ template <bool STATS>
 static int dwt_bwd_in_launch(int dtype, const DwtArgs& a, const void* dy, void* dtiled, const DwtBn& n, const void* xt, float* partial, void* stream) {
     const int rpt = dwt_bwd_in_rows(a);
     const dim3 grid = dwt_bwd_in_grid(a, rpt);
-#define HS_DWT_BI(RPT) \
-    if (dtype == HS_DTYPE_F32) hipLaunchKernelGGL((dw_tiles_bwd_in_kernel<float, RPT, STATS>), grid, dim3(256), 0, (hipStream_t)stream, a, (const float*)dy, (float*)dtiled, n, (const float*)xt, partial); \
-    else if (dtype == HS_DTYPE_F16) hipLaunchKernelGGL((dw_tiles_bwd_in_kernel<f16_t, RPT, STATS>), grid, dim3(256), 0, (hipStream_t)stream, a, (const f16_t*)dy, (f16_t*)dtiled, n, (const f16_t*)xt, partial); \
-    else hipLaunchKernelGGL((dw_tiles_bwd_in_kernel<bf16_t, RPT, STATS>), grid, dim3(256), 0, (hipStream_t)stream, a, (const bf16_t*)dy, (bf16_t*)dtiled, n, (const bf16_t*)xt, partial);
-    if (rpt == 3) { HS_DWT_BI(3) } else if (rpt == 2) { HS_DWT_BI(2) } else { HS_DWT_BI(1) }
-#undef HS_DWT_BI
+    with_storage(dtype, [&](auto tag) {
+        using T = decltype(tag);
+        if (rpt == 3) hipLaunchKernelGGL((dw_tiles_bwd_in_kernel<T, 3, STATS>), grid, dim3(256), 0, (hipStream_t)stream, a, (const T*)dy, (T*)dtiled, n, (const T*)xt, partial);
+        else if (rpt == 2) hipLaunchKernelGGL((dw_tiles_bwd_in_kernel<T, 2, STATS>), grid, dim3(256), 0, (hipStream_t)stream, a, (const T*)dy, (T*)dtiled, n, (const T*)xt, partial);
+        else hipLaunchKernelGGL((dw_tiles_bwd_in_kernel<T, 1, STATS>), grid, dim3(256), 0, (hipStream_t)stream, a, (const T*)dy, (T*)dtiled, n, (const T*)xt, partial);
+    });
     return launch_status();
 }
 
@@ -1470,6 +1457,21 @@ extern "C" int hs_dw_tiles_bn_bwd_in(int32_t dtype, const void* dy, const float*
     return dwt_bwd_in_launch<true>(dtype, a, dy, dtiled, n, tiled, partial, stream);
 }
 
+// the three forms of dw_tiles_bwd_w_kernel; BN: the tiles are normalised on load from n's saved statistics
+template <bool BN>
+static int dwt_bwd_w_launch(int dtype, const DwtArgs& a, const DwtBn& n, const void* tiled, const void* dy, void* stream) {
+    const unsigned patches = (unsigned)(a.B * a.fh * a.fw);
+    const bool even = (a.ph & 1) == 0, rows16 = even && (a.ph / 2) * (a.pw / 2) <= 16;            // rows16: a channel per row of 16 lanes
+    const dim3 grid(patches, (a.C + 3) / 4), gridr(patches, (a.C + 15) / 16), gridc(patches, (a.C + 4 * HS_DWT_BWD_W_CPW - 1) / (4 * HS_DWT_BWD_W_CPW));
+    with_storage(dtype, [&](auto tag) {
+        using T = decltype(tag);
+        if (rows16) hipLaunchKernelGGL((dw_tiles_bwd_w_kernel<T, BN, 2, true>), gridr, dim3(256), 0, (hipStream_t)stream, a, n, (const T*)tiled, (const T*)dy);
+        else if (even) hipLaunchKernelGGL((dw_tiles_bwd_w_kernel<T, BN, 2, false, HS_DWT_BWD_W_CPW>), gridc, dim3(256), 0, (hipStream_t)stream, a, n, (const T*)tiled, (const T*)dy);
+        else hipLaunchKernelGGL((dw_tiles_bwd_w_kernel<T, BN>), grid, dim3(256), 0, (hipStream_t)stream, a, n, (const T*)tiled, (const T*)dy);
+    });
+    return launch_status();
+}
+
 extern "C" int hs_dw_tiles_bwd_w(int32_t dtype, const void* tiled, const void* dy, int32_t batch, int32_t channels, int32_t H, int32_t W,
                                  int32_t fh, int32_t fw, float* dbank, int64_t ld, int32_t patch_major, void* stream) {
     DwtArgs a;
@@ -1477,21 +1479,7 @@ extern "C" int hs_dw_tiles_bwd_w(int32_t dtype, const void* tiled, const void* d
     if (st != HS_OK) return st;
     if (!dbank) return HS_ERR_BAD_ARG;
     a.dbank = dbank;
-    const dim3 grid((unsigned)(batch * fh * fw), (channels + 3) / 4);
-    if ((a.ph & 1) == 0 && (a.ph / 2) * (a.pw / 2) <= 16) {                  // a channel per row of 16 lanes
-        const dim3 gridr((unsigned)(batch * fh * fw), (channels + 15) / 16);
-        if (dtype == HS_DTYPE_F32) hipLaunchKernelGGL((dw_tiles_bwd_w_kernel<float, false, 2, true>), gridr, dim3(256), 0, (hipStream_t)stream, a, DwtBn{}, (const float*)tiled, (const float*)dy);
-        else if (dtype == HS_DTYPE_F16) hipLaunchKernelGGL((dw_tiles_bwd_w_kernel<f16_t, false, 2, true>), gridr, dim3(256), 0, (hipStream_t)stream, a, DwtBn{}, (const f16_t*)tiled, (const f16_t*)dy);
-        else hipLaunchKernelGGL((dw_tiles_bwd_w_kernel<bf16_t, false, 2, true>), gridr, dim3(256), 0, (hipStream_t)stream, a, DwtBn{}, (const bf16_t*)tiled, (const bf16_t*)dy);
-    } else if ((a.ph & 1) == 0) {
-        const dim3 gridc((unsigned)(batch * fh * fw), (channels + 4 * HS_DWT_BWD_W_CPW - 1) / (4 * HS_DWT_BWD_W_CPW));
-        if (dtype == HS_DTYPE_F32) hipLaunchKernelGGL((dw_tiles_bwd_w_kernel<float, false, 2, false, HS_DWT_BWD_W_CPW>), gridc, dim3(256), 0, (hipStream_t)stream, a, DwtBn{}, (const float*)tiled, (const float*)dy);
-        else if (dtype == HS_DTYPE_F16) hipLaunchKernelGGL((dw_tiles_bwd_w_kernel<f16_t, false, 2, false, HS_DWT_BWD_W_CPW>), gridc, dim3(256), 0, (hipStream_t)stream, a, DwtBn{}, (const f16_t*)tiled, (const f16_t*)dy);
-        else hipLaunchKernelGGL((dw_tiles_bwd_w_kernel<bf16_t, false, 2, false, HS_DWT_BWD_W_CPW>), gridc, dim3(256), 0, (hipStream_t)stream, a, DwtBn{}, (const bf16_t*)tiled, (const bf16_t*)dy);
-    } else if (dtype == HS_DTYPE_F32) hipLaunchKernelGGL((dw_tiles_bwd_w_kernel<float, false>), grid, dim3(256), 0, (hipStream_t)stream, a, DwtBn{}, (const float*)tiled, (const float*)dy);
-    else if (dtype == HS_DTYPE_F16) hipLaunchKernelGGL((dw_tiles_bwd_w_kernel<f16_t, false>), grid, dim3(256), 0, (hipStream_t)stream, a, DwtBn{}, (const f16_t*)tiled, (const f16_t*)dy);
-    else hipLaunchKernelGGL((dw_tiles_bwd_w_kernel<bf16_t, false>), grid, dim3(256), 0, (hipStream_t)stream, a, DwtBn{}, (const bf16_t*)tiled, (const bf16_t*)dy);
-    return launch_status();
+    return dwt_bwd_w_launch<false>(dtype, a, DwtBn{}, tiled, dy, stream);
 }
 
 // hs_dw_tiles_bwd_w on the RAW tiles of hs_dw_tiles_bn_fwd: the same on-load normalisation from the saved statistics
@@ -1504,34 +1492,19 @@ extern "C" int hs_dw_tiles_bn_bwd_w(int32_t dtype, const void* tiled, const void
     if (!dbank || !save_mean || !save_invstd || act < HS_ACT_NONE || act > HS_ACT_RELU6) return HS_ERR_BAD_ARG;
     a.dbank = dbank;
     DwtBn n{nullptr, gamma, beta, const_cast<float*>(save_mean), const_cast<float*>(save_invstd), nullptr, nullptr, nullptr, 0.f, 0.f, 0.f, 0, act};
-    const dim3 grid((unsigned)(batch * fh * fw), (channels + 3) / 4);
-    if ((a.ph & 1) == 0 && (a.ph / 2) * (a.pw / 2) <= 16) {                  // a channel per row of 16 lanes
-        const dim3 gridr((unsigned)(batch * fh * fw), (channels + 15) / 16);
-        if (dtype == HS_DTYPE_F32) hipLaunchKernelGGL((dw_tiles_bwd_w_kernel<float, true, 2, true>), gridr, dim3(256), 0, (hipStream_t)stream, a, n, (const float*)tiled, (const float*)dy);
-        else if (dtype == HS_DTYPE_F16) hipLaunchKernelGGL((dw_tiles_bwd_w_kernel<f16_t, true, 2, true>), gridr, dim3(256), 0, (hipStream_t)stream, a, n, (const f16_t*)tiled, (const f16_t*)dy);
-        else hipLaunchKernelGGL((dw_tiles_bwd_w_kernel<bf16_t, true, 2, true>), gridr, dim3(256), 0, (hipStream_t)stream, a, n, (const bf16_t*)tiled, (const bf16_t*)dy);
-    } else if ((a.ph & 1) == 0) {
-        const dim3 gridc((unsigned)(batch * fh * fw), (channels + 4 * HS_DWT_BWD_W_CPW - 1) / (4 * HS_DWT_BWD_W_CPW));
-        if (dtype == HS_DTYPE_F32) hipLaunchKernelGGL((dw_tiles_bwd_w_kernel<float, true, 2, false, HS_DWT_BWD_W_CPW>), gridc, dim3(256), 0, (hipStream_t)stream, a, n, (const float*)tiled, (const float*)dy);
-        else if (dtype == HS_DTYPE_F16) hipLaunchKernelGGL((dw_tiles_bwd_w_kernel<f16_t, true, 2, false, HS_DWT_BWD_W_CPW>), gridc, dim3(256), 0, (hipStream_t)stream, a, n, (const f16_t*)tiled, (const f16_t*)dy);
-        else hipLaunchKernelGGL((dw_tiles_bwd_w_kernel<bf16_t, true, 2, false, HS_DWT_BWD_W_CPW>), gridc, dim3(256), 0, (hipStream_t)stream, a, n, (const bf16_t*)tiled, (const bf16_t*)dy);
-    } else if (dtype == HS_DTYPE_F32) hipLaunchKernelGGL((dw_tiles_bwd_w_kernel<float, true>), grid, dim3(256), 0, (hipStream_t)stream, a, n, (const float*)tiled, (const float*)dy);
-    else if (dtype == HS_DTYPE_F16) hipLaunchKernelGGL((dw_tiles_bwd_w_kernel<f16_t, true>), grid, dim3(256), 0, (hipStream_t)stream, a, n, (const f16_t*)tiled, (const f16_t*)dy);
-    else hipLaunchKernelGGL((dw_tiles_bwd_w_kernel<bf16_t, true>), grid, dim3(256), 0, (hipStream_t)stream, a, n, (const bf16_t*)tiled, (const bf16_t*)dy);
-    return launch_status();
+    return dwt_bwd_w_launch<true>(dtype, a, n, tiled, dy, stream);
 }
 
 // ---- round 5: the train-mode inverted residual's BatchNorm2 + ReLU6 normalised ON LOAD by its last 1 x 1 layer (no normalised copy of
 // the hidden map): forward on the raw input + hs_bn_train_stats_fwd's slice sums, weight gradient on the raw input + saved statistics.
 // k = 1, groups = 1, c_out <= 32, c_in <= 64, patches of >= 64 pixels; anything else: HS_ERR_UNSUPPORTED (the caller normalises first).
-#define HS_T2(dtype, F32, BF16, F16) do { if ((dtype) == HS_DTYPE_F32) { F32; } else if ((dtype) == HS_DTYPE_F16) { F16; } else { BF16; } } while (0)
 extern "C" int hs_patch_conv_bn_fwd(int32_t dtype, const void* x, const float* bn_partial, const float* gamma, const float* beta,
                                     float* running_mean, float* running_var, float momentum, float eps, int32_t act, float* save_mean,
                                     float* save_invstd, int64_t* num_batches_tracked, const float* bank, int64_t ld, int32_t batch,
                                     int32_t c_in, int32_t H, int32_t W, int32_t fh, int32_t fw, int32_t c_out, void* y, void* stream) {
     if (!x || !y || !bank || !bn_partial || !save_mean || !save_invstd || batch <= 0 || c_in <= 0 || c_out <= 0 || H <= 0 || W <= 0 || fh <= 0 || fw <= 0)
         return HS_ERR_BAD_ARG;
-    if ((dtype != HS_DTYPE_F32 && dtype != HS_DTYPE_BF16 && dtype != HS_DTYPE_F16) || ((running_mean != nullptr) != (running_var != nullptr)) ||
+    if (!storage_known(dtype) || ((running_mean != nullptr) != (running_var != nullptr)) ||
         act < HS_ACT_NONE || act > HS_ACT_RELU6 || eps < 0.f || ld < (int64_t)c_in * c_out) return HS_ERR_BAD_ARG;
     if (H % fh || W % fw) return HS_ERR_NOT_DIVISIBLE;
     ConvBwdArgs a;
@@ -1544,9 +1517,8 @@ extern "C" int hs_patch_conv_bn_fwd(int32_t dtype, const void* x, const float* b
     const dim3 grid((unsigned)(batch * fh * fw));
     hipStream_t s = (hipStream_t)stream;
     const bool px2 = dw3_pairs(a, x, y) && a.ph * a.pw >= 128;
-#define HS_FB_L(MTV, KQV, PXV) HS_T2(dtype, hipLaunchKernelGGL((patch_conv_bn_fwd_k1m_kernel<MTV, KQV, PXV, float>), grid, dim3(256), 0, s, a, bn), \
-                                            hipLaunchKernelGGL((patch_conv_bn_fwd_k1m_kernel<MTV, KQV, PXV, bf16_t>), grid, dim3(256), 0, s, a, bn), \
-                                            hipLaunchKernelGGL((patch_conv_bn_fwd_k1m_kernel<MTV, KQV, PXV, f16_t>), grid, dim3(256), 0, s, a, bn))
+#define HS_FB_L(MTV, KQV, PXV) with_storage(dtype, [&](auto tag) { \
+        hipLaunchKernelGGL((patch_conv_bn_fwd_k1m_kernel<MTV, KQV, PXV, decltype(tag)>), grid, dim3(256), 0, s, a, bn); })
 #define HS_FB(MTV, KQV) if (mt == MTV && kq == KQV) { if (px2) HS_FB_L(MTV, KQV, 2); else HS_FB_L(MTV, KQV, 1); return launch_status(); }
     HS_FB(1, 1) HS_FB(1, 2) HS_FB(1, 3) HS_FB(1, 4) HS_FB(2, 1) HS_FB(2, 2) HS_FB(2, 3) HS_FB(2, 4)
 #undef HS_FB
@@ -1559,7 +1531,7 @@ extern "C" int hs_patch_conv_bn_bwd_w(int32_t dtype, const void* x, const void* 
                                       int32_t fw, int32_t c_out, float* dbank, int64_t ld, void* stream) {
     if (!x || !dy || !dbank || !save_mean || !save_invstd || batch <= 0 || c_in <= 0 || c_out <= 0 || H <= 0 || W <= 0 || fh <= 0 || fw <= 0)
         return HS_ERR_BAD_ARG;
-    if ((dtype != HS_DTYPE_F32 && dtype != HS_DTYPE_BF16 && dtype != HS_DTYPE_F16) || act < HS_ACT_NONE || act > HS_ACT_RELU6 || ld < (int64_t)c_in * c_out) return HS_ERR_BAD_ARG;
+    if (!storage_known(dtype) || act < HS_ACT_NONE || act > HS_ACT_RELU6 || ld < (int64_t)c_in * c_out) return HS_ERR_BAD_ARG;
     if (H % fh || W % fw) return HS_ERR_NOT_DIVISIBLE;
     ConvBwdArgs a;
     fast_args(a, nullptr, (long)ld, batch, c_in, H, W, fh, fw, c_out);
@@ -1567,23 +1539,19 @@ extern "C" int hs_patch_conv_bn_bwd_w(int32_t dtype, const void* x, const void* 
     const int mt = (c_out + 15) / 16, nt = (c_in + 15) / 16;
     if (a.ph * a.pw < 16 || mt > 2 || nt > 4) return HS_ERR_UNSUPPORTED;
     ConvBn bn{nullptr, gamma, beta, const_cast<float*>(save_mean), const_cast<float*>(save_invstd), nullptr, nullptr, nullptr, 0.f, 0.f, 0.f, act};
-    const bool vec = (a.pw & 3) == 0 && ((a.ph * a.pw) & 15) == 0 && (W & 3) == 0 && ((((size_t)x) | ((size_t)dy)) & (dtype == HS_DTYPE_F32 ? 15 : 7)) == 0;
+    const bool vec = (a.pw & 3) == 0 && ((a.ph * a.pw) & 15) == 0 && (W & 3) == 0 && ((((size_t)x) | ((size_t)dy)) & (4 * storage_bytes(dtype) - 1)) == 0;
     const bool pairs = !vec && (a.pw & 1) == 0 && (W & 1) == 0 && ((((size_t)x) | ((size_t)dy)) & 7) == 0;
     const dim3 grid((unsigned)(batch * fh * fw));
     hipStream_t s = (hipStream_t)stream;
 #define HS_BWB(MTV, NTV) if (mt == MTV && nt == NTV) { \
-        if (vec) HS_T2(dtype, hipLaunchKernelGGL((patch_conv_bwd_weight_k1m_kernel<MTV, NTV, 1, float, true>), grid, dim3(256), 0, s, a, bn), \
-                              hipLaunchKernelGGL((patch_conv_bwd_weight_k1m_kernel<MTV, NTV, 1, bf16_t, true>), grid, dim3(256), 0, s, a, bn), \
-                              hipLaunchKernelGGL((patch_conv_bwd_weight_k1m_kernel<MTV, NTV, 1, f16_t, true>), grid, dim3(256), 0, s, a, bn)); \
-        else if (pairs) HS_T2(dtype, hipLaunchKernelGGL((patch_conv_bwd_weight_k1m_kernel<MTV, NTV, 2, float, true>), grid, dim3(256), 0, s, a, bn), \
-                                     hipLaunchKernelGGL((patch_conv_bwd_weight_k1m_kernel<MTV, NTV, 2, bf16_t, true>), grid, dim3(256), 0, s, a, bn), \
-                                     hipLaunchKernelGGL((patch_conv_bwd_weight_k1m_kernel<MTV, NTV, 2, f16_t, true>), grid, dim3(256), 0, s, a, bn)); \
-        else HS_T2(dtype, hipLaunchKernelGGL((patch_conv_bwd_weight_k1m_kernel<MTV, NTV, 0, float, true>), grid, dim3(256), 0, s, a, bn), \
-                          hipLaunchKernelGGL((patch_conv_bwd_weight_k1m_kernel<MTV, NTV, 0, bf16_t, true>), grid, dim3(256), 0, s, a, bn), \
-                          hipLaunchKernelGGL((patch_conv_bwd_weight_k1m_kernel<MTV, NTV, 0, f16_t, true>), grid, dim3(256), 0, s, a, bn)); \
+        with_storage(dtype, [&](auto tag) { \
+            using T = decltype(tag); \
+            if (vec) hipLaunchKernelGGL((patch_conv_bwd_weight_k1m_kernel<MTV, NTV, 1, T, true>), grid, dim3(256), 0, s, a, bn); \
+            else if (pairs) hipLaunchKernelGGL((patch_conv_bwd_weight_k1m_kernel<MTV, NTV, 2, T, true>), grid, dim3(256), 0, s, a, bn); \
+            else hipLaunchKernelGGL((patch_conv_bwd_weight_k1m_kernel<MTV, NTV, 0, T, true>), grid, dim3(256), 0, s, a, bn); \
+        }); \
         return launch_status(); }
     HS_BWB(1, 1) HS_BWB(1, 2) HS_BWB(1, 3) HS_BWB(1, 4) HS_BWB(2, 1) HS_BWB(2, 2) HS_BWB(2, 3) HS_BWB(2, 4)
 #undef HS_BWB
     return HS_ERR_UNSUPPORTED;
 }
-#undef HS_T2

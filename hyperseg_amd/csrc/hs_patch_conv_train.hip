@@ -202,23 +202,19 @@ int launch_conv1x1_h16(int dtype, const void* x, int batch, int cin, int H, int 
 #endif
 using namespace hs;
 
-#define HS_BY_DTYPE(dtype, CALL_F32, CALL_BF16, CALL_F16) \
-    if ((dtype) == HS_DTYPE_F32) { CALL_F32; } else if ((dtype) == HS_DTYPE_BF16) { CALL_BF16; } else if ((dtype) == HS_DTYPE_F16) { CALL_F16; } \
-    else return HS_ERR_BAD_ARG;
-
 extern "C" int hs_patch_conv_plain_fwd(int32_t dtype, const void* x, const void* bank, int64_t ld, int32_t batch, int32_t c_in,
                                        int32_t H, int32_t W, int32_t fh, int32_t fw, int32_t c_out, int32_t k, int32_t pad,
                                        int32_t pad_mode, int32_t groups, void* y, void* stream) {
     PlainArgs a{};
     int st = fill_plain(a, ld, batch, c_in, H, W, fh, fw, c_out, k, pad, pad_mode, groups);
     if (st != HS_OK) return st;
-    if (!x || !bank || !y) return HS_ERR_BAD_ARG;
+    if (!x || !bank || !y || !storage_known(dtype)) return HS_ERR_BAD_ARG;
     {
         const int r = try_fast_fwd(dtype, x, bank, (long)ld, batch, c_in, H, W, fh, fw, c_out, k, pad, pad_mode, groups, nullptr, nullptr,
                                    HS_ACT_NONE, y, (hipStream_t)stream);
         if (r != 1) return r;
     }
-    if ((dtype == HS_DTYPE_BF16 || dtype == HS_DTYPE_F16) && k == 1 && pad == 0 && groups == 1 && HS_PLAIN_K1_BF16) {     // tiny patches in bf16 / fp16: the inference path's k = 1 form, typed (round 6)
+    if (storage_bytes(dtype) == 2 && k == 1 && pad == 0 && groups == 1 && HS_PLAIN_K1_BF16) {     // tiny patches in bf16 / fp16: the inference path's k = 1 form, typed (round 6)
         const int r = launch_conv1x1_h16(dtype, x, batch, c_in, H, W, fh, fw, (const float*)bank, (long)ld, c_out, y, (hipStream_t)stream);
         if (r != 1) return r;
     }
@@ -238,18 +234,14 @@ extern "C" int hs_patch_conv_plain_fwd(int32_t dtype, const void* x, const void*
     a.tiles_x = (a.pw + a.TW - 1) / a.TW;
     const size_t lds = tile_bytes(a.TH, a.TW);
     const long blocks = (long)batch * fh * fw * a.tiles_y * a.tiles_x;
-    static std::atomic<unsigned long long> done32{0}, done16{0}, doneh{0};
-    if (lds > 64 * 1024) {
-        const int e = dtype == HS_DTYPE_F32 ? allow_full_lds((const void*)plain_fwd_kernel<float>, done32)
-                    : dtype == HS_DTYPE_F16 ? allow_full_lds((const void*)plain_fwd_kernel<f16_t>, doneh)
-                                            : allow_full_lds((const void*)plain_fwd_kernel<bf16_t>, done16);
-        if (e != HS_OK) return e;
-    }
-    HS_BY_DTYPE(dtype,
-        hipLaunchKernelGGL(plain_fwd_kernel<float>, dim3((unsigned)blocks), dim3(256), lds, (hipStream_t)stream, a),
-        hipLaunchKernelGGL(plain_fwd_kernel<bf16_t>, dim3((unsigned)blocks), dim3(256), lds, (hipStream_t)stream, a),
-        hipLaunchKernelGGL(plain_fwd_kernel<f16_t>, dim3((unsigned)blocks), dim3(256), lds, (hipStream_t)stream, a))
-    return launch_status();
+    int e = HS_OK;
+    with_storage(dtype, [&](auto tag) {
+        using T = decltype(tag);
+        static std::atomic<unsigned long long> done{0};            // one per instantiation of this lambda: a flag per kernel
+        if (lds > 64 * 1024 && (e = allow_full_lds((const void*)plain_fwd_kernel<T>, done)) != HS_OK) return;
+        hipLaunchKernelGGL(plain_fwd_kernel<T>, dim3((unsigned)blocks), dim3(256), lds, (hipStream_t)stream, a);
+    });
+    return e != HS_OK ? e : launch_status();
 }
 
 extern "C" int hs_patch_conv_plain_bwd_in(int32_t dtype, const void* dy, const void* bank, int64_t ld, int32_t batch,
@@ -258,7 +250,7 @@ extern "C" int hs_patch_conv_plain_bwd_in(int32_t dtype, const void* dy, const v
     PlainArgs a{};
     int st = fill_plain(a, ld, batch, c_in, H, W, fh, fw, c_out, k, pad, pad_mode, groups);
     if (st != HS_OK) return st;
-    if (!dy || !bank || !dx) return HS_ERR_BAD_ARG;
+    if (!dy || !bank || !dx || !storage_known(dtype)) return HS_ERR_BAD_ARG;
     {
         const int r = try_fast_bwd_in(dtype, dy, bank, (long)ld, batch, c_in, H, W, fh, fw, c_out, k, pad, pad_mode, groups, dx,
                                       (hipStream_t)stream);
@@ -267,10 +259,9 @@ extern "C" int hs_patch_conv_plain_bwd_in(int32_t dtype, const void* dy, const v
     a.dy = dy; a.bank = bank; a.dx = dx;
     const size_t total = (size_t)batch * c_in * H * W;
     const unsigned blocks = (unsigned)((total + 255) / 256 > 32768 ? 32768 : (total + 255) / 256);
-    HS_BY_DTYPE(dtype,
-        hipLaunchKernelGGL(plain_bwd_in_kernel<float>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, a),
-        hipLaunchKernelGGL(plain_bwd_in_kernel<bf16_t>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, a),
-        hipLaunchKernelGGL(plain_bwd_in_kernel<f16_t>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, a))
+    with_storage(dtype, [&](auto tag) {
+        hipLaunchKernelGGL(plain_bwd_in_kernel<decltype(tag)>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, a);
+    });
     return launch_status();
 }
 
@@ -280,7 +271,7 @@ extern "C" int hs_patch_conv_plain_bwd_w(int32_t dtype, const void* x, const voi
     PlainArgs a{};
     int st = fill_plain(a, ld, batch, c_in, H, W, fh, fw, c_out, k, pad, pad_mode, groups);
     if (st != HS_OK) return st;
-    if (!x || !dy || !dbank) return HS_ERR_BAD_ARG;
+    if (!x || !dy || !dbank || !storage_known(dtype)) return HS_ERR_BAD_ARG;
     {
         const int r = try_fast_bwd_w(dtype, x, dy, batch, c_in, H, W, fh, fw, c_out, k, pad, pad_mode, groups, dbank, (long)ld,
                                      (hipStream_t)stream);
@@ -309,17 +300,13 @@ extern "C" int hs_patch_conv_plain_bwd_w(int32_t dtype, const void* x, const voi
     }
     if (ob <= 0) return HS_ERR_LDS;
     a.ob = ob;
-    static std::atomic<unsigned long long> done32{0}, done16{0}, doneh{0};
-    if (lds > 64 * 1024) {
-        const int e = dtype == HS_DTYPE_F32 ? allow_full_lds((const void*)plain_bwd_w_kernel<float>, done32)
-                    : dtype == HS_DTYPE_F16 ? allow_full_lds((const void*)plain_bwd_w_kernel<f16_t>, doneh)
-                                            : allow_full_lds((const void*)plain_bwd_w_kernel<bf16_t>, done16);
-        if (e != HS_OK) return e;
-    }
     dim3 grid((unsigned)(batch * fh * fw), (unsigned)((c_out + ob - 1) / ob));
-    HS_BY_DTYPE(dtype,
-        hipLaunchKernelGGL(plain_bwd_w_kernel<float>, grid, dim3(256), lds, (hipStream_t)stream, a),
-        hipLaunchKernelGGL(plain_bwd_w_kernel<bf16_t>, grid, dim3(256), lds, (hipStream_t)stream, a),
-        hipLaunchKernelGGL(plain_bwd_w_kernel<f16_t>, grid, dim3(256), lds, (hipStream_t)stream, a))
-    return launch_status();
+    int e = HS_OK;
+    with_storage(dtype, [&](auto tag) {
+        using T = decltype(tag);
+        static std::atomic<unsigned long long> done{0};            // a flag per kernel, as above
+        if (lds > 64 * 1024 && (e = allow_full_lds((const void*)plain_bwd_w_kernel<T>, done)) != HS_OK) return;
+        hipLaunchKernelGGL(plain_bwd_w_kernel<T>, grid, dim3(256), lds, (hipStream_t)stream, a);
+    });
+    return e != HS_OK ? e : launch_status();
 }

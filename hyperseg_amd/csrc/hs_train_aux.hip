@@ -974,7 +974,7 @@ extern "C" int hs_bank_unpack_fwd(const float* bank, int64_t ld, int32_t batch, 
 extern "C" int hs_upsample_bilinear_typed_bwd(int32_t dtype, const void* dy, int64_t dy_batch_stride, int32_t batch, int32_t channels, int32_t Hi,
                                               int32_t Wi, int32_t Ho, int32_t Wo, void* dx, void* stream) {
     if (!dy || !dx || batch <= 0 || channels <= 0 || Hi <= 0 || Wi <= 0 || Ho <= 0 || Wo <= 0) return HS_ERR_BAD_ARG;
-    if (dtype != HS_DTYPE_F32 && dtype != HS_DTYPE_BF16 && dtype != HS_DTYPE_F16) return HS_ERR_BAD_ARG;
+    if (!storage_known(dtype)) return HS_ERR_BAD_ARG;
     if (dy_batch_stride <= 0) dy_batch_stride = (int64_t)channels * Ho * Wo;                         // 0 = packed (B, C, Ho, Wo)
     if (dy_batch_stride < (int64_t)channels * Ho * Wo) return HS_ERR_BAD_ARG;
     if ((long)batch * channels > 65535 || Ho < Hi || Wo < Wi) return HS_ERR_UNSUPPORTED;          // upsampling only (the decoder's use)
@@ -983,20 +983,16 @@ extern "C" int hs_upsample_bilinear_typed_bwd(int32_t dtype, const void* dy, int
     const long bs = (long)dy_batch_stride;
     const float sy = (float)Hi / (float)Ho, sx = (float)Wi / (float)Wo;
     // the 2 x 2 form reads aligned pairs: every row of g must start on a pair boundary (Wo = 2 Wi is even; the base and the batch stride decide)
-    const size_t pair_bytes = dtype == HS_DTYPE_F32 ? 8 : 4;
-    if (Ho == 2 * Hi && Wo == 2 * Wi && (reinterpret_cast<size_t>(dy) % pair_bytes) == 0 && (bs & 1) == 0) {
-        const dim3 grid2(((Wi + 1) / 2 + 63) / 64, ((Hi + 1) / 2 + 3) / 4, batch * channels);
-        if (dtype == HS_DTYPE_F32) hipLaunchKernelGGL(upsample2x_bwd_kernel<float>, grid2, dim3(256), 0, q, (const float*)dy, channels, bs, Hi, Wi, (float*)dx);
-        else if (dtype == HS_DTYPE_F16) hipLaunchKernelGGL(upsample2x_bwd_kernel<f16_t>, grid2, dim3(256), 0, q, (const f16_t*)dy, channels, bs, Hi, Wi, (f16_t*)dx);
-        else hipLaunchKernelGGL(upsample2x_bwd_kernel<bf16_t>, grid2, dim3(256), 0, q, (const bf16_t*)dy, channels, bs, Hi, Wi, (bf16_t*)dx);
-        return launch_status();
-    }
-    if (dtype == HS_DTYPE_F32)
-        hipLaunchKernelGGL(upsample_bilinear_bwd_kernel<float>, grid, dim3(256), 0, q, (const float*)dy, channels, bs, Hi, Wi, Ho, Wo, sy, sx, (float*)dx);
-    else if (dtype == HS_DTYPE_F16)
-        hipLaunchKernelGGL(upsample_bilinear_bwd_kernel<f16_t>, grid, dim3(256), 0, q, (const f16_t*)dy, channels, bs, Hi, Wi, Ho, Wo, sy, sx, (f16_t*)dx);
-    else
-        hipLaunchKernelGGL(upsample_bilinear_bwd_kernel<bf16_t>, grid, dim3(256), 0, q, (const bf16_t*)dy, channels, bs, Hi, Wi, Ho, Wo, sy, sx, (bf16_t*)dx);
+    const size_t pair_bytes = 2 * (size_t)storage_bytes(dtype);
+    with_storage(dtype, [&](auto tag) {
+        using T = decltype(tag);
+        if (Ho == 2 * Hi && Wo == 2 * Wi && (reinterpret_cast<size_t>(dy) % pair_bytes) == 0 && (bs & 1) == 0) {
+            const dim3 grid2(((Wi + 1) / 2 + 63) / 64, ((Hi + 1) / 2 + 3) / 4, batch * channels);
+            hipLaunchKernelGGL(upsample2x_bwd_kernel<T>, grid2, dim3(256), 0, q, (const T*)dy, channels, bs, Hi, Wi, (T*)dx);
+        } else {
+            hipLaunchKernelGGL(upsample_bilinear_bwd_kernel<T>, grid, dim3(256), 0, q, (const T*)dy, channels, bs, Hi, Wi, Ho, Wo, sy, sx, (T*)dx);
+        }
+    });
     return launch_status();
 }
 
@@ -1024,32 +1020,19 @@ extern "C" int hs_bn_act_train_fwd(int32_t dtype, const void* x, int32_t batch, 
     if (!x || !y || !save_mean || !save_invstd || !workspace || ((running_mean != nullptr) != (running_var != nullptr))) return HS_ERR_BAD_ARG;
     const dim3 grid(channels, BN_CHUNKS);
     hipStream_t s = (hipStream_t)stream;
-    if ((long)batch * pixels <= BN_SMALL_MAX && (dtype == HS_DTYPE_F32 || dtype == HS_DTYPE_BF16 || dtype == HS_DTYPE_F16)) {            // one launch: a workgroup per channel
-        if (dtype == HS_DTYPE_F32)
-            hipLaunchKernelGGL(bn_fwd_small_kernel<float>, dim3(channels), dim3(BN_SMALL_THREADS), 0, s, a, (const float*)x, gamma, beta, running_mean,
-                               running_var, save_mean, save_invstd, (float*)y, (long long*)num_batches_tracked);
-        else if (dtype == HS_DTYPE_F16)
-            hipLaunchKernelGGL(bn_fwd_small_kernel<f16_t>, dim3(channels), dim3(BN_SMALL_THREADS), 0, s, a, (const f16_t*)x, gamma, beta, running_mean,
-                               running_var, save_mean, save_invstd, (f16_t*)y, (long long*)num_batches_tracked);
-        else
-            hipLaunchKernelGGL(bn_fwd_small_kernel<bf16_t>, dim3(channels), dim3(BN_SMALL_THREADS), 0, s, a, (const bf16_t*)x, gamma, beta, running_mean,
-                               running_var, save_mean, save_invstd, (bf16_t*)y, (long long*)num_batches_tracked);
-        return launch_status();
-    }
-    if (dtype == HS_DTYPE_F32) {
-        hipLaunchKernelGGL(bn_stats_kernel<float>, grid, dim3(256), 0, s, a, (const float*)x, (float*)workspace);
-        hipLaunchKernelGGL(bn_apply_kernel<float>, grid, dim3(256), 0, s, a, (const float*)x, (const float*)workspace, gamma, beta,
-                           running_mean, running_var, save_mean, save_invstd, (float*)y, (long long*)num_batches_tracked);
-    } else if (dtype == HS_DTYPE_BF16) {
-        hipLaunchKernelGGL(bn_stats_kernel<bf16_t>, grid, dim3(256), 0, s, a, (const bf16_t*)x, (float*)workspace);
-        hipLaunchKernelGGL(bn_apply_kernel<bf16_t>, grid, dim3(256), 0, s, a, (const bf16_t*)x, (const float*)workspace, gamma, beta,
-                           running_mean, running_var, save_mean, save_invstd, (bf16_t*)y, (long long*)num_batches_tracked);
-    } else if (dtype == HS_DTYPE_F16) {
-        hipLaunchKernelGGL(bn_stats_kernel<f16_t>, grid, dim3(256), 0, s, a, (const f16_t*)x, (float*)workspace);
-        hipLaunchKernelGGL(bn_apply_kernel<f16_t>, grid, dim3(256), 0, s, a, (const f16_t*)x, (const float*)workspace, gamma, beta,
-                           running_mean, running_var, save_mean, save_invstd, (f16_t*)y, (long long*)num_batches_tracked);
-    } else return HS_ERR_BAD_ARG;
-    return launch_status();
+    const bool small = (long)batch * pixels <= BN_SMALL_MAX;              // one launch: a workgroup per channel
+    const bool known = with_storage(dtype, [&](auto tag) {
+        using T = decltype(tag);
+        if (small) {
+            hipLaunchKernelGGL(bn_fwd_small_kernel<T>, dim3(channels), dim3(BN_SMALL_THREADS), 0, s, a, (const T*)x, gamma, beta, running_mean,
+                               running_var, save_mean, save_invstd, (T*)y, (long long*)num_batches_tracked);
+            return;
+        }
+        hipLaunchKernelGGL(bn_stats_kernel<T>, grid, dim3(256), 0, s, a, (const T*)x, (float*)workspace);
+        hipLaunchKernelGGL(bn_apply_kernel<T>, grid, dim3(256), 0, s, a, (const T*)x, (const float*)workspace, gamma, beta,
+                           running_mean, running_var, save_mean, save_invstd, (T*)y, (long long*)num_batches_tracked);
+    });
+    return known ? launch_status() : HS_ERR_BAD_ARG;
 }
 
 // The statistics pass alone (partial sums per channel and slice into `workspace`): for consumers that normalise on load
@@ -1060,11 +1043,11 @@ extern "C" int hs_bn_train_stats_fwd(int32_t dtype, const void* x, int32_t batch
     if (st != HS_OK) return st;
     if (!x || !workspace) return HS_ERR_BAD_ARG;
     const dim3 grid(channels, BN_CHUNKS);
-    if (dtype == HS_DTYPE_F32) hipLaunchKernelGGL(bn_stats_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, a, (const float*)x, (float*)workspace);
-    else if (dtype == HS_DTYPE_BF16) hipLaunchKernelGGL(bn_stats_kernel<bf16_t>, grid, dim3(256), 0, (hipStream_t)stream, a, (const bf16_t*)x, (float*)workspace);
-    else if (dtype == HS_DTYPE_F16) hipLaunchKernelGGL(bn_stats_kernel<f16_t>, grid, dim3(256), 0, (hipStream_t)stream, a, (const f16_t*)x, (float*)workspace);
-    else return HS_ERR_BAD_ARG;
-    return launch_status();
+    const bool known = with_storage(dtype, [&](auto tag) {
+        using T = decltype(tag);
+        hipLaunchKernelGGL(bn_stats_kernel<T>, grid, dim3(256), 0, (hipStream_t)stream, a, (const T*)x, (float*)workspace);
+    });
+    return known ? launch_status() : HS_ERR_BAD_ARG;
 }
 
 extern "C" int hs_bn_act_train_bwd(int32_t dtype, const void* x, const void* dy, int32_t batch, int32_t channels, int64_t pixels,
@@ -1076,35 +1059,20 @@ extern "C" int hs_bn_act_train_bwd(int32_t dtype, const void* x, const void* dy,
     if (!x || !dy || !dx || !save_mean || !save_invstd || !workspace) return HS_ERR_BAD_ARG;
     const dim3 grid(channels, BN_CHUNKS);
     hipStream_t s = (hipStream_t)stream;
-    if ((long)batch * pixels <= BN_SMALL_MAX && (dtype == HS_DTYPE_F32 || dtype == HS_DTYPE_BF16 || dtype == HS_DTYPE_F16)) {
-        if (dtype == HS_DTYPE_F32)
-            hipLaunchKernelGGL(bn_bwd_small_kernel<float>, dim3(channels), dim3(BN_SMALL_THREADS), 0, s, a, (const float*)x, (const float*)dy, gamma, beta,
-                               save_mean, save_invstd, (float*)dx, dgamma, dbeta);
-        else if (dtype == HS_DTYPE_F16)
-            hipLaunchKernelGGL(bn_bwd_small_kernel<f16_t>, dim3(channels), dim3(BN_SMALL_THREADS), 0, s, a, (const f16_t*)x, (const f16_t*)dy, gamma, beta,
-                               save_mean, save_invstd, (f16_t*)dx, dgamma, dbeta);
-        else
-            hipLaunchKernelGGL(bn_bwd_small_kernel<bf16_t>, dim3(channels), dim3(BN_SMALL_THREADS), 0, s, a, (const bf16_t*)x, (const bf16_t*)dy, gamma, beta,
-                               save_mean, save_invstd, (bf16_t*)dx, dgamma, dbeta);
-        return launch_status();
-    }
-    if (dtype == HS_DTYPE_F32) {
-        hipLaunchKernelGGL(bn_bwd_stats_kernel<float>, grid, dim3(256), 0, s, a, (const float*)x, (const float*)dy, gamma, beta, save_mean,
+    const bool small = (long)batch * pixels <= BN_SMALL_MAX;
+    const bool known = with_storage(dtype, [&](auto tag) {
+        using T = decltype(tag);
+        if (small) {
+            hipLaunchKernelGGL(bn_bwd_small_kernel<T>, dim3(channels), dim3(BN_SMALL_THREADS), 0, s, a, (const T*)x, (const T*)dy, gamma, beta,
+                               save_mean, save_invstd, (T*)dx, dgamma, dbeta);
+            return;
+        }
+        hipLaunchKernelGGL(bn_bwd_stats_kernel<T>, grid, dim3(256), 0, s, a, (const T*)x, (const T*)dy, gamma, beta, save_mean,
                            save_invstd, (float*)workspace);
-        hipLaunchKernelGGL(bn_bwd_apply_kernel<float>, grid, dim3(256), 0, s, a, (const float*)x, (const float*)dy, (const float*)workspace,
-                           gamma, beta, save_mean, save_invstd, (float*)dx, dgamma, dbeta);
-    } else if (dtype == HS_DTYPE_BF16) {
-        hipLaunchKernelGGL(bn_bwd_stats_kernel<bf16_t>, grid, dim3(256), 0, s, a, (const bf16_t*)x, (const bf16_t*)dy, gamma, beta, save_mean,
-                           save_invstd, (float*)workspace);
-        hipLaunchKernelGGL(bn_bwd_apply_kernel<bf16_t>, grid, dim3(256), 0, s, a, (const bf16_t*)x, (const bf16_t*)dy, (const float*)workspace,
-                           gamma, beta, save_mean, save_invstd, (bf16_t*)dx, dgamma, dbeta);
-    } else if (dtype == HS_DTYPE_F16) {
-        hipLaunchKernelGGL(bn_bwd_stats_kernel<f16_t>, grid, dim3(256), 0, s, a, (const f16_t*)x, (const f16_t*)dy, gamma, beta, save_mean,
-                           save_invstd, (float*)workspace);
-        hipLaunchKernelGGL(bn_bwd_apply_kernel<f16_t>, grid, dim3(256), 0, s, a, (const f16_t*)x, (const f16_t*)dy, (const float*)workspace,
-                           gamma, beta, save_mean, save_invstd, (f16_t*)dx, dgamma, dbeta);
-    } else return HS_ERR_BAD_ARG;
-    return launch_status();
+        hipLaunchKernelGGL(bn_bwd_apply_kernel<T>, grid, dim3(256), 0, s, a, (const T*)x, (const T*)dy, (const float*)workspace,
+                           gamma, beta, save_mean, save_invstd, (T*)dx, dgamma, dbeta);
+    });
+    return known ? launch_status() : HS_ERR_BAD_ARG;
 }
 
 // The second half of hs_bn_act_train_bwd alone, from sums some producer left as `n_partials` {sum d, sum d x_hat} pairs per channel
@@ -1118,17 +1086,12 @@ extern "C" int hs_bn_act_train_bwd_apply(int32_t dtype, const void* x, const voi
     if (!x || !dy || !dx || !save_mean || !save_invstd || !partial || n_partials <= 0 || n_partials > 0x7fffffffL) return HS_ERR_BAD_ARG;
     const dim3 grid(channels, BN_CHUNKS);
     hipStream_t s = (hipStream_t)stream;
-    if (dtype == HS_DTYPE_F32)
-        hipLaunchKernelGGL(bn_bwd_apply_np_kernel<float>, grid, dim3(256), 0, s, a, (const float*)x, (const float*)dy, partial, (int)n_partials, gamma, beta,
-                           save_mean, save_invstd, (float*)dx, dgamma, dbeta);
-    else if (dtype == HS_DTYPE_BF16)
-        hipLaunchKernelGGL(bn_bwd_apply_np_kernel<bf16_t>, grid, dim3(256), 0, s, a, (const bf16_t*)x, (const bf16_t*)dy, partial, (int)n_partials, gamma, beta,
-                           save_mean, save_invstd, (bf16_t*)dx, dgamma, dbeta);
-    else if (dtype == HS_DTYPE_F16)
-        hipLaunchKernelGGL(bn_bwd_apply_np_kernel<f16_t>, grid, dim3(256), 0, s, a, (const f16_t*)x, (const f16_t*)dy, partial, (int)n_partials, gamma, beta,
-                           save_mean, save_invstd, (f16_t*)dx, dgamma, dbeta);
-    else return HS_ERR_BAD_ARG;
-    return launch_status();
+    const bool known = with_storage(dtype, [&](auto tag) {
+        using T = decltype(tag);
+        hipLaunchKernelGGL(bn_bwd_apply_np_kernel<T>, grid, dim3(256), 0, s, a, (const T*)x, (const T*)dy, partial, (int)n_partials, gamma, beta,
+                           save_mean, save_invstd, (T*)dx, dgamma, dbeta);
+    });
+    return known ? launch_status() : HS_ERR_BAD_ARG;
 }
 
 static int tile_args(TileArgs& a, int B, int C, int H, int W, int fh, int fw, int pm = 0) {
@@ -1140,12 +1103,6 @@ static int tile_args(TileArgs& a, int B, int C, int H, int W, int fh, int fw, in
     return HS_OK;
 }
 
-#define HS_TILE_LAUNCH(dtype, KERNEL_F32, KERNEL_BF16, KERNEL_F16, grid, SRC, DST) \
-    if ((dtype) == HS_DTYPE_F32) hipLaunchKernelGGL(KERNEL_F32, grid, dim3(256), 0, (hipStream_t)stream, a, (const float*)(SRC), (float*)(DST)); \
-    else if ((dtype) == HS_DTYPE_BF16) hipLaunchKernelGGL(KERNEL_BF16, grid, dim3(256), 0, (hipStream_t)stream, a, (const bf16_t*)(SRC), (bf16_t*)(DST)); \
-    else if ((dtype) == HS_DTYPE_F16) hipLaunchKernelGGL(KERNEL_F16, grid, dim3(256), 0, (hipStream_t)stream, a, (const f16_t*)(SRC), (f16_t*)(DST)); \
-    else return HS_ERR_BAD_ARG;
-
 extern "C" int hs_halo_tiles_fwd(int32_t dtype, const void* x, int32_t batch, int32_t channels, int32_t H, int32_t W, int32_t fh,
                                  int32_t fw, void* tiled, int32_t patch_major, void* stream) {
     TileArgs a;
@@ -1153,8 +1110,11 @@ extern "C" int hs_halo_tiles_fwd(int32_t dtype, const void* x, int32_t batch, in
     if (st != HS_OK) return st;
     if (!x || !tiled) return HS_ERR_BAD_ARG;
     const dim3 grid((fw * (a.pw + 2) + 63) / 64, (fh * (a.ph + 2) + 15) / 16, (batch * channels + 1) / 2);        // four rows of two planes per thread
-    HS_TILE_LAUNCH(dtype, halo_tiles_fwd_kernel<float>, halo_tiles_fwd_kernel<bf16_t>, halo_tiles_fwd_kernel<f16_t>, grid, x, tiled)
-    return launch_status();
+    const bool known = with_storage(dtype, [&](auto tag) {
+        using T = decltype(tag);
+        hipLaunchKernelGGL(halo_tiles_fwd_kernel<T>, grid, dim3(256), 0, (hipStream_t)stream, a, (const T*)x, (T*)tiled);
+    });
+    return known ? launch_status() : HS_ERR_BAD_ARG;
 }
 
 extern "C" int hs_halo_tiles_bwd(int32_t dtype, const void* dtiled, int32_t batch, int32_t channels, int32_t H, int32_t W,
@@ -1163,46 +1123,47 @@ extern "C" int hs_halo_tiles_bwd(int32_t dtype, const void* dtiled, int32_t batc
     const int st = tile_args(a, batch, channels, H, W, fh, fw, patch_major);
     if (st != HS_OK) return st;
     if (!dtiled || !dx) return HS_ERR_BAD_ARG;
+    hipStream_t s = (hipStream_t)stream;
     const int npx = a.ph * a.pw;
-    if (a.ph >= 3 && a.pw >= 3 && npx <= 256 && 256 % npx == 0 && batch <= 65535) {       // mapped by patch
-        const int per = 256 / npx;
-        const float inv_npx = 1.0f / (float)npx;
-        const int ch = per == 1 ? HS_HALO_BWD_CH_BIG : HS_HALO_BWD_CH_SMALL;      // channels per thread
-        const dim3 gridp((unsigned)(fh * fw), (unsigned)((channels + per * ch - 1) / (per * ch)), (unsigned)batch);
-        if (dtype != HS_DTYPE_F32 && dtype != HS_DTYPE_BF16 && dtype != HS_DTYPE_F16) return HS_ERR_BAD_ARG;
-#define HS_HB_LAUNCH(CH) \
-        if (dtype == HS_DTYPE_F32) hipLaunchKernelGGL((halo_tiles_bwd_patch_kernel<float, CH>), gridp, dim3(256), 0, (hipStream_t)stream, a, (const float*)dtiled, (float*)dx, inv_npx); \
-        else if (dtype == HS_DTYPE_F16) hipLaunchKernelGGL((halo_tiles_bwd_patch_kernel<f16_t, CH>), gridp, dim3(256), 0, (hipStream_t)stream, a, (const f16_t*)dtiled, (f16_t*)dx, inv_npx); \
-        else hipLaunchKernelGGL((halo_tiles_bwd_patch_kernel<bf16_t, CH>), gridp, dim3(256), 0, (hipStream_t)stream, a, (const bf16_t*)dtiled, (bf16_t*)dx, inv_npx);
-        if (ch == 8) { HS_HB_LAUNCH(8) } else if (ch == 4) { HS_HB_LAUNCH(4) } else { HS_HB_LAUNCH(2) }
-#undef HS_HB_LAUNCH
-        return launch_status();
-    }
+    const bool by_patch = a.ph >= 3 && a.pw >= 3 && npx <= 256 && 256 % npx == 0 && batch <= 65535;
+    const int per = by_patch ? 256 / npx : 1;
+    const float inv_npx = 1.0f / (float)npx;
+    const int ch = per == 1 ? HS_HALO_BWD_CH_BIG : HS_HALO_BWD_CH_SMALL;      // channels per thread
+    const dim3 gridp((unsigned)(fh * fw), (unsigned)((channels + per * ch - 1) / (per * ch)), (unsigned)batch);
     const dim3 grid((W + 63) / 64, (H + 3) / 4, batch * channels);
-    HS_TILE_LAUNCH(dtype, halo_tiles_bwd_kernel<float>, halo_tiles_bwd_kernel<bf16_t>, halo_tiles_bwd_kernel<f16_t>, grid, dtiled, dx)
-    return launch_status();
+    const bool known = with_storage(dtype, [&](auto tag) {
+        using T = decltype(tag);
+        if (!by_patch) hipLaunchKernelGGL(halo_tiles_bwd_kernel<T>, grid, dim3(256), 0, s, a, (const T*)dtiled, (T*)dx);
+        else if (ch == 8) hipLaunchKernelGGL((halo_tiles_bwd_patch_kernel<T, 8>), gridp, dim3(256), 0, s, a, (const T*)dtiled, (T*)dx, inv_npx);
+        else if (ch == 4) hipLaunchKernelGGL((halo_tiles_bwd_patch_kernel<T, 4>), gridp, dim3(256), 0, s, a, (const T*)dtiled, (T*)dx, inv_npx);
+        else hipLaunchKernelGGL((halo_tiles_bwd_patch_kernel<T, 2>), gridp, dim3(256), 0, s, a, (const T*)dtiled, (T*)dx, inv_npx);
+    });
+    return known ? launch_status() : HS_ERR_BAD_ARG;
+}
+
+// the interior of halo tiles (BWD = false: tiled -> y) and its adjoint (BWD = true: dy -> dtiled)
+template <bool BWD>
+static int tile_interior(int dtype, const void* src, int batch, int channels, int H, int W, int fh, int fw, void* dst, hipStream_t stream) {
+    TileArgs a;
+    const int st = tile_args(a, batch, channels, H, W, fh, fw);
+    if (st != HS_OK) return st;
+    if (!src || !dst) return HS_ERR_BAD_ARG;
+    const dim3 grid = BWD ? dim3((fw * (a.pw + 2) + 63) / 64, (fh * (a.ph + 2) + 3) / 4, batch * channels) : dim3((W + 63) / 64, (H + 3) / 4, batch * channels);
+    const bool known = with_storage(dtype, [&](auto tag) {
+        using T = decltype(tag);
+        hipLaunchKernelGGL((tile_interior_kernel<T, BWD>), grid, dim3(256), 0, stream, a, (const T*)src, (T*)dst);
+    });
+    return known ? launch_status() : HS_ERR_BAD_ARG;
 }
 
 extern "C" int hs_tile_interior_fwd(int32_t dtype, const void* tiled, int32_t batch, int32_t channels, int32_t H, int32_t W,
                                     int32_t fh, int32_t fw, void* y, void* stream) {
-    TileArgs a;
-    const int st = tile_args(a, batch, channels, H, W, fh, fw);
-    if (st != HS_OK) return st;
-    if (!tiled || !y) return HS_ERR_BAD_ARG;
-    const dim3 grid((W + 63) / 64, (H + 3) / 4, batch * channels);
-    HS_TILE_LAUNCH(dtype, (tile_interior_kernel<float, false>), (tile_interior_kernel<bf16_t, false>), (tile_interior_kernel<f16_t, false>), grid, tiled, y)
-    return launch_status();
+    return tile_interior<false>(dtype, tiled, batch, channels, H, W, fh, fw, y, (hipStream_t)stream);
 }
 
 extern "C" int hs_tile_interior_bwd(int32_t dtype, const void* dy, int32_t batch, int32_t channels, int32_t H, int32_t W,
                                     int32_t fh, int32_t fw, void* dtiled, void* stream) {
-    TileArgs a;
-    const int st = tile_args(a, batch, channels, H, W, fh, fw);
-    if (st != HS_OK) return st;
-    if (!dy || !dtiled) return HS_ERR_BAD_ARG;
-    const dim3 grid((fw * (a.pw + 2) + 63) / 64, (fh * (a.ph + 2) + 3) / 4, batch * channels);
-    HS_TILE_LAUNCH(dtype, (tile_interior_kernel<float, true>), (tile_interior_kernel<bf16_t, true>), (tile_interior_kernel<f16_t, true>), grid, dy, dtiled)
-    return launch_status();
+    return tile_interior<true>(dtype, dy, batch, channels, H, W, fh, fw, dtiled, (hipStream_t)stream);
 }
 
 extern "C" int64_t hs_bootstrap_mean_workspace(void) { return (int64_t)(BM_STATE + 8) * 4 + (int64_t)BM_WG * 4 * 4; }
@@ -1262,40 +1223,30 @@ extern "C" int hs_bootstrap_mean_bwd(const float* values, int32_t n, const float
     return hs_bootstrap_mean_batched_bwd(values, 1, n, state5, grad_out, grad_values, stream);
 }
 
-extern "C" int hs_cross_entropy_typed_fwd(int32_t dtype, const void* logits, const int64_t* target, int32_t batch, int32_t classes, int64_t pixels,
-                                          int64_t ignore_index, float* loss, void* stream) {
-    if (!logits || !target || !loss || batch <= 0 || classes <= 0 || pixels <= 0) return HS_ERR_BAD_ARG;
-    if (dtype != HS_DTYPE_F32 && dtype != HS_DTYPE_BF16 && dtype != HS_DTYPE_F16) return HS_ERR_BAD_ARG;
+// The one front of the cross-entropy entries below: BWD = false writes the (batch, pixels) fp32 losses to `out`; BWD = true the gradient of the
+// logits, in their storage type, from the upstream `g` (per pixel, or -- with bstate / gmean -- the bootstrap selection's weight, ce_upstream).
+template <bool BWD>
+static int cross_entropy(int dtype, const void* logits, const int64_t* target, int batch, int classes, int64_t pixels, int64_t ignore_index,
+                         const float* g, void* out, void* stream, const float* bstate = nullptr, const float* gmean = nullptr, float gscale = 1.0f) {
+    if (!logits || !target || !out || (BWD && !g) || batch <= 0 || classes <= 0 || pixels <= 0) return HS_ERR_BAD_ARG;
     const long total = (long)batch * pixels;
     const dim3 blocks((unsigned)((total + 255) / 256 > 65535 * 16 ? 65535 * 16 : (total + 255) / 256));
-    if (dtype == HS_DTYPE_F32)
-        launch_cross_entropy<false, float>(blocks, (hipStream_t)stream, (const float*)logits, (const long long*)target, classes, (long)pixels, total,
-                                           (long long)ignore_index, nullptr, (void*)loss);
-    else if (dtype == HS_DTYPE_F16)
-        launch_cross_entropy<false, f16_t>(blocks, (hipStream_t)stream, (const f16_t*)logits, (const long long*)target, classes, (long)pixels, total,
-                                            (long long)ignore_index, nullptr, (void*)loss);
-    else
-        launch_cross_entropy<false, bf16_t>(blocks, (hipStream_t)stream, (const bf16_t*)logits, (const long long*)target, classes, (long)pixels, total,
-                                            (long long)ignore_index, nullptr, (void*)loss);
-    return launch_status();
+    const bool known = with_storage(dtype, [&](auto tag) {
+        using T = decltype(tag);
+        launch_cross_entropy<BWD, T>(blocks, (hipStream_t)stream, (const T*)logits, (const long long*)target, classes, (long)pixels, total,
+                                     (long long)ignore_index, g, out, bstate, gmean, gscale);
+    });
+    return known ? launch_status() : HS_ERR_BAD_ARG;
+}
+
+extern "C" int hs_cross_entropy_typed_fwd(int32_t dtype, const void* logits, const int64_t* target, int32_t batch, int32_t classes, int64_t pixels,
+                                          int64_t ignore_index, float* loss, void* stream) {
+    return cross_entropy<false>(dtype, logits, target, batch, classes, pixels, ignore_index, nullptr, loss, stream);
 }
 
 extern "C" int hs_cross_entropy_typed_bwd(int32_t dtype, const void* logits, const int64_t* target, int32_t batch, int32_t classes, int64_t pixels,
                                           int64_t ignore_index, const float* grad_loss, void* grad_logits, void* stream) {
-    if (!logits || !target || !grad_loss || !grad_logits || batch <= 0 || classes <= 0 || pixels <= 0) return HS_ERR_BAD_ARG;
-    if (dtype != HS_DTYPE_F32 && dtype != HS_DTYPE_BF16 && dtype != HS_DTYPE_F16) return HS_ERR_BAD_ARG;
-    const long total = (long)batch * pixels;
-    const dim3 blocks((unsigned)((total + 255) / 256 > 65535 * 16 ? 65535 * 16 : (total + 255) / 256));
-    if (dtype == HS_DTYPE_F32)
-        launch_cross_entropy<true, float>(blocks, (hipStream_t)stream, (const float*)logits, (const long long*)target, classes, (long)pixels, total,
-                                          (long long)ignore_index, grad_loss, grad_logits);
-    else if (dtype == HS_DTYPE_F16)
-        launch_cross_entropy<true, f16_t>(blocks, (hipStream_t)stream, (const f16_t*)logits, (const long long*)target, classes, (long)pixels, total,
-                                           (long long)ignore_index, grad_loss, grad_logits);
-    else
-        launch_cross_entropy<true, bf16_t>(blocks, (hipStream_t)stream, (const bf16_t*)logits, (const long long*)target, classes, (long)pixels, total,
-                                           (long long)ignore_index, grad_loss, grad_logits);
-    return launch_status();
+    return cross_entropy<true>(dtype, logits, target, batch, classes, pixels, ignore_index, grad_loss, grad_logits, stream);
 }
 
 extern "C" int hs_cross_entropy_fwd(const float* logits, const int64_t* target, int32_t batch, int32_t classes, int64_t pixels,
@@ -1329,20 +1280,8 @@ extern "C" int hs_bootstrapped_ce_fwd(int32_t dtype, const void* logits, const i
 extern "C" int hs_bootstrapped_ce_bwd(int32_t dtype, const void* logits, const int64_t* target, int32_t batch, int32_t classes, int64_t pixels,
                                       int64_t ignore_index, const float* loss, const float* state8, const float* grad_mean, void* grad_logits,
                                       void* stream) {
-    if (!logits || !target || !loss || !state8 || !grad_mean || !grad_logits || batch <= 0 || classes <= 0 || pixels <= 0) return HS_ERR_BAD_ARG;
-    if (dtype != HS_DTYPE_F32 && dtype != HS_DTYPE_BF16 && dtype != HS_DTYPE_F16) return HS_ERR_BAD_ARG;
-    const long total = (long)batch * pixels;
-    const dim3 blocks((unsigned)((total + 255) / 256 > 65535 * 16 ? 65535 * 16 : (total + 255) / 256));
-    if (dtype == HS_DTYPE_F32)
-        launch_cross_entropy<true, float>(blocks, (hipStream_t)stream, (const float*)logits, (const long long*)target, classes, (long)pixels, total,
-                                          (long long)ignore_index, loss, grad_logits, state8, grad_mean, 1.0f / (float)batch);
-    else if (dtype == HS_DTYPE_F16)
-        launch_cross_entropy<true, f16_t>(blocks, (hipStream_t)stream, (const f16_t*)logits, (const long long*)target, classes, (long)pixels, total,
-                                           (long long)ignore_index, loss, grad_logits, state8, grad_mean, 1.0f / (float)batch);
-    else
-        launch_cross_entropy<true, bf16_t>(blocks, (hipStream_t)stream, (const bf16_t*)logits, (const long long*)target, classes, (long)pixels, total,
-                                           (long long)ignore_index, loss, grad_logits, state8, grad_mean, 1.0f / (float)batch);
-    return launch_status();
+    if (!state8 || !grad_mean) return HS_ERR_BAD_ARG;
+    return cross_entropy<true>(dtype, logits, target, batch, classes, pixels, ignore_index, loss, grad_logits, stream, state8, grad_mean, 1.0f / (float)batch);
 }
 
 // ------------------------------------------------------------------------------------------------------------------------------

@@ -326,7 +326,7 @@ extern "C" int hs_cross_entropy_score_fwd(int32_t dtype, const void* logits, con
                                           int64_t pixels, int64_t ignore_index, float* loss, int32_t num_classes, int32_t per_image,
                                           int64_t* confusion, uint8_t* mask, void* stream) {
     if (!logits || !target || !loss || batch <= 0 || classes <= 0 || pixels <= 0) return HS_ERR_BAD_ARG;
-    if (dtype != HS_DTYPE_F32 && dtype != HS_DTYPE_BF16 && dtype != HS_DTYPE_F16) return HS_ERR_BAD_ARG;
+    if (!storage_known(dtype)) return HS_ERR_BAD_ARG;
     if (classes > 256) return HS_ERR_BAD_ARG;                                                 // uint8 class indices
     int n = 0;
     const int st = score_args(classes, num_classes, confusion, &n);
@@ -339,9 +339,10 @@ extern "C" int hs_cross_entropy_score_fwd(int32_t dtype, const void* logits, con
     unsigned long long* out = reinterpret_cast<unsigned long long*>(confusion);
     const long long* t = (const long long*)target;
     hipStream_t s = (hipStream_t)stream;
-    if (dtype == HS_DTYPE_F32) launch_ce_score<float>(grid, lds, s, (const float*)logits, t, classes, (long)pixels, ignore_index, loss, n, out, stride, mask);
-    else if (dtype == HS_DTYPE_F16) launch_ce_score<f16_t>(grid, lds, s, (const f16_t*)logits, t, classes, (long)pixels, ignore_index, loss, n, out, stride, mask);
-    else launch_ce_score<bf16_t>(grid, lds, s, (const bf16_t*)logits, t, classes, (long)pixels, ignore_index, loss, n, out, stride, mask);
+    with_storage(dtype, [&](auto tag) {
+        using T = decltype(tag);
+        launch_ce_score<T>(grid, lds, s, (const T*)logits, t, classes, (long)pixels, ignore_index, loss, n, out, stride, mask);
+    });
     return launch_status();
 }
 
