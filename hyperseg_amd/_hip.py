@@ -126,6 +126,10 @@ def _load():
         'hs_cross_entropy_typed_bwd': ([i32, vp, vp, i32, i32, i64, i64, vp, vp, vp], C.c_int),
         'hs_bootstrapped_ce_fwd': ([i32, vp, vp, i32, i32, i64, i64, i32, C.c_float, vp, vp, vp, vp, vp], C.c_int),
         'hs_bootstrapped_ce_bwd': ([i32, vp, vp, i32, i32, i64, i64, vp, vp, vp, vp, vp], C.c_int),
+        'hs_cross_entropy_weighted_fwd': ([i32, vp, vp, vp, i32, i32, i64, i64, vp, vp], C.c_int),
+        'hs_cross_entropy_weighted_bwd': ([i32, vp, vp, vp, i32, i32, i64, i64, vp, vp, vp], C.c_int),
+        'hs_bootstrapped_ce_weighted_fwd': ([i32, vp, vp, vp, i32, i32, i64, i64, i32, C.c_float, vp, vp, vp, vp, vp], C.c_int),
+        'hs_bootstrapped_ce_weighted_bwd': ([i32, vp, vp, vp, i32, i32, i64, i64, vp, vp, vp, vp, vp], C.c_int),
         'hs_bn_act_train_fwd': ([i32, vp, i32, i32, i64, vp, vp, vp, vp, C.c_float, C.c_float, i32, vp, vp, vp, vp, vp, vp], C.c_int),
         'hs_bn_act_train_bwd': ([i32, vp, vp, i32, i32, i64, vp, vp, vp, vp, C.c_float, i32, vp, vp, vp, vp, vp], C.c_int),
         'hs_dw_tiles_bn_bwd_in_partials': ([i32, i32, i32, i32, i32], C.c_int64),
@@ -146,6 +150,8 @@ def _load():
         'hs_upsample2_confusion_fwd': ([vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, i32, i32, i32, vp, vp, vp], C.c_int),
         'hs_cross_entropy_score_fwd': ([i32, vp, vp, i32, i32, i64, i64, vp, i32, i32, vp, vp, vp], C.c_int),
         'hs_upsample_ce_confusion_fwd': ([vp, i32, i32, i32, i32, i32, i32, vp, i32, i64, vp, i32, i32, vp, vp, vp], C.c_int),
+        'hs_cross_entropy_score_weighted_fwd': ([i32, vp, vp, vp, i32, i32, i64, i64, vp, i32, i32, vp, vp, vp], C.c_int),
+        'hs_upsample_ce_confusion_weighted_fwd': ([vp, i32, i32, i32, i32, i32, i32, vp, i32, vp, i64, vp, i32, i32, vp, vp, vp], C.c_int),
         'hs_stage_input_fwd': ([C.POINTER(StageInputC), vp, vp], C.c_int),
         'hs_stage_input_typed_fwd': ([C.POINTER(StageInputC), i32, i32, vp, vp], C.c_int),
         'hs_patch_conv_bwd_input': ([vp, vp, i64, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp], C.c_int),
@@ -217,7 +223,9 @@ EXPORTS = ['hs_version', 'hs_build_info', 'hs_signal2weights_fwd', 'hs_signal2we
            'hs_image_ingest_fwd', 'hs_stem_dw_u8_fwd', 'hs_overlay_fwd', 'hs_upsample_overlay_fwd',
            'hs_frame_resize_fwd', 'hs_label_resize_fwd', 'hs_resize_tables_fwd', 'hs_frame_resize_batch_fwd', 'hs_label_resize_batch_fwd', 'hs_color_jitter_fwd', 'hs_frame_rotate_fwd', 'hs_label_rotate_fwd',
            'hs_resize_tables_ragged_fwd', 'hs_color_jitter_ragged_fwd', 'hs_frame_resize_ragged_fwd', 'hs_label_resize_ragged_fwd', 'hs_frame_rotate_ragged_fwd', 'hs_label_rotate_ragged_fwd',
-           'hs_cross_entropy_score_fwd', 'hs_upsample_ce_confusion_fwd']
+           'hs_cross_entropy_score_fwd', 'hs_upsample_ce_confusion_fwd',
+           'hs_cross_entropy_weighted_fwd', 'hs_cross_entropy_weighted_bwd', 'hs_bootstrapped_ce_weighted_fwd', 'hs_bootstrapped_ce_weighted_bwd',
+           'hs_cross_entropy_score_weighted_fwd', 'hs_upsample_ce_confusion_weighted_fwd']
 
 
 def check(status, what):

@@ -645,15 +645,17 @@ _CHECK_LABELS = os.environ.get('HS_CHECK_LABELS', '0') == '1'
 
 
 class PixelCrossEntropy(torch.autograd.Function):
-    """F.cross_entropy(logits, target, ignore_index=..., reduction='none') for fp32 / bf16 (N, C, H, W) CUDA logits, one launch per
-    direction (hs_cross_entropy_typed_fwd / _bwd; stock: log-softmax + gather and their adjoints, after a widening cast for bf16).
-    The loss is fp32 and the arithmetic f32 for either storage type; the logits' gradient has the logits' type.
+    """F.cross_entropy(logits, target, weight=..., ignore_index=..., reduction='none') for fp32 / bf16 / fp16 (N, C, H, W) CUDA logits, one
+    launch per direction (hs_cross_entropy_typed_fwd / _bwd; stock: log-softmax + gather and their adjoints, after a widening cast for the
+    16-bit types).  The loss is fp32 and the arithmetic f32 for either storage type; the logits' gradient has the logits' type.
+    ``weight`` (optional, last): the fp32 (C,) class-weight table on the logits' device -- hs_cross_entropy_weighted_fwd / _bwd, loss =
+    weight[t] * (the unweighted loss) with one more f32 multiply, the adjoint's upstream weight[t] * g; saved for backward, no gradient.
     ``target`` must be int64 of shape (N, H, W) -- checked here, as F.cross_entropy does: the kernel walks N*H*W pixels of BOTH
     tensors.  A label outside [0, C) other than ``ignore_index`` contributes a zero loss and a zero gradient (the stock CUDA kernel
     fires a device-side assert for it); ``HS_CHECK_LABELS=1`` makes this function verify the range first (one host read, debugging)."""
 
     @staticmethod
-    def forward(ctx, logits, target, ignore_index):
+    def forward(ctx, logits, target, ignore_index, weight=None):
         if logits.dim() < 2 or tuple(target.shape) != (logits.shape[0],) + tuple(logits.shape[2:]):
             raise ValueError(f'Expected target of shape {(logits.shape[0],) + tuple(logits.shape[2:])} for logits of shape '
                              f'{tuple(logits.shape)}, got {tuple(target.shape)}')
@@ -662,6 +664,7 @@ class PixelCrossEntropy(torch.autograd.Function):
         if target.device != logits.device:
             raise ValueError(f'PixelCrossEntropy: target on {target.device}, logits on {logits.device}')
         refuse_mixed_halves(logits)
+        weight = HF.class_weight_table(weight, logits.shape[1], logits.device, 'PixelCrossEntropy: weight')
         logits, target = logits.contiguous(), target.contiguous()
         n, c = logits.shape[:2]
         px = logits.numel() // (n * c)
@@ -671,25 +674,35 @@ class PixelCrossEntropy(torch.autograd.Function):
                 raise IndexError(f'Target {int(target[bad][0])} is out of bounds for {c} classes (ignore_index {int(ignore_index)})')
         with _hip.device_scope(logits.device):
             loss = torch.empty(target.shape, device=logits.device, dtype=torch.float32)
-            st = _hip.lib.hs_cross_entropy_typed_fwd(DTYPE_CODES[logits.dtype], logits.data_ptr(), target.data_ptr(), n, c, px, int(ignore_index),
-                                                     loss.data_ptr(), _hip.stream_ptr())
-            _hip.check(st, 'hs_cross_entropy_typed_fwd')
-        ctx.save_for_backward(logits, target)
+            if weight is None:
+                st = _hip.lib.hs_cross_entropy_typed_fwd(DTYPE_CODES[logits.dtype], logits.data_ptr(), target.data_ptr(), n, c, px, int(ignore_index),
+                                                         loss.data_ptr(), _hip.stream_ptr())
+                _hip.check(st, 'hs_cross_entropy_typed_fwd')
+            else:
+                st = _hip.lib.hs_cross_entropy_weighted_fwd(DTYPE_CODES[logits.dtype], logits.data_ptr(), target.data_ptr(), weight.data_ptr(), n, c,
+                                                            px, int(ignore_index), loss.data_ptr(), _hip.stream_ptr())
+                _hip.check(st, 'hs_cross_entropy_weighted_fwd')
+        ctx.save_for_backward(*((logits, target) if weight is None else (logits, target, weight)))
         ctx.ignore_index = int(ignore_index)
         return loss
 
     @staticmethod
     def backward(ctx, g):
-        logits, target = ctx.saved_tensors
+        logits, target, *weight = ctx.saved_tensors
         n, c = logits.shape[:2]
         px = logits.numel() // (n * c)
         g = g.contiguous().float()
         with _hip.device_scope(logits.device):
             dl = torch.empty_like(logits)
-            st = _hip.lib.hs_cross_entropy_typed_bwd(DTYPE_CODES[logits.dtype], logits.data_ptr(), target.data_ptr(), n, c, px, ctx.ignore_index,
-                                                     g.data_ptr(), dl.data_ptr(), _hip.stream_ptr())
-            _hip.check(st, 'hs_cross_entropy_typed_bwd')
-        return dl, None, None
+            if not weight:
+                st = _hip.lib.hs_cross_entropy_typed_bwd(DTYPE_CODES[logits.dtype], logits.data_ptr(), target.data_ptr(), n, c, px, ctx.ignore_index,
+                                                         g.data_ptr(), dl.data_ptr(), _hip.stream_ptr())
+                _hip.check(st, 'hs_cross_entropy_typed_bwd')
+            else:
+                st = _hip.lib.hs_cross_entropy_weighted_bwd(DTYPE_CODES[logits.dtype], logits.data_ptr(), target.data_ptr(), weight[0].data_ptr(), n, c,
+                                                            px, ctx.ignore_index, g.data_ptr(), dl.data_ptr(), _hip.stream_ptr())
+                _hip.check(st, 'hs_cross_entropy_weighted_bwd')
+        return dl, None, None, None
 
 
 class BootstrapMean(torch.autograd.Function):
@@ -719,15 +732,17 @@ class BootstrapMean(torch.autograd.Function):
         return gv, None, None
 
 
-def _bootstrapped_ce_forward(ctx, logits, target, ignore_index, k, thresh, confusion=None):
+def _bootstrapped_ce_forward(ctx, logits, target, ignore_index, k, thresh, confusion=None, weight=None):
     """The forward of ``BootstrappedCrossEntropy`` -- and, with ``confusion`` (int64 (n, n), accumulated into), of
-    ``BootstrappedCrossEntropyScored``: the same checks, buffers and saved tensors, the two differ in the launches alone."""
+    ``BootstrappedCrossEntropyScored``: the same checks, buffers and saved tensors, the two differ in the launches alone.  ``weight``: the
+    class-weight table (``PixelCrossEntropy``'s) -- the weighted twin of the loss launch, the same launches after it; saved for backward."""
     if logits.dim() != 4 or tuple(target.shape) != (logits.shape[0],) + tuple(logits.shape[2:]):
         raise ValueError(f'Expected target of shape {(logits.shape[0],) + tuple(logits.shape[2:])} for logits of shape '
                          f'{tuple(logits.shape)}, got {tuple(target.shape)}')
     if target.dtype != torch.int64 or target.device != logits.device:
         raise ValueError(f'BootstrappedCrossEntropy: expected int64 class indices on {logits.device}, got {target.dtype} on {target.device}')
     refuse_mixed_halves(logits)
+    weight = HF.class_weight_table(weight, logits.shape[1], logits.device, 'BootstrappedCrossEntropy: weight')
     logits, target = logits.contiguous(), target.contiguous()
     n, c = logits.shape[:2]
     px = logits.numel() // (n * c)
@@ -739,23 +754,34 @@ def _bootstrapped_ce_forward(ctx, logits, target, ignore_index, k, thresh, confu
         ws = torch.empty(n * int(_hip.lib.hs_bootstrap_mean_workspace()), device=logits.device, dtype=torch.uint8)
         loss = torch.empty(n, px, device=logits.device, dtype=torch.float32)
         out = torch.empty(n * 8 + 1, device=logits.device, dtype=torch.float32)              # (N, 8) state | the mean
-        if confusion is None:
+        if confusion is None and weight is None:
             st = _hip.lib.hs_bootstrapped_ce_fwd(DTYPE_CODES[logits.dtype], logits.data_ptr(), target.data_ptr(), n, c, px, int(ignore_index),
                                                  int(k), float(thresh), ws.data_ptr(), loss.data_ptr(), out.data_ptr(),
                                                  out.data_ptr() + 4 * n * 8, _hip.stream_ptr())
             _hip.check(st, 'hs_bootstrapped_ce_fwd')
+        elif confusion is None:
+            st = _hip.lib.hs_bootstrapped_ce_weighted_fwd(DTYPE_CODES[logits.dtype], logits.data_ptr(), target.data_ptr(), weight.data_ptr(), n, c,
+                                                          px, int(ignore_index), int(k), float(thresh), ws.data_ptr(), loss.data_ptr(),
+                                                          out.data_ptr(), out.data_ptr() + 4 * n * 8, _hip.stream_ptr())
+            _hip.check(st, 'hs_bootstrapped_ce_weighted_fwd')
         else:                                                    # the same launches, the first one counting as well
             nc = confusion.shape[-1]
             if confusion.dtype != torch.int64 or tuple(confusion.shape) != (nc, nc) or confusion.device != logits.device \
                     or not confusion.is_contiguous():
                 raise ValueError(f'the score matrix must be a contiguous int64 (n, n) tensor on {logits.device}')
-            st = _hip.lib.hs_cross_entropy_score_fwd(DTYPE_CODES[logits.dtype], logits.data_ptr(), target.data_ptr(), n, c, px, int(ignore_index),
-                                                     loss.data_ptr(), nc, 0, confusion.data_ptr(), None, _hip.stream_ptr())
-            _hip.check(st, 'hs_cross_entropy_score_fwd')
+            if weight is None:
+                st = _hip.lib.hs_cross_entropy_score_fwd(DTYPE_CODES[logits.dtype], logits.data_ptr(), target.data_ptr(), n, c, px, int(ignore_index),
+                                                         loss.data_ptr(), nc, 0, confusion.data_ptr(), None, _hip.stream_ptr())
+                _hip.check(st, 'hs_cross_entropy_score_fwd')
+            else:
+                st = _hip.lib.hs_cross_entropy_score_weighted_fwd(DTYPE_CODES[logits.dtype], logits.data_ptr(), target.data_ptr(), weight.data_ptr(),
+                                                                  n, c, px, int(ignore_index), loss.data_ptr(), nc, 0, confusion.data_ptr(), None,
+                                                                  _hip.stream_ptr())
+                _hip.check(st, 'hs_cross_entropy_score_weighted_fwd')
             st = _hip.lib.hs_bootstrap_mean_of_batch_fwd(loss.data_ptr(), n, px, int(k), float(thresh), ws.data_ptr(), out.data_ptr(),
                                                          out.data_ptr() + 4 * n * 8, _hip.stream_ptr())
             _hip.check(st, 'hs_bootstrap_mean_of_batch_fwd')
-    ctx.save_for_backward(logits, target, loss, out)
+    ctx.save_for_backward(*((logits, target, loss, out) if weight is None else (logits, target, loss, out, weight)))
     ctx.ignore_index = int(ignore_index)
     return out[n * 8:].view(())
 
@@ -766,36 +792,45 @@ class BootstrappedCrossEntropy(torch.autograd.Function):
     ``BootstrapMeanOfBatch.apply(PixelCrossEntropy.apply(...).flatten(1), k, thresh)`` bit for bit, with ONE launch backward
     (hs_bootstrapped_ce_bwd: the pixel weights are formed inside the cross entropy's adjoint) where the pair takes two and an (N, HW)
     gradient tensor between them.  (A forward that also took the selection's first histogram level while making the losses measured
-    slower -- hs_train_aux.hip -- and is not in.)"""
+    slower -- hs_train_aux.hip -- and is not in.)  ``weight`` (optional, last): the class-weight table, ``PixelCrossEntropy``'s -- the
+    weighted entries (hs_bootstrapped_ce_weighted_fwd / _bwd), the same launch counts; the selection ranks the weighted losses, which it
+    needs >= 0: finite weights >= 0 only."""
 
     @staticmethod
-    def forward(ctx, logits, target, ignore_index, k, thresh):
-        return _bootstrapped_ce_forward(ctx, logits, target, ignore_index, k, thresh)
+    def forward(ctx, logits, target, ignore_index, k, thresh, weight=None):
+        return _bootstrapped_ce_forward(ctx, logits, target, ignore_index, k, thresh, weight=weight)
 
     @staticmethod
     def backward(ctx, g):
-        logits, target, loss, state = ctx.saved_tensors
+        logits, target, loss, state, *weight = ctx.saved_tensors
         n, c = logits.shape[:2]
         px = logits.numel() // (n * c)
         if g.dtype != torch.float32 or not g.is_contiguous():
             g = g.float().contiguous()
         with _hip.device_scope(logits.device):
             dl = torch.empty_like(logits)
-            st = _hip.lib.hs_bootstrapped_ce_bwd(DTYPE_CODES[logits.dtype], logits.data_ptr(), target.data_ptr(), n, c, px, ctx.ignore_index,
-                                                 loss.data_ptr(), state.data_ptr(), g.data_ptr(), dl.data_ptr(), _hip.stream_ptr())
-            _hip.check(st, 'hs_bootstrapped_ce_bwd')
-        return dl, None, None, None, None
+            if not weight:
+                st = _hip.lib.hs_bootstrapped_ce_bwd(DTYPE_CODES[logits.dtype], logits.data_ptr(), target.data_ptr(), n, c, px, ctx.ignore_index,
+                                                     loss.data_ptr(), state.data_ptr(), g.data_ptr(), dl.data_ptr(), _hip.stream_ptr())
+                _hip.check(st, 'hs_bootstrapped_ce_bwd')
+            else:
+                st = _hip.lib.hs_bootstrapped_ce_weighted_bwd(DTYPE_CODES[logits.dtype], logits.data_ptr(), target.data_ptr(), weight[0].data_ptr(),
+                                                              n, c, px, ctx.ignore_index, loss.data_ptr(), state.data_ptr(), g.data_ptr(),
+                                                              dl.data_ptr(), _hip.stream_ptr())
+                _hip.check(st, 'hs_bootstrapped_ce_weighted_bwd')
+        return dl, None, None, None, None, None
 
 
 class BootstrappedCrossEntropyScored(torch.autograd.Function):
     """``BootstrappedCrossEntropy`` whose loss launch also scores the batch (``BootstrappedCrossEntropyLoss.score``): the per-pixel losses
     come from hs_cross_entropy_score_fwd, which adds the (target, argmax) counts of the batch to ``confusion`` (int64 (n, n), accumulated)
     from the logits it already holds in registers; the same batch reduction follows (hs_bootstrap_mean_of_batch_fwd: the launches
-    hs_bootstrapped_ce_fwd makes after its first).  The same loss bits, and the same one-launch adjoint."""
+    hs_bootstrapped_ce_fwd makes after its first).  The same loss bits, and the same one-launch adjoint.  ``weight`` (optional, last): as
+    ``BootstrappedCrossEntropy``'s (hs_cross_entropy_score_weighted_fwd: the counts do not see it)."""
 
     @staticmethod
-    def forward(ctx, logits, target, ignore_index, k, thresh, confusion):
-        return _bootstrapped_ce_forward(ctx, logits, target, ignore_index, k, thresh, confusion)
+    def forward(ctx, logits, target, ignore_index, k, thresh, confusion, weight=None):
+        return _bootstrapped_ce_forward(ctx, logits, target, ignore_index, k, thresh, confusion, weight)
 
     @staticmethod
     def backward(ctx, g):

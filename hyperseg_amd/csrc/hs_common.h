@@ -134,6 +134,19 @@ template <> struct Pair<f16_t> {
     static __device__ __forceinline__ void st(f16_t* p, size_t i, float a, float b) { *reinterpret_cast<uint32_t*>(p + i) = pack(a, b); }
 };
 
+// The class-weight table of the cross-entropy kernels (nn.CrossEntropyLoss(weight=...): fp32, one entry per class) as a compile-time
+// variant: those kernels end in a parameter pack `CW... cw` that is empty -- the unweighted instantiations, whose arguments and code are
+// what they were -- or one `const float*`, the table.  class_weight(t, live, cw...) is then 1 (never multiplied with), or w[t] for a live
+// target (class 0's entry otherwise, unused: the index stays inside the table).  The gather depends on the target alone, so a kernel
+// asks for it right after the target load and it is in flight with the logit loads.
+__device__ __forceinline__ float class_weight(long long, bool) { return 1.0f; }
+__device__ __forceinline__ float class_weight(long long t, bool live, const float* __restrict__ w) { return w[live ? t : 0]; }
+// ... and the one multiply it enters: w * u (f32, its own rounding: the build has -ffp-contract=off), or u as it is
+template <bool W> __device__ __forceinline__ float weighted(float w, float u) {
+    if constexpr (W) return w * u;
+    else return u;
+}
+
 // Host side: the ONE place an HS_DTYPE_* code picks a kernel instantiation.  with_storage calls f with a value of the code's storage type
 // (the launch is written once: `using T = decltype(tag);` ... kernel<T>, (const T*)x, (T*)y) and returns true; for any other code it calls
 // nothing and returns false -- an extern "C" entry answers that with HS_ERR_BAD_ARG before its first launch or memset, a try_fast_* route

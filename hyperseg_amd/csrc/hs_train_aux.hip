@@ -877,8 +877,8 @@ void bank_unpack_kernel(const float* __restrict__ bank, long ld, int hp_total, i
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
-// Per-pixel cross entropy of (N, C, H, W) logits against (N, H, W) int64 labels (F.cross_entropy(..., reduction='none'), no class
-// weights: what BootstrappedCrossEntropyLoss feeds its top-k rule, bootstrapped_ce_loss.py:20-23), forward and adjoint, one launch each
+// Per-pixel cross entropy of (N, C, H, W) logits against (N, H, W) int64 labels (F.cross_entropy(..., reduction='none'), with or
+// without class weights: what BootstrappedCrossEntropyLoss feeds its top-k rule, bootstrapped_ce_loss.py:20-23), forward and adjoint, one launch each
 // (stock: log-softmax + gather, and their two adjoints -- four launches of ~25 us at config 5).  One thread per pixel; the C logits of a
 // pixel are HW floats apart, so a wave reads C coalesced rows.  loss = log(sum exp(x - max)) + max - x[t]; ignored labels give 0 and
 // no gradient; d x[c] = (softmax[c] - [c == t]) * g.
@@ -900,16 +900,20 @@ __device__ __forceinline__ float ce_upstream(const float* __restrict__ g, long e
 // (Round 6, visit x8: a forward variant that also took level 0 of the selection's histograms while it made the losses -- an LDS histogram per
 //  workgroup pass, flushed with one global atomic per non-empty bin -- measured 38.5 us against 10.3 + 6.8 for the two launches: the loss launch
 //  has 2592 workgroups where bm_hist_kernel has 256, and their flushes meet on the few hundred bins the losses crowd into.  Removed.)
-template <bool BWD, typename T, int CF>
+// CW (W): class weights, nothing or the table (class_weight, hs_common.h) -- the forward's loss is w[t] * (the unweighted loss), ONE more f32 multiply; the adjoint's upstream
+// is w[t] * (the upstream as above, which in the bootstrapped form reads the saved WEIGHTED loss); 0 where the pixel is not live, as without.
+template <bool BWD, typename T, int CF, typename... CW>
 __global__ __launch_bounds__(256)
 void cross_entropy_kernel(const T* __restrict__ x, const long long* __restrict__ target, int C, long hw, long total, long long ignore_index,
                           const float* __restrict__ g, void* __restrict__ out_, const float* __restrict__ bstate, const float* __restrict__ gmean,
-                          float gscale) {
+                          float gscale, CW... cw) {
+    constexpr bool W = sizeof...(CW) != 0;
     for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long)gridDim.x * 256) {
         const long n = e / hw, p = e - n * hw;
         const T* __restrict__ xp = x + n * C * hw + p;
         const long long t = target[e];
         const bool live = t != ignore_index && t >= 0 && t < C;
+        const float wt = class_weight(t, live, cw...);                            // (W: issued here, in flight with the logit loads)
         if constexpr (CF > 0) {
             float v[CF];
 #pragma unroll
@@ -925,10 +929,10 @@ void cross_entropy_kernel(const T* __restrict__ x, const long long* __restrict__
                 xt = (c == (int)t) ? v[c] : xt;
             }
             if constexpr (!BWD) {
-                ((float*)out_)[e] = live ? (logf(sum) + m) - xt : 0.0f;
+                ((float*)out_)[e] = live ? weighted<W>(wt, (logf(sum) + m) - xt) : 0.0f;
             } else {
                 T* __restrict__ dp = (T*)out_ + n * C * hw + p;
-                const float gl = live ? gi : 0.0f, inv = 1.0f / sum;
+                const float gl = live ? weighted<W>(wt, gi) : 0.0f, inv = 1.0f / sum;
 #pragma unroll
                 for (int c = 0; c < CF; ++c) Store<T>::st(dp, (long)c * hw, (expf(v[c] - m) * inv - (c == (int)t ? 1.0f : 0.0f)) * gl);
             }
@@ -938,23 +942,23 @@ void cross_entropy_kernel(const T* __restrict__ x, const long long* __restrict__
             float sum = 0.0f;
             for (int c = 0; c < C; ++c) sum += expf(Store<T>::ld(xp, (long)c * hw) - m);
             if constexpr (!BWD) {
-                ((float*)out_)[e] = live ? (logf(sum) + m) - Store<T>::ld(xp, (long)(live ? t : 0) * hw) : 0.0f;
+                ((float*)out_)[e] = live ? weighted<W>(wt, (logf(sum) + m) - Store<T>::ld(xp, (long)(live ? t : 0) * hw)) : 0.0f;
             } else {
                 T* __restrict__ dp = (T*)out_ + n * C * hw + p;
-                const float gi = live ? ce_upstream(g, e, n, bstate, gmean, gscale) : 0.0f, inv = 1.0f / sum;
+                const float gi = live ? weighted<W>(wt, ce_upstream(g, e, n, bstate, gmean, gscale)) : 0.0f, inv = 1.0f / sum;
                 for (int c = 0; c < C; ++c) Store<T>::st(dp, (long)c * hw, (expf(Store<T>::ld(xp, (long)c * hw) - m) * inv - (c == (int)t ? 1.0f : 0.0f)) * gi);
             }
         }
     }
 }
 
-template <bool BWD, typename T>
+template <bool BWD, typename T, typename... CW>
 static void launch_cross_entropy(dim3 blocks, hipStream_t s, const T* x, const long long* target, int C, long hw, long total, long long ignore_index,
-                                 const float* g, void* out, const float* bstate = nullptr, const float* gmean = nullptr, float gscale = 1.0f) {
-    if (C == 12) hipLaunchKernelGGL((cross_entropy_kernel<BWD, T, 12>), blocks, dim3(256), 0, s, x, target, C, hw, total, ignore_index, g, out, bstate, gmean, gscale);
-    else if (C == 19) hipLaunchKernelGGL((cross_entropy_kernel<BWD, T, 19>), blocks, dim3(256), 0, s, x, target, C, hw, total, ignore_index, g, out, bstate, gmean, gscale);
-    else if (C == 21) hipLaunchKernelGGL((cross_entropy_kernel<BWD, T, 21>), blocks, dim3(256), 0, s, x, target, C, hw, total, ignore_index, g, out, bstate, gmean, gscale);
-    else hipLaunchKernelGGL((cross_entropy_kernel<BWD, T, 0>), blocks, dim3(256), 0, s, x, target, C, hw, total, ignore_index, g, out, bstate, gmean, gscale);
+                                 const float* g, void* out, const float* bstate, const float* gmean, float gscale, CW... cw) {
+    if (C == 12) hipLaunchKernelGGL((cross_entropy_kernel<BWD, T, 12, CW...>), blocks, dim3(256), 0, s, x, target, C, hw, total, ignore_index, g, out, bstate, gmean, gscale, cw...);
+    else if (C == 19) hipLaunchKernelGGL((cross_entropy_kernel<BWD, T, 19, CW...>), blocks, dim3(256), 0, s, x, target, C, hw, total, ignore_index, g, out, bstate, gmean, gscale, cw...);
+    else if (C == 21) hipLaunchKernelGGL((cross_entropy_kernel<BWD, T, 21, CW...>), blocks, dim3(256), 0, s, x, target, C, hw, total, ignore_index, g, out, bstate, gmean, gscale, cw...);
+    else hipLaunchKernelGGL((cross_entropy_kernel<BWD, T, 0, CW...>), blocks, dim3(256), 0, s, x, target, C, hw, total, ignore_index, g, out, bstate, gmean, gscale, cw...);
 }
 
 }  // namespace hs
@@ -1225,16 +1229,18 @@ extern "C" int hs_bootstrap_mean_bwd(const float* values, int32_t n, const float
 
 // The one front of the cross-entropy entries below: BWD = false writes the (batch, pixels) fp32 losses to `out`; BWD = true the gradient of the
 // logits, in their storage type, from the upstream `g` (per pixel, or -- with bstate / gmean -- the bootstrap selection's weight, ce_upstream).
-template <bool BWD>
+// cw: nothing, or -- the weighted twins -- their (classes,) fp32 table.
+template <bool BWD, typename... CW>
 static int cross_entropy(int dtype, const void* logits, const int64_t* target, int batch, int classes, int64_t pixels, int64_t ignore_index,
-                         const float* g, void* out, void* stream, const float* bstate = nullptr, const float* gmean = nullptr, float gscale = 1.0f) {
+                         const float* g, void* out, void* stream, const float* bstate = nullptr, const float* gmean = nullptr, float gscale = 1.0f,
+                         CW... cw) {
     if (!logits || !target || !out || (BWD && !g) || batch <= 0 || classes <= 0 || pixels <= 0) return HS_ERR_BAD_ARG;
     const long total = (long)batch * pixels;
     const dim3 blocks((unsigned)((total + 255) / 256 > 65535 * 16 ? 65535 * 16 : (total + 255) / 256));
     const bool known = with_storage(dtype, [&](auto tag) {
         using T = decltype(tag);
         launch_cross_entropy<BWD, T>(blocks, (hipStream_t)stream, (const T*)logits, (const long long*)target, classes, (long)pixels, total,
-                                     (long long)ignore_index, g, out, bstate, gmean, gscale);
+                                     (long long)ignore_index, g, out, bstate, gmean, gscale, cw...);
     });
     return known ? launch_status() : HS_ERR_BAD_ARG;
 }
@@ -1282,6 +1288,40 @@ extern "C" int hs_bootstrapped_ce_bwd(int32_t dtype, const void* logits, const i
                                       void* stream) {
     if (!state8 || !grad_mean) return HS_ERR_BAD_ARG;
     return cross_entropy<true>(dtype, logits, target, batch, classes, pixels, ignore_index, loss, grad_logits, stream, state8, grad_mean, 1.0f / (float)batch);
+}
+
+// The weighted twins (nn.CrossEntropyLoss(weight=...) under the top-k rule): each is the entry above plus `weight`, the (classes,) fp32 table on
+// the device.  loss = weight[t] * (the unweighted loss); the adjoints take weight[t] * (their upstream).  The selection ranks the weighted
+// losses and relies on losses >= 0: the caller passes finite weights >= 0 only (nothing here reads the table on the host).
+extern "C" int hs_cross_entropy_weighted_fwd(int32_t dtype, const void* logits, const int64_t* target, const float* weight, int32_t batch,
+                                             int32_t classes, int64_t pixels, int64_t ignore_index, float* loss, void* stream) {
+    if (!weight) return HS_ERR_BAD_ARG;
+    return cross_entropy<false>(dtype, logits, target, batch, classes, pixels, ignore_index, nullptr, loss, stream, nullptr, nullptr, 1.0f, weight);
+}
+
+extern "C" int hs_cross_entropy_weighted_bwd(int32_t dtype, const void* logits, const int64_t* target, const float* weight, int32_t batch,
+                                             int32_t classes, int64_t pixels, int64_t ignore_index, const float* grad_loss, void* grad_logits,
+                                             void* stream) {
+    if (!weight) return HS_ERR_BAD_ARG;
+    return cross_entropy<true>(dtype, logits, target, batch, classes, pixels, ignore_index, grad_loss, grad_logits, stream, nullptr, nullptr, 1.0f, weight);
+}
+
+extern "C" int hs_bootstrapped_ce_weighted_fwd(int32_t dtype, const void* logits, const int64_t* target, const float* weight, int32_t batch,
+                                               int32_t classes, int64_t pixels, int64_t ignore_index, int32_t k, float thresh, void* workspace,
+                                               float* loss, float* out8, float* mean_out, void* stream) {
+    if (!weight || !workspace || !out8 || !mean_out || k <= 0 || batch > 65535) return HS_ERR_BAD_ARG;
+    if (pixels <= k || pixels > 0x7fffffffL) return HS_ERR_UNSUPPORTED;
+    const int st = hs_cross_entropy_weighted_fwd(dtype, logits, target, weight, batch, classes, pixels, ignore_index, loss, stream);
+    if (st != HS_OK) return st;
+    return bootstrap_mean_fwd(loss, batch, (int32_t)pixels, k, thresh, workspace, out8, mean_out, stream);
+}
+
+extern "C" int hs_bootstrapped_ce_weighted_bwd(int32_t dtype, const void* logits, const int64_t* target, const float* weight, int32_t batch,
+                                               int32_t classes, int64_t pixels, int64_t ignore_index, const float* loss, const float* state8,
+                                               const float* grad_mean, void* grad_logits, void* stream) {
+    if (!weight || !state8 || !grad_mean) return HS_ERR_BAD_ARG;
+    return cross_entropy<true>(dtype, logits, target, batch, classes, pixels, ignore_index, loss, grad_logits, stream, state8, grad_mean,
+                                1.0f / (float)batch, weight);
 }
 
 // ------------------------------------------------------------------------------------------------------------------------------

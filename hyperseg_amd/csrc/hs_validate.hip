@@ -28,10 +28,14 @@ __device__ __forceinline__ bool ce_live(long long t, long long ignore_index, int
 
 // Logits in memory: one thread = one pixel per trip, its C logits HW elements apart (a wave reads C coalesced rows).  CF: the class count
 // at compile time (the pixel's logits loaded once, all in flight together), 0 = any count (three passes), as cross_entropy_kernel.
-template <typename T, int CF>
+// CW (W; here and in the two kernels below): class weights, nothing or the table (class_weight, hs_common.h) -- loss = w[t] * (the unweighted loss), cross_entropy_kernel<.., W>'s
+// bits.  The table is gathered from memory per pixel, right after the target (a few cached lines): nothing is staged, no barrier is added.
+template <typename T, int CF, typename... CW>
 __global__ __launch_bounds__(EVAL_THREADS)
 void ce_score_kernel(const T* __restrict__ x, const long long* __restrict__ target, int C, long hw, long long ignore_index,
-                     float* __restrict__ loss, int n, unsigned long long* __restrict__ out, long out_image_stride, uint8_t* __restrict__ mask) {
+                     float* __restrict__ loss, int n, unsigned long long* __restrict__ out, long out_image_stride, uint8_t* __restrict__ mask,
+                     CW... cw) {
+    constexpr bool W = sizeof...(CW) != 0;
     extern __shared__ unsigned hist[];
     const int nn = n * n, lane = threadIdx.x & 63;
     const bool count = out != nullptr;                           // (uniform)
@@ -45,6 +49,7 @@ void ce_score_kernel(const T* __restrict__ x, const long long* __restrict__ targ
         const T* __restrict__ xp = xb + p;
         const long long t = target[b * hw + p];
         const bool live = ce_live(t, ignore_index, C);
+        const float wt = class_weight(t, live, cw...);
         float value;
         int best_c = 0;
         if constexpr (CF > 0) {
@@ -63,7 +68,7 @@ void ce_score_kernel(const T* __restrict__ x, const long long* __restrict__ targ
                 sum += expf(v[c] - m);
                 xt = (c == (int)t) ? v[c] : xt;
             }
-            value = live ? (logf(sum) + m) - xt : 0.0f;
+            value = live ? weighted<W>(wt, (logf(sum) + m) - xt) : 0.0f;
         } else {
             float m = Store<T>::ld(xp, 0), best = m;
             for (int c = 1; c < C; ++c) {
@@ -73,7 +78,7 @@ void ce_score_kernel(const T* __restrict__ x, const long long* __restrict__ targ
             }
             float sum = 0.0f;
             for (int c = 0; c < C; ++c) sum += expf(Store<T>::ld(xp, (long)c * hw) - m);
-            value = live ? (logf(sum) + m) - Store<T>::ld(xp, (long)(live ? t : 0) * hw) : 0.0f;
+            value = live ? weighted<W>(wt, (logf(sum) + m) - Store<T>::ld(xp, (long)(live ? t : 0) * hw)) : 0.0f;
         }
         if (here) {
             loss[b * hw + p] = value;
@@ -143,11 +148,13 @@ __device__ __forceinline__ void argmax2x_block_best(const float* __restrict__ xb
 // General resize (any ratio, the identity included): upsample_confusion_kernel's mapping, one thread = 4 consecutive output pixels of a row,
 // all C classes of them its own.  Two passes over the classes: the arg-max and the maxima, then -- the scores recomputed by the same
 // operations, so the same bits; the loads hit the cache -- the exp-sum ascending and the target's score.
-template <typename TT>
+template <typename TT, typename... CW>
 __global__ __launch_bounds__(EVAL_THREADS)
 void upsample_ce_confusion_kernel(const float* __restrict__ x, int C, int Hi, int Wi, int Ho, int Wo, float scale_y, float scale_x,
                                   const TT* __restrict__ target, long long ignore_index, float* __restrict__ loss, int n,
-                                  unsigned long long* __restrict__ out, long out_image_stride, uint8_t* __restrict__ mask, int vec) {
+                                  unsigned long long* __restrict__ out, long out_image_stride, uint8_t* __restrict__ mask, int vec,
+                                  CW... cw) {
+    constexpr bool W = sizeof...(CW) != 0;
     extern __shared__ unsigned hist[];
     const int nn = n * n, lane = threadIdx.x & 63;
     const bool count = out != nullptr;                           // (uniform)
@@ -174,6 +181,10 @@ void upsample_ce_confusion_kernel(const float* __restrict__ x, int C, int Hi, in
 #pragma unroll
             for (int i = 0; i < 4; ++i) tv[i] = target[at + (4 * q + i < Wo ? i : 0)];
         }
+        float wt[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i)                              // (W: in flight with the second pass' loads)
+            wt[i] = class_weight((long long)tv[i], ce_live((long long)tv[i], ignore_index, C), cw...);
         float sum[4] = {0.0f, 0.0f, 0.0f, 0.0f}, xt[4] = {0.0f, 0.0f, 0.0f, 0.0f};
 #pragma unroll 2
         for (int c = 0; c < C; ++c) {
@@ -187,7 +198,8 @@ void upsample_ce_confusion_kernel(const float* __restrict__ x, int C, int Hi, in
         }
         float v[4];
 #pragma unroll
-        for (int i = 0; i < 4; ++i) v[i] = ce_live((long long)tv[i], ignore_index, C) ? (logf(sum[i]) + m[i]) - xt[i] : 0.0f;
+        for (int i = 0; i < 4; ++i)
+            v[i] = ce_live((long long)tv[i], ignore_index, C) ? weighted<W>(wt[i], (logf(sum[i]) + m[i]) - xt[i]) : 0.0f;
         if (live) {
             if (vec) {
                 *reinterpret_cast<float4*>(loss + at) = make_float4(v[0], v[1], v[2], v[3]);
@@ -235,11 +247,12 @@ __device__ __forceinline__ void ce2x_take(const float (&o0)[4], const float (&o1
 // classes over the quad, after which all four lanes hold the block's indices and maxima.  Second pass: a quad-tree sum would not be the
 // sequential one, so the quad again makes four classes at a time (lane `sub`: class 4 g + sub, the same up2x_block), the values are
 // exchanged within the quad (ce2x_take) and each lane runs the ascending exp-sum of the two pixels it also counts.
-template <typename TT>
+template <typename TT, typename... CW>
 __global__ __launch_bounds__(EVAL_THREADS)
 void upsample2x_ce_confusion_kernel(const float* __restrict__ x, int C, int Hi, int Wi, const TT* __restrict__ target, long long ignore_index,
                                     float* __restrict__ loss, int n, unsigned long long* __restrict__ out, long out_image_stride,
-                                    uint8_t* __restrict__ mask, int vec) {
+                                    uint8_t* __restrict__ mask, int vec, CW... cw) {
+    constexpr bool W = sizeof...(CW) != 0;
     extern __shared__ unsigned hist[];
     const int nn = n * n, lane = threadIdx.x & 63;
     const bool count = out != nullptr;                           // (uniform)
@@ -277,6 +290,11 @@ void upsample2x_ce_confusion_kernel(const float* __restrict__ x, int C, int Hi, 
         TT tv[2];
         load2(target + mine, vec != 0, tv);
         const long long ta = (long long)tv[0], tb = (long long)tv[1];
+        float wa = 1.0f, wb = 1.0f;
+        if constexpr (W) {                                      // in flight with the second pass' loads
+            wa = class_weight(ta, ce_live(ta, ignore_index, C), cw...);
+            wb = class_weight(tb, ce_live(tb, ignore_index, C), cw...);
+        }
         float sa = 0.0f, sb = 0.0f, xa = 0.0f, xb2 = 0.0f;
         for (int c0 = 0; c0 < C; c0 += 4) {                      // (uniform: every lane of the wave takes every trip and every branch below)
             float o0[4], o1[4];
@@ -287,8 +305,8 @@ void upsample2x_ce_confusion_kernel(const float* __restrict__ x, int C, int Hi, 
             if (c0 + 3 < C) ce2x_take<3>(o0, o1, row1, right, c0 + 3, ta, tb, ma, mb, sa, sb, xa, xb2);
         }
         if (live) {
-            loss[mine] = ce_live(ta, ignore_index, C) ? (logf(sa) + ma) - xa : 0.0f;
-            loss[mine + 1] = ce_live(tb, ignore_index, C) ? (logf(sb) + mb) - xb2 : 0.0f;
+            loss[mine] = ce_live(ta, ignore_index, C) ? weighted<W>(wa, (logf(sa) + ma) - xa) : 0.0f;
+            loss[mine + 1] = ce_live(tb, ignore_index, C) ? weighted<W>(wb, (logf(sb) + mb) - xb2) : 0.0f;
         }
         if (count) {
             count_key(hist, live ? pair_key<TT>(tv[0], pa, n) : -1, lane);
@@ -298,14 +316,14 @@ void upsample2x_ce_confusion_kernel(const float* __restrict__ x, int C, int Hi, 
     if (count) hist_flush(hist, nn, out + b * out_image_stride);
 }
 
-template <typename T>
+template <typename T, typename... CW>
 static void launch_ce_score(dim3 grid, size_t lds, hipStream_t s, const T* x, const long long* target, int C, long hw, long long ignore_index,
-                            float* loss, int n, unsigned long long* out, long stride, uint8_t* mask) {
+                            float* loss, int n, unsigned long long* out, long stride, uint8_t* mask, CW... cw) {
     const dim3 block(EVAL_THREADS);
-    if (C == 12) hipLaunchKernelGGL((ce_score_kernel<T, 12>), grid, block, lds, s, x, target, C, hw, ignore_index, loss, n, out, stride, mask);
-    else if (C == 19) hipLaunchKernelGGL((ce_score_kernel<T, 19>), grid, block, lds, s, x, target, C, hw, ignore_index, loss, n, out, stride, mask);
-    else if (C == 21) hipLaunchKernelGGL((ce_score_kernel<T, 21>), grid, block, lds, s, x, target, C, hw, ignore_index, loss, n, out, stride, mask);
-    else hipLaunchKernelGGL((ce_score_kernel<T, 0>), grid, block, lds, s, x, target, C, hw, ignore_index, loss, n, out, stride, mask);
+    if (C == 12) hipLaunchKernelGGL((ce_score_kernel<T, 12, CW...>), grid, block, lds, s, x, target, C, hw, ignore_index, loss, n, out, stride, mask, cw...);
+    else if (C == 19) hipLaunchKernelGGL((ce_score_kernel<T, 19, CW...>), grid, block, lds, s, x, target, C, hw, ignore_index, loss, n, out, stride, mask, cw...);
+    else if (C == 21) hipLaunchKernelGGL((ce_score_kernel<T, 21, CW...>), grid, block, lds, s, x, target, C, hw, ignore_index, loss, n, out, stride, mask, cw...);
+    else hipLaunchKernelGGL((ce_score_kernel<T, 0, CW...>), grid, block, lds, s, x, target, C, hw, ignore_index, loss, n, out, stride, mask, cw...);
 }
 
 // what both entries ask of (classes, num_classes, confusion): nothing of num_classes where nothing is counted
@@ -318,13 +336,10 @@ static int score_args(int classes, int num_classes, const void* confusion, int* 
     return HS_OK;
 }
 
-}  // namespace hs
-
-using namespace hs;
-
-extern "C" int hs_cross_entropy_score_fwd(int32_t dtype, const void* logits, const int64_t* target, int32_t batch, int32_t classes,
-                                          int64_t pixels, int64_t ignore_index, float* loss, int32_t num_classes, int32_t per_image,
-                                          int64_t* confusion, uint8_t* mask, void* stream) {
+// the one front of hs_cross_entropy_score_fwd and its weighted twin
+template <typename... CW>
+static int ce_score(int32_t dtype, const void* logits, const int64_t* target, int32_t batch, int32_t classes, int64_t pixels, int64_t ignore_index,
+                    float* loss, int32_t num_classes, int32_t per_image, int64_t* confusion, uint8_t* mask, void* stream, CW... cw) {
     if (!logits || !target || !loss || batch <= 0 || classes <= 0 || pixels <= 0) return HS_ERR_BAD_ARG;
     if (!storage_known(dtype)) return HS_ERR_BAD_ARG;
     if (classes > 256) return HS_ERR_BAD_ARG;                                                 // uint8 class indices
@@ -341,14 +356,16 @@ extern "C" int hs_cross_entropy_score_fwd(int32_t dtype, const void* logits, con
     hipStream_t s = (hipStream_t)stream;
     with_storage(dtype, [&](auto tag) {
         using T = decltype(tag);
-        launch_ce_score<T>(grid, lds, s, (const T*)logits, t, classes, (long)pixels, ignore_index, loss, n, out, stride, mask);
+        launch_ce_score<T>(grid, lds, s, (const T*)logits, t, classes, (long)pixels, ignore_index, loss, n, out, stride, mask, cw...);
     });
     return launch_status();
 }
 
-extern "C" int hs_upsample_ce_confusion_fwd(const float* x, int32_t batch, int32_t channels, int32_t Hi, int32_t Wi, int32_t Ho, int32_t Wo,
-                                            const void* target, int32_t target_dtype, int64_t ignore_index, float* loss, int32_t num_classes,
-                                            int32_t per_image, int64_t* confusion, uint8_t* mask, void* stream) {
+// ... and of hs_upsample_ce_confusion_fwd and its weighted twin
+template <typename... CW>
+static int upsample_ce_confusion(const float* x, int32_t batch, int32_t channels, int32_t Hi, int32_t Wi, int32_t Ho, int32_t Wo, const void* target,
+                                 int32_t target_dtype, int64_t ignore_index, float* loss, int32_t num_classes, int32_t per_image,
+                                 int64_t* confusion, uint8_t* mask, void* stream, CW... cw) {
     if (!x || !target || !loss || batch <= 0 || channels <= 0 || Hi <= 0 || Wi <= 0 || Ho <= 0 || Wo <= 0) return HS_ERR_BAD_ARG;
     if (!eval_storage_ok(target_dtype) || channels > 256) return HS_ERR_BAD_ARG;               // uint8 class indices
     int n = 0;
@@ -366,11 +383,11 @@ extern "C" int hs_upsample_ce_confusion_fwd(const float* x, int32_t batch, int32
         const long passes = ((long)Hi * (Wi / 2) + EVAL_THREADS / 4 - 1) / (EVAL_THREADS / 4);
         const dim3 grid(eval_grid_x(passes, batch), (unsigned)batch);
         if (target_dtype == HS_EVAL_U8)
-            hipLaunchKernelGGL(upsample2x_ce_confusion_kernel<uint8_t>, grid, dim3(EVAL_THREADS), lds, s, x, channels, Hi, Wi,
-                               (const uint8_t*)target, ii, loss, n, out, stride, mask, vec);
+            hipLaunchKernelGGL((upsample2x_ce_confusion_kernel<uint8_t, CW...>), grid, dim3(EVAL_THREADS), lds, s, x, channels, Hi, Wi,
+                               (const uint8_t*)target, ii, loss, n, out, stride, mask, vec, cw...);
         else
-            hipLaunchKernelGGL(upsample2x_ce_confusion_kernel<int64_t>, grid, dim3(EVAL_THREADS), lds, s, x, channels, Hi, Wi,
-                               (const int64_t*)target, ii, loss, n, out, stride, mask, vec);
+            hipLaunchKernelGGL((upsample2x_ce_confusion_kernel<int64_t, CW...>), grid, dim3(EVAL_THREADS), lds, s, x, channels, Hi, Wi,
+                               (const int64_t*)target, ii, loss, n, out, stride, mask, vec, cw...);
         return launch_status();
     }
     const int vec = (Wo & 3) == 0 && aligned_to(target, tsz == 1 ? 4 : 16) && aligned_to(loss, 16) && (!mask || aligned_to(mask, 4));
@@ -378,10 +395,45 @@ extern "C" int hs_upsample_ce_confusion_fwd(const float* x, int32_t batch, int32
     const dim3 grid(eval_grid_x(passes, batch), (unsigned)batch);
     const float sy = (float)Hi / (float)Ho, sx = (float)Wi / (float)Wo;
     if (target_dtype == HS_EVAL_U8)
-        hipLaunchKernelGGL(upsample_ce_confusion_kernel<uint8_t>, grid, dim3(EVAL_THREADS), lds, s, x, channels, Hi, Wi, Ho, Wo, sy, sx,
-                           (const uint8_t*)target, ii, loss, n, out, stride, mask, vec);
+        hipLaunchKernelGGL((upsample_ce_confusion_kernel<uint8_t, CW...>), grid, dim3(EVAL_THREADS), lds, s, x, channels, Hi, Wi, Ho, Wo, sy, sx,
+                           (const uint8_t*)target, ii, loss, n, out, stride, mask, vec, cw...);
     else
-        hipLaunchKernelGGL(upsample_ce_confusion_kernel<int64_t>, grid, dim3(EVAL_THREADS), lds, s, x, channels, Hi, Wi, Ho, Wo, sy, sx,
-                           (const int64_t*)target, ii, loss, n, out, stride, mask, vec);
+        hipLaunchKernelGGL((upsample_ce_confusion_kernel<int64_t, CW...>), grid, dim3(EVAL_THREADS), lds, s, x, channels, Hi, Wi, Ho, Wo, sy, sx,
+                           (const int64_t*)target, ii, loss, n, out, stride, mask, vec, cw...);
     return launch_status();
+}
+
+}  // namespace hs
+
+using namespace hs;
+
+extern "C" int hs_cross_entropy_score_fwd(int32_t dtype, const void* logits, const int64_t* target, int32_t batch, int32_t classes,
+                                          int64_t pixels, int64_t ignore_index, float* loss, int32_t num_classes, int32_t per_image,
+                                          int64_t* confusion, uint8_t* mask, void* stream) {
+    return ce_score(dtype, logits, target, batch, classes, pixels, ignore_index, loss, num_classes, per_image, confusion, mask, stream);
+}
+
+extern "C" int hs_upsample_ce_confusion_fwd(const float* x, int32_t batch, int32_t channels, int32_t Hi, int32_t Wi, int32_t Ho, int32_t Wo,
+                                            const void* target, int32_t target_dtype, int64_t ignore_index, float* loss, int32_t num_classes,
+                                            int32_t per_image, int64_t* confusion, uint8_t* mask, void* stream) {
+    return upsample_ce_confusion(x, batch, channels, Hi, Wi, Ho, Wo, target, target_dtype, ignore_index, loss, num_classes, per_image,
+                                 confusion, mask, stream);
+}
+
+// The weighted twins: `weight` is the (classes,) / (channels,) fp32 table on the device, finite and >= 0 by the caller's word (it is not read on
+// the host).  Masks and counts are the unweighted entries'; loss = weight[t] * theirs.
+extern "C" int hs_cross_entropy_score_weighted_fwd(int32_t dtype, const void* logits, const int64_t* target, const float* weight, int32_t batch,
+                                                   int32_t classes, int64_t pixels, int64_t ignore_index, float* loss, int32_t num_classes,
+                                                   int32_t per_image, int64_t* confusion, uint8_t* mask, void* stream) {
+    if (!weight) return HS_ERR_BAD_ARG;
+    return ce_score(dtype, logits, target, batch, classes, pixels, ignore_index, loss, num_classes, per_image, confusion, mask, stream, weight);
+}
+
+extern "C" int hs_upsample_ce_confusion_weighted_fwd(const float* x, int32_t batch, int32_t channels, int32_t Hi, int32_t Wi, int32_t Ho, int32_t Wo,
+                                                     const void* target, int32_t target_dtype, const float* weight, int64_t ignore_index,
+                                                     float* loss, int32_t num_classes, int32_t per_image, int64_t* confusion, uint8_t* mask,
+                                                     void* stream) {
+    if (!weight) return HS_ERR_BAD_ARG;
+    return upsample_ce_confusion(x, batch, channels, Hi, Wi, Ho, Wo, target, target_dtype, ignore_index, loss, num_classes, per_image,
+                                 confusion, mask, stream, weight);
 }

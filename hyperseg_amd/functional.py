@@ -1478,15 +1478,30 @@ def confusion_update(pred, target, num_classes, out=None, per_image=False):
     return out
 
 
+def class_weight_table(weight, classes, device, what='weight'):
+    """The class-weight table as the weighted cross-entropy launches read it (here and in ``autograd``): None, or the fp32 (C,) contiguous
+    tensor on the logits' device, detached; anything else raises.  Its VALUES -- finite, >= 0 -- are the caller's word
+    (``training.weight_fusable`` checks them once per table): nothing here reads the device."""
+    if weight is None:
+        return None
+    if not isinstance(weight, torch.Tensor) or weight.dtype != torch.float32 or tuple(weight.shape) != (classes,) or weight.device != device \
+            or not weight.is_contiguous():
+        raise ValueError(f'{what} must be a contiguous float32 ({classes},) tensor on {device}, got {getattr(weight, "dtype", type(weight))} '
+                         f'{tuple(getattr(weight, "shape", ()))} on {getattr(weight, "device", None)}')
+    return weight.detach()
+
+
 @_on_operand_device
-def cross_entropy_score(logits, target, ignore_index, num_classes, out=None, per_image=False, masks=False):
+def cross_entropy_score(logits, target, ignore_index, num_classes, out=None, per_image=False, masks=False, weight=None):
     """The per-pixel cross entropy of (B, C, H, W) logits (f32 / bf16 / f16) against int64 ``target`` (B, H, W) AND the batch's score, one
     launch (hs_cross_entropy_score_fwd): returns ``(loss, out)`` -- ``(loss, out, masks)`` with ``masks=True``.  ``loss`` (B, H, W) f32 is
     ``autograd.PixelCrossEntropy``'s bit for bit (0 where the target is ``ignore_index`` or outside [0, C)); the masks are
     ``logits.argmax(1)`` as uint8; ``out[t, p] += 1`` for every pixel whose target is in [0, num_classes) -- ``confusion_update``'s rule,
     which does not know ``ignore_index``: an in-range ignored pixel has loss 0 and is still counted, as in the reference's train.py.
     ``out`` follows ``upsample_confusion``'s convention (accumulated into when given, a new zeroed matrix otherwise; (B, n, n) with
-    ``per_image``); ``num_classes=None`` counts nothing and returns ``out`` None.  Nothing here reads the device: capturable."""
+    ``per_image``); ``num_classes=None`` counts nothing and returns ``out`` None.  ``weight``: the fp32 (C,) class-weight table on the
+    logits' device (hs_cross_entropy_score_weighted_fwd) -- ``loss`` is then the weighted ``PixelCrossEntropy``'s bit for bit, masks and
+    counts are as without.  Nothing here reads the device: capturable (a graph holds the table's address)."""
     if not isinstance(logits, torch.Tensor) or logits.dim() != 4 or logits.dtype not in DTYPE_CODES:
         raise ValueError('logits must be (B, C, H, W) float32, bfloat16 or float16')
     b, c, h, w = logits.shape
@@ -1497,20 +1512,26 @@ def cross_entropy_score(logits, target, ignore_index, num_classes, out=None, per
     xp = _hip.dev_ptr(logits, 'logits', logits.dtype)
     loss = torch.empty(b, h, w, device=logits.device, dtype=torch.float32)
     mask = torch.empty(b, h, w, device=logits.device, dtype=torch.uint8) if masks else None
-    st = _hip.lib.hs_cross_entropy_score_fwd(DTYPE_CODES[logits.dtype], xp, target.data_ptr(), b, c, h * w, int(ignore_index), loss.data_ptr(),
-                                             n, 1 if per_image else 0, None if out is None else out.data_ptr(),
-                                             mask.data_ptr() if masks else None, _hip.stream_ptr())
-    _hip.check(st, 'hs_cross_entropy_score_fwd')
+    tail = (loss.data_ptr(), n, 1 if per_image else 0, None if out is None else out.data_ptr(), mask.data_ptr() if masks else None, _hip.stream_ptr())
+    table = class_weight_table(weight, c, logits.device)
+    if table is None:
+        st = _hip.lib.hs_cross_entropy_score_fwd(DTYPE_CODES[logits.dtype], xp, target.data_ptr(), b, c, h * w, int(ignore_index), *tail)
+        _hip.check(st, 'hs_cross_entropy_score_fwd')
+    else:
+        st = _hip.lib.hs_cross_entropy_score_weighted_fwd(DTYPE_CODES[logits.dtype], xp, target.data_ptr(), table.data_ptr(), b, c, h * w, int(ignore_index), *tail)
+        _hip.check(st, 'hs_cross_entropy_score_weighted_fwd')
     return (loss, out, mask) if masks else (loss, out)
 
 
 @_on_operand_device
-def upsample_ce_confusion(x, size, target, ignore_index, num_classes, out=None, per_image=False):
+def upsample_ce_confusion(x, size, target, ignore_index, num_classes, out=None, per_image=False, weight=None):
     """The validation step's last launch (hs_upsample_ce_confusion_fwd): ``x`` (B, C, Hi, Wi) f32 resized to ``size`` in registers, and from
     each output pixel's scores its cross entropy against ``target`` (B, Ho, Wo; uint8 or int64), its class and its count.  Returns
     ``(loss, out, masks)``: ``loss`` (B, Ho, Wo) f32 bit-identical to ``PixelCrossEntropy`` on ``upsample_bilinear(x, size)``, the uint8
     masks to ``upsample_argmax``'s, the counts to ``upsample_confusion``'s (``out``, ``per_image`` and the errors raised: that
-    function's; ``num_classes=None``: nothing counted, ``out`` None).  The resized logits never exist in memory.  Capturable."""
+    function's; ``num_classes=None``: nothing counted, ``out`` None).  ``weight``: the fp32 (C,) class-weight table on ``x``'s device
+    (hs_upsample_ce_confusion_weighted_fwd): ``loss`` is the weighted ``PixelCrossEntropy``'s, masks and counts as without.  The resized
+    logits never exist in memory.  Capturable (a graph holds the table's address)."""
     b, c, hi, wi = _logits_shape(x)
     ho, wo = _size2(size, 'size')
     target = _eval_target(target, (b, ho, wo), x)
@@ -1518,10 +1539,14 @@ def upsample_ce_confusion(x, size, target, ignore_index, num_classes, out=None, 
     xp = _hip.dev_ptr(x, 'x')
     loss = torch.empty(b, ho, wo, device=x.device, dtype=torch.float32)
     mask = torch.empty(b, ho, wo, device=x.device, dtype=torch.uint8)
-    st = _hip.lib.hs_upsample_ce_confusion_fwd(xp, b, c, hi, wi, ho, wo, target.data_ptr(), _EVAL_DTYPES[target.dtype], int(ignore_index),
-                                               loss.data_ptr(), n, 1 if per_image else 0, None if out is None else out.data_ptr(),
-                                               mask.data_ptr(), _hip.stream_ptr())
-    _hip.check(st, 'hs_upsample_ce_confusion_fwd')
+    tail = (int(ignore_index), loss.data_ptr(), n, 1 if per_image else 0, None if out is None else out.data_ptr(), mask.data_ptr(), _hip.stream_ptr())
+    table = class_weight_table(weight, c, x.device)
+    if table is None:
+        st = _hip.lib.hs_upsample_ce_confusion_fwd(xp, b, c, hi, wi, ho, wo, target.data_ptr(), _EVAL_DTYPES[target.dtype], *tail)
+        _hip.check(st, 'hs_upsample_ce_confusion_fwd')
+    else:
+        st = _hip.lib.hs_upsample_ce_confusion_weighted_fwd(xp, b, c, hi, wi, ho, wo, target.data_ptr(), _EVAL_DTYPES[target.dtype], table.data_ptr(), *tail)
+        _hip.check(st, 'hs_upsample_ce_confusion_weighted_fwd')
     return loss, out, mask
 
 

@@ -82,15 +82,19 @@ class Epilogue:
     """What rides on the decoder's final upsample launch instead of writing the logits: the uint8 arg-max masks, plain -- at the frame's
     size, or resized once more to ``out_size`` -- or scored by that launch (``score``) or blended over the frames by it (``blend``): one of
     the two per forward.  ``ignore_index`` (with ``score``): the criterion's -- a validation step, the launch also makes every pixel's
-    cross entropy against the score's target.  A scored forward takes its output size from its target."""
+    cross entropy against the score's target.  ``weight`` (with ``ignore_index`` and ``score``): the criterion's class-weight table, fp32
+    (C,) on the device, finite and >= 0 -- the losses are then the weighted ones.  A scored forward takes its output size from its target."""
     score: Optional[Score] = None
     blend: Optional[Blend] = None
     out_size: Optional[tuple] = None
     ignore_index: Optional[int] = None
+    weight: Optional[object] = None
 
     def __post_init__(self):
         if self.ignore_index is not None and (self.score is None or self.blend is not None):
             raise ValueError('the loss rides on a scored epilogue: a score with it, no blend')
+        if self.weight is not None and (self.ignore_index is None or self.score is None):
+            raise ValueError('class weights weigh the loss: they ride on a scored epilogue with an ignore_index')
         if self.score is not None and self.blend is not None:
             raise ValueError('score and blend both ride on the final upsample launch: one of them per forward for now')
         if self.out_size is not None:
@@ -112,7 +116,9 @@ class Epilogue:
                     raise ValueError('the loss rides on a scored epilogue at the frame\'s size: no other out_size')
                 if label != size:
                     raise ValueError(f'the loss needs a target at the output size {size}, got {label}')
-                per_pixel, _, masks = HF.upsample_ce_confusion(p, size, target, self.ignore_index, num_classes, out=out, per_image=per_image)
+                weighted = {} if self.weight is None else dict(weight=self.weight)          # (the unweighted call is what it was)
+                per_pixel, _, masks = HF.upsample_ce_confusion(p, size, target, self.ignore_index, num_classes, out=out, per_image=per_image,
+                                                               **weighted)
                 return masks, per_pixel
             if label != size and tuple(p.shape[2:]) != size:
                 return HF.upsample2_confusion(p, size, target, num_classes, out=out, per_image=per_image, masks=True)[1]
@@ -306,9 +312,13 @@ class HyperGenBase(EpochOnModeSwitch, nn.Module):
         if not (isinstance(x, torch.Tensor) and x.dim() == 4 and not self.training and isinstance(target, torch.Tensor)
                 and (staged or (x.is_cuda and target.is_cuda)) and self._scorable(target, x.shape[0], n)):
             return False
-        if not (isinstance(criterion, BootstrappedCrossEntropyLoss) and criterion.weight is None and criterion.score is None
-                and USE_HIP_BOOTSTRAP and USE_FUSED_LOSS):
+        if not (isinstance(criterion, BootstrappedCrossEntropyLoss) and criterion.score is None and USE_HIP_BOOTSTRAP and USE_FUSED_LOSS):
             return False
+        if criterion.weight is not None:                        # a table the HIP loss takes (asked once per table), on the model's device
+            device = next(self.parameters()).device if staged else x.device
+            classes = getattr(self.decoder, 'num_classes', None)      # the logits' channels (a decoder that does not say: composed route)
+            if classes is None or not criterion.weight_takes_hip(classes, device):
+                return False
         if tuple(target.shape) != (x.shape[0],) + self.frame_size(x) or x.shape[0] > 65535:
             return False
         pixels = target.shape[1] * target.shape[2]
@@ -321,12 +331,13 @@ class HyperGenBase(EpochOnModeSwitch, nn.Module):
         adds the batch's (target, prediction) counts to ``confmat`` (a ``hyperseg_amd.fps.ConfusionMatrix``; None: loss and masks only;
         ``per_image`` as ``evaluate``'s).  ``training.running_scores(confmat.mat)`` gives the numbers train.py picks ``model_best`` by.
 
-        A single CUDA tensor in eval mode, a ``BootstrappedCrossEntropyLoss`` without class weights (and without a ``score`` of its own),
+        A single CUDA tensor in eval mode, a ``BootstrappedCrossEntropyLoss`` (without a ``score`` of its own; class weights, if any, a
+        table the HIP loss takes: ``training.weight_fusable`` -- fp32 (C,) on the device, finite and >= 0),
         a uint8 / int64 target at the frame's size with more than ``criterion.k`` pixels and at most ``HF.eval_max_classes()`` classes:
         the forward's last launch (``HF.upsample_ce_confusion``) makes the per-pixel losses, the masks and the counts -- the
         full-resolution logits are never written -- and the criterion's own batch reduction follows (the launches its fused forward
-        makes after its first).  Everything else -- list inputs, training mode, CPU, a target of another size, class weights, another
-        criterion -- computes ``pred = self(x)``, resizes it to the target as ``evaluate`` does, and takes ``criterion(pred,
+        makes after its first).  Everything else -- list inputs, training mode, CPU, a target of another size, class weights the HIP
+        loss does not take, another criterion -- computes ``pred = self(x)``, resizes it to the target as ``evaluate`` does, and takes ``criterion(pred,
         target.long())``, ``argmax`` and ``confmat``'s own update.  On the device every route gives the same loss bits, masks and
         counts from the same decoder input.  (An unprepared model's stock torch encoder does not repeat its own bits from one call to
         the next, so two separate passes of it need not agree to the bit, whichever routes they take: DESIGN 3.11.)  The
@@ -342,7 +353,8 @@ class HyperGenBase(EpochOnModeSwitch, nn.Module):
             out = None
             if confmat is not None:
                 out = torch.zeros((x.shape[0], n, n), dtype=torch.int64, device=x.device) if per_image else confmat.matrix(x.device)
-            got = self.process_single_tensor(x, epilogue=Epilogue(Score(target, n, out, per_image), ignore_index=criterion.ignore_index))
+            got = self.process_single_tensor(x, epilogue=Epilogue(Score(target, n, out, per_image), ignore_index=criterion.ignore_index,
+                                                                       weight=criterion.weight))
             if not isinstance(got, tuple):
                 raise RuntimeError('the decoder returned logits where its epilogue was asked for: nothing was scored')
             masks, per_pixel = got

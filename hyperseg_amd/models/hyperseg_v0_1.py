@@ -114,6 +114,7 @@ class MultiScaleDecoder(EpochOnModeSwitch, nn.Module):
         kernel_sizes = per_level(kernel_sizes, n, 'kernel_sizes')
         level_layers = per_level(level_layers, n, 'level_layers')
         self.level_layers, self.levels = level_layers, n
+        self.num_classes = num_classes                        # the logits' channels (a plain attribute, as the v1_0 decoders')
         self.layer_params = []
         coarse_to_fine = feat_channels[::-1]
 

@@ -557,6 +557,7 @@ class MultiScaleDecoder(EpochOnModeSwitch, nn.Module):
         if isinstance(groups, (list, tuple)):
             per_level(groups, n, 'groups')
         self.level_layers, self.levels = level_layers, n
+        self.num_classes = num_classes                        # the logits' channels (a plain attribute: what validate() sizes a class-weight table by)
         self.layer_params, self.coords_cache = [], {}
         self.weight_groups = weight_groups
 

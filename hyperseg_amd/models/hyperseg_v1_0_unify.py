@@ -82,6 +82,7 @@ class MultiScaleDecoder(EpochOnModeSwitch, nn.Module):
         level_layers = per_level(level_layers, n, 'level_layers')
         expand_ratio = per_level(expand_ratio, n, 'expand_ratio')
         self.level_layers, self.levels, self.unify_level = level_layers, n, unify_level
+        self.num_classes = num_classes                        # the logits' channels (a plain attribute: what validate() sizes a class-weight table by)
         self.layer_params, self.coords_cache = [], {}
         self.weight_groups = weight_groups
 

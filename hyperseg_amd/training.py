@@ -21,6 +21,19 @@ from .augment import BatchAugment, BatchAugmentVOC, VOCBatchParams, _voc_cpu, de
 
 USE_HIP_BOOTSTRAP = True       # tests switch it off to reach the torch statements of the rule below
 USE_FUSED_LOSS = True          # False: cross entropy and the bootstrapped mean as two Functions (two launches backward; the fused one's equality test)
+USE_HIP_CLASS_WEIGHTS = True   # False: a criterion with class weights takes the composed route (F.cross_entropy), as before the weighted kernels
+
+
+def weight_fusable(weight, classes, device):
+    """Whether the HIP loss routes take this class-weight table: an fp32 ``(classes,)`` contiguous tensor on ``device`` (the logits')
+    whose every element is finite and >= 0 -- the top-k selection ranks the weighted losses and relies on losses >= 0.  Anything else
+    (a negative or non-finite entry, another dtype or shape, a CPU table against CUDA logits) keeps the composed route, which takes
+    whatever ``F.cross_entropy`` takes.  A pure function of its arguments; the value test reads the device once (criteria cache it)."""
+    if not isinstance(weight, torch.Tensor) or weight.dtype != torch.float32 or tuple(weight.shape) != (int(classes),) or not weight.is_contiguous():
+        return False
+    if weight.device != torch.device(device):
+        return False
+    return bool((torch.isfinite(weight) & (weight >= 0)).all())
 
 
 def bootstrap_mean_reference(per_pixel, k, thresh):
@@ -53,12 +66,20 @@ def bootstrap_mean_capturable(per_pixel, k, thresh):
     return torch.where(top[k] > thresh, mean_over, top[:k].mean())
 
 
-def bootstrapped_cross_entropy(pred, target, k=4096, thresh=0.3, weight=None, ignore_index=-100, score=None):
-    """pred (N, C, H, W) logits, target (N, H, W) int64 -> scalar.  ``score``: ``BootstrappedCrossEntropyLoss.score``."""
+def bootstrapped_cross_entropy(pred, target, k=4096, thresh=0.3, weight=None, ignore_index=-100, score=None, weight_ok=None):
+    """pred (N, C, H, W) logits, target (N, H, W) int64 -> scalar.  ``score``: ``BootstrappedCrossEntropyLoss.score``.  ``weight``: the
+    class-weight table; the HIP routes take it where it is fusable (:func:`weight_fusable`; ``weight_ok``: that answer where the caller
+    holds it already -- the criterion caches it per table -- None: asked here, one read of the device)."""
     capturing = pred.is_cuda and torch.cuda.is_current_stream_capturing()
+    if weight is not None and pred.is_cuda and pred.dim() == 4:
+        if weight_ok is None:
+            weight_ok = USE_HIP_CLASS_WEIGHTS and weight_fusable(weight, pred.shape[1], pred.device)
+    else:
+        weight_ok = False
+    hip_w = weight if weight_ok else None                       # what the Functions below are given: None where there is no table
     # the per-pixel losses of the WHOLE batch in one pass over (N, C, H, W) (the reference permutes every image to (HW, C) first,
     # bootstrapped_ce_loss.py:20-23: same values, a transposed copy + a softmax + a gather per image and direction)
-    hip_ce = (USE_HIP_BOOTSTRAP and weight is None and pred.is_cuda and pred.dtype in (torch.float32, torch.bfloat16, torch.float16) and pred.dim() == 4
+    hip_ce = (USE_HIP_BOOTSTRAP and (weight is None or weight_ok) and pred.is_cuda and pred.dtype in (torch.float32, torch.bfloat16, torch.float16) and pred.dim() == 4
               and target.dtype == torch.int64 and target.device == pred.device)
     fused = hip_ce and USE_FUSED_LOSS and pred.shape[2] * pred.shape[3] > k and pred.shape[0] <= 65535 and pred.shape[2] * pred.shape[3] < 2 ** 31
     if score is not None:
@@ -66,14 +87,18 @@ def bootstrapped_cross_entropy(pred, target, k=4096, thresh=0.3, weight=None, ig
             raise ValueError(f'{pred.shape[1] if pred.dim() > 1 else 0} logit channels but the score counts {score.num_classes} classes')
         if fused and _score_in_loss_launch(score.num_classes):
             from .autograd import BootstrappedCrossEntropyScored           # the loss launch counts the batch: no further launch
+            if hip_w is not None:
+                return BootstrappedCrossEntropyScored.apply(pred, target, ignore_index, k, thresh, score.matrix(pred.device), hip_w)
             return BootstrappedCrossEntropyScored.apply(pred, target, ignore_index, k, thresh, score.matrix(pred.device))
         score.update(target.flatten(), pred.detach().argmax(1).flatten())  # every other route: the loss as it was, scored by the matrix itself
     if fused:
         from .autograd import BootstrappedCrossEntropy                     # the whole loss as one Function: its adjoint is one launch (round 6)
+        if hip_w is not None:
+            return BootstrappedCrossEntropy.apply(pred, target, ignore_index, k, thresh, hip_w)
         return BootstrappedCrossEntropy.apply(pred, target, ignore_index, k, thresh)
     if hip_ce:
         from .autograd import PixelCrossEntropy                            # one launch per direction (hs_cross_entropy_typed_fwd / _bwd)
-        per_all = PixelCrossEntropy.apply(pred, target, ignore_index)
+        per_all = PixelCrossEntropy.apply(pred, target, ignore_index) if hip_w is None else PixelCrossEntropy.apply(pred, target, ignore_index, hip_w)
     else:
         per_all = F.cross_entropy(pred.float(), target, weight=weight, ignore_index=ignore_index, reduction='none')
     per_rows = per_all.flatten(1)
@@ -100,12 +125,20 @@ def _score_in_loss_launch(num_classes):
 class BootstrappedCrossEntropyLoss(nn.Module):
     """``score``: a plain attribute, default None -- set it to a ``hyperseg_amd.fps.ConfusionMatrix`` and every ``forward`` also adds the
     batch's (target, ``input.argmax(1)``) counts to it: the running score the reference's epoch loop keeps next to the loss
-    (train.py:124-126, ``running_metrics.update``).  On the fused-loss route (CUDA logits, no class weights, more than ``k`` pixels, at
+    (train.py:124-126, ``running_metrics.update``).  On the fused-loss route (CUDA logits, more than ``k`` pixels, at
     most ``functional.eval_max_classes()`` classes) the loss launch itself counts, from the logits it holds in registers, into
     ``score.matrix(device)``: the same loss bits, the same gradients, no further launch and nothing read back, so a captured step
     (``GraphedTrainStep``) counts with every replay.  Every other route computes the loss as without it and calls ``score.update``.
     Counting follows the reference's ``runningScore``, which does not know ``ignore_index``: every target in [0, n) is counted, also one
-    that equals an in-range ``ignore_index`` (its loss is 0).  :func:`running_scores` turns the matrix into train.py's numbers."""
+    that equals an in-range ``ignore_index`` (its loss is 0).  :func:`running_scores` turns the matrix into train.py's numbers.
+
+    ``weight``: the reference criterion's class weights (``nn.CrossEntropyLoss(weight, ...)`` under the top-k rule; e.g. CamVid's
+    ``class_weight`` table with its 0 for Void).  A fusable table (:func:`weight_fusable`: fp32 ``(C,)`` on the logits' device, finite and
+    >= 0) rides on the same HIP routes as no table -- the weighted twins of the loss launches, the same launch counts, scored and
+    validation routes included; any other table takes the composed route (``F.cross_entropy``).  The value test reads the device, so its
+    answer is kept per ``(data_ptr, _version)`` of the buffer: one read per table, none inside a captured step (``GraphedTrainStep``'s
+    warm-up asks first).  A buffer made under ``torch.inference_mode()`` carries no version and takes the composed route.  A captured graph holds the table's ADDRESS: change the weights in place (``criterion.weight.mul_(2)``,
+    ``.copy_``), never by assigning a new tensor."""
 
     score = None
 
@@ -116,8 +149,26 @@ class BootstrappedCrossEntropyLoss(nn.Module):
         self.k, self.thresh, self.ignore_index = k, thresh, ignore_index
         self.register_buffer('weight', weight)
 
+    def weight_takes_hip(self, classes, device):
+        """``weight_fusable(self.weight, classes, device)`` under the module switch, asked once per table (its address and version)."""
+        w = self.weight
+        if w is None or not USE_HIP_CLASS_WEIGHTS:
+            return False
+        try:
+            version = w._version
+        except RuntimeError:                                     # an inference tensor keeps no version: its changes cannot be seen,
+            return False                                         # so it is never cached -- the composed route, as before
+        key = (w.data_ptr(), version, w.dtype, tuple(w.shape), w.device, int(classes), torch.device(device))
+        held = self.__dict__.get('_weight_ok')
+        if held is None or held[0] != key:
+            held = self.__dict__['_weight_ok'] = (key, weight_fusable(w, classes, device))
+        return held[1]
+
     def forward(self, input, target):
-        return bootstrapped_cross_entropy(input, target, self.k, self.thresh, self.weight, self.ignore_index, self.score)
+        ok = None
+        if self.weight is not None and input.dim() == 4:
+            ok = self.weight_takes_hip(input.shape[1], input.device)
+        return bootstrapped_cross_entropy(input, target, self.k, self.thresh, self.weight, self.ignore_index, self.score, ok)
 
 
 @torch.no_grad()

@@ -1048,7 +1048,10 @@ class GraphedModel(nn.Module):
         ``evaluate`` graphs); the warm-up passes count into a scratch matrix.  ``loss`` is the graph's static 0-dim tensor: valid until
         the next call of the same shape.  The values are ``model.validate``'s (its note on an unprepared model's
         stock encoder applies).  What the graph cannot serve takes ``model.validate``'s routes, counting into the same
-        matrix."""
+        matrix.  A criterion with class weights the HIP loss takes (``training.weight_fusable``) is served the same way: the captured
+        launch holds the ADDRESS of ``criterion.weight``, so -- as with ``score.mat`` -- change the table in place (``weight.mul_(2)``,
+        ``weight.copy_(...)``; the next replay reads the new values), never by assigning a new tensor (a table at a new address gets a
+        new graph; a table that stops being fusable goes back to ``model.validate``'s composed route)."""
         criterion = self.criterion
         if criterion is None:
             raise ValueError('GraphedModel.validate needs the loss: GraphedModel(model, criterion=BootstrappedCrossEntropyLoss(...))')
@@ -1064,14 +1067,15 @@ class GraphedModel(nn.Module):
         device = next(model.parameters()).device
         confusion = None if n is None else self._confusion_on(device, x.shape[0])
         key = ('validate', tuple(x.shape), x.dtype, target.dtype, device, self._norm_of(x), tuple(target.shape), criterion.k, criterion.thresh,
-               criterion.ignore_index)
+               criterion.ignore_index, None if criterion.weight is None else criterion.weight.data_ptr())
         entry = self._graphs.get(key)
         if entry is None:
             from ..autograd import BootstrapMeanOfBatch
 
             def run(xs, ts, out):
                 masks, per_pixel = model.process_single_tensor(
-                    model.resized(xs), epilogue=Epilogue(Score(ts, n, out, self.per_image), ignore_index=criterion.ignore_index))
+                    model.resized(xs), epilogue=Epilogue(Score(ts, n, out, self.per_image), ignore_index=criterion.ignore_index,
+                                                              weight=criterion.weight))
                 return BootstrapMeanOfBatch.apply(per_pixel.flatten(1), criterion.k, criterion.thresh), masks
 
             entry = self._capture_counting(key, [x, target], device, run, confusion)

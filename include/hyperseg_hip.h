@@ -365,6 +365,15 @@ int hs_cross_entropy_score_fwd(int32_t dtype, const void* logits, const int64_t*
 int hs_upsample_ce_confusion_fwd(const float* x, int32_t batch, int32_t channels, int32_t Hi, int32_t Wi, int32_t Ho, int32_t Wo,
                                  const void* target, int32_t target_dtype, int64_t ignore_index, float* loss, int32_t num_classes,
                                  int32_t per_image, int64_t* confusion, uint8_t* mask, void* stream);
+/* ... with class weights (nn.CrossEntropyLoss(weight=...)): `weight` f32 (classes,) / (channels,) on the device, non-NULL else
+ * HS_ERR_BAD_ARG.  loss = weight[t] * (the unweighted entry's loss), one more f32 multiply, hs_cross_entropy_weighted_fwd's bits; masks
+ * and counts are the unweighted entries'.  The table is read by the launch only (capturable: the graph holds its address). */
+int hs_cross_entropy_score_weighted_fwd(int32_t dtype, const void* logits, const int64_t* target, const float* weight, int32_t batch,
+                                        int32_t classes, int64_t pixels, int64_t ignore_index, float* loss, int32_t num_classes,
+                                        int32_t per_image, int64_t* confusion, uint8_t* mask, void* stream);
+int hs_upsample_ce_confusion_weighted_fwd(const float* x, int32_t batch, int32_t channels, int32_t Hi, int32_t Wi, int32_t Ho, int32_t Wo,
+                                          const void* target, int32_t target_dtype, const float* weight, int64_t ignore_index, float* loss,
+                                          int32_t num_classes, int32_t per_image, int64_t* confusion, uint8_t* mask, void* stream);
 
 /* Backward of hs_patch_conv_fwd (plain input x, no fused prologue / epilogue), fp32 -- SURVEY.md Appendix E.
  * The reference has no backward of its own (autograd over F.pad/unfold/grouped conv2d/fold: meta_patch.py:35-57);
@@ -894,6 +903,24 @@ int hs_bootstrapped_ce_fwd(int32_t dtype, const void* logits, const int64_t* tar
                            int64_t ignore_index, int32_t k, float thresh, void* workspace, float* loss, float* out8, float* mean_out, void* stream);
 int hs_bootstrapped_ce_bwd(int32_t dtype, const void* logits, const int64_t* target, int32_t batch, int32_t classes, int64_t pixels,
                            int64_t ignore_index, const float* loss, const float* state8, const float* grad_mean, void* grad_logits, void* stream);
+/* The four entries above with class weights (nn.CrossEntropyLoss(weight, ignore_index, reduction='none') under the top-k rule): `weight` f32
+ * (classes,) on the device, non-NULL else HS_ERR_BAD_ARG; everything else is the unweighted twin's contract.
+ *   forward: loss = weight[t] * u, u the unweighted entry's loss -- one more f32 multiply; 0 where the target is ignore_index or outside
+ *     [0, classes).
+ *   adjoint: grad_logits = (softmax - onehot) * (weight[t] * upstream), upstream = grad_loss[e], or -- bootstrapped form -- the selection's
+ *     weight formed from the saved (weighted) loss as in hs_bootstrapped_ce_bwd; 0 where the target is not live.
+ * The selection ranks the weighted losses and relies on losses >= 0: the caller passes finite weights >= 0 (the table is never read on the
+ * host; a captured graph holds its address). */
+int hs_cross_entropy_weighted_fwd(int32_t dtype, const void* logits, const int64_t* target, const float* weight, int32_t batch, int32_t classes,
+                                  int64_t pixels, int64_t ignore_index, float* loss, void* stream);
+int hs_cross_entropy_weighted_bwd(int32_t dtype, const void* logits, const int64_t* target, const float* weight, int32_t batch, int32_t classes,
+                                  int64_t pixels, int64_t ignore_index, const float* grad_loss, void* grad_logits, void* stream);
+int hs_bootstrapped_ce_weighted_fwd(int32_t dtype, const void* logits, const int64_t* target, const float* weight, int32_t batch,
+                                    int32_t classes, int64_t pixels, int64_t ignore_index, int32_t k, float thresh, void* workspace, float* loss,
+                                    float* out8, float* mean_out, void* stream);
+int hs_bootstrapped_ce_weighted_bwd(int32_t dtype, const void* logits, const int64_t* target, const float* weight, int32_t batch,
+                                    int32_t classes, int64_t pixels, int64_t ignore_index, const float* loss, const float* state8,
+                                    const float* grad_mean, void* grad_logits, void* stream);
 
 /* Materialises a stage input (B, 2*coords + c_skip + c_prev, H, W); test/diagnostic twin of the
  * fused prologue (the product path never calls it). */
