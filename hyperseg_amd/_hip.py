@@ -3,9 +3,15 @@
 The library is the product: importing this module without the built .so raises, and every
 wrapper refuses non-CUDA / non-fp32 / non-contiguous tensors instead of falling back to anything.
 PyTorch is used only for device memory and the current HIP stream.
+
+``SIGNATURES`` is the one list of entries.  ``lib`` is the raw CDLL: an entry returns what the C function returns, for the callers
+that look at a status before deciding (HS_ERR_UNSUPPORTED = "nothing launched, take the other route") and pass it to ``check``
+afterwards.  ``run`` holds a checked twin of every entry that returns a status: ``run.hs_x_fwd(...)`` raises
+HipLibraryError('hs_x_fwd: <reason>') for anything but 0 -- what ``check(lib.hs_x_fwd(...), 'hs_x_fwd')`` does, with the name typed once.
 """
 import ctypes as C
 import os
+import types
 
 import torch
 
@@ -66,166 +72,142 @@ class S2wTrainLayerC(C.Structure):
                 ('bank', C.c_void_p), ('ld', C.c_int64), ('dbank', C.c_void_p), ('dw', C.c_void_p), ('ds', C.c_void_p)]
 
 
-def _load():
-    if not os.path.exists(_LIB_PATH):
-        raise HipLibraryError(
-            f'{_LIB_PATH} is missing: build it with `python -m hyperseg_amd.build` (hipcc, gfx950). '
-            'hyperseg_amd has no fallback path.')
-    lib = C.CDLL(_LIB_PATH)
-    i32, i64, vp = C.c_int32, C.c_int64, C.c_void_p
-    sig = {
-        'hs_version': ([], C.c_int),
-        'hs_build_info': ([], C.c_char_p),
-        'hs_signal2weights_fwd': ([vp, i32, i32, i32, i32, i32, i32, i32, vp, i32, i32, vp, i64, vp], C.c_int),
-        'hs_signal2weights_multi_fwd': ([vp, i32, i32, i32, i32, C.POINTER(S2wLayerC), i32, vp], C.c_int),
-        'hs_s2w_pack_floats': ([i32, i32, i32], C.c_int64),
-        'hs_s2w_pack_fwd': ([vp, i32, i32, i32, vp, vp], C.c_int),
-        'hs_bank_pack_fwd': ([vp, i32, i32, i32, i32, i32, i32, vp, i64, vp], C.c_int),
-        'hs_bn_fold_fwd': ([vp, vp, vp, vp, C.c_float, i32, vp, vp, vp], C.c_int),
-        'hs_patch_conv_fwd': ([C.POINTER(StageInputC), i32, i32, vp, i64, i32, i32, i32, i32, i32,
-                               C.POINTER(EpilogueC), vp, vp], C.c_int),
-        'hs_patch_conv_s2w_fwd': ([C.POINTER(StageInputC), i32, i32, vp, i64, i32, i32, C.POINTER(EpilogueC), vp,
-                                   vp, i32, i32, i32, i32, C.POINTER(S2wLayerC), i32, vp], C.c_int),
-        'hs_k1_chain_workspace': ([i32, i32, i32, C.POINTER(K1LevelC), i32], C.c_int64),
-        'hs_k1_chain_fwd': ([i32, i32, i32, C.POINTER(K1LevelC), i32, vp, vp, vp], C.c_int),
-        'hs_decoder_chain_workspace': ([i32, i32, i32, C.POINTER(K1LevelC), i32, C.POINTER(ChainIrLevelC)], C.c_int64),
-        'hs_decoder_chain_fwd': ([i32, i32, i32, C.POINTER(K1LevelC), i32, C.POINTER(ChainIrLevelC), vp, vp, vp], C.c_int),
-        'hs_meta_conv_fwd': ([vp, i32, i32, i32, i32, vp, i64] + [i32] * 13 + [C.POINTER(EpilogueC), vp, vp], C.c_int),
-        'hs_meta_conv_bwd': ([vp, i32, i32, i32, i32, vp, i64] + [i32] * 12 + [vp, vp, vp, i64, vp], C.c_int),
-        'hs_patch_conv_gen_fwd': ([C.POINTER(StageInputC), i32, i32, vp, i32, C.POINTER(S2wLayerC), i32,
-                                   C.POINTER(EpilogueC), vp, vp], C.c_int),
-        'hs_patch_ir_fwd': ([C.POINTER(StageInputC), i32, i32, vp, i64, i32, i32, C.POINTER(EpilogueC),
-                             C.POINTER(EpilogueC), C.POINTER(EpilogueC), i32, i32, vp, vp], C.c_int),
-        'hs_patch_ir_v0_fwd': ([C.POINTER(StageInputC), i32, i32, vp, i64, i32, i32, C.POINTER(EpilogueC),
-                                C.POINTER(EpilogueC), C.POINTER(EpilogueC), i32, vp, vp], C.c_int),
-        'hs_patch_ir_v0_ws_fwd': ([C.POINTER(StageInputC), i32, i32, vp, i64, i32, i32, C.POINTER(EpilogueC),
-                                   C.POINTER(EpilogueC), C.POINTER(EpilogueC), i32, vp, i64, vp, vp], C.c_int),
-        'hs_patch_ir_v0_workspace': ([C.POINTER(StageInputC), i32, i32, i32, i32], C.c_int64),
-        'hs_halo_tiles_fwd': ([i32, vp, i32, i32, i32, i32, i32, i32, vp, i32, vp], C.c_int),
-        'hs_halo_tiles_bwd': ([i32, vp, i32, i32, i32, i32, i32, i32, vp, i32, vp], C.c_int),
-        'hs_tile_interior_fwd': ([i32, vp, i32, i32, i32, i32, i32, i32, vp, vp], C.c_int),
-        'hs_tile_interior_bwd': ([i32, vp, i32, i32, i32, i32, i32, i32, vp, vp], C.c_int),
-        'hs_dw_tiles_fwd': ([i32, vp, vp, i64, i32, i32, i32, i32, i32, i32, vp, i32, vp], C.c_int),
-        'hs_dw_tiles_bwd_in': ([i32, vp, vp, i64, i32, i32, i32, i32, i32, i32, vp, i32, vp], C.c_int),
-        'hs_dw_tiles_bwd_w': ([i32, vp, vp, i32, i32, i32, i32, i32, i32, vp, i64, i32, vp], C.c_int),
-        'hs_bank_unpack_fwd': ([vp, i64, i32, i32, i32, i32, i32, i32, vp, vp], C.c_int),
-        'hs_upsample_bilinear_bwd': ([vp, i64, i32, i32, i32, i32, i32, i32, vp, vp], C.c_int),
-        'hs_upsample_bilinear_bf16_fwd': ([vp, i32, i32, i32, i32, i32, i32, vp, vp], C.c_int),
-        'hs_upsample_bilinear_f16_fwd': ([vp, i32, i32, i32, i32, i32, i32, vp, vp], C.c_int),
-        'hs_upsample_bilinear_typed_bwd': ([i32, vp, i64, i32, i32, i32, i32, i32, i32, vp, vp], C.c_int),
-        'hs_bn_train_workspace': ([i32], C.c_int64),
-        'hs_bn_train_stats_fwd': ([i32, vp, i32, i32, i64, vp, vp], C.c_int),
-        'hs_dw_tiles_bn_fwd': ([i32, vp, vp, vp, vp, vp, vp, C.c_float, C.c_float, i32, vp, vp, vp, vp, i64, i32, i32, i32, i32, i32, i32, vp, i32, vp], C.c_int),
-        'hs_dw_tiles_bn_bwd_w': ([i32, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, i64, i32, vp], C.c_int),
-        'hs_s2w_train_fwd': ([vp, i32, i32, i32, i32, C.POINTER(S2wTrainLayerC), i32, vp], C.c_int),
-        'hs_s2w_train_workspace': ([i32, i32, i32, C.POINTER(S2wTrainLayerC), i32], C.c_int64),
-        'hs_s2w_train_bwd': ([vp, i32, i32, i32, i32, C.POINTER(S2wTrainLayerC), i32, vp, vp, i64, vp], C.c_int),
-        'hs_cross_entropy_fwd': ([vp, vp, i32, i32, i64, i64, vp, vp], C.c_int),
-        'hs_cross_entropy_bwd': ([vp, vp, i32, i32, i64, i64, vp, vp, vp], C.c_int),
-        'hs_cross_entropy_typed_fwd': ([i32, vp, vp, i32, i32, i64, i64, vp, vp], C.c_int),
-        'hs_cross_entropy_typed_bwd': ([i32, vp, vp, i32, i32, i64, i64, vp, vp, vp], C.c_int),
-        'hs_bootstrapped_ce_fwd': ([i32, vp, vp, i32, i32, i64, i64, i32, C.c_float, vp, vp, vp, vp, vp], C.c_int),
-        'hs_bootstrapped_ce_bwd': ([i32, vp, vp, i32, i32, i64, i64, vp, vp, vp, vp, vp], C.c_int),
-        'hs_cross_entropy_weighted_fwd': ([i32, vp, vp, vp, i32, i32, i64, i64, vp, vp], C.c_int),
-        'hs_cross_entropy_weighted_bwd': ([i32, vp, vp, vp, i32, i32, i64, i64, vp, vp, vp], C.c_int),
-        'hs_bootstrapped_ce_weighted_fwd': ([i32, vp, vp, vp, i32, i32, i64, i64, i32, C.c_float, vp, vp, vp, vp, vp], C.c_int),
-        'hs_bootstrapped_ce_weighted_bwd': ([i32, vp, vp, vp, i32, i32, i64, i64, vp, vp, vp, vp, vp], C.c_int),
-        'hs_bn_act_train_fwd': ([i32, vp, i32, i32, i64, vp, vp, vp, vp, C.c_float, C.c_float, i32, vp, vp, vp, vp, vp, vp], C.c_int),
-        'hs_bn_act_train_bwd': ([i32, vp, vp, i32, i32, i64, vp, vp, vp, vp, C.c_float, i32, vp, vp, vp, vp, vp], C.c_int),
-        'hs_dw_tiles_bn_bwd_in_partials': ([i32, i32, i32, i32, i32], C.c_int64),
-        'hs_dw_tiles_bn_bwd_in': ([i32, vp, vp, i64, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, i32, vp], C.c_int),
-        'hs_bn_act_train_bwd_apply': ([i32, vp, vp, i32, i32, i64, vp, vp, vp, vp, i32, vp, i64, vp, vp, vp, vp], C.c_int),
-        'hs_bootstrap_mean_workspace': ([], C.c_int64),
-        'hs_bootstrap_mean_fwd': ([vp, i32, i32, C.c_float, vp, vp, vp], C.c_int),
-        'hs_bootstrap_mean_bwd': ([vp, i32, vp, vp, vp, vp], C.c_int),
-        'hs_bootstrap_mean_batched_fwd': ([vp, i32, i32, i32, C.c_float, vp, vp, vp], C.c_int),
-        'hs_bootstrap_mean_batched_bwd': ([vp, i32, i32, vp, vp, vp, vp], C.c_int),
-        'hs_patch_ir_route': ([C.POINTER(StageInputC), i32, i32, i32, i32, i32, i32], C.c_int),
-        'hs_ir_tile_map': ([i32, i32, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), i32], C.c_int),
-        'hs_upsample_bilinear_fwd': ([vp, i32, i32, i32, i32, i32, i32, vp, vp], C.c_int),
-        'hs_upsample_argmax_fwd': ([vp, i32, i32, i32, i32, i32, i32, vp, vp], C.c_int),
-        'hs_eval_max_classes': ([], C.c_int),
-        'hs_upsample_confusion_fwd': ([vp, i32, i32, i32, i32, i32, i32, vp, i32, i32, i32, vp, vp, vp], C.c_int),
-        'hs_confusion_fwd': ([vp, i32, vp, i32, i32, i64, i32, i32, vp, vp], C.c_int),
-        'hs_upsample2_confusion_fwd': ([vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, i32, i32, i32, vp, vp, vp], C.c_int),
-        'hs_cross_entropy_score_fwd': ([i32, vp, vp, i32, i32, i64, i64, vp, i32, i32, vp, vp, vp], C.c_int),
-        'hs_upsample_ce_confusion_fwd': ([vp, i32, i32, i32, i32, i32, i32, vp, i32, i64, vp, i32, i32, vp, vp, vp], C.c_int),
-        'hs_cross_entropy_score_weighted_fwd': ([i32, vp, vp, vp, i32, i32, i64, i64, vp, i32, i32, vp, vp, vp], C.c_int),
-        'hs_upsample_ce_confusion_weighted_fwd': ([vp, i32, i32, i32, i32, i32, i32, vp, i32, vp, i64, vp, i32, i32, vp, vp, vp], C.c_int),
-        'hs_stage_input_fwd': ([C.POINTER(StageInputC), vp, vp], C.c_int),
-        'hs_stage_input_typed_fwd': ([C.POINTER(StageInputC), i32, i32, vp, vp], C.c_int),
-        'hs_patch_conv_bwd_input': ([vp, vp, i64, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp], C.c_int),
-        'hs_patch_conv_bwd_weight': ([vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, i64, vp], C.c_int),
-        'hs_patch_conv_plain_fwd': ([i32, vp, vp, i64, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp], C.c_int),
-        'hs_patch_conv_plain_bwd_in': ([i32, vp, vp, i64, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp], C.c_int),
-        'hs_patch_conv_plain_bwd_w': ([i32, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, i64, vp], C.c_int),
-        'hs_depthwise_conv_fwd': ([vp, i32, i32, i32, i32, vp, i32, i32, i32, i32, i32, i32, vp, vp, i32, vp, vp, vp, vp, vp], C.c_int),
-        'hs_pointwise_conv_fwd': ([vp, i32, i32, i32, vp, i32, vp, vp, vp, i32, vp, vp, vp], C.c_int),
-        'hs_affine_act_fwd': ([vp, i32, i32, i32, vp, vp, i32, vp, vp, vp], C.c_int),
-        'hs_patch_conv_bn_fwd': ([i32, vp, vp, vp, vp, vp, vp, C.c_float, C.c_float, i32, vp, vp, vp, vp, i64, i32, i32, i32, i32, i32, i32, i32, vp, vp], C.c_int),
-        'hs_patch_conv_bn_bwd_w': ([i32, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, i64, vp], C.c_int),
-        'hs_bootstrap_mean_of_batch_fwd': ([vp, i32, i32, i32, C.c_float, vp, vp, vp, vp], C.c_int),
-        'hs_bootstrap_mean_of_batch_bwd': ([vp, i32, i32, vp, vp, vp, vp], C.c_int),
-        'hs_adam_blocks': ([vp, i32], C.c_int64),
-        'hs_adam_step': ([vp, vp, vp, vp, vp, i32, vp, C.c_float, C.c_double, C.c_double, C.c_float, C.c_float, i32, i32, vp, vp], C.c_int),
-        'hs_adam_step_amp': ([vp, vp, vp, vp, vp, i32, vp, C.c_float, C.c_double, C.c_double, C.c_float, C.c_float, i32, i32, vp, vp, vp, vp], C.c_int),
-        'hs_depthwise_pool_blocks': ([i32, i32], C.c_int),
-        'hs_depthwise_conv_se_fwd': ([vp, i32, i32, i32, i32, vp, i32, i32, i32, i32, i32, i32, vp, vp, i32, vp, vp, vp, C.POINTER(SeTailC), vp], C.c_int),
-        'hs_mbconv_expand_dw_se_fwd': ([vp, i32, i32, i32, i32, vp, i32, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, C.POINTER(SeTailC), vp], C.c_int),
-        'hs_se_tail_workspace': ([i32, i32, i32, i32, i64], C.c_int64),
-        'hs_se_tail_tails': ([i32, i32, i32, i64], C.c_int),
-        'hs_mbconv_se_workgroups': ([i32, i32, i32, i32, i32, i32], C.c_int64),
-        'hs_stem_conv_fwd': ([vp, i32, i32, i32, i32, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp], C.c_int),
-        'hs_mbconv_tiles': ([i32, i32, i32, i32], C.c_int),
-        'hs_stem_dw_fwd': ([vp, i32, i32, i32, vp, i32, vp, vp, i32, i32, i32, i32, vp, i32, i32, i32, vp, vp, vp, vp, vp], C.c_int),
-        'hs_image_ingest_fwd': ([vp, i32, i32, i32, i32, i32, vp, vp, vp], C.c_int),
-        'hs_stem_dw_u8_fwd': ([vp, i32, vp, i32, i32, i32, vp, i32, vp, vp, i32, i32, i32, i32, vp, i32, i32, i32, vp, vp, vp, vp, vp], C.c_int),
-        'hs_overlay_fwd': ([vp, vp, i32, i32, i32, i32, vp, i32, i32, vp, vp], C.c_int),
-        'hs_upsample_overlay_fwd': ([vp, i32, i32, i32, i32, i32, i32, vp, i32, vp, i32, i32, vp, vp, vp], C.c_int),
-        'hs_frame_resize_fwd': ([vp, i32, i32, i32, i32, vp, vp, i32, i32, vp, vp, i32, i32, i32, i32, i32, i32, i32, C.c_uint32, vp, vp, vp], C.c_int),
-        'hs_label_resize_fwd': ([vp, i32, i32, i32, i32, vp, i32, vp, i32, i32, i32, i32, i32, i32, i32, vp, i32, vp], C.c_int),
-        'hs_resize_tables_fwd': ([vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp], C.c_int),
-        'hs_frame_resize_batch_fwd': ([vp, i32, i32, i32, i32, vp, vp, vp, vp, i32, i32, i32, C.c_uint32, vp, vp, vp], C.c_int),
-        'hs_label_resize_batch_fwd': ([vp, i32, i32, i32, i32, vp, vp, vp, i32, i32, i32, vp, i32, vp], C.c_int),
-        'hs_color_jitter_fwd': ([vp, i32, i32, i32, i32, vp, vp, vp, vp, vp], C.c_int),
-        'hs_frame_rotate_fwd': ([vp, i32, i32, i32, i32, vp, i32, i32, C.c_uint32, C.c_uint32, vp, vp, vp], C.c_int),
-        'hs_label_rotate_fwd': ([vp, i32, i32, i32, i32, vp, i32, i32, i32, i32, vp, i32, vp], C.c_int),
-        'hs_resize_tables_ragged_fwd': ([vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp], C.c_int),
-        'hs_color_jitter_ragged_fwd': ([vp, i32, i32, i32, i32, vp, vp, vp, vp, vp], C.c_int),
-        'hs_frame_resize_ragged_fwd': ([vp, i32, i32, i32, i32, vp, vp, vp, vp, i32, i32, i32, vp, vp], C.c_int),
-        'hs_label_resize_ragged_fwd': ([vp, i32, i32, i32, i32, vp, vp, vp, i32, i32, vp, vp], C.c_int),
-        'hs_frame_rotate_ragged_fwd': ([vp, i32, i32, i32, i32, vp, vp, vp, i32, i32, C.c_uint32, C.c_uint32, vp, vp, vp], C.c_int),
-        'hs_label_rotate_ragged_fwd': ([vp, i32, i32, i32, vp, vp, vp, i32, i32, i32, i32, vp, i32, vp], C.c_int),
-        'hs_mbconv_expand_dw_fwd': ([vp, i32, i32, i32, i32, vp, i32, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp], C.c_int),
-        'hs_se_gate_fwd': ([vp, i32, i32, i32, C.c_float, vp, vp, i32, vp, vp, vp, vp, vp, i32, vp, vp, vp], C.c_int),
-        'hs_gemm_split_kp': ([i32], C.c_int),
-        'hs_gemm_split_fwd': ([vp, vp, vp, vp, vp, i32, vp, vp, i32, i32, i32, i32, i32, vp], C.c_int),
-        'hs_gemm_split_conv2x2_fwd': ([vp, vp, vp, vp, i32, vp, vp, i32, i32, i32, i32, i32, i32, vp], C.c_int),
-        'hs_gemm_split_up2_fwd': ([vp, vp, vp, vp, i32, vp, i32, i32, i32, i32, i32, i32, vp], C.c_int),
-        'hs_pooled_shift_fwd': ([vp, i32, C.c_float, vp, vp, vp, i32, i32, vp], C.c_int),
-    }
-    for name, (argtypes, restype) in sig.items():
-        fn = getattr(lib, name)          # AttributeError here = the .so does not match the header
-        fn.argtypes, fn.restype = argtypes, restype
-    if lib.hs_version() != 1:
-        raise HipLibraryError(f'ABI mismatch: library reports version {lib.hs_version()}, binding expects 1')
-    return lib
-
-
-lib = _load()
-EXPORTS = ['hs_version', 'hs_build_info', 'hs_signal2weights_fwd', 'hs_signal2weights_multi_fwd', 'hs_s2w_pack_floats', 'hs_s2w_pack_fwd', 'hs_bank_pack_fwd', 'hs_bn_fold_fwd',
-           'hs_patch_conv_fwd', 'hs_patch_conv_s2w_fwd', 'hs_k1_chain_workspace', 'hs_k1_chain_fwd', 'hs_decoder_chain_workspace', 'hs_decoder_chain_fwd', 'hs_meta_conv_fwd', 'hs_meta_conv_bwd', 'hs_patch_conv_gen_fwd', 'hs_patch_ir_fwd', 'hs_patch_ir_v0_fwd', 'hs_patch_ir_v0_ws_fwd', 'hs_patch_ir_v0_workspace', 'hs_patch_ir_route', 'hs_ir_tile_map', 'hs_upsample_bilinear_fwd', 'hs_upsample_argmax_fwd',
-           'hs_stage_input_fwd', 'hs_depthwise_conv_fwd', 'hs_depthwise_pool_blocks', 'hs_stem_conv_fwd', 'hs_stem_dw_fwd', 'hs_mbconv_tiles', 'hs_mbconv_expand_dw_fwd', 'hs_se_gate_fwd', 'hs_depthwise_conv_se_fwd', 'hs_mbconv_expand_dw_se_fwd', 'hs_se_tail_workspace', 'hs_se_tail_tails', 'hs_mbconv_se_workgroups', 'hs_pointwise_conv_fwd', 'hs_affine_act_fwd', 'hs_gemm_split_kp', 'hs_gemm_split_fwd', 'hs_gemm_split_conv2x2_fwd', 'hs_gemm_split_up2_fwd', 'hs_pooled_shift_fwd', 'hs_patch_conv_bwd_input',
-           'hs_patch_conv_bwd_weight', 'hs_halo_tiles_fwd', 'hs_halo_tiles_bwd', 'hs_tile_interior_fwd', 'hs_tile_interior_bwd', 'hs_dw_tiles_fwd', 'hs_dw_tiles_bwd_in', 'hs_dw_tiles_bwd_w',
-           'hs_s2w_train_fwd', 'hs_s2w_train_workspace', 'hs_s2w_train_bwd', 'hs_cross_entropy_fwd', 'hs_cross_entropy_bwd', 'hs_cross_entropy_typed_fwd', 'hs_cross_entropy_typed_bwd', 'hs_bootstrapped_ce_fwd', 'hs_bootstrapped_ce_bwd', 'hs_bootstrap_mean_workspace', 'hs_bootstrap_mean_fwd', 'hs_bootstrap_mean_bwd', 'hs_bootstrap_mean_batched_fwd', 'hs_bootstrap_mean_batched_bwd', 'hs_bn_train_workspace', 'hs_bn_train_stats_fwd', 'hs_dw_tiles_bn_fwd', 'hs_dw_tiles_bn_bwd_w', 'hs_patch_conv_bn_fwd', 'hs_patch_conv_bn_bwd_w', 'hs_adam_blocks', 'hs_adam_step', 'hs_bootstrap_mean_of_batch_fwd', 'hs_bootstrap_mean_of_batch_bwd', 'hs_upsample_bilinear_bwd', 'hs_upsample_bilinear_typed_bwd', 'hs_upsample_bilinear_bf16_fwd', 'hs_stage_input_typed_fwd', 'hs_bank_unpack_fwd', 'hs_bn_act_train_fwd',
-           'hs_bn_act_train_bwd', 'hs_dw_tiles_bn_bwd_in_partials', 'hs_dw_tiles_bn_bwd_in', 'hs_bn_act_train_bwd_apply', 'hs_patch_conv_plain_fwd', 'hs_patch_conv_plain_bwd_in', 'hs_patch_conv_plain_bwd_w',
-           'hs_upsample_bilinear_f16_fwd', 'hs_adam_step_amp', 'hs_eval_max_classes', 'hs_upsample_confusion_fwd', 'hs_confusion_fwd', 'hs_upsample2_confusion_fwd',
-           'hs_image_ingest_fwd', 'hs_stem_dw_u8_fwd', 'hs_overlay_fwd', 'hs_upsample_overlay_fwd',
-           'hs_frame_resize_fwd', 'hs_label_resize_fwd', 'hs_resize_tables_fwd', 'hs_frame_resize_batch_fwd', 'hs_label_resize_batch_fwd', 'hs_color_jitter_fwd', 'hs_frame_rotate_fwd', 'hs_label_rotate_fwd',
-           'hs_resize_tables_ragged_fwd', 'hs_color_jitter_ragged_fwd', 'hs_frame_resize_ragged_fwd', 'hs_label_resize_ragged_fwd', 'hs_frame_rotate_ragged_fwd', 'hs_label_rotate_ragged_fwd',
-           'hs_cross_entropy_score_fwd', 'hs_upsample_ce_confusion_fwd',
-           'hs_cross_entropy_weighted_fwd', 'hs_cross_entropy_weighted_bwd', 'hs_bootstrapped_ce_weighted_fwd', 'hs_bootstrapped_ce_weighted_bwd',
-           'hs_cross_entropy_score_weighted_fwd', 'hs_upsample_ce_confusion_weighted_fwd']
+STATUS = 'hs_status'      # what a SIGNATURES row returns: this marker (0, a negative HS_ERR_* or a hipError_t) or a ctypes value type
+i32, i64, vp = C.c_int32, C.c_int64, C.c_void_p
+# THE list of the library's entries (tests/test_model_boundary.py holds it against the header): name -> (argtypes, STATUS | value type).
+# Value entries are sizes, counts, route codes, hs_version and hs_build_info; every launcher, hs_adam_step* and hs_ir_tile_map return a status.
+SIGNATURES = {
+    'hs_version': ([], C.c_int),
+    'hs_build_info': ([], C.c_char_p),
+    'hs_signal2weights_fwd': ([vp, i32, i32, i32, i32, i32, i32, i32, vp, i32, i32, vp, i64, vp], STATUS),
+    'hs_signal2weights_multi_fwd': ([vp, i32, i32, i32, i32, C.POINTER(S2wLayerC), i32, vp], STATUS),
+    'hs_s2w_pack_floats': ([i32, i32, i32], C.c_int64),
+    'hs_s2w_pack_fwd': ([vp, i32, i32, i32, vp, vp], STATUS),
+    'hs_bank_pack_fwd': ([vp, i32, i32, i32, i32, i32, i32, vp, i64, vp], STATUS),
+    'hs_bn_fold_fwd': ([vp, vp, vp, vp, C.c_float, i32, vp, vp, vp], STATUS),
+    'hs_patch_conv_fwd': ([C.POINTER(StageInputC), i32, i32, vp, i64, i32, i32, i32, i32, i32,
+                           C.POINTER(EpilogueC), vp, vp], STATUS),
+    'hs_patch_conv_s2w_fwd': ([C.POINTER(StageInputC), i32, i32, vp, i64, i32, i32, C.POINTER(EpilogueC), vp,
+                               vp, i32, i32, i32, i32, C.POINTER(S2wLayerC), i32, vp], STATUS),
+    'hs_k1_chain_workspace': ([i32, i32, i32, C.POINTER(K1LevelC), i32], C.c_int64),
+    'hs_k1_chain_fwd': ([i32, i32, i32, C.POINTER(K1LevelC), i32, vp, vp, vp], STATUS),
+    'hs_decoder_chain_workspace': ([i32, i32, i32, C.POINTER(K1LevelC), i32, C.POINTER(ChainIrLevelC)], C.c_int64),
+    'hs_decoder_chain_fwd': ([i32, i32, i32, C.POINTER(K1LevelC), i32, C.POINTER(ChainIrLevelC), vp, vp, vp], STATUS),
+    'hs_meta_conv_fwd': ([vp, i32, i32, i32, i32, vp, i64] + [i32] * 13 + [C.POINTER(EpilogueC), vp, vp], STATUS),
+    'hs_meta_conv_bwd': ([vp, i32, i32, i32, i32, vp, i64] + [i32] * 12 + [vp, vp, vp, i64, vp], STATUS),
+    'hs_patch_conv_gen_fwd': ([C.POINTER(StageInputC), i32, i32, vp, i32, C.POINTER(S2wLayerC), i32,
+                               C.POINTER(EpilogueC), vp, vp], STATUS),
+    'hs_patch_ir_fwd': ([C.POINTER(StageInputC), i32, i32, vp, i64, i32, i32, C.POINTER(EpilogueC),
+                         C.POINTER(EpilogueC), C.POINTER(EpilogueC), i32, i32, vp, vp], STATUS),
+    'hs_patch_ir_v0_fwd': ([C.POINTER(StageInputC), i32, i32, vp, i64, i32, i32, C.POINTER(EpilogueC),
+                            C.POINTER(EpilogueC), C.POINTER(EpilogueC), i32, vp, vp], STATUS),
+    'hs_patch_ir_v0_ws_fwd': ([C.POINTER(StageInputC), i32, i32, vp, i64, i32, i32, C.POINTER(EpilogueC),
+                               C.POINTER(EpilogueC), C.POINTER(EpilogueC), i32, vp, i64, vp, vp], STATUS),
+    'hs_patch_ir_v0_workspace': ([C.POINTER(StageInputC), i32, i32, i32, i32], C.c_int64),
+    'hs_halo_tiles_fwd': ([i32, vp, i32, i32, i32, i32, i32, i32, vp, i32, vp], STATUS),
+    'hs_halo_tiles_bwd': ([i32, vp, i32, i32, i32, i32, i32, i32, vp, i32, vp], STATUS),
+    'hs_tile_interior_fwd': ([i32, vp, i32, i32, i32, i32, i32, i32, vp, vp], STATUS),
+    'hs_tile_interior_bwd': ([i32, vp, i32, i32, i32, i32, i32, i32, vp, vp], STATUS),
+    'hs_dw_tiles_fwd': ([i32, vp, vp, i64, i32, i32, i32, i32, i32, i32, vp, i32, vp], STATUS),
+    'hs_dw_tiles_bwd_in': ([i32, vp, vp, i64, i32, i32, i32, i32, i32, i32, vp, i32, vp], STATUS),
+    'hs_dw_tiles_bwd_w': ([i32, vp, vp, i32, i32, i32, i32, i32, i32, vp, i64, i32, vp], STATUS),
+    'hs_bank_unpack_fwd': ([vp, i64, i32, i32, i32, i32, i32, i32, vp, vp], STATUS),
+    'hs_upsample_bilinear_bwd': ([vp, i64, i32, i32, i32, i32, i32, i32, vp, vp], STATUS),
+    'hs_upsample_bilinear_bf16_fwd': ([vp, i32, i32, i32, i32, i32, i32, vp, vp], STATUS),
+    'hs_upsample_bilinear_f16_fwd': ([vp, i32, i32, i32, i32, i32, i32, vp, vp], STATUS),
+    'hs_upsample_bilinear_typed_bwd': ([i32, vp, i64, i32, i32, i32, i32, i32, i32, vp, vp], STATUS),
+    'hs_bn_train_workspace': ([i32], C.c_int64),
+    'hs_bn_train_stats_fwd': ([i32, vp, i32, i32, i64, vp, vp], STATUS),
+    'hs_dw_tiles_bn_fwd': ([i32, vp, vp, vp, vp, vp, vp, C.c_float, C.c_float, i32, vp, vp, vp, vp, i64, i32, i32, i32, i32, i32, i32, vp, i32, vp], STATUS),
+    'hs_dw_tiles_bn_bwd_w': ([i32, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, i64, i32, vp], STATUS),
+    'hs_s2w_train_fwd': ([vp, i32, i32, i32, i32, C.POINTER(S2wTrainLayerC), i32, vp], STATUS),
+    'hs_s2w_train_workspace': ([i32, i32, i32, C.POINTER(S2wTrainLayerC), i32], C.c_int64),
+    'hs_s2w_train_bwd': ([vp, i32, i32, i32, i32, C.POINTER(S2wTrainLayerC), i32, vp, vp, i64, vp], STATUS),
+    'hs_cross_entropy_fwd': ([vp, vp, i32, i32, i64, i64, vp, vp], STATUS),
+    'hs_cross_entropy_bwd': ([vp, vp, i32, i32, i64, i64, vp, vp, vp], STATUS),
+    'hs_cross_entropy_typed_fwd': ([i32, vp, vp, i32, i32, i64, i64, vp, vp], STATUS),
+    'hs_cross_entropy_typed_bwd': ([i32, vp, vp, i32, i32, i64, i64, vp, vp, vp], STATUS),
+    'hs_bootstrapped_ce_fwd': ([i32, vp, vp, i32, i32, i64, i64, i32, C.c_float, vp, vp, vp, vp, vp], STATUS),
+    'hs_bootstrapped_ce_bwd': ([i32, vp, vp, i32, i32, i64, i64, vp, vp, vp, vp, vp], STATUS),
+    'hs_cross_entropy_weighted_fwd': ([i32, vp, vp, vp, i32, i32, i64, i64, vp, vp], STATUS),
+    'hs_cross_entropy_weighted_bwd': ([i32, vp, vp, vp, i32, i32, i64, i64, vp, vp, vp], STATUS),
+    'hs_bootstrapped_ce_weighted_fwd': ([i32, vp, vp, vp, i32, i32, i64, i64, i32, C.c_float, vp, vp, vp, vp, vp], STATUS),
+    'hs_bootstrapped_ce_weighted_bwd': ([i32, vp, vp, vp, i32, i32, i64, i64, vp, vp, vp, vp, vp], STATUS),
+    'hs_bn_act_train_fwd': ([i32, vp, i32, i32, i64, vp, vp, vp, vp, C.c_float, C.c_float, i32, vp, vp, vp, vp, vp, vp], STATUS),
+    'hs_bn_act_train_bwd': ([i32, vp, vp, i32, i32, i64, vp, vp, vp, vp, C.c_float, i32, vp, vp, vp, vp, vp], STATUS),
+    'hs_dw_tiles_bn_bwd_in_partials': ([i32, i32, i32, i32, i32], C.c_int64),
+    'hs_dw_tiles_bn_bwd_in': ([i32, vp, vp, i64, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, i32, vp], STATUS),
+    'hs_bn_act_train_bwd_apply': ([i32, vp, vp, i32, i32, i64, vp, vp, vp, vp, i32, vp, i64, vp, vp, vp, vp], STATUS),
+    'hs_bootstrap_mean_workspace': ([], C.c_int64),
+    'hs_bootstrap_mean_fwd': ([vp, i32, i32, C.c_float, vp, vp, vp], STATUS),
+    'hs_bootstrap_mean_bwd': ([vp, i32, vp, vp, vp, vp], STATUS),
+    'hs_bootstrap_mean_batched_fwd': ([vp, i32, i32, i32, C.c_float, vp, vp, vp], STATUS),
+    'hs_bootstrap_mean_batched_bwd': ([vp, i32, i32, vp, vp, vp, vp], STATUS),
+    'hs_patch_ir_route': ([C.POINTER(StageInputC), i32, i32, i32, i32, i32, i32], C.c_int),
+    'hs_ir_tile_map': ([i32, i32, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), i32], STATUS),
+    'hs_upsample_bilinear_fwd': ([vp, i32, i32, i32, i32, i32, i32, vp, vp], STATUS),
+    'hs_upsample_argmax_fwd': ([vp, i32, i32, i32, i32, i32, i32, vp, vp], STATUS),
+    'hs_eval_max_classes': ([], C.c_int),
+    'hs_upsample_confusion_fwd': ([vp, i32, i32, i32, i32, i32, i32, vp, i32, i32, i32, vp, vp, vp], STATUS),
+    'hs_confusion_fwd': ([vp, i32, vp, i32, i32, i64, i32, i32, vp, vp], STATUS),
+    'hs_upsample2_confusion_fwd': ([vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, i32, i32, i32, vp, vp, vp], STATUS),
+    'hs_cross_entropy_score_fwd': ([i32, vp, vp, i32, i32, i64, i64, vp, i32, i32, vp, vp, vp], STATUS),
+    'hs_upsample_ce_confusion_fwd': ([vp, i32, i32, i32, i32, i32, i32, vp, i32, i64, vp, i32, i32, vp, vp, vp], STATUS),
+    'hs_cross_entropy_score_weighted_fwd': ([i32, vp, vp, vp, i32, i32, i64, i64, vp, i32, i32, vp, vp, vp], STATUS),
+    'hs_upsample_ce_confusion_weighted_fwd': ([vp, i32, i32, i32, i32, i32, i32, vp, i32, vp, i64, vp, i32, i32, vp, vp, vp], STATUS),
+    'hs_stage_input_fwd': ([C.POINTER(StageInputC), vp, vp], STATUS),
+    'hs_stage_input_typed_fwd': ([C.POINTER(StageInputC), i32, i32, vp, vp], STATUS),
+    'hs_patch_conv_bwd_input': ([vp, vp, i64, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp], STATUS),
+    'hs_patch_conv_bwd_weight': ([vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, i64, vp], STATUS),
+    'hs_patch_conv_plain_fwd': ([i32, vp, vp, i64, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp], STATUS),
+    'hs_patch_conv_plain_bwd_in': ([i32, vp, vp, i64, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp], STATUS),
+    'hs_patch_conv_plain_bwd_w': ([i32, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, i64, vp], STATUS),
+    'hs_depthwise_conv_fwd': ([vp, i32, i32, i32, i32, vp, i32, i32, i32, i32, i32, i32, vp, vp, i32, vp, vp, vp, vp, vp], STATUS),
+    'hs_pointwise_conv_fwd': ([vp, i32, i32, i32, vp, i32, vp, vp, vp, i32, vp, vp, vp], STATUS),
+    'hs_affine_act_fwd': ([vp, i32, i32, i32, vp, vp, i32, vp, vp, vp], STATUS),
+    'hs_patch_conv_bn_fwd': ([i32, vp, vp, vp, vp, vp, vp, C.c_float, C.c_float, i32, vp, vp, vp, vp, i64, i32, i32, i32, i32, i32, i32, i32, vp, vp], STATUS),
+    'hs_patch_conv_bn_bwd_w': ([i32, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, i64, vp], STATUS),
+    'hs_bootstrap_mean_of_batch_fwd': ([vp, i32, i32, i32, C.c_float, vp, vp, vp, vp], STATUS),
+    'hs_bootstrap_mean_of_batch_bwd': ([vp, i32, i32, vp, vp, vp, vp], STATUS),
+    'hs_adam_blocks': ([vp, i32], C.c_int64),
+    'hs_adam_step': ([vp, vp, vp, vp, vp, i32, vp, C.c_float, C.c_double, C.c_double, C.c_float, C.c_float, i32, i32, vp, vp], STATUS),
+    'hs_adam_step_amp': ([vp, vp, vp, vp, vp, i32, vp, C.c_float, C.c_double, C.c_double, C.c_float, C.c_float, i32, i32, vp, vp, vp, vp], STATUS),
+    'hs_depthwise_pool_blocks': ([i32, i32], C.c_int),
+    'hs_depthwise_conv_se_fwd': ([vp, i32, i32, i32, i32, vp, i32, i32, i32, i32, i32, i32, vp, vp, i32, vp, vp, vp, C.POINTER(SeTailC), vp], STATUS),
+    'hs_mbconv_expand_dw_se_fwd': ([vp, i32, i32, i32, i32, vp, i32, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, C.POINTER(SeTailC), vp], STATUS),
+    'hs_se_tail_workspace': ([i32, i32, i32, i32, i64], C.c_int64),
+    'hs_se_tail_tails': ([i32, i32, i32, i64], C.c_int),
+    'hs_mbconv_se_workgroups': ([i32, i32, i32, i32, i32, i32], C.c_int64),
+    'hs_stem_conv_fwd': ([vp, i32, i32, i32, i32, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp], STATUS),
+    'hs_mbconv_tiles': ([i32, i32, i32, i32], C.c_int),
+    'hs_stem_dw_fwd': ([vp, i32, i32, i32, vp, i32, vp, vp, i32, i32, i32, i32, vp, i32, i32, i32, vp, vp, vp, vp, vp], STATUS),
+    'hs_image_ingest_fwd': ([vp, i32, i32, i32, i32, i32, vp, vp, vp], STATUS),
+    'hs_stem_dw_u8_fwd': ([vp, i32, vp, i32, i32, i32, vp, i32, vp, vp, i32, i32, i32, i32, vp, i32, i32, i32, vp, vp, vp, vp, vp], STATUS),
+    'hs_overlay_fwd': ([vp, vp, i32, i32, i32, i32, vp, i32, i32, vp, vp], STATUS),
+    'hs_upsample_overlay_fwd': ([vp, i32, i32, i32, i32, i32, i32, vp, i32, vp, i32, i32, vp, vp, vp], STATUS),
+    'hs_frame_resize_fwd': ([vp, i32, i32, i32, i32, vp, vp, i32, i32, vp, vp, i32, i32, i32, i32, i32, i32, i32, C.c_uint32, vp, vp, vp], STATUS),
+    'hs_label_resize_fwd': ([vp, i32, i32, i32, i32, vp, i32, vp, i32, i32, i32, i32, i32, i32, i32, vp, i32, vp], STATUS),
+    'hs_resize_tables_fwd': ([vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp], STATUS),
+    'hs_frame_resize_batch_fwd': ([vp, i32, i32, i32, i32, vp, vp, vp, vp, i32, i32, i32, C.c_uint32, vp, vp, vp], STATUS),
+    'hs_label_resize_batch_fwd': ([vp, i32, i32, i32, i32, vp, vp, vp, i32, i32, i32, vp, i32, vp], STATUS),
+    'hs_color_jitter_fwd': ([vp, i32, i32, i32, i32, vp, vp, vp, vp, vp], STATUS),
+    'hs_frame_rotate_fwd': ([vp, i32, i32, i32, i32, vp, i32, i32, C.c_uint32, C.c_uint32, vp, vp, vp], STATUS),
+    'hs_label_rotate_fwd': ([vp, i32, i32, i32, i32, vp, i32, i32, i32, i32, vp, i32, vp], STATUS),
+    'hs_resize_tables_ragged_fwd': ([vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp], STATUS),
+    'hs_color_jitter_ragged_fwd': ([vp, i32, i32, i32, i32, vp, vp, vp, vp, vp], STATUS),
+    'hs_frame_resize_ragged_fwd': ([vp, i32, i32, i32, i32, vp, vp, vp, vp, i32, i32, i32, vp, vp], STATUS),
+    'hs_label_resize_ragged_fwd': ([vp, i32, i32, i32, i32, vp, vp, vp, i32, i32, vp, vp], STATUS),
+    'hs_frame_rotate_ragged_fwd': ([vp, i32, i32, i32, i32, vp, vp, vp, i32, i32, C.c_uint32, C.c_uint32, vp, vp, vp], STATUS),
+    'hs_label_rotate_ragged_fwd': ([vp, i32, i32, i32, vp, vp, vp, i32, i32, i32, i32, vp, i32, vp], STATUS),
+    'hs_mbconv_expand_dw_fwd': ([vp, i32, i32, i32, i32, vp, i32, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp], STATUS),
+    'hs_se_gate_fwd': ([vp, i32, i32, i32, C.c_float, vp, vp, i32, vp, vp, vp, vp, vp, i32, vp, vp, vp], STATUS),
+    'hs_gemm_split_kp': ([i32], C.c_int),
+    'hs_gemm_split_fwd': ([vp, vp, vp, vp, vp, i32, vp, vp, i32, i32, i32, i32, i32, vp], STATUS),
+    'hs_gemm_split_conv2x2_fwd': ([vp, vp, vp, vp, i32, vp, vp, i32, i32, i32, i32, i32, i32, vp], STATUS),
+    'hs_gemm_split_up2_fwd': ([vp, vp, vp, vp, i32, vp, i32, i32, i32, i32, i32, i32, vp], STATUS),
+    'hs_pooled_shift_fwd': ([vp, i32, C.c_float, vp, vp, vp, i32, i32, vp], STATUS),
+}
+EXPORTS = list(SIGNATURES)
 
 
 def check(status, what):
@@ -234,6 +216,43 @@ def check(status, what):
     if status < 0:
         raise HipLibraryError(f'{what}: {_STATUS.get(status, status)}')
     raise HipLibraryError(f'{what}: HIP launch failed with hipError_t {status}')
+
+
+def _raise_unless_ok(status, fn, args):
+    """ctypes ``errcheck`` of the checked entries: runs inside the foreign call's return, where ``check`` ran on the line after it."""
+    if status:
+        check(status, fn.__name__)
+    return status
+
+
+def _load():
+    """(lib, run): the raw CDLL -- every entry returns what the C function returns -- and, for the STATUS entries, a namespace of
+    SEPARATE function objects (``lib[name]`` makes a fresh one per lookup) that raise HipLibraryError('<entry>: <reason>') for a
+    non-zero status and return it otherwise."""
+    if not os.path.exists(_LIB_PATH):
+        raise HipLibraryError(
+            f'{_LIB_PATH} is missing: build it with `python -m hyperseg_amd.build` (hipcc, gfx950). '
+            'hyperseg_amd has no fallback path.')
+    lib = C.CDLL(_LIB_PATH)
+    run = types.SimpleNamespace()
+    for name, (argtypes, returns) in SIGNATURES.items():
+        fn = getattr(lib, name)          # AttributeError here = the .so does not match the header
+        fn.argtypes, fn.restype = argtypes, C.c_int if returns is STATUS else returns
+        if returns is STATUS:
+            checked = lib[name]
+            checked.argtypes, checked.restype, checked.errcheck = argtypes, C.c_int, _raise_unless_ok
+            setattr(run, name, checked)
+    if lib.hs_version() != 1:
+        raise HipLibraryError(f'ABI mismatch: library reports version {lib.hs_version()}, binding expects 1')
+    return lib, run
+
+
+lib, run = _load()
+
+
+def ptr(t):
+    """``t.data_ptr()``, or None (a NULL operand) for None."""
+    return None if t is None else t.data_ptr()
 
 
 def dev_ptr(t, name='tensor', dtype=torch.float32):

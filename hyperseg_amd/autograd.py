@@ -53,15 +53,14 @@ def _plain_conv(kind, dtype, a, b, ld, shape, meta, out):
     """One of the storage-typed training kernels (hs_patch_conv_plain_*): fp32, or bf16 storage + fp32 accumulation."""
     (fh, fw), c_out, k, pad, mode, groups = meta
     bsz, c_in, h, w = shape
-    fn = getattr(_hip.lib, 'hs_patch_conv_plain_' + kind)
+    fn = getattr(_hip.run, 'hs_patch_conv_plain_' + kind)
     code = DTYPE_CODES[dtype]
     if kind == 'bwd_w':
-        st = fn(code, _hip.dev_ptr(a, 'x', dtype), _hip.dev_ptr(b, 'dy', dtype), bsz, c_in, h, w, fh, fw, c_out, k, pad,
-                HF.PAD_MODES[mode], groups, out.data_ptr(), ld, _hip.stream_ptr())
+        fn(code, _hip.dev_ptr(a, 'x', dtype), _hip.dev_ptr(b, 'dy', dtype), bsz, c_in, h, w, fh, fw, c_out, k, pad,
+           HF.PAD_MODES[mode], groups, out.data_ptr(), ld, _hip.stream_ptr())
     else:
-        st = fn(code, _hip.dev_ptr(a, 'x' if kind == 'fwd' else 'dy', dtype), b.data_ptr(), ld, bsz, c_in, h, w, fh, fw,
-                c_out, k, pad, HF.PAD_MODES[mode], groups, out.data_ptr(), _hip.stream_ptr())
-    _hip.check(st, 'hs_patch_conv_plain_' + kind)
+        fn(code, _hip.dev_ptr(a, 'x' if kind == 'fwd' else 'dy', dtype), b.data_ptr(), ld, bsz, c_in, h, w, fh, fw,
+           c_out, k, pad, HF.PAD_MODES[mode], groups, out.data_ptr(), _hip.stream_ptr())
     return out
 
 
@@ -160,9 +159,8 @@ class PatchConv(torch.autograd.Function):
             if ctx.needs_input_grad[0]:
                 dx = torch.empty_like(x)
                 if x.dtype == torch.float32:
-                    st = _hip.lib.hs_patch_conv_bwd_input(_hip.dev_ptr(dy, 'dy'), bank_ptr, ld, b, c_in, h, w, fh, fw, c_out,
-                                                          k, pad, HF.PAD_MODES[mode], groups, dx.data_ptr(), stream)
-                    _hip.check(st, 'hs_patch_conv_bwd_input')
+                    _hip.run.hs_patch_conv_bwd_input(_hip.dev_ptr(dy, 'dy'), bank_ptr, ld, b, c_in, h, w, fh, fw, c_out,
+                                                     k, pad, HF.PAD_MODES[mode], groups, dx.data_ptr(), stream)
                 else:
                     _plain_conv('bwd_in', x.dtype, dy, bank, ld, x.shape, ctx.meta, dx)
             if ctx.needs_input_grad[1]:
@@ -171,10 +169,9 @@ class PatchConv(torch.autograd.Function):
                 full = _dbank_for(ctx.grad_slot, bank, rows, x.device)
                 assert rows <= full.shape[1]
                 if x.dtype == torch.float32:
-                    st = _hip.lib.hs_patch_conv_bwd_weight(_hip.dev_ptr(x, 'x'), _hip.dev_ptr(dy, 'dy'), b, c_in, h, w, fh, fw,
-                                                           c_out, k, pad, HF.PAD_MODES[mode], groups, full.data_ptr(),
-                                                           full.stride(0), stream)
-                    _hip.check(st, 'hs_patch_conv_bwd_weight')
+                    _hip.run.hs_patch_conv_bwd_weight(_hip.dev_ptr(x, 'x'), _hip.dev_ptr(dy, 'dy'), b, c_in, h, w, fh, fw,
+                                                      c_out, k, pad, HF.PAD_MODES[mode], groups, full.data_ptr(),
+                                                      full.stride(0), stream)
                 else:
                     _plain_conv('bwd_w', x.dtype, x, dy, full.stride(0), x.shape, ctx.meta, full)
                 dbank = full
@@ -183,8 +180,7 @@ class PatchConv(torch.autograd.Function):
 
 def _tile_call(name, dtype, src, b, c, h, w, grid, dst, layout=None):
     args = (DTYPE_CODES[dtype], src.data_ptr(), b, c, h, w, grid[0], grid[1], dst.data_ptr())
-    st = getattr(_hip.lib, name)(*args, _hip.stream_ptr()) if layout is None else getattr(_hip.lib, name)(*args, int(layout), _hip.stream_ptr())
-    _hip.check(st, name)
+    getattr(_hip.run, name)(*args, *(() if layout is None else (int(layout),)), _hip.stream_ptr())
     return dst
 
 
@@ -239,9 +235,8 @@ def _dw_tiles_input_gradient(t, dy, bank, shape, grid, patch_major):
     """hs_dw_tiles_bwd_in: the valid depthwise adjoint, a halo-tile image like ``t`` (same layout and storage type)."""
     b, c, h, w = shape
     dt = torch.empty_like(t)
-    st = _hip.lib.hs_dw_tiles_bwd_in(DTYPE_CODES[t.dtype], dy.data_ptr(), bank.data_ptr(), bank.stride(0), b, c, h, w, grid[0], grid[1],
-                                     dt.data_ptr(), int(patch_major), _hip.stream_ptr())
-    _hip.check(st, 'hs_dw_tiles_bwd_in')
+    _hip.run.hs_dw_tiles_bwd_in(DTYPE_CODES[t.dtype], dy.data_ptr(), bank.data_ptr(), bank.stride(0), b, c, h, w, grid[0], grid[1],
+                                dt.data_ptr(), int(patch_major), _hip.stream_ptr())
     return dt
 
 
@@ -264,9 +259,8 @@ class DwTilesValid(torch.autograd.Function):
         ctx.meta = (b, c, h, w, tuple(grid), t.dtype, bool(patch_major))
         with _hip.device_scope(t.device):
             y = torch.empty(b, c, h, w, device=t.device, dtype=t.dtype)
-            st = _hip.lib.hs_dw_tiles_fwd(DTYPE_CODES[t.dtype], t.data_ptr(), bank.data_ptr(), bank.stride(0), b, c, h, w, grid[0], grid[1],
-                                          y.data_ptr(), int(patch_major), _hip.stream_ptr())
-            _hip.check(st, 'hs_dw_tiles_fwd')
+            _hip.run.hs_dw_tiles_fwd(DTYPE_CODES[t.dtype], t.data_ptr(), bank.data_ptr(), bank.stride(0), b, c, h, w, grid[0], grid[1],
+                                     y.data_ptr(), int(patch_major), _hip.stream_ptr())
         ctx.save_for_backward(t, bank)
         return y
 
@@ -281,9 +275,8 @@ class DwTilesValid(torch.autograd.Function):
                 dt = _dw_tiles_input_gradient(t, dy, bank, (b, c, h, w), grid, pm)
             if ctx.needs_input_grad[1]:
                 dbank = _dbank_for(ctx.grad_slot, bank, 9 * c, dy.device)
-                st = _hip.lib.hs_dw_tiles_bwd_w(DTYPE_CODES[dtype], t.data_ptr(), dy.data_ptr(), b, c, h, w, grid[0], grid[1], dbank.data_ptr(),
-                                                dbank.stride(0), int(pm), _hip.stream_ptr())
-                _hip.check(st, 'hs_dw_tiles_bwd_w')
+                _hip.run.hs_dw_tiles_bwd_w(DTYPE_CODES[dtype], t.data_ptr(), dy.data_ptr(), b, c, h, w, grid[0], grid[1], dbank.data_ptr(),
+                                           dbank.stride(0), int(pm), _hip.stream_ptr())
         return dt, dbank, None, None, None
 
 
@@ -300,6 +293,45 @@ def tiles_supported(x):
     return x.is_cuda and x.dtype in DTYPE_CODES and x.shape[0] * x.shape[1] <= 65535 and x.shape[2] >= 2 and x.shape[3] >= 2
 
 
+def _bn_workspace(c, dev):
+    """Scratch of the training BatchNorm launches over ``c`` channels (hs_bn_train_workspace)."""
+    return torch.empty(int(_hip.lib.hs_bn_train_workspace(c)), device=dev, dtype=torch.uint8)
+
+
+def _bn_operands(weight, bias, running_mean, running_var, momentum, eps, act, mean, invstd):
+    """The BatchNorm run of the training forwards' argument lists (hs_bn_act_train_fwd, hs_dw_tiles_bn_fwd, hs_patch_conv_bn_fwd): the
+    parameters and running estimates (NULL where None), the scalars, the two saved statistics."""
+    return (_hip.ptr(weight), _hip.ptr(bias), _hip.ptr(running_mean), _hip.ptr(running_var), float(momentum), float(eps), int(act),
+            mean.data_ptr(), invstd.data_ptr())
+
+
+def _bn_adjoint(x, dy, rows, px, weight, bias, mean, invstd, eps, act, stream):
+    """BatchNorm + activation's adjoint (hs_bn_act_train_bwd) over ``x`` read as (rows, C, px), from the saved statistics: (dx, dg, db),
+    dg / db None where the parameter is.  Inside the caller's device scope."""
+    c, dev = x.shape[1], x.device
+    dx = torch.empty_like(x)
+    dg = torch.empty(c, device=dev, dtype=torch.float32) if weight is not None else None
+    db = torch.empty(c, device=dev, dtype=torch.float32) if bias is not None else None
+    ws = _bn_workspace(c, dev)
+    _hip.run.hs_bn_act_train_bwd(DTYPE_CODES[x.dtype], x.data_ptr(), dy.data_ptr(), rows, c, px, _hip.ptr(weight), _hip.ptr(bias),
+                                 mean.data_ptr(), invstd.data_ptr(), eps, act, ws.data_ptr(), dx.data_ptr(), _hip.ptr(dg), _hip.ptr(db), stream)
+    return dx, dg, db
+
+
+def _bn_step(function, bn, x, act, *rest):
+    """``function.apply(x, <bn's parameters, estimates and scalars>, act, <step counter>, *rest)`` for the three Functions that run a training
+    BatchNorm, and what is owed after one: the kernel increments the step counter itself where it can (an int64 word on x's device: one
+    launch less per BatchNorm and step), this does otherwise; the running statistics changed through a raw pointer -- no tensor version
+    moved -- so the weights' epoch is bumped."""
+    nbt = bn.num_batches_tracked
+    in_kernel = nbt is not None and nbt.device == x.device and nbt.dtype == torch.int64
+    y = function.apply(x, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.momentum, bn.eps, act, nbt if in_kernel else None, *rest)
+    if nbt is not None and not in_kernel:
+        nbt.add_(1)
+    HF.bump_weights_epoch()
+    return y
+
+
 class BNActTrain(torch.autograd.Function):
     """BatchNorm2d (training mode, batch statistics, running estimates updated in place) + none / ReLU / ReLU6 in two launches per
     direction (hs_bn_act_train_fwd / _bwd).  fp32 parameters; x in fp32, bf16 or fp16 storage."""
@@ -314,15 +346,10 @@ class BNActTrain(torch.autograd.Function):
         with _hip.device_scope(dev):
             y = torch.empty_like(x)
             mean, invstd = torch.empty(c, device=dev, dtype=torch.float32), torch.empty(c, device=dev, dtype=torch.float32)
-            ws = torch.empty(int(_hip.lib.hs_bn_train_workspace(c)), device=dev, dtype=torch.uint8)
-            st = _hip.lib.hs_bn_act_train_fwd(DTYPE_CODES[x.dtype], x.data_ptr(), b, c, px,
-                                              weight.data_ptr() if weight is not None else None,
-                                              bias.data_ptr() if bias is not None else None,
-                                              running_mean.data_ptr() if running_mean is not None else None,
-                                              running_var.data_ptr() if running_var is not None else None,
-                                              float(momentum), float(eps), int(act), mean.data_ptr(), invstd.data_ptr(), ws.data_ptr(),
-                                              y.data_ptr(), counter.data_ptr() if counter is not None else None, _hip.stream_ptr())
-            _hip.check(st, 'hs_bn_act_train_fwd')
+            ws = _bn_workspace(c, dev)
+            _hip.run.hs_bn_act_train_fwd(DTYPE_CODES[x.dtype], x.data_ptr(), b, c, px,
+                                         *_bn_operands(weight, bias, running_mean, running_var, momentum, eps, act, mean, invstd),
+                                         ws.data_ptr(), y.data_ptr(), _hip.ptr(counter), _hip.stream_ptr())
         ctx.save_for_backward(x, weight, bias, mean, invstd)
         ctx.meta = (b, c, px, float(eps), int(act))
         return y
@@ -332,18 +359,8 @@ class BNActTrain(torch.autograd.Function):
         x, weight, bias, mean, invstd = ctx.saved_tensors
         b, c, px, eps, act = ctx.meta
         dy = dy.contiguous().to(x.dtype)
-        dev = x.device
-        with _hip.device_scope(dev):
-            dx = torch.empty_like(x)
-            dg = torch.empty(c, device=dev, dtype=torch.float32) if weight is not None else None
-            db = torch.empty(c, device=dev, dtype=torch.float32) if bias is not None else None
-            ws = torch.empty(int(_hip.lib.hs_bn_train_workspace(c)), device=dev, dtype=torch.uint8)
-            st = _hip.lib.hs_bn_act_train_bwd(DTYPE_CODES[x.dtype], x.data_ptr(), dy.data_ptr(), b, c, px,
-                                              weight.data_ptr() if weight is not None else None,
-                                              bias.data_ptr() if bias is not None else None, mean.data_ptr(), invstd.data_ptr(), eps, act,
-                                              ws.data_ptr(), dx.data_ptr(), dg.data_ptr() if dg is not None else None,
-                                              db.data_ptr() if db is not None else None, _hip.stream_ptr())
-            _hip.check(st, 'hs_bn_act_train_bwd')
+        with _hip.device_scope(x.device):
+            dx, dg, db = _bn_adjoint(x, dy, b, px, weight, bias, mean, invstd, eps, act, _hip.stream_ptr())
         return dx, dg, db, None, None, None, None, None, None
 
 
@@ -367,14 +384,7 @@ def bn_act(bn, act_layer, x):
     parameters on the GPU and the activation is None / ReLU / ReLU6; the stock modules otherwise (eval mode, other layers, CPU)."""
     act = _bn_hip_act(bn, act_layer, x)
     if act >= 0:
-        nbt = bn.num_batches_tracked
-        in_kernel = nbt is not None and nbt.device == x.device and nbt.dtype == torch.int64
-        # the step counter is incremented by the kernel itself (one launch less per BatchNorm and step)
-        y = BNActTrain.apply(x, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.momentum, bn.eps, act, nbt if in_kernel else None)
-        if nbt is not None and not in_kernel:
-            nbt.add_(1)
-        HF.bump_weights_epoch()               # running statistics changed through a raw pointer: no tensor version moved
-        return y
+        return _bn_step(BNActTrain, bn, x, act)
     if bn.training:
         HF.bump_weights_epoch()               # stock BN's running-statistics update does not bump their versions either
     y = bn(x)
@@ -405,15 +415,12 @@ class DwTilesBN(torch.autograd.Function):
         with _hip.device_scope(dev):
             y = torch.empty(b, c, h, w, device=dev, dtype=t.dtype)
             mean, invstd = torch.empty(c, device=dev, dtype=torch.float32), torch.empty(c, device=dev, dtype=torch.float32)
-            ws = torch.empty(int(_hip.lib.hs_bn_train_workspace(c)), device=dev, dtype=torch.uint8)
+            ws = _bn_workspace(c, dev)
             code = DTYPE_CODES[t.dtype]
-            _hip.check(_hip.lib.hs_bn_train_stats_fwd(code, t.data_ptr(), t.shape[0], c, px, ws.data_ptr(), _hip.stream_ptr()), 'hs_bn_train_stats_fwd')
-            st = _hip.lib.hs_dw_tiles_bn_fwd(code, t.data_ptr(), ws.data_ptr(), weight.data_ptr(), bias.data_ptr(),
-                                             running_mean.data_ptr() if running_mean is not None else None,
-                                             running_var.data_ptr() if running_var is not None else None, float(momentum), float(eps), int(act),
-                                             mean.data_ptr(), invstd.data_ptr(), counter.data_ptr() if counter is not None else None,
-                                             bank.data_ptr(), bank.stride(0), b, c, h, w, fh, fw, y.data_ptr(), int(patch_major), _hip.stream_ptr())
-            _hip.check(st, 'hs_dw_tiles_bn_fwd')
+            _hip.run.hs_bn_train_stats_fwd(code, t.data_ptr(), t.shape[0], c, px, ws.data_ptr(), _hip.stream_ptr())
+            _hip.run.hs_dw_tiles_bn_fwd(code, t.data_ptr(), ws.data_ptr(),
+                                        *_bn_operands(weight, bias, running_mean, running_var, momentum, eps, act, mean, invstd), _hip.ptr(counter),
+                                        bank.data_ptr(), bank.stride(0), b, c, h, w, fh, fw, y.data_ptr(), int(patch_major), _hip.stream_ptr())
         ctx.save_for_backward(t, weight, bias, mean, invstd, bank)
         ctx.meta = (b, c, h, w, (fh, fw), float(eps), int(act), bool(patch_major), px)
         return y
@@ -430,31 +437,25 @@ class DwTilesBN(torch.autograd.Function):
             stream = _hip.stream_ptr()
             if ctx.needs_input_grad[9]:
                 dbank = _dbank_for(ctx.grad_slot, bank, 9 * c, dev)
-                st = _hip.lib.hs_dw_tiles_bn_bwd_w(code, t.data_ptr(), dy.data_ptr(), weight.data_ptr(), bias.data_ptr(), mean.data_ptr(), invstd.data_ptr(),
-                                                   act, b, c, h, w, fh, fw, dbank.data_ptr(), dbank.stride(0), int(pm), stream)
-                _hip.check(st, 'hs_dw_tiles_bn_bwd_w')
-            if ctx.needs_input_grad[0] or ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
+                _hip.run.hs_dw_tiles_bn_bwd_w(code, t.data_ptr(), dy.data_ptr(), weight.data_ptr(), bias.data_ptr(), mean.data_ptr(), invstd.data_ptr(),
+                                              act, b, c, h, w, fh, fw, dbank.data_ptr(), dbank.stride(0), int(pm), stream)
+            need_t = ctx.needs_input_grad[0] or ctx.needs_input_grad[1] or ctx.needs_input_grad[2]
+            if need_t and USE_DW_BN_BWD_FUSED:
+                # round 6: the depthwise adjoint leaves BatchNorm1's two sums as one pair per workgroup; no statistics launch
                 dt = torch.empty_like(t)
                 dg = torch.empty(c, device=dev, dtype=torch.float32)
                 db = torch.empty(c, device=dev, dtype=torch.float32)
-                if USE_DW_BN_BWD_FUSED:
-                    # round 6: the depthwise adjoint leaves BatchNorm1's two sums as one pair per workgroup; no statistics launch
-                    npart = int(_hip.lib.hs_dw_tiles_bn_bwd_in_partials(b, h, w, fh, fw))
-                    da = torch.empty_like(t)
-                    part = torch.empty(c * npart * 2, device=dev, dtype=torch.float32)
-                    st = _hip.lib.hs_dw_tiles_bn_bwd_in(code, dy.data_ptr(), bank.data_ptr(), bank.stride(0), t.data_ptr(), weight.data_ptr(), bias.data_ptr(),
-                                                        mean.data_ptr(), invstd.data_ptr(), act, b, c, h, w, fh, fw, da.data_ptr(), part.data_ptr(), int(pm), stream)
-                    _hip.check(st, 'hs_dw_tiles_bn_bwd_in')
-                    st = _hip.lib.hs_bn_act_train_bwd_apply(code, t.data_ptr(), da.data_ptr(), t.shape[0], c, px, weight.data_ptr(), bias.data_ptr(),
-                                                            mean.data_ptr(), invstd.data_ptr(), act, part.data_ptr(), npart, dt.data_ptr(), dg.data_ptr(),
-                                                            db.data_ptr(), stream)
-                    _hip.check(st, 'hs_bn_act_train_bwd_apply')
-                else:
-                    da = _dw_tiles_input_gradient(t, dy, bank, (b, c, h, w), (fh, fw), pm)   # gradient of the (never materialised) normalised tiles, stored in t's type
-                    ws = torch.empty(int(_hip.lib.hs_bn_train_workspace(c)), device=dev, dtype=torch.uint8)
-                    st = _hip.lib.hs_bn_act_train_bwd(code, t.data_ptr(), da.data_ptr(), t.shape[0], c, px, weight.data_ptr(), bias.data_ptr(),
-                                                      mean.data_ptr(), invstd.data_ptr(), eps, act, ws.data_ptr(), dt.data_ptr(), dg.data_ptr(), db.data_ptr(), stream)
-                    _hip.check(st, 'hs_bn_act_train_bwd')
+                npart = int(_hip.lib.hs_dw_tiles_bn_bwd_in_partials(b, h, w, fh, fw))
+                da = torch.empty_like(t)
+                part = torch.empty(c * npart * 2, device=dev, dtype=torch.float32)
+                _hip.run.hs_dw_tiles_bn_bwd_in(code, dy.data_ptr(), bank.data_ptr(), bank.stride(0), t.data_ptr(), weight.data_ptr(), bias.data_ptr(),
+                                               mean.data_ptr(), invstd.data_ptr(), act, b, c, h, w, fh, fw, da.data_ptr(), part.data_ptr(), int(pm), stream)
+                _hip.run.hs_bn_act_train_bwd_apply(code, t.data_ptr(), da.data_ptr(), t.shape[0], c, px, weight.data_ptr(), bias.data_ptr(),
+                                                   mean.data_ptr(), invstd.data_ptr(), act, part.data_ptr(), npart, dt.data_ptr(), dg.data_ptr(),
+                                                   db.data_ptr(), stream)
+            elif need_t:
+                da = _dw_tiles_input_gradient(t, dy, bank, (b, c, h, w), (fh, fw), pm)   # gradient of the (never materialised) normalised tiles, stored in t's type
+                dt, dg, db = _bn_adjoint(t, da, t.shape[0], px, weight, bias, mean, invstd, eps, act, stream)
         return dt, dg, db, None, None, None, None, None, None, dbank, None, None, None
 
 
@@ -464,14 +465,7 @@ def dw_tiles_bn(bn, act_layer, t, bank, size, grid, patch_major):
     act = _bn_hip_act(bn, act_layer, t) if USE_DW_BN_FUSED and getattr(bn, 'weight', None) is not None else -1      # nn.Identity / 'Unit' norms: no weight -> the two Functions
     if act < 0:
         return DwTilesValid.apply(bn_act(bn, act_layer, t), bank, size, grid, patch_major)
-    nbt = bn.num_batches_tracked
-    in_kernel = nbt is not None and nbt.device == t.device and nbt.dtype == torch.int64
-    y = DwTilesBN.apply(t, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.momentum, bn.eps, act, nbt if in_kernel else None,
-                        bank, tuple(size), tuple(grid), bool(patch_major))
-    if nbt is not None and not in_kernel:
-        nbt.add_(1)
-    HF.bump_weights_epoch()
-    return y
+    return _bn_step(DwTilesBN, bn, t, act, bank, tuple(size), tuple(grid), bool(patch_major))
 
 
 USE_DW_BN_FUSED = True  # tests switch it off to compare with BNActTrain + DwTilesValid
@@ -501,15 +495,12 @@ class PatchConvBN(torch.autograd.Function):
         with _hip.device_scope(dev):
             y = torch.empty(b, c_out, h, w, device=dev, dtype=x.dtype)
             mean, invstd = torch.empty(c, device=dev, dtype=torch.float32), torch.empty(c, device=dev, dtype=torch.float32)
-            ws = torch.empty(int(_hip.lib.hs_bn_train_workspace(c)), device=dev, dtype=torch.uint8)
+            ws = _bn_workspace(c, dev)
             code = DTYPE_CODES[x.dtype]
-            _hip.check(_hip.lib.hs_bn_train_stats_fwd(code, x.data_ptr(), b, c, h * w, ws.data_ptr(), _hip.stream_ptr()), 'hs_bn_train_stats_fwd')
-            st = _hip.lib.hs_patch_conv_bn_fwd(code, x.data_ptr(), ws.data_ptr(), weight.data_ptr(), bias.data_ptr(),
-                                               running_mean.data_ptr() if running_mean is not None else None,
-                                               running_var.data_ptr() if running_var is not None else None, float(momentum), float(eps), int(act),
-                                               mean.data_ptr(), invstd.data_ptr(), counter.data_ptr() if counter is not None else None,
-                                               bank.data_ptr(), bank.stride(0), b, c, h, w, fh, fw, int(c_out), y.data_ptr(), _hip.stream_ptr())
-            _hip.check(st, 'hs_patch_conv_bn_fwd')
+            _hip.run.hs_bn_train_stats_fwd(code, x.data_ptr(), b, c, h * w, ws.data_ptr(), _hip.stream_ptr())
+            _hip.run.hs_patch_conv_bn_fwd(code, x.data_ptr(), ws.data_ptr(),
+                                          *_bn_operands(weight, bias, running_mean, running_var, momentum, eps, act, mean, invstd), _hip.ptr(counter),
+                                          bank.data_ptr(), bank.stride(0), b, c, h, w, fh, fw, int(c_out), y.data_ptr(), _hip.stream_ptr())
         ctx.save_for_backward(x, weight, bias, mean, invstd, bank)
         ctx.meta = (b, c, h, w, (fh, fw), float(eps), int(act), int(c_out))
         return y
@@ -526,18 +517,11 @@ class PatchConvBN(torch.autograd.Function):
             stream = _hip.stream_ptr()
             if ctx.needs_input_grad[9]:
                 dbank = _dbank_for(ctx.grad_slot, bank, c_out * c, dev)
-                st = _hip.lib.hs_patch_conv_bn_bwd_w(code, x.data_ptr(), dy.data_ptr(), weight.data_ptr(), bias.data_ptr(), mean.data_ptr(), invstd.data_ptr(),
-                                                     act, b, c, h, w, fh, fw, c_out, dbank.data_ptr(), dbank.stride(0), stream)
-                _hip.check(st, 'hs_patch_conv_bn_bwd_w')
+                _hip.run.hs_patch_conv_bn_bwd_w(code, x.data_ptr(), dy.data_ptr(), weight.data_ptr(), bias.data_ptr(), mean.data_ptr(), invstd.data_ptr(),
+                                                act, b, c, h, w, fh, fw, c_out, dbank.data_ptr(), dbank.stride(0), stream)
             if ctx.needs_input_grad[0] or ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
                 da = _conv_input_gradient(x, dy, bank, (fh, fw), c_out)              # gradient of the (never materialised) normalised map, in x's type
-                dx = torch.empty_like(x)
-                dg = torch.empty(c, device=dev, dtype=torch.float32)
-                db = torch.empty(c, device=dev, dtype=torch.float32)
-                ws = torch.empty(int(_hip.lib.hs_bn_train_workspace(c)), device=dev, dtype=torch.uint8)
-                st = _hip.lib.hs_bn_act_train_bwd(code, x.data_ptr(), da.data_ptr(), b, c, h * w, weight.data_ptr(), bias.data_ptr(),
-                                                  mean.data_ptr(), invstd.data_ptr(), eps, act, ws.data_ptr(), dx.data_ptr(), dg.data_ptr(), db.data_ptr(), stream)
-                _hip.check(st, 'hs_bn_act_train_bwd')
+                dx, dg, db = _bn_adjoint(x, da, b, h * w, weight, bias, mean, invstd, eps, act, stream)
         return dx, dg, db, None, None, None, None, None, None, dbank, None, None
 
 
@@ -557,14 +541,7 @@ def patch_conv_bn(bn, act_layer, x, bank, grid, c_out):
         and (not torch.is_autocast_enabled('cuda') or torch.get_autocast_dtype('cuda') in HALF_DTYPES)
     if not covered:
         return patch_conv_apply(bn_act(bn, act_layer, x), bank, grid, c_out, 1, 0, 'zeros', 1)
-    nbt = bn.num_batches_tracked
-    in_kernel = nbt is not None and nbt.device == x.device and nbt.dtype == torch.int64
-    y = PatchConvBN.apply(x, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.momentum, bn.eps, act, nbt if in_kernel else None,
-                          bank, tuple(grid), int(c_out))
-    if nbt is not None and not in_kernel:
-        nbt.add_(1)
-    HF.bump_weights_epoch()
-    return y
+    return _bn_step(PatchConvBN, bn, x, act, bank, tuple(grid), int(c_out))
 
 
 USE_CONV_BN_FUSED = True  # tests switch it off to compare with BNActTrain + PatchConv
@@ -589,10 +566,10 @@ class S2WBanksTrain(torch.autograd.Function):
             a.signal_index, a.signal_channels, a.groups = m['signal_index'], m['signal_channels'], m['groups']
             a.w, a.wc, a.rows = w.data_ptr(), w.shape[0], m['rows']
             a.ld = m['ld']
-            a.bank = banks[i].data_ptr() if banks is not None else None
-            a.dbank = dbanks[i].data_ptr() if dbanks is not None and dbanks[i] is not None else None
-            a.dw = dws[i].data_ptr() if dws is not None and dws[i] is not None else None
-            a.ds = dss[i].data_ptr() if dss is not None and dss[i] is not None else None
+            a.bank = _hip.ptr(banks[i]) if banks is not None else None
+            a.dbank = _hip.ptr(dbanks[i]) if dbanks is not None else None
+            a.dw = _hip.ptr(dws[i]) if dws is not None else None
+            a.ds = _hip.ptr(dss[i]) if dss is not None else None
         return arr
 
     @staticmethod
@@ -609,8 +586,7 @@ class S2WBanksTrain(torch.autograd.Function):
                 banks.append(buf[off:off + p * m['ld']].view(p, m['ld']))
                 off += p * m['ld']
             arr = S2WBanksTrain._table(meta, signal, weights, banks=banks)
-            st = _hip.lib.hs_s2w_train_fwd(signal.data_ptr(), b, c, fh, fw, arr, len(meta), _hip.stream_ptr())
-            _hip.check(st, 'hs_s2w_train_fwd')
+            _hip.run.hs_s2w_train_fwd(signal.data_ptr(), b, c, fh, fw, arr, len(meta), _hip.stream_ptr())
         ctx.save_for_backward(signal, *weights)
         ctx.meta = meta
         return tuple(banks)
@@ -635,13 +611,36 @@ class S2WBanksTrain(torch.autograd.Function):
             arr = S2WBanksTrain._table(meta, signal, weights, dbanks=dbs, dws=dws, dss=dss)
             nws = int(_hip.lib.hs_s2w_train_workspace(b, fh, fw, arr, len(meta))) if any(need_w) else 0
             ws = torch.empty(nws, device=signal.device, dtype=torch.uint8) if nws else None
-            st = _hip.lib.hs_s2w_train_bwd(signal.data_ptr(), b, c, fh, fw, arr, len(meta), dsig.data_ptr() if need_s else None,
-                                           ws.data_ptr() if ws is not None else None, nws, _hip.stream_ptr())
-            _hip.check(st, 'hs_s2w_train_bwd')
+            _hip.run.hs_s2w_train_bwd(signal.data_ptr(), b, c, fh, fw, arr, len(meta), _hip.ptr(dsig), _hip.ptr(ws), nws, _hip.stream_ptr())
         return (None, dsig) + tuple(dws)
 
 
 _CHECK_LABELS = os.environ.get('HS_CHECK_LABELS', '0') == '1'
+
+
+def _loss_operands(who, rank_ok, logits, target, ignore_index, weight):
+    """The front of the loss Functions -> (logits, target, weight, n, c, px): the target checks F.cross_entropy makes (the kernels walk
+    N*H*W pixels of BOTH tensors), in each Function's own words; the class-weight table; contiguous operands; and with HS_CHECK_LABELS=1
+    the label range (one host read, debugging)."""
+    if not rank_ok or tuple(target.shape) != (logits.shape[0],) + tuple(logits.shape[2:]):
+        raise ValueError(f'Expected target of shape {(logits.shape[0],) + tuple(logits.shape[2:])} for logits of shape '
+                         f'{tuple(logits.shape)}, got {tuple(target.shape)}')
+    if who == 'PixelCrossEntropy':
+        if target.dtype != torch.int64:
+            raise ValueError(f'{who}: expected int64 class indices, got {target.dtype}')
+        if target.device != logits.device:
+            raise ValueError(f'{who}: target on {target.device}, logits on {logits.device}')
+    elif target.dtype != torch.int64 or target.device != logits.device:
+        raise ValueError(f'{who}: expected int64 class indices on {logits.device}, got {target.dtype} on {target.device}')
+    refuse_mixed_halves(logits)
+    weight = HF.class_weight_table(weight, logits.shape[1], logits.device, f'{who}: weight')
+    logits, target = logits.contiguous(), target.contiguous()
+    n, c = logits.shape[:2]
+    if _CHECK_LABELS and target.numel():
+        bad = (target != int(ignore_index)) & ((target < 0) | (target >= c))
+        if bool(bad.any()):
+            raise IndexError(f'Target {int(target[bad][0])} is out of bounds for {c} classes (ignore_index {int(ignore_index)})')
+    return logits, target, weight, n, c, logits.numel() // (n * c)
 
 
 class PixelCrossEntropy(torch.autograd.Function):
@@ -656,32 +655,11 @@ class PixelCrossEntropy(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, logits, target, ignore_index, weight=None):
-        if logits.dim() < 2 or tuple(target.shape) != (logits.shape[0],) + tuple(logits.shape[2:]):
-            raise ValueError(f'Expected target of shape {(logits.shape[0],) + tuple(logits.shape[2:])} for logits of shape '
-                             f'{tuple(logits.shape)}, got {tuple(target.shape)}')
-        if target.dtype != torch.int64:
-            raise ValueError(f'PixelCrossEntropy: expected int64 class indices, got {target.dtype}')
-        if target.device != logits.device:
-            raise ValueError(f'PixelCrossEntropy: target on {target.device}, logits on {logits.device}')
-        refuse_mixed_halves(logits)
-        weight = HF.class_weight_table(weight, logits.shape[1], logits.device, 'PixelCrossEntropy: weight')
-        logits, target = logits.contiguous(), target.contiguous()
-        n, c = logits.shape[:2]
-        px = logits.numel() // (n * c)
-        if _CHECK_LABELS and target.numel():
-            bad = (target != int(ignore_index)) & ((target < 0) | (target >= c))
-            if bool(bad.any()):
-                raise IndexError(f'Target {int(target[bad][0])} is out of bounds for {c} classes (ignore_index {int(ignore_index)})')
+        logits, target, weight, n, c, px = _loss_operands('PixelCrossEntropy', logits.dim() >= 2, logits, target, ignore_index, weight)
         with _hip.device_scope(logits.device):
             loss = torch.empty(target.shape, device=logits.device, dtype=torch.float32)
-            if weight is None:
-                st = _hip.lib.hs_cross_entropy_typed_fwd(DTYPE_CODES[logits.dtype], logits.data_ptr(), target.data_ptr(), n, c, px, int(ignore_index),
-                                                         loss.data_ptr(), _hip.stream_ptr())
-                _hip.check(st, 'hs_cross_entropy_typed_fwd')
-            else:
-                st = _hip.lib.hs_cross_entropy_weighted_fwd(DTYPE_CODES[logits.dtype], logits.data_ptr(), target.data_ptr(), weight.data_ptr(), n, c,
-                                                            px, int(ignore_index), loss.data_ptr(), _hip.stream_ptr())
-                _hip.check(st, 'hs_cross_entropy_weighted_fwd')
+            HF.loss_launch('hs_cross_entropy_typed_fwd', weight, DTYPE_CODES[logits.dtype], logits.data_ptr(), target.data_ptr(), n, c, px,
+                           int(ignore_index), loss.data_ptr(), _hip.stream_ptr())
         ctx.save_for_backward(*((logits, target) if weight is None else (logits, target, weight)))
         ctx.ignore_index = int(ignore_index)
         return loss
@@ -694,14 +672,8 @@ class PixelCrossEntropy(torch.autograd.Function):
         g = g.contiguous().float()
         with _hip.device_scope(logits.device):
             dl = torch.empty_like(logits)
-            if not weight:
-                st = _hip.lib.hs_cross_entropy_typed_bwd(DTYPE_CODES[logits.dtype], logits.data_ptr(), target.data_ptr(), n, c, px, ctx.ignore_index,
-                                                         g.data_ptr(), dl.data_ptr(), _hip.stream_ptr())
-                _hip.check(st, 'hs_cross_entropy_typed_bwd')
-            else:
-                st = _hip.lib.hs_cross_entropy_weighted_bwd(DTYPE_CODES[logits.dtype], logits.data_ptr(), target.data_ptr(), weight[0].data_ptr(), n, c,
-                                                            px, ctx.ignore_index, g.data_ptr(), dl.data_ptr(), _hip.stream_ptr())
-                _hip.check(st, 'hs_cross_entropy_weighted_bwd')
+            HF.loss_launch('hs_cross_entropy_typed_bwd', weight[0] if weight else None, DTYPE_CODES[logits.dtype], logits.data_ptr(),
+                           target.data_ptr(), n, c, px, ctx.ignore_index, g.data_ptr(), dl.data_ptr(), _hip.stream_ptr())
         return dl, None, None, None
 
 
@@ -716,8 +688,7 @@ class BootstrapMean(torch.autograd.Function):
         with _hip.device_scope(values.device):
             ws = torch.empty(int(_hip.lib.hs_bootstrap_mean_workspace()), device=values.device, dtype=torch.uint8)
             out = torch.empty(8, device=values.device, dtype=torch.float32)
-            st = _hip.lib.hs_bootstrap_mean_fwd(values.data_ptr(), n, int(k), float(thresh), ws.data_ptr(), out.data_ptr(), _hip.stream_ptr())
-            _hip.check(st, 'hs_bootstrap_mean_fwd')
+            _hip.run.hs_bootstrap_mean_fwd(values.data_ptr(), n, int(k), float(thresh), ws.data_ptr(), out.data_ptr(), _hip.stream_ptr())
         ctx.save_for_backward(values, out)
         return out[0].clone()
 
@@ -726,9 +697,8 @@ class BootstrapMean(torch.autograd.Function):
         values, state = ctx.saved_tensors
         with _hip.device_scope(values.device):
             gv = torch.empty_like(values)
-            st = _hip.lib.hs_bootstrap_mean_bwd(values.data_ptr(), values.numel(), state.data_ptr(),
-                                                g.contiguous().float().data_ptr(), gv.data_ptr(), _hip.stream_ptr())
-            _hip.check(st, 'hs_bootstrap_mean_bwd')
+            _hip.run.hs_bootstrap_mean_bwd(values.data_ptr(), values.numel(), state.data_ptr(),
+                                           g.contiguous().float().data_ptr(), gv.data_ptr(), _hip.stream_ptr())
         return gv, None, None
 
 
@@ -736,51 +706,23 @@ def _bootstrapped_ce_forward(ctx, logits, target, ignore_index, k, thresh, confu
     """The forward of ``BootstrappedCrossEntropy`` -- and, with ``confusion`` (int64 (n, n), accumulated into), of
     ``BootstrappedCrossEntropyScored``: the same checks, buffers and saved tensors, the two differ in the launches alone.  ``weight``: the
     class-weight table (``PixelCrossEntropy``'s) -- the weighted twin of the loss launch, the same launches after it; saved for backward."""
-    if logits.dim() != 4 or tuple(target.shape) != (logits.shape[0],) + tuple(logits.shape[2:]):
-        raise ValueError(f'Expected target of shape {(logits.shape[0],) + tuple(logits.shape[2:])} for logits of shape '
-                         f'{tuple(logits.shape)}, got {tuple(target.shape)}')
-    if target.dtype != torch.int64 or target.device != logits.device:
-        raise ValueError(f'BootstrappedCrossEntropy: expected int64 class indices on {logits.device}, got {target.dtype} on {target.device}')
-    refuse_mixed_halves(logits)
-    weight = HF.class_weight_table(weight, logits.shape[1], logits.device, 'BootstrappedCrossEntropy: weight')
-    logits, target = logits.contiguous(), target.contiguous()
-    n, c = logits.shape[:2]
-    px = logits.numel() // (n * c)
-    if _CHECK_LABELS and target.numel():
-        bad = (target != int(ignore_index)) & ((target < 0) | (target >= c))
-        if bool(bad.any()):
-            raise IndexError(f'Target {int(target[bad][0])} is out of bounds for {c} classes (ignore_index {int(ignore_index)})')
+    logits, target, weight, n, c, px = _loss_operands('BootstrappedCrossEntropy', logits.dim() == 4, logits, target, ignore_index, weight)
+    operands = (DTYPE_CODES[logits.dtype], logits.data_ptr(), target.data_ptr(), n, c, px, int(ignore_index))
     with _hip.device_scope(logits.device):
         ws = torch.empty(n * int(_hip.lib.hs_bootstrap_mean_workspace()), device=logits.device, dtype=torch.uint8)
         loss = torch.empty(n, px, device=logits.device, dtype=torch.float32)
         out = torch.empty(n * 8 + 1, device=logits.device, dtype=torch.float32)              # (N, 8) state | the mean
-        if confusion is None and weight is None:
-            st = _hip.lib.hs_bootstrapped_ce_fwd(DTYPE_CODES[logits.dtype], logits.data_ptr(), target.data_ptr(), n, c, px, int(ignore_index),
-                                                 int(k), float(thresh), ws.data_ptr(), loss.data_ptr(), out.data_ptr(),
-                                                 out.data_ptr() + 4 * n * 8, _hip.stream_ptr())
-            _hip.check(st, 'hs_bootstrapped_ce_fwd')
-        elif confusion is None:
-            st = _hip.lib.hs_bootstrapped_ce_weighted_fwd(DTYPE_CODES[logits.dtype], logits.data_ptr(), target.data_ptr(), weight.data_ptr(), n, c,
-                                                          px, int(ignore_index), int(k), float(thresh), ws.data_ptr(), loss.data_ptr(),
-                                                          out.data_ptr(), out.data_ptr() + 4 * n * 8, _hip.stream_ptr())
-            _hip.check(st, 'hs_bootstrapped_ce_weighted_fwd')
+        if confusion is None:
+            HF.loss_launch('hs_bootstrapped_ce_fwd', weight, *operands, int(k), float(thresh), ws.data_ptr(), loss.data_ptr(), out.data_ptr(),
+                           out.data_ptr() + 4 * n * 8, _hip.stream_ptr())
         else:                                                    # the same launches, the first one counting as well
             nc = confusion.shape[-1]
             if confusion.dtype != torch.int64 or tuple(confusion.shape) != (nc, nc) or confusion.device != logits.device \
                     or not confusion.is_contiguous():
                 raise ValueError(f'the score matrix must be a contiguous int64 (n, n) tensor on {logits.device}')
-            if weight is None:
-                st = _hip.lib.hs_cross_entropy_score_fwd(DTYPE_CODES[logits.dtype], logits.data_ptr(), target.data_ptr(), n, c, px, int(ignore_index),
-                                                         loss.data_ptr(), nc, 0, confusion.data_ptr(), None, _hip.stream_ptr())
-                _hip.check(st, 'hs_cross_entropy_score_fwd')
-            else:
-                st = _hip.lib.hs_cross_entropy_score_weighted_fwd(DTYPE_CODES[logits.dtype], logits.data_ptr(), target.data_ptr(), weight.data_ptr(),
-                                                                  n, c, px, int(ignore_index), loss.data_ptr(), nc, 0, confusion.data_ptr(), None,
-                                                                  _hip.stream_ptr())
-                _hip.check(st, 'hs_cross_entropy_score_weighted_fwd')
-            st = _hip.lib.hs_bootstrap_mean_of_batch_fwd(loss.data_ptr(), n, px, int(k), float(thresh), ws.data_ptr(), out.data_ptr(),
-                                                         out.data_ptr() + 4 * n * 8, _hip.stream_ptr())
-            _hip.check(st, 'hs_bootstrap_mean_of_batch_fwd')
+            HF.loss_launch('hs_cross_entropy_score_fwd', weight, *operands, loss.data_ptr(), nc, 0, confusion.data_ptr(), None, _hip.stream_ptr())
+            _hip.run.hs_bootstrap_mean_of_batch_fwd(loss.data_ptr(), n, px, int(k), float(thresh), ws.data_ptr(), out.data_ptr(),
+                                                    out.data_ptr() + 4 * n * 8, _hip.stream_ptr())
     ctx.save_for_backward(*((logits, target, loss, out) if weight is None else (logits, target, loss, out, weight)))
     ctx.ignore_index = int(ignore_index)
     return out[n * 8:].view(())
@@ -809,15 +751,8 @@ class BootstrappedCrossEntropy(torch.autograd.Function):
             g = g.float().contiguous()
         with _hip.device_scope(logits.device):
             dl = torch.empty_like(logits)
-            if not weight:
-                st = _hip.lib.hs_bootstrapped_ce_bwd(DTYPE_CODES[logits.dtype], logits.data_ptr(), target.data_ptr(), n, c, px, ctx.ignore_index,
-                                                     loss.data_ptr(), state.data_ptr(), g.data_ptr(), dl.data_ptr(), _hip.stream_ptr())
-                _hip.check(st, 'hs_bootstrapped_ce_bwd')
-            else:
-                st = _hip.lib.hs_bootstrapped_ce_weighted_bwd(DTYPE_CODES[logits.dtype], logits.data_ptr(), target.data_ptr(), weight[0].data_ptr(),
-                                                              n, c, px, ctx.ignore_index, loss.data_ptr(), state.data_ptr(), g.data_ptr(),
-                                                              dl.data_ptr(), _hip.stream_ptr())
-                _hip.check(st, 'hs_bootstrapped_ce_weighted_bwd')
+            HF.loss_launch('hs_bootstrapped_ce_bwd', weight[0] if weight else None, DTYPE_CODES[logits.dtype], logits.data_ptr(), target.data_ptr(),
+                           n, c, px, ctx.ignore_index, loss.data_ptr(), state.data_ptr(), g.data_ptr(), dl.data_ptr(), _hip.stream_ptr())
         return dl, None, None, None, None, None
 
 
@@ -858,9 +793,8 @@ class MetaConvGeneral(torch.autograd.Function):
             raise ValueError(f'kernel {kernel_size} (dilation {dilation}) does not fit the padded {h}x{wd} input')
         y = torch.empty(b, c_out, ho, wo, device=x.device, dtype=torch.float32)
         with _hip.device_scope(x.device):
-            st = _hip.lib.hs_meta_conv_fwd(_hip.dev_ptr(x, 'x'), b, cin, h, wd, w.data_ptr(), w.stride(0), c_out, kh, kw,
-                                           sh, sw, pt, pb, pl, pr, dh, dw, 0, groups, None, y.data_ptr(), _hip.stream_ptr())
-            _hip.check(st, 'hs_meta_conv_fwd')
+            _hip.run.hs_meta_conv_fwd(_hip.dev_ptr(x, 'x'), b, cin, h, wd, w.data_ptr(), w.stride(0), c_out, kh, kw,
+                                      sh, sw, pt, pb, pl, pr, dh, dw, 0, groups, None, y.data_ptr(), _hip.stream_ptr())
         ctx.save_for_backward(x, w)
         ctx.meta = (c_out, kernel_size, stride, pads, dilation, groups)
         return y
@@ -877,11 +811,8 @@ class MetaConvGeneral(torch.autograd.Function):
         if ctx.needs_input_grad[1]:
             dwt = (torch.empty if rows == w.shape[1] else torch.zeros)(w.shape, device=w.device, dtype=torch.float32)
         with _hip.device_scope(x.device):
-            st = _hip.lib.hs_meta_conv_bwd(x.data_ptr(), b, cin, h, wd, w.data_ptr(), w.stride(0), c_out, kh, kw, sh, sw, pt, pb, pl, pr,
-                                           dh, dw, groups, dy.data_ptr(), dx.data_ptr() if dx is not None else None,
-                                           dwt.data_ptr() if dwt is not None else None, dwt.stride(0) if dwt is not None else 0,
-                                           _hip.stream_ptr())
-            _hip.check(st, 'hs_meta_conv_bwd')
+            _hip.run.hs_meta_conv_bwd(x.data_ptr(), b, cin, h, wd, w.data_ptr(), w.stride(0), c_out, kh, kw, sh, sw, pt, pb, pl, pr,
+                                      dh, dw, groups, dy.data_ptr(), _hip.ptr(dx), _hip.ptr(dwt), dwt.stride(0) if dwt is not None else 0, _hip.stream_ptr())
         return dx, dwt, None, None, None, None, None, None
 
 
@@ -910,9 +841,8 @@ class BootstrapMeanBatched(torch.autograd.Function):
         with _hip.device_scope(values.device):
             ws = torch.empty(imgs * int(_hip.lib.hs_bootstrap_mean_workspace()), device=values.device, dtype=torch.uint8)
             out = torch.empty(imgs, 8, device=values.device, dtype=torch.float32)
-            st = _hip.lib.hs_bootstrap_mean_batched_fwd(values.data_ptr(), imgs, n, int(k), float(thresh), ws.data_ptr(), out.data_ptr(),
-                                                        _hip.stream_ptr())
-            _hip.check(st, 'hs_bootstrap_mean_batched_fwd')
+            _hip.run.hs_bootstrap_mean_batched_fwd(values.data_ptr(), imgs, n, int(k), float(thresh), ws.data_ptr(), out.data_ptr(),
+                                                   _hip.stream_ptr())
         ctx.save_for_backward(values, out)
         return out[:, 0].clone()
 
@@ -922,9 +852,8 @@ class BootstrapMeanBatched(torch.autograd.Function):
         imgs, n = values.shape
         with _hip.device_scope(values.device):
             gv = torch.empty_like(values)
-            st = _hip.lib.hs_bootstrap_mean_batched_bwd(values.data_ptr(), imgs, n, state.data_ptr(), g.contiguous().float().data_ptr(),
-                                                        gv.data_ptr(), _hip.stream_ptr())
-            _hip.check(st, 'hs_bootstrap_mean_batched_bwd')
+            _hip.run.hs_bootstrap_mean_batched_bwd(values.data_ptr(), imgs, n, state.data_ptr(), g.contiguous().float().data_ptr(),
+                                                   gv.data_ptr(), _hip.stream_ptr())
         return gv, None, None
 
 
@@ -941,9 +870,8 @@ class BootstrapMeanOfBatch(torch.autograd.Function):
         with _hip.device_scope(values.device):
             ws = torch.empty(imgs * int(_hip.lib.hs_bootstrap_mean_workspace()), device=values.device, dtype=torch.uint8)
             out = torch.empty(imgs * 8 + 1, device=values.device, dtype=torch.float32)          # (imgs, 8) state | the mean
-            st = _hip.lib.hs_bootstrap_mean_of_batch_fwd(values.data_ptr(), imgs, n, int(k), float(thresh), ws.data_ptr(), out.data_ptr(),
-                                                         out.data_ptr() + 4 * imgs * 8, _hip.stream_ptr())
-            _hip.check(st, 'hs_bootstrap_mean_of_batch_fwd')
+            _hip.run.hs_bootstrap_mean_of_batch_fwd(values.data_ptr(), imgs, n, int(k), float(thresh), ws.data_ptr(), out.data_ptr(),
+                                                    out.data_ptr() + 4 * imgs * 8, _hip.stream_ptr())
         ctx.save_for_backward(values, out)
         return out[imgs * 8:].view(())
 
@@ -955,8 +883,7 @@ class BootstrapMeanOfBatch(torch.autograd.Function):
             g = g.float().contiguous()
         with _hip.device_scope(values.device):
             gv = torch.empty_like(values)
-            st = _hip.lib.hs_bootstrap_mean_of_batch_bwd(values.data_ptr(), imgs, n, state.data_ptr(), g.data_ptr(), gv.data_ptr(), _hip.stream_ptr())
-            _hip.check(st, 'hs_bootstrap_mean_of_batch_bwd')
+            _hip.run.hs_bootstrap_mean_of_batch_bwd(values.data_ptr(), imgs, n, state.data_ptr(), g.data_ptr(), gv.data_ptr(), _hip.stream_ptr())
         return gv, None, None
 
 
@@ -983,8 +910,7 @@ class UpsampleBilinear(torch.autograd.Function):
         name = 'hs_upsample_bilinear_bf16_fwd' if x.dtype == torch.bfloat16 else 'hs_upsample_bilinear_f16_fwd'
         with _hip.device_scope(x.device):
             y = torch.empty(b, c, size[0], size[1], device=x.device, dtype=x.dtype)
-            st = getattr(_hip.lib, name)(_hip.dev_ptr(x, 'x', x.dtype), b, c, hi, wi, size[0], size[1], y.data_ptr(), _hip.stream_ptr())
-            _hip.check(st, name)
+            getattr(_hip.run, name)(_hip.dev_ptr(x, 'x', x.dtype), b, c, hi, wi, size[0], size[1], y.data_ptr(), _hip.stream_ptr())
         return y
 
     @staticmethod
@@ -993,8 +919,7 @@ class UpsampleBilinear(torch.autograd.Function):
         dy = dy.contiguous().to(dt)
         with _hip.device_scope(dy.device):
             dx = torch.empty(b, c, hi, wi, device=dy.device, dtype=dt)
-            st = _hip.lib.hs_upsample_bilinear_typed_bwd(DTYPE_CODES[dt], dy.data_ptr(), 0, b, c, hi, wi, ho, wo, dx.data_ptr(), _hip.stream_ptr())
-            _hip.check(st, 'hs_upsample_bilinear_typed_bwd')
+            _hip.run.hs_upsample_bilinear_typed_bwd(DTYPE_CODES[dt], dy.data_ptr(), 0, b, c, hi, wi, ho, wo, dx.data_ptr(), _hip.stream_ptr())
         return dx, None
 
 
@@ -1060,8 +985,7 @@ class BankPack(torch.autograd.Function):
         if dbank.is_cuda and dbank.dtype == torch.float32 and dbank.stride(1) == 1 and b <= 65535:
             with _hip.device_scope(dbank.device):                  # one LDS-tiled transpose incl. the zero tail (hs_bank_unpack_fwd)
                 dw = torch.empty(ctx.shape, device=dbank.device, dtype=torch.float32)
-                st = _hip.lib.hs_bank_unpack_fwd(dbank.data_ptr(), dbank.stride(0), b, c, fh, fw, 0, ctx.rows, dw.data_ptr(), _hip.stream_ptr())
-                _hip.check(st, 'hs_bank_unpack_fwd')
+                _hip.run.hs_bank_unpack_fwd(dbank.data_ptr(), dbank.stride(0), b, c, fh, fw, 0, ctx.rows, dw.data_ptr(), _hip.stream_ptr())
             return dw.to(ctx.dtype), None
         dw = dbank.new_zeros(ctx.shape, dtype=ctx.dtype)
         dw[:, :ctx.rows] = dbank[:, :ctx.rows].reshape(b, fh, fw, ctx.rows).permute(0, 3, 1, 2).to(ctx.dtype)
@@ -1108,9 +1032,8 @@ class StageMaterialize(torch.autograd.Function):
                     dyc = dyc.float()
                 with _hip.device_scope(dy.device):
                     dprev = torch.empty(b, cp, hp, wp, device=dy.device, dtype=dyc.dtype)
-                    st = _hip.lib.hs_upsample_bilinear_typed_bwd(DTYPE_CODES[dyc.dtype], dyc.data_ptr() + dyc.element_size() * (off + cs) * h * w,
-                                                                 dyc.shape[1] * h * w, b, cp, hp, wp, h, w, dprev.data_ptr(), _hip.stream_ptr())
-                    _hip.check(st, 'hs_upsample_bilinear_typed_bwd')
+                    _hip.run.hs_upsample_bilinear_typed_bwd(DTYPE_CODES[dyc.dtype], dyc.data_ptr() + dyc.element_size() * (off + cs) * h * w,
+                                                            dyc.shape[1] * h * w, b, cp, hp, wp, h, w, dprev.data_ptr(), _hip.stream_ptr())
                 dprev = dprev.to(pdt)
         return dskip, dprev, None
 

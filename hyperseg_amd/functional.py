@@ -140,8 +140,7 @@ class StageInput:
         st = self.c_struct(pdt)
         y = torch.empty(self.shape, device=self.device, dtype=dtype)
         with _hip.device_scope(self.device):
-            _hip.check(_hip.lib.hs_stage_input_typed_fwd(C.byref(st), codes[pdt], codes[dtype], y.data_ptr(), _hip.stream_ptr()),
-                       'hs_stage_input_typed_fwd')
+            _hip.run.hs_stage_input_typed_fwd(C.byref(st), codes[pdt], codes[dtype], y.data_ptr(), _hip.stream_ptr())
         return y
 
 
@@ -188,11 +187,10 @@ def signal2weights(signal, wsw_t, signal_index, signal_channels, groups, rows, o
     ld = _round_up(rows, 4)
     if out is None:
         out = torch.empty(b * fh * fw, ld, device=signal.device, dtype=torch.float32)
-    st = _hip.lib.hs_signal2weights_fwd(
+    _hip.run.hs_signal2weights_fwd(
         sig_ptr, b, c_signal, fh, fw, signal_index, signal_channels, groups,
         _hip.dev_ptr(wsw_t, 'wsw_t'), wc, rows,
         _hip.dev_ptr(out, 'bank'), out.stride(0), _hip.stream_ptr())
-    _hip.check(st, 'hs_signal2weights_fwd')
     return out
 
 
@@ -335,8 +333,7 @@ def s2w_packed(wsw_t, signal_channels, groups):
             if n < 0:
                 _hip.check(int(n), 'hs_s2w_pack_floats')
             hit = torch.empty(n, device=wsw_t.device, dtype=torch.float32)
-            _hip.check(_hip.lib.hs_s2w_pack_fwd(_hip.dev_ptr(wsw_t, 'wsw_t'), signal_channels, groups, wsw_t.shape[1], hit.data_ptr(),
-                                                _hip.stream_ptr()), 'hs_s2w_pack_fwd')
+            _hip.run.hs_s2w_pack_fwd(_hip.dev_ptr(wsw_t, 'wsw_t'), signal_channels, groups, wsw_t.shape[1], hit.data_ptr(), _hip.stream_ptr())
             publish_ready(wsw_t.device)
             _S2W_BLK[key] = (weakref.ref(wsw_t), hit, producer_stream(wsw_t.device))
     return hit
@@ -353,8 +350,7 @@ def signal2weights_multi(signal, layers, buf=None):
     b, _, fh, fw = signal.shape
     signal, sig_ptr, c_signal = _channel_view(signal, 'signal')
     arr, refs = _s2w_layer_table(signal, layers, buf)
-    st = _hip.lib.hs_signal2weights_multi_fwd(sig_ptr, b, c_signal, fh, fw, arr, len(layers), _hip.stream_ptr())
-    _hip.check(st, 'hs_signal2weights_multi_fwd')
+    _hip.run.hs_signal2weights_multi_fwd(sig_ptr, b, c_signal, fh, fw, arr, len(layers), _hip.stream_ptr())
     return refs
 
 
@@ -434,9 +430,8 @@ def bank_pack(w, ch_offset, rows, out=None):
     ld = _round_up(rows, 4)
     if out is None:
         out = torch.empty(b * fh * fw, ld, device=w.device, dtype=torch.float32)
-    st = _hip.lib.hs_bank_pack_fwd(w_ptr, b, hp_total, fh, fw, ch_offset, rows,
-                                   _hip.dev_ptr(out, 'bank'), out.stride(0), _hip.stream_ptr())
-    _hip.check(st, 'hs_bank_pack_fwd')
+    _hip.run.hs_bank_pack_fwd(w_ptr, b, hp_total, fh, fw, ch_offset, rows,
+                              _hip.dev_ptr(out, 'bank'), out.stride(0), _hip.stream_ptr())
     return out
 
 
@@ -444,10 +439,9 @@ def bank_pack(w, ch_offset, rows, out=None):
 def bn_fold(gamma, beta, mean, var, eps=BN_EPS_DEFAULT):
     n = mean.numel()
     out = torch.empty(2, n, device=mean.device, dtype=torch.float32)
-    st = _hip.lib.hs_bn_fold_fwd(_hip.dev_ptr(gamma, 'bn weight'), _hip.dev_ptr(beta, 'bn bias'),
-                                 _hip.dev_ptr(mean, 'bn running_mean'), _hip.dev_ptr(var, 'bn running_var'),
-                                 float(eps), n, out[0].data_ptr(), out[1].data_ptr(), _hip.stream_ptr())
-    _hip.check(st, 'hs_bn_fold_fwd')
+    _hip.run.hs_bn_fold_fwd(_hip.dev_ptr(gamma, 'bn weight'), _hip.dev_ptr(beta, 'bn bias'),
+                            _hip.dev_ptr(mean, 'bn running_mean'), _hip.dev_ptr(var, 'bn running_var'),
+                            float(eps), n, out[0].data_ptr(), out[1].data_ptr(), _hip.stream_ptr())
     return out[0], out[1]
 
 
@@ -483,10 +477,9 @@ def patch_conv(x, grid, bank, c_out, k=1, padding=0, padding_mode='reflect', gro
             co.refs, co.carried = refs, True
             CoScheduledBanks._active = None
             return y
-    st = _hip.lib.hs_patch_conv_fwd(C.byref(st_in), fh, fw, bank_ptr, ld, c_out, k,
-                                    padding, PAD_MODES[padding_mode], groups, C.byref(ep), y.data_ptr(),
-                                    _hip.stream_ptr())
-    _hip.check(st, 'hs_patch_conv_fwd')
+    _hip.run.hs_patch_conv_fwd(C.byref(st_in), fh, fw, bank_ptr, ld, c_out, k,
+                               padding, PAD_MODES[padding_mode], groups, C.byref(ep), y.data_ptr(),
+                               _hip.stream_ptr())
     return y
 
 
@@ -705,10 +698,9 @@ def meta_conv(x, w, c_out, kernel_size, stride=(1, 1), padding=(0, 0), dilation=
     ep = _epilogue(scale, shift, act)
     y = torch.empty(b, c_out, ho, wo, device=x.device, dtype=torch.float32)
     w_ptr, ldw = _bank_ptr(w)            # a column range w[:, a:b] of a wider tensor (MetaSequential's slice) is read in place: ldw = its row stride
-    st = _hip.lib.hs_meta_conv_fwd(_hip.dev_ptr(x, 'x'), b, cin, h, wd, w_ptr, ldw, c_out, kh, kw,
-                                   sh, sw, pt, pb, pl, pr, dh, dw, PAD_MODES[padding_mode], groups, C.byref(ep), y.data_ptr(),
-                                   _hip.stream_ptr())
-    _hip.check(st, 'hs_meta_conv_fwd')
+    _hip.run.hs_meta_conv_fwd(_hip.dev_ptr(x, 'x'), b, cin, h, wd, w_ptr, ldw, c_out, kh, kw,
+                              sh, sw, pt, pb, pl, pr, dh, dw, PAD_MODES[padding_mode], groups, C.byref(ep), y.data_ptr(),
+                              _hip.stream_ptr())
     return y
 
 
@@ -748,10 +740,9 @@ def patch_ir(x, grid, bank, hidden, c_out, bn1, bn2, bn3, residual=False, math=N
     e1, e2, e3 = _epilogue(*bn1), _epilogue(*bn2), _epilogue(*bn3)
     y = torch.empty(b, c_out, h, w, device=stage.device, dtype=torch.float32)
     bank_ptr, ld = _bank_ptr(bank)
-    st = _hip.lib.hs_patch_ir_fwd(C.byref(st_in), fh, fw, bank_ptr, ld, hidden, c_out,
-                                  C.byref(e1), C.byref(e2), C.byref(e3), int(bool(residual)), ir_math_code(math),
-                                  y.data_ptr(), _hip.stream_ptr())
-    _hip.check(st, 'hs_patch_ir_fwd')
+    _hip.run.hs_patch_ir_fwd(C.byref(st_in), fh, fw, bank_ptr, ld, hidden, c_out,
+                             C.byref(e1), C.byref(e2), C.byref(e3), int(bool(residual)), ir_math_code(math),
+                             y.data_ptr(), _hip.stream_ptr())
     return y
 
 
@@ -774,7 +765,7 @@ def patch_ir_v0(x, grid, bank, hidden, c_out, bn1, bn2, bn3, math=None):
     need = int(_hip.lib.hs_patch_ir_v0_workspace(C.byref(st_in), fh, fw, hidden, c_out)) if D2_ROUTE else 0
     ws = torch.empty(need // 4, device=stage.device, dtype=torch.float32) if need > 0 else None
     st = _hip.lib.hs_patch_ir_v0_ws_fwd(C.byref(st_in), fh, fw, bank_ptr, ld, hidden, c_out, C.byref(e1), C.byref(e2), C.byref(e3),
-                                        ir_math_code(math), ws.data_ptr() if ws is not None else None, need, y.data_ptr(),
+                                        ir_math_code(math), _hip.ptr(ws), need, y.data_ptr(),
                                         _hip.stream_ptr())
     if st == -3:
         return None
@@ -859,9 +850,9 @@ def ir_tile_map(reg, mode, pwr):
     (host-side introspection, no GPU needed)."""
     import numpy as np
     nt, nt3 = C.c_int32(0), C.c_int32(0)
-    _hip.check(_hip.lib.hs_ir_tile_map(reg, mode, pwr, C.byref(nt), C.byref(nt3), None, 0), 'hs_ir_tile_map')
+    _hip.run.hs_ir_tile_map(reg, mode, pwr, C.byref(nt), C.byref(nt3), None, 0)
     buf = (C.c_int32 * (nt.value * 48))()
-    _hip.check(_hip.lib.hs_ir_tile_map(reg, mode, pwr, C.byref(nt), C.byref(nt3), buf, nt.value * 48), 'hs_ir_tile_map')
+    _hip.run.hs_ir_tile_map(reg, mode, pwr, C.byref(nt), C.byref(nt3), buf, nt.value * 48)
     return nt3.value, np.ctypeslib.as_array(buf).reshape(nt.value, 16, 3).copy()
 
 
@@ -967,27 +958,25 @@ def depthwise_conv_bn_act(x, weight, stride, pad_top, pad_left, out_size, scale=
         desc = se_tail_descriptor(x.device, b, c, nblk, c * nblk, *se)
         if desc is not None:
             d, gate, _ws = desc
-            st = _hip.lib.hs_depthwise_conv_se_fwd(_hip.dev_ptr(x, 'x'), b, c, h, w, _hip.dev_ptr(weight, 'weight'), k, stride,
-                                                   pad_top, pad_left, ho, wo,
-                                                   _hip.dev_ptr(scale, 'scale') if scale is not None else None,
-                                                   _hip.dev_ptr(shift, 'shift') if shift is not None else None, int(act), y.data_ptr(),
-                                                   _hip.dev_ptr(in_scale, 'in_scale') if in_scale is not None else None,
-                                                   _hip.dev_ptr(in_shift, 'in_shift') if in_shift is not None else None,
-                                                   C.byref(d), _hip.stream_ptr())
-            _hip.check(st, 'hs_depthwise_conv_se_fwd')
+            _hip.run.hs_depthwise_conv_se_fwd(_hip.dev_ptr(x, 'x'), b, c, h, w, _hip.dev_ptr(weight, 'weight'), k, stride,
+                                              pad_top, pad_left, ho, wo,
+                                              _hip.dev_ptr(scale, 'scale') if scale is not None else None,
+                                              _hip.dev_ptr(shift, 'shift') if shift is not None else None, int(act), y.data_ptr(),
+                                              _hip.dev_ptr(in_scale, 'in_scale') if in_scale is not None else None,
+                                              _hip.dev_ptr(in_shift, 'in_shift') if in_shift is not None else None,
+                                              C.byref(d), _hip.stream_ptr())
             return y, gate, True
     partial = None
     if pool:
         partial = torch.empty(b * c, _hip.lib.hs_depthwise_pool_blocks(ho, wo), device=x.device, dtype=torch.float32)
-    st = _hip.lib.hs_depthwise_conv_fwd(_hip.dev_ptr(x, 'x'), b, c, h, w, _hip.dev_ptr(weight, 'weight'), k, stride,
-                                        pad_top, pad_left, ho, wo,
-                                        _hip.dev_ptr(scale, 'scale') if scale is not None else None,
-                                        _hip.dev_ptr(shift, 'shift') if shift is not None else None, int(act),
-                                        y.data_ptr(), partial.data_ptr() if pool else None,
-                                        _hip.dev_ptr(in_scale, 'in_scale') if in_scale is not None else None,
-                                        _hip.dev_ptr(in_shift, 'in_shift') if in_shift is not None else None,
-                                        _hip.stream_ptr())
-    _hip.check(st, 'hs_depthwise_conv_fwd')
+    _hip.run.hs_depthwise_conv_fwd(_hip.dev_ptr(x, 'x'), b, c, h, w, _hip.dev_ptr(weight, 'weight'), k, stride,
+                                   pad_top, pad_left, ho, wo,
+                                   _hip.dev_ptr(scale, 'scale') if scale is not None else None,
+                                   _hip.dev_ptr(shift, 'shift') if shift is not None else None, int(act),
+                                   y.data_ptr(), partial.data_ptr() if pool else None,
+                                   _hip.dev_ptr(in_scale, 'in_scale') if in_scale is not None else None,
+                                   _hip.dev_ptr(in_shift, 'in_shift') if in_shift is not None else None,
+                                   _hip.stream_ptr())
     if se is not None and pool:
         return y, partial, False
     return (y, partial) if pool else y
@@ -1000,10 +989,9 @@ def stem_conv_bn_swish(x, weight, pad_top, pad_left, out_size, scale, shift):
     cout = weight.shape[0]
     ho, wo = out_size
     y = torch.empty(b, cout, ho, wo, device=x.device, dtype=torch.float32)
-    st = _hip.lib.hs_stem_conv_fwd(_hip.dev_ptr(x, 'x'), b, cin, h, w, _hip.dev_ptr(weight, 'weight'), cout, pad_top, pad_left,
-                                   ho, wo, _hip.dev_ptr(scale, 'scale'), _hip.dev_ptr(shift, 'shift'), y.data_ptr(),
-                                   _hip.stream_ptr())
-    _hip.check(st, 'hs_stem_conv_fwd')
+    _hip.run.hs_stem_conv_fwd(_hip.dev_ptr(x, 'x'), b, cin, h, w, _hip.dev_ptr(weight, 'weight'), cout, pad_top, pad_left,
+                              ho, wo, _hip.dev_ptr(scale, 'scale'), _hip.dev_ptr(shift, 'shift'), y.data_ptr(),
+                              _hip.stream_ptr())
     return y
 
 
@@ -1024,9 +1012,8 @@ def image_ingest(x_u8, norm, out=None):
         out = torch.empty(b, 3, h, w, device=x_u8.device, dtype=torch.float32)
     elif not isinstance(out, torch.Tensor) or tuple(out.shape) != (b, 3, h, w) or out.device != x_u8.device:
         raise ValueError(f'out must be a float32 tensor of shape {(b, 3, h, w)} on {x_u8.device}')
-    st = _hip.lib.hs_image_ingest_fwd(_hip.dev_ptr(x_u8, 'x_u8', torch.uint8), _LAYOUT_CODES[norm.layout], b, 3, h, w,
-                                      _hip.dev_ptr(norm.table(x_u8.device), 'table'), _hip.dev_ptr(out, 'out'), _hip.stream_ptr())
-    _hip.check(st, 'hs_image_ingest_fwd')
+    _hip.run.hs_image_ingest_fwd(_hip.dev_ptr(x_u8, 'x_u8', torch.uint8), _LAYOUT_CODES[norm.layout], b, 3, h, w,
+                                 _hip.dev_ptr(norm.table(x_u8.device), 'table'), _hip.dev_ptr(out, 'out'), _hip.stream_ptr())
     return out
 
 
@@ -1079,22 +1066,20 @@ def mbconv_expand_dw(x, w_expand, scale0, shift0, w_dw, stride, pad_top, pad_lef
         desc = se_tail_descriptor(x.device, b, cmid, nblk, int(_hip.lib.hs_mbconv_se_workgroups(b, cmid, k, stride, ho, wo)), *se)
         if desc is not None:
             d, gate, _ws = desc
-            st = _hip.lib.hs_mbconv_expand_dw_se_fwd(_hip.dev_ptr(x, 'x'), b, cin, h, w, _hip.dev_ptr(w_expand, 'w_expand'), cmid,
-                                                     _hip.dev_ptr(scale0, 'scale0'), _hip.dev_ptr(shift0, 'shift0'),
-                                                     _hip.dev_ptr(w_dw, 'w_dw'), k, stride, pad_top, pad_left, ho, wo,
-                                                     _hip.dev_ptr(scale1, 'scale1'), _hip.dev_ptr(shift1, 'shift1'), y.data_ptr(),
-                                                     C.byref(d), _hip.stream_ptr())
-            _hip.check(st, 'hs_mbconv_expand_dw_se_fwd')
+            _hip.run.hs_mbconv_expand_dw_se_fwd(_hip.dev_ptr(x, 'x'), b, cin, h, w, _hip.dev_ptr(w_expand, 'w_expand'), cmid,
+                                                _hip.dev_ptr(scale0, 'scale0'), _hip.dev_ptr(shift0, 'shift0'),
+                                                _hip.dev_ptr(w_dw, 'w_dw'), k, stride, pad_top, pad_left, ho, wo,
+                                                _hip.dev_ptr(scale1, 'scale1'), _hip.dev_ptr(shift1, 'shift1'), y.data_ptr(),
+                                                C.byref(d), _hip.stream_ptr())
             return y, gate, True
     partial = None
     if pool:
         partial = torch.empty(b * cmid, _hip.lib.hs_mbconv_tiles(k, stride, ho, wo), device=x.device, dtype=torch.float32)
-    st = _hip.lib.hs_mbconv_expand_dw_fwd(_hip.dev_ptr(x, 'x'), b, cin, h, w, _hip.dev_ptr(w_expand, 'w_expand'), cmid,
-                                          _hip.dev_ptr(scale0, 'scale0'), _hip.dev_ptr(shift0, 'shift0'),
-                                          _hip.dev_ptr(w_dw, 'w_dw'), k, stride, pad_top, pad_left, ho, wo,
-                                          _hip.dev_ptr(scale1, 'scale1'), _hip.dev_ptr(shift1, 'shift1'), y.data_ptr(),
-                                          partial.data_ptr() if pool else None, _hip.stream_ptr())
-    _hip.check(st, 'hs_mbconv_expand_dw_fwd')
+    _hip.run.hs_mbconv_expand_dw_fwd(_hip.dev_ptr(x, 'x'), b, cin, h, w, _hip.dev_ptr(w_expand, 'w_expand'), cmid,
+                                     _hip.dev_ptr(scale0, 'scale0'), _hip.dev_ptr(shift0, 'shift0'),
+                                     _hip.dev_ptr(w_dw, 'w_dw'), k, stride, pad_top, pad_left, ho, wo,
+                                     _hip.dev_ptr(scale1, 'scale1'), _hip.dev_ptr(shift1, 'shift1'), y.data_ptr(),
+                                     partial.data_ptr() if pool else None, _hip.stream_ptr())
     if se is not None and pool:
         return y, partial, False
     return (y, partial) if pool else y
@@ -1107,10 +1092,9 @@ def pointwise_conv(x, weight, gate=None, scale=None, shift=None, act=0, residual
     cout = weight.shape[0]
     y = torch.empty(b, cout, h, w, device=x.device, dtype=torch.float32)
     opt = lambda t, n: _hip.dev_ptr(t, n) if t is not None else None   # noqa: E731
-    st = _hip.lib.hs_pointwise_conv_fwd(_hip.dev_ptr(x, 'x'), b, cin, h * w, _hip.dev_ptr(weight, 'weight'), cout,
-                                        opt(gate, 'gate'), opt(scale, 'scale'), opt(shift, 'shift'), int(act),
-                                        opt(residual, 'residual'), y.data_ptr(), _hip.stream_ptr())
-    _hip.check(st, 'hs_pointwise_conv_fwd')
+    _hip.run.hs_pointwise_conv_fwd(_hip.dev_ptr(x, 'x'), b, cin, h * w, _hip.dev_ptr(weight, 'weight'), cout,
+                                   opt(gate, 'gate'), opt(scale, 'scale'), opt(shift, 'shift'), int(act),
+                                   opt(residual, 'residual'), y.data_ptr(), _hip.stream_ptr())
     return y
 
 
@@ -1119,12 +1103,11 @@ def affine_act_(x, scale, shift, act=0, residual=None):
     """In place: x = act(scale[c]*x + shift[c]) + residual  (folded BN + activation + skip add, one launch);
     ``scale=None`` means 1."""
     b, c, h, w = x.shape
-    st = _hip.lib.hs_affine_act_fwd(_hip.dev_ptr(x, 'x'), b, c, h * w,
-                                    _hip.dev_ptr(scale, 'scale') if scale is not None else None,
-                                    _hip.dev_ptr(shift, 'shift'), int(act),
-                                    _hip.dev_ptr(residual, 'residual') if residual is not None else None, x.data_ptr(),
-                                    _hip.stream_ptr())
-    _hip.check(st, 'hs_affine_act_fwd')
+    _hip.run.hs_affine_act_fwd(_hip.dev_ptr(x, 'x'), b, c, h * w,
+                               _hip.dev_ptr(scale, 'scale') if scale is not None else None,
+                               _hip.dev_ptr(shift, 'shift'), int(act),
+                               _hip.dev_ptr(residual, 'residual') if residual is not None else None, x.data_ptr(),
+                               _hip.stream_ptr())
     return x
 
 
@@ -1145,14 +1128,13 @@ def se_gate(partial, batch, hw, w_reduce, b_reduce, w_expand, b_expand, w_proj=N
     if w_proj is not None:
         cout = w_proj.shape[0]
         w_scaled = torch.empty(batch, cout, c, 1, 1, device=dev, dtype=torch.float32)
-    st = _hip.lib.hs_se_gate_fwd(_hip.dev_ptr(partial, 'partial'), batch, c, partial.shape[1], 1.0 / float(hw),
-                                 _hip.dev_ptr(w_reduce, 'w_reduce'), _hip.dev_ptr(b_reduce, 'b_reduce'), csq,
-                                 _hip.dev_ptr(w_expand, 'w_expand'), _hip.dev_ptr(b_expand, 'b_expand'),
-                                 squeezed.data_ptr(), gate.data_ptr(),
-                                 _hip.dev_ptr(w_proj, 'w_proj') if w_proj is not None else None, cout,
-                                 _hip.dev_ptr(out_scale, 'out_scale') if out_scale is not None else None,
-                                 w_scaled.data_ptr() if w_scaled is not None else None, _hip.stream_ptr())
-    _hip.check(st, 'hs_se_gate_fwd')
+    _hip.run.hs_se_gate_fwd(_hip.dev_ptr(partial, 'partial'), batch, c, partial.shape[1], 1.0 / float(hw),
+                            _hip.dev_ptr(w_reduce, 'w_reduce'), _hip.dev_ptr(b_reduce, 'b_reduce'), csq,
+                            _hip.dev_ptr(w_expand, 'w_expand'), _hip.dev_ptr(b_expand, 'b_expand'),
+                            squeezed.data_ptr(), gate.data_ptr(),
+                            _hip.dev_ptr(w_proj, 'w_proj') if w_proj is not None else None, cout,
+                            _hip.dev_ptr(out_scale, 'out_scale') if out_scale is not None else None,
+                            _hip.ptr(w_scaled), _hip.stream_ptr())
     return w_scaled if w_proj is not None else gate
 
 
@@ -1213,12 +1195,11 @@ def gemm_split(sw, x, gate=None, shift=None, act=ACT_NONE, residual=None, out=No
         raise ValueError(f'gate has shape {tuple(gate.shape)}, expected {(b, cin)}')
     if shift is not None and shift.numel() != sw.c_out:
         raise ValueError(f'shift has {shift.numel()} entries, expected {sw.c_out}')
-    st = _hip.lib.hs_gemm_split_fwd(_hip.dev_ptr(sw.frag, 'w_frag', torch.float16), _hip.dev_ptr(sw.inv, 'w_inv'),
-                                    _hip.dev_ptr(gate, 'gate') if gate is not None else None, _hip.dev_ptr(x, 'x'),
-                                    _hip.dev_ptr(shift, 'shift') if shift is not None else None, int(act),
-                                    _hip.dev_ptr(residual, 'residual') if residual is not None else None,
-                                    _hip.dev_ptr(out, 'out'), b, sw.c_out, cin, sw.kp, h * w, _hip.stream_ptr())
-    _hip.check(st, 'hs_gemm_split_fwd')
+    _hip.run.hs_gemm_split_fwd(_hip.dev_ptr(sw.frag, 'w_frag', torch.float16), _hip.dev_ptr(sw.inv, 'w_inv'),
+                               _hip.dev_ptr(gate, 'gate') if gate is not None else None, _hip.dev_ptr(x, 'x'),
+                               _hip.dev_ptr(shift, 'shift') if shift is not None else None, int(act),
+                               _hip.dev_ptr(residual, 'residual') if residual is not None else None,
+                               _hip.dev_ptr(out, 'out'), b, sw.c_out, cin, sw.kp, h * w, _hip.stream_ptr())
     return out
 
 
@@ -1243,12 +1224,11 @@ def gemm_split_conv2x2(sw, x, shift=None, act=ACT_NONE, out=None, pool_partial=N
     nblk = -(-(h // 2) * (w // 2) // 16)
     if pool_partial is not None and tuple(pool_partial.shape) != (b, sw.c_out, nblk):
         raise ValueError(f'pool_partial has shape {tuple(pool_partial.shape)}, expected {(b, sw.c_out, nblk)}')
-    st = _hip.lib.hs_gemm_split_conv2x2_fwd(_hip.dev_ptr(sw.frag, 'w_frag', torch.float16), _hip.dev_ptr(sw.inv, 'w_inv'),
-                                            _hip.dev_ptr(x, 'x'), _hip.dev_ptr(shift, 'shift') if shift is not None else None,
-                                            int(act), _hip.dev_ptr(out, 'out'),
-                                            _hip.dev_ptr(pool_partial, 'pool_partial') if pool_partial is not None else None,
-                                            b, sw.c_out, cin, sw.kp, h // 2, w // 2, _hip.stream_ptr())
-    _hip.check(st, 'hs_gemm_split_conv2x2_fwd')
+    _hip.run.hs_gemm_split_conv2x2_fwd(_hip.dev_ptr(sw.frag, 'w_frag', torch.float16), _hip.dev_ptr(sw.inv, 'w_inv'),
+                                       _hip.dev_ptr(x, 'x'), _hip.dev_ptr(shift, 'shift') if shift is not None else None,
+                                       int(act), _hip.dev_ptr(out, 'out'),
+                                       _hip.dev_ptr(pool_partial, 'pool_partial') if pool_partial is not None else None,
+                                       b, sw.c_out, cin, sw.kp, h // 2, w // 2, _hip.stream_ptr())
     return out
 
 
@@ -1266,10 +1246,9 @@ def gemm_split_up2(sw, x, shift=None, act=ACT_NONE, out=None):
         raise ValueError(f'out has shape {tuple(out.shape)}, expected {shape}')
     if shift is not None and shift.numel() != sw.c_out:
         raise ValueError(f'shift has {shift.numel()} entries, expected {sw.c_out}')
-    st = _hip.lib.hs_gemm_split_up2_fwd(_hip.dev_ptr(sw.frag, 'w_frag', torch.float16), _hip.dev_ptr(sw.inv, 'w_inv'),
-                                        _hip.dev_ptr(x, 'x'), _hip.dev_ptr(shift, 'shift') if shift is not None else None,
-                                        int(act), _hip.dev_ptr(out, 'out'), b, sw.c_out, cin, sw.kp, h, w, _hip.stream_ptr())
-    _hip.check(st, 'hs_gemm_split_up2_fwd')
+    _hip.run.hs_gemm_split_up2_fwd(_hip.dev_ptr(sw.frag, 'w_frag', torch.float16), _hip.dev_ptr(sw.inv, 'w_inv'),
+                                   _hip.dev_ptr(x, 'x'), _hip.dev_ptr(shift, 'shift') if shift is not None else None,
+                                   int(act), _hip.dev_ptr(out, 'out'), b, sw.c_out, cin, sw.kp, h, w, _hip.stream_ptr())
     return out
 
 
@@ -1282,9 +1261,8 @@ def pooled_shift(pool_partial, pixels, wb, shift):
     if pool_partial.shape[0] != 1 or tuple(wb.shape) != (m, c):
         raise ValueError(f'pool_partial {tuple(pool_partial.shape)} / wb {tuple(wb.shape)} / shift {m}: expected (1, C, nblk), (M, C), M')
     out = torch.empty(m, device=shift.device, dtype=torch.float32)
-    st = _hip.lib.hs_pooled_shift_fwd(_hip.dev_ptr(pool_partial, 'pool_partial'), nblk, 1.0 / pixels, _hip.dev_ptr(wb, 'wb'),
-                                      _hip.dev_ptr(shift, 'shift'), _hip.dev_ptr(out, 'shift_out'), m, c, _hip.stream_ptr())
-    _hip.check(st, 'hs_pooled_shift_fwd')
+    _hip.run.hs_pooled_shift_fwd(_hip.dev_ptr(pool_partial, 'pool_partial'), nblk, 1.0 / pixels, _hip.dev_ptr(wb, 'wb'),
+                                 _hip.dev_ptr(shift, 'shift'), _hip.dev_ptr(out, 'shift_out'), m, c, _hip.stream_ptr())
     return out
 
 
@@ -1298,9 +1276,8 @@ def upsample_bilinear(x, size, out=None):
         y = out
     else:
         y = torch.empty(b, c, ho, wo, device=x.device, dtype=torch.float32)
-    st = _hip.lib.hs_upsample_bilinear_fwd(_hip.dev_ptr(x, 'x'), b, c, hi, wi, ho, wo, y.data_ptr(),
-                                           _hip.stream_ptr())
-    _hip.check(st, 'hs_upsample_bilinear_fwd')
+    _hip.run.hs_upsample_bilinear_fwd(_hip.dev_ptr(x, 'x'), b, c, hi, wi, ho, wo, y.data_ptr(),
+                                      _hip.stream_ptr())
     return y
 
 
@@ -1311,8 +1288,7 @@ def upsample_argmax(x, size):
     b, c, hi, wi = x.shape
     ho, wo = size
     mask = torch.empty(b, ho, wo, device=x.device, dtype=torch.uint8)
-    st = _hip.lib.hs_upsample_argmax_fwd(_hip.dev_ptr(x, 'x'), b, c, hi, wi, ho, wo, mask.data_ptr(), _hip.stream_ptr())
-    _hip.check(st, 'hs_upsample_argmax_fwd')
+    _hip.run.hs_upsample_argmax_fwd(_hip.dev_ptr(x, 'x'), b, c, hi, wi, ho, wo, mask.data_ptr(), _hip.stream_ptr())
     return mask
 
 
@@ -1401,10 +1377,9 @@ def upsample_confusion(x, size, target, num_classes, out=None, per_image=False, 
     target = _eval_target(target, (b, ho, wo), x)
     n, out = _score_out(num_classes, c, out, b, per_image, x.device, counted=True)
     mask = torch.empty(b, ho, wo, device=x.device, dtype=torch.uint8) if masks else None
-    st = _hip.lib.hs_upsample_confusion_fwd(_hip.dev_ptr(x, 'x'), b, c, hi, wi, ho, wo, target.data_ptr(), _EVAL_DTYPES[target.dtype], n,
-                                            1 if per_image else 0, out.data_ptr(), mask.data_ptr() if masks else None,
-                                            _hip.stream_ptr())
-    _hip.check(st, 'hs_upsample_confusion_fwd')
+    _hip.run.hs_upsample_confusion_fwd(_hip.dev_ptr(x, 'x'), b, c, hi, wi, ho, wo, target.data_ptr(), _EVAL_DTYPES[target.dtype], n,
+                                       1 if per_image else 0, out.data_ptr(), mask.data_ptr() if masks else None,
+                                       _hip.stream_ptr())
     return (out, mask) if masks else out
 
 
@@ -1434,10 +1409,9 @@ def upsample2_confusion(x, mid_size, target, num_classes, out=None, per_image=Fa
     target = _eval_target(target, (b, ho, wo), x)
     n, out = _score_out(num_classes, c, out, b, per_image, x.device, counted=True)
     mask = torch.empty(b, ho, wo, device=x.device, dtype=torch.uint8) if masks else None
-    st = _hip.lib.hs_upsample2_confusion_fwd(_hip.dev_ptr(x, 'x'), b, c, hi, wi, hm, wm, ho, wo, target.data_ptr(), _EVAL_DTYPES[target.dtype], n,
-                                             1 if per_image else 0, out.data_ptr(), mask.data_ptr() if masks else None,
-                                             _hip.stream_ptr())
-    _hip.check(st, 'hs_upsample2_confusion_fwd')
+    _hip.run.hs_upsample2_confusion_fwd(_hip.dev_ptr(x, 'x'), b, c, hi, wi, hm, wm, ho, wo, target.data_ptr(), _EVAL_DTYPES[target.dtype], n,
+                                        1 if per_image else 0, out.data_ptr(), mask.data_ptr() if masks else None,
+                                        _hip.stream_ptr())
     return (out, mask) if masks else out
 
 
@@ -1451,9 +1425,8 @@ def upsample2_argmax(x, mid_size, size):
     if (ho, wo) == (hm, wm) or (hi, wi) == (hm, wm):
         return upsample_argmax(x, (ho, wo))
     mask = torch.empty(b, ho, wo, device=x.device, dtype=torch.uint8)
-    st = _hip.lib.hs_upsample2_confusion_fwd(_hip.dev_ptr(x, 'x'), b, c, hi, wi, hm, wm, ho, wo, None, 0, 0, 0, None, mask.data_ptr(),
-                                             _hip.stream_ptr())
-    _hip.check(st, 'hs_upsample2_confusion_fwd')
+    _hip.run.hs_upsample2_confusion_fwd(_hip.dev_ptr(x, 'x'), b, c, hi, wi, hm, wm, ho, wo, None, 0, 0, 0, None, mask.data_ptr(),
+                                        _hip.stream_ptr())
     return mask
 
 
@@ -1472,9 +1445,8 @@ def confusion_update(pred, target, num_classes, out=None, per_image=False):
     if per_image and pred.dim() < 2:
         raise ValueError('per_image needs a leading image dimension')
     out = _eval_out(out, (b, n, n) if per_image else (n, n), pred.device)
-    st = _hip.lib.hs_confusion_fwd(pred.data_ptr(), _EVAL_DTYPES[pred.dtype], target.data_ptr(), _EVAL_DTYPES[target.dtype], b,
-                                   pred.numel() // b, n, 1 if per_image else 0, out.data_ptr(), _hip.stream_ptr())
-    _hip.check(st, 'hs_confusion_fwd')
+    _hip.run.hs_confusion_fwd(pred.data_ptr(), _EVAL_DTYPES[pred.dtype], target.data_ptr(), _EVAL_DTYPES[target.dtype], b,
+                              pred.numel() // b, n, 1 if per_image else 0, out.data_ptr(), _hip.stream_ptr())
     return out
 
 
@@ -1489,6 +1461,21 @@ def class_weight_table(weight, classes, device, what='weight'):
         raise ValueError(f'{what} must be a contiguous float32 ({classes},) tensor on {device}, got {getattr(weight, "dtype", type(weight))} '
                          f'{tuple(getattr(weight, "shape", ()))} on {getattr(weight, "device", None)}')
     return weight.detach()
+
+
+# loss entry -> (its class-weighted twin, where the twin's argument list takes the table: after the target, or after the target's type code)
+_WEIGHTED_TWINS = {'hs_cross_entropy_typed_fwd': ('hs_cross_entropy_weighted_fwd', 3), 'hs_cross_entropy_typed_bwd': ('hs_cross_entropy_weighted_bwd', 3),
+                   'hs_bootstrapped_ce_fwd': ('hs_bootstrapped_ce_weighted_fwd', 3), 'hs_bootstrapped_ce_bwd': ('hs_bootstrapped_ce_weighted_bwd', 3),
+                   'hs_cross_entropy_score_fwd': ('hs_cross_entropy_score_weighted_fwd', 3),
+                   'hs_upsample_ce_confusion_fwd': ('hs_upsample_ce_confusion_weighted_fwd', 9)}
+
+
+def loss_launch(entry, table, *args):
+    """``entry(*args)`` -- with a class-weight ``table`` (``class_weight_table``'s) the weighted twin, the table's pointer spliced in."""
+    if table is None:
+        return getattr(_hip.run, entry)(*args)
+    twin, at = _WEIGHTED_TWINS[entry]
+    return getattr(_hip.run, twin)(*args[:at], table.data_ptr(), *args[at:])
 
 
 @_on_operand_device
@@ -1512,14 +1499,9 @@ def cross_entropy_score(logits, target, ignore_index, num_classes, out=None, per
     xp = _hip.dev_ptr(logits, 'logits', logits.dtype)
     loss = torch.empty(b, h, w, device=logits.device, dtype=torch.float32)
     mask = torch.empty(b, h, w, device=logits.device, dtype=torch.uint8) if masks else None
-    tail = (loss.data_ptr(), n, 1 if per_image else 0, None if out is None else out.data_ptr(), mask.data_ptr() if masks else None, _hip.stream_ptr())
-    table = class_weight_table(weight, c, logits.device)
-    if table is None:
-        st = _hip.lib.hs_cross_entropy_score_fwd(DTYPE_CODES[logits.dtype], xp, target.data_ptr(), b, c, h * w, int(ignore_index), *tail)
-        _hip.check(st, 'hs_cross_entropy_score_fwd')
-    else:
-        st = _hip.lib.hs_cross_entropy_score_weighted_fwd(DTYPE_CODES[logits.dtype], xp, target.data_ptr(), table.data_ptr(), b, c, h * w, int(ignore_index), *tail)
-        _hip.check(st, 'hs_cross_entropy_score_weighted_fwd')
+    tail = (loss.data_ptr(), n, 1 if per_image else 0, _hip.ptr(out), mask.data_ptr() if masks else None, _hip.stream_ptr())
+    loss_launch('hs_cross_entropy_score_fwd', class_weight_table(weight, c, logits.device),
+                DTYPE_CODES[logits.dtype], xp, target.data_ptr(), b, c, h * w, int(ignore_index), *tail)
     return (loss, out, mask) if masks else (loss, out)
 
 
@@ -1539,14 +1521,9 @@ def upsample_ce_confusion(x, size, target, ignore_index, num_classes, out=None, 
     xp = _hip.dev_ptr(x, 'x')
     loss = torch.empty(b, ho, wo, device=x.device, dtype=torch.float32)
     mask = torch.empty(b, ho, wo, device=x.device, dtype=torch.uint8)
-    tail = (int(ignore_index), loss.data_ptr(), n, 1 if per_image else 0, None if out is None else out.data_ptr(), mask.data_ptr(), _hip.stream_ptr())
-    table = class_weight_table(weight, c, x.device)
-    if table is None:
-        st = _hip.lib.hs_upsample_ce_confusion_fwd(xp, b, c, hi, wi, ho, wo, target.data_ptr(), _EVAL_DTYPES[target.dtype], *tail)
-        _hip.check(st, 'hs_upsample_ce_confusion_fwd')
-    else:
-        st = _hip.lib.hs_upsample_ce_confusion_weighted_fwd(xp, b, c, hi, wi, ho, wo, target.data_ptr(), _EVAL_DTYPES[target.dtype], table.data_ptr(), *tail)
-        _hip.check(st, 'hs_upsample_ce_confusion_weighted_fwd')
+    tail = (int(ignore_index), loss.data_ptr(), n, 1 if per_image else 0, _hip.ptr(out), mask.data_ptr(), _hip.stream_ptr())
+    loss_launch('hs_upsample_ce_confusion_fwd', class_weight_table(weight, c, x.device),
+                xp, b, c, hi, wi, ho, wo, target.data_ptr(), _EVAL_DTYPES[target.dtype], *tail)
     return loss, out, mask
 
 
@@ -1580,10 +1557,9 @@ def overlay(masks, frames, style, out=None):
     masks = masks if masks.is_contiguous() else masks.contiguous()
     b, h, w = style.frame_size(frames)
     out = _overlay_out(out, frames)
-    st = _hip.lib.hs_overlay_fwd(masks.data_ptr(), frames.data_ptr(), _LAYOUT_CODES[style.layout], b, h, w,
-                                 _hip.dev_ptr(style.tables(frames.device), 'tables'), style.num_colors, style.ignore_index,
-                                 out.data_ptr(), _hip.stream_ptr())
-    _hip.check(st, 'hs_overlay_fwd')
+    _hip.run.hs_overlay_fwd(masks.data_ptr(), frames.data_ptr(), _LAYOUT_CODES[style.layout], b, h, w,
+                            _hip.dev_ptr(style.tables(frames.device), 'tables'), style.num_colors, style.ignore_index,
+                            out.data_ptr(), _hip.stream_ptr())
     return out
 
 
@@ -1601,10 +1577,9 @@ def upsample_overlay(x, size, frames, style, out=None):
         raise ValueError(f'the frames are on {frames.device}, the logits on {x.device}')
     out = _overlay_out(out, frames)
     mask = torch.empty(b, ho, wo, device=x.device, dtype=torch.uint8)
-    st = _hip.lib.hs_upsample_overlay_fwd(_hip.dev_ptr(x, 'x'), b, c, hi, wi, ho, wo, frames.data_ptr(), _LAYOUT_CODES[style.layout],
-                                          _hip.dev_ptr(style.tables(x.device), 'tables'), style.num_colors, style.ignore_index,
-                                          mask.data_ptr(), out.data_ptr(), _hip.stream_ptr())
-    _hip.check(st, 'hs_upsample_overlay_fwd')
+    _hip.run.hs_upsample_overlay_fwd(_hip.dev_ptr(x, 'x'), b, c, hi, wi, ho, wo, frames.data_ptr(), _LAYOUT_CODES[style.layout],
+                                     _hip.dev_ptr(style.tables(x.device), 'tables'), style.num_colors, style.ignore_index,
+                                     mask.data_ptr(), out.data_ptr(), _hip.stream_ptr())
     return mask, out
 
 
@@ -1744,11 +1719,10 @@ def frame_resize(x_u8, size, filter='bilinear', layout='hwc', view=None, norm=No
     table = _norm_table(norm, layout, x_u8.device)
     yb, ykk = resample.device_coeffs(hi, hr, filter, x_u8.device)
     xb, xkk = resample.device_coeffs(wi, wr, filter, x_u8.device)
-    st = _hip.lib.hs_frame_resize_fwd(_hip.dev_ptr(x_u8, 'x_u8', torch.uint8), _LAYOUT_CODES[layout], b, hi, wi,
-                                      yb.data_ptr(), ykk.data_ptr(), ykk.shape[1], hr, xb.data_ptr(), xkk.data_ptr(), xkk.shape[1], wr,
-                                      ho, wo, oy, ox, int(view.hflip), _fill_word(view.fill), table,
-                                      _hip.dev_ptr(out, 'out', out.dtype), _hip.stream_ptr())
-    _hip.check(st, 'hs_frame_resize_fwd')
+    _hip.run.hs_frame_resize_fwd(_hip.dev_ptr(x_u8, 'x_u8', torch.uint8), _LAYOUT_CODES[layout], b, hi, wi,
+                                 yb.data_ptr(), ykk.data_ptr(), ykk.shape[1], hr, xb.data_ptr(), xkk.data_ptr(), xkk.shape[1], wr,
+                                 ho, wo, oy, ox, int(view.hflip), _fill_word(view.fill), table,
+                                 _hip.dev_ptr(out, 'out', out.dtype), _hip.stream_ptr())
     return out
 
 
@@ -1766,10 +1740,9 @@ def label_resize(t, size, view=None, fill=255, out=None):
         raise ValueError('empty batch')
     fill = _label_fill(fill, out)
     iy, ix = resample.device_nearest(hi, hr, t.device), resample.device_nearest(wi, wr, t.device)
-    st = _hip.lib.hs_label_resize_fwd(_hip.dev_ptr(t, 'labels', t.dtype), _LABEL_DTYPES[t.dtype], b, hi, wi, iy.data_ptr(), hr, ix.data_ptr(), wr,
-                                      ho, wo, oy, ox, int(view.hflip), fill, _hip.dev_ptr(out, 'out', out.dtype), _LABEL_DTYPES[out.dtype],
-                                      _hip.stream_ptr())
-    _hip.check(st, 'hs_label_resize_fwd')
+    _hip.run.hs_label_resize_fwd(_hip.dev_ptr(t, 'labels', t.dtype), _LABEL_DTYPES[t.dtype], b, hi, wi, iy.data_ptr(), hr, ix.data_ptr(), wr,
+                                 ho, wo, oy, ox, int(view.hflip), fill, _hip.dev_ptr(out, 'out', out.dtype), _LABEL_DTYPES[out.dtype],
+                                 _hip.stream_ptr())
     return out
 
 
@@ -1835,9 +1808,8 @@ def resize_tables(params, in_hw, crop, filter, ks_max, workspace=None):
     if min(hi, wi, ho, wo, ks_max) < 1:
         raise ValueError(f'sizes must be >= 1, got {(hi, wi)} -> {(ho, wo)}, ks_max {ks_max}')
     t = _tables_over(ResizeTables, workspace, b, (hi, wi), (ho, wo), ks_max, params.device)
-    st = _hip.lib.hs_resize_tables_fwd(_hip.dev_ptr(params, 'params', torch.int32), b, hi, wi, ho, wo, code, ks_max,
-                                       t.bounds.data_ptr(), t.kk.data_ptr(), t.nearest.data_ptr(), t.status.data_ptr(), _hip.stream_ptr())
-    _hip.check(st, 'hs_resize_tables_fwd')
+    _hip.run.hs_resize_tables_fwd(_hip.dev_ptr(params, 'params', torch.int32), b, hi, wi, ho, wo, code, ks_max,
+                                  t.bounds.data_ptr(), t.kk.data_ptr(), t.nearest.data_ptr(), t.status.data_ptr(), _hip.stream_ptr())
     return t
 
 
@@ -1854,11 +1826,10 @@ def frame_resize_batch(x_u8, params, tables, layout='hwc', fill=(0, 0, 0), norm=
     fill = _fill_word(fill)
     out = _frame_out(out, b, ho, wo, layout, norm, x_u8.device)
     table = _norm_table(norm, layout, x_u8.device)
-    st = _hip.lib.hs_frame_resize_batch_fwd(_hip.dev_ptr(x_u8, 'x_u8', torch.uint8), _LAYOUT_CODES[layout], b, hi, wi,
-                                            _hip.dev_ptr(params, 'params', torch.int32), tables.bounds.data_ptr(), tables.kk.data_ptr(),
-                                            tables.status.data_ptr(), tables.ks_max, ho, wo, fill, table,
-                                            _hip.dev_ptr(out, 'out', out.dtype), _hip.stream_ptr())
-    _hip.check(st, 'hs_frame_resize_batch_fwd')
+    _hip.run.hs_frame_resize_batch_fwd(_hip.dev_ptr(x_u8, 'x_u8', torch.uint8), _LAYOUT_CODES[layout], b, hi, wi,
+                                       _hip.dev_ptr(params, 'params', torch.int32), tables.bounds.data_ptr(), tables.kk.data_ptr(),
+                                       tables.status.data_ptr(), tables.ks_max, ho, wo, fill, table,
+                                       _hip.dev_ptr(out, 'out', out.dtype), _hip.stream_ptr())
     return out
 
 
@@ -1872,10 +1843,9 @@ def label_resize_batch(t, params, tables, fill=255, out=None):
     ho, wo = tables.crop
     out = _label_out(out, (b, ho, wo), t.dtype, t.device)
     fill = _label_fill(fill, out)
-    st = _hip.lib.hs_label_resize_batch_fwd(_hip.dev_ptr(t, 'labels', t.dtype), _LABEL_DTYPES[t.dtype], b, hi, wi,
-                                            _hip.dev_ptr(params, 'params', torch.int32), tables.nearest.data_ptr(), tables.status.data_ptr(),
-                                            ho, wo, fill, _hip.dev_ptr(out, 'out', out.dtype), _LABEL_DTYPES[out.dtype], _hip.stream_ptr())
-    _hip.check(st, 'hs_label_resize_batch_fwd')
+    _hip.run.hs_label_resize_batch_fwd(_hip.dev_ptr(t, 'labels', t.dtype), _LABEL_DTYPES[t.dtype], b, hi, wi,
+                                       _hip.dev_ptr(params, 'params', torch.int32), tables.nearest.data_ptr(), tables.status.data_ptr(),
+                                       ho, wo, fill, _hip.dev_ptr(out, 'out', out.dtype), _LABEL_DTYPES[out.dtype], _hip.stream_ptr())
     return out
 
 
@@ -1906,10 +1876,9 @@ def color_jitter(x_u8, params, layout='hwc', norm=None, out=None, table=None):
     if table is None:
         table = records.to(x_u8.device)
     sums = torch.empty(b, device=x_u8.device, dtype=torch.int64) if need_mean else None
-    st = _hip.lib.hs_color_jitter_fwd(_hip.dev_ptr(x_u8, 'x_u8', torch.uint8), _LAYOUT_CODES[layout], b, h, w,
-                                      _hip.dev_ptr(table, 'table', torch.int32), None if sums is None else sums.data_ptr(), norm_table,
-                                      _hip.dev_ptr(out, 'out', out.dtype), _hip.stream_ptr())
-    _hip.check(st, 'hs_color_jitter_fwd')
+    _hip.run.hs_color_jitter_fwd(_hip.dev_ptr(x_u8, 'x_u8', torch.uint8), _LAYOUT_CODES[layout], b, h, w,
+                                 _hip.dev_ptr(table, 'table', torch.int32), None if sums is None else sums.data_ptr(), norm_table,
+                                 _hip.dev_ptr(out, 'out', out.dtype), _hip.stream_ptr())
     return out
 
 
@@ -1939,10 +1908,9 @@ def frame_rotate(x_u8, angle, layout='hwc', size=None, fill=(0, 0, 0), pad_fill=
     out = _frame_out(out, b, ho, wo, layout, norm, x_u8.device)
     norm_table = _norm_table(norm, layout, x_u8.device)
     table = table.to(x_u8.device)                              # the host-built one goes up here; the caller's is there already
-    st = _hip.lib.hs_frame_rotate_fwd(_hip.dev_ptr(x_u8, 'x_u8', torch.uint8), _LAYOUT_CODES[layout], b, h, w,
-                                      _hip.dev_ptr(table, 'table', torch.float64), ho, wo, fill, pad_fill, norm_table,
-                                      _hip.dev_ptr(out, 'out', out.dtype), _hip.stream_ptr())
-    _hip.check(st, 'hs_frame_rotate_fwd')
+    _hip.run.hs_frame_rotate_fwd(_hip.dev_ptr(x_u8, 'x_u8', torch.uint8), _LAYOUT_CODES[layout], b, h, w,
+                                 _hip.dev_ptr(table, 'table', torch.float64), ho, wo, fill, pad_fill, norm_table,
+                                 _hip.dev_ptr(out, 'out', out.dtype), _hip.stream_ptr())
     return out
 
 
@@ -1966,10 +1934,9 @@ def label_rotate(t, angle, size=None, fill=0, pad_fill=255, out=None, table=None
     fill, pad_fill = _label_fill(fill, out), _label_fill(pad_fill, out, 'pad_fill')
     table = rotate.fixed_table(h, w, angle, b) if table is None else rotate.check_table(table, b, torch.int32, t.device)
     table = table.to(t.device)                                 # the host-built one goes up here; the caller's is there already
-    st = _hip.lib.hs_label_rotate_fwd(_hip.dev_ptr(t, 'labels', t.dtype), _LABEL_DTYPES[t.dtype], b, h, w,
-                                      _hip.dev_ptr(table, 'table', torch.int32), ho, wo, fill, pad_fill,
-                                      _hip.dev_ptr(out, 'out', out.dtype), _LABEL_DTYPES[out.dtype], _hip.stream_ptr())
-    _hip.check(st, 'hs_label_rotate_fwd')
+    _hip.run.hs_label_rotate_fwd(_hip.dev_ptr(t, 'labels', t.dtype), _LABEL_DTYPES[t.dtype], b, h, w,
+                                 _hip.dev_ptr(table, 'table', torch.int32), ho, wo, fill, pad_fill,
+                                 _hip.dev_ptr(out, 'out', out.dtype), _LABEL_DTYPES[out.dtype], _hip.stream_ptr())
     return out
 
 
@@ -2040,10 +2007,9 @@ def resize_tables_ragged(params, canvas_hw, mid_hw, filter, ks_max, workspace=No
     if ks_max < 1:
         raise ValueError(f'ks_max must be >= 1, got {ks_max}')
     t = _tables_over(RaggedTables, workspace, b, (hm, wm), (hc, wc), ks_max, params.device)
-    st = _hip.lib.hs_resize_tables_ragged_fwd(_hip.dev_ptr(params, 'params', torch.int32), b, hm, wm, hc, wc, code, ks_max,
-                                              t.bounds.data_ptr(), t.kk.data_ptr(), t.nearest.data_ptr(), t.status.data_ptr(),
-                                              _hip.stream_ptr())
-    _hip.check(st, 'hs_resize_tables_ragged_fwd')
+    _hip.run.hs_resize_tables_ragged_fwd(_hip.dev_ptr(params, 'params', torch.int32), b, hm, wm, hc, wc, code, ks_max,
+                                         t.bounds.data_ptr(), t.kk.data_ptr(), t.nearest.data_ptr(), t.status.data_ptr(),
+                                         _hip.stream_ptr())
     return t
 
 
@@ -2065,11 +2031,10 @@ def color_jitter_ragged(x_u8, params, table, layout='hwc', contrast=True, out=No
     out = _out(out, x_u8.shape, torch.uint8, x_u8.device)
     if contrast:
         sums = _out(sums, (b,), torch.int64, x_u8.device)
-    st = _hip.lib.hs_color_jitter_ragged_fwd(_hip.dev_ptr(x_u8, 'canvas', torch.uint8), _LAYOUT_CODES[layout], b, hm, wm,
-                                             _hip.dev_ptr(params, 'params', torch.int32), _hip.dev_ptr(table, 'table', torch.int32),
-                                             _hip.dev_ptr(sums, 'sums', torch.int64) if contrast else None,
-                                             _hip.dev_ptr(out, 'out', torch.uint8), _hip.stream_ptr())
-    _hip.check(st, 'hs_color_jitter_ragged_fwd')
+    _hip.run.hs_color_jitter_ragged_fwd(_hip.dev_ptr(x_u8, 'canvas', torch.uint8), _LAYOUT_CODES[layout], b, hm, wm,
+                                        _hip.dev_ptr(params, 'params', torch.int32), _hip.dev_ptr(table, 'table', torch.int32),
+                                        _hip.dev_ptr(sums, 'sums', torch.int64) if contrast else None,
+                                        _hip.dev_ptr(out, 'out', torch.uint8), _hip.stream_ptr())
     return out
 
 
@@ -2084,11 +2049,10 @@ def frame_resize_ragged(x_u8, params, tables, layout='hwc', out=None):
     b = _ragged_tables(tables, params, n, x_u8.device, canvas_hw=(hm, wm))
     hc, wc = tables.mid_hw
     out = _frame_out(out, b, hc, wc, layout, None, x_u8.device)
-    st = _hip.lib.hs_frame_resize_ragged_fwd(_hip.dev_ptr(x_u8, 'canvas', torch.uint8), _LAYOUT_CODES[layout], b, hm, wm,
-                                             _hip.dev_ptr(params, 'params', torch.int32), tables.bounds.data_ptr(), tables.kk.data_ptr(),
-                                             tables.status.data_ptr(), tables.ks_max, hc, wc, _hip.dev_ptr(out, 'out', torch.uint8),
-                                             _hip.stream_ptr())
-    _hip.check(st, 'hs_frame_resize_ragged_fwd')
+    _hip.run.hs_frame_resize_ragged_fwd(_hip.dev_ptr(x_u8, 'canvas', torch.uint8), _LAYOUT_CODES[layout], b, hm, wm,
+                                        _hip.dev_ptr(params, 'params', torch.int32), tables.bounds.data_ptr(), tables.kk.data_ptr(),
+                                        tables.status.data_ptr(), tables.ks_max, hc, wc, _hip.dev_ptr(out, 'out', torch.uint8),
+                                        _hip.stream_ptr())
     return out
 
 
@@ -2101,10 +2065,9 @@ def label_resize_ragged(t, params, tables, out=None):
     b = _ragged_tables(tables, params, n, t.device, canvas_hw=(hm, wm))
     hc, wc = tables.mid_hw
     out = _out(out, (b, hc, wc), torch.uint8, t.device)
-    st = _hip.lib.hs_label_resize_ragged_fwd(_hip.dev_ptr(t, 'labels', t.dtype), _LABEL_DTYPES[t.dtype], b, hm, wm,
-                                             _hip.dev_ptr(params, 'params', torch.int32), tables.nearest.data_ptr(), tables.status.data_ptr(),
-                                             hc, wc, _hip.dev_ptr(out, 'out', torch.uint8), _hip.stream_ptr())
-    _hip.check(st, 'hs_label_resize_ragged_fwd')
+    _hip.run.hs_label_resize_ragged_fwd(_hip.dev_ptr(t, 'labels', t.dtype), _LABEL_DTYPES[t.dtype], b, hm, wm,
+                                        _hip.dev_ptr(params, 'params', torch.int32), tables.nearest.data_ptr(), tables.status.data_ptr(),
+                                        hc, wc, _hip.dev_ptr(out, 'out', torch.uint8), _hip.stream_ptr())
     return out
 
 
@@ -2124,11 +2087,10 @@ def frame_rotate_ragged(x_u8, params, tables, matrices, layout='hwc', size=None,
     rotate.check_table(matrices, b, torch.float64, x_u8.device)
     out = _frame_out(out, b, ho, wo, layout, norm, x_u8.device)
     table = _norm_table(norm, layout, x_u8.device)
-    st = _hip.lib.hs_frame_rotate_ragged_fwd(_hip.dev_ptr(x_u8, 'canvas', torch.uint8), _LAYOUT_CODES[layout], b, hc, wc,
-                                             _hip.dev_ptr(params, 'params', torch.int32), tables.status.data_ptr(),
-                                             _hip.dev_ptr(matrices, 'matrices', torch.float64), ho, wo, fill, pad_fill,
-                                             table, _hip.dev_ptr(out, 'out', out.dtype), _hip.stream_ptr())
-    _hip.check(st, 'hs_frame_rotate_ragged_fwd')
+    _hip.run.hs_frame_rotate_ragged_fwd(_hip.dev_ptr(x_u8, 'canvas', torch.uint8), _LAYOUT_CODES[layout], b, hc, wc,
+                                        _hip.dev_ptr(params, 'params', torch.int32), tables.status.data_ptr(),
+                                        _hip.dev_ptr(matrices, 'matrices', torch.float64), ho, wo, fill, pad_fill,
+                                        table, _hip.dev_ptr(out, 'out', out.dtype), _hip.stream_ptr())
     return out
 
 
@@ -2145,10 +2107,9 @@ def label_rotate_ragged(t, params, tables, fixed, size=None, fill=0, pad_fill=25
     rotate.check_table(fixed, b, torch.int32, t.device)
     out = _label_out(out, (b, ho, wo), torch.int64, t.device)
     fill, pad_fill = _label_fill(fill, out), _label_fill(pad_fill, out, 'pad_fill')
-    st = _hip.lib.hs_label_rotate_ragged_fwd(_hip.dev_ptr(t, 'labels', torch.uint8), b, hc, wc, _hip.dev_ptr(params, 'params', torch.int32),
-                                             tables.status.data_ptr(), _hip.dev_ptr(fixed, 'fixed', torch.int32), ho, wo, fill, pad_fill,
-                                             _hip.dev_ptr(out, 'out', out.dtype), _LABEL_DTYPES[out.dtype], _hip.stream_ptr())
-    _hip.check(st, 'hs_label_rotate_ragged_fwd')
+    _hip.run.hs_label_rotate_ragged_fwd(_hip.dev_ptr(t, 'labels', torch.uint8), b, hc, wc, _hip.dev_ptr(params, 'params', torch.int32),
+                                        tables.status.data_ptr(), _hip.dev_ptr(fixed, 'fixed', torch.int32), ho, wo, fill, pad_fill,
+                                        _hip.dev_ptr(out, 'out', out.dtype), _LABEL_DTYPES[out.dtype], _hip.stream_ptr())
     return out
 
 

@@ -283,20 +283,17 @@ class Adam(torch.optim.Optimizer):
                 if lr_dev is not None and (lr_dev.dtype != torch.float32 or lr_dev.numel() != 1):
                     raise NotImplementedError('hyperseg_amd.training.Adam: a device learning rate must be one fp32 element')
                 args = (arr(chunk), arr(grads), arr([self.state[p]['exp_avg'] for p in chunk]), arr([self.state[p]['exp_avg_sq'] for p in chunk]),
-                        numel, n, lr_dev.data_ptr() if lr_dev is not None else None, 0.0 if lr_dev is not None else float(lr),
+                        numel, n, _hip.ptr(lr_dev), 0.0 if lr_dev is not None else float(lr),
                         float(group['betas'][0]), float(group['betas'][1]), float(group['eps']), float(group['weight_decay']),
                         int(group['decoupled_weight_decay']), int(group['maximize']), held[1].data_ptr())
                 if found_inf is None:
                     with _hip.device_scope(dev):
-                        status = _hip.lib.hs_adam_step(*args, _hip.stream_ptr(dev))
-                    _hip.check(status, 'hs_adam_step')
+                        _hip.run.hs_adam_step(*args, _hip.stream_ptr(dev))
                     continue
                 inf_dev = _amp_word(found_inf, dev)
                 scale_dev = _amp_word(grad_scale, dev) if grad_scale is not None else None
                 with _hip.device_scope(dev):
-                    status = _hip.lib.hs_adam_step_amp(*args, scale_dev.data_ptr() if scale_dev is not None else None, inf_dev.data_ptr(),
-                                                       _hip.stream_ptr(dev))
-                _hip.check(status, 'hs_adam_step_amp')
+                    _hip.run.hs_adam_step_amp(*args, _hip.ptr(scale_dev), inf_dev.data_ptr(), _hip.stream_ptr(dev))
                 if grad_scale is not None:
                     for p, g in zip(chunk, grads):
                         if g is not p.grad:                                        # a non-contiguous gradient: the unscaled copy goes back

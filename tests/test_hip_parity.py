@@ -437,6 +437,44 @@ def test_errors_are_loud(HF, dev):
     assert y.requires_grad and y.grad_fn is not None
 
 
+def test_checked_entry_reports_its_own_name(HF, dev):
+    """A launch the wrapper makes through the checked namespace (``_hip.run``) raises as ``_hip.check`` did: the entry's name, then the
+    status' text.  A 6 x 6 map does not tile into a 4 x 4 grid -- a host-side refusal (HS_ERR_GRID), nothing is launched."""
+    from hyperseg_amd._hip import HipLibraryError
+    x = torch.randn(1, 4, 6, 6, generator=G(1030)).to(dev)
+    bank = torch.randn(16, 8, generator=G(1031)).to(dev)
+    with pytest.raises(HipLibraryError, match='hs_patch_conv_fwd: feature map does not tile'):
+        HF.patch_conv(x, (4, 4), bank, 2, 1, 0, 'zeros', 1)
+
+
+def test_coscheduled_refusal_falls_through_to_the_plain_launch(HF, dev, monkeypatch):
+    """hs_patch_conv_s2w_fwd is called RAW: its HS_ERR_UNSUPPORTED (-3; riders that cannot take the blocked form -- 54 patches per frame,
+    test_coscheduled_banks_heterogeneous_launch's last raw case) is a route decision, not an error -- nothing raises, the block carried
+    nothing, and hs_patch_conv_fwd (checked) made the launch."""
+    from hyperseg_amd import _hip
+    g = torch.Generator().manual_seed(3)
+    xs = torch.randn(2, 6, 9 * 4, 6 * 4, generator=g).to(dev)
+    sig = torch.relu(torch.randn(2, 64, 9, 6, generator=g)).to(dev)
+    lay = [dict(wsw_t=torch.randn(8, 100, generator=g).to(dev), signal_index=8, signal_channels=32, groups=4, rows=98)]
+    bank = torch.randn(2 * 9 * 6, 32, generator=g).to(dev)
+    want = HF.patch_conv(xs, (9, 6), bank, 5, 1, 0, 'zeros', 1)
+    seen = []
+
+    def recording(space, name):
+        real = getattr(space, name)
+
+        def call(*a):
+            seen.append((name, real(*a)))
+            return seen[-1][1]
+        monkeypatch.setattr(space, name, call)
+    recording(_hip.lib, 'hs_patch_conv_s2w_fwd')
+    recording(_hip.run, 'hs_patch_conv_fwd')
+    with HF.CoScheduledBanks(sig, lay) as co:
+        y = HF.patch_conv(xs, (9, 6), bank, 5, 1, 0, 'zeros', 1)
+    assert seen == [('hs_patch_conv_s2w_fwd', -3), ('hs_patch_conv_fwd', 0)]
+    assert not co.carried and torch.equal(y, want)
+
+
 @pytest.mark.parametrize('shape,size', [((2, 19, 16, 32), (32, 64)), ((1, 19, 64, 128), (128, 256)), ((1, 7, 9, 13), (18, 26)),
                                         ((2, 21, 11, 14), (33, 31)), ((1, 5, 12, 20), (12, 20)), ((1, 1, 8, 8), (16, 16)),
                                         ((1, 256, 4, 6), (8, 12))])

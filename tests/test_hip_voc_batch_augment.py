@@ -149,22 +149,25 @@ SUMS_ARG = {'hs_color_jitter_fwd': 6, 'hs_color_jitter_ragged_fwd': 7}       # t
 
 
 def count_launches(fn):
-    """Launches made through the COUNTED library entries while ``fn`` runs, counted at the ctypes boundary: every entry makes one,
-    the two jitter entries three when they are handed a sums workspace (include/hyperseg_hip.h)."""
+    """Launches made through the COUNTED library entries while ``fn`` runs, counted at the ctypes boundary -- in both namespaces of the
+    binding, the checked entries the wrappers call (``_hip.run``) and the raw ones (``_hip.lib``): every entry makes one, the two jitter
+    entries three when they are handed a sums workspace (include/hyperseg_hip.h)."""
     from hyperseg_amd import _hip
-    counts, saved = {}, {}
-    for name in COUNTED:
-        saved[name] = real = getattr(_hip.lib, name)
+    counts, saved = {}, []
+    for space in (_hip.run, _hip.lib):
+        for name in COUNTED:
+            real = getattr(space, name)
+            saved.append((space, name, real))
 
-        def counting(*a, _real=real, _name=name):
-            counts[_name] = counts.get(_name, 0) + (3 if _name in SUMS_ARG and a[SUMS_ARG[_name]] is not None else 1)
-            return _real(*a)
-        setattr(_hip.lib, name, counting)
+            def counting(*a, _real=real, _name=name):
+                counts[_name] = counts.get(_name, 0) + (3 if _name in SUMS_ARG and a[SUMS_ARG[_name]] is not None else 1)
+                return _real(*a)
+            setattr(space, name, counting)
     try:
         fn()
     finally:
-        for name, real in saved.items():
-            setattr(_hip.lib, name, real)
+        for space, name, real in saved:
+            setattr(space, name, real)
     return counts
 
 

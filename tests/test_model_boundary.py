@@ -438,6 +438,7 @@ def test_c_abi_exports_match_header():
     """The in-tree shared library loads without a GPU and exports every entry point include/hyperseg_hip.h declares (and the
     ctypes binding knows exactly that set); no compute call is made."""
     import ctypes
+    import inspect
     import os
     import re
     from conftest import REPO
@@ -453,6 +454,40 @@ def test_c_abi_exports_match_header():
     assert lib.hs_version() == 1
     lib.hs_build_info.restype = ctypes.c_char_p
     assert b'gfx950' in lib.hs_build_info()
+    # ONE list: the signature table holds every declared name exactly once (a repeated key of a dict display wins silently, so the source
+    # is counted), and EXPORTS is its keys
+    keys = re.findall(r"^    '(hs_[a-z0-9_]+)': \(", inspect.getsource(_hip), flags=re.M)
+    assert sorted(keys) == sorted(declared) and _hip.EXPORTS == list(_hip.SIGNATURES) == keys
+    # every entry that returns a status has a checked twin -- its own function object, the same argument types -- and no other entry has
+    for name, (argtypes, returns) in _hip.SIGNATURES.items():
+        raw, checked = getattr(_hip.lib, name), getattr(_hip.run, name, None)
+        assert raw.errcheck is None, name
+        if returns is _hip.STATUS:
+            assert checked is not None and checked is not raw and checked.argtypes == raw.argtypes == argtypes, name
+            assert checked.restype is raw.restype is ctypes.c_int and checked.errcheck is _hip._raise_unless_ok, name
+        else:
+            assert checked is None and raw.restype is returns, name
+    assert vars(_hip.run).keys() == {n for n, (_, r) in _hip.SIGNATURES.items() if r is _hip.STATUS}
+
+
+def test_checked_entry_raises_where_the_raw_entry_returns_the_status():
+    """The two namespaces of the binding on an entry that is host logic only (hs_ir_tile_map; mode 3 does not exist): ``lib`` returns the
+    negative status as it is, ``run`` raises HipLibraryError('<entry>: <reason>') with ``_hip.check``'s text -- and returns 0 for a call
+    that succeeds."""
+    import ctypes as C
+    from hyperseg_amd import _hip
+    nt, nt3 = C.c_int32(0), C.c_int32(0)
+    args = (8, 3, 8, C.byref(nt), C.byref(nt3), None, 0)
+    st = _hip.lib.hs_ir_tile_map(*args)
+    assert st < 0 and st in _hip._STATUS
+    with pytest.raises(_hip.HipLibraryError) as e:
+        _hip.run.hs_ir_tile_map(*args)
+    assert str(e.value) == f'hs_ir_tile_map: {_hip._STATUS[st]}'
+    with pytest.raises(_hip.HipLibraryError) as e:
+        _hip.check(st, 'hs_ir_tile_map')
+    assert str(e.value) == f'hs_ir_tile_map: {_hip._STATUS[st]}'
+    good = (8, 0, 8, C.byref(nt), C.byref(nt3), None, 0)
+    assert _hip.lib.hs_ir_tile_map(*good) == 0 and _hip.run.hs_ir_tile_map(*good) == 0 and nt.value > 0
 
 
 def test_k1_chain_plan_on_the_host():

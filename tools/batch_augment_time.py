@@ -132,8 +132,8 @@ def main():
     want, got = route_a(p0), route_c(p0)
     same = torch.equal(want[0], got[0]) and torch.equal(want[1], got[1])
     lines.append(f'(c) equals (a), image and label, byte for byte: {same}; status all zero: {not bool(aug.status.any())}')
-    counts_a = count_launches(_hip.lib, lambda: route_a(draw()))
-    counts_c = count_launches(_hip.lib, lambda: route_c(draw()))
+    counts_a = count_launches(_hip.run, lambda: route_a(draw()))
+    counts_c = count_launches(_hip.run, lambda: route_c(draw()))
     lines.append(f'library launches per batch, (a): {sum(counts_a.values())} {counts_a};  (c): {sum(counts_c.values())} {counts_c}')
 
     fixed = (0.75, (0, 384), False)                               # tools/color_jitter_time.py's (c): the README's 0.636 ms case

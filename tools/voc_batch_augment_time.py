@@ -107,8 +107,8 @@ def main():
         same = same and eq
         lines.append(f'--- {tag}')
         lines.append(f'(b) equals (a) on every sample, image and label, byte for byte: {eq}; status all zero: {not bool(aug.status.any())}')
-        counts_a = count_launches(_hip.lib, lambda: route_a(draw(jitter)))
-        counts_b = count_launches(_hip.lib, lambda: route_b(draw(jitter)))
+        counts_a = count_launches(_hip.run, lambda: route_a(draw(jitter)))
+        counts_b = count_launches(_hip.run, lambda: route_b(draw(jitter)))
         counts_b_all[jitter] = sum(counts_b.values())
         lines.append(f'library launches per batch, (a): {sum(counts_a.values())} {counts_a};  (b): {sum(counts_b.values())} {counts_b}')
 
