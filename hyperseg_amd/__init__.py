@@ -15,4 +15,7 @@ def __getattr__(name):
     if name == 'Overlay':
         from .utils.inference import Overlay
         return Overlay
+    if name == 'LabelCodec':
+        from .utils.labels import LabelCodec
+        return LabelCodec
     raise AttributeError(f'module {__name__!r} has no attribute {name!r}')

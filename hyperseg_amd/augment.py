@@ -38,7 +38,12 @@ def _outputs(b, h, w, device):
     return torch.empty(b, 3, h, w, dtype=torch.float32, device=device), torch.empty(b, h, w, dtype=torch.int64, device=device)
 
 
-def _crop_cpu(frames_u8, labels, sizes, offsets, flips, jitter, crop, norm, filter, fill, lbl_fill):
+def _labels_shape(label_codec, b, h, w):
+    """The shape of the labels of (B, H, W) frames: raw labels have their codec's (a colour image has three bytes per pixel)."""
+    return (b, h, w) if label_codec is None else label_codec.raw_shape(b, h, w)
+
+
+def _crop_cpu(frames_u8, labels, sizes, offsets, flips, jitter, crop, norm, filter, fill, lbl_fill, label_codec=None):
     """The crop chain on CPU tensors for given resized ``sizes`` (Hr, Wr), ``offsets`` and ``flips`` per sample (``utils.resample``,
     ``utils.jitter``): what :func:`device_augment` and :class:`BatchAugment` return for them."""
     from .utils import resample
@@ -49,14 +54,14 @@ def _crop_cpu(frames_u8, labels, sizes, offsets, flips, jitter, crop, norm, filt
     for i, (size, offset, flip) in enumerate(zip(sizes, offsets, flips)):
         view = resample.ResizeView((ch, cw), tuple(int(o) for o in offset), bool(flip), fill)
         dst[i:i + 1] = resample.frame_resize_cpu(frames_u8[i:i + 1], size, filter, norm.layout, view=view, norm=dst_norm)
-        label[i:i + 1] = resample.label_resize_cpu(labels[i:i + 1], size, view=view, fill=lbl_fill, out_dtype=torch.int64)
+        label[i:i + 1] = resample.label_resize_cpu(labels[i:i + 1], size, view=view, fill=lbl_fill, out_dtype=torch.int64, codec=label_codec)
     if jitter is not None:
         from .utils import jitter as J
         dst = J.color_jitter_cpu(dst, J.per_sample(jitter, b), norm.layout, norm=norm)
     return dst, label
 
 
-def device_augment(frames_u8, labels, scale, crop, offset, hflip, norm, lbl_fill=255, fill=(0, 0, 0), jitter=None):
+def device_augment(frames_u8, labels, scale, crop, offset, hflip, norm, lbl_fill=255, fill=(0, 0, 0), jitter=None, label_codec=None):
     """The reference's train-time chain RandomResize -> RandomCrop(pad_if_needed) -> RandomHorizontalFlip -> ToTensor -> Normalize
     (hyperseg/datasets/seg_transforms.py:224-334) for GIVEN parameters, on the device: per sample one ``functional.frame_resize``
     launch (bicubic, Pillow's bytes, looked up in ``norm``'s table) and one ``functional.label_resize`` launch (nearest), each
@@ -73,10 +78,15 @@ def device_augment(frames_u8, labels, scale, crop, offset, hflip, norm, lbl_fill
     end of the image chain, as in the reference's Cityscapes HyperSeg-S config -- the resize launch then writes the uint8 crop (padding
     included: the contrast mean sees it, as it does on the padded PIL image) and ``functional.color_jitter`` produces the normalised
     image of the whole batch, Pillow's bytes through ``norm``'s table (``utils.jitter.color_jitter_cpu`` for CPU tensors).  ``None``:
-    nothing changes."""
+    nothing changes.
+
+    ``label_codec`` (a ``LabelCodec``): ``labels`` are RAW -- ids (B, H, W) or a colour image uint8 (B, H, W, 3) -- and the label launch
+    encodes the pixel it gathers (``functional.label_resize(codec=)``): the same launches, no host pass.  ``lbl_fill`` is a class
+    value and is not encoded."""
     b, h, w = norm.frame_size(frames_u8)
-    if not isinstance(labels, torch.Tensor) or tuple(labels.shape) != (b, h, w):
-        raise ValueError(f'labels must be (B, H, W) = {(b, h, w)}, got {tuple(getattr(labels, "shape", ()))}')
+    want = _labels_shape(label_codec, b, h, w)
+    if not isinstance(labels, torch.Tensor) or tuple(labels.shape) != want:
+        raise ValueError(f'labels must be {"(B, H, W)" if len(want) == 3 else "(B, H, W, 3)"} = {want}, got {tuple(getattr(labels, "shape", ()))}')
     ch, cw = (int(s) for s in crop)
     sizes = [_resized((h, w), s) for s in _per_sample(scale, b, 'scale')]
     offsets, flips = _per_sample(offset, b, 'offset', pair=True), _per_sample(hflip, b, 'hflip')
@@ -85,7 +95,7 @@ def device_augment(frames_u8, labels, scale, crop, offset, hflip, norm, lbl_fill
         jitter = J.per_sample(jitter, b)
     frames_u8, labels = frames_u8.contiguous(), labels.contiguous()
     if not frames_u8.is_cuda:
-        return _crop_cpu(frames_u8, labels, sizes, offsets, flips, jitter, (ch, cw), norm, 'bicubic', fill, lbl_fill)
+        return _crop_cpu(frames_u8, labels, sizes, offsets, flips, jitter, (ch, cw), norm, 'bicubic', fill, lbl_fill, label_codec)
     from . import functional as HF
     from .utils import resample
     image, label = _outputs(b, ch, cw, frames_u8.device)
@@ -96,7 +106,7 @@ def device_augment(frames_u8, labels, scale, crop, offset, hflip, norm, lbl_fill
     for i in range(b):
         view = resample.ResizeView((ch, cw), tuple(int(o) for o in offsets[i]), bool(flips[i]), fill)
         HF.frame_resize(frames_u8[i:i + 1], sizes[i], 'bicubic', norm.layout, view=view, norm=dst_norm, out=dst[i:i + 1])
-        HF.label_resize(labels[i:i + 1], sizes[i], view=view, fill=lbl_fill, out=label[i:i + 1])
+        HF.label_resize(labels[i:i + 1], sizes[i], view=view, fill=lbl_fill, out=label[i:i + 1], codec=label_codec)
     if jitter is not None:
         HF.color_jitter(dst, jitter, norm.layout, norm=norm, out=image)
     return image, label
@@ -159,10 +169,15 @@ class BatchAugment:
     ``scale_range``: (lo, hi) of the scales that will be asked for -- ``lo`` sizes the tables' rows (``utils.resample.ks_for``);
     ``filter``: the frames' filter (``device_augment`` is 'bicubic'); ``lbl_fill`` / ``fill``: the padding; ``batch``: the batch size, or
     None = the first call's.  The object owns the workspace, the ``params`` tensor (int32 (B, 6) = Hr, Wr, oy, ox, hflip, reserved) and a
-    pinned staging buffer, all made at the first GPU call.  One object serves one stream at a time."""
+    pinned staging buffer, all made at the first GPU call.  One object serves one stream at a time.  ``label_codec`` (a ``LabelCodec``):
+    the labels are RAW, as ``device_augment(label_codec=)`` takes them, and the label launch encodes them -- still three launches."""
 
-    def __init__(self, in_hw, crop, norm, scale_range, filter='bicubic', lbl_fill=255, fill=(0, 0, 0), batch=None):
+    def __init__(self, in_hw, crop, norm, scale_range, filter='bicubic', lbl_fill=255, fill=(0, 0, 0), batch=None, label_codec=None):
         from .utils import resample
+        from .utils.labels import LabelCodec
+        if label_codec is not None and not isinstance(label_codec, LabelCodec):
+            raise ValueError(f'label_codec must be a hyperseg_amd.LabelCodec or None, got {type(label_codec).__name__}')
+        self.label_codec = label_codec
         self.in_hw = tuple(int(s) for s in in_hw)
         self.crop = tuple(int(s) for s in crop)
         if len(self.in_hw) != 2 or len(self.crop) != 2 or min(self.in_hw + self.crop) < 1:
@@ -196,8 +211,10 @@ class BatchAugment:
         b, h, w = self.norm.frame_size(frames_u8)
         if (h, w) != self.in_hw:
             raise ValueError(f'frames are {(h, w)}, this BatchAugment was made for {self.in_hw}')
-        if not isinstance(labels, torch.Tensor) or tuple(labels.shape) != (b, h, w) or labels.device != frames_u8.device:
-            raise ValueError(f'labels must be (B, H, W) = {(b, h, w)} on {frames_u8.device}, got {tuple(getattr(labels, "shape", ()))}')
+        want = _labels_shape(self.label_codec, b, h, w)
+        if not isinstance(labels, torch.Tensor) or tuple(labels.shape) != want or labels.device != frames_u8.device:
+            raise ValueError(f'labels must be {"(B, H, W)" if len(want) == 3 else "(B, H, W, 3)"} = {want} on {frames_u8.device}, got '
+                             f'{tuple(getattr(labels, "shape", ()))}')
         return self._dev.latch(b)
 
     def _on(self, device):
@@ -205,6 +222,8 @@ class BatchAugment:
         if self._dev.on(device, HF.RESIZE_PARAM_WORDS, HF.ResizeTables, self.in_hw, self.crop, self.ks_max):
             self.params = self._dev.buffer.view(self.batch, HF.RESIZE_PARAM_WORDS)
             self.norm.table(device)
+            if self.label_codec is not None:
+                self.label_codec.device_words(device)
 
     def rows(self, scale, offset, hflip, batch=None):
         """The ``params`` rows of given augmentation parameters (each one value or a sequence of B, as ``device_augment``'s): a CPU int32
@@ -221,13 +240,13 @@ class BatchAugment:
     def _cpu(self, frames_u8, labels, rows, jitter):
         rows = rows.tolist()
         return _crop_cpu(frames_u8, labels, [r[:2] for r in rows], [r[2:4] for r in rows], [r[4] for r in rows], jitter, self.crop,
-                         self.norm, self.filter, self.fill, self.lbl_fill)
+                         self.norm, self.filter, self.fill, self.lbl_fill, self.label_codec)
 
     def _launch(self, frames_u8, labels, params, dst, dst_norm, label):
         from . import functional as HF
         tables = HF.resize_tables(params, self.in_hw, self.crop, self.filter, self.ks_max, workspace=self.tables.workspace)
         HF.frame_resize_batch(frames_u8, params, tables, self.norm.layout, fill=self.fill, norm=dst_norm, out=dst)
-        HF.label_resize_batch(labels, params, tables, fill=self.lbl_fill, out=label)
+        HF.label_resize_batch(labels, params, tables, fill=self.lbl_fill, out=label, codec=self.label_codec)
 
     def run(self, frames_u8, labels, params=None, out=None):
         """The three launches over whatever ``self.params`` (or the given device tensor of that shape) holds when they RUN: no host

@@ -23,6 +23,7 @@
 #include "hs_common.h"
 #include "hs_ingest.h"
 #include "hs_resample_px.h"
+#include "hs_label_codec.h"
 
 namespace hs {
 
@@ -84,11 +85,16 @@ static void launch_frame_resize(const ResizeArgs& a, dim3 grid, hipStream_t s) {
     else hipLaunchKernelGGL((frame_resize_kernel<HWC, NORM, false>), grid, block, 0, s, a);
 }
 
-// labels: a gather through the two nearest tables; one thread per output pixel
-template <typename TI, typename TO>
+// labels: a gather through the two nearest tables; one thread per output pixel.  CODEC (hs_label_codec.h): the source pixel is a raw
+// label -- an id, or 3 colour bytes -- and is encoded on the way; the fill is stored as given (the reference pads after its dataset
+// has encoded, with a class value)
+template <typename TI, typename TO, int CODEC, typename... CA>
 __global__ __launch_bounds__(256)
 void label_resize_kernel(const TI* __restrict__ x, const int32_t* __restrict__ iy, const int32_t* __restrict__ ix, TO* __restrict__ y,
-                         int Hi, int Wi, int Hr, int Wr, int Ho, int Wo, int oy, int ox, int hflip, int fill) {
+                         int Hi, int Wi, int Hr, int Wr, int Ho, int Wo, int oy, int ox, int hflip, int fill, CA... ca) {
+    __shared__ uint32_t codec[codec_lds_words<CODEC>()];
+    const auto c = codec_args(ca...);
+    codec_stage<CODEC>(codec, c, (int)threadIdx.x);
     const long item = (long)blockIdx.x * 256 + threadIdx.x;
     if (item >= (long)Ho * Wo) return;
     const int yy = (int)(item / Wo), xx = (int)(item - (long)yy * Wo);
@@ -97,7 +103,8 @@ void label_resize_kernel(const TI* __restrict__ x, const int32_t* __restrict__ i
     TO v = (TO)fill;
     if (ry >= 0 && ry < Hr && rx >= 0 && rx < Wr) {
         const int sy = min(max(iy[ry], 0), Hi - 1), sx = min(max(ix[rx], 0), Wi - 1);
-        v = (TO)x[(b * Hi + sy) * (size_t)Wi + sx];
+        if constexpr (CODEC == CODEC_NONE) v = (TO)x[(b * Hi + sy) * (size_t)Wi + sx];
+        else v = (TO)codec_gather<CODEC>(x, (b * Hi + sy) * (size_t)Wi + sx, codec, c);
     }
     y[b * (size_t)Ho * Wo + (size_t)item] = v;
 }
@@ -133,25 +140,61 @@ extern "C" int hs_frame_resize_fwd(const uint8_t* x, int32_t layout, int32_t bat
     return launch_status();
 }
 
+struct LabelResizeArgs {
+    const void* x; const int32_t* iy; const int32_t* ix; void* y;
+    int in_dtype, out_dtype, batch, Hi, Wi, Hr, Wr, Ho, Wo, oy, ox, hflip, fill;
+};
+
+static int label_resize_checks(const LabelResizeArgs& a) {
+    if (!a.x || !a.y || !a.iy || !a.ix) return HS_ERR_BAD_ARG;
+    if (a.batch <= 0 || a.Hi <= 0 || a.Wi <= 0 || a.Hr <= 0 || a.Wr <= 0 || a.Ho <= 0 || a.Wo <= 0) return HS_ERR_BAD_ARG;
+    if ((a.in_dtype != HS_EVAL_U8 && a.in_dtype != HS_EVAL_I64) || (a.out_dtype != HS_EVAL_U8 && a.out_dtype != HS_EVAL_I64)) return HS_ERR_BAD_ARG;
+    if (a.batch > 65535 || !resize_dims_ok(a.Hi, a.Wi, a.Hr, a.Wr, a.Ho, a.Wo)) return HS_ERR_UNSUPPORTED;
+    if (a.oy < -RS_MAX_DIM || a.oy > RS_MAX_DIM || a.ox < -RS_MAX_DIM || a.ox > RS_MAX_DIM) return HS_ERR_UNSUPPORTED;
+    if (((long)a.Ho * a.Wo + 255) / 256 > 0x7fffffffL) return HS_ERR_UNSUPPORTED;
+    return HS_OK;
+}
+
+template <typename TI, typename TO, int CODEC, typename... CA>
+static void launch_label_resize(const LabelResizeArgs& a, hipStream_t s, CA... ca) {
+    const dim3 grid((unsigned)(((long)a.Ho * a.Wo + 255) / 256), (unsigned)a.batch), block(256);
+    hipLaunchKernelGGL((label_resize_kernel<TI, TO, CODEC, CA...>), grid, block, 0, s, static_cast<const TI*>(a.x), a.iy, a.ix,
+                       static_cast<TO*>(a.y), a.Hi, a.Wi, a.Hr, a.Wr, a.Ho, a.Wo, a.oy, a.ox, a.hflip, a.fill, ca...);
+}
+
+// the storage types of a checked launch; a colour image is bytes
+template <int CODEC, typename... CA>
+static void label_resize_typed(const LabelResizeArgs& a, hipStream_t s, CA... ca) {
+    const bool u8_out = a.out_dtype == HS_EVAL_U8;
+    if (CODEC == CODEC_COLORS || a.in_dtype == HS_EVAL_U8) {
+        if (u8_out) launch_label_resize<uint8_t, uint8_t, CODEC>(a, s, ca...);
+        else launch_label_resize<uint8_t, int64_t, CODEC>(a, s, ca...);
+    } else if constexpr (CODEC != CODEC_COLORS) {
+        if (u8_out) launch_label_resize<int64_t, uint8_t, CODEC>(a, s, ca...);
+        else launch_label_resize<int64_t, int64_t, CODEC>(a, s, ca...);
+    }
+}
+
 extern "C" int hs_label_resize_fwd(const void* x, int32_t in_dtype, int32_t batch, int32_t Hi, int32_t Wi,
                                    const int32_t* y_index, int32_t Hr, const int32_t* x_index, int32_t Wr,
                                    int32_t Ho, int32_t Wo, int32_t oy, int32_t ox, int32_t hflip, int32_t fill,
                                    void* y, int32_t out_dtype, void* stream) {
-    if (!x || !y || !y_index || !x_index) return HS_ERR_BAD_ARG;
-    if (batch <= 0 || Hi <= 0 || Wi <= 0 || Hr <= 0 || Wr <= 0 || Ho <= 0 || Wo <= 0) return HS_ERR_BAD_ARG;
-    if ((in_dtype != HS_EVAL_U8 && in_dtype != HS_EVAL_I64) || (out_dtype != HS_EVAL_U8 && out_dtype != HS_EVAL_I64)) return HS_ERR_BAD_ARG;
-    if (batch > 65535 || !resize_dims_ok(Hi, Wi, Hr, Wr, Ho, Wo)) return HS_ERR_UNSUPPORTED;
-    if (oy < -RS_MAX_DIM || oy > RS_MAX_DIM || ox < -RS_MAX_DIM || ox > RS_MAX_DIM) return HS_ERR_UNSUPPORTED;
-    const long blocks = ((long)Ho * Wo + 255) / 256;
-    if (blocks > 0x7fffffffL) return HS_ERR_UNSUPPORTED;
-    const dim3 grid((unsigned)blocks, (unsigned)batch), block(256);
-    hipStream_t s = (hipStream_t)stream;
-#define HS_LABEL_LAUNCH(TI, TO) hipLaunchKernelGGL((label_resize_kernel<TI, TO>), grid, block, 0, s, static_cast<const TI*>(x), y_index, \
-                                                   x_index, static_cast<TO*>(y), Hi, Wi, Hr, Wr, Ho, Wo, oy, ox, (int)(hflip != 0), fill)
-    if (in_dtype == HS_EVAL_U8 && out_dtype == HS_EVAL_U8) HS_LABEL_LAUNCH(uint8_t, uint8_t);
-    else if (in_dtype == HS_EVAL_U8) HS_LABEL_LAUNCH(uint8_t, int64_t);
-    else if (out_dtype == HS_EVAL_U8) HS_LABEL_LAUNCH(int64_t, uint8_t);
-    else HS_LABEL_LAUNCH(int64_t, int64_t);
-#undef HS_LABEL_LAUNCH
+    const LabelResizeArgs a{x, y_index, x_index, y, in_dtype, out_dtype, batch, Hi, Wi, Hr, Wr, Ho, Wo, oy, ox, (int)(hflip != 0), fill};
+    if (const int st = label_resize_checks(a)) return st;
+    label_resize_typed<CODEC_NONE>(a, (hipStream_t)stream);
     return launch_status();
 }
+
+extern "C" int hs_label_resize_coded_fwd(const void* x, int32_t in_dtype, int32_t batch, int32_t Hi, int32_t Wi,
+                                         const int32_t* y_index, int32_t Hr, const int32_t* x_index, int32_t Wr,
+                                         int32_t Ho, int32_t Wo, int32_t oy, int32_t ox, int32_t hflip, int32_t fill,
+                                         const int32_t* codec_words, int32_t codec_kind, int32_t n, int32_t unmatched,
+                                         void* y, int32_t out_dtype, void* stream) {
+    const LabelResizeArgs a{x, y_index, x_index, y, in_dtype, out_dtype, batch, Hi, Wi, Hr, Wr, Ho, Wo, oy, ox, (int)(hflip != 0), fill};
+    if (const int st = label_resize_checks(a)) return st;
+    if (const int st = codec_check(codec_words, codec_kind, in_dtype, n, unmatched)) return st;
+    if (codec_kind == HS_CODEC_COLORS) label_resize_typed<CODEC_COLORS>(a, (hipStream_t)stream, codec_words, (int)n, (int)unmatched);
+    else label_resize_typed<CODEC_TABLE>(a, (hipStream_t)stream, codec_words, (int)n, (int)unmatched);
+    return launch_status();
+}
+

@@ -29,6 +29,7 @@
 #include "hs_ingest.h"
 #include "hs_resample_px.h"
 #include "hs_resample_tables.h"
+#include "hs_label_codec.h"
 
 namespace hs {
 
@@ -163,11 +164,16 @@ void frame_resize_batch_kernel(const BatchResizeArgs a) {
     resize_store<HWC, NORM>(a.y, tab, b, a.Ho, a.Wo, x, y0, col_in, row_in, acc, a.fill);
 }
 
-// labels: a gather through the sample's two nearest tables; one thread per output pixel
-template <typename TI, typename TO>
+// labels: a gather through the sample's two nearest tables; one thread per output pixel.  CODEC as in hs_resample.hip's label kernel: the
+// source pixel is encoded, the fill is stored as given
+template <typename TI, typename TO, int CODEC, typename... CA>
 __global__ __launch_bounds__(256)
 void label_resize_batch_kernel(const TI* __restrict__ x, const int32_t* __restrict__ params, const int32_t* __restrict__ nearest,
-                               const int32_t* __restrict__ status, TO* __restrict__ y, int Hi, int Wi, int Ho, int Wo, int M, int fill) {
+                               const int32_t* __restrict__ status, TO* __restrict__ y, int Hi, int Wi, int Ho, int Wo, int M, int fill,
+                               CA... ca) {
+    __shared__ uint32_t codec[codec_lds_words<CODEC>()];
+    const auto c = codec_args(ca...);
+    codec_stage<CODEC>(codec, c, (int)threadIdx.x);
     const long item = (long)blockIdx.x * 256 + threadIdx.x;
     if (item >= (long)Ho * Wo) return;
     const size_t b = blockIdx.y;
@@ -182,7 +188,8 @@ void label_resize_batch_kernel(const TI* __restrict__ x, const int32_t* __restri
         const int32_t* __restrict__ iy = nearest + (b * 2 + 0) * (size_t)M;
         const int32_t* __restrict__ ix = nearest + (b * 2 + 1) * (size_t)M;
         const int sy = min(max(iy[jy], 0), Hi - 1), sx = min(max(ix[jx], 0), Wi - 1);
-        v = (TO)x[(b * Hi + sy) * (size_t)Wi + sx];
+        if constexpr (CODEC == CODEC_NONE) v = (TO)x[(b * Hi + sy) * (size_t)Wi + sx];
+        else v = (TO)codec_gather<CODEC>(x, (b * Hi + sy) * (size_t)Wi + sx, codec, c);
     }
     y[b * (size_t)Ho * Wo + (size_t)item] = v;
 }
@@ -238,24 +245,57 @@ extern "C" int hs_frame_resize_batch_fwd(const uint8_t* x, int32_t layout, int32
     return launch_status();
 }
 
+struct LabelBatchArgs {
+    const void* x; const int32_t* params; const int32_t* nearest; const int32_t* status; void* y;
+    int in_dtype, out_dtype, batch, Hi, Wi, Ho, Wo, fill;
+};
+
+static int label_batch_checks(const LabelBatchArgs& a) {
+    if (!a.x || !a.y || !a.params || !a.nearest || !a.status) return HS_ERR_BAD_ARG;
+    if (a.batch <= 0 || a.Hi <= 0 || a.Wi <= 0 || a.Ho <= 0 || a.Wo <= 0) return HS_ERR_BAD_ARG;
+    if ((a.in_dtype != HS_EVAL_U8 && a.in_dtype != HS_EVAL_I64) || (a.out_dtype != HS_EVAL_U8 && a.out_dtype != HS_EVAL_I64)) return HS_ERR_BAD_ARG;
+    if (!batch_dims_ok(a.batch, a.Hi, a.Wi, a.Ho, a.Wo)) return HS_ERR_UNSUPPORTED;
+    if (((long)a.Ho * a.Wo + 255) / 256 > 0x7fffffffL) return HS_ERR_UNSUPPORTED;
+    return HS_OK;
+}
+
+template <typename TI, typename TO, int CODEC, typename... CA>
+static void launch_label_batch(const LabelBatchArgs& a, hipStream_t s, CA... ca) {
+    const dim3 grid((unsigned)(((long)a.Ho * a.Wo + 255) / 256), (unsigned)a.batch), block(256);
+    hipLaunchKernelGGL((label_resize_batch_kernel<TI, TO, CODEC, CA...>), grid, block, 0, s, static_cast<const TI*>(a.x), a.params, a.nearest,
+                       a.status, static_cast<TO*>(a.y), a.Hi, a.Wi, a.Ho, a.Wo, a.Ho > a.Wo ? a.Ho : a.Wo, a.fill, ca...);
+}
+
+// the storage types of a checked launch; a colour image is bytes
+template <int CODEC, typename... CA>
+static void label_batch_typed(const LabelBatchArgs& a, hipStream_t s, CA... ca) {
+    const bool u8_out = a.out_dtype == HS_EVAL_U8;
+    if (CODEC == CODEC_COLORS || a.in_dtype == HS_EVAL_U8) {
+        if (u8_out) launch_label_batch<uint8_t, uint8_t, CODEC>(a, s, ca...);
+        else launch_label_batch<uint8_t, int64_t, CODEC>(a, s, ca...);
+    } else if constexpr (CODEC != CODEC_COLORS) {
+        if (u8_out) launch_label_batch<int64_t, uint8_t, CODEC>(a, s, ca...);
+        else launch_label_batch<int64_t, int64_t, CODEC>(a, s, ca...);
+    }
+}
+
 extern "C" int hs_label_resize_batch_fwd(const void* x, int32_t in_dtype, int32_t batch, int32_t Hi, int32_t Wi, const int32_t* params,
                                          const int32_t* nearest, const int32_t* status, int32_t Ho, int32_t Wo, int32_t fill,
                                          void* y, int32_t out_dtype, void* stream) {
-    if (!x || !y || !params || !nearest || !status) return HS_ERR_BAD_ARG;
-    if (batch <= 0 || Hi <= 0 || Wi <= 0 || Ho <= 0 || Wo <= 0) return HS_ERR_BAD_ARG;
-    if ((in_dtype != HS_EVAL_U8 && in_dtype != HS_EVAL_I64) || (out_dtype != HS_EVAL_U8 && out_dtype != HS_EVAL_I64)) return HS_ERR_BAD_ARG;
-    if (!batch_dims_ok(batch, Hi, Wi, Ho, Wo)) return HS_ERR_UNSUPPORTED;
-    const long blocks = ((long)Ho * Wo + 255) / 256;
-    if (blocks > 0x7fffffffL) return HS_ERR_UNSUPPORTED;
-    const int M = Ho > Wo ? Ho : Wo;
-    const dim3 grid((unsigned)blocks, (unsigned)batch), block(256);
-    hipStream_t s = (hipStream_t)stream;
-#define HS_LABEL_LAUNCH(TI, TO) hipLaunchKernelGGL((label_resize_batch_kernel<TI, TO>), grid, block, 0, s, static_cast<const TI*>(x), params, \
-                                                   nearest, status, static_cast<TO*>(y), Hi, Wi, Ho, Wo, M, fill)
-    if (in_dtype == HS_EVAL_U8 && out_dtype == HS_EVAL_U8) HS_LABEL_LAUNCH(uint8_t, uint8_t);
-    else if (in_dtype == HS_EVAL_U8) HS_LABEL_LAUNCH(uint8_t, int64_t);
-    else if (out_dtype == HS_EVAL_U8) HS_LABEL_LAUNCH(int64_t, uint8_t);
-    else HS_LABEL_LAUNCH(int64_t, int64_t);
-#undef HS_LABEL_LAUNCH
+    const LabelBatchArgs a{x, params, nearest, status, y, in_dtype, out_dtype, batch, Hi, Wi, Ho, Wo, fill};
+    if (const int st = label_batch_checks(a)) return st;
+    label_batch_typed<CODEC_NONE>(a, (hipStream_t)stream);
+    return launch_status();
+}
+
+extern "C" int hs_label_resize_batch_coded_fwd(const void* x, int32_t in_dtype, int32_t batch, int32_t Hi, int32_t Wi, const int32_t* params,
+                                               const int32_t* nearest, const int32_t* status, int32_t Ho, int32_t Wo, int32_t fill,
+                                               const int32_t* codec_words, int32_t codec_kind, int32_t n, int32_t unmatched,
+                                               void* y, int32_t out_dtype, void* stream) {
+    const LabelBatchArgs a{x, params, nearest, status, y, in_dtype, out_dtype, batch, Hi, Wi, Ho, Wo, fill};
+    if (const int st = label_batch_checks(a)) return st;
+    if (const int st = codec_check(codec_words, codec_kind, in_dtype, n, unmatched)) return st;
+    if (codec_kind == HS_CODEC_COLORS) label_batch_typed<CODEC_COLORS>(a, (hipStream_t)stream, codec_words, (int)n, (int)unmatched);
+    else label_batch_typed<CODEC_TABLE>(a, (hipStream_t)stream, codec_words, (int)n, (int)unmatched);
     return launch_status();
 }

@@ -174,7 +174,7 @@ def _sync(device):
 
 
 @torch.no_grad()
-def measure_fps(model, batches, device, num_classes, passes=2, fused_metrics=False, overlay=False):
+def measure_fps(model, batches, device, num_classes, passes=2, fused_metrics=False, overlay=False, label_codec=None):
     """``batches``: list of (input, target) host tensors (inputs pinned when CUDA is used).  Runs ``passes`` passes over
     them and reports the LAST one (the reference's warm-up + timed pass).  Returns a dict.  ``fused_metrics``: where the
     model has ``evaluate`` (a HyperGen, a GraphedModel) the frame is scored by the forward's last launch -- INSIDE the timed
@@ -182,7 +182,9 @@ def measure_fps(model, batches, device, num_classes, passes=2, fused_metrics=Fal
     is served by ``model.overlay`` (masks + the uint8 display blended with ``overlay_style``) instead of the forward, inside the
     timed region; the masks are scored outside it as the reference's protocol does.  Targets of another size than the frame's are
     scored at their own resolution: the logits are resized to the label before the arg-max (test.py:167-168), outside the timed region
-    on the unfused route; a model that returns masks hands them out at the label's size where its ``segment`` takes ``size=``."""
+    on the unfused route; a model that returns masks hands them out at the label's size where its ``segment`` takes ``size=``.
+    ``label_codec`` (a ``LabelCodec``; the model's ``label_codec``): the targets are RAW dataset labels.  They are encoded where they are
+    scored: by ``model.evaluate`` inside the timed region with ``fused_metrics``, outside it otherwise."""
     result = {}
     if overlay and fused_metrics:
         raise ValueError('overlay and fused_metrics both ride on the final upsample launch: one of them per run')
@@ -213,6 +215,7 @@ def measure_fps(model, batches, device, num_classes, passes=2, fused_metrics=Fal
             total_time += time.perf_counter() - t0
             frames += pred.shape[0]
             if not fused:
+                target = encode_labels(target, label_codec)
                 if pred.dim() == 4 and pred.shape[2:] != target.shape[1:]:            # test.py:167-168
                     pred = _resize_logits(pred, tuple(target.shape[1:]))
                 elif pred.dim() == 3 and pred.shape[1:] != target.shape[1:]:
@@ -223,7 +226,7 @@ def measure_fps(model, batches, device, num_classes, passes=2, fused_metrics=Fal
         acc, _, iou = conf.compute()
         result = {'fps': frames / total_time, 'frames': frames, 'seconds': total_time, 'pass': p,
                   'global_accuracy': float(acc), 'mean_iou': float(iou.mean()),
-                  'label_size': list(batches[-1][1].shape[1:]) if batches else None}
+                  'label_size': list(batches[-1][1].shape[1:3]) if batches else None}
     return result
 
 
@@ -249,9 +252,52 @@ def _masks_at(model, x, size):
                          f'label\'s {size}: score it with logits, or with targets of the frame\'s size') from e
 
 
-def synthetic_batches(n, batch_size, size, num_classes, device, seed=0, uint8=False, layout='hwc', label_size=None):
+def encode_labels(target, codec):
+    """``target`` as class indices: raw labels of ``codec`` (None: nothing is raw) through ``functional.label_encode`` on the device,
+    ``codec.encode_cpu`` on the CPU."""
+    if codec is None or not codec.is_raw(target):
+        return target
+    return _kernels().label_encode(target.contiguous(), codec) if target.is_cuda else codec.encode_cpu(target)
+
+
+def random_codec(kind, num_classes, seed=0):
+    """A seeded synthetic ``LabelCodec`` whose inverse image covers every class 0..num_classes-1: ``'table'`` -- 2 n + 15 raw ids, every class
+    at two of them and 255 at the rest, shuffled (Cityscapes' table has that form: 34 ids, 19 classes); ``'colors'`` -- n distinct random
+    colours."""
+    from .utils.labels import LabelCodec
+    g = torch.Generator().manual_seed(seed)
+    if kind == 'table':
+        values = torch.tensor(list(range(num_classes)) * 2 + [255] * 15)
+        return LabelCodec.table(values[torch.randperm(len(values), generator=g)].tolist())
+    if kind != 'colors':
+        raise ValueError(f"kind {kind!r}: expected 'table' or 'colors'")
+    packed = torch.unique(torch.randint(0, 1 << 24, (4 * num_classes + 8,), generator=g))
+    packed = packed[torch.randperm(len(packed), generator=g)][:num_classes]
+    assert len(packed) == num_classes
+    return LabelCodec.colors(torch.stack((packed & 255, packed >> 8 & 255, packed >> 16), 1).tolist())
+
+
+def raw_labels(t, codec, generator):
+    """Raw labels that ``codec`` encodes to the class indices ``t`` (int64 (B, H, W), every value one the codec produces): for a table a
+    random raw id of the class per pixel, uint8; for a colour list the class's LAST colour, uint8 (B, H, W, 3)."""
+    if codec.is_colors:
+        last = {tuple(c): i for i, c in enumerate(codec.values)}
+        palette = torch.zeros(256, 3, dtype=torch.uint8)
+        for c, i in last.items():
+            palette[i] = torch.tensor(c, dtype=torch.uint8)
+        return palette[t]
+    ids = [[i for i, v in enumerate(codec.values) if v == c] for c in range(256)]
+    width = max(len(i) for i in ids)
+    table = torch.tensor([i + [0] * (width - len(i)) for i in ids])
+    count = torch.tensor([max(len(i), 1) for i in ids])
+    pick = (torch.rand(t.shape, generator=generator, dtype=torch.float64) * count[t]).long().clamp_(max=width - 1)
+    return table[t, torch.minimum(pick, count[t] - 1)].to(torch.uint8)
+
+
+def synthetic_batches(n, batch_size, size, num_classes, device, seed=0, uint8=False, layout='hwc', label_size=None, label_codec=None):
     """``uint8``: uint8 frames in ``layout`` ('hwc': (B, H, W, 3), 'chw': (B, 3, H, W)) from the same generator seed instead of
-    float32 (B, 3, H, W) images.  ``label_size``: (H, W) of the targets where it is not the frames' (None: the frames')."""
+    float32 (B, 3, H, W) images.  ``label_size``: (H, W) of the targets where it is not the frames' (None: the frames').
+    ``label_codec``: the same targets as RAW labels of that codec (:func:`raw_labels`)."""
     g = torch.Generator().manual_seed(seed)
     out = []
     for _ in range(n):
@@ -261,6 +307,8 @@ def synthetic_batches(n, batch_size, size, num_classes, device, seed=0, uint8=Fa
         else:
             x = torch.rand(batch_size, 3, *size, generator=g)
         t = torch.randint(0, num_classes, (batch_size,) + tuple(size if label_size is None else label_size), generator=g)
+        if label_codec is not None:
+            t = raw_labels(t, label_codec, g)
         out.append((x.pin_memory() if device.type == 'cuda' else x, t))
     return out
 
@@ -289,6 +337,10 @@ def main(argv=None):
     ap.add_argument('--label-size', nargs=2, type=int, metavar=('H', 'W'), default=None,
                     help="draw the targets at this size instead of the frame's: the logits are resized to it before they are counted "
                          "(test.py:167-168; the reference's Cityscapes test configs: 1024 2048)")
+    ap.add_argument('--raw-labels', choices=('table', 'colors'), default=None,
+                    help="the targets are RAW dataset labels -- ids (Cityscapes' form) or a colour image (CamVid's) drawn through a seeded "
+                         "random LabelCodec whose inverse image covers every class -- and model.label_codec encodes them on the device, "
+                         "where they are scored: inside the timed region with --fused-metrics, outside it otherwise")
     ap.add_argument('--resize', nargs=2, type=int, metavar=('H', 'W'), default=None,
                     help="on top of --uint8: attach FrameResize((H, W)) (model.input_resize) -- the synthetic frames are made at "
                          "--camera-size and resized on the device with PIL.Image.resize's bilinear arithmetic, inside the timed region "
@@ -348,6 +400,9 @@ def main(argv=None):
         palette = torch.randint(0, 256, (spec['num_classes'], 3), generator=torch.Generator().manual_seed(0))
         model.overlay_style = Overlay(palette, layout=args.layout)
         model.inference_hflip = False        # inert for tensor inputs, but overlay() takes its segment() + blend route while it is set
+    codec = None if args.raw_labels is None else random_codec(args.raw_labels, spec['num_classes'])
+    if codec is not None:
+        model.label_codec = codec
     model = model.to(device)
     if args.gpus and len(args.gpus) > 1 and device.type == 'cuda':
         if args.graph:
@@ -358,9 +413,9 @@ def main(argv=None):
         model = GraphedModel(model, num_classes=spec['num_classes'] if args.fused_metrics else None)
     bs = args.batch_size or spec['batch']
     uniq = synthetic_batches(min(args.distinct, args.iterations), bs, frame_size, spec['num_classes'], device,
-                             uint8=args.uint8, layout=args.layout, label_size=label_size)
+                             uint8=args.uint8, layout=args.layout, label_size=label_size, label_codec=codec)
     batches = [uniq[i % len(uniq)] for i in range(args.iterations)]
-    res = measure_fps(model, batches, device, spec['num_classes'], fused_metrics=args.fused_metrics, overlay=args.overlay)
+    res = measure_fps(model, batches, device, spec['num_classes'], fused_metrics=args.fused_metrics, overlay=args.overlay, label_codec=codec)
     frame = uniq[0][0]
     res.update(input_dtype=str(frame.dtype).replace('torch.', ''), input_bytes_per_frame=frame[0].numel() * frame.element_size())
     res.update(config=args.config, batch_size=bs, size=list(spec['size']), device=str(device), remove_bn=args.remove_bn,
@@ -372,6 +427,8 @@ def main(argv=None):
     if args.fused_metrics:
         res.update(fused_metrics=True, protocol=res['protocol'] + ' + confusion matrix counted inside the timed region by the '
                    "forward's last launch (the reference scores outside it)")
+    if codec is not None:
+        res.update(raw_labels=args.raw_labels, protocol=res['protocol'] + f' + raw {args.raw_labels} labels encoded on the device where they are scored')
     if args.overlay:
         res.update(overlay=True, protocol=res['protocol'] + " + uint8 overlay blended inside the timed region by the forward's last launch")
     print(json.dumps(res))

@@ -1726,23 +1726,68 @@ def frame_resize(x_u8, size, filter='bilinear', layout='hwc', view=None, norm=No
     return out
 
 
+def _raw_labels_bhw(t, codec, name='labels'):
+    """(B, H, W) of labels as ``codec`` (a ``utils.labels.LabelCodec``, or None: class indices) takes them."""
+    from .utils.labels import LabelCodec
+    if codec is None:
+        return _labels_bhw(t, name=name)
+    if not isinstance(codec, LabelCodec):
+        raise ValueError(f'codec must be a hyperseg_amd.LabelCodec or None, got {type(codec).__name__}')
+    return codec.check_raw(t, name)
+
+
+def _codec_operands(codec, device):
+    """``(codec_words, codec_kind, n, unmatched)`` of the coded entries.  The first use on a device copies the words there: call it
+    after every other check."""
+    return (_hip.dev_ptr(codec.device_words(device), 'codec words', torch.int32), *codec.launch_operands)
+
+
 @_on_operand_device
-def label_resize(t, size, view=None, fill=255, out=None):
+def label_encode(t, codec, out=None):
+    """A dataset's label encoding on the device, one launch (hs_label_encode_fwd): raw labels -- uint8 / int64 (B, H, W) ids for
+    ``LabelCodec.table``, uint8 (B, H, W, 3) colour images for ``LabelCodec.colors`` -- become class indices (B, H, W).  Returns the
+    input's dtype for a table and uint8 for colours, or ``out``'s (uint8 | int64, contiguous, (B, H, W)).  Equal to
+    ``codec.encode_cpu``.  Nothing is read back once the codec's words are on the device (first call per codec): capturable."""
+    if codec is None:
+        raise ValueError('label_encode needs a codec: hyperseg_amd.LabelCodec.table(values) or .colors(colors)')
+    b, h, w = _raw_labels_bhw(t, codec)
+    out = _label_out(out, (b, h, w), codec.out_dtype(t), t.device)
+    if b == 0 or h == 0 or w == 0:
+        raise ValueError('empty batch')
+    x = _hip.dev_ptr(t, 'labels', t.dtype)
+    y = _hip.dev_ptr(out, 'out', out.dtype)
+    _hip.run.hs_label_encode_fwd(x, _LABEL_DTYPES[t.dtype], b, h, w, *_codec_operands(codec, t.device), y, _LABEL_DTYPES[out.dtype],
+                                 _hip.stream_ptr())
+    return out
+
+
+@_on_operand_device
+def label_resize(t, size, view=None, fill=255, out=None, codec=None):
     """Labels (B, Hi, Wi), uint8 or int64, resized to ``size`` with ``PIL.Image.resize(..., NEAREST)``'s index tables (hs_label_resize_fwd,
     one launch), then ``view`` as :func:`frame_resize`'s with ``fill`` outside (the view's own fill is the frames').  Returns the
-    input's dtype, or ``out``'s (uint8 | int64, contiguous, (B, Ho, Wo)).  Equal to ``utils.resample.label_resize_cpu``."""
+    input's dtype, or ``out``'s (uint8 | int64, contiguous, (B, Ho, Wo)).  Equal to ``utils.resample.label_resize_cpu``.
+
+    ``codec`` (a ``LabelCodec``): ``t`` holds RAW labels as :func:`label_encode` takes them and the same one launch encodes the pixel it
+    gathers (hs_label_resize_coded_fwd); ``fill`` is stored as given, never encoded -- the reference pads after its dataset has
+    encoded.  The default output is then uint8 for a colour image.  ``None``: today's entry with today's arguments."""
     from .utils import resample
-    b, hi, wi = _labels_bhw(t)
+    b, hi, wi = _raw_labels_bhw(t, codec)
     hi, wi, hr, wr, view = _resize_geometry((hi, wi), size, view)
     (ho, wo), (oy, ox) = view.size, view.offset
-    out = _label_out(out, (b, ho, wo), t.dtype, t.device)
+    out = _label_out(out, (b, ho, wo), t.dtype if codec is None else codec.out_dtype(t), t.device)
     if b == 0:
         raise ValueError('empty batch')
     fill = _label_fill(fill, out)
     iy, ix = resample.device_nearest(hi, hr, t.device), resample.device_nearest(wi, wr, t.device)
-    _hip.run.hs_label_resize_fwd(_hip.dev_ptr(t, 'labels', t.dtype), _LABEL_DTYPES[t.dtype], b, hi, wi, iy.data_ptr(), hr, ix.data_ptr(), wr,
-                                 ho, wo, oy, ox, int(view.hflip), fill, _hip.dev_ptr(out, 'out', out.dtype), _LABEL_DTYPES[out.dtype],
-                                 _hip.stream_ptr())
+    if codec is None:
+        _hip.run.hs_label_resize_fwd(_hip.dev_ptr(t, 'labels', t.dtype), _LABEL_DTYPES[t.dtype], b, hi, wi, iy.data_ptr(), hr, ix.data_ptr(), wr,
+                                     ho, wo, oy, ox, int(view.hflip), fill, _hip.dev_ptr(out, 'out', out.dtype), _LABEL_DTYPES[out.dtype],
+                                     _hip.stream_ptr())
+        return out
+    x, y = _hip.dev_ptr(t, 'labels', t.dtype), _hip.dev_ptr(out, 'out', out.dtype)
+    _hip.run.hs_label_resize_coded_fwd(x, _LABEL_DTYPES[t.dtype], b, hi, wi, iy.data_ptr(), hr, ix.data_ptr(), wr, ho, wo, oy, ox,
+                                       int(view.hflip), fill, *_codec_operands(codec, t.device), y, _LABEL_DTYPES[out.dtype],
+                                       _hip.stream_ptr())
     return out
 
 
@@ -1834,18 +1879,24 @@ def frame_resize_batch(x_u8, params, tables, layout='hwc', fill=(0, 0, 0), norm=
 
 
 @_on_operand_device
-def label_resize_batch(t, params, tables, fill=255, out=None):
+def label_resize_batch(t, params, tables, fill=255, out=None, codec=None):
     """:func:`label_resize` for a batch whose samples each have a geometry of their own, one launch (hs_label_resize_batch_fwd):
     labels (B, Hi, Wi), uint8 or int64, through ``tables``' nearest indices, the ``tables.crop`` window of each sample with ``fill``
-    outside.  Returns the input's dtype, or ``out``'s (uint8 | int64, contiguous, (B, h, w)).  Capturable."""
-    n, hi, wi = _labels_bhw(t)
+    outside.  Returns the input's dtype, or ``out``'s (uint8 | int64, contiguous, (B, h, w)).  ``codec``: raw labels, encoded by the same
+    launch (hs_label_resize_batch_coded_fwd), as :func:`label_resize`'s.  Capturable."""
+    n, hi, wi = _raw_labels_bhw(t, codec)
     b = _batch_tables(tables, params, n, (hi, wi), t.device)
     ho, wo = tables.crop
-    out = _label_out(out, (b, ho, wo), t.dtype, t.device)
+    out = _label_out(out, (b, ho, wo), t.dtype if codec is None else codec.out_dtype(t), t.device)
     fill = _label_fill(fill, out)
-    _hip.run.hs_label_resize_batch_fwd(_hip.dev_ptr(t, 'labels', t.dtype), _LABEL_DTYPES[t.dtype], b, hi, wi,
-                                       _hip.dev_ptr(params, 'params', torch.int32), tables.nearest.data_ptr(), tables.status.data_ptr(),
-                                       ho, wo, fill, _hip.dev_ptr(out, 'out', out.dtype), _LABEL_DTYPES[out.dtype], _hip.stream_ptr())
+    if codec is None:
+        _hip.run.hs_label_resize_batch_fwd(_hip.dev_ptr(t, 'labels', t.dtype), _LABEL_DTYPES[t.dtype], b, hi, wi,
+                                           _hip.dev_ptr(params, 'params', torch.int32), tables.nearest.data_ptr(), tables.status.data_ptr(),
+                                           ho, wo, fill, _hip.dev_ptr(out, 'out', out.dtype), _LABEL_DTYPES[out.dtype], _hip.stream_ptr())
+        return out
+    x, p, y = _hip.dev_ptr(t, 'labels', t.dtype), _hip.dev_ptr(params, 'params', torch.int32), _hip.dev_ptr(out, 'out', out.dtype)
+    _hip.run.hs_label_resize_batch_coded_fwd(x, _LABEL_DTYPES[t.dtype], b, hi, wi, p, tables.nearest.data_ptr(), tables.status.data_ptr(),
+                                             ho, wo, fill, *_codec_operands(codec, t.device), y, _LABEL_DTYPES[out.dtype], _hip.stream_ptr())
     return out
 
 

@@ -166,6 +166,20 @@ class HyperGenBase(EpochOnModeSwitch, nn.Module):
     overlay_style = None
     # a utils.inference.FrameResize: uint8 frames of another size (camera frames) are resized to it on the device first.  A plain attribute
     input_resize = None
+    # a utils.labels.LabelCodec: ``evaluate`` and ``validate`` then take RAW dataset labels -- ids, or a colour image -- and encode them
+    # first, on every route.  A plain attribute as well
+    label_codec = None
+
+    def encoded(self, target):
+        """``target`` itself, or -- with ``label_codec`` set and a target of the codec's input kind (uint8 (B, H, W, 3) for a colour
+        list; for a table every 3-D integer target: with a codec set targets are raw by contract) -- the class indices:
+        ``HF.label_encode`` (one launch) on the device, ``codec.encode_cpu`` on the CPU."""
+        codec = self.label_codec
+        if codec is None or not codec.is_raw(target):
+            return target
+        if target.dtype not in (torch.uint8, torch.int64):
+            target = target.long()
+        return HF.label_encode(target.contiguous(), codec) if target.is_cuda else codec.encode_cpu(target)
 
     def resized(self, x):
         """``x`` itself, or -- a uint8 frame tensor of another size than ``input_resize``'s -- the resized uint8 frames (one launch)."""
@@ -283,9 +297,11 @@ class HyperGenBase(EpochOnModeSwitch, nn.Module):
         protocol of the reference's Cityscapes test configs) by ``HF.upsample2_confusion``, the returned masks then at the target's
         size.  Everything else -- list inputs (pyramid / h-flip inference), more classes than the kernel covers, training mode, CPU
         -- computes the masks the way ``segment()`` / ``forward()`` do (resizing the logits to a target of another size) and
-        counts them with ``confmat``'s own update.  Same numbers on every route."""
+        counts them with ``confmat``'s own update.  Same numbers on every route.  With ``label_codec`` set a raw ``target`` is encoded
+        first (:meth:`encoded`), whatever the route."""
         n = confmat.num_classes
         x = self.resized(x)
+        target = self.encoded(target)
         fused = (isinstance(x, torch.Tensor) and x.is_cuda and not self.training and isinstance(target, torch.Tensor)
                  and target.is_cuda and self._scorable(target, x.shape[0], n))
         if fused:
@@ -344,6 +360,7 @@ class HyperGenBase(EpochOnModeSwitch, nn.Module):
         CPU's composed route is stock torch ops: same masks and counts, the loss to rounding."""
         n = None if confmat is None else confmat.num_classes
         x = self.resized(x)
+        target = self.encoded(target)
         batch = (x if isinstance(x, torch.Tensor) else x[0]).shape[0]
         if not isinstance(target, torch.Tensor) or target.is_floating_point() or target.dim() != 3 or target.shape[0] != batch:
             raise ValueError(f'target must be ({batch}, H, W) class indices (uint8 or int64), got {getattr(target, "dtype", type(target))} '

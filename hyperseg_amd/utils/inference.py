@@ -1004,6 +1004,15 @@ class GraphedModel(nn.Module):
             got = scorer(x, target, *args, cm)
         return got
 
+    def _codec_of(self, target):
+        """``(key part, target as the routes' checks see it)``: with ``model.label_codec`` set and a raw ``target`` the codec -- the
+        static buffer then holds the raw label and the captured chain starts with the encode launch -- and a meta tensor of the encoded
+        label's shape and dtype; else ``()`` (keys and graphs are what they are without a codec) and ``target`` itself."""
+        codec = getattr(self.model, 'label_codec', None)
+        if codec is None or not codec.is_raw(target) or target.dtype not in (torch.uint8, torch.int64):
+            return (), target
+        return (codec,), codec.encoded_like(target)
+
     def _capture_counting(self, key, inputs, device, run, confusion):
         """``_capture`` of ``run(*static, out)`` counting into ``confusion``; the warm-up passes execute, so they count into a scratch copy."""
         scratch = None if confusion is None else torch.zeros_like(confusion)
@@ -1020,18 +1029,21 @@ class GraphedModel(nn.Module):
         one launch (``functional.upsample2_confusion``: the logits resized to the label, test.py:167-168), the masks at the
         target's size; the key holds the target's shape, so each label size gets a graph of its own.  What the graph cannot serve
         (``forward``'s list, plus a target of another type, or more classes than the kernel covers) is scored eagerly by
-        ``model.evaluate`` into the same matrix."""
+        ``model.evaluate`` into the same matrix.  With ``model.label_codec`` set and a raw ``target`` (``model.encoded``) the static buffer
+        holds the raw label, ``functional.label_encode`` is the chain's first node and the codec is part of the key."""
         n = self.num_classes
+        codec, seen = self._codec_of(target)
         graphable = (self._graphable(x) and x.dim() == 4 and hasattr(self.model, 'frame_size') and hasattr(self.model, 'process_single_tensor')
-                     and n is not None and HyperGenBase._scorable(target, x.shape[0], n) and target.numel() > 0)
+                     and n is not None and HyperGenBase._scorable(seen, x.shape[0], n) and target.numel() > 0)
         if not graphable:
             return self._score_eagerly(self.model.evaluate, *self._to_model_device(x, target))
         device = next(self.model.parameters()).device
         confusion = self._confusion_on(device, x.shape[0])
-        key = ('evaluate', tuple(x.shape), x.dtype, target.dtype, device, self._norm_of(x), tuple(target.shape))
+        key = ('evaluate', tuple(x.shape), x.dtype, target.dtype, device, self._norm_of(x), tuple(target.shape)) + codec
         entry = self._graphs.get(key)
         if entry is None:
             def run(xs, ts, out):
+                ts = self.model.encoded(ts) if codec else ts     # (a raw label: the encode launch is a node of the graph)
                 return self.model.process_single_tensor(self.model.resized(xs), epilogue=Epilogue(Score(ts, n, out, self.per_image)))
 
             entry = self._capture_counting(key, [x, target], device, run, confusion)
@@ -1057,8 +1069,9 @@ class GraphedModel(nn.Module):
             raise ValueError('GraphedModel.validate needs the loss: GraphedModel(model, criterion=BootstrappedCrossEntropyLoss(...))')
         model = self.model
         n = self.num_classes
+        codec, seen = self._codec_of(target)
         graphable = (self._graphable(x) and isinstance(target, torch.Tensor) and target.numel() > 0 and hasattr(model, '_validate_fused')
-                     and model._validate_fused(x, target, criterion, n, staged=True))
+                     and model._validate_fused(x, seen, criterion, n, staged=True))
         if not graphable:
             x, target = self._to_model_device(x, target)
             if n is None:
@@ -1067,12 +1080,13 @@ class GraphedModel(nn.Module):
         device = next(model.parameters()).device
         confusion = None if n is None else self._confusion_on(device, x.shape[0])
         key = ('validate', tuple(x.shape), x.dtype, target.dtype, device, self._norm_of(x), tuple(target.shape), criterion.k, criterion.thresh,
-               criterion.ignore_index, None if criterion.weight is None else criterion.weight.data_ptr())
+               criterion.ignore_index, None if criterion.weight is None else criterion.weight.data_ptr()) + codec
         entry = self._graphs.get(key)
         if entry is None:
             from ..autograd import BootstrapMeanOfBatch
 
             def run(xs, ts, out):
+                ts = model.encoded(ts) if codec else ts
                 masks, per_pixel = model.process_single_tensor(
                     model.resized(xs), epilogue=Epilogue(Score(ts, n, out, self.per_image), ignore_index=criterion.ignore_index,
                                                               weight=criterion.weight))

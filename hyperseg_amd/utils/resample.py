@@ -261,9 +261,12 @@ def frame_resize_cpu(x_u8, size, filter='bilinear', layout='hwc', view=None, nor
     return torch.stack([table[c][chw[:, c]] for c in range(3)], 1).contiguous()
 
 
-def label_resize_cpu(t, size, view=None, fill=255, out_dtype=None):
+def label_resize_cpu(t, size, view=None, fill=255, out_dtype=None, codec=None):
     """``functional.label_resize`` on CPU tensors: labels (B, Hi, Wi), uint8 or int64, gathered through the two nearest tables, then the
-    view with ``fill`` (the view's own fill is not read)."""
+    view with ``fill`` (the view's own fill is not read).  ``codec`` (a ``utils.labels.LabelCodec``): ``t`` holds raw labels, which are
+    encoded first (``codec.encode_cpu``); ``fill`` is not."""
+    if codec is not None:
+        t = codec.encode_cpu(t)
     if not isinstance(t, torch.Tensor) or t.dtype not in (torch.uint8, torch.int64) or t.dim() != 3:
         raise ValueError(f'labels must be uint8 or int64 (B, H, W), got {getattr(t, "dtype", type(t))} {tuple(getattr(t, "shape", ()))}')
     hi, wi = t.shape[1:]

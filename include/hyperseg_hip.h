@@ -572,6 +572,35 @@ int hs_frame_resize_batch_fwd(const uint8_t* x, int32_t layout, int32_t batch, i
 int hs_label_resize_batch_fwd(const void* x, int32_t in_dtype, int32_t batch, int32_t Hi, int32_t Wi, const int32_t* params,
                               const int32_t* nearest, const int32_t* status, int32_t Ho, int32_t Wo, int32_t fill,
                               void* y, int32_t out_dtype, void* stream);
+/* A dataset's label encoding on the device (csrc/hs_label_codec.hip, csrc/hs_label_codec.h; the rules and their CPU twin:
+ * hyperseg_amd/utils/labels.py), the per-pixel step the reference's loaders do on the host before their transforms see a label.
+ * codec_kind HS_CODEC_TABLE (hyperseg/datasets/cityscapes.py:210-211): a raw id outside [0, n) becomes values[0], every other id v
+ *   becomes values[v]; 1 <= n <= 256.  codec_words: int32 (64), on the device = the 256 table bytes, little-endian, entries from n on
+ *   holding values[0].  x (B, H, W), HS_EVAL_U8 or HS_EVAL_I64 (in_kind / in_dtype).  unmatched is not read.
+ * codec_kind HS_CODEC_COLORS (hyperseg/datasets/camvid.py:96-98): the index of the LAST of the n colours equal to the pixel, or
+ *   unmatched (0..255) where none is; 1 <= n <= 255.  codec_words: int32 (1 + n) = n, then the colours r | g << 8 | b << 16.
+ *   x uint8 (B, H, W, 3): in_kind / in_dtype must be HS_EVAL_U8.
+ * y (B, ., .) is HS_EVAL_U8 or HS_EVAL_I64 (out_dtype); every result is a byte value.
+ *   hs_label_encode_fwd: whole images, one launch.  Any alignment of x and y; the wide loads and stores are taken where the addresses
+ *     allow them.  HS_ERR_UNSUPPORTED -- nothing launched -- for batch > 65535.
+ *   hs_label_resize_coded_fwd / hs_label_resize_batch_coded_fwd: hs_label_resize_fwd / hs_label_resize_batch_fwd reading RAW labels: the
+ *     source pixel is gathered (3 bytes of a colour image), encoded and stored.  fill is stored AS GIVEN, never encoded: the reference
+ *     pads and crops after its dataset has encoded, with a class value.  Everything else as the un-coded entries, their limits included.
+ * Anything else in codec_kind, n, unmatched or the input type: HS_ERR_BAD_ARG.  Nothing is read back: capturable. */
+#define HS_CODEC_NONE 0
+#define HS_CODEC_TABLE 1
+#define HS_CODEC_COLORS 2
+int hs_label_encode_fwd(const void* x, int32_t in_kind, int32_t batch, int32_t H, int32_t W, const int32_t* codec_words,
+                        int32_t codec_kind, int32_t n, int32_t unmatched, void* y, int32_t out_dtype, void* stream);
+int hs_label_resize_coded_fwd(const void* x, int32_t in_dtype, int32_t batch, int32_t Hi, int32_t Wi,
+                              const int32_t* y_index, int32_t Hr, const int32_t* x_index, int32_t Wr,
+                              int32_t Ho, int32_t Wo, int32_t oy, int32_t ox, int32_t hflip, int32_t fill,
+                              const int32_t* codec_words, int32_t codec_kind, int32_t n, int32_t unmatched,
+                              void* y, int32_t out_dtype, void* stream);
+int hs_label_resize_batch_coded_fwd(const void* x, int32_t in_dtype, int32_t batch, int32_t Hi, int32_t Wi, const int32_t* params,
+                                    const int32_t* nearest, const int32_t* status, int32_t Ho, int32_t Wo, int32_t fill,
+                                    const int32_t* codec_words, int32_t codec_kind, int32_t n, int32_t unmatched,
+                                    void* y, int32_t out_dtype, void* stream);
 /* torchvision's ColorJitter on uint8 RGB frames with Pillow's bytes (csrc/hs_jitter.hip; the arithmetic: hyperseg_amd/utils/jitter.py):
  * up to four operations per sample, each on the uint8 result of the one before, in the order its record gives.
  * table: int32 (B, HS_JITTER_TABLE_WORDS), on the device, one record per sample -- word 0 the order, 4 bits per operation from the lowest
