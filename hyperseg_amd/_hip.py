@@ -155,6 +155,8 @@ SIGNATURES = {
     'hs_upsample_ce_confusion_fwd': ([vp, i32, i32, i32, i32, i32, i32, vp, i32, i64, vp, i32, i32, vp, vp, vp], STATUS),
     'hs_cross_entropy_score_weighted_fwd': ([i32, vp, vp, vp, i32, i32, i64, i64, vp, i32, i32, vp, vp, vp], STATUS),
     'hs_upsample_ce_confusion_weighted_fwd': ([vp, i32, i32, i32, i32, i32, i32, vp, i32, vp, i64, vp, i32, i32, vp, vp, vp], STATUS),
+    'hs_upsample2_ce_confusion_fwd': ([vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, i32, i64, vp, i32, i32, vp, vp, vp], STATUS),
+    'hs_upsample2_ce_confusion_weighted_fwd': ([vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, i32, vp, i64, vp, i32, i32, vp, vp, vp], STATUS),
     'hs_stage_input_fwd': ([C.POINTER(StageInputC), vp, vp], STATUS),
     'hs_stage_input_typed_fwd': ([C.POINTER(StageInputC), i32, i32, vp, vp], STATUS),
     'hs_patch_conv_bwd_input': ([vp, vp, i64, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp], STATUS),

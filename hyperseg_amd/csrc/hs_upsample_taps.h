@@ -190,6 +190,14 @@ __device__ __forceinline__ void bilinear2_row4(const float* __restrict__ plane, 
         out[i] = t.ty2.l0 * top + t.ty2.l1 * bot;
     }
 }
+// Pixel i of bilinear2_row4 alone, by the same operations (hs_validate.hip's second pass takes the four pixels two at a time).
+__device__ __forceinline__ float bilinear2_at(const float* __restrict__ plane, int Wi, const Row4x2& t, int i) {
+    const float m00 = tap_value(plane, Wi, t.ty1[0], t.tx1[i][0]), m01 = tap_value(plane, Wi, t.ty1[0], t.tx1[i][1]);
+    const float m10 = tap_value(plane, Wi, t.ty1[1], t.tx1[i][0]), m11 = tap_value(plane, Wi, t.ty1[1], t.tx1[i][1]);
+    const float top = t.tx2[i].l0 * m00 + t.tx2[i].l1 * m01;
+    const float bot = t.tx2[i].l0 * m10 + t.tx2[i].l1 * m11;
+    return t.ty2.l0 * top + t.ty2.l1 * bot;
+}
 // argmax_row4 over the composition: strictly greater wins, the first maximum is kept.
 __device__ __forceinline__ void argmax2_row4(const float* __restrict__ xb, int C, int Hi, int Wi, const Row4x2& t, int (&idx)[4]) {
     float best[4];

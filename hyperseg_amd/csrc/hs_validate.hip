@@ -16,6 +16,7 @@
 // confusion == nullptr: nothing is counted (loss and masks only).
 #include <hip/hip_runtime.h>
 #include <cstdint>
+#include <cstdlib>
 #include "hyperseg_hip.h"
 #include "hs_common.h"
 #include "hs_upsample_taps.h"
@@ -220,6 +221,110 @@ void upsample_ce_confusion_kernel(const float* __restrict__ x, int C, int Hi, in
     if (count) hist_flush(hist, nn, out + b * out_image_stride);
 }
 
+// argmax2_row4 (hs_upsample_taps.h) handing out the maxima as well, as argmax_row4_best does for the one-stage form -- for pixels I0 and
+// I0 + 1 of the thread's four: the same loads, the same comparisons per pixel, so hs_upsample2_confusion_fwd's indices.  Two pixels per
+// class loop, not four: the compiler hoists every load's 64-bit offset out of the loop (16 loads per pixel: argmax2_row4 alone takes 236
+// VGPRs), and with the targets, weights, sums and target scores of this kernel beside them the four-pixel loops spill (13 to 32 VGPRs to
+// scratch at the 256 that 512 threads allow).  Two loops of two pixels make each load once all the same.
+template <int I0>
+__device__ __forceinline__ void argmax2_row4_best(const float* __restrict__ xb, int C, size_t plane, int Wi, const Row4x2& t, int (&idx)[4],
+                                                  float (&best)[4]) {
+#pragma unroll
+    for (int i = I0; i < I0 + 2; ++i) { idx[i] = 0; best[i] = bilinear2_at(xb, Wi, t, i); }
+#pragma unroll 1
+    for (int c = 1; c < C; ++c) {
+        const float* __restrict__ pc = xb + (size_t)c * plane;
+#pragma unroll
+        for (int i = I0; i < I0 + 2; ++i) {
+            const float o = bilinear2_at(pc, Wi, t, i);
+            if (o > best[i]) { best[i] = o; idx[i] = c; }
+        }
+    }
+}
+
+// ... and the second pass for the same two pixels: the ascending exp-sum and the target's score, the scores recomputed by the same operations.
+template <int I0, typename TT>
+__device__ __forceinline__ void ce2_row4_sums(const float* __restrict__ xb, int C, size_t plane, int Wi, const Row4x2& t, const TT (&tv)[4],
+                                              const float (&m)[4], float (&sum)[4], float (&xt)[4]) {
+#pragma unroll 1
+    for (int c = 0; c < C; ++c) {
+        const float* __restrict__ pc = xb + (size_t)c * plane;
+#pragma unroll
+        for (int i = I0; i < I0 + 2; ++i) {
+            const float o = bilinear2_at(pc, Wi, t, i);
+            sum[i] += expf(o - m[i]);
+            xt[i] = ((long long)tv[i] == (long long)c) ? o : xt[i];
+        }
+    }
+}
+
+// Two resizes composed in registers (x -> mid -> label: the decoder's final resize, then train.py:119-120's to the label's size), any
+// first and any second stage: upsample2_confusion_kernel's mapping (hs_eval.hip), one thread = 4 consecutive label pixels of a row over a
+// Row4x2, and upsample_ce_confusion_kernel's two passes over the classes -- bilinear2_row4 recomputed by the same operations in the second,
+// so the same bits.  Neither the mid nor the label-size logits exist in memory.
+template <typename TT, typename... CW>
+__global__ __launch_bounds__(EVAL_THREADS)
+void upsample2_ce_confusion_kernel(const float* __restrict__ x, int C, Stages2 s, const TT* __restrict__ target, long long ignore_index,
+                                   float* __restrict__ loss, int n, unsigned long long* __restrict__ out, long out_image_stride,
+                                   uint8_t* __restrict__ mask, int vec, CW... cw) {
+    constexpr bool W = sizeof...(CW) != 0;
+    extern __shared__ unsigned hist[];
+    const int nn = n * n, lane = threadIdx.x & 63;
+    const bool count = out != nullptr;                           // (uniform)
+    if (count) hist_zero(hist, nn);
+    const size_t b = blockIdx.y;
+    const int Ho = s.Ho, Wo = s.Wo, wq = (Wo + 3) / 4;
+    const int items = Ho * wq;
+    const size_t plane = (size_t)s.Hi * s.Wi;
+    const float* __restrict__ xb = x + b * C * plane;
+    for (int base = blockIdx.x * EVAL_THREADS; base < items; base += gridDim.x * EVAL_THREADS) {      // wave-uniform trip count
+        const int e0 = base + (int)threadIdx.x;
+        const bool live = e0 < items;
+        const int e = live ? e0 : items - 1;
+        const int q = e % wq, yo = e / wq;
+        const Row4x2 t = row4x2_taps(yo, q, s);
+        const size_t at = (b * Ho + yo) * Wo + 4 * q;
+        TT tv[4];
+        if (vec) {
+            load4(target + at, tv);
+        } else {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) tv[i] = target[at + (4 * q + i < Wo ? i : 0)];
+        }
+        float wt[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i)                              // (W: in flight with the class loops' loads)
+            wt[i] = class_weight((long long)tv[i], ce_live((long long)tv[i], ignore_index, C), cw...);
+        int idx[4];
+        float m[4], sum[4] = {0.0f, 0.0f, 0.0f, 0.0f}, xt[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+        argmax2_row4_best<0>(xb, C, plane, s.Wi, t, idx, m);     // both passes of one pair, then the other's: its load offsets die in between
+        ce2_row4_sums<0>(xb, C, plane, s.Wi, t, tv, m, sum, xt);
+        argmax2_row4_best<2>(xb, C, plane, s.Wi, t, idx, m);
+        ce2_row4_sums<2>(xb, C, plane, s.Wi, t, tv, m, sum, xt);
+        float v[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+            v[i] = ce_live((long long)tv[i], ignore_index, C) ? weighted<W>(wt[i], (logf(sum[i]) + m[i]) - xt[i]) : 0.0f;
+        if (live) {
+            if (vec) {
+                *reinterpret_cast<float4*>(loss + at) = make_float4(v[0], v[1], v[2], v[3]);
+                if (mask != nullptr) *reinterpret_cast<uchar4*>(mask + at) = make_uchar4(idx[0], idx[1], idx[2], idx[3]);
+            } else {
+                for (int i = 0; i < 4 && 4 * q + i < Wo; ++i) {
+                    loss[at + i] = v[i];
+                    if (mask != nullptr) mask[at + i] = (uint8_t)idx[i];
+                }
+            }
+        }
+        if (count) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+                count_key(hist, (live && 4 * q + i < Wo) ? pair_key<TT>(tv[i], idx[i], n) : -1, lane);
+        }
+    }
+    if (count) hist_flush(hist, nn, out + b * out_image_stride);
+}
+
 // lane J of every quad's value in all four of its lanes, on the DPP path (quad_perm [J, J, J, J]); all lanes present
 template <int J>
 __device__ __forceinline__ float quad_bcast(float v) {
@@ -316,6 +421,158 @@ void upsample2x_ce_confusion_kernel(const float* __restrict__ x, int C, int Hi, 
     if (count) hist_flush(hist, nn, out + b * out_image_stride);
 }
 
+// argmax2x2x_block (hs_upsample_taps.h) handing out the maxima as well: on return all four lanes of the quad hold the 4 x 8 label block's
+// indices AND maxima.  Restated, as the two copies above are.
+__device__ __forceinline__ void argmax2x2x_block_best(const float* __restrict__ xb, int C, int Hi, int Wi, int yi, int q, int sub,
+                                                      int (&idx)[4][8], float (&best)[4][8]) {
+    constexpr float NEG = -3.402823466e38f;
+    const bool top = yi == 0, bottom = yi == Hi - 1, left = q == 0, right = 2 * q + 2 >= Wi;
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+#pragma unroll
+        for (int k = 0; k < 8; ++k) { best[r][k] = NEG; idx[r][k] = sub; }
+    for (int c0 = sub; c0 < C; c0 += 20) {
+        float in[5][3][4];
+#pragma unroll
+        for (int u = 0; u < 5; ++u) {
+            const int c = min(c0 + 4 * u, C - 1);
+            load2x_block(xb + (size_t)c * Hi * Wi, Hi, Wi, yi, q, in[u]);
+        }
+#pragma unroll
+        for (int u = 0; u < 5; ++u) {
+            const int c = c0 + 4 * u;
+            if (c < C) {
+                float o[4][8];
+                up2x2x_block(in[u], top, bottom, left, right, o);
+#pragma unroll
+                for (int r = 0; r < 4; ++r)
+#pragma unroll
+                    for (int k = 0; k < 8; ++k)
+                        if (o[r][k] > best[r][k]) { best[r][k] = o[r][k]; idx[r][k] = c; }
+            }
+        }
+    }
+#pragma unroll
+    for (int m = 1; m <= 2; m <<= 1) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+#pragma unroll
+            for (int k = 0; k < 8; ++k) {
+                const float v = __shfl_xor(best[r][k], m, 64);
+                const int j = __shfl_xor(idx[r][k], m, 64);
+                if (v > best[r][k] || (v == best[r][k] && j < idx[r][k])) { best[r][k] = v; idx[r][k] = j; }
+            }
+    }
+}
+
+// One class of the composed exact-2x second pass: lane J of the quad made the class' 4 x 8 label block; every lane takes the label row it
+// accounts for (row `sub`) and adds class c to its eight sums.
+template <int J, typename TT>
+__device__ __forceinline__ void ce2x2x_take(const float (&o)[4][8], int sub, int c, const TT (&t)[8], const float (&m)[8], float (&s)[8],
+                                            float (&xt)[8]) {
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        const float r0 = quad_bcast<J>(o[0][k]), r1 = quad_bcast<J>(o[1][k]), r2 = quad_bcast<J>(o[2][k]), r3 = quad_bcast<J>(o[3][k]);
+        const float v = sub == 0 ? r0 : sub == 1 ? r1 : sub == 2 ? r2 : r3;
+        s[k] += expf(v - m[k]);
+        xt[k] = ((long long)t[k] == (long long)c) ? v : xt[k];
+    }
+}
+
+// Both stages exact 2x: upsample2x2x_confusion_kernel's mapping (hs_eval.hip), four consecutive lanes per x block (yi, q) = 4 x 8 label
+// block, lane `sub` accounting for label row 4 yi + sub.  First pass: argmax2x2x_block's split of the classes over the quad.  Second pass,
+// as upsample2x_ce_confusion_kernel's: the quad makes four classes at a time (lane `sub`: class c0 + sub, the same load2x_block +
+// up2x2x_block), the values are exchanged within the quad (ce2x2x_take) and each lane runs the ascending exp-sums of its row's eight pixels.
+template <typename TT, typename... CW>
+__global__ __launch_bounds__(EVAL_THREADS)
+void upsample2x2x_ce_confusion_kernel(const float* __restrict__ x, int C, int Hi, int Wi, const TT* __restrict__ target, long long ignore_index,
+                                      float* __restrict__ loss, int n, unsigned long long* __restrict__ out, long out_image_stride,
+                                      uint8_t* __restrict__ mask, int vec, CW... cw) {
+    constexpr bool W = sizeof...(CW) != 0;
+    extern __shared__ unsigned hist[];
+    const int nn = n * n, lane = threadIdx.x & 63;
+    const bool count = out != nullptr;                           // (uniform)
+    if (count) hist_zero(hist, nn);
+    const size_t b = blockIdx.y;
+    const int wq = Wi >> 1, Wo = 4 * Wi;
+    const int items = Hi * wq;                                  // 4 x 8 label blocks of this image
+    const int sub = (int)(threadIdx.x & 3);
+    const size_t plane = (size_t)Hi * Wi;
+    const float* __restrict__ xb = x + b * C * plane;
+    for (int base = blockIdx.x * (EVAL_THREADS / 4); base < items; base += gridDim.x * (EVAL_THREADS / 4)) {
+        const int e0 = base + (int)(threadIdx.x >> 2);
+        const bool live = e0 < items;
+        const int e = live ? e0 : items - 1;                    // surplus lanes shadow the last block (the quad exchanges: convergent)
+        const int q = e % wq, yi = e / wq;
+        const bool top = yi == 0, bottom = yi == Hi - 1, left = q == 0, right = 2 * q + 2 >= Wi;
+        int p[8];
+        float m[8];
+        {
+            int idx[4][8];
+            float best[4][8];
+            argmax2x2x_block_best(xb, C, Hi, Wi, yi, q, sub, idx, best);
+#pragma unroll
+            for (int k = 0; k < 8; ++k) {
+                p[k] = sub == 0 ? idx[0][k] : sub == 1 ? idx[1][k] : sub == 2 ? idx[2][k] : idx[3][k];
+                m[k] = sub == 0 ? best[0][k] : sub == 1 ? best[1][k] : sub == 2 ? best[2][k] : best[3][k];
+            }
+        }
+        const size_t at = (b * 4 * Hi + 4 * yi + sub) * Wo + 8 * q;
+        TT tv[8];
+        if (vec) {
+            TT ta[4], tb[4];
+            load4(target + at, ta);
+            load4(target + at + 4, tb);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) { tv[k] = ta[k]; tv[4 + k] = tb[k]; }
+        } else {
+#pragma unroll
+            for (int k = 0; k < 8; ++k) tv[k] = target[at + k];
+        }
+        float wt[8];
+#pragma unroll
+        for (int k = 0; k < 8; ++k)                              // (W: in flight with the second pass' loads)
+            wt[k] = class_weight((long long)tv[k], ce_live((long long)tv[k], ignore_index, C), cw...);
+        float s[8], xt[8];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) s[k] = xt[k] = 0.0f;
+        for (int c0 = 0; c0 < C; c0 += 4) {                      // (uniform: every lane of the wave takes every trip and every branch below)
+            float in[3][4], o[4][8];
+            load2x_block(xb + (size_t)min(c0 + sub, C - 1) * plane, Hi, Wi, yi, q, in);
+            up2x2x_block(in, top, bottom, left, right, o);
+            ce2x2x_take<0>(o, sub, c0, tv, m, s, xt);
+            if (c0 + 1 < C) ce2x2x_take<1>(o, sub, c0 + 1, tv, m, s, xt);
+            if (c0 + 2 < C) ce2x2x_take<2>(o, sub, c0 + 2, tv, m, s, xt);
+            if (c0 + 3 < C) ce2x2x_take<3>(o, sub, c0 + 3, tv, m, s, xt);
+        }
+        float v[8];
+#pragma unroll
+        for (int k = 0; k < 8; ++k)
+            v[k] = ce_live((long long)tv[k], ignore_index, C) ? weighted<W>(wt[k], (logf(s[k]) + m[k]) - xt[k]) : 0.0f;
+        if (live) {
+            if (vec) {
+                *reinterpret_cast<float4*>(loss + at) = make_float4(v[0], v[1], v[2], v[3]);
+                *reinterpret_cast<float4*>(loss + at + 4) = make_float4(v[4], v[5], v[6], v[7]);
+                if (mask != nullptr) {
+                    *reinterpret_cast<uchar4*>(mask + at) = make_uchar4(p[0], p[1], p[2], p[3]);
+                    *reinterpret_cast<uchar4*>(mask + at + 4) = make_uchar4(p[4], p[5], p[6], p[7]);
+                }
+            } else {
+#pragma unroll
+                for (int k = 0; k < 8; ++k) {
+                    loss[at + k] = v[k];
+                    if (mask != nullptr) mask[at + k] = (uint8_t)p[k];
+                }
+            }
+        }
+        if (count) {
+#pragma unroll
+            for (int k = 0; k < 8; ++k) count_key(hist, live ? pair_key<TT>(tv[k], p[k], n) : -1, lane);
+        }
+    }
+    if (count) hist_flush(hist, nn, out + b * out_image_stride);
+}
+
 template <typename T, typename... CW>
 static void launch_ce_score(dim3 grid, size_t lds, hipStream_t s, const T* x, const long long* target, int C, long hw, long long ignore_index,
                             float* loss, int n, unsigned long long* out, long stride, uint8_t* mask, CW... cw) {
@@ -403,6 +660,57 @@ static int upsample_ce_confusion(const float* x, int32_t batch, int32_t channels
     return launch_status();
 }
 
+// ... and of hs_upsample2_ce_confusion_fwd and its weighted twin: hs_upsample2_confusion_fwd's choice of form (hs_eval.hip).
+template <typename... CW>
+static int upsample2_ce_confusion(const float* x, int32_t batch, int32_t channels, int32_t Hi, int32_t Wi, int32_t Hm, int32_t Wm, int32_t Ho,
+                                  int32_t Wo, const void* target, int32_t target_dtype, int64_t ignore_index, float* loss, int32_t num_classes,
+                                  int32_t per_image, int64_t* confusion, uint8_t* mask, void* stream, CW... cw) {
+    if (!x || !target || !loss || batch <= 0 || channels <= 0 || Hi <= 0 || Wi <= 0 || Hm <= 0 || Wm <= 0 || Ho <= 0 || Wo <= 0)
+        return HS_ERR_BAD_ARG;
+    if (!eval_storage_ok(target_dtype) || channels > 256) return HS_ERR_BAD_ARG;               // uint8 class indices
+    int n = 0;
+    const int status = score_args(channels, num_classes, confusion, &n);
+    if (status != HS_OK) return status;
+    if (batch > 65535 || (long)Ho * Wo > 0x7fffffffL - 4096 || (long)Hm * Wm > 0x7fffffffL - 4096) return HS_ERR_UNSUPPORTED;
+    const size_t lds = (size_t)n * n * sizeof(unsigned);
+    const long stride = per_image ? (long)n * n : 0;
+    unsigned long long* out = reinterpret_cast<unsigned long long*>(confusion);
+    const bool u8 = target_dtype == HS_EVAL_U8;
+    const bool aligned = aligned_to(target, u8 ? 4 : 16) && aligned_to(loss, 16) && (!mask || aligned_to(mask, 4));
+    const long long ii = (long long)ignore_index;
+    hipStream_t s = (hipStream_t)stream;
+    // dev A/B knob (tools/validate_label_time.py): HS_VALIDATE_2X2X=0 sends 2x o 2x shapes to the general form; read per call, so that one
+    // process can capture both
+    const char* knob = getenv("HS_VALIDATE_2X2X");
+    if (is_exact2x(Hi, Wi, Hm, Wm) && is_exact2x(Hm, Wm, Ho, Wo) && !(knob && atoi(knob) == 0)) {
+        const int vec = aligned;                                                              // rows of 8 k label pixels
+        const long passes = ((long)Hi * (Wi / 2) + EVAL_THREADS / 4 - 1) / (EVAL_THREADS / 4);
+        const dim3 grid(eval_grid_x(passes, batch), (unsigned)batch);
+        if (u8)
+            hipLaunchKernelGGL((upsample2x2x_ce_confusion_kernel<uint8_t, CW...>), grid, dim3(EVAL_THREADS), lds, s, x, channels, Hi, Wi,
+                               (const uint8_t*)target, ii, loss, n, out, stride, mask, vec, cw...);
+        else
+            hipLaunchKernelGGL((upsample2x2x_ce_confusion_kernel<int64_t, CW...>), grid, dim3(EVAL_THREADS), lds, s, x, channels, Hi, Wi,
+                               (const int64_t*)target, ii, loss, n, out, stride, mask, vec, cw...);
+        return launch_status();
+    }
+    Stages2 st;
+    st.Hi = Hi; st.Wi = Wi; st.Hm = Hm; st.Wm = Wm; st.Ho = Ho; st.Wo = Wo;
+    st.exact1 = is_exact2x(Hi, Wi, Hm, Wm); st.exact2 = is_exact2x(Hm, Wm, Ho, Wo);           // the form hs_upsample_bilinear_fwd takes per stage
+    st.sy1 = (float)Hi / (float)Hm; st.sx1 = (float)Wi / (float)Wm;
+    st.sy2 = (float)Hm / (float)Ho; st.sx2 = (float)Wm / (float)Wo;
+    const int vec = (Wo & 3) == 0 && aligned;
+    const long passes = ((long)Ho * ((Wo + 3) / 4) + EVAL_THREADS - 1) / EVAL_THREADS;
+    const dim3 grid(eval_grid_x(passes, batch), (unsigned)batch);
+    if (u8)
+        hipLaunchKernelGGL((upsample2_ce_confusion_kernel<uint8_t, CW...>), grid, dim3(EVAL_THREADS), lds, s, x, channels, st,
+                           (const uint8_t*)target, ii, loss, n, out, stride, mask, vec, cw...);
+    else
+        hipLaunchKernelGGL((upsample2_ce_confusion_kernel<int64_t, CW...>), grid, dim3(EVAL_THREADS), lds, s, x, channels, st,
+                           (const int64_t*)target, ii, loss, n, out, stride, mask, vec, cw...);
+    return launch_status();
+}
+
 }  // namespace hs
 
 using namespace hs;
@@ -436,4 +744,21 @@ extern "C" int hs_upsample_ce_confusion_weighted_fwd(const float* x, int32_t bat
     if (!weight) return HS_ERR_BAD_ARG;
     return upsample_ce_confusion(x, batch, channels, Hi, Wi, Ho, Wo, target, target_dtype, ignore_index, loss, num_classes, per_image,
                                  confusion, mask, stream, weight);
+}
+
+// The same at the LABEL's resolution: two resizes composed in registers, x (Hi, Wi) -> mid (Hm, Wm) -> (Ho, Wo).
+extern "C" int hs_upsample2_ce_confusion_fwd(const float* x, int32_t batch, int32_t channels, int32_t Hi, int32_t Wi, int32_t Hm, int32_t Wm,
+                                             int32_t Ho, int32_t Wo, const void* target, int32_t target_dtype, int64_t ignore_index, float* loss,
+                                             int32_t num_classes, int32_t per_image, int64_t* confusion, uint8_t* mask, void* stream) {
+    return upsample2_ce_confusion(x, batch, channels, Hi, Wi, Hm, Wm, Ho, Wo, target, target_dtype, ignore_index, loss, num_classes, per_image,
+                                  confusion, mask, stream);
+}
+
+extern "C" int hs_upsample2_ce_confusion_weighted_fwd(const float* x, int32_t batch, int32_t channels, int32_t Hi, int32_t Wi, int32_t Hm,
+                                                      int32_t Wm, int32_t Ho, int32_t Wo, const void* target, int32_t target_dtype,
+                                                      const float* weight, int64_t ignore_index, float* loss, int32_t num_classes,
+                                                      int32_t per_image, int64_t* confusion, uint8_t* mask, void* stream) {
+    if (!weight) return HS_ERR_BAD_ARG;
+    return upsample2_ce_confusion(x, batch, channels, Hi, Wi, Hm, Wm, Ho, Wo, target, target_dtype, ignore_index, loss, num_classes, per_image,
+                                  confusion, mask, stream, weight);
 }

@@ -1467,7 +1467,8 @@ def class_weight_table(weight, classes, device, what='weight'):
 _WEIGHTED_TWINS = {'hs_cross_entropy_typed_fwd': ('hs_cross_entropy_weighted_fwd', 3), 'hs_cross_entropy_typed_bwd': ('hs_cross_entropy_weighted_bwd', 3),
                    'hs_bootstrapped_ce_fwd': ('hs_bootstrapped_ce_weighted_fwd', 3), 'hs_bootstrapped_ce_bwd': ('hs_bootstrapped_ce_weighted_bwd', 3),
                    'hs_cross_entropy_score_fwd': ('hs_cross_entropy_score_weighted_fwd', 3),
-                   'hs_upsample_ce_confusion_fwd': ('hs_upsample_ce_confusion_weighted_fwd', 9)}
+                   'hs_upsample_ce_confusion_fwd': ('hs_upsample_ce_confusion_weighted_fwd', 9),
+                   'hs_upsample2_ce_confusion_fwd': ('hs_upsample2_ce_confusion_weighted_fwd', 11)}
 
 
 def loss_launch(entry, table, *args):
@@ -1524,6 +1525,34 @@ def upsample_ce_confusion(x, size, target, ignore_index, num_classes, out=None, 
     tail = (int(ignore_index), loss.data_ptr(), n, 1 if per_image else 0, _hip.ptr(out), mask.data_ptr(), _hip.stream_ptr())
     loss_launch('hs_upsample_ce_confusion_fwd', class_weight_table(weight, c, x.device),
                 xp, b, c, hi, wi, ho, wo, target.data_ptr(), _EVAL_DTYPES[target.dtype], *tail)
+    return loss, out, mask
+
+
+@_on_operand_device
+def upsample2_ce_confusion(x, mid_size, target, ignore_index, num_classes, out=None, per_image=False, weight=None):
+    """``upsample_ce_confusion`` at the LABEL's resolution (hs_upsample2_ce_confusion_fwd): the logits ``x`` (B, C, Hi, Wi) f32 are resized
+    to ``mid_size`` (the frame's size, where the model's logits live) and from there to ``target``'s size (train.py:119-120), both resizes
+    composed in registers, and from each label pixel's scores come its cross entropy against ``target`` (B, Ho, Wo; uint8 or int64), its
+    class and its count -- one launch; neither resized tensor exists in memory.  Returns ``(loss, out, masks)``: ``loss`` (B, Ho, Wo) f32
+    bit-identical to ``PixelCrossEntropy`` on ``upsample_bilinear(upsample_bilinear(x, mid_size), target.shape[1:])``, masks and counts to
+    ``upsample2_confusion``'s.  ``ignore_index``, ``num_classes``, ``out``, ``per_image``, ``weight`` and the errors raised are
+    ``upsample_ce_confusion``'s, which this simply calls when the target is at ``mid_size`` already (or ``x`` is).  Capturable."""
+    b, c, hi, wi = _logits_shape(x)
+    hm, wm = _size2(mid_size, 'mid_size')
+    target = _eval_labels(target, 'target')
+    if target.dim() != 3 or target.shape[0] != b:
+        raise ValueError(f'target has shape {tuple(target.shape)}, expected ({b}, Ho, Wo)')
+    ho, wo = int(target.shape[1]), int(target.shape[2])
+    if (ho, wo) == (hm, wm) or (hi, wi) == (hm, wm):
+        return upsample_ce_confusion(x, (ho, wo), target, ignore_index, num_classes, out=out, per_image=per_image, weight=weight)
+    target = _eval_target(target, (b, ho, wo), x)
+    n, out = _score_out(num_classes, c, out, b, per_image, x.device)
+    xp = _hip.dev_ptr(x, 'x')
+    loss = torch.empty(b, ho, wo, device=x.device, dtype=torch.float32)
+    mask = torch.empty(b, ho, wo, device=x.device, dtype=torch.uint8)
+    tail = (int(ignore_index), loss.data_ptr(), n, 1 if per_image else 0, _hip.ptr(out), mask.data_ptr(), _hip.stream_ptr())
+    loss_launch('hs_upsample2_ce_confusion_fwd', class_weight_table(weight, c, x.device),
+                xp, b, c, hi, wi, hm, wm, ho, wo, target.data_ptr(), _EVAL_DTYPES[target.dtype], *tail)
     return loss, out, mask
 
 

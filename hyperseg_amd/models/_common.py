@@ -83,18 +83,24 @@ class Epilogue:
     size, or resized once more to ``out_size`` -- or scored by that launch (``score``) or blended over the frames by it (``blend``): one of
     the two per forward.  ``ignore_index`` (with ``score``): the criterion's -- a validation step, the launch also makes every pixel's
     cross entropy against the score's target.  ``weight`` (with ``ignore_index`` and ``score``): the criterion's class-weight table, fp32
-    (C,) on the device, finite and >= 0 -- the losses are then the weighted ones.  A scored forward takes its output size from its target."""
+    (C,) on the device, finite and >= 0 -- the losses are then the weighted ones.  A scored forward takes its output size from its target.
+    ``loss_at_label`` (with ``ignore_index``; off by default): a target of another size than the frame's is then taken at ITS resolution by
+    the validation step too, as train.py:119-120 does -- losses, masks and counts at the label's size from the one launch; without it such
+    a target is rejected where a loss is asked for."""
     score: Optional[Score] = None
     blend: Optional[Blend] = None
     out_size: Optional[tuple] = None
     ignore_index: Optional[int] = None
     weight: Optional[object] = None
+    loss_at_label: bool = False
 
     def __post_init__(self):
         if self.ignore_index is not None and (self.score is None or self.blend is not None):
             raise ValueError('the loss rides on a scored epilogue: a score with it, no blend')
         if self.weight is not None and (self.ignore_index is None or self.score is None):
             raise ValueError('class weights weigh the loss: they ride on a scored epilogue with an ignore_index')
+        if self.loss_at_label and self.ignore_index is None:
+            raise ValueError('loss_at_label places the loss: it rides on a scored epilogue with an ignore_index')
         if self.score is not None and self.blend is not None:
             raise ValueError('score and blend both ride on the final upsample launch: one of them per forward for now')
         if self.out_size is not None:
@@ -105,7 +111,10 @@ class Epilogue:
         validation step (per_pixel: f32 (B, H, W), what ``BootstrappedCrossEntropyLoss`` ranks), ``(masks, overlay)`` of a blend.  A
         score's target of another size than ``size`` is scored at ITS resolution, as test.py:167-168 does: the logits at ``size`` are
         resized once more, to the target's size, before the arg-max -- both resizes composed in the one launch, a single one where ``p``
-        is at ``size`` already; the masks are then at the target's size."""
+        is at ``size`` already; the masks are then at the target's size.  A validation step takes such a target only with
+        ``loss_at_label`` set: the logits at ``size`` are resized to the target before the criterion as well (train.py:119-120), by
+        ``HF.upsample2_ce_confusion`` -- ``HF.upsample_ce_confusion`` straight to the target's size where ``p`` is at ``size`` already -- and
+        ``per_pixel`` is at the target's size too."""
         size = tuple(size)
         resized = self.out_size is not None and self.out_size != size
         if self.score is not None:
@@ -114,9 +123,17 @@ class Epilogue:
             if self.ignore_index is not None:
                 if resized:
                     raise ValueError('the loss rides on a scored epilogue at the frame\'s size: no other out_size')
-                if label != size:
+                if label != size and not self.loss_at_label:
                     raise ValueError(f'the loss needs a target at the output size {size}, got {label}')
                 weighted = {} if self.weight is None else dict(weight=self.weight)          # (the unweighted call is what it was)
+                if label != size:
+                    if tuple(p.shape[2:]) != size:
+                        per_pixel, _, masks = HF.upsample2_ce_confusion(p, size, target, self.ignore_index, num_classes, out=out,
+                                                                        per_image=per_image, **weighted)
+                    else:
+                        per_pixel, _, masks = HF.upsample_ce_confusion(p, label, target, self.ignore_index, num_classes, out=out,
+                                                                       per_image=per_image, **weighted)
+                    return masks, per_pixel
                 per_pixel, _, masks = HF.upsample_ce_confusion(p, size, target, self.ignore_index, num_classes, out=out, per_image=per_image,
                                                                **weighted)
                 return masks, per_pixel
@@ -340,6 +357,25 @@ class HyperGenBase(EpochOnModeSwitch, nn.Module):
         pixels = target.shape[1] * target.shape[2]
         return criterion.k < pixels < 2 ** 31
 
+    def _validate_fused_at_label(self, x, target, criterion, n, staged=False):
+        """validate()'s fused route at the LABEL's resolution applies: ``_validate_fused``'s conditions for a target of ANOTHER size than the
+        frame's, ``criterion.k`` and the pixel bound taken on the label's pixels."""
+        from ..training import BootstrappedCrossEntropyLoss, USE_HIP_BOOTSTRAP, USE_FUSED_LOSS
+        if not (isinstance(x, torch.Tensor) and x.dim() == 4 and not self.training and isinstance(target, torch.Tensor)
+                and (staged or (x.is_cuda and target.is_cuda)) and self._scorable(target, x.shape[0], n)):
+            return False
+        if not (isinstance(criterion, BootstrappedCrossEntropyLoss) and criterion.score is None and USE_HIP_BOOTSTRAP and USE_FUSED_LOSS):
+            return False
+        if criterion.weight is not None:                        # (as _validate_fused)
+            device = next(self.parameters()).device if staged else x.device
+            classes = getattr(self.decoder, 'num_classes', None)
+            if classes is None or not criterion.weight_takes_hip(classes, device):
+                return False
+        if tuple(target.shape[1:]) == self.frame_size(x) or x.shape[0] > 65535:
+            return False
+        pixels = target.shape[1] * target.shape[2]
+        return criterion.k < pixels < 2 ** 31
+
     @torch.no_grad()
     def validate(self, x, target, criterion, confmat=None, per_image=False):
         """One validation batch of the reference's epoch loop (train.py:118-126 in ``eval()`` mode under ``no_grad``): returns ``(loss,
@@ -352,7 +388,11 @@ class HyperGenBase(EpochOnModeSwitch, nn.Module):
         a uint8 / int64 target at the frame's size with more than ``criterion.k`` pixels and at most ``HF.eval_max_classes()`` classes:
         the forward's last launch (``HF.upsample_ce_confusion``) makes the per-pixel losses, the masks and the counts -- the
         full-resolution logits are never written -- and the criterion's own batch reduction follows (the launches its fused forward
-        makes after its first).  Everything else -- list inputs, training mode, CPU, a target of another size, class weights the HIP
+        makes after its first).  A target of ANOTHER size than the frame's (the reference's Cityscapes validation: the image is resized,
+        the label is not, train.py:119-120 resizes the logits to the label) takes the same route at the label's resolution, under the same
+        conditions with ``criterion.k`` taken against the label's pixels: the last launch (``HF.upsample2_ce_confusion``) composes the
+        decoder's final resize with the one to the label, and losses, masks and counts are at the label's size; neither the frame-size nor
+        the label-size logits are written.  Everything else -- list inputs, training mode, CPU, class weights the HIP
         loss does not take, another criterion -- computes ``pred = self(x)``, resizes it to the target as ``evaluate`` does, and takes ``criterion(pred,
         target.long())``, ``argmax`` and ``confmat``'s own update.  On the device every route gives the same loss bits, masks and
         counts from the same decoder input.  (An unprepared model's stock torch encoder does not repeat its own bits from one call to
@@ -365,13 +405,16 @@ class HyperGenBase(EpochOnModeSwitch, nn.Module):
         if not isinstance(target, torch.Tensor) or target.is_floating_point() or target.dim() != 3 or target.shape[0] != batch:
             raise ValueError(f'target must be ({batch}, H, W) class indices (uint8 or int64), got {getattr(target, "dtype", type(target))} '
                              f'{tuple(getattr(target, "shape", ()))}')
-        if self._validate_fused(x, target, criterion, n):
+        fused = self._validate_fused(x, target, criterion, n)
+        at_label = not fused and self._validate_fused_at_label(x, target, criterion, n)
+        if fused or at_label:
             from ..autograd import BootstrapMeanOfBatch
             out = None
             if confmat is not None:
                 out = torch.zeros((x.shape[0], n, n), dtype=torch.int64, device=x.device) if per_image else confmat.matrix(x.device)
+            at = dict(loss_at_label=True) if at_label else {}       # (the same-size epilogue is what it was)
             got = self.process_single_tensor(x, epilogue=Epilogue(Score(target, n, out, per_image), ignore_index=criterion.ignore_index,
-                                                                       weight=criterion.weight))
+                                                                       weight=criterion.weight, **at))
             if not isinstance(got, tuple):
                 raise RuntimeError('the decoder returned logits where its epilogue was asked for: nothing was scored')
             masks, per_pixel = got

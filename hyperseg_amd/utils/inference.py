@@ -1058,7 +1058,9 @@ class GraphedModel(nn.Module):
         staged into static buffers, the graph is the forward's chain with ``functional.upsample_ce_confusion`` as its last launch
         followed by the criterion's batch reduction, keyed by the shapes and dtypes of both (and apart from the ``forward`` /
         ``evaluate`` graphs); the warm-up passes count into a scratch matrix.  ``loss`` is the graph's static 0-dim tensor: valid until
-        the next call of the same shape.  The values are ``model.validate``'s (its note on an unprepared model's
+        the next call of the same shape.  A target of another size than the frame's is served the same way at the label's resolution
+        (``model.validate``'s conditions for it): the last launch is ``functional.upsample2_ce_confusion``, loss inputs, masks and counts
+        are at the label's size, and -- the key holds the target's shape -- each label size gets a graph of its own.  The values are ``model.validate``'s (its note on an unprepared model's
         stock encoder applies).  What the graph cannot serve takes ``model.validate``'s routes, counting into the same
         matrix.  A criterion with class weights the HIP loss takes (``training.weight_fusable``) is served the same way: the captured
         launch holds the ADDRESS of ``criterion.weight``, so -- as with ``score.mat`` -- change the table in place (``weight.mul_(2)``,
@@ -1070,8 +1072,10 @@ class GraphedModel(nn.Module):
         model = self.model
         n = self.num_classes
         codec, seen = self._codec_of(target)
-        graphable = (self._graphable(x) and isinstance(target, torch.Tensor) and target.numel() > 0 and hasattr(model, '_validate_fused')
-                     and model._validate_fused(x, seen, criterion, n, staged=True))
+        graphable = self._graphable(x) and isinstance(target, torch.Tensor) and target.numel() > 0 and hasattr(model, '_validate_fused')
+        at_label = False
+        if graphable and not model._validate_fused(x, seen, criterion, n, staged=True):
+            at_label = graphable = model._validate_fused_at_label(x, seen, criterion, n, staged=True)
         if not graphable:
             x, target = self._to_model_device(x, target)
             if n is None:
@@ -1087,9 +1091,10 @@ class GraphedModel(nn.Module):
 
             def run(xs, ts, out):
                 ts = model.encoded(ts) if codec else ts
+                at = dict(loss_at_label=True) if at_label else {}
                 masks, per_pixel = model.process_single_tensor(
                     model.resized(xs), epilogue=Epilogue(Score(ts, n, out, self.per_image), ignore_index=criterion.ignore_index,
-                                                              weight=criterion.weight))
+                                                              weight=criterion.weight, **at))
                 return BootstrapMeanOfBatch.apply(per_pixel.flatten(1), criterion.k, criterion.thresh), masks
 
             entry = self._capture_counting(key, [x, target], device, run, confusion)

@@ -374,6 +374,23 @@ int hs_cross_entropy_score_weighted_fwd(int32_t dtype, const void* logits, const
 int hs_upsample_ce_confusion_weighted_fwd(const float* x, int32_t batch, int32_t channels, int32_t Hi, int32_t Wi, int32_t Ho, int32_t Wo,
                                           const void* target, int32_t target_dtype, const float* weight, int64_t ignore_index, float* loss,
                                           int32_t num_classes, int32_t per_image, int64_t* confusion, uint8_t* mask, void* stream);
+/* The validation step at the LABEL's resolution (train.py:119-120: the logits, at the frame's size, are resized to a label of another size
+ * before the criterion and the arg-max): hs_upsample_ce_confusion_fwd over TWO resizes composed in registers, x (Hi, Wi) -> mid (Hm, Wm) ->
+ * (Ho, Wo), targets at (batch, Ho, Wo).  A label pixel's class scores are exactly what hs_upsample_bilinear_fwd(hs_upsample_bilinear_fwd(x
+ * -> Hm, Wm) -> Ho, Wo) stores (each stage in the form that entry takes for its shape, the second clamping in mid index space), so
+ *   loss (batch, Ho, Wo) f32 is hs_cross_entropy_typed_fwd's on those logits bit for bit (times weight[t] in the twin),
+ *   mask (optional) and the counts are hs_upsample2_confusion_fwd's,
+ * and neither the mid nor the label-size logits are ever in memory.  Two forms, chosen as hs_upsample2_confusion_fwd chooses: both stages
+ * exact 2x, and any other pair of stages (down-sampling and identity stages included).  confusion, num_classes, per_image, ignore_index,
+ * the limits (channels <= 256, num_classes <= hs_eval_max_classes(), batch <= 65535, Ho * Wo and Hm * Wm < 2^31 - 4096) and the status
+ * codes: hs_upsample_ce_confusion_fwd's.  Nothing is read back: capturable. */
+int hs_upsample2_ce_confusion_fwd(const float* x, int32_t batch, int32_t channels, int32_t Hi, int32_t Wi, int32_t Hm, int32_t Wm, int32_t Ho,
+                                  int32_t Wo, const void* target, int32_t target_dtype, int64_t ignore_index, float* loss, int32_t num_classes,
+                                  int32_t per_image, int64_t* confusion, uint8_t* mask, void* stream);
+int hs_upsample2_ce_confusion_weighted_fwd(const float* x, int32_t batch, int32_t channels, int32_t Hi, int32_t Wi, int32_t Hm, int32_t Wm,
+                                           int32_t Ho, int32_t Wo, const void* target, int32_t target_dtype, const float* weight,
+                                           int64_t ignore_index, float* loss, int32_t num_classes, int32_t per_image, int64_t* confusion,
+                                           uint8_t* mask, void* stream);
 
 /* Backward of hs_patch_conv_fwd (plain input x, no fused prologue / epilogue), fp32 -- SURVEY.md Appendix E.
  * The reference has no backward of its own (autograd over F.pad/unfold/grouped conv2d/fold: meta_patch.py:35-57);
