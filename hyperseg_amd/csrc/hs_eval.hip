@@ -12,6 +12,8 @@
 //   * across workgroups the whole matrix is a few cache lines, so each workgroup flushes once, at its end: non-zero bins only,
 //     consecutive lanes on consecutive bins, one 64-bit global atomic add each (global_atomic_add_x2, no compare-and-swap).
 // No cross-workgroup waiting of any kind.
+// Host side: the entries at the end of the file share one launch front with hs_validate.hip's (hs_eval_count.h: histogram operands,
+// target-type dispatcher, grids, shape check; Stages2's constructor: hs_upsample_taps.h); refusal order and `vec` stay each entry's own.
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include "hyperseg_hip.h"
@@ -251,47 +253,41 @@ using namespace hs;
 
 extern "C" int hs_eval_max_classes(void) { return EVAL_MAX_CLASSES; }
 
+// The entries below are fronts in the shape DESIGN.md 3.11.3 describes: the entry's own refusals in its own order, eval_hist's operands, its own
+// `vec` predicate per form, and each kernel form launched from one line under with_target.
+
 extern "C" int hs_upsample_confusion_fwd(const float* x, int32_t batch, int32_t channels, int32_t Hi, int32_t Wi, int32_t Ho, int32_t Wo,
                                          const void* target, int32_t target_dtype, int32_t num_classes, int32_t per_image,
                                          int64_t* confusion, uint8_t* mask, void* stream) {
-    if (!x || !target || !confusion || batch <= 0 || channels <= 0 || Hi <= 0 || Wi <= 0 || Ho <= 0 || Wo <= 0) return HS_ERR_BAD_ARG;
+    if (!target || !confusion || !eval_shape_given(x, batch, channels, Hi, Wi, Ho, Wo, Ho, Wo)) return HS_ERR_BAD_ARG;
     if (!eval_storage_ok(target_dtype) || num_classes <= 0 || channels > num_classes) return HS_ERR_BAD_ARG;
     if (num_classes > 256) return HS_ERR_BAD_ARG;                                            // uint8 class indices
-    if (num_classes > EVAL_MAX_CLASSES || batch > 65535 || (long)Ho * Wo > 0x7fffffffL - 4096) return HS_ERR_UNSUPPORTED;
-    const size_t lds = (size_t)num_classes * num_classes * sizeof(unsigned);
-    const long stride = per_image ? (long)num_classes * num_classes : 0;
-    unsigned long long* out = reinterpret_cast<unsigned long long*>(confusion);
+    if (num_classes > EVAL_MAX_CLASSES || !eval_shape_fits(batch, Ho, Wo, Ho, Wo)) return HS_ERR_UNSUPPORTED;
+    const Hist h = eval_hist(num_classes, per_image, confusion);
     const size_t tsz = target_dtype == HS_EVAL_U8 ? 1 : 8;
+    const dim3 block(EVAL_THREADS);
     hipStream_t s = (hipStream_t)stream;
     if (is_exact2x(Hi, Wi, Ho, Wo)) {
         const int vec = aligned_to(target, 2 * tsz) && (!mask || aligned_to(mask, 4));
-        const long passes = ((long)Hi * (Wi / 2) + EVAL_THREADS / 4 - 1) / (EVAL_THREADS / 4);
-        const dim3 grid(eval_grid_x(passes, batch), (unsigned)batch);
-        if (target_dtype == HS_EVAL_U8)
-            hipLaunchKernelGGL(upsample2x_confusion_kernel<uint8_t>, grid, dim3(EVAL_THREADS), lds, s, x, channels, Hi, Wi,
-                               (const uint8_t*)target, num_classes, out, stride, mask, vec);
-        else
-            hipLaunchKernelGGL(upsample2x_confusion_kernel<int64_t>, grid, dim3(EVAL_THREADS), lds, s, x, channels, Hi, Wi,
-                               (const int64_t*)target, num_classes, out, stride, mask, vec);
+        with_target(target_dtype, target, [&](auto t) {
+            hipLaunchKernelGGL(upsample2x_confusion_kernel<pointee<decltype(t)>>, eval_grid_quads(Hi, Wi, batch), block, h.lds, s, x, channels, Hi, Wi,
+                               t, h.n, h.out, h.stride, mask, vec);
+        });
         return launch_status();
     }
     const int vec = (Wo & 3) == 0 && aligned_to(target, tsz == 1 ? 4 : 16) && (!mask || aligned_to(mask, 4));
-    const long passes = ((long)Ho * ((Wo + 3) / 4) + EVAL_THREADS - 1) / EVAL_THREADS;
-    const dim3 grid(eval_grid_x(passes, batch), (unsigned)batch);
     const float sy = (float)Hi / (float)Ho, sx = (float)Wi / (float)Wo;
-    if (target_dtype == HS_EVAL_U8)
-        hipLaunchKernelGGL(upsample_confusion_kernel<uint8_t>, grid, dim3(EVAL_THREADS), lds, s, x, channels, Hi, Wi, Ho, Wo, sy, sx,
-                           (const uint8_t*)target, num_classes, out, stride, mask, vec);
-    else
-        hipLaunchKernelGGL(upsample_confusion_kernel<int64_t>, grid, dim3(EVAL_THREADS), lds, s, x, channels, Hi, Wi, Ho, Wo, sy, sx,
-                           (const int64_t*)target, num_classes, out, stride, mask, vec);
+    with_target(target_dtype, target, [&](auto t) {
+        hipLaunchKernelGGL(upsample_confusion_kernel<pointee<decltype(t)>>, eval_grid_rows4(Ho, Wo, batch), block, h.lds, s, x, channels, Hi, Wi, Ho, Wo,
+                           sy, sx, t, h.n, h.out, h.stride, mask, vec);
+    });
     return launch_status();
 }
 
 extern "C" int hs_upsample2_confusion_fwd(const float* x, int32_t batch, int32_t channels, int32_t Hi, int32_t Wi, int32_t Hm, int32_t Wm,
                                           int32_t Ho, int32_t Wo, const void* target, int32_t target_dtype, int32_t num_classes,
                                           int32_t per_image, int64_t* confusion, uint8_t* mask, void* stream) {
-    if (!x || batch <= 0 || channels <= 0 || Hi <= 0 || Wi <= 0 || Hm <= 0 || Wm <= 0 || Ho <= 0 || Wo <= 0) return HS_ERR_BAD_ARG;
+    if (!eval_shape_given(x, batch, channels, Hi, Wi, Hm, Wm, Ho, Wo)) return HS_ERR_BAD_ARG;
     const bool count = target != nullptr;
     if (count != (confusion != nullptr) || (!count && !mask)) return HS_ERR_BAD_ARG;          // masks only: neither, and a mask to write
     if (count) {
@@ -301,40 +297,25 @@ extern "C" int hs_upsample2_confusion_fwd(const float* x, int32_t batch, int32_t
     } else if (channels > 256) {
         return HS_ERR_UNSUPPORTED;                                                            // as hs_upsample_argmax_fwd
     }
-    if (batch > 65535 || (long)Ho * Wo > 0x7fffffffL - 4096 || (long)Hm * Wm > 0x7fffffffL - 4096) return HS_ERR_UNSUPPORTED;
-    const int n = count ? num_classes : 0;
-    const size_t lds = (size_t)n * n * sizeof(unsigned);
-    const long stride = per_image ? (long)n * n : 0;
-    unsigned long long* out = reinterpret_cast<unsigned long long*>(confusion);
-    const bool u8 = !count || target_dtype == HS_EVAL_U8;                                     // masks only: either instantiation serves
-    const bool aligned = (!count || aligned_to(target, u8 ? 4 : 16)) && (!mask || aligned_to(mask, 4));
+    if (!eval_shape_fits(batch, Hm, Wm, Ho, Wo)) return HS_ERR_UNSUPPORTED;
+    const Hist h = eval_hist(num_classes, per_image, confusion);
+    const int dtype = count ? target_dtype : HS_EVAL_U8;                                      // masks only: the uint8 instantiation, a null pointer
+    const bool aligned = (!count || aligned_to(target, dtype == HS_EVAL_U8 ? 4 : 16)) && (!mask || aligned_to(mask, 4));
+    const dim3 block(EVAL_THREADS);
     hipStream_t s = (hipStream_t)stream;
     if (is_exact2x(Hi, Wi, Hm, Wm) && is_exact2x(Hm, Wm, Ho, Wo)) {
         const int vec = aligned;                                                              // rows of 8 k label pixels
-        const long passes = ((long)Hi * (Wi / 2) + EVAL_THREADS / 4 - 1) / (EVAL_THREADS / 4);
-        const dim3 grid(eval_grid_x(passes, batch), (unsigned)batch);
-        if (u8)
-            hipLaunchKernelGGL(upsample2x2x_confusion_kernel<uint8_t>, grid, dim3(EVAL_THREADS), lds, s, x, channels, Hi, Wi,
-                               (const uint8_t*)target, n, out, stride, mask, vec);
-        else
-            hipLaunchKernelGGL(upsample2x2x_confusion_kernel<int64_t>, grid, dim3(EVAL_THREADS), lds, s, x, channels, Hi, Wi,
-                               (const int64_t*)target, n, out, stride, mask, vec);
+        with_target(dtype, target, [&](auto t) {
+            hipLaunchKernelGGL(upsample2x2x_confusion_kernel<pointee<decltype(t)>>, eval_grid_quads(Hi, Wi, batch), block, h.lds, s, x, channels, Hi, Wi,
+                               t, h.n, h.out, h.stride, mask, vec);
+        });
         return launch_status();
     }
-    Stages2 st;
-    st.Hi = Hi; st.Wi = Wi; st.Hm = Hm; st.Wm = Wm; st.Ho = Ho; st.Wo = Wo;
-    st.exact1 = is_exact2x(Hi, Wi, Hm, Wm); st.exact2 = is_exact2x(Hm, Wm, Ho, Wo);           // the form hs_upsample_bilinear_fwd takes per stage
-    st.sy1 = (float)Hi / (float)Hm; st.sx1 = (float)Wi / (float)Wm;
-    st.sy2 = (float)Hm / (float)Ho; st.sx2 = (float)Wm / (float)Wo;
     const int vec = (Wo & 3) == 0 && aligned;
-    const long passes = ((long)Ho * ((Wo + 3) / 4) + EVAL_THREADS - 1) / EVAL_THREADS;
-    const dim3 grid(eval_grid_x(passes, batch), (unsigned)batch);
-    if (u8)
-        hipLaunchKernelGGL(upsample2_confusion_kernel<uint8_t>, grid, dim3(EVAL_THREADS), lds, s, x, channels, st,
-                           (const uint8_t*)target, n, out, stride, mask, vec);
-    else
-        hipLaunchKernelGGL(upsample2_confusion_kernel<int64_t>, grid, dim3(EVAL_THREADS), lds, s, x, channels, st,
-                           (const int64_t*)target, n, out, stride, mask, vec);
+    with_target(dtype, target, [&](auto t) {
+        hipLaunchKernelGGL(upsample2_confusion_kernel<pointee<decltype(t)>>, eval_grid_rows4(Ho, Wo, batch), block, h.lds, s, x, channels,
+                           stages2(Hi, Wi, Hm, Wm, Ho, Wo), t, h.n, h.out, h.stride, mask, vec);
+    });
     return launch_status();
 }
 
@@ -343,21 +324,16 @@ extern "C" int hs_confusion_fwd(const void* pred, int32_t pred_dtype, const void
     if (!pred || !target || !confusion || batch <= 0 || elements <= 0 || num_classes <= 0) return HS_ERR_BAD_ARG;
     if (!eval_storage_ok(pred_dtype) || !eval_storage_ok(target_dtype)) return HS_ERR_BAD_ARG;
     if (num_classes > EVAL_MAX_CLASSES || batch > 65535 || elements > 0x7fffffffL - 4096) return HS_ERR_UNSUPPORTED;
-    const size_t lds = (size_t)num_classes * num_classes * sizeof(unsigned);
-    const long stride = per_image ? (long)num_classes * num_classes : 0;
-    unsigned long long* out = reinterpret_cast<unsigned long long*>(confusion);
+    const Hist h = eval_hist(num_classes, per_image, confusion);
     const size_t psz = pred_dtype == HS_EVAL_U8 ? 1 : 8, tsz = target_dtype == HS_EVAL_U8 ? 1 : 8;
     const int vec = (elements & 3) == 0 && aligned_to(pred, psz == 1 ? 4 : 16) && aligned_to(target, tsz == 1 ? 4 : 16);
-    const long passes = ((elements + 3) / 4 + EVAL_THREADS - 1) / EVAL_THREADS;
-    const dim3 grid(eval_grid_x(passes, batch), (unsigned)batch), block(EVAL_THREADS);
     hipStream_t s = (hipStream_t)stream;
-    const long N = (long)elements;
-#define HS_EVAL_LAUNCH(TP, TT) \
-    hipLaunchKernelGGL((confusion_kernel<TP, TT>), grid, block, lds, s, (const TP*)pred, (const TT*)target, N, num_classes, out, stride, vec)
-    if (pred_dtype == HS_EVAL_U8 && target_dtype == HS_EVAL_U8) HS_EVAL_LAUNCH(uint8_t, uint8_t);
-    else if (pred_dtype == HS_EVAL_U8) HS_EVAL_LAUNCH(uint8_t, int64_t);
-    else if (target_dtype == HS_EVAL_U8) HS_EVAL_LAUNCH(int64_t, uint8_t);
-    else HS_EVAL_LAUNCH(int64_t, int64_t);
-#undef HS_EVAL_LAUNCH
+    with_target(pred_dtype, pred, [&](auto p) {
+        with_target(target_dtype, target, [&](auto t) {
+            hipLaunchKernelGGL((confusion_kernel<pointee<decltype(p)>, pointee<decltype(t)>>), eval_grid_rows4(1, elements, batch), dim3(EVAL_THREADS),
+                               h.lds, s, p, t, (long)elements, h.n, h.out, h.stride, vec);
+        });
+    });
     return launch_status();
 }
+

@@ -1,8 +1,10 @@
 // Counting core of the on-device evaluation kernels (hs_eval.hip, hs_validate.hip): the per-workgroup n x n LDS histogram, the wave's
 // ballot aggregation into it, its one flush per workgroup, the label loads and the grid cap.  Shape and reasons: hs_eval.hip's header.
+// Below the device code, the host front of their entries: histogram operands, target-type dispatcher, grids and the shape check.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
+#include <type_traits>
 #include "hs_common.h"
 
 namespace hs {
@@ -80,5 +82,43 @@ static unsigned eval_grid_x(long passes, int batch) {
 }
 static bool eval_storage_ok(int dtype) { return dtype == HS_EVAL_U8 || dtype == HS_EVAL_I64; }
 static bool aligned_to(const void* p, size_t a) { return ((uintptr_t)p % a) == 0; }
+
+// ---- The launch front the scoring entries share.  Host code only.  Each entry keeps its own `vec` predicate and its own
+// order of refusals; what it takes from here is how the operands of a launch are made once the call is accepted.
+
+// The LDS histogram's operands: nothing is counted (n = 0, no LDS) where there is no matrix to count into.
+struct Hist { int n; size_t lds; long stride; unsigned long long* out; };
+static Hist eval_hist(int num_classes, int per_image, int64_t* confusion) {
+    const int n = confusion ? num_classes : 0;
+    return {n, (size_t)n * n * sizeof(unsigned), per_image ? (long)n * n : 0, reinterpret_cast<unsigned long long*>(confusion)};
+}
+
+// The ONE place an HS_EVAL_* code picks a kernel instantiation, as with_storage (hs_common.h) is for HS_DTYPE_*: calls f with `p` as a typed
+// pointer (`using TT = pointee<decltype(t)>;` ... kernel<TT>, t) and returns true; for any other code it calls nothing and returns false (the
+// entries refuse such a code with eval_storage_ok, at the place in their order where they always did).
+template <typename P> using pointee = std::remove_cv_t<std::remove_pointer_t<P>>;
+template <typename F> __attribute__((always_inline)) inline bool with_target(int dtype, const void* p, F&& f) {
+    if (dtype == HS_EVAL_U8) { f((const uint8_t*)p); return true; }
+    if (dtype == HS_EVAL_I64) { f((const int64_t*)p); return true; }
+    return false;
+}
+
+// Grids of the two mappings: one thread = 4 consecutive pixels of a row of (Ho, Wo); four lanes = one 2 x 4 block of pairs of (Hi, Wi)'s columns.
+static dim3 eval_grid_rows4(long Ho, long Wo, int batch) {
+    return dim3(eval_grid_x((Ho * ((Wo + 3) / 4) + EVAL_THREADS - 1) / EVAL_THREADS, batch), (unsigned)batch);
+}
+static dim3 eval_grid_quads(int Hi, int Wi, int batch) {
+    return dim3(eval_grid_x(((long)Hi * (Wi / 2) + EVAL_THREADS / 4 - 1) / (EVAL_THREADS / 4), batch), (unsigned)batch);
+}
+
+// The shape check of the resizing entries, x (batch, channels, Hi, Wi) -> mid (Hm, Wm) -> (Ho, Wo); a one-stage entry names its output as its
+// mid.  Two halves, because every entry refuses its class counts between them: given (else HS_ERR_BAD_ARG), fits (else HS_ERR_UNSUPPORTED:
+// blockIdx.y, and int pixel indices with room for a grid stride).
+static bool eval_shape_given(const void* x, int batch, int channels, int Hi, int Wi, int Hm, int Wm, int Ho, int Wo) {
+    return x && batch > 0 && channels > 0 && Hi > 0 && Wi > 0 && Hm > 0 && Wm > 0 && Ho > 0 && Wo > 0;
+}
+static bool eval_shape_fits(int batch, int Hm, int Wm, int Ho, int Wo) {
+    return batch <= 65535 && (long)Ho * Wo <= 0x7fffffffL - 4096 && (long)Hm * Wm <= 0x7fffffffL - 4096;
+}
 
 }  // namespace hs

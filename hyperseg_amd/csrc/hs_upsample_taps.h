@@ -165,6 +165,11 @@ __device__ __forceinline__ float tap_value(const float* __restrict__ plane, int 
 // General composition, any first and any second stage.  One thread = 4 consecutive label pixels of a row, as Row4: the label row's
 // two mid rows (ty2) and each pixel's two mid columns (tx2), and for each of those mid rows / columns its taps in x (ty1 / tx1).
 struct Stages2 { int Hi, Wi, Hm, Wm, Ho, Wo; int exact1, exact2; float sy1, sx1, sy2, sx2; };
+// (host) each stage in the form hs_upsample_bilinear_fwd takes for it
+inline Stages2 stages2(int Hi, int Wi, int Hm, int Wm, int Ho, int Wo) {
+    return {Hi, Wi, Hm, Wm, Ho, Wo, is_exact2x(Hi, Wi, Hm, Wm), is_exact2x(Hm, Wm, Ho, Wo),
+            (float)Hi / (float)Hm, (float)Wi / (float)Wm, (float)Hm / (float)Ho, (float)Wm / (float)Wo};
+}
 struct Row4x2 { Tap ty2; Tap ty1[2]; Tap tx2[4]; Tap tx1[4][2]; };
 __device__ __forceinline__ Row4x2 row4x2_taps(int yo, int q, const Stages2& s) {
     Row4x2 t;

@@ -14,6 +14,7 @@
 // the loss launch's workgroup per 256 pixels: thousands of workgroups flushing a histogram each meet on a few bins (the note above
 // cross_entropy_kernel: 38.5 us against 17).  No cross-workgroup waiting, no float atomics: the losses are plain stores.
 // confusion == nullptr: nothing is counted (loss and masks only).
+// Host side: three template fronts (one per entry and its weighted twin) over hs_eval.hip's launch front (hs_eval_count.h).
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include <cstdlib>
@@ -573,141 +574,110 @@ void upsample2x2x_ce_confusion_kernel(const float* __restrict__ x, int C, int Hi
     if (count) hist_flush(hist, nn, out + b * out_image_stride);
 }
 
+// ---- The launch fronts: one per entry and its weighted twin (CW: nothing, or the table), each kernel form launched from
+// one line.  Histogram operands, target-type dispatcher, grids and the shape check: hs_eval_count.h.
+
 template <typename T, typename... CW>
-static void launch_ce_score(dim3 grid, size_t lds, hipStream_t s, const T* x, const long long* target, int C, long hw, long long ignore_index,
-                            float* loss, int n, unsigned long long* out, long stride, uint8_t* mask, CW... cw) {
+static void launch_ce_score(dim3 grid, const Hist& h, hipStream_t s, const T* x, const long long* target, int C, long hw, long long ignore_index,
+                            float* loss, uint8_t* mask, CW... cw) {
     const dim3 block(EVAL_THREADS);
-    if (C == 12) hipLaunchKernelGGL((ce_score_kernel<T, 12, CW...>), grid, block, lds, s, x, target, C, hw, ignore_index, loss, n, out, stride, mask, cw...);
-    else if (C == 19) hipLaunchKernelGGL((ce_score_kernel<T, 19, CW...>), grid, block, lds, s, x, target, C, hw, ignore_index, loss, n, out, stride, mask, cw...);
-    else if (C == 21) hipLaunchKernelGGL((ce_score_kernel<T, 21, CW...>), grid, block, lds, s, x, target, C, hw, ignore_index, loss, n, out, stride, mask, cw...);
-    else hipLaunchKernelGGL((ce_score_kernel<T, 0, CW...>), grid, block, lds, s, x, target, C, hw, ignore_index, loss, n, out, stride, mask, cw...);
+    if (C == 12) hipLaunchKernelGGL((ce_score_kernel<T, 12, CW...>), grid, block, h.lds, s, x, target, C, hw, ignore_index, loss, h.n, h.out, h.stride, mask, cw...);
+    else if (C == 19) hipLaunchKernelGGL((ce_score_kernel<T, 19, CW...>), grid, block, h.lds, s, x, target, C, hw, ignore_index, loss, h.n, h.out, h.stride, mask, cw...);
+    else if (C == 21) hipLaunchKernelGGL((ce_score_kernel<T, 21, CW...>), grid, block, h.lds, s, x, target, C, hw, ignore_index, loss, h.n, h.out, h.stride, mask, cw...);
+    else hipLaunchKernelGGL((ce_score_kernel<T, 0, CW...>), grid, block, h.lds, s, x, target, C, hw, ignore_index, loss, h.n, h.out, h.stride, mask, cw...);
 }
 
-// what both entries ask of (classes, num_classes, confusion): nothing of num_classes where nothing is counted
-static int score_args(int classes, int num_classes, const void* confusion, int* n) {
-    *n = 0;
+// what the loss entries ask of (classes, num_classes, confusion): nothing of num_classes where nothing is counted.  The LDS limit is asked first,
+// so 257 classes are HS_ERR_UNSUPPORTED here and HS_ERR_BAD_ARG from hs_eval.hip's entries (kept as it is: DESIGN.md 3.11.3).
+static int score_args(int classes, int num_classes, const void* confusion) {
     if (!confusion) return HS_OK;
     if (num_classes > EVAL_MAX_CLASSES) return HS_ERR_UNSUPPORTED;                                   // the LDS histogram (<= 256: uint8 class indices)
     if (num_classes <= 0 || classes > num_classes) return HS_ERR_BAD_ARG;
-    *n = num_classes;
     return HS_OK;
 }
 
-// the one front of hs_cross_entropy_score_fwd and its weighted twin
+// hs_cross_entropy_score_fwd: logits in memory, one pixel per thread
 template <typename... CW>
 static int ce_score(int32_t dtype, const void* logits, const int64_t* target, int32_t batch, int32_t classes, int64_t pixels, int64_t ignore_index,
                     float* loss, int32_t num_classes, int32_t per_image, int64_t* confusion, uint8_t* mask, void* stream, CW... cw) {
     if (!logits || !target || !loss || batch <= 0 || classes <= 0 || pixels <= 0) return HS_ERR_BAD_ARG;
     if (!storage_known(dtype)) return HS_ERR_BAD_ARG;
     if (classes > 256) return HS_ERR_BAD_ARG;                                                 // uint8 class indices
-    int n = 0;
-    const int st = score_args(classes, num_classes, confusion, &n);
-    if (st != HS_OK) return st;
+    const int status = score_args(classes, num_classes, confusion);
+    if (status != HS_OK) return status;
     if (batch > 65535 || pixels > 0x7fffffffL - 4096) return HS_ERR_UNSUPPORTED;
-    const size_t lds = (size_t)n * n * sizeof(unsigned);
-    const long stride = per_image ? (long)n * n : 0;
-    const long passes = ((long)pixels + EVAL_THREADS - 1) / EVAL_THREADS;
-    const dim3 grid(eval_grid_x(passes, batch), (unsigned)batch);
-    unsigned long long* out = reinterpret_cast<unsigned long long*>(confusion);
-    const long long* t = (const long long*)target;
-    hipStream_t s = (hipStream_t)stream;
+    const Hist h = eval_hist(num_classes, per_image, confusion);
+    const dim3 grid(eval_grid_x(((long)pixels + EVAL_THREADS - 1) / EVAL_THREADS, batch), (unsigned)batch);
     with_storage(dtype, [&](auto tag) {
         using T = decltype(tag);
-        launch_ce_score<T>(grid, lds, s, (const T*)logits, t, classes, (long)pixels, ignore_index, loss, n, out, stride, mask, cw...);
+        launch_ce_score<T>(grid, h, (hipStream_t)stream, (const T*)logits, (const long long*)target, classes, (long)pixels, ignore_index, loss, mask, cw...);
     });
     return launch_status();
 }
 
-// ... and of hs_upsample_ce_confusion_fwd and its weighted twin
+// hs_upsample_ce_confusion_fwd: hs_upsample_confusion_fwd's choice of form (hs_eval.hip)
 template <typename... CW>
 static int upsample_ce_confusion(const float* x, int32_t batch, int32_t channels, int32_t Hi, int32_t Wi, int32_t Ho, int32_t Wo, const void* target,
                                  int32_t target_dtype, int64_t ignore_index, float* loss, int32_t num_classes, int32_t per_image,
                                  int64_t* confusion, uint8_t* mask, void* stream, CW... cw) {
-    if (!x || !target || !loss || batch <= 0 || channels <= 0 || Hi <= 0 || Wi <= 0 || Ho <= 0 || Wo <= 0) return HS_ERR_BAD_ARG;
+    if (!target || !loss || !eval_shape_given(x, batch, channels, Hi, Wi, Ho, Wo, Ho, Wo)) return HS_ERR_BAD_ARG;
     if (!eval_storage_ok(target_dtype) || channels > 256) return HS_ERR_BAD_ARG;               // uint8 class indices
-    int n = 0;
-    const int st = score_args(channels, num_classes, confusion, &n);
-    if (st != HS_OK) return st;
-    if (batch > 65535 || (long)Ho * Wo > 0x7fffffffL - 4096) return HS_ERR_UNSUPPORTED;
-    const size_t lds = (size_t)n * n * sizeof(unsigned);
-    const long stride = per_image ? (long)n * n : 0;
-    unsigned long long* out = reinterpret_cast<unsigned long long*>(confusion);
+    const int status = score_args(channels, num_classes, confusion);
+    if (status != HS_OK) return status;
+    if (!eval_shape_fits(batch, Ho, Wo, Ho, Wo)) return HS_ERR_UNSUPPORTED;
+    const Hist h = eval_hist(num_classes, per_image, confusion);
     const size_t tsz = target_dtype == HS_EVAL_U8 ? 1 : 8;
     const long long ii = (long long)ignore_index;
+    const dim3 block(EVAL_THREADS);
     hipStream_t s = (hipStream_t)stream;
     if (is_exact2x(Hi, Wi, Ho, Wo)) {
         const int vec = aligned_to(target, 2 * tsz) && (!mask || aligned_to(mask, 4));
-        const long passes = ((long)Hi * (Wi / 2) + EVAL_THREADS / 4 - 1) / (EVAL_THREADS / 4);
-        const dim3 grid(eval_grid_x(passes, batch), (unsigned)batch);
-        if (target_dtype == HS_EVAL_U8)
-            hipLaunchKernelGGL((upsample2x_ce_confusion_kernel<uint8_t, CW...>), grid, dim3(EVAL_THREADS), lds, s, x, channels, Hi, Wi,
-                               (const uint8_t*)target, ii, loss, n, out, stride, mask, vec, cw...);
-        else
-            hipLaunchKernelGGL((upsample2x_ce_confusion_kernel<int64_t, CW...>), grid, dim3(EVAL_THREADS), lds, s, x, channels, Hi, Wi,
-                               (const int64_t*)target, ii, loss, n, out, stride, mask, vec, cw...);
+        with_target(target_dtype, target, [&](auto t) {
+            hipLaunchKernelGGL((upsample2x_ce_confusion_kernel<pointee<decltype(t)>, CW...>), eval_grid_quads(Hi, Wi, batch), block, h.lds, s, x, channels,
+                               Hi, Wi, t, ii, loss, h.n, h.out, h.stride, mask, vec, cw...);
+        });
         return launch_status();
     }
     const int vec = (Wo & 3) == 0 && aligned_to(target, tsz == 1 ? 4 : 16) && aligned_to(loss, 16) && (!mask || aligned_to(mask, 4));
-    const long passes = ((long)Ho * ((Wo + 3) / 4) + EVAL_THREADS - 1) / EVAL_THREADS;
-    const dim3 grid(eval_grid_x(passes, batch), (unsigned)batch);
     const float sy = (float)Hi / (float)Ho, sx = (float)Wi / (float)Wo;
-    if (target_dtype == HS_EVAL_U8)
-        hipLaunchKernelGGL((upsample_ce_confusion_kernel<uint8_t, CW...>), grid, dim3(EVAL_THREADS), lds, s, x, channels, Hi, Wi, Ho, Wo, sy, sx,
-                           (const uint8_t*)target, ii, loss, n, out, stride, mask, vec, cw...);
-    else
-        hipLaunchKernelGGL((upsample_ce_confusion_kernel<int64_t, CW...>), grid, dim3(EVAL_THREADS), lds, s, x, channels, Hi, Wi, Ho, Wo, sy, sx,
-                           (const int64_t*)target, ii, loss, n, out, stride, mask, vec, cw...);
+    with_target(target_dtype, target, [&](auto t) {
+        hipLaunchKernelGGL((upsample_ce_confusion_kernel<pointee<decltype(t)>, CW...>), eval_grid_rows4(Ho, Wo, batch), block, h.lds, s, x, channels,
+                           Hi, Wi, Ho, Wo, sy, sx, t, ii, loss, h.n, h.out, h.stride, mask, vec, cw...);
+    });
     return launch_status();
 }
 
-// ... and of hs_upsample2_ce_confusion_fwd and its weighted twin: hs_upsample2_confusion_fwd's choice of form (hs_eval.hip).
+// hs_upsample2_ce_confusion_fwd: hs_upsample2_confusion_fwd's choice of form (hs_eval.hip)
 template <typename... CW>
 static int upsample2_ce_confusion(const float* x, int32_t batch, int32_t channels, int32_t Hi, int32_t Wi, int32_t Hm, int32_t Wm, int32_t Ho,
                                   int32_t Wo, const void* target, int32_t target_dtype, int64_t ignore_index, float* loss, int32_t num_classes,
                                   int32_t per_image, int64_t* confusion, uint8_t* mask, void* stream, CW... cw) {
-    if (!x || !target || !loss || batch <= 0 || channels <= 0 || Hi <= 0 || Wi <= 0 || Hm <= 0 || Wm <= 0 || Ho <= 0 || Wo <= 0)
-        return HS_ERR_BAD_ARG;
+    if (!target || !loss || !eval_shape_given(x, batch, channels, Hi, Wi, Hm, Wm, Ho, Wo)) return HS_ERR_BAD_ARG;
     if (!eval_storage_ok(target_dtype) || channels > 256) return HS_ERR_BAD_ARG;               // uint8 class indices
-    int n = 0;
-    const int status = score_args(channels, num_classes, confusion, &n);
+    const int status = score_args(channels, num_classes, confusion);
     if (status != HS_OK) return status;
-    if (batch > 65535 || (long)Ho * Wo > 0x7fffffffL - 4096 || (long)Hm * Wm > 0x7fffffffL - 4096) return HS_ERR_UNSUPPORTED;
-    const size_t lds = (size_t)n * n * sizeof(unsigned);
-    const long stride = per_image ? (long)n * n : 0;
-    unsigned long long* out = reinterpret_cast<unsigned long long*>(confusion);
-    const bool u8 = target_dtype == HS_EVAL_U8;
-    const bool aligned = aligned_to(target, u8 ? 4 : 16) && aligned_to(loss, 16) && (!mask || aligned_to(mask, 4));
+    if (!eval_shape_fits(batch, Hm, Wm, Ho, Wo)) return HS_ERR_UNSUPPORTED;
+    const Hist h = eval_hist(num_classes, per_image, confusion);
+    const bool aligned = aligned_to(target, target_dtype == HS_EVAL_U8 ? 4 : 16) && aligned_to(loss, 16) && (!mask || aligned_to(mask, 4));
     const long long ii = (long long)ignore_index;
+    const dim3 block(EVAL_THREADS);
     hipStream_t s = (hipStream_t)stream;
     // dev A/B knob (tools/validate_label_time.py): HS_VALIDATE_2X2X=0 sends 2x o 2x shapes to the general form; read per call, so that one
     // process can capture both
     const char* knob = getenv("HS_VALIDATE_2X2X");
     if (is_exact2x(Hi, Wi, Hm, Wm) && is_exact2x(Hm, Wm, Ho, Wo) && !(knob && atoi(knob) == 0)) {
         const int vec = aligned;                                                              // rows of 8 k label pixels
-        const long passes = ((long)Hi * (Wi / 2) + EVAL_THREADS / 4 - 1) / (EVAL_THREADS / 4);
-        const dim3 grid(eval_grid_x(passes, batch), (unsigned)batch);
-        if (u8)
-            hipLaunchKernelGGL((upsample2x2x_ce_confusion_kernel<uint8_t, CW...>), grid, dim3(EVAL_THREADS), lds, s, x, channels, Hi, Wi,
-                               (const uint8_t*)target, ii, loss, n, out, stride, mask, vec, cw...);
-        else
-            hipLaunchKernelGGL((upsample2x2x_ce_confusion_kernel<int64_t, CW...>), grid, dim3(EVAL_THREADS), lds, s, x, channels, Hi, Wi,
-                               (const int64_t*)target, ii, loss, n, out, stride, mask, vec, cw...);
+        with_target(target_dtype, target, [&](auto t) {
+            hipLaunchKernelGGL((upsample2x2x_ce_confusion_kernel<pointee<decltype(t)>, CW...>), eval_grid_quads(Hi, Wi, batch), block, h.lds, s, x, channels,
+                               Hi, Wi, t, ii, loss, h.n, h.out, h.stride, mask, vec, cw...);
+        });
         return launch_status();
     }
-    Stages2 st;
-    st.Hi = Hi; st.Wi = Wi; st.Hm = Hm; st.Wm = Wm; st.Ho = Ho; st.Wo = Wo;
-    st.exact1 = is_exact2x(Hi, Wi, Hm, Wm); st.exact2 = is_exact2x(Hm, Wm, Ho, Wo);           // the form hs_upsample_bilinear_fwd takes per stage
-    st.sy1 = (float)Hi / (float)Hm; st.sx1 = (float)Wi / (float)Wm;
-    st.sy2 = (float)Hm / (float)Ho; st.sx2 = (float)Wm / (float)Wo;
     const int vec = (Wo & 3) == 0 && aligned;
-    const long passes = ((long)Ho * ((Wo + 3) / 4) + EVAL_THREADS - 1) / EVAL_THREADS;
-    const dim3 grid(eval_grid_x(passes, batch), (unsigned)batch);
-    if (u8)
-        hipLaunchKernelGGL((upsample2_ce_confusion_kernel<uint8_t, CW...>), grid, dim3(EVAL_THREADS), lds, s, x, channels, st,
-                           (const uint8_t*)target, ii, loss, n, out, stride, mask, vec, cw...);
-    else
-        hipLaunchKernelGGL((upsample2_ce_confusion_kernel<int64_t, CW...>), grid, dim3(EVAL_THREADS), lds, s, x, channels, st,
-                           (const int64_t*)target, ii, loss, n, out, stride, mask, vec, cw...);
+    with_target(target_dtype, target, [&](auto t) {
+        hipLaunchKernelGGL((upsample2_ce_confusion_kernel<pointee<decltype(t)>, CW...>), eval_grid_rows4(Ho, Wo, batch), block, h.lds, s, x, channels,
+                           stages2(Hi, Wi, Hm, Wm, Ho, Wo), t, ii, loss, h.n, h.out, h.stride, mask, vec, cw...);
+    });
     return launch_status();
 }
 

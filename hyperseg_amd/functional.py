@@ -1365,22 +1365,21 @@ def _score_out(num_classes, channels, out, batch, per_image, device, counted=Fal
     return n, _eval_out(out, (batch, n, n) if per_image else (n, n), device)
 
 
-@_on_operand_device
-def upsample_confusion(x, size, target, num_classes, out=None, per_image=False, masks=False):
-    """``upsample_argmax(x, size)`` with every output pixel counted against ``target`` (B, Ho, Wo; uint8 or int64) in the same
-    launch (hs_upsample_confusion_fwd): ``out[t, p] += 1`` for every pixel whose target ``t`` is in [0, num_classes), every
-    other target value ignored (seg_utils.py:15-17).  ``out``: an int64 (n, n) -- ``per_image``: (B, n, n) -- matrix to
-    ACCUMULATE into; None allocates a zeroed one.  Returns ``out``, or ``(out, masks)`` with ``masks=True`` (the uint8 masks,
-    bit-identical to ``upsample_argmax``'s).  Nothing here reads the device: the call is capturable in a HIP graph."""
+def _scoring_operands(x, sizes, target, num_classes, out, per_image, counted=False, masks=True, loss=False):
+    """What the four scoring wrappers share.  ``sizes``: what follows (Hi, Wi) in the entry's argument list -- (Ho, Wo), or (Hm, Wm, Ho, Wo) --
+    the target's size last.  Checks the logits, the target and the matrix (``_score_out``), allocates the masks and the per-pixel losses that
+    were asked for, and returns ``(head, tail, out, mask, loss)``: the entry is called with ``*head, *tail`` -- a loss entry puts the ignore
+    index and the losses between the two."""
     b, c, hi, wi = _logits_shape(x)
-    ho, wo = (int(s) for s in size)
+    ho, wo = sizes[-2:]
     target = _eval_target(target, (b, ho, wo), x)
-    n, out = _score_out(num_classes, c, out, b, per_image, x.device, counted=True)
+    n, out = _score_out(num_classes, c, out, b, per_image, x.device, counted=counted)
+    xp = _hip.dev_ptr(x, 'x')
+    loss = torch.empty(b, ho, wo, device=x.device, dtype=torch.float32) if loss else None
     mask = torch.empty(b, ho, wo, device=x.device, dtype=torch.uint8) if masks else None
-    _hip.run.hs_upsample_confusion_fwd(_hip.dev_ptr(x, 'x'), b, c, hi, wi, ho, wo, target.data_ptr(), _EVAL_DTYPES[target.dtype], n,
-                                       1 if per_image else 0, out.data_ptr(), mask.data_ptr() if masks else None,
-                                       _hip.stream_ptr())
-    return (out, mask) if masks else out
+    head = (xp, b, c, hi, wi, *sizes, target.data_ptr(), _EVAL_DTYPES[target.dtype])
+    tail = (n, 1 if per_image else 0, _hip.ptr(out), _hip.ptr(mask), _hip.stream_ptr())
+    return head, tail, out, mask, loss
 
 
 def _size2(size, name):
@@ -1388,6 +1387,31 @@ def _size2(size, name):
     if h <= 0 or w <= 0:
         raise ValueError(f'{name} must be a positive (H, W), got {tuple(size)}')
     return h, w
+
+
+def _label_stages(x, mid_size, target):
+    """The two stages of a wrapper at the label's resolution: ``(target, (hm, wm, ho, wo), one_stage)`` -- ``one_stage``: the target is at
+    ``mid_size`` already, or ``x`` is, and the one-stage wrapper serves, resizing straight to (ho, wo)."""
+    b, _, hi, wi = _logits_shape(x)
+    hm, wm = _size2(mid_size, 'mid_size')
+    target = _eval_labels(target, 'target')
+    if target.dim() != 3 or target.shape[0] != b:
+        raise ValueError(f'target has shape {tuple(target.shape)}, expected ({b}, Ho, Wo)')
+    ho, wo = int(target.shape[1]), int(target.shape[2])
+    return target, (hm, wm, ho, wo), (ho, wo) == (hm, wm) or (hi, wi) == (hm, wm)
+
+
+@_on_operand_device
+def upsample_confusion(x, size, target, num_classes, out=None, per_image=False, masks=False):
+    """``upsample_argmax(x, size)`` with every output pixel counted against ``target`` (B, Ho, Wo; uint8 or int64) in the same
+    launch (hs_upsample_confusion_fwd): ``out[t, p] += 1`` for every pixel whose target ``t`` is in [0, num_classes), every
+    other target value ignored (seg_utils.py:15-17).  ``out``: an int64 (n, n) -- ``per_image``: (B, n, n) -- matrix to
+    ACCUMULATE into; None allocates a zeroed one.  Returns ``out``, or ``(out, masks)`` with ``masks=True`` (the uint8 masks,
+    bit-identical to ``upsample_argmax``'s).  Nothing here reads the device: the call is capturable in a HIP graph."""
+    ho, wo = (int(s) for s in size)
+    head, tail, out, mask, _ = _scoring_operands(x, (ho, wo), target, num_classes, out, per_image, counted=True, masks=masks)
+    _hip.run.hs_upsample_confusion_fwd(*head, *tail)
+    return (out, mask) if masks else out
 
 
 @_on_operand_device
@@ -1398,20 +1422,11 @@ def upsample2_confusion(x, mid_size, target, num_classes, out=None, per_image=Fa
     counts are bit-identical to ``upsample_bilinear(upsample_bilinear(x, mid_size), target.shape[1:]).argmax(1)`` and its count.
     ``out``, ``per_image``, ``masks``, the returned value and the errors raised are ``upsample_confusion``'s, which this simply
     calls when the target is at ``mid_size`` already (or ``x`` is).  Nothing here reads the device: the call is capturable."""
-    b, c, hi, wi = _logits_shape(x)
-    hm, wm = _size2(mid_size, 'mid_size')
-    target = _eval_labels(target, 'target')
-    if target.dim() != 3 or target.shape[0] != b:
-        raise ValueError(f'target has shape {tuple(target.shape)}, expected ({b}, Ho, Wo)')
-    ho, wo = int(target.shape[1]), int(target.shape[2])
-    if (ho, wo) == (hm, wm) or (hi, wi) == (hm, wm):
-        return upsample_confusion(x, (ho, wo), target, num_classes, out=out, per_image=per_image, masks=masks)
-    target = _eval_target(target, (b, ho, wo), x)
-    n, out = _score_out(num_classes, c, out, b, per_image, x.device, counted=True)
-    mask = torch.empty(b, ho, wo, device=x.device, dtype=torch.uint8) if masks else None
-    _hip.run.hs_upsample2_confusion_fwd(_hip.dev_ptr(x, 'x'), b, c, hi, wi, hm, wm, ho, wo, target.data_ptr(), _EVAL_DTYPES[target.dtype], n,
-                                        1 if per_image else 0, out.data_ptr(), mask.data_ptr() if masks else None,
-                                        _hip.stream_ptr())
+    target, sizes, one_stage = _label_stages(x, mid_size, target)
+    if one_stage:
+        return upsample_confusion(x, sizes[2:], target, num_classes, out=out, per_image=per_image, masks=masks)
+    head, tail, out, mask, _ = _scoring_operands(x, sizes, target, num_classes, out, per_image, counted=True, masks=masks)
+    _hip.run.hs_upsample2_confusion_fwd(*head, *tail)
     return (out, mask) if masks else out
 
 
@@ -1515,16 +1530,8 @@ def upsample_ce_confusion(x, size, target, ignore_index, num_classes, out=None, 
     function's; ``num_classes=None``: nothing counted, ``out`` None).  ``weight``: the fp32 (C,) class-weight table on ``x``'s device
     (hs_upsample_ce_confusion_weighted_fwd): ``loss`` is the weighted ``PixelCrossEntropy``'s, masks and counts as without.  The resized
     logits never exist in memory.  Capturable (a graph holds the table's address)."""
-    b, c, hi, wi = _logits_shape(x)
-    ho, wo = _size2(size, 'size')
-    target = _eval_target(target, (b, ho, wo), x)
-    n, out = _score_out(num_classes, c, out, b, per_image, x.device)
-    xp = _hip.dev_ptr(x, 'x')
-    loss = torch.empty(b, ho, wo, device=x.device, dtype=torch.float32)
-    mask = torch.empty(b, ho, wo, device=x.device, dtype=torch.uint8)
-    tail = (int(ignore_index), loss.data_ptr(), n, 1 if per_image else 0, _hip.ptr(out), mask.data_ptr(), _hip.stream_ptr())
-    loss_launch('hs_upsample_ce_confusion_fwd', class_weight_table(weight, c, x.device),
-                xp, b, c, hi, wi, ho, wo, target.data_ptr(), _EVAL_DTYPES[target.dtype], *tail)
+    head, tail, out, mask, loss = _scoring_operands(x, _size2(size, 'size'), target, num_classes, out, per_image, loss=True)
+    loss_launch('hs_upsample_ce_confusion_fwd', class_weight_table(weight, x.shape[1], x.device), *head, int(ignore_index), loss.data_ptr(), *tail)
     return loss, out, mask
 
 
@@ -1537,22 +1544,11 @@ def upsample2_ce_confusion(x, mid_size, target, ignore_index, num_classes, out=N
     bit-identical to ``PixelCrossEntropy`` on ``upsample_bilinear(upsample_bilinear(x, mid_size), target.shape[1:])``, masks and counts to
     ``upsample2_confusion``'s.  ``ignore_index``, ``num_classes``, ``out``, ``per_image``, ``weight`` and the errors raised are
     ``upsample_ce_confusion``'s, which this simply calls when the target is at ``mid_size`` already (or ``x`` is).  Capturable."""
-    b, c, hi, wi = _logits_shape(x)
-    hm, wm = _size2(mid_size, 'mid_size')
-    target = _eval_labels(target, 'target')
-    if target.dim() != 3 or target.shape[0] != b:
-        raise ValueError(f'target has shape {tuple(target.shape)}, expected ({b}, Ho, Wo)')
-    ho, wo = int(target.shape[1]), int(target.shape[2])
-    if (ho, wo) == (hm, wm) or (hi, wi) == (hm, wm):
-        return upsample_ce_confusion(x, (ho, wo), target, ignore_index, num_classes, out=out, per_image=per_image, weight=weight)
-    target = _eval_target(target, (b, ho, wo), x)
-    n, out = _score_out(num_classes, c, out, b, per_image, x.device)
-    xp = _hip.dev_ptr(x, 'x')
-    loss = torch.empty(b, ho, wo, device=x.device, dtype=torch.float32)
-    mask = torch.empty(b, ho, wo, device=x.device, dtype=torch.uint8)
-    tail = (int(ignore_index), loss.data_ptr(), n, 1 if per_image else 0, _hip.ptr(out), mask.data_ptr(), _hip.stream_ptr())
-    loss_launch('hs_upsample2_ce_confusion_fwd', class_weight_table(weight, c, x.device),
-                xp, b, c, hi, wi, hm, wm, ho, wo, target.data_ptr(), _EVAL_DTYPES[target.dtype], *tail)
+    target, sizes, one_stage = _label_stages(x, mid_size, target)
+    if one_stage:
+        return upsample_ce_confusion(x, sizes[2:], target, ignore_index, num_classes, out=out, per_image=per_image, weight=weight)
+    head, tail, out, mask, loss = _scoring_operands(x, sizes, target, num_classes, out, per_image, loss=True)
+    loss_launch('hs_upsample2_ce_confusion_fwd', class_weight_table(weight, x.shape[1], x.device), *head, int(ignore_index), loss.data_ptr(), *tail)
     return loss, out, mask
 
 

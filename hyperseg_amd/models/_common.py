@@ -126,16 +126,12 @@ class Epilogue:
                 if label != size and not self.loss_at_label:
                     raise ValueError(f'the loss needs a target at the output size {size}, got {label}')
                 weighted = {} if self.weight is None else dict(weight=self.weight)          # (the unweighted call is what it was)
-                if label != size:
-                    if tuple(p.shape[2:]) != size:
-                        per_pixel, _, masks = HF.upsample2_ce_confusion(p, size, target, self.ignore_index, num_classes, out=out,
-                                                                        per_image=per_image, **weighted)
-                    else:
-                        per_pixel, _, masks = HF.upsample_ce_confusion(p, label, target, self.ignore_index, num_classes, out=out,
-                                                                       per_image=per_image, **weighted)
-                    return masks, per_pixel
-                per_pixel, _, masks = HF.upsample_ce_confusion(p, size, target, self.ignore_index, num_classes, out=out, per_image=per_image,
-                                                               **weighted)
+                if label != size and tuple(p.shape[2:]) != size:
+                    per_pixel, _, masks = HF.upsample2_ce_confusion(p, size, target, self.ignore_index, num_classes, out=out,
+                                                                    per_image=per_image, **weighted)
+                else:                                                   # (a target at the frame's size: label == size)
+                    per_pixel, _, masks = HF.upsample_ce_confusion(p, label, target, self.ignore_index, num_classes, out=out,
+                                                                   per_image=per_image, **weighted)
                 return masks, per_pixel
             if label != size and tuple(p.shape[2:]) != size:
                 return HF.upsample2_confusion(p, size, target, num_classes, out=out, per_image=per_image, masks=True)[1]
@@ -338,43 +334,44 @@ class HyperGenBase(EpochOnModeSwitch, nn.Module):
         self._count(confmat, target, masks, per_image)
         return masks
 
-    def _validate_fused(self, x, target, criterion, n, staged=False):
-        """validate()'s fused route applies: see there.  ``staged``: a serving wrapper copies ``x`` and ``target`` to the model's device
-        first (``GraphedModel.validate``), so where they live now does not matter."""
+    def _validate_route(self, x, target, criterion, n, staged=False):
+        """The fused route validate() takes for this batch -- see there: 'frame' (a target at the frame's size), 'label' (a target of
+        another size: the route at the LABEL's resolution, ``criterion.k`` and the pixel bound taken on the label's pixels) or None (the
+        composed route).  ``staged``: a serving wrapper copies ``x`` and ``target`` to the model's device first
+        (``GraphedModel.validate``), so where they live now does not matter."""
         from ..training import BootstrappedCrossEntropyLoss, USE_HIP_BOOTSTRAP, USE_FUSED_LOSS
         if not (isinstance(x, torch.Tensor) and x.dim() == 4 and not self.training and isinstance(target, torch.Tensor)
                 and (staged or (x.is_cuda and target.is_cuda)) and self._scorable(target, x.shape[0], n)):
-            return False
+            return None
         if not (isinstance(criterion, BootstrappedCrossEntropyLoss) and criterion.score is None and USE_HIP_BOOTSTRAP and USE_FUSED_LOSS):
-            return False
+            return None
         if criterion.weight is not None:                        # a table the HIP loss takes (asked once per table), on the model's device
             device = next(self.parameters()).device if staged else x.device
             classes = getattr(self.decoder, 'num_classes', None)      # the logits' channels (a decoder that does not say: composed route)
             if classes is None or not criterion.weight_takes_hip(classes, device):
-                return False
-        if tuple(target.shape) != (x.shape[0],) + self.frame_size(x) or x.shape[0] > 65535:
-            return False
-        pixels = target.shape[1] * target.shape[2]
-        return criterion.k < pixels < 2 ** 31
+                return None
+        if x.shape[0] > 65535 or not criterion.k < target.shape[1] * target.shape[2] < 2 ** 31:
+            return None
+        return 'frame' if tuple(target.shape[1:]) == self.frame_size(x) else 'label'
+
+    def _validate_fused(self, x, target, criterion, n, staged=False):
+        return self._validate_route(x, target, criterion, n, staged) == 'frame'
 
     def _validate_fused_at_label(self, x, target, criterion, n, staged=False):
-        """validate()'s fused route at the LABEL's resolution applies: ``_validate_fused``'s conditions for a target of ANOTHER size than the
-        frame's, ``criterion.k`` and the pixel bound taken on the label's pixels."""
-        from ..training import BootstrappedCrossEntropyLoss, USE_HIP_BOOTSTRAP, USE_FUSED_LOSS
-        if not (isinstance(x, torch.Tensor) and x.dim() == 4 and not self.training and isinstance(target, torch.Tensor)
-                and (staged or (x.is_cuda and target.is_cuda)) and self._scorable(target, x.shape[0], n)):
-            return False
-        if not (isinstance(criterion, BootstrappedCrossEntropyLoss) and criterion.score is None and USE_HIP_BOOTSTRAP and USE_FUSED_LOSS):
-            return False
-        if criterion.weight is not None:                        # (as _validate_fused)
-            device = next(self.parameters()).device if staged else x.device
-            classes = getattr(self.decoder, 'num_classes', None)
-            if classes is None or not criterion.weight_takes_hip(classes, device):
-                return False
-        if tuple(target.shape[1:]) == self.frame_size(x) or x.shape[0] > 65535:
-            return False
-        pixels = target.shape[1] * target.shape[2]
-        return criterion.k < pixels < 2 ** 31
+        return self._validate_route(x, target, criterion, n, staged) == 'label'
+
+    def _validate_step(self, x, target, criterion, n, out, per_image, route):
+        """The fused validation step of ``route`` ('frame' or 'label': ``_validate_route``), eager or under capture: the forward with the
+        scoring epilogue as its last launch, then the criterion's batch reduction.  ``x`` resized, ``target`` encoded; returns ``(loss,
+        masks)``."""
+        from ..autograd import BootstrapMeanOfBatch
+        at = dict(loss_at_label=True) if route == 'label' else {}       # (the same-size epilogue is what it was)
+        got = self.process_single_tensor(x, epilogue=Epilogue(Score(target, n, out, per_image), ignore_index=criterion.ignore_index,
+                                                                   weight=criterion.weight, **at))
+        if not isinstance(got, tuple):
+            raise RuntimeError('the decoder returned logits where its epilogue was asked for: nothing was scored')
+        masks, per_pixel = got
+        return BootstrapMeanOfBatch.apply(per_pixel.flatten(1), criterion.k, criterion.thresh), masks
 
     @torch.no_grad()
     def validate(self, x, target, criterion, confmat=None, per_image=False):
@@ -405,22 +402,15 @@ class HyperGenBase(EpochOnModeSwitch, nn.Module):
         if not isinstance(target, torch.Tensor) or target.is_floating_point() or target.dim() != 3 or target.shape[0] != batch:
             raise ValueError(f'target must be ({batch}, H, W) class indices (uint8 or int64), got {getattr(target, "dtype", type(target))} '
                              f'{tuple(getattr(target, "shape", ()))}')
-        fused = self._validate_fused(x, target, criterion, n)
-        at_label = not fused and self._validate_fused_at_label(x, target, criterion, n)
-        if fused or at_label:
-            from ..autograd import BootstrapMeanOfBatch
+        route = self._validate_route(x, target, criterion, n)
+        if route is not None:
             out = None
             if confmat is not None:
                 out = torch.zeros((x.shape[0], n, n), dtype=torch.int64, device=x.device) if per_image else confmat.matrix(x.device)
-            at = dict(loss_at_label=True) if at_label else {}       # (the same-size epilogue is what it was)
-            got = self.process_single_tensor(x, epilogue=Epilogue(Score(target, n, out, per_image), ignore_index=criterion.ignore_index,
-                                                                       weight=criterion.weight, **at))
-            if not isinstance(got, tuple):
-                raise RuntimeError('the decoder returned logits where its epilogue was asked for: nothing was scored')
-            masks, per_pixel = got
+            loss, masks = self._validate_step(x, target, criterion, n, out, per_image, route)
             if confmat is not None and per_image:
                 confmat.add_per_image(out)
-            return BootstrapMeanOfBatch.apply(per_pixel.flatten(1), criterion.k, criterion.thresh), masks
+            return loss, masks
         pred = self._logits_at(x, target.shape[1:])
         target = target.to(pred.device)
         loss = criterion(pred, target.long())

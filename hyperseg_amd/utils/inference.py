@@ -1072,11 +1072,10 @@ class GraphedModel(nn.Module):
         model = self.model
         n = self.num_classes
         codec, seen = self._codec_of(target)
-        graphable = self._graphable(x) and isinstance(target, torch.Tensor) and target.numel() > 0 and hasattr(model, '_validate_fused')
-        at_label = False
-        if graphable and not model._validate_fused(x, seen, criterion, n, staged=True):
-            at_label = graphable = model._validate_fused_at_label(x, seen, criterion, n, staged=True)
-        if not graphable:
+        route = None
+        if self._graphable(x) and isinstance(target, torch.Tensor) and target.numel() > 0 and hasattr(model, '_validate_route'):
+            route = model._validate_route(x, seen, criterion, n, staged=True)
+        if route is None:
             x, target = self._to_model_device(x, target)
             if n is None:
                 return model.validate(x, target, criterion)
@@ -1087,15 +1086,9 @@ class GraphedModel(nn.Module):
                criterion.ignore_index, None if criterion.weight is None else criterion.weight.data_ptr()) + codec
         entry = self._graphs.get(key)
         if entry is None:
-            from ..autograd import BootstrapMeanOfBatch
-
             def run(xs, ts, out):
                 ts = model.encoded(ts) if codec else ts
-                at = dict(loss_at_label=True) if at_label else {}
-                masks, per_pixel = model.process_single_tensor(
-                    model.resized(xs), epilogue=Epilogue(Score(ts, n, out, self.per_image), ignore_index=criterion.ignore_index,
-                                                              weight=criterion.weight, **at))
-                return BootstrapMeanOfBatch.apply(per_pixel.flatten(1), criterion.k, criterion.thresh), masks
+                return model._validate_step(model.resized(xs), ts, criterion, n, out, self.per_image, route)
 
             entry = self._capture_counting(key, [x, target], device, run, confusion)
         return self._replay(entry, [x, target], device)
