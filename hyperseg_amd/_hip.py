@@ -210,6 +210,12 @@ SIGNATURES = {
     'hs_gemm_split_fwd': ([vp, vp, vp, vp, vp, i32, vp, vp, i32, i32, i32, i32, i32, vp], STATUS),
     'hs_gemm_split_conv2x2_fwd': ([vp, vp, vp, vp, i32, vp, vp, i32, i32, i32, i32, i32, i32, vp], STATUS),
     'hs_gemm_split_up2_fwd': ([vp, vp, vp, vp, i32, vp, i32, i32, i32, i32, i32, i32, vp], STATUS),
+    'hs_depthwise_route': ([i32] * 11, C.c_int),
+    'hs_mbconv_route': ([i32] * 11, C.c_int),
+    'hs_stem_dw_route': ([i32] * 9, C.c_int),
+    'hs_stem_route': ([i32] * 3, C.c_int),
+    'hs_se_gate_route': ([i32] * 5, C.c_int),
+    'hs_pointwise_route': ([i32] * 5, C.c_int),
     'hs_pooled_shift_fwd': ([vp, i32, C.c_float, vp, vp, vp, i32, i32, vp], STATUS),
 }
 EXPORTS = list(SIGNATURES)

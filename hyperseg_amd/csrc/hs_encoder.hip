@@ -546,6 +546,39 @@ void se_gate_fused_kernel(const float* __restrict__ partial, int nblk, float inv
 
 using namespace hs;
 
+// threads per workgroup of a depthwise launch (one thread = one output quad), and the bytes of the tiled form's input band of a 256-thread
+// workgroup (Wo % 4 == 0, Wo / 4 divides 256): the launcher and the route predicate share both
+static int depthwise_threads(int Ho, int Wo) {
+    const int quads = Ho * ((Wo + 3) / 4);
+    return quads >= 256 ? 256 : ((quads + 63) / 64) * 64;
+}
+static size_t depthwise_tile_lds(int k, int stride, int Wo) {
+    const int rows_out = 256 / (Wo / 4), rows_in = (rows_out - 1) * stride + k, tw = ((Wo - 1) * stride + k + 3) & ~3;
+    return (size_t)rows_in * tw * sizeof(float);
+}
+
+// Which instantiation of depthwise_conv_kernel a launch gets: HS_DW_ROUTE(form, k, stride, PL) of include/hyperseg_hip.h, or
+// HS_ERR_UNSUPPORTED.  The launcher and hs_depthwise_route both call this; nothing else decides.
+// TILED -- for batched work (>= 8192 planes) and for every 5 x 5 launch (8.75 swishes per output there), on planes of >= 256 output quads:
+// the 3 x 3 launches of a batch-1 encoder are latency-bound and the extra barrier costs more than the taps' swishes (HyperSeg-M,
+// round 2: 1009 vs 1020 frames/s with it on everywhere; round 3 same-box A/B, profiles/round3_gemm_split_policy_ab.txt section 6:
+// 5 x 5 only 0.7758 ms per frame against 0.7801, everywhere 0.7794, 5 x 5 incl. the 128-thread maps 0.7822).
+static int depthwise_route(long nplanes, int k, int stride, int pad_l, int W, int Ho, int Wo, bool x_aligned16, bool prologue) {
+    const int threads = depthwise_threads(Ho, Wo);
+    if (prologue && (nplanes >= 8192 || k == 5) && threads == 256 && (Wo & 3) == 0 && threads % (Wo / 4) == 0 && (k == 3 || k == 5) &&
+        (stride == 1 || stride == 2)) {
+        if (depthwise_tile_lds(k, stride, Wo) <= 64 * 1024) return HS_DW_ROUTE(HS_DW_FORM_TILED, k, stride, 0);
+    }
+    const bool vec = (W & 3) == 0 && x_aligned16;
+    int pl = -1;                                              // the vector forms: the left padding is a template constant
+    if (k == 3 && stride == 1) { if (vec && pad_l == 1) pl = 1; }
+    else if (k == 3 && stride == 2) { if (vec && (pad_l == 0 || pad_l == 1)) pl = pad_l; }
+    else if (k == 5 && stride == 1) { if (vec && pad_l == 2) pl = 2; }
+    else if (k == 5 && stride == 2) { if (vec && (pad_l == 1 || pad_l == 2)) pl = pad_l; }
+    else return HS_ERR_UNSUPPORTED;
+    return pl >= 0 ? HS_DW_ROUTE(HS_DW_FORM_VECTOR, k, stride, pl) : HS_DW_ROUTE(HS_DW_FORM_GENERIC, k, stride, 0);
+}
+
 static int depthwise_conv_launch(const float* x, int32_t batch, int32_t channels, int32_t H, int32_t W,
                                  const float* w, int32_t k, int32_t stride, int32_t pad_t, int32_t pad_l,
                                  int32_t Ho, int32_t Wo, const float* scale, const float* shift, int32_t act,
@@ -557,7 +590,7 @@ static int depthwise_conv_launch(const float* x, int32_t batch, int32_t channels
     const long nplanes = (long)batch * channels;
     if (nplanes > 65535L * 65535L) return HS_ERR_UNSUPPORTED;
     const int quads = Ho * ((Wo + 3) / 4);
-    const int threads = quads >= 256 ? 256 : ((quads + 63) / 64) * 64;
+    const int threads = depthwise_threads(Ho, Wo);
     const int gy = nplanes > 65535 ? 32768 : (int)nplanes;
     dim3 grid((quads + threads - 1) / threads, gy, (unsigned)((nplanes + gy - 1) / gy));
     hipStream_t s = (hipStream_t)stream;
@@ -570,36 +603,44 @@ static int depthwise_conv_launch(const float* x, int32_t batch, int32_t channels
 #define HS_DW_(KK, SS, PP, SETV) hipLaunchKernelGGL((depthwise_conv_kernel<KK, SS, PP, false, SETV>), grid, dim3(threads), se_lds, s, x, w, scale, shift, \
                                              y, channels, H, W, Ho, Wo, pad_t, pad_l, act, pool_partial, in_scale, in_shift, (int)nplanes, se)
 #define HS_DW(KK, SS, PP) do { if (se_in) HS_DW_(KK, SS, PP, true); else HS_DW_(KK, SS, PP, false); } while (0)
+    // ONE predicate decides the instantiation, for this launch and for hs_depthwise_route
+    const int route = depthwise_route(nplanes, k, stride, pad_l, W, Ho, Wo, (((size_t)x) & 15) == 0, in_scale != nullptr);
+    if (route < 0) return route;
     // the LDS-tiled form: BN0 + swish prologue, whole output rows per workgroup (same thread -> output map, same partials)
-    const int wq = Wo / 4;
-    // For batched work (>= 8192 planes) and for every 5 x 5 launch (8.75 swishes per output there), on planes of >= 256 output quads:
-    // the 3 x 3 launches of a batch-1 encoder are latency-bound and the extra barrier costs more than the taps' swishes (HyperSeg-M,
-    // round 2: 1009 vs 1020 frames/s with it on everywhere; round 3 same-box A/B, profiles/round3_gemm_split_policy_ab.txt section 6:
-    // 5 x 5 only 0.7758 ms per frame against 0.7801, everywhere 0.7794, 5 x 5 incl. the 128-thread maps 0.7822).
-    if (in_scale && (nplanes >= 8192 || k == 5) && threads == 256 && (Wo & 3) == 0 && threads % wq == 0 && (k == 3 || k == 5) &&
-        (stride == 1 || stride == 2)) {
-        const int rows_out = threads / wq, rows_in = (rows_out - 1) * stride + k, tw = ((Wo - 1) * stride + k + 3) & ~3;
-        const size_t tile_lds = (size_t)rows_in * tw * sizeof(float);
+    if ((route >> 8) == HS_DW_FORM_TILED) {
+        const size_t tile_lds = depthwise_tile_lds(k, stride, Wo);         // the size the route was decided on
         const size_t lds = tile_lds > se_lds ? tile_lds : se_lds;
-        if (tile_lds <= 64 * 1024) {
 #define HS_DWT_(KK, SS, SETV) hipLaunchKernelGGL((depthwise_conv_kernel<KK, SS, -1, true, SETV>), grid, dim3(threads), lds, s, x, w, scale, shift, y, \
                                           channels, H, W, Ho, Wo, pad_t, pad_l, act, pool_partial, in_scale, in_shift, (int)nplanes, se)
 #define HS_DWT(KK, SS) do { if (se_in) HS_DWT_(KK, SS, true); else HS_DWT_(KK, SS, false); } while (0)
-            if (k == 3 && stride == 1) HS_DWT(3, 1); else if (k == 3) HS_DWT(3, 2); else if (stride == 1) HS_DWT(5, 1); else HS_DWT(5, 2);
+        if (k == 3 && stride == 1) HS_DWT(3, 1); else if (k == 3) HS_DWT(3, 2); else if (stride == 1) HS_DWT(5, 1); else HS_DWT(5, 2);
 #undef HS_DWT
 #undef HS_DWT_
-            return launch_status();
-        }
+        return launch_status();
     }
-    const bool vec = (W & 3) == 0 && (((size_t)x) & 15) == 0;
-    if (k == 3 && stride == 1) { if (vec && pad_l == 1) HS_DW(3, 1, 1); else HS_DW(3, 1, -1); }
-    else if (k == 3 && stride == 2) { if (vec && pad_l == 0) HS_DW(3, 2, 0); else if (vec && pad_l == 1) HS_DW(3, 2, 1); else HS_DW(3, 2, -1); }
-    else if (k == 5 && stride == 1) { if (vec && pad_l == 2) HS_DW(5, 1, 2); else HS_DW(5, 1, -1); }
-    else if (k == 5 && stride == 2) { if (vec && pad_l == 1) HS_DW(5, 2, 1); else if (vec && pad_l == 2) HS_DW(5, 2, 2); else HS_DW(5, 2, -1); }
-    else return HS_ERR_UNSUPPORTED;
+    switch (route) {
+        case HS_DW_ROUTE(HS_DW_FORM_VECTOR, 3, 1, 1): HS_DW(3, 1, 1); break;
+        case HS_DW_ROUTE(HS_DW_FORM_GENERIC, 3, 1, 0): HS_DW(3, 1, -1); break;
+        case HS_DW_ROUTE(HS_DW_FORM_VECTOR, 3, 2, 0): HS_DW(3, 2, 0); break;
+        case HS_DW_ROUTE(HS_DW_FORM_VECTOR, 3, 2, 1): HS_DW(3, 2, 1); break;
+        case HS_DW_ROUTE(HS_DW_FORM_GENERIC, 3, 2, 0): HS_DW(3, 2, -1); break;
+        case HS_DW_ROUTE(HS_DW_FORM_VECTOR, 5, 1, 2): HS_DW(5, 1, 2); break;
+        case HS_DW_ROUTE(HS_DW_FORM_GENERIC, 5, 1, 0): HS_DW(5, 1, -1); break;
+        case HS_DW_ROUTE(HS_DW_FORM_VECTOR, 5, 2, 1): HS_DW(5, 2, 1); break;
+        case HS_DW_ROUTE(HS_DW_FORM_VECTOR, 5, 2, 2): HS_DW(5, 2, 2); break;
+        case HS_DW_ROUTE(HS_DW_FORM_GENERIC, 5, 2, 0): HS_DW(5, 2, -1); break;
+        default: return HS_ERR_UNSUPPORTED;
+    }
 #undef HS_DW
 #undef HS_DW_
     return launch_status();
+}
+
+extern "C" int hs_depthwise_route(int32_t batch, int32_t channels, int32_t H, int32_t W, int32_t k, int32_t stride, int32_t pad_l,
+                                  int32_t Ho, int32_t Wo, int32_t x_aligned16, int32_t prologue) {
+    if (batch <= 0 || channels <= 0 || H <= 0 || W <= 0 || Ho <= 0 || Wo <= 0 || pad_l < 0) return HS_ERR_BAD_ARG;
+    if ((long)batch * channels > 65535L * 65535L) return HS_ERR_UNSUPPORTED;
+    return depthwise_route((long)batch * channels, k, stride, pad_l, W, Ho, Wo, x_aligned16 != 0, prologue != 0);
 }
 
 extern "C" int hs_depthwise_conv_fwd(const float* x, int32_t batch, int32_t channels, int32_t H, int32_t W,
@@ -643,6 +684,27 @@ extern "C" int hs_depthwise_pool_blocks(int32_t Ho, int32_t Wo) {
     return (quads + threads - 1) / threads;
 }
 
+static int se_early_fold(int nblk) { return nblk <= 256 ? 1 : (nblk <= 512 ? 2 : 4); }      // pseudo-channels per channel (<= 256 partials each)
+
+// Which form hs_se_gate_fwd takes (HS_SE_ROUTE_* of include/hyperseg_hip.h): the launcher and hs_se_gate_route both call this.
+// aligned16: partial and w_reduce are both 16-byte aligned (the early form reads them as quads).
+static int se_gate_route(int channels, int nblk, int c_squeezed, bool proj, bool aligned16) {
+    const long units = (long)channels * ((nblk & 3) == 0 ? nblk >> 2 : nblk);
+    if ((channels & 3) == 0 && channels <= 768 && c_squeezed <= SEF_MAX_CSQ && units <= 2048) return HS_SE_ROUTE_FUSED;
+    static const bool off = [] { const char* e = getenv("HS_SE_EARLY"); return e && atoi(e) == 0; }();      // dev A/B knob
+    const int fold = se_early_fold(nblk);
+    if (!off && !proj && (channels & 3) == 0 && channels * fold <= 4 * SEE_MAX_IT && c_squeezed <= 8 && (nblk & (4 * fold - 1)) == 0 &&
+        nblk <= 1024 && aligned16) return HS_SE_ROUTE_EARLY;
+    if (HS_SE_FUSED_WIDE && (channels & 3) == 0 && channels <= 256 && c_squeezed <= SEF_MAX_CSQ && units <= 6144) return HS_SE_ROUTE_FUSED_WIDE;
+    return HS_SE_ROUTE_TWO_LAUNCH;
+}
+
+extern "C" int hs_se_gate_route(int32_t channels, int32_t nblk, int32_t c_squeezed, int32_t with_w_proj, int32_t aligned16) {
+    if (channels <= 0 || nblk <= 0 || c_squeezed <= 0) return HS_ERR_BAD_ARG;
+    if (c_squeezed > 65535) return HS_ERR_UNSUPPORTED;
+    return se_gate_route(channels, nblk, c_squeezed, with_w_proj != 0, aligned16 != 0);
+}
+
 extern "C" int hs_se_gate_fwd(const float* partial, int32_t batch, int32_t channels, int32_t nblk, float inv_hw,
                               const float* w_reduce, const float* b_reduce, int32_t c_squeezed, const float* w_expand,
                               const float* b_expand, float* squeezed, float* gate, const float* w_proj, int32_t c_out,
@@ -653,24 +715,20 @@ extern "C" int hs_se_gate_fwd(const float* partial, int32_t batch, int32_t chann
     if (batch > 65535 || c_squeezed > 65535) return HS_ERR_UNSUPPORTED;
     hipStream_t s = (hipStream_t)stream;
     const int row_groups = w_proj ? (c_out + 63) / 64 : 1;
-    const long units = (long)channels * ((nblk & 3) == 0 ? nblk >> 2 : nblk);
-    if ((channels & 3) == 0 && channels <= 768 && c_squeezed <= SEF_MAX_CSQ && units <= 2048) {
+    const int route = se_gate_route(channels, nblk, c_squeezed, w_proj != nullptr, (((size_t)partial | (size_t)w_reduce) & 15) == 0);
+    if (route == HS_SE_ROUTE_FUSED) {
         hipLaunchKernelGGL((se_gate_fused_kernel<8, 3>), dim3((channels + 63) / 64, batch, row_groups), dim3(256), 0, s, partial, nblk,
                            inv_hw, w_reduce, b_reduce, w_expand, b_expand, channels, c_squeezed, squeezed, gate, w_proj, c_out,
                            out_scale, w_scaled);
         return launch_status();
     }
-    {   // the early blocks (many partials, few channels) as one single-workgroup launch
-        static const bool off = [] { const char* e = getenv("HS_SE_EARLY"); return e && atoi(e) == 0; }();      // dev A/B knob
-        const int fold = nblk <= 256 ? 1 : (nblk <= 512 ? 2 : 4);                // pseudo-channels per channel (<= 256 partials each)
-        if (!off && !w_proj && (channels & 3) == 0 && channels * fold <= 4 * SEE_MAX_IT && c_squeezed <= 8 && (nblk & (4 * fold - 1)) == 0 &&
-            nblk <= 1024 && ((size_t)partial & 15) == 0 && ((size_t)w_reduce & 15) == 0) {
-            hipLaunchKernelGGL(se_gate_early_kernel, dim3(1, batch), dim3(256), 0, s, partial, nblk / fold, inv_hw, w_reduce, b_reduce, w_expand,
-                               b_expand, channels * fold, c_squeezed, squeezed, gate, fold);
-            return launch_status();
-        }
+    if (route == HS_SE_ROUTE_EARLY) {   // the early blocks (many partials, few channels) as one single-workgroup launch
+        const int fold = se_early_fold(nblk);
+        hipLaunchKernelGGL(se_gate_early_kernel, dim3(1, batch), dim3(256), 0, s, partial, nblk / fold, inv_hw, w_reduce, b_reduce, w_expand,
+                           b_expand, channels * fold, c_squeezed, squeezed, gate, fold);
+        return launch_status();
     }
-    if (HS_SE_FUSED_WIDE && (channels & 3) == 0 && channels <= 256 && c_squeezed <= SEF_MAX_CSQ && units <= 6144) {
+    if (route == HS_SE_ROUTE_FUSED_WIDE) {
         hipLaunchKernelGGL((se_gate_fused_kernel<24, 1>), dim3((channels + 63) / 64, batch, row_groups), dim3(256), 0, s, partial, nblk,
                            inv_hw, w_reduce, b_reduce, w_expand, b_expand, channels, c_squeezed, squeezed, gate, w_proj, c_out,
                            out_scale, w_scaled);
@@ -823,13 +881,11 @@ void pointwise_conv_kernel(const float* __restrict__ x, const float* __restrict_
 }
 
 template <int NB>
-static int launch_pointwise(int nt, dim3 grid, hipStream_t s, const float* x, const float* w, const float* gate,
+static int launch_pointwise(int nt, bool vec, dim3 grid, hipStream_t s, const float* x, const float* w, const float* gate,
                             const float* scale, const float* shift, const float* residual, float* y, int c_in, int c_out,
                             int pixels, int act) {
 #define HS_PW(NT) hipLaunchKernelGGL((pointwise_conv_kernel<NB, NT>), grid, dim3(256), 0, s, x, w, gate, scale, shift, \
                                      residual, y, c_in, c_out, pixels, act)
-    static const bool vec_off = [] { const char* e = getenv("HS_PW_VEC"); return e && atoi(e) == 0; }();      // dev A/B knob
-    const bool vec = !vec_off && nt == 4 && (pixels & 63) == 0 && ((((size_t)x | (size_t)y | (size_t)residual)) & 15) == 0;
     if (vec) hipLaunchKernelGGL((pointwise_conv_kernel<NB, 4, true>), grid, dim3(256), 0, s, x, w, gate, scale, shift, residual, y, c_in,
                                 c_out, pixels, act);
     else if (nt == 4) HS_PW(4); else if (nt == 2) HS_PW(2); else HS_PW(1);
@@ -839,26 +895,45 @@ static int launch_pointwise(int nt, dim3 grid, hipStream_t s, const float* x, co
 
 }  // namespace hs
 
-extern "C" int hs_pointwise_conv_fwd(const float* x, int32_t batch, int32_t c_in, int32_t pixels, const float* w,
-                                     int32_t c_out, const float* gate, const float* scale, const float* shift, int32_t act,
-                                     const float* residual, float* y, void* stream) {
-    if (!x || !w || !y || batch <= 0 || c_in <= 0 || c_out <= 0 || pixels <= 0 || (scale && !shift)) return HS_ERR_BAD_ARG;
+// Which instantiation hs_pointwise_conv_fwd takes: HS_PW_ROUTE(NB, NT, vec) of include/hyperseg_hip.h or HS_ERR_UNSUPPORTED; the launcher
+// and hs_pointwise_route both call this.  aligned16: x, y and the residual (when given) are all 16-byte aligned.
+static int pointwise_route(int batch, int c_in, int c_out, int pixels, bool aligned16) {
     if (batch > 65535 || (c_out + 31) / 32 > 65535) return HS_ERR_UNSUPPORTED;
     if (c_in > 128) return HS_ERR_UNSUPPORTED;              // larger K: library GEMM (utils/inference.py routes those)
     const int mblocks = (c_out + 31) / 32;
     int nt = 4;
     while (nt > 1 && (long)((pixels + 64 * nt - 1) / (64 * nt)) * mblocks * batch < 512) nt >>= 1;
+    static const bool vec_off = [] { const char* e = getenv("HS_PW_VEC"); return e && atoi(e) == 0; }();      // dev A/B knob
+    const bool vec = !vec_off && nt == 4 && (pixels & 63) == 0 && aligned16;
+    const int nb = (c_in + 15) / 16;
+    return HS_PW_ROUTE(nb, nt, vec ? 1 : 0);
+}
+
+extern "C" int hs_pointwise_route(int32_t batch, int32_t c_in, int32_t c_out, int32_t pixels, int32_t aligned16) {
+    if (batch <= 0 || c_in <= 0 || c_out <= 0 || pixels <= 0) return HS_ERR_BAD_ARG;
+    return pointwise_route(batch, c_in, c_out, pixels, aligned16 != 0);
+}
+
+extern "C" int hs_pointwise_conv_fwd(const float* x, int32_t batch, int32_t c_in, int32_t pixels, const float* w,
+                                     int32_t c_out, const float* gate, const float* scale, const float* shift, int32_t act,
+                                     const float* residual, float* y, void* stream) {
+    if (!x || !w || !y || batch <= 0 || c_in <= 0 || c_out <= 0 || pixels <= 0 || (scale && !shift)) return HS_ERR_BAD_ARG;
+    const int route = pointwise_route(batch, c_in, c_out, pixels, ((((size_t)x | (size_t)y | (size_t)residual)) & 15) == 0);
+    if (route < 0) return route;
+    const int mblocks = (c_out + 31) / 32;
+    const int nt = (route >> 4) & 15;
+    const bool vec = (route & 1) != 0;
     dim3 grid((pixels + 64 * nt - 1) / (64 * nt), mblocks, batch);
     hipStream_t s = (hipStream_t)stream;
-    switch ((c_in + 15) / 16) {
-        case 1: return hs::launch_pointwise<1>(nt, grid, s, x, w, gate, scale, shift, residual, y, c_in, c_out, pixels, act);
-        case 2: return hs::launch_pointwise<2>(nt, grid, s, x, w, gate, scale, shift, residual, y, c_in, c_out, pixels, act);
-        case 3: return hs::launch_pointwise<3>(nt, grid, s, x, w, gate, scale, shift, residual, y, c_in, c_out, pixels, act);
-        case 4: return hs::launch_pointwise<4>(nt, grid, s, x, w, gate, scale, shift, residual, y, c_in, c_out, pixels, act);
-        case 5: return hs::launch_pointwise<5>(nt, grid, s, x, w, gate, scale, shift, residual, y, c_in, c_out, pixels, act);
-        case 6: return hs::launch_pointwise<6>(nt, grid, s, x, w, gate, scale, shift, residual, y, c_in, c_out, pixels, act);
-        case 7: return hs::launch_pointwise<7>(nt, grid, s, x, w, gate, scale, shift, residual, y, c_in, c_out, pixels, act);
-        default: return hs::launch_pointwise<8>(nt, grid, s, x, w, gate, scale, shift, residual, y, c_in, c_out, pixels, act);
+    switch (route >> 8) {
+        case 1: return hs::launch_pointwise<1>(nt, vec, grid, s, x, w, gate, scale, shift, residual, y, c_in, c_out, pixels, act);
+        case 2: return hs::launch_pointwise<2>(nt, vec, grid, s, x, w, gate, scale, shift, residual, y, c_in, c_out, pixels, act);
+        case 3: return hs::launch_pointwise<3>(nt, vec, grid, s, x, w, gate, scale, shift, residual, y, c_in, c_out, pixels, act);
+        case 4: return hs::launch_pointwise<4>(nt, vec, grid, s, x, w, gate, scale, shift, residual, y, c_in, c_out, pixels, act);
+        case 5: return hs::launch_pointwise<5>(nt, vec, grid, s, x, w, gate, scale, shift, residual, y, c_in, c_out, pixels, act);
+        case 6: return hs::launch_pointwise<6>(nt, vec, grid, s, x, w, gate, scale, shift, residual, y, c_in, c_out, pixels, act);
+        case 7: return hs::launch_pointwise<7>(nt, vec, grid, s, x, w, gate, scale, shift, residual, y, c_in, c_out, pixels, act);
+        default: return hs::launch_pointwise<8>(nt, vec, grid, s, x, w, gate, scale, shift, residual, y, c_in, c_out, pixels, act);
     }
 }
 
@@ -997,6 +1072,17 @@ void stem_conv_kernel(const float* __restrict__ x, const float* __restrict__ w, 
 }
 }  // namespace hs
 
+// Which instantiation of stem_conv_kernel a launch gets (HS_STEM_ROUTE_* of include/hyperseg_hip.h): hs_stem_conv_fwd and hs_stem_route both call this
+static int stem_route(int W, int pad_l, bool x_aligned16) {
+    const bool vec = (W & 3) == 0 && x_aligned16;
+    return vec && pad_l == 0 ? HS_STEM_ROUTE_VECTOR_PL0 : (vec && pad_l == 1 ? HS_STEM_ROUTE_VECTOR_PL1 : HS_STEM_ROUTE_GENERIC);
+}
+
+extern "C" int hs_stem_route(int32_t W, int32_t pad_l, int32_t x_aligned16) {
+    if (W <= 0 || pad_l < 0) return HS_ERR_BAD_ARG;
+    return stem_route(W, pad_l, x_aligned16 != 0);
+}
+
 extern "C" int hs_stem_conv_fwd(const float* x, int32_t batch, int32_t c_in, int32_t H, int32_t W, const float* w,
                                 int32_t c_out, int32_t pad_t, int32_t pad_l, int32_t Ho, int32_t Wo, const float* scale,
                                 const float* shift, float* y, void* stream) {
@@ -1005,10 +1091,10 @@ extern "C" int hs_stem_conv_fwd(const float* x, int32_t batch, int32_t c_in, int
     if (c_in != 3 || batch > 65535) return HS_ERR_UNSUPPORTED;
     const int quads = Ho * ((Wo + 3) / 4);
     dim3 grid((quads + 255) / 256, (c_out + HS_STEM_CG - 1) / HS_STEM_CG, batch);
-    const bool vec = (W & 3) == 0 && (((size_t)x) & 15) == 0;
+    const int route = stem_route(W, pad_l, (((size_t)x) & 15) == 0);
 #define HS_STEM(PP) hipLaunchKernelGGL((hs::stem_conv_kernel<3, PP>), grid, dim3(256), 0, (hipStream_t)stream, x, w, scale, shift, \
                                        y, c_out, H, W, Ho, Wo, pad_t, pad_l)
-    if (vec && pad_l == 0) HS_STEM(0); else if (vec && pad_l == 1) HS_STEM(1); else HS_STEM(-1);
+    if (route == HS_STEM_ROUTE_VECTOR_PL0) HS_STEM(0); else if (route == HS_STEM_ROUTE_VECTOR_PL1) HS_STEM(1); else HS_STEM(-1);
 #undef HS_STEM
     return hs::launch_status();
 }

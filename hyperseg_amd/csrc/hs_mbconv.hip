@@ -255,6 +255,9 @@ int try_launch_mbconv_lean(const float* x, int batch, int c_in, int H, int W, co
                            const float* scale1, const float* shift1, float* y, float* pool, int oth, int tiles_y, int tiles_x,
                            int chunks_per_wg, int ngroups, hipStream_t stream);                 // hs_mbconv_lean.hip
 
+bool mbconv_lean_covers(int c_in, int H, int W, int c_mid, int k, int stride, int Wo, int oth, bool aligned16);                 // hs_mbconv_lean.hip
+bool stem_dw_lean_covers(int sH, int sW, int c_mid, int spad_t, int spad_l, int Hs, int Ws, int k, int oth, bool aligned16);    // hs_mbconv_lean.hip
+
 int try_launch_stem_dw_lean(const void* x, const float* table, int layout, int batch, int sH, int sW, const float* w28, int c_mid,
                             const float* scale0, const float* shift0, int spad_t, int spad_l, int Hs, int Ws, const float* w_dw, int k,
                             int pad_t, int pad_l, const float* scale1, const float* shift1, float* y, float* pool, int oth, int tiles_y,
@@ -299,6 +302,28 @@ extern "C" int64_t hs_mbconv_se_workgroups(int32_t batch, int32_t c_mid, int32_t
     return (int64_t)ty * tx * ng;
 }
 
+// Which kernel hs_mbconv_expand_dw_fwd takes (HS_MB_ROUTE of include/hyperseg_hip.h, HS_ERR_UNSUPPORTED where dispatch_ks has no
+// instantiation): mbconv_launch and hs_mbconv_route both call this.  se: the launch carries an SE tail (the full kernel only).
+static int mbconv_route(int c_in, int H, int W, int c_mid, int k, int stride, int Wo, bool aligned16, bool se) {
+    if (stride != 1 && stride != 2) return HS_ERR_UNSUPPORTED;
+    if (!se && mbconv_lean_covers(c_in, H, W, c_mid, k, stride, Wo, mbx_oth(stride), aligned16)) return HS_MB_ROUTE(HS_MB_FORM_LEAN, k, stride);
+    if ((k != 3 && k != 5) || (c_in + 3) / 4 > 20) return HS_ERR_UNSUPPORTED;      // dispatch_ks: wider inputs do not fit the register file
+    return HS_MB_ROUTE(HS_MB_FORM_FULL, k, stride);
+}
+
+extern "C" int hs_mbconv_route(int32_t batch, int32_t c_in, int32_t H, int32_t W, int32_t c_mid, int32_t k, int32_t stride,
+                               int32_t Ho, int32_t Wo, int32_t aligned16, int32_t with_se_tail) {
+    if (batch <= 0 || c_in <= 0 || c_mid <= 0 || H <= 0 || W <= 0 || Ho <= 0 || Wo <= 0) return HS_ERR_BAD_ARG;
+    return mbconv_route(c_in, H, W, c_mid, k, stride, Wo, aligned16 != 0, with_se_tail != 0);
+}
+
+extern "C" int hs_stem_dw_route(int32_t H, int32_t W, int32_t c_mid, int32_t stem_pad_t, int32_t stem_pad_l, int32_t Hs, int32_t Ws,
+                                int32_t k, int32_t aligned16) {
+    if (c_mid <= 0 || H <= 0 || W <= 0 || Hs <= 0 || Ws <= 0) return HS_ERR_BAD_ARG;
+    return stem_dw_lean_covers(H, W, c_mid, stem_pad_t, stem_pad_l, Hs, Ws, k, mbx_oth(1), aligned16 != 0) ? HS_MB_ROUTE(HS_MB_FORM_STEM, 3, 1)
+                                                                                                          : HS_ERR_UNSUPPORTED;
+}
+
 static int mbconv_launch(const float* x, int32_t batch, int32_t c_in, int32_t H, int32_t W,
                          const float* w_expand, int32_t c_mid, const float* scale0, const float* shift0,
                          const float* w_dw, int32_t k, int32_t stride, int32_t pad_t, int32_t pad_l,
@@ -311,14 +336,15 @@ static int mbconv_launch(const float* x, int32_t batch, int32_t c_in, int32_t H,
     a.x = x; a.w_e = w_expand; a.s0 = scale0; a.b0 = shift0; a.w_dw = w_dw; a.s1 = scale1; a.b1 = shift1;
     a.y = y; a.pool = pool_partial;
     a.Cin = c_in; a.Cmid = c_mid; a.H = H; a.W = W; a.Ho = Ho; a.Wo = Wo; a.pad_t = pad_t; a.pad_l = pad_l;
-    if (stride != 1 && stride != 2) return HS_ERR_UNSUPPORTED;
+    const int route = mbconv_route(c_in, H, W, c_mid, k, stride, Wo, (((size_t)y | (size_t)scale0 | (size_t)shift0) & 15) == 0, se_in != nullptr);
+    if (route < 0) return route;
     mbx_grid(batch, c_mid, stride, Ho, Wo, a.tiles_y, a.tiles_x, a.chunks_per_wg, a.ngroups);
     hipStream_t s = (hipStream_t)stream;
-    if (!se_in && (stride == 1 || stride == 2)) {      // the lean form (hs_mbconv_lean.hip) wherever the shape allows: same tiles, same sums
+    if ((route >> 8) == HS_MB_FORM_LEAN) {             // the lean form (hs_mbconv_lean.hip) wherever the shape allows: same tiles, same sums
         const int st = try_launch_mbconv_lean(x, batch, c_in, H, W, w_expand, c_mid, scale0, shift0, w_dw, k, stride, pad_t, pad_l, Ho, Wo,
                                               scale1, shift1, y, pool_partial, mbx_oth(stride), a.tiles_y, a.tiles_x, a.chunks_per_wg,
                                               a.ngroups, s);
-        if (st != 1) return st;
+        if (st != 1) return st;                        // 1: more than 2^31 workgroups -- the general kernel refuses those too
     }
     a.se = SeTail{};
     if (se_in) {

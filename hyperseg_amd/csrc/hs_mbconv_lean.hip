@@ -360,23 +360,42 @@ static int launch_mbl(std::conditional_t<U8, MblArgsU8, MblArgs>& a, int batch, 
     return launch_status();
 }
 
+// Whether the lean kernel covers a shape: try_launch_mbconv_lean and hs_mbconv_route (hs_mbconv.hip) both ask this, nothing else decides.
+// aligned16: y, scale0 and shift0 are all 16-byte aligned.
+bool mbconv_lean_covers(int c_in, int H, int W, int c_mid, int k, int stride, int Wo, int oth, bool aligned16) {
+    static const bool off = [] { const char* e = getenv("HS_MBX_LEAN"); return e && atoi(e) == 0; }();      // dev A/B knob
+    if (off) return false;
+    if ((c_in & 3) != 0 || (c_mid & 15) != 0 || Wo % 16 != 0) return false;         // (a ragged LAST TILE ROW is fine: rows past Ho are neither stored nor pooled)
+    if ((size_t)c_in * H * W >= (1u << 30)) return false;                   // 32-bit byte offsets from the batch element's base
+    if (!aligned16) return false;
+    const int ks = c_in >> 2;
+    if (k == 5 && stride == 2 && oth == 8 && ks > 6) return false;  // that instantiation does not fit the register file (spills)
+    if (ks != 4 && ks != 6 && ks != 8 && ks != 10) return false;    // the instantiated input widths (16, 24, 32, 40 channels)
+    if (!(k == 3 || k == 5)) return false;
+    return stride == 1 ? (oth == 16 || oth == 8) : (stride == 2 && (oth == 8 || oth == 4));
+}
+
+// Whether the stem form covers a shape: try_launch_stem_dw_lean and hs_stem_dw_route both ask this.
+bool stem_dw_lean_covers(int sH, int sW, int c_mid, int spad_t, int spad_l, int Hs, int Ws, int k, int oth, bool aligned16) {
+    if (k != 3 || (c_mid & 15) != 0 || Ws % 16 != 0 || spad_t < 0 || spad_l < 0) return false;
+    if ((size_t)3 * sH * sW >= (1u << 29)) return false;                      // 32-bit byte offsets, with room for the clamped windows
+    if (2 * (Hs - 1) - spad_t >= sH || 2 * (Ws - 1) - spad_l >= sW) return false;  // every output's window starts inside the image
+    if (!aligned16) return false;
+    return oth == 16 || oth == 8;
+}
+
 // Returns 1 when the shape is outside what the lean kernel covers (the caller then takes the general kernel).
 int try_launch_mbconv_lean(const float* x, int batch, int c_in, int H, int W, const float* w_expand, int c_mid, const float* scale0,
                            const float* shift0, const float* w_dw, int k, int stride, int pad_t, int pad_l, int Ho, int Wo,
                            const float* scale1, const float* shift1, float* y, float* pool, int oth, int tiles_y, int tiles_x,
                            int chunks_per_wg, int ngroups, hipStream_t stream) {
-    static const bool off = [] { const char* e = getenv("HS_MBX_LEAN"); return e && atoi(e) == 0; }();      // dev A/B knob
-    if (off) return 1;
-    if ((c_in & 3) != 0 || (c_mid & 15) != 0 || Wo % 16 != 0) return 1;             // (a ragged LAST TILE ROW is fine: rows past Ho are neither stored nor pooled)
-    if ((size_t)c_in * H * W >= (1u << 30)) return 1;                       // 32-bit byte offsets from the batch element's base
-    if ((((size_t)y | (size_t)scale0 | (size_t)shift0) & 15) != 0) return 1;
+    if (!mbconv_lean_covers(c_in, H, W, c_mid, k, stride, Wo, oth, (((size_t)y | (size_t)scale0 | (size_t)shift0) & 15) == 0)) return 1;
     MblArgs a;
     a.x = x; a.w_e = w_expand; a.s0 = scale0; a.b0 = shift0; a.w_dw = w_dw; a.s1 = scale1; a.b1 = shift1; a.y = y; a.pool = pool;
     a.Cmid = c_mid; a.H = H; a.W = W; a.Ho = Ho; a.Wo = Wo; a.pad_t = pad_t; a.pad_l = pad_l;
     a.tiles_y = tiles_y; a.tiles_x = tiles_x; a.chunks_per_wg = chunks_per_wg; a.ngroups = ngroups;
     a.sH = a.sW = a.spad_t = a.spad_l = 0;
     const int ks = c_in >> 2;
-    if (k == 5 && stride == 2 && oth == 8 && ks > 6) return 1;      // that instantiation does not fit the register file (spills)
     // (Cin = 80 -- KS = 20, HyperSeg-M's 64 x 32 blocks -- was instantiated and measured in round 6: 11.5 us against the GEMM + depthwise
     // pair's 12.2 per block in isolation, but the whole frame LOSES 4.5 us with the fusion threshold raised to 80 channels:
     // profiles/round6_mbconv_lean_cin80_negative_w13.txt.  Not instantiated.)
@@ -386,12 +405,12 @@ int try_launch_mbconv_lean(const float* x, int batch, int c_in, int H, int W, co
         if (ks == 6) return launch_mbl<K_, S_, OTH_, 16, 6>(a, batch, stream); \
         if (ks == 8) return launch_mbl<K_, S_, OTH_, 16, 8>(a, batch, stream);      /* EfficientNet-B3's 32-channel blocks (HyperSeg-L) */ \
         if (ks == 10) return launch_mbl<K_, S_, OTH_, 16, 10>(a, batch, stream); \
-        return 1; \
+        return HS_ERR_UNSUPPORTED;                  /* not reached: mbconv_lean_covers admits these four only */ \
     }
     HS_MBL_KS(3, 1, 16) HS_MBL_KS(3, 1, 8) HS_MBL_KS(5, 1, 16) HS_MBL_KS(5, 1, 8)
     HS_MBL_KS(3, 2, 8) HS_MBL_KS(3, 2, 4) HS_MBL_KS(5, 2, 8) HS_MBL_KS(5, 2, 4)
 #undef HS_MBL_KS
-    return 1;
+    return HS_ERR_UNSUPPORTED;                      // not reached (mbconv_lean_covers)
 }
 
 // The stem form: x = the image (B, 3, sH, sW), w28 = the stem weight (c_mid, 27) padded to 28 columns, (Hs, Ws) = the stem's output map
@@ -401,10 +420,7 @@ int try_launch_stem_dw_lean(const void* x, const float* table, int layout, int b
                             const float* scale0, const float* shift0, int spad_t, int spad_l, int Hs, int Ws, const float* w_dw, int k,
                             int pad_t, int pad_l, const float* scale1, const float* shift1, float* y, float* pool, int oth, int tiles_y,
                             int tiles_x, int chunks_per_wg, int ngroups, hipStream_t stream) {
-    if (k != 3 || (c_mid & 15) != 0 || Ws % 16 != 0 || spad_t < 0 || spad_l < 0) return 1;
-    if ((size_t)3 * sH * sW >= (1u << 29)) return 1;                          // 32-bit byte offsets, with room for the clamped windows
-    if (2 * (Hs - 1) - spad_t >= sH || 2 * (Ws - 1) - spad_l >= sW) return 1;  // every output's window starts inside the image
-    if ((((size_t)y | (size_t)scale0 | (size_t)shift0) & 15) != 0) return 1;
+    if (!stem_dw_lean_covers(sH, sW, c_mid, spad_t, spad_l, Hs, Ws, k, oth, (((size_t)y | (size_t)scale0 | (size_t)shift0) & 15) == 0)) return 1;
     MblArgsU8 a;
     a.x = static_cast<const float*>(x); a.w_e = w28; a.s0 = scale0; a.b0 = shift0; a.w_dw = w_dw; a.s1 = scale1; a.b1 = shift1; a.y = y; a.pool = pool;
     a.Cmid = c_mid; a.H = Hs; a.W = Ws; a.Ho = Hs; a.Wo = Ws; a.pad_t = pad_t; a.pad_l = pad_l;

@@ -1138,6 +1138,74 @@ def se_gate(partial, batch, hw, w_reduce, b_reduce, w_expand, b_expand, w_proj=N
     return w_scaled if w_proj is not None else gate
 
 
+def _route(code, what):
+    """A route query's answer: None for HS_ERR_UNSUPPORTED (the launcher refuses the shape), HipLibraryError for any other error."""
+    if code == -3:
+        return None
+    if code < 0:
+        _hip.check(code, what)
+    return code
+
+
+_DW_FORMS = {0: 'generic', 1: 'vector', 2: 'tiled'}
+_MB_FORMS = {0: 'full', 1: 'lean', 2: 'stem'}
+SE_ROUTES = {0: 'fused', 1: 'early', 2: 'fused_wide', 3: 'two_launch'}
+
+
+def depthwise_route(shape, k, stride, pad_left, out_size, prologue=False, aligned=True):
+    """Which instantiation ``depthwise_conv_bn_act`` launches for x of ``shape`` = (B, C, H, W) (include/hyperseg_hip.h,
+    hs_depthwise_route): 'tiled_k5s1' | 'vector_k3s2_pl1' | 'generic_k3s2' ..., None where the launcher refuses.  ``aligned``: x is
+    16-byte aligned (the allocator's tensors are).  Host only."""
+    b, c, h, w = shape
+    r = _route(_hip.lib.hs_depthwise_route(b, c, h, w, k, stride, pad_left, out_size[0], out_size[1], int(bool(aligned)), int(bool(prologue))),
+               'hs_depthwise_route')
+    if r is None:
+        return None
+    form, name = _DW_FORMS[r >> 8], f'k{(r >> 4) & 15}s{(r >> 2) & 3}'
+    return f'{form}_{name}_pl{r & 3}' if form == 'vector' else f'{form}_{name}'
+
+
+def mbconv_route(shape, c_mid, k, stride, out_size, aligned=True, se_tail=False):
+    """Which kernel ``mbconv_expand_dw`` launches for x of ``shape`` = (B, Cin, H, W): 'lean_k3s1' | 'full_k5s2' ..., None where the
+    launcher refuses (hs_mbconv_route).  ``aligned``: y, scale0 and shift0 are 16-byte aligned.  Host only."""
+    b, cin, h, w = shape
+    r = _route(_hip.lib.hs_mbconv_route(b, cin, h, w, c_mid, k, stride, out_size[0], out_size[1], int(bool(aligned)), int(bool(se_tail))),
+               'hs_mbconv_route')
+    return None if r is None else f'{_MB_FORMS[r >> 8]}_k{(r >> 4) & 15}s{r & 15}'
+
+
+def stem_dw_route(size, c_mid, stem_pad_top, stem_pad_left, stem_out_size, k=3, aligned=True):
+    """'stem_k3s1' where ``stem_dw`` launches for an image of ``size`` = (H, W), None where it returns None (hs_stem_dw_route).  Host only."""
+    r = _route(_hip.lib.hs_stem_dw_route(size[0], size[1], c_mid, stem_pad_top, stem_pad_left, stem_out_size[0], stem_out_size[1], k,
+                                         int(bool(aligned))), 'hs_stem_dw_route')
+    return None if r is None else f'{_MB_FORMS[r >> 8]}_k{(r >> 4) & 15}s{r & 15}'
+
+
+def se_gate_route(channels, nblk, c_squeezed, w_proj=False, aligned=True):
+    """The form ``se_gate`` takes: 'fused' | 'early' | 'fused_wide' | 'two_launch', None where it refuses (hs_se_gate_route).  ``aligned``: partial and
+    w_reduce are 16-byte aligned.  Host only."""
+    r = _route(_hip.lib.hs_se_gate_route(channels, nblk, c_squeezed, int(bool(w_proj)), int(bool(aligned))), 'hs_se_gate_route')
+    return None if r is None else SE_ROUTES[r]
+
+
+STEM_ROUTES = {0: 'generic', 1: 'vector_pl0', 2: 'vector_pl1'}
+
+
+def stem_route(width, pad_left, aligned=True):
+    """The form ``stem_conv_bn_swish`` takes for an image ``width`` wide: 'vector_pl0' | 'vector_pl1' | 'generic' (hs_stem_route).  Host only."""
+    return STEM_ROUTES[_route(_hip.lib.hs_stem_route(width, pad_left, int(bool(aligned))), 'hs_stem_route')]
+
+
+def pointwise_route(batch, c_in, c_out, pixels, aligned=True):
+    """The instantiation ``pointwise_conv`` launches: 'vec_nb6' (interleaved 16-byte form) | 'nt4_nb6' | 'nt2_nb1' | 'nt1_nb2' ... with nb
+    = ceil(c_in / 16) and nt the 16-pixel tiles per wave; None for c_in > 128 (hs_pointwise_route).  ``aligned``: x, y and the residual
+    are 16-byte aligned.  Host only."""
+    r = _route(_hip.lib.hs_pointwise_route(batch, c_in, c_out, pixels, int(bool(aligned))), 'hs_pointwise_route')
+    if r is None:
+        return None
+    return f'vec_nb{r >> 8}' if r & 1 else f'nt{(r >> 4) & 15}_nb{r >> 8}'
+
+
 class SplitWeights:
     """A static 1x1-conv weight prepared for ``hs_gemm_split_fwd``: f16 hi / lo pieces of the power-of-two row-scaled weight in
     MFMA-fragment order + the inverse row scales (include/hyperseg_hip.h)."""

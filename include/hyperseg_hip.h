@@ -724,6 +724,64 @@ int hs_pointwise_conv_fwd(const float* x, int32_t batch, int32_t c_in, int32_t p
 int hs_affine_act_fwd(const float* x, int32_t batch, int32_t channels, int32_t pixels, const float* scale,
                       const float* shift, int32_t act, const float* residual, float* y, void* stream);
 
+/* Route queries of the encoder helpers (host only: nothing is launched, no pointer is read).  Each answers with the ONE static
+ * predicate its launcher dispatches on -- under the current environment, the dev A/B knobs HS_SE_EARLY, HS_PW_VEC, HS_MBX_LEAN and
+ * HS_MBX_OTH1 / HS_MBX_OTH2 included -- from the shape and pointer-alignment facts the launcher looks at.  Negative: the HS_ERR_* the
+ * launcher would return for the shape.  For the tests that pin which kernel a case runs (tests/test_hip_encoder_f64.py).
+ *
+ * hs_depthwise_route -> HS_DW_ROUTE(form, k, stride, pl):
+ *   HS_DW_FORM_TILED    BN0 + swish prologue, k in {3,5}, >= 256 output quads, Wo % 4 == 0, Wo / 4 divides 256, the input band of a
+ *                       workgroup <= 64 KB of LDS, and (k == 5 or >= 8192 planes): whole output rows per workgroup through LDS; pl = 0
+ *   HS_DW_FORM_VECTOR   W % 4 == 0, x 16-byte aligned and pad_l one of the compiled constants pl -- (k3,s1): 1; (k3,s2): 0, 1;
+ *                       (k5,s1): 2; (k5,s2): 1, 2 -- tap rows as aligned 16-byte loads
+ *   HS_DW_FORM_GENERIC  everything else: any pad_l / W, 4-byte loads; pl = 0
+ * pad_t never enters the choice.  x_aligned16 / prologue: x is 16-byte aligned / in_scale is given. */
+#define HS_DW_FORM_GENERIC 0
+#define HS_DW_FORM_VECTOR 1
+#define HS_DW_FORM_TILED 2
+#define HS_DW_ROUTE(form, k, stride, pl) (((form) << 8) | ((k) << 4) | ((stride) << 2) | (pl))
+int hs_depthwise_route(int32_t batch, int32_t channels, int32_t H, int32_t W, int32_t k, int32_t stride, int32_t pad_l,
+                       int32_t Ho, int32_t Wo, int32_t x_aligned16, int32_t prologue);
+/* hs_stem_route -> the form of hs_stem_conv_fwd: the vector forms need W % 4 == 0, x 16-byte aligned and pad_l 0 or 1. */
+#define HS_STEM_ROUTE_GENERIC 0
+#define HS_STEM_ROUTE_VECTOR_PL0 1
+#define HS_STEM_ROUTE_VECTOR_PL1 2
+int hs_stem_route(int32_t W, int32_t pad_l, int32_t x_aligned16);
+/* hs_mbconv_route -> HS_MB_ROUTE(form, k, stride) for hs_mbconv_expand_dw_fwd (with_se_tail: hs_mbconv_expand_dw_se_fwd):
+ *   HS_MB_FORM_LEAN  no SE tail, c_in in {16, 24, 32, 40} (not 32 / 40 at k 5, stride 2), c_mid % 16 == 0, Wo % 16 == 0, y / scale0 /
+ *                    shift0 16-byte aligned (aligned16), c_in H W < 2^30: hs_mbconv_lean.hip
+ *   HS_MB_FORM_FULL  every other shape with c_in <= 80: the general kernel (ragged tile columns, any channel counts)
+ * hs_stem_dw_route -> HS_MB_ROUTE(HS_MB_FORM_STEM, 3, 1) where hs_stem_dw_fwd / hs_stem_dw_u8_fwd launch, HS_ERR_UNSUPPORTED where
+ * they return it (k != 3, c_mid % 16, Ws % 16, an output window that starts outside the image, misaligned y / scale0 / shift0).
+ * The instantiation's input width (KS) follows from c_in alone and the tile height from the stride; neither is part of the code. */
+#define HS_MB_FORM_FULL 0
+#define HS_MB_FORM_LEAN 1
+#define HS_MB_FORM_STEM 2
+#define HS_MB_ROUTE(form, k, stride) (((form) << 8) | ((k) << 4) | (stride))
+int hs_mbconv_route(int32_t batch, int32_t c_in, int32_t H, int32_t W, int32_t c_mid, int32_t k, int32_t stride,
+                    int32_t Ho, int32_t Wo, int32_t aligned16, int32_t with_se_tail);
+int hs_stem_dw_route(int32_t H, int32_t W, int32_t c_mid, int32_t stem_pad_t, int32_t stem_pad_l, int32_t Hs, int32_t Ws,
+                     int32_t k, int32_t aligned16);
+/* hs_se_gate_route -> the form hs_se_gate_fwd takes, tried in this order (units = channels * (nblk % 4 == 0 ? nblk / 4 : nblk)):
+ *   HS_SE_ROUTE_FUSED       channels % 4 == 0, channels <= 768, c_squeezed <= 32, units <= 2048: one launch, se_gate_fused_kernel<8, 3>
+ *   HS_SE_ROUTE_EARLY       no w_proj, channels % 4 == 0, channels * fold <= 144 (fold = 1 / 2 / 4 for nblk <= 256 / 512 / 1024),
+ *                           c_squeezed <= 8, nblk <= 1024, nblk % (4 fold) == 0, partial and w_reduce 16-byte aligned (aligned16): one workgroup
+ *   HS_SE_ROUTE_FUSED_WIDE  se_gate_fused_kernel<24, 1>; compiled only with -DHS_SE_FUSED_WIDE=1 (measured negative, hs_encoder.hip): the
+ *                           product build never returns this code
+ *   HS_SE_ROUTE_TWO_LAUNCH  everything else: squeeze + excite
+ * (The gate finished by the pooling launch's last workgroups is another ENTRY, hs_depthwise_conv_se_fwd / hs_mbconv_expand_dw_se_fwd, not
+ * a route of this one; hs_se_tail_tails is its query.) */
+#define HS_SE_ROUTE_FUSED 0
+#define HS_SE_ROUTE_EARLY 1
+#define HS_SE_ROUTE_FUSED_WIDE 2
+#define HS_SE_ROUTE_TWO_LAUNCH 3
+int hs_se_gate_route(int32_t channels, int32_t nblk, int32_t c_squeezed, int32_t with_w_proj, int32_t aligned16);
+/* hs_pointwise_route -> HS_PW_ROUTE(nb, nt, vec): nb = ceil(c_in / 16) 16-channel K batches (1..8), nt = 16-pixel tiles per wave (4,
+ * halved while the launch would have fewer than 512 workgroups), vec = 1: the interleaved 16-byte form (nt == 4, pixels % 64 == 0, x, y
+ * and the residual 16-byte aligned (aligned16)).  HS_ERR_UNSUPPORTED for c_in > 128. */
+#define HS_PW_ROUTE(nb, nt, vec) (((nb) << 8) | ((nt) << 4) | (vec))
+int hs_pointwise_route(int32_t batch, int32_t c_in, int32_t c_out, int32_t pixels, int32_t aligned16);
+
 /* Encoder-side helper (opt-in: prepare_for_inference(split_gemm=True); off by default): a 1x1 convolution as a GEMM on the
  * f16 matrix cores with split operands, f32 storage and accumulation,
  *   y[b,o,p] = act(sum_c w[o,c] * gate[b,c] * x[b,c,p] + shift[o]) + residual[b,o,p]
