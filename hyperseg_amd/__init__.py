@@ -12,6 +12,9 @@ def __getattr__(name):
     if name == 'ColorJitterParams':
         from .utils.jitter import ColorJitterParams
         return ColorJitterParams
+    if name == 'GaussianBlurParams':
+        from .utils.blur import GaussianBlurParams
+        return GaussianBlurParams
     if name == 'Overlay':
         from .utils.inference import Overlay
         return Overlay

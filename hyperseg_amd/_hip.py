@@ -196,6 +196,7 @@ SIGNATURES = {
     'hs_label_resize_coded_fwd': ([vp, i32, i32, i32, i32, vp, i32, vp, i32, i32, i32, i32, i32, i32, i32, vp, i32, i32, i32, vp, i32, vp], STATUS),
     'hs_label_resize_batch_coded_fwd': ([vp, i32, i32, i32, i32, vp, vp, vp, i32, i32, i32, vp, i32, i32, i32, vp, i32, vp], STATUS),
     'hs_color_jitter_fwd': ([vp, i32, i32, i32, i32, vp, vp, vp, vp, vp], STATUS),
+    'hs_gaussian_blur_fwd': ([vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp], STATUS),
     'hs_frame_rotate_fwd': ([vp, i32, i32, i32, i32, vp, i32, i32, C.c_uint32, C.c_uint32, vp, vp, vp], STATUS),
     'hs_label_rotate_fwd': ([vp, i32, i32, i32, i32, vp, i32, i32, i32, i32, vp, i32, vp], STATUS),
     'hs_resize_tables_ragged_fwd': ([vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp], STATUS),

@@ -43,13 +43,17 @@ def _labels_shape(label_codec, b, h, w):
     return (b, h, w) if label_codec is None else label_codec.raw_shape(b, h, w)
 
 
-def _crop_cpu(frames_u8, labels, sizes, offsets, flips, jitter, crop, norm, filter, fill, lbl_fill, label_codec=None):
+def _crop_cpu(frames_u8, labels, sizes, offsets, flips, jitter, crop, norm, filter, fill, lbl_fill, label_codec=None, blur=None,
+              blur_table=None):
     """The crop chain on CPU tensors for given resized ``sizes`` (Hr, Wr), ``offsets`` and ``flips`` per sample (``utils.resample``,
-    ``utils.jitter``): what :func:`device_augment` and :class:`BatchAugment` return for them."""
+    ``utils.jitter``, ``utils.blur``): what :func:`device_augment` and :class:`BatchAugment` return for them.  The blur is given as
+    ``blur`` (a list of B ``GaussianBlurParams``) or as ``blur_table``, the records :meth:`BatchAugment.run` takes."""
     from .utils import resample
     b, (ch, cw) = frames_u8.shape[0], crop
-    dst_norm = norm if jitter is None else None              # with a jitter the resize gives the uint8 crop, the jitter normalises
-    dst = torch.empty((b, 3, ch, cw), dtype=torch.float32) if jitter is None else torch.empty(_frames_shape(norm.layout, b, ch, cw), dtype=torch.uint8)
+    blurred = blur is not None or blur_table is not None
+    u8 = jitter is not None or blurred                       # then the resize gives the uint8 crop and the last image step normalises
+    dst_norm = None if u8 else norm
+    dst = torch.empty(_frames_shape(norm.layout, b, ch, cw), dtype=torch.uint8) if u8 else torch.empty((b, 3, ch, cw), dtype=torch.float32)
     label = torch.empty(b, ch, cw, dtype=torch.int64)
     for i, (size, offset, flip) in enumerate(zip(sizes, offsets, flips)):
         view = resample.ResizeView((ch, cw), tuple(int(o) for o in offset), bool(flip), fill)
@@ -57,11 +61,15 @@ def _crop_cpu(frames_u8, labels, sizes, offsets, flips, jitter, crop, norm, filt
         label[i:i + 1] = resample.label_resize_cpu(labels[i:i + 1], size, view=view, fill=lbl_fill, out_dtype=torch.int64, codec=label_codec)
     if jitter is not None:
         from .utils import jitter as J
-        dst = J.color_jitter_cpu(dst, J.per_sample(jitter, b), norm.layout, norm=norm)
+        dst = J.color_jitter_cpu(dst, J.per_sample(jitter, b), norm.layout, norm=None if blurred else norm)
+    if blurred:
+        from .utils import blur as BL
+        dst = BL.gaussian_blur_cpu(dst, blur, norm.layout, norm=norm, table=blur_table)
     return dst, label
 
 
-def device_augment(frames_u8, labels, scale, crop, offset, hflip, norm, lbl_fill=255, fill=(0, 0, 0), jitter=None, label_codec=None):
+def device_augment(frames_u8, labels, scale, crop, offset, hflip, norm, lbl_fill=255, fill=(0, 0, 0), jitter=None, label_codec=None,
+                   blur=None):
     """The reference's train-time chain RandomResize -> RandomCrop(pad_if_needed) -> RandomHorizontalFlip -> ToTensor -> Normalize
     (hyperseg/datasets/seg_transforms.py:224-334) for GIVEN parameters, on the device: per sample one ``functional.frame_resize``
     launch (bicubic, Pillow's bytes, looked up in ``norm``'s table) and one ``functional.label_resize`` launch (nearest), each
@@ -82,7 +90,14 @@ def device_augment(frames_u8, labels, scale, crop, offset, hflip, norm, lbl_fill
 
     ``label_codec`` (a ``LabelCodec``): ``labels`` are RAW -- ids (B, H, W) or a colour image uint8 (B, H, W, 3) -- and the label launch
     encodes the pixel it gathers (``functional.label_resize(codec=)``): the same launches, no host pass.  ``lbl_fill`` is a class
-    value and is not encoded."""
+    value and is not encoded.
+
+    ``blur`` (a ``GaussianBlurParams``, or a sequence of B with ``None`` for a sample that is not blurred; :func:`draw_gaussian_blur`
+    draws one): the reference's ``RandomGaussianBlur`` (seg_transforms.py:361-378, ``ImageFilter.GaussianBlur``) as the LAST step of the
+    image chain -- after the crop and the flip and after ``jitter`` if one is given, on the uint8 crop (padding included), before the
+    normalisation: ``functional.gaussian_blur`` produces the normalised image of the whole batch in two launches
+    (``utils.blur.gaussian_blur_cpu`` for CPU tensors), and the jitter, if any, then writes bytes.  The label is not touched.  ``None``:
+    nothing changes.  A radius the device kernels do not take raises ValueError before any launch."""
     b, h, w = norm.frame_size(frames_u8)
     want = _labels_shape(label_codec, b, h, w)
     if not isinstance(labels, torch.Tensor) or tuple(labels.shape) != want:
@@ -93,23 +108,39 @@ def device_augment(frames_u8, labels, scale, crop, offset, hflip, norm, lbl_fill
     if jitter is not None:
         from .utils import jitter as J
         jitter = J.per_sample(jitter, b)
+    if blur is not None:
+        from .utils import blur as BL
+        blur = BL.per_sample(blur, b)
     frames_u8, labels = frames_u8.contiguous(), labels.contiguous()
     if not frames_u8.is_cuda:
-        return _crop_cpu(frames_u8, labels, sizes, offsets, flips, jitter, (ch, cw), norm, 'bicubic', fill, lbl_fill, label_codec)
+        return _crop_cpu(frames_u8, labels, sizes, offsets, flips, jitter, (ch, cw), norm, 'bicubic', fill, lbl_fill, label_codec, blur)
     from . import functional as HF
     from .utils import resample
+    blur_table = None if blur is None else HF.blur_records(blur, b).to(frames_u8.device)       # raises before any launch
     image, label = _outputs(b, ch, cw, frames_u8.device)
     dst, dst_norm = image, norm
-    if jitter is not None:                                   # the resize writes the uint8 crop, the jitter normalises
+    if jitter is not None or blur is not None:               # the resize writes the uint8 crop, the last image step normalises
         dst_norm = None
         dst = torch.empty(_frames_shape(norm.layout, b, ch, cw), dtype=torch.uint8, device=frames_u8.device)
     for i in range(b):
         view = resample.ResizeView((ch, cw), tuple(int(o) for o in offsets[i]), bool(flips[i]), fill)
         HF.frame_resize(frames_u8[i:i + 1], sizes[i], 'bicubic', norm.layout, view=view, norm=dst_norm, out=dst[i:i + 1])
         HF.label_resize(labels[i:i + 1], sizes[i], view=view, fill=lbl_fill, out=label[i:i + 1], codec=label_codec)
-    if jitter is not None:
-        HF.color_jitter(dst, jitter, norm.layout, norm=norm, out=image)
+    _image_tail(dst, jitter, blur_table, norm, image)
     return image, label
+
+
+def _image_tail(crop_u8, jitter, blur_table, norm, image, blur_status=None):
+    """The steps of the image chain behind the crop, on the device: ``jitter`` (a list of B ``ColorJitterParams`` or None), then the blur
+    of the device records ``blur_table`` (or None); the last one looks the bytes up in ``norm``'s table and writes ``image``."""
+    from . import functional as HF
+    if jitter is not None:
+        if blur_table is None:
+            HF.color_jitter(crop_u8, jitter, norm.layout, norm=norm, out=image)
+        else:
+            crop_u8 = HF.color_jitter(crop_u8, jitter, norm.layout)
+    if blur_table is not None:
+        HF.gaussian_blur(crop_u8, None, norm.layout, norm=norm, out=image, table=blur_table, status=blur_status)
 
 
 class _DeviceParams:
@@ -170,7 +201,11 @@ class BatchAugment:
     ``filter``: the frames' filter (``device_augment`` is 'bicubic'); ``lbl_fill`` / ``fill``: the padding; ``batch``: the batch size, or
     None = the first call's.  The object owns the workspace, the ``params`` tensor (int32 (B, 6) = Hr, Wr, oy, ox, hflip, reserved) and a
     pinned staging buffer, all made at the first GPU call.  One object serves one stream at a time.  ``label_codec`` (a ``LabelCodec``):
-    the labels are RAW, as ``device_augment(label_codec=)`` takes them, and the label launch encodes them -- still three launches."""
+    the labels are RAW, as ``device_augment(label_codec=)`` takes them, and the label launch encodes them -- still three launches.
+
+    A Gaussian blur at the end of the image chain (``blur=`` of ``__call__`` and :meth:`run`, as ``device_augment``'s) adds two launches;
+    its records sit behind ``params`` in the same buffer (:attr:`blur_table`, int32 (B, 4)) and go up in the same copy, and
+    :attr:`blur_status` (int32 (B,)) holds what the blur launch declined."""
 
     def __init__(self, in_hw, crop, norm, scale_range, filter='bicubic', lbl_fill=255, fill=(0, 0, 0), batch=None, label_codec=None):
         from .utils import resample
@@ -196,7 +231,7 @@ class BatchAugment:
             raise ValueError(f'scale {lo} leaves nothing of {self.in_hw}')
         # ks_for is the rule; rounding the resized size down can make the true ratio a little larger than 1 / lo
         self.ks_max = max(resample.ks_for(filter, lo), *(resample.ksize_of(i, o, filter) for i, o in zip(self.in_hw, smallest)))
-        self.params = None
+        self.params = self.blur_table = self.blur_status = self._crop_u8 = None
 
     def _resized(self, scale):
         return _resized(self.in_hw, scale)
@@ -217,10 +252,20 @@ class BatchAugment:
                              f'{tuple(getattr(labels, "shape", ()))}')
         return self._dev.latch(b)
 
+    def _views(self, buffer):
+        """(params (B, 6), blur records (B, 4)) over one int32 buffer of B * 10 words."""
+        from . import functional as HF
+        from .utils import blur as BL
+        p, r = torch.split(buffer, (self.batch * HF.RESIZE_PARAM_WORDS, self.batch * BL.TABLE_WORDS))
+        return p.view(self.batch, HF.RESIZE_PARAM_WORDS), r.view(self.batch, BL.TABLE_WORDS)
+
     def _on(self, device):
         from . import functional as HF
-        if self._dev.on(device, HF.RESIZE_PARAM_WORDS, HF.ResizeTables, self.in_hw, self.crop, self.ks_max):
-            self.params = self._dev.buffer.view(self.batch, HF.RESIZE_PARAM_WORDS)
+        from .utils import blur as BL
+        if self._dev.on(device, HF.RESIZE_PARAM_WORDS + BL.TABLE_WORDS, HF.ResizeTables, self.in_hw, self.crop, self.ks_max):
+            self.params, self.blur_table = self._views(self._dev.buffer)
+            self.blur_status = torch.zeros(self.batch, dtype=torch.int32, device=device)
+            self._crop_u8 = None
             self.norm.table(device)
             if self.label_codec is not None:
                 self.label_codec.device_words(device)
@@ -237,10 +282,17 @@ class BatchAugment:
             rows.append(self._resized(s) + (int(o[0]), int(o[1]), int(bool(f)), 0))
         return torch.tensor(rows, dtype=torch.int32)
 
-    def _cpu(self, frames_u8, labels, rows, jitter):
+    def _cpu(self, frames_u8, labels, rows, jitter, blur=None, blur_table=None):
         rows = rows.tolist()
         return _crop_cpu(frames_u8, labels, [r[:2] for r in rows], [r[2:4] for r in rows], [r[4] for r in rows], jitter, self.crop,
-                         self.norm, self.filter, self.fill, self.lbl_fill, self.label_codec)
+                         self.norm, self.filter, self.fill, self.lbl_fill, self.label_codec, blur, blur_table)
+
+    def _crop_bytes(self, device):
+        """The uint8 crop of the batch between the resize launch and the image steps behind it: made once, so that a captured ``run``
+        finds it where it was."""
+        if self._crop_u8 is None or self._crop_u8.device != device:
+            self._crop_u8 = torch.empty(_frames_shape(self.norm.layout, self.batch, *self.crop), dtype=torch.uint8, device=device)
+        return self._crop_u8
 
     def _launch(self, frames_u8, labels, params, dst, dst_norm, label):
         from . import functional as HF
@@ -248,44 +300,68 @@ class BatchAugment:
         HF.frame_resize_batch(frames_u8, params, tables, self.norm.layout, fill=self.fill, norm=dst_norm, out=dst)
         HF.label_resize_batch(labels, params, tables, fill=self.lbl_fill, out=label, codec=self.label_codec)
 
-    def run(self, frames_u8, labels, params=None, out=None):
+    def run(self, frames_u8, labels, params=None, out=None, blur=None):
         """The three launches over whatever ``self.params`` (or the given device tensor of that shape) holds when they RUN: no host
         state is read or written, so a captured ``run`` replays with the parameters last copied into the tensor.  ``frames_u8`` and
         ``labels`` must be contiguous.  ``out``: ``(image, label)`` to write into.  Returns ``(image float32 (B, 3, h, w), label int64
-        (B, h, w))``.  Nothing checks the parameters on the host: a row the table launch declines sets :attr:`status`."""
+        (B, h, w))``.  Nothing checks the parameters on the host: a row the table launch declines sets :attr:`status`.
+
+        ``blur``: the blur records the same way -- an int32 (B, ``utils.blur.TABLE_WORDS``) tensor on the frames' device
+        (``utils.blur.params_table``), or True for the object's own :attr:`blur_table`, which ``__call__`` fills.  The resize then
+        writes the uint8 crop and ``functional.gaussian_blur`` normalises it: FIVE launches, and a captured ``run`` replays with the
+        radii last copied into the table (a record with apply 0 leaves its sample unblurred).  A record the kernels do not take sets
+        :attr:`blur_status`."""
         b = self._check(frames_u8, labels)
         if not frames_u8.is_cuda:
             rows = self.params if params is None else params
-            if rows is None:
-                raise ValueError('run on CPU tensors needs params')
-            return self._cpu(frames_u8, labels, rows, None)
+            if rows is None or blur is True:
+                raise ValueError('run on CPU tensors needs params, and the blur records themselves')
+            return self._cpu(frames_u8, labels, rows, None, blur_table=blur)
         self._on(frames_u8.device)
         params = self.params if params is None else params
         image, label = _outputs(b, *self.crop, frames_u8.device) if out is None else out
-        self._launch(frames_u8, labels, params, image, self.norm, label)
+        if blur is None:
+            self._launch(frames_u8, labels, params, image, self.norm, label)
+        else:
+            crop_u8 = self._crop_bytes(frames_u8.device)
+            self._launch(frames_u8, labels, params, crop_u8, None, label)
+            _image_tail(crop_u8, None, self.blur_table if blur is True else blur, self.norm, image, self.blur_status)
         return image, label
 
-    def __call__(self, frames_u8, labels, scale, offset, hflip, jitter=None):
-        """``device_augment(frames_u8, labels, scale, crop, offset, hflip, norm, lbl_fill, fill, jitter)``: same arguments, same
-        results.  The resized sizes are ``round((H, W) * scale)`` on the host; the parameters go up in one non-blocking copy."""
+    def __call__(self, frames_u8, labels, scale, offset, hflip, jitter=None, blur=None):
+        """``device_augment(frames_u8, labels, scale, crop, offset, hflip, norm, lbl_fill, fill, jitter, blur=blur)``: same arguments,
+        same results.  The resized sizes are ``round((H, W) * scale)`` on the host; the parameters -- the blur records among them -- go
+        up in one non-blocking copy."""
         b = self._check(frames_u8, labels)
         rows = self.rows(scale, offset, hflip, b)                # raises before any launch
+        if blur is not None:
+            from .utils import blur as BL
+            blur = BL.per_sample(blur, b)
         if not frames_u8.is_cuda:
-            return self._cpu(frames_u8, labels, rows, jitter)
+            return self._cpu(frames_u8, labels, rows, jitter, blur)
         from . import functional as HF
+        records = None if blur is None else HF.blur_records(blur, b)             # raises before any launch
         self._on(frames_u8.device)
         frames_u8, labels = frames_u8.contiguous(), labels.contiguous()
-        self._dev.upload(lambda staging: staging.view_as(rows).copy_(rows))
+
+        def fill_staging(staging):
+            s_rows, s_records = self._views(staging)
+            s_rows.copy_(rows)
+            if records is None:
+                s_records.zero_()
+            else:
+                s_records.copy_(records)
+        self._dev.upload(fill_staging)
         image, label = _outputs(b, *self.crop, frames_u8.device)
-        if jitter is None:
+        if jitter is None and blur is None:
             self._launch(frames_u8, labels, self.params, image, self.norm, label)
-        else:                                                    # the resize writes the uint8 crop, the jitter normalises
-            from .utils import jitter as J
-            jitter = J.per_sample(jitter, b)
-            layout = self.norm.layout
-            crop_u8 = torch.empty(_frames_shape(layout, b, *self.crop), dtype=torch.uint8, device=frames_u8.device)
+        else:                                                    # the resize writes the uint8 crop, the last image step normalises
+            if jitter is not None:
+                from .utils import jitter as J
+                jitter = J.per_sample(jitter, b)
+            crop_u8 = torch.empty(_frames_shape(self.norm.layout, b, *self.crop), dtype=torch.uint8, device=frames_u8.device)
             self._launch(frames_u8, labels, self.params, crop_u8, None, label)
-            HF.color_jitter(crop_u8, jitter, layout, norm=self.norm, out=image)
+            _image_tail(crop_u8, jitter, None if blur is None else self.blur_table, self.norm, image, self.blur_status)
         return image, label
 
 
@@ -659,3 +735,15 @@ def draw_color_jitter(brightness=0.0, contrast=0.0, saturation=0.0, hue=0.0, gen
         lo, hi = (-x, x) if name == 'hue' else (max(0.0, 1.0 - x), 1.0 + x)
         factors[name] = min(max(lo + (hi - lo) * r, lo), hi) if x > 0 else None
     return ColorJitterParams(tuple(n for n in order if factors[n] is not None), **factors)
+
+
+def draw_gaussian_blur(p=0.5, r=5, generator=None):
+    """One ``GaussianBlurParams`` drawn as the reference's ``RandomGaussianBlur(p, r)`` draws (hyperseg/datasets/seg_transforms.py:361-378):
+    with probability ``p`` the image is blurred with ``ImageFilter.GaussianBlur(radius=r)``, else it is left as it is (``apply`` False).
+    ``generator``: a CPU ``torch.Generator``.  A convenience for ``device_augment(blur=...)``, one call per sample: it does NOT claim to
+    consume random numbers as the reference's ``random.random()`` does."""
+    from .utils.blur import GaussianBlurParams
+    p = float(p)
+    if not 0.0 <= p <= 1.0:
+        raise ValueError(f'p must lie in [0, 1], got {p}')
+    return GaussianBlurParams(r, float(torch.rand((), generator=generator, dtype=torch.float64)) < p)

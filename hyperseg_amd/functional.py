@@ -1677,7 +1677,7 @@ def upsample_overlay(x, size, frames, style, out=None):
 
 
 # ------------------------------------------------------------------------------------------
-# uint8 frames and their labels: resize, colour jitter, rotate (csrc/hs_resample.hip, hs_jitter.hip, hs_rotate.hip).  Every wrapper
+# uint8 frames and their labels: resize, colour jitter, blur, rotate (csrc/hs_resample.hip, hs_jitter.hip, hs_blur.hip, hs_rotate.hip).  Every wrapper
 # checks its operands with the helpers below -- each raises ValueError, before any launch or host-to-device copy -- allocates, calls
 # its library entry and checks the status.
 # ------------------------------------------------------------------------------------------
@@ -2023,6 +2023,65 @@ def color_jitter(x_u8, params, layout='hwc', norm=None, out=None, table=None):
     _hip.run.hs_color_jitter_fwd(_hip.dev_ptr(x_u8, 'x_u8', torch.uint8), _LAYOUT_CODES[layout], b, h, w,
                                  _hip.dev_ptr(table, 'table', torch.int32), None if sums is None else sums.data_ptr(), norm_table,
                                  _hip.dev_ptr(out, 'out', out.dtype), _hip.stream_ptr())
+    return out
+
+
+def _blur_table(table, b, device):
+    from .utils import blur
+    if (not isinstance(table, torch.Tensor) or table.dtype != torch.int32 or tuple(table.shape) != (b, blur.TABLE_WORDS)
+            or table.device != device or not table.is_contiguous()):
+        raise ValueError(f'table must be a contiguous int32 tensor of shape {(b, blur.TABLE_WORDS)} on {device}')
+    return table
+
+
+def blur_records(params, b):
+    """``utils.blur.params_table(params, b)`` after refusing, on the host, a radius whose box radius the device kernels do not take."""
+    from .utils import blur
+    records = blur.params_table(params, b)
+    beyond = (records[:, 0] != 0) & (records[:, 1] > blur.MAX_RADIUS)
+    if bool(beyond.any()):
+        i = int(beyond.nonzero()[0])
+        raise ValueError(f'sample {i}: radius {blur.per_sample(params, b)[i].radius} has the box radius {int(records[i, 1])}, the device '
+                         f'kernels take up to {blur.MAX_RADIUS} (HS_BLUR_MAX_RADIUS)')
+    return records
+
+
+@_on_operand_device
+def gaussian_blur(x_u8, params, layout='hwc', norm=None, out=None, table=None, status=None):
+    """Pillow's ``ImageFilter.GaussianBlur`` for given parameters on uint8 frames (B, H, W, 3) / (B, 3, H, W) (``layout``), Pillow's bytes
+    (hs_gaussian_blur_fwd; the arithmetic: ``utils.blur``).  ``params``: one ``GaussianBlurParams`` for the batch or a sequence of B (a
+    ``None`` among them: that sample is not blurred).  Returns uint8 in the input's layout, or with ``norm`` (a
+    ``utils.inference.InputNorm``) the float32 (B, 3, H, W) image looked up in its table -- a sample that is not blurred too.  ``out``: a
+    contiguous tensor of that shape and dtype to write into.  Equal to ``utils.blur.gaussian_blur_cpu``.  A radius whose box radius
+    exceeds ``utils.blur.MAX_RADIUS`` (a sigma of about 16) raises ValueError before anything is launched or copied.
+
+    ``table``: the caller's own parameter records on the device -- int32 (B, ``utils.blur.TABLE_WORDS``), contiguous, what
+    ``utils.blur.params_table(params, B).to(device)`` gives; ``params`` is then not read (pass None).  The kernels read the table when
+    they run, so a captured graph replays with what the caller last copied into it; a record whose box radius the kernels do not take
+    leaves its sample unblurred and sets its word of ``status`` -- int32 (B,) on the device, written by every call (default a new one,
+    never read here).  Two launches (rows, columns) and a uint8 intermediate of the frames' size; without ``table`` one small
+    host-to-device copy of the records in front.  Nothing is read back: with ``table`` the call is capturable."""
+    b, h, w = _frames_bhw(x_u8, layout)
+    if b == 0 or h == 0 or w == 0:
+        raise ValueError('empty batch')
+    device = x_u8.device
+    if table is None:
+        records = blur_records(params, b)
+    else:
+        _blur_table(table, b, device)
+    if status is not None and (not isinstance(status, torch.Tensor) or status.dtype != torch.int32 or tuple(status.shape) != (b,)
+                               or status.device != device or not status.is_contiguous()):
+        raise ValueError(f'status must be a contiguous int32 tensor of shape {(b,)} on {device}')
+    out = _frame_out(out, b, h, w, layout, norm, device)
+    norm_table = _norm_table(norm, layout, device)
+    if table is None:
+        table = records.to(device)
+    if status is None:
+        status = torch.empty(b, device=device, dtype=torch.int32)
+    tmp = torch.empty_like(x_u8, memory_format=torch.contiguous_format)
+    _hip.run.hs_gaussian_blur_fwd(_hip.dev_ptr(x_u8, 'x_u8', torch.uint8), _LAYOUT_CODES[layout], b, h, w,
+                                  _hip.dev_ptr(table, 'table', torch.int32), tmp.data_ptr(), norm_table,
+                                  _hip.dev_ptr(out, 'out', out.dtype), status.data_ptr(), _hip.stream_ptr())
     return out
 
 

@@ -16,7 +16,7 @@ import torch.nn.functional as F
 from torch.optim.lr_scheduler import LRScheduler
 
 # the on-device frame augmentation lives in hyperseg_amd.augment; the names stay addressable as training.X
-from .augment import BatchAugment, BatchAugmentVOC, VOCBatchParams, _voc_cpu, device_augment, device_augment_voc, draw_color_jitter  # noqa: F401
+from .augment import BatchAugment, BatchAugmentVOC, VOCBatchParams, _voc_cpu, device_augment, device_augment_voc, draw_color_jitter, draw_gaussian_blur  # noqa: F401
 
 
 USE_HIP_BOOTSTRAP = True       # tests switch it off to reach the torch statements of the rule below

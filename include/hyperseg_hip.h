@@ -634,6 +634,26 @@ int hs_label_resize_batch_coded_fwd(const void* x, int32_t in_dtype, int32_t bat
 #define HS_JITTER_TABLE_WORDS 8
 int hs_color_jitter_fwd(const uint8_t* x, int32_t layout, int32_t batch, int32_t H, int32_t W, const int32_t* table,
                         uint64_t* sums, const float* norm_table, void* y, void* stream);
+/* Pillow's ImageFilter.GaussianBlur on uint8 RGB frames with Pillow's bytes (csrc/hs_blur.hip; the arithmetic: hyperseg_amd/utils/blur.py):
+ * an extended box blur, three box passes along the rows and three along the columns, each on the uint8 result of the one before.
+ * table: int32 (B, HS_BLUR_TABLE_WORDS), on the device, one record per sample -- word 0 the apply flag (0: the sample comes out as it
+ *   went in), word 1 the box radius r, words 2-3 the 8.24 weights ww and fw of one pass,
+ *   out[x] = (ww * sum(in[clamp(x + d)], |d| <= r) + fw * (in[clamp(x - r - 1)] + in[clamp(x + r + 1)]) + 2^23) >> 24 in 32 unsigned bits.
+ *   The kernels read it when they RUN: a captured graph replays with what the table holds then.  No record can make an access leave the
+ *   frame or the LDS: r is the only word that moves an address, and a record with r outside [0, HS_BLUR_MAX_RADIUS] leaves its sample
+ *   unblurred (as apply 0 does) and sets status[b] = HS_BLUR_STATUS_RADIUS; ww and fw are used as they are.
+ * status: int32 (B), on the device; every call writes all B words (0 where the record was taken).
+ * x uint8 (B, H, W, 3) | (B, 3, H, W) by layout.  tmp: uint8 workspace of x's size, the row launch's result.  norm_table null: y uint8
+ *   in the input's layout; else y float32 (B, 3, H, W), every byte -- of an unblurred sample too -- looked up in the (3, 256) table of
+ *   hs_image_ingest_fwd by the column launch.  Any alignment of x, tmp and y (a float's 4 bytes for the float form).  Two launches.
+ * HS_ERR_UNSUPPORTED -- nothing launched -- for batch > 65535 or H or W above HS_BLUR_MAX_DIM = 2^15 (3 H W then fits 32 unsigned bits
+ *   and a launch's tiles one grid dimension; offsets are 64-bit all the same).  Nothing is read back: capturable. */
+#define HS_BLUR_TABLE_WORDS 4
+#define HS_BLUR_MAX_RADIUS 15
+#define HS_BLUR_MAX_DIM 32768
+#define HS_BLUR_STATUS_RADIUS 1
+int hs_gaussian_blur_fwd(const uint8_t* x, int32_t layout, int32_t batch, int32_t H, int32_t W, const int32_t* table,
+                         uint8_t* tmp, const float* norm_table, void* y, int32_t* status, void* stream);
 /* uint8 frames and labels rotated on the device with Pillow's arithmetic (csrc/hs_rotate.hip; the arithmetic: hyperseg_amd/utils/rotate.py):
  * PIL.Image.rotate(angle, expand=False) about the centre, what the reference's RandomRotation runs (hyperseg/datasets/seg_transforms.py:
  * 384-426), and the ConstantPad after it (:181-217) as a VIEW: the output is (Ho, Wo), the rotated (H, W) image at its top-left corner, a
