@@ -144,6 +144,9 @@ SIGNATURES = {
     'hs_bootstrap_mean_batched_fwd': ([vp, i32, i32, i32, C.c_float, vp, vp, vp], STATUS),
     'hs_bootstrap_mean_batched_bwd': ([vp, i32, i32, vp, vp, vp, vp], STATUS),
     'hs_patch_ir_route': ([C.POINTER(StageInputC), i32, i32, i32, i32, i32, i32], C.c_int),
+    'hs_patch_ir_form': ([C.POINTER(StageInputC), i32, i32, i64, i32, i32, i32, i32, i32, i32, C.POINTER(C.c_int32)], C.c_int),
+    'hs_patch_ir_v0_route': ([C.POINTER(StageInputC), i32, i32, i64, i32, i32, i32, i32, C.POINTER(C.c_int32)], C.c_int),
+    'hs_patch_conv_route': ([C.POINTER(StageInputC), i32, i32, i64] + [i32] * 10 + [C.POINTER(C.c_int32)], C.c_int),
     'hs_ir_tile_map': ([i32, i32, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), i32], STATUS),
     'hs_upsample_bilinear_fwd': ([vp, i32, i32, i32, i32, i32, i32, vp, vp], STATUS),
     'hs_upsample_argmax_fwd': ([vp, i32, i32, i32, i32, i32, i32, vp, vp], STATUS),

@@ -520,6 +520,9 @@ void upsample_argmax_kernel(const float* __restrict__ x, int B, int C, int Hi, i
 int try_fast_fwd(int dtype, const void* x, const void* bank, long ld, int batch, int c_in, int H, int W, int fh, int fw, int c_out,
                  int k, int pad, int pad_mode, int groups, const float* scale, const float* shift, int act, void* y,
                  hipStream_t stream);                                                                            // hs_patch_conv_bwd.hip
+int fast_fwd_form(bool aligned8, int batch, int c_in, int H, int W, int fh, int fw, int c_out, int k, int pad, int pad_mode, int groups,
+                  bool with_scale, bool with_shift, int act, int form[4]);                                         // hs_patch_conv_bwd.hip
+bool k1m_form(const StageIn& si, int fh, int fw, long ld, bool bank_aligned16, int cin, int c_out, int form[4]);   // hs_patch_conv_k1m.hip
 int try_launch_k1m(const StageIn& si, int fh, int fw, const float* bank, long ld, int cin, int c_out,
                    const float* scale, const float* shift, int act, float* y, hipStream_t stream);     // hs_patch_conv_k1m.hip
 
@@ -527,23 +530,51 @@ int try_launch_k1m(const StageIn& si, int fh, int fw, const float* bank, long ld
 
 using namespace hs;
 
+// What the k = 1 whole-patch form is for a shape (launch_conv1x1 and hs_patch_conv_route): false = it does not apply; PWL = the kernel's
+// instantiation (log2 of a square patch's edge for 1, 2, 4, 8 pixels, -1 = any patch), split = lanes that share one output's reduction.
+static bool conv1x1_form(int cin, int ph, int pw, int c_out, int cin_g, long ld, bool bank_aligned16, int& pwl, int& split, size_t& lds1) {
+    const size_t hp4 = ((size_t)c_out * cin_g + 3) & ~(size_t)3;
+    lds1 = (hp4 + (size_t)cin * ph * pw) * sizeof(float);
+    if (!(lds1 <= 96 * 1024 && (ld & 3) == 0 && bank_aligned16 && ph * pw <= 4096)) return false;
+    const int outs = c_out * ph * pw;
+    split = 1;
+    while (split < 64 && outs * split * 2 <= CONV_THREADS && split * 2 <= cin_g) split *= 2;
+    pwl = ph != pw ? -1 : ph == 1 ? 0 : ph == 2 ? 1 : ph == 4 ? 2 : ph == 8 ? 3 : -1;
+    return true;
+}
+
+// The generic kernel's tile: the whole patch if it fits the LDS budget, otherwise split (rows first, then columns).  HS_ERR_LDS where
+// not even a one-pixel tile fits.  (hs_patch_conv_fwd and hs_patch_conv_route.)
+static int conv_tiles(int cin, int c_out, int cin_g, int k, int pad, int ph, int pw, int& TH, int& TW, int& tiles_y, int& tiles_x, size_t& lds) {
+    const int w_stride = (cin_g * k * k) | 1;
+    const size_t budget = 96 * 1024;
+    const size_t wbytes = (size_t)c_out * w_stride * sizeof(float);
+    if (wbytes + (size_t)cin * (1 + 2 * pad) * (1 + 2 * pad) * sizeof(float) > 150 * 1024) return HS_ERR_LDS;
+    TW = pw > 64 ? 64 : pw;
+    TH = ph > 64 ? 64 : ph;
+    auto tile_bytes = [&](int th, int tw) { return wbytes + (size_t)cin * (th + 2 * pad) * (tw + 2 * pad) * sizeof(float); };
+    while (tile_bytes(TH, TW) > budget && (TH > 1 || TW > 1)) {
+        if (TH >= TW && TH > 1) TH = (TH + 1) / 2; else TW = (TW + 1) / 2;
+    }
+    tiles_y = (ph + TH - 1) / TH;
+    tiles_x = (pw + TW - 1) / TW;
+    lds = tile_bytes(TH, TW);
+    return HS_OK;
+}
+
 // The k = 1 whole-patch-per-workgroup form; ``co``: blocked signal2weights workgroups to run beside it (heterogeneous launch) or
 // null.  1 = the form does not apply.
 static int launch_conv1x1(const StageIn& si, int batch, int fh, int fw, int ph, int pw, const float* bank, long ld, int c_out, int groups,
                           int cin_g, int cout_g, const float* scale, const float* shift, int act, float* y, const S2bArgs* co,
                           hipStream_t stream) {
-    const int cin = si.cin();
-    const size_t hp4 = ((size_t)c_out * cin_g + 3) & ~(size_t)3;
-    size_t lds1 = (hp4 + (size_t)cin * ph * pw) * sizeof(float);
-    if (!(lds1 <= 96 * 1024 && (ld & 3) == 0 && ((uintptr_t)bank & 15) == 0 && ph * pw <= 4096)) return 1;
+    size_t lds1;
+    int pwl, split;
+    if (!conv1x1_form(si.cin(), ph, pw, c_out, cin_g, ld, ((uintptr_t)bank & 15) == 0, pwl, split, lds1)) return 1;
     Conv1S2wArgs g;
     Conv1Args& f = g.c;
     f.in = si; f.fh = fh; f.fw = fw; f.ph = ph; f.pw = pw; f.bank = bank; f.ld = ld;
     f.cout = c_out; f.groups = groups; f.cin_g = cin_g; f.cout_g = cout_g;
     f.scale = scale; f.shift = shift; f.act = act; f.y = y;
-    const int outs = c_out * ph * pw;
-    int split = 1;
-    while (split < 64 && outs * split * 2 <= CONV_THREADS && split * 2 <= cin_g) split *= 2;
     f.split = split;
     const long conv_blocks = (long)batch * fh * fw;
     if (co) {
@@ -562,10 +593,10 @@ static int launch_conv1x1(const StageIn& si, int batch, int fh, int fw, int ph, 
         if (co) hipLaunchKernelGGL(patch_conv1x1_s2w_kernel<PWL>, grid, dim3(CONV_THREADS), lds1, stream, g); \
         else hipLaunchKernelGGL(patch_conv1x1_kernel<PWL>, grid, dim3(CONV_THREADS), lds1, stream, f); \
         return launch_status(); } while (0)
-    if (ph == pw && ph == 1) HS_K1_LAUNCH(0);
-    if (ph == pw && ph == 2) HS_K1_LAUNCH(1);
-    if (ph == pw && ph == 4) HS_K1_LAUNCH(2);
-    if (ph == pw && ph == 8) HS_K1_LAUNCH(3);
+    if (pwl == 0) HS_K1_LAUNCH(0);
+    if (pwl == 1) HS_K1_LAUNCH(1);
+    if (pwl == 2) HS_K1_LAUNCH(2);
+    if (pwl == 3) HS_K1_LAUNCH(3);
     HS_K1_LAUNCH(-1);
 #undef HS_K1_LAUNCH
 }
@@ -638,21 +669,10 @@ extern "C" int hs_patch_conv_fwd(const hs_stage_input* in, int32_t fh, int32_t f
                                      nullptr, (hipStream_t)stream);
         if (r != 1) return r;
     }
-    const int wrow = a.cin_g * k * k;
-    a.w_stride = wrow | 1;
-    // tile: whole patch if it fits the LDS budget, otherwise split (rows first, then columns)
-    const size_t budget = 96 * 1024;
-    const size_t wbytes = (size_t)c_out * a.w_stride * sizeof(float);
-    if (wbytes + (size_t)cin * (1 + 2 * pad) * (1 + 2 * pad) * sizeof(float) > 150 * 1024) return HS_ERR_LDS;
-    a.TW = a.pw > 64 ? 64 : a.pw;
-    a.TH = a.ph > 64 ? 64 : a.ph;
-    auto tile_bytes = [&](int th, int tw) { return wbytes + (size_t)cin * (th + 2 * pad) * (tw + 2 * pad) * sizeof(float); };
-    while (tile_bytes(a.TH, a.TW) > budget && (a.TH > 1 || a.TW > 1)) {
-        if (a.TH >= a.TW && a.TH > 1) a.TH = (a.TH + 1) / 2; else a.TW = (a.TW + 1) / 2;
-    }
-    a.tiles_y = (a.ph + a.TH - 1) / a.TH;
-    a.tiles_x = (a.pw + a.TW - 1) / a.TW;
-    const size_t lds = tile_bytes(a.TH, a.TW);
+    a.w_stride = (a.cin_g * k * k) | 1;
+    size_t lds;
+    st = conv_tiles(cin, c_out, a.cin_g, k, pad, a.ph, a.pw, a.TH, a.TW, a.tiles_y, a.tiles_x, lds);
+    if (st != HS_OK) return st;
     if (lds > 64 * 1024) {
         static std::atomic<unsigned long long> done{0};
         const int e = allow_full_lds((const void*)patch_conv_kernel, done);
@@ -661,6 +681,48 @@ extern "C" int hs_patch_conv_fwd(const hs_stage_input* in, int32_t fh, int32_t f
     const long blocks = (long)in->batch * fh * fw * a.tiles_y * a.tiles_x;
     hipLaunchKernelGGL(patch_conv_kernel, dim3((unsigned)blocks), dim3(CONV_THREADS), lds, (hipStream_t)stream, a);
     return launch_status();
+}
+
+// Which form hs_patch_conv_fwd takes (include/hyperseg_hip.h): the same argument checks and the same predicates in the same order,
+// nothing launched, pointers may be null.
+extern "C" int hs_patch_conv_route(const hs_stage_input* in, int32_t fh, int32_t fw, int64_t ld, int32_t c_out, int32_t k, int32_t pad,
+                                   int32_t pad_mode, int32_t groups, int32_t with_scale, int32_t with_shift, int32_t act,
+                                   int32_t aligned16, int32_t aligned8, int32_t* form) {
+    if (!in) return HS_ERR_BAD_ARG;
+    hs_stage_input probe = *in;
+    alignas(16) static const float dummy = 0.0f;                 // make_stage only checks that the pointers exist
+    if (probe.c_skip > 0 && !probe.skip) probe.skip = &dummy;
+    if (probe.c_prev > 0 && !probe.prev) probe.prev = &dummy;
+    StageIn si;
+    const int st = make_stage(&probe, &si);
+    if (st != HS_OK) return st;
+    if (fh <= 0 || fw <= 0 || c_out <= 0 || k <= 0 || groups <= 0 || pad < 0) return HS_ERR_BAD_ARG;
+    if (2 * pad != k - 1) return HS_ERR_UNSUPPORTED;
+    if (pad_mode < HS_PAD_ZEROS || pad_mode > HS_PAD_CIRCULAR) return HS_ERR_BAD_ARG;
+    if (in->H % fh != 0 || in->W % fw != 0) return HS_ERR_NOT_DIVISIBLE;
+    const int cin = si.cin();
+    if (cin % groups != 0 || c_out % groups != 0) return HS_ERR_BAD_ARG;
+    if (pad_mode == HS_PAD_REFLECT && (pad >= in->H || pad >= in->W)) return HS_ERR_BAD_ARG;
+    const int ph = in->H / fh, pw = in->W / fw, cin_g = cin / groups;
+    if (ld < (int64_t)c_out * cin_g * k * k) return HS_ERR_BAD_ARG;
+    if (with_scale && !with_shift) return HS_ERR_BAD_ARG;
+    int f[4] = {0, 0, 0, 0};
+    auto answer = [&](int route) { if (form) for (int i = 0; i < 4; ++i) form[i] = f[i]; return route; };
+    if (!si.coords && si.c_prev == 0) {
+        const int r = fast_fwd_form(aligned8 != 0, si.B, cin, si.H, si.W, fh, fw, c_out, k, pad, pad_mode, groups, with_scale != 0,
+                                    with_shift != 0, act, f);
+        if (r >= 0) return answer(r);
+    }
+    if (k == 1 && groups == 1 && k1m_form(si, fh, fw, (long)ld, aligned16 != 0, cin, c_out, f)) return answer(HS_CONV_ROUTE_K1M);
+    if (k == 1) {
+        size_t lds1;
+        f[0] = f[1] = f[2] = f[3] = 0;
+        if (conv1x1_form(cin, ph, pw, c_out, cin_g, (long)ld, aligned16 != 0, f[0], f[1], lds1)) return answer(HS_CONV_ROUTE_K1);
+    }
+    size_t lds;
+    f[0] = f[1] = f[2] = f[3] = 0;
+    const int e = conv_tiles(cin, c_out, cin_g, k, pad, ph, pw, f[0], f[1], f[2], f[3], lds);
+    return e != HS_OK ? e : answer(HS_CONV_ROUTE_TILED);
 }
 
 // hs_patch_conv_s2w_fwd: hs_patch_conv_fwd (k = 1, no padding) and hs_signal2weights_multi_fwd for ``layers`` in ONE launch (see

@@ -36,6 +36,8 @@ struct ConvBwdArgs {
     float inv_ph, inv_pw;              // 1 / ph, 1 / pw (div_by_inv: the image-level depthwise kernels)
 };
 
+int fast_fwd_form(bool aligned8, int batch, int c_in, int H, int W, int fh, int fw, int c_out, int k, int pad, int pad_mode, int groups,
+                  bool with_scale, bool with_shift, int act, int form[4]);
 int try_fast_fwd(int dtype, const void* x, const void* bank, long ld, int batch, int c_in, int H, int W, int fh, int fw, int c_out,
                  int k, int pad, int pad_mode, int groups, const float* scale, const float* shift, int act, void* y, hipStream_t stream);
 int try_fast_bwd_in(int dtype, const void* dy, const void* bank, long ld, int batch, int c_in, int H, int W, int fh, int fw,
@@ -1134,18 +1136,46 @@ static void fast_args(ConvBwdArgs& a, const void* bank, long ld, int batch, int 
     a.inv_ph = 1.0f / (float)a.ph; a.inv_pw = 1.0f / (float)a.pw;
 }
 // the pair forms: even patch and image widths (a pair never straddles a tile or a row), 8-byte aligned planes, div_by_inv's range
+static bool dw3_pairs_shape(int pw, int H, int W, long planes, bool aligned8) {
+    return (pw & 1) == 0 && (W & 1) == 0 && aligned8 && H < (1 << 21) && W < (1 << 21) && planes < (1 << 21);
+}
 static bool dw3_pairs(const ConvBwdArgs& a, const void* p, const void* q) {
-    return (a.pw & 1) == 0 && (a.W & 1) == 0 && ((((size_t)p) | ((size_t)q)) & 7) == 0 && a.H < (1 << 21) && a.W < (1 << 21) && (long)a.B * a.cin < (1 << 21);
+    return dw3_pairs_shape(a.pw, a.H, a.W, (long)a.B * a.cin, ((((size_t)p) | ((size_t)q)) & 7) == 0);
+}
+
+// The form try_fast_fwd takes for a plain input (hs_patch_conv_route asks the same question with nothing launched): -1 = none,
+// HS_CONV_ROUTE_PLAIN_DW3 with form = {pairs}, or HS_CONV_ROUTE_PLAIN_K1M with form = {MT, KQ, pixels per lane, affine}.
+int hs::fast_fwd_form(bool aligned8, int batch, int c_in, int H, int W, int fh, int fw, int c_out, int k, int pad, int pad_mode, int groups,
+                      bool with_scale, bool with_shift, int act, int form[4]) {
+    form[0] = form[1] = form[2] = form[3] = 0;
+    if (H % fh || W % fw) return -1;
+    const int ph = H / fh, pw = W / fw;
+    const bool pairs = dw3_pairs_shape(pw, H, W, (long)batch * c_in, aligned8);
+    if (k == 3 && pad == 1 && pad_mode == HS_PAD_ZEROS && groups == c_in && c_in == c_out && !with_scale && act == HS_ACT_NONE &&
+        (long)batch * c_in <= 65535) {                                  // plain depthwise 3x3 (the autograd path's middle layer)
+        form[0] = pairs ? 1 : 0;
+        return HS_CONV_ROUTE_PLAIN_DW3;
+    }
+    if (k != 1 || groups != 1 || ph * pw < 64) return -1;
+    const int mt = (c_out + 15) / 16, kq = (c_in + 15) / 16;
+    const bool affine = with_scale || act != HS_ACT_NONE;
+    if (affine && (!with_scale || !with_shift)) return -1;              // an activation without the affine rows: the generic kernel
+    if (mt > 4 || kq > 4 || (mt == 4 && kq == 4)) return -1;            // the instantiated (MT, KQ) pairs
+    form[0] = mt; form[1] = kq; form[2] = pairs && ph * pw >= 128 ? 2 : 1; form[3] = affine ? 1 : 0;
+    return HS_CONV_ROUTE_PLAIN_K1M;
 }
 
 int hs::try_fast_fwd(int dtype, const void* x, const void* bank, long ld, int batch, int c_in, int H, int W, int fh, int fw, int c_out,
                      int k, int pad, int pad_mode, int groups, const float* scale, const float* shift, int act, void* y, hipStream_t stream) {
     if (H % fh || W % fw || !storage_known(dtype)) return 1;
+    int form[4];
+    const int route = fast_fwd_form(((((size_t)x) | ((size_t)y)) & 7) == 0, batch, c_in, H, W, fh, fw, c_out, k, pad, pad_mode, groups,
+                                    scale != nullptr, shift != nullptr, act, form);
+    if (route < 0) return 1;
     ConvBwdArgs a;
     fast_args(a, bank, ld, batch, c_in, H, W, fh, fw, c_out);
-    if (k == 3 && pad == 1 && pad_mode == HS_PAD_ZEROS && groups == c_in && c_in == c_out && !scale && act == HS_ACT_NONE &&
-        (long)batch * c_in <= 65535) {                                  // plain depthwise 3x3 (the autograd path's middle layer)
-        if (dw3_pairs(a, x, y)) {
+    if (route == HS_CONV_ROUTE_PLAIN_DW3) {                             // plain depthwise 3x3 (the autograd path's middle layer)
+        if (form[0]) {
             const dim3 grid2((W / 2 + 63) / 64, (H + 3) / 4, batch * c_in);
             with_storage(dtype, [&](auto tag) {
                 using T = decltype(tag);
@@ -1160,15 +1190,13 @@ int hs::try_fast_fwd(int dtype, const void* x, const void* bank, long ld, int ba
         });
         return launch_status();
     }
-    if (k != 1 || groups != 1 || a.ph * a.pw < 64) return 1;
     a.dy = (const float*)x; a.dx = (float*)y;
-    const int mt = (c_out + 15) / 16, kq = (c_in + 15) / 16;
+    const int mt = form[0], kq = form[1];
     const dim3 grid((unsigned)(batch * fh * fw));
     // even widths, aligned planes, patches of at least four super-tiles: two adjacent pixels per lane (measured at config 5, visit r5c: 23.8 -> 23.1
     // and 13.3 -> 12.1 us on the 324- / 256-pixel patches, 7.4 -> 9.5 us on the 16-pixel ones, where half of a super-tile's lanes idle)
-    const bool px2 = dw3_pairs(a, x, y) && a.ph * a.pw >= 128;
-    const bool affine = scale != nullptr || act != HS_ACT_NONE;
-    if (affine && (!scale || !shift)) return 1;                         // an activation without the affine rows: the generic kernel
+    const bool px2 = form[2] == 2;
+    const bool affine = form[3] != 0;
 #define HS_FW_L(MTV, KQV, PXV, AFV) with_storage(dtype, [&](auto tag) { \
         hipLaunchKernelGGL((patch_conv_fwd_k1m_kernel<MTV, KQV, PXV, AFV, decltype(tag)>), grid, dim3(256), 0, stream, a, scale, shift, act); })
 #define HS_FW(MTV, KQV) if (mt == MTV && kq == KQV) { \

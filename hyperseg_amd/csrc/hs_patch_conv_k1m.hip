@@ -156,6 +156,7 @@ void patch_conv_k1m_kernel(K1mArgs a) {
     }
 }
 
+bool k1m_form(const StageIn& si, int fh, int fw, long ld, bool bank_aligned16, int cin, int c_out, int form[4]);
 int try_launch_k1m(const StageIn& si, int fh, int fw, const float* bank, long ld, int cin, int c_out,
                    const float* scale, const float* shift, int act, float* y, hipStream_t stream);
 
@@ -166,22 +167,32 @@ using namespace hs;
 // 0 = launched, 1 = not covered (hs_patch_conv_fwd goes on to its other forms), else an error code.  Coverage: k = 1, groups = 1,
 // square patches of 1 or 2 pixels, at least 1024 patches, even cin <= 144, cout <= 96, a previous level (if any) bilinear at exactly
 // half the resolution, 16-byte aligned bank rows.
+bool hs::k1m_form(const StageIn& si, int fh, int fw, long ld, bool bank_aligned16, int cin, int c_out, int form[4]) {
+    form[0] = form[1] = form[2] = form[3] = 0;
+    if (si.H % fh || si.W % fw) return false;
+    const int ph = si.H / fh, pw = si.W / fw;
+    if (ph != pw || pw != 2) return false;     // one-pixel patches (level 0, 98 -> 96) measured SLOWER here: 126 vs 82 us -- the staged kernel keeps them
+    if ((long)si.B * fh * fw < HS_K1M_MIN_PATCHES || si.B > 65535 || fh > 65535) return false;
+    if (cin > K1M_MAXC || (cin & 1) || cin < 4 || c_out > 96 || si.c_skip < 1) return false;
+    if (si.c_prev > 0 && (si.prev_mode != HS_PREV_BILINEAR || si.Hp * 2 != si.H || si.Wp * 2 != si.W)) return false;
+    if ((ld & 3) || !bank_aligned16) return false;
+    if (((cin + 15) & ~15) > K1M_MAXC) return false;
+    form[0] = (c_out + 15) / 16 <= 3 ? 3 : 6;          // RT
+    form[1] = (cin & 3) == 0 ? 4 : 2;                  // AL
+    form[2] = si.c_prev > 0 ? 1 : 0;                   // PREV
+    return true;
+}
+
 int hs::try_launch_k1m(const StageIn& si, int fh, int fw, const float* bank, long ld, int cin, int c_out,
                        const float* scale, const float* shift, int act, float* y, hipStream_t stream) {
-    if (si.H % fh || si.W % fw) return 1;
-    const int ph = si.H / fh, pw = si.W / fw;
-    if (ph != pw || pw != 2) return 1;     // one-pixel patches (level 0, 98 -> 96) measured SLOWER here: 126 vs 82 us -- the staged kernel keeps them
-    if ((long)si.B * fh * fw < HS_K1M_MIN_PATCHES || si.B > 65535 || fh > 65535) return 1;
-    if (cin > K1M_MAXC || (cin & 1) || cin < 4 || c_out > 96 || si.c_skip < 1) return 1;
-    if (si.c_prev > 0 && (si.prev_mode != HS_PREV_BILINEAR || si.Hp * 2 != si.H || si.Wp * 2 != si.W)) return 1;
-    if ((ld & 3) || (((size_t)bank) & 15)) return 1;
+    int form[4];
+    if (!k1m_form(si, fh, fw, ld, (((size_t)bank) & 15) == 0, cin, c_out, form)) return 1;
+    const int pw = 2;
     const int kp = (cin + 15) & ~15;
-    if (kp > K1M_MAXC) return 1;
     K1mArgs a{si, bank, ld, fh, fw, cin, c_out, kp, scale, shift, act, y};
     const dim3 grid((fw + 3) / 4, fh, si.B), block(256);
     const size_t lds = (size_t)4 * pw * pw * (kp + 4) * sizeof(float);
-    const int al = (cin & 3) == 0 ? 4 : 2;
-    const int rt = (c_out + 15) / 16;
+    const int rt = form[0], al = form[1];
 #define HS_K1M_(PWV, RTV, ALV) do { if (si.c_prev > 0) hipLaunchKernelGGL((patch_conv_k1m_kernel<PWV, RTV, ALV, true>), grid, block, lds, stream, a); \
                                     else hipLaunchKernelGGL((patch_conv_k1m_kernel<PWV, RTV, ALV, false>), grid, block, lds, stream, a); } while (0)
 #define HS_K1M(PWV, RTV) do { if (al == 4) HS_K1M_(PWV, RTV, 4); else HS_K1M_(PWV, RTV, 2); } while (0)

@@ -198,11 +198,13 @@ static int launch_ir(const IrArgs& a, int threads, size_t lds, long blocks, hipS
 
 int try_launch_ir_fused(int mode, const StageIn& in, int fh, int fw, const float* bank, long ld, int cin, int c_skip,
                         int hid, int c_out, const float* s1, const float* b1, const float* s2, const float* b2,
-                        const float* s3, const float* b3, float* y, hipStream_t stream);   // hs_patch_ir_fused.hip
+                        const float* s3, const float* b3, float* y, hipStream_t stream, int* form = nullptr);   // hs_patch_ir_fused.hip
 int try_launch_irc(const StageIn& in, int fh, int fw, const float* bank, long ld, int hid, int c_out,
                    const float* s1, const float* b1, const float* s2, const float* b2, const float* s3, const float* b3,
-                   float* y, hipStream_t stream);                                           // hs_patch_irc.hip
+                   float* y, hipStream_t stream, int* form = nullptr);                      // hs_patch_irc.hip
 size_t ird_workspace_bytes(const StageIn& si, int fh, int fw, int cin, int hid, int c_out);  // hs_patch_ir_d2.hip
+bool ird_form(const StageIn& si, int fh, int fw, long ld, int cin, int hid, int c_out, bool with_workspace, size_t workspace_bytes,
+              bool aligned16, int form[4]);                                                  // hs_patch_ir_d2.hip
 int try_launch_ird(const StageIn& si, int fh, int fw, const float* bank, long ld, int cin, int hid, int c_out,
                    const float* s1, const float* b1, const float* s2, const float* b2, const float* s3, const float* b3,
                    float* workspace, size_t workspace_bytes, float* y, hipStream_t stream);
@@ -219,6 +221,26 @@ using namespace hs;
 static bool ir_auto_prefers_f32(int math, int c_skip, long patches, int ph, int pw) {
     if (math != HS_IR_MATH_AUTO || c_skip > 4 || ph % 16 != 0 || pw % 16 != 0) return false;
     return patches * (ph / 16) * (pw / 16) > 2 * 256;
+}
+
+// The generic kernel's instantiation, HS_IR_GENERIC(CIN, CSKIP, COUT): exact channel counts for the decoder's own shapes in the fused
+// form (coords + bilinear previous level, no residual), else the narrowest width class; -1 = none (hs_patch_ir_fwd and hs_patch_ir_form).
+static int ir_generic_form(bool fused_form, int cin, int c_skip, int c_out) {
+    static const int exact[5][3] = {
+        {24, 6, 16},     // HyperSeg-M / CamVid-S level 3
+        {34, 16, 19},    // HyperSeg-M level 4 (Cityscapes, 19 classes)
+        {14, 4, 8},      // HyperSeg-S level 3
+        {26, 16, 19},    // HyperSeg-S level 4
+        {22, 4, 12},     // CamVid-S level 4 (12 classes)
+    };
+    if (fused_form)
+        for (const auto& e : exact)
+            if (cin == e[0] && c_skip == e[1] && c_out == e[2]) return HS_IR_GENERIC(e[0], e[1], e[2]);
+    if (cin <= 16 && c_out <= 16) return HS_IR_GENERIC(16, 0, 16);
+    if (cin <= 32 && c_out <= 32) return HS_IR_GENERIC(32, 0, 32);
+    if (cin <= 64 && c_out <= 32) return HS_IR_GENERIC(64, 0, 32);
+    if (cin <= 128 && c_out <= 64) return HS_IR_GENERIC(128, 0, 64);
+    return -1;
 }
 
 extern "C" int hs_patch_ir_fwd(const hs_stage_input* in, int32_t fh, int32_t fw, const float* bank, int64_t ld,
@@ -266,48 +288,112 @@ extern "C" int hs_patch_ir_fwd(const hs_stage_input* in, int32_t fh, int32_t fw,
                                              a.s1, a.b1, a.s2, a.b2, a.s3, a.b3, y, s);
         if (st_m != 1) return st_m;
     }
-#define HS_IR_CASE(CI, CS, CO) \
-    if (fused_form && a.cin == CI && in->c_skip == CS && c_out == CO) return launch_ir<CI, CS, CO, true>(a, threads, lds, blocks, s);
-    HS_IR_CASE(24, 6, 16)    // HyperSeg-M / CamVid-S level 3
-    HS_IR_CASE(34, 16, 19)   // HyperSeg-M level 4 (Cityscapes, 19 classes)
-    HS_IR_CASE(14, 4, 8)     // HyperSeg-S level 3
-    HS_IR_CASE(26, 16, 19)   // HyperSeg-S level 4
-    HS_IR_CASE(22, 4, 12)    // CamVid-S level 4 (12 classes)
+    const int inst = ir_generic_form(fused_form, a.cin, in->c_skip, c_out);
+#define HS_IR_CASE(CI, CS, CO, EX) if (inst == HS_IR_GENERIC(CI, CS, CO)) return launch_ir<CI, CS, CO, EX>(a, threads, lds, blocks, s);
+    HS_IR_CASE(24, 6, 16, true) HS_IR_CASE(34, 16, 19, true) HS_IR_CASE(14, 4, 8, true) HS_IR_CASE(26, 16, 19, true) HS_IR_CASE(22, 4, 12, true)
+    HS_IR_CASE(16, 0, 16, false) HS_IR_CASE(32, 0, 32, false) HS_IR_CASE(64, 0, 32, false) HS_IR_CASE(128, 0, 64, false)
 #undef HS_IR_CASE
-    if (a.cin <= 16 && c_out <= 16) return launch_ir<16, 0, 16, false>(a, threads, lds, blocks, s);
-    if (a.cin <= 32 && c_out <= 32) return launch_ir<32, 0, 32, false>(a, threads, lds, blocks, s);
-    if (a.cin <= 64 && c_out <= 32) return launch_ir<64, 0, 32, false>(a, threads, lds, blocks, s);
-    if (a.cin <= 128 && c_out <= 64) return launch_ir<128, 0, 64, false>(a, threads, lds, blocks, s);
     return HS_ERR_UNSUPPORTED;
 }
 
-// Which kernel hs_patch_ir_fwd would run (host only): the same dispatch with nothing launched.
-extern "C" int hs_patch_ir_route(const hs_stage_input* in, int32_t fh, int32_t fw, int32_t hidden, int32_t c_out,
-                                 int32_t residual, int32_t math) {
-    if (math < HS_IR_MATH_AUTO || math > HS_IR_MATH_SPLIT) return HS_ERR_BAD_ARG;
+// Which kernel hs_patch_ir_fwd would run, and its form inside the route (host only): the same dispatch with nothing launched.
+// strict: answer as the LAUNCHER does -- its argument checks (short ld, residual with cin != c_out, H or W below 2) and any error of a
+// matrix-core launcher other than "not covered" (HS_ERR_LDS) come back as that error; hs_patch_ir_route keeps its older, lenient answers.
+static int ir_form(const hs_stage_input* in, int32_t fh, int32_t fw, int64_t ld_arg, int32_t hidden, int32_t c_out,
+                   int32_t residual, int32_t math, int32_t bank_aligned16, int32_t y_aligned16, int32_t* form, bool strict) {
+    if (math < HS_IR_MATH_AUTO || math > HS_IR_MATH_SPLIT || !in) return HS_ERR_BAD_ARG;
     hs_stage_input probe = *in;
-    alignas(16) static const float dummy = 0.0f;                 // make_stage only checks that the pointers exist; 16-byte aligned like a real bank
-    if (probe.c_skip > 0 && !probe.skip) probe.skip = &dummy;
-    if (probe.c_prev > 0 && !probe.prev) probe.prev = &dummy;
+    alignas(16) static const float dummy[2] = {0.0f, 0.0f};      // make_stage only checks that the pointers exist; dummy + 1: a bank 4 bytes off
+    if (probe.c_skip > 0 && !probe.skip) probe.skip = dummy;
+    if (probe.c_prev > 0 && !probe.prev) probe.prev = dummy;
     StageIn si;
     const int st = make_stage(&probe, &si);
     if (st != HS_OK) return st;
     if (fh <= 0 || fw <= 0 || hidden <= 0 || c_out <= 0) return HS_ERR_BAD_ARG;
     if (in->H % fh != 0 || in->W % fw != 0) return HS_ERR_NOT_DIVISIBLE;
+    if (strict && (in->H < 2 || in->W < 2)) return HS_ERR_BAD_ARG;
     const int cin = si.cin();
-    const long ld = (((long)cin * hidden + 9L * hidden + (long)hidden * c_out) + 3) & ~3L;
+    const long need = (long)cin * hidden + 9L * hidden + (long)hidden * c_out;
+    const long ld = ld_arg > 0 ? (long)ld_arg : (need + 3) & ~3L;
+    if (strict && ld < need) return HS_ERR_BAD_ARG;
+    if (strict && residual && cin != c_out) return HS_ERR_BAD_ARG;
+    int f[4] = {0, 0, 0, 0};
+    auto answer = [&](int route) { if (form) for (int i = 0; i < 4; ++i) form[i] = f[i]; return route; };
+    const float* bank = bank_aligned16 ? dummy : dummy + 1;
+    float* const query = nullptr;                                // y == nullptr: the launchers answer without launching
+    // try_launch_irc looks at y's alignment only when it is given a y: the query states that fact as y_aligned16 instead
     const bool fused_form = in->coords && si.prev_mode == HS_PREV_BILINEAR && !residual;
-    if (fused_form && ir_auto_prefers_f32(math, in->c_skip, (long)in->batch * fh * fw, in->H / fh, in->W / fw) &&
-        try_launch_ir_fused(0, si, fh, fw, &dummy, ld, cin, in->c_skip, hidden, c_out, &dummy, &dummy, &dummy, &dummy,
-                            &dummy, &dummy, nullptr, nullptr) == HS_OK)
-        return HS_IR_ROUTE_F32_MFMA;
-    if (fused_form && math != HS_IR_MATH_F32 &&
-        try_launch_irc(si, fh, fw, &dummy, ld, hidden, c_out, &dummy, &dummy, &dummy, &dummy, &dummy, &dummy, nullptr, nullptr) == HS_OK)
-        return HS_IR_ROUTE_SPLIT_MFMA;
-    if (fused_form && try_launch_ir_fused(0, si, fh, fw, &dummy, ld, cin, in->c_skip, hidden, c_out, &dummy, &dummy, &dummy, &dummy,
-                                          &dummy, &dummy, nullptr, nullptr) == HS_OK)
-        return HS_IR_ROUTE_F32_MFMA;
-    return HS_IR_ROUTE_GENERIC;
+    // 0: covered; 1: not covered, the next form is asked; anything else: the launcher returns it (strict), or goes on (lenient)
+    auto fused = [&] { return try_launch_ir_fused(0, si, fh, fw, bank, ld, cin, in->c_skip, hidden, c_out, dummy, dummy, dummy, dummy, dummy, dummy,
+                                                  query, nullptr, f); };
+    if (fused_form && ir_auto_prefers_f32(math, in->c_skip, (long)in->batch * fh * fw, in->H / fh, in->W / fw)) {
+        const int r = fused();
+        if (r == HS_OK) return answer(HS_IR_ROUTE_F32_MFMA);
+        if (strict && r != 1) return r;
+    }
+    if (fused_form && math != HS_IR_MATH_F32 && y_aligned16) {
+        const int r = try_launch_irc(si, fh, fw, bank, ld, hidden, c_out, dummy, dummy, dummy, dummy, dummy, dummy, query, nullptr, f);
+        if (r == HS_OK) return answer(HS_IR_ROUTE_SPLIT_MFMA);
+        if (strict && r != 1) return r;
+    }
+    if (fused_form) {
+        const int r = fused();
+        if (r == HS_OK) return answer(HS_IR_ROUTE_F32_MFMA);
+        if (strict && r != 1) return r;
+    }
+    f[0] = ir_generic_form(fused_form, cin, in->c_skip, c_out);
+    if (f[0] < 0) return HS_ERR_UNSUPPORTED;
+    const int ph = in->H / fh, pw = in->W / fw;
+    const int TH = ph > IR_MAX_TILE ? IR_MAX_TILE : ph, TW = pw > IR_MAX_TILE ? IR_MAX_TILE : pw;
+    f[1] = (f[0] >> 8 & 255) != 0; f[2] = (ph + TH - 1) / TH; f[3] = (pw + TW - 1) / TW;
+    return answer(HS_IR_ROUTE_GENERIC);
+}
+
+extern "C" int hs_patch_ir_form(const hs_stage_input* in, int32_t fh, int32_t fw, int64_t ld, int32_t hidden, int32_t c_out,
+                                int32_t residual, int32_t math, int32_t bank_aligned16, int32_t y_aligned16, int32_t* form) {
+    return ir_form(in, fh, fw, ld, hidden, c_out, residual, math, bank_aligned16, y_aligned16, form, true);
+}
+
+// The route alone, for an aligned bank and output (the allocator's tensors are), with the answers it has always given: 'generic' wherever no
+// matrix-core form covers the call, whatever the launcher's own argument checks would say.
+extern "C" int hs_patch_ir_route(const hs_stage_input* in, int32_t fh, int32_t fw, int32_t hidden, int32_t c_out,
+                                 int32_t residual, int32_t math) {
+    if (!in) return HS_ERR_BAD_ARG;
+    const int r = ir_form(in, fh, fw, 0, hidden, c_out, residual, math, 1, 1, nullptr, false);
+    return r == HS_ERR_UNSUPPORTED ? HS_IR_ROUTE_GENERIC : r;
+}
+
+// Which form hs_patch_ir_v0_ws_fwd takes (host only): its checks and its dispatch, nothing launched.
+extern "C" int hs_patch_ir_v0_route(const hs_stage_input* in, int32_t fh, int32_t fw, int64_t ld_arg, int32_t hidden, int32_t c_out,
+                                    int32_t with_workspace, int32_t bank_aligned16, int32_t* form) {
+    if (!in) return HS_ERR_BAD_ARG;
+    hs_stage_input probe = *in;
+    alignas(16) static const float dummy[2] = {0.0f, 0.0f};
+    if (probe.c_skip > 0 && !probe.skip) probe.skip = dummy;
+    if (probe.c_prev > 0 && !probe.prev) probe.prev = dummy;
+    StageIn si;
+    const int st = make_stage(&probe, &si);
+    if (st != HS_OK) return st;
+    if (fh <= 0 || fw <= 0 || hidden <= 0 || c_out <= 0) return HS_ERR_BAD_ARG;
+    if (in->H % fh != 0 || in->W % fw != 0) return HS_ERR_NOT_DIVISIBLE;
+    if (in->H < 2 || in->W < 2) return HS_ERR_BAD_ARG;
+    const int cin = si.cin();
+    const long need = (long)cin * hidden + 9L * hidden + (long)hidden * c_out;
+    const long ld = ld_arg > 0 ? (long)ld_arg : (need + 3) & ~3L;
+    if (ld < need) return HS_ERR_BAD_ARG;
+    if (!(in->coords && si.prev_mode == HS_PREV_BILINEAR)) return HS_ERR_UNSUPPORTED;
+    int f[4] = {0, 0, 0, 0};
+    auto answer = [&](int route) { if (form) for (int i = 0; i < 4; ++i) form[i] = f[i]; return route; };
+    // with_workspace: the caller hands over hs_patch_ir_v0_workspace() bytes, 16-byte aligned (functional.patch_ir_v0 does)
+    if (with_workspace && ird_form(si, fh, fw, ld, cin, hidden, c_out, true, ird_workspace_bytes(si, fh, fw, cin, hidden, c_out),
+                                   bank_aligned16 != 0, f))
+        return answer(HS_IR_V0_ROUTE_D2);
+    const float* bank = bank_aligned16 ? dummy : dummy + 1;
+    const int r = try_launch_ir_fused(1, si, fh, fw, bank, ld, cin, in->c_skip, hidden, c_out, dummy, dummy, dummy, dummy, dummy, dummy,
+                                      nullptr, nullptr, f);
+    if (r == 1) return HS_ERR_UNSUPPORTED;
+    if (r != HS_OK) return r;
+    return answer(f[1] == 0 ? HS_IR_V0_ROUTE_PX : HS_IR_V0_ROUTE_FUSED);
 }
 
 // Op D, fused form only (the decoder's own shapes); anything else returns HS_ERR_UNSUPPORTED and the caller runs the

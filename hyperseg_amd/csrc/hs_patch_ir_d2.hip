@@ -359,17 +359,31 @@ size_t hs::ird_workspace_bytes(const StageIn& si, int fh, int fw, int cin, int h
     return (size_t)si.B * si.H * si.W * hidp * sizeof(float);
 }
 
+// Whether hs_patch_ir_v0_ws_fwd takes the two-launch form (try_launch_ird and hs_patch_ir_v0_route), and its instantiation:
+// form = {patch edge, RT (6 for hid > 48 or cin > 32, else 3), AL (4 | 2), 16-channel hidden steps of the second launch}.
+bool hs::ird_form(const StageIn& si, int fh, int fw, long ld, int cin, int hid, int c_out, bool with_workspace, size_t workspace_bytes,
+                  bool aligned16, int form[4]) {
+    form[0] = form[1] = form[2] = form[3] = 0;
+    const size_t need = ird_workspace_bytes(si, fh, fw, cin, hid, c_out);
+    if (need == 0 || !with_workspace || workspace_bytes < need) return false;
+    if ((ld & 3) || !aligned16) return false;
+    form[0] = si.W / fw;
+    form[1] = hid > 48 || cin > 32 ? 6 : 3;
+    form[2] = (cin & 3) == 0 ? 4 : 2;                                   // cin even (hid = expand * cin is a multiple of 4)
+    form[3] = ((hid + 15) & ~15) / 16;
+    return true;
+}
+
 int hs::try_launch_ird(const StageIn& si, int fh, int fw, const float* bank, long ld, int cin, int hid, int c_out,
                        const float* s1, const float* b1, const float* s2, const float* b2, const float* s3, const float* b3,
                        float* workspace, size_t workspace_bytes, float* y, hipStream_t stream) {
-    const size_t need = ird_workspace_bytes(si, fh, fw, cin, hid, c_out);
-    if (need == 0 || !workspace || workspace_bytes < need) return 1;
-    if ((ld & 3) || (((size_t)bank) & 15) || (((size_t)workspace) & 15)) return 1;
-    const int pw = si.W / fw, hidp = (hid + 15) & ~15;
+    int form[4];
+    if (!ird_form(si, fh, fw, ld, cin, hid, c_out, workspace != nullptr, workspace_bytes, ((((size_t)bank) | ((size_t)workspace)) & 15) == 0, form)) return 1;
+    const int pw = form[0], hidp = (hid + 15) & ~15;
     IrdArgs a{si, bank, ld, fh, fw, cin, hid, c_out, hidp, s1, b1, s2, b2, s3, b3, workspace, y};
     const dim3 grid((fw + 3) / 4, fh, si.B), block(256);
-    const int al = (cin & 3) == 0 ? 4 : 2;                              // cin even (hid = expand * cin is a multiple of 4)
-    const bool big = hid > 48 || cin > 32;                              // (RT, KQ) = (6, 3), else (3, 2)
+    const int al = form[2];
+    const bool big = form[1] == 6;                                      // (RT, KQ) = (6, 3), else (3, 2)
     // beyond 64 KiB of dynamic LDS (8 x 8 patches with wide inputs; pass 2 at 8 x 8: 69 KB) the kernel's ceiling is raised once per device
 #define HS_D2A(PWV, RTV, KQV, ALV) do { \
         const size_t lds1 = ((size_t)IrdP1<PWV, KQV>::XL + (size_t)si.c_prev * IrdP1<PWV, KQV>::WP) * sizeof(float); \
@@ -394,7 +408,7 @@ int hs::try_launch_ird(const StageIn& si, int fh, int fw, const float* bank, lon
             if (e != HS_OK) return e; \
         } \
         hipLaunchKernelGGL((ird_dw_pw3_kernel<PWV, KQV>), grid, block, lds2, stream, a); } while (0)
-    const int kq = hidp / 16;
+    const int kq = form[3];
     if (pw == 4) { switch (kq) { case 1: HS_D2C(4, 1); break; case 2: HS_D2C(4, 2); break; case 3: HS_D2C(4, 3); break; case 4: HS_D2C(4, 4); break;
                                  case 5: HS_D2C(4, 5); break; default: HS_D2C(4, 6); break; } }
     else { switch (kq) { case 1: HS_D2C(8, 1); break; case 2: HS_D2C(8, 2); break; case 3: HS_D2C(8, 3); break; case 4: HS_D2C(8, 4); break;

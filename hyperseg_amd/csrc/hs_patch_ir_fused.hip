@@ -483,7 +483,7 @@ void patch_ir_fused_kernel(IrFusedArgs a) {
 }
 
 template <int CIN, int CSKIP, int COUT, int REG, int MODE, int PWR>
-static int launch_irf(IrFusedArgs& a, hipStream_t stream) {
+static int launch_irf(IrFusedArgs& a, hipStream_t stream, int* form) {
     using G = IrfGeom<REG>;
     if (a.in.H % REG != 0 || a.in.W % REG != 0) return 1;      // regions must tile the level
     a.regs_y = a.in.H / REG; a.regs_x = a.in.W / REG;
@@ -495,6 +495,7 @@ static int launch_irf(IrFusedArgs& a, hipStream_t stream) {
     // operand rows past the last hidden channel / k past cin are read unmasked: they must stay inside the patch's bank
     if (16 * CIN + 4 > a.hid * (9 + COUT) || 144 > a.hid * COUT) return 1;
     if (lds > 160 * 1024) return HS_ERR_LDS;
+    if (form) { form[0] = REG; form[1] = PWR; form[2] = HS_IR_GENERIC(CIN, CSKIP, COUT); form[3] = a.in.B * a.regs_y * a.regs_x; }   // hs_patch_ir_form
     if (a.y == nullptr) return HS_OK;                         // route query (hs_patch_ir_route): the shape is covered, nothing is launched
     if (lds > 64 * 1024) {
         static std::atomic<unsigned long long> done{0};       // one per instantiation
@@ -511,7 +512,7 @@ static int launch_irf(IrFusedArgs& a, hipStream_t stream) {
 // instantiation matches (the caller then uses the generic kernels), otherwise the launch status.
 int try_launch_ir_fused(int mode, const StageIn& in, int fh, int fw, const float* bank, long ld, int cin, int c_skip,
                         int hid, int c_out, const float* s1, const float* b1, const float* s2, const float* b2,
-                        const float* s3, const float* b3, float* y, hipStream_t stream) {
+                        const float* s3, const float* b3, float* y, hipStream_t stream, int* form) {
     IrFusedArgs a;
     a.in = in; a.fh = fh; a.fw = fw; a.ph = in.H / fh; a.pw = in.W / fw;
     a.bank = bank; a.ld = ld; a.hid = hid;
@@ -524,11 +525,11 @@ int try_launch_ir_fused(int mode, const StageIn& in, int fh, int fw, const float
     if (a.ph != a.pw) return 1;
     const int p = a.ph;
     if (mode == 1) {   // the narrow Op D levels: one lane per pixel (hs_patch_ir_px.hip)
-        const int e = try_launch_ir_px(a, cin, c_skip, c_out, stream);
+        const int e = try_launch_ir_px(a, cin, c_skip, c_out, stream, form);
         if (e != 1) return e;
     }
 #define HS_IRF_CASE(CI, CS, CO, REG, MODE, PWR) \
-    if (cin == CI && c_skip == CS && c_out == CO) return launch_irf<CI, CS, CO, REG, MODE, PWR>(a, stream);
+    if (cin == CI && c_skip == CS && c_out == CO) return launch_irf<CI, CS, CO, REG, MODE, PWR>(a, stream, form);
     if (mode == 0) {
         if (p % 16 == 0) {
             HS_IRF_CASE(34, 16, 19, 16, 0, 16)   // HyperSeg-M level 4 (Cityscapes, 19 classes)

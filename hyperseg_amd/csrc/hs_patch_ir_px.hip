@@ -388,10 +388,13 @@ void patch_ir_px_kernel(IrFusedArgs a) {
 }
 
 template <int CIN, int CSKIP, int COUT, int HID, int GC>
-static int launch_irp(IrFusedArgs& a, hipStream_t stream) {
+static int launch_irp(IrFusedArgs& a, hipStream_t stream, int* form) {
     using G = IrPxGeom<CIN, CSKIP, COUT, HID, GC>;
     if (a.hid != HID || a.in.H % 16 != 0 || a.in.W % 16 != 0) return 1;
     a.regs_y = a.in.H / 16; a.regs_x = a.in.W / 16;
+    // hs_patch_ir_v0_route: PWR = 0 marks this one-lane-per-pixel form
+    if (form) { form[0] = 16; form[1] = 0; form[2] = HS_IR_GENERIC(CIN, CSKIP, COUT); form[3] = a.in.B * a.regs_y * a.regs_x; }
+    if (a.y == nullptr) return HS_OK;                         // route query: the shape is covered, nothing is launched
     constexpr size_t lds = (size_t)G::FLOATS * sizeof(float);
     static_assert(lds <= 160 * 1024, "LDS");
     if (lds > 64 * 1024) {
@@ -405,12 +408,12 @@ static int launch_irp(IrFusedArgs& a, hipStream_t stream) {
 }
 
 // Op D levels with narrow channels and patch edges that are multiples of 16 pixels; 1 = no instantiation
-int try_launch_ir_px(IrFusedArgs& a, int cin, int c_skip, int c_out, hipStream_t stream) {
+int try_launch_ir_px(IrFusedArgs& a, int cin, int c_skip, int c_out, hipStream_t stream, int* form) {
     if (a.ph != a.pw || a.ph % 16 != 0) return 1;
 // GC = hidden groups per LDS chunk: sets the h1 footprint and with it the workgroups per CU (level 5: 3 chunks of 8 channels,
 // 35 KB -> 4 per CU; level 4: 4 chunks of 8, 40 KB -> 4 per CU; one chunk would be 53 / 71 KB -> 3 / 2 per CU)
 #define HS_IRP_CASE(CI, CS, CO, HID, GC) \
-    if (cin == CI && c_skip == CS && c_out == CO && a.hid == HID) return launch_irp<CI, CS, CO, HID, GC>(a, stream);
+    if (cin == CI && c_skip == CS && c_out == CO && a.hid == HID) return launch_irp<CI, CS, CO, HID, GC>(a, stream, form);
     HS_IRP_CASE(11, 3, 21, 22, 2)    // HyperSeg-L level 5 (PASCAL VOC: 21 classes)
     HS_IRP_CASE(16, 6, 6, 32, 2)     // HyperSeg-L level 4
 #undef HS_IRP_CASE

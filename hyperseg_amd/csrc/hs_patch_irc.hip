@@ -819,11 +819,12 @@ void patch_irc_kernel(IrcArgs a) {
 }
 
 template <int SPL, int PPL, int MT3, int RH_, int NW_ = 4>
-static int launch_irc(IrcArgs& a, hipStream_t stream) {
+static int launch_irc(IrcArgs& a, hipStream_t stream, int* form) {
     using G = IrcGeom<RH_, NW_>;
     const int cin = 2 + a.in.c_skip + a.in.c_prev;
     const IrcLds L = irc_lds_map(cin, a.hid, a.cout, MT3, G::H1_FLOATS, G::H2_HALFS);
     if (L.total > 160 * 1024) return 1;
+    if (form) { form[0] = G::RH; form[1] = G::NW; form[2] = (a.ph / G::RH) * (a.pw / G::RW); form[3] = SPL << 8 | PPL << 4 | MT3; }   // hs_patch_ir_form
     if (a.y == nullptr) return HS_OK;                         // route query (hs_patch_ir_route): covered, nothing is launched
     if (L.total > 64 * 1024) {
         static std::atomic<unsigned long long> done{0};
@@ -845,7 +846,7 @@ static int launch_irc(IrcArgs& a, hipStream_t stream) {
 // Returns 1 when the shape is outside what the kernel covers (the caller then takes the exact-f32 kernels).
 int try_launch_irc(const StageIn& in, int fh, int fw, const float* bank, long ld, int hid, int c_out,
                    const float* s1, const float* b1, const float* s2, const float* b2, const float* s3, const float* b3,
-                   float* y, hipStream_t stream) {
+                   float* y, hipStream_t stream, int* form) {
     IrcArgs a;
     a.in = in; a.fh = fh; a.fw = fw; a.ph = in.H / fh; a.pw = in.W / fw;
     a.bank = bank; a.ld = ld; a.hid = hid; a.cout = c_out;
@@ -873,8 +874,8 @@ int try_launch_irc(const StageIn& in, int fh, int fw, const float* bank, long ld
 #endif
 #define HS_IRC_CASE(SPL, PPL) \
     if (cs <= 4 * SPL && cp <= 4 * PPL) { \
-        if (tall) return c_out <= 16 ? launch_irc<SPL, PPL, 1, 16, HS_IRC_NW>(a, stream) : launch_irc<SPL, PPL, 2, 16, HS_IRC_NW>(a, stream); \
-        return c_out <= 16 ? launch_irc<SPL, PPL, 1, 8>(a, stream) : launch_irc<SPL, PPL, 2, 8>(a, stream); \
+        if (tall) return c_out <= 16 ? launch_irc<SPL, PPL, 1, 16, HS_IRC_NW>(a, stream, form) : launch_irc<SPL, PPL, 2, 16, HS_IRC_NW>(a, stream, form); \
+        return c_out <= 16 ? launch_irc<SPL, PPL, 1, 8>(a, stream, form) : launch_irc<SPL, PPL, 2, 8>(a, stream, form); \
     }
     HS_IRC_CASE(1, 2)      // <= 4 skip + <= 8 previous-level channels
     HS_IRC_CASE(1, 4)      // CamVid-S level 4 (4 + 16)

@@ -845,6 +845,88 @@ def patch_ir_route(shape, c_skip, c_prev, grid, hidden, c_out, math=None, residu
     return IR_ROUTES[r]
 
 
+def _stage_probe(shape, c_skip, c_prev, coords, prev_size=None):
+    """The pointer-free hs_stage_input of a route query: ``shape`` = (B, H, W); the previous level at half the resolution (bilinear)
+    unless ``prev_size`` says otherwise (equal to (H, W): taken as it is)."""
+    b, h, w = shape
+    si = _hip.StageInputC()
+    si.skip, si.prev, si.batch, si.H, si.W = None, None, b, h, w
+    hp, wp = prev_size if prev_size is not None else (h // 2, w // 2)
+    si.c_skip, si.c_prev, si.Hp, si.Wp = c_skip, c_prev, (hp if c_prev > 0 else 0), (wp if c_prev > 0 else 0)
+    si.coords = int(bool(coords))
+    si.prev_mode = 0 if c_prev == 0 else (_hip.PREV_SAME if (hp, wp) == (h, w) else _hip.PREV_BILINEAR)
+    return si
+
+
+def _ir_inst(word):
+    return f'{word >> 16}_{(word >> 8) & 255}_{word & 255}'
+
+
+def patch_ir_form(shape, c_skip, c_prev, grid, hidden, c_out, math=None, residual=False, coords=True, ld=0, bank_aligned=True,
+                  y_aligned=True):
+    """(route, form) of ``patch_ir`` (hs_patch_ir_form): the route of :func:`patch_ir_route` and the instantiation inside it --
+    'generic': 'exact_24_6_16_t1x1' | 'class_32_0_32_t1x2' ... (tiles per patch); 'split_mfma': 'rh16_nw4_r2_s1p4m1' (region rows, waves,
+    regions per patch, skip / previous-level quads and output tiles); 'f32_mfma': 'reg16_pwr16_34_16_19'.  None where the launcher
+    refuses the shape.  ``bank_aligned`` / ``y_aligned``: 16-byte alignment of the bank and of the output.  Host only."""
+    si = _stage_probe(shape, c_skip, c_prev, coords)
+    f = (C.c_int32 * 4)()
+    r = _route(_hip.lib.hs_patch_ir_form(C.byref(si), grid[0], grid[1], ld, hidden, c_out, int(bool(residual)), ir_math_code(math),
+                                         int(bool(bank_aligned)), int(bool(y_aligned)), f), 'hs_patch_ir_form')
+    if r is None:
+        return None
+    if r == 0:
+        form = f'{"exact" if f[1] else "class"}_{_ir_inst(f[0])}_t{f[2]}x{f[3]}'
+    elif r == 2:
+        form = f'rh{f[0]}_nw{f[1]}_r{f[2]}_s{f[3] >> 8}p{(f[3] >> 4) & 15}m{f[3] & 15}'
+    else:
+        form = f'reg{f[0]}_pwr{f[1]}_{_ir_inst(f[2])}'
+    return IR_ROUTES[r], form
+
+
+IR_V0_ROUTES = {0: 'd2', 1: 'px', 2: 'fused'}
+
+
+def patch_ir_v0_route(shape, c_skip, c_prev, grid, hidden, c_out, ld=0, workspace=None, bank_aligned=True):
+    """(route, form) of ``patch_ir_v0`` (hs_patch_ir_v0_route): ('d2', 'pw4_rt3_al4_kq2') -- two launches through the workspace --,
+    ('px', '16_6_6') or ('fused', 'reg8_pwr4_48_12_12'); None where ``patch_ir_v0`` returns None.  ``workspace``: whether the call
+    passes one (None: as ``patch_ir_v0`` does, D2_ROUTE).  Host only."""
+    si = _stage_probe(shape, c_skip, c_prev, True)
+    f = (C.c_int32 * 4)()
+    ws = D2_ROUTE if workspace is None else bool(workspace)
+    r = _route(_hip.lib.hs_patch_ir_v0_route(C.byref(si), grid[0], grid[1], ld, hidden, c_out, int(ws), int(bool(bank_aligned)), f),
+               'hs_patch_ir_v0_route')
+    if r is None:
+        return None
+    form = (f'pw{f[0]}_rt{f[1]}_al{f[2]}_kq{f[3]}' if r == 0 else _ir_inst(f[2]) if r == 1 else f'reg{f[0]}_pwr{f[1]}_{_ir_inst(f[2])}')
+    return IR_V0_ROUTES[r], form
+
+
+CONV_ROUTES = {0: 'plain_dw3', 1: 'plain_k1m', 2: 'k1m', 3: 'k1', 4: 'tiled'}
+
+
+def patch_conv_route(shape, c_skip, c_prev, grid, c_out, k=1, padding=0, padding_mode='reflect', groups=1, scale=False, shift=None,
+                     act=ACT_NONE, coords=False, prev_size=None, ld=0, bank_aligned=True, aligned8=True):
+    """(route, form) of ``patch_conv`` for a stage of ``shape`` = (B, H, W) (hs_patch_conv_route): ('plain_dw3', 'pairs' | 'single'),
+    ('plain_k1m', 'mt2_kq1_px2_affine'), ('k1m', 'rt3_al4_prev1'), ('k1', 'pwl2_split4') or ('tiled', 'th35_tw64_2x2').  ``scale`` /
+    ``shift`` / ``act``: the epilogue as given to ``patch_conv`` (truth values; shift defaults to scale).  ``ld``: the bank's row stride
+    (0: the packed row rounded up to 4).  ``bank_aligned`` / ``aligned8``: 16-byte alignment of the bank, 8-byte alignment of x and y.
+    Host only."""
+    si = _stage_probe(shape, c_skip, c_prev, coords, prev_size)
+    cin = 2 * bool(coords) + c_skip + c_prev
+    if ld == 0:
+        ld = _round_up(c_out * max(cin // groups, 1) * k * k, 4)
+    shift = scale if shift is None else shift
+    f = (C.c_int32 * 4)()
+    r = _route(_hip.lib.hs_patch_conv_route(C.byref(si), grid[0], grid[1], ld, c_out, k, padding, PAD_MODES[padding_mode], groups,
+                                            int(bool(scale)), int(bool(shift)), int(act), int(bool(bank_aligned)), int(bool(aligned8)), f),
+               'hs_patch_conv_route')
+    if r is None:
+        return None
+    form = [('pairs' if f[0] else 'single'), f'mt{f[0]}_kq{f[1]}_px{f[2]}' + ('_affine' if f[3] else ''), f'rt{f[0]}_al{f[1]}_prev{f[2]}',
+            f'pwl{f[0]}_split{f[1]}', f'th{f[0]}_tw{f[1]}_{f[2]}x{f[3]}'][r]
+    return CONV_ROUTES[r], form
+
+
 def ir_tile_map(reg, mode, pwr):
     """(n_pixel_tiles, array (n_tiles, 16, 3) of (u, v, live)) -- the fused inverted-residual kernel's tile map
     (host-side introspection, no GPU needed)."""

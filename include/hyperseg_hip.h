@@ -287,6 +287,53 @@ typedef enum { HS_IR_ROUTE_GENERIC = 0, HS_IR_ROUTE_F32_MFMA = 1, HS_IR_ROUTE_SP
 int hs_patch_ir_route(const hs_stage_input* in, int32_t fh, int32_t fw, int32_t hidden, int32_t c_out,
                       int32_t residual, int32_t math);
 
+/* hs_patch_ir_route plus the FORM inside the route (host only, as above; form: 4 words, may be null).  bank_aligned16 / y_aligned16:
+ * the facts the launcher reads off the bank and output pointers (the split kernel's bank DMA and 16-byte stores; a bank view at a
+ * 4-byte offset takes the direct kernels).  ld: the bank's row stride, 0 = the packed row rounded up to 4.
+ *   HS_IR_ROUTE_GENERIC     form[0] = HS_IR_GENERIC(cin, c_skip, c_out) of the instantiation -- the five exact ones (24, 6, 16),
+ *                           (34, 16, 19), (14, 4, 8), (26, 16, 19), (22, 4, 12), or a width class (16, 0, 16), (32, 0, 32), (64, 0, 32),
+ *                           (128, 0, 64); form[1] = 1 for an exact one; form[2], form[3] = tiles_y, tiles_x per patch
+ *   HS_IR_ROUTE_SPLIT_MFMA  form[0] = RH (8 | 16 region rows), form[1] = NW (waves per region), form[2] = regions per patch,
+ *                           form[3] = SPL << 8 | PPL << 4 | MT3 (quads of skip / previous-level channels, 16-channel output tiles)
+ *   HS_IR_ROUTE_F32_MFMA    form[0] = REG (region edge 8 | 16), form[1] = PWR (patch edge inside the region),
+ *                           form[2] = HS_IR_GENERIC(cin, c_skip, c_out) of the instantiation, form[3] = regions in the launch
+ * A negative answer is the launcher's error code (HS_ERR_UNSUPPORTED beyond the widest class). */
+#define HS_IR_GENERIC(cin, c_skip, c_out) (((cin) << 16) | ((c_skip) << 8) | (c_out))
+int hs_patch_ir_form(const hs_stage_input* in, int32_t fh, int32_t fw, int64_t ld, int32_t hidden, int32_t c_out, int32_t residual,
+                     int32_t math, int32_t bank_aligned16, int32_t y_aligned16, int32_t* form);
+
+/* Which form hs_patch_ir_v0_ws_fwd takes (host only; form: 4 words, may be null), or HS_ERR_UNSUPPORTED where it answers that:
+ *   HS_IR_V0_ROUTE_D2     two launches through the workspace (4 x 4 / 8 x 8 patches; with_workspace: the caller passes one of
+ *                         hs_patch_ir_v0_workspace() bytes, 16-byte aligned): form[0] = patch edge, form[1] = RT (3 | 6), form[2] = AL
+ *                         (4 | 2), form[3] = 16-channel hidden steps of the second launch
+ *   HS_IR_V0_ROUTE_PX     one launch, one lane per pixel (hs_patch_ir_px.hip): form[0] = 16, form[2] = HS_IR_GENERIC(...)
+ *   HS_IR_V0_ROUTE_FUSED  one launch on the f32 matrix cores (hs_patch_ir_fused.hip): form as for HS_IR_ROUTE_F32_MFMA */
+#define HS_IR_V0_ROUTE_D2 0
+#define HS_IR_V0_ROUTE_PX 1
+#define HS_IR_V0_ROUTE_FUSED 2
+int hs_patch_ir_v0_route(const hs_stage_input* in, int32_t fh, int32_t fw, int64_t ld, int32_t hidden, int32_t c_out,
+                         int32_t with_workspace, int32_t bank_aligned16, int32_t* form);
+
+/* Which of its five forms hs_patch_conv_fwd takes (host only; pointers in `in` may be null; form: 4 words, may be null).  The forms are
+ * tried in this order; every predicate is the one the launcher dispatches on.  aligned16: the bank is 16-byte aligned; aligned8: x and y
+ * are 8-byte aligned (plain inputs: the pair forms).  with_scale / with_shift / act: the epilogue's fields.
+ *   HS_CONV_ROUTE_PLAIN_DW3  plain input, depthwise 3 x 3 with zero padding, no epilogue: image-level kernel; form[0] = 1 for the
+ *                            two-pixels-per-lane form (even patch and image widths, aligned8)
+ *   HS_CONV_ROUTE_PLAIN_K1M  plain input, k = 1, groups = 1, patches >= 64 pixels, c_out <= 64, c_in <= 64 (not both > 48): f32 matrix
+ *                            cores; form = {MT, KQ (16-channel tiles of c_out / c_in), pixels per lane (1 | 2), affine}
+ *   HS_CONV_ROUTE_K1M        k = 1, groups = 1, >= 1024 patches of 2 x 2 pixels, even 4 <= cin <= 144, c_out <= 96: the weight stream
+ *                            (hs_patch_conv_k1m.hip); form = {RT (3 | 6), AL (4 | 2), PREV (0 | 1)}
+ *   HS_CONV_ROUTE_K1         k = 1: one workgroup per patch; form = {PWL (log2 of the patch edge for 1, 2, 4, 8; -1 otherwise), split}
+ *   HS_CONV_ROUTE_TILED      the generic kernel; form = {TH, TW, tiles_y, tiles_x} */
+#define HS_CONV_ROUTE_PLAIN_DW3 0
+#define HS_CONV_ROUTE_PLAIN_K1M 1
+#define HS_CONV_ROUTE_K1M 2
+#define HS_CONV_ROUTE_K1 3
+#define HS_CONV_ROUTE_TILED 4
+int hs_patch_conv_route(const hs_stage_input* in, int32_t fh, int32_t fw, int64_t ld, int32_t c_out, int32_t k, int32_t pad,
+                        int32_t pad_mode, int32_t groups, int32_t with_scale, int32_t with_shift, int32_t act, int32_t aligned16,
+                        int32_t aligned8, int32_t* form);
+
 /* Introspection for the tests (host only, no GPU): the matrix-core tile map of the fused inverted-residual kernel for a
  * region edge `reg` (8|16), mode (0 = Op C, 1 = Op D) and patch edge inside the region `pwr`.  out[(t*16+n)*3 + {0,1,2}]
  * = halo coordinates (u, v) and liveness of column n of pw1 tile t (csrc/hs_ir_tiles.h). */
