@@ -18,6 +18,9 @@ def __getattr__(name):
     if name == 'Overlay':
         from .utils.inference import Overlay
         return Overlay
+    if name == 'Confidence':
+        from .utils.confidence import Confidence
+        return Confidence
     if name == 'LabelCodec':
         from .utils.labels import LabelCodec
         return LabelCodec

@@ -11,7 +11,7 @@ Reproduces the reference's protocol on synthetic frames (no dataset, checkpoint 
 ``torch.cuda.synchronize()`` is guarded so that the plumbing also runs on a CPU-only box (with a CPU-capable model).
 
     python -m hyperseg_amd.fps --config hyperseg-m --iterations 200 [--prepare] [--graph] [--remove-bn] [--batch-size 1]
-                               [--uint8 [--layout hwc|chw] [--overlay] [--resize H W [--camera-size H W]]] [--label-size H W] [--fused-metrics]
+                               [--confidence] [--uint8 [--layout hwc|chw] [--overlay] [--resize H W [--camera-size H W]]] [--label-size H W] [--fused-metrics]
 
 ``--label-size H W`` draws the targets at that size instead of the frame's: the reference's Cityscapes test configs resize the image
 only, so every frame's logits are resized to the label before they are counted (test.py:167-168) -- done here as well, by the
@@ -174,7 +174,7 @@ def _sync(device):
 
 
 @torch.no_grad()
-def measure_fps(model, batches, device, num_classes, passes=2, fused_metrics=False, overlay=False, label_codec=None):
+def measure_fps(model, batches, device, num_classes, passes=2, fused_metrics=False, overlay=False, label_codec=None, confidence=False):
     """``batches``: list of (input, target) host tensors (inputs pinned when CUDA is used).  Runs ``passes`` passes over
     them and reports the LAST one (the reference's warm-up + timed pass).  Returns a dict.  ``fused_metrics``: where the
     model has ``evaluate`` (a HyperGen, a GraphedModel) the frame is scored by the forward's last launch -- INSIDE the timed
@@ -183,11 +183,15 @@ def measure_fps(model, batches, device, num_classes, passes=2, fused_metrics=Fal
     timed region; the masks are scored outside it as the reference's protocol does.  Targets of another size than the frame's are
     scored at their own resolution: the logits are resized to the label before the arg-max (test.py:167-168), outside the timed region
     on the unfused route; a model that returns masks hands them out at the label's size where its ``segment`` takes ``size=``.
+    ``confidence``: every frame is served by ``model.confidence`` (masks + the confidence map in ``confidence_style``) instead of the
+    forward, inside the timed region; the masks are scored outside it.
     ``label_codec`` (a ``LabelCodec``; the model's ``label_codec``): the targets are RAW dataset labels.  They are encoded where they are
     scored: by ``model.evaluate`` inside the timed region with ``fused_metrics``, outside it otherwise."""
     result = {}
     if overlay and fused_metrics:
         raise ValueError('overlay and fused_metrics both ride on the final upsample launch: one of them per run')
+    if confidence and (overlay or fused_metrics):
+        raise ValueError('confidence, overlay and fused_metrics all ride on the final upsample launch: one of them per run')
     fused = bool(fused_metrics) and hasattr(model, 'evaluate')
     owns = fused and getattr(model, 'owns_confusion', False)        # GraphedModel: the matrix lives with the graph
     for p in range(passes):
@@ -209,6 +213,8 @@ def measure_fps(model, batches, device, num_classes, passes=2, fused_metrics=Fal
                 pred = model.evaluate(x, target) if owns else model.evaluate(x, target, conf)
             elif overlay:
                 pred = model.overlay(x)[0]
+            elif confidence:
+                pred = model.confidence(x)[0]
             else:
                 pred = model(x)
             _sync(device)
@@ -334,6 +340,9 @@ def main(argv=None):
     ap.add_argument('--overlay', action='store_true',
                     help="serve the display as well (model.overlay): the class map coloured with a seeded synthetic palette and alpha-blended "
                          "over the uint8 frame by the forward's last launch, inside the timed region; needs --uint8")
+    ap.add_argument('--confidence', action='store_true',
+                    help="serve the confidence map as well (model.confidence): beside the masks, every pixel's soft-max probability of its "
+                         "class as uint8, from the forward's last launch, inside the timed region")
     ap.add_argument('--label-size', nargs=2, type=int, metavar=('H', 'W'), default=None,
                     help="draw the targets at this size instead of the frame's: the logits are resized to it before they are counted "
                          "(test.py:167-168; the reference's Cityscapes test configs: 1024 2048)")
@@ -362,6 +371,10 @@ def main(argv=None):
         raise SystemExit('--overlay blends over the uint8 frames: it needs --uint8')
     if args.overlay and args.fused_metrics:
         raise SystemExit('--overlay and --fused-metrics both ride on the final upsample launch: one of them per run')
+    if args.confidence and (args.overlay or args.fused_metrics):
+        raise SystemExit('--confidence, --overlay and --fused-metrics all ride on the final upsample launch: one of them per run')
+    if args.confidence and args.gpus and len(args.gpus) > 1:
+        raise SystemExit('--confidence serves one device: with several --gpus run one process per GPU')
     if args.label_size is not None and min(args.label_size) <= 0:
         raise SystemExit('--label-size H W: two positive integers')
     if args.resize is not None and not args.uint8:
@@ -400,6 +413,10 @@ def main(argv=None):
         palette = torch.randint(0, 256, (spec['num_classes'], 3), generator=torch.Generator().manual_seed(0))
         model.overlay_style = Overlay(palette, layout=args.layout)
         model.inference_hflip = False        # inert for tensor inputs, but overlay() takes its segment() + blend route while it is set
+    if args.confidence:
+        from .utils.confidence import Confidence
+        model.confidence_style = Confidence()
+        model.inference_hflip = False        # inert for tensor inputs, but confidence() takes its composed route while it is set
     codec = None if args.raw_labels is None else random_codec(args.raw_labels, spec['num_classes'])
     if codec is not None:
         model.label_codec = codec
@@ -415,7 +432,8 @@ def main(argv=None):
     uniq = synthetic_batches(min(args.distinct, args.iterations), bs, frame_size, spec['num_classes'], device,
                              uint8=args.uint8, layout=args.layout, label_size=label_size, label_codec=codec)
     batches = [uniq[i % len(uniq)] for i in range(args.iterations)]
-    res = measure_fps(model, batches, device, spec['num_classes'], fused_metrics=args.fused_metrics, overlay=args.overlay, label_codec=codec)
+    res = measure_fps(model, batches, device, spec['num_classes'], fused_metrics=args.fused_metrics, overlay=args.overlay, label_codec=codec,
+                      confidence=args.confidence)
     frame = uniq[0][0]
     res.update(input_dtype=str(frame.dtype).replace('torch.', ''), input_bytes_per_frame=frame[0].numel() * frame.element_size())
     res.update(config=args.config, batch_size=bs, size=list(spec['size']), device=str(device), remove_bn=args.remove_bn,
@@ -431,6 +449,8 @@ def main(argv=None):
         res.update(raw_labels=args.raw_labels, protocol=res['protocol'] + f' + raw {args.raw_labels} labels encoded on the device where they are scored')
     if args.overlay:
         res.update(overlay=True, protocol=res['protocol'] + " + uint8 overlay blended inside the timed region by the forward's last launch")
+    if args.confidence:
+        res.update(confidence=True, protocol=res['protocol'] + " + uint8 confidence map made inside the timed region by the forward's last launch")
     print(json.dumps(res))
     return res
 

@@ -1758,6 +1758,70 @@ def upsample_overlay(x, size, frames, style, out=None):
     return mask, out
 
 
+def _confidence_operands(x, size, dtype, threshold, fill, out, name='x'):
+    """What the three confidence wrappers share: checks (ValueError, before any launch), the uint8 masks and the confidence tensor at
+    ``(B, *size)``.  Returns ``(b, c, hi, wi, tail, mask, conf)``: an entry is called with its shape arguments followed by ``*tail``."""
+    from .utils.confidence import CONF_DTYPES, check_args
+    dtype, threshold, fill = check_args(dtype, threshold, fill)
+    b, c, hi, wi = _logits_shape(x)
+    if not x.is_cuda:
+        raise ValueError(f'{name} is on {x.device}: the confidence kernels run on the GPU (utils.confidence.confidence_cpu takes CPU tensors)')
+    if x.dtype != torch.float32 or not x.is_contiguous():
+        raise ValueError(f'{name} must be contiguous float32 (B, C, H, W) logits, got {x.dtype}')
+    if c > 256:
+        raise ValueError('more than 256 logit channels: the masks are uint8')
+    shape = (b,) + tuple(size)
+    if out is None:
+        conf = torch.empty(shape, device=x.device, dtype=dtype)
+    else:
+        if not isinstance(out, torch.Tensor) or out.dtype != dtype or tuple(out.shape) != shape or out.device != x.device or not out.is_contiguous():
+            raise ValueError(f'out must be a contiguous {dtype} tensor of shape {shape} on {x.device}, got '
+                             f'{getattr(out, "dtype", type(out))} {tuple(getattr(out, "shape", ()))} on {getattr(out, "device", None)}')
+        conf = out
+    mask = torch.empty(shape, device=x.device, dtype=torch.uint8)
+    tail = (CONF_DTYPES[dtype], 0.0 if threshold is None else threshold, fill, mask.data_ptr(), conf.data_ptr(), _hip.stream_ptr())
+    return b, c, hi, wi, tail, mask, conf
+
+
+@_on_operand_device
+def confidence(logits, dtype=torch.uint8, threshold=None, fill=255, out=None):
+    """``(masks, conf)`` of finished fp32 logits (B, C, H, W), one launch (hs_confidence_fwd): the uint8 masks ``logits.argmax(1)`` and
+    the soft-max probability of that class, ``softmax(logits, 1).max(1)``, taken in fp32 by the recurrence of csrc/hs_confidence.h --
+    ``dtype`` float32, or uint8 as ``uint8(conf * 255 + 0.5)``.  ``threshold``: a pixel whose fp32 confidence is ``< threshold`` gets
+    ``fill`` in the masks (pseudo-labels with an ignore value); the confidence is not changed by it.  ``out``: a contiguous ``dtype``
+    (B, H, W) tensor for the confidence.  The composed route's kernel: the fused entries below give the same bits.  Capturable."""
+    b, c, h, w, tail, mask, conf = _confidence_operands(logits, tuple(_logits_shape(logits)[2:]), dtype, threshold, fill, out, name='logits')
+    _hip.run.hs_confidence_fwd(logits.data_ptr(), b, c, h, w, *tail)
+    return mask, conf
+
+
+@_on_operand_device
+def upsample_confidence(x, size, dtype=torch.uint8, threshold=None, fill=255, out=None):
+    """``upsample_argmax(x, size)`` with the confidence as the same launch's epilogue (hs_upsample_confidence_fwd).  Returns ``(masks,
+    conf)``: the uint8 masks, bit-identical to ``upsample_argmax``'s (before the threshold), and the confidence, bit-identical to
+    ``confidence(upsample_bilinear(x, size))``'s; the resized logits never exist in memory.  ``dtype``, ``threshold``, ``fill``, ``out``:
+    as :func:`confidence`'s.  Capturable."""
+    ho, wo = _size2(size, 'size')
+    b, c, hi, wi, tail, mask, conf = _confidence_operands(x, (ho, wo), dtype, threshold, fill, out)
+    _hip.run.hs_upsample_confidence_fwd(x.data_ptr(), b, c, hi, wi, ho, wo, *tail)
+    return mask, conf
+
+
+@_on_operand_device
+def upsample2_confidence(x, mid_size, size, dtype=torch.uint8, threshold=None, fill=255, out=None):
+    """``upsample_confidence`` over two composed resizes (hs_upsample2_confidence_fwd): ``x`` resized to ``mid_size`` and from there to
+    ``size``, one launch; neither resized tensor exists in memory.  Masks bit-identical to ``upsample2_argmax``'s, the confidence to
+    ``confidence(upsample_bilinear(upsample_bilinear(x, mid_size), size))``'s; ``upsample_confidence`` where one of the stages is the
+    identity.  Capturable."""
+    _, _, hi, wi = _logits_shape(x)
+    (hm, wm), (ho, wo) = _size2(mid_size, 'mid_size'), _size2(size, 'size')
+    if (ho, wo) == (hm, wm) or (hi, wi) == (hm, wm):
+        return upsample_confidence(x, (ho, wo), dtype=dtype, threshold=threshold, fill=fill, out=out)
+    b, c, hi, wi, tail, mask, conf = _confidence_operands(x, (ho, wo), dtype, threshold, fill, out)
+    _hip.run.hs_upsample2_confidence_fwd(x.data_ptr(), b, c, hi, wi, hm, wm, ho, wo, *tail)
+    return mask, conf
+
+
 # ------------------------------------------------------------------------------------------
 # uint8 frames and their labels: resize, colour jitter, blur, rotate (csrc/hs_resample.hip, hs_jitter.hip, hs_blur.hip, hs_rotate.hip).  Every wrapper
 # checks its operands with the helpers below -- each raises ValueError, before any launch or host-to-device copy -- allocates, calls

@@ -86,9 +86,12 @@ class Epilogue:
     (C,) on the device, finite and >= 0 -- the losses are then the weighted ones.  A scored forward takes its output size from its target.
     ``loss_at_label`` (with ``ignore_index``; off by default): a target of another size than the frame's is then taken at ITS resolution by
     the validation step too, as train.py:119-120 does -- losses, masks and counts at the label's size from the one launch; without it such
-    a target is rejected where a loss is asked for."""
+    a target is rejected where a loss is asked for.  ``confidence`` (a ``utils.confidence.Confidence``): the launch also makes every
+    pixel's confidence -- the soft-max probability of its class -- in the style's dtype, and fills the masks below the style's threshold;
+    it goes with ``out_size``, not with ``score`` or ``blend``."""
     score: Optional[Score] = None
     blend: Optional[Blend] = None
+    confidence: Optional[object] = None
     out_size: Optional[tuple] = None
     ignore_index: Optional[int] = None
     weight: Optional[object] = None
@@ -103,12 +106,15 @@ class Epilogue:
             raise ValueError('loss_at_label places the loss: it rides on a scored epilogue with an ignore_index')
         if self.score is not None and self.blend is not None:
             raise ValueError('score and blend both ride on the final upsample launch: one of them per forward for now')
+        if self.confidence is not None and (self.score is not None or self.blend is not None):
+            raise ValueError('confidence and score / blend all ride on the final upsample launch: one of them per forward for now')
         if self.out_size is not None:
             self.out_size = tuple(self.out_size)
 
     def apply(self, p, size):
         """The last level's output ``p`` -> the masks at ``size`` (the frame's), straight from the one launch; ``(masks, per_pixel)`` of a
-        validation step (per_pixel: f32 (B, H, W), what ``BootstrappedCrossEntropyLoss`` ranks), ``(masks, overlay)`` of a blend.  A
+        validation step (per_pixel: f32 (B, H, W), what ``BootstrappedCrossEntropyLoss`` ranks), ``(masks, overlay)`` of a blend, ``(masks, conf)`` of a
+        confidence epilogue (at ``out_size`` where one is given, both resizes composed in the one launch).  A
         score's target of another size than ``size`` is scored at ITS resolution, as test.py:167-168 does: the logits at ``size`` are
         resized once more, to the target's size, before the arg-max -- both resizes composed in the one launch, a single one where ``p``
         is at ``size`` already; the masks are then at the target's size.  A validation step takes such a target only with
@@ -141,6 +147,11 @@ class Epilogue:
                 raise ValueError('the overlay is blended over the frames, at their size: another out_size does not go with a blend')
             frames, style, out = self.blend
             return HF.upsample_overlay(p, size, frames, style, out=out)
+        if self.confidence is not None:
+            style = self.confidence
+            if not resized:
+                return HF.upsample_confidence(p, size, style.dtype, style.threshold, style.fill)
+            return HF.upsample2_confidence(p, size, self.out_size, style.dtype, style.threshold, style.fill)
         if not resized:
             return HF.upsample_argmax(p, size)
         return HF.upsample2_argmax(p, size, self.out_size)
@@ -177,6 +188,8 @@ class HyperGenBase(EpochOnModeSwitch, nn.Module):
     input_norm = None
     # a utils.inference.Overlay: what ``overlay()`` colours and blends with.  A plain attribute as well
     overlay_style = None
+    # a utils.confidence.Confidence: the dtype, threshold and fill byte ``confidence()`` serves with.  A plain attribute as well
+    confidence_style = None
     # a utils.inference.FrameResize: uint8 frames of another size (camera frames) are resized to it on the device first.  A plain attribute
     input_resize = None
     # a utils.labels.LabelCodec: ``evaluate`` and ``validate`` then take RAW dataset labels -- ids, or a colour image -- and encode them
@@ -458,6 +471,34 @@ class HyperGenBase(EpochOnModeSwitch, nn.Module):
             out.copy_(blended)
             blended = out
         return masks, blended
+
+    @torch.no_grad()
+    def confidence(self, x, size=None, style=None):
+        """``segment(x, size)`` plus how sure the model is: returns ``(masks, conf)`` -- the uint8 masks and, per pixel, the soft-max
+        probability of its class, ``softmax(logits, 1).max(1)`` taken in fp32 (csrc/hs_confidence.h), as ``style.dtype`` (``style``: a
+        ``utils.confidence.Confidence``, default ``self.confidence_style``, else ``Confidence()``: uint8, no threshold); with a
+        threshold the masks carry the style's fill byte where the confidence is below it.  A single CUDA tensor in eval mode without
+        h-flip inference gets both from the forward's last launch (``HF.upsample_confidence``; with ``size=`` ``HF.upsample2_confidence``)
+        -- no further launch, no read of the device, the full-resolution logits never written; uint8 frames, ``input_resize`` and
+        ``size=`` as in ``segment()``.  Everything else -- list inputs, h-flip inference, training mode, CPU -- takes the logits (resized
+        to ``size``) and ``HF.confidence``, on the CPU ``utils.confidence.confidence_cpu``.  Same masks on every route; on the device the
+        same confidence bits from the same decoder input."""
+        from ..utils.confidence import Confidence
+        style = self.confidence_style if style is None else style
+        style = Confidence() if style is None else style
+        if not isinstance(style, Confidence):
+            raise TypeError('confidence() takes a hyperseg_amd.Confidence as its style')
+        x = self.resized(x)
+        first = x if isinstance(x, torch.Tensor) else x[0]
+        frame = self.frame_size(first, isinstance(x, torch.Tensor))
+        size = frame if size is None else tuple(int(s) for s in size)
+        fused = isinstance(x, torch.Tensor) and x.is_cuda and not self.training and not self.inference_hflip
+        if fused:
+            got = self.process_single_tensor(x, epilogue=Epilogue(confidence=style, out_size=None if size == frame else size))
+            if isinstance(got, tuple):
+                return got
+            raise RuntimeError('the decoder returned logits where its epilogue was asked for: no confidence was made')
+        return style.of_logits(self._logits_at(x, size))
 
     def gather_results(self, x, y=None):
         assert x is not None

@@ -1125,3 +1125,32 @@ class GraphedModel(nn.Module):
 
             entry = self._capture(key, inputs, device, run=run)
         return self._replay(entry, inputs, device)
+
+    @torch.no_grad()
+    def confidence(self, x, size=None):
+        """One replay per frame that also says how sure the model is: returns ``(masks, conf)`` as ``model.confidence`` does, in
+        ``model.confidence_style`` (none set: ``Confidence()``, uint8 without a threshold).  ``x`` may live on the device or in (pinned)
+        host memory and is staged into the graph's static buffer.  The graph is the forward's chain of launches with the last one replaced
+        by ``functional.upsample_confidence`` (``size=``: ``functional.upsample2_confidence``), keyed like the ``forward`` graphs plus the
+        style and the size.  Both returned tensors are graph-owned: valid until the next ``confidence`` of the same shape, which overwrites
+        them (``clone_output=True`` hands out copies).  What the graph cannot serve (``forward``'s list, and h-flip inference) takes
+        ``model.confidence``'s eager routes."""
+        from .confidence import Confidence
+        model = self.model
+        graphable = (self._graphable(x) and x.dim() == 4 and not model.inference_hflip and hasattr(model, 'process_single_tensor')
+                     and hasattr(model, 'frame_size'))
+        if not graphable:
+            return model.confidence(self._to_model_device(x)[0], size=size)
+        style = getattr(model, 'confidence_style', None) or Confidence()
+        device = next(model.parameters()).device
+        frame = tuple(model.frame_size(x))
+        size = frame if size is None else tuple(int(s) for s in size)
+        key = ('confidence', tuple(x.shape), x.dtype, device, self._norm_of(x), style, size)
+        entry = self._graphs.get(key)
+        if entry is None:
+            def run(xs):
+                xs = model.resized(xs)               # (a camera-size uint8 frame: the resize is the graph's first node)
+                return model.process_single_tensor(xs, epilogue=Epilogue(confidence=style, out_size=None if size == frame else size))
+
+            entry = self._capture(key, [x], device, run=run)
+        return self._replay(entry, [x], device)

@@ -580,6 +580,32 @@ int hs_overlay_fwd(const uint8_t* masks, const uint8_t* frames, int32_t layout, 
 int hs_upsample_overlay_fwd(const float* x, int32_t batch, int32_t channels, int32_t Hi, int32_t Wi, int32_t Ho, int32_t Wo,
                             const uint8_t* frames, int32_t layout, const float* tables, int32_t num_colors, int32_t ignore_index,
                             uint8_t* mask, uint8_t* overlay, void* stream);
+/* Served confidence maps (csrc/hs_confidence.hip): beside the uint8 arg-max mask, the soft-max probability of the winning class of every
+ * output pixel.  For the class scores v_0 .. v_{C-1} of a pixel -- exactly what hs_upsample_bilinear_fwd stores for it -- the mask is the
+ * arg-max (strictly greater wins: the lowest class on ties) and the confidence is softmax(v)[argmax] = 1 / sum_c exp(v_c - v_max), taken in
+ * fp32 in one ascending pass over the classes with a running maximum m and a rescaled running sum s (csrc/hs_confidence.h: v_c > m gives
+ * s = s * expf(m - v_c) + 1, m = v_c; otherwise s += expf(v_c - m)), by the same device function in all three entries, so their
+ * confidences agree to the bit.  channels == 1 gives 1.0.  A pixel with a non-finite score has an unspecified confidence, changes no other
+ * pixel, and keeps the mask byte the arg-max entry of the same shape writes.
+ *   conf (batch, Ho, Wo), conf_dtype: HS_CONF_F32 (float) or HS_CONF_U8 (the served form: (uint8)(conf * 255.0f + 0.5f));
+ *   mask (batch, Ho, Wo) uint8; a pixel whose fp32 confidence is < threshold gets the byte `fill` (0..255) there instead of its class
+ *     (pseudo-labels with an ignore value); conf is not changed by it.  threshold <= 0 fills nothing.
+ * channels <= 256 else HS_ERR_UNSUPPORTED; any H, W >= 1 (each plane below 2^31 - 4096 pixels) and any alignment of logits / mask / conf
+ * (wide loads and stores are taken where the addresses allow, single elements otherwise).  Nothing is read back: capturable.
+ *   hs_confidence_fwd: from finished fp32 logits (batch, channels, H, W) -- the composed route's kernel.
+ *   hs_upsample_confidence_fwd: hs_upsample_argmax_fwd (same taps, same arg-max rule, both of its forms, the identity included) with the
+ *     confidence as the launch's epilogue: mask bit-identical to hs_upsample_argmax_fwd's (before the threshold), conf bit-identical to
+ *     hs_upsample_bilinear_fwd + hs_confidence_fwd; the resized logits never exist in memory.
+ *   hs_upsample2_confidence_fwd: the same over two composed resizes x (Hi, Wi) -> (Hm, Wm) -> (Ho, Wo), in both forms of
+ *     hs_upsample2_confusion_fwd (both stages exact 2x; any other pair, down-sampling and identity stages included): mask bit-identical to
+ *     that entry's, conf to two hs_upsample_bilinear_fwd + hs_confidence_fwd. */
+typedef enum { HS_CONF_F32 = 0, HS_CONF_U8 = 1 } hs_conf_dtype;
+int hs_confidence_fwd(const float* logits, int32_t batch, int32_t channels, int32_t H, int32_t W, int32_t conf_dtype, float threshold,
+                      int32_t fill, uint8_t* mask, void* conf, void* stream);
+int hs_upsample_confidence_fwd(const float* x, int32_t batch, int32_t channels, int32_t Hi, int32_t Wi, int32_t Ho, int32_t Wo,
+                               int32_t conf_dtype, float threshold, int32_t fill, uint8_t* mask, void* conf, void* stream);
+int hs_upsample2_confidence_fwd(const float* x, int32_t batch, int32_t channels, int32_t Hi, int32_t Wi, int32_t Hm, int32_t Wm, int32_t Ho,
+                                int32_t Wo, int32_t conf_dtype, float threshold, int32_t fill, uint8_t* mask, void* conf, void* stream);
 /* Camera-size uint8 frames and their labels resized on the device with Pillow's arithmetic (csrc/hs_resample.hip): what the reference's
  * torchvision Resize / RandomResize compute on PIL images (hyperseg/datasets/seg_transforms.py:224-246), plus the crop, pad and flip that
  * follow them (:249-334) as a VIEW, so that only what the crop keeps is resampled.  One geometry per launch, shared by the batch.
