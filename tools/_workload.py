@@ -1,6 +1,6 @@
-"""Decoder-only workload for the dev tools: a HyperGen model with synthetic weights, one synthetic frame pushed through the
-encoder and the context head, returning (decoder, feature pyramid, signal) on the GPU.  (The dev tools deliberately stay
-clear of oracle/: that directory is the tests' checker.)"""
+"""Workloads of the dev tools.  ``decoder_workload``: a HyperGen model with synthetic weights, one synthetic frame pushed through the
+encoder and the context head, returning (decoder, feature pyramid, signal) on the GPU.  ``targets`` / ``label_targets``: the label maps
+the scoring and validation tools count against.  (The dev tools deliberately stay clear of oracle/: that directory is the tests' checker.)"""
 import os
 import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -24,3 +24,28 @@ def decoder_workload(name='M', batch=None, device='cuda:0', seed=0):
     head = head.contiguous() if isinstance(head, torch.Tensor) else head
     pyramid = [t.contiguous() for t in [x] + feats[:-1]]
     return model.decoder, pyramid, head
+
+
+def targets(pattern, h, w, n, seed):
+    """A (1, h, w) int64 target: 'uniform' random classes, 'ignored' with 15 % of them 255, 'rects' piecewise constant."""
+    g = torch.Generator().manual_seed(seed)
+    t = torch.randint(0, n, (1, h, w), generator=g)
+    if pattern == 'ignored':
+        t[torch.rand(1, h, w, generator=g) < 0.15] = 255
+    elif pattern == 'rects':
+        t[:] = 0
+        for k in range(6):
+            y0, x0 = int(torch.randint(0, h - 1, (1,), generator=g)), int(torch.randint(0, w - 1, (1,), generator=g))
+            t[:, y0:y0 + h // 2, x0:x0 + w // 3] = 255 if k == 3 else int(torch.randint(0, n, (1,), generator=g))
+    return t
+
+
+def label_targets(h, w, n, seed):
+    """Piecewise constant with one ignored rectangle, as label maps are.  (Not ``targets('rects', ...)``: that one draws a random map
+    first, so its rectangles fall elsewhere.)"""
+    g = torch.Generator().manual_seed(seed)
+    t = torch.zeros(1, h, w, dtype=torch.int64)
+    for k in range(6):
+        y0, x0 = int(torch.randint(0, h - 1, (1,), generator=g)), int(torch.randint(0, w - 1, (1,), generator=g))
+        t[:, y0:y0 + h // 2, x0:x0 + w // 3] = 255 if k == 3 else int(torch.randint(0, n, (1,), generator=g))
+    return t

@@ -16,74 +16,13 @@ launch); the bytes ``utils.resample._DEVICE_TABLES`` holds after ``--growth-batc
 result against (a)'s, byte for byte (asserted).  With ``--parent-tree`` (a checkout of the parent commit, built): ``python bench.py
 --gpus 1 --steps 200 --warmup 20`` of that tree and of this one, fresh child processes, alternating, ``--bench-rounds`` times each."""
 import argparse
-import json
 import os
-import statistics
-import subprocess
-import sys
-import time
 
 import torch
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-if REPO not in sys.path:
-    sys.path.insert(0, REPO)
+from _measure import REPO, Lines, compare_bench, count_launches, exceeds, graph_of, region_ms, report, require_gpu, wall_ms, write_report
 
 COUNTED = ('hs_frame_resize_fwd', 'hs_label_resize_fwd', 'hs_resize_tables_fwd', 'hs_frame_resize_batch_fwd', 'hs_label_resize_batch_fwd')
-
-
-def region_ms(fn, reps):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    torch.cuda.synchronize()
-    e0.record()
-    for _ in range(reps):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / reps
-
-
-def wall_ms(fn, reps):
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for _ in range(reps):
-        fn()
-    torch.cuda.synchronize()
-    return 1e3 * (time.perf_counter() - t0) / reps
-
-
-def report(lines, title, samples):
-    med = {}
-    lines.append(title)
-    for k, s in samples.items():
-        med[k] = statistics.median(s)
-        lines.append(f'  {k:72s} median {med[k]:.4f}  min {min(s):.4f}  max {max(s):.4f}  spread {max(s) - min(s):.4f}   samples ' +
-                     ' '.join(f'{v:.4f}' for v in s))
-    return med, {k: max(s) - min(s) for k, s in samples.items()}
-
-
-def count_launches(lib, fn):
-    """Calls of the COUNTED library entries while ``fn`` runs: name -> count."""
-    counts, saved = {}, {}
-    for name in COUNTED:
-        saved[name] = real = getattr(lib, name)
-
-        def counting(*a, _real=real, _name=name):
-            counts[_name] = counts.get(_name, 0) + 1
-            return _real(*a)
-        setattr(lib, name, counting)
-    try:
-        fn()
-    finally:
-        for name, real in saved.items():
-            setattr(lib, name, real)
-    return counts
-
-
-def bench_value(tree):
-    out = subprocess.run([sys.executable, 'bench.py', '--gpus', '1', '--steps', '200', '--warmup', '20'], cwd=tree, capture_output=True,
-                         text=True, timeout=300, check=True).stdout
-    return float(json.loads([ln for ln in out.splitlines() if ln.startswith('{')][-1])['value'])
 
 
 def main():
@@ -95,8 +34,7 @@ def main():
     ap.add_argument('--bench-rounds', type=int, default=3)
     ap.add_argument('--out', default=os.path.join(REPO, 'profiles', 'batch_augment_time.txt'))
     args = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit('batch_augment_time.py measures on the GPU: no device found')
+    require_gpu('batch_augment_time.py')
     from hyperseg_amd import _hip
     from hyperseg_amd import functional as HF
     from hyperseg_amd.training import BatchAugment, device_augment
@@ -126,14 +64,15 @@ def main():
     def route_c(p):
         return aug(frames, labels, *p)
 
-    lines = [f'Cityscapes HyperSeg-S train chain, batch {b}, {wi}x{hi} uint8 hwc frames -> {crop[1]}x{crop[0]} crops, bicubic, scales uniform in '
-             f'({lo}, {hi_s}) drawn fresh per batch; {args.rounds} interleaved rounds; ks_max {aug.ks_max}']
+    lines = Lines()
+    lines.append(f'Cityscapes HyperSeg-S train chain, batch {b}, {wi}x{hi} uint8 hwc frames -> {crop[1]}x{crop[0]} crops, bicubic, scales uniform in '
+                 f'({lo}, {hi_s}) drawn fresh per batch; {args.rounds} interleaved rounds; ks_max {aug.ks_max}')
     p0 = draw()
     want, got = route_a(p0), route_c(p0)
     same = torch.equal(want[0], got[0]) and torch.equal(want[1], got[1])
     lines.append(f'(c) equals (a), image and label, byte for byte: {same}; status all zero: {not bool(aug.status.any())}')
-    counts_a = count_launches(_hip.run, lambda: route_a(draw()))
-    counts_c = count_launches(_hip.run, lambda: route_c(draw()))
+    counts_a = count_launches(_hip.run, COUNTED, lambda: route_a(draw()))
+    counts_c = count_launches(_hip.run, COUNTED, lambda: route_c(draw()))
     lines.append(f'library launches per batch, (a): {sum(counts_a.values())} {counts_a};  (c): {sum(counts_c.values())} {counts_c}')
 
     fixed = (0.75, (0, 384), False)                               # tools/color_jitter_time.py's (c): the README's 0.636 ms case
@@ -146,10 +85,7 @@ def main():
     with torch.cuda.graph(graph):
         aug.run(frames, labels, out=out)
     launches = 50
-    tgraph = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(tgraph):
-        for _ in range(launches):
-            HF.resize_tables(aug.params, (hi, wi), crop, 'bicubic', aug.ks_max, workspace=aug.workspace)
+    tgraph = graph_of(lambda: HF.resize_tables(aug.params, (hi, wi), crop, 'bicubic', aug.ks_max, workspace=aug.workspace), launches, warm=0)
     staged = [aug.rows(*draw()).to(dev) for _ in range(args.rounds)]
 
     keys = {'a': '(a) device_augment, fresh draws, WALL per batch',
@@ -172,8 +108,8 @@ def main():
     lines.append(f'  (a) / (c) wall = {med[a] / med[cw]:.1f}x  ({med[a]:.3f} -> {med[cw]:.3f} ms): the user-visible number')
     for name, k in (('(c) device events', ce), ('(d) graph replay', keys['d'])):
         diff, both = med[bb] - med[k], spread[bb] + spread[k]
-        verdict = 'beats (b) by more than the sum of the two spreads' if diff > both else \
-            'does NOT beat (b) by more than the sum of the two spreads' if diff >= -both else 'is SLOWER than (b) by more than the sum of the two spreads'
+        verdict = 'beats (b) by more than the sum of the two spreads' if exceeds(bb, k, med, spread) else \
+            'is SLOWER than (b) by more than the sum of the two spreads' if exceeds(k, bb, med, spread) else 'does NOT beat (b) by more than the sum of the two spreads'
         lines.append(f'  (b) - {name} = {diff:+.4f} ms, sum of the two spreads {both:.4f}: {name} {verdict}')
 
     before = sum(t.numel() * t.element_size() for v in resample._DEVICE_TABLES.values() for t in v)
@@ -186,28 +122,8 @@ def main():
                  f'{args.growth_batches} more batches of (a) = {(after - before) / 1e3 / args.growth_batches:.0f} KB per batch, never freed;  '
                  f"(c)'s workspace: {aug.workspace.numel() * 4 / 1e6:.2f} MB, fixed")
 
-    bench_error = None
-    if args.parent_tree:
-        vals = {'parent': [], 'this tree': []}
-        try:
-            for _ in range(args.bench_rounds):
-                vals['parent'].append(bench_value(args.parent_tree))
-                vals['this tree'].append(bench_value(REPO))
-        except (subprocess.SubprocessError, ValueError, IndexError, KeyError) as e:
-            bench_error = e
-        lines.append(f'bench.py --gpus 1 --steps 200 --warmup 20, fresh processes, alternating, {args.bench_rounds} each; frames/s')
-        for k, s in vals.items():
-            if s:
-                lines.append(f'  {k:10s} median {statistics.median(s):.2f}  min {min(s):.2f}  max {max(s):.2f}   samples ' + ' '.join(f'{v:.2f}' for v in s))
-        if bench_error is not None:
-            lines.append(f'  the comparison stopped early: {type(bench_error).__name__}')
-    else:
-        lines.append('bench.py: no --parent-tree given, not compared in this run')
-    text = '\n'.join(lines)
-    print(text)
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, 'w') as f:
-        f.write(text + '\n')
+    bench_error = compare_bench(lines, args.parent_tree, args.bench_rounds)
+    write_report(lines, args.out)
     assert same, 'BatchAugment disagrees with device_augment'
     assert sum(counts_c.values()) == 3, f'BatchAugment made {counts_c} launches, expected 3'
     if bench_error is not None:

@@ -16,59 +16,11 @@ With ``--parent-tree`` (a checkout of the parent commit, built): ``python bench.
 this one, as fresh child processes, alternating, ``--bench-rounds`` times each; both values go into the same file.
 The device's bytes must equal the CPU implementation's and -- with Pillow -- Pillow's (asserted)."""
 import argparse
-import json
 import os
-import statistics
-import subprocess
-import sys
-import time
 
 import torch
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-if REPO not in sys.path:
-    sys.path.insert(0, REPO)
-
-
-def region_ms(fn, reps):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    torch.cuda.synchronize()
-    e0.record()
-    for _ in range(reps):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / reps
-
-
-def host_ms(fn, reps):
-    t0 = time.perf_counter()
-    for _ in range(reps):
-        fn()
-    return 1e3 * (time.perf_counter() - t0) / reps
-
-
-def report(lines, title, samples):
-    med = {}
-    lines.append(title)
-    for k, s in samples.items():
-        med[k] = statistics.median(s)
-        lines.append(f'  {k:62s} median {med[k]:.4f}  min {min(s):.4f}  max {max(s):.4f}  spread {max(s) - min(s):.4f}   samples ' +
-                     ' '.join(f'{v:.4f}' for v in s))
-    return med, {k: max(s) - min(s) for k, s in samples.items()}
-
-
-def interleaved(lines, title, variants, rounds, warmup=3):
-    """variants: name -> (timer, fn, reps)."""
-    for _, fn, _ in variants.values():
-        for _ in range(warmup):
-            fn()
-    torch.cuda.synchronize()
-    samples = {k: [] for k in variants}
-    for _ in range(rounds):
-        for k, (timer, fn, reps) in variants.items():
-            samples[k].append(timer(fn, reps))
-    return report(lines, title, samples)
+from _measure import REPO, Lines, compare_bench, graph_of, host_ms, interleaved, per_launch, region_ms, require_gpu, write_report
 
 
 def pillow_jitter(Image, ImageEnhance, np, a, p):
@@ -84,12 +36,6 @@ def pillow_jitter(Image, ImageEnhance, np, a, p):
     return np.asarray(img)
 
 
-def bench_value(tree):
-    out = subprocess.run([sys.executable, 'bench.py', '--gpus', '1', '--steps', '200', '--warmup', '20'], cwd=tree, capture_output=True,
-                         text=True, timeout=300, check=True).stdout
-    return float(json.loads([ln for ln in out.splitlines() if ln.startswith('{')][-1])['value'])
-
-
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split('\n')[0])
     ap.add_argument('--rounds', type=int, default=7)
@@ -98,8 +44,7 @@ def main():
     ap.add_argument('--bench-rounds', type=int, default=3)
     ap.add_argument('--out', default=os.path.join(REPO, 'profiles', 'color_jitter_time.txt'))
     args = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit('color_jitter_time.py measures on the GPU: no device found')
+    require_gpu('color_jitter_time.py')
     try:
         import numpy as np
         from PIL import Image, ImageEnhance
@@ -127,20 +72,14 @@ def main():
     pillow_same = None
     if Image is not None:
         pillow_same = all(bool((pillow_jitter(Image, ImageEnhance, np, crops[i].numpy(), params[i]) == got[i].numpy()).all()) for i in range(b))
-    lines = [f'ColorJitter(0.25, 0.25, 0.25, 0.25), batch {b}, {w}x{h} uint8 hwc crops, all four operations, order and factors per sample; '
-             f'{args.rounds} interleaved rounds',
-             f'the device bytes equal the CPU implementation (first 2 samples): {cpu_same}',
-             f'the device bytes equal Pillow (all {b} samples): {pillow_same if Image is not None else "Pillow is not installed"}']
+    lines = Lines()
+    lines.append(f'ColorJitter(0.25, 0.25, 0.25, 0.25), batch {b}, {w}x{h} uint8 hwc crops, all four operations, order and factors per sample; '
+                 f'{args.rounds} interleaved rounds')
+    lines.append(f'the device bytes equal the CPU implementation (first 2 samples): {cpu_same}')
+    lines.append(f'the device bytes equal Pillow (all {b} samples): {pillow_same if Image is not None else "Pillow is not installed"}')
 
     launches = 50
-    for _ in range(3):
-        HF.color_jitter(crops_dev, None, 'hwc', norm=norm, out=out_f, table=table)
-    torch.cuda.synchronize()
-    graph = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(graph):
-        for _ in range(launches):
-            HF.color_jitter(crops_dev, None, 'hwc', norm=norm, out=out_f, table=table)
-    graph.replay()
+    graph = graph_of(lambda: HF.color_jitter(crops_dev, None, 'hwc', norm=norm, out=out_f, table=table), launches, warm=3)
     legs = {}
     if Image is not None:
         arrays = [c.numpy() for c in crops]
@@ -150,8 +89,8 @@ def main():
     else:
         lines.append('(a) SKIPPED: Pillow is not installed on this machine')
     key_b = f'(b) device color_jitter -> float32, per batch of {b} (graph of {launches})'
-    legs[key_b] = (lambda fn, reps: region_ms(fn, reps) / launches, graph.replay, args.reps)
-    med, spread = interleaved(lines, '(a) host clock / (b) device events; ms', legs, args.rounds)
+    legs[key_b] = (per_launch(launches), graph.replay, args.reps)
+    med, spread = interleaved(lines, '(a) host clock / (b) device events; ms', legs, args.rounds, warmup=3)
     if Image is not None:
         key_a = f'(a) host Pillow, 1 thread, per batch of {b}'
         lines.append(f'  (a) / (b) per batch = {med[key_a] / med[key_b]:.0f}x; (a) - (b) = {med[key_a] - med[key_b]:+.4f} ms, sum of the two spreads '
@@ -168,32 +107,12 @@ def main():
     aug = lambda jit: device_augment(frames, labels, 0.75, (h, w), (0, 384), False, norm, jitter=jit)
     legs = {'(c) device_augment, 16 frames 2048x1024 -> 768x768, no jitter': (region_ms, lambda: aug(None), 5),
             '(c) device_augment, the same with jitter=': (region_ms, lambda: aug(params), 5)}
-    med, spread = interleaved(lines, '(c) eager launches, device events; ms per batch', legs, args.rounds)
+    med, spread = interleaved(lines, '(c) eager launches, device events; ms per batch', legs, args.rounds, warmup=3)
     keys = list(legs)
     lines.append(f'  with - without = {med[keys[1]] - med[keys[0]]:+.4f} ms per batch (sum of the two spreads {spread[keys[0]] + spread[keys[1]]:.4f})')
 
-    bench_error = None
-    if args.parent_tree:
-        vals = {'parent': [], 'this tree': []}
-        try:
-            for _ in range(args.bench_rounds):
-                vals['parent'].append(bench_value(args.parent_tree))
-                vals['this tree'].append(bench_value(REPO))
-        except (subprocess.SubprocessError, ValueError, IndexError, KeyError) as e:
-            bench_error = e
-        lines.append(f'bench.py --gpus 1 --steps 200 --warmup 20, fresh processes, alternating, {args.bench_rounds} each; frames/s')
-        for k, s in vals.items():
-            if s:
-                lines.append(f'  {k:10s} median {statistics.median(s):.2f}  min {min(s):.2f}  max {max(s):.2f}   samples ' + ' '.join(f'{v:.2f}' for v in s))
-        if bench_error is not None:
-            lines.append(f'  the comparison stopped early: {type(bench_error).__name__}')
-    else:
-        lines.append('bench.py: no --parent-tree given, not compared in this run')
-    text = '\n'.join(lines)
-    print(text)
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, 'w') as f:
-        f.write(text + '\n')
+    bench_error = compare_bench(lines, args.parent_tree, args.bench_rounds)
+    write_report(lines, args.out)
     assert cpu_same, 'the device jitter disagrees with the CPU implementation'
     assert pillow_same is not False, 'the device jitter disagrees with Pillow'
     if bench_error is not None:

@@ -15,25 +15,10 @@ Stated, not asserted: whether (2f) is below (4) by more than the sum of the two 
 give the same confidence bits and the masks of (1); (4) agrees with them to 1e-6."""
 import argparse
 import os
-import statistics
-import sys
 
 import torch
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-if REPO not in sys.path:
-    sys.path.insert(0, REPO)
-
-
-def region_ms(fn, reps):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    torch.cuda.synchronize()
-    e0.record()
-    for _ in range(reps):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / reps
+from _measure import REPO, Lines, exceeds, interleaved, region_ms, require_gpu, write_report
 
 
 def main():
@@ -42,8 +27,7 @@ def main():
     ap.add_argument('--reps', type=int, default=200)
     ap.add_argument('--out', default=os.path.join(REPO, 'profiles', 'confidence_time.txt'))
     args = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit('confidence_time.py measures on the GPU: no device found')
+    require_gpu('confidence_time.py')
     from hyperseg_amd import Confidence, configs, functional as HF
     from hyperseg_amd.utils.inference import GraphedModel, prepare_for_inference
     from hyperseg_amd.utils.synthetic import fill_by_name
@@ -84,7 +68,7 @@ def main():
     def r4l():
         keep['4L'] = torch.softmax(HF.upsample_bilinear(logits_g(x), big), 1).max(1)
 
-    variants = {'1': r1, '2u': r2u, '2f': r2f, '3': r3, '4': r4, '2uL': r2ul, '4L': r4l}
+    variants = {'(1)': r1, '(2u)': r2u, '(2f)': r2f, '(3)': r3, '(4)': r4, '(2uL)': r2ul, '(4L)': r4l}
     for fn in variants.values():                    # every shape and graph warmed before anything is timed
         for _ in range(5):
             fn()
@@ -92,28 +76,16 @@ def main():
     same_masks = torch.equal(keep['1'], keep['2f'][0]) and torch.equal(keep['1'], keep['2u'][0]) and torch.equal(keep['1'], keep['3'][0])
     same_bits = torch.equal(keep['2f'][1], keep['3'][1]) and torch.equal(keep['2u'][1], (keep['2f'][1] * 255.0 + 0.5).to(torch.uint8))
     stock_gap = float((keep['4'].values - keep['2f'][1]).abs().max())
-    samples = {k: [] for k in variants}
-    for _ in range(args.rounds):
-        for k, fn in variants.items():
-            samples[k].append(region_ms(fn, args.reps))
-    lines = [f'HyperSeg-M {w}x{h} bs 1, prepared, HIP-graph replay, resident input; {args.rounds} interleaved rounds x {args.reps} frames, ms per frame',
-             f'masks of (1), (2u), (2f), (3) equal: {same_masks};  confidence bits of (2f) and (3) equal, (2u) their quantisation: {same_bits};  '
-             f'max |(4) - (2f)| = {stock_gap:.2e}']
-    med, spread = {}, {}
-    for k in variants:
-        s = samples[k]
-        med[k], spread[k] = statistics.median(s), max(s) - min(s)
-        lines.append(f'({k:3s}) median {med[k]:.4f}  min {min(s):.4f}  max {max(s):.4f}  spread {spread[k]:.4f}   samples ' + ' '.join(f'{v:.4f}' for v in s))
-    lines.append('   '.join(f'({k}) - (1) = {med[k] - med["1"]:+.4f} ms' for k in ('2u', '2f', '3', '4')))
-    for a, b in (('2f', '4'), ('2u', '4'), ('2f', '3'), ('2uL', '4L')):
-        gap, both = med[b] - med[a], spread[a] + spread[b]
-        lines.append(f'({b}) - ({a}) = {gap:+.4f} ms vs the sum of the two spreads {both:.4f}: ({a}) is '
-                     + ('below' if gap > both else 'NOT below') + f' ({b}) by more than that')
-    text = '\n'.join(lines)
-    print(text)
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, 'w') as f:
-        f.write(text + '\n')
+    lines = Lines()
+    lines.append(f'HyperSeg-M {w}x{h} bs 1, prepared, HIP-graph replay, resident input; {args.rounds} interleaved rounds x {args.reps} frames, ms per frame')
+    lines.append(f'masks of (1), (2u), (2f), (3) equal: {same_masks};  confidence bits of (2f) and (3) equal, (2u) their quantisation: {same_bits};  '
+                 f'max |(4) - (2f)| = {stock_gap:.2e}')
+    med, spread = interleaved(lines, None, {k: (region_ms, fn, args.reps) for k, fn in variants.items()}, args.rounds, warmup=0)
+    lines.append('   '.join(f'{k} - (1) = {med[k] - med["(1)"]:+.4f} ms' for k in ('(2u)', '(2f)', '(3)', '(4)')))
+    for a, b in (('(2f)', '(4)'), ('(2u)', '(4)'), ('(2f)', '(3)'), ('(2uL)', '(4L)')):
+        lines.append(f'{b} - {a} = {med[b] - med[a]:+.4f} ms vs the sum of the two spreads {spread[a] + spread[b]:.4f}: {a} is '
+                     + ('below' if exceeds(b, a, med, spread) else 'NOT below') + f' {b} by more than that')
+    write_report(lines, args.out)
     assert same_masks and same_bits, 'the routes disagree'
     assert stock_gap < 1e-6, 'stock softmax disagrees with the kernels'
 

@@ -15,37 +15,10 @@ random, 15 % ignored, piecewise constant).  All four variants must produce the s
 import argparse
 import os
 import statistics
-import sys
 
 import torch
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-if REPO not in sys.path:
-    sys.path.insert(0, REPO)
-
-
-def region_ms(fn, reps):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    torch.cuda.synchronize()
-    e0.record()
-    for _ in range(reps):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / reps
-
-
-def targets(pattern, h, w, n, seed):
-    g = torch.Generator().manual_seed(seed)
-    t = torch.randint(0, n, (1, h, w), generator=g)
-    if pattern == 'ignored':
-        t[torch.rand(1, h, w, generator=g) < 0.15] = 255
-    elif pattern == 'rects':
-        t[:] = 0
-        for k in range(6):
-            y0, x0 = int(torch.randint(0, h - 1, (1,), generator=g)), int(torch.randint(0, w - 1, (1,), generator=g))
-            t[:, y0:y0 + h // 2, x0:x0 + w // 3] = 255 if k == 3 else int(torch.randint(0, n, (1,), generator=g))
-    return t
+from _measure import REPO, Lines, interleaved, region_ms, require_gpu, write_report
 
 
 def main():
@@ -54,12 +27,12 @@ def main():
     ap.add_argument('--reps', type=int, default=200)
     ap.add_argument('--out', default=os.path.join(REPO, 'profiles', 'eval_epilogue_time.txt'))
     args = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit('eval_epilogue_time.py measures on the GPU: no device found')
+    require_gpu('eval_epilogue_time.py')
     from hyperseg_amd import configs, functional as HF
     from hyperseg_amd.fps import ConfusionMatrix
     from hyperseg_amd.utils.inference import GraphedModel, prepare_for_inference
     from hyperseg_amd.utils.synthetic import fill_by_name
+    from _workload import targets
     dev = torch.device('cuda:0')
     n, (h, w) = 19, (512, 1024)
     model = fill_by_name(configs.build('hyperseg-m').eval(), seed=0)
@@ -85,7 +58,7 @@ def main():
     def d():
         served.evaluate(x, tgt)
 
-    variants = {'a': a, 'b': b, 'c': c, 'd': d}
+    variants = {'(a)': a, '(b)': b, '(c)': c, '(d)': d}
     for fn in variants.values():                    # every shape and graph warmed before anything is timed
         for _ in range(5):
             fn()
@@ -94,23 +67,14 @@ def main():
     b(); c(); d()
     torch.cuda.synchronize()
     same = torch.equal(stock.mat, kern.mat) and torch.equal(stock.mat, served.confusion)
-    samples = {k: [] for k in variants}
-    for _ in range(args.rounds):
-        for k, fn in variants.items():
-            samples[k].append(region_ms(fn, args.reps))
-    lines = [f'HyperSeg-M {w}x{h} bs 1, prepared, HIP-graph replay; {args.rounds} interleaved rounds x {args.reps} frames, ms per frame',
-             f'matrices of (b), (c), (d) equal: {same}']
-    med = {}
-    for k in variants:
-        s = samples[k]
-        med[k] = statistics.median(s)
-        lines.append(f'({k}) median {med[k]:.4f}  min {min(s):.4f}  max {max(s):.4f}  spread {max(s) - min(s):.4f}   samples ' +
-                     ' '.join(f'{v:.4f}' for v in s))
-    spread = {k: max(v) - min(v) for k, v in samples.items()}
-    lines.append(f'(d) - (a) = {med["d"] - med["a"]:+.4f} ms   (c) - (a) = {med["c"] - med["a"]:+.4f} ms   (b) - (a) = {med["b"] - med["a"]:+.4f} ms')
-    lines.append(f'(b) - (d) = {med["b"] - med["d"]:.4f} ms vs spread {max(spread["b"], spread["d"]):.4f};  '
-                 f'(b) - (c) = {med["b"] - med["c"]:.4f} ms vs spread {max(spread["b"], spread["c"]):.4f};  '
-                 f'(c) - (d) = {med["c"] - med["d"]:+.4f} ms vs spread {max(spread["c"], spread["d"]):.4f}')
+    lines = Lines()
+    lines.append(f'HyperSeg-M {w}x{h} bs 1, prepared, HIP-graph replay; {args.rounds} interleaved rounds x {args.reps} frames, ms per frame')
+    lines.append(f'matrices of (b), (c), (d) equal: {same}')
+    med, spread = interleaved(lines, None, {k: (region_ms, fn, args.reps) for k, fn in variants.items()}, args.rounds, warmup=0)
+    lines.append(f'(d) - (a) = {med["(d)"] - med["(a)"]:+.4f} ms   (c) - (a) = {med["(c)"] - med["(a)"]:+.4f} ms   (b) - (a) = {med["(b)"] - med["(a)"]:+.4f} ms')
+    lines.append(f'(b) - (d) = {med["(b)"] - med["(d)"]:.4f} ms vs spread {max(spread["(b)"], spread["(d)"]):.4f};  '
+                 f'(b) - (c) = {med["(b)"] - med["(c)"]:.4f} ms vs spread {max(spread["(b)"], spread["(c)"]):.4f};  '
+                 f'(c) - (d) = {med["(c)"] - med["(d)"]:+.4f} ms vs spread {max(spread["(c)"], spread["(d)"]):.4f}')
     # the two kernels alone, full size, per target pattern (smooth + noise logits stand in for the decoder's last level)
     g = torch.Generator().manual_seed(3)
     logits = (torch.nn.functional.interpolate(torch.randn(1, n, h // 8, w // 8, generator=g), size=(h // 2, w // 2), mode='bilinear')
@@ -129,14 +93,10 @@ def main():
                 s = [1e3 * region_ms(lambda: fn(t), 100) for _ in range(3)]
                 lines.append(f'kernel alone, {pattern:8s} {str(dt)[6:]:6s} {name:42s} {statistics.median(s):8.2f} us  '
                              f'(min {min(s):.2f} max {max(s):.2f}; eager launches back to back)')
-    text = '\n'.join(lines)
-    print(text)
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, 'w') as f:
-        f.write(text + '\n')
+    write_report(lines, args.out)
     assert same, 'the variants disagree on the matrix'
-    assert med['b'] - med['d'] > max(spread['b'], spread['d']), '(d) is not below (b) by more than the spread'
-    assert med['b'] - med['c'] > max(spread['b'], spread['c']), '(c) is not below (b) by more than the spread'
+    assert med['(b)'] - med['(d)'] > max(spread['(b)'], spread['(d)']), '(d) is not below (b) by more than the spread'
+    assert med['(b)'] - med['(c)'] > max(spread['(b)'], spread['(c)']), '(c) is not below (b) by more than the spread'
 
 
 if __name__ == '__main__':

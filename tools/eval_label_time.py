@@ -19,43 +19,20 @@ the label, arg-max + count), on smooth + noise logits at each model's last-level
 import argparse
 import os
 import statistics
-import sys
 
 import torch
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-if REPO not in sys.path:
-    sys.path.insert(0, REPO)
+from _measure import REPO, Lines, exceeds, interleaved, region_ms, require_gpu, write_report
 
 LABEL = (1024, 2048)
 MODELS = {'m': ('hyperseg-m', (512, 1024)), 's': ('hyperseg-s', (768, 1536))}
-
-
-def region_ms(fn, reps):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    torch.cuda.synchronize()
-    e0.record()
-    for _ in range(reps):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / reps
-
-
-def targets(h, w, n, seed):
-    """Piecewise constant with one ignored rectangle, as label maps are."""
-    g = torch.Generator().manual_seed(seed)
-    t = torch.zeros(1, h, w, dtype=torch.int64)
-    for k in range(6):
-        y0, x0 = int(torch.randint(0, h - 1, (1,), generator=g)), int(torch.randint(0, w - 1, (1,), generator=g))
-        t[:, y0:y0 + h // 2, x0:x0 + w // 3] = 255 if k == 3 else int(torch.randint(0, n, (1,), generator=g))
-    return t
 
 
 def one_model(tag, rounds, reps, lines):
     from hyperseg_amd import configs, functional as HF
     from hyperseg_amd.utils.inference import GraphedModel, prepare_for_inference
     from hyperseg_amd.utils.synthetic import fill_by_name
+    from _workload import label_targets
     dev = torch.device('cuda:0')
     name, (h, w) = MODELS[tag]
     n = configs.MODELS[name]['num_classes']
@@ -64,7 +41,7 @@ def one_model(tag, rounds, reps, lines):
     model.inference_hflip = False       # inert for tensor inputs, but segment() takes the logits + argmax route while it is set
     model = model.to(dev)
     x = torch.rand(1, 3, h, w, generator=torch.Generator().manual_seed(1)).to(dev)
-    tgt = targets(LABEL[0], LABEL[1], n, 2).to(dev)
+    tgt = label_targets(LABEL[0], LABEL[1], n, 2).to(dev)
     served = GraphedModel(model, masks=True, num_classes=n)
     logits_served = GraphedModel(model)
     mats = {k: torch.zeros(n, n, dtype=torch.int64, device=dev) for k in 'bc'}
@@ -85,7 +62,7 @@ def one_model(tag, rounds, reps, lines):
     def d():
         served.evaluate(x, tgt)
 
-    legs = {'a': a, 'b': b, 'c': c, 'd': d}
+    legs = {'(a)': a, '(b)': b, '(c)': c, '(d)': d}
     for fn in legs.values():                        # every shape and graph warmed before anything is timed
         for _ in range(3):
             fn()
@@ -98,21 +75,14 @@ def one_model(tag, rounds, reps, lines):
     same = torch.equal(mats['b'], mats['c']) and torch.equal(mats['b'], served.confusion)
     assert same, f'{name}: the legs disagree on the matrix'
     assert int(mats['b'].sum()) == int((tgt != 255).sum())
-    samples = {k: [] for k in legs}
-    for _ in range(rounds):
-        for k, fn in legs.items():
-            samples[k].append(region_ms(fn, reps))
+    if lines:
+        lines.append('')
     lines.append(f'{name} {w}x{h} bs 1, prepared; int64 labels {LABEL[1]}x{LABEL[0]}; {rounds} interleaved rounds x {reps} frames, ms per frame')
     lines.append(f'matrices of (b), (c), (d) equal: {same}')
-    med, spread = {}, {}
-    for k in legs:
-        s = samples[k]
-        med[k], spread[k] = statistics.median(s), max(s) - min(s)
-        lines.append(f'({k}) median {med[k]:.4f}  min {min(s):.4f}  max {max(s):.4f}  spread {spread[k]:.4f}   samples ' +
-                     ' '.join(f'{v:.4f}' for v in s))
-    ok = med['b'] - med['d'] > spread['b'] + spread['d']
-    lines.append(f'(b) - (d) = {med["b"] - med["d"]:+.4f} ms vs spread(b) + spread(d) = {spread["b"] + spread["d"]:.4f}: requirement '
-                 f'{"met" if ok else "NOT met"};  (c) - (d) = {med["c"] - med["d"]:+.4f} ms;  (d) - (a) = {med["d"] - med["a"]:+.4f} ms')
+    med, spread = interleaved(lines, None, {k: (region_ms, fn, reps) for k, fn in legs.items()}, rounds, warmup=0)
+    ok = exceeds('(b)', '(d)', med, spread)
+    lines.append(f'(b) - (d) = {med["(b)"] - med["(d)"]:+.4f} ms vs spread(b) + spread(d) = {spread["(b)"] + spread["(d)"]:.4f}: requirement '
+                 f'{"met" if ok else "NOT met"};  (c) - (d) = {med["(c)"] - med["(d)"]:+.4f} ms;  (d) - (a) = {med["(d)"] - med["(a)"]:+.4f} ms')
     # the kernel alone against the three launches it replaces, at this model's last-level size
     hi, wi = h // 2, w // 2
     g = torch.Generator().manual_seed(3)
@@ -134,7 +104,6 @@ def one_model(tag, rounds, reps, lines):
         s = [1e3 * region_ms(fn, 50) for _ in range(3)]
         lines.append(f'kernel alone, {hi}x{wi} -> {h}x{w} -> {LABEL[0]}x{LABEL[1]}: {label:56s} {statistics.median(s):9.2f} us  '
                      f'(min {min(s):.2f} max {max(s):.2f}; eager launches back to back)')
-    lines.append('')
     return ok
 
 
@@ -145,16 +114,11 @@ def main():
     ap.add_argument('--models', nargs='+', choices=sorted(MODELS), default=['m', 's'])
     ap.add_argument('--out', default=os.path.join(REPO, 'profiles', 'eval_label_time.txt'))
     args = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit('eval_label_time.py measures on the GPU: no device found')
-    lines, ok = [], True
+    require_gpu('eval_label_time.py')
+    lines, ok = Lines(), True
     for tag in args.models:
         ok = one_model(tag, args.rounds, args.reps, lines) and ok
-    text = '\n'.join(lines)
-    print(text)
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, 'w') as f:
-        f.write(text)
+    write_report(lines, args.out)
     if not ok:
         raise SystemExit('(d) is not below (b) by more than the sum of the two spreads on every model')
 

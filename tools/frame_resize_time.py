@@ -16,69 +16,14 @@ The masks of (b) / (d) must equal those of (c) on the frame ``FrameResize`` make
 import argparse
 import os
 import statistics
-import sys
-import time
 
 import torch
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-if REPO not in sys.path:
-    sys.path.insert(0, REPO)
-
-
-def region_ms(fn, reps):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    torch.cuda.synchronize()
-    e0.record()
-    for _ in range(reps):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / reps
-
-
-def protocol_ms(fn, reps):
-    total = 0.0
-    for _ in range(reps):
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        fn()
-        torch.cuda.synchronize()
-        total += time.perf_counter() - t0
-    return 1e3 * total / reps
-
-
-def report(lines, title, samples):
-    med = {}
-    lines.append(title)
-    for k, s in samples.items():
-        med[k] = statistics.median(s)
-        lines.append(f'  {k:58s} median {med[k]:.4f}  min {min(s):.4f}  max {max(s):.4f}  spread {max(s) - min(s):.4f}   samples ' +
-                     ' '.join(f'{v:.4f}' for v in s))
-    return med, {k: max(s) - min(s) for k, s in samples.items()}
-
-
-def interleaved(lines, title, timer, variants, rounds, reps):
-    for fn in variants.values():                                   # every graph and shape warm before anything is timed
-        for _ in range(10):
-            fn()
-    torch.cuda.synchronize()
-    samples = {k: [] for k in variants}
-    for _ in range(rounds):
-        for k, fn in variants.items():
-            samples[k].append(timer(fn, reps))
-    return report(lines, title, samples)
+from _measure import REPO, Lines, exceeds, graph_of, interleaved, protocol_ms, region_ms, require_gpu, write_report
 
 
 def launches_us(fn, lines, name, mb):
-    for _ in range(5):
-        fn()
-    torch.cuda.synchronize()
-    graph = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(graph):
-        for _ in range(50):
-            fn()
-    graph.replay()
+    graph = graph_of(fn, 50, warm=5)
     s = [1e3 * region_ms(graph.replay, 20) / 50 for _ in range(5)]
     us = statistics.median(s)
     lines.append(f'  {name:46s} {us:7.2f} us per launch (min {min(s):.2f} max {max(s):.2f})  {mb:.2f} MB  ->  {mb / us:.3f} TB/s '
@@ -92,8 +37,7 @@ def main():
     ap.add_argument('--reps', type=int, default=200)
     ap.add_argument('--out', default=os.path.join(REPO, 'profiles', 'frame_resize_time.txt'))
     args = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit('frame_resize_time.py measures on the GPU: no device found')
+    require_gpu('frame_resize_time.py')
     try:
         from PIL import Image
     except ImportError:
@@ -128,26 +72,27 @@ def main():
         small_np[...] = Image.fromarray(cam_np).resize((w, h), Image.BILINEAR)
         return plain(small_host)
 
-    lines = [f'HyperSeg-M, camera {wc}x{hc} -> {w}x{h} bilinear, bs 1, prepared (split GEMM), HIP-graph replay, uint8 masks out; '
-             f'{args.rounds} interleaved rounds x {args.reps} frames',
-             f'masks with the resize in the graph equal the masks on the resized frame: {same}',
-             f'the resized frame equals PIL.Image.resize byte for byte: {pillow_same if Image is not None else "Pillow is not installed"}']
+    lines = Lines()
+    lines.append(f'HyperSeg-M, camera {wc}x{hc} -> {w}x{h} bilinear, bs 1, prepared (split GEMM), HIP-graph replay, uint8 masks out; '
+                 f'{args.rounds} interleaved rounds x {args.reps} frames')
+    lines.append(f'masks with the resize in the graph equal the masks on the resized frame: {same}')
+    lines.append(f'the resized frame equals PIL.Image.resize byte for byte: {pillow_same if Image is not None else "Pillow is not installed"}')
     legs = {}
     if Image is not None:
-        legs['(a) host PIL resize (1 thread) + H2D 1.6 MB + replay'] = host_leg
+        legs['(a) host PIL resize (1 thread) + H2D 1.6 MB + replay'] = (protocol_ms, host_leg, args.reps)
     else:
         lines.append('(a) SKIPPED: Pillow is not installed on this machine')
-    legs['(b) H2D 6.3 MB camera frame + replay with the resize'] = lambda: resizing(cam_host)
+    legs['(b) H2D 6.3 MB camera frame + replay with the resize'] = (protocol_ms, lambda: resizing(cam_host), args.reps)
     med, spread = interleaved(lines, '(a) / (b) reference protocol: sync, [resize,] H2D of a pinned frame + replay, sync; host clock, ms per frame',
-                              protocol_ms, legs, args.rounds, args.reps)
+                              legs, args.rounds, warmup=10)
     keys = list(legs)
     if len(keys) == 2:
         diff, both = med[keys[0]] - med[keys[1]], spread[keys[0]] + spread[keys[1]]
         lines.append(f'  (a) - (b) = {diff:+.4f} ms; sum of the two spreads {both:.4f}: (b) is '
-                     f'{"below (a) by more than that" if diff > both else "NOT below (a) by more than that"}')
-    legs = {'(c) resident resized frame, replay': lambda: plain(small_dev),
-            '(d) resident camera frame, replay with the resize': lambda: resizing(cam_dev)}
-    med, spread = interleaved(lines, '(c) / (d) resident input, replay only; device events, ms per frame', region_ms, legs, args.rounds, args.reps)
+                     f'{"below (a) by more than that" if exceeds(keys[0], keys[1], med, spread) else "NOT below (a) by more than that"}')
+    legs = {'(c) resident resized frame, replay': (region_ms, lambda: plain(small_dev), args.reps),
+            '(d) resident camera frame, replay with the resize': (region_ms, lambda: resizing(cam_dev), args.reps)}
+    med, spread = interleaved(lines, '(c) / (d) resident input, replay only; device events, ms per frame', legs, args.rounds, warmup=10)
     keys = list(legs)
     lines.append(f'  (d) - (c) = {med[keys[1]] - med[keys[0]]:+.4f} ms: the resize inside a replay  (sum of the two spreads: '
                  f'{spread[keys[0]] + spread[keys[1]]:.4f})')
@@ -162,11 +107,7 @@ def main():
     launches_us(lambda: HF.image_ingest(small_dev, norm, out=out_f), lines, 'image_ingest 1024x512', 15 * h * w / 1e6)
     lines.append('  note: launches inside ONE replayed graph reading and writing the same buffers again and again -- they stay in the 256 MB '
                  'last-level cache; the cost inside a frame is (d) - (c)')
-    text = '\n'.join(lines)
-    print(text)
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, 'w') as f:
-        f.write(text + '\n')
+    write_report(lines, args.out)
     assert same, 'the resize inside the graph disagrees with the resized frame'
     assert pillow_same is not False, 'the device resize disagrees with Pillow'
 

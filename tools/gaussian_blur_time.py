@@ -16,73 +16,11 @@ With ``--parent-tree`` (a checkout of the parent commit, built): ``python bench.
 this one, as fresh child processes, alternating, ``--bench-rounds`` times each; both values go into the same file.
 The device's bytes must equal the CPU implementation's and -- with Pillow -- Pillow's (asserted)."""
 import argparse
-import json
 import os
-import statistics
-import subprocess
-import sys
-import time
 
 import torch
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-if REPO not in sys.path:
-    sys.path.insert(0, REPO)
-
-
-def region_ms(fn, reps):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    torch.cuda.synchronize()
-    e0.record()
-    for _ in range(reps):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / reps
-
-
-def host_ms(fn, reps):
-    t0 = time.perf_counter()
-    for _ in range(reps):
-        fn()
-    return 1e3 * (time.perf_counter() - t0) / reps
-
-
-class Lines(list):
-    """The report: every line is printed as it is added, so a long run shows where it is."""
-
-    def append(self, line):
-        print(line, flush=True)
-        super().append(line)
-
-
-def report(lines, title, samples):
-    med = {}
-    lines.append(title)
-    for k, s in samples.items():
-        med[k] = statistics.median(s)
-        lines.append(f'  {k:62s} median {med[k]:.4f}  min {min(s):.4f}  max {max(s):.4f}  spread {max(s) - min(s):.4f}   samples ' +
-                     ' '.join(f'{v:.4f}' for v in s))
-    return med, {k: max(s) - min(s) for k, s in samples.items()}
-
-
-def interleaved(lines, title, variants, rounds, warmup=3):
-    """variants: name -> (timer, fn, reps)."""
-    for _, fn, _ in variants.values():
-        for _ in range(warmup):
-            fn()
-    torch.cuda.synchronize()
-    samples = {k: [] for k in variants}
-    for _ in range(rounds):
-        for k, (timer, fn, reps) in variants.items():
-            samples[k].append(timer(fn, reps))
-    return report(lines, title, samples)
-
-
-def bench_value(tree):
-    out = subprocess.run([sys.executable, 'bench.py', '--gpus', '1', '--steps', '200', '--warmup', '20'], cwd=tree, capture_output=True,
-                         text=True, timeout=300, check=True).stdout
-    return float(json.loads([ln for ln in out.splitlines() if ln.startswith('{')][-1])['value'])
+from _measure import REPO, Lines, compare_bench, exceeds, graph_of, host_ms, interleaved, per_launch, region_ms, require_gpu, write_report
 
 
 def main():
@@ -93,8 +31,7 @@ def main():
     ap.add_argument('--bench-rounds', type=int, default=3)
     ap.add_argument('--out', default=os.path.join(REPO, 'profiles', 'gaussian_blur_time.txt'))
     args = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit('gaussian_blur_time.py measures on the GPU: no device found')
+    require_gpu('gaussian_blur_time.py')
     try:
         import numpy as np
         from PIL import Image, ImageFilter
@@ -133,14 +70,7 @@ def main():
 
     launches = 50
     call = lambda: HF.gaussian_blur(crops_dev, None, 'hwc', norm=norm, out=out_f, table=table, status=status)
-    for _ in range(3):
-        call()
-    torch.cuda.synchronize()
-    graph = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(graph):
-        for _ in range(launches):
-            call()
-    graph.replay()
+    graph = graph_of(call, launches, warm=3)
     legs = {}
     if Image is not None:
         arrays = [c.numpy() for c in crops]
@@ -149,12 +79,12 @@ def main():
     else:
         lines.append('(a) SKIPPED: Pillow is not installed on this machine')
     key_b = f'(b) device gaussian_blur -> float32, per batch of {b} (graph of {launches})'
-    legs[key_b] = (lambda fn, reps: region_ms(fn, reps) / launches, graph.replay, args.reps)
-    med, spread = interleaved(lines, '(a) host clock / (b) device events; ms', legs, args.rounds)
+    legs[key_b] = (per_launch(launches), graph.replay, args.reps)
+    med, spread = interleaved(lines, '(a) host clock / (b) device events; ms', legs, args.rounds, warmup=3)
     beats = None
     if Image is not None:
         key_a = f'(a) host Pillow, 1 thread, per batch of {b}'
-        beats = med[key_a] - med[key_b] > spread[key_a] + spread[key_b]
+        beats = exceeds(key_a, key_b, med, spread)
         lines.append(f'  (a) / (b) per batch = {med[key_a] / med[key_b]:.0f}x; (a) - (b) = {med[key_a] - med[key_b]:+.4f} ms, sum of the two spreads '
                      f'{spread[key_a] + spread[key_b]:.4f}: the device route beats the host route by more than that: {beats}')
     mb = b * h * w * (3 + 3 + 3 + 12) / 1e6
@@ -170,31 +100,12 @@ def main():
     aug = lambda blur: device_augment(frames, labels, 0.75, (h, w), (0, 384), False, norm, blur=blur)
     legs = {'(c) device_augment, 16 frames 2048x1024 -> 768x768, no blur': (region_ms, lambda: aug(None), 5),
             '(c) device_augment, the same with blur=': (region_ms, lambda: aug(params), 5)}
-    med, spread = interleaved(lines, '(c) eager launches, device events; ms per batch', legs, args.rounds)
+    med, spread = interleaved(lines, '(c) eager launches, device events; ms per batch', legs, args.rounds, warmup=3)
     keys = list(legs)
     lines.append(f'  with - without = {med[keys[1]] - med[keys[0]]:+.4f} ms per batch (sum of the two spreads {spread[keys[0]] + spread[keys[1]]:.4f})')
 
-    bench_error = None
-    if args.parent_tree:
-        vals = {'parent': [], 'this tree': []}
-        try:
-            for _ in range(args.bench_rounds):
-                vals['parent'].append(bench_value(args.parent_tree))
-                vals['this tree'].append(bench_value(REPO))
-        except (subprocess.SubprocessError, ValueError, IndexError, KeyError) as e:
-            bench_error = e
-        lines.append(f'bench.py --gpus 1 --steps 200 --warmup 20, fresh processes, alternating, {args.bench_rounds} each; frames/s')
-        for k, s in vals.items():
-            if s:
-                lines.append(f'  {k:10s} median {statistics.median(s):.2f}  min {min(s):.2f}  max {max(s):.2f}   samples ' + ' '.join(f'{v:.2f}' for v in s))
-        if bench_error is not None:
-            lines.append(f'  the comparison stopped early: {type(bench_error).__name__}')
-    else:
-        lines.append('bench.py: no --parent-tree given, not compared in this run')
-    text = '\n'.join(lines)
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, 'w') as f:
-        f.write(text + '\n')
+    bench_error = compare_bench(lines, args.parent_tree, args.bench_rounds)
+    write_report(lines, args.out)
     assert cpu_same, 'the device blur disagrees with the CPU implementation'
     assert pillow_same is not False, 'the device blur disagrees with Pillow'
     assert beats is not False, 'the device route does not beat the host route by more than the sum of the two spreads'

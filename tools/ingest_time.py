@@ -13,46 +13,10 @@ All uint8 variants must produce the float route's logits bit for bit (asserted).
 import argparse
 import os
 import statistics
-import sys
-import time
 
 import torch
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-if REPO not in sys.path:
-    sys.path.insert(0, REPO)
-
-
-def region_ms(fn, reps):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    torch.cuda.synchronize()
-    e0.record()
-    for _ in range(reps):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / reps
-
-
-def protocol_ms(fn, reps):
-    total = 0.0
-    for _ in range(reps):
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        fn()
-        torch.cuda.synchronize()
-        total += time.perf_counter() - t0
-    return 1e3 * total / reps
-
-
-def report(lines, title, samples):
-    med = {}
-    lines.append(title)
-    for k, s in samples.items():
-        med[k] = statistics.median(s)
-        lines.append(f'  {k:46s} median {med[k]:.4f}  min {min(s):.4f}  max {max(s):.4f}  spread {max(s) - min(s):.4f}   samples ' +
-                     ' '.join(f'{v:.4f}' for v in s))
-    return med, {k: max(s) - min(s) for k, s in samples.items()}
+from _measure import REPO, Lines, graph_of, interleaved, protocol_ms, region_ms, require_gpu, write_report
 
 
 def main():
@@ -61,8 +25,7 @@ def main():
     ap.add_argument('--reps', type=int, default=200)
     ap.add_argument('--out', default=os.path.join(REPO, 'profiles', 'uint8_ingest_time.txt'))
     args = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit('ingest_time.py measures on the GPU: no device found')
+    require_gpu('ingest_time.py')
     from hyperseg_amd import configs, functional as HF
     from hyperseg_amd.utils.inference import GraphedModel, InputNorm, prepare_for_inference
     from hyperseg_amd.utils.synthetic import fill_by_name
@@ -93,18 +56,11 @@ def main():
                {'float32 route': lambda: served(f32_dev),
                 'uint8 fused stem (hs_stem_dw_u8_fwd)': lambda: served(u8_dev),
                 'uint8 through image_ingest + float route': lambda: served_ingest(u8_dev)})]
-    lines = [f'HyperSeg-M {w}x{h} bs 1, prepared (split GEMM), HIP-graph replay; {args.rounds} interleaved rounds x {args.reps} frames',
-             f'logits of the float route, the fused uint8 stem and the image_ingest route equal: {same}']
+    lines = Lines()
+    lines.append(f'HyperSeg-M {w}x{h} bs 1, prepared (split GEMM), HIP-graph replay; {args.rounds} interleaved rounds x {args.reps} frames')
+    lines.append(f'logits of the float route, the fused uint8 stem and the image_ingest route equal: {same}')
     for title, timer, variants in groups:
-        for fn in variants.values():                                   # every graph and shape warm before anything is timed
-            for _ in range(10):
-                fn()
-        torch.cuda.synchronize()
-        samples = {k: [] for k in variants}
-        for _ in range(args.rounds):
-            for k, fn in variants.items():
-                samples[k].append(timer(fn, args.reps))
-        med, spread = report(lines, title, samples)
+        med, spread = interleaved(lines, title, {k: (timer, fn, args.reps) for k, fn in variants.items()}, args.rounds, warmup=10)
         keys = list(variants)
         for k in keys[1:]:
             lines.append(f'  [{k}] - [{keys[0]}] = {med[k] - med[keys[0]]:+.4f} ms  (spread of the two: {max(spread[k], spread[keys[0]]):.4f})')
@@ -117,14 +73,7 @@ def main():
             shape = (1, hh, ww, 3) if layout == 'hwc' else (1, 3, hh, ww)
             x = torch.randint(0, 256, shape, generator=torch.Generator().manual_seed(2), dtype=torch.uint8).to(dev)
             out = torch.empty(1, 3, hh, ww, device=dev)
-            for _ in range(5):
-                HF.image_ingest(x, nl, out=out)
-            torch.cuda.synchronize()
-            graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(graph):
-                for _ in range(50):
-                    HF.image_ingest(x, nl, out=out)
-            graph.replay()
+            graph = graph_of(lambda: HF.image_ingest(x, nl, out=out), 50, warm=5)
             s = [1e3 * region_ms(graph.replay, 20) / 50 for _ in range(5)]
             us = statistics.median(s)
             mb = 5 * 3 * hh * ww / 1e6
@@ -133,11 +82,7 @@ def main():
     lines.append('  note: these are launches inside ONE replayed graph writing the same output again and again: what the figure shows is the cost of '
                  'a small launch in a graph with its output staying in the 256 MB last-level cache -- neither the HBM roof nor the cost of '
                  'the launch inside a frame, which (b) gives as the difference between the image_ingest route and the float route')
-    text = '\n'.join(lines)
-    print(text)
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, 'w') as f:
-        f.write(text + '\n')
+    write_report(lines, args.out)
     assert same, 'the uint8 routes disagree with the float route'
 
 

@@ -15,46 +15,19 @@ Every device result is compared with ``LabelCodec.encode_cpu`` / the pre-encoded
 checkout of the parent commit, built): ``python bench.py --gpus 1 --steps 200 --warmup 20`` of that tree and of this one, fresh child
 processes, alternating, ``--bench-rounds`` times each."""
 import argparse
-import json
 import os
-import statistics
-import subprocess
-import sys
 import time
 
 import numpy as np
 import torch
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-if REPO not in sys.path:
-    sys.path.insert(0, REPO)
+from _measure import REPO, Lines, compare_bench, exceeds, graph_of, interleaved, per_launch, region_ms, report, require_gpu, write_report
 
 HBM_BYTES_PER_S = 8e12
 CITYSCAPES = [255, 255, 255, 255, 255, 255, 255, 0, 1, 255, 255, 2, 3, 4, 255, 255, 255, 5, 255, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 255, 255,
               16, 17, 18]
 CAMVID = [(128, 128, 128), (128, 0, 0), (192, 192, 128), (128, 64, 128), (0, 0, 192), (128, 128, 0), (192, 128, 128), (64, 64, 128),
           (64, 0, 128), (64, 64, 0), (0, 128, 192), (0, 0, 0)]
-
-
-def region_ms(fn, reps):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    torch.cuda.synchronize()
-    e0.record()
-    for _ in range(reps):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / reps
-
-
-def report(lines, title, samples):
-    med = {}
-    lines.append(title)
-    for k, s in samples.items():
-        med[k] = statistics.median(s)
-        lines.append(f'  {k:78s} median {med[k]:.4f}  min {min(s):.4f}  max {max(s):.4f}  spread {max(s) - min(s):.4f}   samples ' +
-                     ' '.join(f'{v:.4f}' for v in s))
-    return med, {k: max(s) - min(s) for k, s in samples.items()}
 
 
 def cityscapes_lines(target, table):
@@ -70,26 +43,6 @@ def camvid_lines(label_rgb, color_map):
     return label_index
 
 
-def captured(fn, warm=3):
-    side = torch.cuda.Stream()
-    side.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(side):
-        for _ in range(warm):
-            fn()
-    torch.cuda.current_stream().wait_stream(side)
-    torch.cuda.synchronize()
-    graph = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(graph):
-        fn()
-    return graph
-
-
-def bench_value(tree):
-    out = subprocess.run([sys.executable, 'bench.py', '--gpus', '1', '--steps', '200', '--warmup', '20'], cwd=tree, capture_output=True,
-                         text=True, timeout=300, check=True).stdout
-    return float(json.loads([ln for ln in out.splitlines() if ln.startswith('{')][-1])['value'])
-
-
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split('\n')[0])
     ap.add_argument('--rounds', type=int, default=7)
@@ -99,8 +52,7 @@ def main():
     ap.add_argument('--skip-evaluate', action='store_true')
     ap.add_argument('--out', default=os.path.join(REPO, 'profiles', 'label_codec_time.txt'))
     args = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit('label_codec_time.py measures on the GPU: no device found')
+    require_gpu('label_codec_time.py')
     torch.set_num_threads(1)                                       # the host route is a loader thread's
     from hyperseg_amd import LabelCodec, configs, fps
     from hyperseg_amd import functional as HF
@@ -114,8 +66,9 @@ def main():
     ids = torch.randint(0, 34, (b, 1024, 2048), generator=g, dtype=torch.uint8)
     rgb = torch.tensor(CAMVID, dtype=torch.uint8)[torch.randint(0, 12, (b, 720, 960), generator=g)].contiguous()
     rgb[..., 0][torch.rand(b, 720, 960, generator=g) < 0.02] ^= 1              # a few pixels of no class
-    lines = [f'label encoding, batch {b}: Cityscapes id table on 2048x1024 uint8 labels, CamVid colour list (12) on 960x720 RGB labels; '
-             f'{args.rounds} interleaved rounds']
+    lines = Lines()
+    lines.append(f'label encoding, batch {b}: Cityscapes id table on 2048x1024 uint8 labels, CamVid colour list (12) on 960x720 RGB labels; '
+                 f'{args.rounds} interleaved rounds')
 
     # ---- host
     np_table, np_ids, np_rgb = np.array(CITYSCAPES, dtype='uint8'), ids.numpy(), rgb.numpy()
@@ -146,19 +99,11 @@ def main():
     same_c = torch.equal(HF.label_encode(d_rgb, colors, out=o_rgb).cpu(), torch.from_numpy(want_rgb)) and torch.equal(o_rgb.cpu(), colors.encode_cpu(rgb))
     lines.append(f'label_encode equals the numpy lines and encode_cpu, byte for byte: table {same_t}, colours {same_c}')
 
-    def many(fn):
-        def run():
-            for _ in range(launches):
-                fn()
-        return run
-    g_t = captured(many(lambda: HF.label_encode(d_ids, table, out=o_ids)), warm=1)
-    g_c = captured(many(lambda: HF.label_encode(d_rgb, colors, out=o_rgb)), warm=1)
-    enc = {f'label_encode table, per launch (graph of {launches}), device events': [],
-           f'label_encode colours, per launch (graph of {launches}), device events': []}
-    for _ in range(args.rounds):
-        for k, gr in zip(enc, (g_t, g_c)):
-            enc[k].append(region_ms(gr.replay, args.reps) / launches)
-    med, _ = report(lines, 'ms per launch, batch of 16', enc)
+    g_t = graph_of(lambda: HF.label_encode(d_ids, table, out=o_ids), launches, warm=1)
+    g_c = graph_of(lambda: HF.label_encode(d_rgb, colors, out=o_rgb), launches, warm=1)
+    enc = {f'label_encode table, per launch (graph of {launches}), device events': (per_launch(launches), g_t.replay, args.reps),
+           f'label_encode colours, per launch (graph of {launches}), device events': (per_launch(launches), g_c.replay, args.reps)}
+    med, _ = interleaved(lines, 'ms per launch, batch of 16', enc, args.rounds, warmup=0)
     for k, nbytes in zip(enc, (2 * ids.numel(), rgb.numel() + rgb.numel() // 3)):
         rate = nbytes / (med[k] * 1e-3)
         lines.append(f'  {k.split(",")[0]}: {nbytes / 1e6:.1f} MB moved (read once + written once; both fit the 256 MiB last-level cache '
@@ -185,19 +130,16 @@ def main():
     same_a = torch.equal(want[0], got[0]) and torch.equal(want[1], got[1])
     lines.append(f'BatchAugment(label_codec=) equals BatchAugment on pre-encoded labels, image and label, byte for byte: {same_a}')
     outs = [(torch.empty_like(want[0]), torch.empty_like(want[1])) for _ in range(3)]
-    routes = {'(a) BatchAugment.run, pre-encoded labels, graph replay': captured(lambda: plain.run(frames, encoded, out=outs[0])),
-              '(b) BatchAugment.run(label_codec=), raw labels, graph replay': captured(lambda: coded.run(frames, d_ids, out=outs[1])),
-              '(c) label_encode launch + (a), graph replay': captured(lambda: plain.run(frames, HF.label_encode(d_ids, table, out=scratch), out=outs[2]))}
-    aug = {k: [] for k in routes}
-    for _ in range(args.rounds):
-        for k, gr in routes.items():
-            aug[k].append(region_ms(gr.replay, args.reps))
-    med, spread = report(lines, f'ms per batch of 16, {in_hw[1]}x{in_hw[0]} -> {crop[1]}x{crop[0]} bicubic, device events', aug)
+    routes = {'(a) BatchAugment.run, pre-encoded labels, graph replay': lambda: plain.run(frames, encoded, out=outs[0]),
+              '(b) BatchAugment.run(label_codec=), raw labels, graph replay': lambda: coded.run(frames, d_ids, out=outs[1]),
+              '(c) label_encode launch + (a), graph replay': lambda: plain.run(frames, HF.label_encode(d_ids, table, out=scratch), out=outs[2])}
+    med, spread = interleaved(lines, f'ms per batch of 16, {in_hw[1]}x{in_hw[0]} -> {crop[1]}x{crop[0]} bicubic, device events',
+                              {k: (region_ms, graph_of(fn, 1, warm=3).replay, args.reps) for k, fn in routes.items()}, args.rounds, warmup=0)
     ka, kb, kc = routes
     diff, both = med[kb] - med[ka], spread[ka] + spread[kb]
     lines.append(f'  (b) - (a) = {diff:+.4f} ms, sum of the two spreads {both:.4f}: (b) ' +
-                 ('does NOT exceed (a) by more than the sum of the two spreads' if diff <= both else
-                  'EXCEEDS (a) by more than the sum of the two spreads (the codec staged into LDS per 256-pixel workgroup of the label gather)'))
+                 ('EXCEEDS (a) by more than the sum of the two spreads (the codec staged into LDS per 256-pixel workgroup of the label gather)'
+                  if exceeds(kb, ka, med, spread) else 'does NOT exceed (a) by more than the sum of the two spreads'))
     lines.append(f'  (c) - (b) = {med[kc] - med[kb]:+.4f} ms: what encoding inside the label gather saves over a launch in front')
 
     # ---- GraphedModel.evaluate
@@ -234,28 +176,8 @@ def main():
         lines.append(f'  raw - encoded = {med[k1] - med[k0]:+.4f} ms (sum of the two spreads {spread[k0] + spread[k1]:.4f}): the price of the encode '
                      'launch that is not fused into the count')
 
-    bench_error = None
-    if args.parent_tree:
-        vals = {'parent': [], 'this tree': []}
-        try:
-            for _ in range(args.bench_rounds):
-                vals['parent'].append(bench_value(args.parent_tree))
-                vals['this tree'].append(bench_value(REPO))
-        except (subprocess.SubprocessError, ValueError, IndexError, KeyError) as e:
-            bench_error = e
-        lines.append(f'bench.py --gpus 1 --steps 200 --warmup 20, fresh processes, alternating, {args.bench_rounds} each; frames/s')
-        for k, s in vals.items():
-            if s:
-                lines.append(f'  {k:10s} median {statistics.median(s):.2f}  min {min(s):.2f}  max {max(s):.2f}   samples ' + ' '.join(f'{v:.2f}' for v in s))
-        if bench_error is not None:
-            lines.append(f'  the comparison stopped early: {type(bench_error).__name__}')
-    else:
-        lines.append('bench.py: no --parent-tree given, not compared in this run')
-    text = '\n'.join(lines)
-    print(text)
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, 'w') as f:
-        f.write(text + '\n')
+    bench_error = compare_bench(lines, args.parent_tree, args.bench_rounds)
+    write_report(lines, args.out)
     assert same_t and same_c, 'label_encode disagrees with the reference lines'
     assert same_a, 'BatchAugment(label_codec=) disagrees with the pre-encoded route'
     assert same_e, 'evaluate with a raw label disagrees with the encoded one'

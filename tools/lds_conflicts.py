@@ -41,12 +41,6 @@ def cycles(op, addrs, active=None):
     return total, len(groups)
 
 
-def report(name, op, addrs, active=None):
-    c, ideal = cycles(op, addrs, active)
-    print(f'{name:58s} {op:20s} {c:3d} cycles (conflict-free {ideal}) x{c / ideal:.2f}')
-    return c, ideal
-
-
 # ------------------------------------------------------------------------------------------------------------------
 # hs_patch_irc.hip layouts (region RH x 16 pixels, halo (RH + 2) x 18, chunk of 16 hidden channels, 4 waves)
 # ------------------------------------------------------------------------------------------------------------------

@@ -17,26 +17,12 @@ fraction of the HBM roof for 0.5 MB of masks + 1.5 MB of frame read + 1.5 MB of 
 import argparse
 import os
 import statistics
-import sys
 
 import torch
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-if REPO not in sys.path:
-    sys.path.insert(0, REPO)
+from _measure import REPO, Lines, graph_of, interleaved, region_ms, require_gpu, write_report
 
 HBM_ROOF = 8.0e12        # bytes / s
-
-
-def region_ms(fn, reps):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    torch.cuda.synchronize()
-    e0.record()
-    for _ in range(reps):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / reps
 
 
 def stock_overlay(img, seg, color_map_tensor, alpha, ignore_index):
@@ -57,8 +43,7 @@ def main():
     ap.add_argument('--reps', type=int, default=200)
     ap.add_argument('--out', default=os.path.join(REPO, 'profiles', 'overlay_time.txt'))
     args = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit('overlay_time.py measures on the GPU: no device found')
+    require_gpu('overlay_time.py')
     from hyperseg_amd import InputNorm, Overlay, configs, functional as HF
     from hyperseg_amd.utils.inference import GraphedModel, prepare_for_inference
     from hyperseg_amd.utils.synthetic import fill_by_name
@@ -98,7 +83,7 @@ def main():
     def d8():
         keep['d8'] = served.overlay(frames)[1]
 
-    variants = {'a': a, 'b': b, 'c': c, 'd': d, 'a8': a8, 'd8': d8}
+    variants = {'(a)': a, '(b)': b, '(c)': c, '(d)': d, '(a8)': a8, '(d8)': d8}
     for fn in variants.values():                    # every shape and graph warmed before anything is timed
         for _ in range(5):
             fn()
@@ -106,38 +91,22 @@ def main():
     same = torch.equal(keep['b'], keep['c']) and torch.equal(keep['c'], keep['d'])
     masks8 = served(frames).clone()
     same8 = torch.equal(keep['d8'], HF.overlay(masks8, frames, style))
-    samples = {k: [] for k in variants}
-    for _ in range(args.rounds):
-        for k, fn in variants.items():
-            samples[k].append(region_ms(fn, args.reps))
-    lines = [f'HyperSeg-M {w}x{h} bs 1, prepared, HIP-graph replay, resident input; {args.rounds} interleaved rounds x {args.reps} frames, ms per frame',
-             f'overlays of (b), (c), (d) equal: {same};  (d8) equals hs_overlay_fwd on its own masks: {same8}']
-    med = {}
-    for k in variants:
-        s = samples[k]
-        med[k] = statistics.median(s)
-        lines.append(f'({k}) median {med[k]:.4f}  min {min(s):.4f}  max {max(s):.4f}  spread {max(s) - min(s):.4f}   samples ' +
-                     ' '.join(f'{v:.4f}' for v in s))
-    spread = {k: max(v) - min(v) for k, v in samples.items()}
-    lines.append(f'(d) - (a) = {med["d"] - med["a"]:+.4f} ms   (c) - (a) = {med["c"] - med["a"]:+.4f} ms   (b) - (a) = {med["b"] - med["a"]:+.4f} ms   '
-                 f'(d8) - (a8) = {med["d8"] - med["a8"]:+.4f} ms')
-    lines.append(f'(b) - (d) = {med["b"] - med["d"]:.4f} ms vs spread {max(spread["b"], spread["d"]):.4f};  '
-                 f'(b) - (c) = {med["b"] - med["c"]:.4f} ms vs spread {max(spread["b"], spread["c"]):.4f};  '
-                 f'(c) - (d) = {med["c"] - med["d"]:+.4f} ms vs spread {max(spread["c"], spread["d"]):.4f}')
+    lines = Lines()
+    lines.append(f'HyperSeg-M {w}x{h} bs 1, prepared, HIP-graph replay, resident input; {args.rounds} interleaved rounds x {args.reps} frames, ms per frame')
+    lines.append(f'overlays of (b), (c), (d) equal: {same};  (d8) equals hs_overlay_fwd on its own masks: {same8}')
+    med, spread = interleaved(lines, None, {k: (region_ms, fn, args.reps) for k, fn in variants.items()}, args.rounds, warmup=0)
+    lines.append(f'(d) - (a) = {med["(d)"] - med["(a)"]:+.4f} ms   (c) - (a) = {med["(c)"] - med["(a)"]:+.4f} ms   (b) - (a) = {med["(b)"] - med["(a)"]:+.4f} ms   '
+                 f'(d8) - (a8) = {med["(d8)"] - med["(a8)"]:+.4f} ms')
+    lines.append(f'(b) - (d) = {med["(b)"] - med["(d)"]:.4f} ms vs spread {max(spread["(b)"], spread["(d)"]):.4f};  '
+                 f'(b) - (c) = {med["(b)"] - med["(c)"]:.4f} ms vs spread {max(spread["(b)"], spread["(c)"]):.4f};  '
+                 f'(c) - (d) = {med["(c)"] - med["(d)"]:+.4f} ms vs spread {max(spread["(c)"], spread["(d)"]):.4f}')
     # the standalone kernel alone: a graph of 50 launches replayed 20 times per sample
     masks = served(x).clone()
     for layout in ('hwc', 'chw'):
         st = Overlay(style.color_map, layout=layout)
         fr = frames if layout == 'hwc' else frames.permute(0, 3, 1, 2).contiguous()
         out = torch.empty_like(fr)
-        for _ in range(3):
-            HF.overlay(masks, fr, st, out=out)
-        torch.cuda.synchronize()
-        graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph):
-            for _ in range(50):
-                HF.overlay(masks, fr, st, out=out)
-        graph.replay()
+        graph = graph_of(lambda: HF.overlay(masks, fr, st, out=out), 50, warm=3)
         s = [1e3 * region_ms(graph.replay, 20) / 50 for _ in range(5)]
         nbytes = masks.numel() + 2 * fr.numel()
         us = statistics.median(s)
@@ -145,14 +114,10 @@ def main():
                      f'{nbytes / us / 1e6:.2f} TB/s = {100 * nbytes / (us * 1e-6) / HBM_ROOF:.0f} % of the 8 TB/s roof')
     lines.append('note: the launches of that graph rewrite one output from inputs that stay in the 256 MB last-level cache: the figure is the cost of '
                  'this small launch inside a graph, not HBM streaming')
-    text = '\n'.join(lines)
-    print(text)
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, 'w') as f:
-        f.write(text + '\n')
+    write_report(lines, args.out)
     assert same and same8, 'the variants disagree on the overlay'
-    assert med['b'] - med['d'] > max(spread['b'], spread['d']), '(d) is not below (b) by more than the spread'
-    assert med['b'] - med['c'] > max(spread['b'], spread['c']), '(c) is not below (b) by more than the spread'
+    assert med['(b)'] - med['(d)'] > max(spread['(b)'], spread['(d)']), '(d) is not below (b) by more than the spread'
+    assert med['(b)'] - med['(c)'] > max(spread['(b)'], spread['(c)']), '(c) is not below (b) by more than the spread'
 
 
 if __name__ == '__main__':

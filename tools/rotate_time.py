@@ -15,77 +15,11 @@ With ``--parent-tree`` (a checkout of the parent commit, built): ``python bench.
 this one, as fresh child processes, alternating, ``--bench-rounds`` times each; both values go into the same file.
 The device's bytes must equal the CPU implementation's and -- with Pillow -- Pillow's (asserted)."""
 import argparse
-import json
 import os
-import statistics
-import subprocess
-import sys
-import time
 
 import torch
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-if REPO not in sys.path:
-    sys.path.insert(0, REPO)
-
-
-def region_ms(fn, reps):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    torch.cuda.synchronize()
-    e0.record()
-    for _ in range(reps):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / reps
-
-
-def host_ms(fn, reps):
-    t0 = time.perf_counter()
-    for _ in range(reps):
-        fn()
-    return 1e3 * (time.perf_counter() - t0) / reps
-
-
-def report(lines, title, samples):
-    med = {}
-    lines.append(title)
-    for k, s in samples.items():
-        med[k] = statistics.median(s)
-        lines.append(f'  {k:66s} median {med[k]:.4f}  min {min(s):.4f}  max {max(s):.4f}  spread {max(s) - min(s):.4f}   samples ' +
-                     ' '.join(f'{v:.4f}' for v in s))
-    return med, {k: max(s) - min(s) for k, s in samples.items()}
-
-
-def interleaved(lines, title, variants, rounds, warmup=3):
-    """variants: name -> (timer, fn, reps)."""
-    for _, fn, _ in variants.values():
-        for _ in range(warmup):
-            fn()
-    torch.cuda.synchronize()
-    samples = {k: [] for k in variants}
-    for _ in range(rounds):
-        for k, (timer, fn, reps) in variants.items():
-            samples[k].append(timer(fn, reps))
-    return report(lines, title, samples)
-
-
-def graph_of(fn, launches):
-    for _ in range(3):
-        fn()
-    torch.cuda.synchronize()
-    graph = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(graph):
-        for _ in range(launches):
-            fn()
-    graph.replay()
-    return graph
-
-
-def bench_value(tree):
-    out = subprocess.run([sys.executable, 'bench.py', '--gpus', '1', '--steps', '200', '--warmup', '20'], cwd=tree, capture_output=True,
-                         text=True, timeout=300, check=True).stdout
-    return float(json.loads([ln for ln in out.splitlines() if ln.startswith('{')][-1])['value'])
+from _measure import REPO, Lines, compare_bench, graph_of, host_ms, interleaved, per_launch, region_ms, require_gpu, write_report
 
 
 def main():
@@ -96,8 +30,7 @@ def main():
     ap.add_argument('--bench-rounds', type=int, default=3)
     ap.add_argument('--out', default=os.path.join(REPO, 'profiles', 'rotate_time.txt'))
     args = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit('rotate_time.py measures on the GPU: no device found')
+    require_gpu('rotate_time.py')
     try:
         import numpy as np
         from PIL import Image
@@ -130,14 +63,15 @@ def main():
         pillow_same = all(bool((np.asarray(Image.fromarray(frames[i].numpy()).rotate(angles[i], Image.BICUBIC)) == got[i].numpy()).all()) and
                           bool((np.asarray(Image.fromarray(labels[i].numpy()).rotate(angles[i], Image.NEAREST)) == lgot[i].numpy()).all())
                           for i in range(b))
-    lines = [f'RandomRotation(30.) + ConstantPad({pad}), batch {b}, {w}x{h} uint8 hwc frames ({ws}x{hs} scaled by {scale}) and uint8 labels, an angle '
-             f'per sample; {args.rounds} interleaved rounds',
-             f'the device bytes equal the CPU implementation (first 2 samples, frame and label): {cpu_same}',
-             f'the device bytes equal Pillow (all {b} samples, frame and label): {pillow_same if Image is not None else "Pillow is not installed"}']
+    lines = Lines()
+    lines.append(f'RandomRotation(30.) + ConstantPad({pad}), batch {b}, {w}x{h} uint8 hwc frames ({ws}x{hs} scaled by {scale}) and uint8 labels, an angle '
+                 f'per sample; {args.rounds} interleaved rounds')
+    lines.append(f'the device bytes equal the CPU implementation (first 2 samples, frame and label): {cpu_same}')
+    lines.append(f'the device bytes equal Pillow (all {b} samples, frame and label): {pillow_same if Image is not None else "Pillow is not installed"}')
 
     launches = 50
-    g_frame = graph_of(lambda: HF.frame_rotate(frames_dev, None, size=(pad, pad), norm=norm, out=img, table=m), launches)
-    g_label = graph_of(lambda: HF.label_rotate(labels_dev, None, size=(pad, pad), out=lbl, table=f), launches)
+    g_frame = graph_of(lambda: HF.frame_rotate(frames_dev, None, size=(pad, pad), norm=norm, out=img, table=m), launches, warm=3)
+    g_label = graph_of(lambda: HF.label_rotate(labels_dev, None, size=(pad, pad), out=lbl, table=f), launches, warm=3)
     legs = {}
     if Image is not None:
         fa, la = [x.numpy() for x in frames], [t.numpy() for t in labels]
@@ -148,12 +82,11 @@ def main():
         legs[f'(a) host Pillow, 1 thread, frame + label, per batch of {b}'] = (host_ms, lambda: [pillow_rotate(i) for i in range(b)], 1)
     else:
         lines.append('(a) SKIPPED: Pillow is not installed on this machine')
-    per_launch = lambda fn, reps: region_ms(fn, reps) / launches
     key_f = f'(b) device frame_rotate -> padded float32, per launch of {b} (graph of {launches})'
     key_l = f'(b) device label_rotate -> padded int64, per launch of {b} (graph of {launches})'
-    legs[key_f] = (per_launch, g_frame.replay, args.reps)
-    legs[key_l] = (per_launch, g_label.replay, args.reps)
-    med, spread = interleaved(lines, '(a) host clock / (b) device events; ms', legs, args.rounds)
+    legs[key_f] = (per_launch(launches), g_frame.replay, args.reps)
+    legs[key_l] = (per_launch(launches), g_label.replay, args.reps)
+    med, spread = interleaved(lines, '(a) host clock / (b) device events; ms', legs, args.rounds, warmup=3)
     if Image is not None:
         key_a = f'(a) host Pillow, 1 thread, frame + label, per batch of {b}'
         lines.append(f'  (a) / (b, frame + label) per batch = {med[key_a] / (med[key_f] + med[key_l]):.0f}x')
@@ -169,30 +102,10 @@ def main():
     aug = lambda jit: device_augment_voc(src, src_lbl, flips, jit, scale, angles, pad, norm)
     legs = {f'(c) device_augment_voc, {b} frames {ws}x{hs} -> {pad}x{pad}, no jitter': (region_ms, lambda: aug(None), 3),
             '(c) device_augment_voc, the same with jitter=': (region_ms, lambda: aug(params), 3)}
-    interleaved(lines, '(c) eager launches, device events; ms per batch', legs, args.rounds)
+    interleaved(lines, '(c) eager launches, device events; ms per batch', legs, args.rounds, warmup=3)
 
-    bench_error = None
-    if args.parent_tree:
-        vals = {'parent': [], 'this tree': []}
-        try:
-            for _ in range(args.bench_rounds):
-                vals['parent'].append(bench_value(args.parent_tree))
-                vals['this tree'].append(bench_value(REPO))
-        except (subprocess.SubprocessError, ValueError, IndexError, KeyError) as e:
-            bench_error = e
-        lines.append(f'bench.py --gpus 1 --steps 200 --warmup 20, fresh processes, alternating, {args.bench_rounds} each; value')
-        for k, s in vals.items():
-            if s:
-                lines.append(f'  {k:10s} median {statistics.median(s):.2f}  min {min(s):.2f}  max {max(s):.2f}   samples ' + ' '.join(f'{v:.2f}' for v in s))
-        if bench_error is not None:
-            lines.append(f'  the comparison stopped early: {type(bench_error).__name__}')
-    else:
-        lines.append('bench.py: no --parent-tree given, not compared in this run')
-    text = '\n'.join(lines)
-    print(text)
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, 'w') as fh:
-        fh.write(text + '\n')
+    bench_error = compare_bench(lines, args.parent_tree, args.bench_rounds, unit='value')
+    write_report(lines, args.out)
     assert cpu_same, 'the device rotation disagrees with the CPU implementation'
     assert pillow_same is not False, 'the device rotation disagrees with Pillow'
     if bench_error is not None:

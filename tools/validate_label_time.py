@@ -19,38 +19,14 @@ of ``--reps`` batches between two device events; medians with spreads (max - min
 import argparse
 import os
 import statistics
-import sys
 
 import torch
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-if REPO not in sys.path:
-    sys.path.insert(0, REPO)
+from _measure import REPO, Lines, exceeds, interleaved, region_ms, require_gpu, write_report
 
 LABEL = (1024, 2048)
 MODELS = {'m': ('hyperseg-m', (512, 1024)), 's': ('hyperseg-s', (768, 1536))}
 KNOB = 'HS_VALIDATE_2X2X'
-
-
-def region_ms(fn, reps):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    torch.cuda.synchronize()
-    e0.record()
-    for _ in range(reps):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / reps
-
-
-def targets(h, w, n, seed):
-    """Piecewise constant with one ignored rectangle, as label maps are."""
-    g = torch.Generator().manual_seed(seed)
-    t = torch.zeros(1, h, w, dtype=torch.int64)
-    for k in range(6):
-        y0, x0 = int(torch.randint(0, h - 1, (1,), generator=g)), int(torch.randint(0, w - 1, (1,), generator=g))
-        t[:, y0:y0 + h // 2, x0:x0 + w // 3] = 255 if k == 3 else int(torch.randint(0, n, (1,), generator=g))
-    return t
 
 
 class general_form:
@@ -67,12 +43,13 @@ def one_config(tag, weighted, model, n, rounds, reps, lines):
     from hyperseg_amd import functional as HF
     from hyperseg_amd.training import BootstrappedCrossEntropyLoss
     from hyperseg_amd.utils.inference import GraphedModel
+    from _workload import label_targets
     dev = torch.device('cuda:0')
     name, (h, w) = MODELS[tag]
     table = (0.5 + torch.rand(n, generator=torch.Generator().manual_seed(5))).to(dev) if weighted else None
     crit = BootstrappedCrossEntropyLoss(ignore_index=255, weight=table)
     x = torch.rand(1, 3, h, w, generator=torch.Generator().manual_seed(1)).to(dev)
-    tgt = targets(LABEL[0], LABEL[1], n, 2).to(dev)
+    tgt = label_targets(LABEL[0], LABEL[1], n, 2).to(dev)
     has_2x2x = (2 * h, 2 * w) == LABEL
     scorer = GraphedModel(model, masks=True, num_classes=n)
     served = GraphedModel(model, masks=True, num_classes=n, criterion=crit)
@@ -94,11 +71,11 @@ def one_config(tag, weighted, model, n, rounds, reps, lines):
     def d():
         got['d'] = forced.validate(x, tgt)[0]
 
-    legs = {'a': a, 'b': b, 'c': c}
+    legs = {'(a)': a, '(b)': b, '(c)': c}
     if has_2x2x:
         with general_form():                        # the capture fixes the form this graph replays
             d()
-        legs['d'] = d
+        legs['(d)'] = d
     for fn in legs.values():                        # every shape and graph warmed before anything is timed
         for _ in range(3):
             fn()
@@ -115,24 +92,18 @@ def one_config(tag, weighted, model, n, rounds, reps, lines):
         same = same and torch.equal(mat_a, forced.confusion) and float(got['d']) == float(got['c'])
     assert same, f'{name}: the legs disagree'
     assert int(mat_a.sum()) == int((tgt != 255).sum())
-    samples = {k: [] for k in legs}
-    for _ in range(rounds):
-        for k, fn in legs.items():
-            samples[k].append(region_ms(fn, reps))
+    if lines:
+        lines.append('')
     lines.append(f'{name} {w}x{h} bs 1, prepared; int64 labels {LABEL[1]}x{LABEL[0]}; criterion {"weighted (19-entry table)" if weighted else "unweighted"}; '
                  f'{rounds} interleaved rounds x {reps} batches, ms per batch')
     lines.append(f'losses and matrices of the legs equal: {same} (loss {float(got["c"]):.6f})')
-    med, spread = {}, {}
-    for k in legs:
-        s = samples[k]
-        med[k], spread[k] = statistics.median(s), max(s) - min(s)
-        lines.append(f'({k}) median {med[k]:.4f}  min {min(s):.4f}  max {max(s):.4f}  spread {spread[k]:.4f}   samples ' + ' '.join(f'{v:.4f}' for v in s))
-    ok = med['a'] - med['c'] > spread['a'] + spread['c']
-    lines.append(f'(a) - (c) = {med["a"] - med["c"]:+.4f} ms vs spread(a) + spread(c) = {spread["a"] + spread["c"]:.4f}: requirement '
-                 f'{"met" if ok else "NOT met"};  the price of the loss (c) - (b) = {med["c"] - med["b"]:+.4f} ms')
+    med, spread = interleaved(lines, None, {k: (region_ms, fn, reps) for k, fn in legs.items()}, rounds, warmup=0)
+    ok = exceeds('(a)', '(c)', med, spread)
+    lines.append(f'(a) - (c) = {med["(a)"] - med["(c)"]:+.4f} ms vs spread(a) + spread(c) = {spread["(a)"] + spread["(c)"]:.4f}: requirement '
+                 f'{"met" if ok else "NOT met"};  the price of the loss (c) - (b) = {med["(c)"] - med["(b)"]:+.4f} ms')
     if has_2x2x:
-        keep = med['d'] - med['c'] > spread['d'] + spread['c']
-        lines.append(f'(d) - (c) = {med["d"] - med["c"]:+.4f} ms vs spread(c) + spread(d) = {spread["c"] + spread["d"]:.4f}: the 2x o 2x form '
+        keep = exceeds('(d)', '(c)', med, spread)
+        lines.append(f'(d) - (c) = {med["(d)"] - med["(c)"]:+.4f} ms vs spread(c) + spread(d) = {spread["(c)"] + spread["(d)"]:.4f}: the 2x o 2x form '
                      f'{"beats the general form by more than the spreads: keep" if keep else "does not beat the general form by more than the spreads: drop"}')
     # the kernel alone, at this model's last-level size
     hi, wi = h // 2, w // 2
@@ -156,7 +127,6 @@ def one_config(tag, weighted, model, n, rounds, reps, lines):
             timed('upsample2_ce_confusion (general form, forced)')
     else:
         timed('upsample2_ce_confusion (general form)')
-    lines.append('')
     return ok
 
 
@@ -183,16 +153,11 @@ def main():
     ap.add_argument('--models', nargs='+', choices=sorted(MODELS), default=['m', 's'])
     ap.add_argument('--out', default=os.path.join(REPO, 'profiles', 'validate_label_time.txt'))
     args = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit('validate_label_time.py measures on the GPU: no device found')
-    lines, ok = [], True
+    require_gpu('validate_label_time.py')
+    lines, ok = Lines(), True
     for tag in args.models:
         ok = one_model(tag, args.rounds, args.reps, lines) and ok
-    text = '\n'.join(lines)
-    print(text)
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, 'w') as f:
-        f.write(text)
+    write_report(lines, args.out)
     if not ok:
         raise SystemExit('(c) is not below (a) by more than the sum of the two spreads on every configuration')
 

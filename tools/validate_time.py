@@ -17,30 +17,13 @@ Reported: medians, spreads (max - min over the rounds), (d) against (b), and (f)
 agree on loss, masks and matrix; (f) and (g) on the matrix."""
 import argparse
 import os
-import statistics
 import sys
 
 import torch
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-if REPO not in sys.path:
-    sys.path.insert(0, REPO)
+from _measure import REPO, Lines, interleaved, region_ms, require_gpu, write_report
+
 sys.path.insert(0, os.path.join(REPO, 'tests'))
-
-from eval_epilogue_time import region_ms, targets        # noqa: E402  (tools/ is on sys.path: this script's directory)
-
-
-def interleaved(variants, rounds, reps, lines):
-    samples = {k: [] for k in variants}
-    for _ in range(rounds):
-        for k, fn in variants.items():
-            samples[k].append(region_ms(fn, reps))
-    med, spread = {}, {}
-    for k, s in samples.items():
-        med[k], spread[k] = statistics.median(s), max(s) - min(s)
-        lines.append(f'({k}) median {med[k]:.4f}  min {min(s):.4f}  max {max(s):.4f}  spread {spread[k]:.4f}   samples ' +
-                     ' '.join(f'{v:.4f}' for v in s))
-    return med, spread
 
 
 def validation_legs(args, dev, lines):
@@ -49,6 +32,7 @@ def validation_legs(args, dev, lines):
     from hyperseg_amd.training import BootstrappedCrossEntropyLoss
     from hyperseg_amd.utils.inference import GraphedModel, prepare_for_inference
     from hyperseg_amd.utils.synthetic import fill_by_name
+    from _workload import targets
     n, (h, w) = 19, (512, 1024)
     model = fill_by_name(configs.build('hyperseg-m').eval(), seed=0)
     prepare_for_inference(model, fold_bn=False, fused_depthwise=True)
@@ -76,8 +60,8 @@ def validation_legs(args, dev, lines):
     def d():
         got['d'] = served.validate(x, tgt)
 
-    variants = {'a': a, 'b': b, 'c': c, 'd': d}
-    for fn in variants.values():
+    variants = {'(a)': a, '(b)': b, '(c)': c, '(d)': d}
+    for fn in variants.values():                    # the legs are warm before the equality check; interleaved() warms nothing more
         for _ in range(5):
             fn()
     torch.cuda.synchronize()
@@ -88,10 +72,10 @@ def validation_legs(args, dev, lines):
             and all(torch.equal(got[k][0], got['b'][0]) and torch.equal(got[k][1].long(), got['b'][1]) for k in 'cd'))
     lines.append(f'HyperSeg-M {w}x{h} bs 1, prepared; {args.rounds} interleaved rounds x {args.reps} batches, ms per batch')
     lines.append(f'loss, masks and matrix of (b), (c), (d) equal: {same}')
-    med, spread = interleaved(variants, args.rounds, args.reps, lines)
-    lines.append(f'(d) against (b): {med["b"] - med["d"]:+.4f} ms saved ({med["b"] / med["d"]:.2f}x), summed spreads {spread["b"] + spread["d"]:.4f};  '
-                 f'(c) against (b): {med["b"] - med["c"]:+.4f} ms, summed spreads {spread["b"] + spread["c"]:.4f};  '
-                 f'(d) - (a) = {med["d"] - med["a"]:+.4f} ms, summed spreads {spread["d"] + spread["a"]:.4f}')
+    med, spread = interleaved(lines, None, {k: (region_ms, fn, args.reps) for k, fn in variants.items()}, args.rounds, warmup=0)
+    lines.append(f'(d) against (b): {med["(b)"] - med["(d)"]:+.4f} ms saved ({med["(b)"] / med["(d)"]:.2f}x), summed spreads {spread["(b)"] + spread["(d)"]:.4f};  '
+                 f'(c) against (b): {med["(b)"] - med["(c)"]:+.4f} ms, summed spreads {spread["(b)"] + spread["(c)"]:.4f};  '
+                 f'(d) - (a) = {med["(d)"] - med["(a)"]:+.4f} ms, summed spreads {spread["(d)"] + spread["(a)"]:.4f}')
     return same
 
 
@@ -120,7 +104,7 @@ def training_legs(args, dev, lines):
         _, pred = steps['g'].step()
         after.update(target.flatten(), pred.argmax(1).flatten())
 
-    variants = {'e': steps['e'].step, 'f': steps['f'].step, 'g': g}
+    variants = {'(e)': steps['e'].step, '(f)': steps['f'].step, '(g)': g}
     for fn in variants.values():
         for _ in range(5):
             fn()
@@ -131,10 +115,10 @@ def training_legs(args, dev, lines):
     same = torch.equal(crits['f'].score.mat, after.mat)        # the three twins take the same steps: the same predictions
     lines.append(f'config 5 (CamVid-S decoder, 576x576, bs 2), GraphedTrainStep; {args.rounds} interleaved rounds x {args.reps} steps, ms per step')
     lines.append(f'matrix of (f) and (g) equal: {same}')
-    med, spread = interleaved(variants, args.rounds, args.reps, lines)
-    lines.append(f'(f) - (e) = {med["f"] - med["e"]:+.4f} ms, summed spreads {spread["f"] + spread["e"]:.4f};  '
-                 f'(g) - (e) = {med["g"] - med["e"]:+.4f} ms, summed spreads {spread["g"] + spread["e"]:.4f};  '
-                 f'(g) - (f) = {med["g"] - med["f"]:+.4f} ms, summed spreads {spread["g"] + spread["f"]:.4f}')
+    med, spread = interleaved(lines, None, {k: (region_ms, fn, args.reps) for k, fn in variants.items()}, args.rounds, warmup=0)
+    lines.append(f'(f) - (e) = {med["(f)"] - med["(e)"]:+.4f} ms, summed spreads {spread["(f)"] + spread["(e)"]:.4f};  '
+                 f'(g) - (e) = {med["(g)"] - med["(e)"]:+.4f} ms, summed spreads {spread["(g)"] + spread["(e)"]:.4f};  '
+                 f'(g) - (f) = {med["(g)"] - med["(f)"]:+.4f} ms, summed spreads {spread["(g)"] + spread["(f)"]:.4f}')
     return same
 
 
@@ -144,18 +128,13 @@ def main():
     ap.add_argument('--reps', type=int, default=100)
     ap.add_argument('--out', default=os.path.join(REPO, 'profiles', 'validate_time.txt'))
     args = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit('validate_time.py measures on the GPU: no device found')
+    require_gpu('validate_time.py')
     dev = torch.device('cuda:0')
-    lines = []
+    lines = Lines()
     with torch.no_grad():               # GraphedModel replays only where nothing can ask for a gradient
         same_v = validation_legs(args, dev, lines)
     same_t = training_legs(args, dev, lines)
-    text = '\n'.join(lines)
-    print(text)
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, 'w') as f:
-        f.write(text + '\n')
+    write_report(lines, args.out)
     assert same_v and same_t, 'the legs disagree on what they compute'
 
 

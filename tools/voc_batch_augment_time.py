@@ -17,17 +17,11 @@ of the parent commit, built): ``python bench.py --gpus 1 --steps 200 --warmup 20
 alternating, ``--bench-rounds`` times each."""
 import argparse
 import os
-import statistics
-import sys
 
 import torch
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-if REPO not in sys.path:
-    sys.path.insert(0, REPO)
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-
-from batch_augment_time import bench_value, region_ms, report, wall_ms  # noqa: E402
+from _measure import (REPO, Lines, compare_bench, count_launches, exceeds, graph_of, interleaved, per_launch, region_ms, report, require_gpu,
+                      wall_ms, write_report)
 
 COUNTED = ('hs_frame_resize_fwd', 'hs_label_resize_fwd', 'hs_color_jitter_fwd', 'hs_frame_rotate_fwd', 'hs_label_rotate_fwd',
            'hs_resize_tables_ragged_fwd', 'hs_color_jitter_ragged_fwd', 'hs_frame_resize_ragged_fwd', 'hs_label_resize_ragged_fwd',
@@ -35,22 +29,9 @@ COUNTED = ('hs_frame_resize_fwd', 'hs_label_resize_fwd', 'hs_color_jitter_fwd', 
 SUMS_ARG = {'hs_color_jitter_fwd': 6, 'hs_color_jitter_ragged_fwd': 7}
 
 
-def count_launches(lib, fn):
-    """Launches made through the COUNTED library entries while ``fn`` runs: name -> count."""
-    counts, saved = {}, {}
-    for name in COUNTED:
-        saved[name] = real = getattr(lib, name)
-
-        def counting(*a, _real=real, _name=name):
-            counts[_name] = counts.get(_name, 0) + (3 if _name in SUMS_ARG and a[SUMS_ARG[_name]] is not None else 1)
-            return _real(*a)
-        setattr(lib, name, counting)
-    try:
-        fn()
-    finally:
-        for name, real in saved.items():
-            setattr(lib, name, real)
-    return counts
+def launches_of(name, args):
+    """Every entry makes one launch, the jitter entries three when they are given a sums workspace."""
+    return 3 if name in SUMS_ARG and args[SUMS_ARG[name]] is not None else 1
 
 
 def main():
@@ -62,9 +43,7 @@ def main():
     ap.add_argument('--bench-rounds', type=int, default=3)
     ap.add_argument('--out', default=os.path.join(REPO, 'profiles', 'voc_batch_augment_time.txt'))
     args = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit('voc_batch_augment_time.py measures on the GPU: no device found')
-    import subprocess
+    require_gpu('voc_batch_augment_time.py')
     from hyperseg_amd import _hip
     from hyperseg_amd import functional as HF
     from hyperseg_amd.training import BatchAugmentVOC, device_augment_voc, draw_color_jitter
@@ -94,9 +73,10 @@ def main():
     def route_b(p):
         return aug(frames, labels, sizes, *p)
 
-    lines = [f'VOC-SBD HyperSeg-L train chain, batch {b}, a {canvas_hw[1]}x{canvas_hw[0]} uint8 {layout} canvas of 500x375 and 375x500 frames -> '
-             f'{pad}x{pad}, scales uniform in ({lo}, {hi}) and angles in +-30 drawn fresh per batch; {args.rounds} interleaved rounds; '
-             f'ks_max {aug.ks_max}']
+    lines = Lines()
+    lines.append(f'VOC-SBD HyperSeg-L train chain, batch {b}, a {canvas_hw[1]}x{canvas_hw[0]} uint8 {layout} canvas of 500x375 and 375x500 frames -> '
+                 f'{pad}x{pad}, scales uniform in ({lo}, {hi}) and angles in +-30 drawn fresh per batch; {args.rounds} interleaved rounds; '
+                 f'ks_max {aug.ks_max}')
     same, counts_b_all = True, {}
     launches = 50
     for jitter in (False, True):
@@ -107,8 +87,8 @@ def main():
         same = same and eq
         lines.append(f'--- {tag}')
         lines.append(f'(b) equals (a) on every sample, image and label, byte for byte: {eq}; status all zero: {not bool(aug.status.any())}')
-        counts_a = count_launches(_hip.run, lambda: route_a(draw(jitter)))
-        counts_b = count_launches(_hip.run, lambda: route_b(draw(jitter)))
+        counts_a = count_launches(_hip.run, COUNTED, lambda: route_a(draw(jitter)), weight=launches_of)
+        counts_b = count_launches(_hip.run, COUNTED, lambda: route_b(draw(jitter)), weight=launches_of)
         counts_b_all[jitter] = sum(counts_b.values())
         lines.append(f'library launches per batch, (a): {sum(counts_a.values())} {counts_a};  (b): {sum(counts_b.values())} {counts_b}')
 
@@ -140,7 +120,7 @@ def main():
         med, spread = report(lines, f'ms per batch of {b} (draw() itself, host, is inside the fresh-draw legs of both routes)', samples)
         for name, ka, kb in (('wall', keys['aw'], keys['bw']), ('device events', keys['ae'], keys['be'])):
             diff, both = med[ka] - med[kb], spread[ka] + spread[kb]
-            verdict = 'faster than (a) by more than the sum of the two spreads' if diff > both else \
+            verdict = 'faster than (a) by more than the sum of the two spreads' if exceeds(ka, kb, med, spread) else \
                 'NOT faster than (a) by more than the sum of the two spreads'
             lines.append(f'  {name}: (a) / (b) = {med[ka] / med[kb]:.1f}x  ({med[ka]:.3f} -> {med[kb]:.3f} ms); (a) - (b) = {diff:+.4f} ms, sum of the '
                          f'two spreads {both:.4f}: (b) is {verdict}')
@@ -156,19 +136,9 @@ def main():
         'hs_frame_rotate_ragged_fwd': lambda: HF.frame_rotate_ragged(aug._mid, p.rows, t, p.matrices, layout, mid, norm=norm, out=out[0]),
         'hs_label_rotate_ragged_fwd': lambda: HF.label_rotate_ragged(aug._mid_label, p.rows, t, p.fixed, mid, out=out[1]),
     }
-    graphs = {}
-    for name, fn in alone.items():
-        fn()
-        torch.cuda.synchronize()
-        graphs[name] = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graphs[name]):
-            for _ in range(launches):
-                fn()
-    samples = {f'(d) {name}': [] for name in alone}
-    for _ in range(args.rounds):
-        for name in alone:
-            samples[f'(d) {name}'].append(region_ms(graphs[name].replay, args.reps) / launches)
-    med_d, _ = report(lines, f'--- each new launch alone, ms per launch (graph of {launches}), the last drawn parameters (with jitter)', samples)
+    legs = {f'(d) {name}': (per_launch(launches), graph_of(fn, launches, warm=1).replay, args.reps) for name, fn in alone.items()}
+    med_d, _ = interleaved(lines, f'--- each new launch alone, ms per launch (graph of {launches}), the last drawn parameters (with jitter)', legs,
+                           args.rounds, warmup=0)
     lines.append(f'  the longest: {max(med_d, key=med_d.get)}')
 
     before = sum(x.numel() * x.element_size() for v in resample._DEVICE_TABLES.values() for x in v)
@@ -182,28 +152,8 @@ def main():
                  f'{args.growth_batches} more batches of (a) = {(after - before) / 1e3 / args.growth_batches:.0f} KB per batch, never freed;  '
                  f"(b)'s workspace {aug.workspace.numel() * 4 / 1e6:.2f} MB, with its canvases and parameters {held / 1e6:.2f} MB, fixed")
 
-    bench_error = None
-    if args.parent_tree:
-        vals = {'parent': [], 'this tree': []}
-        try:
-            for _ in range(args.bench_rounds):
-                vals['parent'].append(bench_value(args.parent_tree))
-                vals['this tree'].append(bench_value(REPO))
-        except (subprocess.SubprocessError, ValueError, IndexError, KeyError) as e:
-            bench_error = e
-        lines.append(f'bench.py --gpus 1 --steps 200 --warmup 20, fresh processes, alternating, {args.bench_rounds} each; frames/s')
-        for k, s in vals.items():
-            if s:
-                lines.append(f'  {k:10s} median {statistics.median(s):.2f}  min {min(s):.2f}  max {max(s):.2f}   samples ' + ' '.join(f'{v:.2f}' for v in s))
-        if bench_error is not None:
-            lines.append(f'  the comparison stopped early: {type(bench_error).__name__}')
-    else:
-        lines.append('bench.py: no --parent-tree given, not compared in this run')
-    text = '\n'.join(lines)
-    print(text)
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, 'w') as f:
-        f.write(text + '\n')
+    bench_error = compare_bench(lines, args.parent_tree, args.bench_rounds)
+    write_report(lines, args.out)
     assert same, 'BatchAugmentVOC disagrees with device_augment_voc'
     assert counts_b_all == {False: 5, True: 8}, f'BatchAugmentVOC made {counts_b_all} launches, expected 5 without and 8 with jitter'
     if bench_error is not None:

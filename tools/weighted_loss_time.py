@@ -3,7 +3,7 @@
     timeout -k 10 1100 python tools/weighted_loss_time.py [--rounds 7] [--reps 100] [--parent DIR] [--out profiles/weighted_loss_time.txt]
 
 One visit; the legs of each group timed INTERLEAVED (round r times every leg in turn, ``--rounds`` rounds), each sample a region of
-``--reps`` steps between two device events (tools/validate_time.py's protocol).  No threshold is asserted: the numbers are the record.
+``--reps`` steps between two device events (tools/_measure.py's protocol).  No threshold is asserted: the numbers are the record.
 ``training.USE_HIP_CLASS_WEIGHTS = False`` is the same-tree stand-in for the route a weighted criterion took before the weighted
 kernels: F.cross_entropy with the table, stock adjoints, argmax + ConfusionMatrix.update, the composed validation.
 Config 5 (CamVid-S decoder, 576 x 576, batch 2) through GraphedTrainStep, a RANDOM 12-entry table of CamVid's shape (11 weights in
@@ -26,13 +26,9 @@ import sys
 
 import torch
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-if REPO not in sys.path:
-    sys.path.insert(0, REPO)
-sys.path.insert(0, os.path.join(REPO, 'tests'))
+from _measure import REPO, Lines, interleaved, region_ms, require_gpu, verdict, write_report
 
-from eval_epilogue_time import targets                    # noqa: E402  (tools/ is on sys.path: this script's directory)
-from validate_time import interleaved                    # noqa: E402
+sys.path.insert(0, os.path.join(REPO, 'tests'))
 
 
 def table(n, seed, dev):
@@ -49,11 +45,6 @@ class _Autocast(torch.nn.Module):
     def forward(self, x, s):
         with torch.autocast('cuda', dtype=torch.float16):
             return self.d(x, s)
-
-
-def verdict(name, a, b, med, spread):
-    d, s = med[b] - med[a], spread[a] + spread[b]
-    return f'{name} = {d:+.4f} ms, summed spreads {s:.4f}: {"within" if abs(d) <= s else "beyond"}'
 
 
 def training_legs(args, dev, lines, amp):
@@ -78,8 +69,8 @@ def training_legs(args, dev, lines, amp):
                                                    scaler=torch.amp.GradScaler('cuda') if amp else None)
         finally:
             training.USE_HIP_CLASS_WEIGHTS = True
-    variants = {k: v.step for k, v in steps.items()}
-    for fn in variants.values():
+    variants = {f'({k})': v.step for k, v in steps.items()}
+    for fn in variants.values():                    # the legs are warm before the agreement check; interleaved() warms nothing more
         for _ in range(5):
             fn()
     torch.cuda.synchronize()
@@ -89,8 +80,8 @@ def training_legs(args, dev, lines, amp):
                  f'{args.rounds} interleaved rounds x {args.reps} steps, ms per step; the loss after the warm-up: ' +
                  ', '.join(f'({k}) loss {float(v.loss):.6f}' for k, v in steps.items()))
     lines.append(f'(w) and (s) agree on the loss (1e-3 relative) and on the pixels counted: {same}')
-    med, spread = interleaved(variants, args.rounds, args.reps, lines)
-    lines.append(verdict('(w) - (u)', 'u', 'w', med, spread) + ';  ' + verdict('(s) - (w)', 'w', 's', med, spread))
+    med, spread = interleaved(lines, None, {k: (region_ms, fn, args.reps) for k, fn in variants.items()}, args.rounds, warmup=0)
+    lines.append(verdict('(w) - (u)', '(u)', '(w)', med, spread) + ';  ' + verdict('(s) - (w)', '(w)', '(s)', med, spread))
     return same
 
 
@@ -98,6 +89,7 @@ def validation_legs(args, dev, lines):
     from hyperseg_amd import configs, training
     from hyperseg_amd.utils.inference import GraphedModel, prepare_for_inference
     from hyperseg_amd.utils.synthetic import fill_by_name
+    from _workload import targets
     n, (h, w) = 19, (512, 1024)
     model = fill_by_name(configs.build('hyperseg-m').eval(), seed=0)
     prepare_for_inference(model, fold_bn=False, fused_depthwise=True)
@@ -125,7 +117,7 @@ def validation_legs(args, dev, lines):
         finally:
             training.USE_HIP_CLASS_WEIGHTS = True
 
-    variants = {'vu': vu, 'vw': vw, 'vs': vs}
+    variants = {'(vu)': vu, '(vw)': vw, '(vs)': vs}
     for fn in variants.values():
         for _ in range(5):
             fn()
@@ -139,9 +131,9 @@ def validation_legs(args, dev, lines):
     graphs = sum(1 for k in served_s._graphs if k[0] == 'validate')
     lines.append(f'HyperSeg-M {w}x{h} bs 1, prepared, GraphedModel.validate; {args.rounds} interleaved rounds x {args.reps} batches, ms per batch')
     lines.append(f'loss {lw:.7f} / {ls:.7f} (1e-5 relative), masks and matrix of (vw) and (vs) agree: {same}; validate graphs of the switched-off wrapper: {graphs}')
-    med, spread = interleaved(variants, args.rounds, args.reps, lines)
-    lines.append(verdict('(vw) - (vu)', 'vu', 'vw', med, spread) + ';  ' + verdict('(vs) - (vw)', 'vw', 'vs', med, spread) +
-                 f' ({med["vs"] / med["vw"]:.2f}x)')
+    med, spread = interleaved(lines, None, {k: (region_ms, fn, args.reps) for k, fn in variants.items()}, args.rounds, warmup=0)
+    lines.append(verdict('(vw) - (vu)', '(vu)', '(vw)', med, spread) + ';  ' + verdict('(vs) - (vw)', '(vw)', '(vs)', med, spread) +
+                 f' ({med["(vs)"] / med["(vw)"]:.2f}x)')
     return same and graphs == 0
 
 
@@ -173,24 +165,18 @@ def main():
     ap.add_argument('--parent', default=None, help='a built checkout of the parent commit: bench.py is then run in both trees')
     ap.add_argument('--out', default=os.path.join(REPO, 'profiles', 'weighted_loss_time.txt'))
     args = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit('weighted_loss_time.py measures on the GPU: no device found')
+    require_gpu('weighted_loss_time.py')
     dev = torch.device('cuda:0')
-    lines = []
+    lines = Lines()
     ok = training_legs(args, dev, lines, amp=False)
     ok = training_legs(args, dev, lines, amp=True) and ok
     with torch.no_grad():               # GraphedModel replays only where nothing can ask for a gradient
         ok = validation_legs(args, dev, lines) and ok
-    text = '\n'.join(lines)
-    print(text, flush=True)
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, 'w') as f:
-        f.write(text + '\n')
+    write_report(lines, args.out)
     if args.parent:
         torch.cuda.empty_cache()
-        bench_lines = []
+        bench_lines = Lines()
         bench_legs(args, bench_lines)
-        print('\n'.join(bench_lines), flush=True)
         with open(args.out, 'a') as f:
             f.write('\n'.join(bench_lines) + '\n')
     assert ok, 'the legs disagree on what they compute'
