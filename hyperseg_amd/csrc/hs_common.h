@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <atomic>
+#include <type_traits>
 #include "hyperseg_hip.h"
 
 namespace hs {
@@ -146,6 +147,12 @@ template <bool W> __device__ __forceinline__ float weighted(float w, float u) {
     if constexpr (W) return w * u;
     else return u;
 }
+
+// `p` is a multiple of `a` bytes (`a`: a power of two), on either side
+__host__ __device__ __forceinline__ bool aligned_to(const void* p, size_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
+// what the typed pointer that a dispatcher hands to its f points at: `using T = pointee<decltype(p)>;` (with_target: hs_eval_count.h,
+// with_conf: hs_confidence.hip)
+template <typename P> using pointee = std::remove_cv_t<std::remove_pointer_t<P>>;
 
 // Host side: the ONE place an HS_DTYPE_* code picks a kernel instantiation.  with_storage calls f with a value of the code's storage type
 // (the launch is written once: `using T = decltype(tag);` ... kernel<T>, (const T*)x, (T*)y) and returns true; for any other code it calls

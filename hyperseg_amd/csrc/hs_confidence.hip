@@ -15,7 +15,6 @@
 // on another workgroup, nothing is read back by the host.
 #include <hip/hip_runtime.h>
 #include <cstdint>
-#include <type_traits>
 #include "hyperseg_hip.h"
 #include "hs_common.h"
 #include "hs_upsample_taps.h"
@@ -83,8 +82,6 @@ __device__ __forceinline__ void confidence_row4(const Scores& scores, int C, boo
     }
 }
 
-__device__ __forceinline__ bool conf_aligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
-
 // Pixels pix .. pix + live - 1 (1 <= live <= 4) of image-major (B, Ho, Wo) outputs: mask and confidence.  OUT: float | uint8_t.
 template <typename OUT>
 __device__ __forceinline__ void confidence_store4(const Conf (&st)[4], int live, uint8_t* __restrict__ mdst, OUT* __restrict__ cdst,
@@ -96,19 +93,19 @@ __device__ __forceinline__ void confidence_store4(const Conf (&st)[4], int live,
         conf[i] = confidence_value(st[i]);
         lab[i] = confidence_label(st[i].idx, conf[i], threshold, fill);
     }
-    if (live == 4 && conf_aligned(mdst, 4)) {
+    if (live == 4 && aligned_to(mdst, 4)) {
         *reinterpret_cast<uchar4*>(mdst) = make_uchar4(lab[0], lab[1], lab[2], lab[3]);
     } else {
         for (int i = 0; i < live; ++i) mdst[i] = lab[i];
     }
     if constexpr (sizeof(OUT) == 4) {
-        if (live == 4 && conf_aligned(cdst, 16)) {
+        if (live == 4 && aligned_to(cdst, 16)) {
             *reinterpret_cast<float4*>(cdst) = make_float4(conf[0], conf[1], conf[2], conf[3]);
         } else {
             for (int i = 0; i < live; ++i) cdst[i] = conf[i];
         }
     } else {
-        if (live == 4 && conf_aligned(cdst, 4)) {
+        if (live == 4 && aligned_to(cdst, 4)) {
             *reinterpret_cast<uchar4*>(cdst) = make_uchar4(confidence_u8(conf[0]), confidence_u8(conf[1]), confidence_u8(conf[2]), confidence_u8(conf[3]));
         } else {
             for (int i = 0; i < live; ++i) cdst[i] = confidence_u8(conf[i]);
@@ -190,8 +187,7 @@ static int confidence_args(const void* x, int batch, int channels, int H0, int W
     return HS_OK;
 }
 
-// calls f with `conf` as a pointer of its storage type (`using OUT = pointee_t<decltype(c)>;`)
-template <typename P> using pointee_t = std::remove_pointer_t<P>;
+// calls f with `conf` as a pointer of its storage type (`using OUT = pointee<decltype(c)>;`)
 template <typename F> __attribute__((always_inline)) inline void with_conf(int conf_dtype, void* conf, F&& f) {
     if (conf_dtype == HS_CONF_F32) f((float*)conf); else f((uint8_t*)conf);
 }
@@ -207,7 +203,7 @@ extern "C" int hs_confidence_fwd(const float* logits, int32_t batch, int32_t cha
     if (st != HS_OK) return st;
     const int vec = (W & 3) == 0 && (reinterpret_cast<uintptr_t>(logits) & 15) == 0;
     with_conf(conf_dtype, conf, [&](auto c) {
-        hipLaunchKernelGGL(confidence_kernel<pointee_t<decltype(c)>>, dim3(blocks), dim3(CONF_THREADS), 0, (hipStream_t)stream, logits, batch,
+        hipLaunchKernelGGL(confidence_kernel<pointee<decltype(c)>>, dim3(blocks), dim3(CONF_THREADS), 0, (hipStream_t)stream, logits, batch,
                            channels, H, W, vec, threshold, fill, mask, c);
     });
     return launch_status();
@@ -220,7 +216,7 @@ extern "C" int hs_upsample_confidence_fwd(const float* x, int32_t batch, int32_t
     if (st != HS_OK) return st;
     const int exact = is_exact2x(Hi, Wi, Ho, Wo);
     with_conf(conf_dtype, conf, [&](auto c) {
-        hipLaunchKernelGGL(upsample_confidence_kernel<pointee_t<decltype(c)>>, dim3(blocks), dim3(CONF_THREADS), 0, (hipStream_t)stream, x, batch,
+        hipLaunchKernelGGL(upsample_confidence_kernel<pointee<decltype(c)>>, dim3(blocks), dim3(CONF_THREADS), 0, (hipStream_t)stream, x, batch,
                            channels, Hi, Wi, Ho, Wo, exact, (float)Hi / (float)Ho, (float)Wi / (float)Wo, threshold, fill, mask, c);
     });
     return launch_status();
@@ -234,7 +230,7 @@ extern "C" int hs_upsample2_confidence_fwd(const float* x, int32_t batch, int32_
     if (st != HS_OK) return st;
     const Stages2 s = stages2(Hi, Wi, Hm, Wm, Ho, Wo);
     with_conf(conf_dtype, conf, [&](auto c) {
-        hipLaunchKernelGGL(upsample2_confidence_kernel<pointee_t<decltype(c)>>, dim3(blocks), dim3(CONF_THREADS), 0, (hipStream_t)stream, x, batch,
+        hipLaunchKernelGGL(upsample2_confidence_kernel<pointee<decltype(c)>>, dim3(blocks), dim3(CONF_THREADS), 0, (hipStream_t)stream, x, batch,
                            channels, s, threshold, fill, mask, c);
     });
     return launch_status();

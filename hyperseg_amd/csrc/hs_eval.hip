@@ -12,6 +12,8 @@
 //   * across workgroups the whole matrix is a few cache lines, so each workgroup flushes once, at its end: non-zero bins only,
 //     consecutive lanes on consecutive bins, one 64-bit global atomic add each (global_atomic_add_x2, no compare-and-swap).
 // No cross-workgroup waiting of any kind.
+// Which item a thread works on in a pass of its grid-stride loop -- item_rows4 / item_quad, surplus lanes shadowing the last item -- is
+// stated once for these kernels and hs_validate.hip's (hs_last_launch.h); the loads, stores and counting tails stay written out here.
 // Host side: the entries at the end of the file share one launch front with hs_validate.hip's (hs_eval_count.h: histogram operands,
 // target-type dispatcher, grids, shape check; Stages2's constructor: hs_upsample_taps.h); refusal order and `vec` stay each entry's own.
 #include <hip/hip_runtime.h>
@@ -38,10 +40,9 @@ void upsample_confusion_kernel(const float* __restrict__ x, int C, int Hi, int W
     const int items = Ho * wq;
     const float* __restrict__ xb = x + b * C * Hi * Wi;
     for (int base = blockIdx.x * EVAL_THREADS; base < items; base += gridDim.x * EVAL_THREADS) {      // wave-uniform trip count
-        const int e0 = base + (int)threadIdx.x;
-        const bool live = e0 < items;
-        const int e = live ? e0 : items - 1;
-        const int q = e % wq, yo = e / wq;
+        const Item it = item_rows4(base, items, wq);
+        const bool live = it.live;
+        const int q = it.q, yo = it.y;
         const Row4 t = row4_taps(yo, q, Hi, Wi, Wo, scale_y, scale_x);
         int idx[4];
         argmax_row4(xb, C, Hi, Wi, t, idx);
@@ -82,10 +83,9 @@ void upsample2x_confusion_kernel(const float* __restrict__ x, int C, int Hi, int
     const int sub = (int)(threadIdx.x & 3);
     const float* __restrict__ xb = x + b * C * Hi * Wi;
     for (int base = blockIdx.x * (EVAL_THREADS / 4); base < items; base += gridDim.x * (EVAL_THREADS / 4)) {
-        const int e0 = base + (int)(threadIdx.x >> 2);
-        const bool live = e0 < items;
-        const int e = live ? e0 : items - 1;                    // surplus lanes shadow the last block (argmax2x_block: convergent)
-        const int q = e % wq, yi = e / wq;
+        const Item it = item_quad(base, items, wq);             // (argmax2x_block: convergent)
+        const bool live = it.live;
+        const int q = it.q, yi = it.y;
         int idx0[4], idx1[4];
         argmax2x_block(xb, C, Hi, Wi, yi, q, sub, idx0, idx1);
         const size_t at = (b * 2 * Hi + 2 * yi) * Wo + 4 * q;
@@ -124,10 +124,9 @@ void upsample2_confusion_kernel(const float* __restrict__ x, int C, Stages2 s, c
     const int items = Ho * wq;
     const float* __restrict__ xb = x + b * C * s.Hi * s.Wi;
     for (int base = blockIdx.x * EVAL_THREADS; base < items; base += gridDim.x * EVAL_THREADS) {      // wave-uniform trip count
-        const int e0 = base + (int)threadIdx.x;
-        const bool live = e0 < items;
-        const int e = live ? e0 : items - 1;
-        const int q = e % wq, yo = e / wq;
+        const Item it = item_rows4(base, items, wq);
+        const bool live = it.live;
+        const int q = it.q, yo = it.y;
         const Row4x2 t = row4x2_taps(yo, q, s);
         int idx[4];
         argmax2_row4(xb, C, s.Hi, s.Wi, t, idx);
@@ -172,10 +171,9 @@ void upsample2x2x_confusion_kernel(const float* __restrict__ x, int C, int Hi, i
     const int sub = (int)(threadIdx.x & 3);
     const float* __restrict__ xb = x + b * C * Hi * Wi;
     for (int base = blockIdx.x * (EVAL_THREADS / 4); base < items; base += gridDim.x * (EVAL_THREADS / 4)) {
-        const int e0 = base + (int)(threadIdx.x >> 2);
-        const bool live = e0 < items;
-        const int e = live ? e0 : items - 1;                    // surplus lanes shadow the last block (argmax2x2x_block: convergent)
-        const int q = e % wq, yi = e / wq;
+        const Item it = item_quad(base, items, wq);             // (argmax2x2x_block: convergent)
+        const bool live = it.live;
+        const int q = it.q, yi = it.y;
         int idx[4][8];
         argmax2x2x_block(xb, C, Hi, Wi, yi, q, sub, idx);
         int p[8];

@@ -1,11 +1,12 @@
 // Counting core of the on-device evaluation kernels (hs_eval.hip, hs_validate.hip): the per-workgroup n x n LDS histogram, the wave's
-// ballot aggregation into it, its one flush per workgroup, the label loads and the grid cap.  Shape and reasons: hs_eval.hip's header.
+// ballot aggregation into it, its one flush per workgroup, the label loads and the grid cap.  Shape and reasons: hs_eval.hip's header; which
+// item a thread of those kernels works on: hs_last_launch.h.
 // Below the device code, the host front of their entries: histogram operands, target-type dispatcher, grids and the shape check.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
-#include <type_traits>
 #include "hs_common.h"
+#include "hs_last_launch.h"
 
 namespace hs {
 
@@ -81,7 +82,6 @@ static unsigned eval_grid_x(long passes, int batch) {
     return (unsigned)(per_image < 1 ? 1 : per_image);
 }
 static bool eval_storage_ok(int dtype) { return dtype == HS_EVAL_U8 || dtype == HS_EVAL_I64; }
-static bool aligned_to(const void* p, size_t a) { return ((uintptr_t)p % a) == 0; }
 
 // ---- The launch front the scoring entries share.  Host code only.  Each entry keeps its own `vec` predicate and its own
 // order of refusals; what it takes from here is how the operands of a launch are made once the call is accepted.
@@ -96,7 +96,6 @@ static Hist eval_hist(int num_classes, int per_image, int64_t* confusion) {
 // The ONE place an HS_EVAL_* code picks a kernel instantiation, as with_storage (hs_common.h) is for HS_DTYPE_*: calls f with `p` as a typed
 // pointer (`using TT = pointee<decltype(t)>;` ... kernel<TT>, t) and returns true; for any other code it calls nothing and returns false (the
 // entries refuse such a code with eval_storage_ok, at the place in their order where they always did).
-template <typename P> using pointee = std::remove_cv_t<std::remove_pointer_t<P>>;
 template <typename F> __attribute__((always_inline)) inline bool with_target(int dtype, const void* p, F&& f) {
     if (dtype == HS_EVAL_U8) { f((const uint8_t*)p); return true; }
     if (dtype == HS_EVAL_I64) { f((const int64_t*)p); return true; }

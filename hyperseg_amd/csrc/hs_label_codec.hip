@@ -25,8 +25,6 @@ constexpr int LE_THREADS = 256;
 using le_u32x4 = __attribute__((ext_vector_type(4))) uint32_t;
 using le_i64x2 = __attribute__((ext_vector_type(2))) long long;
 
-__device__ __forceinline__ bool aligned_to(const void* p, uintptr_t bytes) { return (reinterpret_cast<uintptr_t>(p) & (bytes - 1)) == 0; }
-
 // N results (a multiple of 4) to consecutive labels
 template <int N>
 __device__ __forceinline__ void store_run(uint8_t* __restrict__ dst, const int (&v)[N]) {

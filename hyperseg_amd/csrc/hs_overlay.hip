@@ -41,8 +41,6 @@ __device__ __forceinline__ unsigned overlay_value(const float* __restrict__ tab,
     return (unsigned)rintf((t * 0.5f + 0.5f) * 255.0f);
 }
 
-__device__ __forceinline__ bool aligned4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3) == 0; }
-
 // Pixels pix .. pix + n - 1 (1 <= n <= 4, one row) of the frame at `fb` blended into the overlay at `ob` (both: image b's first byte),
 // `plane` = H * W, cls: their class indices.
 template <bool HWC>
@@ -54,7 +52,7 @@ __device__ __forceinline__ void overlay_row4(const float* __restrict__ tab, cons
     if constexpr (HWC) {
         const uint8_t* __restrict__ p = fb + pix * 3;
         uint8_t* __restrict__ d = ob + pix * 3;
-        if (n == 4 && aligned4(p) && aligned4(d)) {
+        if (n == 4 && aligned_to(p, 4) && aligned_to(d, 4)) {
             // r0 g0 b0 r1 | g1 b1 r2 g2 | b2 r3 g3 b3: byte j is channel j % 3 of pixel j / 3
             unsigned w[3], o[3] = {0u, 0u, 0u};
 #pragma unroll
@@ -76,7 +74,7 @@ __device__ __forceinline__ void overlay_row4(const float* __restrict__ tab, cons
         for (int c = 0; c < 3; ++c) {
             const uint8_t* __restrict__ p = fb + c * plane + pix;
             uint8_t* __restrict__ d = ob + c * plane + pix;
-            if (n == 4 && aligned4(p) && aligned4(d)) {
+            if (n == 4 && aligned_to(p, 4) && aligned_to(d, 4)) {
                 const unsigned w = *reinterpret_cast<const unsigned*>(p);
                 unsigned o = 0u;
 #pragma unroll
@@ -105,7 +103,7 @@ void overlay_kernel(const uint8_t* __restrict__ mask, const uint8_t* __restrict_
         const size_t pix = (size_t)yy * W + x0;
         const uint8_t* __restrict__ mp = mask + b * plane + pix;
         int cls[4];
-        if (n == 4 && aligned4(mp)) {
+        if (n == 4 && aligned_to(mp, 4)) {
             const unsigned w = *reinterpret_cast<const unsigned*>(mp);
 #pragma unroll
             for (int i = 0; i < 4; ++i) cls[i] = (int)((w >> (8 * i)) & 255u);
@@ -178,7 +176,7 @@ void upsample_overlay_kernel(const float* __restrict__ x, int B, int C, int Hi, 
     const size_t plane = (size_t)Ho * Wo, pix = (size_t)yo * Wo + 4 * q;
     const int live = min(4, Wo - 4 * q);
     uint8_t* dst = mask + b * plane + pix;
-    if (live == 4 && aligned4(dst)) {
+    if (live == 4 && aligned_to(dst, 4)) {
         *reinterpret_cast<uchar4*>(dst) = make_uchar4(idx[0], idx[1], idx[2], idx[3]);
     } else {
         for (int i = 0; i < live; ++i) dst[i] = (uint8_t)idx[i];

@@ -14,6 +14,7 @@
 // the loss launch's workgroup per 256 pixels: thousands of workgroups flushing a histogram each meet on a few bins (the note above
 // cross_entropy_kernel: 38.5 us against 17).  No cross-workgroup waiting, no float atomics: the losses are plain stores.
 // confusion == nullptr: nothing is counted (loss and masks only).
+// The item of a thread in a pass of the resizing kernels' loops is hs_eval.hip's: item_rows4 / item_quad (hs_last_launch.h).
 // Host side: three template fronts (one per entry and its weighted twin) over hs_eval.hip's launch front (hs_eval_count.h).
 #include <hip/hip_runtime.h>
 #include <cstdint>
@@ -93,8 +94,13 @@ void ce_score_kernel(const T* __restrict__ x, const long long* __restrict__ targ
 
 // argmax_row4 (hs_upsample_taps.h) handing out the maxima as well: the same loads, the same comparisons, so the same indices.  The
 // strict maximum IS cross_entropy_kernel's fmaxf chain for finite scores (they differ in the sign of a zero maximum at most, which
-// neither expf(v - m) nor logf(sum) + m shows).  Restated here, not factored out of argmax_row4: that changes the register allocation
-// of the kernels built on it.
+// neither expf(v - m) nor logf(sum) + m shows).  Restated here, not factored out of argmax_row4.  Tried once with the three *_best
+// functions moved to hs_upsample_taps.h (argmax_row4_best<UNROLL>) and the index-only forms calling them with a local array for the
+// maxima: this file's 40 kernels and every argmax_row4 kernel came out instruction for instruction as before, but the index-only quad
+// kernels did not (VGPRs / SGPRs, scratch 0 throughout; before -> after): upsample2x_confusion_kernel<u8> 138 / 79 -> 138 / 73,
+// <i64> 136 / 79 -> 138 / 73; upsample2x2x_confusion_kernel<u8> 211 -> 199 VGPRs with 4909 -> 5015 instructions, <i64> 210 -> 199 with
+// 4915 -> 5014; upsample2x_argmax_kernel 120 / 46 -> 120 / 40; upsample2x_overlay_kernel: same registers, 5 instructions fewer.  No
+// occupancy step either way, but not the same figures, so the copies stay (profiles/last_launch_helpers_isa.txt).
 __device__ __forceinline__ void argmax_row4_best(const float* __restrict__ xb, int C, int Hi, int Wi, const Row4& t, int (&idx)[4],
                                                  float (&best)[4]) {
 #pragma unroll
@@ -167,10 +173,9 @@ void upsample_ce_confusion_kernel(const float* __restrict__ x, int C, int Hi, in
     const size_t plane = (size_t)Hi * Wi;
     const float* __restrict__ xb = x + b * C * plane;
     for (int base = blockIdx.x * EVAL_THREADS; base < items; base += gridDim.x * EVAL_THREADS) {      // wave-uniform trip count
-        const int e0 = base + (int)threadIdx.x;
-        const bool live = e0 < items;
-        const int e = live ? e0 : items - 1;
-        const int q = e % wq, yo = e / wq;
+        const Item it = item_rows4(base, items, wq);
+        const bool live = it.live;
+        const int q = it.q, yo = it.y;
         const Row4 t = row4_taps(yo, q, Hi, Wi, Wo, scale_y, scale_x);
         int idx[4];
         float m[4];
@@ -279,10 +284,9 @@ void upsample2_ce_confusion_kernel(const float* __restrict__ x, int C, Stages2 s
     const size_t plane = (size_t)s.Hi * s.Wi;
     const float* __restrict__ xb = x + b * C * plane;
     for (int base = blockIdx.x * EVAL_THREADS; base < items; base += gridDim.x * EVAL_THREADS) {      // wave-uniform trip count
-        const int e0 = base + (int)threadIdx.x;
-        const bool live = e0 < items;
-        const int e = live ? e0 : items - 1;
-        const int q = e % wq, yo = e / wq;
+        const Item it = item_rows4(base, items, wq);
+        const bool live = it.live;
+        const int q = it.q, yo = it.y;
         const Row4x2 t = row4x2_taps(yo, q, s);
         const size_t at = (b * Ho + yo) * Wo + 4 * q;
         TT tv[4];
@@ -371,10 +375,9 @@ void upsample2x_ce_confusion_kernel(const float* __restrict__ x, int C, int Hi, 
     const size_t plane = (size_t)Hi * Wi;
     const float* __restrict__ xb = x + b * C * plane;
     for (int base = blockIdx.x * (EVAL_THREADS / 4); base < items; base += gridDim.x * (EVAL_THREADS / 4)) {
-        const int e0 = base + (int)(threadIdx.x >> 2);
-        const bool live = e0 < items;
-        const int e = live ? e0 : items - 1;                    // surplus lanes shadow the last block (the quad exchanges: convergent)
-        const int q = e % wq, yi = e / wq;
+        const Item it = item_quad(base, items, wq);             // (the quad exchanges: convergent)
+        const bool live = it.live;
+        const int q = it.q, yi = it.y;
         int idx0[4], idx1[4];
         float best0[4], best1[4];
         argmax2x_block_best(xb, C, Hi, Wi, yi, q, sub, idx0, idx1, best0, best1);
@@ -501,10 +504,9 @@ void upsample2x2x_ce_confusion_kernel(const float* __restrict__ x, int C, int Hi
     const size_t plane = (size_t)Hi * Wi;
     const float* __restrict__ xb = x + b * C * plane;
     for (int base = blockIdx.x * (EVAL_THREADS / 4); base < items; base += gridDim.x * (EVAL_THREADS / 4)) {
-        const int e0 = base + (int)(threadIdx.x >> 2);
-        const bool live = e0 < items;
-        const int e = live ? e0 : items - 1;                    // surplus lanes shadow the last block (the quad exchanges: convergent)
-        const int q = e % wq, yi = e / wq;
+        const Item it = item_quad(base, items, wq);             // (the quad exchanges: convergent)
+        const bool live = it.live;
+        const int q = it.q, yi = it.y;
         const bool top = yi == 0, bottom = yi == Hi - 1, left = q == 0, right = 2 * q + 2 >= Wi;
         int p[8];
         float m[8];

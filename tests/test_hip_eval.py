@@ -119,6 +119,38 @@ def test_upsample_confusion_full_size(pattern):
     assert torch.equal(HF.confusion_update(ref_masks, t.to(torch.uint8).to(DEV), 19).cpu(), want)
 
 
+def second_trip_shape(mapping, batch):
+    """(Hi, Wi, Ho, Wo) whose items per image exceed one pass of the scoring grid -- ceil(CUs / batch) workgroups per image of 512
+    items (rows of four) or 128 (quads) -- so the grid-stride loop takes a second trip, with surplus lanes on it.  Rows of four: a general
+    ratio and Wo % 4 == 2; quads: exact 2x."""
+    per_image = -(-torch.cuda.get_device_properties(DEV).multi_processor_count // batch)
+    if mapping == 'quads':
+        wi = 258
+        hi = per_image * 128 // (wi // 2) + 3
+        assert hi * (wi // 2) > per_image * 128
+        return hi, wi, 2 * hi, 2 * wi
+    wo = 518
+    ho = per_image * 512 // ((wo + 3) // 4) + 3
+    assert ho * ((wo + 3) // 4) > per_image * 512
+    return ho // 3 + 1, wo // 3 + 1, ho, wo
+
+
+@pytest.mark.parametrize('tdtype', [torch.int64, torch.uint8])
+@pytest.mark.parametrize('mapping', ['rows4', 'quads'])
+def test_upsample_confusion_second_grid_trip(mapping, tdtype):
+    """Batch 2, C = 5 < n = 21, more items per image than one pass of the grid: masks and matrix as the parts give them."""
+    from hyperseg_amd import functional as HF
+    hi, wi, ho, wo = second_trip_shape(mapping, 2)
+    x = _logits(2, 5, hi, wi, 7300).to(DEV)
+    t = _targets('ignored', 2, ho, wo, 21, 7301, tdtype)
+    ref_masks = HF.upsample_argmax(x, (ho, wo))
+    out, masks = HF.upsample_confusion(x, (ho, wo), t.to(DEV), 21, masks=True)
+    assert torch.equal(masks, ref_masks) and torch.equal(out.cpu(), _stock(t, ref_masks, 21))
+    slabs = HF.upsample_confusion(x, (ho, wo), t.to(DEV), 21, per_image=True)
+    for b in range(2):
+        assert torch.equal(slabs[b].cpu(), _stock(t[b], ref_masks[b], 21))
+
+
 @pytest.mark.parametrize('size', [(32, 48), (25, 37)])
 def test_accumulation_and_per_image(size):
     """Two calls into one ``out`` = the sum; per_image slabs sum to the (n, n) result and slab b equals a call on image b alone."""

@@ -115,6 +115,55 @@ def test_equals_its_parts(k, tdtype, pattern):
         assert not torch.equal(HF.upsample_argmax(x, label), want_masks)
 
 
+# The smallest shapes at which the four geometries of the last launch differ, x (2, C, 4, 6): (mid or None, target size).  C = 5: the quad
+# forms' class split has a tail (c0 + sub < C); C = 21: argmax2x_block's 20-class batch loop takes a second trip.  (7, 10), (9, 13),
+# (14, 22): Wo % 4 != 0, the row tail and the forms without vector loads.
+SMALL = {'2x': (None, (8, 12)), 'general': (None, (7, 10)), 'two-stage-odd': ((8, 12), (9, 13)), 'two-stage-even': ((8, 12), (14, 22)),
+         '2x2x': ((8, 12), (16, 24))}
+
+
+@functools.lru_cache(maxsize=None)
+def _small(geometry, c):
+    """(x, logits at the target's size by upsample_bilinear, their arg-max): computed once per cell and left unchanged."""
+    from hyperseg_amd import functional as HF
+    mid, size = SMALL[geometry]
+    x = _logits(2, c, 4, 6, 8700 + c).to(DEV)
+    up = HF.upsample_bilinear(x, size) if mid is None else HF.upsample_bilinear(HF.upsample_bilinear(x, mid), size)
+    return x, up, up.argmax(1).to(torch.uint8)
+
+
+def _offset_by_one(t):
+    """A copy of ``t`` whose base lies one element into its storage: the forms without vector loads."""
+    o = torch.empty(t.numel() + 1, dtype=t.dtype, device=t.device)[1:].view_as(t).copy_(t)
+    assert o.storage_offset() == 1
+    return o
+
+
+@pytest.mark.parametrize('tdtype', [torch.int64, torch.uint8], ids=['i64', 'u8'])
+@pytest.mark.parametrize('c', [5, 21])
+@pytest.mark.parametrize('geometry', sorted(SMALL))
+def test_small_shapes_every_cell(geometry, c, tdtype):
+    """Confusion sink, every geometry at its smallest shape: target aligned and one element into its storage, with and without the mask
+    output, n = C and n > C, and (two-stage entries) masks alone; masks == arg-max of upsample_bilinear's logits, counts == the stock
+    CPU count."""
+    from hyperseg_amd import functional as HF
+    mid, size = SMALL[geometry]
+    x, _, want_masks = _small(geometry, c)
+    for n in (c, c + 3):
+        t = _targets('ignored', 2, size[0], size[1], n, 8800 + n, tdtype)
+        want = _stock(t, want_masks, n)
+        for td in (t.to(DEV), _offset_by_one(t.to(DEV))):
+            if mid is None:
+                out, masks = HF.upsample_confusion(x, size, td, n, masks=True)
+                bare = HF.upsample_confusion(x, size, td, n)
+            else:
+                out, masks = HF.upsample2_confusion(x, mid, td, n, masks=True)
+                bare = HF.upsample2_confusion(x, mid, td, n)
+            assert torch.equal(masks, want_masks) and torch.equal(out.cpu(), want) and torch.equal(bare.cpu(), want)
+    alone = HF.upsample_argmax(x, size) if mid is None else HF.upsample2_argmax(x, mid, size)
+    assert torch.equal(alone, want_masks)
+
+
 def _quantised(t):
     return (t * 4).round().clamp(-4, 4) / 4
 

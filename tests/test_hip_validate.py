@@ -7,7 +7,7 @@ import pytest
 import torch
 
 from conftest import G
-from test_hip_eval import MODELS, SHAPES, _logits, _model, _model_targets, _stock, _targets
+from test_hip_eval import MODELS, SHAPES, _logits, _model, _model_targets, _stock, _targets, second_trip_shape
 
 pytestmark = pytest.mark.gpu
 DEV = torch.device('cuda:0')
@@ -125,6 +125,21 @@ def test_upsample_ce_confusion_equals_the_composed_route(shape, tdtype):
     assert to.storage_offset() == 1
     loss1, out1, masks1 = HF.upsample_ce_confusion(x, (ho, wo), to, 255, n)
     assert torch.equal(loss1, loss0) and torch.equal(masks1, ref_masks) and torch.equal(out1, want)
+
+
+@pytest.mark.parametrize('tdtype', [torch.int64, torch.uint8])
+@pytest.mark.parametrize('mapping', ['rows4', 'quads'])
+def test_upsample_ce_confusion_second_grid_trip(mapping, tdtype):
+    """Batch 2, C = 5 < n = 21, more items per image than one pass of the grid (test_hip_eval.second_trip_shape): loss, masks and
+    counts as the composed route gives them."""
+    from hyperseg_amd import functional as HF
+    hi, wi, ho, wo = second_trip_shape(mapping, 2)
+    x = _logits(2, 5, hi, wi, 8500).to(DEV)
+    t = _targets('ignored', 2, ho, wo, 21, 8501, tdtype).to(DEV)
+    loss, out, masks = HF.upsample_ce_confusion(x, (ho, wo), t, 255, 21)
+    assert torch.equal(loss, _ce(HF.upsample_bilinear(x, (ho, wo)), t.long(), 255))
+    ref_masks = HF.upsample_argmax(x, (ho, wo))
+    assert torch.equal(masks, ref_masks) and torch.equal(out.cpu(), _stock(t, ref_masks, 21))
 
 
 def test_upsample_ce_confusion_argument_errors():

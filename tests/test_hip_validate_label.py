@@ -14,7 +14,7 @@ import torch
 
 from conftest import G
 from test_hip_eval import MODELS, _model, _stock
-from test_hip_eval_label import MARGIN, MAX_LEFT_OUT, SHAPES, _case, _label_size, _label_targets, _logits, _targets, _tie_logits
+from test_hip_eval_label import MARGIN, MAX_LEFT_OUT, SHAPES, SMALL, _case, _label_size, _label_targets, _logits, _small, _targets, _tie_logits
 from test_hip_validate import _ce, _criterion, _pin_stock_encoder
 
 pytestmark = pytest.mark.gpu
@@ -86,6 +86,33 @@ def test_equals_the_composed_route(k, tdtype, pattern):
     if k == 7:                                                   # identity second stage: upsample_ce_confusion outright
         l7, o7, m7 = HF.upsample_ce_confusion(x, label, td, 255, n)
         assert torch.equal(l7, loss0) and torch.equal(o7, want) and torch.equal(m7, masks0)
+
+
+@pytest.mark.parametrize('tdtype', [torch.int64, torch.uint8], ids=['i64', 'u8'])
+@pytest.mark.parametrize('c', [5, 21])
+@pytest.mark.parametrize('geometry', sorted(SMALL))
+def test_small_shapes_every_cell(geometry, c, tdtype):
+    """Loss sink, every geometry at its smallest shape (tests/test_hip_eval_label.py's SMALL): target aligned and one element into its
+    storage, counted (n = C + 3) and not, weighted and not; loss == PixelCrossEntropy on upsample_bilinear's logits bit for bit, masks
+    == their arg-max, counts == the stock CPU count."""
+    from hyperseg_amd import functional as HF
+    from hyperseg_amd.autograd import PixelCrossEntropy
+    mid, size = SMALL[geometry]
+    x, up, want_masks = _small(geometry, c)
+    n = c + 3
+    t = _targets('ignored', 2, size[0], size[1], c, 9300 + c, tdtype)
+    want = _stock(t, want_masks, n)
+    w = (0.25 + 2.0 * torch.rand(c, generator=G(9310 + c))).to(DEV)
+    for weight in (None, w):
+        want_loss = _ce(up, t.to(DEV).long(), 255) if weight is None else PixelCrossEntropy.apply(up, t.to(DEV).long(), 255, weight)
+        for td in (t.to(DEV), _offset_by_one(t.to(DEV))):
+            for classes in (n, None):
+                if mid is None:
+                    loss, out, masks = HF.upsample_ce_confusion(x, size, td, 255, classes, weight=weight)
+                else:
+                    loss, out, masks = HF.upsample2_ce_confusion(x, mid, td, 255, classes, weight=weight)
+                assert torch.equal(loss, want_loss) and torch.equal(masks, want_masks)
+                assert (out is None) if classes is None else torch.equal(out.cpu(), want)
 
 
 @pytest.mark.parametrize('tdtype', [torch.int64, torch.uint8], ids=['i64', 'u8'])
