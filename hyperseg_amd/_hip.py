@@ -72,6 +72,12 @@ class S2wTrainLayerC(C.Structure):
                 ('bank', C.c_void_p), ('ld', C.c_int64), ('dbank', C.c_void_p), ('dw', C.c_void_p), ('ds', C.c_void_p)]
 
 
+class TtaPassC(C.Structure):
+    # hs_tta_pass of include/hyperseg_hip.h
+    _fields_ = [('x', C.c_void_p), ('Hi', C.c_int32), ('Wi', C.c_int32), ('Hm', C.c_int32), ('Wm', C.c_int32),
+                ('flipped', C.c_int32), ('entry', C.c_int32)]
+
+
 STATUS = 'hs_status'      # what a SIGNATURES row returns: this marker (0, a negative HS_ERR_* or a hipError_t) or a ctypes value type
 i32, i64, vp = C.c_int32, C.c_int64, C.c_void_p
 # THE list of the library's entries (tests/test_model_boundary.py holds it against the header): name -> (argtypes, STATUS | value type).
@@ -154,6 +160,7 @@ SIGNATURES = {
     'hs_upsample_confusion_fwd': ([vp, i32, i32, i32, i32, i32, i32, vp, i32, i32, i32, vp, vp, vp], STATUS),
     'hs_confusion_fwd': ([vp, i32, vp, i32, i32, i64, i32, i32, vp, vp], STATUS),
     'hs_upsample2_confusion_fwd': ([vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, i32, i32, i32, vp, vp, vp], STATUS),
+    'hs_tta_merge_fwd': ([C.POINTER(TtaPassC), i32, i32, i32, i32, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp], STATUS),
     'hs_cross_entropy_score_fwd': ([i32, vp, vp, i32, i32, i64, i64, vp, i32, i32, vp, vp, vp], STATUS),
     'hs_upsample_ce_confusion_fwd': ([vp, i32, i32, i32, i32, i32, i32, vp, i32, i64, vp, i32, i32, vp, vp, vp], STATUS),
     'hs_cross_entropy_score_weighted_fwd': ([i32, vp, vp, vp, i32, i32, i64, i64, vp, i32, i32, vp, vp, vp], STATUS),

@@ -12,6 +12,10 @@ Reproduces the reference's protocol on synthetic frames (no dataset, checkpoint 
 
     python -m hyperseg_amd.fps --config hyperseg-m --iterations 200 [--prepare] [--graph] [--remove-bn] [--batch-size 1]
                                [--confidence] [--uint8 [--layout hwc|chw] [--overlay] [--resize H W [--camera-size H W]]] [--label-size H W] [--fused-metrics]
+                               [--hflip [--pyramid N]]
+
+``--hflip`` feeds every frame as a list (``--pyramid N``: N entries, the smaller ones ``F.avg_pool2d`` of the frame -- NOT ``cv2.pyrDown``) and
+runs the reference's flip / pyramid loop, whose passes the device merges in one launch (``functional.tta_merge``); eager only.
 
 ``--label-size H W`` draws the targets at that size instead of the frame's: the reference's Cityscapes test configs resize the image
 only, so every frame's logits are resized to the label before they are counted (test.py:167-168) -- done here as well, by the
@@ -29,6 +33,7 @@ per-frame synchronisation exactly like the reference's, and by default its eager
 ``--graph`` keeps the protocol but makes the forward one HIP-graph replay (``utils.inference.GraphedModel``)."""
 import argparse
 import json
+import sys
 import time
 
 import torch
@@ -319,6 +324,16 @@ def synthetic_batches(n, batch_size, size, num_classes, device, seed=0, uint8=Fa
     return out
 
 
+def pyramid_of(x, entries, device):
+    """The list input of ``--hflip`` / ``--pyramid``: ``[x, avg_pool2d(x, 2), avg_pool2d(x, 4), ...]``, ``entries`` long, pinned like ``x``
+    (a synthetic pyramid: NOT cv2.pyrDown's 5 x 5 Gaussian)."""
+    out = [x]
+    for k in range(1, entries):
+        y = torch.nn.functional.avg_pool2d(x, 2 ** k).contiguous()
+        out.append(y.pin_memory() if device.type == 'cuda' else y)
+    return out
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split('\n')[0])
     ap.add_argument('--config', default='hyperseg-m', help='a name from hyperseg_amd.configs.MODELS')
@@ -363,8 +378,21 @@ def main(argv=None):
     ap.add_argument('--gpus', nargs='+', type=int, metavar='N', default=None,
                     help='GPU ids (test_fps.py:31-32): more than one wraps the model in nn.DataParallel exactly as the reference does '
                          '(test_fps.py:155-156; one Python thread per replica -- the mirror is re-entrant for that); the first id is the primary device')
+    ap.add_argument('--hflip', action='store_true',
+                    help="the reference's accuracy mode (hyperseg_v1_0.py:71-91): every frame goes in as a LIST -- one entry, or --pyramid N "
+                         "entries -- and is run plain and mirrored (inference_hflip); on the device the passes are merged in one launch "
+                         "(functional.tta_merge).  Eager only: a list is never replayed from a graph")
+    ap.add_argument('--pyramid', type=int, metavar='N', default=None,
+                    help='with or without --hflip: a list of N entries per frame, entry k the frame average-pooled by 2^k '
+                         '(F.avg_pool2d: a synthetic stand-in that does NOT reproduce cv2.pyrDown, which seg_transforms.Pyramids uses; '
+                         'OpenCV is not a dependency, building the pyramid on the device is out of scope)')
     ap.add_argument('--cpu-only', '--cpu_only', dest='cpu_only', action='store_true')
     args = ap.parse_args(argv)
+    lists = args.hflip or args.pyramid is not None
+    if args.pyramid is not None and args.pyramid < 1:
+        raise SystemExit('--pyramid N: a positive number of entries')
+    if lists and (args.uint8 or args.overlay or args.confidence or args.resize is not None):
+        raise SystemExit('--hflip / --pyramid feed float lists: not with --uint8, --overlay, --confidence or --resize')
     if args.trace:
         args.graph = True
     if args.overlay and not args.uint8:
@@ -417,6 +445,12 @@ def main(argv=None):
         from .utils.confidence import Confidence
         model.confidence_style = Confidence()
         model.inference_hflip = False        # inert for tensor inputs, but confidence() takes its composed route while it is set
+    if lists:
+        model.inference_hflip = bool(args.hflip)
+        if args.graph:
+            print('--hflip / --pyramid: list inputs are served eagerly (a GraphedModel hands them to the wrapped model); running eager',
+                  file=sys.stderr)
+            args.graph = False
     codec = None if args.raw_labels is None else random_codec(args.raw_labels, spec['num_classes'])
     if codec is not None:
         model.label_codec = codec
@@ -431,10 +465,17 @@ def main(argv=None):
     bs = args.batch_size or spec['batch']
     uniq = synthetic_batches(min(args.distinct, args.iterations), bs, frame_size, spec['num_classes'], device,
                              uint8=args.uint8, layout=args.layout, label_size=label_size, label_codec=codec)
+    if lists:
+        uniq = [(pyramid_of(x, args.pyramid or 1, device), t) for x, t in uniq]
     batches = [uniq[i % len(uniq)] for i in range(args.iterations)]
     res = measure_fps(model, batches, device, spec['num_classes'], fused_metrics=args.fused_metrics, overlay=args.overlay, label_codec=codec,
                       confidence=args.confidence)
-    frame = uniq[0][0]
+    frame = uniq[0][0][0] if lists else uniq[0][0]
+    if lists:
+        from . import functional as HF
+        res.update(hflip=bool(args.hflip), pyramid=args.pyramid or 1, 
+                   tta_merge=bool(HF.TTA_MERGE and device.type == 'cuda'            # the route the model takes for these lists
+                                  and (args.pyramid or 1) * (2 if args.hflip else 1) <= HF.TTA_MAX_PASSES))
     res.update(input_dtype=str(frame.dtype).replace('torch.', ''), input_bytes_per_frame=frame[0].numel() * frame.element_size())
     res.update(config=args.config, batch_size=bs, size=list(spec['size']), device=str(device), remove_bn=args.remove_bn,
                prepared=bool(args.prepare and not args.remove_bn), graph=bool(args.graph and device.type == 'cuda'),

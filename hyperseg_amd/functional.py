@@ -35,6 +35,9 @@ def _device_of(a):
         return a.device
     if isinstance(a, (StageInput, BankRef, SignalRef, U8Frame)):
         return a.device
+    # a pass list of tta_merge, [(x, mid_size, flipped, entry), ...]: its first pass's tensor's
+    if isinstance(a, (list, tuple)) and a and isinstance(a[0], (list, tuple)) and a[0] and isinstance(a[0][0], torch.Tensor):
+        return a[0][0].device
     return None
 
 
@@ -1613,6 +1616,129 @@ def confusion_update(pred, target, num_classes, out=None, per_image=False):
     _hip.run.hs_confusion_fwd(pred.data_ptr(), _EVAL_DTYPES[pred.dtype], target.data_ptr(), _EVAL_DTYPES[target.dtype], b,
                               pred.numel() // b, n, 1 if per_image else 0, out.data_ptr(), _hip.stream_ptr())
     return out
+
+
+# Flip and pyramid inference (the reference's list-input mode, hyperseg_v1_0.py:71-91) merged in the forward's last launch (hs_tta_merge_fwd).
+# HS_TTA_MERGE=0 (or TTA_MERGE = False) sends every model through the composed route, tta_merge_composed: the same bits.
+TTA_MERGE = os.environ.get('HS_TTA_MERGE', '1') != '0'
+TTA_MAX_PASSES = 8                                         # HS_TTA_MAX_PASSES of include/hyperseg_hip.h
+TtaMerged = collections.namedtuple('TtaMerged', 'logits masks out')
+
+
+def _tta_passes(passes):
+    """The pass list checked: ``[(x, (hm, wm), flipped, entry), ...]`` with x contiguous-checked later; returns (passes, b, c, (ho, wo))."""
+    passes = [(x, _size2(mid, 'mid_size'), bool(flipped), int(entry)) for x, mid, flipped, entry in passes]
+    if not passes:
+        raise ValueError('passes is empty')
+    b, c = _logits_shape(passes[0][0])[:2]
+    last = -1
+    for i, (x, mid, _, entry) in enumerate(passes):
+        if tuple(_logits_shape(x)[:2]) != (b, c) or x.device != passes[0][0].device:
+            raise ValueError(f'pass {i}: x is {tuple(x.shape)} on {x.device}, pass 0 is ({b}, {c}, ., .) on {passes[0][0].device}')
+        if entry not in (last, last + 1) or (entry == last and mid != passes[i - 1][1]):
+            raise ValueError('passes are sorted by entry, entries 0, 1, ... without a gap, one mid_size per entry')
+        last = entry
+    return passes, b, c, passes[0][1]
+
+
+def tta_merge_takes(n_passes, channels, num_classes=None):
+    """What hs_tta_merge_fwd launches for (a host predicate: the model's route rule and ``tta_merge``'s own refusals): at most 8 passes, at
+    most 256 logit channels and, where it counts, at most ``eval_max_classes()`` classes."""
+    return n_passes <= TTA_MAX_PASSES and channels <= 256 and (num_classes is None or int(num_classes) <= min(256, eval_max_classes()))
+
+
+def _tta_gather_max(gather):
+    if gather not in ('mean', 'max'):
+        raise ValueError(f"gather must be 'mean' or 'max', got {gather!r}")
+    return gather != 'mean'
+
+
+@_on_operand_device
+def tta_merge(passes, gather, target=None, num_classes=None, out=None, per_image=False, logits=False, masks=True):
+    """The reference's list-input inference (hyperseg_v1_0.py:76-89) from the decoder's per-pass outputs in ONE launch (hs_tta_merge_fwd).
+    ``passes``: a list of ``(x, mid_size, flipped, entry)`` -- x f32 (B, C, Hi, Wi), what the decoder hands to its final resize;
+    ``mid_size`` that pass's frame size; ``flipped``: the pass ran on the mirrored frame; ``entry``: its pyramid entry (sorted, from 0).
+    Per entry the passes are resized to ``mid_size`` (a flipped one mirrored back) and their max taken, an entry of another size than
+    entry 0's is resized to it, and the entries are folded in order -- ``gather`` 'mean': ``(p + out) * 0.5``, 'max': ``max(p, out)``.
+    Returns ``TtaMerged(logits, masks, out)``: the f32 logits (B, C, Ho, Wo) with ``logits=True``, the uint8 arg-max masks with
+    ``masks=True``, and with ``target`` (B, Ho, Wo; uint8 or int64) the int64 matrix ``out`` ((n, n), ``per_image``: (B, n, n)) with this
+    call's (target, prediction) counts ACCUMULATED (``upsample_confusion``'s rule); what was not asked for is None.  Bit-identical to
+    ``tta_merge_composed`` for finite inputs; none of the per-pass, per-entry or merged logits exist in memory unless asked for.  More than
+    8 passes, more than 256 channels or more classes than ``eval_max_classes()``: NotImplementedError (``tta_merge_takes``; the caller
+    takes the composed route).  Nothing here reads the device: the call is capturable."""
+    passes, b, c, (ho, wo) = _tta_passes(passes)
+    gather_max = _tta_gather_max(gather)
+    dev = passes[0][0].device
+    if not (logits or masks or target is not None):
+        raise ValueError('nothing asked for: logits, masks or a target to count against')
+    n, tp, tdtype = 0, None, 0
+    if target is not None:
+        target = _eval_target(target, (b, ho, wo), passes[0][0])
+        if num_classes is None:
+            raise ValueError('a target needs num_classes')
+        if c > int(num_classes):
+            raise ValueError(f'{c} logit channels but num_classes = {num_classes}')
+        if int(num_classes) > 256:
+            raise ValueError('num_classes > 256: the masks are uint8')
+        n = _eval_classes(num_classes)
+        tp, tdtype = target.data_ptr(), _EVAL_DTYPES[target.dtype]
+    elif out is not None:
+        raise ValueError('out= needs a target: nothing is counted without it')
+    if not tta_merge_takes(len(passes), c):
+        raise NotImplementedError(f'{len(passes)} passes of {c} channels: the merge launch takes up to {TTA_MAX_PASSES} passes of up to 256')
+    table = (_hip.TtaPassC * len(passes))()
+    for rec, (x, (hm, wm), flipped, entry) in zip(table, passes):
+        rec.x, rec.Hi, rec.Wi, rec.Hm, rec.Wm, rec.flipped, rec.entry = _hip.dev_ptr(x, 'x'), x.shape[2], x.shape[3], hm, wm, flipped, entry
+    out = _eval_out(out, (b, n, n) if per_image else (n, n), dev) if target is not None else None
+    y = torch.empty(b, c, ho, wo, device=dev, dtype=torch.float32) if logits else None
+    mask = torch.empty(b, ho, wo, device=dev, dtype=torch.uint8) if masks else None
+    _hip.run.hs_tta_merge_fwd(table, len(passes), b, c, 1 if gather_max else 0, tp, tdtype, ho, wo, n, 1 if per_image else 0,
+                              _hip.ptr(out), _hip.ptr(mask), _hip.ptr(y), _hip.stream_ptr())
+    return TtaMerged(y, mask, out)
+
+
+def tta_merge_composed(passes, gather, target=None, num_classes=None, out=None, per_image=False, logits=False, masks=True):
+    """``tta_merge`` stated with one launch per step -- the route ``HyperGenBase.forward`` took for a list before the merge launch and
+    takes with ``TTA_MERGE`` off: ``upsample_bilinear`` per pass (none where x is at ``mid_size``), ``torch.flip`` and ``torch.max`` per
+    entry, ``upsample_bilinear`` per entry of another size than entry 0's, the fold, ``argmax`` and ``confusion_update``.  On CPU tensors
+    the resizes are ``F.interpolate(..., 'bilinear')`` and the count ``fps.ConfusionMatrix``'s: the reference's statement."""
+    passes, b, c, size = _tta_passes(passes)
+    gather_max = _tta_gather_max(gather)
+    cuda = passes[0][0].is_cuda
+
+    def resize(t, to):
+        if tuple(t.shape[2:]) == tuple(to):
+            return t
+        return upsample_bilinear(t.contiguous(), to) if cuda else torch.nn.functional.interpolate(t, size=to, mode='bilinear')
+
+    merged, i = None, 0
+    while i < len(passes):
+        entry, mid, y = passes[i][3], passes[i][1], None
+        while i < len(passes) and passes[i][3] == entry:
+            x, _, flipped, _ = passes[i]
+            v = resize(x, mid)
+            v = torch.flip(v, [-1]) if flipped else v
+            y = v if y is None else torch.max(y, v)
+            i += 1
+        y = resize(y, size)
+        merged = y if merged is None else (torch.max(y, merged) if gather_max else (y + merged) * 0.5)
+    mask = merged.argmax(1).to(torch.uint8) if (masks or target is not None) else None
+    if target is not None:
+        if tuple(target.shape) != (b,) + tuple(size):
+            raise ValueError(f'target has shape {tuple(target.shape)}, expected {(b,) + tuple(size)}')
+        if cuda:
+            out = confusion_update(mask, target, num_classes, out=out, per_image=per_image)
+        else:
+            from .fps import ConfusionMatrix
+            n = int(num_classes)
+            out = torch.zeros((b, n, n) if per_image else (n, n), dtype=torch.int64) if out is None else out
+            for k in range(b) if per_image else (slice(None),):
+                cm = ConfusionMatrix(n)
+                cm.update_stock(target[k].flatten().long(), mask[k].flatten().long())
+                (out[k] if per_image else out).add_(cm.mat)
+    elif out is not None:
+        raise ValueError('out= needs a target: nothing is counted without it')
+    return TtaMerged(merged if logits else None, mask if masks else None, out if target is not None else None)
 
 
 def class_weight_table(weight, classes, device, what='weight'):

@@ -77,6 +77,13 @@ class Blend(NamedTuple):
     out: object
 
 
+class Deferred(NamedTuple):
+    """What a decoder returns for ``Epilogue(defer=True)``: ``x``, the input of its final resize (contiguous f32 (B, C, Hi, Wi)), and
+    ``size``, the frame's (H, W) the resize would have gone to -- the launch is left to ``HF.tta_merge``."""
+    x: object
+    size: tuple
+
+
 @dataclass
 class Epilogue:
     """What rides on the decoder's final upsample launch instead of writing the logits: the uint8 arg-max masks, plain -- at the frame's
@@ -88,7 +95,9 @@ class Epilogue:
     the validation step too, as train.py:119-120 does -- losses, masks and counts at the label's size from the one launch; without it such
     a target is rejected where a loss is asked for.  ``confidence`` (a ``utils.confidence.Confidence``): the launch also makes every
     pixel's confidence -- the soft-max probability of its class -- in the style's dtype, and fills the masks below the style's threshold;
-    it goes with ``out_size``, not with ``score`` or ``blend``."""
+    it goes with ``out_size``, not with ``score`` or ``blend``.  ``defer`` (with nothing else): the last launch is not made at all -- the
+    decoder returns a :class:`Deferred`, the input of its final resize and the frame's size, for the one launch that merges the passes of a
+    list input (``HF.tta_merge``); the only epilogue a flipped pass takes."""
     score: Optional[Score] = None
     blend: Optional[Blend] = None
     confidence: Optional[object] = None
@@ -96,8 +105,12 @@ class Epilogue:
     ignore_index: Optional[int] = None
     weight: Optional[object] = None
     loss_at_label: bool = False
+    defer: bool = False
 
     def __post_init__(self):
+        if self.defer and (self.score is not None or self.blend is not None or self.confidence is not None or self.out_size is not None
+                           or self.ignore_index is not None or self.weight is not None or self.loss_at_label):
+            raise ValueError('a deferred last launch makes nothing: defer goes with no other epilogue field')
         if self.ignore_index is not None and (self.score is None or self.blend is not None):
             raise ValueError('the loss rides on a scored epilogue: a score with it, no blend')
         if self.weight is not None and (self.ignore_index is None or self.score is None):
@@ -121,7 +134,9 @@ class Epilogue:
         ``loss_at_label`` set: the logits at ``size`` are resized to the target before the criterion as well (train.py:119-120), by
         ``HF.upsample2_ce_confusion`` -- ``HF.upsample_ce_confusion`` straight to the target's size where ``p`` is at ``size`` already -- and
         ``per_pixel`` is at the target's size too."""
-        size = tuple(size)
+        size = tuple(int(v) for v in size)
+        if self.defer:
+            return Deferred(p.contiguous(), size)
         resized = self.out_size is not None and self.out_size != size
         if self.score is not None:
             target, num_classes, out, per_image = self.score
@@ -246,7 +261,8 @@ class HyperGenBase(EpochOnModeSwitch, nn.Module):
 
     def process_single_tensor(self, x, hflip=False, epilogue=None):
         """The logits of one tensor; with ``epilogue`` (an :class:`Epilogue`; inference only, unflipped) what it makes of the decoder's last
-        launch instead: the uint8 masks, or masks and per-pixel losses / overlay."""
+        launch instead: the uint8 masks, or masks and per-pixel losses / overlay.  ``Epilogue(defer=True)`` also rides on a flipped frame:
+        the :class:`Deferred` is then the MIRRORED frame's (not flipped back: ``HF.tta_merge`` reads it mirrored)."""
         frame = None
         if x.dtype == torch.uint8:
             norm = self._require_norm()
@@ -266,8 +282,10 @@ class HyperGenBase(EpochOnModeSwitch, nn.Module):
             head_out = head_out.contiguous()
         pyramid = [t.contiguous() for t in [x] + features[:-1]]
         # (outside training: the decoders assert that themselves)
-        assert epilogue is None or not hflip, 'an epilogue rides on the last launch of an unflipped frame'
+        assert epilogue is None or not hflip or epilogue.defer, 'an epilogue rides on the last launch of an unflipped frame'
         y = self.decoder(pyramid, head_out, epilogue=epilogue)
+        if isinstance(y, Deferred):
+            return y
         return torch.flip(y, [-1]) if hflip else y
 
     def _logits_at(self, x, size):
@@ -298,7 +316,8 @@ class HyperGenBase(EpochOnModeSwitch, nn.Module):
     def segment(self, x, size=None):
         """uint8 class masks (B, H, W) == ``self(x).argmax(1)`` (the reference's test.py:171 / test_fps.py:194 epilogue).
         For a single tensor in eval mode the argmax is taken inside the final upsample kernel and the full-resolution
-        logits are never written; pyramid / h-flip inference falls back to the logits path.  ``size``: masks at that (H, W) instead
+        logits are never written; a list input (pyramid / h-flip inference) on the device in eval mode gets its masks from the one
+        launch that merges its passes (``HF.tta_merge``: :meth:`_tta_route`), no logits of any pass or entry written.  ``size``: masks at that (H, W) instead
         of the frame's -- the logits resized to it before the arg-max, as test.py:167-168 does for a label of another size; from
         the same one launch (``HF.upsample2_argmax``) where the arg-max is, else the logits route plus that resize."""
         x = self.resized(x)
@@ -306,6 +325,8 @@ class HyperGenBase(EpochOnModeSwitch, nn.Module):
         if size is not None and tuple(size) == self.frame_size(first, isinstance(x, torch.Tensor)):
             size = None
         fused = isinstance(x, torch.Tensor) and not self.training and not self.inference_hflip
+        if size is None and self._tta_route(x):
+            return self._tta_merged(x, masks=True).masks
         if size is None:
             return self.process_single_tensor(x, epilogue=Epilogue()) if fused else self(x).argmax(1).to(torch.uint8)
         size = tuple(int(s) for s in size)
@@ -321,8 +342,10 @@ class HyperGenBase(EpochOnModeSwitch, nn.Module):
         target is scored by the forward's last launch: no further launch, no read of the device -- a target of the output's size by
         ``HF.upsample_confusion``, one of another size at ITS resolution (the LOGITS are resized to it, test.py:167-168 -- the
         protocol of the reference's Cityscapes test configs) by ``HF.upsample2_confusion``, the returned masks then at the target's
-        size.  Everything else -- list inputs (pyramid / h-flip inference), more classes than the kernel covers, training mode, CPU
-        -- computes the masks the way ``segment()`` / ``forward()`` do (resizing the logits to a target of another size) and
+        size.  A list input (pyramid / h-flip inference) on the device in eval mode is scored by the launch that merges its passes
+        (``HF.tta_merge``) when the target is at the first entry's size; a target of another size, or more classes than the kernel
+        covers, gets its masks from ``segment()`` / ``forward()`` -- the same launch -- and ``confmat``'s own update.  Everything else --
+        training mode, CPU -- computes the masks the way ``segment()`` / ``forward()`` do (resizing the logits to a target of another size) and
         counts them with ``confmat``'s own update.  Same numbers on every route.  With ``label_codec`` set a raw ``target`` is encoded
         first (:meth:`encoded`), whatever the route."""
         n = confmat.num_classes
@@ -340,6 +363,14 @@ class HyperGenBase(EpochOnModeSwitch, nn.Module):
                 return masks
             raise RuntimeError('the decoder returned logits where its epilogue was asked for: nothing was scored')
         out_res = self.frame_size(x, True) if isinstance(x, torch.Tensor) else self.frame_size(x[0], False)
+        if (self._tta_route(x) and isinstance(target, torch.Tensor) and target.is_cuda and tuple(target.shape[1:]) == out_res
+                and self._scorable(target, x[0].shape[0], n)):
+            mat = confmat.matrix(x[0].device)
+            out = torch.zeros((x[0].shape[0], n, n), dtype=torch.int64, device=x[0].device) if per_image else mat
+            got = self._tta_merged(x, masks=True, score=Score(target, n, out, per_image))
+            if per_image:
+                confmat.add_per_image(out)
+            return got.masks
         if tuple(target.shape[1:]) != out_res:
             masks = self._logits_at(x, target.shape[1:]).argmax(1).to(torch.uint8)
         else:
@@ -402,7 +433,8 @@ class HyperGenBase(EpochOnModeSwitch, nn.Module):
         the label is not, train.py:119-120 resizes the logits to the label) takes the same route at the label's resolution, under the same
         conditions with ``criterion.k`` taken against the label's pixels: the last launch (``HF.upsample2_ce_confusion``) composes the
         decoder's final resize with the one to the label, and losses, masks and counts are at the label's size; neither the frame-size nor
-        the label-size logits are written.  Everything else -- list inputs, training mode, CPU, class weights the HIP
+        the label-size logits are written.  Everything else -- list inputs (whose logits ``self(x)`` come from the launch that merges their
+        passes, ``HF.tta_merge``), training mode, CPU, class weights the HIP
         loss does not take, another criterion -- computes ``pred = self(x)``, resizes it to the target as ``evaluate`` does, and takes ``criterion(pred,
         target.long())``, ``argmax`` and ``confmat``'s own update.  On the device every route gives the same loss bits, masks and
         counts from the same decoder input.  (An unprepared model's stock torch encoder does not repeat its own bits from one call to
@@ -440,7 +472,7 @@ class HyperGenBase(EpochOnModeSwitch, nn.Module):
         A single CUDA tensor in eval mode without h-flip inference is blended by the forward's last launch
         (``HF.upsample_overlay``) -- no further launch, no read of the device, whether the frame went into the stem launch or through
         ``image_ingest``.  Everything else -- list inputs, h-flip inference, training mode, CPU -- computes the masks the way
-        ``segment()`` does and calls ``style.blend``.  Same bytes on every route.  ``out``: a uint8 tensor of the frames' shape for
+        ``segment()`` does (a list's from the launch that merges its passes, ``HF.tta_merge``) and calls ``style.blend``.  Same bytes on every route.  ``out``: a uint8 tensor of the frames' shape for
         the overlay."""
         style = self.overlay_style if style is None else style
         if style is None:
@@ -480,8 +512,8 @@ class HyperGenBase(EpochOnModeSwitch, nn.Module):
         threshold the masks carry the style's fill byte where the confidence is below it.  A single CUDA tensor in eval mode without
         h-flip inference gets both from the forward's last launch (``HF.upsample_confidence``; with ``size=`` ``HF.upsample2_confidence``)
         -- no further launch, no read of the device, the full-resolution logits never written; uint8 frames, ``input_resize`` and
-        ``size=`` as in ``segment()``.  Everything else -- list inputs, h-flip inference, training mode, CPU -- takes the logits (resized
-        to ``size``) and ``HF.confidence``, on the CPU ``utils.confidence.confidence_cpu``.  Same masks on every route; on the device the
+        ``size=`` as in ``segment()``.  Everything else -- list inputs, h-flip inference, training mode, CPU -- takes the logits (a
+        list's from the launch that merges its passes, ``HF.tta_merge``; resized to ``size``) and ``HF.confidence``, on the CPU ``utils.confidence.confidence_cpu``.  Same masks on every route; on the device the
         same confidence bits from the same decoder input."""
         from ..utils.confidence import Confidence
         style = self.confidence_style if style is None else style
@@ -500,6 +532,44 @@ class HyperGenBase(EpochOnModeSwitch, nn.Module):
             raise RuntimeError('the decoder returned logits where its epilogue was asked for: no confidence was made')
         return style.of_logits(self._logits_at(x, size))
 
+    def _tta_deferrable(self, x):
+        """The passes of a list input can hand over the input of their final resize (``Epilogue(defer=True)``): eval mode, every entry a
+        CUDA tensor, nothing that needs grad, a decoder whose route takes an epilogue.  Such a list is merged from its deferred passes --
+        by the merge launch (:meth:`_tta_route`) or, launch per step, by ``HF.tta_merge_composed``; training mode, the CPU and tensors
+        that need grad keep the loop of :meth:`forward`."""
+        if not isinstance(x, (list, tuple)) or len(x) == 0 or self.training:
+            return False
+        if not all(isinstance(t, torch.Tensor) and t.is_cuda and t.dim() == 4 for t in x):
+            return False
+        # (asked of the parameters only with grad enabled, and only up to the first that needs it: serving runs under no_grad)
+        if torch.is_grad_enabled() and (any(t.requires_grad for t in x) or any(p.requires_grad for p in self.parameters())):
+            return False
+        groups = getattr(self.decoder, '_hyper_modules', None)      # (several signal-fed modules in a level: the per-module route, no epilogue)
+        return groups is None or not any(len(g) > 1 for g in groups())
+
+    def _tta_route(self, x):
+        """A list input takes the merge launch (``HF.tta_merge``: the decoder's passes deferred, merged in ONE launch): a deferrable list
+        (:meth:`_tta_deferrable`) of at most ``HF.TTA_MAX_PASSES`` passes in total (entries, times two with ``inference_hflip``), with
+        ``HF.TTA_MERGE`` on.  A single tensor, which the reference never flips, is not involved at all."""
+        if not HF.TTA_MERGE or not isinstance(x, (list, tuple)) or len(x) * (2 if self.inference_hflip else 1) > HF.TTA_MAX_PASSES:
+            return False
+        return self._tta_deferrable(x)
+
+    def _tta_merged(self, x, logits=False, masks=False, score=None):
+        """The passes of the list ``x`` in the reference's order (per entry: plain, then mirrored), each with its last launch deferred, and
+        the one launch that merges them -- ``HF.tta_merge``'s result; with ``HF.TTA_MERGE`` off, or more passes or channels than the
+        launch takes, ``HF.tta_merge_composed`` of the same passes: the composed route, stated there once."""
+        passes = []
+        for entry, level in enumerate(x):
+            for flipped in ((False, True) if self.inference_hflip else (False,)):
+                got = self.process_single_tensor(level, hflip=flipped, epilogue=Epilogue(defer=True))
+                if not isinstance(got, Deferred):
+                    raise RuntimeError('the decoder returned logits where its last launch was to be deferred')
+                passes.append((got.x, got.size, flipped, entry))
+        scored = {} if score is None else dict(target=score.target, num_classes=score.num_classes, out=score.out, per_image=score.per_image)
+        merge = HF.tta_merge if HF.TTA_MERGE and HF.tta_merge_takes(len(passes), passes[0][0].shape[1]) else HF.tta_merge_composed
+        return merge(passes, 'mean' if self.inference_gather == 'mean' else 'max', logits=logits, masks=masks, **scored)
+
     def gather_results(self, x, y=None):
         assert x is not None
         if y is None:
@@ -510,6 +580,8 @@ class HyperGenBase(EpochOnModeSwitch, nn.Module):
         if isinstance(x, torch.Tensor):
             return self.process_single_tensor(self.resized(x))
         assert isinstance(x, (list, tuple)), 'x must be of type list, tuple, or tensor'
+        if self._tta_deferrable(x):                     # (on the device in eval mode: the merge launch, or tta_merge_composed)
+            return self._tta_merged(x, logits=True).logits
         out_res = self.frame_size(x[0], resize=False)   # the first pyramid level sets the output resolution
         merged = None
         for level in x:

@@ -391,6 +391,31 @@ int hs_upsample2_confusion_fwd(const float* x, int32_t batch, int32_t channels, 
                                int32_t Ho, int32_t Wo, const void* target, int32_t target_dtype, int32_t num_classes, int32_t per_image,
                                int64_t* confusion, uint8_t* mask, void* stream);
 
+/* Flip and pyramid inference merged in one launch (csrc/hs_tta_merge.hip; the reference's list-input mode, hyperseg_v1_0.py:71-91).
+ * passes: a HOST array of n_passes <= HS_TTA_MAX_PASSES records, copied into the launch's arguments (no device-side table, nothing
+ * allocated), sorted by entry, entries 0, 1, ... without a gap, one (Hm, Wm) per entry.  Each pass: x f32 (batch, channels, Hi, Wi), what
+ * the decoder hands to its final resize; (Hm, Wm) its frame's size, where the reference's logits live; flipped: it ran on the mirrored
+ * frame; entry: the pyramid entry it belongs to.  The output size (Ho, Wo) is entry 0's (Hm, Wm).  Per output pixel and class:
+ *   a pass at (ym, xm) of its entry is what hs_upsample_bilinear_fwd(x -> Hm, Wm) stores there (x itself where (Hi, Wi) == (Hm, Wm)), a
+ *     flipped pass read at column Wm - 1 - xm;
+ *   an entry is the max over its passes at its own resolution; an entry of another size than (Ho, Wo) is then resized to it as
+ *     hs_upsample_bilinear_fwd would resize that max map (the max taken at each mid tap before the second interpolation);
+ *   entries are folded in order: out = (p + out) * 0.5, or max(p, out) with gather_max != 0.
+ * Bit-identical to that composition of launches for finite inputs.  Sinks, selected by non-null pointers (at least one): logits f32
+ * (batch, channels, Ho, Wo); mask uint8 (batch, Ho, Wo), the first maximum; confusion together with target (batch, target_h, target_w):
+ * hs_confusion_fwd's counts of (target, arg-max), accumulated, per_image slabs, HS_EVAL_U8 or HS_EVAL_I64 targets, channels <=
+ * num_classes <= 256 else HS_ERR_BAD_ARG.  HS_ERR_UNSUPPORTED -- nothing launched -- for n_passes > HS_TTA_MAX_PASSES, channels > 256,
+ * num_classes > hs_eval_max_classes() when counting, or a target of another size than (Ho, Wo).  Nothing is read back: capturable. */
+#define HS_TTA_MAX_PASSES 8
+typedef struct {
+    const float* x;
+    int32_t Hi, Wi, Hm, Wm;
+    int32_t flipped, entry;
+} hs_tta_pass;
+int hs_tta_merge_fwd(const hs_tta_pass* passes, int32_t n_passes, int32_t batch, int32_t channels, int32_t gather_max,
+                     const void* target, int32_t target_dtype, int32_t target_h, int32_t target_w, int32_t num_classes,
+                     int32_t per_image, int64_t* confusion, uint8_t* mask, float* logits, void* stream);
+
 /* The validation step's middle (csrc/hs_validate.hip; hyperseg/train.py:118-126: the loss of a batch and its running score): the
  * per-pixel cross entropy, the class arg-max and the (target, prediction) count from ONE pass over each pixel's class scores.
  *   loss (batch, pixels) f32: hs_cross_entropy_typed_fwd's values bit for bit (0 where the target is ignore_index or outside
