@@ -222,6 +222,8 @@ SIGNATURES = {
     'hs_se_gate_fwd': ([vp, i32, i32, i32, C.c_float, vp, vp, i32, vp, vp, vp, vp, vp, i32, vp, vp, vp], STATUS),
     'hs_gemm_split_kp': ([i32], C.c_int),
     'hs_gemm_split_fwd': ([vp, vp, vp, vp, vp, i32, vp, vp, i32, i32, i32, i32, i32, vp], STATUS),
+    'hs_gemm_split_se_fwd': ([vp, vp, vp, i32, C.c_float, vp, vp, i32, vp, vp, vp, vp, i32, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp], STATUS),
+    'hs_gemm_split_se_route': ([i32] * 6, C.c_int),
     'hs_gemm_split_conv2x2_fwd': ([vp, vp, vp, vp, i32, vp, vp, i32, i32, i32, i32, i32, i32, vp], STATUS),
     'hs_gemm_split_up2_fwd': ([vp, vp, vp, vp, i32, vp, i32, i32, i32, i32, i32, i32, vp], STATUS),
     'hs_depthwise_route': ([i32] * 11, C.c_int),

@@ -16,7 +16,7 @@ CSRC = os.path.join(PKG, 'csrc')
 LIB_DIR = os.path.join(PKG, 'lib')
 LIB_PATH = os.path.join(LIB_DIR, 'libhyperseg_hip.so')
 SOURCES = ['hs_weights.hip', 'hs_patch_conv.hip', 'hs_patch_conv_gen.hip', 'hs_patch_conv_k1m.hip', 'hs_k1_chain.hip', 'hs_meta_conv.hip', 'hs_patch_ir.hip', 'hs_patch_ir_fused.hip', 'hs_patch_irc.hip', 'hs_patch_ir_px.hip', 'hs_patch_ir_d2.hip', 'hs_encoder.hip', 'hs_mbconv.hip', 'hs_mbconv_lean.hip', 'hs_gemm_split.hip', 'hs_patch_conv_bwd.hip', 'hs_patch_conv_train.hip', 'hs_train_aux.hip', 'hs_s2w_train.hip', 'hs_eval.hip', 'hs_tta_merge.hip', 'hs_ingest.hip', 'hs_overlay.hip', 'hs_confidence.hip', 'hs_resample.hip', 'hs_resample_batch.hip', 'hs_jitter.hip', 'hs_blur.hip', 'hs_validate.hip', 'hs_rotate.hip', 'hs_augment_ragged.hip', 'hs_label_codec.hip']
-HEADERS = [os.path.join(CSRC, 'hs_common.h'), os.path.join(CSRC, 'hs_ir_tiles.h'), os.path.join(CSRC, 'hs_ir_common.h'), os.path.join(CSRC, 'hs_s2w_blocked.h'), os.path.join(CSRC, 'hs_se_tail.h'), os.path.join(CSRC, 'hs_upsample_taps.h'), os.path.join(CSRC, 'hs_ingest.h'), os.path.join(CSRC, 'hs_resample_px.h'), os.path.join(CSRC, 'hs_resample_tables.h'), os.path.join(CSRC, 'hs_jitter_px.h'), os.path.join(CSRC, 'hs_blur_px.h'), os.path.join(CSRC, 'hs_rotate_px.h'), os.path.join(CSRC, 'hs_eval_count.h'), os.path.join(CSRC, 'hs_last_launch.h'), os.path.join(CSRC, 'hs_confidence.h'), os.path.join(CSRC, 'hs_label_codec.h'), os.path.join(REPO, 'include', 'hyperseg_hip.h')]
+HEADERS = [os.path.join(CSRC, 'hs_common.h'), os.path.join(CSRC, 'hs_ir_tiles.h'), os.path.join(CSRC, 'hs_ir_common.h'), os.path.join(CSRC, 'hs_s2w_blocked.h'), os.path.join(CSRC, 'hs_se_tail.h'), os.path.join(CSRC, 'hs_se_gate_phases.h'), os.path.join(CSRC, 'hs_upsample_taps.h'), os.path.join(CSRC, 'hs_ingest.h'), os.path.join(CSRC, 'hs_resample_px.h'), os.path.join(CSRC, 'hs_resample_tables.h'), os.path.join(CSRC, 'hs_jitter_px.h'), os.path.join(CSRC, 'hs_blur_px.h'), os.path.join(CSRC, 'hs_rotate_px.h'), os.path.join(CSRC, 'hs_eval_count.h'), os.path.join(CSRC, 'hs_last_launch.h'), os.path.join(CSRC, 'hs_confidence.h'), os.path.join(CSRC, 'hs_label_codec.h'), os.path.join(REPO, 'include', 'hyperseg_hip.h')]
 # -amdgpu-kernarg-preload-count=16: gfx950 preloads the first 16 kernel-argument dwords into SGPRs at wave launch, so the
 # first address computations do not wait for a scalar load (round 3, visit r5a: 0.9168 -> 0.9019 ms per HyperSeg-M frame,
 # encoder tests green on it; the whole GPU suite runs on this build since).

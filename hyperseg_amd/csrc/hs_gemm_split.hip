@@ -25,6 +25,7 @@
 //   shift, the activation and the residual, and are stored as 128-byte runs; the tail's operands are requested before the
 //   barrier.  (The probed dev kernel had only the accumulate-onto-Y tail; shift / activation / separate residual are new.)
 #include "hs_common.h"
+#include "hs_se_gate_phases.h"
 #include <type_traits>
 
 namespace hs {
@@ -50,6 +51,17 @@ struct GemmSplitArgs {
     int up2_wo;                            // > 0: the N = Ho x up2_wo outputs are stored nearest-2x upsampled, y (B, M, 2 Ho, 2 up2_wo)
 };
 
+// SEG form (gemm_split_kernel<..., true>): the squeeze-excite gate of the block is derived by the workgroup itself instead of read from a.gate
+struct GemmSeArgs {
+    const float* __restrict__ partial;     // (B K, nblk) pool partial sums
+    const float* __restrict__ w1; const float* __restrict__ b1;        // reduce (Csq, K), (Csq)
+    const float* __restrict__ w2t; const float* __restrict__ b2;       // expand, transposed (Csq, K), (K)
+    float* gate_out; float* squeezed_out;  // (B, K), (B, Csq) or null: written by workgroup (0, 0) of each frame
+    float inv_hw; int nblk, Csq;
+};
+template <bool SEG> struct GemmSeOperand {};                            // the kernel's second operand: empty in the plain forms
+template <> struct GemmSeOperand<true> : GemmSeArgs {};
+
 // FAST: K % 8 == 0 and N % 2 == 0 (every encoder / context-head layer): paired pixel loads and vector gate loads, decided at
 // LAUNCH time -- a run-time branch around a load makes the compiler wait for it where the branches join.
 // NS: 16-pixel strips per workgroup.  2 = the 32-pixel block above; 1 = HALF of it, for launches whose 32-pixel grid would leave
@@ -71,9 +83,15 @@ struct GemmSplitArgs {
 // PATCH: X is read through a 2x2 / stride-2 window -- the GEMM of a Conv2d(C, M, kernel 2, stride 2) on a (C, 2 Ho, 2 Wo) map,
 // k = 4 c + 2 dy + dx (the conv weight's own flatten order), pixel n = oy Wo + ox: the two dx of a (c, dy) are ONE 8-byte load
 // (16 bytes for a lane's two pixels), so the im2col copy of the library path is never written.  No gate in this form.
-template <int KS, int NWV, bool FAST, int NS, int MT, int NCH, bool PATCH>
+// SEG (non-PATCH, FAST, NCH == 1, K <= 768: the project convolutions of the MBConv blocks whose gate takes hs_se_gate_fwd's FUSED form):
+// the launch that computed the gate existed only to hand <= 3 KB to this one.  Every workgroup requests the gate's operands -- the pool
+// partial sums, the reduce weights, the expand weights' columns, the biases -- in the same up-front block as its X / A / tail loads, runs
+// the three phases of hs_se_gate_phases.h across all of its threads (LDS aliasing gs_red) and leaves gate[0..K) in LDS, where each lane
+// group takes its 8 values per k-step.  Everything after that is the plain form's text.
+template <int KS, int NWV, bool FAST, int NS, int MT, int NCH, bool PATCH, bool SEG = false>
 __global__ __launch_bounds__(64 * NWV)
-void gemm_split_kernel(GemmSplitArgs a) {
+void gemm_split_kernel(GemmSplitArgs a, GemmSeOperand<SEG> se) {
+    static_assert(!SEG || (FAST && !PATCH && NCH == 1 && (NWV == 8 ? KS <= 3 : KS == 1)), "SEG: the project convolutions' forms only");
     extern __shared__ __attribute__((aligned(16))) float gs_red[];        // [nwv][16 MT rows][16 NS pixels]
     constexpr int nthr = 64 * NWV, nwv = NWV;                              // compile-time: the tail's element count and the reduction unroll
     constexpr int NP = 16 * NS, NR = 16 * MT, NE = NR * NP;                // pixels, rows and outputs per workgroup
@@ -144,7 +162,9 @@ void gemm_split_kernel(GemmSplitArgs a) {
 #pragma unroll
             for (int s = 0; s < KS; ++s) {
                 const int k0 = ((wave * NCH + c) * KS + s) * 32 + 8 * kg;
-                if constexpr (FAST) {
+                if constexpr (SEG) {
+                    // from LDS, once the workgroup has derived the gate (below)
+                } else if constexpr (FAST) {
                     // a run of 8 gate values either exists entirely or not at all (K % 8 == 0): clamp the address, mask by a multiply
                     const float* gp = gb ? gb + min(k0, a.K - 8) : a.w_inv;   // w_inv: any valid 32 bytes when there is no gate
                     const gs_f32x4 g0 = *reinterpret_cast<const gs_f32x4*>(gp), g1 = *reinterpret_cast<const gs_f32x4*>(gp + 4);
@@ -181,7 +201,44 @@ void gemm_split_kernel(GemmSplitArgs a) {
     };
     constexpr bool LATE_TAIL = KS * NCH >= 3;                           // deep K: the f32 strips fill the registers until they are split
     if constexpr (!LATE_TAIL) load_tail();
+    // SEG: the gate's operands.  K <= 32 KS NWV and <= 768: a thread takes SE_CI channels of phase C, a wave SE_RW reduce rows of SE_W1U quads
+    constexpr int SE_PV = SEP_MAX_UNITS / nthr, SE_RW = SEP_MAX_CSQ / NWV, SE_W1U = NWV == 8 ? (KS < 3 ? KS : 3) : 1;
+    constexpr int SE_CI = NWV == 8 && KS >= 3 ? 2 : 1;
+    float4 se_pv[SE_PV], se_w1v[SE_RW][SE_W1U];
+    float se_b1v[SE_RW], se_w2q[SE_CI][4][8], se_b2v[SE_CI];
+    if constexpr (SEG) {
+        se_load_units<nthr, SE_PV>(se.partial + (size_t)b * a.K * se.nblk, se.nblk, a.K, tid, se_pv);
+        se_load_reduce<NWV, SE_RW, SE_W1U>(se.w1, se.b1, a.K, se.Csq, wave, lane, se_w1v, se_b1v);
+#pragma unroll
+        for (int ci = 0; ci < SE_CI; ++ci) se_load_expand(se.w2t, se.b2, a.K, se.Csq, min(tid + nthr * ci, a.K - 1), se_w2q[ci], se_b2v[ci]);
+    }
     __builtin_amdgcn_sched_barrier(0);                                  // every request above is out before the first wait
+    if constexpr (SEG) {
+        float* mean_c = gs_red + SEP_MEAN; float* zs = gs_red + SEP_ZS; float* gate_s = gs_red + SEP_GATE;
+        se_channel_means<nthr, SE_PV>(se_pv, se.nblk, a.K, se.inv_hw, tid, gs_red + SEP_PART, mean_c);
+        se_squeeze_rows<NWV, SE_RW, SE_W1U>(se_w1v, se_b1v, mean_c, a.K, se.Csq, wave, lane, zs);
+        __syncthreads();
+        const bool first = blockIdx.x == 0 && blockIdx.y == 0;          // the frame's gate leaves through ONE workgroup (tests; the model passes no buffer)
+        if (first && se.squeezed_out && tid < se.Csq) se.squeezed_out[(size_t)b * se.Csq + tid] = zs[tid];
+#pragma unroll
+        for (int ci = 0; ci < SE_CI; ++ci) {
+            const int ch = tid + nthr * ci;
+            const float g = se_channel_gate(se_w2q[ci], se_b2v[ci], zs, se.Csq);
+            if (ch < a.K) {
+                gate_s[ch] = g;
+                if (first && se.gate_out) se.gate_out[(size_t)b * a.K + ch] = g;
+            }
+        }
+        __syncthreads();
+#pragma unroll
+        for (int s = 0; s < KS; ++s) {
+            const float* gp = gate_s + min((wave * KS + s) * 32 + 8 * kg, a.K - 8);
+            const gs_f32x4 g0 = *reinterpret_cast<const gs_f32x4*>(gp), g1 = *reinterpret_cast<const gs_f32x4*>(gp + 4);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) { gv[0][s][j] = g0[j]; gv[0][s][4 + j] = g1[j]; }
+        }
+        __syncthreads();                                                // gate_s is gs_red: every read of it is done before the first partial tile lands
+    }
 
     gs_f32x4 tot[MT][NS];
 #pragma unroll
@@ -199,7 +256,7 @@ void gemm_split_kernel(GemmSplitArgs a) {
                 for (int j = 0; j < 8; ++j) {
                     const float mk = (FAST || PATCH ? k0 : k0 + j) < a.K ? 1.0f : 0.0f;
                     float g = mk;
-                    if constexpr (!PATCH) g = gb ? gv[c][s][j] * mk : mk;
+                    if constexpr (!PATCH) g = SEG || gb ? gv[c][s][j] * mk : mk;
                     xv[c][t][s][j] *= g;
                     mx = max(mx, __float_as_uint(xv[c][t][s][j]) & 0x7fffffffu);
                 }
@@ -367,31 +424,49 @@ extern "C" int hs_gemm_split_kp(int32_t c_in) {
     return nwv * nch * ks * 32;
 }
 
+// The launch policy of the plain (non-PATCH) form for a shape: waves / k-steps / chunks, the NS = 1 ("narrow") and MT = 4 ("tall") choices,
+// the grid and gs_red's bytes.  launch_gemm_split_plain and launch_gemm_split_se both take it from here; nothing else decides.
+struct GemmSplitPolicy {
+    int nwv, ks, nch;
+    bool narrow, tall, fast;
+    dim3 grid;
+    size_t lds;
+};
+static int gemm_split_policy(int batch, int c_out, int c_in, int kp, int pixels, GemmSplitPolicy& p) {
+    if (!gemm_split_plan(c_in, p.nwv, p.ks, p.nch)) return HS_ERR_UNSUPPORTED;            // Cin > 2560: the library GEMM
+    if (kp != p.nwv * p.nch * p.ks * 32 || (p.ks > 1 && p.nwv != 8)) return HS_ERR_BAD_ARG;
+    if (batch > 65535 || (c_out + 31) / 32 > 65535) return HS_ERR_UNSUPPORTED;
+    p.grid = dim3((pixels + 31) / 32, ((c_out + 15) / 16 + 1) / 2, batch);
+    const size_t wgs = (size_t)p.grid.x * p.grid.y * p.grid.z;
+    p.narrow = wgs <= HS_GS_NARROW_MAX_WG && pixels > 16;
+    p.tall = wgs >= HS_GS_TALL_MIN_WG && c_out > 32;
+    if (p.narrow) p.grid.x = (pixels + 15) / 16;
+    if (p.tall) p.grid.y = ((c_out + 15) / 16 + 3) / 4;
+    p.lds = (size_t)p.nwv * (p.narrow ? 512 : p.tall ? 2048 : 1024) * sizeof(float);
+    // the vector-load / 2-instruction-split form for every K depth: whole frame 0.814 ms against 0.832 (k-steps <= 2 only) and 0.858
+    // (never), same box, interleaved (profiles/round3_gemm_split_policy_ab.txt)
+    p.fast = (c_in & 7) == 0 && (pixels & 1) == 0 && c_in >= 8;
+    return HS_OK;
+}
+
 static int launch_gemm_split_plain(const void* w_frag, const float* w_inv, const float* gate, const float* x, const float* shift,
                                    int32_t act, const float* residual, float* y, int32_t batch, int32_t c_out, int32_t c_in,
                                    int32_t kp, int32_t pixels, int up2_wo, void* stream) {
     if (!w_frag || !w_inv || !x || !y || batch <= 0 || c_out <= 0 || c_in <= 0 || pixels <= 0) return HS_ERR_BAD_ARG;
     if (act < 0 || act > 3) return HS_ERR_BAD_ARG;
-    int nwv, ks, nch;
-    if (!gemm_split_plan(c_in, nwv, ks, nch)) return HS_ERR_UNSUPPORTED;                  // Cin > 2560: the library GEMM
-    if (kp != nwv * nch * ks * 32 || (ks > 1 && nwv != 8)) return HS_ERR_BAD_ARG;
-    if (batch > 65535 || (c_out + 31) / 32 > 65535) return HS_ERR_UNSUPPORTED;
+    GemmSplitPolicy pol;
+    const int pst = gemm_split_policy(batch, c_out, c_in, kp, pixels, pol);
+    if (pst != HS_OK) return pst;
+    const int nwv = pol.nwv, ks = pol.ks, nch = pol.nch;
+    const bool narrow = pol.narrow, tall = pol.tall, fast = pol.fast;
+    dim3 grid = pol.grid;
+    const size_t lds = pol.lds;
     GemmSplitArgs a{(const _Float16*)w_frag, w_inv, gate, x, shift, residual, y, c_out, c_in, kp / 32, pixels, act, 0, nullptr, up2_wo};
-    dim3 grid((pixels + 31) / 32, ((c_out + 15) / 16 + 1) / 2, batch);
-    const size_t wgs = (size_t)grid.x * grid.y * grid.z;
-    const bool narrow = wgs <= HS_GS_NARROW_MAX_WG && pixels > 16;
-    const bool tall = wgs >= HS_GS_TALL_MIN_WG && c_out > 32;
-    if (narrow) grid.x = (pixels + 15) / 16;
-    if (tall) grid.y = ((c_out + 15) / 16 + 3) / 4;
-    const size_t lds = (size_t)nwv * (narrow ? 512 : tall ? 2048 : 1024) * sizeof(float);
     hipStream_t s = (hipStream_t)stream;
-    // the vector-load / 2-instruction-split form for every K depth: whole frame 0.814 ms against 0.832 (k-steps <= 2 only) and 0.858
-    // (never), same box, interleaved (profiles/round3_gemm_split_policy_ab.txt)
-    const bool fast = (c_in & 7) == 0 && (pixels & 1) == 0 && c_in >= 8;
 #define HS_GS_(KSV, NWV, F) do { \
-        if (narrow) hipLaunchKernelGGL((gemm_split_kernel<KSV, NWV, F, 1, 2, 1, false>), grid, dim3(64 * NWV), lds, s, a); \
-        else if (tall) hipLaunchKernelGGL((gemm_split_kernel<KSV, NWV, F, 2, 4, 1, false>), grid, dim3(64 * NWV), lds, s, a); \
-        else hipLaunchKernelGGL((gemm_split_kernel<KSV, NWV, F, 2, 2, 1, false>), grid, dim3(64 * NWV), lds, s, a); } while (0)
+        if (narrow) hipLaunchKernelGGL((gemm_split_kernel<KSV, NWV, F, 1, 2, 1, false>), grid, dim3(64 * NWV), lds, s, a, GemmSeOperand<false>{}); \
+        else if (tall) hipLaunchKernelGGL((gemm_split_kernel<KSV, NWV, F, 2, 4, 1, false>), grid, dim3(64 * NWV), lds, s, a, GemmSeOperand<false>{}); \
+        else hipLaunchKernelGGL((gemm_split_kernel<KSV, NWV, F, 2, 2, 1, false>), grid, dim3(64 * NWV), lds, s, a, GemmSeOperand<false>{}); } while (0)
 #define HS_GS(KSV, NWV) do { if (fast) HS_GS_(KSV, NWV, true); else HS_GS_(KSV, NWV, false); } while (0)
     if (nch == 2) {
         // 1280 < Cin <= 2560 (round 6: HyperSeg-M's last project conv, K = 1920): two chunks of KS k-steps per wave, each scaled by its own
@@ -399,7 +474,7 @@ static int launch_gemm_split_plain(const void* w_frag, const float* w_inv, const
         if (!fast || up2_wo > 0) return HS_ERR_UNSUPPORTED;
         grid.x = (pixels + 15) / 16; grid.y = ((c_out + 15) / 16 + 1) / 2;
         const size_t lds2 = (size_t)8 * 512 * sizeof(float);
-#define HS_GS2(KSV) hipLaunchKernelGGL((gemm_split_kernel<KSV, 8, true, 1, 2, 2, false>), grid, dim3(512), lds2, s, a)
+#define HS_GS2(KSV) hipLaunchKernelGGL((gemm_split_kernel<KSV, 8, true, 1, 2, 2, false>), grid, dim3(512), lds2, s, a, GemmSeOperand<false>{})
         switch (ks) { case 3: HS_GS2(3); break; case 4: HS_GS2(4); break; case 5: HS_GS2(5); break; default: return HS_ERR_UNSUPPORTED; }
 #undef HS_GS2
         return launch_status();
@@ -413,6 +488,56 @@ static int launch_gemm_split_plain(const void* w_frag, const float* w_inv, const
     }
 #undef HS_GS
 #undef HS_GS_
+    return launch_status();
+}
+
+// Where the project GEMM derives the block's gate itself: exactly where hs_se_gate_fwd takes its FUSED form (asked of hs_se_gate_route, the
+// one place that decides it) AND hs_gemm_split_fwd takes a FAST single-chunk form, with the operands the quad loads need 16-byte aligned.
+static int gemm_split_se_route(int channels, int nblk, int c_squeezed, int c_out, int pixels, bool aligned16, int batch, GemmSplitPolicy& pol) {
+    if (channels <= 0 || nblk <= 0 || c_squeezed <= 0 || c_out <= 0 || pixels <= 0 || batch <= 0) return HS_ERR_BAD_ARG;
+    const int kp = hs_gemm_split_kp(channels);
+    if (kp < 0) return HS_ERR_UNSUPPORTED;
+    const int pst = gemm_split_policy(batch, c_out, channels, kp, pixels, pol);
+    if (pst != HS_OK) return pst;
+    if (hs_se_gate_route(channels, nblk, c_squeezed, 0, aligned16 ? 1 : 0) != HS_SE_ROUTE_FUSED) return HS_ERR_UNSUPPORTED;
+    if (!aligned16 || !pol.fast || pol.nch != 1 || channels > SEP_MAX_C || c_squeezed > SEP_MAX_CSQ) return HS_ERR_UNSUPPORTED;
+    if (pol.ks > (pol.nwv == 8 ? 3 : 1)) return HS_ERR_UNSUPPORTED;                       // cannot happen for channels <= 768; the kernel's static_assert
+    return HS_GSE_ROUTE(pol.ks, pol.nwv);
+}
+
+extern "C" int hs_gemm_split_se_route(int32_t channels, int32_t nblk, int32_t c_squeezed, int32_t c_out, int32_t pixels, int32_t aligned16) {
+    GemmSplitPolicy pol;
+    return gemm_split_se_route(channels, nblk, c_squeezed, c_out, pixels, aligned16 != 0, 1, pol);
+}
+
+extern "C" int hs_gemm_split_se_fwd(const void* w_frag, const float* w_inv, const float* partial, int32_t nblk, float inv_hw,
+                                    const float* w_reduce, const float* b_reduce, int32_t c_squeezed, const float* w_expand_t,
+                                    const float* b_expand, const float* x, const float* shift, int32_t act, const float* residual,
+                                    float* y, int32_t batch, int32_t c_out, int32_t c_in, int32_t kp, int32_t pixels,
+                                    float* gate_out, float* squeezed_out, void* stream) {
+    if (!w_frag || !w_inv || !x || !y || batch <= 0 || c_out <= 0 || c_in <= 0 || pixels <= 0) return HS_ERR_BAD_ARG;
+    if (!partial || !w_reduce || !b_reduce || !w_expand_t || !b_expand || nblk <= 0 || c_squeezed <= 0) return HS_ERR_BAD_ARG;
+    if (act < 0 || act > 3) return HS_ERR_BAD_ARG;
+    GemmSplitPolicy pol;
+    const bool aligned16 = (((size_t)partial | (size_t)w_reduce) & 15) == 0;
+    const int route = gemm_split_se_route(c_in, nblk, c_squeezed, c_out, pixels, aligned16, batch, pol);
+    if (route < 0) return route;
+    if (kp != pol.nwv * pol.ks * 32) return HS_ERR_BAD_ARG;
+    GemmSplitArgs a{(const _Float16*)w_frag, w_inv, nullptr, x, shift, residual, y, c_out, c_in, kp / 32, pixels, act, 0, nullptr, 0};
+    GemmSeOperand<true> se{{partial, w_reduce, b_reduce, w_expand_t, b_expand, gate_out, squeezed_out, inv_hw, nblk, c_squeezed}};
+    const size_t se_lds = (size_t)SEP_LDS_FLOATS * sizeof(float);
+    const size_t lds = pol.lds > se_lds ? pol.lds : se_lds;               // the phases' LDS aliases gs_red
+    hipStream_t s = (hipStream_t)stream;
+#define HS_GSE(KSV, NWV) do { \
+        if (pol.narrow) hipLaunchKernelGGL((gemm_split_kernel<KSV, NWV, true, 1, 2, 1, false, true>), pol.grid, dim3(64 * NWV), lds, s, a, se); \
+        else if (pol.tall) hipLaunchKernelGGL((gemm_split_kernel<KSV, NWV, true, 2, 4, 1, false, true>), pol.grid, dim3(64 * NWV), lds, s, a, se); \
+        else hipLaunchKernelGGL((gemm_split_kernel<KSV, NWV, true, 2, 2, 1, false, true>), pol.grid, dim3(64 * NWV), lds, s, a, se); } while (0)
+    switch (pol.ks) {
+        case 1: if (pol.nwv == 2) HS_GSE(1, 2); else if (pol.nwv == 4) HS_GSE(1, 4); else HS_GSE(1, 8); break;
+        case 2: HS_GSE(2, 8); break;
+        default: HS_GSE(3, 8); break;
+    }
+#undef HS_GSE
     return launch_status();
 }
 
@@ -459,7 +584,7 @@ extern "C" int hs_gemm_split_conv2x2_fwd(const void* w_frag, const float* w_inv,
     dim3 grid((pixels + 15) / 16, ((c_out + 15) / 16 + 1) / 2, batch);
     const size_t lds = (size_t)8 * 512 * sizeof(float);
     hipStream_t s = (hipStream_t)stream;
-#define HS_GP(KSV, NCHV) hipLaunchKernelGGL((gemm_split_kernel<KSV, 8, true, 1, 2, NCHV, true>), grid, dim3(512), lds, s, a)
+#define HS_GP(KSV, NCHV) hipLaunchKernelGGL((gemm_split_kernel<KSV, 8, true, 1, 2, NCHV, true>), grid, dim3(512), lds, s, a, GemmSeOperand<false>{})
     switch (ks * 2 + nch - 1) {
         case 2: HS_GP(1, 1); break;
         case 4: HS_GP(2, 1); break;

@@ -1356,6 +1356,56 @@ def gemm_split(sw, x, gate=None, shift=None, act=ACT_NONE, residual=None, out=No
     return out
 
 
+def gemm_split_se_route(channels, nblk, c_squeezed, c_out, pixels, aligned=True):
+    """The form ``gemm_split_se`` launches: 'ks2_w8' ... (k-steps per wave, waves per workgroup), None where it refuses -- anything
+    but a shape for which ``se_gate`` is 'fused' and ``gemm_split`` a paired-load single-chunk launch (hs_gemm_split_se_route).
+    ``aligned``: partial and w_reduce are 16-byte aligned.  Host only."""
+    r = _route(_hip.lib.hs_gemm_split_se_route(channels, nblk, c_squeezed, c_out, pixels, int(bool(aligned))), 'hs_gemm_split_se_route')
+    return None if r is None else f'ks{r >> 4}_w{r & 15}'
+
+
+@_on_operand_device
+def gemm_split_se(sw, x, partial, hw, w_reduce, b_reduce, w_expand_t, b_expand, shift=None, act=ACT_NONE, residual=None, out=None,
+                  gate_out=None, squeezed_out=None):
+    """``gemm_split(sw, x, gate=se_gate(partial, B, hw, w_reduce, b_reduce, w_expand_t, b_expand), ...)`` as ONE launch: every
+    workgroup of the GEMM derives the gate from the pool partial sums (B C, nblk) itself (hs_gemm_split_se_fwd); the result equals
+    the composed route's bit for bit.  ``gate_out`` (B, C) / ``squeezed_out`` (B, Csq): optional f32 tensors that receive the gate
+    and the squeezed activations.  Raises HipLibraryError where ``gemm_split_se_route`` answers None."""
+    b, cin, h, w = x.shape
+    if cin != sw.c_in:
+        raise ValueError(f'input has {cin} channels, the weight {sw.c_in}')
+    shape = (b, sw.c_out, h, w)
+    if out is None:
+        out = torch.empty(shape, device=x.device, dtype=torch.float32)
+    elif tuple(out.shape) != shape:
+        raise ValueError(f'out has shape {tuple(out.shape)}, expected {shape}')
+    if residual is not None and tuple(residual.shape) != shape:
+        raise ValueError(f'residual has shape {tuple(residual.shape)}, expected {shape}')
+    if shift is not None and shift.numel() != sw.c_out:
+        raise ValueError(f'shift has {shift.numel()} entries, expected {sw.c_out}')
+    if partial.dim() != 2 or partial.shape[0] != b * cin:
+        raise ValueError(f'partial has shape {tuple(partial.shape)}, expected ({b * cin}, nblk)')
+    csq = w_reduce.shape[0]
+    if w_reduce.numel() != csq * cin or b_reduce.numel() != csq:
+        raise ValueError(f'w_reduce / b_reduce have {w_reduce.numel()} / {b_reduce.numel()} entries, expected {csq * cin} / {csq}')
+    if tuple(w_expand_t.shape) != (csq, cin) or b_expand.numel() != cin:
+        raise ValueError(f'w_expand_t has shape {tuple(w_expand_t.shape)} and b_expand {b_expand.numel()} entries, expected {(csq, cin)} and {cin}')
+    if gate_out is not None and tuple(gate_out.shape) != (b, cin):
+        raise ValueError(f'gate_out has shape {tuple(gate_out.shape)}, expected {(b, cin)}')
+    if squeezed_out is not None and tuple(squeezed_out.shape) != (b, csq):
+        raise ValueError(f'squeezed_out has shape {tuple(squeezed_out.shape)}, expected {(b, csq)}')
+    _hip.run.hs_gemm_split_se_fwd(_hip.dev_ptr(sw.frag, 'w_frag', torch.float16), _hip.dev_ptr(sw.inv, 'w_inv'),
+                                  _hip.dev_ptr(partial, 'partial'), partial.shape[1], 1.0 / float(hw),
+                                  _hip.dev_ptr(w_reduce, 'w_reduce'), _hip.dev_ptr(b_reduce, 'b_reduce'), csq,
+                                  _hip.dev_ptr(w_expand_t, 'w_expand_t'), _hip.dev_ptr(b_expand, 'b_expand'), _hip.dev_ptr(x, 'x'),
+                                  _hip.dev_ptr(shift, 'shift') if shift is not None else None, int(act),
+                                  _hip.dev_ptr(residual, 'residual') if residual is not None else None,
+                                  _hip.dev_ptr(out, 'out'), b, sw.c_out, cin, sw.kp, h * w,
+                                  _hip.dev_ptr(gate_out, 'gate_out') if gate_out is not None else None,
+                                  _hip.dev_ptr(squeezed_out, 'squeezed_out') if squeezed_out is not None else None, _hip.stream_ptr())
+    return out
+
+
 @_on_operand_device
 def gemm_split_conv2x2(sw, x, shift=None, act=ACT_NONE, out=None, pool_partial=None):
     """y (B, Cout, H/2, W/2) = act(Conv2d(kernel 2, stride 2)(x) + shift[:, None, None]) on the f16 matrix cores with split

@@ -283,6 +283,12 @@ def _bn_affine(bn):
 # project conv, K = 1920 -- measured 1.8 us SLOWER on it than on the library GEMM (profiles/round6_split_gemm_k1920_negative_w14.txt)
 SPLIT_GEMM_MAX_K = int(os.environ.get('HS_SPLIT_GEMM_MAX_K', '1280'))
 STEM_DW = os.environ.get('HS_STEM_DW', '1') != '0'       # stem + block 0's depthwise half as one launch (hs_stem_dw_fwd); 0: two launches
+# the project GEMM derives the block's squeeze-excite gate itself (hs_gemm_split_se_fwd) where it covers the shape; 0: hs_se_gate_fwd + hs_gemm_split_fwd
+HS_GEMM_SE = os.environ.get('HS_GEMM_SE', '1') != '0'
+# ... up to this many mid channels: the 672-channel blocks (3 k-steps per wave, 75 KB of reduce + 75 KB of expand weights per workgroup)
+# measured 0.6-1.0 us SLOWER per launch than the pair they replace, the 240- and 480-channel ones 1.7-3.9 us faster
+# (profiles/gemm_split_se_frame_sequence.txt); the library entry covers them all the same
+GEMM_SE_MAX_CIN = 512
 FUSE_EXPAND_MIN_PIXELS = int(os.environ.get('HS_FUSE_EXPAND_MIN_PIXELS', '2048'))
 FUSE_EXPAND_MAX_CIN = int(os.environ.get('HS_FUSE_EXPAND_MAX_CIN', '40'))      # wider inputs: 1 wave / SIMD, slower than GEMM + dw
 
@@ -553,6 +559,17 @@ class FusedMBConv(nn.Module):
             if sw is not None:
                 # our own GEMM (f16 matrix cores, split operands): the BN2 scale is folded into the static split weights, the
                 # gate multiplies the rows of y on load -- no per-frame copy of the project weights is written
+                # ... and where the gate is still to be computed from the pool partial sums, the GEMM's own workgroups derive it (one launch
+                # less per block, same bits).  CUDA tensors only: on CPU tensors (the boundary tests' stand-ins) the calls below are made
+                if (HS_GEMM_SE and y.is_cuda and not gated and cmid <= GEMM_SE_MAX_CIN and
+                        HF.gemm_split_se_route(cmid, pooled.shape[1], self._red_w.shape[0], sw.c_out, ho * wo,
+                                               aligned=(pooled.data_ptr() | red.weight.data_ptr()) % 16 == 0) is not None):
+                    se_ops = (pooled, ho * wo, red.weight, red.bias, self._exp_t, exp.bias)
+                    if self.defer_shift:
+                        if skip is None:
+                            return HF.gemm_split_se(sw, y, *se_ops)
+                        return HF.gemm_split_se(sw, y, *se_ops, residual=skip, out=skip)
+                    return HF.gemm_split_se(sw, y, *se_ops, shift=proj.shift, residual=skip)
                 gate = se_gate()
                 if self.defer_shift:
                     if skip is None:

@@ -919,6 +919,22 @@ int hs_gemm_split_kp(int32_t c_in);
 int hs_gemm_split_fwd(const void* w_frag, const float* w_inv, const float* gate, const float* x, const float* shift,
                       int32_t act, const float* residual, float* y, int32_t batch, int32_t c_out, int32_t c_in, int32_t kp,
                       int32_t pixels, void* stream);
+/* The same launch deriving the block's squeeze-excite gate itself: the operands are those of the entry above with `gate` replaced by
+ * the operands of the gate's own entry above (partial (B c_in, nblk), inv_hw, w_reduce (c_squeezed, c_in), b_reduce, w_expand_t
+ * (c_squeezed, c_in), b_expand).  Every workgroup runs the three phases of csrc/hs_se_gate_phases.h before its first product; the
+ * gate it uses equals the FUSED form's bit for bit, hence so does y.  gate_out (B, c_in) / squeezed_out (B, c_squeezed): optional,
+ * written by one workgroup per frame.  Covered exactly where the gate's own query answers HS_SE_ROUTE_FUSED (no w_proj) AND the
+ * launch above takes a FAST single-chunk form (c_in % 8 == 0, pixels % 2 == 0), with partial and w_reduce 16-byte aligned:
+ * c_in <= 768, c_squeezed <= 32, units <= 2048.  Anything else: HS_ERR_UNSUPPORTED, nothing launched.  Waves, 16-pixel strips and
+ * row tiles per workgroup are the launch above's for the same shape.
+ * The route query -> HS_GSE_ROUTE(ks, nwv): k-steps per wave (1..3) and waves per workgroup (2, 4, 8). */
+#define HS_GSE_ROUTE(ks, nwv) (((ks) << 4) | (nwv))
+int hs_gemm_split_se_fwd(const void* w_frag, const float* w_inv, const float* partial, int32_t nblk, float inv_hw,
+                         const float* w_reduce, const float* b_reduce, int32_t c_squeezed, const float* w_expand_t,
+                         const float* b_expand, const float* x, const float* shift, int32_t act, const float* residual,
+                         float* y, int32_t batch, int32_t c_out, int32_t c_in, int32_t kp, int32_t pixels,
+                         float* gate_out, float* squeezed_out, void* stream);
+int hs_gemm_split_se_route(int32_t channels, int32_t nblk, int32_t c_squeezed, int32_t c_out, int32_t pixels, int32_t aligned16);
 /* Conv2d(c_in, c_out, kernel 2, stride 2, no padding, no bias) + shift + act with the same arithmetic: x (B,c_in,2Ho,2Wo) ->
  * y (B,c_out,Ho,Wo), the window read on load (K = 4 c_in, k = 4 c + 2 dy + dx: the conv weight's own flatten order; no im2col
  * copy).  w_frag / w_inv from the (c_out, 4 c_in) weight, kp = hs_gemm_split_kp(4 c_in); 34 <= c_in <= 640, c_in and Wo even,
