@@ -171,6 +171,7 @@ SIGNATURES = {
     'hs_stage_input_typed_fwd': ([C.POINTER(StageInputC), i32, i32, vp, vp], STATUS),
     'hs_patch_conv_bwd_input': ([vp, vp, i64, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp], STATUS),
     'hs_patch_conv_bwd_weight': ([vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, i64, vp], STATUS),
+    'hs_patch_conv_bwd_route': ([i32, i32, i32, i32, i64] + [i32] * 11 + [C.POINTER(C.c_int32), C.POINTER(C.c_int32)], STATUS),
     'hs_patch_conv_plain_fwd': ([i32, vp, vp, i64, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp], STATUS),
     'hs_patch_conv_plain_bwd_in': ([i32, vp, vp, i64, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp], STATUS),
     'hs_patch_conv_plain_bwd_w': ([i32, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, i64, vp], STATUS),

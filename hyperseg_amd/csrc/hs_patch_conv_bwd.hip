@@ -40,6 +40,10 @@ int fast_fwd_form(bool aligned8, int batch, int c_in, int H, int W, int fh, int 
                   bool with_scale, bool with_shift, int act, int form[4]);
 int try_fast_fwd(int dtype, const void* x, const void* bank, long ld, int batch, int c_in, int H, int W, int fh, int fw, int c_out,
                  int k, int pad, int pad_mode, int groups, const float* scale, const float* shift, int act, void* y, hipStream_t stream);
+int bwd_in_form(int dtype, size_t addr, int batch, int c_in, int H, int W, int fh, int fw, int c_out, int k, int pad, int pad_mode, int groups,
+                int form[4]);
+int bwd_w_form(int dtype, size_t addr, int batch, int c_in, int H, int W, int fh, int fw, int c_out, int k, int pad, int pad_mode, int groups,
+               int form[4], size_t* lds_bytes);
 int try_fast_bwd_in(int dtype, const void* dy, const void* bank, long ld, int batch, int c_in, int H, int W, int fh, int fw,
                     int c_out, int k, int pad, int pad_mode, int groups, void* dx, hipStream_t stream);
 int try_fast_bwd_w(int dtype, const void* x, const void* dy, int batch, int c_in, int H, int W, int fh, int fw, int c_out, int k,
@@ -1210,14 +1214,37 @@ int hs::try_fast_fwd(int dtype, const void* x, const void* bank, long ld, int ba
     return 1;
 }
 
+// The form the input gradient takes (hs_patch_conv_bwd_route asks the same question with nothing launched).  `addr`: the two tensors'
+// addresses or-ed (dy | dx).  HS_BWD_ROUTE_DW3 with form = {pairs}; HS_BWD_ROUTE_TINY; HS_BWD_ROUTE_K1M with form = {CT, KQ (16-channel
+// tiles of c_in / c_out), pixels per lane}; HS_BWD_ROUTE_GENERIC (one thread per input element) for everything else.
+int hs::bwd_in_form(int dtype, size_t addr, int batch, int c_in, int H, int W, int fh, int fw, int c_out, int k, int pad, int pad_mode, int groups,
+                    int form[4]) {
+    form[0] = form[1] = form[2] = form[3] = 0;
+    if (H % fh || W % fw || !storage_known(dtype)) return HS_BWD_ROUTE_GENERIC;
+    const int ph = H / fh, pw = W / fw;
+    const bool pairs = dw3_pairs_shape(pw, H, W, (long)batch * c_in, (addr & 7) == 0);
+    if (k == 3 && pad == 1 && pad_mode == HS_PAD_ZEROS && groups == c_in && c_in == c_out && (long)batch * c_in <= 65535) {
+        form[0] = pairs ? 1 : 0;
+        return HS_BWD_ROUTE_DW3;
+    }
+    if (k != 1 || groups != 1) return HS_BWD_ROUTE_GENERIC;
+    if (ph * pw < 16) return c_out <= 1024 ? HS_BWD_ROUTE_TINY : HS_BWD_ROUTE_GENERIC;
+    const int ct = (c_in + 15) / 16, kq = (c_out + 15) / 16;
+    if (!((ct <= 4 && kq <= 4 && !(ct == 4 && kq == 4)) || (ct == 6 && kq <= 2))) return HS_BWD_ROUTE_GENERIC;      // the instantiated (CT, KQ) pairs
+    form[0] = ct; form[1] = kq; form[2] = pairs && ph * pw >= 128 ? 2 : 1;
+    return HS_BWD_ROUTE_K1M;
+}
+
 int hs::try_fast_bwd_in(int dtype, const void* dy, const void* bank, long ld, int batch, int c_in, int H, int W, int fh, int fw,
                         int c_out, int k, int pad, int pad_mode, int groups, void* dx, hipStream_t stream) {
-    if (H % fh || W % fw || !storage_known(dtype)) return 1;
+    int form[4];
+    const int route = bwd_in_form(dtype, ((size_t)dy) | ((size_t)dx), batch, c_in, H, W, fh, fw, c_out, k, pad, pad_mode, groups, form);
+    if (route == HS_BWD_ROUTE_GENERIC) return 1;
     ConvBwdArgs a;
     fast_args(a, bank, ld, batch, c_in, H, W, fh, fw, c_out);
     a.dy = (const float*)dy; a.dx = (float*)dx;
-    if (k == 3 && pad == 1 && pad_mode == HS_PAD_ZEROS && groups == c_in && c_in == c_out && (long)batch * c_in <= 65535) {
-        if (dw3_pairs(a, dy, dx)) {
+    if (route == HS_BWD_ROUTE_DW3) {
+        if (form[0]) {
             const dim3 grid2((W / 2 + 63) / 64, (H + 3) / 4, batch * c_in);
             with_storage(dtype, [&](auto tag) {
                 using T = decltype(tag);
@@ -1232,17 +1259,16 @@ int hs::try_fast_bwd_in(int dtype, const void* dy, const void* bank, long ld, in
         });
         return launch_status();
     }
-    if (k == 1 && groups == 1 && a.ph * a.pw < 16 && c_out <= 1024) {
+    if (route == HS_BWD_ROUTE_TINY) {
         const dim3 gridt((unsigned)(batch * fh * fw));
         with_storage(dtype, [&](auto tag) {
             hipLaunchKernelGGL(patch_conv_bwd_input_tiny_kernel<decltype(tag)>, gridt, dim3(128), (size_t)c_out * 64, stream, a);
         });
         return launch_status();
     }
-    if (k != 1 || groups != 1 || a.ph * a.pw < 16) return 1;
-    const int ct = (c_in + 15) / 16, kq = (c_out + 15) / 16;
+    const int ct = form[0], kq = form[1];
     const dim3 grid((unsigned)(batch * fh * fw));
-    const bool px2 = dw3_pairs(a, dy, dx) && a.ph * a.pw >= 128;
+    const bool px2 = form[2] == 2;
 #define HS_BI(CTV, KQV) if (ct == CTV && kq == KQV) { \
         with_storage(dtype, [&](auto tag) { \
             using T = decltype(tag); \
@@ -1253,18 +1279,76 @@ int hs::try_fast_bwd_in(int dtype, const void* dy, const void* bank, long ld, in
     HS_BI(1, 1) HS_BI(1, 2) HS_BI(1, 3) HS_BI(1, 4) HS_BI(2, 1) HS_BI(2, 2) HS_BI(2, 3) HS_BI(2, 4)
     HS_BI(3, 1) HS_BI(3, 2) HS_BI(3, 3) HS_BI(3, 4) HS_BI(4, 1) HS_BI(4, 2) HS_BI(4, 3) HS_BI(6, 1) HS_BI(6, 2)
 #undef HS_BI
-    return 1;
+    return HS_ERR_UNSUPPORTED;                                          // a form the predicate names and nothing instantiates: never silently generic
+}
+
+// The form the per-patch weight gradient takes (hs_patch_conv_bwd_route likewise).  `addr`: x | dy.  HS_BWD_ROUTE_DW3 with form = {pairs};
+// HS_BWD_ROUTE_TINY; HS_BWD_ROUTE_K1M with form = {MT, NT (16-channel tiles of c_out / c_in), loads: 1 = four elements, 2 = pairs, 0 = scalar};
+// HS_BWD_ROUTE_GENERIC with form = {ob (output channels per block), blocks, 1 where the LDS request exceeds 64 KB} and *lds_bytes = that
+// request -- the fp32 kernel's (hs_patch_conv_bwd_weight: the typed launcher sizes its own) --, HS_ERR_LDS where not even one block fits.
+// The return value is a ROUTE (>= 0) or an HS_ERR_* (< 0), never a status: HS_BWD_ROUTE_DW3 is 0 like HS_OK, so a caller tests `< 0` for
+// failure and compares against the HS_BWD_ROUTE_* names, as bwd_in_form's callers do (that one never fails).
+int hs::bwd_w_form(int dtype, size_t addr, int batch, int c_in, int H, int W, int fh, int fw, int c_out, int k, int pad, int pad_mode, int groups,
+                   int form[4], size_t* lds_bytes) {
+    form[0] = form[1] = form[2] = form[3] = 0;
+    if (lds_bytes) *lds_bytes = 0;
+    if (H % fh || W % fw || groups <= 0 || c_in % groups || c_out % groups) return HS_ERR_BAD_ARG;
+    const int ph = H / fh, pw = W / fw;
+    if (storage_known(dtype)) {
+        if (k == 3 && pad == 1 && pad_mode == HS_PAD_ZEROS && groups == c_in && c_in == c_out && (c_in + 3) / 4 <= 65535) {
+            form[0] = dw3_pairs_shape(pw, H, W, (long)batch * c_in, (addr & 7) == 0) ? 1 : 0;
+            return HS_BWD_ROUTE_DW3;
+        }
+        if (k == 1 && groups == 1 && ph * pw < 16 && (long)c_out * c_in < (1 << 21) && (size_t)(c_out + c_in) * 17 * 4 <= 64 * 1024)
+            return HS_BWD_ROUTE_TINY;
+        const int mt = (c_out + 15) / 16, nt = (c_in + 15) / 16;
+        if (k == 1 && groups == 1 && ph * pw >= 16 && ((mt <= 2 && nt <= 4) || (mt <= 4 && nt <= 2))) {       // the instantiated (MT, NT) pairs
+            const bool vec = (pw & 3) == 0 && ((ph * pw) & 15) == 0 && (W & 3) == 0 &&
+                             (addr & (4 * storage_bytes(dtype) - 1)) == 0;                               // four elements per load, either storage type
+            const bool pairs = !vec && (pw & 1) == 0 && (W & 1) == 0 && (addr & 7) == 0;                 // either storage type
+            form[0] = mt; form[1] = nt; form[2] = vec ? 1 : pairs ? 2 : 0;
+            return HS_BWD_ROUTE_K1M;
+        }
+    }
+    // output-channel block: as many channels (whole groups when the convolution is grouped) as fit beside the X tile
+    const int cin_g = c_in / groups, cout_g = c_out / groups;
+    const size_t npix = (size_t)ph * pw, tpos = (size_t)(ph + 2 * pad) * (pw + 2 * pad);
+    int ob = 0;
+    size_t lds = 0;
+    for (const size_t budget : {(size_t)64 * 1024, (size_t)150 * 1024}) {
+        if (groups == 1) {
+            const size_t xb = (size_t)c_in * tpos * sizeof(float);
+            if (xb + npix * sizeof(float) > budget) continue;
+            ob = (int)((budget - xb) / (npix * sizeof(float)));
+            ob = ob > c_out ? c_out : ob;
+            lds = xb + (size_t)ob * npix * sizeof(float);
+        } else {
+            const size_t per_group = ((size_t)cout_g * npix + (size_t)cin_g * tpos) * sizeof(float);
+            if (per_group > budget) continue;
+            int gb = (int)(budget / per_group);
+            gb = gb > groups ? groups : gb;
+            ob = gb * cout_g;
+            lds = (size_t)gb * per_group;
+        }
+        break;
+    }
+    if (ob <= 0) return HS_ERR_LDS;
+    form[0] = ob; form[1] = (c_out + ob - 1) / ob; form[2] = lds > 64 * 1024 ? 1 : 0;
+    if (lds_bytes) *lds_bytes = lds;
+    return HS_BWD_ROUTE_GENERIC;
 }
 
 int hs::try_fast_bwd_w(int dtype, const void* x, const void* dy, int batch, int c_in, int H, int W, int fh, int fw, int c_out, int k,
                        int pad, int pad_mode, int groups, void* dbank, long ld, hipStream_t stream) {
-    if (H % fh || W % fw || !storage_known(dtype)) return 1;
+    int form[4];
+    const int route = bwd_w_form(dtype, ((size_t)x) | ((size_t)dy), batch, c_in, H, W, fh, fw, c_out, k, pad, pad_mode, groups, form, nullptr);
+    if (route != HS_BWD_ROUTE_DW3 && route != HS_BWD_ROUTE_TINY && route != HS_BWD_ROUTE_K1M) return 1;
     ConvBwdArgs a;
     fast_args(a, nullptr, ld, batch, c_in, H, W, fh, fw, c_out);
     a.x = (const float*)x; a.dy = (const float*)dy; a.dbank = (float*)dbank;
-    if (k == 3 && pad == 1 && pad_mode == HS_PAD_ZEROS && groups == c_in && c_in == c_out && (c_in + 3) / 4 <= 65535) {
+    if (route == HS_BWD_ROUTE_DW3) {
         const dim3 grid((unsigned)(batch * fh * fw), (c_in + 3) / 4);
-        const bool pair = dw3_pairs(a, x, dy);
+        const bool pair = form[0] != 0;
         with_storage(dtype, [&](auto tag) {
             using T = decltype(tag);
             if (pair) hipLaunchKernelGGL(patch_dw3_bwd_weight_pair_kernel<T>, grid, dim3(256), 0, stream, a);
@@ -1272,7 +1356,7 @@ int hs::try_fast_bwd_w(int dtype, const void* x, const void* dy, int batch, int 
         });
         return launch_status();
     }
-    if (k == 1 && groups == 1 && a.ph * a.pw < 16 && (long)c_out * c_in < (1 << 21) && (size_t)(c_out + c_in) * 17 * 4 <= 64 * 1024) {
+    if (route == HS_BWD_ROUTE_TINY) {
         const dim3 gridt((unsigned)(batch * fh * fw));
         const size_t lds = (size_t)(c_out + c_in) * 17 * 4;
         with_storage(dtype, [&](auto tag) {
@@ -1280,12 +1364,9 @@ int hs::try_fast_bwd_w(int dtype, const void* x, const void* dy, int batch, int 
         });
         return launch_status();
     }
-    if (k != 1 || groups != 1 || a.ph * a.pw < 16) return 1;
-    const bool vec = (a.pw & 3) == 0 && ((a.ph * a.pw) & 15) == 0 && (W & 3) == 0 &&
-                     ((((size_t)x) | ((size_t)dy)) & (4 * storage_bytes(dtype) - 1)) == 0;           // four elements per load, either storage type
-    const int mt = (c_out + 15) / 16, nt = (c_in + 15) / 16;
+    const int mt = form[0], nt = form[1];
+    const bool vec = form[2] == 1, pairs = form[2] == 2;
     const dim3 grid((unsigned)(batch * fh * fw));
-    const bool pairs = !vec && (a.pw & 1) == 0 && (W & 1) == 0 && ((((size_t)x) | ((size_t)dy)) & 7) == 0;       // either storage type
 #define HS_BW(MTV, NTV) if (mt == MTV && nt == NTV) { \
         with_storage(dtype, [&](auto tag) { \
             using T = decltype(tag); \
@@ -1296,7 +1377,7 @@ int hs::try_fast_bwd_w(int dtype, const void* x, const void* dy, int batch, int 
         return launch_status(); }
     HS_BW(1, 1) HS_BW(1, 2) HS_BW(1, 3) HS_BW(1, 4) HS_BW(2, 1) HS_BW(2, 2) HS_BW(2, 3) HS_BW(2, 4) HS_BW(3, 1) HS_BW(3, 2) HS_BW(4, 1) HS_BW(4, 2)
 #undef HS_BW
-    return 1;
+    return HS_ERR_UNSUPPORTED;                                          // as in try_fast_bwd_in
 }
 
 static int fill_bwd(ConvBwdArgs& a, const float* x, const float* dy, const float* bank, int64_t ld, int32_t batch,
@@ -1349,37 +1430,41 @@ extern "C" int hs_patch_conv_bwd_weight(const float* x, const float* dy, int32_t
                                      (hipStream_t)stream);
         if (r != 1) return r;
     }
-    // output-channel block: as many channels (whole groups when the convolution is grouped) as fit beside the X tile
-    const size_t npix = (size_t)a.ph * a.pw, tpos = (size_t)(a.ph + 2 * pad) * (a.pw + 2 * pad);
-    int ob = 0;
+    int form[4];
     size_t lds = 0;
-    for (const size_t budget : {(size_t)64 * 1024, (size_t)150 * 1024}) {
-        if (groups == 1) {
-            const size_t xb = (size_t)c_in * tpos * sizeof(float);
-            if (xb + npix * sizeof(float) > budget) continue;
-            ob = (int)((budget - xb) / (npix * sizeof(float)));
-            ob = ob > c_out ? c_out : ob;
-            lds = xb + (size_t)ob * npix * sizeof(float);
-        } else {
-            const size_t per_group = ((size_t)a.cout_g * npix + (size_t)a.cin_g * tpos) * sizeof(float);
-            if (per_group > budget) continue;
-            int gb = (int)(budget / per_group);
-            gb = gb > groups ? groups : gb;
-            ob = gb * a.cout_g;
-            lds = (size_t)gb * per_group;
-        }
-        break;
-    }
-    if (ob <= 0) return HS_ERR_LDS;
+    st = bwd_w_form(HS_DTYPE_F32, ((size_t)x) | ((size_t)dy), batch, c_in, H, W, fh, fw, c_out, k, pad, pad_mode, groups, form, &lds);
+    if (st != HS_BWD_ROUTE_GENERIC) return st < 0 ? st : HS_ERR_UNSUPPORTED;
+    const int ob = form[0];
     if (lds > 64 * 1024) {
         static std::atomic<unsigned long long> done{0};
         const int e = allow_full_lds((const void*)patch_conv_bwd_weight_kernel, done);
         if (e != HS_OK) return e;
     }
-    const unsigned nblk = (unsigned)((c_out + ob - 1) / ob);
+    const unsigned nblk = (unsigned)form[1];
     hipLaunchKernelGGL(patch_conv_bwd_weight_kernel, dim3((unsigned)(batch * fh * fw), nblk), dim3(256), lds,
                        (hipStream_t)stream, a, ob);
     return launch_status();
+}
+
+// Which kernel hs_patch_conv_bwd_input (which = 0) / hs_patch_conv_bwd_weight (which = 1) -- and hs_patch_conv_plain_bwd_in / _bwd_w for the
+// fast forms -- launch for these arguments: the launchers' own predicates, nothing launched.  align_a / align_b: the two tensors' addresses
+// modulo 16 (dy and dx; x and dy).
+extern "C" int hs_patch_conv_bwd_route(int32_t which, int32_t dtype, int32_t align_a, int32_t align_b, int64_t ld, int32_t batch, int32_t c_in,
+                                       int32_t H, int32_t W, int32_t fh, int32_t fw, int32_t c_out, int32_t k, int32_t pad, int32_t pad_mode,
+                                       int32_t groups, int32_t* route, int32_t* form) {
+    if (!route || !form || which < 0 || which > 1 || align_a < 0 || align_b < 0 || !storage_known(dtype)) return HS_ERR_BAD_ARG;
+    ConvBwdArgs a;
+    static const float probe = 0.0f;                                    // fill_bwd refuses a null dy; nothing reads it
+    const int st = fill_bwd(a, nullptr, &probe, nullptr, ld, batch, c_in, H, W, fh, fw, c_out, k, pad, pad_mode, groups);
+    if (st != HS_OK) return st;
+    const size_t addr = ((size_t)align_a | (size_t)align_b) & 15;
+    int f[4];
+    const int r = which == 0 ? bwd_in_form(dtype, addr, batch, c_in, H, W, fh, fw, c_out, k, pad, pad_mode, groups, f)
+                             : bwd_w_form(dtype, addr, batch, c_in, H, W, fh, fw, c_out, k, pad, pad_mode, groups, f, nullptr);
+    if (r < 0) return r;
+    *route = r;
+    for (int i = 0; i < 4; ++i) form[i] = f[i];
+    return HS_OK;
 }
 
 // ---- valid depthwise 3 x 3 on halo tiles (dw_tiles_*): the middle layer of a train-mode v1_0 inverted residual, tile image <-> (B, C, H, W)

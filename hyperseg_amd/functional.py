@@ -930,6 +930,32 @@ def patch_conv_route(shape, c_skip, c_prev, grid, c_out, k=1, padding=0, padding
     return CONV_ROUTES[r], form
 
 
+BWD_ROUTES = {0: 'dw3', 1: 'tiny', 2: 'k1m', 3: 'generic'}
+_BWD_LOADS = {0: 'scalar', 1: 'vec', 2: 'pairs'}
+
+
+def patch_conv_bwd_route(which, shape, c_in, grid, c_out, k=1, padding=0, padding_mode='reflect', groups=1, dtype=torch.float32, align=(0, 0),
+                         ld=0):
+    """(route, form) of the backward of ``patch_conv`` for x of ``shape`` = (B, H, W) and ``c_in`` channels (hs_patch_conv_bwd_route):
+    ``which`` = 'input' -> ('dw3', 'pairs' | 'single'), ('tiny', ''), ('k1m', 'ct2_kq1_px2'), ('generic', ''); ``which`` = 'weight' ->
+    ('dw3', 'pairs' | 'single'), ('tiny', ''), ('k1m', 'mt2_nt1_vec' | '..._pairs' | '..._scalar'), ('generic', 'ob6_blocks2_lds64' |
+    '..._lds150').  ``align``: the addresses modulo 16 of (dy, dx) / (x, dy).  ``ld``: the bank's row stride (0: the packed row).  Host only."""
+    code = {'input': 0, 'weight': 1}[which]
+    if ld == 0:
+        ld = c_out * max(c_in // groups, 1) * k * k
+    r, f = C.c_int32(-1), (C.c_int32 * 4)()
+    _hip.run.hs_patch_conv_bwd_route(code, DTYPE_CODES[dtype], int(align[0]) % 16, int(align[1]) % 16, ld, shape[0], c_in, shape[1], shape[2],
+                                     grid[0], grid[1], c_out, k, padding, PAD_MODES[padding_mode], groups, C.byref(r), f)
+    route = BWD_ROUTES[r.value]
+    if route == 'dw3':
+        return route, 'pairs' if f[0] else 'single'
+    if route == 'k1m':
+        return route, f'ct{f[0]}_kq{f[1]}_px{f[2]}' if code == 0 else f'mt{f[0]}_nt{f[1]}_{_BWD_LOADS[f[2]]}'
+    if route == 'generic' and code == 1:
+        return route, f'ob{f[0]}_blocks{f[1]}_lds{150 if f[2] else 64}'
+    return route, ''
+
+
 def ir_tile_map(reg, mode, pwr):
     """(n_pixel_tiles, array (n_tiles, 16, 3) of (u, v, live)) -- the fused inverted-residual kernel's tile map
     (host-side introspection, no GPU needed)."""

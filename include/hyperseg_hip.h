@@ -477,6 +477,27 @@ int hs_patch_conv_bwd_weight(const float* x, const float* dy, int32_t batch, int
                              int32_t fh, int32_t fw, int32_t c_out, int32_t k, int32_t pad, int32_t pad_mode,
                              int32_t groups, float* dbank, int64_t ld, void* stream);
 
+/* Which kernel the two launchers above take (which = 0: input gradient, 1: weight gradient), and hs_patch_conv_plain_bwd_in / _bwd_w
+ * below for the first three routes (host only, nothing launched; every predicate is the one the launcher dispatches on).  dtype: an
+ * hs_dtype; align_a / align_b: the addresses of the two tensors the alignment conditions read, modulo 16 (dy and dx for the input
+ * gradient, x and dy for the weight gradient: 0 for an allocator's tensor).  Writes *route and form[4]:
+ *   HS_BWD_ROUTE_DW3      depthwise 3 x 3 with zero padding: form[0] = 1 for the two-pixels-per-lane form (even patch and image widths,
+ *                         8-byte aligned tensors)
+ *   HS_BWD_ROUTE_TINY     k = 1, groups = 1, patches of fewer than 16 pixels (input gradient: c_out <= 1024; weight gradient:
+ *                         (c_out + c_in) * 17 * 4 bytes of LDS <= 64 KB)
+ *   HS_BWD_ROUTE_K1M      k = 1, groups = 1, patches of >= 16 pixels, f32 matrix cores.  Input gradient: form = {CT, KQ (16-channel tiles
+ *                         of c_in / c_out), pixels per lane (1 | 2)}; weight gradient: form = {MT, NT (tiles of c_out / c_in), loads
+ *                         (1 = four elements, 2 = pairs, 0 = scalar)}
+ *   HS_BWD_ROUTE_GENERIC  everything else.  Weight gradient: form = {ob = output channels per block, blocks, 1 where the LDS request
+ *                         exceeds 64 KB} of the fp32 kernel; HS_ERR_LDS where not one block fits. */
+#define HS_BWD_ROUTE_DW3 0
+#define HS_BWD_ROUTE_TINY 1
+#define HS_BWD_ROUTE_K1M 2
+#define HS_BWD_ROUTE_GENERIC 3
+int hs_patch_conv_bwd_route(int32_t which, int32_t dtype, int32_t align_a, int32_t align_b, int64_t ld, int32_t batch, int32_t c_in,
+                            int32_t H, int32_t W, int32_t fh, int32_t fw, int32_t c_out, int32_t k, int32_t pad, int32_t pad_mode,
+                            int32_t groups, int32_t* route, int32_t* form);
+
 /* Training-path twins with a storage type: HS_DTYPE_F32, or HS_DTYPE_BF16 = bf16 storage of the ACTIVATIONS and their gradients
  * (x, y, dy, dx read and written as bf16: half the HBM bytes) with fp32 accumulation (BASELINE config 5; the reference has no
  * reduced-precision path: SURVEY 8d).  `bank` and `dbank` are fp32 (const float* / float*) for either dtype: the bank comes out of

@@ -164,13 +164,19 @@ def bilinear_with_grads(fn, a, b_, r):
 
 # ------------------------------------------------------------------------------------------------------------ BatchNorm + ReLU6
 
-def bn_relu6(x, weight, bias, eps=1e-5, relu6=True):
-    """Train-mode batch_norm (batch statistics, biased variance) + relu6."""
+def _act_arg(relu6, act):
+    """``act`` = 'none' | 'relu' | 'relu6' names the activation where given; ``relu6`` (True / False, and 'relu') is the older spelling."""
+    return relu6 if act is None else {'none': False, 'relu': 'relu', 'relu6': True}[act]
+
+
+def bn_relu6(x, weight, bias, eps=1e-5, relu6=True, act=None):
+    """Train-mode batch_norm (batch statistics, biased variance) + relu6 (``relu6`` = 'relu': + relu; False: nothing)."""
+    relu6 = _act_arg(relu6, act)
     y = F.batch_norm(x, None, None, weight, bias, True, 0.0, eps)
-    return F.relu6(y) if relu6 else y
+    return F.relu(y) if relu6 == 'relu' else F.relu6(y) if relu6 else y
 
 
-def bn_train_ref(x, weight, bias, r, eps=1e-5, relu6=True, momentum=0.1, rm0=None, rv0=None, r_err=None):
+def bn_train_ref(x, weight, bias, r, eps=1e-5, relu6=True, momentum=0.1, rm0=None, rv0=None, r_err=None, act=None):
     """The float64 values of train-mode batch_norm (+ relu6) over dim 1 of ``x`` and of its adjoint for the upstream ``r``, each with the
     bound's mag64 and, where needed, an absolute ``extra`` -- derived for the algorithm the kernels document (hs_train_aux.hip): sums over
     the n elements of a channel taken about the channel's first element c, d = x - c; mean = c + E[d], var = E[d^2] - E[d]^2;
@@ -186,6 +192,7 @@ def bn_train_ref(x, weight, bias, r, eps=1e-5, relu6=True, momentum=0.1, rm0=Non
     ``r_err``: an absolute bound on the error of the upstream gradient the kernel sees (it is another kernel's fp16 output); it enters
     the extras exactly like A's terms, with |r| replaced by r_err over all elements.
     Returns {name: (ref64, mag64, extra64)} for y, dx, dg, db, mean, var, rm, rv and 'z_mag' (the pre-activation's mag64), 'n'."""
+    relu6 = _act_arg(relu6, act)
     c = x.shape[1]
     dims = [i for i in range(x.dim()) if i != 1]
     shp = [1, c] + [1] * (x.dim() - 2)
@@ -206,8 +213,11 @@ def bn_train_ref(x, weight, bias, r, eps=1e-5, relu6=True, momentum=0.1, rm0=Non
     X = invstd * Mm + xh.abs() * K
     z = w_ * xh + b_
     z_mag = w_.abs() * (X + invstd * (x.abs() + mean.abs())) + b_.abs()
-    amb = ((z.abs() <= E * z_mag) | ((z - 6).abs() <= E * z_mag)) if relu6 else torch.zeros_like(z, dtype=torch.bool)
-    mask = ((z > 0) & (z < 6)).double() if relu6 else torch.ones_like(z)
+    if relu6 == 'relu':                             # one threshold: the unit is undecided within E mag z of 0 only
+        amb, mask = z.abs() <= E * z_mag, (z > 0).double()
+    else:
+        amb = ((z.abs() <= E * z_mag) | ((z - 6).abs() <= E * z_mag)) if relu6 else torch.zeros_like(z, dtype=torch.bool)
+        mask = ((z > 0) & (z < 6)).double() if relu6 else torch.ones_like(z)
     g = r * mask
     loose = r.abs() * amb + (r_err if r_err is not None else 0.0) * torch.ones_like(r)
     xdb, xdg = loose.sum(dims, keepdim=True), (loose * xh.abs()).sum(dims, keepdim=True)
@@ -268,7 +278,7 @@ def round16(t):
     return t.half().double()
 
 
-def bn_linear_ref(x, weight, bias, bank, r, linear, terms, eps=1e-5, round_copy=False):
+def bn_linear_ref(x, weight, bias, bank, r, linear, terms, eps=1e-5, round_copy=False, half=True):
     """y = linear(relu6(batch_norm(x)), bank) and its adjoint for the upstream ``r``, with the bound's mag64 / extra64 per result.
     ``linear(z, bank)`` is one of the per-patch statements above (linear in each operand); ``terms`` = (forward, input adjoint, bank
     adjoint) products per output.  ``round_copy``: the two-step route stores the normalised copy z as binary16 between its two kernels
@@ -279,12 +289,14 @@ def bn_linear_ref(x, weight, bias, bank, r, linear, terms, eps=1e-5, round_copy=
     Error that enters through an operand is pushed through the next statement on absolute values:
       e_z  = E z_mag (ReLU6 is 1-Lipschitz), plus -- rounded copy -- |rn(a) - rn(b)| <= |a - b| + ulp/2(a) + ulp/2(b): 2 (2^-11 |z| + 2^-24);
       e_dz = (terms_in + 2) 2^-23 mag dz + 2 (2^-11 |dz| + 2^-24), likewise;
-      y: extra = linear(e_z, |bank|);  dbank: extra = adjoint_bank(e_z, |r|);  dx, dg, db: bn_train_ref's ``r_err`` = e_dz."""
+      y: extra = linear(e_z, |bank|);  dbank: extra = adjoint_bank(e_z, |r|);  dx, dg, db: bn_train_ref's ``r_err`` = e_dz.
+    ``half=False``: fp32 storage -- z and dz are stored as computed, so nothing is rounded to binary16 and the 2^-11 / 2^-24 terms drop:
+    e_z = E z_mag, e_dz = (terms_in + 2) 2^-23 mag dz + the share of e_z that dz's own operand carries (none: dz reads r and the bank)."""
     t_fwd, t_in, t_w = terms
     fwd = bn_train_ref(x, weight, bias, torch.zeros_like(x), eps, True)
     z = fwd['y'][0]
     e_z = fwd['E'] * fwd['z_mag']
-    if round_copy:
+    if round_copy and half:
         e_z = e_z * (1 + U16) + 2 * (U16 * z.abs() + SUB16)
         z = round16(z)
     lin = bilinear_with_grads(linear, z, bank, r)
@@ -292,8 +304,8 @@ def bn_linear_ref(x, weight, bias, bank, r, linear, terms, eps=1e-5, round_copy=
     y_extra = linear(za, ba)
     w_extra = torch.autograd.grad(y_extra, ba, r.abs())[0]
     dz, dz_mag = lin['da']
-    e_dz = sum_bound(t_in, dz_mag) + 2 * (U16 * dz.abs() + SUB16)
-    bwd = bn_train_ref(x, weight, bias, round16(dz), eps, True, r_err=e_dz)
+    e_dz = sum_bound(t_in, dz_mag) + (2 * (U16 * dz.abs() + SUB16) if half else 0.0)
+    bwd = bn_train_ref(x, weight, bias, round16(dz) if half else dz, eps, True, r_err=e_dz)
     out = dict(y=(lin['y'][0], lin['y'][1], y_extra.detach(), t_fwd), dbank=(lin['db'][0], lin['db'][1], w_extra, t_w))
     for k in ('dx', 'dg', 'db', 'rm', 'rv'):
         out[k] = bwd[k] + (bwd['n'],)
