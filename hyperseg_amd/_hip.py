@@ -198,6 +198,7 @@ SIGNATURES = {
     'hs_stem_dw_u8_fwd': ([vp, i32, vp, i32, i32, i32, vp, i32, vp, vp, i32, i32, i32, i32, vp, i32, i32, i32, vp, vp, vp, vp, vp], STATUS),
     'hs_overlay_fwd': ([vp, vp, i32, i32, i32, i32, vp, i32, i32, vp, vp], STATUS),
     'hs_upsample_overlay_fwd': ([vp, i32, i32, i32, i32, i32, i32, vp, i32, vp, i32, i32, vp, vp, vp], STATUS),
+    'hs_upsample2_overlay_fwd': ([vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, i32, vp, i32, i32, vp, vp, vp], STATUS),
     'hs_confidence_fwd': ([vp, i32, i32, i32, i32, i32, C.c_float, i32, vp, vp, vp], STATUS),
     'hs_upsample_confidence_fwd': ([vp, i32, i32, i32, i32, i32, i32, i32, C.c_float, i32, vp, vp, vp], STATUS),
     'hs_upsample2_confidence_fwd': ([vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, C.c_float, i32, vp, vp, vp], STATUS),

@@ -2,6 +2,10 @@
 // chain tensor2rgb(blend_seg(img, pred, color_map, alpha, ignore_index)) (hyperseg/test.py:230-292, utils/seg_utils.py:82-103,
 // utils/img_utils.py:62-75) for a frame normalised with mean = std = 0.5 -- either from finished masks (hs_overlay_fwd) or as the epilogue
 // of the final upsample + arg-max launch, where every output pixel's class index already sits in a register (hs_upsample_overlay_fwd).
+// An overlay served at ANOTHER size than the model's frame -- the camera frame's, when the model sees a down-scaled copy of it -- takes
+// hs_upsample2_overlay_fwd: the decoder's final resize composed with the one to that size (test.py:167-168: the logits are resized before
+// the arg-max), the class indices of hs_upsample2_confusion_fwd's masks-only call, blended over the frames at that size in the same
+// launch; neither resized logits tensor nor a frame-size mask ever exists in memory.
 //
 // The arithmetic is data (hyperseg_amd.utils.inference.Overlay builds it on the host, in float32, by the reference's own operations):
 //   tables = [ A (256) | A1 (256) | S (n x 3) ],  A[v] = img(v) * am,  A1[v] = img(v),  S[c][ch] = (color[c][ch] / 128 - 1) * (1 - am)
@@ -184,6 +188,76 @@ void upsample_overlay_kernel(const float* __restrict__ x, int B, int C, int Hi, 
     overlay_row4<HWC>(tab, frames + b * plane * 3, out + b * plane * 3, plane, pix, live, idx, ncol, ignore);
 }
 
+// Two resizes composed in registers (x -> mid -> frame: the decoder's final resize, then the one to the camera frame's size), both stages
+// exact 2x: argmax2x2x_block (hs_upsample_taps.h), four consecutive lanes per x block (yi, q) = 4 x 8 output block, after which all four
+// lanes hold the block's 32 class indices; lane `sub` takes output row 4 yi + sub: two dword stores of masks, two rows of four blended.
+template <bool HWC>
+__global__ __launch_bounds__(OVL_THREADS)
+void upsample2x2x_overlay_kernel(const float* __restrict__ x, int B, int C, int Hi, int Wi, const uint8_t* __restrict__ frames,
+                                 const float* __restrict__ tables, int ncol, int ignore, uint8_t* __restrict__ mask,
+                                 uint8_t* __restrict__ out) {
+    __shared__ float tab[OVL_TABLE_FLOATS];
+    overlay_tables_to_lds(tables, tab, ncol);
+    __syncthreads();
+    const int wq = Wi >> 1;
+    const size_t n = (size_t)B * Hi * wq;
+    const int Wo = 4 * Wi;
+    const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int sub = (int)(t & 3);
+    const size_t e0 = t >> 2;
+    const size_t e = e0 < n ? e0 : n - 1;                    // surplus lanes shadow the last block (argmax2x2x_block: convergent)
+    const int q = e % wq; size_t r = e / wq;
+    const int yi = r % Hi; const size_t b = r / Hi;
+    const float* __restrict__ xb = x + b * C * Hi * Wi;
+    int idx[4][8];
+    argmax2x2x_block(xb, C, Hi, Wi, yi, q, sub, idx);
+    if (e0 >= n) return;
+    int lo[4], hi[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        lo[k] = sub == 0 ? idx[0][k] : sub == 1 ? idx[1][k] : sub == 2 ? idx[2][k] : idx[3][k];
+        hi[k] = sub == 0 ? idx[0][4 + k] : sub == 1 ? idx[1][4 + k] : sub == 2 ? idx[2][4 + k] : idx[3][4 + k];
+    }
+    const size_t plane = (size_t)4 * Hi * Wo;
+    const size_t pix = (size_t)(4 * yi + sub) * Wo + 8 * q;  // of the lane's row, inside image b
+    uint8_t* dst = mask + b * plane + pix;
+    *reinterpret_cast<uchar4*>(dst) = make_uchar4(lo[0], lo[1], lo[2], lo[3]);
+    *reinterpret_cast<uchar4*>(dst + 4) = make_uchar4(hi[0], hi[1], hi[2], hi[3]);
+    overlay_row4<HWC>(tab, frames + b * plane * 3, out + b * plane * 3, plane, pix, 4, lo, ncol, ignore);
+    overlay_row4<HWC>(tab, frames + b * plane * 3, out + b * plane * 3, plane, pix + 4, 4, hi, ncol, ignore);
+}
+
+// Two resizes composed, any first and any second stage (down-sampling and identity stages included): argmax2_row4 (hs_upsample_taps.h),
+// otherwise upsample_overlay_kernel.
+template <bool HWC>
+__global__ __launch_bounds__(OVL_THREADS)
+void upsample2_overlay_kernel(const float* __restrict__ x, int B, int C, Stages2 s, const uint8_t* __restrict__ frames,
+                              const float* __restrict__ tables, int ncol, int ignore, uint8_t* __restrict__ mask,
+                              uint8_t* __restrict__ out) {
+    __shared__ float tab[OVL_TABLE_FLOATS];
+    overlay_tables_to_lds(tables, tab, ncol);
+    __syncthreads();
+    const int Ho = s.Ho, Wo = s.Wo, wq = (Wo + 3) / 4;
+    const size_t n = (size_t)B * Ho * wq;
+    const size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= n) return;
+    const int q = e % wq; size_t r = e / wq;
+    const int yo = r % Ho; const size_t b = r / Ho;
+    const Row4x2 t = row4x2_taps(yo, q, s);
+    const float* __restrict__ xb = x + b * C * s.Hi * s.Wi;
+    int idx[4];
+    argmax2_row4(xb, C, s.Hi, s.Wi, t, idx);
+    const size_t plane = (size_t)Ho * Wo, pix = (size_t)yo * Wo + 4 * q;
+    const int live = min(4, Wo - 4 * q);
+    uint8_t* dst = mask + b * plane + pix;
+    if (live == 4 && aligned_to(dst, 4)) {
+        *reinterpret_cast<uchar4*>(dst) = make_uchar4(idx[0], idx[1], idx[2], idx[3]);
+    } else {
+        for (int i = 0; i < live; ++i) dst[i] = (uint8_t)idx[i];
+    }
+    overlay_row4<HWC>(tab, frames + b * plane * 3, out + b * plane * 3, plane, pix, live, idx, ncol, ignore);
+}
+
 static bool overlay_args_ok(int layout, const float* tables, int num_colors) {
     return tables && (layout == HS_LAYOUT_HWC || layout == HS_LAYOUT_CHW) && num_colors >= 1 && num_colors <= OVL_MAX_COLORS;
 }
@@ -229,5 +303,36 @@ extern "C" int hs_upsample_overlay_fwd(const float* x, int32_t batch, int32_t ch
     const float sy = (float)Hi / (float)Ho, sx = (float)Wi / (float)Wo;
     if (hwc) hipLaunchKernelGGL(upsample_overlay_kernel<true>, grid, block, 0, s, x, batch, channels, Hi, Wi, Ho, Wo, sy, sx, frames, tables, num_colors, ignore_index, mask, overlay);
     else hipLaunchKernelGGL(upsample_overlay_kernel<false>, grid, block, 0, s, x, batch, channels, Hi, Wi, Ho, Wo, sy, sx, frames, tables, num_colors, ignore_index, mask, overlay);
+    return launch_status();
+}
+
+extern "C" int hs_upsample2_overlay_fwd(const float* x, int32_t batch, int32_t channels, int32_t Hi, int32_t Wi, int32_t Hm, int32_t Wm,
+                                        int32_t Ho, int32_t Wo, const uint8_t* frames, int32_t layout, const float* tables,
+                                        int32_t num_colors, int32_t ignore_index, uint8_t* mask, uint8_t* overlay, void* stream) {
+    if (!x || !frames || !mask || !overlay || batch <= 0 || channels <= 0 || Hi <= 0 || Wi <= 0 || Hm <= 0 || Wm <= 0 || Ho <= 0 || Wo <= 0)
+        return HS_ERR_BAD_ARG;
+    if (!overlay_args_ok(layout, tables, num_colors)) return HS_ERR_BAD_ARG;
+    if (channels > 256) return HS_ERR_UNSUPPORTED;           // uint8 class indices
+    // int pixel indices inside a plane (the taps), an unsigned grid
+    if ((long)Hi * Wi > 0x7fffffffL - 4096 || (long)Hm * Wm > 0x7fffffffL - 4096 || (long)Ho * Wo > 0x7fffffffL - 4096) return HS_ERR_UNSUPPORTED;
+    hipStream_t s = (hipStream_t)stream;
+    const bool hwc = layout == HS_LAYOUT_HWC;
+    if (is_exact2x(Hi, Wi, Hm, Wm) && is_exact2x(Hm, Wm, Ho, Wo)) {       // the form hs_upsample2_confusion_fwd takes for this pair: same masks
+        if ((reinterpret_cast<uintptr_t>(mask) & 3) != 0) return HS_ERR_UNSUPPORTED;      // it stores the masks as dwords
+        const size_t n2 = (size_t)batch * Hi * (Wi / 2) * 4;         // 4 lanes per 4x8 output block
+        const size_t nb = (n2 + OVL_THREADS - 1) / OVL_THREADS;
+        if (nb > 0x7fffffffu) return HS_ERR_UNSUPPORTED;
+        const dim3 grid((unsigned)nb), block(OVL_THREADS);
+        if (hwc) hipLaunchKernelGGL(upsample2x2x_overlay_kernel<true>, grid, block, 0, s, x, batch, channels, Hi, Wi, frames, tables, num_colors, ignore_index, mask, overlay);
+        else hipLaunchKernelGGL(upsample2x2x_overlay_kernel<false>, grid, block, 0, s, x, batch, channels, Hi, Wi, frames, tables, num_colors, ignore_index, mask, overlay);
+        return launch_status();
+    }
+    const size_t n = (size_t)batch * Ho * ((Wo + 3) / 4);
+    const size_t nb = (n + OVL_THREADS - 1) / OVL_THREADS;
+    if (nb > 0x7fffffffu) return HS_ERR_UNSUPPORTED;
+    const dim3 grid((unsigned)nb), block(OVL_THREADS);
+    const Stages2 st = stages2(Hi, Wi, Hm, Wm, Ho, Wo);
+    if (hwc) hipLaunchKernelGGL(upsample2_overlay_kernel<true>, grid, block, 0, s, x, batch, channels, st, frames, tables, num_colors, ignore_index, mask, overlay);
+    else hipLaunchKernelGGL(upsample2_overlay_kernel<false>, grid, block, 0, s, x, batch, channels, st, frames, tables, num_colors, ignore_index, mask, overlay);
     return launch_status();
 }

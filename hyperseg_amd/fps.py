@@ -11,7 +11,7 @@ Reproduces the reference's protocol on synthetic frames (no dataset, checkpoint 
 ``torch.cuda.synchronize()`` is guarded so that the plumbing also runs on a CPU-only box (with a CPU-capable model).
 
     python -m hyperseg_amd.fps --config hyperseg-m --iterations 200 [--prepare] [--graph] [--remove-bn] [--batch-size 1]
-                               [--confidence] [--uint8 [--layout hwc|chw] [--overlay] [--resize H W [--camera-size H W]]] [--label-size H W] [--fused-metrics]
+                               [--confidence] [--uint8 [--layout hwc|chw] [--overlay] [--resize H W [--camera-size H W] [--overlay-at-camera]]] [--label-size H W] [--fused-metrics]
                                [--hflip [--pyramid N]]
 
 ``--hflip`` feeds every frame as a list (``--pyramid N``: N entries, the smaller ones ``F.avg_pool2d`` of the frame -- NOT ``cv2.pyrDown``) and
@@ -179,13 +179,15 @@ def _sync(device):
 
 
 @torch.no_grad()
-def measure_fps(model, batches, device, num_classes, passes=2, fused_metrics=False, overlay=False, label_codec=None, confidence=False):
+def measure_fps(model, batches, device, num_classes, passes=2, fused_metrics=False, overlay=False, label_codec=None, confidence=False,
+                overlay_size=None):
     """``batches``: list of (input, target) host tensors (inputs pinned when CUDA is used).  Runs ``passes`` passes over
     them and reports the LAST one (the reference's warm-up + timed pass).  Returns a dict.  ``fused_metrics``: where the
     model has ``evaluate`` (a HyperGen, a GraphedModel) the frame is scored by the forward's last launch -- INSIDE the timed
     region, which the reference's protocol keeps outside it; models without it are scored as before.  ``overlay``: every frame
     is served by ``model.overlay`` (masks + the uint8 display blended with ``overlay_style``) instead of the forward, inside the
-    timed region; the masks are scored outside it as the reference's protocol does.  Targets of another size than the frame's are
+    timed region; the masks are scored outside it as the reference's protocol does.  ``overlay_size`` (with ``overlay``): the display is
+    served at that (H, W) -- the camera frame's, with ``input_resize`` set -- by ``model.overlay(x, size=overlay_size)``.  Targets of another size than the frame's are
     scored at their own resolution: the logits are resized to the label before the arg-max (test.py:167-168), outside the timed region
     on the unfused route; a model that returns masks hands them out at the label's size where its ``segment`` takes ``size=``.
     ``confidence``: every frame is served by ``model.confidence`` (masks + the confidence map in ``confidence_style``) instead of the
@@ -217,7 +219,7 @@ def measure_fps(model, batches, device, num_classes, passes=2, fused_metrics=Fal
             if fused:
                 pred = model.evaluate(x, target) if owns else model.evaluate(x, target, conf)
             elif overlay:
-                pred = model.overlay(x)[0]
+                pred = model.overlay(x)[0] if overlay_size is None else model.overlay(x, size=overlay_size)[0]
             elif confidence:
                 pred = model.confidence(x)[0]
             else:
@@ -355,6 +357,9 @@ def main(argv=None):
     ap.add_argument('--overlay', action='store_true',
                     help="serve the display as well (model.overlay): the class map coloured with a seeded synthetic palette and alpha-blended "
                          "over the uint8 frame by the forward's last launch, inside the timed region; needs --uint8")
+    ap.add_argument('--overlay-at-camera', action='store_true',
+                    help="on top of --uint8 --overlay --resize H W: serve masks and overlay at --camera-size, blended over the camera frame "
+                         "itself (model.overlay(x, size=camera size)): both resizes of the logits and the blend in the forward's last launch")
     ap.add_argument('--confidence', action='store_true',
                     help="serve the confidence map as well (model.confidence): beside the masks, every pixel's soft-max probability of its "
                          "class as uint8, from the forward's last launch, inside the timed region")
@@ -397,6 +402,8 @@ def main(argv=None):
         args.graph = True
     if args.overlay and not args.uint8:
         raise SystemExit('--overlay blends over the uint8 frames: it needs --uint8')
+    if args.overlay_at_camera and (not args.overlay or args.resize is None):
+        raise SystemExit('--overlay-at-camera serves the overlay at the camera frame\'s size: it needs --overlay and --resize H W')
     if args.overlay and args.fused_metrics:
         raise SystemExit('--overlay and --fused-metrics both ride on the final upsample launch: one of them per run')
     if args.confidence and (args.overlay or args.fused_metrics):
@@ -436,6 +443,8 @@ def main(argv=None):
         model.input_resize = FrameResize(args.resize, 'bilinear', args.layout)
         frame_size = tuple(args.camera_size) if args.camera_size is not None else (2 * args.resize[0], 2 * args.resize[1])
         label_size = tuple(args.resize) if label_size is None else label_size       # the masks come at the resized frame's size
+        if args.overlay_at_camera and args.label_size is None:
+            label_size = frame_size                                                   # ... or, served at the camera's size, at that
     if args.overlay:
         from .utils.inference import Overlay
         palette = torch.randint(0, 256, (spec['num_classes'], 3), generator=torch.Generator().manual_seed(0))
@@ -469,7 +478,7 @@ def main(argv=None):
         uniq = [(pyramid_of(x, args.pyramid or 1, device), t) for x, t in uniq]
     batches = [uniq[i % len(uniq)] for i in range(args.iterations)]
     res = measure_fps(model, batches, device, spec['num_classes'], fused_metrics=args.fused_metrics, overlay=args.overlay, label_codec=codec,
-                      confidence=args.confidence)
+                      confidence=args.confidence, overlay_size=frame_size if args.overlay_at_camera else None)
     frame = uniq[0][0][0] if lists else uniq[0][0]
     if lists:
         from . import functional as HF
@@ -490,6 +499,8 @@ def main(argv=None):
         res.update(raw_labels=args.raw_labels, protocol=res['protocol'] + f' + raw {args.raw_labels} labels encoded on the device where they are scored')
     if args.overlay:
         res.update(overlay=True, protocol=res['protocol'] + " + uint8 overlay blended inside the timed region by the forward's last launch")
+    if args.overlay_at_camera:
+        res.update(overlay_size=list(frame_size), protocol=res['protocol'] + " at the camera frame's size, over the camera frame")
     if args.confidence:
         res.update(confidence=True, protocol=res['protocol'] + " + uint8 confidence map made inside the timed region by the forward's last launch")
     print(json.dumps(res))

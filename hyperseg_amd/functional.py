@@ -1960,6 +1960,32 @@ def upsample_overlay(x, size, frames, style, out=None):
     return mask, out
 
 
+@_on_operand_device
+def upsample2_overlay(x, mid_size, size, frames, style, out=None):
+    """``upsample_overlay`` over two composed resizes (hs_upsample2_overlay_fwd): the logits ``x`` resized to ``mid_size`` (the model's
+    frame) and from there to ``size`` (the camera frame's), arg-maxed and blended over ``frames`` (uint8, at ``size``, in ``style.layout``)
+    in one launch; neither resized tensor exists in memory.  Returns ``(masks, overlay)``: the masks bit-identical to
+    ``upsample2_argmax``'s, the overlay equal to ``overlay(masks, frames, style)``.  ``out`` and the errors raised are
+    ``upsample_overlay``'s, which this simply calls where one of the stages is the identity.  Capturable."""
+    b, c, hi, wi = _logits_shape(x)
+    (hm, wm), (ho, wo) = _size2(mid_size, 'mid_size'), _size2(size, 'size')
+    if (ho, wo) == (hm, wm) or (hi, wi) == (hm, wm):
+        return upsample_overlay(x, (ho, wo), frames, style, out=out)
+    if tuple(style.frame_size(frames)) != (b, ho, wo):
+        raise ValueError(f'the frames are {tuple(style.frame_size(frames))} (B, H, W), the masks will be {(b, ho, wo)}')
+    frames = _overlay_frames(frames, style)
+    if frames.device != x.device:
+        raise ValueError(f'the frames are on {frames.device}, the logits on {x.device}')
+    if c > 256:
+        raise ValueError('more than 256 logit channels: the masks are uint8')
+    out = _overlay_out(out, frames)
+    mask = torch.empty(b, ho, wo, device=x.device, dtype=torch.uint8)
+    _hip.run.hs_upsample2_overlay_fwd(_hip.dev_ptr(x, 'x'), b, c, hi, wi, hm, wm, ho, wo, frames.data_ptr(), _LAYOUT_CODES[style.layout],
+                                      _hip.dev_ptr(style.tables(x.device), 'tables'), style.num_colors, style.ignore_index,
+                                      mask.data_ptr(), out.data_ptr(), _hip.stream_ptr())
+    return mask, out
+
+
 def _confidence_operands(x, size, dtype, threshold, fill, out, name='x'):
     """What the three confidence wrappers share: checks (ValueError, before any launch), the uint8 masks and the confidence tensor at
     ``(B, *size)``.  Returns ``(b, c, hi, wi, tail, mask, conf)``: an entry is called with its shape arguments followed by ``*tail``."""

@@ -71,10 +71,13 @@ class Score(NamedTuple):
 
 class Blend(NamedTuple):
     """Colour the class map with ``style`` (a ``utils.inference.Overlay``) and blend it over the uint8 ``frames`` into ``out`` (None: a new
-    tensor)."""
+    tensor).  ``size``: the (H, W) of ``frames`` where that is another size than the model's frame (a camera frame the model sees
+    down-scaled): the logits are resized to it before the arg-max (test.py:167-168), masks and overlay are then at ``size``.  None: the
+    model's frame size."""
     frames: object
     style: object
     out: object
+    size: object = None
 
 
 class Deferred(NamedTuple):
@@ -126,7 +129,9 @@ class Epilogue:
 
     def apply(self, p, size):
         """The last level's output ``p`` -> the masks at ``size`` (the frame's), straight from the one launch; ``(masks, per_pixel)`` of a
-        validation step (per_pixel: f32 (B, H, W), what ``BootstrappedCrossEntropyLoss`` ranks), ``(masks, overlay)`` of a blend, ``(masks, conf)`` of a
+        validation step (per_pixel: f32 (B, H, W), what ``BootstrappedCrossEntropyLoss`` ranks), ``(masks, overlay)`` of a blend (at the blend's
+        ``size`` where it names another one: ``HF.upsample2_overlay``, both resizes composed; ``HF.upsample_overlay`` straight to it where ``p``
+        is at the frame's size already), ``(masks, conf)`` of a
         confidence epilogue (at ``out_size`` where one is given, both resizes composed in the one launch).  A
         score's target of another size than ``size`` is scored at ITS resolution, as test.py:167-168 does: the logits at ``size`` are
         resized once more, to the target's size, before the arg-max -- both resizes composed in the one launch, a single one where ``p``
@@ -160,8 +165,13 @@ class Epilogue:
         if self.blend is not None:
             if resized:
                 raise ValueError('the overlay is blended over the frames, at their size: another out_size does not go with a blend')
-            frames, style, out = self.blend
-            return HF.upsample_overlay(p, size, frames, style, out=out)
+            frames, style, out, at = self.blend
+            at = size if at is None else tuple(int(v) for v in at)
+            if at == size:
+                return HF.upsample_overlay(p, size, frames, style, out=out)
+            if tuple(p.shape[2:]) == size:                          # (no final resize to compose with: one stage, straight to the frames)
+                return HF.upsample_overlay(p, at, frames, style, out=out)
+            return HF.upsample2_overlay(p, size, at, frames, style, out=out)
         if self.confidence is not None:
             style = self.confidence
             if not resized:
@@ -465,7 +475,7 @@ class HyperGenBase(EpochOnModeSwitch, nn.Module):
         return loss.detach(), masks
 
     @torch.no_grad()
-    def overlay(self, x, frames=None, style=None, out=None):
+    def overlay(self, x, frames=None, style=None, out=None, size=None):
         """``segment(x)`` plus the display: returns ``(masks, overlay)`` -- the uint8 masks and the class map coloured and alpha-blended
         over the uint8 frames, as uint8 in the frames' layout (``style``: a ``utils.inference.Overlay``, default
         ``self.overlay_style``).  A uint8 ``x`` is its own frame; a float ``x`` needs ``frames=``, the uint8 frames of the same size.
@@ -473,11 +483,21 @@ class HyperGenBase(EpochOnModeSwitch, nn.Module):
         (``HF.upsample_overlay``) -- no further launch, no read of the device, whether the frame went into the stem launch or through
         ``image_ingest``.  Everything else -- list inputs, h-flip inference, training mode, CPU -- computes the masks the way
         ``segment()`` does (a list's from the launch that merges its passes, ``HF.tta_merge``) and calls ``style.blend``.  Same bytes on every route.  ``out``: a uint8 tensor of the frames' shape for
-        the overlay."""
+        the overlay.
+
+        ``size=(H, W)``: the display at that size instead of the model's frame -- the camera's, when ``input_resize`` shows the model a
+        down-scaled copy.  The logits are resized to it before the arg-max, as ``segment(size=)`` does (test.py:167-168); masks and overlay
+        are at ``(H, W)``.  The frames blended over are ``frames=`` ((B, H, W) frames), else a uint8 ``x`` whose own size is ``(H, W)`` --
+        the camera frame before ``input_resize``, or the frame itself where there is no resize -- else a ``ValueError`` naming both sizes.
+        The fused route composes both resizes and the blend in the forward's last launch (``HF.upsample2_overlay``; a decoder without
+        a final resize: ``HF.upsample_overlay`` straight to ``size``): neither logits tensor and no frame-size mask are written.  The
+        other routes resize the logits (``_logits_at``), arg-max them and call ``style.blend``.  Same bytes on every route."""
         style = self.overlay_style if style is None else style
         if style is None:
             raise TypeError('overlay() needs a style: set model.overlay_style = hyperseg_amd.Overlay(color_map, alpha, ignore_index, '
                             'layout) or pass style=')
+        if size is not None:
+            return self._overlay_at(x, frames, style, out, tuple(int(s) for s in size))
         x = self.resized(x)
         first = x if isinstance(x, torch.Tensor) else x[0]
         if frames is None:
@@ -498,6 +518,48 @@ class HyperGenBase(EpochOnModeSwitch, nn.Module):
                 return got
             raise RuntimeError('the decoder returned logits where its epilogue was asked for: nothing was blended')
         masks = self.segment(x)
+        blended = style.blend(frames.to(masks.device), masks)
+        if out is not None:
+            out.copy_(blended)
+            blended = out
+        return masks, blended
+
+    def _overlay_frames_at(self, x, frames, style, size):
+        """The frames ``overlay(x, frames, size=size)`` blends over: ``frames`` where given, else ``x`` (a list: its first entry) where it
+        is uint8 frames of ``size`` already -- the camera frame, before ``input_resize`` -- in the style's layout.  Raises ``ValueError``
+        unless they are (B, *size) frames."""
+        first = x if isinstance(x, torch.Tensor) else x[0]
+        if frames is None:
+            if first.dtype == torch.uint8:
+                if style.layout != self._require_norm().layout:
+                    raise ValueError(f"the input frames are '{self.input_norm.layout}' (model.input_norm), the style blends over "
+                                     f"'{style.layout}' frames")
+                own = tuple(style.frame_size(first)[1:])
+            else:
+                own = tuple(first.shape[2:])
+            if first.dtype != torch.uint8 or own != size:
+                raise ValueError(f'overlay(size={size}) blends over frames of that size: the input is {own} '
+                                 f'({str(first.dtype).replace("torch.", "")}), pass frames= with uint8 frames of {size}')
+            frames = first
+        want = (first.shape[0],) + size
+        if tuple(style.frame_size(frames)) != want:
+            raise ValueError(f'frames are {tuple(style.frame_size(frames))} (B, H, W), overlay(size=) needs {want}')
+        return frames
+
+    def _overlay_at(self, x, frames, style, out, size):
+        """``overlay`` with ``size=``: see there."""
+        frames = self._overlay_frames_at(x, frames, style, size)
+        x = self.resized(x)
+        first = x if isinstance(x, torch.Tensor) else x[0]
+        if size == self.frame_size(first, isinstance(x, torch.Tensor)):
+            return self.overlay(x, frames=frames, style=style, out=out)
+        fused = isinstance(x, torch.Tensor) and x.is_cuda and frames.is_cuda and not self.training and not self.inference_hflip
+        if fused:
+            got = self.process_single_tensor(x, epilogue=Epilogue(blend=Blend(frames, style, out, size)))
+            if isinstance(got, tuple):
+                return got
+            raise RuntimeError('the decoder returned logits where its epilogue was asked for: nothing was blended')
+        masks = self._logits_at(x, size).argmax(1).to(torch.uint8)
         blended = style.blend(frames.to(masks.device), masks)
         if out is not None:
             out.copy_(blended)

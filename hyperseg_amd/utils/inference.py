@@ -1111,32 +1111,46 @@ class GraphedModel(nn.Module):
         return self._replay(entry, [x, target], device)
 
     @torch.no_grad()
-    def overlay(self, x, frames=None):
+    def overlay(self, x, frames=None, size=None):
         """One replay per frame that also draws it: returns ``(masks, overlay)`` as ``model.overlay`` does, blended with
         ``model.overlay_style``.  A uint8 ``x`` is its own frame; a float ``x`` comes with its uint8 ``frames``.  Both may live on the
         device or in (pinned) host memory and are staged into static buffers of the graph.  The graph is the forward's chain of launches
         with the last one replaced by ``functional.upsample_overlay``, keyed like the uint8 ``forward`` graphs plus the style (the
         captured launch holds its tables, layout and ignore index).  Both returned tensors are graph-owned: valid until the next
         ``overlay`` of the same shape, which overwrites them (``clone_output=True`` hands out copies).  What the graph cannot serve
-        (``forward``'s list, and h-flip inference) takes ``model.overlay``'s eager routes."""
+        (``forward``'s list, and h-flip inference) takes ``model.overlay``'s eager routes.
+
+        ``size=(H, W)``: the overlay at that size, as ``model.overlay(..., size=)`` serves it -- over ``frames`` at ``size``, else over a
+        uint8 ``x`` of that size: the camera frame, with ``model.input_resize`` set.  The camera frame is staged once, into one static
+        buffer that feeds both the graph's resize node and its last launch (``functional.upsample2_overlay``); masks and overlay are
+        graph-owned at ``size``, and the size is part of the key."""
         model = self.model
         style = getattr(model, 'overlay_style', None)
+        size = None if size is None else tuple(int(s) for s in size)
         graphable = (style is not None and self._graphable(x) and x.dim() == 4 and not model.inference_hflip
-                     and (frames is not None or x.dtype == torch.uint8) and hasattr(model, 'process_single_tensor'))
+                     and (frames is not None or x.dtype == torch.uint8) and hasattr(model, 'process_single_tensor')
+                     and (size is None or hasattr(model, '_overlay_frames_at')))
         if not graphable:
             x, frames = self._to_model_device(x, frames)
-            return model.overlay(x, frames=frames)
+            return model.overlay(x, frames=frames) if size is None else model.overlay(x, frames=frames, size=size)
         device = next(model.parameters()).device
-        if frames is None and style.layout != model._require_norm().layout:
-            raise ValueError(f"the input frames are '{model.input_norm.layout}' (model.input_norm), the style blends over '{style.layout}' frames")
-        size = (x.shape[0],) + tuple(model.frame_size(x))
-        if frames is not None and tuple(style.frame_size(frames)) != size:
-            raise ValueError(f'frames are {tuple(style.frame_size(frames))} (B, H, W), the input is {size}')
-        key = ('overlay', tuple(x.shape), x.dtype, None if frames is None else tuple(frames.shape), device, self._norm_of(x), style)
+        if size is not None:
+            model._overlay_frames_at(x, frames, style, size)        # (raises unless there are frames at `size` to blend over)
+            if size == tuple(model.frame_size(x)):
+                size = None                                         # the model's frame: the graph it always was
+        if size is None:
+            if frames is None and style.layout != model._require_norm().layout:
+                raise ValueError(f"the input frames are '{model.input_norm.layout}' (model.input_norm), the style blends over '{style.layout}' frames")
+            shape = (x.shape[0],) + tuple(model.frame_size(x))
+            if frames is not None and tuple(style.frame_size(frames)) != shape:
+                raise ValueError(f'frames are {tuple(style.frame_size(frames))} (B, H, W), the input is {shape}')
+        key = ('overlay', tuple(x.shape), x.dtype, None if frames is None else tuple(frames.shape), device, self._norm_of(x), style, size)
         entry = self._graphs.get(key)
         inputs = [x] if frames is None else [x, frames]
         if entry is None:
             def run(xs, fs=None):
+                if size is not None:                 # (the camera frame: read by the resize node and by the last launch)
+                    return model.process_single_tensor(model.resized(xs), epilogue=Epilogue(blend=Blend(xs if fs is None else fs, style, None, size)))
                 xs = model.resized(xs)               # (a camera-size uint8 frame: the resize is the graph's first node)
                 return model.process_single_tensor(xs, epilogue=Epilogue(blend=Blend(xs if fs is None else fs, style, None)))
 

@@ -620,12 +620,21 @@ int hs_stem_dw_u8_fwd(const uint8_t* x, int32_t layout, const float* table, int3
  *   hs_overlay_fwd: from finished masks (batch, H, W) uint8; batch <= 65535.
  *   hs_upsample_overlay_fwd: hs_upsample_argmax_fwd (same taps, same arg-max rule, both of its forms) with the blend as the launch's
  *     epilogue: writes mask (batch, Ho, Wo), bit-identical to hs_upsample_argmax_fwd's, and overlay; frames are (batch, Ho, Wo) frames.
- *     mask 4-byte aligned where the exact-2x form applies, else HS_ERR_UNSUPPORTED. */
+ *     mask 4-byte aligned where the exact-2x form applies, else HS_ERR_UNSUPPORTED.
+ *   hs_upsample2_overlay_fwd: the overlay at another size than the model's frame (the camera frame's): the same over two composed resizes
+ *     x (Hi, Wi) -> (Hm, Wm) -> (Ho, Wo), in both forms of hs_upsample2_confusion_fwd (both stages exact 2x: one 3 x 4 neighbourhood of x
+ *     per 4 x 8 output block; any other pair, down-sampling and identity stages included): mask (batch, Ho, Wo) bit-identical to that
+ *     entry's masks-only call, overlay byte-identical to hs_overlay_fwd(mask, frames); frames are (batch, Ho, Wo) frames.  mask 4-byte
+ *     aligned where the 2x o 2x form applies, else HS_ERR_UNSUPPORTED; channels <= 256 and each plane below 2^31 - 4096 pixels, else
+ *     HS_ERR_UNSUPPORTED.  Neither resized logits tensor exists in memory; nothing is read back: capturable. */
 int hs_overlay_fwd(const uint8_t* masks, const uint8_t* frames, int32_t layout, int32_t batch, int32_t H, int32_t W,
                    const float* tables, int32_t num_colors, int32_t ignore_index, uint8_t* overlay, void* stream);
 int hs_upsample_overlay_fwd(const float* x, int32_t batch, int32_t channels, int32_t Hi, int32_t Wi, int32_t Ho, int32_t Wo,
                             const uint8_t* frames, int32_t layout, const float* tables, int32_t num_colors, int32_t ignore_index,
                             uint8_t* mask, uint8_t* overlay, void* stream);
+int hs_upsample2_overlay_fwd(const float* x, int32_t batch, int32_t channels, int32_t Hi, int32_t Wi, int32_t Hm, int32_t Wm, int32_t Ho,
+                             int32_t Wo, const uint8_t* frames, int32_t layout, const float* tables, int32_t num_colors,
+                             int32_t ignore_index, uint8_t* mask, uint8_t* overlay, void* stream);
 /* Served confidence maps (csrc/hs_confidence.hip): beside the uint8 arg-max mask, the soft-max probability of the winning class of every
  * output pixel.  For the class scores v_0 .. v_{C-1} of a pixel -- exactly what hs_upsample_bilinear_fwd stores for it -- the mask is the
  * arg-max (strictly greater wins: the lowest class on ties) and the confidence is softmax(v)[argmax] = 1 / sum_c exp(v_c - v_max), taken in
