@@ -63,7 +63,15 @@ DW3_CASES = [dict(c=6, b=1, grid=(2, 3), patch=(6, 7)), dict(c=3, b=2, grid=(3, 
 K1_CASES = [dict(cin=5, cout=3, grid=(1, 2), patch=(4, 12)), dict(cin=6, cout=20, grid=(2, 2), patch=(3, 7)),
             dict(cin=17, cout=33, grid=(2, 1), patch=(16, 20)), dict(cin=94, cout=32, grid=(2, 2), patch=(4, 4)),
             dict(cin=82, cout=64, grid=(4, 6), patch=(1, 1))]
-BN_SHAPES = [(3, 16, 1, 1), (1, 3, 7, 5), (2, 5, 129, 33), (1, 3, 300, 211)]
+# hs_bn_act_train_fwd / _bwd (hs_train_aux.hip) have no query; their conditions, quoted:
+#     const bool small = (long)batch * pixels <= BN_SMALL_MAX;              // one launch: a workgroup per channel     (BN_SMALL_MAX = 16 * 1024)
+#     bn_pairs_ok(a): (a.HW & 1) == 0 && a.HW >= 256   [and 4-byte aligned tensors]                                    (the two-launch kernels)
+# Planes of 256 (two image boundaries in every 512-element step of a lane in pair mode), 258 (one or two; bn_slice2 cuts mid-image) and
+# 254 (even but below 256: single elements, the control): with 5 / 5 / 3 images they stay below BN_SMALL_MAX and take the one-launch
+# kernels (images crossed by bn_small_index); BN_WALK_SHAPES are the same planes past it, where a slice is longer than the workgroup's
+# 256 pairs and lanes do step (tests/test_hip_bf16_kernels.py test_bn_shapes_meet_the_quoted_conditions).
+BN_WALK_SHAPES = [(65, 2, 16, 16), (130, 2, 6, 43), (67, 2, 2, 127)]
+BN_SHAPES = [(3, 16, 1, 1), (1, 3, 7, 5), (2, 5, 129, 33), (1, 3, 300, 211), (5, 3, 16, 16), (5, 2, 6, 43), (3, 2, 2, 127)] + BN_WALK_SHAPES
 DW_BN_GEOM = (2, 6, 10, 10, 7, 8)
 CONV_BN_CASES = [(13, 5, (12, 12), 8), (24, 8, (2, 3), 8)]
 STAGE_CASES = [dict(b=2, cs=5, cp=3, hw=(10, 14), up=False, coords=True), dict(b=2, cs=6, cp=0, hw=(9, 8), up=False, coords=True),

@@ -13,7 +13,20 @@ summation, fused or unfused products) of ``mag64``, the same statement on absolu
 an ulp, at most 2^-11 |ref64| for normal results and 2^-24 (half the smallest subnormal) below.  fp32 outputs drop the first two terms.
 ``extra64`` is an ABSOLUTE allowance the caller derives the same way for errors that enter through an operand (the error bound of a
 previous kernel's output pushed through this one on absolute values, or the terms whose ReLU6 unit is undecided within that bound) --
-never a measured constant."""
+never a measured constant.
+
+The 16-bit format is a parameter (``fmt``, a ``Format``; default BINARY16, so every call without it means what it always meant).  With
+BFLOAT16 the same argument gives
+
+    |got - ref64| <= 2^-8 |ref64| + 2^-126 + (terms + 2) 2^-23 mag64
+
+bf16 keeps 8 significant bits: half an ulp is at most 2^-8 |ref64|.  It shares fp32's exponent range, so its absolute term has to cover
+the low end of the fp32 ARITHMETIC as well as of the store: an fp32 result below the smallest normal 2^-126 is either flushed to zero
+(error < 2^-126, and the zero is stored exactly) or kept as an fp32 subnormal (error 2^-150) and rounded to a bf16 subnormal (half of
+2^-133: 2^-134); 2^-126, one smallest fp32 normal, covers both.  Round-to-nearest-even goes to infinity from the midpoint between the
+largest bf16, 2^128 (1 - 2^-8), and 2^128: 2^128 (1 - 2^-9)."""
+import collections
+
 import torch
 import torch.nn.functional as F
 
@@ -22,6 +35,12 @@ SUB16 = 2.0 ** -24        # half the smallest binary16 subnormal
 U32 = 2.0 ** -23          # one fp32 ulp, relative: (terms + 2) U32 >= gamma_terms of an fp32 sum of products
 F16_MAX = 65504.0
 F16_INF_FROM = 65520.0    # round-to-nearest-even gives inf from here on
+
+# A 16-bit storage format as the bound sees it: ``u`` the relative half-ulp, ``sub`` the absolute term, ``inf_from`` the magnitude from
+# which round-to-nearest-even stores an infinity (derivations: the module docstring).
+Format = collections.namedtuple('Format', 'name dtype u sub inf_from')
+BINARY16 = Format('fp16', torch.float16, U16, SUB16, F16_INF_FROM)
+BFLOAT16 = Format('bf16', torch.bfloat16, 2.0 ** -8, 2.0 ** -126, 2.0 ** 128 * (1 - 2.0 ** -9))
 
 
 def f64(t):
@@ -33,16 +52,17 @@ def sum_bound(terms, mag64):
     return (float(terms) + 2.0) * U32 * mag64
 
 
-def f16_bound(ref64, terms, mag64, half=True):
+def f16_bound(ref64, terms, mag64, half=True, fmt=BINARY16):
     e = sum_bound(terms, mag64)
-    return e + U16 * ref64.abs() + SUB16 if half else e
+    return e + fmt.u * ref64.abs() + fmt.sub if half else e
 
 
-def assert_within_f16(got, ref64, terms, mag64, extra64=None, half=True, what=''):
+def assert_within_f16(got, ref64, terms, mag64, extra64=None, half=True, what='', fmt=BINARY16):
     """``got`` (any float type, any device) against the float64 ``ref64`` under the bound of this module's docstring.  NaN positions
     must match.  Where the bound reaches past the binary16 range (|ref64| + bound >= 65520) ``got`` may be the infinity of ref64's sign;
     where |ref64| - bound >= 65520 it must be; a finite ``got`` is always held to the bound itself (65504 for 65510 passes, as .half()
-    gives it).  ``half=False``: an fp32 output (no binary16 terms, no overflow rule)."""
+    gives it).  ``half=False``: an fp32 output (no binary16 terms, no overflow rule).  ``fmt``: the 16-bit format (its ``u``, ``sub`` and
+    ``inf_from`` in place of binary16's).  Returns (worst err / bound, its index) of a tensor that passes, for reports."""
     got = f64(got)
     ref64 = ref64.detach().double()
     assert got.shape == ref64.shape, (what, tuple(got.shape), tuple(ref64.shape))
@@ -57,26 +77,33 @@ def assert_within_f16(got, ref64, terms, mag64, extra64=None, half=True, what=''
     live = ~(nan | rinf)
     r = torch.where(live, ref64, torch.zeros_like(ref64))
     g = torch.where(live, got, torch.zeros_like(got))
-    bound = f16_bound(r, terms, full(mag64), half)
+    bound = f16_bound(r, terms, full(mag64), half, fmt)
     if extra64 is not None:
         bound = bound + full(extra64)
     ginf = g.isinf()
     if half:
-        may = (r.abs() + bound >= F16_INF_FROM) & (torch.sign(g) == torch.sign(r))
-        must = r.abs() - bound >= F16_INF_FROM
-        assert bool((ginf <= may).all()), f'{what}: {int((ginf & ~may).sum())} infinities where the reference is finite in binary16'
-        assert bool((must <= ginf).all()), f'{what}: {int((must & ~ginf).sum())} finite values where the reference overflows binary16'
+        may = (r.abs() + bound >= fmt.inf_from) & (torch.sign(g) == torch.sign(r))
+        must = r.abs() - bound >= fmt.inf_from
+        assert bool((ginf <= may).all()), f'{what}: {int((ginf & ~may).sum())} infinities where the reference is finite in {fmt.name}'
+        assert bool((must <= ginf).all()), f'{what}: {int((must & ~ginf).sum())} finite values where the reference overflows {fmt.name}'
     else:
         assert not bool(ginf.any()), f'{what}: infinite fp32 output'
     err = torch.where(ginf, torch.zeros_like(g), (g - r).abs())
     bad = err > bound
+    ratio = torch.where(err > 0, err / bound.clamp(min=1e-300), torch.zeros_like(err))
+    worst = int(torch.argmax(ratio)) if ratio.numel() else 0
     if bool(bad.any()):
-        ratio = torch.where(bad, err / bound.clamp(min=1e-300), torch.zeros_like(err))
-        worst = int(torch.argmax(ratio))
         idx = [tuple(int(v) for v in i) for i in torch.nonzero(bad)[:8]]
-        raise AssertionError(f'{what}: {int(bad.sum())} of {ref64.numel()} elements outside the fp16 bound; worst |err| {float(err.flatten()[worst]):.3e} '
+        raise AssertionError(f'{what}: {int(bad.sum())} of {ref64.numel()} elements outside the {fmt.name} bound; worst |err| {float(err.flatten()[worst]):.3e} '
                              f'vs bound {float(bound.flatten()[worst]):.3e} (ref {float(r.flatten()[worst]):.6g}, got {float(g.flatten()[worst]):.6g}); '
                              f'first indices {idx}')
+    if not ratio.numel():
+        return 0.0, ()
+    index = []
+    for size in reversed(ratio.shape):
+        worst, at = divmod(worst, size)
+        index.insert(0, at)
+    return float(ratio.max()), tuple(index)
 
 
 # ------------------------------------------------------------------------------------------------------------ tile re-layouts
@@ -272,13 +299,46 @@ def bootstrapped_ce(logits, target, ignore_index, k, thresh):
     return bootstrapped_mean(pixel_ce(logits, target, ignore_index), k, thresh)
 
 
+def bootstrap_weight_slack(per_pixel, per_err, k, thresh, live=None):
+    """How far a pixel's weight in its image's bootstrapped mean may differ from the float64 one because the selection is decided on
+    the kernel's FP32 losses -- the loss's counterpart of ReLU6's undecided unit.  ``per_err``: the absolute bound of each fp32 loss.
+    Set A: the pixels whose float64 loss lies within that bound of the selection's boundary.
+      * threshold branch (the (k+1)-th largest loss is above ``thresh``: the mean of the losses above it): A = |loss - thresh| <= err;
+        the count c of selected pixels lies in [lo, hi] = [c - |A selected|, c + |A not selected|]: a pixel of A may weigh 0 or up to
+        1 / lo, any other selected pixel 1 / c' with c' in [lo, hi].
+      * top-k branch (the mean of the k largest): the count is k; the boundary is [the (k+1)-th largest, the k-th largest] (its own error:
+        the image's largest err); a pixel of A may weigh anything in [0, 1 / k] -- the kernels share the weight left at the boundary
+        among the pixels that TIE there, and losses below fp32's resolution all tie at 0 with the ignored pixels (log1p(x) = 0 in fp32 for
+        x < 2^-24: the confident pixels of a sharp image).  The window is as wide as the fp32 loss bound, not as those zeros: a pixel's
+        own ``err`` plus the boundary pixel's (unknown which pixel: the image's largest), so live pixels with small but non-zero losses
+        within that bound of the boundary are undecided too.
+    ``live`` (bool, per pixel): pixels that are not ignored; an ignored pixel gets no slack -- its gradient is exactly 0 whatever its weight.
+    binary16 hides the difference under its 2^-24 absolute term (such a pixel's gradient is ~1e-13); bf16, with fp32's exponent range, does
+    not.  The branch itself must be decided by the data (raises otherwise).  Returns the slack per pixel, in the shape of ``per_pixel``."""
+    out = torch.zeros(per_pixel.shape, dtype=per_pixel.dtype)
+    for v, err, dev in zip(per_pixel.flatten(1), per_err.flatten(1), out.view(out.shape[0], -1)):
+        order = v.sort(descending=True)
+        ranked = order.values
+        assert float((ranked[k] - thresh).abs()) > float(err[order.indices[k]]), 'the data leave the selection branch undecided'
+        if ranked[k] > thresh:
+            sel, amb = v > thresh, (v - thresh).abs() <= err
+            c = int(sel.sum())
+            lo, hi = c - int((amb & sel).sum()), c + int((amb & ~sel).sum())
+            assert lo > 0
+            dev.copy_(torch.where(amb, torch.full_like(v, 1.0 / lo), sel * max(1.0 / lo - 1.0 / c, 1.0 / c - 1.0 / hi)))
+        else:
+            e = err + err.max()
+            dev.copy_(((v >= ranked[k] - e) & (v <= ranked[k - 1] + e)).to(v.dtype) / k)
+    return out if live is None else out * live
+
+
 # ------------------------------------------------------------------------------------------------------------ BatchNorm + ReLU6 + a linear layer
 
-def round16(t):
-    return t.half().double()
+def round16(t, fmt=BINARY16):
+    return t.to(fmt.dtype).double()
 
 
-def bn_linear_ref(x, weight, bias, bank, r, linear, terms, eps=1e-5, round_copy=False, half=True):
+def bn_linear_ref(x, weight, bias, bank, r, linear, terms, eps=1e-5, round_copy=False, half=True, fmt=BINARY16):
     """y = linear(relu6(batch_norm(x)), bank) and its adjoint for the upstream ``r``, with the bound's mag64 / extra64 per result.
     ``linear(z, bank)`` is one of the per-patch statements above (linear in each operand); ``terms`` = (forward, input adjoint, bank
     adjoint) products per output.  ``round_copy``: the two-step route stores the normalised copy z as binary16 between its two kernels
@@ -297,15 +357,15 @@ def bn_linear_ref(x, weight, bias, bank, r, linear, terms, eps=1e-5, round_copy=
     z = fwd['y'][0]
     e_z = fwd['E'] * fwd['z_mag']
     if round_copy and half:
-        e_z = e_z * (1 + U16) + 2 * (U16 * z.abs() + SUB16)
-        z = round16(z)
+        e_z = e_z * (1 + fmt.u) + 2 * (fmt.u * z.abs() + fmt.sub)
+        z = round16(z, fmt)
     lin = bilinear_with_grads(linear, z, bank, r)
     za, ba = e_z.clone().requires_grad_(True), bank.abs().clone().requires_grad_(True)
     y_extra = linear(za, ba)
     w_extra = torch.autograd.grad(y_extra, ba, r.abs())[0]
     dz, dz_mag = lin['da']
-    e_dz = sum_bound(t_in, dz_mag) + (2 * (U16 * dz.abs() + SUB16) if half else 0.0)
-    bwd = bn_train_ref(x, weight, bias, round16(dz) if half else dz, eps, True, r_err=e_dz)
+    e_dz = sum_bound(t_in, dz_mag) + (2 * (fmt.u * dz.abs() + fmt.sub) if half else 0.0)
+    bwd = bn_train_ref(x, weight, bias, round16(dz, fmt) if half else dz, eps, True, r_err=e_dz)
     out = dict(y=(lin['y'][0], lin['y'][1], y_extra.detach(), t_fwd), dbank=(lin['db'][0], lin['db'][1], w_extra, t_w))
     for k in ('dx', 'dg', 'db', 'rm', 'rv'):
         out[k] = bwd[k] + (bwd['n'],)
