@@ -638,6 +638,15 @@ class FusedContextHead(nn.Module):
     def _affine(self, i):
         return getattr(self, f'scale{i}'), getattr(self, f'shift{i}')
 
+    @staticmethod
+    def _affine_relu(t, scale, shift):
+        """In place relu(scale * t + shift): hs_affine_act_fwd where it takes the map (16-byte rows: H*W % 4 == 0), stock ops on the few
+        pixels of a map it refuses (3 x 5, 1 x 1 -- maps WeightMapper.forward never hands over; a direct call stays total)."""
+        from .. import functional as HF
+        if (t.shape[2] * t.shape[3]) % 4 == 0:
+            return HF.affine_act_(t, scale, shift, HF.ACT_RELU)
+        return t.mul_(scale.view(1, -1, 1, 1)).add_(shift.view(1, -1, 1, 1)).relu_()
+
     def _split_weights(self, name, weight, scale, max_k=1280):
         """``weight`` (Cout, K) with the BN ``scale`` folded into its rows, prepared for hs_gemm_split_fwd (None when K is outside
         what the kernel covers); rebuilt when the conv weight or the BN scale change in place (functional._key)."""
@@ -686,7 +695,7 @@ class FusedContextHead(nn.Module):
                 feat.append(HF.gemm_split_conv2x2(sw_dn, src, shift=getattr(self, f'shift{1 + i}'), act=HF.ACT_RELU, pool_partial=pool))
             else:
                 t = F.conv2d(src, down[0].weight, stride=2)
-                feat.append(HF.affine_act_(t, *self._affine(1 + i), HF.ACT_RELU))
+                feat.append(self._affine_relu(t, *self._affine(1 + i)))
         t = feat[-1]
         pooled_const = t.shape[-2:] != (1, 1)            # the bottom is replaced by its global average
         for level in range(n - 1, -1, -1):
@@ -709,11 +718,11 @@ class FusedContextHead(nn.Module):
                 if sw_up is not None:
                     y = HF.gemm_split(sw_up, skip.contiguous(), shift=shift, act=HF.ACT_RELU)
                 else:
-                    y = HF.affine_act_(torch.mm(wgt[:, :half], skip.view(half, sh * sw)).view(1, half, sh, sw), scale, shift, HF.ACT_RELU)
+                    y = self._affine_relu(torch.mm(wgt[:, :half], skip.view(half, sh * sw)).view(1, half, sh, sw), scale, shift)
                 pooled_const = False
             else:
                 y = torch.mm(wgt, torch.cat((skip, t), dim=1).view(cin, sh * sw)).view(1, half, sh, sw)
-                y = HF.affine_act_(y, scale, shift, HF.ACT_RELU)
+                y = self._affine_relu(y, scale, shift)
             if level > 0:
                 t = wm.upsample(y)
             else:

@@ -80,9 +80,10 @@ class Chain:
         self.q = q or {}                  # tier 2: name of a sum -> MARGIN * q_cpu replacing (K + 2) u
 
     def inp(self, t):
-        """An fp32 input tensor (or None) as a travelling value: exact."""
-        if t is None:
-            return None
+        """An fp32 input tensor (or None) as a travelling value: exact.  A travelling value (v, e) -- another stage's result -- passes
+        through as it is, so that the ``*_ref`` stages compose (util_block_ref.py)."""
+        if t is None or isinstance(t, tuple):
+            return t
         assert t.dtype == torch.float32
         t = t.to(self.dtype)
         return t, (torch.zeros_like(t) if self.mode == 'bound' else None)
@@ -133,6 +134,14 @@ class Chain:
         lip = LIP_SIGMOID if code == ACT_SIGMOID else LIP_SWISH
         fl = FLOOR if code == ACT_SIGMOID else FLOOR * (z.abs() + e + 1)
         return a, lip * (1 + ACT_ALLOW) * e + ACT_ALLOW * a.abs() + fl
+
+    def mul(self, A, B):
+        """The product of two travelling values (broadcast): e = |a| e_b + |b| e_a + e_a e_b + u |a b| (the last: the product's rounding)."""
+        (a, ea), (b, eb) = A, B
+        p = a * b
+        if ea is None or eb is None:
+            return p, None
+        return p, a.abs() * eb + b.abs() * ea + ea * eb + U32 * p.abs() + SUB
 
     def add(self, V, R):
         if R is None:
@@ -327,6 +336,9 @@ def pointwise_ref(ch, x, w, gate=None, scale=None, shift=None, act=ACT_NONE, res
     """hs_pointwise_conv_fwd on x (B, Cin, P): act(scale * sum_c w[o,c] (gate[b,c] x[b,c,p]) + shift) + residual.  Tier-2 name: 'conv'."""
     w_ = ch.coef(w).flatten(1)
     cin = w_.shape[1]
+    if isinstance(gate, tuple):                      # a travelling gate (B, Cin): the product carries both operands' errors and its own rounding
+        x = ch.mul(ch.inp(x), tuple(None if t is None else t[:, :, None] for t in gate))
+        gate = None
     g = None if gate is None else ch.coef(gate)
     after = ch.defect == 'gate_after_scale' and g is not None
     gx = lambda t: t if (g is None or after) else t * g[:, :, None]      # noqa: E731
